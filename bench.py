@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — GP fits/sec (Gram + LL^T + solve) at N = 16384 fp64 on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, runs W warm-up steps, times K steps and prints the result line (headline, roofline of the dominant
+kernel from the timed steps, self-check of the last timed fit).  `--full` adds every other measurement: the
+predictions, the configs block, the CPU baselines and, for N > 1, the auxiliary replicas / N = 65536 blocks.
+`--dump-outputs DIR` writes what the last timed step computed - the information vector K^-1 y and log|K| a caller
+of the fit receives - as DIR/information.npy and DIR/log_determinant.npy (float64; rank 0's).
 
 A "step" is one `agp_fit_create` on one synthetic 3-D dataset whose inputs are
 already resident in HBM: Gram of the measurement-wrapped features + target
@@ -14,10 +20,10 @@ IndependentNoise(0.1), N = 16384, fp64), the size the metric is quoted on.
 N > 1: `value` is ONE fit of the same problem row-block-sharded over the N GPUs (RCCL inside the library; strong
 scaling); N independent fits ("replicas", weak scaling) are reported in an auxiliary block.
 
-Rank 0 prints ONE JSON line (contract in the task statement) including
+Rank 0 prints ONE JSON line including
   roofline      for the dominant kernel (fp64 MFMA trailing update), from HIP
                 events recorded on the library's stream around every launch
-  cpu_baseline  the oracle (albatross-faithful port: serial Gram + unblocked
+  cpu_baseline  (--full) the oracle (albatross-faithful port: serial Gram + unblocked
                 pivoted LDL^T, 1 thread) timed on a bounded sample
 """
 import argparse
@@ -696,9 +702,14 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--n", "--train-points", dest="n", type=int, default=N_TRAIN,
                     help="training points (default 16384 = BASELINE config 3; 32768 / 65536: sizes where sharding one fit pays)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-predict", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the `configs` block (BASELINE configs 2, 4, 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline: predictions, the `configs` block (BASELINE configs 2, "
+                         "4, 5, ...), the CPU baselines and, for N > 1, the replicas / N = 65536 blocks (off: the timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's information vector and log-determinant as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the `cpu_baseline` block")
+    ap.add_argument("--no-predict", action="store_true", help="--full without the `predict` block")
+    ap.add_argument("--no-configs", action="store_true", help="--full without the `configs` block (BASELINE configs 2, 4, 5)")
     ap.add_argument("--force-sharded", action="store_true", help="N = 1: time the sharded entry point (one rank, no transport)")
     ap.add_argument("--multi-gpu", choices=["sharded", "replicas"], default="sharded",
                     help="N > 1: 'sharded' (default) = `value` is ONE fit row-block-sharded over all ranks (RCCL broadcast + "
@@ -710,7 +721,19 @@ def parse_args(argv=None):
                     help="N > 1: exit 0 when the replicas fallback was measured instead of the sharded fit (default: the labelled "
                          f"line is still printed, but the exit code is {FALLBACK_EXIT} - a dead RCCL path is not a green run)")
     ap.add_argument("--fallback-note", default="", help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
+    return args
+
+
+def dump_outputs(directory, arrays):
+    """DIR/<name>.npy, float64, for comparing the outputs of two builds on the same seeded inputs"""
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def launch_ranks(args, argv):
@@ -757,7 +780,10 @@ def launch_ranks(args, argv):
     # `--n` for an abbreviation of `--nnodes`
     argv = ["--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup), "--train-points", str(args.n),
             "--multi-gpu", args.multi_gpu]
-    for flag, on in (("--no-cpu-baseline", args.no_cpu_baseline), ("--no-predict", args.no_predict), ("--no-configs", args.no_configs),
+    if args.dump_outputs:
+        argv += ["--dump-outputs", args.dump_outputs]
+    for flag, on in (("--full", args.full), ("--no-cpu-baseline", args.no_cpu_baseline), ("--no-predict", args.no_predict),
+                     ("--no-configs", args.no_configs),
                      ("--force-sharded", args.force_sharded), ("--no-fallback", args.no_fallback),
                      ("--allow-fallback", args.allow_fallback)):
         if on:
@@ -882,27 +908,46 @@ def run_rank(args):
     feats = make_feats(x_d.ptr, n)
     sfit = ShardedGaussianProcessFit(ctx, cov, comm) if sharded else None
 
-    def replica_step(want_information=False):
+    # the fit of the latest step stays alive until the next step (or release()) destroys it, so that what the last timed
+    # step computed can be read after the timed loop.  With --warmup >= 1 every timed step is one destroy and one create;
+    # with --warmup 0 the first timed step has no fit to destroy (K steps, K - 1 destroys)
+    held = [None]
+
+    def release():
+        if held[0] is not None:
+            lib.agp_fit_destroy(held[0])
+            held[0] = None
+
+    def replica_step():
+        release()
         h = C.c_void_p()
-        info = np.empty(n) if want_information else None
-        st = lib.agp_fit_create(ctx._h, kh, C.byref(feats), C.c_void_p(y_d.ptr), None, C.byref(h),
-                                None if info is None else C.c_void_p(info.ctypes.data), None)
+        st = lib.agp_fit_create(ctx._h, kh, C.byref(feats), C.c_void_p(y_d.ptr), None, C.byref(h), None, None)
         if st != capi.AGP_OK:
             raise RuntimeError(f"agp_fit_create failed: {lib.agp_status_string(st).decode()} "
                                f"{lib.agp_last_error(ctx._h).decode()}")
-        lib.agp_fit_destroy(h)
-        return info
+        held[0] = h
 
-    def sharded_step(want_information=False):
-        res = sfit.fit(None, None, features_struct=feats, device_targets=y_d.ptr)
-        return res.information if want_information else None
+    def replica_outputs():
+        """information vector and log-determinant of the fit of the latest replica step"""
+        info, logdet = np.empty(lib.agp_fit_size(held[0])), C.c_double()
+        for st in (lib.agp_fit_download_information(ctx._h, held[0], C.c_void_p(info.ctypes.data)),
+                   lib.agp_fit_log_determinant(held[0], C.byref(logdet))):
+            if st != capi.AGP_OK:
+                raise RuntimeError(f"reading the fit failed: {lib.agp_status_string(st).decode()}")
+        return info, logdet.value
+
+    last_sharded = [None]
+
+    def sharded_step():
+        last_sharded[0] = sfit.fit(None, None, features_struct=feats, device_targets=y_d.ptr)
 
     # ---- self-check (and, for N > 1, the decision whether the sharded path is usable at all) ----
     self_check = None
     if sharded:
         ok, why = True, ""
         try:
-            resid = sampled_residual(x_h, y_h, sharded_step(True))
+            sharded_step()
+            resid = sampled_residual(x_h, y_h, last_sharded[0].information)
             if os.environ.get("BENCH_TEST_SHARDED_FAILURE") == str(rank):  # test hook: this rank's self-check "fails"
                 resid = 1.0
             self_check = {"rows": 64, "max_rel_residual": resid, "ok": bool(resid < 1e-8),
@@ -987,14 +1032,23 @@ def run_rank(args):
             sys.stderr.write(f"bench.py rank {rank}: per-step wall ms {[round(1e3 * v, 2) for v in step_walls]}, loop {1e3 * t_loop:.2f} ms, "
                              f"with closing barrier {1e3 * elapsed:.2f} ms\n")
 
-        if not sharded:  # self-check of the replica path: one more fit of the timed problem, outside the timed region
-            resid = sampled_residual(x_h, y_h, replica_step(True))
+        # what the last timed step computed (outside the timed region)
+        if sharded:
+            outputs = {"information": last_sharded[0].information, "log_determinant": [last_sharded[0].log_determinant]}
+        else:
+            info_last, logdet_last = replica_outputs()
+            release()
+            outputs = {"information": info_last, "log_determinant": [logdet_last]}
+            # self-check of the replica path on the last timed fit
+            resid = sampled_residual(x_h, y_h, info_last)
             self_check = {"rows": 64, "max_rel_residual": resid, "ok": bool(resid < 1e-8),
-                          "what": "max_r |(K a)_r - y_r| / max|y| of one more fit of the timed problem, numpy from the features"}
+                          "what": "max_r |(K a)_r - y_r| / max|y| of the last timed fit, numpy from the features"}
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, outputs)
 
-        # ---- auxiliary (N > 1, sharded): N independent fits, one per GPU ("replicas") ----
+        # ---- auxiliary (N > 1, sharded, --full): N independent fits, one per GPU ("replicas") ----
         aux = None
-        if world > 1 and sharded:
+        if world > 1 and sharded and args.full:
             replica_step()
             barrier()
             tr = time.perf_counter()
@@ -1002,6 +1056,7 @@ def run_rank(args):
                 replica_step()
             barrier()
             tr = max_over_ranks(time.perf_counter() - tr)
+            release()
             aux = {"replicas": {"fits_per_sec": 3 * world / tr, "scaling": "weak",
                                 "note": "one independent fit per GPU (every rank a copy of the problem), no collective"}}
     except Exception as exc:  # noqa: BLE001
@@ -1011,12 +1066,12 @@ def run_rank(args):
         sys.stderr.flush()
         os._exit(3)
 
-    # ---- secondary: predict points/sec at M = 4096 (per GPU) against one resident fit ----
+    # ---- secondary (--full): predict points/sec at M = 4096 (per GPU) against one resident fit ----
     # N = 1: the fit of the timed problem.  N > 1: the test points are the partitioned unit - every rank holds a resident fit
     # (its own) and predicts its own 4096 points, no collective; `*_pts_per_sec` is the whole-job rate (N x 4096 points /
     # max-over-ranks time).  Sharded runs add the distributed marginal prediction straight from the sharded factor.
     predict = None
-    if not args.no_predict and (world > 1 or not sharded):
+    if args.full and not args.no_predict and (world > 1 or not sharded):
         try:
             m = 4096
             xs_h, _ = make_dataset(m, 43 + 1000 * rank)
@@ -1057,12 +1112,12 @@ def run_rank(args):
             sys.stderr.flush()
             os._exit(3)
 
-    # ---- auxiliary (N > 1, sharded), LAST thing that touches the communicator: the same sharded fit at N = 65536, where the
+    # ---- auxiliary (N > 1, sharded, --full), LAST thing that touches the communicator: the same sharded fit at N = 65536, where the
     # 8-rank schedule is COMPUTE-bound (one rank's share 227-250 ms against 1.67 s on one GPU; at N = 16384 it is bound by
     # the owner chain) - the first real scaling curve should show both regimes.  Outside `value`.  A failure here must not
     # cost the headline line: it is recorded, the line goes out, and the ranks leave without running destructors.
     aux_big, aux_broken = None, False
-    if world > 1 and sharded and not single_device and not args.no_configs and n == N_TRAIN:
+    if world > 1 and sharded and not single_device and args.full and not args.no_configs and n == N_TRAIN:
         try:
             nb = 65536
             xb, yb = make_dataset(nb, 45)
@@ -1102,7 +1157,7 @@ def run_rank(args):
                 continue
 
     configs = None
-    if rank == 0 and world == 1 and not sharded and not args.no_configs:
+    if rank == 0 and world == 1 and not sharded and args.full and not args.no_configs:
         x_d.free()
         y_d.free()
         configs = other_configs(ab, ctx)
@@ -1172,7 +1227,7 @@ def run_rank(args):
             out["n65536_sharded"] = aux_big
         if configs is not None:
             out["configs"] = configs
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline()
         # LAST on the line (the driver's record keeps the final 2 kB verbatim): where a step's wall time goes.
         # ms_per_step_loop_only = the same K steps without the closing barrier (every step returns after its streams have
@@ -1181,7 +1236,7 @@ def run_rank(args):
         out["timing"] = {"value": fits / elapsed, "ms_per_step": 1e3 * elapsed / args.steps,
                          "ms_per_step_loop_only": 1e3 * sum(step_walls) / args.steps,
                          "closing_barrier_ms": 1e3 * (elapsed - t_loop),
-                         "min_step_ms": 1e3 * min(step_walls), "max_step_ms": 1e3 * max(step_walls),
+                         "steps_timed": len(step_walls), "min_step_ms": 1e3 * min(step_walls), "max_step_ms": 1e3 * max(step_walls),
                          "max_step_index": int(np.argmax(step_walls)),
                          "wall_minus_stages_ms": out["roofline"]["wall_minus_stages_ms"],
                          "roofline_frac": out["roofline"]["frac"], "avg_launch_ms": out["roofline"]["avg_launch_ms"],

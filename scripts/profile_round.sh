@@ -11,7 +11,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 B="$ROOT/bench.py"
 FAST="--no-cpu-baseline --no-predict --no-configs"
-python3 "$B" > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
+python3 "$B" --full > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o bench -- python3 "$B" --steps 5 --warmup 2 $FAST > "$OUT/bench_under_rocprof.json" 2> "$OUT/stats.err"
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d "$OUT/pmc_fetch" -o bench -- python3 "$B" --steps 2 --warmup 1 $FAST > /dev/null 2> "$OUT/pmc_fetch.err"
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d "$OUT/pmc_write" -o bench -- python3 "$B" --steps 2 --warmup 1 $FAST > /dev/null 2> "$OUT/pmc_write.err"

@@ -152,3 +152,31 @@ def test_bench_json_contract():
     t = j["timing"]
     assert t["hip_runtimes_in_process"] == 1 and t["ms_per_step"] == j["ms_per_step"] and t["max_step_index"] == 0
     assert len(json.dumps({"stages_ms_per_fit": j["stages_ms_per_fit"], "timing": t})) < 1500
+
+
+@pytest.mark.parametrize("path", [[], ["--force-sharded"]], ids=["replica", "sharded"])
+def test_bench_dumps_the_last_timed_fit(tmp_path, path):
+    """--dump-outputs: the information vector and log-determinant of the last timed step as float64 .npy files, against
+    the oracle on the same seeded problem, for the replica path and the sharded entry point; the loop runs --steps timed
+    steps; a plain run carries none of the blocks of --full."""
+    n = 2048
+    out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "0",
+                                   "--n", str(n), "--dump-outputs", str(tmp_path), *path], text=True, cwd=ROOT)
+    j = json.loads([l for l in out.splitlines() if l.startswith("{")][-1])
+    assert j["steps"] == 3 and j["timing"]["steps_timed"] == 3 and 0 <= j["timing"]["max_step_index"] < 3
+    assert j["warmup"] == 0 and j["self_check"]["ok"]
+    assert abs(j["value"] - 1e3 / j["ms_per_step"]) < 1e-6 * j["value"]
+    for key in ("predict", "configs", "cpu_baseline"):
+        assert key not in j, key
+    check_dumped_fit(tmp_path, n)
+
+
+def check_dumped_fit(directory, n):
+    """bench.py's dumped outputs against the oracle's fit of bench.make_dataset(n, 44)"""
+    info = np.load(os.path.join(directory, "information.npy"))
+    logdet = np.load(os.path.join(directory, "log_determinant.npy"))
+    assert info.dtype == np.float64 and info.shape == (n,) and logdet.dtype == np.float64 and logdet.shape == (1,)
+    x, y = synthetic_3d(n, 44)
+    ofit = orc.OracleFit(ab.SquaredExponential(1.0, 1.0) + ab.IndependentNoise(0.1), x, y)
+    assert np.abs(info - ofit.information).max() <= 1e-8 * np.abs(ofit.information).max()
+    assert abs(logdet[0] - ofit.log_determinant) <= 1e-6 * n

@@ -9,6 +9,7 @@ and the replicated factor's predictions; all against the oracle."""
 import os
 import socket
 import sys
+import threading
 
 import numpy as np
 import pytest
@@ -219,7 +220,7 @@ def test_sharded_fit_rccl_one_rank_per_gpu(n, block):
     boxes have one: skipped there, run by whoever has a node)."""
     ngpu = ab._capi.load().agp_device_count()
     if ngpu < 2:
-        pytest.skip("needs at least two GPUs")
+        pytest.skip(f"needs 2 GPUs, found {ngpu}")
     world = min(ngpu, 4)
     import torch.multiprocessing as mp
     mpc = mp.get_context("spawn")
@@ -251,41 +252,47 @@ def _worker(rank, world, port, n, block, out, transport="callbacks", env=None):
             comm = Communicator.ipc(ctx, mailbox_doubles=1 << 16)
         else:
             comm = Communicator.from_torch(ctx, transport=transport)
-        x, y, yvar = problem(n)
-        cov = ab.Matern52(2.0, 1.0) + ab.IndependentNoise(0.1)
-        sharded = ShardedGaussianProcessFit(ctx, cov, comm)
-        res = sharded.fit(x, y, yvar)
-        if transport != "callbacks":
-            assert sharded.stage(2) == (0. if (env or {}).get("AGP_SHARD_HOST_PACING") == "1" else 1.)  # the pacing that ran
-            res2 = sharded.fit(x, 2. * y, yvar)  # the flags' sequence numbers carry on from fit to fit
-            assert np.abs(res2.information - 2. * res.information).max() <= 1e-12 * np.abs(res.information).max()
-            res = sharded.fit(x, y, yvar)
-        fm = sharded.replicate(ab.gp_from_covariance(cov, context=ctx))
-        xs = np.random.default_rng(3).uniform(0., 10., (64, 3))
-        mine = slice(rank * 64 // world, (rank + 1) * 64 // world)  # this rank's share of the test points
-        marg = fm.predict(xs[mine]).marginal()
-        dmean, dvar = sharded.predict_marginal(xs)  # all 64 points, from the sharded factor itself (collective)
-        assert np.abs(dmean[mine] - marg.mean).max() <= 1e-9 * np.abs(marg.mean).max()
-        assert np.abs(dvar[mine] - marg.covariance).max() <= 1e-9 * np.abs(marg.covariance).max() + 1e-10
-        # ... and the joint prediction (every rank its own rows of V, one all-reduce of the 64 x 64 product) against the
-        # replicated factor's
-        jmean, jcov = sharded.predict_joint(xs)
-        rj = fm.predict(xs).joint()
-        assert np.abs(jmean - rj.mean).max() <= 1e-9 * np.abs(rj.mean).max()
-        assert np.abs(jcov - rj.covariance).max() <= 1e-9 * np.abs(rj.covariance).max() + 1e-10
-        assert np.abs(np.diag(jcov) - dvar).max() <= 1e-9 * np.abs(dvar).max() + 1e-10
-        bad = None
-        try:
-            xb = np.random.default_rng(99).uniform(0., 10., (n, 3))
-            xb[n // 2 + 3] = xb[1]
-            ShardedGaussianProcessFit(ctx, ab.SquaredExponential(1., 1.), comm).fit(xb, y)
-        except ab.NotPositiveDefiniteError as e:
-            bad = str(e)
-        out[rank] = (res.information, res.log_determinant, marg.mean, marg.covariance, bad)
+        out[rank] = _rank_checks(ctx, comm, rank, world, n, transport, env)
         comm.close()
         ctx.close()
     finally:
         dist.destroy_process_group()
+
+
+def _rank_checks(ctx, comm, rank, world, n, transport, env):
+    """one rank's sharded fit, predictions and singular fit over `comm`: (information, log-determinant, its share of the
+    marginal mean / variance, the not-positive-definite message)"""
+    x, y, yvar = problem(n)
+    cov = ab.Matern52(2.0, 1.0) + ab.IndependentNoise(0.1)
+    sharded = ShardedGaussianProcessFit(ctx, cov, comm)
+    res = sharded.fit(x, y, yvar)
+    if transport != "callbacks":
+        assert sharded.stage(2) == (0. if (env or {}).get("AGP_SHARD_HOST_PACING") == "1" else 1.)  # the pacing that ran
+        res2 = sharded.fit(x, 2. * y, yvar)  # the flags' sequence numbers carry on from fit to fit
+        assert np.abs(res2.information - 2. * res.information).max() <= 1e-12 * np.abs(res.information).max()
+        res = sharded.fit(x, y, yvar)
+    fm = sharded.replicate(ab.gp_from_covariance(cov, context=ctx))
+    xs = np.random.default_rng(3).uniform(0., 10., (64, 3))
+    mine = slice(rank * 64 // world, (rank + 1) * 64 // world)  # this rank's share of the test points
+    marg = fm.predict(xs[mine]).marginal()
+    dmean, dvar = sharded.predict_marginal(xs)  # all 64 points, from the sharded factor itself (collective)
+    assert np.abs(dmean[mine] - marg.mean).max() <= 1e-9 * np.abs(marg.mean).max()
+    assert np.abs(dvar[mine] - marg.covariance).max() <= 1e-9 * np.abs(marg.covariance).max() + 1e-10
+    # ... and the joint prediction (every rank its own rows of V, one all-reduce of the 64 x 64 product) against the
+    # replicated factor's
+    jmean, jcov = sharded.predict_joint(xs)
+    rj = fm.predict(xs).joint()
+    assert np.abs(jmean - rj.mean).max() <= 1e-9 * np.abs(rj.mean).max()
+    assert np.abs(jcov - rj.covariance).max() <= 1e-9 * np.abs(rj.covariance).max() + 1e-10
+    assert np.abs(np.diag(jcov) - dvar).max() <= 1e-9 * np.abs(dvar).max() + 1e-10
+    bad = None
+    try:
+        xb = np.random.default_rng(99).uniform(0., 10., (n, 3))
+        xb[n // 2 + 3] = xb[1]
+        ShardedGaussianProcessFit(ctx, ab.SquaredExponential(1., 1.), comm).fit(xb, y)
+    except ab.NotPositiveDefiniteError as e:
+        bad = str(e)
+    return res.information, res.log_determinant, marg.mean, marg.covariance, bad
 
 
 def _free_port():
@@ -295,11 +302,12 @@ def _free_port():
 
 
 # (4, 2300, 128): 18 block columns over 4 ranks in snake order - every rank is the root of several broadcasts (roots != 0)
-# (8, 1400, 128) / (8, 1100, 256): the world size of the node (8 processes sharing this box's one GPU; the gloo-callback transport is
-# host-synchronous - (8, 4200, 128), (8, 2100, 256) and (4, 4200, 128) took 285 s of the suite here; those sizes run on the
-# device-asynchronous ipc transport below in 20-27 s each)
-@pytest.mark.parametrize("world,n,block", [(2, 1500, 128), (3, 2100, 256), (2, 2048, 512), (4, 2300, 128), (8, 1400, 128),
-                                           (8, 1100, 256)])
+# (5, 1400, 128): 11 block columns over 5 ranks, the snake turns twice; (5, 900, 256): 4 block columns over 5 ranks, one rank
+# owns nothing.  At most 5 rank processes: with the test process, at most six processes have the GPU open at once, which
+# shared GPU hosts running the suite can require; world = 8, the size of the node, runs as threads of one process below.
+# The gloo-callback transport is host-synchronous - larger sizes run on the device-asynchronous ipc transport further down.
+@pytest.mark.parametrize("world,n,block", [(2, 1500, 128), (3, 2100, 256), (2, 2048, 512), (4, 2300, 128), (5, 1400, 128),
+                                           (5, 900, 256)])
 def test_sharded_fit_two_processes_one_gpu(world, n, block):
     import torch.multiprocessing as mp
     mpc = mp.get_context("spawn")
@@ -315,13 +323,75 @@ def test_sharded_fit_two_processes_one_gpu(world, n, block):
         _check_against_oracle(out, world, n, expect_bad=True)
 
 
+class _ThreadCollectives:
+    """Host-synchronous collectives between ranks that are threads of this process (one context each): every call
+    deposits its array, waits for all ranks and combines the deposits in rank order, so every rank gets the same bits."""
+
+    def __init__(self, world):
+        self.barrier = threading.Barrier(world, timeout=120)
+        self.slots = [None] * world
+
+    def for_rank(self, rank):
+        def exchange(arr):
+            self.slots[rank] = np.array(arr, copy=True)
+            self.barrier.wait()
+            got = list(self.slots)
+            self.barrier.wait()  # (nobody deposits the next call's array before every rank has read this one's)
+            return got
+
+        def broadcast(buf, root):
+            buf[:] = exchange(buf)[root]
+
+        def all_gather(send, recv):
+            recv[:] = np.concatenate(exchange(send))
+
+        def all_reduce(buf, op):
+            got = np.stack(exchange(buf))
+            buf[:] = got.max(axis=0) if op == 1 else got.sum(axis=0)
+        return broadcast, all_gather, all_reduce
+
+
+# (8, 1400, 128): 11 block columns over the node's 8 ranks; (8, 1100, 256): 5 block columns over 8 ranks, three ranks own
+# nothing.  The ranks are threads of this process, each with its own context on the one GPU, and the callback transport
+# carries the collectives: the multi-rank schedule with the real kernels, without 8 processes holding the device.
+@pytest.mark.parametrize("world,n,block", [(8, 1400, 128), (8, 1100, 256)])
+def test_sharded_fit_ranks_as_threads_one_gpu(world, n, block, monkeypatch):
+    monkeypatch.setenv("AGP_SHARD_BLOCK", str(block))  # (read when each context is created)
+    hub = _ThreadCollectives(world)
+    out, errors = {}, []
+
+    def rank_thread(rank):
+        ctx = comm = None
+        try:
+            ctx = ab.Context(0)
+            comm = Communicator.callbacks(world, rank, *hub.for_rank(rank))
+            out[rank] = _rank_checks(ctx, comm, rank, world, n, "callbacks", None)
+        except BaseException as exc:  # noqa: BLE001 - reported below; the peers leave their barriers at once
+            errors.append(f"rank {rank}: {type(exc).__name__}: {exc}")
+            hub.barrier.abort()
+        finally:
+            if comm is not None:
+                comm.close()
+            if ctx is not None:
+                ctx.close()
+    threads = [threading.Thread(target=rank_thread, args=(r,)) for r in range(world)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(300)
+    assert not any(t.is_alive() for t in threads)
+    assert not errors, errors
+    _check_against_oracle(out, world, n, expect_bad=True)
+
+
 # The asynchronous schedule with asynchronous collectives on ONE GPU (csrc/shard_ipc.hip): every broadcast / all-gather /
 # all-reduce is a few kernels on the collectives' queue writing into the peers' hipIpc mailboxes - the host never waits
-# between the steps, exactly as over RCCL.  Device pacing (flags + gate kernels, the default) and host pacing.
+# between the steps, exactly as over RCCL.  Device pacing (flags + gate kernels, the default) and host pacing.  At most
+# 5 rank processes, as above (hipIpc mailboxes need one process per rank).
 @pytest.mark.parametrize("world,n,block,transport,pacing", [
     (2, 1500, 128, "ipc", "device"), (2, 2048, 512, "ipc", "host"), (3, 2100, 256, "ipc_small", "device"),
-    (4, 4200, 128, "ipc", "device"), (4, 2100, 128, "ipc_small", "host"), (8, 4200, 128, "ipc", "device"),
-    (8, 2100, 256, "ipc_small", "device")])
+    (4, 4200, 128, "ipc", "device"), (4, 2100, 128, "ipc_small", "host"), (5, 4200, 128, "ipc", "device"),
+    (5, 2100, 256, "ipc_small", "device")])
 def test_sharded_fit_async_transport_processes_one_gpu(world, n, block, transport, pacing):
     import torch.multiprocessing as mp
     mpc = mp.get_context("spawn")
@@ -512,15 +582,16 @@ def _run_bench(extra_env, *args):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, BENCH_SINGLE_DEVICE="1", **extra_env)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--n", "2048",
-                        *args], env=env, capture_output=True, text=True, timeout=600)
+                        "--full", *args], env=env, capture_output=True, text=True, timeout=600)
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
     return p.returncode, (json.loads(lines[-1]) if lines else None), p.stderr
 
 
-def test_bench_starts_its_own_ranks():
+def test_bench_starts_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` with no launcher: the two ranks are child processes; on this one-GPU box they share GPU 0
-    and the collectives are staged over gloo (BENCH_SINGLE_DEVICE test mode - the transport string says so)."""
-    rc, line, err = _run_bench({})
+    and the collectives are staged over gloo (BENCH_SINGLE_DEVICE test mode - the transport string says so).  The
+    launcher hands --dump-outputs to the ranks: rank 0 writes the last timed sharded fit."""
+    rc, line, err = _run_bench({}, "--dump-outputs", str(tmp_path))
     assert rc == 0 and line is not None, err[-2000:]
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["config"]["n_ranks"] == 2
     assert "callbacks" in line["config"]["transport"] and "not RCCL" in line["config"]["transport"]
@@ -530,6 +601,8 @@ def test_bench_starts_its_own_ranks():
     pr = line["predict"]
     assert pr["m"] == 2 * pr["m_per_gpu"] and pr["scaling"] == "weak" and pr["marginal_pts_per_sec"] > 0
     assert pr["sharded_factor"]["marginal_pts_per_sec"] > 0
+    from test_device_inputs_gpu import check_dumped_fit
+    check_dumped_fit(tmp_path, 2048)
 
 
 def test_bench_falls_back_to_replicas_when_the_sharded_fit_fails_its_check():
