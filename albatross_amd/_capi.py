@@ -41,6 +41,7 @@ MAX_KERNEL_NODES = 32
 MAX_STACK = 8
 MAX_DIM = 8
 MAX_SCALE_COLUMNS = 4
+MAX_GRADIENT_SLOTS = 64
 
 
 class KernelNode(C.Structure):
@@ -51,6 +52,10 @@ class KernelNode(C.Structure):
         ("order", C.c_int32),
         ("params", C.c_double * 4),
     ]
+
+
+class GradientSlot(C.Structure):
+    _fields_ = [("node", C.c_int32), ("param", C.c_int32)]
 
 
 class Features(C.Structure):
@@ -92,6 +97,7 @@ EXPORTS = [
     ("agp_fit_download_factor", C.c_int, [_P, _P, _P, C.c_int64]),
     ("agp_fit_download_information", C.c_int, [_P, _P, _P]),
     ("agp_nll", C.c_int, [_P, _P, C.POINTER(Features), _P, _P, _D]),
+    ("agp_nll_gradient", C.c_int, [_P, _P, C.POINTER(Features), _P, _P, C.c_int, _P, _P, C.c_int64, _D, _P, _P]),
     ("agp_nll_batch", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, _P, _P]),
     ("agp_fit_create_batch", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P, _P]),
     ("agp_solve", C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int]),

@@ -240,6 +240,32 @@ class CovarianceFunction:
     def program_nodes(self):
         return self.program()[0]
 
+    def _param_slots(self, leaves):
+        """append (scaling_function or None, [(param index, name), ...]) per leaf, in the order _emit emits them"""
+        raise NotImplementedError
+
+    def param_slots(self):
+        """The gradient slot table of program() (agp_nll_gradient): one (node, param, name) per parameter of every
+        leaf.  node indexes the postfix program; param indexes the node's params[], or - for a ScalingTerm - the
+        column of the tangent matrix that holds d f / d name at the features.  Returns (slots, tangent_columns),
+        tangent_columns[c] = (scaling_function, name) of column c.  A name shared by several leaves has a slot per
+        leaf: it is one parameter of the reference (map_join / set_param_if_exists_in_any, covariance_function.hpp:
+        235-242), whose derivative is the sum over its slots."""
+        nodes, _ = self.program()
+        leaves = []
+        self._param_slots(leaves)
+        leaf_nodes = [i for i, nd in enumerate(nodes) if nd.op <= capi.OP_SCALING]
+        if len(leaf_nodes) != len(leaves):
+            raise AssertionError("slot table out of step with the program")
+        slots, columns = [], []
+        for node, (fn, params) in zip(leaf_nodes, leaves):
+            for idx, name in params:
+                if fn is not None:
+                    idx = len(columns)
+                    columns.append((fn, name))
+                slots.append((node, idx, name))
+        return slots, columns
+
     def features(self, x, is_measurement=False):
         """Flatten a feature vector for this covariance function: evaluates
         every ScalingTerm's f(x_i) once per point (scaling_function.hpp:79-83)."""
@@ -311,6 +337,9 @@ class _Radial(CovarianceFunction):
         nodes.append(_node(self._op, metric=self.distance_metric_.metric,
                            params=(self._params[self._ls], self._params[self._sg])))
 
+    def _param_slots(self, leaves):
+        leaves.append((None, [(0, self._ls), (1, self._sg)]))
+
 
 class SquaredExponential(_Radial):
     """sigma^2 exp(-(d/l)^2)  (radial.hpp:131-189)."""
@@ -354,6 +383,9 @@ class Constant(CovarianceFunction):
     def _emit(self, nodes, scalers):
         nodes.append(_node(capi.OP_CONSTANT, params=(self._params["sigma_constant"],)))
 
+    def _param_slots(self, leaves):
+        leaves.append((None, [(0, "sigma_constant")]))
+
 
 class Polynomial(CovarianceFunction):
     """Polynomial<order> on 1-D features (polynomials.hpp:63-90)."""
@@ -371,6 +403,9 @@ class Polynomial(CovarianceFunction):
         nodes.append(_node(capi.OP_POLYNOMIAL, order=self.order,
                            params=[self._params[f"sigma_polynomial_{i}"] for i in range(self.order + 1)]))
 
+    def _param_slots(self, leaves):
+        leaves.append((None, [(q, f"sigma_polynomial_{q}") for q in range(self.order + 1)]))
+
 
 class IndependentNoise(CovarianceFunction):
     """sigma^2 iff x == y  (noise.hpp:20-44)."""
@@ -384,6 +419,9 @@ class IndependentNoise(CovarianceFunction):
     def _emit(self, nodes, scalers):
         nodes.append(_node(capi.OP_INDEPENDENT_NOISE, params=(self._params["sigma_independent_noise"],)))
 
+    def _param_slots(self, leaves):
+        leaves.append((None, [(0, "sigma_independent_noise")]))
+
 
 class Nugget(CovarianceFunction):
     """nugget.hpp:32-49 (default_nugget_noise = 1e-8)"""
@@ -396,6 +434,9 @@ class Nugget(CovarianceFunction):
 
     def _emit(self, nodes, scalers):
         nodes.append(_node(capi.OP_NUGGET, params=(self._params["nugget_sigma"],)))
+
+    def _param_slots(self, leaves):
+        leaves.append((None, [(0, "nugget_sigma")]))
 
 
 class ScalingFunction:
@@ -417,6 +458,19 @@ class ScalingFunction:
 
     def __call__(self, coords):
         return self._call_impl(coords)
+
+    def derivative(self, coords, name):
+        """d f / d name at the features: the subclass's `_derivative_impl(coords, name)` if it has one, otherwise a
+        central difference of `_call_impl` with step 1e-6 max(1, |value|)"""
+        if hasattr(self, "_derivative_impl"):
+            return np.asarray(self._derivative_impl(coords, name), dtype=np.float64).reshape(-1)
+        import copy
+        value = self.get_params()[name]
+        h = 1e-6 * max(1.0, abs(value))
+        up, down = copy.deepcopy(self), copy.deepcopy(self)
+        up.set_param(name, value + h)
+        down.set_param(name, value - h)
+        return ((np.asarray(up(coords), dtype=np.float64) - np.asarray(down(coords), dtype=np.float64)) / (2 * h)).reshape(-1)
 
 
 class ScalingTerm(CovarianceFunction):
@@ -443,6 +497,9 @@ class ScalingTerm(CovarianceFunction):
     def _emit(self, nodes, scalers):
         nodes.append(_node(capi.OP_SCALING, column=len(scalers)))
         scalers.append(self.scaling_function_)
+
+    def _param_slots(self, leaves):
+        leaves.append((self.scaling_function_, [(None, name) for name in self.scaling_function_.get_params()]))
 
 
 class _Binary(CovarianceFunction):
@@ -473,6 +530,10 @@ class _Binary(CovarianceFunction):
         self.lhs_._emit(nodes, scalers)
         self.rhs_._emit(nodes, scalers)
         nodes.append(_node(self._op))
+
+    def _param_slots(self, leaves):
+        self.lhs_._param_slots(leaves)
+        self.rhs_._param_slots(leaves)
 
 
 class SumOfCovarianceFunctions(_Binary):
@@ -506,6 +567,9 @@ class MeasurementOnly(CovarianceFunction):
         self.sub_cov_._emit(nodes, scalers)
         nodes.append(_node(capi.OP_MEASUREMENT_ONLY))
 
+    def _param_slots(self, leaves):
+        self.sub_cov_._param_slots(leaves)
+
 
 def measurement_only(cov):
     return MeasurementOnly(cov)
@@ -536,6 +600,9 @@ class OnlyForAlternatives(CovarianceFunction):
         if _ALTERNATIVE_INDEX not in scalers:
             scalers.append(_ALTERNATIVE_INDEX)  # one shared column for every gate of the program
         nodes.append(_node(capi.OP_TYPE_PAIR, column=scalers.index(_ALTERNATIVE_INDEX), params=(self.a_, self.b_)))
+
+    def _param_slots(self, leaves):
+        self.sub_cov_._param_slots(leaves)
 
 
 def only_for_alternatives(cov, a, b=None):

@@ -629,6 +629,14 @@ static int build_and_factor(agp_context *c, const DevProgram *dprog, const DevPr
   return AGP_OK;
 }
 
+namespace agp {
+// build_and_factor as agp_nll calls it, for the gradient (gradient.hip)
+int build_and_factor_nll(agp_context *c, const DevProgram *dprog, const DevProgram *hprog, const FeatView &xm, double *A,
+                         long long lda, double *invd, double *y, const double *yvar) {
+  return build_and_factor(c, dprog, hprog, xm, A, lda, invd, y, yvar);
+}
+}  // namespace agp
+
 int status_from_flags(const agp_context *ctx) {
   if (ctx->h_flags[2]) {  // a consumer of the fused panel kernel gave up waiting for its producer (chol.hip)
     const_cast<agp_context *>(ctx)->last_error = "panel kernel: hand-over of a diagonal block timed out";

@@ -151,6 +151,14 @@ int copy_out(agp_context *ctx, const double *dev, long long count, double *dst, 
 int copy_out_2d(agp_context *ctx, const double *dev, long long ld_dev, long long rows, long long cols, double *dst,
                 long long ld_dst, int location);
 int status_from_flags(const agp_context *ctx);
+namespace agp {
+// Gram + LL^T + forward substitution of y exactly as agp_nll makes them (api.hip: build_and_factor); on return the stream
+// is synchronised and ctx->h_flags / h_scalars hold the status and the log determinant
+int build_and_factor_nll(agp_context *c, const DevProgram *dprog, const DevProgram *hprog, const FeatView &xm, double *A,
+                         long long lda, double *invd, double *y, const double *yvar);
+// C (lower tiles, ldc) = R^T R for a lower-triangular n x n R (gradient.hip)
+void launch_rtr_lower(hipStream_t s, const double *R, long long ldr, long long n, double *C, long long ldc);
+}  // namespace agp
 // x = L^-T z for ONE vector (api.hip): z is overwritten with x; ws: backsolve_ws_elems(n) doubles of scratch
 extern "C" {  // (defined inside api.hip's extern "C" block)
 size_t backsolve_ws_elems(long long n);

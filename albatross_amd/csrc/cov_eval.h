@@ -450,4 +450,188 @@ __device__ __forceinline__ double eval_sop(const SopProgram &P, const Point<DIMP
   return out[0];
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------
+// Tangent (forward-mode) form of eval_pair for agp_nll_gradient (gradient.hip).  Every stack slot carries the value
+// and its derivatives with respect to G parameter SLOTS: slot g is parameter param[g] of the leaf at node[g] (raw
+// parameter values, as the reference's compute_gradient perturbs them, tune/finite_difference.hpp:37-90), or - for an
+// AGP_OP_SCALING leaf - the direction whose tangent of f the caller supplies per point (tx[g], ty[g]).  The composite
+// nodes follow eval_pair: a sum adds the tangents, a product takes the product rule with the reference's short circuit
+// (lhs == 0: the value is lhs, the tangent lhs' rhs where lhs' != 0 and 0 elsewhere), a gate that zeros the value zeros
+// the tangents.  Only the interpreter form exists: the contraction that calls it is small next to the two O(N^3)
+// steps of the gradient.
+// ---------------------------------------------------------------------------------------------------------------
+template <int G>
+struct TangentSlots {
+  int node[G];   // leaf node of slot g (-1: unused slot)
+  int param[G];  // 0..3: params[] of the leaf; AGP_OP_SCALING: the tangent column (its values come in tx / ty)
+};
+
+template <int DIMP, int G>
+__device__ __forceinline__ void eval_pair_tangent(const DevProgram *__restrict__ Pp, const TangentSlots<G> &S,
+                                                  const Point<DIMP> &x, const Point<DIMP> &y, const double (&tx)[G],
+                                                  const double (&ty)[G], bool have_ids, bool both_measurement,
+                                                  double (&dk)[G]) {
+  const DevProgram &P = *Pp;
+  double d_euclid = 0., d_radial = 0., d_angular = 0.;
+  if (P.metric_mask & (1 << AGP_METRIC_EUCLIDEAN)) {
+    if (DIMP == 1) {
+      d_euclid = fabs(x.c[0] - y.c[0]);
+    } else {
+      double s = 0.;
+#pragma unroll
+      for (int d = 0; d < DIMP; ++d) {
+        const double t = x.c[d] - y.c[d];
+        s += t * t;
+      }
+      d_euclid = sqrt(s);
+    }
+  }
+  if (P.metric_mask & (1 << AGP_METRIC_RADIAL)) d_radial = fabs(x.norm - y.norm);
+  if (P.metric_mask & (1 << AGP_METRIC_ANGULAR)) {
+    double dot = 0.;
+#pragma unroll
+    for (int d = 0; d < DIMP; ++d) dot += x.c[d] * y.c[d];
+    const double c = dot / (x.norm * y.norm);
+    const double eps = 1e-16;  // EPSILON, distance_metrics.hpp:18
+    d_angular = (c > 1. - eps) ? 0. : ((c < -1. + eps) ? M_PI : acos_fast(c));
+  }
+  bool equal = false;
+  if (P.uses_equality) {
+    if (have_ids) {
+      equal = (x.id == y.id);
+    } else {
+      equal = true;
+#pragma unroll
+      for (int d = 0; d < DIMP; ++d) equal = equal && (x.c[d] == y.c[d]);
+    }
+  }
+
+  stack_t st = (stack_t)(0.);
+  stack_t tg[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) tg[g] = (stack_t)(0.);
+  int sp = 0;
+  unsigned defined = 0u;
+  for (int t = 0; t < P.n_nodes; ++t) {
+    const agp_kernel_node &nd = P.nodes[t];
+    const int op = nd.op;
+    if (op <= AGP_OP_SCALING) {
+      // the leaf's value and its partial derivatives dp[q] with respect to params[q]
+      double v = 0., dp[4] = {0., 0., 0., 0.};
+      if (op <= AGP_OP_MATERN52) {
+        const double dist = nd.metric == AGP_METRIC_EUCLIDEAN ? d_euclid
+                            : (nd.metric == AGP_METRIC_RADIAL ? d_radial : d_angular);
+        const double l = nd.params[0], sigma = nd.params[1];
+        if (l > 0.) {  // l <= 0: value 0, tangent 0 (radial.hpp:26-28)
+          double shape, dshape_dl;  // v = sigma^2 shape(d / l)
+          if (op == AGP_OP_SQUARED_EXPONENTIAL) {
+            const double q = dist / l, e = exp_neg(q * q);
+            shape = e;
+            dshape_dl = e * 2. * q * q / l;
+          } else if (op == AGP_OP_EXPONENTIAL) {
+            const double q = fabs(dist / l), e = exp_neg(q);
+            shape = e;
+            dshape_dl = e * q / l;
+          } else if (op == AGP_OP_MATERN32) {
+            const double q = sqrt(3.) * dist / l, e = exp_neg(q);
+            shape = (1 + q) * e;
+            dshape_dl = q * q * e / l;
+          } else {
+            const double q = sqrt(5.) * dist / l, e = exp_neg(q);
+            shape = (1 + q + q * q * (1. / 3.)) * e;
+            dshape_dl = q * q * (1 + q) * (1. / 3.) * e / l;
+          }
+          v = sigma * sigma * shape;
+          dp[0] = sigma * sigma * dshape_dl;
+          dp[1] = 2. * sigma * shape;
+        }
+      } else if (op == AGP_OP_CONSTANT) {
+        v = nd.params[0] * nd.params[0];
+        dp[0] = 2. * nd.params[0];
+      } else if (op == AGP_OP_INDEPENDENT_NOISE || op == AGP_OP_NUGGET) {
+        v = equal ? nd.params[0] * nd.params[0] : 0.;
+        dp[0] = equal ? 2. * nd.params[0] : 0.;
+      } else if (op == AGP_OP_POLYNOMIAL) {
+        double xp = 1., yp = 1.;
+        for (int q = 0; q <= nd.order; ++q) {
+          const double s = nd.params[q];
+          v += s * s * xp * yp;
+          dp[q] = 2. * s * xp * yp;
+          xp *= x.c[0];
+          yp *= y.c[0];
+        }
+      }
+      double fx = 0., fy = 0.;
+      if (op == AGP_OP_SCALING) {
+        fx = x.s[0];
+        fy = y.s[0];
+#pragma unroll
+        for (int k = 1; k < AGP_MAX_SCALE_COLUMNS; ++k) {
+          fx = (nd.column == k) ? x.s[k] : fx;
+          fy = (nd.column == k) ? y.s[k] : fy;
+        }
+        v = fx * fy;
+      }
+      stack_set(st, sp, v);
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        double d = 0.;
+        if (S.node[g] == t) {
+          const int q = S.param[g];
+          d = op == AGP_OP_SCALING ? tx[g] * fy + fx * ty[g]
+                                   : (q == 0 ? dp[0] : (q == 1 ? dp[1] : (q == 2 ? dp[2] : dp[3])));
+        }
+        stack_set(tg[g], sp, d);
+      }
+      ++sp;
+      defined |= 1u << (sp - 1);
+    } else if (op == AGP_OP_SUM) {
+      const double r = stack_get(st, sp - 1), l = stack_get(st, sp - 2);
+      const bool dl = (defined >> (sp - 2)) & 1u, dr = (defined >> (sp - 1)) & 1u;
+      stack_set(st, sp - 2, l + r);
+#pragma unroll
+      for (int g = 0; g < G; ++g) stack_set(tg[g], sp - 2, stack_get(tg[g], sp - 2) + stack_get(tg[g], sp - 1));
+      defined = (defined & ~(3u << (sp - 2))) | ((unsigned)(dl || dr) << (sp - 2));
+      --sp;
+    } else if (op == AGP_OP_PRODUCT) {
+      const double r = stack_get(st, sp - 1), l = stack_get(st, sp - 2);
+      const bool dl = (defined >> (sp - 2)) & 1u, dr = (defined >> (sp - 1)) & 1u;
+      stack_set(st, sp - 2, (dl && dr) ? ((l != 0.) ? l * r : l) : (dl ? l : (dr ? r : 0.)));
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const double tr = stack_get(tg[g], sp - 1), tl = stack_get(tg[g], sp - 2);
+        double d;
+        if (dl && dr) d = (l != 0.) ? tl * r + l * tr : ((tl != 0.) ? tl * r : 0.);
+        else d = dl ? tl : (dr ? tr : 0.);
+        stack_set(tg[g], sp - 2, d);
+      }
+      defined = (defined & ~(3u << (sp - 2))) | ((unsigned)(dl || dr) << (sp - 2));
+      --sp;
+    } else if (op == AGP_OP_MEASUREMENT_ONLY) {
+      if (!both_measurement) {
+        stack_set(st, sp - 1, 0.);
+#pragma unroll
+        for (int g = 0; g < G; ++g) stack_set(tg[g], sp - 1, 0.);
+      }
+    } else if (op == AGP_OP_TYPE_PAIR) {
+      double ax = x.s[0], ay = y.s[0];
+#pragma unroll
+      for (int k = 1; k < AGP_MAX_SCALE_COLUMNS; ++k) {
+        ax = (nd.column == k) ? x.s[k] : ax;
+        ay = (nd.column == k) ? y.s[k] : ay;
+      }
+      const double a = nd.params[0], b = nd.params[1];
+      if (!((ax == a && ay == b) || (ax == b && ay == a))) {
+        stack_set(st, sp - 1, 0.);
+#pragma unroll
+        for (int g = 0; g < G; ++g) stack_set(tg[g], sp - 1, 0.);
+        defined &= ~(1u << (sp - 1));
+      }
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < G; ++g) dk[g] = tg[g][0];
+}
+
 }  // namespace agp

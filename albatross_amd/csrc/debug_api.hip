@@ -235,6 +235,35 @@ extern "C" AGP_DEBUG_API int agp_debug_symv_lower(agp_context *ctx, const double
   return AGP_OK;
 }
 
+// C = R^T R (lower tiles; the whole diagonal tiles) for a lower-triangular n x n R, column-major with leading dimension ld:
+// the kernel of agp_nll_gradient's K^-1 (gradient.hip: rtr_lower_kernel).  ms (optional): its device time.
+extern "C" AGP_DEBUG_API int agp_debug_rtr_lower(agp_context *ctx, const double *R, int64_t n, int64_t ld, double *C,
+                                                 double *ms) {
+  if (!ctx || !R || !C || n <= 0 || ld < n) return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const size_t bytes = sizeof(double) * (size_t)ld * (size_t)n;
+  double *dR = nullptr, *dC = nullptr;
+  AGP_HIP_CHECK(ctx, hipMalloc(&dR, bytes));
+  AGP_HIP_CHECK(ctx, hipMalloc(&dC, bytes));
+  AGP_HIP_CHECK(ctx, hipMemcpy(dR, R, bytes, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipMemset(dC, 0, bytes));
+  hipEvent_t e0, e1;
+  AGP_HIP_CHECK(ctx, hipEventCreate(&e0));
+  AGP_HIP_CHECK(ctx, hipEventCreate(&e1));
+  AGP_HIP_CHECK(ctx, hipEventRecord(e0, ctx->stream));
+  launch_rtr_lower(ctx->stream, dR, ld, n, dC, ld);
+  AGP_HIP_CHECK(ctx, hipEventRecord(e1, ctx->stream));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  float t = 0.f;
+  (void)hipEventElapsedTime(&t, e0, e1);
+  if (ms) *ms = t;
+  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  AGP_HIP_CHECK(ctx, hipMemcpy(C, dC, bytes, hipMemcpyDeviceToHost));
+  (void)hipFree(dR); (void)hipFree(dC);
+  return AGP_OK;
+}
+
 // acos_fast (cov_eval.h) on an array: accuracy test against the correctly rounded acos
 __global__ void acos_fast_kernel(const double *t, double *out, long long n) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;

@@ -1130,6 +1130,50 @@ class GaussianProcessRegression:
         return -out.value
 
 
+    def log_likelihood_gradient(self, dataset):
+        """(log_likelihood(dataset), {name: d log_likelihood / d name}) for every name of get_params(), exact to fp64
+        rounding (agp_nll_gradient: one fit, K^-1 and a contraction against the derivative of the covariance program).
+        The reference's tuner takes forward differences instead (compute_gradient, tune/finite_difference.hpp:37-90).
+        As in log_likelihood, the target variance is not added and priors are not included.  ScalingTerm parameters
+        go through the scaling function's d f / d name at the features (ScalingFunction.derivative), mean-function
+        parameters through (d mu / d name)^T alpha with a central difference of the mean function on the host."""
+        import copy
+        if has_linear_combinations(dataset.features):
+            raise NotImplementedError("log_likelihood_gradient: LinearCombination features go through the dense path")
+        ctx = self._ctx()
+        cov = self.covariance_function_
+        fs = cov.features(_values_of(dataset.features))
+        y, _ = self._targets(fs, dataset.targets)
+        slots, columns = cov.param_slots()
+        if len(slots) > capi.MAX_GRADIENT_SLOTS:
+            raise ValueError(f"more than {capi.MAX_GRADIENT_SLOTS} covariance parameter slots")
+        n = fs.n
+        tangents = None
+        if columns:
+            tangents = np.empty((n, len(columns)), order="F")
+            for c, (fn, name) in enumerate(columns):
+                tangents[:, c] = fn.derivative(fs.coords, name)
+        table = (capi.GradientSlot * max(1, len(slots)))(*[capi.GradientSlot(node, p) for node, p, _ in slots])
+        s = fs.as_struct()
+        nll = C.c_double()
+        grad_nll = np.zeros(len(slots))
+        alpha = np.empty(n)
+        ctx._check(ctx._lib.agp_nll_gradient(ctx._h, ctx.kernel(cov), C.byref(s), _ptr(y), None, len(slots), table,
+                                             _ptr(tangents), n, C.byref(nll), _ptr(grad_nll), _ptr(alpha)),
+                   "agp_nll_gradient")
+        grad = {name: 0. for name in self.get_params()}
+        for (_, _, name), g in zip(slots, grad_nll):
+            grad[name] -= g
+        # y = targets - mu: d log p / d theta = (d mu / d theta)^T alpha
+        for name, value in self.mean_function_.get_params().items():
+            h = 1e-6 * max(1.0, abs(value))
+            up, down = copy.deepcopy(self.mean_function_), copy.deepcopy(self.mean_function_)
+            up.set_param(name, value + h)
+            down.set_param(name, value - h)
+            dmu = (np.asarray(up(fs.coords), dtype=np.float64) - np.asarray(down(fs.coords), dtype=np.float64)) / (2 * h)
+            grad[name] += float(dmu @ alpha)
+        return -nll.value, grad
+
 class LeaveOneOutGrouper:
     """LeaveOneOutGrouper (indexing/group_by.hpp): every observation is its own group."""
 

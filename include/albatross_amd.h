@@ -260,6 +260,33 @@ AGP_API int agp_fit_download_information(agp_context *ctx, const agp_fit *fit,
 AGP_API int agp_nll(agp_context *ctx, const agp_kernel *k, const agp_features *x,
             const double *y, const double *y_var, double *out);
 
+/* Exact gradient of agp_nll with respect to covariance parameters: one fit, K^-1 = R^T R with R = L^-1, and
+ *   dNLL / dtheta = 1/2 sum_ij (K^-1 - alpha alpha^T)_ij dK_ij / dtheta,   alpha = K^-1 y,
+ * with dK / dtheta evaluated pair by pair (never stored).  ~2 N^3 / 3 flop beyond the fit, whatever n_slots is;
+ * exact to fp64 rounding (the reference's tuner takes forward differences of the log-likelihood,
+ * tune/finite_difference.hpp:37-90).  Two calls give bit-identical results.
+ * A slot names one parameter: `node` is the index of a LEAF in the kernel's postfix program and `param`
+ *   - for a radial, constant, noise, nugget or polynomial leaf: the index into that node's params[] (derivative with
+ *     respect to the raw value, e.g. sigma, not sigma^2);
+ *   - for an AGP_OP_SCALING leaf: the column of `tangents` that holds df/dtheta at the n features (column-major,
+ *     leading dimension ldt >= n; the highest such column + 1 columns are read).
+ * y, y_var and tangents live at x->location, as for agp_nll.  nll (1 value), grad_nll (n_slots values) and
+ * information (n values, alpha; may be NULL) are host memory.  Slots that name a non-leaf node or a parameter the
+ * leaf does not have, or more than AGP_MAX_GRADIENT_SLOTS slots: AGP_ERR_INVALID_ARGUMENT.  NaN input and a covariance
+ * that is not positive definite: AGP_ERR_NAN_INPUT / AGP_ERR_NOT_POSITIVE_DEFINITE, as agp_nll.  With profiling on,
+ * agp_last_stage_ms reports 0 gram, 1 factor, 2 alpha and R = L^-1, 6 R^T R, 7 the contraction. */
+#define AGP_MAX_GRADIENT_SLOTS 64
+typedef struct {
+  int32_t node;
+  int32_t param;
+} agp_gradient_slot;
+AGP_API int agp_nll_gradient(agp_context *ctx, const agp_kernel *k, const agp_features *x,
+                     const double *y, const double *y_var,
+                     int n_slots, const agp_gradient_slot *slots,
+                     const double *tangents, int64_t ldt,
+                     double *nll, double *grad_nll,
+                     double *information);
+
 /* Tuner objective batching: agp_nll for `count` parameter vectors of one model on one dataset in lock step
  * (batched Gram slabs + batched LL^T; blockIdx.y = parameter vector) — the evaluations that
  * compute_gradient (include/albatross/src/tune/finite_difference.hpp:20-94) and the ModelTuner objective

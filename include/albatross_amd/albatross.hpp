@@ -25,6 +25,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -364,6 +365,18 @@ inline agp_kernel_node node(int op, int metric = 0, int column = 0, int order = 
 
 using ParameterStore = std::map<std::string, double>;
 
+namespace detail {
+// One row of the gradient slot table next to a covariance program (emit_slots beside emit; agp_nll_gradient): the
+// parameter `name` of the leaf at postfix index slot.node, slot.param its index in the node's params[]; a ScalingTerm
+// parameter carries instead the tangent d f / d name at a feature (slot.param is then set to its tangent column).
+template <typename X>
+struct GradSlot {
+  agp_gradient_slot slot;
+  std::string name;
+  std::function<double(const X &)> tangent;
+};
+}  // namespace detail
+
 // ---------------------------------------------------------------------------
 // distance metrics (distance_metrics.hpp:30-90): tags; the math runs on device
 // ---------------------------------------------------------------------------
@@ -524,6 +537,12 @@ constexpr double default_radial_sigma = 10.;      // radial.hpp:17
     void emit(std::vector<agp_kernel_node> &nodes, int &) const {                                          \
       nodes.push_back(detail::node(OP, DistanceMetricType::metric, 0, 0, length_scale, sigma));            \
     }                                                                                                      \
+    template <typename X>                                                                                  \
+    void emit_slots(std::vector<detail::GradSlot<X>> &out, int &node) const {                              \
+      out.push_back({{node, 0}, LS_NAME, {}});                                                             \
+      out.push_back({{node, 1}, SIGMA_NAME, {}});                                                          \
+      ++node;                                                                                              \
+    }                                                                                                      \
     template <typename X> void fill_scales(const X &, double *, int &) const {}                           \
     double length_scale, sigma;                                                                            \
     DistanceMetricType distance_metric_;                                                                   \
@@ -553,6 +572,8 @@ class SquaredExponential<AngularDistance>;
       value = v;                                                                                          \
     }                                                                                                     \
     void emit(std::vector<agp_kernel_node> &nodes, int &) const { nodes.push_back(detail::node(OP, 0, 0, 0, value)); } \
+    template <typename X>                                                                                 \
+    void emit_slots(std::vector<detail::GradSlot<X>> &out, int &node) const { out.push_back({{node++, 0}, PNAME, {}}); } \
     template <typename X> void fill_scales(const X &, double *, int &) const {}                          \
     double value;                                                                                         \
   };
@@ -576,6 +597,10 @@ class IndependentNoise : public CovarianceFunction<IndependentNoise<Observed>> {
   }
   void emit(std::vector<agp_kernel_node> &nodes, int &) const {
     nodes.push_back(detail::node(AGP_OP_INDEPENDENT_NOISE, 0, 0, 0, sigma_independent_noise));
+  }
+  template <typename X>
+  void emit_slots(std::vector<detail::GradSlot<X>> &out, int &node) const {
+    out.push_back({{node++, 0}, "sigma_independent_noise", {}});
   }
   template <typename X> void fill_scales(const X &, double *, int &) const {}
   double sigma_independent_noise;
@@ -603,6 +628,11 @@ class Polynomial : public CovarianceFunction<Polynomial<order>> {
   void emit(std::vector<agp_kernel_node> &nodes, int &) const {
     nodes.push_back(detail::node(AGP_OP_POLYNOMIAL, 0, 0, order, sigmas[0], sigmas[1], sigmas[2], sigmas[3]));
   }
+  template <typename X>
+  void emit_slots(std::vector<detail::GradSlot<X>> &out, int &node) const {
+    for (int i = 0; i <= order; ++i) out.push_back({{node, i}, "sigma_polynomial_" + std::to_string(i), {}});
+    ++node;
+  }
   template <typename X> void fill_scales(const X &, double *, int &) const {}
   std::array<double, 4> sigmas{};
 };
@@ -622,6 +652,20 @@ class ScalingTerm : public CovarianceFunction<ScalingTerm<ScalingFunction>> {
   void emit(std::vector<agp_kernel_node> &nodes, int &column) const {
     nodes.push_back(detail::node(AGP_OP_SCALING, 0, column, 0));
     ++column;
+  }
+  // the tangent of f: a central difference of _call_impl on copies of the function at value +- h, h = 1e-6 max(1, |value|)
+  template <typename X>
+  void emit_slots(std::vector<detail::GradSlot<X>> &out, int &node) const {
+    for (const auto &kv : scaling_function_.get_params()) {
+      const double h = 1e-6 * std::max(1., std::fabs(kv.second));
+      ScalingFunction up = scaling_function_, down = scaling_function_;
+      up.set_param(kv.first, kv.second + h);
+      down.set_param(kv.first, kv.second - h);
+      out.push_back({{node, -1}, kv.first, [up, down, h](const X &x) {
+                       return (detail::scale_of(up, x) - detail::scale_of(down, x)) / (2. * h);
+                     }});
+    }
+    ++node;
   }
   template <typename X>
   void fill_scales(const X &x, double *out, int &column) const {
@@ -669,6 +713,12 @@ class Binary : public CovarianceFunction<Self> {
     nodes.push_back(detail::node(OP));
   }
   template <typename X>
+  void emit_slots(std::vector<detail::GradSlot<X>> &out, int &node) const {
+    lhs_.template emit_slots<X>(out, node);
+    rhs_.template emit_slots<X>(out, node);
+    ++node;
+  }
+  template <typename X>
   void fill_scales(const X &x, double *out, int &column) const {
     lhs_.template fill_scales<X>(x, out, column);
     rhs_.template fill_scales<X>(x, out, column);
@@ -713,6 +763,11 @@ class MeasurementOnly : public CovarianceFunction<MeasurementOnly<SubCovariance>
     nodes.push_back(detail::node(AGP_OP_MEASUREMENT_ONLY));
   }
   template <typename X>
+  void emit_slots(std::vector<detail::GradSlot<X>> &out, int &node) const {
+    sub_cov_.template emit_slots<X>(out, node);
+    ++node;
+  }
+  template <typename X>
   void fill_scales(const X &x, double *out, int &column) const { sub_cov_.template fill_scales<X>(x, out, column); }
 
  private:
@@ -746,6 +801,11 @@ class OnlyForAlternatives : public CovarianceFunction<OnlyForAlternatives<SubCov
     nd.params[0] = a_;
     nd.params[1] = b_;
     nodes.push_back(nd);
+  }
+  template <typename X>
+  void emit_slots(std::vector<detail::GradSlot<X>> &out, int &node) const {
+    sub_cov_.template emit_slots<X>(out, node);
+    ++node;
   }
   template <typename X>
   void fill_scales(const X &x, double *out, int &column) const {
@@ -1681,6 +1741,66 @@ class GaussianProcessRegression {
                                 nullptr, out.data()),
                   ctx->ctx, "agp_nll_batch");
     for (double &v : out) v = -v;
+    return out;
+  }
+
+  // log_likelihood(dataset) and its exact gradient with respect to every name of get_params() (agp_nll_gradient: one
+  // fit, K^-1 = R^T R, a contraction against the derivative of the covariance program).  The reference's tuner takes
+  // forward differences instead (compute_gradient, tune/finite_difference.hpp:37-90).  ScalingTerm parameters go
+  // through a central difference of the scaling function per feature, mean-function parameters through
+  // (d mu / d name)^T information with a central difference of the mean function.  No target variance, no priors.
+  struct LogLikelihoodGradient {
+    double log_likelihood;
+    ParameterStore gradient;
+  };
+
+  template <typename FeatureType>
+  LogLikelihoodGradient log_likelihood_gradient(const RegressionDataset<FeatureType> &dataset) const {
+    using X = typename detail::unwrap<FeatureType>::type;
+    auto ctx = detail::default_context();
+    detail::KernelHolder k(covariance_function_.program());
+    detail::Flat f = detail::flatten(covariance_function_, dataset.features);
+    const std::size_t n = dataset.features.size();
+    std::vector<detail::GradSlot<X>> rows;
+    int node = 0;
+    covariance_function_.template emit_slots<X>(rows, node);
+    std::vector<agp_gradient_slot> slots;
+    std::vector<double> tangents;
+    int columns = 0;
+    for (auto &r : rows) {
+      if (r.tangent) {
+        r.slot.param = columns++;
+        tangents.resize(n * static_cast<std::size_t>(columns));
+        for (std::size_t i = 0; i < n; ++i)
+          tangents[static_cast<std::size_t>(r.slot.param) * n + i] = r.tangent(detail::unwrap<FeatureType>::get(dataset.features[i]));
+      }
+      slots.push_back(r.slot);
+    }
+    Vector y = dataset.targets.mean;
+    if (!std::is_same<MeanFunc, ZeroMean>::value)
+      for (std::size_t i = 0; i < y.size(); ++i)
+        y[i] -= mean_function_._call_impl(detail::unwrap<FeatureType>::get(dataset.features[i]));
+    double nll = 0.;
+    std::vector<double> grad(slots.size()), alpha(n);
+    detail::check(agp_nll_gradient(ctx->ctx, k.k, &f.view, y.data(), nullptr, static_cast<int>(slots.size()), slots.data(),
+                                   columns > 0 ? tangents.data() : nullptr, static_cast<std::int64_t>(n), &nll, grad.data(),
+                                   alpha.data()),
+                  ctx->ctx, "agp_nll_gradient");
+    LogLikelihoodGradient out{-nll, {}};
+    for (const auto &kv : get_params()) out.gradient[kv.first] = 0.;
+    for (std::size_t s = 0; s < slots.size(); ++s) out.gradient[rows[s].name] -= grad[s];
+    for (const auto &kv : mean_function_.get_params()) {  // y = targets - mu: d log p / d theta = (d mu / d theta)^T alpha
+      const double h = 1e-6 * std::max(1., std::fabs(kv.second));
+      MeanFunc up = mean_function_, down = mean_function_;
+      up.set_param(kv.first, kv.second + h);
+      down.set_param(kv.first, kv.second - h);
+      double g = 0.;
+      for (std::size_t i = 0; i < n; ++i) {
+        const X &x = detail::unwrap<FeatureType>::get(dataset.features[i]);
+        g += (up._call_impl(x) - down._call_impl(x)) / (2. * h) * alpha[i];
+      }
+      out.gradient[kv.first] += g;
+    }
     return out;
   }
 
