@@ -197,6 +197,10 @@ static agp_context::Tuning read_tuning() {
   set_f16x2_kernel((int)number("AGP_F16X2_LDS_PAD", 8192), (int)number("AGP_F16X2_TERMS", 4), (int)number("AGP_F16X2_CHUNK", 32));
   t.mixed_nbo = number("AGP_MIXED_NBO", 512);
   t.fp64_nbo = number("AGP_FP64_NBO", 0);
+  // (the rule agp_fit_create_mixed applies to AGP_MIXED_NBO: outer block edges must fall on 128-column panel edges, and
+  // only a width above 512 changes anything - the panels of an outer block are NB = 128 wide, and a 700-wide block would
+  // end inside its last panel)
+  if (t.fp64_nbo <= 512 || t.fp64_nbo % 128 != 0) t.fp64_nbo = 0;
   set_bf16x3_kernel((int)number("AGP_BF16X3_KERNEL", 2), (int)number("AGP_BF16X3_LDS_PAD", 8192));
   t.sparse_pivoted = flag("AGP_SPARSE_PIVOTED", false);
   t.predict_chunk = number("AGP_PREDICT_CHUNK", 0);
@@ -1086,6 +1090,10 @@ static int fit_create_impl(agp_context *c, const agp_kernel *k, const agp_featur
   // (hand-over: the sentinel-filled output itself up to BACKSUB_DIRECT_BLOCKS blocks, per-block flags in the unused
   // block-inverse buffer beyond)
   const bool coop_direct = coop && (n + NB - 1) / NB <= BACKSUB_DIRECT_BLOCKS;
+  ctx->sched.reset_factor(n);
+  ctx->sched.backsub = coop ? (coop_direct ? ctx->sched.BS_COOP_DIRECT : ctx->sched.BS_COOP_FLAGS)
+                            : (backsolve_width(n) ? ctx->sched.BS_WIDE : ctx->sched.BS_CHAIN);
+  ctx->sched.bs_done = 0;
   if (coop && coop_direct) pre.sentinel(fit->alpha, n);
   else if (coop) pre.fill(fit->winv, 0ull, backsub_done_words(n, 1));
   FactorTimers ftimers;
@@ -1108,6 +1116,7 @@ static int fit_create_impl(agp_context *c, const agp_kernel *k, const agp_featur
   ctx->nbo_override = 0;
   ctx->nbo_wide = 0;
   bs_done = ctx->bs_W ? ctx->bs_done : 0;
+  ctx->sched.bs_done = bs_done;
   ctx->bs_W = nullptr;
   ctx->bs_done = 0;
   if (yvar_d) { (void)hipFree(yvar_d); yvar_d = nullptr; }
@@ -1196,13 +1205,16 @@ static int fit_create_impl(agp_context *c, const agp_kernel *k, const agp_featur
 static int fit_create_retrying(agp_context *c, const agp_kernel *k, const agp_features *x, const double *y, const double *y_var,
                                agp_fit **out, double *information, double *log_det, MixedRequest *mixed) {
   int st = fit_create_impl(c, k, x, y, y_var, out, information, log_det, mixed);
+  if (c && c->h_flags) c->sched.handover_timeout = c->h_flags[2];
   if (st == AGP_ERR_HIP && c && c->h_flags && c->h_flags[2] && (c->tune.step_below > 0 || c->tune.panel_fused || c->tune.merge_above > 0)) {
     if (out && *out) { agp_fit_destroy(*out); *out = nullptr; }
     c->tune.step_below = 0;
     c->tune.panel_fused = false;
     c->tune.backsub_coop = false;  // (the one-launch substitution hands over inside a launch too)
     c->tune.merge_above = 0;       // (... and the gate of a merged bulk update waits for another stream's launch)
+    ++c->sched.demotions;
     st = fit_create_impl(c, k, x, y, y_var, out, information, log_det, mixed);
+    if (c->h_flags) c->sched.handover_timeout = c->h_flags[2];
   }
   return st;
 }

@@ -1105,12 +1105,15 @@ static void panel_phase(agp_context *ctx, hipStream_t s, double *A, long long n,
           }
         }
         hipLaunchKernelGGL(panel_fused_kernel<true>, dim3(grid), dim3(256), 0, s, pa);
+        ++ctx->sched.panels_step;
       } else {
         hipLaunchKernelGGL(panel_fused_kernel<false>, dim3((unsigned)(1 + (pa.below + 63) / 64)), dim3(256), 0, s, pa);
+        ++ctx->sched.panels_fused;
       }
       if (below <= 0) continue;
     } else {
       launch_potrf(s, A, lda, k, nbk, invd, y, ctx->d_flags, ctx->d_scalars);
+      ++ctx->sched.panels_split;
       if (below <= 0) continue;
       TrsmArgs t;
       t.img = invd + (k / NB) * (long long)IMG_DOUBLES;
@@ -1235,6 +1238,8 @@ void factor_lower(agp_context *ctx, double *A, long long n, long long lda, doubl
   hipStream_t sa = ctx->stream, sb = ctx->stream2;
   hipStream_t sb_prev = sb;
   bool have_u2 = false, p32_flip = false;
+  agp_context::ScheduleRecord &rec = ctx->sched;
+  rec.reset_factor(n);
   long long K0 = 0, step_index = 0;
   const long long nbo_fixed = ctx->nbo_override;
   int variant = ctx->update_variant;
@@ -1265,6 +1270,7 @@ void factor_lower(agp_context *ctx, double *A, long long n, long long lda, doubl
   // hands the inversion to the second stream itself once that mark has passed; the last four panels run meanwhile.
   const bool early_inv = step_all && ctx->bs_W && ctx->bs_done == 0 && ctx->ev_inv && ctx->stream2 && ctx->bs_BW > 0 &&
                          n % ctx->bs_BW == 0 && n / ctx->bs_BW >= 2;
+  rec.add_step(kend, step_all ? rec.STEP : 0u);
   panel_phase(ctx, sa, A, n, lda, invd, y, K0, kend, timers, step_all, early_inv ? (n / ctx->bs_BW - 1) * ctx->bs_BW - NB : -1,
               early_inv ? ctx->ev_c : nullptr);
   if (early_inv) {
@@ -1276,6 +1282,7 @@ void factor_lower(agp_context *ctx, double *A, long long n, long long lda, doubl
                                 /*rhs_lower=*/true, done);
       (void)hipEventRecord(ctx->ev_inv, si);
       ctx->bs_done = done;
+      rec.inv_bits |= rec.INV_EARLY;
     }
   }
   while (kend < n) {
@@ -1287,7 +1294,8 @@ void factor_lower(agp_context *ctx, double *A, long long n, long long lda, doubl
     // of them to the second stream and back
     const long long K = kend - K0;
     const bool step = step_ok(n - kend);
-    if (step || (nbo_fixed == 0 && n - kend <= SINGLE_BELOW)) next_end = n;
+    const bool single = !step && nbo_fixed == 0 && n - kend <= SINGLE_BELOW;
+    if (step || single) next_end = n;
     if (ctx->bs_W && ctx->bs_done == 0 && next_end == n && ctx->ev_inv && ctx->stream2) {
       // Last step: everything left of kend is final and the second stream has nothing more to do - it inverts the wide
       // diagonal blocks the backward substitution of the fit will need (all but the last ones), off the chain.
@@ -1302,6 +1310,7 @@ void factor_lower(agp_context *ctx, double *A, long long n, long long lda, doubl
                                   /*rhs_lower=*/true, done);
         (void)hipEventRecord(ctx->ev_inv, si);
         ctx->bs_done = done;
+        rec.inv_bits |= rec.INV_LAST_STEP;
       }
     }
     const double *P = A + K0 * lda + kend;  // panel rows kend.., columns K0..kend
@@ -1360,6 +1369,7 @@ void factor_lower(agp_context *ctx, double *A, long long n, long long lda, doubl
       (void)hipEventRecord(ctx->ev_b, sb);
       have_u2 = true;
       launch_head_gate(sa, cnt, (unsigned long long)head_tiles, ctx->d_flags);
+      rec.add_step(next_end, rec.MERGED | (sb == ctx->stream_masked ? rec.MASKED : 0u));
       panel_phase(ctx, sa, A, n, lda, invd, y, kend, next_end, timers, false);
       K0 = kend;
       kend = next_end;
@@ -1400,6 +1410,8 @@ void factor_lower(agp_context *ctx, double *A, long long n, long long lda, doubl
     if (sb != sb_prev && have_u2) (void)hipStreamWaitEvent(sb, ctx->ev_b, 0);  // U2(j - 1) ran on the other bulk stream
     sb_prev = sb;
     const bool throttle = next_end < n && (n - kend) <= THROTTLE_BELOW;
+    rec.add_step(next_end, (step ? rec.STEP : 0u) | (throttle ? rec.THROTTLED : 0u) | (single ? rec.SINGLE : 0u) |
+                               (next_end < n && sb == ctx->stream_masked ? rec.MASKED : 0u));
     if (throttle) panel_phase(ctx, sa, A, n, lda, invd, y, kend, next_end, timers, step);
     if (next_end < n) {
       if (throttle) {
@@ -1445,6 +1457,7 @@ void factor_lower(agp_context *ctx, double *A, long long n, long long lda, doubl
                                   (bw / NB) * (long long)IMG_DOUBLES, ctx->bs_W + first * bw * bw, bw * bw, bw, bw, /*rhs_lower=*/true, cnt);
         (void)hipEventRecord(ctx->ev_inv, si);
         ctx->bs_done = last;
+        rec.inv_bits |= rec.INV_TAIL;
       }
     }
     K0 = kend;

@@ -155,6 +155,38 @@ struct agp_context {
   static constexpr long long HEADCNT_WORDS = 256;
   unsigned long long *d_headcnt = nullptr;
   bool headcnt_ready = false;
+  // What the last factorisation / fit of this context ran: host-side only, filled at the branch points of factor_lower,
+  // panel_phase (chol.hip) and fit_create_impl (api.hip), read by the tests through agp_debug_schedule (debug_api.hip,
+  // which documents the layout).  Nothing in the library reads it back.
+  struct ScheduleRecord {
+    // outer steps: bits of each step
+    static constexpr unsigned MERGED = 1, STEP = 2, THROTTLED = 4, MASKED = 8, SINGLE = 16;
+    // back substitution of the last fit
+    enum Backsub { BS_NONE = 0, BS_COOP_DIRECT = 1, BS_COOP_FLAGS = 2, BS_WIDE = 3, BS_CHAIN = 4 };
+    // inversions of the wide diagonal blocks under the factorisation (bits)
+    static constexpr unsigned INV_EARLY = 1, INV_LAST_STEP = 2, INV_TAIL = 4;
+    long long n = 0;
+    long long steps = 0, steps_dropped = 0;  // outer steps recorded / not recorded (beyond HEADCNT_WORDS)
+    long long kend[HEADCNT_WORDS] = {};      // last column + 1 of each outer step
+    unsigned bits[HEADCNT_WORDS] = {};
+    long long panels_step = 0, panels_fused = 0, panels_split = 0;  // panel_fused_kernel<true> / <false> / POTRF + TRSM
+    int backsub = BS_NONE;
+    long long bs_done = 0;  // wide inverses computed under the factorisation
+    unsigned inv_bits = 0;
+    int handover_timeout = 0;  // flags[2] after the factorisation (fit: after the whole fit)
+    long long demotions = 0;   // fit_create_retrying fell back to the two-launch schedule (over the life of the context)
+    void reset_factor(long long n_) {
+      n = n_;
+      steps = steps_dropped = 0;
+      panels_step = panels_fused = panels_split = 0;
+      inv_bits = 0;
+      handover_timeout = 0;
+    }
+    void add_step(long long end, unsigned b) {
+      if (steps < HEADCNT_WORDS) { kend[steps] = end; bits[steps] = b; ++steps; }
+      else ++steps_dropped;
+    }
+  } sched;
   // Early inversion of the wide diagonal blocks for the backward substitution of a fit (api.hip: backward_solve_vec_any):
   // set by the caller of factor_lower (bs_W = where the inverses go, bs_BW = their width); factor_lower inverts the
   // blocks that are final when it enters its single-stream tail on the (then idle) second stream, records ev_inv and

@@ -906,6 +906,44 @@ AGP_DEBUG_API int agp_debug_factor(agp_context *ctx, double *A, int64_t n, int64
   if (bad_pivot) *bad_pivot = flags[1] ? flags[1] - 1 : -1;
   (void)hipFree(dA); (void)hipFree(dI);
   if (dy) (void)hipFree(dy);
+  ctx->sched.backsub = agp_context::ScheduleRecord::BS_NONE;
+  ctx->sched.bs_done = 0;
+  ctx->sched.handover_timeout = flags[2];
+  return AGP_OK;
+}
+
+// The schedule record of the context (common.h: agp_context::ScheduleRecord): what its last factorisation - through
+// agp_debug_factor or a fit of the product library on the same context - and its last fit ran.  Layout of `out` (int64):
+//   [0]  n of the last factorisation          [1]  outer steps recorded      [2]  outer steps beyond the record
+//   [3]  panel step launches (panel_fused_kernel<true>)   [4]  fused panel launches (<false>)   [5]  POTRF + TRSM panels
+//   [6]  back substitution of the last fit: 0 none (agp_debug_factor), 1 one launch with the output as hand-over,
+//        2 one launch with per-block flags, 3 512-wide inverted blocks, 4 the 128-row chain
+//   [7]  wide inverses computed under the factorisation (bs_done)
+//   [8]  when: 1 early (all-step factorisation), 2 at the last outer step, 4 under the step tail
+//   [9]  hand-over time-out flag (flags[2]) after the factorisation or fit   [10] demotions of this context
+//   [11] workgroup slots of the step kernel (0: not asked yet)   [12] CUs   [13] 1 if the CU-masked bulk stream exists
+//   [14..18] switches in force: AGP_STEP_BELOW, AGP_PANEL_FUSED, AGP_MERGE_ABOVE, AGP_BACKSUB_COOP, AGP_FP64_NBO
+//   [19] reserved (0)
+//   [20 + 2 i], [21 + 2 i]: last column + 1 and bits of outer step i (1 merged bulk launch, 2 step launches, 4 host-throttled
+//        bulk update, 8 bulk update on the CU-masked stream, 16 single-stream end)
+// At most `cap` words are written; the full record is 20 + 2 * HEADCNT_WORDS.
+constexpr int64_t SCHED_HEADER = 20;
+AGP_DEBUG_API int agp_debug_schedule(agp_context *ctx, int64_t *out, int64_t cap) {
+  if (!ctx || !out || cap < 0) return AGP_ERR_INVALID_ARGUMENT;
+  const agp_context::ScheduleRecord &r = ctx->sched;
+  int64_t w[SCHED_HEADER + 2 * agp_context::HEADCNT_WORDS] = {};
+  w[0] = r.n; w[1] = r.steps; w[2] = r.steps_dropped;
+  w[3] = r.panels_step; w[4] = r.panels_fused; w[5] = r.panels_split;
+  w[6] = r.backsub; w[7] = r.bs_done; w[8] = r.inv_bits; w[9] = r.handover_timeout; w[10] = r.demotions;
+  w[11] = ctx->step_slots; w[12] = ctx->cus; w[13] = ctx->stream_masked ? 1 : 0;
+  w[14] = ctx->tune.step_below; w[15] = ctx->tune.panel_fused ? 1 : 0; w[16] = ctx->tune.merge_above;
+  w[17] = ctx->tune.backsub_coop ? 1 : 0; w[18] = ctx->tune.fp64_nbo;
+  for (long long i = 0; i < r.steps; ++i) {
+    w[SCHED_HEADER + 2 * i] = r.kend[i];
+    w[SCHED_HEADER + 2 * i + 1] = r.bits[i];
+  }
+  const int64_t total = SCHED_HEADER + 2 * agp_context::HEADCNT_WORDS;
+  for (int64_t i = 0; i < cap && i < total; ++i) out[i] = w[i];
   return AGP_OK;
 }
 

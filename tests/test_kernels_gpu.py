@@ -226,6 +226,8 @@ def test_factor_matches_oracle_llt(ctx, dbg, n):
     bad = C.c_int64()
     assert dbg.agp_debug_factor(ctx._h, _p(Ad), n, lda, _p(yd), C.byref(logdet), C.byref(bad)) == 0
     assert bad.value == -1
+    # the padding rows (lda > n) come back bit-identical: no store beyond row n - 1 at a ragged edge
+    assert np.all(np.ascontiguousarray(Ad[n:]).view(np.uint64) == np.array(np.nan).view(np.uint64))
     L = np.tril(Ad[:n])
     Lo, info = orc.llt(A)
     assert info == 0
@@ -255,7 +257,9 @@ def test_panel_step_kernel(make_ctx, dbg, n, monkeypatch):
     """AGP_STEP_BELOW: the chain-bound tail as ONE launch per panel (chol.hip: panel_phase step_mode - the update-ahead panel
     kernel plus trailing-update workgroups in the same launch) against the two-launch tail (AGP_STEP_BELOW=0, and with
     AGP_PANEL_FUSED=0 the round-2 POTRF / TRSM launches) and numpy; sizes with a partial last panel, a partial last
-    64-row tile, and a tail that starts in the middle of the matrix.  The switches are read per context."""
+    64-row tile, and a tail that starts in the middle of the matrix.  The switches are read per context; the schedule
+    record of each context (test_fit_schedules_gpu.schedule) shows that the mode ran the panels it is named after."""
+    from test_fit_schedules_gpu import schedule, step_fits
     rng = np.random.default_rng(n)
     B = rng.standard_normal((n, n))
     A = np.asfortranarray(B @ B.T + n * np.eye(n))
@@ -265,11 +269,26 @@ def test_panel_step_kernel(make_ctx, dbg, n, monkeypatch):
         monkeypatch.setenv("AGP_STEP_BELOW", "0" if mode == "unfused" else mode)
         monkeypatch.setenv("AGP_PANEL_FUSED", "0" if mode == "unfused" else "1")
         ctx = make_ctx()
-        Ad, yd = A.copy(order="F"), y.copy()
+        lda = n + 3
+        Ad = np.full((lda, n), np.nan, order="F")
+        Ad[:n] = A
+        yd = y.copy()
         logdet, bad = C.c_double(), C.c_int64()
-        assert dbg.agp_debug_factor(ctx._h, _p(Ad), n, n, _p(yd), C.byref(logdet), C.byref(bad)) == 0
+        assert dbg.agp_debug_factor(ctx._h, _p(Ad), n, lda, _p(yd), C.byref(logdet), C.byref(bad)) == 0
         assert bad.value == -1
-        out[mode] = (np.tril(Ad), yd, logdet.value)
+        assert np.all(np.ascontiguousarray(Ad[n:]).view(np.uint64) == np.array(np.nan).view(np.uint64))
+        rec = schedule(ctx)
+        assert rec["n"] == n and rec["handover_timeout"] == 0, rec
+        if mode in ("2048", "8192"):
+            # the step tail starts where at most `mode` rows remain; it has step launches when it spans two panels or more
+            tail = n if n <= int(mode) else n - max(e for e, _ in rec["outer"][:-1])
+            if step_fits(rec, min(n, int(mode))) and tail > 128:
+                assert rec["panels_step"] > 0, rec
+        else:
+            assert rec["panels_step"] == 0, rec
+        if mode == "unfused":
+            assert rec["panels_fused"] == 0, rec
+        out[mode] = (np.tril(Ad[:n]), yd, logdet.value)
     L = np.linalg.cholesky(A)
     for mode in out:
         assert np.abs(out[mode][0] - L).max() <= 1e-11 * np.abs(L).max()

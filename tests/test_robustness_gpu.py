@@ -8,6 +8,7 @@ import pytest
 
 import albatross_amd as ab
 from conftest import synthetic_3d
+from test_fit_schedules_gpu import BS_COOP_DIRECT, BS_COOP_FLAGS, MERGED, count_steps, schedule
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -94,6 +95,8 @@ def test_repeated_small_fits_are_bitwise_identical(ctx, n, reps):
             got = (fm.get_fit().information.copy(), fm.get_fit().log_determinant)
             if first is None:
                 first = got
+                rec = schedule(ctx)  # the one-launch back substitution ran (no demotion of the shared context)
+                assert rec["backsub"] in (BS_COOP_DIRECT, BS_COOP_FLAGS) and rec["demotions"] == 0, rec
             else:
                 assert np.array_equal(got[0], first[0]) and got[1] == first[1], (n, i)
         del fm
@@ -115,13 +118,17 @@ def test_merged_bulk_launches_on_several_contexts_at_once(ctx):
     K = ctx.gram(cov, ab.Measurement(x))
     assert np.abs(K @ want - y).max() <= 1e-9 * np.abs(K).sum(axis=1).max() * np.abs(want).max()
     del K
-    results, errors = {}, []
+    rec = schedule(ctx)  # the reference fit ran merged bulk launches
+    assert count_steps(rec, MERGED) > 0 and rec["demotions"] == 0 and rec["handover_timeout"] == 0, rec
+    results, errors, merged = {}, [], {}
 
     def work(tag):
         try:
             c = ab.Context(0)
             for _ in range(3):
                 results[tag] = np.array(ab.gp_from_covariance(cov, context=c).fit(ds).get_fit().information)
+            r = schedule(c)
+            merged[tag] = (count_steps(r, MERGED), r["demotions"])
             c.close()
         except Exception as exc:  # noqa: BLE001
             errors.append(exc)
@@ -131,6 +138,10 @@ def test_merged_bulk_launches_on_several_contexts_at_once(ctx):
     for t in ts:
         t.join()
     assert not errors, errors
+    # (merged launches, demotions) of each thread's last fit: a demoted context is accepted (see above), but at least one
+    # thread must have run the merged schedule for this test to be about it
+    print("merged launches / demotions per thread:", merged)
+    assert any(m > 0 and d == 0 for m, d in merged.values()), merged
     for i in range(3):
         assert np.array_equal(results[i], want)
 
@@ -146,10 +157,15 @@ def test_merged_bulk_launches_match_the_separate_update(make_ctx, monkeypatch):
     c1 = make_ctx()
     a1 = np.array(ab.gp_from_covariance(cov, context=c1).fit(ds).get_fit().information)
     ld1 = ab.gp_from_covariance(cov, context=c1).fit(ds).get_fit().log_determinant
+    r1 = schedule(c1)
     monkeypatch.setenv("AGP_MERGE_ABOVE", "0")
     c0 = make_ctx()
     f0 = ab.gp_from_covariance(cov, context=c0).fit(ds).get_fit()
     a0, ld0 = np.array(f0.information), f0.log_determinant
+    r0 = schedule(c0)
+    # the two contexts ran the two schedules this test compares, neither demoted
+    assert count_steps(r1, MERGED) >= 1 and r1["demotions"] == 0 and r1["handover_timeout"] == 0, r1
+    assert count_steps(r0, MERGED) == 0 and r0["demotions"] == 0 and r0["handover_timeout"] == 0, r0
     assert np.abs(a1 - a0).max() <= 1e-9 * np.abs(a0).max()
     assert abs(ld1 - ld0) <= 1e-9 * abs(ld0)
     K = c1.gram(cov, ab.Measurement(x))
