@@ -130,7 +130,7 @@ struct agp_context_impl : agp_context {
   agp_context_ext ext;
   std::vector<hipEvent_t> gemm_events;
   std::vector<double> gemm_flops;
-  hipEvent_t stage_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  hipEvent_t stage_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   double *partial_ws = nullptr;
   size_t partial_bytes = 0;
   double gemm_ms_sum = 0., gemm_flop_sum = 0.;
@@ -158,6 +158,8 @@ int build_and_factor_nll(agp_context *c, const DevProgram *dprog, const DevProgr
                          long long lda, double *invd, double *y, const double *yvar);
 // C (lower tiles, ldc) = R^T R for a lower-triangular n x n R (gradient.hip)
 void launch_rtr_lower(hipStream_t s, const double *R, long long ldr, long long n, double *C, long long ldc);
+// S (lower tiles, lds) = G^T G for a full n x n G (gradient.hip: agp_loo_nll_gradient's C diag(b) C)
+void launch_gtg_lower(hipStream_t s, const double *G, long long ldg, long long n, double *S, long long lds);
 }  // namespace agp
 // x = L^-T z for ONE vector (api.hip): z is overwritten with x; ws: backsolve_ws_elems(n) doubles of scratch
 extern "C" {  // (defined inside api.hip's extern "C" block)

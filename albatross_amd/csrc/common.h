@@ -72,7 +72,7 @@ struct agp_context {
   double *h_scalars = nullptr;  // pinned mirror
   void *h_status_dev = nullptr;  // h_flags (the whole status block) as the device addresses it, or nullptr
   bool profiling = false;
-  double stage_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double stage_ms[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   // reusable factor workspace (agp_nll re-uses it between tuner steps)
   double *ws_A = nullptr;
   size_t ws_A_bytes = 0;

@@ -246,7 +246,9 @@ extern "C" AGP_DEBUG_API int agp_debug_rtr_lower(agp_context *ctx, const double 
   AGP_HIP_CHECK(ctx, hipMalloc(&dR, bytes));
   AGP_HIP_CHECK(ctx, hipMalloc(&dC, bytes));
   AGP_HIP_CHECK(ctx, hipMemcpy(dR, R, bytes, hipMemcpyHostToDevice));
-  AGP_HIP_CHECK(ctx, hipMemset(dC, 0, bytes));
+  // on the kernel's stream: a hipMemset on the null stream does not order with the context's non-blocking stream and
+  // could still be zeroing tiles the kernel has written
+  AGP_HIP_CHECK(ctx, hipMemsetAsync(dC, 0, bytes, ctx->stream));
   hipEvent_t e0, e1;
   AGP_HIP_CHECK(ctx, hipEventCreate(&e0));
   AGP_HIP_CHECK(ctx, hipEventCreate(&e1));
@@ -261,6 +263,35 @@ extern "C" AGP_DEBUG_API int agp_debug_rtr_lower(agp_context *ctx, const double 
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
   AGP_HIP_CHECK(ctx, hipMemcpy(C, dC, bytes, hipMemcpyDeviceToHost));
   (void)hipFree(dR); (void)hipFree(dC);
+  return AGP_OK;
+}
+
+// S = G^T G (lower tiles; the whole diagonal tiles) for a full n x n G, column-major with leading dimension ld: the
+// kernel of agp_loo_nll_gradient's C diag(b) C (gradient.hip: gtg_lower_kernel).  ms (optional): its device time.
+extern "C" AGP_DEBUG_API int agp_debug_gtg_lower(agp_context *ctx, const double *G, int64_t n, int64_t ld, double *S,
+                                                 double *ms) {
+  if (!ctx || !G || !S || n <= 0 || ld < n) return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const size_t bytes = sizeof(double) * (size_t)ld * (size_t)n;
+  double *dG = nullptr, *dS = nullptr;
+  AGP_HIP_CHECK(ctx, hipMalloc(&dG, bytes));
+  AGP_HIP_CHECK(ctx, hipMalloc(&dS, bytes));
+  AGP_HIP_CHECK(ctx, hipMemcpy(dG, G, bytes, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipMemsetAsync(dS, 0, bytes, ctx->stream));  // on the kernel's stream, as agp_debug_rtr_lower
+  hipEvent_t e0, e1;
+  AGP_HIP_CHECK(ctx, hipEventCreate(&e0));
+  AGP_HIP_CHECK(ctx, hipEventCreate(&e1));
+  AGP_HIP_CHECK(ctx, hipEventRecord(e0, ctx->stream));
+  launch_gtg_lower(ctx->stream, dG, ld, n, dS, ld);
+  AGP_HIP_CHECK(ctx, hipEventRecord(e1, ctx->stream));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  float t = 0.f;
+  (void)hipEventElapsedTime(&t, e0, e1);
+  if (ms) *ms = t;
+  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  AGP_HIP_CHECK(ctx, hipMemcpy(S, dS, bytes, hipMemcpyDeviceToHost));
+  (void)hipFree(dG); (void)hipFree(dS);
   return AGP_OK;
 }
 

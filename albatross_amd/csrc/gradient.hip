@@ -1,5 +1,6 @@
-// gradient.hip — exact gradient of the negative log-likelihood with respect to the covariance parameters
-// (agp_nll_gradient).
+// gradient.hip — exact gradients of the tuner's objectives with respect to the covariance parameters.
+//
+// agp_nll_gradient, the negative log-likelihood:
 //
 //   dNLL / dtheta = 1/2 sum_ij W_ij dK_ij / dtheta,   W = K^-1 - alpha alpha^T,   alpha = K^-1 y
 //
@@ -10,6 +11,18 @@
 // of W's lower triangle against the tangent form of the covariance program (cov_eval.h: eval_pair_tangent) that never
 // stores dK / dtheta.  Cost: a fit plus ~2 N^3 / 3 flop, whatever P is; no float atomics anywhere, so two calls give
 // bit-identical gradients.
+//
+// agp_loo_nll_gradient, the leave-one-out likelihood metric (LeaveOneOutLikelihood, evaluation/model_metrics.hpp:59-72)
+// and its gradient (GPML 5.4.2, eqs. 5.10-5.13, with the truth's variance s added as prediction_metrics.hpp:113-119 does):
+// with C = K^-1 (K including diag(s)), c_i = C_ii, v_i = 1/c_i + s_i, d_i = alpha_i / c_i,
+//
+//   LOO = sum_i 1/2 (log v_i + d_i^2 / v_i + log 2 pi),   dLOO / dtheta = sum_ij W_ij dK_ij / dtheta,
+//   W = C diag(b) C - 1/2 (u alpha^T + alpha u^T),   b_i = (1 - d_i^2/v_i + 2 alpha_i d_i) / (2 v_i c_i^2),
+//   u = C a,   a_i = d_i / (v_i c_i).
+//
+// The same fit, alpha, R and C = R^T R; then loo_terms_kernel (per point: the NLL term, a, sqrt(b)), u by
+// launch_symv_lower, G = diag(b)^1/2 sym(C) over R (loo_form_g_kernel), S = G^T G = C diag(b) C over C (gtg_lower_kernel:
+// N^3 flop, the only O(N^3) work beyond agp_nll_gradient) and the contraction of W = S - sym(u alpha^T).
 #include <cstring>
 #include <vector>
 
@@ -61,9 +74,10 @@ constexpr int CT_THREADS = 256;
 struct ContractArgs {
   TangentSlots<GRAD_GROUP> slots;
   const double *tang[GRAD_GROUP];  // AGP_OP_SCALING slot g: its tangent column (n values), else nullptr
-  const double *C;                 // K^-1, lower triangle
+  const double *C;                 // K^-1 (LOO: S = C diag(b) C), lower triangle
   long long ldc;
   const double *alpha;
+  const double *u;                 // LOO only: u = C a
   double *partial;                 // [tile][GRAD_GROUP]
 };
 
@@ -82,8 +96,9 @@ __device__ __forceinline__ void load_point(const FeatView &X, long long i, bool 
 }
 
 // One workgroup per 64 x 64 lower tile of K^-1; lane = row i (coalesced reads of K^-1), each wave walks 16 columns j,
-// whose point is the same for the whole wave.
-template <int DIMP>
+// whose point is the same for the whole wave.  LOO: the weight of agp_loo_nll_gradient, S_ij - 1/2 (u_i alpha_j +
+// alpha_i u_j), in place of K^-1_ij - alpha_i alpha_j (the NLL instantiation is unchanged).
+template <int DIMP, bool LOO = false>
 __global__ __launch_bounds__(CT_THREADS) void nll_grad_contract_kernel(const DevProgram *__restrict__ P, FeatView X,
                                                                        ContractArgs a) {
   const long long id = blockIdx.x;
@@ -105,6 +120,7 @@ __global__ __launch_bounds__(CT_THREADS) void nll_grad_contract_kernel(const Dev
 #pragma unroll
     for (int g = 0; g < GRAD_GROUP; ++g) tx[g] = a.tang[g] ? a.tang[g][i] : 0.;
     const double ai = a.alpha[i];
+    const double ui = LOO ? a.u[i] : 0.;
     for (int c = wave; c < CT; c += CT_THREADS / 64) {
       const long long j = (long long)bj * CT + c;
       if (j >= n || j > i) continue;
@@ -113,7 +129,9 @@ __global__ __launch_bounds__(CT_THREADS) void nll_grad_contract_kernel(const Dev
       double ty[GRAD_GROUP];
 #pragma unroll
       for (int g = 0; g < GRAD_GROUP; ++g) ty[g] = a.tang[g] ? a.tang[g][j] : 0.;
-      const double w = (i == j ? 1. : 2.) * (a.C[i + j * a.ldc] - ai * a.alpha[j]);
+      double w;
+      if constexpr (LOO) w = (i == j ? 1. : 2.) * (a.C[i + j * a.ldc] - 0.5 * (ui * a.alpha[j] + ai * a.u[j]));
+      else w = (i == j ? 1. : 2.) * (a.C[i + j * a.ldc] - ai * a.alpha[j]);
       double dk[GRAD_GROUP];
       eval_pair_tangent<DIMP, GRAD_GROUP>(P, a.slots, x, y, tx, ty, X.ids != nullptr, X.meas != 0, dk);
 #pragma unroll
@@ -161,14 +179,102 @@ static long long contract_tiles(long long n) {
   return t * (t + 1) / 2;
 }
 
+template <bool LOO>
 static void launch_contract(hipStream_t s, const DevProgram *P, const FeatView &X, const ContractArgs &a, long long tiles) {
   const dim3 grid((unsigned)tiles), block(CT_THREADS);
   const int dim = X.dim;
-  if (dim == 1) hipLaunchKernelGGL(nll_grad_contract_kernel<1>, grid, block, 0, s, P, X, a);
-  else if (dim == 2) hipLaunchKernelGGL(nll_grad_contract_kernel<2>, grid, block, 0, s, P, X, a);
-  else if (dim == 3) hipLaunchKernelGGL(nll_grad_contract_kernel<3>, grid, block, 0, s, P, X, a);
-  else if (dim == 4) hipLaunchKernelGGL(nll_grad_contract_kernel<4>, grid, block, 0, s, P, X, a);
-  else hipLaunchKernelGGL(nll_grad_contract_kernel<8>, grid, block, 0, s, P, X, a);
+  if (dim == 1) hipLaunchKernelGGL((nll_grad_contract_kernel<1, LOO>), grid, block, 0, s, P, X, a);
+  else if (dim == 2) hipLaunchKernelGGL((nll_grad_contract_kernel<2, LOO>), grid, block, 0, s, P, X, a);
+  else if (dim == 3) hipLaunchKernelGGL((nll_grad_contract_kernel<3, LOO>), grid, block, 0, s, P, X, a);
+  else if (dim == 4) hipLaunchKernelGGL((nll_grad_contract_kernel<4, LOO>), grid, block, 0, s, P, X, a);
+  else hipLaunchKernelGGL((nll_grad_contract_kernel<8, LOO>), grid, block, 0, s, P, X, a);
+}
+
+// ---- leave-one-out terms -----------------------------------------------------------------------------------------
+// Per point i, from c_i = cdiag[i * cstride] (C's diagonal in place, stride ldc + 1, or R's squared column norms) and
+// alpha_i: term[i] = log v_i + d_i^2 / v_i (the NLL term without 1/2 and log 2 pi), a[i] = d_i / (v_i c_i) and
+// sqrt_b[i] = sqrt(b_i); b_i > 0 always (c_i v_i >= 1).  a and sqrt_b may be nullptr (value only).
+__global__ __launch_bounds__(256) void loo_terms_kernel(const double *__restrict__ cdiag, long long cstride,
+                                                        const double *__restrict__ alpha, const double *__restrict__ yvar,
+                                                        long long n, double *__restrict__ term, double *__restrict__ a,
+                                                        double *__restrict__ sqrt_b) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double c = cdiag[i * cstride], al = alpha[i];
+  const double v = 1. / c + (yvar ? yvar[i] : 0.);  // the LOO variance plus the truth's (prediction_metrics.hpp:113-119)
+  const double d = al / c;                           // cross_validation_utils.hpp:146-163
+  const double dv = d * d / v;
+  term[i] = log(v) + dv;
+  if (a) a[i] = d / (v * c);
+  if (sqrt_b) sqrt_b[i] = sqrt((1. - dv + 2. * al * d) / (2. * v * c * c));
+}
+
+// out[0] = 1/2 (sum_i term[i] + n log 2 pi)   (single workgroup, fixed order)
+__global__ __launch_bounds__(1024) void loo_sum_kernel(const double *__restrict__ term, long long n, double *__restrict__ out) {
+  __shared__ double red[16];
+  double acc = 0.;
+  for (long long i = threadIdx.x; i < n; i += 1024) acc += term[i];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.;
+    for (int w = 0; w < 16; ++w) s += red[w];
+    out[0] = 0.5 * (s + (double)n * log(2. * M_PI));
+  }
+}
+
+// G (n x n, ldg) = diag(sqrt_b) sym(C), C given by its lower triangle (ldc): G(k, i) = sqrt_b[k] C(max(k, i), min(k, i)).
+// One 32 x 32 tile of G per workgroup, staged through LDS from the lower tile of C it mirrors, so both the reads and the
+// writes are coalesced.  Only C's lower triangle is read, the diagonal tile's included.
+constexpr int GF_T = 32;
+__global__ __launch_bounds__(256) void loo_form_g_kernel(const double *__restrict__ C, long long ldc,
+                                                         const double *__restrict__ sqrt_b, long long n,
+                                                         double *__restrict__ G, long long ldg) {
+  __shared__ double tile[GF_T][GF_T + 1];
+  const long long bi = blockIdx.x, bj = blockIdx.y;  // rows k of tile bi, columns i of tile bj
+  const long long rb = bi > bj ? bi : bj, cb = bi > bj ? bj : bi;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
+  for (int r = ty; r < GF_T; r += 8) {  // tile[r][tx] = C(rb * 32 + r, cb * 32 + tx), lower part only
+    const long long row = rb * GF_T + r, col = cb * GF_T + tx;
+    tile[r][tx] = (row < n && col < n && row >= col) ? C[row + col * ldc] : 0.;
+  }
+  __syncthreads();
+  for (int c = ty; c < GF_T; c += 8) {  // G(k, i), k = bi * 32 + tx (coalesced), i = bj * 32 + c
+    const long long k = bi * GF_T + tx, i = bj * GF_T + c;
+    if (k >= n || i >= n) continue;
+    double v;
+    if (bi > bj) v = tile[tx][c];
+    else if (bi < bj) v = tile[c][tx];
+    else v = tx >= c ? tile[tx][c] : tile[c][tx];
+    G[k + i * ldg] = sqrt_b[k] * v;
+  }
+}
+
+// ---- S = G^T G, lower tiles, G full ------------------------------------------------------------------------------
+// rtr_lower_kernel's product without its k >= i0 restriction: tile (bi, bj), bi >= bj, sums G(k, i) G(k, j) over all
+// k < K through the same gemm_nt_sub_tile body, both operands k-major.  Every tile is K deep, so the launch order does
+// not matter.  Flop: N^3.  The whole diagonal tile is written.
+__global__ __launch_bounds__(GEMM_THREADS, 2) void gtg_lower_kernel(GemmArgs g) {
+  __shared__ double lds[2 * 2 * GK * GLD];
+  const long long id = blockIdx.x;
+  int bi = (int)((sqrt(8. * (double)id + 1.) - 1.) * 0.5);
+  while ((long long)bi * (bi + 1) / 2 > id) --bi;
+  while ((long long)(bi + 1) * (bi + 2) / 2 <= id) ++bi;
+  const int bj = (int)(id - (long long)bi * (bi + 1) / 2);
+  gemm_nt_sub_tile<true, true, true>(g, bi, bj, lds);
+}
+
+void launch_gtg_lower(hipStream_t s, const double *G, long long ldg, long long n, double *S, long long lds_) {
+  if (n <= 0) return;
+  GemmArgs g;
+  g.C = S; g.ldc = lds_; g.A = G; g.lda = ldg; g.B = G; g.ldb = ldg;
+  g.M = n; g.N = n; g.K = n; g.tri = 1;
+  g.ntr = g.ntc = (int)((n + GT - 1) / GT);
+  g.assign = 1;  // S = + G^T G, S not read
+  const long long tiles = (long long)g.ntr * (g.ntr + 1) / 2;
+  hipLaunchKernelGGL(gtg_lower_kernel, dim3((unsigned)tiles), dim3(GEMM_THREADS), 0, s, g);
 }
 
 }  // namespace agp
@@ -195,14 +301,23 @@ static int check_slots(const agp_kernel *k, int n_slots, const agp_gradient_slot
   return AGP_OK;
 }
 
-extern "C" {
+// ---- the steps both gradients share ------------------------------------------------------------------------------
+// Everything agp_nll_gradient and agp_loo_nll_gradient do up to and including the fit.  Workspaces:
+//   ws_A:   [A | invd | z | yvar], as agp_nll
+//   ws_aux: [R | back-substitution scratch | partials | gradient | tangent columns | extra_elems]
+struct GradientCall {
+  long long n = 0, lda = 0, tiles = 0, ldt_d = 0;
+  double *A = nullptr, *invd = nullptr, *z = nullptr, *yvar_d = nullptr;
+  double *R = nullptr, *bs_ws = nullptr, *partial = nullptr, *grad_d = nullptr, *extra = nullptr;
+  const double *tang_d = nullptr;
+  const DevProgram *dprog = nullptr;
+  DeviceFeatures dx;
+  FeatView xm{};
+};
 
-int agp_nll_gradient(agp_context *c, const agp_kernel *k, const agp_features *x, const double *y, const double *y_var,
-                     int n_slots, const agp_gradient_slot *slots, const double *tangents, int64_t ldt, double *nll,
-                     double *grad_nll, double *information) {
-  if (!c || !k || !x || !y || !nll) return AGP_ERR_INVALID_ARGUMENT;
-  if (n_slots < 0 || n_slots > AGP_MAX_GRADIENT_SLOTS || (n_slots > 0 && (!slots || !grad_nll))) return AGP_ERR_INVALID_ARGUMENT;
-  agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
+static int gradient_setup(agp_context_impl *ctx, const agp_kernel *k, const agp_features *x, const double *y,
+                          const double *y_var, int n_slots, const agp_gradient_slot *slots, const double *tangents,
+                          int64_t ldt, size_t extra_elems, GradientCall &g) {
   AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   int st = validate_features(x);
   if (st != AGP_OK) return st;
@@ -211,92 +326,192 @@ int agp_nll_gradient(agp_context *c, const agp_kernel *k, const agp_features *x,
   int ntc = 0;
   if ((st = check_slots(k, n_slots, slots, &ntc)) != AGP_OK) return st;
   if (ntc > 0 && (!tangents || ldt < n)) return AGP_ERR_INVALID_ARGUMENT;
-  const DevProgram *dprog = nullptr;
-  if ((st = device_program(ctx, k, &dprog)) != AGP_OK) return st;
+  if ((st = device_program(ctx, k, &g.dprog)) != AGP_OK) return st;
   hipStream_t s = ctx->stream;
 
-  // ws_A: [A | invd | z | yvar], as agp_nll
-  const long long lda = factor_ld(n);
+  g.n = n;
+  const long long lda = g.lda = factor_ld(n);
   const long long nblk = (n + NB - 1) / NB;
   const size_t a_bytes = sizeof(double) * (size_t)lda * (size_t)n;
   const size_t aux = sizeof(double) * ((size_t)nblk * (36 * MB * MB) + 2 * (size_t)round_up(n, 2));
   if ((st = ensure_ws(ctx, &ctx->ws_A, &ctx->ws_A_bytes, a_bytes + aux)) != AGP_OK) return st;
-  double *A = ctx->ws_A;
-  double *invd = A + (size_t)lda * (size_t)n;
-  double *z = invd + (size_t)nblk * (36 * MB * MB);
-  double *yvar_d = y_var ? z + round_up(n, 2) : nullptr;
-  // ws_aux: [R | back-substitution scratch | partials | gradient | tangent columns]
-  const long long tiles = contract_tiles(n);
+  g.A = ctx->ws_A;
+  g.invd = g.A + (size_t)lda * (size_t)n;
+  g.z = g.invd + (size_t)nblk * (36 * MB * MB);
+  g.yvar_d = y_var ? g.z + round_up(n, 2) : nullptr;
+  g.tiles = contract_tiles(n);
   const size_t r_elems = (size_t)lda * (size_t)n, bs_elems = backsolve_ws_elems(n);
-  const size_t part_elems = (size_t)tiles * GRAD_GROUP, grad_elems = (size_t)round_up(AGP_MAX_GRADIENT_SLOTS, 2);
+  const size_t part_elems = (size_t)g.tiles * GRAD_GROUP, grad_elems = (size_t)round_up(AGP_MAX_GRADIENT_SLOTS, 2);
   const bool tang_copy = ntc > 0 && x->location == AGP_HOST;
   const size_t tang_elems = tang_copy ? (size_t)round_up(n, 2) * (size_t)ntc : 0;
   if ((st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes,
-                      sizeof(double) * (r_elems + bs_elems + part_elems + grad_elems + tang_elems))) != AGP_OK)
+                      sizeof(double) * (r_elems + bs_elems + part_elems + grad_elems + tang_elems + extra_elems))) != AGP_OK)
     return st;
-  double *R = ctx->ws_aux, *bs_ws = R + r_elems, *partial = bs_ws + bs_elems, *grad_d = partial + part_elems;
-  const double *tang_d = tangents;
-  long long ldt_d = ldt;
+  g.R = ctx->ws_aux;
+  g.bs_ws = g.R + r_elems;
+  g.partial = g.bs_ws + bs_elems;
+  g.grad_d = g.partial + part_elems;
+  g.extra = g.grad_d + grad_elems + tang_elems;
+  g.tang_d = tangents;
+  g.ldt_d = ldt;
   if (tang_copy) {
-    double *t = grad_d + grad_elems;
+    double *t = g.grad_d + grad_elems;
     AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(t, sizeof(double) * (size_t)round_up(n, 2), tangents, sizeof(double) * (size_t)ldt,
                                         sizeof(double) * (size_t)n, (size_t)ntc, hipMemcpyHostToDevice, s));
-    tang_d = t;
-    ldt_d = round_up(n, 2);
+    g.tang_d = t;
+    g.ldt_d = round_up(n, 2);
   }
 
-  DeviceFeatures dx;
-  if ((st = to_device(ctx, x, false, &dx)) != AGP_OK) return st;
-  if ((st = vector_to_device(ctx, y, n, x->location, z)) != AGP_OK) return st;
-  if (y_var && (st = vector_to_device(ctx, y_var, n, x->location, yvar_d)) != AGP_OK) return st;
-  FeatView xm = dx.v;
-  xm.meas = 1;
+  if ((st = to_device(ctx, x, false, &g.dx)) != AGP_OK) return st;
+  if ((st = vector_to_device(ctx, y, n, x->location, g.z)) != AGP_OK) return st;
+  if (y_var && (st = vector_to_device(ctx, y_var, n, x->location, g.yvar_d)) != AGP_OK) return st;
+  g.xm = g.dx.v;
+  g.xm.meas = 1;
   // the fit: A = L, z = L^-1 y, flags and log det (api.hip: build_and_factor via agp_nll's path)
-  st = build_and_factor_nll(ctx, dprog, &k->prog, xm, A, lda, invd, z, yvar_d);
+  st = build_and_factor_nll(ctx, g.dprog, &k->prog, g.xm, g.A, lda, g.invd, g.z, g.yvar_d);
   if (st == AGP_OK) st = status_from_flags(ctx);
-  if (st != AGP_OK) return st;
-  const bool prof = ctx->profiling;
-  // y^T K^-1 y = z^T z, then alpha = L^-T z in place
-  launch_dot(s, z, z, n, ctx->d_scalars + 1);
-  backward_solve_vec_any(s, A, n, lda, invd, z, bs_ws);
-  const double *alpha = z;
-  // R = L^-1 (triangular right-hand side), K^-1 = R^T R over L
-  launch_set_identity(s, R, lda, n);
-  forward_solve_mat_lookahead(ctx, A, n, lda, invd, R, n, lda, /*rhs_lower=*/true);
-  if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[3], s));
-  launch_rtr_lower(s, R, lda, n, A, lda);
-  if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[4], s));
-  // the contraction, GRAD_GROUP slots per pass
+  return st;
+}
+
+// alpha = L^-T z in place, then R = L^-1 (triangular right-hand side); stage event 3 at the end
+static int alpha_and_inverse_factor(agp_context_impl *ctx, GradientCall &g) {
+  hipStream_t s = ctx->stream;
+  backward_solve_vec_any(s, g.A, g.n, g.lda, g.invd, g.z, g.bs_ws);
+  launch_set_identity(s, g.R, g.lda, g.n);
+  forward_solve_mat_lookahead(ctx, g.A, g.n, g.lda, g.invd, g.R, g.n, g.lda, /*rhs_lower=*/true);
+  if (ctx->profiling) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[3], s));
+  return AGP_OK;
+}
+
+// the contraction of W's lower triangle (g.A) against dK / dslot, GRAD_GROUP slots per pass, into g.grad_d
+template <bool LOO>
+static void contract_slots(hipStream_t s, const agp_kernel *k, int n_slots, const agp_gradient_slot *slots,
+                           const GradientCall &g, const double *u, double scale) {
   for (int g0 = 0; g0 < n_slots; g0 += GRAD_GROUP) {
     ContractArgs ca;
-    ca.C = A; ca.ldc = lda; ca.alpha = alpha; ca.partial = partial;
+    ca.C = g.A; ca.ldc = g.lda; ca.alpha = g.z; ca.u = u; ca.partial = g.partial;
     const int cnt = n_slots - g0 < GRAD_GROUP ? n_slots - g0 : GRAD_GROUP;
-    for (int g = 0; g < GRAD_GROUP; ++g) {
-      const bool used = g < cnt;
-      const int node = used ? slots[g0 + g].node : -1, param = used ? slots[g0 + g].param : 0;
-      ca.slots.node[g] = node;
-      ca.slots.param[g] = param;
-      ca.tang[g] = (used && k->prog.nodes[node].op == AGP_OP_SCALING) ? tang_d + (size_t)param * (size_t)ldt_d : nullptr;
+    for (int j = 0; j < GRAD_GROUP; ++j) {
+      const bool used = j < cnt;
+      const int node = used ? slots[g0 + j].node : -1, param = used ? slots[g0 + j].param : 0;
+      ca.slots.node[j] = node;
+      ca.slots.param[j] = param;
+      ca.tang[j] = (used && k->prog.nodes[node].op == AGP_OP_SCALING) ? g.tang_d + (size_t)param * (size_t)g.ldt_d : nullptr;
     }
-    launch_contract(s, dprog, xm, ca, tiles);
-    hipLaunchKernelGGL(nll_grad_reduce_kernel, dim3(GRAD_GROUP), dim3(256), 0, s, partial, tiles, cnt, 0.5, grad_d + g0);
+    launch_contract<LOO>(s, g.dprog, g.xm, ca, g.tiles);
+    hipLaunchKernelGGL(nll_grad_reduce_kernel, dim3(GRAD_GROUP), dim3(256), 0, s, g.partial, g.tiles, cnt, scale, g.grad_d + g0);
   }
+}
+
+static float elapsed(hipEvent_t a, hipEvent_t b) {
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, a, b);
+  return ms;
+}
+
+extern "C" {
+
+int agp_nll_gradient(agp_context *c, const agp_kernel *k, const agp_features *x, const double *y, const double *y_var,
+                     int n_slots, const agp_gradient_slot *slots, const double *tangents, int64_t ldt, double *nll,
+                     double *grad_nll, double *information) {
+  if (!c || !k || !x || !y || !nll) return AGP_ERR_INVALID_ARGUMENT;
+  if (n_slots < 0 || n_slots > AGP_MAX_GRADIENT_SLOTS || (n_slots > 0 && (!slots || !grad_nll))) return AGP_ERR_INVALID_ARGUMENT;
+  agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
+  GradientCall g;
+  int st = gradient_setup(ctx, k, x, y, y_var, n_slots, slots, tangents, ldt, 0, g);
+  if (st != AGP_OK) return st;
+  hipStream_t s = ctx->stream;
+  const long long n = g.n;
+  const bool prof = ctx->profiling;
+  // y^T K^-1 y = z^T z, then alpha = L^-T z in place; R = L^-1, K^-1 = R^T R over L
+  launch_dot(s, g.z, g.z, n, ctx->d_scalars + 1);
+  if ((st = alpha_and_inverse_factor(ctx, g)) != AGP_OK) return st;
+  const double *alpha = g.z;
+  launch_rtr_lower(s, g.R, g.lda, n, g.A, g.lda);
+  if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[4], s));
+  contract_slots<false>(s, k, n_slots, slots, g, nullptr, 0.5);
   if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[5], s));
   AGP_HIP_CHECK(ctx, hipGetLastError());
   AGP_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_scalars, ctx->d_scalars, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (n_slots > 0) AGP_HIP_CHECK(ctx, hipMemcpyAsync(grad_nll, grad_d, sizeof(double) * (size_t)n_slots, hipMemcpyDeviceToHost, s));
+  if (n_slots > 0) AGP_HIP_CHECK(ctx, hipMemcpyAsync(grad_nll, g.grad_d, sizeof(double) * (size_t)n_slots, hipMemcpyDeviceToHost, s));
   if (information) AGP_HIP_CHECK(ctx, hipMemcpyAsync(information, alpha, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
   AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
   *nll = 0.5 * (2. * ctx->h_scalars[0] + ctx->h_scalars[1] + (double)n * std::log(2 * M_PI));  // likelihood.hpp:46
   if (prof) {
     // stage 2: alpha and R = L^-1 (from the end of the factorisation), 6: R^T R, 7: contraction
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, ctx->stage_ev[2], ctx->stage_ev[3]);
-    ctx->stage_ms[2] = ms;
-    (void)hipEventElapsedTime(&ms, ctx->stage_ev[3], ctx->stage_ev[4]);
-    ctx->stage_ms[6] = ms;
-    (void)hipEventElapsedTime(&ms, ctx->stage_ev[4], ctx->stage_ev[5]);
-    ctx->stage_ms[7] = ms;
+    ctx->stage_ms[2] = elapsed(ctx->stage_ev[2], ctx->stage_ev[3]);
+    ctx->stage_ms[6] = elapsed(ctx->stage_ev[3], ctx->stage_ev[4]);
+    ctx->stage_ms[7] = elapsed(ctx->stage_ev[4], ctx->stage_ev[5]);
+  }
+  return AGP_OK;
+}
+
+int agp_loo_nll_gradient(agp_context *c, const agp_kernel *k, const agp_features *x, const double *y, const double *y_var,
+                         int n_slots, const agp_gradient_slot *slots, const double *tangents, int64_t ldt, double *loo_nll,
+                         double *grad_loo_nll, double *mean_weights) {
+  if (!c || !k || !x || !y || !loo_nll) return AGP_ERR_INVALID_ARGUMENT;
+  if (n_slots < 0 || n_slots > AGP_MAX_GRADIENT_SLOTS || (n_slots > 0 && (!slots || !grad_loo_nll)))
+    return AGP_ERR_INVALID_ARGUMENT;
+  agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
+  // extra: [term | a | sqrt_b | u | c | symv scratch], n (rounded up) each but the scratch
+  const long long n = x->n, n2 = round_up(n > 0 ? n : 1, 2);
+  const size_t extra = 5 * (size_t)n2 + symv_ws_elems(n > 0 ? n : 1);
+  GradientCall g;
+  int st = gradient_setup(ctx, k, x, y, y_var, n_slots, slots, tangents, ldt, extra, g);
+  if (st != AGP_OK) return st;
+  hipStream_t s = ctx->stream;
+  double *term = g.extra, *a = term + n2, *sqrt_b = a + n2, *u = sqrt_b + n2, *cdiag = u + n2, *symv_ws = cdiag + n2;
+  const bool prof = ctx->profiling;
+  const bool need_c = n_slots > 0 || mean_weights;  // u = C a needs C = R^T R; the value alone needs only diag(C)
+  if ((st = alpha_and_inverse_factor(ctx, g)) != AGP_OK) return st;
+  const double *alpha = g.z;
+  const unsigned eblocks = (unsigned)((n + 255) / 256);
+  if (!need_c) {
+    // c_i = ||R[:, i]||^2, as agp_fit_inverse_diagonal
+    launch_coldot(s, g.R, g.lda, g.R, g.lda, n, n, cdiag, -1.0, nullptr);
+    hipLaunchKernelGGL(loo_terms_kernel, dim3(eblocks), dim3(256), 0, s, cdiag, 1LL, alpha, g.yvar_d, n, term, nullptr, nullptr);
+    hipLaunchKernelGGL(loo_sum_kernel, dim3(1), dim3(1024), 0, s, term, n, ctx->d_scalars + 2);
+    if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[5], s));
+  } else {
+    launch_rtr_lower(s, g.R, g.lda, n, g.A, g.lda);  // C = K^-1 over L
+    if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[4], s));
+    hipLaunchKernelGGL(loo_terms_kernel, dim3(eblocks), dim3(256), 0, s, g.A, g.lda + 1, alpha, g.yvar_d, n, term, a, sqrt_b);
+    hipLaunchKernelGGL(loo_sum_kernel, dim3(1), dim3(1024), 0, s, term, n, ctx->d_scalars + 2);
+    launch_symv_lower(s, g.A, g.lda, n, a, 1., 0., nullptr, u, symv_ws);  // u = C a
+    if (n_slots > 0) {
+      const unsigned gt = (unsigned)((n + GF_T - 1) / GF_T);
+      hipLaunchKernelGGL(loo_form_g_kernel, dim3(gt, gt), dim3(256), 0, s, g.A, g.lda, sqrt_b, n, g.R, g.lda);  // G over R
+    }
+    if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[5], s));
+    if (n_slots > 0) {
+      launch_gtg_lower(s, g.R, g.lda, n, g.A, g.lda);  // S = C diag(b) C over C
+      if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[6], s));
+      contract_slots<true>(s, k, n_slots, slots, g, u, 1.0);
+      if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[7], s));
+    }
+  }
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_scalars, ctx->d_scalars, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (n_slots > 0)
+    AGP_HIP_CHECK(ctx, hipMemcpyAsync(grad_loo_nll, g.grad_d, sizeof(double) * (size_t)n_slots, hipMemcpyDeviceToHost, s));
+  if (mean_weights) AGP_HIP_CHECK(ctx, hipMemcpyAsync(mean_weights, u, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  *loo_nll = ctx->h_scalars[2];
+  if (prof) {
+    // 2: alpha and R = L^-1; value only: 8 the column norms and the LOO terms; otherwise 6 R^T R, 8 the LOO terms, u
+    // and G, 9 G^T G, 7 the contraction
+    ctx->stage_ms[6] = ctx->stage_ms[7] = ctx->stage_ms[8] = ctx->stage_ms[9] = 0.;
+    ctx->stage_ms[2] = elapsed(ctx->stage_ev[2], ctx->stage_ev[3]);
+    if (!need_c) {
+      ctx->stage_ms[8] = elapsed(ctx->stage_ev[3], ctx->stage_ev[5]);
+    } else {
+      ctx->stage_ms[6] = elapsed(ctx->stage_ev[3], ctx->stage_ev[4]);
+      ctx->stage_ms[8] = elapsed(ctx->stage_ev[4], ctx->stage_ev[5]);
+      if (n_slots > 0) {
+        ctx->stage_ms[9] = elapsed(ctx->stage_ev[5], ctx->stage_ev[6]);
+        ctx->stage_ms[7] = elapsed(ctx->stage_ev[6], ctx->stage_ev[7]);
+      }
+    }
   }
   return AGP_OK;
 }

@@ -1130,20 +1130,15 @@ class GaussianProcessRegression:
         return -out.value
 
 
-    def log_likelihood_gradient(self, dataset):
-        """(log_likelihood(dataset), {name: d log_likelihood / d name}) for every name of get_params(), exact to fp64
-        rounding (agp_nll_gradient: one fit, K^-1 and a contraction against the derivative of the covariance program).
-        The reference's tuner takes forward differences instead (compute_gradient, tune/finite_difference.hpp:37-90).
-        As in log_likelihood, the target variance is not added and priors are not included.  ScalingTerm parameters
-        go through the scaling function's d f / d name at the features (ScalingFunction.derivative), mean-function
-        parameters through (d mu / d name)^T alpha with a central difference of the mean function on the host."""
-        import copy
+    def _slot_gradient(self, entry, dataset, with_variance):
+        """One call of a gradient entry (agp_nll_gradient / agp_loo_nll_gradient) over the slot table of the covariance
+        function: (value, slots, per-slot gradient, the n-vector the entry returns, the flattened features)"""
         if has_linear_combinations(dataset.features):
-            raise NotImplementedError("log_likelihood_gradient: LinearCombination features go through the dense path")
+            raise NotImplementedError(f"{entry}: LinearCombination features go through the dense path")
         ctx = self._ctx()
         cov = self.covariance_function_
         fs = cov.features(_values_of(dataset.features))
-        y, _ = self._targets(fs, dataset.targets)
+        y, yv = self._targets(fs, dataset.targets)
         slots, columns = cov.param_slots()
         if len(slots) > capi.MAX_GRADIENT_SLOTS:
             raise ValueError(f"more than {capi.MAX_GRADIENT_SLOTS} covariance parameter slots")
@@ -1155,24 +1150,60 @@ class GaussianProcessRegression:
                 tangents[:, c] = fn.derivative(fs.coords, name)
         table = (capi.GradientSlot * max(1, len(slots)))(*[capi.GradientSlot(node, p) for node, p, _ in slots])
         s = fs.as_struct()
-        nll = C.c_double()
-        grad_nll = np.zeros(len(slots))
-        alpha = np.empty(n)
-        ctx._check(ctx._lib.agp_nll_gradient(ctx._h, ctx.kernel(cov), C.byref(s), _ptr(y), None, len(slots), table,
-                                             _ptr(tangents), n, C.byref(nll), _ptr(grad_nll), _ptr(alpha)),
-                   "agp_nll_gradient")
+        value = C.c_double()
+        grad = np.zeros(len(slots))
+        vec = np.empty(n)
+        ctx._check(getattr(ctx._lib, entry)(ctx._h, ctx.kernel(cov), C.byref(s), _ptr(y), _ptr(yv) if with_variance else None,
+                                            len(slots), table, _ptr(tangents), n, C.byref(value), _ptr(grad), _ptr(vec)),
+                   entry)
+        return value.value, slots, grad, vec, fs
+
+    def _mean_tangent(self, fs, name):
+        """d mu / d name at the features: a central difference of the mean function on the host"""
+        import copy
+        value = self.mean_function_.get_params()[name]
+        h = 1e-6 * max(1.0, abs(value))
+        up, down = copy.deepcopy(self.mean_function_), copy.deepcopy(self.mean_function_)
+        up.set_param(name, value + h)
+        down.set_param(name, value - h)
+        return (np.asarray(up(fs.coords), dtype=np.float64) - np.asarray(down(fs.coords), dtype=np.float64)) / (2 * h)
+
+    def log_likelihood_gradient(self, dataset):
+        """(log_likelihood(dataset), {name: d log_likelihood / d name}) for every name of get_params(), exact to fp64
+        rounding (agp_nll_gradient: one fit, K^-1 and a contraction against the derivative of the covariance program).
+        The reference's tuner takes forward differences instead (compute_gradient, tune/finite_difference.hpp:37-90).
+        As in log_likelihood, the target variance is not added and priors are not included.  ScalingTerm parameters
+        go through the scaling function's d f / d name at the features (ScalingFunction.derivative), mean-function
+        parameters through (d mu / d name)^T alpha with a central difference of the mean function on the host."""
+        nll, slots, grad_nll, alpha, fs = self._slot_gradient("agp_nll_gradient", dataset, with_variance=False)
         grad = {name: 0. for name in self.get_params()}
         for (_, _, name), g in zip(slots, grad_nll):
             grad[name] -= g
         # y = targets - mu: d log p / d theta = (d mu / d theta)^T alpha
-        for name, value in self.mean_function_.get_params().items():
-            h = 1e-6 * max(1.0, abs(value))
-            up, down = copy.deepcopy(self.mean_function_), copy.deepcopy(self.mean_function_)
-            up.set_param(name, value + h)
-            down.set_param(name, value - h)
-            dmu = (np.asarray(up(fs.coords), dtype=np.float64) - np.asarray(down(fs.coords), dtype=np.float64)) / (2 * h)
-            grad[name] += float(dmu @ alpha)
-        return -nll.value, grad
+        for name in self.mean_function_.get_params():
+            grad[name] += float(self._mean_tangent(fs, name) @ alpha)
+        return -nll, grad
+
+    def leave_one_out_likelihood_gradient(self, dataset):
+        """(LeaveOneOutLikelihood()(dataset, self), {name: d that / d name}) for every name of get_params(), exact to
+        fp64 rounding (agp_loo_nll_gradient).  The value is the METRIC the tuner minimises, sum_i NLL_i of the
+        leave-one-out predictions (evaluation/model_metrics.hpp:59-72), not a log-likelihood: log_likelihood_gradient
+        returns +log p, this returns a sum of negative log-likelihoods.  Unlike log_likelihood, the target variance s is
+        used, twice as the reference does: in the fit, and once more as the truth's variance of each score
+        (v_i = 1 / (K^-1)_ii + s_i).  Priors are not included.  Parameters shared by several leaves are summed;
+        ScalingTerm parameters go through ScalingFunction.derivative, mean-function parameters through -u^T d mu / d name
+        (u = K^-1 a, the entry's mean weights) with a central difference of the mean function on the host.
+        fp64 models only."""
+        if self.precision != "fp64":
+            raise ValueError(f"leave_one_out_likelihood_gradient: fp64 models only, not {self.precision!r}")
+        loo, slots, grad_loo, u, fs = self._slot_gradient("agp_loo_nll_gradient", dataset, with_variance=True)
+        grad = {name: 0. for name in self.get_params()}
+        for (_, _, name), g in zip(slots, grad_loo):
+            grad[name] += g
+        # y = targets - mu: d LOO / d theta = -u^T (d mu / d theta)
+        for name in self.mean_function_.get_params():
+            grad[name] -= float(u @ self._mean_tangent(fs, name))
+        return loo, grad
 
 class LeaveOneOutGrouper:
     """LeaveOneOutGrouper (indexing/group_by.hpp): every observation is its own group."""
@@ -1272,6 +1303,28 @@ class CrossValidation:
         marg = pred.marginals()
         y = dataset.targets.mean
         return np.array([metric(marg[k], MarginalDistribution(y[np.asarray(idx)])) for k, idx in pred.indexer_.items()])
+
+
+class LeaveOneOutLikelihood:
+    """LeaveOneOutLikelihood<> (evaluation/model_metrics.hpp:59-72): metric(dataset, model) = sum over the points of the
+    negative log-likelihood of each point's leave-one-out prediction, scored against the truth with its variance added
+    (prediction_metrics.hpp:113-119).  No prior term.  One fit and R = L^-1 (agp_loo_nll_gradient, value only);
+    model.leave_one_out_likelihood_gradient gives the gradient too."""
+
+    def __call__(self, dataset, model):
+        if model.precision != "fp64":
+            raise ValueError(f"LeaveOneOutLikelihood: fp64 models only, not {model.precision!r}")
+        if has_linear_combinations(dataset.features):
+            raise NotImplementedError("LeaveOneOutLikelihood: LinearCombination features go through the dense path")
+        ctx = model._ctx()
+        cov = model.covariance_function_
+        fs = cov.features(_values_of(dataset.features))
+        y, yv = model._targets(fs, dataset.targets)
+        s = fs.as_struct()
+        out = C.c_double()
+        ctx._check(ctx._lib.agp_loo_nll_gradient(ctx._h, ctx.kernel(cov), C.byref(s), _ptr(y), _ptr(yv), 0, None, None, 0,
+                                                 C.byref(out), None, None), "agp_loo_nll_gradient")
+        return out.value
 
 
 def root_mean_square_error(prediction, truth):

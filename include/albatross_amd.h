@@ -287,6 +287,33 @@ AGP_API int agp_nll_gradient(agp_context *ctx, const agp_kernel *k, const agp_fe
                      double *nll, double *grad_nll,
                      double *information);
 
+/* The leave-one-out likelihood metric, LeaveOneOutLikelihood<>()(dataset, model) (evaluation/model_metrics.hpp:59-72,
+ * without the prior term), and its exact gradient with respect to covariance parameters.  Per point i, with
+ * K = cov(x, x) + diag(y_var), C = K^-1, alpha = C y, c_i = C_ii and s_i = y_var[i] (0 if y_var is NULL):
+ *   v_i = 1/c_i + s_i,   d_i = alpha_i / c_i,   NLL_i = 1/2 (log v_i + d_i^2 / v_i + log 2 pi),   loo_nll = sum_i NLL_i.
+ * y_var is used in BOTH places, as the reference does: in the fit (gp.hpp:65) and once more as the truth's variance of
+ * the score (prediction_metrics.hpp:113-119).  (agp_nll / log_likelihood add it nowhere.)
+ * Gradient (GPML 5.4.2, eqs. 5.10-5.13, with s):
+ *   dloo_nll / dtheta = sum_ij W_ij dK_ij / dtheta,   W = C diag(b) C - 1/2 (u alpha^T + alpha u^T),
+ *   b_i = (1 - d_i^2/v_i + 2 alpha_i d_i) / (2 v_i c_i^2),   u = C a,   a_i = d_i / (v_i c_i).
+ * The steps of agp_nll_gradient (fit, alpha, R = L^-1, C = R^T R), then u = C a, G = diag(b)^1/2 C and
+ * C diag(b) C = G^T G on the fp64 MFMA: N^3 flop beyond agp_nll_gradient, whatever n_slots is, then the contraction.
+ * For a mean-function parameter, dloo_nll / dtheta = -mean_weights^T dm / dtheta (mean_weights = u; y = targets - m).
+ * n_slots == 0 and mean_weights NULL: the value alone, c_i from R's squared column norms (agp_fit_inverse_diagonal);
+ * neither C nor G^T G is formed: a fit plus N^3 / 3 flop.
+ * Slots, tangents, locations, determinism and status codes as agp_nll_gradient: AGP_ERR_INVALID_ARGUMENT for a slot on
+ * a non-leaf node or a parameter the leaf does not have, or more than AGP_MAX_GRADIENT_SLOTS slots; AGP_ERR_NAN_INPUT;
+ * AGP_ERR_NOT_POSITIVE_DEFINITE.  loo_nll (1 value), grad_loo_nll (n_slots values) and mean_weights (n values, may be
+ * NULL) are host memory.  With profiling on, agp_last_stage_ms reports 0 gram, 1 factor, 2 alpha and R = L^-1,
+ * 6 R^T R, 8 the per-point terms, u and G (value only: R's column norms and the terms), 9 G^T G, 7 the contraction;
+ * stages a call does not run report 0. */
+AGP_API int agp_loo_nll_gradient(agp_context *ctx, const agp_kernel *k, const agp_features *x,
+                                 const double *y, const double *y_var,
+                                 int n_slots, const agp_gradient_slot *slots,
+                                 const double *tangents, int64_t ldt,
+                                 double *loo_nll, double *grad_loo_nll,
+                                 double *mean_weights);
+
 /* Tuner objective batching: agp_nll for `count` parameter vectors of one model on one dataset in lock step
  * (batched Gram slabs + batched LL^T; blockIdx.y = parameter vector) — the evaluations that
  * compute_gradient (include/albatross/src/tune/finite_difference.hpp:20-94) and the ModelTuner objective
@@ -361,7 +388,7 @@ AGP_API int agp_nll_dense(agp_context *ctx, const double *deviation, const doubl
 AGP_API int agp_fit_update(agp_context *ctx, const agp_kernel *k, const agp_fit *old, const agp_features *x_new, const double *y_new,
                    const double *y_var_new, agp_fit **out, double *information, double *log_det);
 
-/* ---- leave-one-out fast path (the tuner's LeaveOneOutLikelihood objective) --- */
+/* ---- leave-one-out fast path (the tuner's LeaveOneOutLikelihood objective; the metric and its gradient: agp_loo_nll_gradient) --- */
 /* diag(K^-1): SerializableLDLT::inverse_diagonal (src/eigen/serializable_ldlt.hpp:
  * 137-199: R = L^-1, then the squared column norms of R).  out: n doubles. */
 AGP_API int agp_fit_inverse_diagonal(agp_context *ctx, const agp_fit *fit, double *out,
@@ -661,7 +688,8 @@ AGP_API int agp_sharded_fit_stage(const agp_sharded_fit *fit, int stage, double 
 /* Per-stage device time of the LAST fit / nll on this context, measured with
  * HIP events on the stream the kernels were launched on.  Stages:
  * 0 gram, 1 factor (total), 2 solve, 3 trailing-update kernels only (sum),
- * 4 number of trailing-update launches.  Returns ms (or a count for 4). */
+ * 4 number of trailing-update launches.  Returns ms (or a count for 4).  Stages 6-9:
+ * the gradient entries (agp_nll_gradient, agp_loo_nll_gradient). */
 AGP_API int agp_last_stage_ms(const agp_context *ctx, int stage, double *ms);
 /* enable (1) / disable (0) per-stage event timing (default off: events add
  * host overhead to the launch chain). */

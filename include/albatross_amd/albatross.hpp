@@ -1756,52 +1756,53 @@ class GaussianProcessRegression {
 
   template <typename FeatureType>
   LogLikelihoodGradient log_likelihood_gradient(const RegressionDataset<FeatureType> &dataset) const {
-    using X = typename detail::unwrap<FeatureType>::type;
+    std::vector<std::string> names;
+    std::vector<double> grad, alpha;
+    const double nll = slot_gradient(agp_nll_gradient, "agp_nll_gradient", dataset, nullptr, &names, &grad, &alpha);
+    LogLikelihoodGradient out{-nll, {}};
+    for (const auto &kv : get_params()) out.gradient[kv.first] = 0.;
+    for (std::size_t s = 0; s < names.size(); ++s) out.gradient[names[s]] -= grad[s];
+    for (const auto &kv : mean_function_.get_params())  // y = targets - mu: d log p / d theta = (d mu / d theta)^T alpha
+      out.gradient[kv.first] += mean_tangent_dot(dataset, kv.first, kv.second, alpha);
+    return out;
+  }
+
+  // LeaveOneOutLikelihood<>()(dataset, *this) (evaluation/model_metrics.hpp:59-72, no prior term) and its exact gradient
+  // with respect to every name of get_params() (agp_loo_nll_gradient).  The value is the metric the tuner minimises,
+  // sum_i NLL_i of the leave-one-out predictions, not a log-likelihood.  dataset.targets.covariance is used twice, as in
+  // the reference: in the fit and as the truth's variance of each score.  Mean-function parameters go through
+  // -u^T (d mu / d name), u the entry's mean weights.
+  struct LeaveOneOutLikelihoodGradient {
+    double value;
+    ParameterStore gradient;
+  };
+
+  template <typename FeatureType>
+  LeaveOneOutLikelihoodGradient leave_one_out_likelihood_gradient(const RegressionDataset<FeatureType> &dataset) const {
+    std::vector<std::string> names;
+    std::vector<double> grad, u;
+    const double *yvar = dataset.targets.covariance.empty() ? nullptr : dataset.targets.covariance.data();
+    const double loo = slot_gradient(agp_loo_nll_gradient, "agp_loo_nll_gradient", dataset, yvar, &names, &grad, &u);
+    LeaveOneOutLikelihoodGradient out{loo, {}};
+    for (const auto &kv : get_params()) out.gradient[kv.first] = 0.;
+    for (std::size_t s = 0; s < names.size(); ++s) out.gradient[names[s]] += grad[s];
+    for (const auto &kv : mean_function_.get_params())  // y = targets - mu: d LOO / d theta = -u^T (d mu / d theta)
+      out.gradient[kv.first] -= mean_tangent_dot(dataset, kv.first, kv.second, u);
+    return out;
+  }
+
+  // the value alone (agp_loo_nll_gradient without slots: c_i from R's column norms, no K^-1)
+  template <typename FeatureType>
+  double leave_one_out_likelihood(const RegressionDataset<FeatureType> &dataset) const {
     auto ctx = detail::default_context();
     detail::KernelHolder k(covariance_function_.program());
     detail::Flat f = detail::flatten(covariance_function_, dataset.features);
-    const std::size_t n = dataset.features.size();
-    std::vector<detail::GradSlot<X>> rows;
-    int node = 0;
-    covariance_function_.template emit_slots<X>(rows, node);
-    std::vector<agp_gradient_slot> slots;
-    std::vector<double> tangents;
-    int columns = 0;
-    for (auto &r : rows) {
-      if (r.tangent) {
-        r.slot.param = columns++;
-        tangents.resize(n * static_cast<std::size_t>(columns));
-        for (std::size_t i = 0; i < n; ++i)
-          tangents[static_cast<std::size_t>(r.slot.param) * n + i] = r.tangent(detail::unwrap<FeatureType>::get(dataset.features[i]));
-      }
-      slots.push_back(r.slot);
-    }
-    Vector y = dataset.targets.mean;
-    if (!std::is_same<MeanFunc, ZeroMean>::value)
-      for (std::size_t i = 0; i < y.size(); ++i)
-        y[i] -= mean_function_._call_impl(detail::unwrap<FeatureType>::get(dataset.features[i]));
-    double nll = 0.;
-    std::vector<double> grad(slots.size()), alpha(n);
-    detail::check(agp_nll_gradient(ctx->ctx, k.k, &f.view, y.data(), nullptr, static_cast<int>(slots.size()), slots.data(),
-                                   columns > 0 ? tangents.data() : nullptr, static_cast<std::int64_t>(n), &nll, grad.data(),
-                                   alpha.data()),
-                  ctx->ctx, "agp_nll_gradient");
-    LogLikelihoodGradient out{-nll, {}};
-    for (const auto &kv : get_params()) out.gradient[kv.first] = 0.;
-    for (std::size_t s = 0; s < slots.size(); ++s) out.gradient[rows[s].name] -= grad[s];
-    for (const auto &kv : mean_function_.get_params()) {  // y = targets - mu: d log p / d theta = (d mu / d theta)^T alpha
-      const double h = 1e-6 * std::max(1., std::fabs(kv.second));
-      MeanFunc up = mean_function_, down = mean_function_;
-      up.set_param(kv.first, kv.second + h);
-      down.set_param(kv.first, kv.second - h);
-      double g = 0.;
-      for (std::size_t i = 0; i < n; ++i) {
-        const X &x = detail::unwrap<FeatureType>::get(dataset.features[i]);
-        g += (up._call_impl(x) - down._call_impl(x)) / (2. * h) * alpha[i];
-      }
-      out.gradient[kv.first] += g;
-    }
-    return out;
+    const Vector y = deviation(dataset);
+    const double *yvar = dataset.targets.covariance.empty() ? nullptr : dataset.targets.covariance.data();
+    double loo = 0.;
+    detail::check(agp_loo_nll_gradient(ctx->ctx, k.k, &f.view, y.data(), yvar, 0, nullptr, nullptr, 0, &loo, nullptr, nullptr),
+                  ctx->ctx, "agp_loo_nll_gradient");
+    return loo;
   }
 
   // gp.hpp:442-451 (prior_log_likelihood() is outside the hot path and not included).  As in the reference the
@@ -1821,6 +1822,69 @@ class GaussianProcessRegression {
   }
 
  private:
+  // targets - mu (mean_function_.remove_from)
+  template <typename FeatureType>
+  Vector deviation(const RegressionDataset<FeatureType> &dataset) const {
+    Vector y = dataset.targets.mean;
+    if (!std::is_same<MeanFunc, ZeroMean>::value)
+      for (std::size_t i = 0; i < y.size(); ++i)
+        y[i] -= mean_function_._call_impl(detail::unwrap<FeatureType>::get(dataset.features[i]));
+    return y;
+  }
+
+  // One call of a gradient entry (agp_nll_gradient / agp_loo_nll_gradient) over the slot table of the covariance
+  // function: returns its value; names[s] / grad[s] per slot, vec the n values it returns (alpha / mean weights).
+  template <typename FeatureType, typename Entry>
+  double slot_gradient(Entry entry, const char *what, const RegressionDataset<FeatureType> &dataset, const double *yvar,
+                       std::vector<std::string> *names, std::vector<double> *grad, std::vector<double> *vec) const {
+    using X = typename detail::unwrap<FeatureType>::type;
+    auto ctx = detail::default_context();
+    detail::KernelHolder k(covariance_function_.program());
+    detail::Flat f = detail::flatten(covariance_function_, dataset.features);
+    const std::size_t n = dataset.features.size();
+    std::vector<detail::GradSlot<X>> rows;
+    int node = 0;
+    covariance_function_.template emit_slots<X>(rows, node);
+    std::vector<agp_gradient_slot> slots;
+    std::vector<double> tangents;
+    int columns = 0;
+    for (auto &r : rows) {
+      if (r.tangent) {
+        r.slot.param = columns++;
+        tangents.resize(n * static_cast<std::size_t>(columns));
+        for (std::size_t i = 0; i < n; ++i)
+          tangents[static_cast<std::size_t>(r.slot.param) * n + i] = r.tangent(detail::unwrap<FeatureType>::get(dataset.features[i]));
+      }
+      slots.push_back(r.slot);
+      names->push_back(r.name);
+    }
+    const Vector y = deviation(dataset);
+    double value = 0.;
+    grad->assign(slots.size(), 0.);
+    vec->assign(n, 0.);
+    detail::check(entry(ctx->ctx, k.k, &f.view, y.data(), yvar, static_cast<int>(slots.size()), slots.data(),
+                        columns > 0 ? tangents.data() : nullptr, static_cast<std::int64_t>(n), &value, grad->data(), vec->data()),
+                  ctx->ctx, what);
+    return value;
+  }
+
+  // (d mu / d name)^T w, d mu / d name by a central difference of the mean function with h = 1e-6 max(1, |value|)
+  template <typename FeatureType>
+  double mean_tangent_dot(const RegressionDataset<FeatureType> &dataset, const std::string &name, double value,
+                          const std::vector<double> &w) const {
+    using X = typename detail::unwrap<FeatureType>::type;
+    const double h = 1e-6 * std::max(1., std::fabs(value));
+    MeanFunc up = mean_function_, down = mean_function_;
+    up.set_param(name, value + h);
+    down.set_param(name, value - h);
+    double g = 0.;
+    for (std::size_t i = 0; i < w.size(); ++i) {
+      const X &x = detail::unwrap<FeatureType>::get(dataset.features[i]);
+      g += (up._call_impl(x) - down._call_impl(x)) / (2. * h) * w[i];
+    }
+    return g;
+  }
+
   CovFunc covariance_function_;
   MeanFunc mean_function_;
   std::string model_name_ = "gaussian_process_regression";
@@ -2283,6 +2347,16 @@ struct GaussianProcessNegativeLogLikelihood {
   double operator()(const RegressionDataset<FeatureType> &dataset,
                     const GaussianProcessRegression<CovFunc, MeanFunc> &model) const {
     return -model.log_likelihood(dataset);
+  }
+};
+
+// LeaveOneOutLikelihood<>, evaluation/model_metrics.hpp:59-72: the tuner's leave-one-out metric (no prior term)
+template <typename Unused = void>
+struct LeaveOneOutLikelihood {
+  template <typename FeatureType, typename CovFunc, typename MeanFunc>
+  double operator()(const RegressionDataset<FeatureType> &dataset,
+                    const GaussianProcessRegression<CovFunc, MeanFunc> &model) const {
+    return model.leave_one_out_likelihood(dataset);
   }
 };
 
