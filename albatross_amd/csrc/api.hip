@@ -1466,7 +1466,7 @@ int agp_nll(agp_context *c, const agp_kernel *k, const agp_features *x, const do
 // `bytes` of the context's pinned staging area (common.h: h_stage), grown on demand; nullptr if it cannot be had (the
 // callers then stage through pageable memory and synchronise once).  The previous contents are dead: every user ends its
 // call with a synchronisation of the stream that read them.
-static void *host_stage(agp_context *ctx, size_t bytes) {
+void *host_stage(agp_context *ctx, size_t bytes) {
   if (ctx->h_stage_bytes < bytes) {
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
     ctx->h_stage = nullptr;

@@ -158,11 +158,16 @@ int build_and_factor_nll(agp_context *c, const DevProgram *dprog, const DevProgr
                          long long lda, double *invd, double *y, const double *yvar);
 // C (lower tiles, ldc) = R^T R for a lower-triangular n x n R (gradient.hip)
 void launch_rtr_lower(hipStream_t s, const double *R, long long ldr, long long n, double *C, long long ldc);
+// the same for `count` problems in one launch: R_b = R + b * stride_R, C_b = C + b * stride_C (blockIdx.y = problem)
+void launch_rtr_lower_batched(hipStream_t s, const double *R, long long ldr, long long stride_R, long long n, double *C,
+                              long long ldc, long long stride_C, long long count);
 // S (lower tiles, lds) = G^T G for a full n x n G (gradient.hip: agp_loo_nll_gradient's C diag(b) C)
 void launch_gtg_lower(hipStream_t s, const double *G, long long ldg, long long n, double *S, long long lds);
 }  // namespace agp
 // x = L^-T z for ONE vector (api.hip): z is overwritten with x; ws: backsolve_ws_elems(n) doubles of scratch
 extern "C" {  // (defined inside api.hip's extern "C" block)
+// `bytes` of the context's pinned staging area, or nullptr; valid until the call's final synchronisation
+void *host_stage(agp_context *ctx, size_t bytes);
 size_t backsolve_ws_elems(long long n);
 void backward_solve_vec_any(hipStream_t s, const double *A, long long n, long long lda, const double *invd, double *z,
                             double *ws, long long first_done = 0, hipEvent_t ev_done = nullptr);

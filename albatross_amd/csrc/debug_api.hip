@@ -266,6 +266,35 @@ extern "C" AGP_DEBUG_API int agp_debug_rtr_lower(agp_context *ctx, const double 
   return AGP_OK;
 }
 
+// agp_debug_rtr_lower for `count` problems in one launch (gradient.hip: launch_rtr_lower_batched, agp_nll_gradient_batch's
+// K_b^-1): R and C hold `count` slabs of ld * n doubles each.  ms (optional): the kernel's device time.
+extern "C" AGP_DEBUG_API int agp_debug_rtr_lower_batched(agp_context *ctx, const double *R, int64_t n, int64_t ld, int64_t count,
+                                                         double *C, double *ms) {
+  if (!ctx || !R || !C || n <= 0 || ld < n || count <= 0 || count > 65535) return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const size_t bytes = sizeof(double) * (size_t)ld * (size_t)n * (size_t)count;
+  double *dR = nullptr, *dC = nullptr;
+  AGP_HIP_CHECK(ctx, hipMalloc(&dR, bytes));
+  AGP_HIP_CHECK(ctx, hipMalloc(&dC, bytes));
+  AGP_HIP_CHECK(ctx, hipMemcpy(dR, R, bytes, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipMemsetAsync(dC, 0, bytes, ctx->stream));  // on the kernel's stream, as agp_debug_rtr_lower
+  hipEvent_t e0, e1;
+  AGP_HIP_CHECK(ctx, hipEventCreate(&e0));
+  AGP_HIP_CHECK(ctx, hipEventCreate(&e1));
+  AGP_HIP_CHECK(ctx, hipEventRecord(e0, ctx->stream));
+  launch_rtr_lower_batched(ctx->stream, dR, ld, ld * n, n, dC, ld, ld * n, count);
+  AGP_HIP_CHECK(ctx, hipEventRecord(e1, ctx->stream));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  float t = 0.f;
+  (void)hipEventElapsedTime(&t, e0, e1);
+  if (ms) *ms = t;
+  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  AGP_HIP_CHECK(ctx, hipMemcpy(C, dC, bytes, hipMemcpyDeviceToHost));
+  (void)hipFree(dR); (void)hipFree(dC);
+  return AGP_OK;
+}
+
 // S = G^T G (lower tiles; the whole diagonal tiles) for a full n x n G, column-major with leading dimension ld: the
 // kernel of agp_loo_nll_gradient's C diag(b) C (gradient.hip: gtg_lower_kernel).  ms (optional): its device time.
 extern "C" AGP_DEBUG_API int agp_debug_gtg_lower(agp_context *ctx, const double *G, int64_t n, int64_t ld, double *S,

@@ -23,7 +23,9 @@
 // The same fit, alpha, R and C = R^T R; then loo_terms_kernel (per point: the NLL term, a, sqrt(b)), u by
 // launch_symv_lower, G = diag(b)^1/2 sym(C) over R (loo_form_g_kernel), S = G^T G = C diag(b) C over C (gtg_lower_kernel:
 // N^3 flop, the only O(N^3) work beyond agp_nll_gradient) and the contraction of W = S - sym(u alpha^T).
+#include <climits>
 #include <cstring>
+#include <limits>
 #include <vector>
 
 #include "api_internal.h"
@@ -48,22 +50,32 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void rtr_lower_kernel(GemmArgs g) 
   while ((long long)(bi + 1) * (bi + 2) / 2 <= id) ++bi;
   const int bj = (int)(id - (long long)bi * (bi + 1) / 2);
   const long long k0 = (long long)bi * GT;
+  const long long b = blockIdx.y;  // problem of a batched launch (batch_* = 0: one problem)
   GemmArgs t = g;
-  t.A = g.A + k0;
-  t.B = g.B + k0;
+  t.C = g.C + b * g.batch_C;
+  t.A = g.A + b * g.batch_A + k0;
+  t.B = g.B + b * g.batch_B + k0;
   t.K = g.K - k0;
   gemm_nt_sub_tile<true, true, true>(t, bi, bj, lds);
 }
 
-void launch_rtr_lower(hipStream_t s, const double *R, long long ldr, long long n, double *C, long long ldc) {
-  if (n <= 0) return;
+// C_b = R_b^T R_b for `count` problems (blockIdx.y = problem): R_b = R + b * stride_R, C_b = C + b * stride_C.  Within
+// each problem the deepest tile rows go first, as for one problem; count = 1 is launch_rtr_lower.
+void launch_rtr_lower_batched(hipStream_t s, const double *R, long long ldr, long long stride_R, long long n, double *C,
+                              long long ldc, long long stride_C, long long count) {
+  if (n <= 0 || count <= 0) return;
   GemmArgs g;
   g.C = C; g.ldc = ldc; g.A = R; g.lda = ldr; g.B = R; g.ldb = ldr;
   g.M = n; g.N = n; g.K = n; g.tri = 1;
   g.ntr = g.ntc = (int)((n + GT - 1) / GT);
   g.assign = 1;  // C = + A B^T, C not read
+  g.batch_C = stride_C; g.batch_A = g.batch_B = stride_R;
   const long long tiles = (long long)g.ntr * (g.ntr + 1) / 2;
-  hipLaunchKernelGGL(rtr_lower_kernel, dim3((unsigned)tiles), dim3(GEMM_THREADS), 0, s, g);
+  hipLaunchKernelGGL(rtr_lower_kernel, dim3((unsigned)tiles, (unsigned)count), dim3(GEMM_THREADS), 0, s, g);
+}
+
+void launch_rtr_lower(hipStream_t s, const double *R, long long ldr, long long n, double *C, long long ldc) {
+  launch_rtr_lower_batched(s, R, ldr, 0, n, C, ldc, 0, 1);
 }
 
 // ---- contraction: partial[tile][g] = sum over the tile's pairs i >= j of w_ij dk_ij / dslot_g ------------------------
@@ -97,10 +109,10 @@ __device__ __forceinline__ void load_point(const FeatView &X, long long i, bool 
 
 // One workgroup per 64 x 64 lower tile of K^-1; lane = row i (coalesced reads of K^-1), each wave walks 16 columns j,
 // whose point is the same for the whole wave.  LOO: the weight of agp_loo_nll_gradient, S_ij - 1/2 (u_i alpha_j +
-// alpha_i u_j), in place of K^-1_ij - alpha_i alpha_j (the NLL instantiation is unchanged).
-template <int DIMP, bool LOO = false>
-__global__ __launch_bounds__(CT_THREADS) void nll_grad_contract_kernel(const DevProgram *__restrict__ P, FeatView X,
-                                                                       ContractArgs a) {
+// alpha_i u_j), in place of K^-1_ij - alpha_i alpha_j (the NLL instantiation is unchanged).  The body of both the
+// single-problem kernel and the batched one (tile blockIdx.x, its sums to a.partial[tile][g]).
+template <int DIMP, bool LOO>
+__device__ __forceinline__ void contract_tile(const DevProgram *__restrict__ P, const FeatView &X, const ContractArgs &a) {
   const long long id = blockIdx.x;
   int bi = (int)((sqrt(8. * (double)id + 1.) - 1.) * 0.5);
   while ((long long)bi * (bi + 1) / 2 > id) --bi;
@@ -157,11 +169,14 @@ __global__ __launch_bounds__(CT_THREADS) void nll_grad_contract_kernel(const Dev
   }
 }
 
-// out[base + g] = scale * sum over tiles of partial[tile][g], in a fixed order; one workgroup per slot of the group
-__global__ __launch_bounds__(256) void nll_grad_reduce_kernel(const double *__restrict__ partial, long long tiles, int count,
-                                                              double scale, double *__restrict__ out) {
-  const int g = blockIdx.x;
-  if (g >= count) return;
+template <int DIMP, bool LOO = false>
+__global__ __launch_bounds__(CT_THREADS) void nll_grad_contract_kernel(const DevProgram *__restrict__ P, FeatView X,
+                                                                       ContractArgs a) {
+  contract_tile<DIMP, LOO>(P, X, a);
+}
+
+// sum over tiles of partial[tile][g] in a fixed order (256 strided partial sums, then a tree); the value is in red[0]
+__device__ __forceinline__ double reduce_partials(const double *__restrict__ partial, long long tiles, int g) {
   double v = 0.;
   for (long long t = threadIdx.x; t < tiles; t += 256) v += partial[t * GRAD_GROUP + g];
   __shared__ double red[256];
@@ -171,7 +186,62 @@ __global__ __launch_bounds__(256) void nll_grad_reduce_kernel(const double *__re
     if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
     __syncthreads();
   }
-  if (threadIdx.x == 0) out[g] = scale * red[0];
+  return red[0];
+}
+
+// out[base + g] = scale * sum over tiles of partial[tile][g], in a fixed order; one workgroup per slot of the group
+__global__ __launch_bounds__(256) void nll_grad_reduce_kernel(const double *__restrict__ partial, long long tiles, int count,
+                                                              double scale, double *__restrict__ out) {
+  const int g = blockIdx.x;
+  if (g >= count) return;
+  const double v = reduce_partials(partial, tiles, g);
+  if (threadIdx.x == 0) out[g] = scale * v;
+}
+
+// ---- the batched contraction (agp_nll_gradient_batch) -------------------------------------------------------------
+// One descriptor per problem, built on the host for the call and uploaded with it: the program by value (not the
+// context's device program cache, whose slots later problems would overwrite), the features, K^-1 and alpha of the
+// problem's slabs, its slot table in groups of GRAD_GROUP and the tangent column of every AGP_OP_SCALING slot.
+constexpr int GRAD_GROUPS_MAX = (AGP_MAX_GRADIENT_SLOTS + GRAD_GROUP - 1) / GRAD_GROUP;
+struct ContractDesc {
+  DevProgram prog;
+  FeatView X;
+  const double *C;         // K_b^-1, lower triangle
+  long long ldc;
+  const double *alpha;
+  double *partial;         // [group][tile][GRAD_GROUP]
+  int n_slots;
+  int pad;
+  TangentSlots<GRAD_GROUP> slots[GRAD_GROUPS_MAX];
+  const double *tang[GRAD_GROUPS_MAX * GRAD_GROUP];
+};
+
+// grid: x = tile, y = problem, z = slot group.  DIMP covers the batch's largest dimension (load_point zero-pads);
+// problems with fewer slot groups leave their unused z-slices at once.
+template <int DIMP>
+__global__ __launch_bounds__(CT_THREADS) void nll_grad_contract_batched_kernel(const ContractDesc *__restrict__ D, long long tiles) {
+  const ContractDesc &d = D[blockIdx.y];
+  const int grp = blockIdx.z;
+  if (grp * GRAD_GROUP >= d.n_slots) return;  // (the whole workgroup)
+  ContractArgs a;
+  a.slots = d.slots[grp];
+#pragma unroll
+  for (int g = 0; g < GRAD_GROUP; ++g) a.tang[g] = d.tang[grp * GRAD_GROUP + g];
+  a.C = d.C; a.ldc = d.ldc; a.alpha = d.alpha; a.u = nullptr;
+  a.partial = d.partial + (long long)grp * tiles * GRAD_GROUP;
+  const FeatView X = d.X;
+  contract_tile<DIMP, false>(&d.prog, X, a);
+}
+
+// out[b * ldo + slot] = scale * sum over tiles of problem b's partials of that slot (one workgroup per (slot, problem))
+__global__ __launch_bounds__(256) void nll_grad_reduce_batched_kernel(const ContractDesc *__restrict__ D, long long tiles,
+                                                                      double scale, double *__restrict__ out, long long ldo) {
+  const int slot = blockIdx.x;
+  const long long b = blockIdx.y;
+  const ContractDesc &d = D[b];
+  if (slot >= d.n_slots) return;
+  const double v = reduce_partials(d.partial + (long long)(slot / GRAD_GROUP) * tiles * GRAD_GROUP, tiles, slot % GRAD_GROUP);
+  if (threadIdx.x == 0) out[b * ldo + slot] = scale * v;
 }
 
 static long long contract_tiles(long long n) {
@@ -188,6 +258,15 @@ static void launch_contract(hipStream_t s, const DevProgram *P, const FeatView &
   else if (dim == 3) hipLaunchKernelGGL((nll_grad_contract_kernel<3, LOO>), grid, block, 0, s, P, X, a);
   else if (dim == 4) hipLaunchKernelGGL((nll_grad_contract_kernel<4, LOO>), grid, block, 0, s, P, X, a);
   else hipLaunchKernelGGL((nll_grad_contract_kernel<8, LOO>), grid, block, 0, s, P, X, a);
+}
+
+static void launch_contract_batched(hipStream_t s, int dim_max, const ContractDesc *D, long long tiles, long long count, int groups) {
+  const dim3 grid((unsigned)tiles, (unsigned)count, (unsigned)groups), block(CT_THREADS);
+  if (dim_max == 1) hipLaunchKernelGGL(nll_grad_contract_batched_kernel<1>, grid, block, 0, s, D, tiles);
+  else if (dim_max == 2) hipLaunchKernelGGL(nll_grad_contract_batched_kernel<2>, grid, block, 0, s, D, tiles);
+  else if (dim_max == 3) hipLaunchKernelGGL(nll_grad_contract_batched_kernel<3>, grid, block, 0, s, D, tiles);
+  else if (dim_max == 4) hipLaunchKernelGGL(nll_grad_contract_batched_kernel<4>, grid, block, 0, s, D, tiles);
+  else hipLaunchKernelGGL(nll_grad_contract_batched_kernel<8>, grid, block, 0, s, D, tiles);
 }
 
 // ---- leave-one-out terms -----------------------------------------------------------------------------------------
@@ -512,6 +591,244 @@ int agp_loo_nll_gradient(agp_context *c, const agp_kernel *k, const agp_features
         ctx->stage_ms[7] = elapsed(ctx->stage_ev[6], ctx->stage_ev[7]);
       }
     }
+  }
+  return AGP_OK;
+}
+
+// ---- agp_nll_gradient for `count` problems of one size in lock step ---------------------------------------------
+// The steps of agp_nll_gradient with blockIdx.y = problem: one batched Gram, factor_lower_batched (or its look-ahead form,
+// as agp_fit_create_batch chooses), z_b^T z_b, alpha_b, R_b = L_b^-1 into a second slab, K_b^-1 = R_b^T R_b over L_b,
+// the contraction (grid x = tile, y = problem, z = slot group) and the reduction.  Workspace: the A and R slabs
+// (2 lda n doubles per problem) plus the tile images (stride_I) and O(n) vectors per problem.
+int agp_nll_gradient_batch(agp_context *c, int count, const agp_kernel *const *kernels, const agp_features *const *features,
+                           const double *y, int64_t ldy, const double *y_var, int64_t ldv, const int *n_slots,
+                           const agp_gradient_slot *const *slots, const double *const *tangents, int64_t ldt, double *nll,
+                           double *grad_nll, int64_t ldg, double *information, int64_t ldi, int *status) {
+  if (!c || count <= 0 || !kernels || !features || !y || !n_slots || !nll || !status) return AGP_ERR_INVALID_ARGUMENT;
+  if (count > 65535) return AGP_ERR_INVALID_ARGUMENT;  // gridDim.y of the batched launches
+  agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
+  const long long n = features[0] ? features[0]->n : 0;
+  if (n <= 0 || (ldy != 0 && ldy < n) || (y_var && ldv != 0 && ldv < n) || (information && ldi < n)) return AGP_ERR_INVALID_ARGUMENT;
+  // every problem is checked before anything is written or launched
+  int st = AGP_OK, max_slots = 0, dim_max = 1;
+  std::vector<int> ntc((size_t)count, 0);
+  for (int b = 0; b < count; ++b) {
+    if (!kernels[b] || !features[b] || features[b]->n != n || features[b]->location != features[0]->location)
+      return AGP_ERR_INVALID_ARGUMENT;
+    if ((st = validate_features(features[b])) != AGP_OK) return st;
+    const int ns = n_slots[b];
+    if (ns < 0 || ns > AGP_MAX_GRADIENT_SLOTS || (ns > 0 && (!slots || !slots[b]))) return AGP_ERR_INVALID_ARGUMENT;
+    if ((st = check_slots(kernels[b], ns, ns > 0 ? slots[b] : nullptr, &ntc[(size_t)b])) != AGP_OK) return st;
+    if (ntc[(size_t)b] > 0 && (!tangents || !tangents[b] || ldt < n)) return AGP_ERR_INVALID_ARGUMENT;
+    if (ns > max_slots) max_slots = ns;
+    if (features[b]->dim > dim_max) dim_max = features[b]->dim;
+  }
+  if (max_slots > 0 && (!grad_nll || ldg < max_slots)) return AGP_ERR_INVALID_ARGUMENT;
+  const long long tiles = contract_tiles(n), rtr_tiles = ((n + GT - 1) / GT) * ((n + GT - 1) / GT + 1) / 2;
+  const int groups = (max_slots + GRAD_GROUP - 1) / GRAD_GROUP;
+  if (tiles * CT_THREADS > (long long)UINT_MAX || rtr_tiles * GEMM_THREADS > (long long)UINT_MAX ||
+      tiles * count > (long long)UINT_MAX || rtr_tiles * count > (long long)UINT_MAX)
+    return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+
+  const long long lda = factor_ld(n), nblk = (n + NB - 1) / NB, np2 = round_up(n, 2), cp2 = round_up(count, 2);
+  const long long stride_A = lda * n, stride_I = nblk * (36 * MB * MB);
+  const long long ldgd = round_up(max_slots > 0 ? max_slots : 1, 2);  // device gradient: [count][ldgd]
+  const long long part_per = (long long)groups * tiles * GRAD_GROUP;  // partials per problem
+  const int loc = features[0]->location;
+  const bool lookahead = (double)count * (double)n * (double)n >= 6e7 && n > 2 * NBO;  // as agp_fit_create_batch
+  const bool fused_panels = !lookahead && batched_fused_fits(ctx, n, count);
+  long long tang_elems = 0;
+  if (loc == AGP_HOST)
+    for (int b = 0; b < count; ++b) tang_elems += (long long)ntc[(size_t)b] * np2;
+  const size_t gram_bytes = (gram_batch_table_bytes(count) + 15) / 16 * 16;
+  const size_t desc_bytes = (sizeof(ContractDesc) * (size_t)count + 15) / 16 * 16;
+  // ws_A:   [A slabs | tile images | z / alpha | y_var | logsum | quad | flags (4 ints each) | z slots of the fused panels]
+  // ws_aux: [R slabs | tangent columns | partials | gradient | Gram table | contraction descriptors]
+  const size_t a_elems = (size_t)round_up(count * stride_A, 2) + (size_t)count * (size_t)stride_I + (size_t)count * (size_t)np2 +
+                         (y_var ? (size_t)count * (size_t)np2 : 0) + 4 * (size_t)cp2 + (fused_panels ? (size_t)count * (size_t)np2 : 0);
+  const size_t aux_elems = (size_t)round_up(count * stride_A, 2) + (size_t)tang_elems + (size_t)count * (size_t)part_per +
+                           (size_t)count * (size_t)ldgd + (gram_bytes + desc_bytes) / 8;
+  if ((st = ensure_ws(ctx, &ctx->ws_A, &ctx->ws_A_bytes, sizeof(double) * a_elems)) != AGP_OK) return st;
+  if ((st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, sizeof(double) * aux_elems)) != AGP_OK) return st;
+  double *A = ctx->ws_A, *invd = A + round_up(count * stride_A, 2), *z = invd + (size_t)count * (size_t)stride_I;
+  double *yvar_d = y_var ? z + (size_t)count * (size_t)np2 : nullptr;
+  double *logsum = z + (size_t)count * (size_t)np2 * (y_var ? 2 : 1), *quad = logsum + cp2;
+  int *flags = reinterpret_cast<int *>(quad + cp2);
+  double *zpub = fused_panels ? quad + 3 * cp2 : nullptr;
+  double *R = ctx->ws_aux, *tang_d = R + round_up(count * stride_A, 2), *partial = tang_d + tang_elems;
+  double *grad_d = partial + (size_t)count * (size_t)part_per;
+  char *gram_table = reinterpret_cast<char *>(grad_d + (size_t)count * (size_t)ldgd);
+  ContractDesc *desc_d = reinterpret_cast<ContractDesc *>(gram_table + gram_bytes);
+  hipStream_t s = ctx->stream;
+  const bool prof = ctx->profiling;
+  const hipMemcpyKind kind = loc == AGP_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+
+  // targets (and variances): one pitched copy each, or the shared vector once per problem
+  AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(z, sizeof(double) * (size_t)np2, y, sizeof(double) * (size_t)(ldy ? ldy : n), sizeof(double) * (size_t)n,
+                                      (size_t)(ldy ? count : 1), kind, s));
+  if (!ldy)
+    for (int b = 1; b < count; ++b) AGP_HIP_CHECK(ctx, hipMemcpyAsync(z + (size_t)b * (size_t)np2, y, sizeof(double) * (size_t)n, kind, s));
+  if (y_var) {
+    AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(yvar_d, sizeof(double) * (size_t)np2, y_var, sizeof(double) * (size_t)(ldv ? ldv : n),
+                                        sizeof(double) * (size_t)n, (size_t)(ldv ? count : 1), kind, s));
+    if (!ldv)
+      for (int b = 1; b < count; ++b)
+        AGP_HIP_CHECK(ctx, hipMemcpyAsync(yvar_d + (size_t)b * (size_t)np2, y_var, sizeof(double) * (size_t)n, kind, s));
+  }
+  // tangent columns: host columns are copied into the workspace (leading dimension np2), device ones are read in place
+  std::vector<const double *> tcol((size_t)count, nullptr);
+  std::vector<long long> tld((size_t)count, 0);
+  {
+    double *tcur = tang_d;
+    for (int b = 0; b < count; ++b) {
+      if (ntc[(size_t)b] == 0) continue;
+      if (loc == AGP_HOST) {
+        AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(tcur, sizeof(double) * (size_t)np2, tangents[b], sizeof(double) * (size_t)ldt,
+                                            sizeof(double) * (size_t)n, (size_t)ntc[(size_t)b], hipMemcpyHostToDevice, s));
+        tcol[(size_t)b] = tcur;
+        tld[(size_t)b] = np2;
+        tcur += (size_t)ntc[(size_t)b] * (size_t)np2;
+      } else {
+        tcol[(size_t)b] = tangents[b];
+        tld[(size_t)b] = ldt;
+      }
+    }
+  }
+  // features: problems usually share one feature array (parameter vectors of one model): upload it once
+  std::vector<DeviceFeatures> dxs((size_t)count);
+  std::vector<FeatView> views((size_t)count);
+  std::vector<const DevProgram *> hprogs((size_t)count);
+  std::vector<double *> outs((size_t)count);
+  std::vector<const double *> diag((size_t)count, nullptr);
+  std::vector<int *> nanf((size_t)count);
+  {
+    const agp_features *last = nullptr;
+    int last_b = -1;
+    for (int b = 0; b < count; ++b) {
+      const bool same = last && features[b]->coords == last->coords && features[b]->scales == last->scales &&
+                        features[b]->eq_id == last->eq_id && features[b]->dim == last->dim &&
+                        features[b]->n_scale_columns == last->n_scale_columns;
+      if (!same) {
+        if ((st = to_device(ctx, features[b], false, &dxs[(size_t)b])) != AGP_OK) return st;
+        last = features[b];
+        last_b = b;
+      }
+      views[(size_t)b] = dxs[(size_t)(same ? last_b : b)].v;
+      views[(size_t)b].meas = 1;  // as_measurements(features), gp.hpp:288
+      hprogs[(size_t)b] = &kernels[b]->prog;
+      outs[(size_t)b] = A + (size_t)b * (size_t)stride_A;
+      if (y_var) diag[(size_t)b] = yvar_d + (size_t)b * (size_t)np2;
+      nanf[(size_t)b] = flags + 4 * b;
+    }
+  }
+  if (loc == AGP_HOST) AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));  // (pageable sources)
+  {  // log sums, quadratic terms and flags zeroed; the hand-over buffers of the fused panel launches sentinel-filled
+    PrepArgs prep;
+    prep.fill(logsum, 0ull, 4 * cp2);
+    if (zpub) {
+      prep.sentinel(invd, count * stride_I);
+      prep.sentinel(zpub, count * np2);
+    }
+    launch_prep(s, prep);
+  }
+  // the contraction's descriptors, built in the pinned staging area behind the Gram table's
+  char *pinned = static_cast<char *>(host_stage(ctx, gram_bytes + desc_bytes));
+  std::vector<ContractDesc> desc_pageable;
+  ContractDesc *desc_h = nullptr;
+  if (pinned) desc_h = reinterpret_cast<ContractDesc *>(pinned + gram_bytes);
+  else { desc_pageable.resize((size_t)count); desc_h = desc_pageable.data(); }
+  for (int b = 0; b < count; ++b) {
+    ContractDesc &d = desc_h[b];
+    std::memset(static_cast<void *>(&d), 0, sizeof(ContractDesc));
+    d.prog = kernels[b]->prog;
+    d.X = views[(size_t)b];
+    d.C = A + (size_t)b * (size_t)stride_A;
+    d.ldc = lda;
+    d.alpha = z + (size_t)b * (size_t)np2;
+    d.partial = partial + (size_t)b * (size_t)part_per;
+    d.n_slots = n_slots[b];
+    for (int j = 0; j < GRAD_GROUPS_MAX * GRAD_GROUP; ++j) {
+      const bool used = j < n_slots[b];
+      const int node = used ? slots[b][j].node : -1, param = used ? slots[b][j].param : 0;
+      d.slots[j / GRAD_GROUP].node[j % GRAD_GROUP] = node;
+      d.slots[j / GRAD_GROUP].param[j % GRAD_GROUP] = param;
+      d.tang[j] = (used && kernels[b]->prog.nodes[node].op == AGP_OP_SCALING) ? tcol[(size_t)b] + (size_t)param * (size_t)tld[(size_t)b]
+                                                                              : nullptr;
+    }
+  }
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(desc_d, desc_h, sizeof(ContractDesc) * (size_t)count, hipMemcpyHostToDevice, s));
+  if (!pinned) AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));  // (pageable source)
+
+  if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[0], s));
+  bool gram_done = false;
+  if (count > 1)  // all Gram matrices in ONE launch when the trees share a fast path (gram.hip)
+    gram_done = launch_gram_batch(s, count, hprogs.data(), views.data(), outs.data(), lda, y_var ? diag.data() : nullptr, nanf.data(),
+                                  gram_table, pinned);
+  for (int b = 0; b < count && !gram_done; ++b) {
+    const DevProgram *dprog = nullptr;
+    if ((st = device_program(ctx, kernels[b], &dprog)) != AGP_OK) return st;
+    launch_gram(s, dprog, views[(size_t)b], views[(size_t)b], true, true, outs[(size_t)b], lda, diag[(size_t)b], nanf[(size_t)b],
+                hprogs[(size_t)b]);
+  }
+  if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[1], s));
+  if (lookahead)
+    factor_lower_batched_lookahead(ctx, A, stride_A, n, lda, invd, stride_I, z, np2, count, flags, logsum, 4);
+  else
+    factor_lower_batched(s, A, stride_A, n, lda, invd, stride_I, z, np2, count, flags, logsum, 4, zpub, np2);
+  if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[2], s));
+  // y^T K^-1 y = z^T z, alpha = L^-T z in place, R = L^-1 (triangular right-hand side) into the second slab.  A failed
+  // problem runs on through here on whatever its factor holds: every launch below has fixed trip counts and none waits
+  // on another workgroup's data, so it costs nothing but its own (discarded) results.
+  launch_coldot(s, z, np2, z, np2, n, count, quad, -1.0, nullptr);
+  backward_solve_vec_batched(s, A, stride_A, n, lda, invd, stride_I, z, np2, count);
+  launch_set_identity_batched(s, R, lda, stride_A, n, count);
+  forward_solve_mat_batched(s, A, stride_A, n, lda, invd, stride_I, R, stride_A, n, lda, /*rhs_lower=*/true, count);
+  if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[3], s));
+  launch_rtr_lower_batched(s, R, lda, stride_A, n, A, lda, stride_A, count);  // K_b^-1 over L_b
+  if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[4], s));
+  if (groups > 0) {
+    launch_contract_batched(s, dim_max, desc_d, tiles, count, groups);
+    hipLaunchKernelGGL(nll_grad_reduce_batched_kernel, dim3((unsigned)(groups * GRAD_GROUP), (unsigned)count), dim3(256), 0, s, desc_d,
+                       tiles, 0.5, grad_d, ldgd);
+  }
+  if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[5], s));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  // [logsum | quad | flags], the gradients and (when asked for) every alpha: three transfers, one synchronisation
+  std::vector<double> h_head(4 * (size_t)cp2);
+  std::vector<double> h_grad(max_slots > 0 ? (size_t)count * (size_t)ldgd : 0);
+  std::vector<double> h_alpha(information ? (size_t)count * (size_t)n : 0);
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(h_head.data(), logsum, sizeof(double) * h_head.size(), hipMemcpyDeviceToHost, s));
+  if (max_slots > 0) AGP_HIP_CHECK(ctx, hipMemcpyAsync(h_grad.data(), grad_d, sizeof(double) * h_grad.size(), hipMemcpyDeviceToHost, s));
+  if (information)
+    AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(h_alpha.data(), sizeof(double) * (size_t)n, z, sizeof(double) * (size_t)np2, sizeof(double) * (size_t)n,
+                                        (size_t)count, hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  const int *h_flags = reinterpret_cast<const int *>(h_head.data() + 2 * cp2);
+  for (int b = 0; b < count; ++b)
+    if (h_flags[4 * b + 2]) {  // a hand-over of the fused panel launches timed out (its producer died)
+      ctx->last_error = "batched factorisation: hand-over timed out";
+      return AGP_ERR_HIP;
+    }
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  for (int b = 0; b < count; ++b) {
+    const int *fl = h_flags + 4 * b;
+    status[b] = fl[0] ? AGP_ERR_NAN_INPUT : (fl[1] ? AGP_ERR_NOT_POSITIVE_DEFINITE : AGP_OK);
+    const bool ok = status[b] == AGP_OK;
+    nll[b] = ok ? 0.5 * (2. * h_head[(size_t)b] + h_head[(size_t)cp2 + (size_t)b] + (double)n * std::log(2 * M_PI))  // likelihood.hpp:46
+                : nan;
+    for (int j = 0; j < n_slots[b]; ++j) grad_nll[(size_t)b * (size_t)ldg + (size_t)j] = ok ? h_grad[(size_t)b * (size_t)ldgd + (size_t)j] : nan;
+    if (information && ok)
+      std::memcpy(information + (size_t)b * (size_t)ldi, h_alpha.data() + (size_t)b * (size_t)n, sizeof(double) * (size_t)n);
+  }
+  if (prof) {
+    for (int k : {3, 4, 5, 8, 9}) ctx->stage_ms[k] = 0.;
+    ctx->stage_ms[0] = elapsed(ctx->stage_ev[0], ctx->stage_ev[1]);
+    ctx->stage_ms[1] = elapsed(ctx->stage_ev[1], ctx->stage_ev[2]);
+    ctx->stage_ms[2] = elapsed(ctx->stage_ev[2], ctx->stage_ev[3]);
+    ctx->stage_ms[6] = elapsed(ctx->stage_ev[3], ctx->stage_ev[4]);
+    ctx->stage_ms[7] = elapsed(ctx->stage_ev[4], ctx->stage_ev[5]);
   }
   return AGP_OK;
 }

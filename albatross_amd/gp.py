@@ -1073,15 +1073,8 @@ class GaussianProcessRegression:
         compute_gradient (tune/finite_difference.hpp:20-94) and ModelTuner (tune/tune.hpp:151-161) make one
         after the other.  parameter_sets: iterable of {name: value} overrides of the current parameters.
         A parameter vector whose covariance is not positive definite gives NaN."""
-        import copy
         ctx = self._ctx()
-        models = []
-        for overrides in parameter_sets:
-            m = copy.copy(self)
-            m.covariance_function_ = copy.deepcopy(self.covariance_function_)
-            m.mean_function_ = copy.deepcopy(self.mean_function_)
-            m.set_param_values(overrides)
-            models.append(m)
+        models = self._override_copies(parameter_sets)
         count = len(models)
         if count == 0:
             return np.zeros(0)
@@ -1112,6 +1105,18 @@ class GaussianProcessRegression:
                 ctx._lib.agp_kernel_destroy(kh)
         return -out
 
+    def _override_copies(self, parameter_sets):
+        """one copy of the model per {name: value} override dict, with its own covariance and mean functions"""
+        import copy
+        models = []
+        for overrides in parameter_sets:
+            m = copy.copy(self)
+            m.covariance_function_ = copy.deepcopy(self.covariance_function_)
+            m.mean_function_ = copy.deepcopy(self.mean_function_)
+            m.set_param_values(overrides)
+            models.append(m)
+        return models
+
     def log_likelihood(self, dataset):
         """gp.hpp:442-451 (without priors: the parameter-prior subsystem is out of scope).  Like the reference, the
         covariance is covariance_function_(measurement_features) ALONE: dataset.targets.covariance is not added."""
@@ -1133,30 +1138,18 @@ class GaussianProcessRegression:
     def _slot_gradient(self, entry, dataset, with_variance):
         """One call of a gradient entry (agp_nll_gradient / agp_loo_nll_gradient) over the slot table of the covariance
         function: (value, slots, per-slot gradient, the n-vector the entry returns, the flattened features)"""
-        if has_linear_combinations(dataset.features):
-            raise NotImplementedError(f"{entry}: LinearCombination features go through the dense path")
+        p = _gradient_problem(self, dataset, entry)
         ctx = self._ctx()
-        cov = self.covariance_function_
-        fs = cov.features(_values_of(dataset.features))
-        y, yv = self._targets(fs, dataset.targets)
-        slots, columns = cov.param_slots()
-        if len(slots) > capi.MAX_GRADIENT_SLOTS:
-            raise ValueError(f"more than {capi.MAX_GRADIENT_SLOTS} covariance parameter slots")
-        n = fs.n
-        tangents = None
-        if columns:
-            tangents = np.empty((n, len(columns)), order="F")
-            for c, (fn, name) in enumerate(columns):
-                tangents[:, c] = fn.derivative(fs.coords, name)
-        table = (capi.GradientSlot * max(1, len(slots)))(*[capi.GradientSlot(node, p) for node, p, _ in slots])
-        s = fs.as_struct()
+        n = p.fs.n
+        s = p.fs.as_struct()
         value = C.c_double()
-        grad = np.zeros(len(slots))
+        grad = np.zeros(len(p.slots))
         vec = np.empty(n)
-        ctx._check(getattr(ctx._lib, entry)(ctx._h, ctx.kernel(cov), C.byref(s), _ptr(y), _ptr(yv) if with_variance else None,
-                                            len(slots), table, _ptr(tangents), n, C.byref(value), _ptr(grad), _ptr(vec)),
+        ctx._check(getattr(ctx._lib, entry)(ctx._h, ctx.kernel(self.covariance_function_), C.byref(s), _ptr(p.y),
+                                            _ptr(p.yv) if with_variance else None, len(p.slots), p.table, _ptr(p.tangents), n,
+                                            C.byref(value), _ptr(grad), _ptr(vec)),
                    entry)
-        return value.value, slots, grad, vec, fs
+        return value.value, p.slots, grad, vec, p.fs
 
     def _mean_tangent(self, fs, name):
         """d mu / d name at the features: a central difference of the mean function on the host"""
@@ -1176,13 +1169,33 @@ class GaussianProcessRegression:
         go through the scaling function's d f / d name at the features (ScalingFunction.derivative), mean-function
         parameters through (d mu / d name)^T alpha with a central difference of the mean function on the host."""
         nll, slots, grad_nll, alpha, fs = self._slot_gradient("agp_nll_gradient", dataset, with_variance=False)
+        return -nll, self._log_likelihood_gradient_dict(slots, grad_nll, alpha, fs)
+
+    def _log_likelihood_gradient_dict(self, slots, grad_nll, alpha, fs):
+        """{name: d log p / d name} from agp_nll_gradient's per-slot values and alpha (slots sharing a name summed)"""
         grad = {name: 0. for name in self.get_params()}
         for (_, _, name), g in zip(slots, grad_nll):
             grad[name] -= g
         # y = targets - mu: d log p / d theta = (d mu / d theta)^T alpha
         for name in self.mean_function_.get_params():
             grad[name] += float(self._mean_tangent(fs, name) @ alpha)
-        return -nll, grad
+        return grad
+
+    def log_likelihood_gradients(self, dataset, parameter_sets):
+        """log_likelihood_gradient(dataset) for several parameter vectors at once (agp_nll_gradient_batch): the gradient
+        counterpart of log_likelihoods, for the tuner's small problems where one exact gradient is a chain of small
+        launches.  parameter_sets: iterable of {name: value} overrides of the current parameters (one model copy each,
+        as log_likelihoods makes them).  Returns (log_likelihoods: array[count], gradients: [{name: value}] with every
+        name of get_params()).  Sign, target variance and priors as in log_likelihood_gradient; ScalingTerm tangents
+        are taken per copy, at its own parameters.  A parameter vector whose covariance is not positive definite (or
+        has NaN) gives NaN throughout, not an exception.  fp64 models only."""
+        if self.precision != "fp64":
+            raise ValueError(f"log_likelihood_gradients: fp64 models only, not {self.precision!r}")
+        models = self._override_copies(parameter_sets)
+        if not models:
+            return np.zeros(0), []
+        lls, grads = _log_likelihood_gradients(self._ctx(), models, [dataset] * len(models))
+        return np.asarray(lls), grads
 
     def leave_one_out_likelihood_gradient(self, dataset):
         """(LeaveOneOutLikelihood()(dataset, self), {name: d that / d name}) for every name of get_params(), exact to
@@ -1378,6 +1391,93 @@ def fit_batch(models, datasets):
             pivot = ctx._lib.agp_fit_failed_pivot(fits[b]._h)
             ctx._check(status[b], f"agp_fit_create_batch: problem {b} (pivot {pivot})")
     return [FitModel(m, f) for m, f in zip(models, fits)]
+
+
+class _GradientProblem:
+    """the host side of one gradient problem: flattened features, targets (mean removed) and variances, the slot table
+    of the covariance function (param_slots), its ctypes form and the tangent columns (n x columns, column-major) of
+    its ScalingTerm slots at the function's current parameters (None without such slots)"""
+
+    def __init__(self, fs, y, yv, slots, table, tangents):
+        self.fs, self.y, self.yv, self.slots, self.table, self.tangents = fs, y, yv, slots, table, tangents
+
+
+def _gradient_problem(model, dataset, entry="agp_nll_gradient"):
+    """_GradientProblem of `model` on `dataset`: what agp_nll_gradient, agp_loo_nll_gradient and agp_nll_gradient_batch
+    are given for it"""
+    if has_linear_combinations(dataset.features):
+        raise NotImplementedError(f"{entry}: LinearCombination features go through the dense path")
+    cov = model.covariance_function_
+    fs = cov.features(_values_of(dataset.features))
+    y, yv = model._targets(fs, dataset.targets)
+    slots, columns = cov.param_slots()
+    if len(slots) > capi.MAX_GRADIENT_SLOTS:
+        raise ValueError(f"more than {capi.MAX_GRADIENT_SLOTS} covariance parameter slots")
+    tangents = None
+    if columns:
+        tangents = np.empty((fs.n, len(columns)), order="F")
+        for c, (fn, name) in enumerate(columns):
+            tangents[:, c] = fn.derivative(fs.coords, name)
+    table = (capi.GradientSlot * max(1, len(slots)))(*[capi.GradientSlot(node, p) for node, p, _ in slots])
+    return _GradientProblem(fs, y, yv, slots, table, tangents)
+
+
+def _log_likelihood_gradients(ctx, models, datasets):
+    """one agp_nll_gradient_batch call over models[b] on datasets[b]: ([log p_b], [{name: d log p_b / d name}]), NaN
+    throughout for a problem whose covariance has NaN or is not positive definite"""
+    count = len(models)
+    for m, ds in zip(models, datasets):
+        if m.precision != "fp64" or m._ctx() is not ctx:
+            raise ValueError("log_likelihood_gradient_batch: fp64 models on one context")
+    problems = [_gradient_problem(m, ds, "agp_nll_gradient_batch") for m, ds in zip(models, datasets)]
+    n = problems[0].fs.n
+    if any(p.fs.n != n for p in problems):
+        raise ValueError("log_likelihood_gradient_batch: every dataset must have the same number of points")
+    structs = [p.fs.as_struct() for p in problems]
+    Y = np.asfortranarray(np.stack([p.y for p in problems], axis=1))
+    ldg = max(1, max(len(p.slots) for p in problems))
+    nll = np.empty(count)
+    grad = np.zeros((count, ldg))   # column b of the ldg x count array: row b here
+    alpha = np.empty((count, n))    # likewise, ldi = n
+    status = (C.c_int * count)()
+    n_slots = (C.c_int * count)(*[len(p.slots) for p in problems])
+    tables = (C.c_void_p * count)(*[C.addressof(p.table) for p in problems])
+    tangents = (C.c_void_p * count)(*[None if p.tangents is None else p.tangents.ctypes.data for p in problems])
+    handles = []
+    try:
+        for m in models:  # private handles: the context's small kernel cache may evict while the batch is assembled
+            handles.append(ctx.private_kernel(m.covariance_function_))
+        kernels = (C.c_void_p * count)(*handles)
+        fptrs = (C.c_void_p * count)(*[C.addressof(st) for st in structs])
+        # log_likelihood ignores the target variance (gp.hpp:442-451): y_var = NULL
+        ctx._check(ctx._lib.agp_nll_gradient_batch(ctx._h, count, kernels, fptrs, _ptr(Y), n, None, 0, n_slots, tables, tangents,
+                                                   n, _ptr(nll), _ptr(grad), ldg, _ptr(alpha), n, status),
+                   "agp_nll_gradient_batch")
+    finally:
+        for kh in handles:
+            ctx._lib.agp_kernel_destroy(kh)
+    lls, grads = [], []
+    for b, (m, p) in enumerate(zip(models, problems)):
+        if status[b] != capi.AGP_OK:
+            lls.append(float("nan"))
+            grads.append({name: float("nan") for name in m.get_params()})
+            continue
+        lls.append(-nll[b])
+        grads.append(m._log_likelihood_gradient_dict(p.slots, grad[b, :len(p.slots)], alpha[b], p.fs))
+    return lls, grads
+
+
+def log_likelihood_gradient_batch(models, datasets):
+    """`models[b].log_likelihood_gradient(datasets[b])` for several INDEPENDENT problems of one size in one call
+    (agp_nll_gradient_batch): the gradient counterpart of fit_batch, for multi-start tuning and one model per
+    station / group.  models: fp64 GaussianProcessRegression objects on one context (their covariance trees and feature
+    dimensions may differ); datasets: as many RegressionDatasets with the same number of points.  Returns a list of
+    (log_likelihood, {name: gradient}); a problem whose covariance has NaN or is not positive definite gives NaN
+    throughout instead of raising."""
+    if len(models) != len(datasets) or not models:
+        raise ValueError("log_likelihood_gradient_batch: as many datasets as models, at least one")
+    lls, grads = _log_likelihood_gradients(models[0]._ctx(), list(models), list(datasets))
+    return list(zip(lls, grads))
 
 
 def gp_from_covariance(covariance_function, model_name="gaussian_process_regression", context=None):

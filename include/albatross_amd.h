@@ -287,6 +287,41 @@ AGP_API int agp_nll_gradient(agp_context *ctx, const agp_kernel *k, const agp_fe
                      double *nll, double *grad_nll,
                      double *information);
 
+/* agp_nll_gradient for `count` problems of one size in lock step: problem b computes exactly what agp_nll_gradient computes
+ * for kernels[b], features[b] and column b of y / y_var, with its own slot table (same slot semantics: a leaf node and a
+ * params[] index, or a tangent column for an AGP_OP_SCALING leaf; gradients with respect to the raw value).  The
+ * regime of the tuner and of many independent small models (N of a few hundred to a few thousand), where one gradient
+ * is a serial chain of small launches: the batch runs each step once for all problems (blockIdx.y = problem).
+ *   kernels[b], features[b]   covariance function and features of problem b: all n equal, all at features[0]->location;
+ *                             dim may differ between problems
+ *   y, ldy                    targets, n x count column-major at that location (ldy = 0: one vector shared by all)
+ *   y_var, ldv                target variances likewise (added to the diagonal), or NULL
+ *   n_slots[b], slots[b]      problem b's slot table (0..AGP_MAX_GRADIENT_SLOTS slots; slots[b] may be NULL if it has none)
+ *   tangents[b], ldt          problem b's tangent columns at that location (ldt >= n), NULL if it has no AGP_OP_SCALING slot
+ *   nll[b]                    the negative log-likelihood (host)
+ *   grad_nll, ldg             ldg x count (host): column b holds problem b's n_slots[b] values; ldg >= max n_slots[b]
+ *   information, ldi          n x count (host, alpha_b), or NULL
+ *   status[b]                 AGP_OK / AGP_ERR_NAN_INPUT / AGP_ERR_NOT_POSITIVE_DEFINITE (host)
+ * A failed problem gets nll[b] = NaN and a NaN column of grad_nll (the tuner's NaN objective, tune.hpp:163-165); its
+ * column of information is left untouched and the rest of the batch is unaffected.  A malformed argument in any problem
+ * (count <= 0, n mismatch, mixed locations, a bad slot, ldg < max n_slots, missing tangents or ldt < n where they are
+ * needed) makes the call return AGP_ERR_INVALID_ARGUMENT and write nothing.  No float atomics, fixed-order reductions:
+ * two identical calls are bit-identical, and no problem's arithmetic depends on its position or its neighbours.
+ * Workspace: about count * (2 lda n + tile images) doubles (the A slab and the R slab of every problem, lda ~ n) -
+ * size batches from that.  With profiling on, agp_last_stage_ms reports whole-batch times: 0 gram, 1 factor, 2 alpha
+ * and R = L^-1, 6 R^T R, 7 the contraction. */
+AGP_API int agp_nll_gradient_batch(agp_context *ctx, int count,
+                                   const agp_kernel *const *kernels, const agp_features *const *features,
+                                   const double *y, int64_t ldy,
+                                   const double *y_var, int64_t ldv,
+                                   const int *n_slots,
+                                   const agp_gradient_slot *const *slots,
+                                   const double *const *tangents, int64_t ldt,
+                                   double *nll,
+                                   double *grad_nll, int64_t ldg,
+                                   double *information, int64_t ldi,
+                                   int *status);
+
 /* The leave-one-out likelihood metric, LeaveOneOutLikelihood<>()(dataset, model) (evaluation/model_metrics.hpp:59-72,
  * without the prior term), and its exact gradient with respect to covariance parameters.  Per point i, with
  * K = cov(x, x) + diag(y_var), C = K^-1, alpha = C y, c_i = C_ii and s_i = y_var[i] (0 if y_var is NULL):

@@ -26,6 +26,7 @@
 #include <cstdint>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -1759,11 +1760,67 @@ class GaussianProcessRegression {
     std::vector<std::string> names;
     std::vector<double> grad, alpha;
     const double nll = slot_gradient(agp_nll_gradient, "agp_nll_gradient", dataset, nullptr, &names, &grad, &alpha);
-    LogLikelihoodGradient out{-nll, {}};
-    for (const auto &kv : get_params()) out.gradient[kv.first] = 0.;
-    for (std::size_t s = 0; s < names.size(); ++s) out.gradient[names[s]] -= grad[s];
-    for (const auto &kv : mean_function_.get_params())  // y = targets - mu: d log p / d theta = (d mu / d theta)^T alpha
-      out.gradient[kv.first] += mean_tangent_dot(dataset, kv.first, kv.second, alpha);
+    return gradient_of_log_likelihood(dataset, nll, names, grad.data(), alpha);
+  }
+
+  // log_likelihood_gradient(dataset) for several parameter vectors in ONE batched device pass (agp_nll_gradient_batch),
+  // one model copy per entry as log_likelihoods makes them.  A parameter vector whose covariance is not positive
+  // definite (or has NaN) gives NaN for the value and every gradient entry.
+  template <typename FeatureType>
+  std::vector<LogLikelihoodGradient> log_likelihood_gradients(const RegressionDataset<FeatureType> &dataset,
+                                                             const std::vector<ParameterStore> &parameter_sets) const {
+    const std::size_t count = parameter_sets.size(), n = dataset.features.size();
+    std::vector<LogLikelihoodGradient> out;
+    if (count == 0) return out;
+    auto ctx = detail::default_context();
+    std::vector<GaussianProcessRegression> models(count, *this);
+    std::vector<std::unique_ptr<detail::KernelHolder>> kernels;
+    std::vector<detail::Flat> flats(count);
+    std::vector<const agp_kernel *> kptr(count);
+    std::vector<const agp_features *> fptr(count);
+    std::vector<double> Y(n * count);
+    std::vector<std::vector<std::string>> names(count);
+    std::vector<std::vector<agp_gradient_slot>> slots(count);
+    std::vector<std::vector<double>> tangents(count);
+    std::vector<int> n_slots(count);
+    std::size_t ldg = 1;
+    for (std::size_t b = 0; b < count; ++b) {
+      models[b].set_param_values(parameter_sets[b]);
+      kernels.emplace_back(new detail::KernelHolder(models[b].covariance_function_.program()));
+      flats[b] = detail::flatten(models[b].covariance_function_, dataset.features);
+      kptr[b] = kernels.back()->k;
+      const Vector y = models[b].deviation(dataset);
+      for (std::size_t i = 0; i < n; ++i) Y[b * n + i] = y[i];
+      models[b].slot_table(dataset, &names[b], &slots[b], &tangents[b]);
+      n_slots[b] = static_cast<int>(slots[b].size());
+      ldg = std::max(ldg, slots[b].size());
+    }
+    std::vector<const agp_gradient_slot *> sptr(count);
+    std::vector<const double *> tptr(count);
+    for (std::size_t b = 0; b < count; ++b) {  // after the vectors stopped moving
+      fptr[b] = &flats[b].view;
+      sptr[b] = slots[b].empty() ? nullptr : slots[b].data();
+      tptr[b] = tangents[b].empty() ? nullptr : tangents[b].data();
+    }
+    std::vector<double> nll(count), grad(ldg * count), alpha(n * count);
+    std::vector<int> status(count);
+    // like log_likelihood: the target variance is NOT part of the covariance (gp.hpp:442-451)
+    detail::check(agp_nll_gradient_batch(ctx->ctx, static_cast<int>(count), kptr.data(), fptr.data(), Y.data(),
+                                         static_cast<std::int64_t>(n), nullptr, 0, n_slots.data(), sptr.data(), tptr.data(),
+                                         static_cast<std::int64_t>(n), nll.data(), grad.data(), static_cast<std::int64_t>(ldg),
+                                         alpha.data(), static_cast<std::int64_t>(n), status.data()),
+                  ctx->ctx, "agp_nll_gradient_batch");
+    for (std::size_t b = 0; b < count; ++b) {
+      if (status[b] != AGP_OK) {
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        LogLikelihoodGradient r{nan, {}};
+        for (const auto &kv : models[b].get_params()) r.gradient[kv.first] = nan;
+        out.push_back(r);
+        continue;
+      }
+      const std::vector<double> a(alpha.begin() + static_cast<std::ptrdiff_t>(b * n), alpha.begin() + static_cast<std::ptrdiff_t>((b + 1) * n));
+      out.push_back(models[b].gradient_of_log_likelihood(dataset, nll[b], names[b], grad.data() + b * ldg, a));
+    }
     return out;
   }
 
@@ -1832,40 +1889,62 @@ class GaussianProcessRegression {
     return y;
   }
 
+  // The slot table of the covariance function at the dataset's features: names[s] / slots[s] per slot, and the tangent
+  // columns of its ScalingTerm slots (n x columns, column-major; empty without such slots)
+  template <typename FeatureType>
+  void slot_table(const RegressionDataset<FeatureType> &dataset, std::vector<std::string> *names,
+                  std::vector<agp_gradient_slot> *slots, std::vector<double> *tangents) const {
+    using X = typename detail::unwrap<FeatureType>::type;
+    const std::size_t n = dataset.features.size();
+    std::vector<detail::GradSlot<X>> rows;
+    int node = 0;
+    covariance_function_.template emit_slots<X>(rows, node);
+    int columns = 0;
+    for (auto &r : rows) {
+      if (r.tangent) {
+        r.slot.param = columns++;
+        tangents->resize(n * static_cast<std::size_t>(columns));
+        for (std::size_t i = 0; i < n; ++i)
+          (*tangents)[static_cast<std::size_t>(r.slot.param) * n + i] = r.tangent(detail::unwrap<FeatureType>::get(dataset.features[i]));
+      }
+      slots->push_back(r.slot);
+      names->push_back(r.name);
+    }
+  }
+
   // One call of a gradient entry (agp_nll_gradient / agp_loo_nll_gradient) over the slot table of the covariance
   // function: returns its value; names[s] / grad[s] per slot, vec the n values it returns (alpha / mean weights).
   template <typename FeatureType, typename Entry>
   double slot_gradient(Entry entry, const char *what, const RegressionDataset<FeatureType> &dataset, const double *yvar,
                        std::vector<std::string> *names, std::vector<double> *grad, std::vector<double> *vec) const {
-    using X = typename detail::unwrap<FeatureType>::type;
     auto ctx = detail::default_context();
     detail::KernelHolder k(covariance_function_.program());
     detail::Flat f = detail::flatten(covariance_function_, dataset.features);
     const std::size_t n = dataset.features.size();
-    std::vector<detail::GradSlot<X>> rows;
-    int node = 0;
-    covariance_function_.template emit_slots<X>(rows, node);
     std::vector<agp_gradient_slot> slots;
     std::vector<double> tangents;
-    int columns = 0;
-    for (auto &r : rows) {
-      if (r.tangent) {
-        r.slot.param = columns++;
-        tangents.resize(n * static_cast<std::size_t>(columns));
-        for (std::size_t i = 0; i < n; ++i)
-          tangents[static_cast<std::size_t>(r.slot.param) * n + i] = r.tangent(detail::unwrap<FeatureType>::get(dataset.features[i]));
-      }
-      slots.push_back(r.slot);
-      names->push_back(r.name);
-    }
+    slot_table(dataset, names, &slots, &tangents);
     const Vector y = deviation(dataset);
     double value = 0.;
     grad->assign(slots.size(), 0.);
     vec->assign(n, 0.);
     detail::check(entry(ctx->ctx, k.k, &f.view, y.data(), yvar, static_cast<int>(slots.size()), slots.data(),
-                        columns > 0 ? tangents.data() : nullptr, static_cast<std::int64_t>(n), &value, grad->data(), vec->data()),
+                        tangents.empty() ? nullptr : tangents.data(), static_cast<std::int64_t>(n), &value, grad->data(), vec->data()),
                   ctx->ctx, what);
     return value;
+  }
+
+  // {name: d log p / d name} from agp_nll_gradient's per-slot values (slots sharing a name summed) and alpha
+  template <typename FeatureType>
+  LogLikelihoodGradient gradient_of_log_likelihood(const RegressionDataset<FeatureType> &dataset, double nll,
+                                                   const std::vector<std::string> &names, const double *grad,
+                                                   const std::vector<double> &alpha) const {
+    LogLikelihoodGradient out{-nll, {}};
+    for (const auto &kv : get_params()) out.gradient[kv.first] = 0.;
+    for (std::size_t s = 0; s < names.size(); ++s) out.gradient[names[s]] -= grad[s];
+    for (const auto &kv : mean_function_.get_params())  // y = targets - mu: d log p / d theta = (d mu / d theta)^T alpha
+      out.gradient[kv.first] += mean_tangent_dot(dataset, kv.first, kv.second, alpha);
+    return out;
   }
 
   // (d mu / d name)^T w, d mu / d name by a central difference of the mean function with h = 1e-6 max(1, |value|)
