@@ -151,6 +151,9 @@ int copy_out(agp_context *ctx, const double *dev, long long count, double *dst, 
 int copy_out_2d(agp_context *ctx, const double *dev, long long ld_dev, long long rows, long long cols, double *dst,
                 long long ld_dst, int location);
 int status_from_flags(const agp_context *ctx);
+// slot table of a gradient entry (gradient.hip): every slot a leaf node and a parameter the leaf has; n_tangent_columns:
+// the highest AGP_OP_SCALING tangent column + 1
+int check_slots(const agp_kernel *k, int n_slots, const agp_gradient_slot *slots, int *n_tangent_columns);
 namespace agp {
 // Gram + LL^T + forward substitution of y exactly as agp_nll makes them (api.hip: build_and_factor); on return the stream
 // is synchronised and ctx->h_flags / h_scalars hold the status and the log determinant

@@ -361,7 +361,7 @@ void launch_gtg_lower(hipStream_t s, const double *G, long long ldg, long long n
 using namespace agp;
 
 // ---- slot validation: a leaf node and a parameter index the leaf has ----------------------------------------------
-static int check_slots(const agp_kernel *k, int n_slots, const agp_gradient_slot *slots, int *n_tangent_columns) {
+int check_slots(const agp_kernel *k, int n_slots, const agp_gradient_slot *slots, int *n_tangent_columns) {
   int ntc = 0;
   for (int s = 0; s < n_slots; ++s) {
     const int node = slots[s].node, param = slots[s].param;

@@ -9,6 +9,7 @@
 #include <thread>
 
 #include "api_internal.h"
+#include "sparse_internal.h"
 
 using namespace agp;
 
@@ -26,50 +27,12 @@ using namespace agp;
 // algorithm to ~1e-8 even with cond(K_uu) ~ 1e7.  K_uu and every block of A use LL^T as well.
 // L_acc = L1 L2 (the transpose of the reference's R P^T, up to an orthogonal factor) is kept for
 // FitModel::update.
-struct agp_sparse_fit {
-  agp_context *ctx = nullptr;
-  long long m = 0;
-  std::shared_ptr<DeviceFeatures> u;   // train_features = inducing points (shared with updated fits)
-  std::shared_ptr<agp_fit> kuu;        // train_covariance = factor of K_uu + inducing_nugget I
-  agp_fit *sigma = nullptr;            // L1
-  agp_fit *sigma2 = nullptr;           // L2
-  double *Lacc = nullptr;              // L1 L2, m x ldm, zero above the diagonal
-  double *v = nullptr;                 // information (m)
-  double nll = 0.;
-  // "pivoted form" of a fit made by agp_sparse_fit_from_prediction (rebase_inducing_points) or by an update of one:
-  // the reference's own representation, for covariances that are singular to working precision.
-  std::shared_ptr<agp_ldlt> kz;        // train_covariance as a pivoted L D L^T: K_zz WITHOUT nugget after fit_from_prediction
-                                       // (:416-418), K_uu + inducing nugget after a pivoted fit (:676-679); else kuu
-  std::shared_ptr<agp_ldlt> kp;        // pivoted L D L^T of K_uu + inducing nugget for P = K_uu^-1/2 K_uf of an update, when
-                                       // the LL^T of that matrix (kuu) does not exist
-  double *R = nullptr;                 // m x round_up(m, 2), upper triangular: Sigma^-1 = P R^T R P^T; else sigma/sigma2
-  long long *perm = nullptr;           // P: perm[i] = original index of the column at position i
-  long long rank = -1;                 // numerical_rank of the QR (-1: not a pivoted fit)
-  double inducing_nugget = 0.;         // the nugget an update adds to K_uu for P = K_uu^-1/2 K_uf (:674-685)
-};
-
 namespace agp {
 int comm_all_reduce_device(agp_context *ctx, agp_comm *comm, double *dev, long long count, int op);  // shard_hip.hip
 int comm_wait_stream(agp_context *ctx, hipStream_t s);                                               // shard_hip.hip
 }
 
 namespace {
-
-struct SparseScratch {
-  double *Kuf = nullptr, *Pbuf = nullptr, *M0 = nullptr, *T = nullptr, *vecs = nullptr, *partial = nullptr,
-         *Ag = nullptr, *Pimg = nullptr, *Q1T = nullptr, *Winv = nullptr;
-  std::vector<agp_fit *> blocks;
-  DeviceFeatures dx;
-  // Kuf, Pbuf / Q1T (one region: P is dead before Q1^T is formed) and the split-K slabs live in ctx->pool_sparse
-  double *slabs = nullptr, *pads = nullptr;
-  long long slab_count = 0;
-  ~SparseScratch() {
-    (void)dev_free(M0); (void)dev_free(T); (void)dev_free(vecs);
-    (void)dev_free(partial); (void)dev_free(Ag); (void)dev_free(Pimg); (void)dev_free(Winv);
-    for (agp_fit *b : blocks) agp_fit_destroy(b);
-    dx.release();
-  }
-};
 
 FeatView feature_rows(const FeatView &v, long long o, long long cnt) {
   FeatView r = v;
@@ -79,21 +42,6 @@ FeatView feature_rows(const FeatView &v, long long o, long long cnt) {
   if (v.scales) r.scales = v.scales + o * v.nsc;
   return r;
 }
-
-// AGP_SPARSE_TIMING=1: wall time of every stage (with a stream synchronisation at each boundary) on stderr
-struct StageTimer {
-  hipStream_t s;
-  bool on;
-  std::chrono::steady_clock::time_point last;
-  explicit StageTimer(hipStream_t st, bool enabled) : s(st), on(enabled), last(std::chrono::steady_clock::now()) {}
-  void operator()(const char *name) {
-    if (!on) return;
-    (void)hipStreamSynchronize(s);
-    const auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "  [sparse fit] %-28s %8.2f ms\n", name, std::chrono::duration<double, std::milli>(now - last).count());
-    last = now;
-  }
-};
 
 #define SPX_HIP(expr)                                                                    \
   do {                                                                                   \
@@ -132,20 +80,26 @@ __global__ __launch_bounds__(256) void sum_slabs_kernel(double *C, const double 
   C[i] += acc;
 }
 
-static void syrk_over_observations(hipStream_t s, SparseScratch &w, double *C, long long ldc, const double *W, long long ldw,
-                                   long long m, long long n) {
+// (two operands: C -= A B^T, lower tiles; the fit's products have A = B = W, the gradient's W_uu has not)
+static void product_over_observations(hipStream_t s, SparseScratch &w, double *C, long long ldc, const double *A, const double *B,
+                                      long long ldw, long long m, long long n) {
   const long long S = w.slab_count;
   const long long per = S > 1 ? n / S : 0;
   if (S <= 1 || !w.slabs || per <= 0) {
-    launch_gemm_nt_sub(s, C, ldc, W, ldw, false, W, ldw, false, m, m, n, true);
+    launch_gemm_nt_sub(s, C, ldc, A, ldw, false, B, ldw, false, m, m, n, true);
     return;
   }
   const long long elems = ldc * m;
   (void)hipMemsetAsync(w.slabs, 0, sizeof(double) * (size_t)elems * (size_t)S, s);
-  launch_gemm_nt_sub_batched(s, w.slabs, ldc, elems, W, ldw, false, per * ldw, W, ldw, false, per * ldw, m, m, per, true, S);
+  launch_gemm_nt_sub_batched(s, w.slabs, ldc, elems, A, ldw, false, per * ldw, B, ldw, false, per * ldw, m, m, per, true, S);
   const long long rest = n - per * S;
-  if (rest > 0) launch_gemm_nt_sub(s, C, ldc, W + (size_t)(per * S) * (size_t)ldw, ldw, false, W + (size_t)(per * S) * (size_t)ldw, ldw, false, m, m, rest, true);
+  if (rest > 0) launch_gemm_nt_sub(s, C, ldc, A + (size_t)(per * S) * (size_t)ldw, ldw, false, B + (size_t)(per * S) * (size_t)ldw, ldw, false, m, m, rest, true);
   hipLaunchKernelGGL(sum_slabs_kernel, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, s, C, w.slabs, elems, S);
+}
+
+static void syrk_over_observations(hipStream_t s, SparseScratch &w, double *C, long long ldc, const double *W, long long ldw,
+                                   long long m, long long n) {
+  product_over_observations(s, w, C, ldc, W, W, ldw, m, n);
 }
 
 // The data-dependent half of compute_internal_components (sparse_gp.hpp:642-704) for one set of
@@ -194,15 +148,15 @@ int sparse_observations(agp_context *ctx, const agp_kernel *k, const DevProgram 
     const bool padded_path = !all_equal && n_groups >= 4 && smax * n_groups <= 3 * n;
     const size_t kuf_e = (size_t)ldk * (size_t)n, pq_e = (size_t)ldk * (size_t)(n + m),
                  slab_e = (size_t)w.slab_count * (size_t)ldm_p * (size_t)m,
-                 pad_e = padded_path ? (size_t)ldk * (size_t)(smax * n_groups) : 0;
+                 pad_e = padded_path ? (size_t)ldk * (size_t)(smax * n_groups) : 0, q_e = w.keep_P ? pq_e : 0;
     if ((st = ensure_ws(ctx, &ctx->pool_sparse, &ctx->pool_sparse_bytes,
-                        sizeof(double) * (kuf_e + pq_e + slab_e + 2 * pad_e))) != AGP_OK)
+                        sizeof(double) * (kuf_e + pq_e + slab_e + 2 * pad_e + q_e))) != AGP_OK)
       return st;
     w.Kuf = ctx->pool_sparse;
     w.Pbuf = w.Kuf + kuf_e;
-    w.Q1T = w.Pbuf;
     w.slabs = w.Pbuf + pq_e;
     w.pads = w.slabs + slab_e;
+    w.Q1T = w.keep_P ? w.pads + 2 * pad_e : w.Pbuf;
   }
   launch_gram(s, dprog, uv, xm, false, false, w.Kuf, ldk, nullptr, nullptr, &k->prog);
   if (kp) {  // P = K_uu_ldlt.sqrt_solve(K_uf) with the pivoted L D L^T (:680-685)
@@ -223,6 +177,7 @@ int sparse_observations(agp_context *ctx, const agp_kernel *k, const DevProgram 
   bool uniform = true;
   for (int64_t g = 0; g < n_groups; ++g) uniform = uniform && (offsets[g + 1] - offsets[g] == smax);
   double log_det_a = 0.;
+  w.layout = uniform ? 0 : ((n_groups >= 4 && smax * n_groups <= 3 * n) ? 1 : 2);
   if (uniform) {
     // All groups have the same size: the blocks advance in LOCK STEP through batched launches
     // (blockIdx.y = group) - a dozen launches for the whole of A instead of ~40 per block, which
@@ -355,7 +310,7 @@ int sparse_observations(agp_context *ctx, const agp_kernel *k, const DevProgram 
       }
     for (int64_t g = 0; g < n_groups; ++g) log_det_a += w.blocks[(size_t)g]->log_det;  // fixed order
   }
-  w.Pbuf = nullptr;  // dead: its region of the pool becomes Q1^T
+  if (!w.keep_P) w.Pbuf = nullptr;  // dead: its region of the pool becomes Q1^T
   stage("blocks of A, W, y_w");
   *yw_out = yw;
   *log_det_a_out = log_det_a;
@@ -687,7 +642,8 @@ static int features_checksum(agp_context *ctx, const agp_features *u, double *ou
 static int sparse_fit_create_fast(agp_context *ctx, agp_comm *comm, const agp_kernel *k, const agp_features *x, int64_t n_groups,
                                   const int64_t *offsets, const double *y, const double *y_var, const agp_features *u,
                                   double measurement_nugget, double inducing_nugget, agp_sparse_fit **out,
-                                  double *information, double *nll_out) {
+                                  double *information, double *nll_out, SparseScratch *keep = nullptr,
+                                  double **yw_out = nullptr) {
   if (out) *out = nullptr;
   // ---- argument checks: rank-local, agreed before anything else when the fit is sharded ----
   int st = AGP_OK;
@@ -716,7 +672,8 @@ static int sparse_fit_create_fast(agp_context *ctx, agp_comm *comm, const agp_ke
   hipStream_t s = ctx->stream;
   StageTimer stage(s, getenv("AGP_SPARSE_TIMING") != nullptr);  // (development aid: prints the stage times of one fit)
   std::unique_ptr<agp_sparse_fit, void (*)(agp_sparse_fit *)> f(new (std::nothrow) agp_sparse_fit(), agp_sparse_fit_destroy);
-  SparseScratch w;
+  SparseScratch own_scratch;
+  SparseScratch &w = keep ? *keep : own_scratch;  // (the gradient goes on from what the fit leaves in its scratch)
   const long long ldm = factor_ld(m);
   double *yw = nullptr, log_det_a = 0.;
   // ---- everything up to the first device collective: K_uu (replicated arithmetic) and this rank's own groups ----
@@ -761,9 +718,25 @@ static int sparse_fit_create_fast(agp_context *ctx, agp_comm *comm, const agp_ke
   const double log_det = sums[0] + (f->sigma->log_det + f->sigma2->log_det) - f->kuu->log_det;
   f->nll = 0.5 * (log_det + (sums[1] - ctx->h_scalars[2]) + sums[2] * std::log(2 * M_PI));
   if (nll_out) *nll_out = f->nll;
+  if (yw_out) *yw_out = yw;
   if (out) *out = f.release();
   return AGP_OK;
 }
+
+extern "C++" {
+namespace agp {
+int sparse_fit_fast(agp_context *ctx, const agp_kernel *k, const agp_features *x, int64_t n_groups, const int64_t *offsets,
+                    const double *y, const double *y_var, const agp_features *u, double measurement_nugget,
+                    double inducing_nugget, agp_sparse_fit **out, double *nll_out, SparseScratch *keep, double **yw_out) {
+  return sparse_fit_create_fast(ctx, nullptr, k, x, n_groups, offsets, y, y_var, u, measurement_nugget, inducing_nugget, out,
+                                nullptr, nll_out, keep, yw_out);
+}
+void gemm_over_observations(hipStream_t s, SparseScratch &w, double *C, long long ldc, const double *A, const double *B,
+                            long long ldw, long long m, long long n) {
+  product_over_observations(s, w, C, ldc, A, B, ldw, m, n);
+}
+}  // namespace agp
+}  // extern "C++"
 
 // The LL^T / CholeskyQR2 path first; where it finds K_uu or B^T B not numerically positive definite the reference's
 // pivoted algorithm takes over (one process only).  AGP_SPARSE_PIVOTED=1 forces the pivoted path.

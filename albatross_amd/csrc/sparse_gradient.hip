@@ -1,0 +1,512 @@
+// sparse_gradient.hip — agp_sparse_nll_gradient: exact gradient of the sparse GP's (FITC / PITC) negative log-likelihood.
+//
+// Notation of sparse_api.hip: n observations in groups g, m inducing points u, D = diag(y_var) + measurement_nugget I,
+// K_uu = k(u, u) + inducing_nugget I, Q = K_fu K_uu^-1 K_uf, A = blockdiag_g(k(x_g, x_g) + D_g - Q_gg), Kt = A + Q,
+// NLL = 1/2 (log|Kt| + y^T Kt^-1 y + n log 2 pi).  With alpha = Kt^-1 y, G = Kt^-1 - alpha alpha^T, bd(.) the group-block
+// diagonal part, H = G - bd(G), E = K_fu K_uu^-1:
+//
+//   2 dNLL / dtheta = sum_g <bd(G)_g, dk(x_g, x_g)> + <2 H E, dk(x, u)> + <-E^T H E, dk(u, u)>
+//   dNLL / d measurement_nugget = 1/2 trace(bd(G)),   dNLL / d inducing_nugget = 1/2 trace(-E^T H E)
+//
+// Everything is formed from what the fit leaves behind (sparse_internal.h: the scratch of sparse_fit_fast), as m x n
+// matrices whose column blocks are the groups - no n x n matrix anywhere:
+//   aw = y_w - W^T v,   alpha_g = R_g^T aw_g                         R_g = L_g^-1 (the block factors of A)
+//   Z = Lacc^-1 W = L2^-1 Q1_W,   N_g = -Z_g R_g = -(A^-1 K_fu Lacc^-T)_g^T
+//   -bd(G)_g = alpha_g alpha_g^T + N_g^T N_g - R_g^T R_g              (s_g x s_g slabs, both triangles)
+//   E^T = L_u^-T P,   q = E^T alpha
+//   -(H E)^T = L1^-T L2^-T N + [E_g^T bd(G)_g]_g + q alpha^T          (in place over N)
+//   -W_uu = E^T (H E)                                                 (split-K slabs over the observations)
+// followed by three contractions of those weights against the tangent form of the covariance program (cov_eval.h:
+// eval_pair_tangent) with the measurement / equality semantics of the Gram call that built each matrix: group blocks
+// (measurement, measurement), k(u, x) (plain, measurement), k(u, u) (plain, plain).  No float atomics: per-tile partial
+// sums and fixed-order reductions, so two calls give bit-identical results.
+//
+// Workspace beyond the fit's pool (K_uf | P | slabs): ONE more ldk x (n + m) slab (Q1^T no longer shares P's region),
+// two sets of s_g x s_g group slabs (R_g and bd(G)_g: n * s doubles each for groups of s) and O(n + m^2) vectors.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <memory>
+#include <vector>
+
+#include "api_internal.h"
+#include "sparse_internal.h"
+#include "cov_eval.h"
+
+using namespace agp;
+
+namespace {
+
+constexpr int SG_GROUP = 4;    // slots per walk of the tangent program (every weight is read ceil(P / SG_GROUP) times)
+constexpr int ST = 64;         // contraction tile edge
+constexpr int ST_THREADS = 256;
+
+struct DevFree {
+  void operator()(void *p) const { (void)dev_free(p); }
+};
+template <class T>
+using dev_ptr = std::unique_ptr<T, DevFree>;
+
+#define SG_HIP(expr)                                                                     \
+  do {                                                                                   \
+    hipError_t _e = (expr);                                                              \
+    if (_e != hipSuccess) {                                                              \
+      ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(_e);               \
+      return AGP_ERR_HIP;                                                                \
+    }                                                                                    \
+  } while (0)
+
+// group of global point i: off[g] <= i < off[g + 1]  (off has G + 1 entries)
+__device__ __forceinline__ long long find_group(const long long *__restrict__ off, long long G, long long i) {
+  long long lo = 0, hi = G;
+  while (hi - lo > 1) {
+    const long long mid = (lo + hi) >> 1;
+    if (off[mid] <= i) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// alpha_g = R_g^T aw_g: one wave per point i (lanes over the rows k >= i of column i of R_g: coalesced), butterfly sum
+__global__ __launch_bounds__(256) void group_rt_vec_kernel(const double *__restrict__ R, const long long *__restrict__ off,
+                                                           const long long *__restrict__ roff, const long long *__restrict__ rld,
+                                                           long long G, long long n, const double *__restrict__ aw,
+                                                           double *__restrict__ alpha) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long i = (long long)blockIdx.x * 4 + wave;
+  if (i >= n) return;
+  const long long g = find_group(off, G, i), o = off[g], sg = off[g + 1] - o, il = i - o;
+  const double *col = R + roff[g] + il * rld[g];
+  double acc = 0.;
+  for (long long k = il + lane; k < sg; k += 64) acc += col[k] * aw[o + k];
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) acc += __shfl_xor(acc, d, 64);
+  if (lane == 0) alpha[i] = acc;
+}
+
+// The group slabs hold the lower triangle of bd(Kt^-1)_g = R_g^T R_g - N_g^T N_g.  Overwrite them, BOTH triangles, with
+// -bd(G)_g = alpha_g alpha_g^T - bd(Kt^-1)_g and keep the diagonal of bd(G) in diag[].  One workgroup per column.
+__global__ __launch_bounds__(256) void group_weight_kernel(double *__restrict__ B, const long long *__restrict__ off,
+                                                           const long long *__restrict__ boff, const long long *__restrict__ bld,
+                                                           long long G, const double *__restrict__ alpha,
+                                                           double *__restrict__ diag) {
+  const long long j = blockIdx.x;
+  const long long g = find_group(off, G, j), o = off[g], sg = off[g + 1] - o, jl = j - o, ld = bld[g];
+  double *b = B + boff[g];
+  const double aj = alpha[j];
+  for (long long il = jl + threadIdx.x; il < sg; il += 256) {
+    const double v = aj * alpha[o + il] - b[il + jl * ld];
+    b[il + jl * ld] = v;
+    if (il == jl) diag[j] = -v;
+    else b[jl + il * ld] = v;
+  }
+}
+
+// M (m x n, ldm) += q alpha^T
+__global__ __launch_bounds__(256) void rank_one_add_kernel(double *__restrict__ M, long long ld, long long m,
+                                                           const double *__restrict__ q, const double *__restrict__ alpha) {
+  const long long c = (long long)blockIdx.y * 256 + threadIdx.x, i = blockIdx.x;  // (the long dimension in grid x)
+  if (c < m) M[c + i * ld] += q[c] * alpha[i];
+}
+
+// out[0] = scale * sum_i v[i * stride]   (one workgroup, fixed order)
+__global__ __launch_bounds__(1024) void strided_sum_kernel(const double *__restrict__ v, long long n, long long stride, double scale,
+                                                           double *__restrict__ out) {
+  __shared__ double red[1024];
+  double acc = 0.;
+  for (long long i = threadIdx.x; i < n; i += 1024) acc += v[i * stride];
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int h = 512; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[0] = scale * red[0];
+}
+
+// ---- the contractions: partial[tile][g] = sum over the tile's pairs of mult * w(row, col) dk(row, col) / dslot_g -----
+// One kernel, three shapes (mode):
+//   0  rectangular: rows = feature set R (the inducing points), columns = feature set C (the observations), weight W
+//      (rows x cols, ldw), every pair once.  Tiles column-block-major: id = bc * tiles_r + br.
+//   1  symmetric over one feature set (R == C): lower tiles only, pairs row >= col, off-diagonal pairs twice
+//   2  group blocks: tile ids run over the lower tiles of every group's s_g x s_g slab (tstart[g] = first tile of group
+//      g); rows and columns are the points off[g] .. off[g + 1] of ONE feature set, the weight slab of group g is
+//      W + woff[g] with leading dimension wld[g]
+// lane = row (coalesced reads of the weight's column), each wave walks 16 columns whose point is wave-uniform, as the
+// dense contraction (gradient.hip: contract_tile).
+struct SparseContractArgs {
+  TangentSlots<SG_GROUP> slots;
+  const double *tr[SG_GROUP];  // AGP_OP_SCALING slot g: its tangent column at the row features, else nullptr
+  const double *tc[SG_GROUP];  // ... at the column features
+  const double *W;
+  long long ldw;
+  long long tiles_r;           // mode 0: row tiles
+  const long long *off, *woff, *wld, *tstart;  // mode 2
+  long long G;
+  double *partial;             // [tile][SG_GROUP]
+  int mode;
+};
+
+template <int DIMP>
+__device__ __forceinline__ void load_pt(const FeatView &X, long long i, bool need_norm, Point<DIMP> &p) {
+  double nn = 0.;
+#pragma unroll
+  for (int d = 0; d < DIMP; ++d) {
+    p.c[d] = d < X.dim ? X.coords[i * X.dim + d] : 0.;
+    nn += p.c[d] * p.c[d];
+  }
+  p.norm = need_norm ? sqrt(nn) : 0.;
+#pragma unroll
+  for (int k = 0; k < AGP_MAX_SCALE_COLUMNS; ++k) p.s[k] = k < X.nsc ? X.scales[(long long)k * scale_stride(X) + i] : 0.;
+  p.id = X.ids ? X.ids[i] : -1;
+}
+
+__device__ __forceinline__ void lower_tile(long long id, int &bi, int &bj) {
+  bi = (int)((sqrt(8. * (double)id + 1.) - 1.) * 0.5);
+  while ((long long)bi * (bi + 1) / 2 > id) --bi;
+  while ((long long)(bi + 1) * (bi + 2) / 2 <= id) ++bi;
+  bj = (int)(id - (long long)bi * (bi + 1) / 2);
+}
+
+template <int DIMP>
+__global__ __launch_bounds__(ST_THREADS) void sparse_contract_kernel(const DevProgram *__restrict__ P, FeatView R, FeatView C,
+                                                                     SparseContractArgs a) {
+  const long long id = blockIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  // the tile: local row / column ranges, where they start in the feature sets, and the weight they index
+  long long rbase = 0, cbase = 0, nrl, ncl, ldw = a.ldw;
+  const double *W = a.W;
+  int bi, bj;
+  const bool lower = a.mode != 0;
+  if (a.mode == 0) {
+    bi = (int)(id % a.tiles_r);
+    bj = (int)(id / a.tiles_r);
+    nrl = R.n; ncl = C.n;
+  } else if (a.mode == 1) {
+    lower_tile(id, bi, bj);
+    nrl = ncl = R.n;
+  } else {
+    const long long g = find_group(a.tstart, a.G, id);
+    lower_tile(id - a.tstart[g], bi, bj);
+    rbase = cbase = a.off[g];
+    nrl = ncl = a.off[g + 1] - a.off[g];
+    W = a.W + a.woff[g];
+    ldw = a.wld[g];
+  }
+  const long long il = (long long)bi * ST + lane;
+  const bool need_norm = (P->metric_mask & ((1 << AGP_METRIC_RADIAL) | (1 << AGP_METRIC_ANGULAR))) != 0;
+  const bool have_ids = R.ids != nullptr && C.ids != nullptr, both_meas = R.meas != 0 && C.meas != 0;
+  double acc[SG_GROUP];
+#pragma unroll
+  for (int g = 0; g < SG_GROUP; ++g) acc[g] = 0.;
+  if (il < nrl) {
+    Point<DIMP> x;
+    load_pt<DIMP>(R, rbase + il, need_norm, x);
+    double tx[SG_GROUP];
+#pragma unroll
+    for (int g = 0; g < SG_GROUP; ++g) tx[g] = a.tr[g] ? a.tr[g][rbase + il] : 0.;
+    for (int c = wave; c < ST; c += ST_THREADS / 64) {
+      const long long jl = (long long)bj * ST + c;
+      if (jl >= ncl || (lower && jl > il)) continue;
+      Point<DIMP> y;
+      load_pt<DIMP>(C, cbase + jl, need_norm, y);
+      double ty[SG_GROUP];
+#pragma unroll
+      for (int g = 0; g < SG_GROUP; ++g) ty[g] = a.tc[g] ? a.tc[g][cbase + jl] : 0.;
+      const double w = ((lower && il != jl) ? 2. : 1.) * W[il + jl * ldw];
+      double dk[SG_GROUP];
+      eval_pair_tangent<DIMP, SG_GROUP>(P, a.slots, x, y, tx, ty, have_ids, both_meas, dk);
+#pragma unroll
+      for (int g = 0; g < SG_GROUP; ++g) acc[g] += w * dk[g];
+    }
+  }
+  // fixed-order reduction: butterfly inside the wave, then the four waves in order
+  __shared__ double red[ST_THREADS / 64][SG_GROUP];
+#pragma unroll
+  for (int g = 0; g < SG_GROUP; ++g) {
+    double v = acc[g];
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
+    if (lane == 0) red[wave][g] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < SG_GROUP) {
+    const int g = threadIdx.x;
+    double v = red[0][g];
+#pragma unroll
+    for (int w = 1; w < ST_THREADS / 64; ++w) v += red[w][g];
+    a.partial[id * SG_GROUP + g] = v;
+  }
+}
+
+void launch_sparse_contract(hipStream_t s, const DevProgram *P, const FeatView &R, const FeatView &C, const SparseContractArgs &a,
+                            long long tiles) {
+  if (tiles <= 0) return;
+  const dim3 grid((unsigned)tiles), block(ST_THREADS);
+  const int dim = R.dim;
+  if (dim == 1) hipLaunchKernelGGL(sparse_contract_kernel<1>, grid, block, 0, s, P, R, C, a);
+  else if (dim == 2) hipLaunchKernelGGL(sparse_contract_kernel<2>, grid, block, 0, s, P, R, C, a);
+  else if (dim == 3) hipLaunchKernelGGL(sparse_contract_kernel<3>, grid, block, 0, s, P, R, C, a);
+  else if (dim == 4) hipLaunchKernelGGL(sparse_contract_kernel<4>, grid, block, 0, s, P, R, C, a);
+  else hipLaunchKernelGGL(sparse_contract_kernel<8>, grid, block, 0, s, P, R, C, a);
+}
+
+// out[g] = -1/2 S_blocks[g] - S_fu[g] - 1/2 S_uu[g], every S the sum of its tiles' partials in a fixed order (256 strided
+// partial sums, then a tree); one workgroup per slot of the group.  The signs: the weights held are -bd(G), -(H E)^T, -W_uu.
+__global__ __launch_bounds__(256) void sparse_grad_reduce_kernel(const double *__restrict__ p0, long long t0,
+                                                                 const double *__restrict__ p1, long long t1,
+                                                                 const double *__restrict__ p2, long long t2, int count,
+                                                                 double *__restrict__ out) {
+  const int g = blockIdx.x;
+  if (g >= count) return;
+  __shared__ double red[256];
+  const double *parts[3] = {p0, p1, p2};
+  const long long tiles[3] = {t0, t1, t2};
+  const double scale[3] = {-0.5, -1.0, -0.5};
+  double total = 0.;
+  for (int q = 0; q < 3; ++q) {
+    double v = 0.;
+    for (long long t = threadIdx.x; t < tiles[q]; t += 256) v += parts[q][t * SG_GROUP + g];
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+      if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
+      __syncthreads();
+    }
+    total += scale[q] * red[0];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) out[g] = total;
+}
+
+long long lower_tiles(long long n) {
+  const long long t = (n + ST - 1) / ST;
+  return t * (t + 1) / 2;
+}
+
+}  // namespace
+
+extern "C" {
+
+int agp_sparse_nll_gradient(agp_context *c, const agp_kernel *k, const agp_features *x, int64_t n_groups,
+                            const int64_t *offsets, const double *y, const double *y_var, const agp_features *u,
+                            double measurement_nugget, double inducing_nugget, int n_slots, const agp_gradient_slot *slots,
+                            const double *tangents_x, int64_t ldtx, const double *tangents_u, int64_t ldtu, double *nll,
+                            double *grad_nll, double *grad_nuggets, double *alpha_out) {
+  if (!c || !k || !x || !u || !y || !offsets || !nll || n_groups <= 0) return AGP_ERR_INVALID_ARGUMENT;
+  if (n_slots < 0 || n_slots > AGP_MAX_GRADIENT_SLOTS || (n_slots > 0 && (!slots || !grad_nll))) return AGP_ERR_INVALID_ARGUMENT;
+  agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  auto fail = [&](int code) {
+    *nll = nan;
+    for (int j = 0; j < n_slots; ++j) grad_nll[j] = nan;
+    if (grad_nuggets) grad_nuggets[0] = grad_nuggets[1] = nan;
+    return code;
+  };
+  int st = AGP_OK, ntc = 0;
+  if ((st = check_slots(k, n_slots, slots, &ntc)) != AGP_OK) return st;
+  if (ntc > 0 && (!tangents_x || ldtx < x->n || !tangents_u || ldtu < u->n)) return AGP_ERR_INVALID_ARGUMENT;
+
+  // ---- the fit, exactly as agp_sparse_nll makes it on the LL^T / CholeskyQR2 path (no pivoted fallback: the gradient
+  // of a pseudo-inverse is not what a tuner wants) ----
+  SparseScratch w;
+  w.keep_P = true;
+  agp_sparse_fit *fit_raw = nullptr;
+  double *yw = nullptr, nll_v = 0.;
+  st = sparse_fit_fast(ctx, k, x, n_groups, offsets, y, y_var, u, measurement_nugget, inducing_nugget, &fit_raw, &nll_v, &w, &yw);
+  std::unique_ptr<agp_sparse_fit, void (*)(agp_sparse_fit *)> fit(fit_raw, agp_sparse_fit_destroy);
+  if (st == AGP_ERR_INVALID_ARGUMENT) return st;
+  if (st != AGP_OK) return fail(st);
+
+  hipStream_t s = ctx->stream;
+  StageTimer stage(s, getenv("AGP_SPARSE_TIMING") != nullptr);
+  const long long n = x->n, m = u->n, G = n_groups;
+  const long long ldk = round_up(m, 2), ldm = factor_ld(m), np2 = round_up(n, 2), mp2 = round_up(m, 2);
+  const DevProgram *dprog = nullptr;
+  if ((st = device_program(ctx, k, &dprog)) != AGP_OK) return fail(st);
+  FeatView xm = w.dx.v;
+  xm.meas = 1;
+  const FeatView uv = fit->u->v;
+
+  // ---- group tables: offsets, where each group's s_g x s_g slab starts and its leading dimension, first tile ----
+  long long smax = 0;
+  for (long long g = 0; g < G; ++g) smax = std::max<long long>(smax, offsets[g + 1] - offsets[g]);
+  const bool uniform = w.layout == 0, slabbed = w.layout != 2;
+  const long long lda_b = factor_ld(smax), stride_A = lda_b * smax, stride_I = ((smax + NB - 1) / NB) * (36 * MB * MB);
+  std::vector<long long> tab(4 * (size_t)(G + 1));
+  long long *h_off = tab.data(), *h_roff = h_off + (G + 1), *h_rld = h_roff + (G + 1), *h_tstart = h_rld + (G + 1);
+  long long r_elems = 0, tiles_blocks = 0;
+  for (long long g = 0; g < G; ++g) {
+    const long long sg = offsets[g + 1] - offsets[g];
+    h_off[g] = offsets[g];
+    h_rld[g] = slabbed ? lda_b : factor_ld(sg);
+    h_roff[g] = slabbed ? g * stride_A : r_elems;
+    r_elems = slabbed ? (g + 1) * stride_A : r_elems + h_rld[g] * sg;
+    h_tstart[g] = tiles_blocks;
+    tiles_blocks += lower_tiles(sg);
+  }
+  h_off[G] = n; h_roff[G] = r_elems; h_rld[G] = 0; h_tstart[G] = tiles_blocks;
+  const long long tiles_r = (m + ST - 1) / ST, tiles_fu = tiles_r * ((n + ST - 1) / ST), tiles_uu = lower_tiles(m);
+  if (tiles_blocks > 0x7fffffffLL || tiles_fu > 0x7fffffffLL) return fail(AGP_ERR_INVALID_ARGUMENT);
+
+  // ---- device buffers beyond the pool ----
+  long long *tab_raw = nullptr;
+  SG_HIP(dev_malloc(&tab_raw, sizeof(long long) * tab.size()));
+  dev_ptr<long long> tab_guard(tab_raw);
+  const long long *d_off = tab_raw, *d_roff = d_off + (G + 1), *d_rld = d_roff + (G + 1), *d_tstart = d_rld + (G + 1);
+  SG_HIP(hipMemcpyAsync(tab_raw, tab.data(), sizeof(long long) * tab.size(), hipMemcpyHostToDevice, s));
+  double *Rg = nullptr, *Bg = nullptr, *Wn = nullptr, *vec = nullptr;
+  SG_HIP(dev_malloc(&Rg, sizeof(double) * (size_t)round_up(r_elems, 2)));
+  dev_ptr<double> rg_guard(Rg);
+  SG_HIP(dev_malloc(&Bg, sizeof(double) * (size_t)round_up(r_elems, 2)));
+  dev_ptr<double> bg_guard(Bg);
+  SG_HIP(dev_malloc(&Wn, sizeof(double) * (size_t)ldm * (size_t)m));
+  dev_ptr<double> wn_guard(Wn);
+  const bool tx_copy = ntc > 0 && x->location == AGP_HOST, tu_copy = ntc > 0 && u->location == AGP_HOST;
+  const size_t part_elems = (size_t)(tiles_blocks + tiles_fu + tiles_uu) * SG_GROUP;
+  const size_t vec_elems = 3 * (size_t)np2 + (size_t)mp2 + 8 + (size_t)round_up(AGP_MAX_GRADIENT_SLOTS, 2) + part_elems +
+                           (tx_copy ? (size_t)np2 * (size_t)ntc : 0) + (tu_copy ? (size_t)mp2 * (size_t)ntc : 0);
+  SG_HIP(dev_malloc(&vec, sizeof(double) * vec_elems));
+  dev_ptr<double> vec_guard(vec);
+  double *aw = vec, *alpha = aw + np2, *diag = alpha + np2, *q = diag + np2, *scal = q + mp2, *grad_d = scal + 8;
+  double *part_blocks = grad_d + round_up(AGP_MAX_GRADIENT_SLOTS, 2), *part_fu = part_blocks + (size_t)tiles_blocks * SG_GROUP,
+         *part_uu = part_fu + (size_t)tiles_fu * SG_GROUP, *tcopy = part_uu + (size_t)tiles_uu * SG_GROUP;
+  const double *tang_x = tangents_x, *tang_u = tangents_u;
+  long long ld_tx = ldtx, ld_tu = ldtu;
+  if (tx_copy) {
+    SG_HIP(hipMemcpy2DAsync(tcopy, sizeof(double) * (size_t)np2, tangents_x, sizeof(double) * (size_t)ldtx, sizeof(double) * (size_t)n,
+                            (size_t)ntc, hipMemcpyHostToDevice, s));
+    tang_x = tcopy; ld_tx = np2;
+    tcopy += (size_t)np2 * (size_t)ntc;
+  }
+  if (tu_copy) {
+    SG_HIP(hipMemcpy2DAsync(tcopy, sizeof(double) * (size_t)mp2, tangents_u, sizeof(double) * (size_t)ldtu, sizeof(double) * (size_t)m,
+                            (size_t)ntc, hipMemcpyHostToDevice, s));
+    tang_u = tcopy; ld_tu = mp2;
+  }
+  SG_HIP(hipStreamSynchronize(s));  // (pageable sources)
+
+  // once per group, or once for all groups when they advance in lock step (blockIdx.y = group)
+  auto per_group = [&](auto &&fn) {
+    if (uniform) { fn(0LL, smax, G); return; }
+    for (long long g = 0; g < G; ++g) fn(g, offsets[g + 1] - offsets[g], 1LL);
+  };
+
+  // ---- R_g = L_g^-1 for every block of A ----
+  if (slabbed) {
+    launch_set_identity_batched(s, Rg, lda_b, stride_A, smax, G);
+    forward_solve_mat_batched(s, w.Ag, stride_A, smax, lda_b, w.Pimg, stride_I, Rg, stride_A, smax, lda_b, /*rhs_lower=*/true, G);
+  } else {
+    for (long long g = 0; g < G; ++g) {
+      const long long sg = offsets[g + 1] - offsets[g];
+      const agp_fit *blk = w.blocks[(size_t)g];
+      launch_set_identity(s, Rg + h_roff[g], h_rld[g], sg);
+      forward_solve_mat(s, blk->A, sg, blk->lda, blk->invd, Rg + h_roff[g], sg, h_rld[g], /*rhs_lower=*/true);
+    }
+  }
+  // ---- alpha = A^-1 (y - K_fu v) = L^-T (y_w - W^T v) ----
+  launch_colvec_dot(s, w.Kuf, ldk, m, n, fit->v, -1.0, 1.0, yw, aw);
+  hipLaunchKernelGGL(group_rt_vec_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, Rg, d_off, d_roff, d_rld, G, n, aw, alpha);
+  stage("gradient: R_g, alpha");
+
+  // ---- Z = Lacc^-1 W = L2^-1 Q1_W, then N_g = -Z_g R_g ----
+  const agp_fit *L1 = fit->sigma, *L2 = fit->sigma2;
+  double *Q1W = w.Q1T + (size_t)ldk * (size_t)m, *Z = nullptr, *Nm = nullptr;
+  if (forward_solve_wide_ok(m, n)) {  // out of place into W's buffer (W is dead: aw has been formed)
+    if (!w.Winv) SG_HIP(dev_malloc(&w.Winv, sizeof(double) * (size_t)m * (size_t)WIDE_BW));
+    invert_wide_blocks(s, L2->A, m, L2->lda, L2->invd, WIDE_BW, w.Winv);
+    forward_solve_wide(s, L2->A, m, L2->lda, w.Winv, Q1W, ldk, w.Kuf, ldk, n);
+    Z = w.Kuf; Nm = w.Q1T;
+  } else {
+    forward_solve_mat(s, L2->A, m, L2->lda, L2->invd, Q1W, n, ldk);
+    Z = Q1W; Nm = w.Kuf;
+  }
+  SG_HIP(hipMemsetAsync(Nm, 0, sizeof(double) * (size_t)ldk * (size_t)n, s));
+  per_group([&](long long g, long long sg, long long cnt) {
+    const size_t o = (size_t)offsets[g] * (size_t)ldk;
+    launch_gemm_nt_sub_batched(s, Nm + o, ldk, sg * ldk, Z + o, ldk, false, sg * ldk, Rg + h_roff[g], h_rld[g], true, stride_A, m, sg, sg,
+                               false, cnt);
+  });
+  stage("gradient: Z, N = -Z R");
+
+  // ---- -bd(G)_g = alpha_g alpha_g^T + N_g^T N_g - R_g^T R_g (both triangles) and the diagonal of bd(G) ----
+  per_group([&](long long g, long long sg, long long cnt) {
+    const size_t o = (size_t)offsets[g] * (size_t)ldk;
+    launch_rtr_lower_batched(s, Rg + h_roff[g], h_rld[g], stride_A, sg, Bg + h_roff[g], h_rld[g], stride_A, cnt);
+    launch_gemm_nt_sub_batched(s, Bg + h_roff[g], h_rld[g], stride_A, Nm + o, ldk, true, sg * ldk, Nm + o, ldk, true, sg * ldk, sg, sg, m,
+                               true, cnt);
+  });
+  hipLaunchKernelGGL(group_weight_kernel, dim3((unsigned)n), dim3(256), 0, s, Bg, d_off, d_roff, d_rld, G, alpha, diag);
+  stage("gradient: bd(G) slabs");
+
+  // ---- E^T = K_uu^-1 K_uf = L_u^-T P in place, q = E^T alpha ----
+  double *Et = w.Pbuf;
+  backward_solve_mat(s, fit->kuu->A, m, fit->kuu->lda, fit->kuu->invd, Et, n, ldk);
+  launch_matvec(s, Et, ldk, m, n, alpha, w.partial, 1.0, 0.0, nullptr, q);
+  stage("gradient: E^T = L_u^-T P");
+
+  // ---- -(H E)^T = Lacc^-T N + [E_g^T bd(G)_g]_g + q alpha^T, in place over N (Lacc^-T = L1^-T L2^-T) ----
+  backward_solve_mat(s, L2->A, m, L2->lda, L2->invd, Nm, n, ldk);
+  backward_solve_mat(s, L1->A, m, L1->lda, L1->invd, Nm, n, ldk);
+  stage("gradient: Lacc^-T N");
+  per_group([&](long long g, long long sg, long long cnt) {
+    const size_t o = (size_t)offsets[g] * (size_t)ldk;
+    launch_gemm_nt_sub_batched(s, Nm + o, ldk, sg * ldk, Et + o, ldk, false, sg * ldk, Bg + h_roff[g], h_rld[g], false, stride_A, m, sg, sg,
+                               false, cnt);
+  });
+  hipLaunchKernelGGL(rank_one_add_kernel, dim3((unsigned)n, (unsigned)((m + 255) / 256)), dim3(256), 0, s, Nm, ldk, m, q, alpha);
+  stage("gradient: (H E)^T");
+
+  // ---- -W_uu = E^T (H E): lower tiles, summed over the observations through the fit's split-K slabs ----
+  SG_HIP(hipMemsetAsync(Wn, 0, sizeof(double) * (size_t)ldm * (size_t)m, s));
+  gemm_over_observations(s, w, Wn, ldm, Et, Nm, ldk, m, n);
+  hipLaunchKernelGGL(strided_sum_kernel, dim3(1), dim3(1024), 0, s, diag, n, 1LL, 0.5, scal);           // 1/2 trace(bd(G))
+  hipLaunchKernelGGL(strided_sum_kernel, dim3(1), dim3(1024), 0, s, Wn, m, ldm + 1, -0.5, scal + 1);    // 1/2 trace(W_uu)
+  stage("gradient: W_uu = -E^T H E");
+
+  // ---- the three contractions, SG_GROUP slots per pass ----
+  for (int g0 = 0; g0 < n_slots; g0 += SG_GROUP) {
+    SparseContractArgs ca;
+    std::memset(static_cast<void *>(&ca), 0, sizeof(ca));
+    const int cnt = n_slots - g0 < SG_GROUP ? n_slots - g0 : SG_GROUP;
+    const double *col_x[SG_GROUP], *col_u[SG_GROUP];
+    for (int j = 0; j < SG_GROUP; ++j) {
+      const bool used = j < cnt;
+      const int node = used ? slots[g0 + j].node : -1, param = used ? slots[g0 + j].param : 0;
+      ca.slots.node[j] = node;
+      ca.slots.param[j] = param;
+      const bool scaling = used && k->prog.nodes[node].op == AGP_OP_SCALING;
+      col_x[j] = scaling ? tang_x + (size_t)param * (size_t)ld_tx : nullptr;
+      col_u[j] = scaling ? tang_u + (size_t)param * (size_t)ld_tu : nullptr;
+    }
+    ca.off = d_off; ca.woff = d_roff; ca.wld = d_rld; ca.tstart = d_tstart; ca.G = G; ca.tiles_r = tiles_r;
+    // group blocks: (measurement, measurement) pairs of the observations
+    for (int j = 0; j < SG_GROUP; ++j) ca.tr[j] = ca.tc[j] = col_x[j];
+    ca.W = Bg; ca.ldw = 0; ca.partial = part_blocks; ca.mode = 2;
+    launch_sparse_contract(s, dprog, xm, xm, ca, tiles_blocks);
+    // k(u, x): (plain, measurement)
+    for (int j = 0; j < SG_GROUP; ++j) { ca.tr[j] = col_u[j]; ca.tc[j] = col_x[j]; }
+    ca.W = Nm; ca.ldw = ldk; ca.partial = part_fu; ca.mode = 0;
+    launch_sparse_contract(s, dprog, uv, xm, ca, tiles_fu);
+    // k(u, u): (plain, plain)
+    for (int j = 0; j < SG_GROUP; ++j) ca.tr[j] = ca.tc[j] = col_u[j];
+    ca.W = Wn; ca.ldw = ldm; ca.partial = part_uu; ca.mode = 1;
+    launch_sparse_contract(s, dprog, uv, uv, ca, tiles_uu);
+    hipLaunchKernelGGL(sparse_grad_reduce_kernel, dim3(SG_GROUP), dim3(256), 0, s, part_blocks, tiles_blocks, part_fu, tiles_fu, part_uu,
+                       tiles_uu, cnt, grad_d + g0);
+  }
+  stage("gradient: contractions");
+
+  SG_HIP(hipGetLastError());
+  double h_scal[2] = {nan, nan};
+  SG_HIP(hipMemcpyAsync(h_scal, scal, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (n_slots > 0) SG_HIP(hipMemcpyAsync(grad_nll, grad_d, sizeof(double) * (size_t)n_slots, hipMemcpyDeviceToHost, s));
+  if (alpha_out) SG_HIP(hipMemcpyAsync(alpha_out, alpha, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
+  SG_HIP(hipStreamSynchronize(s));
+  SG_HIP(hipGetLastError());
+  if (grad_nuggets) { grad_nuggets[0] = h_scal[0]; grad_nuggets[1] = h_scal[1]; }
+  *nll = nll_v;
+  return AGP_OK;
+}
+
+}  // extern "C"

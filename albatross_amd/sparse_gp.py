@@ -258,6 +258,43 @@ class SparseGaussianProcessRegression:
         """:524-596, without the parameter priors (out of scope)."""
         return -self._create(dataset, False, comm)[1]
 
+    def log_likelihood_gradient(self, dataset):
+        """(log_likelihood(dataset), {name: d log_likelihood / d name}) for every name of get_params(), exact to fp64
+        rounding (agp_sparse_nll_gradient: one fit plus O(n m^2) work, instead of one more fit per parameter by finite
+        differences).  Covariance parameters go through the slot table of the covariance function (ScalingTerm
+        parameters through the scaling function's derivative at the observations AND at the inducing points), the two
+        nuggets come from the entry directly.  The inducing points are held fixed.  Mean-function parameters: this
+        likelihood is evaluated on the targets as given - like the reference, which keeps y from before
+        mean_function_.remove_from (:664-668) - so it does not depend on them and their derivative is exactly 0."""
+        ctx = self._ctx()
+        cov = self.covariance_function_
+        reordered, offsets, y, yv, u = self._components(dataset)
+        fx, fu = cov.features(reordered), cov.features(u)
+        sx, su = fx.as_struct(), fu.as_struct()
+        slots, columns = cov.param_slots()
+        if len(slots) > capi.MAX_GRADIENT_SLOTS:
+            raise ValueError(f"more than {capi.MAX_GRADIENT_SLOTS} covariance parameter slots")
+        tx = tu = None
+        if columns:
+            tx, tu = np.empty((fx.n, len(columns)), order="F"), np.empty((fu.n, len(columns)), order="F")
+            for c, (fn, name) in enumerate(columns):
+                tx[:, c] = fn.derivative(fx.coords, name)
+                tu[:, c] = fn.derivative(fu.coords, name)
+        table = (capi.GradientSlot * max(1, len(slots)))(*[capi.GradientSlot(node, p) for node, p, _ in slots])
+        nll = C.c_double()
+        grad_nll, grad_nuggets = np.zeros(len(slots)), np.zeros(2)
+        ctx._check(ctx._lib.agp_sparse_nll_gradient(ctx._h, ctx.kernel(cov), C.byref(sx), len(offsets) - 1, _ptr(offsets),
+                                                    _ptr(y), _ptr(yv), C.byref(su), self.measurement_nugget_,
+                                                    self.inducing_nugget_, len(slots), table, _ptr(tx), fx.n, _ptr(tu), fu.n,
+                                                    C.byref(nll), _ptr(grad_nll), _ptr(grad_nuggets), None),
+                   "agp_sparse_nll_gradient")
+        grad = {name: 0. for name in self.get_params()}
+        for (_, _, name), g in zip(slots, grad_nll):
+            grad[name] -= g
+        grad["measurement_nugget"] = -grad_nuggets[0]
+        grad["inducing_nugget"] = -grad_nuggets[1]
+        return -nll.value, grad
+
     def fit_from_prediction(self, new_inducing_points, prediction):
         """fit_from_prediction (:406-461): the fit on `new_inducing_points` that reproduces `prediction`, a
         JointDistribution made AT those points.  Like the reference, the mean is used as given (the mean function is not

@@ -560,6 +560,43 @@ AGP_API int64_t agp_sparse_fit_numerical_rank(const agp_sparse_fit *fit);
 AGP_API int agp_sparse_nll(agp_context *ctx, const agp_kernel *kernel, const agp_features *x, int64_t n_groups,
                    const int64_t *offsets, const double *y, const double *y_var, const agp_features *u,
                    double measurement_nugget, double inducing_nugget, double *out);
+/* Exact gradient of agp_sparse_nll with respect to covariance parameters and the two nuggets.  Arguments up to
+ * inducing_nugget exactly as agp_sparse_nll; slots exactly as agp_nll_gradient (same validation, same
+ * AGP_MAX_GRADIENT_SLOTS, derivative with respect to the raw parameter value).  An AGP_OP_SCALING slot reads its tangent
+ * column at the observations from tangents_x (n values per column, leading dimension ldtx >= n, at x->location) and at
+ * the inducing points from tangents_u (m values per column, ldtu >= m, at u->location).  nll (1 value, the value
+ * agp_sparse_nll returns for the same arguments, bit for bit), grad_nll (n_slots values), grad_nuggets (2 values:
+ * dNLL / d measurement_nugget, dNLL / d inducing_nugget; may be NULL) and alpha (n values, Kt^-1 y in the caller's grouped
+ * order; may be NULL) are host memory.  The inducing points are held fixed.
+ *
+ * With D = diag(y_var) + measurement_nugget I, K_uu = k(u, u) + inducing_nugget I, E = K_fu K_uu^-1,
+ * A = blockdiag_g(k(x_g, x_g) + D_g - (E K_uf)_gg), Kt = A + E K_uf, alpha = Kt^-1 y, G = Kt^-1 - alpha alpha^T,
+ * bd(.) the group-block diagonal part and H = G - bd(G):
+ *   2 dNLL / dtheta = sum_g <bd(G)_g, dk(x_g, x_g) / dtheta>       (measurement, measurement) pairs, group blocks only
+ *                   + <2 H E, dk(x, u) / dtheta>                   (measurement, plain): a MEASUREMENT_ONLY term adds nothing
+ *                   + <-E^T H E, dk(u, u) / dtheta>                (plain, plain)
+ *   dNLL / d measurement_nugget = 1/2 trace(bd(G)),   dNLL / d inducing_nugget = 1/2 trace(-E^T H E)
+ * formed without any n x n matrix from what the fit holds (Sigma = (K_uu + K_uf A^-1 K_fu)^-1 = Lacc^-T Lacc^-1):
+ *   alpha = A^-1 (y - K_fu v),  Kt^-1 E = A^-1 K_fu Sigma,  bd(Kt^-1)_g = A_g^-1 - V_g V_g^T with V = A^-1 K_fu Lacc^-T,
+ *   E^T = L_u^-T P,  A_g^-1 = R_g^T R_g with R_g = L_g^-1.
+ * Work beyond the fit: ~6 n m^2 + 4 n s m + n s^2 flop for groups of s (triangular solves and products on the fp64 MFMA)
+ * and three contractions per group of 4 slots, each reading its weight once.  Workspace: the fit's pool plus ONE more
+ * ldk x n slab (ldk = m rounded up to even; Q1^T no longer shares P's region), 2 n s doubles of group slabs and
+ * O(n + m^2) vectors.  No float atomics, fixed-order reductions: two identical calls give bit-identical results.
+ *
+ * Runs on the LL^T / CholeskyQR2 path only: where agp_sparse_fit_create would fall back to the pivoted L D L^T / QR
+ * (K_uu or B^T B not numerically positive definite) it returns AGP_ERR_NOT_POSITIVE_DEFINITE and writes NaN to nll,
+ * grad_nll and grad_nuggets.  A block of A that is not positive definite and NaN input: status as agp_sparse_nll, NaN
+ * outputs.  Conditioning: the formulas contain K_uu^-1 explicitly, so the error of the gradient relative to the sum
+ * of the absolute contracted terms is of order eps cond(K_uu) (and eps cond(Kt)), not eps: keep the inducing points no
+ * denser than the length scale or raise inducing_nugget when gradients matter.
+ * AGP_SPARSE_TIMING=1 prints the gradient's stages after the fit's. */
+AGP_API int agp_sparse_nll_gradient(agp_context *ctx, const agp_kernel *kernel, const agp_features *x, int64_t n_groups,
+                            const int64_t *offsets, const double *y, const double *y_var, const agp_features *u,
+                            double measurement_nugget, double inducing_nugget,
+                            int n_slots, const agp_gradient_slot *slots,
+                            const double *tangents_x, int64_t ldtx, const double *tangents_u, int64_t ldtu,
+                            double *nll, double *grad_nll, double *grad_nuggets, double *alpha);
 /* _predict_impl (:447-521): mean = K_*u v; covariance = K_** - Q_** + K_*u Sigma K_u*.  The mean
  * function is the caller's (mean_function_.add_to). */
 AGP_API int agp_sparse_predict_mean(agp_context *ctx, const agp_kernel *kernel, const agp_sparse_fit *fit,

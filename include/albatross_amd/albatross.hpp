@@ -2295,6 +2295,45 @@ class SparseGaussianProcessRegression {
     return -fit.negative_log_likelihood;
   }
 
+  // log_likelihood(dataset) and its exact gradient with respect to every name of get_params() (agp_sparse_nll_gradient:
+  // one fit plus O(n m^2) work instead of one more fit per parameter by finite differences).  Covariance parameters go
+  // through the slot table of the covariance function (ScalingTerm parameters through d f / d name at the observations
+  // AND at the inducing points), the two nuggets come from the entry; the inducing points are held fixed.  Mean-function
+  // parameters: this likelihood is evaluated on the targets as given - y is copied before the mean function is removed
+  // (:664-668) - so it does not depend on them and their derivative is exactly 0.
+  template <typename FeatureType>
+  typename GaussianProcessRegression<CovFunc, MeanFunc>::LogLikelihoodGradient
+  log_likelihood_gradient(const RegressionDataset<FeatureType> &dataset) const {
+    const Grouped<FeatureType> grouped = group(dataset);
+    const auto u = inducing_point_strategy_(covariance_function_, dataset.features);
+    if (u.empty()) throw std::invalid_argument("Empty inducing points!");  // :361
+    auto ctx = detail::default_context();
+    detail::KernelHolder k(covariance_function_.program());
+    detail::Flat fx = detail::flatten(covariance_function_, grouped.features);
+    detail::Flat fu = detail::flatten(covariance_function_, u);
+    std::vector<std::string> names;
+    std::vector<agp_gradient_slot> slots;
+    std::vector<double> tx, tu;
+    slot_table(grouped.features, &names, &slots, &tx);
+    slot_table(u, nullptr, nullptr, &tu);
+    const std::size_t n = grouped.features.size(), m = u.size();
+    std::vector<double> grad(slots.size(), 0.);
+    double nll = 0., nuggets[2] = {0., 0.};
+    detail::check(agp_sparse_nll_gradient(ctx->ctx, k.k, &fx.view, static_cast<std::int64_t>(grouped.offsets.size() - 1),
+                                          grouped.offsets.data(), grouped.y.data(), grouped.yv.empty() ? nullptr : grouped.yv.data(),
+                                          &fu.view, measurement_nugget_, inducing_nugget_, static_cast<int>(slots.size()), slots.data(),
+                                          tx.empty() ? nullptr : tx.data(), static_cast<std::int64_t>(n),
+                                          tu.empty() ? nullptr : tu.data(), static_cast<std::int64_t>(m), &nll, grad.data(), nuggets,
+                                          nullptr),
+                  ctx->ctx, "agp_sparse_nll_gradient");
+    typename GaussianProcessRegression<CovFunc, MeanFunc>::LogLikelihoodGradient out{-nll, {}};
+    for (const auto &kv : get_params()) out.gradient[kv.first] = 0.;
+    for (std::size_t s = 0; s < names.size(); ++s) out.gradient[names[s]] -= grad[s];
+    out.gradient[details::measurement_nugget_name()] = -nuggets[0];
+    out.gradient[details::inducing_nugget_name()] = -nuggets[1];
+    return out;
+  }
+
   // fit_from_prediction (:406-461): the fit on `new_inducing_points` that reproduces `prediction`, a joint distribution
   // made AT those points.  Like the reference, the mean is used as given (the mean function is not removed from it).
   template <typename FeatureType>
@@ -2387,6 +2426,29 @@ class SparseGaussianProcessRegression {
                     c, "agp_sparse_fit_create");
     auto ctx = fit->context;
     if (keep) fit->handle = std::shared_ptr<agp_sparse_fit>(h, [ctx](agp_sparse_fit *p) { agp_sparse_fit_destroy(p); });
+  }
+
+  // The slot table of the covariance function at `features` (names / slots may be nullptr) and the tangent columns of
+  // its ScalingTerm slots there (features.size() x columns, column-major; empty without such slots)
+  template <typename F>
+  void slot_table(const std::vector<F> &features, std::vector<std::string> *names, std::vector<agp_gradient_slot> *slots,
+                  std::vector<double> *tangents) const {
+    using X = typename detail::unwrap<F>::type;
+    const std::size_t n = features.size();
+    std::vector<detail::GradSlot<X>> rows;
+    int node = 0;
+    covariance_function_.template emit_slots<X>(rows, node);
+    int columns = 0;
+    for (auto &r : rows) {
+      if (r.tangent) {
+        r.slot.param = columns++;
+        tangents->resize(n * static_cast<std::size_t>(columns));
+        for (std::size_t i = 0; i < n; ++i)
+          (*tangents)[static_cast<std::size_t>(r.slot.param) * n + i] = r.tangent(detail::unwrap<F>::get(features[i]));
+      }
+      if (slots) slots->push_back(r.slot);
+      if (names) names->push_back(r.name);
+    }
   }
 
   CovFunc covariance_function_;
