@@ -9,6 +9,8 @@
 #include "api_internal.h"
 #include "mfma_f64.h"
 #include "shard_internal.h"
+#include "pub.h"
+#include "trsm_kernel.h"
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -397,6 +399,9 @@ extern "C" AGP_DEBUG_API int agp_debug_chain_probe(agp_context *ctx, const int *
 namespace agp {
 void panel_phase_public(agp_context *ctx, hipStream_t s, double *A, long long n, long long lda, double *img, double *y,
                         long long K0, long long kend);
+// solve.hip: z[c] -= sum_r L[k0 + r][c] x[r] for c < ncols, r < nbk (back_update_kernel)
+void launch_back_update(hipStream_t s, const double *A, long long lda, long long k0, int nbk, long long ncols, const double *x,
+                        double *z);
 }
 // blocked: while the chain runs, `blocked` other streams sit at a hipStreamWaitEvent on an event that is recorded
 // behind a long one-workgroup spinner on yet another stream (a queue whose head is an unsatisfied barrier packet)
@@ -909,10 +914,14 @@ AGP_DEBUG_API int agp_debug_time_trailing_update(agp_context *ctx, int64_t M, in
   return st;
 }
 
-// X (n x ncols, ld n) = L^-1 B for L = the LL^T factor of the host matrix K (n x n, lower triangle, ld n) through
+// X = L^-1 B for L = the LL^T factor of the host matrix K (n x n, lower triangle, ld n) through
 // forward_solve_wide (solve.hip): out of place, explicitly inverted 512 x 512 diagonal blocks.  n a multiple of 512.
-AGP_DEBUG_API int agp_debug_forward_solve_wide(agp_context *ctx, const double *K, int64_t n, const double *B, int64_t ncols, double *X) {
-  if (!ctx || !K || !B || !X || n < 1024 || n % 512 != 0 || ncols <= 0) return AGP_ERR_INVALID_ARGUMENT;
+// The device buffers have the leading dimension n + 2 and X enters filled with NaN.  ldx = n: X (n x ncols) receives the n
+// rows of the result; ldx = n + 2: the whole padded buffer, so that the caller sees its two padding rows.  L_out
+// (optional, n x n, ld n): the factor the solve ran against.
+AGP_DEBUG_API int agp_debug_forward_solve_wide(agp_context *ctx, const double *K, int64_t n, const double *B, int64_t ncols, double *X,
+                                               int64_t ldx, double *L_out) {
+  if (!ctx || !K || !B || !X || n < 1024 || n % 512 != 0 || ncols <= 0 || (ldx != n && ldx != n + 2)) return AGP_ERR_INVALID_ARGUMENT;
   AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   agp_fit *f = nullptr;
   int st = agp_factor_create(ctx, K, n, n, 0, AGP_HOST, &f);
@@ -924,15 +933,200 @@ AGP_DEBUG_API int agp_debug_forward_solve_wide(agp_context *ctx, const double *K
   AGP_HIP_CHECK(ctx, hipMalloc(&dW, sizeof(double) * (size_t)n * 512));
   AGP_HIP_CHECK(ctx, hipMemcpy2D(dB, sizeof(double) * (size_t)ldb, B, sizeof(double) * (size_t)n, sizeof(double) * (size_t)n, (size_t)ncols,
                                  hipMemcpyHostToDevice));
-  AGP_HIP_CHECK(ctx, hipMemset(dX, 0, sizeof(double) * (size_t)ldb * (size_t)ncols));
+  AGP_HIP_CHECK(ctx, hipMemsetAsync(dX, 0xFF, sizeof(double) * (size_t)ldb * (size_t)ncols, ctx->stream));  // (all ones: a NaN)
   invert_wide_blocks(ctx->stream, f->A, n, f->lda, f->invd, WIDE_BW, dW);
   forward_solve_wide(ctx->stream, f->A, n, f->lda, dW, dB, ldb, dX, ldb, ncols);
   AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   AGP_HIP_CHECK(ctx, hipGetLastError());
-  AGP_HIP_CHECK(ctx, hipMemcpy2D(X, sizeof(double) * (size_t)n, dX, sizeof(double) * (size_t)ldb, sizeof(double) * (size_t)n, (size_t)ncols,
+  AGP_HIP_CHECK(ctx, hipMemcpy2D(X, sizeof(double) * (size_t)ldx, dX, sizeof(double) * (size_t)ldb, sizeof(double) * (size_t)ldx, (size_t)ncols,
                                  hipMemcpyDeviceToHost));
+  if (L_out)
+    AGP_HIP_CHECK(ctx, hipMemcpy2D(L_out, sizeof(double) * (size_t)n, f->A, sizeof(double) * (size_t)f->lda, sizeof(double) * (size_t)n,
+                                   (size_t)n, hipMemcpyDeviceToHost));
   (void)hipFree(dB); (void)hipFree(dX); (void)hipFree(dW);
   agp_fit_destroy(f);
+  return AGP_OK;
+}
+
+// ONE substitution of solve.hip on host data, with the buffers prepared as the product prepares them (tests/test_substitutions_gpu.py).
+//   K      `count` SPD matrices (n x n, ld n, one after the other), each factored by agp_factor_create
+//   lda    0: the substitution runs on the factor's own A / lda / invd (count = 1); >= n: the factors and their tile images are
+//          copied into slabs with this leading dimension, `count` of them at strides LARGER than a slab, gaps and padding
+//          rows NaN (the batched kinds; the vector kinds at an odd leading dimension)
+//   B      the caller's whole right-hand side buffer, b_doubles long, padding and gaps included: copied in, run in place,
+//          copied back.  Problem p starts at B + p * stride_B; its leading dimension is ldb.
+//   rows, cols   the shape of one right-hand side: n x m for the left solves, nrows x n for the right solves, n x 1 for a vector
+//   opt    rhs_lower of the forward kinds; k0 of SUB_BACK_UPDATE
+//   flags_out (2 * count ints): [2 p] the hand-over time-out flag of problem p (flags[2] of the one-launch kinds),
+//          [2 p + 1] 1 if forward_solve_mat_lookahead's conditions for its two-stream path held
+//   L_out  (optional, count x n x n, ld n) the factors;  W_out (optional, ceil(n / 128) x 128 x 128) the inverted diagonal
+//          blocks of the vector kinds, as the kernels read them
+// A batched kind with count = 1 and stride_B = 0 passes zero strides throughout.
+enum {
+  SUB_FWD_MAT = 0, SUB_FWD_MAT_LOOKAHEAD, SUB_FWD_MAT_BATCHED, SUB_BWD_MAT, SUB_RIGHT_LT, SUB_RIGHT_LT_BATCHED, SUB_FWD_VEC,
+  SUB_BWD_VEC, SUB_BWD_VEC_BATCHED, SUB_COOP_DIRECT, SUB_COOP_FLAGS, SUB_COOP_BATCHED, SUB_BACK_UPDATE, SUB_KINDS
+};
+AGP_DEBUG_API int agp_debug_substitute(agp_context *ctx, int kind, const double *K, int64_t n, int64_t count, int64_t lda, double *B,
+                                       int64_t b_doubles, int64_t rows, int64_t cols, int64_t ldb, int64_t stride_B, int64_t opt,
+                                       int *flags_out, double *L_out, double *W_out) {
+  if (!ctx || !K || !B || !flags_out || kind < 0 || kind >= SUB_KINDS || n <= 0 || count <= 0 || count > 4096 || rows <= 0 ||
+      cols <= 0 || ldb < rows || stride_B < 0 || (lda != 0 && lda < n))
+    return AGP_ERR_INVALID_ARGUMENT;
+  const bool batched = kind == SUB_FWD_MAT_BATCHED || kind == SUB_RIGHT_LT_BATCHED || kind == SUB_BWD_VEC_BATCHED || kind == SUB_COOP_BATCHED;
+  const bool right = kind == SUB_RIGHT_LT || kind == SUB_RIGHT_LT_BATCHED;
+  const bool vector = kind == SUB_FWD_VEC || kind == SUB_BWD_VEC || kind == SUB_BWD_VEC_BATCHED || kind == SUB_COOP_DIRECT ||
+                      kind == SUB_COOP_FLAGS || kind == SUB_COOP_BATCHED;
+  const bool coop = kind == SUB_COOP_DIRECT || kind == SUB_COOP_FLAGS || kind == SUB_COOP_BATCHED;
+  const long long nblk = (n + NB - 1) / NB;
+  const bool zero_strides = batched && count == 1 && stride_B == 0;
+  if (!batched && count != 1) return AGP_ERR_INVALID_ARGUMENT;
+  if (batched && !zero_strides && lda == 0) return AGP_ERR_INVALID_ARGUMENT;
+  if ((right ? cols : rows) != n && kind != SUB_BACK_UPDATE) return AGP_ERR_INVALID_ARGUMENT;
+  if (vector && cols != 1) return AGP_ERR_INVALID_ARGUMENT;
+  const long long one_rhs = ldb * (cols - 1) + rows;  // doubles one right-hand side spans
+  if (!zero_strides && batched && stride_B < one_rhs) return AGP_ERR_INVALID_ARGUMENT;
+  if (b_doubles < (count - 1) * stride_B + one_rhs) return AGP_ERR_INVALID_ARGUMENT;
+  long long k0 = 0, nbk0 = 0;
+  if (kind == SUB_BACK_UPDATE) {  // B: column 0 = z (k0 doubles), column 1 = x (nbk doubles)
+    k0 = opt;
+    if (k0 <= 0 || k0 >= n || k0 % NB != 0 || cols != 2 || rows < k0) return AGP_ERR_INVALID_ARGUMENT;
+    nbk0 = n - k0 < NB ? n - k0 : NB;
+    if (rows < nbk0) return AGP_ERR_INVALID_ARGUMENT;
+  }
+  if (coop) {
+    // only what the product dispatches (api.hip: fit_create_impl, agp_fit_create_batch): the kernel's liveness argument
+    // and its hand-over modes are stated for these shapes
+    if (!ctx->tune.backsub_coop || n > ctx->tune.backsub_coop_max) return AGP_ERR_INVALID_ARGUMENT;
+    if (kind != SUB_COOP_FLAGS && nblk > BACKSUB_DIRECT_BLOCKS) return AGP_ERR_INVALID_ARGUMENT;
+    if (kind == SUB_COOP_FLAGS && nblk <= BACKSUB_DIRECT_BLOCKS) return AGP_ERR_INVALID_ARGUMENT;
+  }
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  for (int64_t p = 0; p < count; ++p) { flags_out[2 * p] = 0; flags_out[2 * p + 1] = 0; }
+
+  // ---- the factors: the fit's own buffers, or NaN-padded slabs
+  agp_fit *own = nullptr;
+  double *slabA = nullptr, *slabI = nullptr;
+  const double *A = nullptr, *invd = nullptr;
+  long long ldA = 0, stride_A = 0, stride_I = 0;
+  int st = AGP_OK;
+  auto cleanup = [&]() {
+    if (own) agp_fit_destroy(own);
+    if (slabA) (void)hipFree(slabA);
+    if (slabI) (void)hipFree(slabI);
+  };
+  if (lda == 0) {
+    st = agp_factor_create(ctx, K, n, n, 0, AGP_HOST, &own);
+    if (st != AGP_OK) { cleanup(); return st; }
+    A = own->A; invd = own->invd; ldA = own->lda;
+    if (L_out)
+      AGP_HIP_CHECK(ctx, hipMemcpy2D(L_out, sizeof(double) * (size_t)n, own->A, sizeof(double) * (size_t)own->lda,
+                                     sizeof(double) * (size_t)n, (size_t)n, hipMemcpyDeviceToHost));
+  } else {
+    ldA = lda;
+    stride_A = round_up(lda * n, 2) + 10;              // (even: the slabs keep the 16-byte alignment of the first)
+    stride_I = nblk * (long long)IMG_DOUBLES + 6;
+    AGP_HIP_CHECK(ctx, hipMalloc(&slabA, sizeof(double) * (size_t)stride_A * (size_t)count));
+    AGP_HIP_CHECK(ctx, hipMalloc(&slabI, sizeof(double) * (size_t)stride_I * (size_t)count));
+    AGP_HIP_CHECK(ctx, hipMemset(slabA, 0xFF, sizeof(double) * (size_t)stride_A * (size_t)count));  // (all ones: a NaN)
+    AGP_HIP_CHECK(ctx, hipMemset(slabI, 0xFF, sizeof(double) * (size_t)stride_I * (size_t)count));
+    for (int64_t p = 0; p < count; ++p) {
+      agp_fit *f = nullptr;
+      st = agp_factor_create(ctx, K + (size_t)p * (size_t)n * (size_t)n, n, n, 0, AGP_HOST, &f);
+      if (st != AGP_OK) { if (f) agp_fit_destroy(f); cleanup(); return st; }
+      hipError_t e = hipMemcpy2D(slabA + p * stride_A, sizeof(double) * (size_t)lda, f->A, sizeof(double) * (size_t)f->lda,
+                                 sizeof(double) * (size_t)n, (size_t)n, hipMemcpyDeviceToDevice);
+      if (e == hipSuccess)
+        e = hipMemcpy(slabI + p * stride_I, f->invd, sizeof(double) * (size_t)nblk * IMG_DOUBLES, hipMemcpyDeviceToDevice);
+      if (e == hipSuccess && L_out)
+        e = hipMemcpy2D(L_out + (size_t)p * (size_t)n * (size_t)n, sizeof(double) * (size_t)n, f->A, sizeof(double) * (size_t)f->lda,
+                        sizeof(double) * (size_t)n, (size_t)n, hipMemcpyDeviceToHost);
+      agp_fit_destroy(f);
+      if (e != hipSuccess) { cleanup(); ctx->last_error = hipGetErrorString(e); return AGP_ERR_HIP; }
+    }
+    A = slabA; invd = slabI;
+  }
+  if (zero_strides) stride_A = stride_I = 0;
+
+  // ---- the right-hand side and the scratch of the kind
+  const size_t bbytes = sizeof(double) * (size_t)b_doubles;
+  double *dB = nullptr, *dX = nullptr, *dW = nullptr, *xstage = nullptr;
+  int *dflags = nullptr;
+  unsigned long long *done = nullptr;
+  auto cleanup_rhs = [&]() {
+    for (void *q : {(void *)dB, (void *)dX, (void *)dW, (void *)xstage, (void *)dflags, (void *)done})
+      if (q) (void)hipFree(q);
+    cleanup();
+  };
+#define SUB_CHECK(expr)                                                                              \
+  do {                                                                                               \
+    hipError_t _e = (expr);                                                                          \
+    if (_e != hipSuccess) { ctx->last_error = hipGetErrorString(_e); cleanup_rhs(); return AGP_ERR_HIP; } \
+  } while (0)
+  SUB_CHECK(hipMalloc(&dB, bbytes));
+  SUB_CHECK(hipMemcpy(dB, B, bbytes, hipMemcpyHostToDevice));
+  if (kind == SUB_FWD_VEC || kind == SUB_BWD_VEC) {
+    SUB_CHECK(hipMalloc(&dW, sizeof(double) * (size_t)nblk * NB * NB));
+    SUB_CHECK(hipMalloc(&xstage, sizeof(double) * (size_t)n));
+  }
+  if (coop) {
+    // x: the caller's buffer once more (its padding and gaps are what comes back around the solution), the sentinel in the
+    // n words of every problem (the product fills count * stride words, its stride being n rounded up to 2)
+    SUB_CHECK(hipMalloc(&dX, bbytes));
+    SUB_CHECK(hipMemcpyAsync(dX, dB, bbytes, hipMemcpyDeviceToDevice, s));
+    SUB_CHECK(hipMalloc(&dflags, sizeof(int) * 4 * (size_t)count));
+    SUB_CHECK(hipMemsetAsync(dflags, 0, sizeof(int) * 4 * (size_t)count, s));
+    if (kind == SUB_COOP_FLAGS) {
+      SUB_CHECK(hipMalloc(&done, sizeof(unsigned long long) * (size_t)backsub_done_words(n, 1)));
+      PrepArgs pre;
+      pre.fill(done, 0ull, backsub_done_words(n, 1));
+      launch_prep(s, pre);
+    } else {
+      for (int64_t p = 0; p < count; ++p) launch_fill_sentinel(s, dX + p * stride_B, n);
+    }
+  }
+  const bool lower = opt != 0;
+  switch (kind) {
+  case SUB_FWD_MAT: forward_solve_mat(s, A, n, ldA, invd, dB, cols, ldb, lower); break;
+  case SUB_FWD_MAT_LOOKAHEAD:
+    flags_out[1] = (n > 2 * NBO && ctx->stream2 && cols >= 64) ? 1 : 0;
+    forward_solve_mat_lookahead(ctx, A, n, ldA, invd, dB, cols, ldb, lower);
+    break;
+  case SUB_FWD_MAT_BATCHED:
+    forward_solve_mat_batched(s, A, stride_A, n, ldA, invd, stride_I, dB, stride_B, cols, ldb, lower, count);
+    break;
+  case SUB_BWD_MAT: backward_solve_mat(s, A, n, ldA, invd, dB, cols, ldb); break;
+  case SUB_RIGHT_LT: right_solve_lt(s, A, n, ldA, invd, dB, rows, ldb); break;
+  case SUB_RIGHT_LT_BATCHED: right_solve_lt_batched(s, A, stride_A, n, ldA, invd, stride_I, dB, stride_B, rows, ldb, count); break;
+  case SUB_FWD_VEC:
+    invert_diag_blocks_forward(s, n, invd, dW);
+    forward_solve_vec(s, A, n, ldA, dW, dB, xstage);
+    break;
+  case SUB_BWD_VEC:
+    invert_diag_blocks(s, A, n, ldA, invd, dW);
+    backward_solve_vec(s, A, n, ldA, dW, dB, xstage);
+    break;
+  case SUB_BWD_VEC_BATCHED: backward_solve_vec_batched(s, A, stride_A, n, ldA, invd, stride_I, dB, stride_B, count); break;
+  case SUB_COOP_DIRECT: backward_solve_coop(s, A, n, ldA, invd, dB, dX, dflags, nullptr, 1, 0, 0, 0, 0, 0); break;
+  case SUB_COOP_FLAGS: backward_solve_coop(s, A, n, ldA, invd, dB, dX, dflags, done, 1, 0, 0, 0, 0, 0); break;
+  case SUB_COOP_BATCHED:
+    backward_solve_coop(s, A, n, ldA, invd, dB, dX, dflags, nullptr, count, stride_A, stride_I, stride_B, stride_B, 4);
+    break;
+  default:  // SUB_BACK_UPDATE: z[c] -= sum_r L[k0 + r][c] x[r], c < k0
+    launch_back_update(s, A, ldA, k0, (int)nbk0, k0, dB + ldb, dB);
+    break;
+  }
+  SUB_CHECK(hipStreamSynchronize(s));
+  SUB_CHECK(hipGetLastError());
+  SUB_CHECK(hipMemcpy(B, coop ? dX : dB, bbytes, hipMemcpyDeviceToHost));
+  if (W_out && dW) SUB_CHECK(hipMemcpy(W_out, dW, sizeof(double) * (size_t)nblk * NB * NB, hipMemcpyDeviceToHost));
+  if (coop) {
+    std::vector<int> hf(4 * (size_t)count);
+    SUB_CHECK(hipMemcpy(hf.data(), dflags, sizeof(int) * 4 * (size_t)count, hipMemcpyDeviceToHost));
+    for (int64_t p = 0; p < count; ++p) flags_out[2 * p] = hf[4 * (size_t)p + 2];
+  }
+#undef SUB_CHECK
+  cleanup_rhs();
   return AGP_OK;
 }
 

@@ -196,20 +196,29 @@ def test_trailing_update_variants(ctx, dbg, M, K, variant):
 def test_forward_solve_wide(ctx, dbg, n, ncols):
     """X = L^-1 B out of place for a right-hand side much wider than L (csrc/solve.hip: forward_solve_wide - inverted 512 x 512
     diagonal blocks, one deep product per block row, in-place triangular products bottom-up): the sparse GP's m x n solves.
-    Ragged column counts exercise the edge tiles of the out-of-place kernel."""
+    Ragged column counts exercise the edge tiles of the out-of-place kernel.
+    Besides the comparison with LAPACK: the componentwise residual bound of tests/substitution_cases.py with b = 512
+    against the factor the device used, and the two padding rows of the result's leading dimension n + 2, which enter as
+    NaN (all bits set) and must come back so."""
     import ctypes as C
     from scipy.linalg import solve_triangular
-    rng = np.random.default_rng(n + ncols)
-    G = rng.standard_normal((n, n))
-    K = np.asfortranarray(G @ G.T / n + np.eye(n))
-    B = np.asfortranarray(rng.standard_normal((n, ncols)))
-    X = np.zeros((n, ncols), order="F")
+    import substitution_cases as sc
+    assert (n, ncols) in sc.WIDE_SHAPES  # (tests/test_substitution_bounds_host.py meets the bound on these)
+    K, B = sc.wide_problem(n, ncols)
+    ldx = n + 2
+    Xp = np.zeros((ldx, ncols), order="F")
+    L = np.zeros((n, n), order="F")
     fn = dbg.agp_debug_forward_solve_wide
     fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
-    assert fn(ctx._h, _p(K), n, _p(B), ncols, _p(X)) == 0
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+    assert fn(ctx._h, _p(K), n, _p(B), ncols, _p(Xp), ldx, _p(L)) == 0
+    X = Xp[:n]
     want = solve_triangular(np.linalg.cholesky(K), B, lower=True)
     assert np.abs(X - want).max() <= 1e-11 * np.abs(want).max()
+    assert np.all(np.ascontiguousarray(Xp[n:]).view(np.uint64) == np.uint64(0xFFFFFFFFFFFFFFFF))  # padding rows untouched
+    ratio = sc.residual_ratio(np.tril(L), np.asfortranarray(X), B, sc.WIDE_BW, False)
+    print(f"forward_solve_wide {n} x {ncols}: residual / bound {ratio:.3g}")
+    assert ratio <= 1.0, ratio
 
 
 @pytest.mark.parametrize("n", [16, 100, 128, 129, 300, 512, 640, 1000, 1537])
