@@ -10,7 +10,7 @@ from .covariance import (AngularDistance, Constant, CovarianceFunction, Euclidea
                          ScalingTerm, SquaredExponential, SumOfCovarianceFunctions, as_measurements,
                          measurement_only, OnlyForAlternatives, VariantFeatures, only_for_alternatives)
 
-from .gp import (AlbatrossAmdError, BlockSymmetric, ExplainedCovariance, PivotedLDLT, Context, DeviceArray, CrossValidation, CrossValidationPrediction, DenseFactor,
+from .gp import (AlbatrossAmdError, DeviceJointDistribution, BlockSymmetric, ExplainedCovariance, PivotedLDLT, Context, DeviceArray, CrossValidation, CrossValidationPrediction, DenseFactor,
                  LeaveOneOutGrouper, LeaveOneOutLikelihood, group_indexer, root_mean_square_error, UpdatedGPFit, negative_log_likelihood, FitModel, GaussianProcessRegression, GPFit, JointDistribution,
                  LinearMean, MeanFunction, SumOfMeanFunctions, ProductOfMeanFunctions, MarginalDistribution, NanInputError, NotPositiveDefiniteError, Prediction,
                  RegressionDataset, ZeroMean, default_context, fit_batch, log_likelihood_gradient_batch, gp_from_covariance, gp_from_covariance_and_mean)
@@ -18,5 +18,7 @@ from .gp import (AlbatrossAmdError, BlockSymmetric, ExplainedCovariance, Pivoted
 from .sparse_gp import (FixedInducingPoints, SparseFitModel, SparseGaussianProcessRegression, SparseGPFit,
                         UniformlySpacedInducingPoints, rebase_inducing_points, sparse_gp_from_covariance,
                         sparse_gp_from_covariance_and_mean)
+
+from .scores import chi_squared_cdf, crps_normal, draw_mvn, energy_score, variogram_score
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -106,6 +106,11 @@ EXPORTS = [
     ("agp_solve", C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_int]),
     ("agp_factor_create", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, _PP]),
     ("agp_nll_dense", C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, _D]),
+    ("agp_standard_normal", C.c_int, [_P, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int]),
+    ("agp_draw_mvn", C.c_int, [_P, _P, _P, C.c_int64, C.c_uint64, _P, C.c_int64, _P, C.c_int64, C.c_int]),
+    ("agp_energy_score", C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_uint64, C.c_int64, _P, C.c_int64, C.c_int, _D]),
+    ("agp_variogram_score", C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P, C.c_int64, C.c_int, C.c_int, _D]),
+    ("agp_crps_normal", C.c_int, [_P, _P, _P, _P, C.c_int64, _P, C.c_int]),
     ("agp_fit_inverse_diagonal", C.c_int, [_P, _P, _P, C.c_int]),
     ("agp_loo_marginal", C.c_int, [_P, _P, _P, _P, _P, C.c_int]),
     ("agp_ldlt_create", C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int, C.c_int, _PP, C.POINTER(C.c_int)]),

@@ -1869,9 +1869,10 @@ int agp_solve(agp_context *ctx, const agp_fit *fit, const double *rhs, int64_t n
 
 // ---- dense-matrix factor ---------------------------------------------------------
 // copies the lower triangle of K into a fresh factor buffer and runs the LL^T;
-// y (device, optional) receives the fused forward substitution
-static int factor_dense(agp_context *c, const double *K, long long n, long long ld, int uplo, int location,
-                        agp_fit *fit, double *y) {
+// y (device, optional) receives the fused forward substitution (api_internal.h: also scores.hip's factor)
+// diag_add (device, optional): n values added to the diagonal of the COPY before it is factored
+int factor_dense(agp_context *c, const double *K, long long n, long long ld, int uplo, int location,
+                 agp_fit *fit, double *y, const double *diag_add) {
   agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
   hipStream_t s = ctx->stream;
   const long long nblk = (n + NB - 1) / NB;
@@ -1905,6 +1906,7 @@ static int factor_dense(agp_context *c, const double *K, long long n, long long 
     launch_upper_to_lower(s, src, ld, fit->A, fit->lda, n);
   AGP_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_flags, 0, 4 * sizeof(int), s));
   AGP_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_scalars, 0, 4 * sizeof(double), s));
+  if (diag_add) launch_add_diagonal(s, fit->A, fit->lda, n, diag_add);
   launch_nan_scan_lower(s, fit->A, fit->lda, n, ctx->d_flags);
   factor_lower(ctx, fit->A, n, fit->lda, fit->invd, y, nullptr);
   AGP_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s));

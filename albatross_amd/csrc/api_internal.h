@@ -167,8 +167,17 @@ void launch_rtr_lower_batched(hipStream_t s, const double *R, long long ldr, lon
 // S (lower tiles, lds) = G^T G for a full n x n G (gradient.hip: agp_loo_nll_gradient's C diag(b) C)
 void launch_gtg_lower(hipStream_t s, const double *G, long long ldg, long long n, double *S, long long lds);
 }  // namespace agp
+// LL^T of a dense matrix at `location` into a fresh factor buffer of `fit` (api.hip: agp_factor_create, agp_nll_dense;
+// scores.hip: agp_energy_score).  y (device, optional) receives the fused forward substitution, diag_add (device,
+// optional) is added to the diagonal of the copy first.  Returns the status of the factorisation.  (Declared in the
+// extern "C" block below.)
+namespace agp {
+void launch_add_diagonal(hipStream_t s, double *A, long long lda, long long n, const double *d);  // scores.hip
+}
 // x = L^-T z for ONE vector (api.hip): z is overwritten with x; ws: backsolve_ws_elems(n) doubles of scratch
 extern "C" {  // (defined inside api.hip's extern "C" block)
+int factor_dense(agp_context *ctx, const double *K, long long n, long long ld, int uplo, int location, agp_fit *fit, double *y,
+                 const double *diag_add = nullptr);
 // `bytes` of the context's pinned staging area, or nullptr; valid until the call's final synchronisation
 void *host_stage(agp_context *ctx, size_t bytes);
 size_t backsolve_ws_elems(long long n);

@@ -242,6 +242,22 @@ class JointDistribution:
         return MarginalDistribution(self.mean, np.diag(self.covariance).copy())
 
 
+class DeviceJointDistribution:
+    """A JointDistribution left in HBM: `mean` (m) and `covariance` (m x m, column-major) are DeviceArrays - what
+    `Prediction.joint(on_device=True)` returns and the scores of albatross_amd.scores take as they are."""
+
+    def __init__(self, mean, covariance):
+        self.mean = mean
+        self.covariance = covariance
+
+    def size(self):
+        return self.mean.shape[0]
+
+    def numpy(self):
+        m = self.size()
+        return JointDistribution(self.mean.numpy(), self.covariance.numpy().ravel().reshape((m, m), order="F"))  # the bytes are column-major
+
+
 class RegressionDataset:
     """RegressionDataset<Feature>{features, targets} (core/dataset.hpp)."""
 
@@ -760,7 +776,10 @@ class Prediction:
     def marginal(self):
         return self._fm._predict_marginal(self._features)
 
-    def joint(self):
+    def joint(self, on_device=False):
+        """on_device=True: a DeviceJointDistribution - the m x m covariance stays in HBM (plain LL^T fits only)"""
+        if on_device:
+            return self._fm._predict_joint_on_device(self._features)
         return self._fm._predict_joint(self._features)
 
 
@@ -913,6 +932,18 @@ class FitModel:
         ctx._check(ctx._lib.agp_predict_joint(ctx._h, ctx.kernel(m.covariance_function_), self._fit._h, C.byref(s),
                                               _ptr(mean), _ptr(cov), capi.HOST), "agp_predict_joint")
         return JointDistribution(mean + m.mean_function_(fs.coords), cov)
+
+
+    def _predict_joint_on_device(self, features):
+        if isinstance(self._fit, UpdatedGPFit):
+            raise NotImplementedError("joint(on_device=True) needs a fit that holds the plain LL^T factor")
+        m, ctx = self._model, self._model._ctx()
+        fs, s = self._xs(features)
+        mean, cov = ctx.device_empty(fs.n), ctx.device_empty((fs.n, fs.n))
+        ctx._check(ctx._lib.agp_predict_joint(ctx._h, ctx.kernel(m.covariance_function_), self._fit._h, C.byref(s),
+                                              C.c_void_p(mean.ptr), C.c_void_p(cov.ptr), capi.DEVICE), "agp_predict_joint")
+        # mean_function_.add_to (gp.hpp:364) on the m values of the mean; the m x m covariance is not moved
+        return DeviceJointDistribution(ctx.to_device(mean.numpy() + m.mean_function_(fs.coords)), cov)
 
 
 class GaussianProcessRegression:

@@ -405,6 +405,56 @@ AGP_API int agp_factor_create(agp_context *ctx, const double *K, int64_t n, int6
 AGP_API int agp_nll_dense(agp_context *ctx, const double *deviation, const double *K,
                   int64_t n, int64_t ld, int uplo, int location, double *out);
 
+/* ---- scoring a joint prediction (src/evaluation/prediction_metrics.hpp) ------------------------------------
+ * The reference scores a JointDistribution against held-out truth on the host; these entries do it where
+ * agp_predict_joint (out_location = AGP_DEVICE) leaves the m x m covariance.  Every ARRAY argument lives at `location`,
+ * every SCALAR result goes to host memory, and nothing is written when the status is not AGP_OK.  All reductions have a
+ * fixed order and use no floating-point atomics: two identical calls return identical bits.
+ *
+ * agp_standard_normal: the generator behind the draws, m x n_columns standard normals, entry (i, j) = column
+ *   first_column + j of an unbounded matrix that depends on `seed` alone - not on the shape of the call.  Philox4x32-10
+ *   (Salmon et al., SC'11) with key = (low, high) word of seed and counter = (row, column, 0, 0) gives r0 .. r3;
+ *   u1 = (((r0 | r1 << 32) >> 11) + 0.5) 2^-53, u2 likewise from (r2, r3), z = sqrt(-2 ln u1) cos(2 pi u2) in fp64.  It
+ *   replaces std::normal_distribution over std::default_random_engine in detail::draw_mvn (:208-214), whose stream is
+ *   NOT reproduced.  m and first_column + n_columns must fit 32 bits.
+ * agp_draw_mvn: detail::draw_mvn (:200-217): out (m x n_draws, ldo) = mean 1^T + L Z, L the lower factor of `fit`
+ *   (m = agp_fit_size), on the fp64 MFMA; only the lower triangle of the factor is used.  z == NULL: Z = columns
+ *   0 .. n_draws - 1 of agp_standard_normal(seed); otherwise Z is the caller's m x n_draws matrix (ldz) and seed is unused.
+ *   `fit` is any agp_fit without phantom rows, normally an agp_factor_create of a joint covariance; a fit grown by
+ *   agp_fit_update returns AGP_ERR_UNSUPPORTED.  The reference draws through its pivoted L D L^T, P L D^1/2 z; this
+ *   library draws through L L^T: the distribution is the same, the sample belonging to ONE z is not - which, with the
+ *   different random stream, is why z can be supplied.
+ * agp_energy_score: score::energy_score (:387-435), ES = E||X - y|| - 0.5 E||X - X'|| by Monte Carlo.  cov (m x m, ldc,
+ *   LOWER triangle read) + diag(truth_var) (truth_var may be NULL) is factored on a copy with the LL^T of
+ *   agp_factor_create (the reference: Eigen::LDLT): AGP_ERR_NOT_POSITIVE_DEFINITE for a pivot <= 0, AGP_ERR_NAN_INPUT
+ *   for a NaN in the triangle.  k = num_samples / 2 + 1 (:265); sample set A = mean + L z_j for the normal columns
+ *   j = 0 .. k - 1 followed by its antithetic half mean - L z_j (:258-277), set B the same from columns k .. 2 k - 1;
+ *   *out = max(0, 0.5 (mean_err_norms(A) + mean_err_norms(B)) - 0.5 pairwise_errors_paired(A, B)) (:221-256, :415-421;
+ *   weights - m values, NULL = ones - enter the first term unsquared and the second squared, as there).  A NaN result
+ *   is returned as NaN.  z == NULL: the normals are agp_standard_normal(seed); otherwise the caller's m x 2 k matrix
+ *   (ldz).  num_samples <= 1, m <= 0, ldc < m or ldz < m: AGP_ERR_INVALID_ARGUMENT.  Scratch besides the factor's copy
+ *   is O(m k).
+ * agp_variogram_score: score::variogram_score (:465-520),
+ *   sum_{i < j} w_ij (|y_i - y_j|^p - E|N(mu_j - mu_i, sigma_ij^2)|^p)^2, sigma_ij = sqrt(c_ii + s_i + c_jj + s_j - 2 c_ij),
+ *   order p = 1 (madogram, detail::expected_abs_normal_1, :287-301) or 2 (variogram, mu^2 + sigma^2); any other order is
+ *   AGP_ERR_INVALID_ARGUMENT.  One pass over the pairs the reference's loop visits: the diagonal and the strict UPPER
+ *   triangle of cov (ldc) and the strict upper triangle of weights (m x m, ldw; NULL = ones) are all that is read of
+ *   them.  s = truth_var (NULL = none) joins the diagonal inside the kernel (:513-520).  m = 1 gives 0.
+ * agp_crps_normal: score::crps_normal (:349-364) elementwise over n triples, its NaN (non-finite argument) and
+ *   sigma <= 0 (absolute error) branches included. */
+AGP_API int agp_standard_normal(agp_context *ctx, uint64_t seed, int64_t m, int64_t first_column, int64_t n_columns,
+                                double *out, int64_t ldo, int location);
+AGP_API int agp_draw_mvn(agp_context *ctx, const agp_fit *fit, const double *mean, int64_t n_draws, uint64_t seed,
+                         const double *z, int64_t ldz, double *out, int64_t ldo, int location);
+AGP_API int agp_energy_score(agp_context *ctx, const double *mean, const double *cov, int64_t ldc, int64_t m,
+                             const double *truth, const double *truth_var, const double *weights, uint64_t seed,
+                             int64_t num_samples, const double *z, int64_t ldz, int location, double *out);
+AGP_API int agp_variogram_score(agp_context *ctx, const double *mean, const double *cov, int64_t ldc, int64_t m,
+                                const double *truth, const double *truth_var, const double *weights, int64_t ldw, int order,
+                                int location, double *out);
+AGP_API int agp_crps_normal(agp_context *ctx, const double *mu, const double *sigma, const double *y, int64_t n, double *out,
+                            int location);
+
 /* ---- update: condition a fit on further observations without refitting ------------------------------------
  * FitModel::update -> GaussianProcessBase::_update_impl (src/models/gp.hpp:384-414) with BlockSymmetric
  * (src/linalg/block_symmetric.hpp:46-115).  The reference keeps the old solver plus Ai_B = A^-1 B and the factor of the

@@ -1072,6 +1072,169 @@ inline double negative_log_likelihood(const Vector &deviation, const Matrix &cov
   return out;
 }
 
+// ---------------------------------------------------------------------------
+// evaluation/prediction_metrics.hpp: scores of a joint prediction against held-out truth, on the device
+// (include/albatross_amd.h, "scoring a joint prediction")
+// ---------------------------------------------------------------------------
+namespace detail {
+// the regularised lower incomplete gamma P(a, x), a > 0 (the role of stats/incomplete_gamma.hpp:134): the series below
+// a + 1, Lentz's continued fraction of Q above
+inline double regularized_lower_gamma(double a, double x) {
+  if (x <= 0.) return 0.;
+  const double log_front = a * std::log(x) - x - std::lgamma(a);
+  if (x < a + 1.) {
+    double term = 1. / a, total = term, n = a;
+    for (int i = 0; i < 10000; ++i) {
+      n += 1.;
+      term *= x / n;
+      total += term;
+      if (std::fabs(term) < std::fabs(total) * 1e-17) break;
+    }
+    const double v = total * std::exp(log_front);
+    return v < 1. ? v : 1.;
+  }
+  const double tiny = 1e-300;
+  double b = x + 1. - a, c = 1. / tiny, d = 1. / b, h = d;
+  for (int i = 1; i < 10000; ++i) {
+    const double an = -static_cast<double>(i) * (static_cast<double>(i) - a);
+    b += 2.;
+    d = an * d + b;
+    if (std::fabs(d) < tiny) d = tiny;
+    c = b + an / c;
+    if (std::fabs(c) < tiny) c = tiny;
+    d = 1. / d;
+    const double delta = d * c;
+    h *= delta;
+    if (std::fabs(delta - 1.) < 1e-16) break;
+  }
+  const double v = 1. - std::exp(log_front) * h;
+  return v > 0. ? v : 0.;
+}
+}  // namespace detail
+
+// stats/chi_squared.hpp:29-67
+inline double chi_squared_cdf(double x, double degrees_of_freedom) {
+  if (std::isnan(x) || x < 0.) return std::nan("");
+  if (degrees_of_freedom == 0) return 1.;
+  if (std::numeric_limits<double>::epsilon() > x) return 0.;
+  if (std::isinf(x)) return 1.;
+  return detail::regularized_lower_gamma(0.5 * degrees_of_freedom, 0.5 * x);
+}
+
+// chi_squared_cdf(deviation, covariance), stats/chi_squared.hpp:74-81: the quadratic form through the device LL^T
+inline double chi_squared_cdf(const Vector &deviation, const Matrix &covariance) {
+  const Vector solved = SerializableLDLT(covariance).solve(deviation);
+  double q = 0.;
+  for (std::size_t i = 0; i < deviation.size(); ++i) q += deviation[i] * solved[i];
+  return chi_squared_cdf(q, static_cast<double>(deviation.size()));
+}
+
+// prediction_metrics.hpp:136-141
+inline double chi_squared_cdf(const JointDistribution &prediction, const MarginalDistribution &truth) {
+  Matrix covariance(prediction.covariance);
+  Vector deviation(prediction.mean);
+  for (std::size_t i = 0; i < deviation.size(); ++i) {
+    deviation[i] -= truth.mean[i];
+    if (!truth.covariance.empty()) covariance(static_cast<std::int64_t>(i), static_cast<std::int64_t>(i)) += truth.covariance[i];
+  }
+  return chi_squared_cdf(deviation, covariance);
+}
+
+struct ChiSquaredCdf {  // prediction_metrics.hpp:143-145
+  double operator()(const JointDistribution &prediction, const MarginalDistribution &truth) const {
+    return chi_squared_cdf(prediction, truth);
+  }
+};
+
+namespace score {
+
+enum class VariogramScoreOrder { cVariogram, cMadogram };  // prediction_metrics.hpp:193-196
+
+namespace constant {  // :337-345
+static constexpr std::int64_t cEnergyScoreDefaultSampleCount{1000};
+static constexpr unsigned cEnergyScoreDefaultSeed{22U};
+static constexpr VariogramScoreOrder cDefaultVariogramScoreOrder{VariogramScoreOrder::cMadogram};
+}  // namespace constant
+
+// score::crps_normal (:349-364), one triple through agp_crps_normal
+inline double crps_normal(double mu, double sigma, double y) {
+  auto ctx = albatross::detail::default_context();
+  double out = 0.;
+  albatross::detail::check(agp_crps_normal(ctx->ctx, &mu, &sigma, &y, 1, &out, AGP_HOST), ctx->ctx, "agp_crps_normal");
+  return out;
+}
+
+// ... and elementwise over vectors
+inline Vector crps_normal(const Vector &mu, const Vector &sigma, const Vector &y) {
+  if (mu.size() != sigma.size() || mu.size() != y.size()) throw std::invalid_argument("crps_normal: sizes differ");
+  auto ctx = albatross::detail::default_context();
+  Vector out(mu.size());
+  albatross::detail::check(agp_crps_normal(ctx->ctx, mu.data(), sigma.data(), y.data(), static_cast<std::int64_t>(mu.size()),
+                                           out.data(), AGP_HOST),
+                           ctx->ctx, "agp_crps_normal");
+  return out;
+}
+
+namespace detail {
+inline double energy_score_impl(const JointDistribution &prediction, const Vector &truth, const Vector *truth_variance,
+                                const Vector *weights, unsigned seed, std::int64_t num_samples) {
+  const std::int64_t m = static_cast<std::int64_t>(prediction.mean.size());
+  if (truth.size() != prediction.mean.size() || prediction.covariance.rows() != m || prediction.covariance.cols() != m ||
+      (weights && weights->size() != truth.size()) || (truth_variance && truth_variance->size() != truth.size()))
+    throw std::invalid_argument("energy_score: predictive distribution, truth and weights have different sizes");
+  auto ctx = albatross::detail::default_context();
+  double out = 0.;
+  albatross::detail::check(
+      agp_energy_score(ctx->ctx, prediction.mean.data(), prediction.covariance.data.data(), m, m, truth.data(),
+                       truth_variance ? truth_variance->data() : nullptr, weights ? weights->data() : nullptr, seed,
+                       num_samples, nullptr, 0, AGP_HOST, &out),
+      ctx->ctx, "agp_energy_score");
+  return out;
+}
+
+inline double variogram_score_impl(const JointDistribution &prediction, const Vector &truth, const Vector *truth_variance,
+                                   const Matrix *weights, VariogramScoreOrder order) {
+  const std::int64_t m = static_cast<std::int64_t>(prediction.mean.size());
+  if (truth.size() != prediction.mean.size() || prediction.covariance.rows() != m || prediction.covariance.cols() != m ||
+      (weights && (weights->rows() != m || weights->cols() != m)) || (truth_variance && truth_variance->size() != truth.size()))
+    throw std::invalid_argument("variogram_score: predictive distribution, truth and weights have different sizes");
+  auto ctx = albatross::detail::default_context();
+  double out = 0.;
+  albatross::detail::check(
+      agp_variogram_score(ctx->ctx, prediction.mean.data(), prediction.covariance.data.data(), m, m, truth.data(),
+                          truth_variance ? truth_variance->data() : nullptr, weights ? weights->data.data() : nullptr, m,
+                          order == VariogramScoreOrder::cVariogram ? 2 : 1, AGP_HOST, &out),
+      ctx->ctx, "agp_variogram_score");
+  return out;
+}
+}  // namespace detail
+
+// score::energy_score (:387-435); the random stream is the library's counter-based generator, not std::default_random_engine
+inline double energy_score(const JointDistribution &prediction, const Vector &truth, const Vector *weights = nullptr,
+                           unsigned seed = constant::cEnergyScoreDefaultSeed,
+                           std::int64_t num_samples = constant::cEnergyScoreDefaultSampleCount) {
+  return detail::energy_score_impl(prediction, truth, nullptr, weights, seed, num_samples);
+}
+inline double energy_score(const JointDistribution &prediction, const MarginalDistribution &truth, const Vector *weights = nullptr,
+                           unsigned seed = constant::cEnergyScoreDefaultSeed,
+                           std::int64_t num_samples = constant::cEnergyScoreDefaultSampleCount) {
+  return detail::energy_score_impl(prediction, truth.mean, truth.covariance.empty() ? nullptr : &truth.covariance, weights, seed,
+                                   num_samples);
+}
+
+// score::variogram_score (:465-520)
+inline double variogram_score(const JointDistribution &prediction, const Vector &truth, const Matrix *weights = nullptr,
+                              VariogramScoreOrder order = constant::cDefaultVariogramScoreOrder) {
+  return detail::variogram_score_impl(prediction, truth, nullptr, weights, order);
+}
+inline double variogram_score(const JointDistribution &prediction, const MarginalDistribution &truth, const Matrix *weights = nullptr,
+                              VariogramScoreOrder order = constant::cDefaultVariogramScoreOrder) {
+  return detail::variogram_score_impl(prediction, truth.mean, truth.covariance.empty() ? nullptr : &truth.covariance, weights,
+                                      order);
+}
+
+}  // namespace score
+
 namespace detail {
 // solve / predict through a device-side CovarianceRepresentation (agp_solver_*, include/albatross_amd.h)
 inline Matrix solver_solve(const std::shared_ptr<ContextHolder> &ctx, const agp_solver *sv, const Matrix &rhs) {
