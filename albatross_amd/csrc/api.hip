@@ -1134,6 +1134,7 @@ static int fit_create_impl(agp_context *c, const agp_kernel *k, const agp_featur
     if (st != AGP_OK) {
       // keep a handle so the caller can query the failed pivot, but no factor
       drop_mixed();
+      fit->fail_status = st;
       *out = fit;
       return st;
     }
@@ -1162,6 +1163,7 @@ static int fit_create_impl(agp_context *c, const agp_kernel *k, const agp_featur
     if (mixed) invert_diag_blocks(s, fit->A, n, fit->lda, fit->invd, fit->winv);
   }
   if (mixed) {
+    fit->mixed = true;
     invert_diag_blocks_forward(s, n, fit->invd, Wfwd);
     const int st3 = refine_information(ctx, fit, Kfull, Wfwd, vec, mixed);
     drop_mixed();
@@ -1179,6 +1181,7 @@ static int fit_create_impl(agp_context *c, const agp_kernel *k, const agp_featur
     fit->failed_pivot = ctx->h_flags[1] ? (int64_t)ctx->h_flags[1] - 1 : -1;
     fit->log_det = 2. * ctx->h_scalars[0];
     if (st != AGP_OK) {  // keep a handle so the caller can query the failed pivot, but no factor
+      fit->fail_status = st;
       *out = fit;
       return st;
     }
@@ -1803,6 +1806,7 @@ int agp_fit_create_batch(agp_context *c, int count, const agp_kernel *const *ker
     fit->failed_pivot = fl[1] ? (int64_t)fl[1] - 1 : -1;
     fit->log_det = 2. * h_log[(size_t)b];
     status[b] = fl[0] ? AGP_ERR_NAN_INPUT : (fl[1] ? AGP_ERR_NOT_POSITIVE_DEFINITE : AGP_OK);  // gp.hpp:66, then the factor
+    fit->fail_status = status[b];
     if (log_det) log_det[b] = fit->log_det;
     out[b] = fit;
   }

@@ -235,6 +235,10 @@ struct agp_fit {
   agp::DeviceFeatures train;
   double log_det = 0.;
   int64_t failed_pivot = -1;
+  // What the creating call reported for this fit: AGP_OK, AGP_ERR_NAN_INPUT or AGP_ERR_NOT_POSITIVE_DEFINITE (failed_pivot
+  // alone cannot tell a NaN input from a good fit).  agp_predict_batch hands it on in status[b].
+  int fail_status = 0;
+  bool mixed = false;  // made by agp_fit_create_mixed: the factor carries the rounding of the low-precision bulk products
   // Fits grown by agp_fit_update: the appended block starts at a multiple of 128, so when the size before the update
   // was not one, the rows in between are PHANTOM rows (identity rows of the factor, zero information, decoupled from
   // everything).  `n` counts them - every kernel works on the padded factor -, `n_real` does not (0: no phantoms) and

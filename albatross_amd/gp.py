@@ -1424,6 +1424,74 @@ def fit_batch(models, datasets):
     return [FitModel(m, f) for m, f in zip(models, fits)]
 
 
+def predict_batch(fit_models, features, what="marginal"):
+    """`fit_models[b].predict(features[b])` for several fits of ONE size in lock step (agp_predict_batch): what follows
+    fit_batch - at a few hundred points one prediction is a handful of latency-bound launches, a batch runs each once.
+    fit_models: FitModels holding plain GPFits on one context (the handles of fit_batch, or any mix of fits of one size:
+    neighbours whose factors lie at one stride are predicted together, the others one by one).  features: ONE array
+    shared by all problems, or a list with one entry per model, every entry with the same number of points;
+    Measurement-wrapped features behave as in predict_with_measurement_noise.  what: "mean" | "marginal" | "joint".
+    Returns a list of mean arrays, MarginalDistributions or JointDistributions, each with its model's mean function
+    added back (gp.hpp:346,364)."""
+    modes = {"mean": 0, "marginal": 1, "joint": 2}
+    if what not in modes:
+        raise ValueError(f"predict_batch: what must be one of {sorted(modes)}, not {what!r}")
+    fit_models = list(fit_models)
+    count = len(fit_models)
+    if count == 0:
+        raise ValueError("predict_batch: at least one fit model")
+    if has_linear_combinations(features):
+        raise ValueError("predict_batch: LinearCombination features are not supported (predict one model at a time)")
+    shared = not isinstance(features, (list, tuple))  # an array, a Measurement or a FeatureSet: one vector for all problems
+    per_model = [features] * count if shared else list(features)
+    if len(per_model) != count:
+        raise ValueError("predict_batch: one feature vector per fit model (or one shared by all)")
+    for fm in fit_models:
+        if not isinstance(fm, FitModel) or type(fm._fit) is not GPFit or fm._fit.mixed_precision:
+            raise ValueError("predict_batch: every fit must be a plain fp64 GPFit (fit / fit_batch)")
+    ctx = fit_models[0]._model._ctx()
+    fsets = []
+    for fm, f in zip(fit_models, per_model):
+        if fm._model._ctx() is not ctx:
+            raise ValueError("predict_batch: every fit model must live on one context")
+        if has_linear_combinations(f):
+            raise ValueError("predict_batch: LinearCombination features are not supported (predict one model at a time)")
+        fsets.append(fm._model.covariance_function_.features(f))
+    m = fsets[0].n
+    if any(fs.n != m for fs in fsets):
+        raise ValueError("predict_batch: every feature vector must have the same number of points")
+    mode = modes[what]
+    structs = [fs.as_struct() for fs in fsets]
+    mean = np.empty((m, count), order="F")
+    second = None if mode == 0 else np.empty((m if mode == 1 else m * m, count), order="F")
+    status = (C.c_int * count)()
+    handles = []
+    try:
+        for fm in fit_models:  # private handles: the context's small kernel cache may evict while the batch is assembled
+            handles.append(ctx.private_kernel(fm._model.covariance_function_))
+        kernels = (C.c_void_p * count)(*handles)
+        fits = (C.c_void_p * count)(*[fm._fit._h.value for fm in fit_models])
+        fptrs = (C.c_void_p * count)(*[C.addressof(st) for st in structs])
+        ctx._check(ctx._lib.agp_predict_batch(ctx._h, count, kernels, fits, fptrs, mode, _ptr(mean), max(m, 1),
+                                              None if second is None else _ptr(second), max(second.shape[0], 1) if second is not None else 0,
+                                              capi.HOST, status), "agp_predict_batch")
+    finally:
+        for kh in handles:
+            ctx._lib.agp_kernel_destroy(kh)
+    for b in range(count):
+        ctx._check(status[b], f"agp_predict_batch: problem {b}")
+    out = []
+    for b, (fm, fs) in enumerate(zip(fit_models, fsets)):
+        mu = mean[:, b] + fm._model.mean_function_(fs.coords)  # mean_function_.add_to
+        if mode == 0:
+            out.append(mu)
+        elif mode == 1:
+            out.append(MarginalDistribution(mu, second[:, b].copy()))
+        else:
+            out.append(JointDistribution(mu, second[:, b].reshape((m, m), order="F").copy(order="F")))
+    return out
+
+
 class _GradientProblem:
     """the host side of one gradient problem: flattened features, targets (mean removed) and variances, the slot table
     of the covariance function (param_slots), its ctypes form and the tangent columns (n x columns, column-major) of

@@ -674,6 +674,50 @@ AGP_API int agp_predict_joint(agp_context *ctx, const agp_kernel *k, const agp_f
                       const agp_features *xs, double *mean, double *cov,
                       int out_location);
 
+/* agp_predict_mean / _marginal / _joint for `count` fits of one size in lock step: problem b computes exactly what the
+ * single call computes for kernels[b], fits[b], xs[b] (gp.hpp:305-366, 82-113; each xs[b]'s own is_measurement flag is
+ * honoured).  The counterpart of agp_fit_create_batch for what every user does after fitting: at N of a few hundred one
+ * prediction is a handful of latency-bound launches, a batch runs each of them once (one grid dimension = problem).
+ *   mode                 0 mean, 1 marginal, 2 joint (the numbering of agp_solver_predict)
+ *   kernels[b], xs[b]    covariance function and test features of problem b: all xs[b] have one m and one location,
+ *                        dim == the training dimension of fits[b]; dim may differ between problems
+ *   fits[b]              plain fp64 LL^T fits with training features, of one n, living on ctx (a mixed-precision fit, a
+ *                        factor of agp_factor_create: AGP_ERR_INVALID_ARGUMENT)
+ *   mean, ldm            m x count, ldm >= m
+ *   second, lds          marginal: m x count variances, lds >= m; joint: problem b's full symmetric m x m covariance,
+ *                        column-major with ld = m, at second + b * lds, lds >= m * m; ignored for mode 0
+ *   status[b]            (host) what the call that created fits[b] reported: AGP_OK, AGP_ERR_NAN_INPUT or
+ *                        AGP_ERR_NOT_POSITIVE_DEFINITE; a failed fit gets NaN-filled outputs, the rest of the batch is
+ *                        unaffected and the call returns AGP_OK
+ * Both outputs live at out_location.  A malformed argument anywhere (count <= 0, a null entry, unequal n or m, mixed
+ * locations, a dimension mismatch, a bad mode, ldm or lds too short, a fit without training features) returns
+ * AGP_ERR_INVALID_ARGUMENT and writes nothing; m == 0 returns AGP_OK.
+ * Lock step: fits[] is cut into maximal runs in which the factors, the tile images and the information vectors lie at
+ * one constant non-negative stride with one leading dimension - consecutive handles of one agp_fit_create_batch call, or
+ * any evenly spaced subset of them; the fits need not come from one call.  A run of two or more goes through the
+ * batched launches, a run of one through agp_predict_mean / _marginal / _joint unchanged (so does a fit grown by
+ * agp_fit_update).  Inside a run there is no synchronisation but the closing one; the descriptor tables are uploaded
+ * from the context's pinned staging area.  Host-resident test features of all runs are uploaded into one device
+ * allocation before the first launch, with one wait for those uploads (device-resident ones are used in place).  Covariance functions of the radial<Euclidean> [+ noise] shapes with one
+ * operator and one dimension in a run are evaluated by ONE launch for the run; other runs by a launch per problem that
+ * does the same arithmetic per problem.  No float atomics, fixed-order reductions: two identical calls are bit-identical,
+ * and no problem's arithmetic depends on its position or its neighbours - with one caveat: the MFMA products of the
+ * substitution and of the joint covariance (launch_gemm_nt_sub_batched) choose their tile shape from tiles x problems
+ * of a launch (64 x 64 tiles below 512, 128 x 128 from there on), so a problem's last bits may differ between two
+ * batches that fall on different sides of that threshold; within the bounds above they agree.
+ * Workspace: per problem ld_n * m doubles (V = L^-1 K*, ld_n = n rounded up to even) for modes 1 and 2, plus ld_m * m
+ * (ld_m = m rounded up to even) for mode 2; a run is cut into sub-batches of whole problems,
+ *   problems per sub-batch = max(1, min(65535, floor(2^28 / (ld_n m + [mode == 2] ld_m m)))),
+ * which keeps those buffers at 2 GiB, the bound of agp_predict_marginal (AGP_PREDICT_CHUNK=<points> replaces the formula
+ * by max(1, floor(points / m))).  Host outputs add a staging copy of the
+ * sub-batch's results (m, 2 m or m + m * m doubles per problem). */
+AGP_API int agp_predict_batch(agp_context *ctx, int count,
+                              const agp_kernel *const *kernels, const agp_fit *const *fits,
+                              const agp_features *const *xs, int mode,
+                              double *mean, int64_t ldm,
+                              double *second, int64_t lds,
+                              int out_location, int *status);
+
 /* ---- CovarianceRepresentation compositions on the device ----------------------------------------------------------
  * The solvers a fit can hold besides its own factor (src/models/gp.hpp:42-45 asks for `solve` and `rows`), and the generic
  * form of _predict_impl over any of them - everything stays in HBM, a solve is device solves + MFMA products:
@@ -842,7 +886,8 @@ AGP_API int agp_set_profiling(agp_context *ctx, int enabled);
  *   AGP_BACKSUB_COOP=0       the fit's back substitution as one launch per block (rounds 1-4) instead of ONE launch
  *   AGP_BACKSUB_COOP_MAX=<n> largest fit that uses the one-launch back substitution (default 2047)
  *   AGP_SPARSE_PIVOTED=1     the sparse GP always takes the literal (pivoted LDL^T + column-pivoted QR) path
- *   AGP_PREDICT_CHUNK=<m>    test points per slice of marginal predictions (default: by memory, 2 GiB per slice)
+ *   AGP_PREDICT_CHUNK=<m>    test points per slice of marginal predictions (default: by memory, 2 GiB per slice);
+ *                            agp_predict_batch: V columns per sub-batch, i.e. max(1, floor(<m> / m)) problems
  *   AGP_SHARD_BLOCK=<b>      128 / 256 / 512 rows per row block of the sharded fit (default 512; tests)
  *   AGP_SHARD_FORCE_COMM=1   ONE rank runs the multi-rank schedule through its transport (RCCL group of one; tests)
  *   AGP_SHARD_HOST_PACING=1  the sharded schedule is paced by the host instead of device-side flags

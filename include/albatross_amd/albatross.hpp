@@ -2252,6 +2252,93 @@ auto GaussianProcessRegression<CovFunc, MeanFunc>::cross_validate() const {
   return CrossValidation<GaussianProcessRegression<CovFunc, MeanFunc>>(*this);
 }
 
+// `fit_models[b].predict(features[b])` for SEVERAL fits of one size in lock step (agp_predict_batch): what follows fit_batch.
+// Every features[b] has the same number of points (Measurement<> features as in predict_with_measurement_noise); fits whose
+// factors lie at one stride - the FitModels of one fit_batch call - are predicted together, any others one by one.  Each
+// model's mean function is added back (gp.hpp:346,364).  Throws for the first problem whose fit had failed.
+template <typename ModelType, typename FeatureType, typename P>
+class BatchPrediction {
+ public:
+  BatchPrediction(const std::vector<FitModel<ModelType, FeatureType>> *fit_models, const std::vector<std::vector<P>> *features)
+      : fms_(fit_models), xs_(features) {
+    if (fms_->empty() || fms_->size() != xs_->size()) throw std::invalid_argument("predict_batch: one feature vector per fit model, at least one");
+    for (const auto &x : *xs_)
+      if (x.size() != (*xs_)[0].size()) throw std::invalid_argument("predict_batch: every feature vector must have the same number of points");
+  }
+  std::vector<Vector> mean() const {
+    std::vector<Vector> means;
+    run(0, &means, nullptr);
+    return means;
+  }
+  std::vector<MarginalDistribution> marginal() const {
+    std::vector<Vector> means;
+    std::vector<double> second;
+    run(1, &means, &second);
+    const std::size_t m = (*xs_)[0].size();
+    std::vector<MarginalDistribution> out;
+    for (std::size_t b = 0; b < means.size(); ++b)
+      out.emplace_back(std::move(means[b]), Vector(second.begin() + (std::ptrdiff_t)(b * m), second.begin() + (std::ptrdiff_t)((b + 1) * m)));
+    return out;
+  }
+  std::vector<JointDistribution> joint() const {
+    std::vector<Vector> means;
+    std::vector<double> second;
+    run(2, &means, &second);
+    const std::size_t m = (*xs_)[0].size();
+    std::vector<JointDistribution> out(means.size());
+    for (std::size_t b = 0; b < means.size(); ++b) {
+      out[b].mean = std::move(means[b]);
+      out[b].covariance = Matrix((std::int64_t)m, (std::int64_t)m);
+      std::copy(second.begin() + (std::ptrdiff_t)(b * m * m), second.begin() + (std::ptrdiff_t)((b + 1) * m * m), out[b].covariance.data.begin());
+    }
+    return out;
+  }
+
+ private:
+  void run(int mode, std::vector<Vector> *means, std::vector<double> *second) const {
+    const std::size_t count = fms_->size(), m = (*xs_)[0].size();
+    auto ctx = (*fms_)[0].get_fit().context;
+    std::vector<std::unique_ptr<detail::KernelHolder>> holders;
+    std::vector<detail::Flat> flats;
+    flats.reserve(count);
+    std::vector<const agp_kernel *> kernels(count);
+    std::vector<const agp_fit *> fits(count);
+    std::vector<const agp_features *> views(count);
+    for (std::size_t b = 0; b < count; ++b) {
+      const auto &fm = (*fms_)[b];
+      holders.emplace_back(new detail::KernelHolder(fm.get_model().get_covariance().program()));
+      flats.push_back(detail::flatten(fm.get_model().get_covariance(), (*xs_)[b]));
+      kernels[b] = holders[b]->k;
+      fits[b] = fm.get_fit().handle.get();
+    }
+    for (std::size_t b = 0; b < count; ++b) views[b] = &flats[b].view;
+    std::vector<double> mean(m * count);
+    const std::size_t per = mode == 1 ? m : m * m;
+    if (second) second->assign(mode == 0 ? 0 : per * count, 0.);
+    std::vector<int> status(count, AGP_OK);
+    detail::check(agp_predict_batch(ctx->ctx, (int)count, kernels.data(), fits.data(), views.data(), mode, mean.data(),
+                                    (std::int64_t)std::max<std::size_t>(m, 1), mode == 0 ? nullptr : second->data(),
+                                    (std::int64_t)std::max<std::size_t>(per, 1), AGP_HOST, status.data()),
+                  ctx->ctx, "agp_predict_batch");
+    for (std::size_t b = 0; b < count; ++b)
+      if (status[b] != AGP_OK) detail::check(status[b], ctx->ctx, ("agp_predict_batch: problem " + std::to_string(b)).c_str());
+    means->clear();
+    for (std::size_t b = 0; b < count; ++b) {
+      means->emplace_back(mean.begin() + (std::ptrdiff_t)(b * m), mean.begin() + (std::ptrdiff_t)((b + 1) * m));
+      (*fms_)[b].get_model().add_mean((*xs_)[b], &means->back());
+    }
+  }
+  const std::vector<FitModel<ModelType, FeatureType>> *fms_;
+  const std::vector<std::vector<P>> *xs_;
+};
+
+// (the arguments must outlive the returned object, like the FitModel of a Prediction)
+template <typename ModelType, typename FeatureType, typename P>
+BatchPrediction<ModelType, FeatureType, P> predict_batch(const std::vector<FitModel<ModelType, FeatureType>> &fit_models,
+                                                         const std::vector<std::vector<P>> &features_per_model) {
+  return BatchPrediction<ModelType, FeatureType, P>(&fit_models, &features_per_model);
+}
+
 // factories, gp.hpp:507-537
 template <typename CovFunc>
 GaussianProcessRegression<CovFunc, ZeroMean> gp_from_covariance(const CovFunc &cov,
