@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "common.h"
+#include "contract.h"
 
 namespace agp {
 // Device allocations of the entry points that build several medium-sized objects per call (sparse GP fits, dense factors,
@@ -154,6 +155,14 @@ int status_from_flags(const agp_context *ctx);
 // slot table of a gradient entry (gradient.hip): every slot a leaf node and a parameter the leaf has; n_tangent_columns:
 // the highest AGP_OP_SCALING tangent column + 1
 int check_slots(const agp_kernel *k, int n_slots, const agp_gradient_slot *slots, int *n_tangent_columns);
+// slots [g0, g0 + GRAD_GROUP) of the table as one group of the contraction (gradient.hip; slots past n_slots: node -1);
+// scaling[j]: slot j is an AGP_OP_SCALING leaf, whose tangent column is group.param[j].  Returns the number of used slots.
+int fill_slot_group(const agp_kernel *k, int n_slots, const agp_gradient_slot *slots, int g0,
+                    agp::TangentSlots<agp::GRAD_GROUP> &group, bool (&scaling)[agp::GRAD_GROUP]);
+// ntc tangent columns of n values (leading dimension ld) where the kernels read them (gradient.hip): host columns are
+// copied to *cursor with leading dimension round_up(n, 2) and the cursor moves past them, device ones are read in place
+int stage_tangents(agp_context *ctx, hipStream_t s, const double *tangents, long long ld, int location, long long n, int ntc,
+                   double **cursor, const double **dev, long long *ld_dev);
 namespace agp {
 // Gram + LL^T + forward substitution of y exactly as agp_nll makes them (api.hip: build_and_factor); on return the stream
 // is synchronised and ctx->h_flags / h_scalars hold the status and the log determinant

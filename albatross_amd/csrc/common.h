@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -25,18 +26,16 @@ constexpr int NBO = 512;
 constexpr int MB = 16;
 constexpr int NMB = NB / MB;  // 8 micro blocks per diagonal block
 
-struct FeatView {
-  const double *coords;  // n x dim row-major (device)
-  const long long *ids;  // n or nullptr
-  const double *scales;  // n x nsc column-major or nullptr
-  long long n;
-  int dim;
-  int nsc;
-  int meas;
-  long long sstride = 0;  // distance between scale columns (0: n) - lets a view cover a sub-range of a larger vector
-};
-
-__host__ __device__ inline long long scale_stride(const FeatView &f) { return f.sstride ? f.sstride : f.n; }
+// f(std::integral_constant<int, DIMP>{}) with the padded dimension DIMP (1, 2, 3, 4 or 8) of a dim-dimensional feature
+// set: the launch of a kernel template on Point<DIMP>
+template <class F>
+inline void dispatch_dim(int dim, F &&f) {
+  if (dim == 1) f(std::integral_constant<int, 1>{});
+  else if (dim == 2) f(std::integral_constant<int, 2>{});
+  else if (dim == 3) f(std::integral_constant<int, 3>{});
+  else if (dim == 4) f(std::integral_constant<int, 4>{});
+  else f(std::integral_constant<int, 8>{});
+}
 
 struct DeviceFeatures {
   FeatView v{};

@@ -36,6 +36,34 @@ struct Point {
   long long id;                      // equality id (only when ids are supplied)
 };
 
+struct FeatView {
+  const double *coords;  // n x dim row-major (device)
+  const long long *ids;  // n or nullptr
+  const double *scales;  // n x nsc column-major or nullptr
+  long long n;
+  int dim;
+  int nsc;
+  int meas;
+  long long sstride = 0;  // distance between scale columns (0: n) - lets a view cover a sub-range of a larger vector
+};
+
+__host__ __device__ inline long long scale_stride(const FeatView &f) { return f.sstride ? f.sstride : f.n; }
+
+// point i of X, zero-padded to DIMP coordinates
+template <int DIMP>
+__device__ __forceinline__ void load_point(const FeatView &X, long long i, bool need_norm, Point<DIMP> &p) {
+  double nn = 0.;
+#pragma unroll
+  for (int d = 0; d < DIMP; ++d) {
+    p.c[d] = d < X.dim ? X.coords[i * X.dim + d] : 0.;
+    nn += p.c[d] * p.c[d];
+  }
+  p.norm = need_norm ? sqrt(nn) : 0.;
+#pragma unroll
+  for (int k = 0; k < AGP_MAX_SCALE_COLUMNS; ++k) p.s[k] = k < X.nsc ? X.scales[(long long)k * scale_stride(X) + i] : 0.;
+  p.id = X.ids ? X.ids[i] : -1;
+}
+
 // exp(-t) for t >= 0 (NaN in -> NaN out, t = +inf -> 0).  Every radial kernel of the reference ends in such an exp
 // (radial.hpp:25-33,191-198,289-297,461-470) and the Gram kernels are VALU-bound on it: the library exp is ~35
 // instructions per call, half of them v_mov of 64-bit literals feeding v_fmac.  This one is 22: Cody-Waite reduction

@@ -8,9 +8,8 @@
 // tune/finite_difference.hpp:37-90): P + 1 evaluations for P parameters, accurate to the likelihood's error over eps.
 // Here: one fit (build_and_factor, api.hip), R = L^-1 (forward_solve_mat_lookahead on a triangular right-hand side,
 // as inverse_diagonal_device does), K^-1 = R^T R into the factor's buffer (rtr_lower_kernel below), and one contraction
-// of W's lower triangle against the tangent form of the covariance program (cov_eval.h: eval_pair_tangent) that never
-// stores dK / dtheta.  Cost: a fit plus ~2 N^3 / 3 flop, whatever P is; no float atomics anywhere, so two calls give
-// bit-identical gradients.
+// of W's lower triangle against the tangent form of the covariance program (contract.h: contract_tile, the body shared
+// with sparse_gradient.hip).  Cost: a fit plus ~2 N^3 / 3 flop, whatever P is.
 //
 // agp_loo_nll_gradient, the leave-one-out likelihood metric (LeaveOneOutLikelihood, evaluation/model_metrics.hpp:59-72)
 // and its gradient (GPML 5.4.2, eqs. 5.10-5.13, with the truth's variance s added as prediction_metrics.hpp:113-119 does):
@@ -29,6 +28,7 @@
 #include <vector>
 
 #include "api_internal.h"
+#include "contract.h"
 #include "cov_eval.h"
 #include "gemm_tiles.h"
 #include "pub.h"
@@ -43,12 +43,8 @@ namespace agp {
 // half.
 __global__ __launch_bounds__(GEMM_THREADS, 2) void rtr_lower_kernel(GemmArgs g) {
   __shared__ double lds[2 * 2 * GK * GLD];
-  // row-major enumeration of the lower tiles: id = bi (bi + 1) / 2 + bj
-  const long long id = blockIdx.x;
-  int bi = (int)((sqrt(8. * (double)id + 1.) - 1.) * 0.5);
-  while ((long long)bi * (bi + 1) / 2 > id) --bi;
-  while ((long long)(bi + 1) * (bi + 2) / 2 <= id) ++bi;
-  const int bj = (int)(id - (long long)bi * (bi + 1) / 2);
+  int bi, bj;
+  lower_tile(blockIdx.x, bi, bj);
   const long long k0 = (long long)bi * GT;
   const long long b = blockIdx.y;  // problem of a batched launch (batch_* = 0: one problem)
   GemmArgs t = g;
@@ -78,11 +74,7 @@ void launch_rtr_lower(hipStream_t s, const double *R, long long ldr, long long n
   launch_rtr_lower_batched(s, R, ldr, 0, n, C, ldc, 0, 1);
 }
 
-// ---- contraction: partial[tile][g] = sum over the tile's pairs i >= j of w_ij dk_ij / dslot_g ------------------------
-constexpr int GRAD_GROUP = 4;   // slots per walk of the tangent program (K^-1 is read ceil(P / GRAD_GROUP) times)
-constexpr int CT = 64;          // contraction tile edge
-constexpr int CT_THREADS = 256;
-
+// ---- contraction of a weight's lower triangle (contract.h): tile blockIdx.x of the row-major lower enumeration ----
 struct ContractArgs {
   TangentSlots<GRAD_GROUP> slots;
   const double *tang[GRAD_GROUP];  // AGP_OP_SCALING slot g: its tangent column (n values), else nullptr
@@ -93,100 +85,23 @@ struct ContractArgs {
   double *partial;                 // [tile][GRAD_GROUP]
 };
 
-template <int DIMP>
-__device__ __forceinline__ void load_point(const FeatView &X, long long i, bool need_norm, Point<DIMP> &p) {
-  double nn = 0.;
-#pragma unroll
-  for (int d = 0; d < DIMP; ++d) {
-    p.c[d] = d < X.dim ? X.coords[i * X.dim + d] : 0.;
-    nn += p.c[d] * p.c[d];
-  }
-  p.norm = need_norm ? sqrt(nn) : 0.;
-#pragma unroll
-  for (int k = 0; k < AGP_MAX_SCALE_COLUMNS; ++k) p.s[k] = k < X.nsc ? X.scales[(long long)k * scale_stride(X) + i] : 0.;
-  p.id = X.ids ? X.ids[i] : -1;
-}
-
-// One workgroup per 64 x 64 lower tile of K^-1; lane = row i (coalesced reads of K^-1), each wave walks 16 columns j,
-// whose point is the same for the whole wave.  LOO: the weight of agp_loo_nll_gradient, S_ij - 1/2 (u_i alpha_j +
-// alpha_i u_j), in place of K^-1_ij - alpha_i alpha_j (the NLL instantiation is unchanged).  The body of both the
-// single-problem kernel and the batched one (tile blockIdx.x, its sums to a.partial[tile][g]).
+// The body of both the single-problem kernel and the batched one.  LOO: the weight of agp_loo_nll_gradient in place of
+// K^-1_ij - alpha_i alpha_j.
 template <int DIMP, bool LOO>
-__device__ __forceinline__ void contract_tile(const DevProgram *__restrict__ P, const FeatView &X, const ContractArgs &a) {
-  const long long id = blockIdx.x;
-  int bi = (int)((sqrt(8. * (double)id + 1.) - 1.) * 0.5);
-  while ((long long)bi * (bi + 1) / 2 > id) --bi;
-  while ((long long)(bi + 1) * (bi + 2) / 2 <= id) ++bi;
-  const int bj = (int)(id - (long long)bi * (bi + 1) / 2);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long long n = X.n;
-  const long long i = (long long)bi * CT + lane;
-  const bool need_norm = (P->metric_mask & ((1 << AGP_METRIC_RADIAL) | (1 << AGP_METRIC_ANGULAR))) != 0;
-  double acc[GRAD_GROUP];
-#pragma unroll
-  for (int g = 0; g < GRAD_GROUP; ++g) acc[g] = 0.;
-  if (i < n) {
-    Point<DIMP> x;
-    load_point<DIMP>(X, i, need_norm, x);
-    double tx[GRAD_GROUP];
-#pragma unroll
-    for (int g = 0; g < GRAD_GROUP; ++g) tx[g] = a.tang[g] ? a.tang[g][i] : 0.;
-    const double ai = a.alpha[i];
-    const double ui = LOO ? a.u[i] : 0.;
-    for (int c = wave; c < CT; c += CT_THREADS / 64) {
-      const long long j = (long long)bj * CT + c;
-      if (j >= n || j > i) continue;
-      Point<DIMP> y;
-      load_point<DIMP>(X, j, need_norm, y);
-      double ty[GRAD_GROUP];
-#pragma unroll
-      for (int g = 0; g < GRAD_GROUP; ++g) ty[g] = a.tang[g] ? a.tang[g][j] : 0.;
-      double w;
-      if constexpr (LOO) w = (i == j ? 1. : 2.) * (a.C[i + j * a.ldc] - 0.5 * (ui * a.alpha[j] + ai * a.u[j]));
-      else w = (i == j ? 1. : 2.) * (a.C[i + j * a.ldc] - ai * a.alpha[j]);
-      double dk[GRAD_GROUP];
-      eval_pair_tangent<DIMP, GRAD_GROUP>(P, a.slots, x, y, tx, ty, X.ids != nullptr, X.meas != 0, dk);
-#pragma unroll
-      for (int g = 0; g < GRAD_GROUP; ++g) acc[g] += w * dk[g];
-    }
-  }
-  // fixed-order reduction: butterfly inside the wave, then the four waves in order
-  __shared__ double red[CT_THREADS / 64][GRAD_GROUP];
-#pragma unroll
-  for (int g = 0; g < GRAD_GROUP; ++g) {
-    double v = acc[g];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (lane == 0) red[wave][g] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < GRAD_GROUP) {
-    const int g = threadIdx.x;
-    double v = red[0][g];
-#pragma unroll
-    for (int w = 1; w < CT_THREADS / 64; ++w) v += red[w][g];
-    a.partial[id * GRAD_GROUP + g] = v;
-  }
+__device__ __forceinline__ void contract_lower(const DevProgram *__restrict__ P, const FeatView &X, const ContractArgs &a) {
+  ContractTile t;
+  lower_tile(blockIdx.x, t.bi, t.bj);
+  t.rbase = t.cbase = 0;
+  t.nrl = t.ncl = X.n;
+  t.lower = true;
+  if constexpr (LOO) contract_tile<DIMP>(P, a.slots, X, X, t, a.tang, a.tang, LooWeight{a.C, a.ldc, a.alpha, a.u}, blockIdx.x, a.partial);
+  else contract_tile<DIMP>(P, a.slots, X, X, t, a.tang, a.tang, NllWeight{a.C, a.ldc, a.alpha}, blockIdx.x, a.partial);
 }
 
 template <int DIMP, bool LOO = false>
 __global__ __launch_bounds__(CT_THREADS) void nll_grad_contract_kernel(const DevProgram *__restrict__ P, FeatView X,
                                                                        ContractArgs a) {
-  contract_tile<DIMP, LOO>(P, X, a);
-}
-
-// sum over tiles of partial[tile][g] in a fixed order (256 strided partial sums, then a tree); the value is in red[0]
-__device__ __forceinline__ double reduce_partials(const double *__restrict__ partial, long long tiles, int g) {
-  double v = 0.;
-  for (long long t = threadIdx.x; t < tiles; t += 256) v += partial[t * GRAD_GROUP + g];
-  __shared__ double red[256];
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int h = 128; h > 0; h >>= 1) {
-    if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
-    __syncthreads();
-  }
-  return red[0];
+  contract_lower<DIMP, LOO>(P, X, a);
 }
 
 // out[base + g] = scale * sum over tiles of partial[tile][g], in a fixed order; one workgroup per slot of the group
@@ -230,7 +145,7 @@ __global__ __launch_bounds__(CT_THREADS) void nll_grad_contract_batched_kernel(c
   a.C = d.C; a.ldc = d.ldc; a.alpha = d.alpha; a.u = nullptr;
   a.partial = d.partial + (long long)grp * tiles * GRAD_GROUP;
   const FeatView X = d.X;
-  contract_tile<DIMP, false>(&d.prog, X, a);
+  contract_lower<DIMP, false>(&d.prog, X, a);
 }
 
 // out[b * ldo + slot] = scale * sum over tiles of problem b's partials of that slot (one workgroup per (slot, problem))
@@ -244,29 +159,18 @@ __global__ __launch_bounds__(256) void nll_grad_reduce_batched_kernel(const Cont
   if (threadIdx.x == 0) out[b * ldo + slot] = scale * v;
 }
 
-static long long contract_tiles(long long n) {
-  const long long t = (n + CT - 1) / CT;
-  return t * (t + 1) / 2;
-}
-
 template <bool LOO>
 static void launch_contract(hipStream_t s, const DevProgram *P, const FeatView &X, const ContractArgs &a, long long tiles) {
-  const dim3 grid((unsigned)tiles), block(CT_THREADS);
-  const int dim = X.dim;
-  if (dim == 1) hipLaunchKernelGGL((nll_grad_contract_kernel<1, LOO>), grid, block, 0, s, P, X, a);
-  else if (dim == 2) hipLaunchKernelGGL((nll_grad_contract_kernel<2, LOO>), grid, block, 0, s, P, X, a);
-  else if (dim == 3) hipLaunchKernelGGL((nll_grad_contract_kernel<3, LOO>), grid, block, 0, s, P, X, a);
-  else if (dim == 4) hipLaunchKernelGGL((nll_grad_contract_kernel<4, LOO>), grid, block, 0, s, P, X, a);
-  else hipLaunchKernelGGL((nll_grad_contract_kernel<8, LOO>), grid, block, 0, s, P, X, a);
+  dispatch_dim(X.dim, [&](auto D) {
+    hipLaunchKernelGGL((nll_grad_contract_kernel<decltype(D)::value, LOO>), dim3((unsigned)tiles), dim3(CT_THREADS), 0, s, P, X, a);
+  });
 }
 
 static void launch_contract_batched(hipStream_t s, int dim_max, const ContractDesc *D, long long tiles, long long count, int groups) {
-  const dim3 grid((unsigned)tiles, (unsigned)count, (unsigned)groups), block(CT_THREADS);
-  if (dim_max == 1) hipLaunchKernelGGL(nll_grad_contract_batched_kernel<1>, grid, block, 0, s, D, tiles);
-  else if (dim_max == 2) hipLaunchKernelGGL(nll_grad_contract_batched_kernel<2>, grid, block, 0, s, D, tiles);
-  else if (dim_max == 3) hipLaunchKernelGGL(nll_grad_contract_batched_kernel<3>, grid, block, 0, s, D, tiles);
-  else if (dim_max == 4) hipLaunchKernelGGL(nll_grad_contract_batched_kernel<4>, grid, block, 0, s, D, tiles);
-  else hipLaunchKernelGGL(nll_grad_contract_batched_kernel<8>, grid, block, 0, s, D, tiles);
+  dispatch_dim(dim_max, [&](auto DIMP) {
+    hipLaunchKernelGGL(nll_grad_contract_batched_kernel<decltype(DIMP)::value>, dim3((unsigned)tiles, (unsigned)count, (unsigned)groups),
+                       dim3(CT_THREADS), 0, s, D, tiles);
+  });
 }
 
 // ---- leave-one-out terms -----------------------------------------------------------------------------------------
@@ -337,11 +241,8 @@ __global__ __launch_bounds__(256) void loo_form_g_kernel(const double *__restric
 // not matter.  Flop: N^3.  The whole diagonal tile is written.
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gtg_lower_kernel(GemmArgs g) {
   __shared__ double lds[2 * 2 * GK * GLD];
-  const long long id = blockIdx.x;
-  int bi = (int)((sqrt(8. * (double)id + 1.) - 1.) * 0.5);
-  while ((long long)bi * (bi + 1) / 2 > id) --bi;
-  while ((long long)(bi + 1) * (bi + 2) / 2 <= id) ++bi;
-  const int bj = (int)(id - (long long)bi * (bi + 1) / 2);
+  int bi, bj;
+  lower_tile(blockIdx.x, bi, bj);
   gemm_nt_sub_tile<true, true, true>(g, bi, bj, lds);
 }
 
@@ -377,6 +278,32 @@ int check_slots(const agp_kernel *k, int n_slots, const agp_gradient_slot *slots
     if (n_params < 0 && param + 1 > ntc) ntc = param + 1;
   }
   *n_tangent_columns = ntc;
+  return AGP_OK;
+}
+
+int fill_slot_group(const agp_kernel *k, int n_slots, const agp_gradient_slot *slots, int g0, TangentSlots<GRAD_GROUP> &group,
+                    bool (&scaling)[GRAD_GROUP]) {
+  const int cnt = n_slots - g0 < GRAD_GROUP ? n_slots - g0 : GRAD_GROUP;
+  for (int j = 0; j < GRAD_GROUP; ++j) {
+    const bool used = j < cnt;
+    group.node[j] = used ? slots[g0 + j].node : -1;
+    group.param[j] = used ? slots[g0 + j].param : 0;
+    scaling[j] = used && k->prog.nodes[group.node[j]].op == AGP_OP_SCALING;
+  }
+  return cnt > 0 ? cnt : 0;
+}
+
+int stage_tangents(agp_context *ctx, hipStream_t s, const double *tangents, long long ld, int location, long long n, int ntc,
+                   double **cursor, const double **dev, long long *ld_dev) {
+  *dev = tangents;
+  *ld_dev = ld;
+  if (ntc <= 0 || location != AGP_HOST) return AGP_OK;
+  const long long np2 = round_up(n, 2);
+  AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(*cursor, sizeof(double) * (size_t)np2, tangents, sizeof(double) * (size_t)ld,
+                                      sizeof(double) * (size_t)n, (size_t)ntc, hipMemcpyHostToDevice, s));
+  *dev = *cursor;
+  *ld_dev = np2;
+  *cursor += (size_t)np2 * (size_t)ntc;
   return AGP_OK;
 }
 
@@ -418,7 +345,7 @@ static int gradient_setup(agp_context_impl *ctx, const agp_kernel *k, const agp_
   g.invd = g.A + (size_t)lda * (size_t)n;
   g.z = g.invd + (size_t)nblk * (36 * MB * MB);
   g.yvar_d = y_var ? g.z + round_up(n, 2) : nullptr;
-  g.tiles = contract_tiles(n);
+  g.tiles = lower_tiles(n);
   const size_t r_elems = (size_t)lda * (size_t)n, bs_elems = backsolve_ws_elems(n);
   const size_t part_elems = (size_t)g.tiles * GRAD_GROUP, grad_elems = (size_t)round_up(AGP_MAX_GRADIENT_SLOTS, 2);
   const bool tang_copy = ntc > 0 && x->location == AGP_HOST;
@@ -431,15 +358,8 @@ static int gradient_setup(agp_context_impl *ctx, const agp_kernel *k, const agp_
   g.partial = g.bs_ws + bs_elems;
   g.grad_d = g.partial + part_elems;
   g.extra = g.grad_d + grad_elems + tang_elems;
-  g.tang_d = tangents;
-  g.ldt_d = ldt;
-  if (tang_copy) {
-    double *t = g.grad_d + grad_elems;
-    AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(t, sizeof(double) * (size_t)round_up(n, 2), tangents, sizeof(double) * (size_t)ldt,
-                                        sizeof(double) * (size_t)n, (size_t)ntc, hipMemcpyHostToDevice, s));
-    g.tang_d = t;
-    g.ldt_d = round_up(n, 2);
-  }
+  double *tcur = g.grad_d + grad_elems;
+  if ((st = stage_tangents(ctx, s, tangents, ldt, x->location, n, ntc, &tcur, &g.tang_d, &g.ldt_d)) != AGP_OK) return st;
 
   if ((st = to_device(ctx, x, false, &g.dx)) != AGP_OK) return st;
   if ((st = vector_to_device(ctx, y, n, x->location, g.z)) != AGP_OK) return st;
@@ -469,14 +389,9 @@ static void contract_slots(hipStream_t s, const agp_kernel *k, int n_slots, cons
   for (int g0 = 0; g0 < n_slots; g0 += GRAD_GROUP) {
     ContractArgs ca;
     ca.C = g.A; ca.ldc = g.lda; ca.alpha = g.z; ca.u = u; ca.partial = g.partial;
-    const int cnt = n_slots - g0 < GRAD_GROUP ? n_slots - g0 : GRAD_GROUP;
-    for (int j = 0; j < GRAD_GROUP; ++j) {
-      const bool used = j < cnt;
-      const int node = used ? slots[g0 + j].node : -1, param = used ? slots[g0 + j].param : 0;
-      ca.slots.node[j] = node;
-      ca.slots.param[j] = param;
-      ca.tang[j] = (used && k->prog.nodes[node].op == AGP_OP_SCALING) ? g.tang_d + (size_t)param * (size_t)g.ldt_d : nullptr;
-    }
+    bool scaling[GRAD_GROUP];
+    const int cnt = fill_slot_group(k, n_slots, slots, g0, ca.slots, scaling);
+    for (int j = 0; j < GRAD_GROUP; ++j) ca.tang[j] = scaling[j] ? g.tang_d + (size_t)ca.slots.param[j] * (size_t)g.ldt_d : nullptr;
     launch_contract<LOO>(s, g.dprog, g.xm, ca, g.tiles);
     hipLaunchKernelGGL(nll_grad_reduce_kernel, dim3(GRAD_GROUP), dim3(256), 0, s, g.partial, g.tiles, cnt, scale, g.grad_d + g0);
   }
@@ -624,7 +539,7 @@ int agp_nll_gradient_batch(agp_context *c, int count, const agp_kernel *const *k
     if (features[b]->dim > dim_max) dim_max = features[b]->dim;
   }
   if (max_slots > 0 && (!grad_nll || ldg < max_slots)) return AGP_ERR_INVALID_ARGUMENT;
-  const long long tiles = contract_tiles(n), rtr_tiles = ((n + GT - 1) / GT) * ((n + GT - 1) / GT + 1) / 2;
+  const long long tiles = lower_tiles(n), rtr_tiles = ((n + GT - 1) / GT) * ((n + GT - 1) / GT + 1) / 2;
   const int groups = (max_slots + GRAD_GROUP - 1) / GRAD_GROUP;
   if (tiles * CT_THREADS > (long long)UINT_MAX || rtr_tiles * GEMM_THREADS > (long long)UINT_MAX ||
       tiles * count > (long long)UINT_MAX || rtr_tiles * count > (long long)UINT_MAX)
@@ -683,16 +598,7 @@ int agp_nll_gradient_batch(agp_context *c, int count, const agp_kernel *const *k
     double *tcur = tang_d;
     for (int b = 0; b < count; ++b) {
       if (ntc[(size_t)b] == 0) continue;
-      if (loc == AGP_HOST) {
-        AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(tcur, sizeof(double) * (size_t)np2, tangents[b], sizeof(double) * (size_t)ldt,
-                                            sizeof(double) * (size_t)n, (size_t)ntc[(size_t)b], hipMemcpyHostToDevice, s));
-        tcol[(size_t)b] = tcur;
-        tld[(size_t)b] = np2;
-        tcur += (size_t)ntc[(size_t)b] * (size_t)np2;
-      } else {
-        tcol[(size_t)b] = tangents[b];
-        tld[(size_t)b] = ldt;
-      }
+      if ((st = stage_tangents(ctx, s, tangents[b], ldt, loc, n, ntc[(size_t)b], &tcur, &tcol[(size_t)b], &tld[(size_t)b])) != AGP_OK) return st;
     }
   }
   // features: problems usually share one feature array (parameter vectors of one model): upload it once
@@ -748,13 +654,11 @@ int agp_nll_gradient_batch(agp_context *c, int count, const agp_kernel *const *k
     d.alpha = z + (size_t)b * (size_t)np2;
     d.partial = partial + (size_t)b * (size_t)part_per;
     d.n_slots = n_slots[b];
-    for (int j = 0; j < GRAD_GROUPS_MAX * GRAD_GROUP; ++j) {
-      const bool used = j < n_slots[b];
-      const int node = used ? slots[b][j].node : -1, param = used ? slots[b][j].param : 0;
-      d.slots[j / GRAD_GROUP].node[j % GRAD_GROUP] = node;
-      d.slots[j / GRAD_GROUP].param[j % GRAD_GROUP] = param;
-      d.tang[j] = (used && kernels[b]->prog.nodes[node].op == AGP_OP_SCALING) ? tcol[(size_t)b] + (size_t)param * (size_t)tld[(size_t)b]
-                                                                              : nullptr;
+    for (int grp = 0; grp < GRAD_GROUPS_MAX; ++grp) {
+      bool scaling[GRAD_GROUP];
+      fill_slot_group(kernels[b], n_slots[b], n_slots[b] > 0 ? slots[b] : nullptr, grp * GRAD_GROUP, d.slots[grp], scaling);
+      for (int j = 0; j < GRAD_GROUP; ++j)
+        d.tang[grp * GRAD_GROUP + j] = scaling[j] ? tcol[(size_t)b] + (size_t)d.slots[grp].param[j] * (size_t)tld[(size_t)b] : nullptr;
     }
   }
   AGP_HIP_CHECK(ctx, hipMemcpyAsync(desc_d, desc_h, sizeof(ContractDesc) * (size_t)count, hipMemcpyHostToDevice, s));

@@ -699,12 +699,7 @@ __global__ __launch_bounds__(256) void gram_diag_kernel(const DevProgram *__rest
 void launch_gram_diagonal(hipStream_t s, const DevProgram *P, const FeatView &X, double *out) {
   if (X.n == 0) return;
   dim3 grid((unsigned)((X.n + 255) / 256));
-  const int dim = X.dim;
-  if (dim == 1) hipLaunchKernelGGL(gram_diag_kernel<1>, grid, dim3(256), 0, s, P, X, out);
-  else if (dim == 2) hipLaunchKernelGGL(gram_diag_kernel<2>, grid, dim3(256), 0, s, P, X, out);
-  else if (dim == 3) hipLaunchKernelGGL(gram_diag_kernel<3>, grid, dim3(256), 0, s, P, X, out);
-  else if (dim == 4) hipLaunchKernelGGL(gram_diag_kernel<4>, grid, dim3(256), 0, s, P, X, out);
-  else hipLaunchKernelGGL(gram_diag_kernel<8>, grid, dim3(256), 0, s, P, X, out);
+  dispatch_dim(X.dim, [&](auto D) { hipLaunchKernelGGL(gram_diag_kernel<decltype(D)::value>, grid, dim3(256), 0, s, P, X, out); });
 }
 
 // ---- fused predictive mean: mean_j = sum_i k(x_i, xs_j) alpha_i ----------------

@@ -16,10 +16,9 @@
 //   E^T = L_u^-T P,   q = E^T alpha
 //   -(H E)^T = L1^-T L2^-T N + [E_g^T bd(G)_g]_g + q alpha^T          (in place over N)
 //   -W_uu = E^T (H E)                                                 (split-K slabs over the observations)
-// followed by three contractions of those weights against the tangent form of the covariance program (cov_eval.h:
-// eval_pair_tangent) with the measurement / equality semantics of the Gram call that built each matrix: group blocks
-// (measurement, measurement), k(u, x) (plain, measurement), k(u, u) (plain, plain).  No float atomics: per-tile partial
-// sums and fixed-order reductions, so two calls give bit-identical results.
+// followed by three contractions of those weights against the tangent form of the covariance program (contract.h:
+// contract_tile, the body shared with gradient.hip) with the measurement / equality semantics of the Gram call that
+// built each matrix: group blocks (measurement, measurement), k(u, x) (plain, measurement), k(u, u) (plain, plain).
 //
 // Workspace beyond the fit's pool (K_uf | P | slabs): ONE more ldk x (n + m) slab (Q1^T no longer shares P's region),
 // two sets of s_g x s_g group slabs (R_g and bd(G)_g: n * s doubles each for groups of s) and O(n + m^2) vectors.
@@ -32,15 +31,12 @@
 
 #include "api_internal.h"
 #include "sparse_internal.h"
+#include "contract.h"
 #include "cov_eval.h"
 
 using namespace agp;
 
 namespace {
-
-constexpr int SG_GROUP = 4;    // slots per walk of the tangent program (every weight is read ceil(P / SG_GROUP) times)
-constexpr int ST = 64;         // contraction tile edge
-constexpr int ST_THREADS = 256;
 
 struct DevFree {
   void operator()(void *p) const { (void)dev_free(p); }
@@ -132,156 +128,69 @@ __global__ __launch_bounds__(1024) void strided_sum_kernel(const double *__restr
 //   2  group blocks: tile ids run over the lower tiles of every group's s_g x s_g slab (tstart[g] = first tile of group
 //      g); rows and columns are the points off[g] .. off[g + 1] of ONE feature set, the weight slab of group g is
 //      W + woff[g] with leading dimension wld[g]
-// lane = row (coalesced reads of the weight's column), each wave walks 16 columns whose point is wave-uniform, as the
-// dense contraction (gradient.hip: contract_tile).
 struct SparseContractArgs {
-  TangentSlots<SG_GROUP> slots;
-  const double *tr[SG_GROUP];  // AGP_OP_SCALING slot g: its tangent column at the row features, else nullptr
-  const double *tc[SG_GROUP];  // ... at the column features
+  TangentSlots<GRAD_GROUP> slots;
+  const double *tr[GRAD_GROUP];  // AGP_OP_SCALING slot g: its tangent column at the row features, else nullptr
+  const double *tc[GRAD_GROUP];  // ... at the column features
   const double *W;
   long long ldw;
   long long tiles_r;           // mode 0: row tiles
   const long long *off, *woff, *wld, *tstart;  // mode 2
   long long G;
-  double *partial;             // [tile][SG_GROUP]
+  double *partial;             // [tile][GRAD_GROUP]
   int mode;
 };
 
 template <int DIMP>
-__device__ __forceinline__ void load_pt(const FeatView &X, long long i, bool need_norm, Point<DIMP> &p) {
-  double nn = 0.;
-#pragma unroll
-  for (int d = 0; d < DIMP; ++d) {
-    p.c[d] = d < X.dim ? X.coords[i * X.dim + d] : 0.;
-    nn += p.c[d] * p.c[d];
-  }
-  p.norm = need_norm ? sqrt(nn) : 0.;
-#pragma unroll
-  for (int k = 0; k < AGP_MAX_SCALE_COLUMNS; ++k) p.s[k] = k < X.nsc ? X.scales[(long long)k * scale_stride(X) + i] : 0.;
-  p.id = X.ids ? X.ids[i] : -1;
-}
-
-__device__ __forceinline__ void lower_tile(long long id, int &bi, int &bj) {
-  bi = (int)((sqrt(8. * (double)id + 1.) - 1.) * 0.5);
-  while ((long long)bi * (bi + 1) / 2 > id) --bi;
-  while ((long long)(bi + 1) * (bi + 2) / 2 <= id) ++bi;
-  bj = (int)(id - (long long)bi * (bi + 1) / 2);
-}
-
-template <int DIMP>
-__global__ __launch_bounds__(ST_THREADS) void sparse_contract_kernel(const DevProgram *__restrict__ P, FeatView R, FeatView C,
+__global__ __launch_bounds__(CT_THREADS) void sparse_contract_kernel(const DevProgram *__restrict__ P, FeatView R, FeatView C,
                                                                      SparseContractArgs a) {
   const long long id = blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // the tile: local row / column ranges, where they start in the feature sets, and the weight they index
-  long long rbase = 0, cbase = 0, nrl, ncl, ldw = a.ldw;
-  const double *W = a.W;
-  int bi, bj;
-  const bool lower = a.mode != 0;
+  ContractTile t;
+  t.rbase = t.cbase = 0;
+  t.lower = a.mode != 0;
+  MatrixWeight w{a.W, a.ldw};
   if (a.mode == 0) {
-    bi = (int)(id % a.tiles_r);
-    bj = (int)(id / a.tiles_r);
-    nrl = R.n; ncl = C.n;
+    t.bi = (int)(id % a.tiles_r);
+    t.bj = (int)(id / a.tiles_r);
+    t.nrl = R.n; t.ncl = C.n;
   } else if (a.mode == 1) {
-    lower_tile(id, bi, bj);
-    nrl = ncl = R.n;
+    lower_tile(id, t.bi, t.bj);
+    t.nrl = t.ncl = R.n;
   } else {
     const long long g = find_group(a.tstart, a.G, id);
-    lower_tile(id - a.tstart[g], bi, bj);
-    rbase = cbase = a.off[g];
-    nrl = ncl = a.off[g + 1] - a.off[g];
-    W = a.W + a.woff[g];
-    ldw = a.wld[g];
+    lower_tile(id - a.tstart[g], t.bi, t.bj);
+    t.rbase = t.cbase = a.off[g];
+    t.nrl = t.ncl = a.off[g + 1] - a.off[g];
+    w = MatrixWeight{a.W + a.woff[g], a.wld[g]};
   }
-  const long long il = (long long)bi * ST + lane;
-  const bool need_norm = (P->metric_mask & ((1 << AGP_METRIC_RADIAL) | (1 << AGP_METRIC_ANGULAR))) != 0;
-  const bool have_ids = R.ids != nullptr && C.ids != nullptr, both_meas = R.meas != 0 && C.meas != 0;
-  double acc[SG_GROUP];
-#pragma unroll
-  for (int g = 0; g < SG_GROUP; ++g) acc[g] = 0.;
-  if (il < nrl) {
-    Point<DIMP> x;
-    load_pt<DIMP>(R, rbase + il, need_norm, x);
-    double tx[SG_GROUP];
-#pragma unroll
-    for (int g = 0; g < SG_GROUP; ++g) tx[g] = a.tr[g] ? a.tr[g][rbase + il] : 0.;
-    for (int c = wave; c < ST; c += ST_THREADS / 64) {
-      const long long jl = (long long)bj * ST + c;
-      if (jl >= ncl || (lower && jl > il)) continue;
-      Point<DIMP> y;
-      load_pt<DIMP>(C, cbase + jl, need_norm, y);
-      double ty[SG_GROUP];
-#pragma unroll
-      for (int g = 0; g < SG_GROUP; ++g) ty[g] = a.tc[g] ? a.tc[g][cbase + jl] : 0.;
-      const double w = ((lower && il != jl) ? 2. : 1.) * W[il + jl * ldw];
-      double dk[SG_GROUP];
-      eval_pair_tangent<DIMP, SG_GROUP>(P, a.slots, x, y, tx, ty, have_ids, both_meas, dk);
-#pragma unroll
-      for (int g = 0; g < SG_GROUP; ++g) acc[g] += w * dk[g];
-    }
-  }
-  // fixed-order reduction: butterfly inside the wave, then the four waves in order
-  __shared__ double red[ST_THREADS / 64][SG_GROUP];
-#pragma unroll
-  for (int g = 0; g < SG_GROUP; ++g) {
-    double v = acc[g];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    if (lane == 0) red[wave][g] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < SG_GROUP) {
-    const int g = threadIdx.x;
-    double v = red[0][g];
-#pragma unroll
-    for (int w = 1; w < ST_THREADS / 64; ++w) v += red[w][g];
-    a.partial[id * SG_GROUP + g] = v;
-  }
+  contract_tile<DIMP>(P, a.slots, R, C, t, a.tr, a.tc, w, id, a.partial);
 }
 
 void launch_sparse_contract(hipStream_t s, const DevProgram *P, const FeatView &R, const FeatView &C, const SparseContractArgs &a,
                             long long tiles) {
   if (tiles <= 0) return;
-  const dim3 grid((unsigned)tiles), block(ST_THREADS);
-  const int dim = R.dim;
-  if (dim == 1) hipLaunchKernelGGL(sparse_contract_kernel<1>, grid, block, 0, s, P, R, C, a);
-  else if (dim == 2) hipLaunchKernelGGL(sparse_contract_kernel<2>, grid, block, 0, s, P, R, C, a);
-  else if (dim == 3) hipLaunchKernelGGL(sparse_contract_kernel<3>, grid, block, 0, s, P, R, C, a);
-  else if (dim == 4) hipLaunchKernelGGL(sparse_contract_kernel<4>, grid, block, 0, s, P, R, C, a);
-  else hipLaunchKernelGGL(sparse_contract_kernel<8>, grid, block, 0, s, P, R, C, a);
+  dispatch_dim(R.dim, [&](auto D) {
+    hipLaunchKernelGGL(sparse_contract_kernel<decltype(D)::value>, dim3((unsigned)tiles), dim3(CT_THREADS), 0, s, P, R, C, a);
+  });
 }
 
-// out[g] = -1/2 S_blocks[g] - S_fu[g] - 1/2 S_uu[g], every S the sum of its tiles' partials in a fixed order (256 strided
-// partial sums, then a tree); one workgroup per slot of the group.  The signs: the weights held are -bd(G), -(H E)^T, -W_uu.
+// out[g] = -1/2 S_blocks[g] - S_fu[g] - 1/2 S_uu[g], every S the sum of its tiles' partials in a fixed order
+// (reduce_partials); one workgroup per slot of the group.  The signs: the weights held are -bd(G), -(H E)^T, -W_uu.
 __global__ __launch_bounds__(256) void sparse_grad_reduce_kernel(const double *__restrict__ p0, long long t0,
                                                                  const double *__restrict__ p1, long long t1,
                                                                  const double *__restrict__ p2, long long t2, int count,
                                                                  double *__restrict__ out) {
   const int g = blockIdx.x;
   if (g >= count) return;
-  __shared__ double red[256];
   const double *parts[3] = {p0, p1, p2};
   const long long tiles[3] = {t0, t1, t2};
   const double scale[3] = {-0.5, -1.0, -0.5};
   double total = 0.;
   for (int q = 0; q < 3; ++q) {
-    double v = 0.;
-    for (long long t = threadIdx.x; t < tiles[q]; t += 256) v += parts[q][t * SG_GROUP + g];
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-      if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
-      __syncthreads();
-    }
-    total += scale[q] * red[0];
+    total += scale[q] * reduce_partials(parts[q], tiles[q], g);
     __syncthreads();
   }
   if (threadIdx.x == 0) out[g] = total;
-}
-
-long long lower_tiles(long long n) {
-  const long long t = (n + ST - 1) / ST;
-  return t * (t + 1) / 2;
 }
 
 }  // namespace
@@ -346,7 +255,7 @@ int agp_sparse_nll_gradient(agp_context *c, const agp_kernel *k, const agp_featu
     tiles_blocks += lower_tiles(sg);
   }
   h_off[G] = n; h_roff[G] = r_elems; h_rld[G] = 0; h_tstart[G] = tiles_blocks;
-  const long long tiles_r = (m + ST - 1) / ST, tiles_fu = tiles_r * ((n + ST - 1) / ST), tiles_uu = lower_tiles(m);
+  const long long tiles_r = (m + CT - 1) / CT, tiles_fu = tiles_r * ((n + CT - 1) / CT), tiles_uu = lower_tiles(m);
   if (tiles_blocks > 0x7fffffffLL || tiles_fu > 0x7fffffffLL) return fail(AGP_ERR_INVALID_ARGUMENT);
 
   // ---- device buffers beyond the pool ----
@@ -363,27 +272,18 @@ int agp_sparse_nll_gradient(agp_context *c, const agp_kernel *k, const agp_featu
   SG_HIP(dev_malloc(&Wn, sizeof(double) * (size_t)ldm * (size_t)m));
   dev_ptr<double> wn_guard(Wn);
   const bool tx_copy = ntc > 0 && x->location == AGP_HOST, tu_copy = ntc > 0 && u->location == AGP_HOST;
-  const size_t part_elems = (size_t)(tiles_blocks + tiles_fu + tiles_uu) * SG_GROUP;
+  const size_t part_elems = (size_t)(tiles_blocks + tiles_fu + tiles_uu) * GRAD_GROUP;
   const size_t vec_elems = 3 * (size_t)np2 + (size_t)mp2 + 8 + (size_t)round_up(AGP_MAX_GRADIENT_SLOTS, 2) + part_elems +
                            (tx_copy ? (size_t)np2 * (size_t)ntc : 0) + (tu_copy ? (size_t)mp2 * (size_t)ntc : 0);
   SG_HIP(dev_malloc(&vec, sizeof(double) * vec_elems));
   dev_ptr<double> vec_guard(vec);
   double *aw = vec, *alpha = aw + np2, *diag = alpha + np2, *q = diag + np2, *scal = q + mp2, *grad_d = scal + 8;
-  double *part_blocks = grad_d + round_up(AGP_MAX_GRADIENT_SLOTS, 2), *part_fu = part_blocks + (size_t)tiles_blocks * SG_GROUP,
-         *part_uu = part_fu + (size_t)tiles_fu * SG_GROUP, *tcopy = part_uu + (size_t)tiles_uu * SG_GROUP;
-  const double *tang_x = tangents_x, *tang_u = tangents_u;
-  long long ld_tx = ldtx, ld_tu = ldtu;
-  if (tx_copy) {
-    SG_HIP(hipMemcpy2DAsync(tcopy, sizeof(double) * (size_t)np2, tangents_x, sizeof(double) * (size_t)ldtx, sizeof(double) * (size_t)n,
-                            (size_t)ntc, hipMemcpyHostToDevice, s));
-    tang_x = tcopy; ld_tx = np2;
-    tcopy += (size_t)np2 * (size_t)ntc;
-  }
-  if (tu_copy) {
-    SG_HIP(hipMemcpy2DAsync(tcopy, sizeof(double) * (size_t)mp2, tangents_u, sizeof(double) * (size_t)ldtu, sizeof(double) * (size_t)m,
-                            (size_t)ntc, hipMemcpyHostToDevice, s));
-    tang_u = tcopy; ld_tu = mp2;
-  }
+  double *part_blocks = grad_d + round_up(AGP_MAX_GRADIENT_SLOTS, 2), *part_fu = part_blocks + (size_t)tiles_blocks * GRAD_GROUP,
+         *part_uu = part_fu + (size_t)tiles_fu * GRAD_GROUP, *tcopy = part_uu + (size_t)tiles_uu * GRAD_GROUP;
+  const double *tang_x = nullptr, *tang_u = nullptr;
+  long long ld_tx = 0, ld_tu = 0;
+  if ((st = stage_tangents(ctx, s, tangents_x, ldtx, x->location, n, ntc, &tcopy, &tang_x, &ld_tx)) != AGP_OK) return st;
+  if ((st = stage_tangents(ctx, s, tangents_u, ldtu, u->location, m, ntc, &tcopy, &tang_u, &ld_tu)) != AGP_OK) return st;
   SG_HIP(hipStreamSynchronize(s));  // (pageable sources)
 
   // once per group, or once for all groups when they advance in lock step (blockIdx.y = group)
@@ -464,35 +364,31 @@ int agp_sparse_nll_gradient(agp_context *c, const agp_kernel *k, const agp_featu
   hipLaunchKernelGGL(strided_sum_kernel, dim3(1), dim3(1024), 0, s, Wn, m, ldm + 1, -0.5, scal + 1);    // 1/2 trace(W_uu)
   stage("gradient: W_uu = -E^T H E");
 
-  // ---- the three contractions, SG_GROUP slots per pass ----
-  for (int g0 = 0; g0 < n_slots; g0 += SG_GROUP) {
+  // ---- the three contractions, GRAD_GROUP slots per pass ----
+  for (int g0 = 0; g0 < n_slots; g0 += GRAD_GROUP) {
     SparseContractArgs ca;
     std::memset(static_cast<void *>(&ca), 0, sizeof(ca));
-    const int cnt = n_slots - g0 < SG_GROUP ? n_slots - g0 : SG_GROUP;
-    const double *col_x[SG_GROUP], *col_u[SG_GROUP];
-    for (int j = 0; j < SG_GROUP; ++j) {
-      const bool used = j < cnt;
-      const int node = used ? slots[g0 + j].node : -1, param = used ? slots[g0 + j].param : 0;
-      ca.slots.node[j] = node;
-      ca.slots.param[j] = param;
-      const bool scaling = used && k->prog.nodes[node].op == AGP_OP_SCALING;
-      col_x[j] = scaling ? tang_x + (size_t)param * (size_t)ld_tx : nullptr;
-      col_u[j] = scaling ? tang_u + (size_t)param * (size_t)ld_tu : nullptr;
+    bool scaling[GRAD_GROUP];
+    const int cnt = fill_slot_group(k, n_slots, slots, g0, ca.slots, scaling);
+    const double *col_x[GRAD_GROUP], *col_u[GRAD_GROUP];
+    for (int j = 0; j < GRAD_GROUP; ++j) {
+      col_x[j] = scaling[j] ? tang_x + (size_t)ca.slots.param[j] * (size_t)ld_tx : nullptr;
+      col_u[j] = scaling[j] ? tang_u + (size_t)ca.slots.param[j] * (size_t)ld_tu : nullptr;
     }
     ca.off = d_off; ca.woff = d_roff; ca.wld = d_rld; ca.tstart = d_tstart; ca.G = G; ca.tiles_r = tiles_r;
     // group blocks: (measurement, measurement) pairs of the observations
-    for (int j = 0; j < SG_GROUP; ++j) ca.tr[j] = ca.tc[j] = col_x[j];
+    for (int j = 0; j < GRAD_GROUP; ++j) ca.tr[j] = ca.tc[j] = col_x[j];
     ca.W = Bg; ca.ldw = 0; ca.partial = part_blocks; ca.mode = 2;
     launch_sparse_contract(s, dprog, xm, xm, ca, tiles_blocks);
     // k(u, x): (plain, measurement)
-    for (int j = 0; j < SG_GROUP; ++j) { ca.tr[j] = col_u[j]; ca.tc[j] = col_x[j]; }
+    for (int j = 0; j < GRAD_GROUP; ++j) { ca.tr[j] = col_u[j]; ca.tc[j] = col_x[j]; }
     ca.W = Nm; ca.ldw = ldk; ca.partial = part_fu; ca.mode = 0;
     launch_sparse_contract(s, dprog, uv, xm, ca, tiles_fu);
     // k(u, u): (plain, plain)
-    for (int j = 0; j < SG_GROUP; ++j) ca.tr[j] = ca.tc[j] = col_u[j];
+    for (int j = 0; j < GRAD_GROUP; ++j) ca.tr[j] = ca.tc[j] = col_u[j];
     ca.W = Wn; ca.ldw = ldm; ca.partial = part_uu; ca.mode = 1;
     launch_sparse_contract(s, dprog, uv, uv, ca, tiles_uu);
-    hipLaunchKernelGGL(sparse_grad_reduce_kernel, dim3(SG_GROUP), dim3(256), 0, s, part_blocks, tiles_blocks, part_fu, tiles_fu, part_uu,
+    hipLaunchKernelGGL(sparse_grad_reduce_kernel, dim3(GRAD_GROUP), dim3(256), 0, s, part_blocks, tiles_blocks, part_fu, tiles_fu, part_uu,
                        tiles_uu, cnt, grad_d + g0);
   }
   stage("gradient: contractions");

@@ -24,7 +24,7 @@ import albatross_amd as ab
 from albatross_amd import _capi as capi
 from conftest import synthetic_3d
 from oracle import oracle_py as orc
-from test_nll_gradient_gpu import LEAVES, _data, _elevation_model, _FirstCoordinateMean, perturbed
+from test_nll_gradient_gpu import LEAVES, _data, _elevation_model, _FirstCoordinateMean, _padded_data, perturbed
 
 pytestmark = pytest.mark.gpu
 
@@ -159,6 +159,16 @@ def test_gradient_scaling_term_and_linear_mean(ctx, n):
     model.set_param_values({"slope": 0.2, "offset": -0.4})
     _, grad = check(model, x, y, _variance(n, n))
     assert {"elevation_scaling_center", "elevation_scaling_factor", "slope", "offset"} <= set(grad)
+
+
+@pytest.mark.parametrize("dim", [4, 5, 8])
+def test_gradient_padded_dimensions(ctx, dim):
+    """The <4> and <8> instantiations of the contraction (5 dimensions are zero-padded to 8, the largest the feature check
+    accepts) at n = 130: a full diagonal tile, a full off-diagonal tile and partial tiles of both kinds.
+    The inputs of test_nll_gradient_gpu.py's case; cond(K + diag(s)) = 1.6e3, 4.6e2, 2.1e1 (numpy)."""
+    x, y = _padded_data(dim)
+    model = ab.gp_from_covariance(ab.SquaredExponential(1.5, 1.2) + ab.IndependentNoise(0.1), context=ctx)
+    check(model, x, y, _variance(130, dim))
 
 
 def test_gradient_polynomial_1d(ctx):

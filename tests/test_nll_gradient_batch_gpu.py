@@ -19,7 +19,7 @@ import albatross_amd as ab
 from albatross_amd import _capi as capi
 from albatross_amd import gp as abgp
 from conftest import synthetic_3d
-from test_nll_gradient_gpu import _FirstCoordinateMean, _elevation_model, reference_gradient
+from test_nll_gradient_gpu import _FirstCoordinateMean, _elevation_model, _padded_data, reference_gradient
 
 pytestmark = pytest.mark.gpu
 
@@ -151,6 +151,22 @@ def test_heterogeneous_batch_matches_numpy_and_single_calls(ctx):
     models = [m for m, _, _ in problems]
     datasets = [ab.RegressionDataset(x, y) for _, x, y in problems]
     out = ab.log_likelihood_gradient_batch(models, datasets)
+    assert len(out) == len(problems)
+    for (m, x, y), ds, (ll, grad) in zip(problems, datasets, out):
+        assert set(grad) == set(m.get_params())
+        scale = _check_numpy(m, x, y, ll, grad)
+        _check_single(m, ds, ll, grad, scale)
+
+
+def test_batch_of_dimensions_2_4_5(ctx):
+    """One launch on Point<8> for problems of 2, 4 and 5 dimensions: the zero-padding of every problem's points up to
+    the batch's largest dimension.  n = 130: full and partial tiles of both kinds.  cond(K) = 8.3e3, 3.7e3, 8.5e2 (numpy)."""
+    problems = []
+    for dim in (2, 4, 5):
+        model = ab.gp_from_covariance(ab.SquaredExponential(1.5, 1.2) + ab.IndependentNoise(0.1), context=ctx)
+        problems.append((model, *_padded_data(dim)))
+    datasets = [ab.RegressionDataset(x, y) for _, x, y in problems]
+    out = ab.log_likelihood_gradient_batch([m for m, _, _ in problems], datasets)
     assert len(out) == len(problems)
     for (m, x, y), ds, (ll, grad) in zip(problems, datasets, out):
         assert set(grad) == set(m.get_params())

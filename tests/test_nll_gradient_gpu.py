@@ -98,6 +98,13 @@ def _data(n, dim, seed):
     return x, y
 
 
+def _padded_data(dim, n=130, seed=70):
+    """n points in [0, 3]^dim: close enough for the covariance to couple them in 4 to 8 dimensions"""
+    rng = np.random.default_rng(seed + dim)
+    x = rng.uniform(0., 3., (n, dim))
+    return x, np.sin(x).sum(axis=1) + 0.1 * np.cos(10. * x[:, 0])
+
+
 LEAVES = [
     ("se euclid", lambda: ab.SquaredExponential(1.5, 1.2) + ab.IndependentNoise(0.1), 3),
     ("exp euclid", lambda: ab.Exponential(3.0, 0.9) + ab.IndependentNoise(0.2), 2),
@@ -161,6 +168,16 @@ def test_gradient_4097_partial_tiles(ctx):
     cov = ab.Exponential(0.7, 1.1, ab.AngularDistance()) * ab.SquaredExponential(4.0, 1.3, ab.RadialDistance()) \
         + ab.Matern32(2.5, 0.5) + ab.IndependentNoise(0.2)
     check_against_reference(ab.gp_from_covariance(cov, context=ctx), x, y)
+
+
+@pytest.mark.parametrize("dim", [4, 5, 8])
+def test_gradient_padded_dimensions(ctx, dim):
+    """The <4> and <8> instantiations of the contraction (5 dimensions are zero-padded to 8, the largest the feature check
+    accepts).  n = 130: three tile rows of 64 with a ragged last one - a full diagonal tile, a full off-diagonal tile and
+    partial tiles of both kinds.  The points fill [0, 3]^dim: in [0, 10]^dim every pair would be many length scales apart
+    and K all but diagonal.  Here the median off-diagonal |K_ij| is 0.15 ... 0.009 and cond(K) = 3.7e3, 8.5e2, 2.3e1 (numpy)."""
+    x, y = _padded_data(dim)
+    check_against_reference(ab.gp_from_covariance(ab.SquaredExponential(1.5, 1.2) + ab.IndependentNoise(0.1), context=ctx), x, y)
 
 
 def test_gradient_matches_central_differences_of_log_likelihood(ctx):

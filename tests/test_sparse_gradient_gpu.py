@@ -125,6 +125,22 @@ def test_se_noise_3d_all_layouts(ctx, layout, with_yvar):
     check(model, ab.RegressionDataset(x, targets), f"SE + noise 3-D, {layout}, y_var={with_yvar}")
 
 
+@pytest.mark.parametrize("dim", [4, 5, 8])
+def test_se_noise_padded_dimensions(ctx, dim):
+    """The <4> and <8> instantiations of the contraction (5 dimensions are zero-padded to 8, the largest the feature check
+    accepts).  n = 130 in ragged groups, m = 65: full and partial tiles of k(u, x) and k(u, u), group blocks smaller than
+    a tile.  The points fill [0, 3]^dim, close enough for the covariance to couple them.  check() asserts cond(K_uu),
+    cond(Kt) <= 1e6; for these inputs cond(K_uu) = 4.5e4, 3.7e3, 7.2e1 and cond(Kt) = 4.6e2, 3.5e2, 9.2e1 (numpy)."""
+    n, m = 130, 65
+    rng = np.random.default_rng(40 + dim)
+    x = rng.uniform(0., 3., (n, dim))
+    y = np.sin(x).sum(axis=1) + 0.1 * np.cos(10. * x[:, 0]) + 0.05 * rng.standard_normal(n)
+    u = x[rng.choice(n, m, replace=False)]
+    cov = ab.SquaredExponential(2.0, 1.0) + ab.measurement_only(ab.IndependentNoise(0.3))
+    model = sparse_model(ctx, cov, x, group_keys("ragged", x, rng), u)
+    check(model, ab.RegressionDataset(x, y), f"SE + noise {dim}-D, ragged")
+
+
 @pytest.mark.parametrize("layout", ["uniform", "ragged"])
 def test_matern52_times_se_plus_noise(ctx, layout):
     n, m = 1530, 90
