@@ -57,6 +57,10 @@ void launch_colvec_dot_strided(hipStream_t s, const double *W, long long ld, lon
 size_t symv_ws_elems(long long n);
 void launch_symv_lower(hipStream_t s, const double *K, long long ld, long long n, const double *p, double alpha, double beta,
                        const double *base, double *out, double *ws);
+// out_b = K_b p_b for `count` such matrices in one launch, without scratch: K_b = K + b * stride_K, p_b and out_b at
+// stride_v (blockIdx.y = problem)
+void launch_symv_lower_batched(hipStream_t s, const double *K, long long ld, long long stride_K, long long n, const double *p,
+                               long long stride_v, double *out, long long count);
 void launch_axpby(hipStream_t s, long long n, double a, const double *x, double b, const double *y, double *out);
 void launch_loo(hipStream_t s, const double *kinv_diag, const double *y, const double *information, long long n,
                 double *mean, double *variance);
@@ -175,6 +179,9 @@ void launch_rtr_lower_batched(hipStream_t s, const double *R, long long ldr, lon
                               long long ldc, long long stride_C, long long count);
 // S (lower tiles, lds) = G^T G for a full n x n G (gradient.hip: agp_loo_nll_gradient's C diag(b) C)
 void launch_gtg_lower(hipStream_t s, const double *G, long long ldg, long long n, double *S, long long lds);
+// the same for `count` problems in one launch: G_b = G + b * stride_G, S_b = S + b * stride_S (blockIdx.y = problem)
+void launch_gtg_lower_batched(hipStream_t s, const double *G, long long ldg, long long stride_G, long long n, double *S,
+                              long long lds, long long stride_S, long long count);
 }  // namespace agp
 // LL^T of a dense matrix at `location` into a fresh factor buffer of `fit` (api.hip: agp_factor_create, agp_nll_dense;
 // scores.hip: agp_energy_score).  y (device, optional) receives the fused forward substitution, diag_add (device,

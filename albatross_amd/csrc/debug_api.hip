@@ -326,6 +326,36 @@ extern "C" AGP_DEBUG_API int agp_debug_gtg_lower(agp_context *ctx, const double 
   return AGP_OK;
 }
 
+// agp_debug_gtg_lower for `count` problems in one launch (gradient.hip: launch_gtg_lower_batched,
+// agp_loo_nll_gradient_batch's C_b diag(b) C_b): G and S hold `count` slabs of ld * n doubles each.  ms (optional): the
+// kernel's device time.
+extern "C" AGP_DEBUG_API int agp_debug_gtg_lower_batched(agp_context *ctx, const double *G, int64_t n, int64_t ld, int64_t count,
+                                                         double *S, double *ms) {
+  if (!ctx || !G || !S || n <= 0 || ld < n || count <= 0 || count > 65535) return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const size_t bytes = sizeof(double) * (size_t)ld * (size_t)n * (size_t)count;
+  double *dG = nullptr, *dS = nullptr;
+  AGP_HIP_CHECK(ctx, hipMalloc(&dG, bytes));
+  AGP_HIP_CHECK(ctx, hipMalloc(&dS, bytes));
+  AGP_HIP_CHECK(ctx, hipMemcpy(dG, G, bytes, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipMemsetAsync(dS, 0, bytes, ctx->stream));  // on the kernel's stream, as agp_debug_rtr_lower
+  hipEvent_t e0, e1;
+  AGP_HIP_CHECK(ctx, hipEventCreate(&e0));
+  AGP_HIP_CHECK(ctx, hipEventCreate(&e1));
+  AGP_HIP_CHECK(ctx, hipEventRecord(e0, ctx->stream));
+  launch_gtg_lower_batched(ctx->stream, dG, ld, ld * n, n, dS, ld, ld * n, count);
+  AGP_HIP_CHECK(ctx, hipEventRecord(e1, ctx->stream));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  float t = 0.f;
+  (void)hipEventElapsedTime(&t, e0, e1);
+  if (ms) *ms = t;
+  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  AGP_HIP_CHECK(ctx, hipMemcpy(S, dS, bytes, hipMemcpyDeviceToHost));
+  (void)hipFree(dG); (void)hipFree(dS);
+  return AGP_OK;
+}
+
 // acos_fast (cov_eval.h) on an array: accuracy test against the correctly rounded acos
 __global__ void acos_fast_kernel(const double *t, double *out, long long n) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;

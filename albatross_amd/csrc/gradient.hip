@@ -22,6 +22,10 @@
 // The same fit, alpha, R and C = R^T R; then loo_terms_kernel (per point: the NLL term, a, sqrt(b)), u by
 // launch_symv_lower, G = diag(b)^1/2 sym(C) over R (loo_form_g_kernel), S = G^T G = C diag(b) C over C (gtg_lower_kernel:
 // N^3 flop, the only O(N^3) work beyond agp_nll_gradient) and the contraction of W = S - sym(u alpha^T).
+//
+// agp_nll_gradient_batch and agp_loo_nll_gradient_batch run the same steps for `count` problems of one size in lock step:
+// every kernel below takes the problem from blockIdx.y (blockIdx.z where y is a tile index) and per-problem strides, and
+// the single-problem calls are its count = 1 case.
 #include <climits>
 #include <cstring>
 #include <limits>
@@ -113,7 +117,7 @@ __global__ __launch_bounds__(256) void nll_grad_reduce_kernel(const double *__re
   if (threadIdx.x == 0) out[g] = scale * v;
 }
 
-// ---- the batched contraction (agp_nll_gradient_batch) -------------------------------------------------------------
+// ---- the batched contraction (agp_nll_gradient_batch, agp_loo_nll_gradient_batch) -----------------------------------
 // One descriptor per problem, built on the host for the call and uploaded with it: the program by value (not the
 // context's device program cache, whose slots later problems would overwrite), the features, K^-1 and alpha of the
 // problem's slabs, its slot table in groups of GRAD_GROUP and the tangent column of every AGP_OP_SCALING slot.
@@ -121,9 +125,10 @@ constexpr int GRAD_GROUPS_MAX = (AGP_MAX_GRADIENT_SLOTS + GRAD_GROUP - 1) / GRAD
 struct ContractDesc {
   DevProgram prog;
   FeatView X;
-  const double *C;         // K_b^-1, lower triangle
+  const double *C;         // K_b^-1 (LOO: S_b = C_b diag(b) C_b), lower triangle
   long long ldc;
   const double *alpha;
+  const double *u;         // LOO only: u_b = C_b a_b
   double *partial;         // [group][tile][GRAD_GROUP]
   int n_slots;
   int pad;
@@ -132,8 +137,8 @@ struct ContractDesc {
 };
 
 // grid: x = tile, y = problem, z = slot group.  DIMP covers the batch's largest dimension (load_point zero-pads);
-// problems with fewer slot groups leave their unused z-slices at once.
-template <int DIMP>
+// problems with fewer slot groups leave their unused z-slices at once.  LOO: the weight of agp_loo_nll_gradient.
+template <int DIMP, bool LOO = false>
 __global__ __launch_bounds__(CT_THREADS) void nll_grad_contract_batched_kernel(const ContractDesc *__restrict__ D, long long tiles) {
   const ContractDesc &d = D[blockIdx.y];
   const int grp = blockIdx.z;
@@ -142,10 +147,10 @@ __global__ __launch_bounds__(CT_THREADS) void nll_grad_contract_batched_kernel(c
   a.slots = d.slots[grp];
 #pragma unroll
   for (int g = 0; g < GRAD_GROUP; ++g) a.tang[g] = d.tang[grp * GRAD_GROUP + g];
-  a.C = d.C; a.ldc = d.ldc; a.alpha = d.alpha; a.u = nullptr;
+  a.C = d.C; a.ldc = d.ldc; a.alpha = d.alpha; a.u = d.u;
   a.partial = d.partial + (long long)grp * tiles * GRAD_GROUP;
   const FeatView X = d.X;
-  contract_lower<DIMP, false>(&d.prog, X, a);
+  contract_lower<DIMP, LOO>(&d.prog, X, a);
 }
 
 // out[b * ldo + slot] = scale * sum over tiles of problem b's partials of that slot (one workgroup per (slot, problem))
@@ -166,9 +171,10 @@ static void launch_contract(hipStream_t s, const DevProgram *P, const FeatView &
   });
 }
 
+template <bool LOO>
 static void launch_contract_batched(hipStream_t s, int dim_max, const ContractDesc *D, long long tiles, long long count, int groups) {
   dispatch_dim(dim_max, [&](auto DIMP) {
-    hipLaunchKernelGGL(nll_grad_contract_batched_kernel<decltype(DIMP)::value>, dim3((unsigned)tiles, (unsigned)count, (unsigned)groups),
+    hipLaunchKernelGGL((nll_grad_contract_batched_kernel<decltype(DIMP)::value, LOO>), dim3((unsigned)tiles, (unsigned)count, (unsigned)groups),
                        dim3(CT_THREADS), 0, s, D, tiles);
   });
 }
@@ -176,13 +182,20 @@ static void launch_contract_batched(hipStream_t s, int dim_max, const ContractDe
 // ---- leave-one-out terms -----------------------------------------------------------------------------------------
 // Per point i, from c_i = cdiag[i * cstride] (C's diagonal in place, stride ldc + 1, or R's squared column norms) and
 // alpha_i: term[i] = log v_i + d_i^2 / v_i (the NLL term without 1/2 and log 2 pi), a[i] = d_i / (v_i c_i) and
-// sqrt_b[i] = sqrt(b_i); b_i > 0 always (c_i v_i >= 1).  a and sqrt_b may be nullptr (value only).
-__global__ __launch_bounds__(256) void loo_terms_kernel(const double *__restrict__ cdiag, long long cstride,
+// sqrt_b[i] = sqrt(b_i); b_i > 0 always (c_i v_i >= 1).  a and sqrt_b may be nullptr (value only).  blockIdx.y = problem:
+// its c starts at cdiag + b * cbatch, its vectors at b * vbatch (one problem: a grid of height 1).
+__global__ __launch_bounds__(256) void loo_terms_kernel(const double *__restrict__ cdiag, long long cstride, long long cbatch,
                                                         const double *__restrict__ alpha, const double *__restrict__ yvar,
-                                                        long long n, double *__restrict__ term, double *__restrict__ a,
-                                                        double *__restrict__ sqrt_b) {
+                                                        long long n, long long vbatch, double *__restrict__ term,
+                                                        double *__restrict__ a, double *__restrict__ sqrt_b) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
+  const long long vb = (long long)blockIdx.y * vbatch;
+  cdiag += (long long)blockIdx.y * cbatch;
+  alpha += vb; term += vb;
+  if (yvar) yvar += vb;
+  if (a) a += vb;
+  if (sqrt_b) sqrt_b += vb;
   const double c = cdiag[i * cstride], al = alpha[i];
   const double v = 1. / c + (yvar ? yvar[i] : 0.);  // the LOO variance plus the truth's (prediction_metrics.hpp:113-119)
   const double d = al / c;                           // cross_validation_utils.hpp:146-163
@@ -192,9 +205,12 @@ __global__ __launch_bounds__(256) void loo_terms_kernel(const double *__restrict
   if (sqrt_b) sqrt_b[i] = sqrt((1. - dv + 2. * al * d) / (2. * v * c * c));
 }
 
-// out[0] = 1/2 (sum_i term[i] + n log 2 pi)   (single workgroup, fixed order)
-__global__ __launch_bounds__(1024) void loo_sum_kernel(const double *__restrict__ term, long long n, double *__restrict__ out) {
+// out[b] = 1/2 (sum_i term_b[i] + n log 2 pi), term_b = term + b * tbatch, b = blockIdx.y   (one workgroup per problem,
+// fixed order)
+__global__ __launch_bounds__(1024) void loo_sum_kernel(const double *__restrict__ term, long long n, long long tbatch,
+                                                       double *__restrict__ out) {
   __shared__ double red[16];
+  term += (long long)blockIdx.y * tbatch;
   double acc = 0.;
   for (long long i = threadIdx.x; i < n; i += 1024) acc += term[i];
 #pragma unroll
@@ -204,18 +220,23 @@ __global__ __launch_bounds__(1024) void loo_sum_kernel(const double *__restrict_
   if (threadIdx.x == 0) {
     double s = 0.;
     for (int w = 0; w < 16; ++w) s += red[w];
-    out[0] = 0.5 * (s + (double)n * log(2. * M_PI));
+    out[blockIdx.y] = 0.5 * (s + (double)n * log(2. * M_PI));
   }
 }
 
 // G (n x n, ldg) = diag(sqrt_b) sym(C), C given by its lower triangle (ldc): G(k, i) = sqrt_b[k] C(max(k, i), min(k, i)).
 // One 32 x 32 tile of G per workgroup, staged through LDS from the lower tile of C it mirrors, so both the reads and the
-// writes are coalesced.  Only C's lower triangle is read, the diagonal tile's included.
+// writes are coalesced.  Only C's lower triangle is read, the diagonal tile's included.  blockIdx.z = problem: C and G
+// at b * batch_M, sqrt_b at b * batch_v.
 constexpr int GF_T = 32;
 __global__ __launch_bounds__(256) void loo_form_g_kernel(const double *__restrict__ C, long long ldc,
                                                          const double *__restrict__ sqrt_b, long long n,
-                                                         double *__restrict__ G, long long ldg) {
+                                                         double *__restrict__ G, long long ldg, long long batch_M,
+                                                         long long batch_v) {
   __shared__ double tile[GF_T][GF_T + 1];
+  C += (long long)blockIdx.z * batch_M;
+  G += (long long)blockIdx.z * batch_M;
+  sqrt_b += (long long)blockIdx.z * batch_v;
   const long long bi = blockIdx.x, bj = blockIdx.y;  // rows k of tile bi, columns i of tile bj
   const long long rb = bi > bj ? bi : bj, cb = bi > bj ? bj : bi;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
@@ -243,18 +264,31 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gtg_lower_kernel(GemmArgs g) 
   __shared__ double lds[2 * 2 * GK * GLD];
   int bi, bj;
   lower_tile(blockIdx.x, bi, bj);
-  gemm_nt_sub_tile<true, true, true>(g, bi, bj, lds);
+  const long long b = blockIdx.y;  // problem of a batched launch (batch_* = 0: one problem)
+  GemmArgs t = g;
+  t.C = g.C + b * g.batch_C;
+  t.A = g.A + b * g.batch_A;
+  t.B = g.B + b * g.batch_B;
+  gemm_nt_sub_tile<true, true, true>(t, bi, bj, lds);
 }
 
-void launch_gtg_lower(hipStream_t s, const double *G, long long ldg, long long n, double *S, long long lds_) {
-  if (n <= 0) return;
+// S_b = G_b^T G_b for `count` problems (blockIdx.y = problem): G_b = G + b * stride_G, S_b = S + b * stride_S; count = 1 is
+// launch_gtg_lower.
+void launch_gtg_lower_batched(hipStream_t s, const double *G, long long ldg, long long stride_G, long long n, double *S,
+                              long long lds_, long long stride_S, long long count) {
+  if (n <= 0 || count <= 0) return;
   GemmArgs g;
   g.C = S; g.ldc = lds_; g.A = G; g.lda = ldg; g.B = G; g.ldb = ldg;
   g.M = n; g.N = n; g.K = n; g.tri = 1;
   g.ntr = g.ntc = (int)((n + GT - 1) / GT);
   g.assign = 1;  // S = + G^T G, S not read
+  g.batch_C = stride_S; g.batch_A = g.batch_B = stride_G;
   const long long tiles = (long long)g.ntr * (g.ntr + 1) / 2;
-  hipLaunchKernelGGL(gtg_lower_kernel, dim3((unsigned)tiles), dim3(GEMM_THREADS), 0, s, g);
+  hipLaunchKernelGGL(gtg_lower_kernel, dim3((unsigned)tiles, (unsigned)count), dim3(GEMM_THREADS), 0, s, g);
+}
+
+void launch_gtg_lower(hipStream_t s, const double *G, long long ldg, long long n, double *S, long long lds_) {
+  launch_gtg_lower_batched(s, G, ldg, 0, n, S, lds_, 0, 1);
 }
 
 }  // namespace agp
@@ -463,18 +497,18 @@ int agp_loo_nll_gradient(agp_context *c, const agp_kernel *k, const agp_features
   if (!need_c) {
     // c_i = ||R[:, i]||^2, as agp_fit_inverse_diagonal
     launch_coldot(s, g.R, g.lda, g.R, g.lda, n, n, cdiag, -1.0, nullptr);
-    hipLaunchKernelGGL(loo_terms_kernel, dim3(eblocks), dim3(256), 0, s, cdiag, 1LL, alpha, g.yvar_d, n, term, nullptr, nullptr);
-    hipLaunchKernelGGL(loo_sum_kernel, dim3(1), dim3(1024), 0, s, term, n, ctx->d_scalars + 2);
+    hipLaunchKernelGGL(loo_terms_kernel, dim3(eblocks), dim3(256), 0, s, cdiag, 1LL, 0LL, alpha, g.yvar_d, n, 0LL, term, nullptr, nullptr);
+    hipLaunchKernelGGL(loo_sum_kernel, dim3(1), dim3(1024), 0, s, term, n, 0LL, ctx->d_scalars + 2);
     if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[5], s));
   } else {
     launch_rtr_lower(s, g.R, g.lda, n, g.A, g.lda);  // C = K^-1 over L
     if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[4], s));
-    hipLaunchKernelGGL(loo_terms_kernel, dim3(eblocks), dim3(256), 0, s, g.A, g.lda + 1, alpha, g.yvar_d, n, term, a, sqrt_b);
-    hipLaunchKernelGGL(loo_sum_kernel, dim3(1), dim3(1024), 0, s, term, n, ctx->d_scalars + 2);
+    hipLaunchKernelGGL(loo_terms_kernel, dim3(eblocks), dim3(256), 0, s, g.A, g.lda + 1, 0LL, alpha, g.yvar_d, n, 0LL, term, a, sqrt_b);
+    hipLaunchKernelGGL(loo_sum_kernel, dim3(1), dim3(1024), 0, s, term, n, 0LL, ctx->d_scalars + 2);
     launch_symv_lower(s, g.A, g.lda, n, a, 1., 0., nullptr, u, symv_ws);  // u = C a
     if (n_slots > 0) {
       const unsigned gt = (unsigned)((n + GF_T - 1) / GF_T);
-      hipLaunchKernelGGL(loo_form_g_kernel, dim3(gt, gt), dim3(256), 0, s, g.A, g.lda, sqrt_b, n, g.R, g.lda);  // G over R
+      hipLaunchKernelGGL(loo_form_g_kernel, dim3(gt, gt), dim3(256), 0, s, g.A, g.lda, sqrt_b, n, g.R, g.lda, 0LL, 0LL);  // G over R
     }
     if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[5], s));
     if (n_slots > 0) {
@@ -510,21 +544,39 @@ int agp_loo_nll_gradient(agp_context *c, const agp_kernel *k, const agp_features
   return AGP_OK;
 }
 
-// ---- agp_nll_gradient for `count` problems of one size in lock step ---------------------------------------------
-// The steps of agp_nll_gradient with blockIdx.y = problem: one batched Gram, factor_lower_batched (or its look-ahead form,
-// as agp_fit_create_batch chooses), z_b^T z_b, alpha_b, R_b = L_b^-1 into a second slab, K_b^-1 = R_b^T R_b over L_b,
-// the contraction (grid x = tile, y = problem, z = slot group) and the reduction.  Workspace: the A and R slabs
-// (2 lda n doubles per problem) plus the tile images (stride_I) and O(n) vectors per problem.
-int agp_nll_gradient_batch(agp_context *c, int count, const agp_kernel *const *kernels, const agp_features *const *features,
-                           const double *y, int64_t ldy, const double *y_var, int64_t ldv, const int *n_slots,
-                           const agp_gradient_slot *const *slots, const double *const *tangents, int64_t ldt, double *nll,
-                           double *grad_nll, int64_t ldg, double *information, int64_t ldi, int *status) {
-  if (!c || count <= 0 || !kernels || !features || !y || !n_slots || !nll || !status) return AGP_ERR_INVALID_ARGUMENT;
+}  // extern "C"
+
+// ---- the steps both batched gradients share ----------------------------------------------------------------------
+// Everything agp_nll_gradient_batch and agp_loo_nll_gradient_batch do up to and including C_b = R_b^T R_b, and the
+// download at the end.  Workspaces:
+//   ws_A:   [A slabs | tile images | z / alpha | y_var | logsum | quad | flags (4 ints each) | z slots of the fused panels]
+//   ws_aux: [R slabs | tangent columns | partials | gradient | Gram table | contraction descriptors | extra vectors]
+struct GradientBatch {
+  long long n = 0, lda = 0, np2 = 0, cp2 = 0, stride_A = 0, tiles = 0, ldgd = 0;
+  int groups = 0, max_slots = 0, dim_max = 1;
+  double *A = nullptr, *z = nullptr, *yvar_d = nullptr;
+  double *logsum = nullptr;  // [logsum | quad | flags]: what gradient_batch_finish downloads
+  double *quad = nullptr;    // one scalar per problem: z_b^T z_b (NLL) or the leave-one-out sum
+  double *R = nullptr, *grad_d = nullptr, *extra = nullptr;
+  ContractDesc *desc_d = nullptr;
+  long long count = 0;
+  double *vector(int k) const { return extra + (size_t)k * (size_t)count * (size_t)np2; }  // extra array k (np2 x count)
+};
+
+// The argument checks of both entries (every problem is checked before anything is written or launched), the uploads,
+// one batched Gram, factor_lower_batched (or its look-ahead form, as agp_fit_create_batch chooses), alpha_b in place and
+// R_b = L_b^-1 into the second slab (stage event 3), then with `rtr` K_b^-1 = R_b^T R_b over L_b (stage event 4).
+// vec / ldvec: the entry's n x count host output, checked only.  quad: z_b^T z_b before alpha overwrites z.
+// extra_vectors: further np2 x count arrays behind the descriptors, laid out like z (GradientBatch::vector(k): array k,
+// problem b's vector at + b * np2); u_vector >= 0: the array that holds every problem's u, for the descriptors.
+static int gradient_batch_begin(agp_context_impl *ctx, int count, const agp_kernel *const *kernels,
+                                const agp_features *const *features, const double *y, int64_t ldy, const double *y_var,
+                                int64_t ldv, const int *n_slots, const agp_gradient_slot *const *slots,
+                                const double *const *tangents, int64_t ldt, const double *grad, int64_t ldg, const double *vec,
+                                int64_t ldvec, bool quad, bool rtr, int extra_vectors, int u_vector, GradientBatch &g) {
   if (count > 65535) return AGP_ERR_INVALID_ARGUMENT;  // gridDim.y of the batched launches
-  agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
   const long long n = features[0] ? features[0]->n : 0;
-  if (n <= 0 || (ldy != 0 && ldy < n) || (y_var && ldv != 0 && ldv < n) || (information && ldi < n)) return AGP_ERR_INVALID_ARGUMENT;
-  // every problem is checked before anything is written or launched
+  if (n <= 0 || (ldy != 0 && ldy < n) || (y_var && ldv != 0 && ldv < n) || (vec && ldvec < n)) return AGP_ERR_INVALID_ARGUMENT;
   int st = AGP_OK, max_slots = 0, dim_max = 1;
   std::vector<int> ntc((size_t)count, 0);
   for (int b = 0; b < count; ++b) {
@@ -538,7 +590,7 @@ int agp_nll_gradient_batch(agp_context *c, int count, const agp_kernel *const *k
     if (ns > max_slots) max_slots = ns;
     if (features[b]->dim > dim_max) dim_max = features[b]->dim;
   }
-  if (max_slots > 0 && (!grad_nll || ldg < max_slots)) return AGP_ERR_INVALID_ARGUMENT;
+  if (max_slots > 0 && (!grad || ldg < max_slots)) return AGP_ERR_INVALID_ARGUMENT;
   const long long tiles = lower_tiles(n), rtr_tiles = ((n + GT - 1) / GT) * ((n + GT - 1) / GT + 1) / 2;
   const int groups = (max_slots + GRAD_GROUP - 1) / GRAD_GROUP;
   if (tiles * CT_THREADS > (long long)UINT_MAX || rtr_tiles * GEMM_THREADS > (long long)UINT_MAX ||
@@ -558,23 +610,25 @@ int agp_nll_gradient_batch(agp_context *c, int count, const agp_kernel *const *k
     for (int b = 0; b < count; ++b) tang_elems += (long long)ntc[(size_t)b] * np2;
   const size_t gram_bytes = (gram_batch_table_bytes(count) + 15) / 16 * 16;
   const size_t desc_bytes = (sizeof(ContractDesc) * (size_t)count + 15) / 16 * 16;
-  // ws_A:   [A slabs | tile images | z / alpha | y_var | logsum | quad | flags (4 ints each) | z slots of the fused panels]
-  // ws_aux: [R slabs | tangent columns | partials | gradient | Gram table | contraction descriptors]
   const size_t a_elems = (size_t)round_up(count * stride_A, 2) + (size_t)count * (size_t)stride_I + (size_t)count * (size_t)np2 +
                          (y_var ? (size_t)count * (size_t)np2 : 0) + 4 * (size_t)cp2 + (fused_panels ? (size_t)count * (size_t)np2 : 0);
   const size_t aux_elems = (size_t)round_up(count * stride_A, 2) + (size_t)tang_elems + (size_t)count * (size_t)part_per +
-                           (size_t)count * (size_t)ldgd + (gram_bytes + desc_bytes) / 8;
+                           (size_t)count * (size_t)ldgd + (gram_bytes + desc_bytes) / 8 + (size_t)extra_vectors * (size_t)count * (size_t)np2;
   if ((st = ensure_ws(ctx, &ctx->ws_A, &ctx->ws_A_bytes, sizeof(double) * a_elems)) != AGP_OK) return st;
   if ((st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, sizeof(double) * aux_elems)) != AGP_OK) return st;
   double *A = ctx->ws_A, *invd = A + round_up(count * stride_A, 2), *z = invd + (size_t)count * (size_t)stride_I;
   double *yvar_d = y_var ? z + (size_t)count * (size_t)np2 : nullptr;
-  double *logsum = z + (size_t)count * (size_t)np2 * (y_var ? 2 : 1), *quad = logsum + cp2;
-  int *flags = reinterpret_cast<int *>(quad + cp2);
-  double *zpub = fused_panels ? quad + 3 * cp2 : nullptr;
+  double *logsum = z + (size_t)count * (size_t)np2 * (y_var ? 2 : 1);
+  int *flags = reinterpret_cast<int *>(logsum + 2 * cp2);
+  double *zpub = fused_panels ? logsum + 4 * cp2 : nullptr;
   double *R = ctx->ws_aux, *tang_d = R + round_up(count * stride_A, 2), *partial = tang_d + tang_elems;
   double *grad_d = partial + (size_t)count * (size_t)part_per;
   char *gram_table = reinterpret_cast<char *>(grad_d + (size_t)count * (size_t)ldgd);
   ContractDesc *desc_d = reinterpret_cast<ContractDesc *>(gram_table + gram_bytes);
+  g.count = count; g.n = n; g.lda = lda; g.np2 = np2; g.cp2 = cp2; g.stride_A = stride_A; g.tiles = tiles; g.ldgd = ldgd;
+  g.groups = groups; g.max_slots = max_slots; g.dim_max = dim_max;
+  g.A = A; g.z = z; g.yvar_d = yvar_d; g.logsum = logsum; g.quad = logsum + cp2; g.R = R; g.grad_d = grad_d; g.desc_d = desc_d;
+  g.extra = reinterpret_cast<double *>(reinterpret_cast<char *>(desc_d) + desc_bytes);
   hipStream_t s = ctx->stream;
   const bool prof = ctx->profiling;
   const hipMemcpyKind kind = loc == AGP_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
@@ -652,6 +706,7 @@ int agp_nll_gradient_batch(agp_context *c, int count, const agp_kernel *const *k
     d.C = A + (size_t)b * (size_t)stride_A;
     d.ldc = lda;
     d.alpha = z + (size_t)b * (size_t)np2;
+    d.u = u_vector >= 0 ? g.vector(u_vector) + (size_t)b * (size_t)np2 : nullptr;
     d.partial = partial + (size_t)b * (size_t)part_per;
     d.n_slots = n_slots[b];
     for (int grp = 0; grp < GRAD_GROUPS_MAX; ++grp) {
@@ -682,30 +737,37 @@ int agp_nll_gradient_batch(agp_context *c, int count, const agp_kernel *const *k
     factor_lower_batched(s, A, stride_A, n, lda, invd, stride_I, z, np2, count, flags, logsum, 4, zpub, np2);
   if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[2], s));
   // y^T K^-1 y = z^T z, alpha = L^-T z in place, R = L^-1 (triangular right-hand side) into the second slab.  A failed
-  // problem runs on through here on whatever its factor holds: every launch below has fixed trip counts and none waits
-  // on another workgroup's data, so it costs nothing but its own (discarded) results.
-  launch_coldot(s, z, np2, z, np2, n, count, quad, -1.0, nullptr);
+  // problem runs on through here and through the entry's own steps on whatever its factor holds: every launch has fixed
+  // trip counts and none waits on another workgroup's data, so it costs nothing but its own (discarded) results.
+  if (quad) launch_coldot(s, z, np2, z, np2, n, count, g.quad, -1.0, nullptr);
   backward_solve_vec_batched(s, A, stride_A, n, lda, invd, stride_I, z, np2, count);
   launch_set_identity_batched(s, R, lda, stride_A, n, count);
   forward_solve_mat_batched(s, A, stride_A, n, lda, invd, stride_I, R, stride_A, n, lda, /*rhs_lower=*/true, count);
   if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[3], s));
-  launch_rtr_lower_batched(s, R, lda, stride_A, n, A, lda, stride_A, count);  // K_b^-1 over L_b
-  if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[4], s));
-  if (groups > 0) {
-    launch_contract_batched(s, dim_max, desc_d, tiles, count, groups);
-    hipLaunchKernelGGL(nll_grad_reduce_batched_kernel, dim3((unsigned)(groups * GRAD_GROUP), (unsigned)count), dim3(256), 0, s, desc_d,
-                       tiles, 0.5, grad_d, ldgd);
+  if (rtr) {
+    launch_rtr_lower_batched(s, R, lda, stride_A, n, A, lda, stride_A, count);  // K_b^-1 over L_b
+    if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[4], s));
   }
-  if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[5], s));
+  return AGP_OK;
+}
+
+// [logsum | quad | flags], the gradients and (when asked for) every vec_d column: three transfers, one synchronisation;
+// then the host outputs.  value(b, logsum_b, quad_b): problem b's objective.  A failed problem gets NaN for its value and
+// its gradient column and keeps its column of vec.
+template <class Value>
+static int gradient_batch_finish(agp_context_impl *ctx, const GradientBatch &g, int count, const int *n_slots, Value value,
+                                 double *values, double *grad, int64_t ldg, const double *vec_d, double *vec, int64_t ldvec,
+                                 int *status) {
+  hipStream_t s = ctx->stream;
+  const long long n = g.n, cp2 = g.cp2;
   AGP_HIP_CHECK(ctx, hipGetLastError());
-  // [logsum | quad | flags], the gradients and (when asked for) every alpha: three transfers, one synchronisation
   std::vector<double> h_head(4 * (size_t)cp2);
-  std::vector<double> h_grad(max_slots > 0 ? (size_t)count * (size_t)ldgd : 0);
-  std::vector<double> h_alpha(information ? (size_t)count * (size_t)n : 0);
-  AGP_HIP_CHECK(ctx, hipMemcpyAsync(h_head.data(), logsum, sizeof(double) * h_head.size(), hipMemcpyDeviceToHost, s));
-  if (max_slots > 0) AGP_HIP_CHECK(ctx, hipMemcpyAsync(h_grad.data(), grad_d, sizeof(double) * h_grad.size(), hipMemcpyDeviceToHost, s));
-  if (information)
-    AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(h_alpha.data(), sizeof(double) * (size_t)n, z, sizeof(double) * (size_t)np2, sizeof(double) * (size_t)n,
+  std::vector<double> h_grad(g.max_slots > 0 ? (size_t)count * (size_t)g.ldgd : 0);
+  std::vector<double> h_vec(vec ? (size_t)count * (size_t)n : 0);
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(h_head.data(), g.logsum, sizeof(double) * h_head.size(), hipMemcpyDeviceToHost, s));
+  if (g.max_slots > 0) AGP_HIP_CHECK(ctx, hipMemcpyAsync(h_grad.data(), g.grad_d, sizeof(double) * h_grad.size(), hipMemcpyDeviceToHost, s));
+  if (vec)
+    AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(h_vec.data(), sizeof(double) * (size_t)n, vec_d, sizeof(double) * (size_t)g.np2, sizeof(double) * (size_t)n,
                                         (size_t)count, hipMemcpyDeviceToHost, s));
   AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
   AGP_HIP_CHECK(ctx, hipGetLastError());
@@ -720,12 +782,42 @@ int agp_nll_gradient_batch(agp_context *c, int count, const agp_kernel *const *k
     const int *fl = h_flags + 4 * b;
     status[b] = fl[0] ? AGP_ERR_NAN_INPUT : (fl[1] ? AGP_ERR_NOT_POSITIVE_DEFINITE : AGP_OK);
     const bool ok = status[b] == AGP_OK;
-    nll[b] = ok ? 0.5 * (2. * h_head[(size_t)b] + h_head[(size_t)cp2 + (size_t)b] + (double)n * std::log(2 * M_PI))  // likelihood.hpp:46
-                : nan;
-    for (int j = 0; j < n_slots[b]; ++j) grad_nll[(size_t)b * (size_t)ldg + (size_t)j] = ok ? h_grad[(size_t)b * (size_t)ldgd + (size_t)j] : nan;
-    if (information && ok)
-      std::memcpy(information + (size_t)b * (size_t)ldi, h_alpha.data() + (size_t)b * (size_t)n, sizeof(double) * (size_t)n);
+    values[b] = ok ? value(h_head[(size_t)b], h_head[(size_t)cp2 + (size_t)b]) : nan;
+    for (int j = 0; j < n_slots[b]; ++j) grad[(size_t)b * (size_t)ldg + (size_t)j] = ok ? h_grad[(size_t)b * (size_t)g.ldgd + (size_t)j] : nan;
+    if (vec && ok) std::memcpy(vec + (size_t)b * (size_t)ldvec, h_vec.data() + (size_t)b * (size_t)n, sizeof(double) * (size_t)n);
   }
+  return AGP_OK;
+}
+
+extern "C" {
+
+// ---- agp_nll_gradient for `count` problems of one size in lock step ---------------------------------------------
+// The steps of agp_nll_gradient with blockIdx.y = problem: gradient_batch_begin (z_b^T z_b, alpha_b, R_b, K_b^-1 =
+// R_b^T R_b over L_b), the contraction (grid x = tile, y = problem, z = slot group) and the reduction.  Workspace: the A
+// and R slabs (2 lda n doubles per problem) plus the tile images (stride_I) and O(n) vectors per problem.
+int agp_nll_gradient_batch(agp_context *c, int count, const agp_kernel *const *kernels, const agp_features *const *features,
+                           const double *y, int64_t ldy, const double *y_var, int64_t ldv, const int *n_slots,
+                           const agp_gradient_slot *const *slots, const double *const *tangents, int64_t ldt, double *nll,
+                           double *grad_nll, int64_t ldg, double *information, int64_t ldi, int *status) {
+  if (!c || count <= 0 || !kernels || !features || !y || !n_slots || !nll || !status) return AGP_ERR_INVALID_ARGUMENT;
+  agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
+  GradientBatch g;
+  int st = gradient_batch_begin(ctx, count, kernels, features, y, ldy, y_var, ldv, n_slots, slots, tangents, ldt, grad_nll, ldg,
+                                information, ldi, /*quad=*/true, /*rtr=*/true, 0, -1, g);
+  if (st != AGP_OK) return st;
+  hipStream_t s = ctx->stream;
+  const bool prof = ctx->profiling;
+  if (g.groups > 0) {
+    launch_contract_batched<false>(s, g.dim_max, g.desc_d, g.tiles, count, g.groups);
+    hipLaunchKernelGGL(nll_grad_reduce_batched_kernel, dim3((unsigned)(g.groups * GRAD_GROUP), (unsigned)count), dim3(256), 0, s, g.desc_d,
+                       g.tiles, 0.5, g.grad_d, g.ldgd);
+  }
+  if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[5], s));
+  const double n_log_2pi = (double)g.n * std::log(2 * M_PI);
+  st = gradient_batch_finish(ctx, g, count, n_slots,
+                             [&](double logsum, double quad) { return 0.5 * (2. * logsum + quad + n_log_2pi); },  // likelihood.hpp:46
+                             nll, grad_nll, ldg, g.z, information, ldi, status);
+  if (st != AGP_OK) return st;
   if (prof) {
     for (int k : {3, 4, 5, 8, 9}) ctx->stage_ms[k] = 0.;
     ctx->stage_ms[0] = elapsed(ctx->stage_ev[0], ctx->stage_ev[1]);
@@ -733,6 +825,82 @@ int agp_nll_gradient_batch(agp_context *c, int count, const agp_kernel *const *k
     ctx->stage_ms[2] = elapsed(ctx->stage_ev[2], ctx->stage_ev[3]);
     ctx->stage_ms[6] = elapsed(ctx->stage_ev[3], ctx->stage_ev[4]);
     ctx->stage_ms[7] = elapsed(ctx->stage_ev[4], ctx->stage_ev[5]);
+  }
+  return AGP_OK;
+}
+
+// ---- agp_loo_nll_gradient for `count` problems of one size in lock step -------------------------------------------
+// The steps of agp_loo_nll_gradient with blockIdx.y (z for the G tiles) = problem, each ONE launch for the batch:
+// gradient_batch_begin (alpha_b, R_b, C_b = R_b^T R_b over L_b), the per-point terms from C_b's diagonal and their sum,
+// u_b = C_b a_b (launch_symv_lower_batched), G_b over R_b, S_b = G_b^T G_b over C_b, the contraction of
+// S_b - sym(u_b alpha_b^T) and the reduction.  Value only (no slots anywhere, no mean_weights): c from the squared
+// column norms of the R slabs, which lie back to back and are one lda x (count n) matrix; no C, G or G^T G.
+// Workspace: that of agp_nll_gradient_batch plus five vectors per problem, [term | a | sqrt_b | u | c], each an
+// np2 x count array like z.
+int agp_loo_nll_gradient_batch(agp_context *c, int count, const agp_kernel *const *kernels, const agp_features *const *features,
+                               const double *y, int64_t ldy, const double *y_var, int64_t ldv, const int *n_slots,
+                               const agp_gradient_slot *const *slots, const double *const *tangents, int64_t ldt,
+                               double *loo_nll, double *grad_loo_nll, int64_t ldg, double *mean_weights, int64_t ldw,
+                               int *status) {
+  if (!c || count <= 0 || count > 65535 || !kernels || !features || !y || !n_slots || !loo_nll || !status)
+    return AGP_ERR_INVALID_ARGUMENT;
+  agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
+  bool need_c = mean_weights != nullptr;  // u = C a needs C = R^T R; the values alone need only diag(C)
+  for (int b = 0; b < count; ++b) need_c = need_c || n_slots[b] != 0;
+  enum { TERM, A_VEC, SQRT_B, U_VEC, C_DIAG, N_VECTORS };  // the extra np2 x count arrays
+  GradientBatch g;
+  int st = gradient_batch_begin(ctx, count, kernels, features, y, ldy, y_var, ldv, n_slots, slots, tangents, ldt, grad_loo_nll, ldg,
+                                mean_weights, ldw, /*quad=*/false, /*rtr=*/need_c, N_VECTORS, U_VEC, g);
+  if (st != AGP_OK) return st;
+  hipStream_t s = ctx->stream;
+  const bool prof = ctx->profiling;
+  const long long n = g.n, np2 = g.np2;
+  double *term = g.vector(TERM), *a = g.vector(A_VEC), *sqrt_b = g.vector(SQRT_B), *u = g.vector(U_VEC), *cdiag = g.vector(C_DIAG);
+  const dim3 egrid((unsigned)((n + 255) / 256), (unsigned)count);
+  if (!need_c) {
+    // c_b[i] = ||R_b[:, i]||^2: count n values, contiguous (the terms kernel's cbatch = n)
+    launch_coldot(s, g.R, g.lda, g.R, g.lda, n, (long long)count * n, cdiag, -1.0, nullptr);
+    hipLaunchKernelGGL(loo_terms_kernel, egrid, dim3(256), 0, s, cdiag, 1LL, n, g.z, g.yvar_d, n, g.np2, term, nullptr, nullptr);
+  } else {
+    hipLaunchKernelGGL(loo_terms_kernel, egrid, dim3(256), 0, s, g.A, g.lda + 1, g.stride_A, g.z, g.yvar_d, n, g.np2, term, a, sqrt_b);
+  }
+  hipLaunchKernelGGL(loo_sum_kernel, dim3(1, (unsigned)count), dim3(1024), 0, s, term, n, np2, g.quad);
+  if (need_c) {
+    launch_symv_lower_batched(s, g.A, g.lda, g.stride_A, n, a, np2, u, count);  // u_b = C_b a_b
+    if (g.groups > 0) {
+      const unsigned gt = (unsigned)((n + GF_T - 1) / GF_T);
+      hipLaunchKernelGGL(loo_form_g_kernel, dim3(gt, gt, (unsigned)count), dim3(256), 0, s, g.A, g.lda, sqrt_b, n, g.R, g.lda, g.stride_A,
+                         np2);  // G_b over R_b
+    }
+  }
+  if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[5], s));
+  if (g.groups > 0) {
+    launch_gtg_lower_batched(s, g.R, g.lda, g.stride_A, n, g.A, g.lda, g.stride_A, count);  // S_b = C_b diag(b) C_b over C_b
+    if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[6], s));
+    launch_contract_batched<true>(s, g.dim_max, g.desc_d, g.tiles, count, g.groups);
+    hipLaunchKernelGGL(nll_grad_reduce_batched_kernel, dim3((unsigned)(g.groups * GRAD_GROUP), (unsigned)count), dim3(256), 0, s, g.desc_d,
+                       g.tiles, 1.0, g.grad_d, g.ldgd);
+    if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[7], s));
+  }
+  st = gradient_batch_finish(ctx, g, count, n_slots, [](double, double loo) { return loo; }, loo_nll, grad_loo_nll, ldg, u,
+                             mean_weights, ldw, status);
+  if (st != AGP_OK) return st;
+  if (prof) {
+    // whole-batch times, the indices of agp_loo_nll_gradient
+    for (int k : {3, 4, 5, 6, 7, 8, 9}) ctx->stage_ms[k] = 0.;
+    ctx->stage_ms[0] = elapsed(ctx->stage_ev[0], ctx->stage_ev[1]);
+    ctx->stage_ms[1] = elapsed(ctx->stage_ev[1], ctx->stage_ev[2]);
+    ctx->stage_ms[2] = elapsed(ctx->stage_ev[2], ctx->stage_ev[3]);
+    if (!need_c) {
+      ctx->stage_ms[8] = elapsed(ctx->stage_ev[3], ctx->stage_ev[5]);
+    } else {
+      ctx->stage_ms[6] = elapsed(ctx->stage_ev[3], ctx->stage_ev[4]);
+      ctx->stage_ms[8] = elapsed(ctx->stage_ev[4], ctx->stage_ev[5]);
+      if (g.groups > 0) {
+        ctx->stage_ms[9] = elapsed(ctx->stage_ev[5], ctx->stage_ev[6]);
+        ctx->stage_ms[7] = elapsed(ctx->stage_ev[6], ctx->stage_ev[7]);
+      }
+    }
   }
   return AGP_OK;
 }

@@ -609,6 +609,60 @@ void launch_symv_lower(hipStream_t s, const double *K, long long ld, long long n
   hipLaunchKernelGGL(symv_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(1024), 0, s, rowpart, colpart, ldp, n, alpha, beta, base, out);
 }
 
+// out_b = K_b p_b for `count` symmetric matrices given by their LOWER triangles, in ONE launch and without scratch
+// (agp_loo_nll_gradient_batch's u_b = C_b a_b): K_b = K + b * stride_K, p_b = p + b * stride_v, out_b = out + b * stride_v.
+// The regime is many problems of a few hundred to a few thousand points, where symv_lower_kernel's two launches and
+// n^2 / 32 partials per problem do not pay.  Workgroup (strip of SYMV_W indices i, problem b), both parts coalesced:
+//   row part     sum_{j <= i} K(i, j) p[j]: thread (i = tid & 31, tj = tid >> 5) takes the columns j = tj, tj + 8, ...
+//   column part  sum_{r > i} K(r, i) p[r]:  wave w takes the strip's columns w, w + 4, ..., its lanes walk the rows r
+// and out[i] adds the eight row sums in order, then the column sum.  No atomics; a problem's bits depend on neither its
+// position in the batch nor its neighbours.  Every stored entry is read twice over the launch (once per part).
+__global__ __launch_bounds__(256) void symv_lower_batched_kernel(const double *__restrict__ K, long long ld, long long stride_K,
+                                                                 long long n, const double *__restrict__ p,
+                                                                 long long stride_v, double *__restrict__ out) {
+  __shared__ double rowpart[8][SYMV_W];
+  __shared__ double colsum[SYMV_W];
+  const long long b = blockIdx.y, i0 = (long long)blockIdx.x * SYMV_W;
+  const double *Kb = K + b * stride_K, *pb = p + b * stride_v;
+  const int tid = threadIdx.x;
+  {
+    const int ti = tid & 31, tj = tid >> 5;
+    const long long i = i0 + ti;
+    double acc = 0.;
+    if (i < n)
+      for (long long j = tj; j <= i; j += 8) acc += Kb[i + j * ld] * pb[j];
+    rowpart[tj][ti] = acc;
+  }
+  {
+    const int lane = tid & 63, wave = tid >> 6;
+    for (int c = wave; c < SYMV_W; c += 4) {
+      const long long i = i0 + c;
+      double acc = 0.;
+      if (i < n) {
+        const double *col = Kb + i * ld;
+        for (long long r = i + 1 + lane; r < n; r += 64) acc += col[r] * pb[r];
+      }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+      if (lane == 0) colsum[c] = acc;
+    }
+  }
+  __syncthreads();
+  if (tid < SYMV_W && i0 + tid < n) {
+    double v = rowpart[0][tid];
+#pragma unroll
+    for (int tj = 1; tj < 8; ++tj) v += rowpart[tj][tid];
+    out[b * stride_v + i0 + tid] = v + colsum[tid];
+  }
+}
+
+void launch_symv_lower_batched(hipStream_t s, const double *K, long long ld, long long stride_K, long long n, const double *p,
+                               long long stride_v, double *out, long long count) {
+  if (n <= 0 || count <= 0) return;
+  hipLaunchKernelGGL(symv_lower_batched_kernel, dim3((unsigned)((n + SYMV_W - 1) / SYMV_W), (unsigned)count), dim3(256), 0, s, K, ld,
+                     stride_K, n, p, stride_v, out);
+}
+
 // batched: out[b * m + j] = sum_i Q_b[i, j] z_b[i], Q_b = Q + b * stride_Q (m x m, ld), z_b = z + b * stride_z
 __global__ __launch_bounds__(256) void colvec_dot_batched_kernel(const double *__restrict__ Q, long long ld,
                                                                  long long stride_Q, long long m,

@@ -1241,13 +1241,49 @@ class GaussianProcessRegression:
         if self.precision != "fp64":
             raise ValueError(f"leave_one_out_likelihood_gradient: fp64 models only, not {self.precision!r}")
         loo, slots, grad_loo, u, fs = self._slot_gradient("agp_loo_nll_gradient", dataset, with_variance=True)
+        return loo, self._leave_one_out_gradient_dict(slots, grad_loo, u, fs)
+
+    def leave_one_out_likelihoods(self, dataset, parameter_sets):
+        """LeaveOneOutLikelihood()(dataset, self) for several parameter vectors at once (agp_loo_nll_gradient_batch
+        without slots: the value-only path, c_i from the column norms of R, no K^-1).  The counterpart of log_likelihoods
+        for the metric: parameter_sets is an iterable of {name: value} overrides of the current parameters, the target
+        variance is used as in leave_one_out_likelihood_gradient.  Returns an array of metric values; a parameter vector
+        whose covariance is not positive definite (or has NaN) gives NaN.  fp64 models only."""
+        if self.precision != "fp64":
+            raise ValueError(f"leave_one_out_likelihoods: fp64 models only, not {self.precision!r}")
+        models = self._override_copies(parameter_sets)
+        if not models:
+            return np.zeros(0)
+        values, _ = _leave_one_out_likelihood_gradients(models, [dataset] * len(models), "leave_one_out_likelihoods", value_only=True)
+        return np.asarray(values)
+
+    def leave_one_out_likelihood_gradients(self, dataset, parameter_sets):
+        """leave_one_out_likelihood_gradient(dataset) for several parameter vectors at once (agp_loo_nll_gradient_batch):
+        the counterpart of log_likelihood_gradients for the metric the tuner minimises.  parameter_sets: iterable of
+        {name: value} overrides of the current parameters (one model copy each).  Returns (values: array[count],
+        gradients: [{name: value}] with every name of get_params()).  Signs, target variance and mean-function
+        parameters as in leave_one_out_likelihood_gradient; ScalingTerm tangents are taken per copy, at its own
+        parameters.  A parameter vector whose covariance is not positive definite (or has NaN) gives NaN throughout,
+        not an exception.  fp64 models only."""
+        if self.precision != "fp64":
+            raise ValueError(f"leave_one_out_likelihood_gradients: fp64 models only, not {self.precision!r}")
+        models = self._override_copies(parameter_sets)
+        if not models:
+            return np.zeros(0), []
+        values, grads = _leave_one_out_likelihood_gradients(models, [dataset] * len(models), "leave_one_out_likelihood_gradients")
+        return np.asarray(values), grads
+
+    def _leave_one_out_gradient_dict(self, slots, grad_loo, u, fs):
+        """{name: d LOO / d name} from agp_loo_nll_gradient's per-slot values and mean weights u (slots sharing a name
+        summed)"""
         grad = {name: 0. for name in self.get_params()}
         for (_, _, name), g in zip(slots, grad_loo):
             grad[name] += g
         # y = targets - mu: d LOO / d theta = -u^T (d mu / d theta)
         for name in self.mean_function_.get_params():
             grad[name] -= float(u @ self._mean_tangent(fs, name))
-        return loo, grad
+        return grad
+
 
 class LeaveOneOutGrouper:
     """LeaveOneOutGrouper (indexing/group_by.hpp): every observation is its own group."""
@@ -1577,6 +1613,77 @@ def log_likelihood_gradient_batch(models, datasets):
         raise ValueError("log_likelihood_gradient_batch: as many datasets as models, at least one")
     lls, grads = _log_likelihood_gradients(models[0]._ctx(), list(models), list(datasets))
     return list(zip(lls, grads))
+
+
+def _leave_one_out_likelihood_gradients(models, datasets, caller, value_only=False):
+    """one agp_loo_nll_gradient_batch call over models[b] on datasets[b]: ([LOO_b], [{name: d LOO_b / d name}]), NaN
+    throughout for a problem whose covariance has NaN or is not positive definite.  caller: the public name, for the
+    error texts.  value_only: no slots and no mean weights (the entry's value-only path); the gradients are None."""
+    count = len(models)
+    # plain checks first, none of which needs a device: LinearCombination features, precision, then one context
+    for ds in datasets:
+        if has_linear_combinations(ds.features):
+            raise NotImplementedError(f"{caller} (agp_loo_nll_gradient_batch): LinearCombination features go through the dense path")
+    if any(m.precision != "fp64" for m in models):
+        raise ValueError(f"{caller}: fp64 models only")
+    ctx = models[0]._ctx()
+    if any(m._ctx() is not ctx for m in models):
+        raise ValueError(f"{caller}: every model must live on one context")
+    problems = [_gradient_problem(m, ds, "agp_loo_nll_gradient_batch") for m, ds in zip(models, datasets)]
+    n = problems[0].fs.n
+    if any(p.fs.n != n for p in problems):
+        raise ValueError(f"{caller}: every dataset must have the same number of points")
+    structs = [p.fs.as_struct() for p in problems]
+    Y = np.asfortranarray(np.stack([p.y for p in problems], axis=1))
+    # the target variance, in the fit and as the truth's variance; problems without one get zeros beside those with one
+    have_var = any(p.yv is not None for p in problems)
+    V = np.asfortranarray(np.stack([np.zeros(n) if p.yv is None else p.yv for p in problems], axis=1)) if have_var else None
+    n_used = [0 if value_only else len(p.slots) for p in problems]
+    ldg = max(1, max(n_used))
+    loo = np.empty(count)
+    grad = np.zeros((count, ldg))                   # column b of the ldg x count array: row b here
+    u = None if value_only else np.empty((count, n))  # likewise, ldw = n
+    status = (C.c_int * count)()
+    n_slots = (C.c_int * count)(*n_used)
+    tables = (C.c_void_p * count)(*[C.addressof(p.table) for p in problems])
+    tangents = (C.c_void_p * count)(*[None if p.tangents is None else p.tangents.ctypes.data for p in problems])
+    handles = []
+    try:
+        for m in models:  # private handles: the context's small kernel cache may evict while the batch is assembled
+            handles.append(ctx.private_kernel(m.covariance_function_))
+        kernels = (C.c_void_p * count)(*handles)
+        fptrs = (C.c_void_p * count)(*[C.addressof(st) for st in structs])
+        ctx._check(ctx._lib.agp_loo_nll_gradient_batch(ctx._h, count, kernels, fptrs, _ptr(Y), n, _ptr(V) if have_var else None, n,
+                                                       n_slots, tables, tangents, n, _ptr(loo), _ptr(grad), ldg,
+                                                       None if value_only else _ptr(u), n, status),
+                   "agp_loo_nll_gradient_batch")
+    finally:
+        for kh in handles:
+            ctx._lib.agp_kernel_destroy(kh)
+    values, grads = [], []
+    for b, (m, p) in enumerate(zip(models, problems)):
+        ok = status[b] == capi.AGP_OK
+        values.append(float(loo[b]) if ok else float("nan"))
+        if value_only:
+            grads.append(None)
+        elif ok:
+            grads.append(m._leave_one_out_gradient_dict(p.slots, grad[b, :len(p.slots)], u[b], p.fs))
+        else:
+            grads.append({name: float("nan") for name in m.get_params()})
+    return values, grads
+
+
+def leave_one_out_likelihood_gradient_batch(models, datasets):
+    """`models[b].leave_one_out_likelihood_gradient(datasets[b])` for several INDEPENDENT problems of one size in one
+    call (agp_loo_nll_gradient_batch): the counterpart of log_likelihood_gradient_batch for the leave-one-out metric.
+    models: fp64 GaussianProcessRegression objects on one context (their covariance trees and feature dimensions may
+    differ); datasets: as many RegressionDatasets with the same number of points, each with or without a target
+    variance.  Returns a list of (value, {name: gradient}); a problem whose covariance has NaN or is not positive
+    definite gives NaN throughout instead of raising."""
+    if len(models) != len(datasets) or not models:
+        raise ValueError("leave_one_out_likelihood_gradient_batch: as many datasets as models, at least one")
+    values, grads = _leave_one_out_likelihood_gradients(list(models), list(datasets), "leave_one_out_likelihood_gradient_batch")
+    return list(zip(values, grads))
 
 
 def gp_from_covariance(covariance_function, model_name="gaussian_process_regression", context=None):

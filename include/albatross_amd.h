@@ -349,6 +349,37 @@ AGP_API int agp_loo_nll_gradient(agp_context *ctx, const agp_kernel *k, const ag
                                  double *loo_nll, double *grad_loo_nll,
                                  double *mean_weights);
 
+/* agp_loo_nll_gradient for `count` problems of one size in lock step: problem b computes exactly what
+ * agp_loo_nll_gradient computes for kernels[b], features[b] and column b of y / y_var (used in both places, the fit and
+ * the truth's variance), with its own slot table.  The leave-one-out counterpart of agp_nll_gradient_batch, for the same
+ * regime (a multi-start or finite-difference tuner of the metric, an ensemble over hyper-parameters, one model per
+ * station): every step runs once for the whole batch (blockIdx.y = problem), the number of launches does not depend on
+ * count.  Arguments as agp_nll_gradient_batch, with
+ *   loo_nll[b]                the leave-one-out metric (host)
+ *   grad_loo_nll, ldg         ldg x count (host): column b holds problem b's n_slots[b] values; ldg >= max n_slots[b]
+ *   mean_weights, ldw         n x count (host, column b is u_b; ldw >= n), or NULL
+ *   status[b]                 AGP_OK / AGP_ERR_NAN_INPUT / AGP_ERR_NOT_POSITIVE_DEFINITE (host)
+ * A failed problem gets loo_nll[b] = NaN and a NaN column of grad_loo_nll; its column of mean_weights is left untouched
+ * and the rest of the batch is unaffected.  A malformed argument in any problem (the list of agp_nll_gradient_batch, or
+ * mean_weights with ldw < n) makes the call return AGP_ERR_INVALID_ARGUMENT and write nothing.  Every n_slots[b] == 0 and
+ * mean_weights NULL: the values alone, c_i from the squared column norms of the R slabs; neither C, G nor G^T G is formed.
+ * No float atomics, fixed-order reductions: two identical calls are bit-identical, and no problem's arithmetic depends on
+ * its position or its neighbours.  Workspace: that of agp_nll_gradient_batch (two lda x n slabs per problem: G_b is
+ * written over R_b and S_b over C_b) plus five n-vectors per problem.  With profiling on, agp_last_stage_ms reports
+ * whole-batch times with the indices of agp_loo_nll_gradient: 0 gram, 1 factor, 2 alpha and R = L^-1, 6 R^T R, 8 the
+ * per-point terms, u and G (value only: the column norms and the terms), 9 G^T G, 7 the contraction. */
+AGP_API int agp_loo_nll_gradient_batch(agp_context *ctx, int count,
+                                       const agp_kernel *const *kernels, const agp_features *const *features,
+                                       const double *y, int64_t ldy,
+                                       const double *y_var, int64_t ldv,
+                                       const int *n_slots,
+                                       const agp_gradient_slot *const *slots,
+                                       const double *const *tangents, int64_t ldt,
+                                       double *loo_nll,
+                                       double *grad_loo_nll, int64_t ldg,
+                                       double *mean_weights, int64_t ldw,
+                                       int *status);
+
 /* Tuner objective batching: agp_nll for `count` parameter vectors of one model on one dataset in lock step
  * (batched Gram slabs + batched LL^T; blockIdx.y = parameter vector) — the evaluations that
  * compute_gradient (include/albatross/src/tune/finite_difference.hpp:20-94) and the ModelTuner objective

@@ -1932,57 +1932,17 @@ class GaussianProcessRegression {
   template <typename FeatureType>
   std::vector<LogLikelihoodGradient> log_likelihood_gradients(const RegressionDataset<FeatureType> &dataset,
                                                              const std::vector<ParameterStore> &parameter_sets) const {
-    const std::size_t count = parameter_sets.size(), n = dataset.features.size();
     std::vector<LogLikelihoodGradient> out;
-    if (count == 0) return out;
-    auto ctx = detail::default_context();
-    std::vector<GaussianProcessRegression> models(count, *this);
-    std::vector<std::unique_ptr<detail::KernelHolder>> kernels;
-    std::vector<detail::Flat> flats(count);
-    std::vector<const agp_kernel *> kptr(count);
-    std::vector<const agp_features *> fptr(count);
-    std::vector<double> Y(n * count);
-    std::vector<std::vector<std::string>> names(count);
-    std::vector<std::vector<agp_gradient_slot>> slots(count);
-    std::vector<std::vector<double>> tangents(count);
-    std::vector<int> n_slots(count);
-    std::size_t ldg = 1;
-    for (std::size_t b = 0; b < count; ++b) {
-      models[b].set_param_values(parameter_sets[b]);
-      kernels.emplace_back(new detail::KernelHolder(models[b].covariance_function_.program()));
-      flats[b] = detail::flatten(models[b].covariance_function_, dataset.features);
-      kptr[b] = kernels.back()->k;
-      const Vector y = models[b].deviation(dataset);
-      for (std::size_t i = 0; i < n; ++i) Y[b * n + i] = y[i];
-      models[b].slot_table(dataset, &names[b], &slots[b], &tangents[b]);
-      n_slots[b] = static_cast<int>(slots[b].size());
-      ldg = std::max(ldg, slots[b].size());
-    }
-    std::vector<const agp_gradient_slot *> sptr(count);
-    std::vector<const double *> tptr(count);
-    for (std::size_t b = 0; b < count; ++b) {  // after the vectors stopped moving
-      fptr[b] = &flats[b].view;
-      sptr[b] = slots[b].empty() ? nullptr : slots[b].data();
-      tptr[b] = tangents[b].empty() ? nullptr : tangents[b].data();
-    }
-    std::vector<double> nll(count), grad(ldg * count), alpha(n * count);
-    std::vector<int> status(count);
     // like log_likelihood: the target variance is NOT part of the covariance (gp.hpp:442-451)
-    detail::check(agp_nll_gradient_batch(ctx->ctx, static_cast<int>(count), kptr.data(), fptr.data(), Y.data(),
-                                         static_cast<std::int64_t>(n), nullptr, 0, n_slots.data(), sptr.data(), tptr.data(),
-                                         static_cast<std::int64_t>(n), nll.data(), grad.data(), static_cast<std::int64_t>(ldg),
-                                         alpha.data(), static_cast<std::int64_t>(n), status.data()),
-                  ctx->ctx, "agp_nll_gradient_batch");
-    for (std::size_t b = 0; b < count; ++b) {
-      if (status[b] != AGP_OK) {
-        const double nan = std::numeric_limits<double>::quiet_NaN();
-        LogLikelihoodGradient r{nan, {}};
-        for (const auto &kv : models[b].get_params()) r.gradient[kv.first] = nan;
-        out.push_back(r);
+    const BatchedSlotGradients r = slot_gradients_batch(agp_nll_gradient_batch, "agp_nll_gradient_batch", dataset, parameter_sets, false);
+    const std::size_t n = dataset.features.size();
+    for (std::size_t b = 0; b < parameter_sets.size(); ++b) {
+      if (r.status[b] != AGP_OK) {
+        out.push_back(LogLikelihoodGradient{std::numeric_limits<double>::quiet_NaN(), r.models[b].nan_gradient()});
         continue;
       }
-      const std::vector<double> a(alpha.begin() + static_cast<std::ptrdiff_t>(b * n), alpha.begin() + static_cast<std::ptrdiff_t>((b + 1) * n));
-      out.push_back(models[b].gradient_of_log_likelihood(dataset, nll[b], names[b], grad.data() + b * ldg, a));
+      const std::vector<double> a(r.vec.begin() + static_cast<std::ptrdiff_t>(b * n), r.vec.begin() + static_cast<std::ptrdiff_t>((b + 1) * n));
+      out.push_back(r.models[b].gradient_of_log_likelihood(dataset, r.value[b], r.names[b], r.grad.data() + b * r.ldg, a));
     }
     return out;
   }
@@ -2025,6 +1985,47 @@ class GaussianProcessRegression {
     return loo;
   }
 
+  // leave_one_out_likelihood_gradient(dataset) for several parameter vectors in ONE batched device pass
+  // (agp_loo_nll_gradient_batch), one model copy per entry as log_likelihood_gradients makes them.  Signs and the target
+  // variance as in leave_one_out_likelihood_gradient.  A parameter vector whose covariance is not positive definite (or
+  // has NaN) gives NaN for the value and every gradient entry.
+  template <typename FeatureType>
+  std::vector<LeaveOneOutLikelihoodGradient> leave_one_out_likelihood_gradients(const RegressionDataset<FeatureType> &dataset,
+                                                                                const std::vector<ParameterStore> &parameter_sets) const {
+    std::vector<LeaveOneOutLikelihoodGradient> out;
+    const BatchedSlotGradients r =
+        slot_gradients_batch(agp_loo_nll_gradient_batch, "agp_loo_nll_gradient_batch", dataset, parameter_sets, true);
+    const std::size_t n = dataset.features.size();
+    for (std::size_t b = 0; b < parameter_sets.size(); ++b) {
+      if (r.status[b] != AGP_OK) {
+        out.push_back(LeaveOneOutLikelihoodGradient{std::numeric_limits<double>::quiet_NaN(), r.models[b].nan_gradient()});
+        continue;
+      }
+      const GaussianProcessRegression &m = r.models[b];
+      LeaveOneOutLikelihoodGradient g{r.value[b], {}};
+      for (const auto &kv : m.get_params()) g.gradient[kv.first] = 0.;
+      for (std::size_t s = 0; s < r.names[b].size(); ++s) g.gradient[r.names[b][s]] += r.grad[b * r.ldg + s];
+      const std::vector<double> u(r.vec.begin() + static_cast<std::ptrdiff_t>(b * n), r.vec.begin() + static_cast<std::ptrdiff_t>((b + 1) * n));
+      for (const auto &kv : m.mean_function_.get_params())  // y = targets - mu: d LOO / d theta = -u^T (d mu / d theta)
+        g.gradient[kv.first] -= m.mean_tangent_dot(dataset, kv.first, kv.second, u);
+      out.push_back(g);
+    }
+    return out;
+  }
+
+  // leave_one_out_likelihood(dataset) for several parameter vectors in ONE batched device pass: the value-only path of
+  // agp_loo_nll_gradient_batch (no slots, no mean weights: c_i from the column norms of R, no K^-1).  NaN where the
+  // covariance is not positive definite.
+  template <typename FeatureType>
+  Vector leave_one_out_likelihoods(const RegressionDataset<FeatureType> &dataset, const std::vector<ParameterStore> &parameter_sets) const {
+    const BatchedSlotGradients r = slot_gradients_batch(agp_loo_nll_gradient_batch, "agp_loo_nll_gradient_batch", dataset, parameter_sets,
+                                                        true, /*value_only=*/true);
+    Vector out(parameter_sets.size());
+    for (std::size_t b = 0; b < out.size(); ++b)
+      out[b] = r.status[b] == AGP_OK ? r.value[b] : std::numeric_limits<double>::quiet_NaN();
+    return out;
+  }
+
   // gp.hpp:442-451 (prior_log_likelihood() is outside the hot path and not included).  As in the reference the
   // covariance is covariance_function_(measurement_features) alone: dataset.targets.covariance is NOT added.
   template <typename FeatureType>
@@ -2050,6 +2051,78 @@ class GaussianProcessRegression {
       for (std::size_t i = 0; i < y.size(); ++i)
         y[i] -= mean_function_._call_impl(detail::unwrap<FeatureType>::get(dataset.features[i]));
     return y;
+  }
+
+  // every name of get_params() -> NaN: the gradient of a failed problem of a batch
+  ParameterStore nan_gradient() const {
+    ParameterStore g;
+    for (const auto &kv : get_params()) g[kv.first] = std::numeric_limits<double>::quiet_NaN();
+    return g;
+  }
+
+  // One call of a batched gradient entry (agp_nll_gradient_batch / agp_loo_nll_gradient_batch) over one model copy per
+  // parameter set: the copies, their slot names, and per problem the value, the ldg slot gradients, the n values the
+  // entry returns (alpha / mean weights) and the status.  with_variance: dataset.targets.covariance is passed on, one
+  // vector shared by every problem.  value_only: no slots and no n-vector are asked for (names, grad and vec stay empty).
+  struct BatchedSlotGradients {
+    std::vector<GaussianProcessRegression> models;
+    std::vector<std::vector<std::string>> names;
+    std::vector<double> value, grad, vec;
+    std::vector<int> status;
+    std::size_t ldg = 1;
+  };
+  using BatchedGradientEntry = int (*)(agp_context *, int, const agp_kernel *const *, const agp_features *const *, const double *,
+                                       std::int64_t, const double *, std::int64_t, const int *, const agp_gradient_slot *const *,
+                                       const double *const *, std::int64_t, double *, double *, std::int64_t, double *, std::int64_t,
+                                       int *);
+
+  template <typename FeatureType>
+  BatchedSlotGradients slot_gradients_batch(BatchedGradientEntry entry, const char *what, const RegressionDataset<FeatureType> &dataset,
+                                            const std::vector<ParameterStore> &parameter_sets, bool with_variance,
+                                            bool value_only = false) const {
+    const std::size_t count = parameter_sets.size(), n = dataset.features.size();
+    BatchedSlotGradients r;
+    if (count == 0) return r;
+    auto ctx = detail::default_context();
+    r.models.assign(count, *this);
+    r.names.resize(count);
+    std::vector<std::unique_ptr<detail::KernelHolder>> kernels;
+    std::vector<detail::Flat> flats(count);
+    std::vector<const agp_kernel *> kptr(count);
+    std::vector<const agp_features *> fptr(count);
+    std::vector<double> Y(n * count);
+    std::vector<std::vector<agp_gradient_slot>> slots(count);
+    std::vector<std::vector<double>> tangents(count);
+    std::vector<int> n_slots(count);
+    for (std::size_t b = 0; b < count; ++b) {
+      r.models[b].set_param_values(parameter_sets[b]);
+      kernels.emplace_back(new detail::KernelHolder(r.models[b].covariance_function_.program()));
+      flats[b] = detail::flatten(r.models[b].covariance_function_, dataset.features);
+      kptr[b] = kernels.back()->k;
+      const Vector y = r.models[b].deviation(dataset);
+      for (std::size_t i = 0; i < n; ++i) Y[b * n + i] = y[i];
+      if (!value_only) r.models[b].slot_table(dataset, &r.names[b], &slots[b], &tangents[b]);
+      n_slots[b] = static_cast<int>(slots[b].size());
+      r.ldg = std::max(r.ldg, slots[b].size());
+    }
+    std::vector<const agp_gradient_slot *> sptr(count);
+    std::vector<const double *> tptr(count);
+    for (std::size_t b = 0; b < count; ++b) {  // after the vectors stopped moving
+      fptr[b] = &flats[b].view;
+      sptr[b] = slots[b].empty() ? nullptr : slots[b].data();
+      tptr[b] = tangents[b].empty() ? nullptr : tangents[b].data();
+    }
+    r.value.resize(count);
+    r.grad.resize(r.ldg * count);
+    if (!value_only) r.vec.resize(n * count);
+    r.status.resize(count);
+    const double *yvar = with_variance && !dataset.targets.covariance.empty() ? dataset.targets.covariance.data() : nullptr;
+    detail::check(entry(ctx->ctx, static_cast<int>(count), kptr.data(), fptr.data(), Y.data(), static_cast<std::int64_t>(n), yvar, 0,
+                        n_slots.data(), sptr.data(), tptr.data(), static_cast<std::int64_t>(n), r.value.data(), r.grad.data(),
+                        static_cast<std::int64_t>(r.ldg), value_only ? nullptr : r.vec.data(), static_cast<std::int64_t>(n),
+                        r.status.data()),
+                  ctx->ctx, what);
+    return r;
   }
 
   // The slot table of the covariance function at the dataset's features: names[s] / slots[s] per slot, and the tangent
