@@ -3,6 +3,8 @@
 // Host-side orchestration only: uploads POD feature vectors, enqueues the HIP
 // kernels of gram.hip / chol.hip / gemm.hip / reduce.hip on the context's
 // stream, reads back the small results.  No CPU arithmetic fallback exists.
+// The batched fits (agp_nll_batch, agp_fit_create_batch) are built on the front end of batch_front.h, their
+// workspaces - and agp_nll's - on the layouts of batch_layout.h.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -13,6 +15,7 @@
 #include <thread>
 
 #include "api_internal.h"
+#include "batch_front.h"
 #include <deque>
 #include <mutex>
 #include <tuple>
@@ -1433,16 +1436,14 @@ int agp_nll(agp_context *c, const agp_kernel *k, const agp_features *x, const do
   if (n <= 0) return AGP_ERR_INVALID_ARGUMENT;
   const DevProgram *dprog = nullptr;
   if ((st = device_program(ctx, k, &dprog)) != AGP_OK) return st;
-  const long long lda = factor_ld(n);
-  const long long nblk = (n + NB - 1) / NB;
-  // workspace: [A | invd | z | yvar]
-  const size_t a_bytes = sizeof(double) * (size_t)lda * (size_t)n;
-  const size_t aux = sizeof(double) * ((size_t)nblk * (36 * MB * MB) + 2 * (size_t)round_up(n, 2));
-  if ((st = ensure_ws(ctx, &ctx->ws_A, &ctx->ws_A_bytes, a_bytes + aux)) != AGP_OK) return st;
-  double *A = ctx->ws_A;
-  double *invd = A + (size_t)lda * (size_t)n;
-  double *z = invd + (size_t)nblk * (36 * MB * MB);
-  double *yvar_d = y_var ? z + round_up(n, 2) : nullptr;
+  const BatchGeometry g = batch_geometry(n, 1);
+  const long long lda = g.lda;
+  WsLayout size;
+  carve_fit(size, g);
+  if ((st = ensure_ws(ctx, &ctx->ws_A, &ctx->ws_A_bytes, size.bytes())) != AGP_OK) return st;
+  WsLayout ws(ctx->ws_A);
+  const FitRegions r = carve_fit(ws, g);
+  double *A = r.A, *invd = r.invd, *z = r.z, *yvar_d = y_var ? r.yvar : nullptr;
   DeviceFeatures dx;
   if ((st = to_device(ctx, x, false, &dx)) != AGP_OK) return st;
   if ((st = vector_to_device(ctx, y, n, x->location, z)) != AGP_OK) { dx.release(); return st; }
@@ -1488,97 +1489,58 @@ void *host_stage(agp_context *ctx, size_t bytes) {
 // slabs and factored by the batched kernels (blockIdx.y = parameter vector), so small and medium N pay
 // the launch chain once instead of `count` times.  A parameter vector whose covariance is not positive
 // definite (or has NaN) yields NaN in its slot, like the reference's NaN metric (tune.hpp:163-165).
+// On the shared front end (batch_front.h): memory from ws_A (batch_layout.h: carve_nll_batch), the context's one status
+// block for all problems and no NaN flags from the Gram, one shared variance vector, never the look-ahead schedule.
 int agp_nll_batch(agp_context *c, int count, const agp_kernel *const *kernels, const agp_features *const *features,
                   const double *y, int64_t ldy, const double *y_var, double *out) {
-  if (!c || count <= 0 || !kernels || !features || !y || !out) return AGP_ERR_INVALID_ARGUMENT;
+  if (!c || !y || !out) return AGP_ERR_INVALID_ARGUMENT;
   agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
+  long long n = 0;
+  int st = check_batch_problems(count, kernels, features, ldy, nullptr, 0, &n);
+  if (st != AGP_OK) return st;
   AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  const long long n = features[0] ? features[0]->n : 0;
-  if (n <= 0 || (ldy != 0 && ldy < n)) return AGP_ERR_INVALID_ARGUMENT;
-  int st = AGP_OK;
-  for (int b = 0; b < count; ++b) {
-    if (!kernels[b] || !features[b] || features[b]->n != n || features[b]->location != features[0]->location)
-      return AGP_ERR_INVALID_ARGUMENT;
-    if ((st = validate_features(features[b])) != AGP_OK) return st;
-  }
-  const long long lda = factor_ld(n), nblk = (n + NB - 1) / NB, np2 = round_up(n, 2);
-  const long long stride_A = lda * n, stride_I = nblk * (36 * MB * MB);
+  const BatchGeometry g = batch_geometry(n, count);
   hipStream_t s = ctx->stream;
-  // workspace: [A slabs | tile images | y slabs | yvar | logsum | quad | z slots of the fused panel launches | Gram table]
-  const bool fused_panels = batched_fused_fits(ctx, n, count);
-  const size_t table_elems = (gram_batch_table_bytes(count) + 7) / 8;
-  const size_t elems = (size_t)count * ((size_t)stride_A + (size_t)stride_I + (size_t)np2) + (size_t)np2 +
-                       2 * (size_t)round_up(count, 2) + (fused_panels ? (size_t)count * (size_t)np2 : 0) + table_elems;
-  if ((st = ensure_ws(ctx, &ctx->ws_A, &ctx->ws_A_bytes, sizeof(double) * elems)) != AGP_OK) return st;
-  double *A = ctx->ws_A, *invd = A + (size_t)count * (size_t)stride_A, *ys = invd + (size_t)count * (size_t)stride_I;
-  double *yvar_d = ys + (size_t)count * (size_t)np2, *logsum = yvar_d + np2, *quad = logsum + round_up(count, 2);
-  double *zpub = fused_panels ? quad + round_up(count, 2) : nullptr;
-  void *table = quad + round_up(count, 2) + (fused_panels ? (size_t)count * (size_t)np2 : 0);
+  const bool fused_panels = batched_fused_panels(ctx, g, /*allow_lookahead=*/false);
+  const size_t table_bytes = gram_batch_table_bytes(count);
+  WsLayout size;
+  carve_nll_batch(size, g, fused_panels, table_bytes);
+  if ((st = ensure_ws(ctx, &ctx->ws_A, &ctx->ws_A_bytes, size.bytes())) != AGP_OK) return st;
+  WsLayout ws(ctx->ws_A);
+  const NllBatchRegions r = carve_nll_batch(ws, g, fused_panels, table_bytes);
   const int loc = features[0]->location;
-  const hipMemcpyKind kind = loc == AGP_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-  for (int b = 0; b < count; ++b)
-    AGP_HIP_CHECK(ctx, hipMemcpyAsync(ys + (size_t)b * (size_t)np2, y + (size_t)b * (size_t)ldy, sizeof(double) * (size_t)n,
-                                      kind, s));
-  if (y_var) AGP_HIP_CHECK(ctx, hipMemcpyAsync(yvar_d, y_var, sizeof(double) * (size_t)n, kind, s));
+  if ((st = upload_problem_columns(ctx, y, ldy, n, count, loc, r.ys, g.np2)) != AGP_OK) return st;
+  if (y_var && (st = upload_problem_columns(ctx, y_var, n, n, 1, loc, r.yvar, g.np2)) != AGP_OK) return st;
   if (loc == AGP_HOST) AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
   {  // one preparation launch: log sums and flags zeroed, the hand-over buffers of the fused panel launches sentinel-filled
     PrepArgs prep;
-    prep.fill(logsum, 0ull, round_up(count, 2));
+    prep.fill(r.logsum, 0ull, g.cp2);
     prep.fill(ctx->d_flags, 0ull, 2);
-    if (zpub) {
-      prep.sentinel(invd, count * stride_I);
-      prep.sentinel(zpub, count * np2);
-    }
-    launch_prep(s, prep);
+    launch_batch_prep(s, prep, g, r.invd, r.zpub);
   }
-  std::vector<DeviceFeatures> dxs((size_t)count);
-  const agp_features *last = nullptr;
-  int last_b = -1;
-  std::vector<FeatView> views((size_t)count);
-  std::vector<const DevProgram *> hprogs((size_t)count);
-  std::vector<double *> outs((size_t)count);
-  for (int b = 0; b < count && st == AGP_OK; ++b) {
-    // parameter vectors usually share one feature array: upload it once
-    const bool same = last && features[b]->coords == last->coords && features[b]->scales == last->scales &&
-                      features[b]->eq_id == last->eq_id;
-    if (!same) {
-      if ((st = to_device(ctx, features[b], false, &dxs[(size_t)b])) != AGP_OK) break;
-      last = features[b];
-      last_b = b;
-    }
-    views[(size_t)b] = dxs[(size_t)(same ? last_b : b)].v;
-    views[(size_t)b].meas = 1;  // as_measurements(features), gp.hpp:288
-    hprogs[(size_t)b] = &kernels[b]->prog;
-    outs[(size_t)b] = A + (size_t)b * (size_t)stride_A;
-  }
-  bool gram_done = false;
-  if (st == AGP_OK && count > 1) {  // all Gram matrices in ONE launch when the trees share a fast path (gram.hip)
-    std::vector<const double *> diag((size_t)count, y_var ? yvar_d : nullptr);
-    // (the descriptor table lives in the workspace and is uploaded from the context's pinned staging area: no allocation,
-    // no synchronisation between the upload and the launch)
-    gram_done = launch_gram_batch(s, count, hprogs.data(), views.data(), outs.data(), lda, y_var ? diag.data() : nullptr, nullptr, table,
-                                  host_stage(ctx, gram_batch_table_bytes(count)));
-  }
-  for (int b = 0; b < count && st == AGP_OK && !gram_done; ++b) {
-    const DevProgram *dprog = nullptr;
-    if ((st = device_program(ctx, kernels[b], &dprog)) != AGP_OK) break;
-    launch_gram(s, dprog, views[(size_t)b], views[(size_t)b], true, true, outs[(size_t)b], lda, y_var ? yvar_d : nullptr, nullptr,
-                &kernels[b]->prog);
-  }
-  if (st == AGP_OK) {
-    factor_lower_batched(s, A, stride_A, n, lda, invd, stride_I, ys, np2, count, ctx->d_flags, logsum, 0, zpub, np2);
-    launch_coldot(s, ys, np2, ys, np2, n, count, quad, -1.0, nullptr);  // z_b^T z_b, z_b = L_b^-1 y_b
-    std::vector<double> h(2 * (size_t)round_up(count, 2));
-    hipError_t e = hipMemcpyAsync(h.data(), logsum, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); st = AGP_ERR_HIP; }
-    else
-      for (int b = 0; b < count; ++b)  // likelihood.hpp:38-47
-        out[b] = 0.5 * (2. * h[(size_t)b] + h[(size_t)round_up(count, 2) + (size_t)b] + (double)n * std::log(2 * M_PI));
-  }
-  for (auto &d : dxs) d.release();
-  return st;
+  BatchGramTables tables(g, kernels, r.A, y_var ? r.yvar : nullptr, 0, nullptr, 0);
+  if ((st = tables.upload_features(ctx, features)) != AGP_OK) return st;
+  if ((st = launch_batch_grams(ctx, g, tables, kernels, r.gram_table, count > 1 ? host_stage(ctx, table_bytes) : nullptr)) != AGP_OK)
+    return st;
+  factor_batch(ctx, g, /*allow_lookahead=*/false, r.A, r.invd, r.ys, ctx->d_flags, 0, r.logsum, r.zpub);
+  launch_coldot(s, r.ys, g.np2, r.ys, g.np2, n, count, r.quad, -1.0, nullptr);  // z_b^T z_b, z_b = L_b^-1 y_b
+  std::vector<double> h(2 * (size_t)g.cp2);  // [logsum | quad]
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(h.data(), r.logsum, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  for (int b = 0; b < count; ++b)  // likelihood.hpp:38-47
+    out[b] = 0.5 * (2. * h[(size_t)b] + h[(size_t)g.cp2 + (size_t)b] + (double)n * std::log(2 * M_PI));
+  return AGP_OK;
+}
+
+// problem's training features inside the slab of its batch: coordinates, equality ids, scale columns
+static FeatView carve_features(WsLayout &ws, const agp_features *f) {
+  FeatView v;
+  v.n = f->n; v.dim = f->dim; v.nsc = f->n_scale_columns; v.meas = 0;
+  v.coords = ws.take<double>((size_t)f->n * (size_t)f->dim);
+  v.ids = f->eq_id ? ws.take<long long>((size_t)f->n) : nullptr;
+  v.scales = f->n_scale_columns > 0 ? ws.take<double>((size_t)f->n * (size_t)f->n_scale_columns) : nullptr;
+  return v;
 }
 
 // B independent fits of one shape in lock step: the Fit<GPFit> constructor (models/gp.hpp:61-69) for `count` datasets /
@@ -1586,44 +1548,37 @@ int agp_nll_batch(agp_context *c, int count, const agp_kernel *const *kernels, c
 // (benchmarks/bench_predict.cc:20-40, the tuner loop tune/tune.hpp:276-290) - ONE fit is bound by the latency of its
 // 128 serial pivots per panel (27-30 us per POTRF, config 2: 0.14 of the MFMA peak); a batch shares that latency and
 // fills the chip with the trailing updates of all problems (factor_lower_batched).
+// On the shared front end (batch_front.h): one allocation of its own that the fits keep (batch_layout.h:
+// carve_fit_batch, then each problem's training features), the tables of the call from dev_malloc
+// (carve_fit_batch_tables), status words per problem, the look-ahead schedule where the predicate asks for it.
 int agp_fit_create_batch(agp_context *c, int count, const agp_kernel *const *kernels, const agp_features *const *features,
                          const double *y, int64_t ldy, const double *y_var, int64_t ldv, agp_fit **out, double *information,
                          int64_t ldi, double *log_det, int *status) {
-  if (!c || count <= 0 || !kernels || !features || !y || !out || !status) return AGP_ERR_INVALID_ARGUMENT;
+  if (!c || count <= 0 || count > BATCH_MAX_PROBLEMS || !kernels || !features || !y || !out || !status) return AGP_ERR_INVALID_ARGUMENT;
   agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
   AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   for (int b = 0; b < count; ++b) { out[b] = nullptr; status[b] = AGP_ERR_INVALID_ARGUMENT; }
-  const long long n = features[0] ? features[0]->n : 0;
-  if (n <= 0 || (ldy != 0 && ldy < n) || (y_var && ldv != 0 && ldv < n) || (information && ldi < n)) return AGP_ERR_INVALID_ARGUMENT;
-  int st = AGP_OK;
-  for (int b = 0; b < count; ++b) {
-    if (!kernels[b] || !features[b] || features[b]->n != n || features[b]->location != features[0]->location)
-      return AGP_ERR_INVALID_ARGUMENT;
-    if ((st = validate_features(features[b])) != AGP_OK) return st;
-  }
-  const long long lda = factor_ld(n), nblk = (n + NB - 1) / NB, np2 = round_up(n, 2), cp2 = round_up(count, 2);
-  const long long stride_A = lda * n, stride_I = nblk * (36 * MB * MB);
+  long long n = 0;
+  int st = check_batch_problems(count, kernels, features, ldy, y_var, ldv, &n);
+  if (st != AGP_OK) return st;
+  if (information && ldi < n) return AGP_ERR_INVALID_ARGUMENT;
+  const BatchGeometry g = batch_geometry(n, count);
   hipStream_t s = ctx->stream;
-  // one allocation: [A slabs | tile images | information | z | logsum | flags (4 ints each) | y_var (scratch) | features]
-  size_t feat_elems = 0;  // per problem: coordinates, equality ids, scale columns (8-byte units)
-  for (int b = 0; b < count; ++b)
-    feat_elems += (size_t)n * ((size_t)features[b]->dim + (features[b]->eq_id ? 1 : 0) + (size_t)features[b]->n_scale_columns);
-  const size_t head_elems = (size_t)count * ((size_t)stride_A + (size_t)stride_I + 2 * (size_t)np2) + (size_t)cp2 + 2 * (size_t)cp2 +
-                            (y_var ? (size_t)count * (size_t)np2 : 0);
-  const size_t elems = head_elems + feat_elems;
+  WsLayout size;
+  carve_fit_batch(size, g, y_var != nullptr);
+  for (int b = 0; b < count; ++b) carve_features(size, features[b]);
+  const size_t bytes = size.bytes();
   double *base = nullptr;
-  if (ctx->pool_batch && ctx->pool_batch_bytes == sizeof(double) * elems) {
+  if (ctx->pool_batch && ctx->pool_batch_bytes == bytes) {
     base = ctx->pool_batch;
     ctx->pool_batch = nullptr;
     ctx->pool_batch_bytes = 0;
   } else {
     if (ctx->pool_batch) { (void)dev_release(ctx->pool_batch); ctx->pool_batch = nullptr; ctx->pool_batch_bytes = 0; }
-    AGP_HIP_CHECK(ctx, hipMalloc(&base, sizeof(double) * elems));
+    AGP_HIP_CHECK(ctx, hipMalloc(&base, bytes));
   }
-  double *A = base, *invd = A + (size_t)count * (size_t)stride_A, *alpha = invd + (size_t)count * (size_t)stride_I;
-  double *z = alpha + (size_t)count * (size_t)np2, *logsum = z + (size_t)count * (size_t)np2;
-  int *flags = reinterpret_cast<int *>(logsum + cp2);
-  double *yvar_d = y_var ? logsum + 3 * cp2 : nullptr;
+  WsLayout ws(base);
+  const FitBatchRegions r = carve_fit_batch(ws, g, y_var != nullptr);
   std::vector<agp_fit *> fits((size_t)count, nullptr);
   auto fail = [&](int code) {
     (void)hipStreamSynchronize(s);
@@ -1642,74 +1597,52 @@ int agp_fit_create_batch(agp_context *c, int count, const agp_kernel *const *ker
   } while (0)
   const int loc = features[0]->location;
   const hipMemcpyKind kind = loc == AGP_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-  // targets (and their variances): constant strides on both sides - one pitched copy each
-  BATCH_CHECK(hipMemcpy2DAsync(z, sizeof(double) * (size_t)np2, y, sizeof(double) * (size_t)(ldy ? ldy : n), sizeof(double) * (size_t)n,
-                               (size_t)(ldy ? count : 1), kind, s));
-  if (!ldy)
-    for (int b = 1; b < count; ++b)  // (one target vector shared by all problems)
-      BATCH_CHECK(hipMemcpyAsync(z + (size_t)b * (size_t)np2, y, sizeof(double) * (size_t)n, kind, s));
-  if (y_var) {
-    BATCH_CHECK(hipMemcpy2DAsync(yvar_d, sizeof(double) * (size_t)np2, y_var, sizeof(double) * (size_t)(ldv ? ldv : n), sizeof(double) * (size_t)n,
-                                 (size_t)(ldv ? count : 1), kind, s));
-    if (!ldv)
-      for (int b = 1; b < count; ++b)
-        BATCH_CHECK(hipMemcpyAsync(yvar_d + (size_t)b * (size_t)np2, y_var, sizeof(double) * (size_t)n, kind, s));
-  }
+  if ((st = upload_problem_columns(ctx, y, ldy, n, count, loc, r.z, g.np2)) != AGP_OK) return fail(st);
+  if (y_var && (st = upload_problem_columns(ctx, y_var, ldv, n, count, loc, r.yvar, g.np2)) != AGP_OK) return fail(st);
   // train_features = features (gp.hpp:63): a copy per fit, inside the batch's allocation (no allocation per problem).
   // Device-resident inputs: ONE table-driven copy launch for all problems (pub.h: CopyItem) instead of a copy kernel per array
   std::vector<CopyItem> copies;
   long long copy_max = 0;
-  auto stage = [&](double *dst, const void *src, long long words) -> hipError_t {
-    if (loc == AGP_HOST) return hipMemcpyAsync(dst, src, sizeof(double) * (size_t)words, kind, s);
-    copies.push_back(CopyItem{reinterpret_cast<unsigned long long *>(dst), static_cast<const unsigned long long *>(src), words});
+  auto stage = [&](const void *dst, const void *src, long long words) -> hipError_t {
+    if (!dst) return hipSuccess;  // (an array the problem does not have)
+    if (loc == AGP_HOST) return hipMemcpyAsync(const_cast<void *>(dst), src, sizeof(double) * (size_t)words, kind, s);
+    copies.push_back(CopyItem{static_cast<unsigned long long *>(const_cast<void *>(dst)), static_cast<const unsigned long long *>(src), words});
     if (words > copy_max) copy_max = words;
     return hipSuccess;
   };
-  double *fcur = base + head_elems;
   for (int b = 0; b < count; ++b) {
     agp_fit *fit = new (std::nothrow) agp_fit();
     if (!fit) return fail(AGP_ERR_INVALID_ARGUMENT);
     fits[(size_t)b] = fit;
     const agp_features *f = features[b];
-    FeatView v;
-    v.n = n; v.dim = f->dim; v.nsc = f->n_scale_columns; v.meas = 0;
-    v.coords = fcur; v.ids = nullptr; v.scales = nullptr;
-    BATCH_CHECK(stage(fcur, f->coords, n * (long long)f->dim));
-    fcur += (size_t)n * (size_t)f->dim;
-    if (f->eq_id) {
-      v.ids = reinterpret_cast<const long long *>(fcur);
-      BATCH_CHECK(stage(fcur, f->eq_id, n));
-      fcur += n;
-    }
-    if (f->n_scale_columns > 0) {
-      v.scales = fcur;
-      BATCH_CHECK(stage(fcur, f->scales, n * (long long)f->n_scale_columns));
-      fcur += (size_t)n * (size_t)f->n_scale_columns;
-    }
+    const FeatView v = carve_features(ws, f);
+    BATCH_CHECK(stage(v.coords, f->coords, n * (long long)f->dim));
+    BATCH_CHECK(stage(v.ids, f->eq_id, n));
+    BATCH_CHECK(stage(v.scales, f->scales, n * (long long)f->n_scale_columns));
     fit->train.v = v;  // (not owned: DeviceFeatures::release has nothing to free)
   }
-  // device scratch behind the features: the copy table and the Gram table of the batched launches
+  // device scratch of the call: the copy table and the Gram table of the batched launches, the z slots of the fused panels
+  const bool fused_panels = batched_fused_panels(ctx, g, /*allow_lookahead=*/true);
+  const size_t copy_bytes = sizeof(CopyItem) * copies.size(), gram_bytes = gram_batch_table_bytes(count);
+  WsLayout tsize;
+  carve_fit_batch_tables(tsize, g, fused_panels, copy_bytes, gram_bytes);
   void *tables = nullptr;
-  const size_t copy_bytes = (sizeof(CopyItem) * copies.size() + 15) / 16 * 16;
-  const size_t gram_bytes = (gram_batch_table_bytes(count) + 15) / 16 * 16;
-  // (fused panel launches for batches whose workgroups fit on the chip at once: they publish z through a slab of their own)
-  const bool lookahead = (double)count * (double)n * (double)n >= 6e7 && n > 2 * NBO;
-  const bool fused_panels = !lookahead && batched_fused_fits(ctx, n, count);
-  const size_t zpub_bytes = fused_panels ? sizeof(double) * (size_t)count * (size_t)np2 : 0;
-  const size_t table_bytes = copy_bytes + gram_bytes + zpub_bytes;
-  if (dev_malloc(&tables, table_bytes) != hipSuccess) { (void)hipGetLastError(); tables = nullptr; }
+  if (dev_malloc(&tables, tsize.bytes()) != hipSuccess) { (void)hipGetLastError(); tables = nullptr; }
   struct FreeTables { void *p; ~FreeTables() { if (p) (void)dev_free(p); } } free_tables{tables};
-  // (both tables are built in the context's pinned staging area: no synchronisation between the uploads and the launches
-  // that read them - the two mid-call synchronisations of round 5 were ~4 % of a batch of 256 fits of N = 512)
-  char *pinned = tables ? static_cast<char *>(host_stage(ctx, copy_bytes + gram_bytes)) : nullptr;
-  double *zpub = (tables && fused_panels) ? reinterpret_cast<double *>(static_cast<char *>(tables) + copy_bytes + gram_bytes) : nullptr;
+  WsLayout tws(tables);
+  const FitBatchTables t = carve_fit_batch_tables(tws, g, fused_panels, copy_bytes, gram_bytes);  // (all null without `tables`)
+  // (both tables are built in the context's pinned staging area, laid out like the device's: no synchronisation between
+  // the uploads and the launches that read them - the two mid-call synchronisations of round 5 were ~4 % of a batch of
+  // 256 fits of N = 512)
+  const size_t gram_off = (size_t)(static_cast<char *>(t.gram_table) - static_cast<char *>(t.copy_table));
+  char *pinned = tables ? static_cast<char *>(host_stage(ctx, gram_off + gram_bytes)) : nullptr;
   if (!copies.empty()) {
     if (tables) {
       const void *src = copies.data();
-      if (pinned) { std::memcpy(pinned, copies.data(), sizeof(CopyItem) * copies.size()); src = pinned; }
-      BATCH_CHECK(hipMemcpyAsync(tables, src, sizeof(CopyItem) * copies.size(), hipMemcpyHostToDevice, s));
+      if (pinned) { std::memcpy(pinned, copies.data(), copy_bytes); src = pinned; }
+      BATCH_CHECK(hipMemcpyAsync(t.copy_table, src, copy_bytes, hipMemcpyHostToDevice, s));
       if (!pinned) BATCH_CHECK(hipStreamSynchronize(s));  // (pageable source)
-      launch_copy_table(s, static_cast<const CopyItem *>(tables), (long long)copies.size(), copy_max);
+      launch_copy_table(s, static_cast<const CopyItem *>(t.copy_table), (long long)copies.size(), copy_max);
     } else {
       for (const CopyItem &c : copies) BATCH_CHECK(hipMemcpyAsync(c.dst, c.src, sizeof(double) * (size_t)c.words, kind, s));
     }
@@ -1717,59 +1650,30 @@ int agp_fit_create_batch(agp_context *c, int count, const agp_kernel *const *ker
   if (loc == AGP_HOST) BATCH_CHECK(hipStreamSynchronize(s));
   // information = L^-T z of every problem in ONE launch (solve.hip: backsub_coop_kernel, blockIdx.y = problem) for sizes
   // of few 128-row blocks: its output vectors are the hand-over buffers and enter sentinel-filled
-  const bool coop = ctx->tune.backsub_coop && n <= ctx->tune.backsub_coop_max && (n + NB - 1) / NB <= BACKSUB_DIRECT_BLOCKS;
+  const bool coop = ctx->tune.backsub_coop && n <= ctx->tune.backsub_coop_max && g.nblk <= BACKSUB_DIRECT_BLOCKS;
   {
     PrepArgs prep;
-    prep.fill(logsum, 0ull, 3 * cp2);  // log sums and flags
-    if (coop) prep.sentinel(alpha, count * np2);
-    if (zpub) {  // the hand-over buffers of the fused panel launches: every tile image and every z slot of the batch
-      prep.sentinel(invd, count * stride_I);
-      prep.sentinel(zpub, count * np2);
-    }
-    launch_prep(s, prep);
+    prep.fill(r.logsum, 0ull, 3 * g.cp2);  // log sums and flags
+    if (coop) prep.sentinel(r.alpha, count * g.np2);
+    launch_batch_prep(s, prep, g, r.invd, t.zpub);
   }
   {
-    std::vector<FeatView> views((size_t)count);
-    std::vector<const DevProgram *> hprogs((size_t)count);
-    std::vector<double *> outs((size_t)count);
-    std::vector<const double *> diag((size_t)count, nullptr);
-    std::vector<int *> nanf((size_t)count);
-    for (int b = 0; b < count; ++b) {
-      views[(size_t)b] = fits[(size_t)b]->train.v;
-      views[(size_t)b].meas = 1;  // as_measurements(features), gp.hpp:288
-      hprogs[(size_t)b] = &kernels[b]->prog;
-      outs[(size_t)b] = A + (size_t)b * (size_t)stride_A;
-      if (y_var) diag[(size_t)b] = yvar_d + (size_t)b * (size_t)np2;
-      nanf[(size_t)b] = flags + 4 * b;
-    }
-    bool gram_done = false;
-    if (tables && count > 1) {  // all Gram matrices in ONE launch when the trees share a fast path (gram.hip)
-      gram_done = launch_gram_batch(s, count, hprogs.data(), views.data(), outs.data(), lda, y_var ? diag.data() : nullptr, nanf.data(),
-                                    static_cast<char *>(tables) + copy_bytes, pinned ? pinned + copy_bytes : nullptr);
-    }
-    for (int b = 0; b < count && !gram_done; ++b) {
-      const DevProgram *dprog = nullptr;
-      if ((st = device_program(ctx, kernels[b], &dprog)) != AGP_OK) return fail(st);
-      launch_gram(s, dprog, views[(size_t)b], views[(size_t)b], true, true, outs[(size_t)b], lda, diag[(size_t)b], nanf[(size_t)b],
-                  &kernels[b]->prog);
-    }
+    BatchGramTables gram(g, kernels, r.A, r.yvar, g.np2, r.flags, 4);
+    for (int b = 0; b < count; ++b) gram.set_view(b, fits[(size_t)b]->train.v);
+    if ((st = launch_batch_grams(ctx, g, gram, kernels, t.gram_table, pinned ? pinned + gram_off : nullptr)) != AGP_OK) return fail(st);
   }
-  // (two streams once the trailing updates of the batch are long enough to hide the panel chain behind)
-  if (lookahead)
-    factor_lower_batched_lookahead(ctx, A, stride_A, n, lda, invd, stride_I, z, np2, count, flags, logsum, 4);
-  else
-    factor_lower_batched(s, A, stride_A, n, lda, invd, stride_I, z, np2, count, flags, logsum, 4, zpub, np2);
+  factor_batch(ctx, g, /*allow_lookahead=*/true, r.A, r.invd, r.z, r.flags, 4, r.logsum, t.zpub);
   // information = L^-T (L^-1 y), gp.hpp:68
   if (coop) {
-    backward_solve_coop(s, A, n, lda, invd, z, alpha, flags, nullptr, count, stride_A, stride_I, np2, np2, 4);
+    backward_solve_coop(s, r.A, n, g.lda, r.invd, r.z, r.alpha, r.flags, nullptr, count, g.stride_A, g.stride_I, g.np2, g.np2, 4);
   } else {
-    BATCH_CHECK(hipMemcpyAsync(alpha, z, sizeof(double) * (size_t)count * (size_t)np2, hipMemcpyDeviceToDevice, s));
-    backward_solve_vec_batched(s, A, stride_A, n, lda, invd, stride_I, alpha, np2, count);
+    BATCH_CHECK(hipMemcpyAsync(r.alpha, r.z, sizeof(double) * (size_t)count * (size_t)g.np2, hipMemcpyDeviceToDevice, s));
+    backward_solve_vec_batched(s, r.A, g.stride_A, n, g.lda, r.invd, g.stride_I, r.alpha, g.np2, count);
   }
-  std::vector<double> h_log((size_t)cp2);
+  std::vector<double> h_log((size_t)g.cp2);
   std::vector<int> h_flags(4 * (size_t)count);
-  BATCH_CHECK(hipMemcpyAsync(h_log.data(), logsum, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, s));
-  BATCH_CHECK(hipMemcpyAsync(h_flags.data(), flags, sizeof(int) * 4 * (size_t)count, hipMemcpyDeviceToHost, s));
+  BATCH_CHECK(hipMemcpyAsync(h_log.data(), r.logsum, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost, s));
+  BATCH_CHECK(hipMemcpyAsync(h_flags.data(), r.flags, sizeof(int) * 4 * (size_t)count, hipMemcpyDeviceToHost, s));
   BATCH_CHECK(hipStreamSynchronize(s));
   BATCH_CHECK(hipGetLastError());
   for (int b = 0; b < count; ++b)
@@ -1783,12 +1687,12 @@ int agp_fit_create_batch(agp_context *c, int count, const agp_kernel *const *ker
     for (int b = 0; b < count; ++b) {
       const int *fl = &h_flags[4 * (size_t)b];
       if (!fl[0] && !fl[1])
-        BATCH_CHECK(hipMemcpy(information + (size_t)b * (size_t)ldi, alpha + (size_t)b * (size_t)np2, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+        BATCH_CHECK(hipMemcpy(information + (size_t)b * (size_t)ldi, r.alpha + (size_t)b * (size_t)g.np2, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
     }
   agp_fit_slab *slab = new (std::nothrow) agp_fit_slab();
   if (!slab) return fail(AGP_ERR_INVALID_ARGUMENT);
   slab->base = base;
-  slab->bytes = sizeof(double) * elems;
+  slab->bytes = bytes;
   slab->refs = count;
   for (int b = 0; b < count; ++b) {
     agp_fit *fit = fits[(size_t)b];
@@ -1796,12 +1700,12 @@ int agp_fit_create_batch(agp_context *c, int count, const agp_kernel *const *ker
     fit->slab = slab;
     fit->device = ctx->device;
     fit->n = n;
-    fit->lda = lda;
-    fit->A_bytes = sizeof(double) * (size_t)stride_A;
-    fit->A = A + (size_t)b * (size_t)stride_A;
-    fit->invd = invd + (size_t)b * (size_t)stride_I;
-    fit->alpha = alpha + (size_t)b * (size_t)np2;
-    fit->z = z + (size_t)b * (size_t)np2;
+    fit->lda = g.lda;
+    fit->A_bytes = sizeof(double) * (size_t)g.stride_A;
+    fit->A = r.A + (size_t)b * (size_t)g.stride_A;
+    fit->invd = r.invd + (size_t)b * (size_t)g.stride_I;
+    fit->alpha = r.alpha + (size_t)b * (size_t)g.np2;
+    fit->z = r.z + (size_t)b * (size_t)g.np2;
     const int *fl = &h_flags[4 * (size_t)b];
     fit->failed_pivot = fl[1] ? (int64_t)fl[1] - 1 : -1;
     fit->log_det = 2. * h_log[(size_t)b];

@@ -1,6 +1,7 @@
 // api_internal.h — host-side helpers shared by the translation units that implement the C-ABI
 // (api.hip: context / Gram / dense fit / predict; cv_api.hip: leave-one-group-out;
-// sparse_api.hip: sparse GP).  Not part of the public interface.
+// sparse_api.hip: sparse GP).  Not part of the public interface.  What the batched fits share beyond these helpers -
+// argument checks, uploads, Gram tables, factor schedule - is batch_front.h, which builds on this header.
 #pragma once
 #include <atomic>
 #include <string>

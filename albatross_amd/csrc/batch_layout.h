@@ -1,0 +1,105 @@
+// batch_layout.h — the slab geometry of a batch of fits of one size and the workspace layouts of the entries built on
+// it (batch_front.h), each written once: a struct whose members are the regions in order, and a carve function that takes
+// them from a WsLayout in that order (a braced list is evaluated left to right).  Plain C++, like ws_layout.h.
+// cp2, np2, lda and the tile images are even: every region of doubles is a multiple of 16 bytes, so neighbouring regions
+// are contiguous (an entry zero-fills or downloads [logsum | quad | flags] as one range).
+#pragma once
+#include "ws_layout.h"
+
+namespace agp {
+
+// `count` problems of n points: factor slabs of lda x n at stride_A, the tile images of the nblk diagonal blocks at
+// stride_I, per-problem vectors at np2, per-batch scalars in arrays of cp2
+struct BatchGeometry {
+  long long n, count, lda, nblk, np2, cp2, stride_A, stride_I;
+  // block: rows of a diagonal block; image_elems: doubles of one block's tile image (batch_front.h: batch_geometry)
+  BatchGeometry(long long n_, long long count_, long long lda_, long long block, long long image_elems)
+      : n(n_), count(count_), lda(lda_), nblk((n_ + block - 1) / block), np2((n_ + 1) / 2 * 2), cp2((count_ + 1) / 2 * 2),
+        stride_A(lda_ * n_), stride_I(nblk * image_elems) {}
+  size_t slabs() const { return (size_t)count * (size_t)stride_A; }
+  size_t images() const { return (size_t)count * (size_t)stride_I; }
+  size_t vectors() const { return (size_t)count * (size_t)np2; }
+};
+
+// agp_nll and the single-problem gradients, ws_A (count = 1)
+struct FitRegions {
+  double *A, *invd, *z, *yvar;
+};
+inline FitRegions carve_fit(WsLayout &ws, const BatchGeometry &g) {
+  return {ws.take<double>(g.slabs()), ws.take<double>(g.images()), ws.take<double>(g.vectors()), ws.take<double>(g.vectors())};
+}
+
+// the single-problem gradients, ws_aux: R = L^-1, back-substitution scratch, partials [tile][GRAD_GROUP], the gradient,
+// host tangent columns (leading dimension np2), the entry's own vectors
+struct GradientAuxRegions {
+  double *R, *bs_ws, *partial, *grad, *tang, *extra;
+};
+inline GradientAuxRegions carve_gradient_aux(WsLayout &ws, const BatchGeometry &g, size_t bs_elems, size_t part_elems,
+                                             size_t grad_elems, size_t tang_elems, size_t extra_elems) {
+  return {ws.take<double>(g.slabs()),   ws.take<double>(bs_elems),   ws.take<double>(part_elems),
+          ws.take<double>(grad_elems), ws.take<double>(tang_elems), ws.take<double>(extra_elems)};
+}
+
+// agp_nll_batch, ws_A.  yvar: one vector shared by all problems; zpub: the z slots of the fused panel launches
+struct NllBatchRegions {
+  double *A, *invd, *ys, *yvar, *logsum, *quad, *zpub;
+  void *gram_table;
+};
+inline NllBatchRegions carve_nll_batch(WsLayout &ws, const BatchGeometry &g, bool fused_panels, size_t gram_table_bytes) {
+  return {ws.take<double>(g.slabs()),      ws.take<double>(g.images()),     ws.take<double>(g.vectors()),
+          ws.take<double>((size_t)g.np2), ws.take<double>((size_t)g.cp2), ws.take<double>((size_t)g.cp2),
+          fused_panels ? ws.take<double>(g.vectors()) : nullptr, ws.take<char>(gram_table_bytes)};
+}
+
+// agp_fit_create_batch, the slab the fits share (alpha: information; flags: 4 ints per problem; yvar: scratch of the
+// call); the copies of the training features follow on the same WsLayout
+struct FitBatchRegions {
+  double *A, *invd, *alpha, *z, *logsum;
+  int *flags;
+  double *yvar;
+};
+inline FitBatchRegions carve_fit_batch(WsLayout &ws, const BatchGeometry &g, bool has_yvar) {
+  return {ws.take<double>(g.slabs()),      ws.take<double>(g.images()),       ws.take<double>(g.vectors()), ws.take<double>(g.vectors()),
+          ws.take<double>((size_t)g.cp2), ws.take<int>(4 * (size_t)g.cp2), has_yvar ? ws.take<double>(g.vectors()) : nullptr};
+}
+
+// agp_fit_create_batch, the scratch that goes with the call
+struct FitBatchTables {
+  void *copy_table, *gram_table;
+  double *zpub;
+};
+inline FitBatchTables carve_fit_batch_tables(WsLayout &ws, const BatchGeometry &g, bool fused_panels, size_t copy_table_bytes,
+                                             size_t gram_table_bytes) {
+  return {ws.take<char>(copy_table_bytes), ws.take<char>(gram_table_bytes), fused_panels ? ws.take<double>(g.vectors()) : nullptr};
+}
+
+// the batched gradients, ws_A (z: then alpha, in place; flags: 4 ints per problem)
+struct GradientBatchRegions {
+  double *A, *invd, *z, *yvar, *logsum, *quad;
+  int *flags;
+  double *zpub;
+};
+inline GradientBatchRegions carve_gradient_batch(WsLayout &ws, const BatchGeometry &g, bool has_yvar, bool fused_panels) {
+  return {ws.take<double>(g.slabs()),      ws.take<double>(g.images()),     ws.take<double>(g.vectors()),
+          has_yvar ? ws.take<double>(g.vectors()) : nullptr,
+          ws.take<double>((size_t)g.cp2), ws.take<double>((size_t)g.cp2), ws.take<int>(4 * (size_t)g.cp2),
+          fused_panels ? ws.take<double>(g.vectors()) : nullptr};
+}
+
+// the batched gradients, ws_aux: R slabs, host tangent columns (leading dimension np2), partials
+// [problem][group][tile][GRAD_GROUP], gradients [problem][ldgd], the Gram table, the contraction descriptors, the entry's
+// own np2 x count arrays
+struct GradientBatchAuxRegions {
+  double *R, *tang, *partial, *grad;
+  void *gram_table, *desc;
+  double *extra;
+};
+inline GradientBatchAuxRegions carve_gradient_batch_aux(WsLayout &ws, const BatchGeometry &g, size_t tang_elems, size_t part_per,
+                                                        size_t ldgd, size_t gram_table_bytes, size_t desc_bytes,
+                                                        size_t extra_vectors) {
+  return {ws.take<double>(g.slabs()),   ws.take<double>(tang_elems), ws.take<double>((size_t)g.count * part_per),
+          ws.take<double>((size_t)g.count * ldgd), ws.take<char>(gram_table_bytes), ws.take<char>(desc_bytes),
+          ws.take<double>(extra_vectors * g.vectors())};
+}
+
+}  // namespace agp

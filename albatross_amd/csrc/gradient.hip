@@ -25,13 +25,15 @@
 //
 // agp_nll_gradient_batch and agp_loo_nll_gradient_batch run the same steps for `count` problems of one size in lock step:
 // every kernel below takes the problem from blockIdx.y (blockIdx.z where y is a tile index) and per-problem strides, and
-// the single-problem calls are its count = 1 case.
+// the single-problem calls are its count = 1 case.  Their checks, uploads, Gram and factor are the front end the batched
+// fits share (batch_front.h); every workspace here is carved by a layout of batch_layout.h.
 #include <climits>
 #include <cstring>
 #include <limits>
 #include <vector>
 
 #include "api_internal.h"
+#include "batch_front.h"
 #include "contract.h"
 #include "cov_eval.h"
 #include "gemm_tiles.h"
@@ -342,9 +344,8 @@ int stage_tangents(agp_context *ctx, hipStream_t s, const double *tangents, long
 }
 
 // ---- the steps both gradients share ------------------------------------------------------------------------------
-// Everything agp_nll_gradient and agp_loo_nll_gradient do up to and including the fit.  Workspaces:
-//   ws_A:   [A | invd | z | yvar], as agp_nll
-//   ws_aux: [R | back-substitution scratch | partials | gradient | tangent columns | extra_elems]
+// Everything agp_nll_gradient and agp_loo_nll_gradient do up to and including the fit.  Workspaces (batch_layout.h):
+// ws_A as agp_nll (carve_fit), ws_aux by carve_gradient_aux with extra_elems doubles of the entry's own at its end.
 struct GradientCall {
   long long n = 0, lda = 0, tiles = 0, ldt_d = 0;
   double *A = nullptr, *invd = nullptr, *z = nullptr, *yvar_d = nullptr;
@@ -370,29 +371,25 @@ static int gradient_setup(agp_context_impl *ctx, const agp_kernel *k, const agp_
   hipStream_t s = ctx->stream;
 
   g.n = n;
-  const long long lda = g.lda = factor_ld(n);
-  const long long nblk = (n + NB - 1) / NB;
-  const size_t a_bytes = sizeof(double) * (size_t)lda * (size_t)n;
-  const size_t aux = sizeof(double) * ((size_t)nblk * (36 * MB * MB) + 2 * (size_t)round_up(n, 2));
-  if ((st = ensure_ws(ctx, &ctx->ws_A, &ctx->ws_A_bytes, a_bytes + aux)) != AGP_OK) return st;
-  g.A = ctx->ws_A;
-  g.invd = g.A + (size_t)lda * (size_t)n;
-  g.z = g.invd + (size_t)nblk * (36 * MB * MB);
-  g.yvar_d = y_var ? g.z + round_up(n, 2) : nullptr;
+  const BatchGeometry geo = batch_geometry(n, 1);
+  const long long lda = g.lda = geo.lda;
   g.tiles = lower_tiles(n);
-  const size_t r_elems = (size_t)lda * (size_t)n, bs_elems = backsolve_ws_elems(n);
-  const size_t part_elems = (size_t)g.tiles * GRAD_GROUP, grad_elems = (size_t)round_up(AGP_MAX_GRADIENT_SLOTS, 2);
-  const bool tang_copy = ntc > 0 && x->location == AGP_HOST;
-  const size_t tang_elems = tang_copy ? (size_t)round_up(n, 2) * (size_t)ntc : 0;
-  if ((st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes,
-                      sizeof(double) * (r_elems + bs_elems + part_elems + grad_elems + tang_elems + extra_elems))) != AGP_OK)
-    return st;
-  g.R = ctx->ws_aux;
-  g.bs_ws = g.R + r_elems;
-  g.partial = g.bs_ws + bs_elems;
-  g.grad_d = g.partial + part_elems;
-  g.extra = g.grad_d + grad_elems + tang_elems;
-  double *tcur = g.grad_d + grad_elems;
+  const size_t tang_elems = ntc > 0 && x->location == AGP_HOST ? (size_t)geo.np2 * (size_t)ntc : 0;
+  auto carve_aux = [&](WsLayout &w) {
+    return carve_gradient_aux(w, geo, backsolve_ws_elems(n), (size_t)g.tiles * GRAD_GROUP, (size_t)round_up(AGP_MAX_GRADIENT_SLOTS, 2),
+                              tang_elems, extra_elems);
+  };
+  WsLayout size_A, size_aux;
+  carve_fit(size_A, geo);
+  carve_aux(size_aux);
+  if ((st = ensure_ws(ctx, &ctx->ws_A, &ctx->ws_A_bytes, size_A.bytes())) != AGP_OK) return st;
+  if ((st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, size_aux.bytes())) != AGP_OK) return st;
+  WsLayout ws_A(ctx->ws_A), ws_aux(ctx->ws_aux);
+  const FitRegions r = carve_fit(ws_A, geo);
+  const GradientAuxRegions a = carve_aux(ws_aux);
+  g.A = r.A; g.invd = r.invd; g.z = r.z; g.yvar_d = y_var ? r.yvar : nullptr;
+  g.R = a.R; g.bs_ws = a.bs_ws; g.partial = a.partial; g.grad_d = a.grad; g.extra = a.extra;
+  double *tcur = a.tang;
   if ((st = stage_tangents(ctx, s, tangents, ldt, x->location, n, ntc, &tcur, &g.tang_d, &g.ldt_d)) != AGP_OK) return st;
 
   if ((st = to_device(ctx, x, false, &g.dx)) != AGP_OK) return st;
@@ -548,9 +545,7 @@ int agp_loo_nll_gradient(agp_context *c, const agp_kernel *k, const agp_features
 
 // ---- the steps both batched gradients share ----------------------------------------------------------------------
 // Everything agp_nll_gradient_batch and agp_loo_nll_gradient_batch do up to and including C_b = R_b^T R_b, and the
-// download at the end.  Workspaces:
-//   ws_A:   [A slabs | tile images | z / alpha | y_var | logsum | quad | flags (4 ints each) | z slots of the fused panels]
-//   ws_aux: [R slabs | tangent columns | partials | gradient | Gram table | contraction descriptors | extra vectors]
+// download at the end.  Workspaces (batch_layout.h): ws_A by carve_gradient_batch, ws_aux by carve_gradient_batch_aux.
 struct GradientBatch {
   long long n = 0, lda = 0, np2 = 0, cp2 = 0, stride_A = 0, tiles = 0, ldgd = 0;
   int groups = 0, max_slots = 0, dim_max = 1;
@@ -563,9 +558,10 @@ struct GradientBatch {
   double *vector(int k) const { return extra + (size_t)k * (size_t)count * (size_t)np2; }  // extra array k (np2 x count)
 };
 
-// The argument checks of both entries (every problem is checked before anything is written or launched), the uploads,
-// one batched Gram, factor_lower_batched (or its look-ahead form, as agp_fit_create_batch chooses), alpha_b in place and
-// R_b = L_b^-1 into the second slab (stage event 3), then with `rtr` K_b^-1 = R_b^T R_b over L_b (stage event 4).
+// The argument checks of both entries (every problem is checked before anything is written or launched), then the
+// shared front end (batch_front.h) - memory from ws_A and ws_aux, status words per problem, the look-ahead schedule where
+// the predicate asks for it - and after the factor alpha_b in place and R_b = L_b^-1 into the second slab (stage event
+// 3), then with `rtr` K_b^-1 = R_b^T R_b over L_b (stage event 4).
 // vec / ldvec: the entry's n x count host output, checked only.  quad: z_b^T z_b before alpha overwrites z.
 // extra_vectors: further np2 x count arrays behind the descriptors, laid out like z (GradientBatch::vector(k): array k,
 // problem b's vector at + b * np2); u_vector >= 0: the array that holds every problem's u, for the descriptors.
@@ -574,15 +570,13 @@ static int gradient_batch_begin(agp_context_impl *ctx, int count, const agp_kern
                                 int64_t ldv, const int *n_slots, const agp_gradient_slot *const *slots,
                                 const double *const *tangents, int64_t ldt, const double *grad, int64_t ldg, const double *vec,
                                 int64_t ldvec, bool quad, bool rtr, int extra_vectors, int u_vector, GradientBatch &g) {
-  if (count > 65535) return AGP_ERR_INVALID_ARGUMENT;  // gridDim.y of the batched launches
-  const long long n = features[0] ? features[0]->n : 0;
-  if (n <= 0 || (ldy != 0 && ldy < n) || (y_var && ldv != 0 && ldv < n) || (vec && ldvec < n)) return AGP_ERR_INVALID_ARGUMENT;
-  int st = AGP_OK, max_slots = 0, dim_max = 1;
+  long long n = 0;
+  int st = check_batch_problems(count, kernels, features, ldy, y_var, ldv, &n);
+  if (st != AGP_OK) return st;
+  if (vec && ldvec < n) return AGP_ERR_INVALID_ARGUMENT;
+  int max_slots = 0, dim_max = 1;
   std::vector<int> ntc((size_t)count, 0);
   for (int b = 0; b < count; ++b) {
-    if (!kernels[b] || !features[b] || features[b]->n != n || features[b]->location != features[0]->location)
-      return AGP_ERR_INVALID_ARGUMENT;
-    if ((st = validate_features(features[b])) != AGP_OK) return st;
     const int ns = n_slots[b];
     if (ns < 0 || ns > AGP_MAX_GRADIENT_SLOTS || (ns > 0 && (!slots || !slots[b]))) return AGP_ERR_INVALID_ARGUMENT;
     if ((st = check_slots(kernels[b], ns, ns > 0 ? slots[b] : nullptr, &ntc[(size_t)b])) != AGP_OK) return st;
@@ -598,116 +592,73 @@ static int gradient_batch_begin(agp_context_impl *ctx, int count, const agp_kern
     return AGP_ERR_INVALID_ARGUMENT;
   AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
 
-  const long long lda = factor_ld(n), nblk = (n + NB - 1) / NB, np2 = round_up(n, 2), cp2 = round_up(count, 2);
-  const long long stride_A = lda * n, stride_I = nblk * (36 * MB * MB);
+  const BatchGeometry geo = batch_geometry(n, count);
+  const long long lda = geo.lda, np2 = geo.np2, cp2 = geo.cp2, stride_A = geo.stride_A, stride_I = geo.stride_I;
   const long long ldgd = round_up(max_slots > 0 ? max_slots : 1, 2);  // device gradient: [count][ldgd]
   const long long part_per = (long long)groups * tiles * GRAD_GROUP;  // partials per problem
   const int loc = features[0]->location;
-  const bool lookahead = (double)count * (double)n * (double)n >= 6e7 && n > 2 * NBO;  // as agp_fit_create_batch
-  const bool fused_panels = !lookahead && batched_fused_fits(ctx, n, count);
+  const bool fused_panels = batched_fused_panels(ctx, geo, /*allow_lookahead=*/true);
   long long tang_elems = 0;
   if (loc == AGP_HOST)
     for (int b = 0; b < count; ++b) tang_elems += (long long)ntc[(size_t)b] * np2;
-  const size_t gram_bytes = (gram_batch_table_bytes(count) + 15) / 16 * 16;
-  const size_t desc_bytes = (sizeof(ContractDesc) * (size_t)count + 15) / 16 * 16;
-  const size_t a_elems = (size_t)round_up(count * stride_A, 2) + (size_t)count * (size_t)stride_I + (size_t)count * (size_t)np2 +
-                         (y_var ? (size_t)count * (size_t)np2 : 0) + 4 * (size_t)cp2 + (fused_panels ? (size_t)count * (size_t)np2 : 0);
-  const size_t aux_elems = (size_t)round_up(count * stride_A, 2) + (size_t)tang_elems + (size_t)count * (size_t)part_per +
-                           (size_t)count * (size_t)ldgd + (gram_bytes + desc_bytes) / 8 + (size_t)extra_vectors * (size_t)count * (size_t)np2;
-  if ((st = ensure_ws(ctx, &ctx->ws_A, &ctx->ws_A_bytes, sizeof(double) * a_elems)) != AGP_OK) return st;
-  if ((st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, sizeof(double) * aux_elems)) != AGP_OK) return st;
-  double *A = ctx->ws_A, *invd = A + round_up(count * stride_A, 2), *z = invd + (size_t)count * (size_t)stride_I;
-  double *yvar_d = y_var ? z + (size_t)count * (size_t)np2 : nullptr;
-  double *logsum = z + (size_t)count * (size_t)np2 * (y_var ? 2 : 1);
-  int *flags = reinterpret_cast<int *>(logsum + 2 * cp2);
-  double *zpub = fused_panels ? logsum + 4 * cp2 : nullptr;
-  double *R = ctx->ws_aux, *tang_d = R + round_up(count * stride_A, 2), *partial = tang_d + tang_elems;
-  double *grad_d = partial + (size_t)count * (size_t)part_per;
-  char *gram_table = reinterpret_cast<char *>(grad_d + (size_t)count * (size_t)ldgd);
-  ContractDesc *desc_d = reinterpret_cast<ContractDesc *>(gram_table + gram_bytes);
+  const size_t gram_bytes = gram_batch_table_bytes(count), desc_bytes = sizeof(ContractDesc) * (size_t)count;
+  auto carve_aux = [&](WsLayout &w) {
+    return carve_gradient_batch_aux(w, geo, (size_t)tang_elems, (size_t)part_per, (size_t)ldgd, gram_bytes, desc_bytes, (size_t)extra_vectors);
+  };
+  WsLayout size_A, size_aux;
+  carve_gradient_batch(size_A, geo, y_var != nullptr, fused_panels);
+  carve_aux(size_aux);
+  if ((st = ensure_ws(ctx, &ctx->ws_A, &ctx->ws_A_bytes, size_A.bytes())) != AGP_OK) return st;
+  if ((st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, size_aux.bytes())) != AGP_OK) return st;
+  WsLayout ws_A(ctx->ws_A), ws_aux(ctx->ws_aux);
+  const GradientBatchRegions r = carve_gradient_batch(ws_A, geo, y_var != nullptr, fused_panels);
+  const GradientBatchAuxRegions a = carve_aux(ws_aux);
+  double *A = r.A, *invd = r.invd, *z = r.z, *R = a.R;
+  ContractDesc *desc_d = static_cast<ContractDesc *>(a.desc);
   g.count = count; g.n = n; g.lda = lda; g.np2 = np2; g.cp2 = cp2; g.stride_A = stride_A; g.tiles = tiles; g.ldgd = ldgd;
   g.groups = groups; g.max_slots = max_slots; g.dim_max = dim_max;
-  g.A = A; g.z = z; g.yvar_d = yvar_d; g.logsum = logsum; g.quad = logsum + cp2; g.R = R; g.grad_d = grad_d; g.desc_d = desc_d;
-  g.extra = reinterpret_cast<double *>(reinterpret_cast<char *>(desc_d) + desc_bytes);
+  g.A = A; g.z = z; g.yvar_d = r.yvar; g.logsum = r.logsum; g.quad = r.quad; g.R = R; g.grad_d = a.grad; g.desc_d = desc_d;
+  g.extra = a.extra;
   hipStream_t s = ctx->stream;
   const bool prof = ctx->profiling;
-  const hipMemcpyKind kind = loc == AGP_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
 
-  // targets (and variances): one pitched copy each, or the shared vector once per problem
-  AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(z, sizeof(double) * (size_t)np2, y, sizeof(double) * (size_t)(ldy ? ldy : n), sizeof(double) * (size_t)n,
-                                      (size_t)(ldy ? count : 1), kind, s));
-  if (!ldy)
-    for (int b = 1; b < count; ++b) AGP_HIP_CHECK(ctx, hipMemcpyAsync(z + (size_t)b * (size_t)np2, y, sizeof(double) * (size_t)n, kind, s));
-  if (y_var) {
-    AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(yvar_d, sizeof(double) * (size_t)np2, y_var, sizeof(double) * (size_t)(ldv ? ldv : n),
-                                        sizeof(double) * (size_t)n, (size_t)(ldv ? count : 1), kind, s));
-    if (!ldv)
-      for (int b = 1; b < count; ++b)
-        AGP_HIP_CHECK(ctx, hipMemcpyAsync(yvar_d + (size_t)b * (size_t)np2, y_var, sizeof(double) * (size_t)n, kind, s));
-  }
+  if ((st = upload_problem_columns(ctx, y, ldy, n, count, loc, z, np2)) != AGP_OK) return st;
+  if (y_var && (st = upload_problem_columns(ctx, y_var, ldv, n, count, loc, r.yvar, np2)) != AGP_OK) return st;
   // tangent columns: host columns are copied into the workspace (leading dimension np2), device ones are read in place
   std::vector<const double *> tcol((size_t)count, nullptr);
   std::vector<long long> tld((size_t)count, 0);
   {
-    double *tcur = tang_d;
+    double *tcur = a.tang;
     for (int b = 0; b < count; ++b) {
       if (ntc[(size_t)b] == 0) continue;
       if ((st = stage_tangents(ctx, s, tangents[b], ldt, loc, n, ntc[(size_t)b], &tcur, &tcol[(size_t)b], &tld[(size_t)b])) != AGP_OK) return st;
     }
   }
-  // features: problems usually share one feature array (parameter vectors of one model): upload it once
-  std::vector<DeviceFeatures> dxs((size_t)count);
-  std::vector<FeatView> views((size_t)count);
-  std::vector<const DevProgram *> hprogs((size_t)count);
-  std::vector<double *> outs((size_t)count);
-  std::vector<const double *> diag((size_t)count, nullptr);
-  std::vector<int *> nanf((size_t)count);
-  {
-    const agp_features *last = nullptr;
-    int last_b = -1;
-    for (int b = 0; b < count; ++b) {
-      const bool same = last && features[b]->coords == last->coords && features[b]->scales == last->scales &&
-                        features[b]->eq_id == last->eq_id && features[b]->dim == last->dim &&
-                        features[b]->n_scale_columns == last->n_scale_columns;
-      if (!same) {
-        if ((st = to_device(ctx, features[b], false, &dxs[(size_t)b])) != AGP_OK) return st;
-        last = features[b];
-        last_b = b;
-      }
-      views[(size_t)b] = dxs[(size_t)(same ? last_b : b)].v;
-      views[(size_t)b].meas = 1;  // as_measurements(features), gp.hpp:288
-      hprogs[(size_t)b] = &kernels[b]->prog;
-      outs[(size_t)b] = A + (size_t)b * (size_t)stride_A;
-      if (y_var) diag[(size_t)b] = yvar_d + (size_t)b * (size_t)np2;
-      nanf[(size_t)b] = flags + 4 * b;
-    }
-  }
+  BatchGramTables gram(geo, kernels, A, r.yvar, np2, r.flags, 4);
+  if ((st = gram.upload_features(ctx, features)) != AGP_OK) return st;
   if (loc == AGP_HOST) AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));  // (pageable sources)
   {  // log sums, quadratic terms and flags zeroed; the hand-over buffers of the fused panel launches sentinel-filled
     PrepArgs prep;
-    prep.fill(logsum, 0ull, 4 * cp2);
-    if (zpub) {
-      prep.sentinel(invd, count * stride_I);
-      prep.sentinel(zpub, count * np2);
-    }
-    launch_prep(s, prep);
+    prep.fill(r.logsum, 0ull, 4 * cp2);
+    launch_batch_prep(s, prep, geo, invd, r.zpub);
   }
-  // the contraction's descriptors, built in the pinned staging area behind the Gram table's
-  char *pinned = static_cast<char *>(host_stage(ctx, gram_bytes + desc_bytes));
+  // the contraction's descriptors, built in the pinned staging area behind the Gram table's, as they lie on the device
+  const size_t desc_off = (size_t)(static_cast<char *>(a.desc) - static_cast<char *>(a.gram_table));
+  char *pinned = static_cast<char *>(host_stage(ctx, desc_off + desc_bytes));
   std::vector<ContractDesc> desc_pageable;
   ContractDesc *desc_h = nullptr;
-  if (pinned) desc_h = reinterpret_cast<ContractDesc *>(pinned + gram_bytes);
+  if (pinned) desc_h = reinterpret_cast<ContractDesc *>(pinned + desc_off);
   else { desc_pageable.resize((size_t)count); desc_h = desc_pageable.data(); }
   for (int b = 0; b < count; ++b) {
     ContractDesc &d = desc_h[b];
     std::memset(static_cast<void *>(&d), 0, sizeof(ContractDesc));
     d.prog = kernels[b]->prog;
-    d.X = views[(size_t)b];
+    d.X = gram.views[(size_t)b];
     d.C = A + (size_t)b * (size_t)stride_A;
     d.ldc = lda;
     d.alpha = z + (size_t)b * (size_t)np2;
     d.u = u_vector >= 0 ? g.vector(u_vector) + (size_t)b * (size_t)np2 : nullptr;
-    d.partial = partial + (size_t)b * (size_t)part_per;
+    d.partial = a.partial + (size_t)b * (size_t)part_per;
     d.n_slots = n_slots[b];
     for (int grp = 0; grp < GRAD_GROUPS_MAX; ++grp) {
       bool scaling[GRAD_GROUP];
@@ -720,21 +671,9 @@ static int gradient_batch_begin(agp_context_impl *ctx, int count, const agp_kern
   if (!pinned) AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));  // (pageable source)
 
   if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[0], s));
-  bool gram_done = false;
-  if (count > 1)  // all Gram matrices in ONE launch when the trees share a fast path (gram.hip)
-    gram_done = launch_gram_batch(s, count, hprogs.data(), views.data(), outs.data(), lda, y_var ? diag.data() : nullptr, nanf.data(),
-                                  gram_table, pinned);
-  for (int b = 0; b < count && !gram_done; ++b) {
-    const DevProgram *dprog = nullptr;
-    if ((st = device_program(ctx, kernels[b], &dprog)) != AGP_OK) return st;
-    launch_gram(s, dprog, views[(size_t)b], views[(size_t)b], true, true, outs[(size_t)b], lda, diag[(size_t)b], nanf[(size_t)b],
-                hprogs[(size_t)b]);
-  }
+  if ((st = launch_batch_grams(ctx, geo, gram, kernels, a.gram_table, pinned)) != AGP_OK) return st;
   if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[1], s));
-  if (lookahead)
-    factor_lower_batched_lookahead(ctx, A, stride_A, n, lda, invd, stride_I, z, np2, count, flags, logsum, 4);
-  else
-    factor_lower_batched(s, A, stride_A, n, lda, invd, stride_I, z, np2, count, flags, logsum, 4, zpub, np2);
+  factor_batch(ctx, geo, /*allow_lookahead=*/true, A, invd, z, r.flags, 4, r.logsum, r.zpub);
   if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[2], s));
   // y^T K^-1 y = z^T z, alpha = L^-T z in place, R = L^-1 (triangular right-hand side) into the second slab.  A failed
   // problem runs on through here and through the entry's own steps on whatever its factor holds: every launch has fixed
@@ -842,7 +781,7 @@ int agp_loo_nll_gradient_batch(agp_context *c, int count, const agp_kernel *cons
                                const agp_gradient_slot *const *slots, const double *const *tangents, int64_t ldt,
                                double *loo_nll, double *grad_loo_nll, int64_t ldg, double *mean_weights, int64_t ldw,
                                int *status) {
-  if (!c || count <= 0 || count > 65535 || !kernels || !features || !y || !n_slots || !loo_nll || !status)
+  if (!c || count <= 0 || count > BATCH_MAX_PROBLEMS || !kernels || !features || !y || !n_slots || !loo_nll || !status)
     return AGP_ERR_INVALID_ARGUMENT;
   agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
   bool need_c = mean_weights != nullptr;  // u = C a needs C = R^T R; the values alone need only diag(C)

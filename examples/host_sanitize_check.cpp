@@ -1,20 +1,27 @@
 // host_sanitize_check.cpp — the host-side C++ of the project under AddressSanitizer + UndefinedBehaviorSanitizer, on
-// a machine WITHOUT a GPU (examples/Makefile: `make asan`).  Two parts:
+// a machine WITHOUT a GPU (examples/Makefile: `make asan`).  Three parts:
 //
 //  1. the sharded-fit schedule (albatross_amd/csrc/shard_sched.hip is plain C++: compiled INTO this binary with the
 //     sanitizers on) driven through agp_debug_shard_factor_custom (csrc/shard_custom.hip) with naive block operations, one rank and - through
 //     in-process "collectives" - the forced multi-rank path; checked against a naive dense solve;
 //  2. the header-only host layer (include/albatross_amd/albatross.hpp): covariance-function programs, parameter
 //     handling, feature flattening (Measurement<>, scale columns), grouping - everything that runs before the
-//     first device call.
+//     first device call;
+//  3. the workspace layouts of the batched fits (albatross_amd/csrc/ws_layout.h, batch_layout.h: plain C++) over a
+//     malloc'd base: every region aligned, inside the allocation and disjoint from the others, the sizing pass equal to
+//     the real one, the size within the alignment padding of the plain sums, first and last word of every region written.
 //
 // Prints "host_sanitize_check ok" and exits 0; any sanitizer report aborts with a non-zero status.
 #include <cmath>
 #include <cstdio>
+#include <cstdint>
 #include <cstdlib>
+#include <functional>
+#include <utility>
 #include <vector>
 
 #include "albatross_amd/albatross.hpp"
+#include "batch_layout.h"    // csrc/: WsLayout, BatchGeometry, the carve functions
 #include "shard_internal.h"  // agp_shard_ops_callbacks (csrc/, test-only)
 
 extern "C" {
@@ -192,12 +199,111 @@ void host_layer_under_sanitizers() {
   RegressionDataset<double> ds(xs, MarginalDistribution(Vector{1., 2., 3., 4.}, Vector{0.1, 0.1, 0.1, 0.1}));
   require(ds.size() == 4, "dataset");
 }
+
+// ---- part 3: the workspace layouts ---------------------------------------------------------------------------------
+struct Region {
+  void *p;
+  size_t bytes;
+};
+
+// `carve` run over a null base and over a malloc'd one; want_elems: the plain sum of 8-byte elements the layout replaces
+void check_layout(const char *what, size_t want_elems, const std::function<std::vector<Region>(agp::WsLayout &)> &carve) {
+  agp::WsLayout size;
+  for (const Region &r : carve(size)) require(r.p == nullptr, what);
+  const size_t bytes = size.bytes();
+  char *base = static_cast<char *>(std::malloc(bytes ? bytes : 1));  // (malloc aligns to 16 bytes)
+  require(base != nullptr && reinterpret_cast<std::uintptr_t>(base) % 16 == 0, "malloc");
+  agp::WsLayout ws(base);
+  const std::vector<Region> regions = carve(ws);
+  require(ws.bytes() == bytes, what);
+  require(bytes >= 8 * want_elems && bytes <= 8 * want_elems + 16 * regions.size(), what);
+  for (size_t i = 0; i < regions.size(); ++i) {
+    const Region &r = regions[i];
+    if (!r.p) continue;  // a region this configuration does not have
+    char *p = static_cast<char *>(r.p);
+    require(reinterpret_cast<std::uintptr_t>(p) % 16 == 0, what);
+    require(p >= base && p + r.bytes <= base + bytes, what);
+    for (size_t j = 0; j < i; ++j) {
+      const char *q = static_cast<const char *>(regions[j].p);
+      require(!q || p + r.bytes <= q || q + regions[j].bytes <= p, what);
+    }
+    if (r.bytes >= 4) {  // first and last word (the status words are ints)
+      *reinterpret_cast<int *>(p) = 1;
+      *reinterpret_cast<int *>(p + r.bytes - 4) = 2;
+    }
+  }
+  std::free(base);
+}
+
+void layouts_under_sanitizers() {
+  const long long NB = 128, IMG = 36 * 16 * 16;  // csrc/common.h: NB; the tile image of one diagonal block, 36 MB x MB tiles
+  const long long shapes[][2] = {{1, 1}, {100, 1}, {129, 3}, {520, 8}, {1100, 50}};
+  for (const auto &shape : shapes)
+    for (int has_var = 0; has_var < 2; ++has_var)
+      for (int fused = 0; fused < 2; ++fused) {
+        const long long n = shape[0], count = shape[1];
+        long long lda = (n + 7) / 8 * 8;  // csrc/api.hip: factor_ld
+        if (lda % 256 == 0) lda += 8;
+        const agp::BatchGeometry g(n, count, lda, NB, IMG);
+        const size_t nblk = (size_t)((n + NB - 1) / NB), np2 = (size_t)((n + 1) / 2 * 2), cp2 = (size_t)((count + 1) / 2 * 2), B = (size_t)count;
+        const size_t sA = (size_t)(lda * n), sI = nblk * (size_t)IMG;
+        require((size_t)g.nblk == nblk && (size_t)g.np2 == np2 && (size_t)g.cp2 == cp2 && (size_t)g.stride_A == sA && (size_t)g.stride_I == sI,
+                "BatchGeometry");
+        const size_t D = sizeof(double);
+        const size_t gram_bytes = 184 * B + 8, desc_bytes = 1000 * B, copy_bytes = 24 * 3 * B;  // tables: any sizes, 16-byte multiples or not
+        const size_t up8 = 7;  // (bytes + up8) / 8: a table's bytes as 8-byte elements
+        // agp_nll_batch
+        check_layout("carve_nll_batch", B * (sA + sI + np2) + np2 + 2 * cp2 + (fused ? B * np2 : 0) + (gram_bytes + up8) / 8, [&](agp::WsLayout &w) {
+          const agp::NllBatchRegions r = agp::carve_nll_batch(w, g, fused, gram_bytes);
+          return std::vector<Region>{{r.A, D * B * sA}, {r.invd, D * B * sI}, {r.ys, D * B * np2}, {r.yvar, D * np2}, {r.logsum, D * cp2},
+                                     {r.quad, D * cp2}, {r.zpub, D * B * np2}, {r.gram_table, gram_bytes}};
+        });
+        // agp_fit_create_batch: the slab, then the scratch of the call
+        check_layout("carve_fit_batch", B * (sA + sI + 2 * np2) + cp2 + 2 * cp2 + (has_var ? B * np2 : 0), [&](agp::WsLayout &w) {
+          const agp::FitBatchRegions r = agp::carve_fit_batch(w, g, has_var);
+          return std::vector<Region>{{r.A, D * B * sA}, {r.invd, D * B * sI}, {r.alpha, D * B * np2}, {r.z, D * B * np2}, {r.logsum, D * cp2},
+                                     {r.flags, sizeof(int) * 4 * cp2}, {r.yvar, D * B * np2}};
+        });
+        check_layout("carve_fit_batch_tables", (copy_bytes + 15) / 16 * 2 + (gram_bytes + 15) / 16 * 2 + (fused ? B * np2 : 0), [&](agp::WsLayout &w) {
+          const agp::FitBatchTables r = agp::carve_fit_batch_tables(w, g, fused, copy_bytes, gram_bytes);
+          return std::vector<Region>{{r.copy_table, copy_bytes}, {r.gram_table, gram_bytes}, {r.zpub, D * B * np2}};
+        });
+        // the batched gradients: ws_A, ws_aux
+        check_layout("carve_gradient_batch", (B * sA + 1) / 2 * 2 + B * sI + B * np2 + (has_var ? B * np2 : 0) + 4 * cp2 + (fused ? B * np2 : 0),
+                     [&](agp::WsLayout &w) {
+                       const agp::GradientBatchRegions r = agp::carve_gradient_batch(w, g, has_var, fused);
+                       return std::vector<Region>{{r.A, D * B * sA}, {r.invd, D * B * sI}, {r.z, D * B * np2}, {r.yvar, D * B * np2},
+                                                  {r.logsum, D * cp2}, {r.quad, D * cp2}, {r.flags, sizeof(int) * 4 * cp2}, {r.zpub, D * B * np2}};
+                     });
+        const size_t tang = has_var ? 2 * B * np2 : 0, part_per = 3 * 10 * 4, ldgd = 6, extra = fused ? 5 : 0;
+        check_layout("carve_gradient_batch_aux",
+                     (B * sA + 1) / 2 * 2 + tang + B * part_per + B * ldgd + ((gram_bytes + 15) / 16 * 16 + (desc_bytes + 15) / 16 * 16) / 8 + extra * B * np2,
+                     [&](agp::WsLayout &w) {
+                       const agp::GradientBatchAuxRegions r = agp::carve_gradient_batch_aux(w, g, tang, part_per, ldgd, gram_bytes, desc_bytes, extra);
+                       return std::vector<Region>{{r.R, D * B * sA}, {r.tang, D * tang}, {r.partial, D * B * part_per}, {r.grad, D * B * ldgd},
+                                                  {r.gram_table, gram_bytes}, {r.desc, desc_bytes}, {r.extra, D * extra * B * np2}};
+                     });
+        if (count == 1) {  // the single-problem entries: agp_nll's ws_A, the gradients' ws_aux
+          check_layout("carve_fit", sA + sI + 2 * np2, [&](agp::WsLayout &w) {
+            const agp::FitRegions r = agp::carve_fit(w, g);
+            return std::vector<Region>{{r.A, D * sA}, {r.invd, D * sI}, {r.z, D * np2}, {r.yvar, D * np2}};
+          });
+          const size_t bs = 2 * np2 + 3, part = 10 * 4, grad = 16, xtra = fused ? 5 * np2 + 7 : 0;
+          check_layout("carve_gradient_aux", sA + bs + part + grad + tang + xtra, [&](agp::WsLayout &w) {
+            const agp::GradientAuxRegions r = agp::carve_gradient_aux(w, g, bs, part, grad, tang, xtra);
+            return std::vector<Region>{{r.R, D * sA}, {r.bs_ws, D * bs}, {r.partial, D * part}, {r.grad, D * grad}, {r.tang, D * tang},
+                                       {r.extra, D * xtra}};
+          });
+        }
+      }
+}
 }  // namespace
 
 int main() {
   schedule_under_sanitizers(false);
   schedule_under_sanitizers(true);
   host_layer_under_sanitizers();
+  layouts_under_sanitizers();
   std::printf("host_sanitize_check ok\n");
   return 0;
 }

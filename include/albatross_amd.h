@@ -390,7 +390,9 @@ AGP_API int agp_loo_nll_gradient_batch(agp_context *ctx, int count,
  *   y            n x count column-major with leading dimension ldy at that location (mean function removed
  *                per parameter vector); ldy = 0: one target vector shared by all
  *   out[b]       the negative log likelihood (host); NaN where the covariance is not positive definite or
- *                has NaN (the reference turns a NaN metric into +inf, tune.hpp:163-165) */
+ *                has NaN (the reference turns a NaN metric into +inf, tune.hpp:163-165)
+ * count is at most 65535 (the batch is one grid dimension of every launch): a larger one, like any other malformed
+ * argument, returns AGP_ERR_INVALID_ARGUMENT and writes nothing. */
 AGP_API int agp_nll_batch(agp_context *ctx, int count, const agp_kernel *const *kernels,
                   const agp_features *const *features, const double *y, int64_t ldy, const double *y_var,
                   double *out);
@@ -410,7 +412,9 @@ AGP_API int agp_nll_batch(agp_context *ctx, int count, const agp_kernel *const *
  *                             AGP_OK no handle has been published (every out[b] is NULL) and nothing is left to destroy
  * y and y_var live where features[0] lives (host or device); `information` and `log_det` are HOST arrays whatever the
  * location, and a failed problem leaves its column of `information` untouched.  No pivoted fall-back is applied to a
- * problem that is not positive definite (agp_fit_create's callers go on to agp_ldlt_*; a batch reports and moves on). */
+ * problem that is not positive definite (agp_fit_create's callers go on to agp_ldlt_*; a batch reports and moves on).
+ * count is at most 65535 (the batch is one grid dimension of every launch): a larger one returns
+ * AGP_ERR_INVALID_ARGUMENT and writes nothing, out and status included. */
 AGP_API int agp_fit_create_batch(agp_context *ctx, int count, const agp_kernel *const *kernels, const agp_features *const *features,
                                  const double *y, int64_t ldy, const double *y_var, int64_t ldv, agp_fit **out, double *information,
                                  int64_t ldi, double *log_det, int *status);
