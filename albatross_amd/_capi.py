@@ -99,6 +99,8 @@ EXPORTS = [
     ("agp_nll", C.c_int, [_P, _P, C.POINTER(Features), _P, _P, _D]),
     ("agp_nll_gradient", C.c_int, [_P, _P, C.POINTER(Features), _P, _P, C.c_int, _P, _P, C.c_int64, _D, _P, _P]),
     ("agp_loo_nll_gradient", C.c_int, [_P, _P, C.POINTER(Features), _P, _P, C.c_int, _P, _P, C.c_int64, _D, _P, _P]),
+    ("agp_logo_nll_gradient", C.c_int, [_P, _P, C.POINTER(Features), _P, _P, C.c_int64, _P, _P, C.c_int, _P, _P, C.c_int64, _D, _P,
+                                        _P]),
     ("agp_nll_gradient_batch", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P,
                                          C.c_int64, _P, C.c_int64, _P]),
     ("agp_loo_nll_gradient_batch", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P,

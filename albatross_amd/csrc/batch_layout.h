@@ -40,6 +40,25 @@ inline GradientAuxRegions carve_gradient_aux(WsLayout &ws, const BatchGeometry &
           ws.take<double>(grad_elems), ws.take<double>(tang_elems), ws.take<double>(extra_elems)};
 }
 
+// agp_logo_nll_gradient, the entry's own region at the end of ws_aux (GradientAuxRegions::extra).  S: the third
+// lda x n slab (C B C; gradient calls only).  X0 / X1 / X2: the padded block slabs of the chunk of groups in flight
+// (A_g then V_g | L_A^-1 then T_g | Sigma_g then B_g), img their tile images, d / z / a_pad its padded vectors, logs_A /
+// logs_V its log sums; term: one NLL term per non-empty group; a, u: n-vectors; meta: the padded index tables and
+// the group sizes of every chunk.
+struct LogoRegions {
+  double *S, *X0, *X1, *X2, *img, *d, *z, *a_pad, *logs_A, *logs_V, *term, *a, *u, *symv;
+  long long *meta;
+};
+inline LogoRegions carve_logo(WsLayout &ws, const BatchGeometry &g, bool gradient, size_t block_elems, size_t img_elems,
+                              size_t vec_elems, size_t count_elems, size_t term_elems, size_t symv_elems, size_t meta_elems) {
+  return {gradient ? ws.take<double>(g.slabs()) : nullptr,
+          ws.take<double>(block_elems), ws.take<double>(block_elems), ws.take<double>(block_elems),
+          ws.take<double>(img_elems),   ws.take<double>(vec_elems),   ws.take<double>(vec_elems),
+          ws.take<double>(vec_elems),   ws.take<double>(count_elems), ws.take<double>(count_elems),
+          ws.take<double>(term_elems),  ws.take<double>((size_t)g.np2), ws.take<double>((size_t)g.np2),
+          ws.take<double>(symv_elems),  ws.take<long long>(meta_elems)};
+}
+
 // agp_nll_batch, ws_A.  yvar: one vector shared by all problems; zpub: the z slots of the fused panel launches
 struct NllBatchRegions {
   double *A, *invd, *ys, *yvar, *logsum, *quad, *zpub;

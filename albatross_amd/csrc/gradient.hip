@@ -23,13 +23,28 @@
 // launch_symv_lower, G = diag(b)^1/2 sym(C) over R (loo_form_g_kernel), S = G^T G = C diag(b) C over C (gtg_lower_kernel:
 // N^3 flop, the only O(N^3) work beyond agp_nll_gradient) and the contraction of W = S - sym(u alpha^T).
 //
+// agp_logo_nll_gradient, the leave-one-GROUP-out likelihood metric (LeaveOneGroupOutLikelihood, Joint predict type,
+// evaluation/model_metrics.hpp:74-93) and its gradient: per group with index set I, A = C[I, I], Sigma = A^-1,
+// d = Sigma alpha_I, V = Sigma + diag(s_I), NLL_g = 1/2 (log |V| + d^T V^-1 d + |I| log 2 pi), and with a_I = Sigma V^-1 d
+//
+//   W = C B C - 1/2 (u alpha^T + alpha u^T),   B = blockdiag(B_g),   u = C a,
+//   B_g = 1/2 Sigma V^-1 Sigma - 1/2 a_I a_I^T + 1/2 (a_I d^T + d a_I^T).
+//
+// B_g is indefinite in general, so there is no G with G^T G = C B C: H = sym(C) B (logo_h_kernel), then S = H C^T
+// (hct_lower_kernel, the N^3 product again, into a third slab).  The front end and the contraction are those of
+// agp_loo_nll_gradient; the group blocks go through the batched LL^T / solve / product launches that
+// agp_held_out_predictions uses (cv_api.hip), the groups sorted by size and cut into chunks of comparable size that
+// advance in lock step (logo_plan, logo_chunk), with the small kernels below around them.
+//
 // agp_nll_gradient_batch and agp_loo_nll_gradient_batch run the same steps for `count` problems of one size in lock step:
 // every kernel below takes the problem from blockIdx.y (blockIdx.z where y is a tile index) and per-problem strides, and
 // the single-problem calls are its count = 1 case.  Their checks, uploads, Gram and factor are the front end the batched
 // fits share (batch_front.h); every workspace here is carved by a layout of batch_layout.h.
+#include <algorithm>
 #include <climits>
 #include <cstring>
 #include <limits>
+#include <utility>
 #include <vector>
 
 #include "api_internal.h"
@@ -293,6 +308,193 @@ void launch_gtg_lower(hipStream_t s, const double *G, long long ldg, long long n
   launch_gtg_lower_batched(s, G, ldg, 0, n, S, lds_, 0, 1);
 }
 
+// ---- leave-one-group-out: the kernels around the batched factor / solve / product chain ---------------------------
+// A chunk of `count` groups padded to one size m: group g of the chunk owns idx[g * m .. (g + 1) * m) (point indices,
+// -1 = padding) and an m x m slab (ld ldb, stride) of each of X0 / X1 / X2; sizes[g] is its real size.  Padded rows and
+// columns of every slab are those of [X 0; 0 I], so they pass through the factorisations, inverses and products as
+// identity blocks: log 1 = 0 in the log sums, zeros in d, z and a.  blockIdx.y (z where y is a tile index) = group;
+// blockIdx.z of mirror_lower_kernel = problem.
+
+// C(j, i) = C(i, j) for i > j, in place: rtr_lower_kernel writes the lower tiles only, the group blocks and the
+// product sym(C) B sym(C) read both.  One 32 x 32 lower tile per workgroup through LDS, reads and writes coalesced.
+__global__ __launch_bounds__(256) void mirror_lower_kernel(double *__restrict__ C, long long ldc, long long n, long long batch_C) {
+  __shared__ double tile[GF_T][GF_T + 1];
+  const long long bi = blockIdx.x, bj = blockIdx.y;
+  if (bi < bj) return;  // (the whole workgroup)
+  C += (long long)blockIdx.z * batch_C;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // 32 x 8
+  for (int c = ty; c < GF_T; c += 8) {  // tile[c][tx] = C(bi * 32 + tx, bj * 32 + c)
+    const long long row = bi * GF_T + tx, col = bj * GF_T + c;
+    tile[c][tx] = (row < n && col < n && row >= col) ? C[row + col * ldc] : 0.;
+  }
+  __syncthreads();
+  for (int c = ty; c < GF_T; c += 8) {  // C(bj * 32 + tx, bi * 32 + c) = C(bi * 32 + c, bj * 32 + tx)
+    const long long row = bj * GF_T + tx, col = bi * GF_T + c;
+    if (row < n && col < n && row < col) C[row + col * ldc] = tile[tx][c];
+  }
+}
+
+// X0_g = [C[I_g, I_g] 0; 0 I] from the full symmetric C: column blockIdx.x of group blockIdx.y
+__global__ __launch_bounds__(256) void logo_gather_blocks_kernel(const double *__restrict__ C, long long ldc,
+                                                                 const long long *__restrict__ idx, long long m,
+                                                                 double *__restrict__ X0, long long ldb, long long stride) {
+  const long long c = blockIdx.x, g = blockIdx.y;
+  const long long *ig = idx + g * m;
+  const long long ic = ig[c];
+  double *out = X0 + g * stride + c * ldb;
+  for (long long r = threadIdx.x; r < m; r += 256) {
+    const long long ir = ig[r];
+    out[r] = (ic >= 0 && ir >= 0) ? C[ir + ic * ldc] : (r == c ? 1. : 0.);
+  }
+}
+
+// value only: X0_g holds -G_g^T G_g of the gathered columns of R (padding columns of G are zero): negate it and put
+// the identity into the padding
+__global__ __launch_bounds__(256) void logo_fix_blocks_kernel(const long long *__restrict__ idx, long long m,
+                                                              double *__restrict__ X0, long long ldb, long long stride) {
+  const long long c = blockIdx.x, g = blockIdx.y;
+  const long long *ig = idx + g * m;
+  const bool cv = ig[c] >= 0;
+  double *x = X0 + g * stride + c * ldb;
+  for (long long r = threadIdx.x; r < m; r += 256) x[r] = (cv && ig[r] >= 0) ? -x[r] : (r == c ? 1. : 0.);
+}
+
+// fixed-order sum of one value per thread over a workgroup of 256 (every thread receives it)
+__device__ __forceinline__ double logo_block_sum(double acc, double *red) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// X2_g holds -Sigma_g (Sigma_g = A_g^-1 = Q^T Q, Q = L_A^-1).  Column c of group g: V_g = Sigma_g + diag(s_I) into X0,
+// T_g = Sigma_g into X1 (nullptr: value only), d_c = (Sigma_g alpha_I)_c into d and z.
+__global__ __launch_bounds__(256) void logo_sigma_kernel(const double *__restrict__ X2, const long long *__restrict__ idx,
+                                                         long long m, long long ldb, long long stride,
+                                                         const double *__restrict__ alpha, const double *__restrict__ yvar,
+                                                         double *__restrict__ X0, double *__restrict__ X1,
+                                                         double *__restrict__ d, double *__restrict__ z) {
+  __shared__ double red[4];
+  const long long c = blockIdx.x, g = blockIdx.y;
+  const long long *ig = idx + g * m;
+  const long long off = g * stride + c * ldb, ic = ig[c];
+  const double sc = (yvar && ic >= 0) ? yvar[ic] : 0.;
+  double acc = 0.;
+  for (long long r = threadIdx.x; r < m; r += 256) {
+    const double sg = -X2[off + r];
+    const long long ir = ig[r];
+    acc += sg * (ir >= 0 ? alpha[ir] : 0.);
+    X0[off + r] = r == c ? sg + sc : sg;
+    if (X1) X1[off + r] = sg;
+  }
+  const double dc = logo_block_sum(acc, red);
+  if (threadIdx.x == 0) d[g * m + c] = z[g * m + c] = dc;
+}
+
+// term[g] = log |V_g| + d_g^T V_g^-1 d_g + |I_g| log 2 pi = 2 logs_V[g] + z_g^T z_g + ..., z_g = L_V^-1 d_g
+__global__ __launch_bounds__(256) void logo_term_kernel(const double *__restrict__ z, long long m,
+                                                        const double *__restrict__ logs_V, const long long *__restrict__ sizes,
+                                                        double *__restrict__ term) {
+  __shared__ double red[4];
+  const long long g = blockIdx.x;
+  double acc = 0.;
+  for (long long r = threadIdx.x; r < m; r += 256) acc += z[g * m + r] * z[g * m + r];
+  const double zz = logo_block_sum(acc, red);
+  if (threadIdx.x == 0) term[g] = 2. * logs_V[g] + zz + (double)sizes[g] * log(2. * M_PI);
+}
+
+// X2_g holds -T_g^T T_g = -Sigma_g V_g^-1 Sigma_g.  Column c of group g:
+//   B_g = 1/2 Sigma V^-1 Sigma - 1/2 a a^T + 1/2 (a d^T + d a^T)   (symmetric, in general INDEFINITE: nothing may take its root)
+// with zero rows and columns in the padding, and a[I_g[c]] = a_pad[c] (no scatter from the padding).
+__global__ __launch_bounds__(256) void logo_assemble_kernel(const long long *__restrict__ idx, long long m, long long ldb,
+                                                            long long stride, const double *__restrict__ a_pad,
+                                                            const double *__restrict__ d, double *__restrict__ X2,
+                                                            double *__restrict__ a) {
+  const long long c = blockIdx.x, g = blockIdx.y;
+  const long long *ig = idx + g * m;
+  const long long ic = ig[c];
+  const double ac = a_pad[g * m + c], dc = d[g * m + c];
+  double *x = X2 + g * stride + c * ldb;
+  for (long long r = threadIdx.x; r < m; r += 256) {
+    const double ar = a_pad[g * m + r], dr = d[g * m + r];
+    x[r] = (ic >= 0 && ig[r] >= 0) ? -0.5 * x[r] - 0.5 * ar * ac + 0.5 * (ar * dc + dr * ac) : 0.;
+  }
+  if (threadIdx.x == 0 && ic >= 0) a[ic] = ac;
+}
+
+// H = sym(C) B (n x n, ldh): column I_g[r] of H is sum_c B_g(c, r) C[:, I_g[c]]; the columns of points in no group
+// stay zero (the caller zero-fills H).  One workgroup: 256 rows j, LOGO_HR columns r of group blockIdx.z; every C(j, I_c)
+// is loaded once for the LOGO_HR columns.  Flop: 2 n sum_g |I_g|^2.
+constexpr int LOGO_HR = 8;
+__global__ __launch_bounds__(256) void logo_h_kernel(const double *__restrict__ C, long long ldc, long long n,
+                                                     const long long *__restrict__ idx, const long long *__restrict__ sizes,
+                                                     long long m, const double *__restrict__ X2, long long ldb, long long stride,
+                                                     double *__restrict__ H, long long ldh) {
+  const long long g = blockIdx.z, r0 = (long long)blockIdx.y * LOGO_HR, sz = sizes[g];
+  if (r0 >= sz) return;  // (the whole workgroup)
+  const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long *ig = idx + g * m;
+  const double *B = X2 + g * stride;
+  double acc[LOGO_HR];
+#pragma unroll
+  for (int t = 0; t < LOGO_HR; ++t) acc[t] = 0.;
+  for (long long c = 0; c < sz; ++c) {
+    const double x = j < n ? C[j + ig[c] * ldc] : 0.;
+#pragma unroll
+    for (int t = 0; t < LOGO_HR; ++t) acc[t] += (r0 + t < sz ? B[c + (r0 + t) * ldb] : 0.) * x;
+  }
+  if (j >= n) return;
+#pragma unroll
+  for (int t = 0; t < LOGO_HR; ++t)
+    if (r0 + t < sz) H[j + ig[r0 + t] * ldh] = acc[t];
+}
+
+// out = 1/2 sum_g term[g]   (one workgroup, fixed order)
+__global__ __launch_bounds__(1024) void logo_sum_kernel(const double *__restrict__ term, long long count, double *__restrict__ out) {
+  __shared__ double red[16];
+  double acc = 0.;
+  for (long long i = threadIdx.x; i < count; i += 1024) acc += term[i];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.;
+    for (int w = 0; w < 16; ++w) s += red[w];
+    *out = 0.5 * s;
+  }
+}
+
+// ---- S = H C^T = sym(C) B sym(C), lower tiles, H and C full -----------------------------------------------------------
+// gtg_lower_kernel's product with two different operands, both stored like the matrix (C is symmetric): tile (bi, bj),
+// bi >= bj, sums H(i, k) C(j, k) over all k through the same gemm_nt_sub_tile body.  Flop: N^3.  S is neither operand.
+__global__ __launch_bounds__(GEMM_THREADS, 2) void hct_lower_kernel(GemmArgs g) {
+  __shared__ double lds[2 * 2 * GK * GLD];
+  int bi, bj;
+  lower_tile(blockIdx.x, bi, bj);
+  const long long b = blockIdx.y;  // problem of a batched launch (batch_* = 0: one problem)
+  GemmArgs t = g;
+  t.C = g.C + b * g.batch_C;
+  t.A = g.A + b * g.batch_A;
+  t.B = g.B + b * g.batch_B;
+  gemm_nt_sub_tile<false, false, true>(t, bi, bj, lds);
+}
+
+void launch_hct_lower_batched(hipStream_t s, const double *H, long long ldh, long long stride_H, const double *C, long long ldc,
+                              long long stride_C, long long n, double *S, long long lds_, long long stride_S, long long count) {
+  if (n <= 0 || count <= 0) return;
+  GemmArgs g;
+  g.C = S; g.ldc = lds_; g.A = H; g.lda = ldh; g.B = C; g.ldb = ldc;
+  g.M = n; g.N = n; g.K = n; g.tri = 1;
+  g.ntr = g.ntc = (int)((n + GT - 1) / GT);
+  g.assign = 1;  // S = + H C^T, S not read
+  g.batch_C = stride_S; g.batch_A = stride_H; g.batch_B = stride_C;
+  const long long tiles = (long long)g.ntr * (g.ntr + 1) / 2;
+  hipLaunchKernelGGL(hct_lower_kernel, dim3((unsigned)tiles, (unsigned)count), dim3(GEMM_THREADS), 0, s, g);
+}
+
 }  // namespace agp
 
 using namespace agp;
@@ -413,19 +615,136 @@ static int alpha_and_inverse_factor(agp_context_impl *ctx, GradientCall &g) {
   return AGP_OK;
 }
 
-// the contraction of W's lower triangle (g.A) against dK / dslot, GRAD_GROUP slots per pass, into g.grad_d
+// the contraction of W's lower triangle (g.A, or the slab `weight` with the same leading dimension) against dK / dslot,
+// GRAD_GROUP slots per pass, into g.grad_d
 template <bool LOO>
 static void contract_slots(hipStream_t s, const agp_kernel *k, int n_slots, const agp_gradient_slot *slots,
-                           const GradientCall &g, const double *u, double scale) {
+                           const GradientCall &g, const double *u, double scale, const double *weight = nullptr) {
   for (int g0 = 0; g0 < n_slots; g0 += GRAD_GROUP) {
     ContractArgs ca;
-    ca.C = g.A; ca.ldc = g.lda; ca.alpha = g.z; ca.u = u; ca.partial = g.partial;
+    ca.C = weight ? weight : g.A; ca.ldc = g.lda; ca.alpha = g.z; ca.u = u; ca.partial = g.partial;
     bool scaling[GRAD_GROUP];
     const int cnt = fill_slot_group(k, n_slots, slots, g0, ca.slots, scaling);
     for (int j = 0; j < GRAD_GROUP; ++j) ca.tang[j] = scaling[j] ? g.tang_d + (size_t)ca.slots.param[j] * (size_t)g.ldt_d : nullptr;
     launch_contract<LOO>(s, g.dprog, g.xm, ca, g.tiles);
     hipLaunchKernelGGL(nll_grad_reduce_kernel, dim3(GRAD_GROUP), dim3(256), 0, s, g.partial, g.tiles, cnt, scale, g.grad_d + g0);
   }
+}
+
+// ---- leave-one-group-out: the chunks of groups that advance in lock step ------------------------------------------
+// The non-empty groups sorted by size and cut into chunks: a chunk is padded to its largest group, which is at most twice
+// its smallest, holds at most max(n, m) padded columns (value only: the gathered columns of R fit the slab L leaves) and a
+// bounded volume of tile images.  Every chunk is ONE chain of batched launches (blockIdx.y = group), so the number of
+// chains follows the number of size classes (<= log2 n, plus the splits of a class too large for one chunk), not the
+// number of groups.  meta: per chunk idx[count * m] (-1 = padding) then sizes[count]; term_off: the chunk's first NLL term.
+struct LogoChunk {
+  long long m, count, idx_off, size_off, term_off;
+};
+struct LogoPlan {
+  std::vector<long long> meta;
+  std::vector<LogoChunk> chunks;
+  long long terms = 0;
+  size_t block_elems = 0, img_elems = 0, vec_elems = 0, count_elems = 0;
+};
+constexpr long long LOGO_CHUNK_GROUPS_MAX = 16384;
+constexpr long long LOGO_CHUNK_IMG_ELEMS_MAX = 32ll << 20;  // 256 MiB of tile images per chunk
+static long long logo_img_stride(long long m) { return (m + NB - 1) / NB * (36ll * MB * MB); }
+
+// AGP_ERR_INVALID_ARGUMENT for malformed offsets, an index out of range, or an index that occurs twice (in one group or
+// in two); empty groups are dropped, points in no group are allowed
+static int logo_plan(long long n, int64_t n_groups, const int64_t *offsets, const int64_t *indices, LogoPlan &p) {
+  if (n_groups < 0 || (n_groups > 0 && (!offsets || offsets[0] != 0))) return AGP_ERR_INVALID_ARGUMENT;
+  std::vector<std::pair<long long, long long>> order;  // (size, group), non-empty groups
+  for (int64_t g = 0; g < n_groups; ++g) {
+    const long long m = offsets[g + 1] - offsets[g];
+    if (m < 0) return AGP_ERR_INVALID_ARGUMENT;
+    if (m > 0) order.emplace_back(m, (long long)g);
+  }
+  const long long total = n_groups > 0 ? offsets[n_groups] : 0;
+  if (total > n || (total > 0 && !indices)) return AGP_ERR_INVALID_ARGUMENT;  // (more than n indices: one occurs twice)
+  std::vector<char> seen((size_t)n, 0);
+  for (long long i = 0; i < total; ++i) {
+    const long long j = indices[i];
+    if (j < 0 || j >= n || seen[(size_t)j]) return AGP_ERR_INVALID_ARGUMENT;
+    seen[(size_t)j] = 1;
+  }
+  std::sort(order.begin(), order.end());
+  p.terms = (long long)order.size();
+  size_t at = 0;
+  while (at < order.size()) {
+    const long long m0 = order[at].first;
+    size_t end = at + 1;
+    while (end < order.size()) {
+      const long long m = order[end].first, cnt = (long long)(end - at) + 1;
+      if (m > 2 * m0 || cnt > LOGO_CHUNK_GROUPS_MAX || cnt * m > n || cnt * logo_img_stride(m) > LOGO_CHUNK_IMG_ELEMS_MAX) break;
+      ++end;
+    }
+    LogoChunk ch;
+    ch.m = order[end - 1].first;
+    ch.count = (long long)(end - at);
+    ch.term_off = (long long)at;
+    ch.idx_off = (long long)p.meta.size();
+    p.meta.resize(p.meta.size() + (size_t)(ch.count * ch.m), -1);
+    for (size_t q = at; q < end; ++q) {
+      const long long g = order[q].second, sz = order[q].first;
+      for (long long a = 0; a < sz; ++a) p.meta[(size_t)ch.idx_off + (size_t)((long long)(q - at) * ch.m + a)] = indices[offsets[g] + a];
+    }
+    ch.size_off = (long long)p.meta.size();
+    for (size_t q = at; q < end; ++q) p.meta.push_back(order[q].first);
+    p.chunks.push_back(ch);
+    const size_t blocks = (size_t)ch.count * (size_t)(factor_ld(ch.m) * ch.m), imgs = (size_t)ch.count * (size_t)logo_img_stride(ch.m);
+    const size_t vec = (size_t)round_up(ch.count * ch.m, 2), cnt2 = (size_t)round_up(ch.count, 2);
+    if (blocks > p.block_elems) p.block_elems = blocks;
+    if (imgs > p.img_elems) p.img_elems = imgs;
+    if (vec > p.vec_elems) p.vec_elems = vec;
+    if (cnt2 > p.count_elems) p.count_elems = cnt2;
+    at = end;
+  }
+  return AGP_OK;
+}
+
+// One chunk through its chain.  X0 enters as [A_g 0; 0 I], A_g = C[I_g, I_g]: from the full C (gradient calls), or from
+// the gathered columns of R, A_g = R[:, I_g]^T R[:, I_g] (value only; the columns go where L was).  Then, all groups at
+// once: A_g = L_A L_A^T, Q = L_A^-1, Sigma_g = Q^T Q, d = Sigma alpha_I, V_g = Sigma_g + diag(s_I) = L_V L_V^T with
+// z = L_V^-1 d riding along, the NLL term; and for the gradient T = L_V^-1 Sigma, a_I = T^T z = Sigma V^-1 d,
+// T^T T = Sigma V^-1 Sigma, B_g and (with slots) the columns I_g of H = sym(C) B.
+static void logo_chunk(agp_context_impl *ctx, const GradientCall &g, const LogoRegions &r, const LogoChunk &ch, bool need_c,
+                       bool need_h) {
+  hipStream_t s = ctx->stream;
+  const long long m = ch.m, count = ch.count, n = g.n;
+  const long long ldb = factor_ld(m), stride_B = ldb * m, stride_I = logo_img_stride(m);
+  const long long *idx = r.meta + ch.idx_off, *sizes = r.meta + ch.size_off;
+  const size_t slab_bytes = sizeof(double) * (size_t)stride_B * (size_t)count;
+  const dim3 cols((unsigned)m, (unsigned)count);
+  if (need_c) {
+    hipLaunchKernelGGL(logo_gather_blocks_kernel, cols, dim3(256), 0, s, g.A, g.lda, idx, m, r.X0, ldb, stride_B);
+  } else {
+    for (long long c0 = 0; c0 < count * m; c0 += 32768)  // (grid limit of the gather: 65535 columns per launch)
+      launch_gather_cols(s, g.R, g.lda, idx + c0, count * m - c0 < 32768 ? count * m - c0 : 32768, 0, n, g.A + c0 * g.lda, g.lda);
+    (void)hipMemsetAsync(r.X0, 0, slab_bytes, s);
+    launch_gemm_nt_sub_batched(s, r.X0, ldb, stride_B, g.A, g.lda, true, m * g.lda, g.A, g.lda, true, m * g.lda, m, m, n, false, count);
+    hipLaunchKernelGGL(logo_fix_blocks_kernel, cols, dim3(256), 0, s, idx, m, r.X0, ldb, stride_B);
+  }
+  (void)hipMemsetAsync(r.logs_A, 0, sizeof(double) * (size_t)round_up(count, 2), s);
+  (void)hipMemsetAsync(r.logs_V, 0, sizeof(double) * (size_t)round_up(count, 2), s);
+  factor_lower_batched(s, r.X0, stride_B, m, ldb, r.img, stride_I, nullptr, 0, count, ctx->d_flags, r.logs_A);
+  launch_set_identity_batched(s, r.X1, ldb, stride_B, m, count);
+  forward_solve_mat_batched(s, r.X0, stride_B, m, ldb, r.img, stride_I, r.X1, stride_B, m, ldb, /*rhs_lower=*/true, count);
+  (void)hipMemsetAsync(r.X2, 0, slab_bytes, s);
+  launch_gemm_nt_sub_batched(s, r.X2, ldb, stride_B, r.X1, ldb, true, stride_B, r.X1, ldb, true, stride_B, m, m, m, false, count);  // -Sigma
+  hipLaunchKernelGGL(logo_sigma_kernel, cols, dim3(256), 0, s, r.X2, idx, m, ldb, stride_B, g.z, g.yvar_d, r.X0, need_c ? r.X1 : nullptr,
+                     r.d, r.z);
+  factor_lower_batched(s, r.X0, stride_B, m, ldb, r.img, stride_I, r.z, m, count, ctx->d_flags, r.logs_V);
+  hipLaunchKernelGGL(logo_term_kernel, dim3((unsigned)count), dim3(256), 0, s, r.z, m, r.logs_V, sizes, r.term + ch.term_off);
+  if (!need_c) return;
+  forward_solve_mat_batched(s, r.X0, stride_B, m, ldb, r.img, stride_I, r.X1, stride_B, m, ldb, /*rhs_lower=*/false, count);  // T
+  launch_colvec_dot_batched(s, r.X1, ldb, stride_B, m, r.z, m, count, r.a_pad);
+  (void)hipMemsetAsync(r.X2, 0, slab_bytes, s);
+  launch_gemm_nt_sub_batched(s, r.X2, ldb, stride_B, r.X1, ldb, true, stride_B, r.X1, ldb, true, stride_B, m, m, m, false, count);  // -T^T T
+  hipLaunchKernelGGL(logo_assemble_kernel, cols, dim3(256), 0, s, idx, m, ldb, stride_B, r.a_pad, r.d, r.X2, r.a);
+  if (need_h)
+    hipLaunchKernelGGL(logo_h_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)((m + LOGO_HR - 1) / LOGO_HR), (unsigned)count), dim3(256),
+                       0, s, g.A, g.lda, n, idx, sizes, m, r.X2, ldb, stride_B, g.R, g.lda);
 }
 
 static float elapsed(hipEvent_t a, hipEvent_t b) {
@@ -533,6 +852,90 @@ int agp_loo_nll_gradient(agp_context *c, const agp_kernel *k, const agp_features
       ctx->stage_ms[6] = elapsed(ctx->stage_ev[3], ctx->stage_ev[4]);
       ctx->stage_ms[8] = elapsed(ctx->stage_ev[4], ctx->stage_ev[5]);
       if (n_slots > 0) {
+        ctx->stage_ms[9] = elapsed(ctx->stage_ev[5], ctx->stage_ev[6]);
+        ctx->stage_ms[7] = elapsed(ctx->stage_ev[6], ctx->stage_ev[7]);
+      }
+    }
+  }
+  return AGP_OK;
+}
+
+int agp_logo_nll_gradient(agp_context *c, const agp_kernel *k, const agp_features *x, const double *y, const double *y_var,
+                          int64_t n_groups, const int64_t *offsets, const int64_t *indices, int n_slots,
+                          const agp_gradient_slot *slots, const double *tangents, int64_t ldt, double *logo_nll,
+                          double *grad_logo_nll, double *mean_weights) {
+  if (!c || !k || !x || !y || !logo_nll) return AGP_ERR_INVALID_ARGUMENT;
+  if (n_slots < 0 || n_slots > AGP_MAX_GRADIENT_SLOTS || (n_slots > 0 && (!slots || !grad_logo_nll)))
+    return AGP_ERR_INVALID_ARGUMENT;
+  agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
+  int st = validate_features(x);
+  if (st != AGP_OK) return st;
+  const long long n = x->n;
+  if (n <= 0) return AGP_ERR_INVALID_ARGUMENT;
+  LogoPlan plan;
+  if ((st = logo_plan(n, n_groups, offsets, indices, plan)) != AGP_OK) return st;
+  const bool need_c = n_slots > 0 || mean_weights;  // value only: the blocks from gathered columns of R, no C, H or S
+  const bool need_h = n_slots > 0;
+  const BatchGeometry geo = batch_geometry(n, 1);
+  auto carve = [&](WsLayout &w) {
+    return carve_logo(w, geo, need_h, plan.block_elems, plan.img_elems, plan.vec_elems, plan.count_elems,
+                      (size_t)round_up(plan.terms > 0 ? plan.terms : 1, 2), symv_ws_elems(n), plan.meta.size());
+  };
+  WsLayout size_own;
+  carve(size_own);
+  GradientCall g;
+  st = gradient_setup(ctx, k, x, y, y_var, n_slots, slots, tangents, ldt, size_own.bytes() / sizeof(double), g);
+  if (st != AGP_OK) return st;
+  WsLayout own(g.extra);
+  const LogoRegions r = carve(own);
+  hipStream_t s = ctx->stream;
+  const bool prof = ctx->profiling;
+  if (!plan.meta.empty()) {
+    AGP_HIP_CHECK(ctx, hipMemcpyAsync(r.meta, plan.meta.data(), sizeof(long long) * plan.meta.size(), hipMemcpyHostToDevice, s));
+    AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));  // (pageable source)
+  }
+  if ((st = alpha_and_inverse_factor(ctx, g)) != AGP_OK) return st;
+  AGP_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_flags, 0, 4 * sizeof(int), s));
+  if (need_c) {
+    launch_rtr_lower(s, g.R, g.lda, n, g.A, g.lda);  // C = K^-1 over L
+    if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[4], s));
+    const unsigned mt = (unsigned)((n + GF_T - 1) / GF_T);
+    hipLaunchKernelGGL(mirror_lower_kernel, dim3(mt, mt), dim3(256), 0, s, g.A, g.lda, n, 0LL);
+    AGP_HIP_CHECK(ctx, hipMemsetAsync(r.a, 0, sizeof(double) * (size_t)geo.np2, s));
+    if (need_h) AGP_HIP_CHECK(ctx, hipMemsetAsync(g.R, 0, sizeof(double) * geo.slabs(), s));  // H over R
+  }
+  for (const LogoChunk &ch : plan.chunks) logo_chunk(ctx, g, r, ch, need_c, need_h);
+  hipLaunchKernelGGL(logo_sum_kernel, dim3(1), dim3(1024), 0, s, r.term, plan.terms, ctx->d_scalars + 2);
+  if (need_c) launch_symv_lower(s, g.A, g.lda, n, r.a, 1., 0., nullptr, r.u, r.symv);  // u = C a
+  if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[5], s));
+  if (need_h) {
+    launch_hct_lower_batched(s, g.R, g.lda, 0, g.A, g.lda, 0, n, r.S, g.lda, 0, 1);  // S = C B C
+    if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[6], s));
+    contract_slots<true>(s, k, n_slots, slots, g, r.u, 1.0, r.S);
+    if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[7], s));
+  }
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  std::vector<double> h_grad((size_t)n_slots), h_u(mean_weights ? (size_t)n : 0);
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_scalars, ctx->d_scalars, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (n_slots > 0) AGP_HIP_CHECK(ctx, hipMemcpyAsync(h_grad.data(), g.grad_d, sizeof(double) * (size_t)n_slots, hipMemcpyDeviceToHost, s));
+  if (mean_weights) AGP_HIP_CHECK(ctx, hipMemcpyAsync(h_u.data(), r.u, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  if ((st = status_from_flags(ctx)) != AGP_OK) return st;  // a group block that did not factor: nothing is written
+  *logo_nll = ctx->h_scalars[2];
+  if (n_slots > 0) std::memcpy(grad_logo_nll, h_grad.data(), sizeof(double) * (size_t)n_slots);
+  if (mean_weights) std::memcpy(mean_weights, h_u.data(), sizeof(double) * (size_t)n);
+  if (prof) {
+    // 2: alpha and R = L^-1; value only: 8 the group blocks and terms; otherwise 6 R^T R, 8 the mirror, the group blocks,
+    // u and H, 9 the product, 7 the contraction
+    ctx->stage_ms[6] = ctx->stage_ms[7] = ctx->stage_ms[8] = ctx->stage_ms[9] = 0.;
+    ctx->stage_ms[2] = elapsed(ctx->stage_ev[2], ctx->stage_ev[3]);
+    if (!need_c) {
+      ctx->stage_ms[8] = elapsed(ctx->stage_ev[3], ctx->stage_ev[5]);
+    } else {
+      ctx->stage_ms[6] = elapsed(ctx->stage_ev[3], ctx->stage_ev[4]);
+      ctx->stage_ms[8] = elapsed(ctx->stage_ev[4], ctx->stage_ev[5]);
+      if (need_h) {
         ctx->stage_ms[9] = elapsed(ctx->stage_ev[5], ctx->stage_ev[6]);
         ctx->stage_ms[7] = elapsed(ctx->stage_ev[6], ctx->stage_ev[7]);
       }

@@ -1273,6 +1273,32 @@ class GaussianProcessRegression:
         values, grads = _leave_one_out_likelihood_gradients(models, [dataset] * len(models), "leave_one_out_likelihood_gradients")
         return np.asarray(values), grads
 
+    def leave_one_group_out_likelihood_gradient(self, dataset, grouper):
+        """(LeaveOneGroupOutLikelihood(grouper)(dataset, self), {name: d that / d name}) for every name of get_params(),
+        exact to fp64 rounding (agp_logo_nll_gradient).  grouper: what CrossValidation.predict accepts - a callable on a
+        feature, a LeaveOneOutGrouper or an indexer dict {key: [indices]}.  The value is the metric the tuner minimises,
+        sum_g NLL_g of the JOINT held-out prediction of each group scored against the group's targets with their variances
+        added (evaluation/model_metrics.hpp:74-93); the target variance is used twice, in the fit and in the score, as in
+        leave_one_out_likelihood_gradient, and priors are not included.  Parameters shared by several leaves are summed;
+        ScalingTerm parameters go through ScalingFunction.derivative, mean-function parameters through
+        -u^T d mu / d name (the entry's mean weights) with a central difference of the mean function on the host.
+        fp64 models only."""
+        if self.precision != "fp64":
+            raise ValueError(f"leave_one_group_out_likelihood_gradient: fp64 models only, not {self.precision!r}")
+        p = _gradient_problem(self, dataset, "agp_logo_nll_gradient")
+        offsets, indices = _group_arrays(dataset, grouper, p.fs.n)
+        ctx = self._ctx()
+        n = p.fs.n
+        s = p.fs.as_struct()
+        value = C.c_double()
+        grad = np.zeros(len(p.slots))
+        u = np.empty(n)
+        ctx._check(ctx._lib.agp_logo_nll_gradient(ctx._h, ctx.kernel(self.covariance_function_), C.byref(s), _ptr(p.y), _ptr(p.yv),
+                                                  len(offsets) - 1, _ptr(offsets), _ptr(indices), len(p.slots), p.table,
+                                                  _ptr(p.tangents), n, C.byref(value), _ptr(grad), _ptr(u)),
+                   "agp_logo_nll_gradient")
+        return value.value, self._leave_one_out_gradient_dict(p.slots, grad, u, p.fs)
+
     def _leave_one_out_gradient_dict(self, slots, grad_loo, u, fs):
         """{name: d LOO / d name} from agp_loo_nll_gradient's per-slot values and mean weights u (slots sharing a name
         summed)"""
@@ -1404,6 +1430,46 @@ class LeaveOneOutLikelihood:
         out = C.c_double()
         ctx._check(ctx._lib.agp_loo_nll_gradient(ctx._h, ctx.kernel(cov), C.byref(s), _ptr(y), _ptr(yv), 0, None, None, 0,
                                                  C.byref(out), None, None), "agp_loo_nll_gradient")
+        return out.value
+
+
+def _group_arrays(dataset, grouper, n):
+    """(offsets, indices) int64 arrays of agp_logo_nll_gradient from what CrossValidation.predict accepts"""
+    indexer = grouper if isinstance(grouper, dict) else group_indexer(dataset.features, grouper)
+    groups = [np.asarray(idx, dtype=np.int64).reshape(-1) for idx in indexer.values()]
+    offsets = np.zeros(len(groups) + 1, dtype=np.int64)
+    if groups:
+        offsets[1:] = np.cumsum([len(g) for g in groups])
+    indices = np.concatenate(groups) if groups else np.zeros(0, dtype=np.int64)
+    return offsets, np.ascontiguousarray(indices, dtype=np.int64)
+
+
+class LeaveOneGroupOutLikelihood:
+    """LeaveOneGroupOutLikelihood<FeatureType>(grouper) (evaluation/model_metrics.hpp:74-93, PredictType =
+    JointDistribution): metric(dataset, model) = sum over the groups of the negative log-likelihood of the group's JOINT
+    held-out prediction, scored against the group's targets with their variances added (prediction_metrics.hpp:112-119).
+    No prior term.  grouper: a callable on a feature, a LeaveOneOutGrouper or an indexer dict.  One fit, R = L^-1 and the
+    group blocks from gathered columns of R (agp_logo_nll_gradient, value only);
+    model.leave_one_group_out_likelihood_gradient gives the gradient too."""
+
+    def __init__(self, grouper):
+        self.grouper_ = grouper
+
+    def __call__(self, dataset, model):
+        if model.precision != "fp64":
+            raise ValueError(f"LeaveOneGroupOutLikelihood: fp64 models only, not {model.precision!r}")
+        if has_linear_combinations(dataset.features):
+            raise NotImplementedError("LeaveOneGroupOutLikelihood: LinearCombination features go through the dense path")
+        ctx = model._ctx()
+        cov = model.covariance_function_
+        fs = cov.features(_values_of(dataset.features))
+        y, yv = model._targets(fs, dataset.targets)
+        offsets, indices = _group_arrays(dataset, self.grouper_, fs.n)
+        s = fs.as_struct()
+        out = C.c_double()
+        ctx._check(ctx._lib.agp_logo_nll_gradient(ctx._h, ctx.kernel(cov), C.byref(s), _ptr(y), _ptr(yv), len(offsets) - 1,
+                                                  _ptr(offsets), _ptr(indices), 0, None, None, 0, C.byref(out), None, None),
+                   "agp_logo_nll_gradient")
         return out.value
 
 

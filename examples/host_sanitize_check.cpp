@@ -294,6 +294,15 @@ void layouts_under_sanitizers() {
             return std::vector<Region>{{r.R, D * sA}, {r.bs_ws, D * bs}, {r.partial, D * part}, {r.grad, D * grad}, {r.tang, D * tang},
                                        {r.extra, D * xtra}};
           });
+          // agp_logo_nll_gradient's own region (odd element counts: every region still starts on 16 bytes)
+          const size_t blk = 3 * (size_t)lda + 5, img = 2 * (size_t)IMG, vec = 2 * np2, cnt = 6, terms = 4, symv = np2 + 3, meta = 2 * np2 + 7;
+          const bool slab = fused != 0;  // (with or without the third slab)
+          check_layout("carve_logo", (slab ? sA : 0) + 3 * blk + img + 3 * vec + 2 * cnt + terms + 2 * np2 + symv + meta, [&](agp::WsLayout &w) {
+            const agp::LogoRegions r = agp::carve_logo(w, g, slab, blk, img, vec, cnt, terms, symv, meta);
+            return std::vector<Region>{{r.S, D * sA}, {r.X0, D * blk}, {r.X1, D * blk}, {r.X2, D * blk}, {r.img, D * img}, {r.d, D * vec},
+                                       {r.z, D * vec}, {r.a_pad, D * vec}, {r.logs_A, D * cnt}, {r.logs_V, D * cnt}, {r.term, D * terms},
+                                       {r.a, D * np2}, {r.u, D * np2}, {r.symv, D * symv}, {r.meta, sizeof(long long) * meta}};
+          });
         }
       }
 }

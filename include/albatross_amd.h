@@ -380,6 +380,50 @@ AGP_API int agp_loo_nll_gradient_batch(agp_context *ctx, int count,
                                        double *mean_weights, int64_t ldw,
                                        int *status);
 
+/* The leave-one-GROUP-out likelihood metric, LeaveOneGroupOutLikelihood<FeatureType>(grouper)(dataset, model) with
+ * PredictType = JointDistribution (evaluation/model_metrics.hpp:74-93, without the prior term), and its exact gradient
+ * with respect to covariance parameters: the objective to tune with when observations come in correlated bunches (one
+ * group per station, pass or day), where a point's neighbours in its own group must not stay in the fit.  (PredictType =
+ * MarginalDistribution scores the marginals only; that is a different formula and is not built.)
+ * Groups as in agp_held_out_predictions: group g holds indices[offsets[g] .. offsets[g + 1]), offsets[0] = 0, host
+ * arrays, indices in any order inside a group.  Empty groups contribute nothing; points in no group contribute no term.
+ * With K = cov(x, x) + diag(y_var), C = K^-1, alpha = C y, s = y_var (0 if NULL), and per group with index set I (size m):
+ *   A = C[I, I]   (SerializableLDLT::inverse_blocks),
+ *   Sigma = A^-1,   d = Sigma alpha_I   (held_out_prediction, Joint: cross_validation_utils.hpp:188-197),
+ *   V = Sigma + diag(s_I)   (negative_log_likelihood(Joint, Marginal): prediction_metrics.hpp:112-119),
+ *   NLL_g = 1/2 (log |V| + d^T V^-1 d + m log 2 pi),   logo_nll = sum_g NLL_g.
+ * y_var is used in BOTH places, as for agp_loo_nll_gradient: in the fit, and as the truth's covariance of the score.
+ * Gradient, with q = V^-1 d and a_I = Sigma q (a: an n-vector assembled over the groups, 0 where a point is in no group):
+ *   B_g = 1/2 Sigma V^-1 Sigma - 1/2 a_I a_I^T + 1/2 (a_I d^T + d a_I^T)   (m x m, symmetric),
+ *   B = the block matrix with B_g at [I_g, I_g], zero elsewhere,   u = C a,   W = C B C - 1/2 (u alpha^T + alpha u^T),
+ *   dlogo_nll / dtheta = sum_ij W_ij dK_ij / dtheta,   dlogo_nll / dtheta_mean = -mean_weights^T dm / dtheta (mean_weights = u).
+ * With singleton groups these are the b_i, a_i, u and W of agp_loo_nll_gradient.  B_g is NOT positive semi-definite in
+ * general (B_g = 1/2 Sigma V^-1 Sigma + 1/2 d d^T - 1/2 e e^T, e = diag(s_I) V^-1 d), so the product takes B as a general
+ * symmetric block matrix: H = sym(C) B, then C B C = H C^T on the fp64 MFMA.
+ * Steps: those of agp_loo_nll_gradient up to C = R^T R; C mirrored to both triangles; the groups sorted by size and cut
+ * into chunks of comparable size (at most 2x padding), each chunk ONE chain of batched launches (gather, two LL^T, two
+ * triangular solves, two products, the assembly), so the number of chains follows the number of size classes, not of
+ * groups; H (2 N sum_g m_g^2 flop); C B C (N^3 flop, as agp_loo_nll_gradient's G^T G); the contraction.
+ * n_slots == 0 and mean_weights NULL: the value alone; A_g = R[:, I_g]^T R[:, I_g] from gathered columns of R, and
+ * neither C, H nor C B C is formed: a fit plus N^3 / 3 flop plus 2 N sum_g m_g^2 for the blocks.
+ * Workspace: ONE lda x n slab more than agp_loo_nll_gradient (C B C cannot overwrite an operand: three slabs, C, H over
+ * R, and S), plus three padded block slabs and the tile images of the chunk in flight (at most max(n, m) padded columns
+ * and 256 MiB of images per chunk) and O(n) vectors.
+ * An index out of range, an index in two groups or twice in one, malformed offsets, or a malformed slot (the list of
+ * agp_nll_gradient): AGP_ERR_INVALID_ARGUMENT, nothing written.  A group block (A_g or V_g) that does not factor:
+ * AGP_ERR_NOT_POSITIVE_DEFINITE, nothing written.  Slots, tangents, locations and the other status codes as
+ * agp_loo_nll_gradient; logo_nll (1 value), grad_logo_nll (n_slots values) and mean_weights (n values, may be NULL) are
+ * host memory.  No float atomics, fixed-order reductions: two identical calls are bit-identical.  With profiling on,
+ * agp_last_stage_ms reports 0 gram, 1 factor, 2 alpha and R = L^-1, 6 R^T R, 8 the group blocks, u and H (value only:
+ * the group blocks from R), 9 the product C B C, 7 the contraction; stages a call does not run report 0. */
+AGP_API int agp_logo_nll_gradient(agp_context *ctx, const agp_kernel *k, const agp_features *x,
+                                  const double *y, const double *y_var,
+                                  int64_t n_groups, const int64_t *offsets, const int64_t *indices,
+                                  int n_slots, const agp_gradient_slot *slots,
+                                  const double *tangents, int64_t ldt,
+                                  double *logo_nll, double *grad_logo_nll,
+                                  double *mean_weights);
+
 /* Tuner objective batching: agp_nll for `count` parameter vectors of one model on one dataset in lock step
  * (batched Gram slabs + batched LL^T; blockIdx.y = parameter vector) — the evaluations that
  * compute_gradient (include/albatross/src/tune/finite_difference.hpp:20-94) and the ModelTuner objective

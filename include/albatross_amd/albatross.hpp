@@ -1640,6 +1640,14 @@ class Communicator {
 // ---------------------------------------------------------------------------
 // GaussianProcessRegression (gp.hpp:170-505)
 // ---------------------------------------------------------------------------
+namespace detail {
+// the groups of dataset.group_by(grouper).indexers() in key order, as (offsets, indices) of agp_logo_nll_gradient
+// (defined behind group_indexer)
+template <typename FeatureType, typename Grouper>
+void group_arrays(const std::vector<FeatureType> &features, const Grouper &grouper, std::vector<std::int64_t> *offsets,
+                  std::vector<std::int64_t> *indices);
+}  // namespace detail
+
 template <typename CovFunc, typename MeanFunc = ZeroMean>
 class GaussianProcessRegression {
  public:
@@ -1985,6 +1993,52 @@ class GaussianProcessRegression {
     return loo;
   }
 
+  // LeaveOneGroupOutLikelihood<FeatureType>(grouper)(dataset, *this) (evaluation/model_metrics.hpp:74-93, Joint predict
+  // type, no prior term) and its exact gradient with respect to every name of get_params() (agp_logo_nll_gradient):
+  // sum_g NLL_g of the joint held-out prediction of each group, scored against the group's targets with their variances
+  // added.  grouper: what cross_validate().predict accepts - a callable on a feature, a LeaveOneOutGrouper or a
+  // GroupIndexer.  The target variance and the mean-function parameters as in leave_one_out_likelihood_gradient.
+  template <typename FeatureType, typename Grouper>
+  LeaveOneOutLikelihoodGradient leave_one_group_out_likelihood_gradient(const RegressionDataset<FeatureType> &dataset,
+                                                                        const Grouper &grouper) const {
+    std::vector<std::int64_t> offsets, indices;
+    detail::group_arrays(dataset.features, grouper, &offsets, &indices);
+    const std::int64_t n_groups = static_cast<std::int64_t>(offsets.size()) - 1;
+    const auto entry = [&](agp_context *c, const agp_kernel *k, const agp_features *x, const double *y, const double *y_var,
+                           int n_slots, const agp_gradient_slot *slots, const double *tangents, std::int64_t ldt, double *value,
+                           double *grad, double *weights) {
+      return agp_logo_nll_gradient(c, k, x, y, y_var, n_groups, offsets.data(), indices.data(), n_slots, slots, tangents, ldt, value,
+                                   grad, weights);
+    };
+    std::vector<std::string> names;
+    std::vector<double> grad, u;
+    const double *yvar = dataset.targets.covariance.empty() ? nullptr : dataset.targets.covariance.data();
+    const double logo = slot_gradient(entry, "agp_logo_nll_gradient", dataset, yvar, &names, &grad, &u);
+    LeaveOneOutLikelihoodGradient out{logo, {}};
+    for (const auto &kv : get_params()) out.gradient[kv.first] = 0.;
+    for (std::size_t s = 0; s < names.size(); ++s) out.gradient[names[s]] += grad[s];
+    for (const auto &kv : mean_function_.get_params())  // y = targets - mu: d LOGO / d theta = -u^T (d mu / d theta)
+      out.gradient[kv.first] -= mean_tangent_dot(dataset, kv.first, kv.second, u);
+    return out;
+  }
+
+  // the value alone (agp_logo_nll_gradient without slots: the group blocks from gathered columns of R, no K^-1)
+  template <typename FeatureType, typename Grouper>
+  double leave_one_group_out_likelihood(const RegressionDataset<FeatureType> &dataset, const Grouper &grouper) const {
+    std::vector<std::int64_t> offsets, indices;
+    detail::group_arrays(dataset.features, grouper, &offsets, &indices);
+    auto ctx = detail::default_context();
+    detail::KernelHolder k(covariance_function_.program());
+    detail::Flat f = detail::flatten(covariance_function_, dataset.features);
+    const Vector y = deviation(dataset);
+    const double *yvar = dataset.targets.covariance.empty() ? nullptr : dataset.targets.covariance.data();
+    double logo = 0.;
+    detail::check(agp_logo_nll_gradient(ctx->ctx, k.k, &f.view, y.data(), yvar, static_cast<std::int64_t>(offsets.size()) - 1,
+                                        offsets.data(), indices.data(), 0, nullptr, nullptr, 0, &logo, nullptr, nullptr),
+                  ctx->ctx, "agp_logo_nll_gradient");
+    return logo;
+  }
+
   // leave_one_out_likelihood_gradient(dataset) for several parameter vectors in ONE batched device pass
   // (agp_loo_nll_gradient_batch), one model copy per entry as log_likelihood_gradients makes them.  Signs and the target
   // variance as in leave_one_out_likelihood_gradient.  A parameter vector whose covariance is not positive definite (or
@@ -2229,6 +2283,25 @@ GroupIndexer<std::size_t> group_indexer(const std::vector<FeatureType> &features
   for (std::size_t i = 0; i < features.size(); ++i) out[i] = {i};
   return out;
 }
+
+template <typename FeatureType, typename GroupKey>
+const GroupIndexer<GroupKey> &group_indexer(const std::vector<FeatureType> &, const GroupIndexer<GroupKey> &indexer) {
+  return indexer;
+}
+
+namespace detail {
+template <typename FeatureType, typename Grouper>
+void group_arrays(const std::vector<FeatureType> &features, const Grouper &grouper, std::vector<std::int64_t> *offsets,
+                  std::vector<std::int64_t> *indices) {
+  const auto &indexer = group_indexer(features, grouper);
+  offsets->assign(1, 0);
+  indices->clear();
+  for (const auto &kv : indexer) {
+    for (const std::size_t i : kv.second) indices->push_back(static_cast<std::int64_t>(i));
+    offsets->push_back(static_cast<std::int64_t>(indices->size()));
+  }
+}
+}  // namespace detail
 
 template <typename ModelType, typename FeatureType, typename GroupKey>
 class CrossValidationPrediction {
@@ -2822,6 +2895,28 @@ struct LeaveOneOutLikelihood {
                     const GaussianProcessRegression<CovFunc, MeanFunc> &model) const {
     return model.leave_one_out_likelihood(dataset);
   }
+};
+
+// LeaveOneGroupOutLikelihood<FeatureType>, evaluation/model_metrics.hpp:74-93: the tuner's metric for observations
+// that come in correlated groups (no prior term).  Only PredictType = JointDistribution, the reference's default, is
+// built: the Marginal predict type scores the held-out marginals, a different formula (out of scope).
+template <typename FeatureType>
+using GroupFunction = std::string (*)(const FeatureType &);
+
+template <typename FeatureType, typename PredictType = JointDistribution>
+class LeaveOneGroupOutLikelihood {
+  static_assert(std::is_same<PredictType, JointDistribution>::value, "LeaveOneGroupOutLikelihood: the Joint predict type only");
+
+ public:
+  explicit LeaveOneGroupOutLikelihood(const GroupFunction<FeatureType> &grouper) : grouper_(grouper) {}
+
+  template <typename CovFunc, typename MeanFunc>
+  double operator()(const RegressionDataset<FeatureType> &dataset, const GaussianProcessRegression<CovFunc, MeanFunc> &model) const {
+    return model.leave_one_group_out_likelihood(dataset, grouper_);
+  }
+
+ private:
+  GroupFunction<FeatureType> grouper_;
 };
 
 }  // namespace albatross
