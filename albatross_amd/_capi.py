@@ -43,6 +43,9 @@ MAX_DIM = 8
 MAX_SCALE_COLUMNS = 4
 MAX_GRADIENT_SLOTS = 64
 
+PREDICT_JOINT = 0  # agp_logo_nll_gradient_typed's predict_type
+PREDICT_MARGINAL = 1
+
 
 class KernelNode(C.Structure):
     _fields_ = [
@@ -101,6 +104,8 @@ EXPORTS = [
     ("agp_loo_nll_gradient", C.c_int, [_P, _P, C.POINTER(Features), _P, _P, C.c_int, _P, _P, C.c_int64, _D, _P, _P]),
     ("agp_logo_nll_gradient", C.c_int, [_P, _P, C.POINTER(Features), _P, _P, C.c_int64, _P, _P, C.c_int, _P, _P, C.c_int64, _D, _P,
                                         _P]),
+    ("agp_logo_nll_gradient_typed", C.c_int, [_P, _P, C.POINTER(Features), _P, _P, C.c_int64, _P, _P, C.c_int, C.c_int, _P, _P,
+                                              C.c_int64, _D, _P, _P, _P]),
     ("agp_nll_gradient_batch", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P,
                                          C.c_int64, _P, C.c_int64, _P]),
     ("agp_loo_nll_gradient_batch", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P,

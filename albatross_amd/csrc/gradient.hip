@@ -35,6 +35,10 @@
 // agp_loo_nll_gradient; the group blocks go through the batched LL^T / solve / product launches that
 // agp_held_out_predictions uses (cv_api.hip), the groups sorted by size and cut into chunks of comparable size that
 // advance in lock step (logo_plan, logo_chunk), with the small kernels below around them.
+// agp_logo_nll_gradient_typed is the same entry with the score's predict type as an argument: AGP_PREDICT_MARGINAL scores
+// each held-out group against the diagonal of V only (v_i = Sigma_ii + s_i, q_i = d_i / v_i, w_i = 1/2 (1 / v_i - q_i^2),
+// a_I = Sigma q, B_g = Sigma diag(w) Sigma + 1/2 (a_I d^T + d a_I^T)): the chain up to Sigma_g is shared, then a per-column
+// kernel and ONE two-operand block product replace the second LL^T, the second solve and T^T T.
 //
 // agp_nll_gradient_batch and agp_loo_nll_gradient_batch run the same steps for `count` problems of one size in lock step:
 // every kernel below takes the problem from blockIdx.y (blockIdx.z where y is a tile index) and per-problem strides, and
@@ -424,6 +428,72 @@ __global__ __launch_bounds__(256) void logo_assemble_kernel(const long long *__r
   if (threadIdx.x == 0 && ic >= 0) a[ic] = ac;
 }
 
+// Marginal predict type.  X2_g holds -Sigma_g.  Column c of group g: d_c = (Sigma_g alpha_I)_c, v_c = Sigma_cc + s_c,
+// q_c = d_c / v_c, and the column's share log v_c + d_c q_c of 2 NLL_g into t.  Gradient calls (X0 != nullptr): Sigma_g into
+// X0 and Sigma_g diag(w) into X1 (this column scaled by w_c = 1/2 (1 / v_c - q_c^2), which is NEGATIVE whenever
+// d_c^2 > v_c).  A padding column is e_c: d_c = q_c = 0, log v_c = log 1 = 0, and w_c is set to 0.
+__global__ __launch_bounds__(256) void logo_marginal_sigma_kernel(const double *__restrict__ X2, const long long *__restrict__ idx,
+                                                                  long long m, long long ldb, long long stride,
+                                                                  const double *__restrict__ alpha, const double *__restrict__ yvar,
+                                                                  double *__restrict__ X0, double *__restrict__ X1,
+                                                                  double *__restrict__ d, double *__restrict__ q,
+                                                                  double *__restrict__ t) {
+  __shared__ double red[4];
+  const long long c = blockIdx.x, g = blockIdx.y;
+  const long long *ig = idx + g * m;
+  const long long off = g * stride + c * ldb, ic = ig[c];
+  double acc = 0.;
+  for (long long r = threadIdx.x; r < m; r += 256) {
+    const long long ir = ig[r];
+    acc += -X2[off + r] * (ir >= 0 ? alpha[ir] : 0.);
+  }
+  const double dc = logo_block_sum(acc, red);
+  const double vc = -X2[off + c] + ((yvar && ic >= 0) ? yvar[ic] : 0.);
+  const double qc = dc / vc;
+  if (threadIdx.x == 0) {
+    d[g * m + c] = dc;
+    q[g * m + c] = qc;
+    t[g * m + c] = log(vc) + dc * qc;
+  }
+  if (!X0) return;
+  const double wc = ic >= 0 ? 0.5 * (1. / vc - qc * qc) : 0.;
+  for (long long r = threadIdx.x; r < m; r += 256) {
+    const double sg = -X2[off + r];
+    X0[off + r] = sg;
+    X1[off + r] = sg * wc;
+  }
+}
+
+// Marginal predict type: term[g] = sum_c (log v_c + d_c q_c) + |I_g| log 2 pi = 2 NLL_g, the scale of logo_term_kernel
+__global__ __launch_bounds__(256) void logo_marginal_term_kernel(const double *__restrict__ t, long long m,
+                                                                 const long long *__restrict__ sizes, double *__restrict__ term) {
+  __shared__ double red[4];
+  const long long g = blockIdx.x;
+  double acc = 0.;
+  for (long long r = threadIdx.x; r < m; r += 256) acc += t[g * m + r];
+  const double sum = logo_block_sum(acc, red);
+  if (threadIdx.x == 0) term[g] = sum + (double)sizes[g] * log(2. * M_PI);
+}
+
+// Marginal predict type.  X2_g holds -(Sigma_g diag(w)) Sigma_g^T.  Column c of group g:
+//   B_g = Sigma diag(w) Sigma + 1/2 (a d^T + d a^T)   (symmetric, INDEFINITE wherever some w_c < 0)
+// with zero rows and columns in the padding, and a[I_g[c]] = a_pad[c] (no scatter from the padding).
+__global__ __launch_bounds__(256) void logo_marginal_assemble_kernel(const long long *__restrict__ idx, long long m, long long ldb,
+                                                                     long long stride, const double *__restrict__ a_pad,
+                                                                     const double *__restrict__ d, double *__restrict__ X2,
+                                                                     double *__restrict__ a) {
+  const long long c = blockIdx.x, g = blockIdx.y;
+  const long long *ig = idx + g * m;
+  const long long ic = ig[c];
+  const double ac = a_pad[g * m + c], dc = d[g * m + c];
+  double *x = X2 + g * stride + c * ldb;
+  for (long long r = threadIdx.x; r < m; r += 256) {
+    const double ar = a_pad[g * m + r], dr = d[g * m + r];
+    x[r] = (ic >= 0 && ig[r] >= 0) ? -x[r] + 0.5 * (ar * dc + dr * ac) : 0.;
+  }
+  if (threadIdx.x == 0 && ic >= 0) a[ic] = ac;
+}
+
 // H = sym(C) B (n x n, ldh): column I_g[r] of H is sum_c B_g(c, r) C[:, I_g[c]]; the columns of points in no group
 // stay zero (the caller zero-fills H).  One workgroup: 256 rows j, LOGO_HR columns r of group blockIdx.z; every C(j, I_c)
 // is loaded once for the LOGO_HR columns.  Flop: 2 n sum_g |I_g|^2.
@@ -643,6 +713,7 @@ struct LogoChunk {
 struct LogoPlan {
   std::vector<long long> meta;
   std::vector<LogoChunk> chunks;
+  std::vector<long long> group;  // term q belongs to the caller's group group[q]
   long long terms = 0;
   size_t block_elems = 0, img_elems = 0, vec_elems = 0, count_elems = 0;
 };
@@ -670,6 +741,7 @@ static int logo_plan(long long n, int64_t n_groups, const int64_t *offsets, cons
   }
   std::sort(order.begin(), order.end());
   p.terms = (long long)order.size();
+  for (const auto &o : order) p.group.push_back(o.second);
   size_t at = 0;
   while (at < order.size()) {
     const long long m0 = order[at].first;
@@ -708,8 +780,11 @@ static int logo_plan(long long n, int64_t n_groups, const int64_t *offsets, cons
 // once: A_g = L_A L_A^T, Q = L_A^-1, Sigma_g = Q^T Q, d = Sigma alpha_I, V_g = Sigma_g + diag(s_I) = L_V L_V^T with
 // z = L_V^-1 d riding along, the NLL term; and for the gradient T = L_V^-1 Sigma, a_I = T^T z = Sigma V^-1 d,
 // T^T T = Sigma V^-1 Sigma, B_g and (with slots) the columns I_g of H = sym(C) B.
+// marginal (AGP_PREDICT_MARGINAL): the same up to -Sigma_g in X2; then d, q = d / v and the terms per column (the shares of
+// 2 NLL_g wait in a_pad until the term kernel has summed them), and for the gradient Sigma into X0, Sigma diag(w) into X1,
+// a_I = Sigma q, -(Sigma diag(w)) Sigma^T as a product of two different operands, B_g, H.  No second LL^T, no T.
 static void logo_chunk(agp_context_impl *ctx, const GradientCall &g, const LogoRegions &r, const LogoChunk &ch, bool need_c,
-                       bool need_h) {
+                       bool need_h, bool marginal) {
   hipStream_t s = ctx->stream;
   const long long m = ch.m, count = ch.count, n = g.n;
   const long long ldb = factor_ld(m), stride_B = ldb * m, stride_I = logo_img_stride(m);
@@ -732,16 +807,27 @@ static void logo_chunk(agp_context_impl *ctx, const GradientCall &g, const LogoR
   forward_solve_mat_batched(s, r.X0, stride_B, m, ldb, r.img, stride_I, r.X1, stride_B, m, ldb, /*rhs_lower=*/true, count);
   (void)hipMemsetAsync(r.X2, 0, slab_bytes, s);
   launch_gemm_nt_sub_batched(s, r.X2, ldb, stride_B, r.X1, ldb, true, stride_B, r.X1, ldb, true, stride_B, m, m, m, false, count);  // -Sigma
-  hipLaunchKernelGGL(logo_sigma_kernel, cols, dim3(256), 0, s, r.X2, idx, m, ldb, stride_B, g.z, g.yvar_d, r.X0, need_c ? r.X1 : nullptr,
-                     r.d, r.z);
-  factor_lower_batched(s, r.X0, stride_B, m, ldb, r.img, stride_I, r.z, m, count, ctx->d_flags, r.logs_V);
-  hipLaunchKernelGGL(logo_term_kernel, dim3((unsigned)count), dim3(256), 0, s, r.z, m, r.logs_V, sizes, r.term + ch.term_off);
-  if (!need_c) return;
-  forward_solve_mat_batched(s, r.X0, stride_B, m, ldb, r.img, stride_I, r.X1, stride_B, m, ldb, /*rhs_lower=*/false, count);  // T
-  launch_colvec_dot_batched(s, r.X1, ldb, stride_B, m, r.z, m, count, r.a_pad);
-  (void)hipMemsetAsync(r.X2, 0, slab_bytes, s);
-  launch_gemm_nt_sub_batched(s, r.X2, ldb, stride_B, r.X1, ldb, true, stride_B, r.X1, ldb, true, stride_B, m, m, m, false, count);  // -T^T T
-  hipLaunchKernelGGL(logo_assemble_kernel, cols, dim3(256), 0, s, idx, m, ldb, stride_B, r.a_pad, r.d, r.X2, r.a);
+  if (marginal) {
+    hipLaunchKernelGGL(logo_marginal_sigma_kernel, cols, dim3(256), 0, s, r.X2, idx, m, ldb, stride_B, g.z, g.yvar_d,
+                       need_c ? r.X0 : nullptr, need_c ? r.X1 : nullptr, r.d, r.z, r.a_pad);
+    hipLaunchKernelGGL(logo_marginal_term_kernel, dim3((unsigned)count), dim3(256), 0, s, r.a_pad, m, sizes, r.term + ch.term_off);
+    if (!need_c) return;
+    launch_colvec_dot_batched(s, r.X0, ldb, stride_B, m, r.z, m, count, r.a_pad);  // a_I = Sigma q (Sigma symmetric)
+    (void)hipMemsetAsync(r.X2, 0, slab_bytes, s);
+    launch_gemm_nt_sub_batched(s, r.X2, ldb, stride_B, r.X1, ldb, false, stride_B, r.X0, ldb, false, stride_B, m, m, m, false, count);
+    hipLaunchKernelGGL(logo_marginal_assemble_kernel, cols, dim3(256), 0, s, idx, m, ldb, stride_B, r.a_pad, r.d, r.X2, r.a);
+  } else {
+    hipLaunchKernelGGL(logo_sigma_kernel, cols, dim3(256), 0, s, r.X2, idx, m, ldb, stride_B, g.z, g.yvar_d, r.X0, need_c ? r.X1 : nullptr,
+                       r.d, r.z);
+    factor_lower_batched(s, r.X0, stride_B, m, ldb, r.img, stride_I, r.z, m, count, ctx->d_flags, r.logs_V);
+    hipLaunchKernelGGL(logo_term_kernel, dim3((unsigned)count), dim3(256), 0, s, r.z, m, r.logs_V, sizes, r.term + ch.term_off);
+    if (!need_c) return;
+    forward_solve_mat_batched(s, r.X0, stride_B, m, ldb, r.img, stride_I, r.X1, stride_B, m, ldb, /*rhs_lower=*/false, count);  // T
+    launch_colvec_dot_batched(s, r.X1, ldb, stride_B, m, r.z, m, count, r.a_pad);
+    (void)hipMemsetAsync(r.X2, 0, slab_bytes, s);
+    launch_gemm_nt_sub_batched(s, r.X2, ldb, stride_B, r.X1, ldb, true, stride_B, r.X1, ldb, true, stride_B, m, m, m, false, count);  // -T^T T
+    hipLaunchKernelGGL(logo_assemble_kernel, cols, dim3(256), 0, s, idx, m, ldb, stride_B, r.a_pad, r.d, r.X2, r.a);
+  }
   if (need_h)
     hipLaunchKernelGGL(logo_h_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)((m + LOGO_HR - 1) / LOGO_HR), (unsigned)count), dim3(256),
                        0, s, g.A, g.lda, n, idx, sizes, m, r.X2, ldb, stride_B, g.R, g.lda);
@@ -864,7 +950,17 @@ int agp_logo_nll_gradient(agp_context *c, const agp_kernel *k, const agp_feature
                           int64_t n_groups, const int64_t *offsets, const int64_t *indices, int n_slots,
                           const agp_gradient_slot *slots, const double *tangents, int64_t ldt, double *logo_nll,
                           double *grad_logo_nll, double *mean_weights) {
+  return agp_logo_nll_gradient_typed(c, k, x, y, y_var, n_groups, offsets, indices, AGP_PREDICT_JOINT, n_slots, slots, tangents, ldt,
+                                     logo_nll, grad_logo_nll, mean_weights, nullptr);
+}
+
+int agp_logo_nll_gradient_typed(agp_context *c, const agp_kernel *k, const agp_features *x, const double *y, const double *y_var,
+                                int64_t n_groups, const int64_t *offsets, const int64_t *indices, int predict_type, int n_slots,
+                                const agp_gradient_slot *slots, const double *tangents, int64_t ldt, double *logo_nll,
+                                double *grad_logo_nll, double *mean_weights, double *group_nll) {
   if (!c || !k || !x || !y || !logo_nll) return AGP_ERR_INVALID_ARGUMENT;
+  if (predict_type != AGP_PREDICT_JOINT && predict_type != AGP_PREDICT_MARGINAL) return AGP_ERR_INVALID_ARGUMENT;
+  const bool marginal = predict_type == AGP_PREDICT_MARGINAL;
   if (n_slots < 0 || n_slots > AGP_MAX_GRADIENT_SLOTS || (n_slots > 0 && (!slots || !grad_logo_nll)))
     return AGP_ERR_INVALID_ARGUMENT;
   agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
@@ -904,7 +1000,7 @@ int agp_logo_nll_gradient(agp_context *c, const agp_kernel *k, const agp_feature
     AGP_HIP_CHECK(ctx, hipMemsetAsync(r.a, 0, sizeof(double) * (size_t)geo.np2, s));
     if (need_h) AGP_HIP_CHECK(ctx, hipMemsetAsync(g.R, 0, sizeof(double) * geo.slabs(), s));  // H over R
   }
-  for (const LogoChunk &ch : plan.chunks) logo_chunk(ctx, g, r, ch, need_c, need_h);
+  for (const LogoChunk &ch : plan.chunks) logo_chunk(ctx, g, r, ch, need_c, need_h, marginal);
   hipLaunchKernelGGL(logo_sum_kernel, dim3(1), dim3(1024), 0, s, r.term, plan.terms, ctx->d_scalars + 2);
   if (need_c) launch_symv_lower(s, g.A, g.lda, n, r.a, 1., 0., nullptr, r.u, r.symv);  // u = C a
   if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[5], s));
@@ -915,8 +1011,9 @@ int agp_logo_nll_gradient(agp_context *c, const agp_kernel *k, const agp_feature
     if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[7], s));
   }
   AGP_HIP_CHECK(ctx, hipGetLastError());
-  std::vector<double> h_grad((size_t)n_slots), h_u(mean_weights ? (size_t)n : 0);
+  std::vector<double> h_grad((size_t)n_slots), h_u(mean_weights ? (size_t)n : 0), h_term(group_nll ? (size_t)plan.terms : 0);
   AGP_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (!h_term.empty()) AGP_HIP_CHECK(ctx, hipMemcpyAsync(h_term.data(), r.term, sizeof(double) * h_term.size(), hipMemcpyDeviceToHost, s));
   AGP_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_scalars, ctx->d_scalars, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
   if (n_slots > 0) AGP_HIP_CHECK(ctx, hipMemcpyAsync(h_grad.data(), g.grad_d, sizeof(double) * (size_t)n_slots, hipMemcpyDeviceToHost, s));
   if (mean_weights) AGP_HIP_CHECK(ctx, hipMemcpyAsync(h_u.data(), r.u, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
@@ -925,6 +1022,10 @@ int agp_logo_nll_gradient(agp_context *c, const agp_kernel *k, const agp_feature
   *logo_nll = ctx->h_scalars[2];
   if (n_slots > 0) std::memcpy(grad_logo_nll, h_grad.data(), sizeof(double) * (size_t)n_slots);
   if (mean_weights) std::memcpy(mean_weights, h_u.data(), sizeof(double) * (size_t)n);
+  if (group_nll) {  // the terms are in the plan's order (by size) and hold 2 NLL_g; an empty group has none
+    std::fill(group_nll, group_nll + n_groups, 0.);
+    for (size_t q = 0; q < h_term.size(); ++q) group_nll[plan.group[q]] = 0.5 * h_term[q];
+  }
   if (prof) {
     // 2: alpha and R = L^-1; value only: 8 the group blocks and terms; otherwise 6 R^T R, 8 the mirror, the group blocks,
     // u and H, 9 the product, 7 the contraction

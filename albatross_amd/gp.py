@@ -1273,18 +1273,20 @@ class GaussianProcessRegression:
         values, grads = _leave_one_out_likelihood_gradients(models, [dataset] * len(models), "leave_one_out_likelihood_gradients")
         return np.asarray(values), grads
 
-    def leave_one_group_out_likelihood_gradient(self, dataset, grouper):
-        """(LeaveOneGroupOutLikelihood(grouper)(dataset, self), {name: d that / d name}) for every name of get_params(),
-        exact to fp64 rounding (agp_logo_nll_gradient).  grouper: what CrossValidation.predict accepts - a callable on a
-        feature, a LeaveOneOutGrouper or an indexer dict {key: [indices]}.  The value is the metric the tuner minimises,
-        sum_g NLL_g of the JOINT held-out prediction of each group scored against the group's targets with their variances
-        added (evaluation/model_metrics.hpp:74-93); the target variance is used twice, in the fit and in the score, as in
-        leave_one_out_likelihood_gradient, and priors are not included.  Parameters shared by several leaves are summed;
-        ScalingTerm parameters go through ScalingFunction.derivative, mean-function parameters through
-        -u^T d mu / d name (the entry's mean weights) with a central difference of the mean function on the host.
-        fp64 models only."""
+    def leave_one_group_out_likelihood_gradient(self, dataset, grouper, predict_type="joint"):
+        """(LeaveOneGroupOutLikelihood(grouper, predict_type)(dataset, self), {name: d that / d name}) for every name of
+        get_params(), exact to fp64 rounding (agp_logo_nll_gradient_typed).  grouper: what CrossValidation.predict accepts -
+        a callable on a feature, a LeaveOneOutGrouper or an indexer dict {key: [indices]}.  The value is the metric the
+        tuner minimises, sum_g NLL_g of the held-out prediction of each group scored against the group's targets with their
+        variances added (evaluation/model_metrics.hpp:74-93): predict_type "joint" scores against the group's full
+        predictive covariance, "marginal" against its diagonal only (prediction_metrics.hpp:112-128).  The target variance
+        is used twice, in the fit and in the score, as in leave_one_out_likelihood_gradient, and priors are not included.
+        Parameters shared by several leaves are summed; ScalingTerm parameters go through ScalingFunction.derivative,
+        mean-function parameters through -u^T d mu / d name (the entry's mean weights) with a central difference of the
+        mean function on the host.  fp64 models only."""
         if self.precision != "fp64":
             raise ValueError(f"leave_one_group_out_likelihood_gradient: fp64 models only, not {self.precision!r}")
+        ptype = _predict_type(predict_type)
         p = _gradient_problem(self, dataset, "agp_logo_nll_gradient")
         offsets, indices = _group_arrays(dataset, grouper, p.fs.n)
         ctx = self._ctx()
@@ -1293,10 +1295,10 @@ class GaussianProcessRegression:
         value = C.c_double()
         grad = np.zeros(len(p.slots))
         u = np.empty(n)
-        ctx._check(ctx._lib.agp_logo_nll_gradient(ctx._h, ctx.kernel(self.covariance_function_), C.byref(s), _ptr(p.y), _ptr(p.yv),
-                                                  len(offsets) - 1, _ptr(offsets), _ptr(indices), len(p.slots), p.table,
-                                                  _ptr(p.tangents), n, C.byref(value), _ptr(grad), _ptr(u)),
-                   "agp_logo_nll_gradient")
+        ctx._check(ctx._lib.agp_logo_nll_gradient_typed(ctx._h, ctx.kernel(self.covariance_function_), C.byref(s), _ptr(p.y), _ptr(p.yv),
+                                                        len(offsets) - 1, _ptr(offsets), _ptr(indices), ptype, len(p.slots), p.table,
+                                                        _ptr(p.tangents), n, C.byref(value), _ptr(grad), _ptr(u), None),
+                   "agp_logo_nll_gradient_typed")
         return value.value, self._leave_one_out_gradient_dict(p.slots, grad, u, p.fs)
 
     def _leave_one_out_gradient_dict(self, slots, grad_loo, u, fs):
@@ -1444,18 +1446,30 @@ def _group_arrays(dataset, grouper, n):
     return offsets, np.ascontiguousarray(indices, dtype=np.int64)
 
 
+_PREDICT_TYPES = {"joint": capi.PREDICT_JOINT, "marginal": capi.PREDICT_MARGINAL}
+
+
+def _predict_type(predict_type):
+    if predict_type not in _PREDICT_TYPES:
+        raise ValueError(f"predict_type: 'joint' or 'marginal', not {predict_type!r}")
+    return _PREDICT_TYPES[predict_type]
+
+
 class LeaveOneGroupOutLikelihood:
-    """LeaveOneGroupOutLikelihood<FeatureType>(grouper) (evaluation/model_metrics.hpp:74-93, PredictType =
-    JointDistribution): metric(dataset, model) = sum over the groups of the negative log-likelihood of the group's JOINT
-    held-out prediction, scored against the group's targets with their variances added (prediction_metrics.hpp:112-119).
-    No prior term.  grouper: a callable on a feature, a LeaveOneOutGrouper or an indexer dict.  One fit, R = L^-1 and the
-    group blocks from gathered columns of R (agp_logo_nll_gradient, value only);
-    model.leave_one_group_out_likelihood_gradient gives the gradient too."""
+    """LeaveOneGroupOutLikelihood<FeatureType, PredictType>(grouper) (evaluation/model_metrics.hpp:74-93):
+    metric(dataset, model) = sum over the groups of the negative log-likelihood of the group's held-out prediction, scored
+    against the group's targets with their variances added (prediction_metrics.hpp:112-128).  predict_type "joint" (the
+    reference's default) scores against the full predictive covariance of the group, "marginal" against its diagonal only:
+    the robust objective for large groups.  No prior term.  grouper: a callable on a feature, a LeaveOneOutGrouper or an
+    indexer dict.  One fit, R = L^-1 and the group blocks from gathered columns of R (agp_logo_nll_gradient_typed, value
+    only); group_scores gives the metric per group, model.leave_one_group_out_likelihood_gradient the gradient too."""
 
-    def __init__(self, grouper):
+    def __init__(self, grouper, predict_type="joint"):
         self.grouper_ = grouper
+        self.predict_type_ = predict_type
+        _predict_type(predict_type)
 
-    def __call__(self, dataset, model):
+    def _evaluate(self, dataset, model, per_group):
         if model.precision != "fp64":
             raise ValueError(f"LeaveOneGroupOutLikelihood: fp64 models only, not {model.precision!r}")
         if has_linear_combinations(dataset.features):
@@ -1464,13 +1478,25 @@ class LeaveOneGroupOutLikelihood:
         cov = model.covariance_function_
         fs = cov.features(_values_of(dataset.features))
         y, yv = model._targets(fs, dataset.targets)
-        offsets, indices = _group_arrays(dataset, self.grouper_, fs.n)
+        indexer = self.grouper_ if isinstance(self.grouper_, dict) else group_indexer(dataset.features, self.grouper_)
+        offsets, indices = _group_arrays(dataset, indexer, fs.n)
         s = fs.as_struct()
         out = C.c_double()
-        ctx._check(ctx._lib.agp_logo_nll_gradient(ctx._h, ctx.kernel(cov), C.byref(s), _ptr(y), _ptr(yv), len(offsets) - 1,
-                                                  _ptr(offsets), _ptr(indices), 0, None, None, 0, C.byref(out), None, None),
-                   "agp_logo_nll_gradient")
-        return out.value
+        terms = np.zeros(len(indexer)) if per_group else None
+        ctx._check(ctx._lib.agp_logo_nll_gradient_typed(ctx._h, ctx.kernel(cov), C.byref(s), _ptr(y), _ptr(yv), len(offsets) - 1,
+                                                        _ptr(offsets), _ptr(indices), _predict_type(self.predict_type_), 0, None, None,
+                                                        0, C.byref(out), None, None, _ptr(terms)),
+                   "agp_logo_nll_gradient_typed")
+        return out.value, indexer, terms
+
+    def __call__(self, dataset, model):
+        return self._evaluate(dataset, model, False)[0]
+
+    def group_scores(self, dataset, model):
+        """{group key: NLL_g} in indexer order (what cross_validated_scores returns for this metric, per group), from one
+        value-only call: the per-group terms the device sums for __call__"""
+        _, indexer, terms = self._evaluate(dataset, model, True)
+        return {key: float(v) for key, v in zip(indexer.keys(), terms)}
 
 
 def root_mean_square_error(prediction, truth):

@@ -384,7 +384,7 @@ AGP_API int agp_loo_nll_gradient_batch(agp_context *ctx, int count,
  * PredictType = JointDistribution (evaluation/model_metrics.hpp:74-93, without the prior term), and its exact gradient
  * with respect to covariance parameters: the objective to tune with when observations come in correlated bunches (one
  * group per station, pass or day), where a point's neighbours in its own group must not stay in the fit.  (PredictType =
- * MarginalDistribution scores the marginals only; that is a different formula and is not built.)
+ * MarginalDistribution scores the marginals only: agp_logo_nll_gradient_typed below.)
  * Groups as in agp_held_out_predictions: group g holds indices[offsets[g] .. offsets[g + 1]), offsets[0] = 0, host
  * arrays, indices in any order inside a group.  Empty groups contribute nothing; points in no group contribute no term.
  * With K = cov(x, x) + diag(y_var), C = K^-1, alpha = C y, s = y_var (0 if NULL), and per group with index set I (size m):
@@ -423,6 +423,40 @@ AGP_API int agp_logo_nll_gradient(agp_context *ctx, const agp_kernel *k, const a
                                   const double *tangents, int64_t ldt,
                                   double *logo_nll, double *grad_logo_nll,
                                   double *mean_weights);
+
+/* agp_logo_nll_gradient with the score's predict type as an argument, and the metric per group.
+ * predict_type = AGP_PREDICT_JOINT, group_nll = NULL is agp_logo_nll_gradient itself, bit for bit.
+ * predict_type = AGP_PREDICT_MARGINAL is LeaveOneGroupOutLikelihood<FeatureType, MarginalDistribution>: the second
+ * overload of NegativeLogLikelihood (prediction_metrics.hpp:112-128) scores a held-out group against the DIAGONAL of its
+ * predictive covariance only, the robust objective for large groups, whose joint score is dominated by the smallest
+ * eigenvalues of V.  With the notation of agp_logo_nll_gradient (A = C[I, I], Sigma = A^-1, d = Sigma alpha_I, s = y_var):
+ *   v_i = Sigma_ii + s_i   (i in I),
+ *   NLL_g = 1/2 sum_i (log v_i + d_i^2 / v_i + log 2 pi),   logo_nll = sum_g NLL_g,
+ *   q_i = d_i / v_i,   w_i = 1/2 (1 / v_i - q_i^2),   a_I = Sigma q,
+ *   B_g = Sigma diag(w) Sigma + 1/2 (a_I d^T + d a_I^T)   (m x m, symmetric),
+ * and B, u = C a, W = C B C - 1/2 (u alpha^T + alpha u^T), dlogo_nll / dtheta = sum_ij W_ij dK_ij / dtheta and the mean
+ * term -mean_weights^T dm / dtheta exactly as for the Joint type (which is the same expression with V^-1 in place of
+ * diag(1 / v)).  w_i < 0 whenever d_i^2 > v_i: B_g is indefinite in general and goes through the same general symmetric
+ * product.  With singleton groups both types are agp_loo_nll_gradient.
+ * Steps: the chain of agp_logo_nll_gradient up to Sigma_g; then per column d, v, q and the terms, and for the gradient
+ * a_I and the block product (Sigma diag(w)) Sigma^T in place of T^T T: no second LL^T and no second triangular solve;
+ * H, C B C and the contraction unchanged.  The value alone stops at the terms.  Same workspace.
+ * group_nll (host, n_groups values, or NULL; both predict types, value-only and gradient calls): group_nll[g] = NLL_g
+ * of group g in the CALLER's order (the device holds one term per non-empty group in its own order, by size; they are
+ * downloaded once and scattered back), 0 for an empty group; their sum is logo_nll up to rounding.
+ * An unknown predict_type: AGP_ERR_INVALID_ARGUMENT.  Every other argument, status code, location rule, the profiling
+ * stages and the determinism guarantee are those of agp_logo_nll_gradient; on any failure nothing is written, group_nll
+ * included.  (Marginal: only A_g is factored, so AGP_ERR_NOT_POSITIVE_DEFINITE refers to A_g.) */
+#define AGP_PREDICT_JOINT 0
+#define AGP_PREDICT_MARGINAL 1
+AGP_API int agp_logo_nll_gradient_typed(agp_context *ctx, const agp_kernel *k, const agp_features *x,
+                                        const double *y, const double *y_var,
+                                        int64_t n_groups, const int64_t *offsets, const int64_t *indices,
+                                        int predict_type,
+                                        int n_slots, const agp_gradient_slot *slots,
+                                        const double *tangents, int64_t ldt,
+                                        double *logo_nll, double *grad_logo_nll,
+                                        double *mean_weights, double *group_nll);
 
 /* Tuner objective batching: agp_nll for `count` parameter vectors of one model on one dataset in lock step
  * (batched Gram slabs + batched LL^T; blockIdx.y = parameter vector) — the evaluations that

@@ -1646,6 +1646,14 @@ namespace detail {
 template <typename FeatureType, typename Grouper>
 void group_arrays(const std::vector<FeatureType> &features, const Grouper &grouper, std::vector<std::int64_t> *offsets,
                   std::vector<std::int64_t> *indices);
+
+// the predict_type of agp_logo_nll_gradient_typed for NegativeLogLikelihood<PredictType> (prediction_metrics.hpp:112-128)
+template <typename PredictType>
+constexpr int predict_type_of() {
+  static_assert(std::is_same<PredictType, JointDistribution>::value || std::is_same<PredictType, MarginalDistribution>::value,
+                "PredictType: JointDistribution or MarginalDistribution");
+  return std::is_same<PredictType, MarginalDistribution>::value ? AGP_PREDICT_MARGINAL : AGP_PREDICT_JOINT;
+}
 }  // namespace detail
 
 template <typename CovFunc, typename MeanFunc = ZeroMean>
@@ -1993,12 +2001,15 @@ class GaussianProcessRegression {
     return loo;
   }
 
-  // LeaveOneGroupOutLikelihood<FeatureType>(grouper)(dataset, *this) (evaluation/model_metrics.hpp:74-93, Joint predict
-  // type, no prior term) and its exact gradient with respect to every name of get_params() (agp_logo_nll_gradient):
-  // sum_g NLL_g of the joint held-out prediction of each group, scored against the group's targets with their variances
-  // added.  grouper: what cross_validate().predict accepts - a callable on a feature, a LeaveOneOutGrouper or a
-  // GroupIndexer.  The target variance and the mean-function parameters as in leave_one_out_likelihood_gradient.
-  template <typename FeatureType, typename Grouper>
+  // LeaveOneGroupOutLikelihood<FeatureType, PredictType>(grouper)(dataset, *this) (evaluation/model_metrics.hpp:74-93, no
+  // prior term) and its exact gradient with respect to every name of get_params() (agp_logo_nll_gradient_typed):
+  // sum_g NLL_g of the held-out prediction of each group, scored against the group's targets with their variances added.
+  // PredictType = JointDistribution (the default) scores against the group's full predictive covariance,
+  // model.template leave_one_group_out_likelihood_gradient<MarginalDistribution>(...) against its diagonal only
+  // (prediction_metrics.hpp:112-128).  grouper: what cross_validate().predict accepts - a callable on a feature, a
+  // LeaveOneOutGrouper or a GroupIndexer.  The target variance and the mean-function parameters as in
+  // leave_one_out_likelihood_gradient.
+  template <typename PredictType = JointDistribution, typename FeatureType, typename Grouper>
   LeaveOneOutLikelihoodGradient leave_one_group_out_likelihood_gradient(const RegressionDataset<FeatureType> &dataset,
                                                                         const Grouper &grouper) const {
     std::vector<std::int64_t> offsets, indices;
@@ -2007,13 +2018,14 @@ class GaussianProcessRegression {
     const auto entry = [&](agp_context *c, const agp_kernel *k, const agp_features *x, const double *y, const double *y_var,
                            int n_slots, const agp_gradient_slot *slots, const double *tangents, std::int64_t ldt, double *value,
                            double *grad, double *weights) {
-      return agp_logo_nll_gradient(c, k, x, y, y_var, n_groups, offsets.data(), indices.data(), n_slots, slots, tangents, ldt, value,
-                                   grad, weights);
+      return agp_logo_nll_gradient_typed(c, k, x, y, y_var, n_groups, offsets.data(), indices.data(),
+                                         detail::predict_type_of<PredictType>(), n_slots, slots, tangents, ldt, value, grad, weights,
+                                         nullptr);
     };
     std::vector<std::string> names;
     std::vector<double> grad, u;
     const double *yvar = dataset.targets.covariance.empty() ? nullptr : dataset.targets.covariance.data();
-    const double logo = slot_gradient(entry, "agp_logo_nll_gradient", dataset, yvar, &names, &grad, &u);
+    const double logo = slot_gradient(entry, "agp_logo_nll_gradient_typed", dataset, yvar, &names, &grad, &u);
     LeaveOneOutLikelihoodGradient out{logo, {}};
     for (const auto &kv : get_params()) out.gradient[kv.first] = 0.;
     for (std::size_t s = 0; s < names.size(); ++s) out.gradient[names[s]] += grad[s];
@@ -2022,9 +2034,11 @@ class GaussianProcessRegression {
     return out;
   }
 
-  // the value alone (agp_logo_nll_gradient without slots: the group blocks from gathered columns of R, no K^-1)
-  template <typename FeatureType, typename Grouper>
-  double leave_one_group_out_likelihood(const RegressionDataset<FeatureType> &dataset, const Grouper &grouper) const {
+  // the value alone (agp_logo_nll_gradient_typed without slots: the group blocks from gathered columns of R, no K^-1);
+  // group_nll, if given, receives NLL_g of every group in key order (the vector cross_validated_scores returns)
+  template <typename PredictType = JointDistribution, typename FeatureType, typename Grouper>
+  double leave_one_group_out_likelihood(const RegressionDataset<FeatureType> &dataset, const Grouper &grouper,
+                                        std::vector<double> *group_nll = nullptr) const {
     std::vector<std::int64_t> offsets, indices;
     detail::group_arrays(dataset.features, grouper, &offsets, &indices);
     auto ctx = detail::default_context();
@@ -2032,10 +2046,12 @@ class GaussianProcessRegression {
     detail::Flat f = detail::flatten(covariance_function_, dataset.features);
     const Vector y = deviation(dataset);
     const double *yvar = dataset.targets.covariance.empty() ? nullptr : dataset.targets.covariance.data();
+    if (group_nll) group_nll->assign(offsets.size() - 1, 0.);
     double logo = 0.;
-    detail::check(agp_logo_nll_gradient(ctx->ctx, k.k, &f.view, y.data(), yvar, static_cast<std::int64_t>(offsets.size()) - 1,
-                                        offsets.data(), indices.data(), 0, nullptr, nullptr, 0, &logo, nullptr, nullptr),
-                  ctx->ctx, "agp_logo_nll_gradient");
+    detail::check(agp_logo_nll_gradient_typed(ctx->ctx, k.k, &f.view, y.data(), yvar, static_cast<std::int64_t>(offsets.size()) - 1,
+                                              offsets.data(), indices.data(), detail::predict_type_of<PredictType>(), 0, nullptr,
+                                              nullptr, 0, &logo, nullptr, nullptr, group_nll ? group_nll->data() : nullptr),
+                  ctx->ctx, "agp_logo_nll_gradient_typed");
     return logo;
   }
 
@@ -2887,32 +2903,44 @@ struct GaussianProcessNegativeLogLikelihood {
   }
 };
 
-// LeaveOneOutLikelihood<>, evaluation/model_metrics.hpp:59-72: the tuner's leave-one-out metric (no prior term)
-template <typename Unused = void>
+// LeaveOneOutLikelihood<PredictType>, evaluation/model_metrics.hpp:59-72: the tuner's leave-one-out metric (no prior
+// term).  A single point's joint and marginal scores are the same number, so PredictType only has to be one of the two.
+template <typename PredictType = JointDistribution>
 struct LeaveOneOutLikelihood {
   template <typename FeatureType, typename CovFunc, typename MeanFunc>
   double operator()(const RegressionDataset<FeatureType> &dataset,
                     const GaussianProcessRegression<CovFunc, MeanFunc> &model) const {
+    (void)detail::predict_type_of<PredictType>();
     return model.leave_one_out_likelihood(dataset);
   }
 };
 
-// LeaveOneGroupOutLikelihood<FeatureType>, evaluation/model_metrics.hpp:74-93: the tuner's metric for observations
-// that come in correlated groups (no prior term).  Only PredictType = JointDistribution, the reference's default, is
-// built: the Marginal predict type scores the held-out marginals, a different formula (out of scope).
+// LeaveOneGroupOutLikelihood<FeatureType, PredictType>, evaluation/model_metrics.hpp:74-93: the tuner's metric for
+// observations that come in correlated groups (no prior term).  PredictType = JointDistribution, the reference's default,
+// scores a held-out group against its full predictive covariance, MarginalDistribution against the diagonal only.
 template <typename FeatureType>
 using GroupFunction = std::string (*)(const FeatureType &);
 
 template <typename FeatureType, typename PredictType = JointDistribution>
 class LeaveOneGroupOutLikelihood {
-  static_assert(std::is_same<PredictType, JointDistribution>::value, "LeaveOneGroupOutLikelihood: the Joint predict type only");
-
  public:
   explicit LeaveOneGroupOutLikelihood(const GroupFunction<FeatureType> &grouper) : grouper_(grouper) {}
 
   template <typename CovFunc, typename MeanFunc>
   double operator()(const RegressionDataset<FeatureType> &dataset, const GaussianProcessRegression<CovFunc, MeanFunc> &model) const {
-    return model.leave_one_group_out_likelihood(dataset, grouper_);
+    return model.template leave_one_group_out_likelihood<PredictType>(dataset, grouper_);
+  }
+
+  // NLL_g per group key, in key order (cross_validated_scores of this metric), from the same single device call
+  template <typename CovFunc, typename MeanFunc>
+  std::map<std::string, double> group_scores(const RegressionDataset<FeatureType> &dataset,
+                                             const GaussianProcessRegression<CovFunc, MeanFunc> &model) const {
+    std::vector<double> terms;
+    model.template leave_one_group_out_likelihood<PredictType>(dataset, grouper_, &terms);
+    std::map<std::string, double> out;
+    std::size_t g = 0;
+    for (const auto &kv : group_indexer(dataset.features, grouper_)) out[kv.first] = terms[g++];
+    return out;
   }
 
  private:
