@@ -16,7 +16,7 @@ from .gp import (AlbatrossAmdError, DeviceJointDistribution, BlockSymmetric, Exp
                  RegressionDataset, ZeroMean, default_context, fit_batch, predict_batch, log_likelihood_gradient_batch,
                  leave_one_out_likelihood_gradient_batch, gp_from_covariance, gp_from_covariance_and_mean)
 
-from .sparse_gp import (FixedInducingPoints, SparseFitModel, SparseGaussianProcessRegression, SparseGPFit,
+from .sparse_gp import (FixedInducingPoints, SparseCrossValidation, SparseCrossValidationPrediction, SparseFitModel, SparseGaussianProcessRegression, SparseGPFit,
                         UniformlySpacedInducingPoints, rebase_inducing_points, sparse_gp_from_covariance,
                         sparse_gp_from_covariance_and_mean)
 

@@ -141,6 +141,8 @@ EXPORTS = [
     ("agp_sparse_nll", C.c_int, [_P, _P, C.POINTER(Features), C.c_int64, _P, _P, _P, C.POINTER(Features), C.c_double, C.c_double, _D]),
     ("agp_sparse_nll_gradient", C.c_int, [_P, _P, C.POINTER(Features), C.c_int64, _P, _P, _P, C.POINTER(Features), C.c_double, C.c_double,
                                           C.c_int, _P, _P, C.c_int64, _P, C.c_int64, _D, _P, _P, _P]),
+    ("agp_sparse_held_out", C.c_int, [_P, _P, C.POINTER(Features), C.c_int64, _P, _P, _P, C.POINTER(Features), C.c_double, C.c_double,
+                                      C.c_int, _P, _P, _P, _P, _P]),
     ("agp_sparse_predict_mean", C.c_int, [_P, _P, _P, C.POINTER(Features), _P, C.c_int]),
     ("agp_sparse_predict_marginal", C.c_int, [_P, _P, _P, C.POINTER(Features), _P, _P, C.c_int]),
     ("agp_sparse_predict_joint", C.c_int, [_P, _P, _P, C.POINTER(Features), _P, _P, C.c_int]),

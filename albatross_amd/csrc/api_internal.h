@@ -168,6 +168,33 @@ int fill_slot_group(const agp_kernel *k, int n_slots, const agp_gradient_slot *s
 // copied to *cursor with leading dimension round_up(n, 2) and the cursor moves past them, device ones are read in place
 int stage_tangents(agp_context *ctx, hipStream_t s, const double *tangents, long long ld, int location, long long n, int ntc,
                    double **cursor, const double **dev, long long *ld_dev);
+// ---- leave-one-group-out: the chunks of groups that advance in lock step (gradient.hip) --------------------------------
+// The non-empty groups sorted by size and cut into chunks: a chunk is padded to its largest group, which is at most twice
+// its smallest, holds at most max(n, m) padded columns (value only: the gathered columns of R fit the slab L leaves) and a
+// bounded volume of tile images.  Every chunk is ONE chain of batched launches (blockIdx.y = group), so the number of
+// chains follows the number of size classes (<= log2 n, plus the splits of a class too large for one chunk), not the
+// number of groups.  meta: per chunk idx[count * m] (-1 = padding) then sizes[count]; term_off: the chunk's first NLL term.
+struct LogoChunk {
+  long long m, count, idx_off, size_off, term_off;
+};
+struct LogoPlan {
+  std::vector<long long> meta;
+  std::vector<LogoChunk> chunks;
+  std::vector<long long> group;  // term q belongs to the caller's group group[q]
+  long long terms = 0;
+  size_t block_elems = 0, img_elems = 0, vec_elems = 0, count_elems = 0;
+};
+namespace agp {
+struct LogoRegions;  // batch_layout.h
+}
+long long logo_img_stride(long long m);
+// AGP_ERR_INVALID_ARGUMENT for malformed offsets, an index out of range, or an index that occurs twice (in one group or
+// in two); empty groups are dropped, points in no group are allowed
+int logo_plan(long long n, int64_t n_groups, const int64_t *offsets, const int64_t *indices, LogoPlan &p);
+// the halves of a chunk's value chain on either side of the sigma kernel, and the fixed-order sum of the terms
+void logo_chunk_sigma(agp_context_impl *ctx, const agp::LogoRegions &r, const LogoChunk &ch);
+void logo_chunk_terms(agp_context_impl *ctx, const agp::LogoRegions &r, const LogoChunk &ch, bool marginal);
+void launch_logo_sum(hipStream_t s, const double *term, long long count, double *out);
 namespace agp {
 // Gram + LL^T + forward substitution of y exactly as agp_nll makes them (api.hip: build_and_factor); on return the stream
 // is synchronised and ctx->h_flags / h_scalars hold the status and the log determinant

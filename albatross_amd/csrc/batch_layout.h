@@ -59,6 +59,44 @@ inline LogoRegions carve_logo(WsLayout &ws, const BatchGeometry &g, bool gradien
           ws.take<double>(symv_elems),  ws.take<long long>(meta_elems)};
 }
 
+// agp_sparse_held_out, the entry's one allocation beyond what the fit and the inverse blocks hold.  chain: the regions
+// the value chain of a chunk works in (S, a, u, symv: not used, nullptr); M: the chunk's slabs of M_g + nugget I; aw,
+// alpha: n-vectors in the grouped order; y, yvar, mean, variance: the same, each only where an output needs it; joint:
+// the concatenated blocks cov_g; joff: where each term's block starts in joint.
+struct SparseHeldOutRegions {
+  LogoRegions chain;
+  double *M, *aw, *alpha, *y, *yvar, *mean, *variance, *joint;
+  long long *joff;
+};
+inline SparseHeldOutRegions carve_sparse_held_out(WsLayout &ws, size_t np2, size_t block_elems, size_t img_elems, size_t vec_elems,
+                                                  size_t count_elems, size_t term_elems, size_t meta_elems, bool want_y,
+                                                  bool want_yvar, bool want_mean, bool want_variance, size_t joint_elems) {
+  SparseHeldOutRegions r;
+  LogoRegions &c = r.chain;
+  c.S = c.a = c.u = c.symv = nullptr;
+  c.X0 = ws.take<double>(block_elems);
+  c.X1 = ws.take<double>(block_elems);
+  c.X2 = ws.take<double>(block_elems);
+  r.M = ws.take<double>(block_elems);
+  c.img = ws.take<double>(img_elems);
+  c.d = ws.take<double>(vec_elems);
+  c.z = ws.take<double>(vec_elems);
+  c.a_pad = ws.take<double>(vec_elems);
+  c.logs_A = ws.take<double>(count_elems);
+  c.logs_V = ws.take<double>(count_elems);
+  c.term = ws.take<double>(term_elems);
+  r.aw = ws.take<double>(np2);
+  r.alpha = ws.take<double>(np2);
+  r.y = want_y ? ws.take<double>(np2) : nullptr;
+  r.yvar = want_yvar ? ws.take<double>(np2) : nullptr;
+  r.mean = want_mean ? ws.take<double>(np2) : nullptr;
+  r.variance = want_variance ? ws.take<double>(np2) : nullptr;
+  r.joint = joint_elems ? ws.take<double>(joint_elems) : nullptr;
+  c.meta = ws.take<long long>(meta_elems);
+  r.joff = joint_elems ? ws.take<long long>(term_elems) : nullptr;
+  return r;
+}
+
 // agp_nll_batch, ws_A.  yvar: one vector shared by all problems; zpub: the z slots of the fused panel launches
 struct NllBatchRegions {
   double *A, *invd, *ys, *yvar, *logsum, *quad, *zpub;

@@ -701,29 +701,12 @@ static void contract_slots(hipStream_t s, const agp_kernel *k, int n_slots, cons
   }
 }
 
-// ---- leave-one-group-out: the chunks of groups that advance in lock step ------------------------------------------
-// The non-empty groups sorted by size and cut into chunks: a chunk is padded to its largest group, which is at most twice
-// its smallest, holds at most max(n, m) padded columns (value only: the gathered columns of R fit the slab L leaves) and a
-// bounded volume of tile images.  Every chunk is ONE chain of batched launches (blockIdx.y = group), so the number of
-// chains follows the number of size classes (<= log2 n, plus the splits of a class too large for one chunk), not the
-// number of groups.  meta: per chunk idx[count * m] (-1 = padding) then sizes[count]; term_off: the chunk's first NLL term.
-struct LogoChunk {
-  long long m, count, idx_off, size_off, term_off;
-};
-struct LogoPlan {
-  std::vector<long long> meta;
-  std::vector<LogoChunk> chunks;
-  std::vector<long long> group;  // term q belongs to the caller's group group[q]
-  long long terms = 0;
-  size_t block_elems = 0, img_elems = 0, vec_elems = 0, count_elems = 0;
-};
+// ---- leave-one-group-out: the chunks of groups that advance in lock step (LogoChunk, LogoPlan: api_internal.h) --------
 constexpr long long LOGO_CHUNK_GROUPS_MAX = 16384;
 constexpr long long LOGO_CHUNK_IMG_ELEMS_MAX = 32ll << 20;  // 256 MiB of tile images per chunk
-static long long logo_img_stride(long long m) { return (m + NB - 1) / NB * (36ll * MB * MB); }
+long long logo_img_stride(long long m) { return (m + NB - 1) / NB * (36ll * MB * MB); }
 
-// AGP_ERR_INVALID_ARGUMENT for malformed offsets, an index out of range, or an index that occurs twice (in one group or
-// in two); empty groups are dropped, points in no group are allowed
-static int logo_plan(long long n, int64_t n_groups, const int64_t *offsets, const int64_t *indices, LogoPlan &p) {
+int logo_plan(long long n, int64_t n_groups, const int64_t *offsets, const int64_t *indices, LogoPlan &p) {
   if (n_groups < 0 || (n_groups > 0 && (!offsets || offsets[0] != 0))) return AGP_ERR_INVALID_ARGUMENT;
   std::vector<std::pair<long long, long long>> order;  // (size, group), non-empty groups
   for (int64_t g = 0; g < n_groups; ++g) {
@@ -775,6 +758,42 @@ static int logo_plan(long long n, int64_t n_groups, const int64_t *offsets, cons
   return AGP_OK;
 }
 
+// The two halves of a chunk's value chain that do not depend on where the blocks come from (logo_chunk below; the sparse
+// model's held-out groups, sparse_gradient.hip).  logo_chunk_sigma: X0 = [A_g 0; 0 I] -> L_A (logs_A), X1 = L_A^-1,
+// X2 = -Sigma_g = -X1^T X1.  The caller's sigma kernel then puts V_g into X0 and d into d / z (Joint), or the columns'
+// shares of 2 NLL_g into a_pad (Marginal).  logo_chunk_terms: Joint V_g = L_V L_V^T with z = L_V^-1 d riding along, then
+// term[g] = 2 NLL_g; Marginal: the sum of the shares.
+void logo_chunk_sigma(agp_context_impl *ctx, const LogoRegions &r, const LogoChunk &ch) {
+  hipStream_t s = ctx->stream;
+  const long long m = ch.m, count = ch.count;
+  const long long ldb = factor_ld(m), stride_B = ldb * m, stride_I = logo_img_stride(m);
+  const size_t slab_bytes = sizeof(double) * (size_t)stride_B * (size_t)count;
+  (void)hipMemsetAsync(r.logs_A, 0, sizeof(double) * (size_t)round_up(count, 2), s);
+  (void)hipMemsetAsync(r.logs_V, 0, sizeof(double) * (size_t)round_up(count, 2), s);
+  factor_lower_batched(s, r.X0, stride_B, m, ldb, r.img, stride_I, nullptr, 0, count, ctx->d_flags, r.logs_A);
+  launch_set_identity_batched(s, r.X1, ldb, stride_B, m, count);
+  forward_solve_mat_batched(s, r.X0, stride_B, m, ldb, r.img, stride_I, r.X1, stride_B, m, ldb, /*rhs_lower=*/true, count);
+  (void)hipMemsetAsync(r.X2, 0, slab_bytes, s);
+  launch_gemm_nt_sub_batched(s, r.X2, ldb, stride_B, r.X1, ldb, true, stride_B, r.X1, ldb, true, stride_B, m, m, m, false, count);  // -Sigma
+}
+
+void logo_chunk_terms(agp_context_impl *ctx, const LogoRegions &r, const LogoChunk &ch, bool marginal) {
+  hipStream_t s = ctx->stream;
+  const long long m = ch.m, count = ch.count;
+  const long long ldb = factor_ld(m), stride_B = ldb * m, stride_I = logo_img_stride(m);
+  const long long *sizes = r.meta + ch.size_off;
+  if (marginal) {
+    hipLaunchKernelGGL(logo_marginal_term_kernel, dim3((unsigned)count), dim3(256), 0, s, r.a_pad, m, sizes, r.term + ch.term_off);
+  } else {
+    factor_lower_batched(s, r.X0, stride_B, m, ldb, r.img, stride_I, r.z, m, count, ctx->d_flags, r.logs_V);
+    hipLaunchKernelGGL(logo_term_kernel, dim3((unsigned)count), dim3(256), 0, s, r.z, m, r.logs_V, sizes, r.term + ch.term_off);
+  }
+}
+
+void launch_logo_sum(hipStream_t s, const double *term, long long count, double *out) {
+  hipLaunchKernelGGL(logo_sum_kernel, dim3(1), dim3(1024), 0, s, term, count, out);
+}
+
 // One chunk through its chain.  X0 enters as [A_g 0; 0 I], A_g = C[I_g, I_g]: from the full C (gradient calls), or from
 // the gathered columns of R, A_g = R[:, I_g]^T R[:, I_g] (value only; the columns go where L was).  Then, all groups at
 // once: A_g = L_A L_A^T, Q = L_A^-1, Sigma_g = Q^T Q, d = Sigma alpha_I, V_g = Sigma_g + diag(s_I) = L_V L_V^T with
@@ -800,17 +819,11 @@ static void logo_chunk(agp_context_impl *ctx, const GradientCall &g, const LogoR
     launch_gemm_nt_sub_batched(s, r.X0, ldb, stride_B, g.A, g.lda, true, m * g.lda, g.A, g.lda, true, m * g.lda, m, m, n, false, count);
     hipLaunchKernelGGL(logo_fix_blocks_kernel, cols, dim3(256), 0, s, idx, m, r.X0, ldb, stride_B);
   }
-  (void)hipMemsetAsync(r.logs_A, 0, sizeof(double) * (size_t)round_up(count, 2), s);
-  (void)hipMemsetAsync(r.logs_V, 0, sizeof(double) * (size_t)round_up(count, 2), s);
-  factor_lower_batched(s, r.X0, stride_B, m, ldb, r.img, stride_I, nullptr, 0, count, ctx->d_flags, r.logs_A);
-  launch_set_identity_batched(s, r.X1, ldb, stride_B, m, count);
-  forward_solve_mat_batched(s, r.X0, stride_B, m, ldb, r.img, stride_I, r.X1, stride_B, m, ldb, /*rhs_lower=*/true, count);
-  (void)hipMemsetAsync(r.X2, 0, slab_bytes, s);
-  launch_gemm_nt_sub_batched(s, r.X2, ldb, stride_B, r.X1, ldb, true, stride_B, r.X1, ldb, true, stride_B, m, m, m, false, count);  // -Sigma
+  logo_chunk_sigma(ctx, r, ch);
   if (marginal) {
     hipLaunchKernelGGL(logo_marginal_sigma_kernel, cols, dim3(256), 0, s, r.X2, idx, m, ldb, stride_B, g.z, g.yvar_d,
                        need_c ? r.X0 : nullptr, need_c ? r.X1 : nullptr, r.d, r.z, r.a_pad);
-    hipLaunchKernelGGL(logo_marginal_term_kernel, dim3((unsigned)count), dim3(256), 0, s, r.a_pad, m, sizes, r.term + ch.term_off);
+    logo_chunk_terms(ctx, r, ch, true);
     if (!need_c) return;
     launch_colvec_dot_batched(s, r.X0, ldb, stride_B, m, r.z, m, count, r.a_pad);  // a_I = Sigma q (Sigma symmetric)
     (void)hipMemsetAsync(r.X2, 0, slab_bytes, s);
@@ -819,8 +832,7 @@ static void logo_chunk(agp_context_impl *ctx, const GradientCall &g, const LogoR
   } else {
     hipLaunchKernelGGL(logo_sigma_kernel, cols, dim3(256), 0, s, r.X2, idx, m, ldb, stride_B, g.z, g.yvar_d, r.X0, need_c ? r.X1 : nullptr,
                        r.d, r.z);
-    factor_lower_batched(s, r.X0, stride_B, m, ldb, r.img, stride_I, r.z, m, count, ctx->d_flags, r.logs_V);
-    hipLaunchKernelGGL(logo_term_kernel, dim3((unsigned)count), dim3(256), 0, s, r.z, m, r.logs_V, sizes, r.term + ch.term_off);
+    logo_chunk_terms(ctx, r, ch, false);
     if (!need_c) return;
     forward_solve_mat_batched(s, r.X0, stride_B, m, ldb, r.img, stride_I, r.X1, stride_B, m, ldb, /*rhs_lower=*/false, count);  // T
     launch_colvec_dot_batched(s, r.X1, ldb, stride_B, m, r.z, m, count, r.a_pad);
@@ -1001,7 +1013,7 @@ int agp_logo_nll_gradient_typed(agp_context *c, const agp_kernel *k, const agp_f
     if (need_h) AGP_HIP_CHECK(ctx, hipMemsetAsync(g.R, 0, sizeof(double) * geo.slabs(), s));  // H over R
   }
   for (const LogoChunk &ch : plan.chunks) logo_chunk(ctx, g, r, ch, need_c, need_h, marginal);
-  hipLaunchKernelGGL(logo_sum_kernel, dim3(1), dim3(1024), 0, s, r.term, plan.terms, ctx->d_scalars + 2);
+  launch_logo_sum(s, r.term, plan.terms, ctx->d_scalars + 2);
   if (need_c) launch_symv_lower(s, g.A, g.lda, n, r.a, 1., 0., nullptr, r.u, r.symv);  // u = C a
   if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[5], s));
   if (need_h) {

@@ -1,5 +1,5 @@
-// sparse_internal.h — what sparse_api.hip (the fit) shares with sparse_gradient.hip (its gradient).  Not part of the
-// public interface.
+// sparse_internal.h — what sparse_api.hip (the fit) shares with sparse_gradient.hip (its gradient and the
+// held-out predictions of its groups).  Not part of the public interface.
 #pragma once
 #include <chrono>
 #include <cstdio>

@@ -16,8 +16,8 @@ import numpy as np
 
 from . import _capi as capi
 from .covariance import CovarianceFunction, Measurement
-from .gp import (JointDistribution, MarginalDistribution, Prediction, RegressionDataset, ZeroMean, _ptr, _values_of,
-                 default_context)
+from .gp import (JointDistribution, MarginalDistribution, Prediction, RegressionDataset, ZeroMean, _predict_type, _ptr,
+                 _values_of, default_context, group_indexer)
 
 DEFAULT_NUGGET = 1e-8  # details::DEFAULT_NUGGET (:22)
 
@@ -193,6 +193,10 @@ class SparseGaussianProcessRegression:
 
     def _group(self, dataset):
         """group_by(features, grouper).indexers() in key order, reordered_inds, subset of features / targets."""
+        return self._group_keys(dataset)[:4]
+
+    def _group_keys(self, dataset):
+        """_group plus the sorted group keys and reordered_inds (position in grouped order -> index in the dataset)."""
         feats = _values_of(dataset.features)
         n = len(feats)
         grouper = self.independent_group_function_
@@ -209,6 +213,7 @@ class SparseGaussianProcessRegression:
             order = np.argsort(inverse, kind="stable").astype(np.int64)
             offsets = np.zeros(len(uniq) + 1, dtype=np.int64)
             offsets[1:] = np.cumsum(np.bincount(inverse, minlength=len(uniq)))
+            keys = [k.item() if hasattr(k, "item") else k for k in uniq]
         else:
             groups = {}
             for i in range(n):
@@ -222,7 +227,7 @@ class SparseGaussianProcessRegression:
         yv = None
         if dataset.targets.covariance is not None:
             yv = np.ascontiguousarray(np.asarray(dataset.targets.covariance, dtype=np.float64)[order])
-        return reordered, offsets, y, yv
+        return reordered, offsets, y, yv, keys, order
 
     def _create(self, dataset, want_fit, comm=None):
         ctx = self._ctx()
@@ -295,6 +300,69 @@ class SparseGaussianProcessRegression:
         grad["inducing_nugget"] = -grad_nuggets[1]
         return -nll.value, grad
 
+    # ---- leave-one-group-out cross validation from one fit (agp_sparse_held_out) ----------------------------------
+    def _held_out(self, dataset, predict_type="joint", value=False, terms=False, mean=False, variance=False, joint=False):
+        """One call of agp_sparse_held_out for the model's own groups.  Returns a dict with the sorted group keys, the
+        offsets of the groups in grouped order, reordered_inds and whichever outputs were asked for.  The inducing points
+        are those the strategy gives for the FULL data set and are held fixed while each group is left out: with
+        FixedInducingPoints this equals refitting without the group, with a data-dependent strategy it is the
+        fixed-inducing-point approximation of it."""
+        ptype = _predict_type(predict_type)
+        ctx, cov = self._ctx(), self.covariance_function_
+        reordered, offsets, y, yv, keys, order = self._group_keys(dataset)
+        u = self.inducing_point_strategy_(cov, _values_of(dataset.features))
+        if len(u) == 0:
+            raise ValueError("Empty inducing points!")
+        fx, fu = cov.features(reordered), cov.features(u)
+        sx, su = fx.as_struct(), fu.as_struct()
+        sizes = np.diff(offsets)
+        out = {"keys": keys, "offsets": offsets, "order": order, "features": fx}
+        nll = C.c_double()
+        t = np.empty(len(sizes)) if terms else None
+        mu = np.empty(fx.n) if mean else None
+        var = np.empty(fx.n) if variance else None
+        jt = np.empty(int(np.sum(sizes * sizes))) if joint else None
+        ctx._check(ctx._lib.agp_sparse_held_out(ctx._h, ctx.kernel(cov), C.byref(sx), len(sizes), _ptr(offsets), _ptr(y), _ptr(yv),
+                                                C.byref(su), self.measurement_nugget_, self.inducing_nugget_, ptype,
+                                                C.byref(nll) if value else None, _ptr(t), _ptr(mu), _ptr(var), _ptr(jt)),
+                   "agp_sparse_held_out")
+        out.update(value=nll.value if value else None, terms=t, variance=var, joint=jt)
+        out["mean"] = None if mu is None else mu + self.mean_function_(fx.coords)  # mean_function_.add_to (:457,473,516)
+        return out
+
+    def held_out_predictions(self, dataset):
+        """{group key: JointDistribution}: for every group of the model's grouper, the prediction of the group by the model
+        fitted to all the other groups (what cross_validate() gives through refits in the reference: fit(rest).predict(x_g)
+        at the plain features of g, the mean function added back), from ONE fit.  The inducing points are those of the full
+        data set and are held fixed (see _held_out)."""
+        r = self._held_out(dataset, mean=True, joint=True)
+        out, at = {}, 0
+        for g, key in enumerate(r["keys"]):
+            lo, hi = int(r["offsets"][g]), int(r["offsets"][g + 1])
+            sz = hi - lo
+            out[key] = JointDistribution(r["mean"][lo:hi], r["joint"][at:at + sz * sz].reshape(sz, sz, order="F"))
+            at += sz * sz
+        return out
+
+    def cross_validate(self):
+        """model.cross_validate() (core/model.hpp:154-156) for the model's own grouper: the surface of the dense
+        CrossValidation, served by held_out_predictions instead of one refit per group."""
+        return SparseCrossValidation(self)
+
+    def leave_one_group_out_likelihood(self, dataset, predict_type="joint"):
+        """LeaveOneGroupOutLikelihood(model's grouper, predict_type)(dataset, model) (evaluation/model_metrics.hpp:74-93):
+        sum over the groups of the negative log-likelihood of the group's held-out prediction against the group's targets
+        with their variances added; "joint" scores against the full predictive covariance of the group, "marginal" against
+        its diagonal (prediction_metrics.hpp:112-128).  No prior term.  Like log_likelihood it is evaluated on the targets
+        as given (the fit keeps y from before mean_function_.remove_from, :664-668).  The inducing points are those of the
+        full data set and are held fixed (see _held_out)."""
+        return self._held_out(dataset, predict_type, value=True)["value"]
+
+    def group_scores(self, dataset, predict_type="joint"):
+        """{group key: NLL_g}, in key order: the terms leave_one_group_out_likelihood sums."""
+        r = self._held_out(dataset, predict_type, terms=True)
+        return dict(zip(r["keys"], r["terms"].tolist()))
+
     def fit_from_prediction(self, new_inducing_points, prediction):
         """fit_from_prediction (:406-461): the fit on `new_inducing_points` that reproduces `prediction`, a
         JointDistribution made AT those points.  Like the reference, the mean is used as given (the mean function is not
@@ -311,6 +379,103 @@ class SparseGaussianProcessRegression:
                                                            fz.n, capi.HOST, self.inducing_nugget_, C.byref(h), None, None),
                    "agp_sparse_fit_from_prediction")
         return SparseFitModel(self, SparseGPFit(ctx, h, new_inducing_points, float("nan")))
+
+
+class SparseCrossValidationPrediction:
+    """CrossValidationPrediction (gp.py) for a sparse model and its own groups: means() / marginals() / joints() come from
+    ONE fit (agp_sparse_held_out), predictions() is the generic refit-per-fold path."""
+
+    def __init__(self, model, dataset, indexer):
+        self.model_, self.dataset_, self.indexer_ = model, dataset, indexer
+        self._cache = {}
+
+    def _held_out(self, joint):
+        if joint not in self._cache:
+            m = self.model_
+            r = m._held_out(self.dataset_, mean=True, variance=not joint, joint=joint)
+            out, at = {}, 0
+            for g, key in enumerate(r["keys"]):
+                lo, hi = int(r["offsets"][g]), int(r["offsets"][g + 1])
+                sz = hi - lo
+                if joint:
+                    out[key] = JointDistribution(r["mean"][lo:hi], r["joint"][at:at + sz * sz].reshape(sz, sz, order="F"))
+                else:
+                    out[key] = MarginalDistribution(r["mean"][lo:hi], r["variance"][lo:hi])
+                at += sz * sz
+            self._cache[joint] = out
+        return self._cache[joint]
+
+    def predictions(self):
+        """predict_fold for every group: fit on the rest, predict the group (cross_validation.hpp:20-43).  The inducing
+        point strategy sees only the rest."""
+        feats = _values_of(self.dataset_.features)
+        y, yv = self.dataset_.targets.mean, self.dataset_.targets.covariance
+        n = len(feats)
+        out = {}
+        for key, idx in self.indexer_.items():
+            held = np.zeros(n, dtype=bool)
+            held[np.asarray(idx)] = True
+            train = np.nonzero(~held)[0]
+            tr_feats = [feats[i] for i in train] if isinstance(feats, list) else feats[train]
+            te_feats = [feats[i] for i in idx] if isinstance(feats, list) else feats[np.asarray(idx)]
+            targets = MarginalDistribution(y[train], None if yv is None else yv[train])
+            out[key] = self.model_.fit(RegressionDataset(tr_feats, targets)).predict(te_feats)
+        return out
+
+    def means(self):
+        return {k: p.mean for k, p in self._held_out(False).items()}
+
+    def marginals(self):
+        return self._held_out(False)
+
+    def joints(self):
+        return self._held_out(True)
+
+    def _concatenate(self, per_group):
+        out = np.empty(self.dataset_.size())
+        for key, idx in self.indexer_.items():
+            out[np.asarray(idx)] = per_group[key]
+        return out
+
+    def mean(self):
+        """concatenate_mean_predictions: group results scattered back to dataset order."""
+        return self._concatenate(self.means())
+
+    def marginal(self):
+        m = self.marginals()
+        return MarginalDistribution(self._concatenate({k: p.mean for k, p in m.items()}),
+                                    self._concatenate({k: p.covariance for k, p in m.items()}))
+
+
+class SparseCrossValidation:
+    """model.cross_validate() of a sparse model.  The held-out groups are the groups of the fit - the model's own grouper:
+    leaving out anything else would cut through the blocks of A, and the one-fit identity (Kt without the group's rows and
+    columns) no longer holds.  grouper may be omitted, the model's grouper, or anything that gives the same groups under the
+    same keys; any other grouper raises ValueError."""
+
+    def __init__(self, model):
+        self.model_ = model
+
+    def predict(self, dataset, grouper=None):
+        _, offsets, _, _, keys, order = self.model_._group_keys(dataset)
+        own = {k: order[offsets[g]:offsets[g + 1]].tolist() for g, k in enumerate(keys)}
+        if grouper is not None and grouper is not self.model_.independent_group_function_:
+            other = grouper if isinstance(grouper, dict) else group_indexer(dataset.features, grouper)
+            if {k: sorted(int(i) for i in v) for k, v in other.items()} != {k: sorted(v) for k, v in own.items()}:
+                raise ValueError("a sparse model cross-validates over its own groups only: the held-out predictions come "
+                                 "from the one fit whose independent blocks are those groups, and this grouper groups the "
+                                 "data differently (refit per fold for it: fit(rest).predict(group))")
+        return SparseCrossValidationPrediction(self.model_, dataset, own)
+
+    def predictions(self, dataset, grouper=None):
+        return self.predict(dataset, grouper).predictions()
+
+    def scores(self, metric, dataset, grouper=None):
+        """cross_validated_scores: metric(prediction of the group, truth of the group) per group."""
+        pred = self.predict(dataset, grouper)
+        marg = pred.marginals()
+        y = dataset.targets.mean
+        return np.array([metric(marg[k], MarginalDistribution(y[np.asarray(idx)])) for k, idx in pred.indexer_.items()])
 
 
 def rebase_inducing_points(fit_model, new_inducing_points):

@@ -303,6 +303,25 @@ void layouts_under_sanitizers() {
                                        {r.z, D * vec}, {r.a_pad, D * vec}, {r.logs_A, D * cnt}, {r.logs_V, D * cnt}, {r.term, D * terms},
                                        {r.a, D * np2}, {r.u, D * np2}, {r.symv, D * symv}, {r.meta, sizeof(long long) * meta}};
           });
+          // agp_sparse_held_out's one allocation: every combination of the optional outputs (has_var: target variances
+          // given; fused: mean and variance asked for; slab: joint asked for)
+          const bool want_mean = fused != 0, want_var = fused != 0, want_yvar = has_var != 0 && (want_var || slab);
+          const size_t jnt = slab ? 3 * np2 + 1 : 0;
+          check_layout("carve_sparse_held_out",
+                       4 * blk + img + 3 * vec + 2 * cnt + terms + 2 * np2 + ((want_mean ? 2 : 0) + (want_yvar ? 1 : 0) + (want_var ? 1 : 0)) * np2 +
+                           jnt + meta + (slab ? terms : 0),
+                       [&](agp::WsLayout &w) {
+                         const agp::SparseHeldOutRegions r =
+                             agp::carve_sparse_held_out(w, np2, blk, img, vec, cnt, terms, meta, want_mean, want_yvar, want_mean, want_var, jnt);
+                         const agp::LogoRegions &c = r.chain;
+                         require(!c.S && !c.a && !c.u && !c.symv, "carve_sparse_held_out: regions of the dense entry");
+                         require((r.y != nullptr) == (want_mean && w.base) && (r.joint != nullptr) == (slab && w.base), "carve_sparse_held_out: options");
+                         return std::vector<Region>{{c.X0, D * blk}, {c.X1, D * blk}, {c.X2, D * blk}, {r.M, D * blk}, {c.img, D * img}, {c.d, D * vec},
+                                                    {c.z, D * vec}, {c.a_pad, D * vec}, {c.logs_A, D * cnt}, {c.logs_V, D * cnt}, {c.term, D * terms},
+                                                    {r.aw, D * np2}, {r.alpha, D * np2}, {r.y, D * np2}, {r.yvar, D * np2}, {r.mean, D * np2},
+                                                    {r.variance, D * np2}, {r.joint, D * jnt}, {c.meta, sizeof(long long) * meta},
+                                                    {r.joff, sizeof(long long) * terms}};
+                       });
         }
       }
 }

@@ -760,6 +760,49 @@ AGP_API int agp_sparse_nll_gradient(agp_context *ctx, const agp_kernel *kernel, 
                             int n_slots, const agp_gradient_slot *slots,
                             const double *tangents_x, int64_t ldtx, const double *tangents_u, int64_t ldtu,
                             double *nll, double *grad_nll, double *grad_nuggets, double *alpha);
+/* Leave-one-group-out cross validation of the sparse model from ONE fit: for every group g of the fit, the prediction of
+ * g by the model fitted to all the OTHER groups (cross_validate() / LeaveOneGroupOutLikelihood through refits,
+ * evaluation/cross_validation.hpp, model_metrics.hpp:74-93, with _predict_impl :447-521 at the plain features of g), and its
+ * negative log-likelihood against the group's targets with their variances added (prediction_metrics.hpp:112-128).
+ * Arguments up to inducing_nugget exactly as agp_sparse_nll; the held-out groups are the fit's own, offsets[g] ..
+ * offsets[g + 1].  The inducing points u are those of the call and are held fixed.
+ *
+ * With D, Kt as above (agp_sparse_nll_gradient), B_g = (Kt^-1)[g, g], Sigma_g = B_g^-1, alpha = Kt^-1 y: dropping group g
+ * from a PITC model leaves exactly Kt without g's rows and columns, so
+ *   d_g    = Sigma_g alpha_g                       (truth minus held-out mean)
+ *   mean_g = y_g - d_g
+ *   cov_g  = Sigma_g - D_g - M_g,   M_g = k(Measurement x_g, Measurement x_g) - k(x_g, x_g)
+ *   V_g    = cov_g + diag(y_var_g) = Sigma_g - measurement_nugget I - M_g
+ *   AGP_PREDICT_JOINT:    NLL_g = 1/2 (log|V_g| + d_g^T V_g^-1 d_g + |g| log 2 pi)
+ *   AGP_PREDICT_MARGINAL: NLL_g = 1/2 sum_c (log v_c + d_c^2 / v_c + log 2 pi),   v_c = (V_g)_cc
+ * M_g is the part of the covariance function that only measurements carry: the fit builds its blocks from measurement
+ * features, a prediction is made at plain ones.  No prior term.  (The dense agp_logo_nll_gradient keeps the fit's noise in
+ * the held-out covariance as the reference's dense fast path does; the sparse model has no fast path there, the refit is
+ * the definition.)
+ *
+ * Outputs, each may be NULL: logo_nll (host, 1 value: sum_g NLL_g), group_nll (host, n_groups values in the caller's
+ * order), and at x->location mean and variance (n values, the caller's grouped order; variance = diag(cov_g)) and joint
+ * (the column-major |g| x |g| blocks cov_g one after the other, sum_g |g|^2 values, as agp_held_out_predictions).
+ *
+ * Stages: the fit; R_g, alpha, Z, N_g and B_g = R_g^T R_g - N_g^T N_g exactly as agp_sparse_nll_gradient forms them (the
+ * same function; nothing after them - no E^T, no Lacc^-T solves, no W_uu); then per chunk of groups of similar size, in
+ * lock step: B_g = L L^T, Q = L^-1, Sigma_g = Q^T Q, M_g pair by pair, V_g, (Joint) V_g = L_V L_V^T with d riding along,
+ * the terms, and one fixed-order sum.
+ * Work beyond the fit: ~2 n m^2 + 4 n s m + 3 n s^2 flop for groups of s, and 2 n s evaluations of the covariance
+ * function.  Workspace: the fit's pool plus ONE more ldk x n slab, 2 n s doubles of group slabs, four padded block slabs
+ * of the largest chunk (at most 4 x 2 n s doubles), O(n) vectors, and sum_g |g|^2 doubles when joint is asked for.
+ * No float atomics, fixed-order reductions: two identical calls give bit-identical results.
+ *
+ * Status: malformed offsets (offsets[0] != 0, offsets[n_groups] != n, an empty group), n_groups <= 0 or an unknown
+ * predict_type: AGP_ERR_INVALID_ARGUMENT, nothing is written.  LL^T / CholeskyQR2 path only: where agp_sparse_fit_create
+ * would fall back to the pivoted path, AGP_ERR_NOT_POSITIVE_DEFINITE.  NaN input and a block of A that is not positive
+ * definite: status as agp_sparse_nll.  A B_g or (Joint) a V_g that is not positive definite:
+ * AGP_ERR_NOT_POSITIVE_DEFINITE.  Every failure after the argument checks writes NaN to all outputs.
+ * AGP_SPARSE_TIMING=1 prints the stages after the fit's. */
+AGP_API int agp_sparse_held_out(agp_context *ctx, const agp_kernel *kernel, const agp_features *x, int64_t n_groups,
+                        const int64_t *offsets, const double *y, const double *y_var, const agp_features *u,
+                        double measurement_nugget, double inducing_nugget, int predict_type,
+                        double *logo_nll, double *group_nll, double *mean, double *variance, double *joint);
 /* _predict_impl (:447-521): mean = K_*u v; covariance = K_** - Q_** + K_*u Sigma K_u*.  The mean
  * function is the caller's (mean_function_.add_to). */
 AGP_API int agp_sparse_predict_mean(agp_context *ctx, const agp_kernel *kernel, const agp_sparse_fit *fit,

@@ -28,6 +28,7 @@
 #include <functional>
 #include <limits>
 #include <map>
+#include <set>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -2746,6 +2747,77 @@ class SparseGaussianProcessRegression {
     return out;
   }
 
+  // ---- leave-one-group-out cross validation from ONE fit (agp_sparse_held_out) -------------------------------------
+  // For every group of the model's grouper: the prediction of the group by the model fitted to all the OTHER groups -
+  // what cross_validate() / LeaveOneGroupOutLikelihood give through refits in the reference (evaluation/
+  // cross_validation.hpp, model_metrics.hpp:74-93), fit(rest).predict(x_g) at the plain features of g.  The inducing
+  // points are those the strategy gives for the FULL data set and are held fixed while a group is left out: with fixed
+  // inducing points this equals refitting, with a data-dependent strategy it is the fixed-inducing-point approximation
+  // of it.  The held-out groups are the fit's own; there is no one-fit identity for any other grouping.
+
+  // {group key: held-out JointDistribution}, the mean function added back
+  template <typename FeatureType>
+  auto held_out_predictions(const RegressionDataset<FeatureType> &dataset) const {
+    using Key = typename std::decay<decltype(independent_group_function_(dataset.features[0]))>::type;
+    const Grouped<FeatureType> grouped = group(dataset);
+    const std::size_t n = grouped.features.size();
+    std::size_t joint_total = 0;
+    for (std::size_t g = 0; g + 1 < grouped.offsets.size(); ++g) {
+      const std::size_t sz = static_cast<std::size_t>(grouped.offsets[g + 1] - grouped.offsets[g]);
+      joint_total += sz * sz;
+    }
+    Vector mean(n);
+    std::vector<double> joint(joint_total);
+    held_out_call(dataset, grouped, AGP_PREDICT_JOINT, nullptr, nullptr, mean.data(), joint.data());
+    add_mean(grouped.features, &mean);  // mean_function_.add_to (:457,473,516)
+    std::map<Key, JointDistribution> out;
+    std::size_t at = 0, g = 0;
+    for (const Key &key : group_keys(dataset)) {
+      const std::int64_t lo = grouped.offsets[g], sz = grouped.offsets[g + 1] - lo;
+      JointDistribution d;
+      d.mean.resize(static_cast<std::size_t>(sz));
+      d.covariance = Matrix(sz, sz);
+      for (std::int64_t i = 0; i < sz; ++i) d.mean[static_cast<std::size_t>(i)] = mean[static_cast<std::size_t>(lo + i)];
+      std::copy(joint.begin() + static_cast<std::ptrdiff_t>(at), joint.begin() + static_cast<std::ptrdiff_t>(at + sz * sz),
+                d.covariance.data.begin());
+      out.emplace(key, std::move(d));
+      at += static_cast<std::size_t>(sz * sz);
+      ++g;
+    }
+    return out;
+  }
+
+  // LeaveOneGroupOutLikelihood<FeatureType, PredictType>(the model's grouper)(dataset, *this): sum over the groups of the
+  // negative log-likelihood of the group's held-out prediction against the group's targets with their variances added.
+  // PredictType = JointDistribution scores against the group's full predictive covariance, MarginalDistribution against
+  // its diagonal (prediction_metrics.hpp:112-128).  No prior term; like log_likelihood it is evaluated on the targets as
+  // given.  terms (optional): NLL_g per group key.
+  template <typename PredictType = JointDistribution, typename FeatureType>
+  double leave_one_group_out_likelihood(
+      const RegressionDataset<FeatureType> &dataset,
+      std::map<typename std::decay<decltype(std::declval<GrouperFunction>()(std::declval<FeatureType>()))>::type, double> *terms =
+          nullptr) const {
+    const Grouped<FeatureType> grouped = group(dataset);
+    std::vector<double> per_group(terms ? grouped.offsets.size() - 1 : 0);
+    double value = 0.;
+    held_out_call(dataset, grouped, detail::predict_type_of<PredictType>(), &value, terms ? per_group.data() : nullptr, nullptr,
+                  nullptr);
+    if (terms) {
+      terms->clear();
+      std::size_t g = 0;
+      for (const auto &key : group_keys(dataset)) terms->emplace(key, per_group[g++]);
+    }
+    return value;
+  }
+
+  // {group key: NLL_g}: the terms leave_one_group_out_likelihood<PredictType> sums
+  template <typename PredictType = JointDistribution, typename FeatureType>
+  auto group_scores(const RegressionDataset<FeatureType> &dataset) const {
+    std::map<typename std::decay<decltype(independent_group_function_(dataset.features[0]))>::type, double> terms;
+    leave_one_group_out_likelihood<PredictType>(dataset, &terms);
+    return terms;
+  }
+
   // fit_from_prediction (:406-461): the fit on `new_inducing_points` that reproduces `prediction`, a joint distribution
   // made AT those points.  Like the reference, the mean is used as given (the mean function is not removed from it).
   template <typename FeatureType>
@@ -2809,6 +2881,29 @@ class SparseGaussianProcessRegression {
   }
 
  private:
+  // the group keys in the order of Grouped::offsets (std::map order)
+  template <typename FeatureType>
+  auto group_keys(const RegressionDataset<FeatureType> &dataset) const {
+    using Key = typename std::decay<decltype(independent_group_function_(dataset.features[0]))>::type;
+    std::set<Key> keys;
+    for (const auto &f : dataset.features) keys.insert(independent_group_function_(f));
+    return keys;
+  }
+  template <typename FeatureType>
+  void held_out_call(const RegressionDataset<FeatureType> &dataset, const Grouped<FeatureType> &grouped, int predict_type,
+                     double *value, double *terms, double *mean, double *joint) const {
+    const auto u = inducing_point_strategy_(covariance_function_, dataset.features);
+    if (u.empty()) throw std::invalid_argument("Empty inducing points!");  // :361
+    auto ctx = detail::default_context();
+    detail::KernelHolder k(covariance_function_.program());
+    detail::Flat fx = detail::flatten(covariance_function_, grouped.features);
+    detail::Flat fu = detail::flatten(covariance_function_, u);
+    detail::check(agp_sparse_held_out(ctx->ctx, k.k, &fx.view, static_cast<std::int64_t>(grouped.offsets.size() - 1),
+                                      grouped.offsets.data(), grouped.y.data(), grouped.yv.empty() ? nullptr : grouped.yv.data(),
+                                      &fu.view, measurement_nugget_, inducing_nugget_, predict_type, value, terms, mean, nullptr,
+                                      joint),
+                  ctx->ctx, "agp_sparse_held_out");
+  }
   template <typename FeatureType, typename U>
   void run(const RegressionDataset<FeatureType> &dataset, SparseGPFit<U> *fit, bool keep, const Communicator *comm = nullptr) const {
     const Grouped<FeatureType> grouped = group(dataset);
