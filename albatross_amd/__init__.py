@@ -22,4 +22,12 @@ from .sparse_gp import (FixedInducingPoints, SparseCrossValidation, SparseCrossV
 
 from .scores import chi_squared_cdf, crps_normal, draw_mvn, energy_score, variogram_score
 
+from .ransac import (RANSAC_RETURN_CODE_EXCEEDED_MAX_FAILED_CANDIDATES, RANSAC_RETURN_CODE_FAILURE, RANSAC_RETURN_CODE_INVALID,
+                     RANSAC_RETURN_CODE_INVALID_ARGUMENTS, RANSAC_RETURN_CODE_NO_CONSENSUS, RANSAC_RETURN_CODE_SUCCESS,
+                     AlwaysAcceptCandidateMetric, ChiSquaredCdf, ChiSquaredConsensusMetric, ChiSquaredIsValidCandidateMetric,
+                     DefaultGPRansacStrategy, DifferentialEntropyConsensusMetric, FeatureCountConsensusMetric,
+                     GaussianProcessRansacStrategy, GPRansacScorer, NegativeLogLikelihood, Ransac, RansacConfig, RansacFit,
+                     RansacIteration, RansacOutput, draw_candidates, gp_ransac_strategy, ransac, ransac_return_code_to_string,
+                     ransac_success)
+
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -46,6 +46,12 @@ MAX_GRADIENT_SLOTS = 64
 PREDICT_JOINT = 0  # agp_logo_nll_gradient_typed's predict_type
 PREDICT_MARGINAL = 1
 
+RANSAC_NLL_JOINT = 0  # agp_ransac_score_trials' inlier_metric
+RANSAC_NLL_MARGINAL = 1
+RANSAC_CHI_SQUARED_CDF = 2
+RANSAC_MAX_CANDIDATE_POINTS = 256
+RANSAC_MAX_GROUP_POINTS = 64
+
 
 class KernelNode(C.Structure):
     _fields_ = [
@@ -106,6 +112,9 @@ EXPORTS = [
                                         _P]),
     ("agp_logo_nll_gradient_typed", C.c_int, [_P, _P, C.POINTER(Features), _P, _P, C.c_int64, _P, _P, C.c_int, C.c_int, _P, _P,
                                               C.c_int64, _D, _P, _P, _P]),
+    ("agp_ransac_score_trials", C.c_int, [_P, _P, C.POINTER(Features), _P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, C.c_int,
+                                          C.c_double, _P, C.c_int64, C.c_int, _P, _P, _P, _P, _P]),
+    ("agp_ransac_draw_candidates", C.c_int, [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, _P]),
     ("agp_nll_gradient_batch", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P,
                                          C.c_int64, _P, C.c_int64, _P]),
     ("agp_loo_nll_gradient_batch", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P,

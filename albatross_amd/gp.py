@@ -1079,6 +1079,12 @@ class GaussianProcessRegression:
             factor = PivotedLDLT(K, ctx)
         return FitModel(self, UpdatedGPFit(feats, factor, factor.solve(y)))
 
+    def ransac(self, strategy, *args, **kwargs):
+        """ModelBase::ransac (ransac.hpp:507-524): model.ransac(strategy, inlier_threshold, random_sample_size,
+        min_consensus_size, max_iterations[, max_failed_candidates]) or model.ransac(strategy, config) -> Ransac"""
+        from .ransac import _model_ransac
+        return _model_ransac(self, strategy, *args, **kwargs)
+
     def cross_validate(self):
         return CrossValidation(self)
 

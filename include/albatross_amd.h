@@ -458,6 +458,63 @@ AGP_API int agp_logo_nll_gradient_typed(agp_context *ctx, const agp_kernel *k, c
                                         double *logo_nll, double *grad_logo_nll,
                                         double *mean_weights, double *group_nll);
 
+/* ---- GP RANSAC: the trials of one run scored in lock step (models/ransac.hpp:172-257 around models/ransac_gp.hpp and
+ * models/conditional_gaussian.hpp).  The reference fits and predicts once per trial; here the prior covariance of the
+ * measurements is built ONCE and n_trials trials are one batch, each O(s^3 + N s^2) against one N x N Gram.
+ * Derived once (gp.hpp:421-425): Sigma = k(as_measurements(x), as_measurements(x)) - y_var is NOT added to it -,
+ * d = deviation = y - mean(x), R = diag(y_var) (zeros for NULL).  The grouping is that of agp_logo_nll_gradient (host
+ * arrays offsets / indices), here with every group non-empty and no point in two groups; points in no group are never
+ * scored.  Trial t has the candidate groups cand_groups[cand_offsets[t] .. cand_offsets[t + 1]) (host, at least one,
+ * distinct); with c their points in that order, s = |c|:
+ *   A = Sigma_cc + R_c = L L^T,   z = L^-1 d_c,   candidate_quadratic[t] = q_c = z^T z = d_c^T A^-1 d_c,
+ *   candidate_log_det[t] = log|A|   (conditional_gaussian.hpp:30-45; chi_squared_cdf(q_c, s) is the candidate check),
+ * and for every group g that is not a candidate (conditional_gaussian.hpp:61-91, prediction_metrics.hpp:112-141)
+ *   W = L^-1 Sigma_cg,   r = W^T z - d_g,   P = Sigma_gg - W^T W + R_g,
+ *   AGP_RANSAC_NLL_JOINT:        1/2 (log|P| + r^T P^-1 r + |g| log 2 pi)
+ *   AGP_RANSAC_NLL_MARGINAL:     the same with P -> diag(P)
+ *   AGP_RANSAC_CHI_SQUARED_CDF:  chi_squared_cdf(r^T P^-1 r, |g|)   (albatross_amd/chi_squared.h: the host's function)
+ * g is an inlier iff metric <= inlier_threshold; a NaN metric (a P that is not positive definite) is an outlier.
+ *   metric            n_groups x n_trials, column t = trial t, leading dimension ld_metric >= n_groups, at
+ *                     metric_location; NaN at the trial's own candidates; may be NULL
+ *   inlier_groups[t], inlier_points[t]   accepted groups and their observations, candidates not counted (host)
+ *   status[t]         AGP_OK, or AGP_ERR_NOT_POSITIVE_DEFINITE when A did not factor: that trial's metrics, q_c and
+ *                     log|A| are NaN and its counts 0; the other trials are unaffected (host)
+ * deviation and y_var live at x->location.
+ * Size limits, checked before anything is launched (AGP_ERR_INVALID_ARGUMENT, nothing written): at most
+ * AGP_RANSAC_MAX_CANDIDATE_POINTS candidate points per trial and AGP_RANSAC_MAX_GROUP_POINTS points per group - the
+ * scoring kernel keeps W for one tile of 64 columns in LDS, 128 KiB of the CU's 160 KiB at s = 256 -, 1 <= n_trials
+ * <= 65535; likewise a candidate id out of range or twice in one trial, an empty group, an index out of range or in
+ * two groups, malformed offsets, an unknown inlier_metric.
+ * Stages: the Gram; a gather of A_t and d_c into slabs padded with a unit diagonal; the batched LL^T of
+ * agp_fit_create_batch in its plain schedule; ONE scoring launch over (tile of groups, trial); a per-trial reduction.
+ * Trials run in size classes of 16, 32, 64, 128 and 256 candidate points, so a trial's padding depends on the trial
+ * alone: a trial scored on its own and the same trial inside any batch give identical bits, as do two identical calls.
+ * Workspace: the N x N Gram, n_groups x n_trials metrics, and at most 512 MiB of slabs for the trials in flight.
+ * With profiling on, agp_last_stage_ms reports 0 gram, 2 gather, 1 factor, 8 scoring and counts. */
+#define AGP_RANSAC_NLL_JOINT 0
+#define AGP_RANSAC_NLL_MARGINAL 1
+#define AGP_RANSAC_CHI_SQUARED_CDF 2
+#define AGP_RANSAC_MAX_CANDIDATE_POINTS 256
+#define AGP_RANSAC_MAX_GROUP_POINTS 64
+AGP_API int agp_ransac_score_trials(agp_context *ctx, const agp_kernel *k, const agp_features *x,
+                                    const double *deviation, const double *y_var,
+                                    int64_t n_groups, const int64_t *offsets, const int64_t *indices,
+                                    int64_t n_trials, const int64_t *cand_offsets, const int64_t *cand_groups,
+                                    int inlier_metric, double inlier_threshold,
+                                    double *metric, int64_t ld_metric, int metric_location,
+                                    int64_t *inlier_groups, int64_t *inlier_points,
+                                    double *candidate_quadratic, double *candidate_log_det, int *status);
+
+/* The candidate sets of n_trials trials: out[t * sample_size .. (t + 1) * sample_size) holds sample_size distinct group
+ * ids of 0 .. n_groups - 1 in ascending order (host only; no context).  This is the project's OWN seeded draw, one
+ * function for every binding so that Python and C++ draw the same sets: trial t seeds a splitmix64 stream with
+ * seed ^ (0xD1B54A32D192ED03 * (t + 1)), Floyd's sampling without replacement takes unbiased (rejection) integers from it,
+ * and the set is sorted.  It does NOT reproduce the sequence of libstdc++'s std::default_random_engine that the
+ * reference's random_without_replacement walks through, so the trials differ from the reference's for the same seed.
+ * sample_size > n_groups or a negative size: AGP_ERR_INVALID_ARGUMENT. */
+AGP_API int agp_ransac_draw_candidates(uint64_t seed, int64_t n_groups, int64_t sample_size, int64_t n_trials,
+                                       int64_t *out);
+
 /* Tuner objective batching: agp_nll for `count` parameter vectors of one model on one dataset in lock step
  * (batched Gram slabs + batched LL^T; blockIdx.y = parameter vector) — the evaluations that
  * compute_gradient (include/albatross/src/tune/finite_difference.hpp:20-94) and the ModelTuner objective

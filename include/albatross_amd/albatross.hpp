@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "../albatross_amd.h"
+#include "chi_squared.h"
 
 namespace albatross {
 
@@ -1078,48 +1079,13 @@ inline double negative_log_likelihood(const Vector &deviation, const Matrix &cov
 // (include/albatross_amd.h, "scoring a joint prediction")
 // ---------------------------------------------------------------------------
 namespace detail {
-// the regularised lower incomplete gamma P(a, x), a > 0 (the role of stats/incomplete_gamma.hpp:134): the series below
-// a + 1, Lentz's continued fraction of Q above
-inline double regularized_lower_gamma(double a, double x) {
-  if (x <= 0.) return 0.;
-  const double log_front = a * std::log(x) - x - std::lgamma(a);
-  if (x < a + 1.) {
-    double term = 1. / a, total = term, n = a;
-    for (int i = 0; i < 10000; ++i) {
-      n += 1.;
-      term *= x / n;
-      total += term;
-      if (std::fabs(term) < std::fabs(total) * 1e-17) break;
-    }
-    const double v = total * std::exp(log_front);
-    return v < 1. ? v : 1.;
-  }
-  const double tiny = 1e-300;
-  double b = x + 1. - a, c = 1. / tiny, d = 1. / b, h = d;
-  for (int i = 1; i < 10000; ++i) {
-    const double an = -static_cast<double>(i) * (static_cast<double>(i) - a);
-    b += 2.;
-    d = an * d + b;
-    if (std::fabs(d) < tiny) d = tiny;
-    c = b + an / c;
-    if (std::fabs(c) < tiny) c = tiny;
-    d = 1. / d;
-    const double delta = d * c;
-    h *= delta;
-    if (std::fabs(delta - 1.) < 1e-16) break;
-  }
-  const double v = 1. - std::exp(log_front) * h;
-  return v > 0. ? v : 0.;
-}
+// the regularised lower incomplete gamma P(a, x), a > 0: chi_squared.h, the one copy the host and the device share
+inline double regularized_lower_gamma(double a, double x) { return albatross_amd_stats::regularized_lower_gamma(a, x); }
 }  // namespace detail
 
-// stats/chi_squared.hpp:29-67
+// stats/chi_squared.hpp:29-67 (chi_squared.h)
 inline double chi_squared_cdf(double x, double degrees_of_freedom) {
-  if (std::isnan(x) || x < 0.) return std::nan("");
-  if (degrees_of_freedom == 0) return 1.;
-  if (std::numeric_limits<double>::epsilon() > x) return 0.;
-  if (std::isinf(x)) return 1.;
-  return detail::regularized_lower_gamma(0.5 * degrees_of_freedom, 0.5 * x);
+  return albatross_amd_stats::chi_squared_cdf(x, degrees_of_freedom);
 }
 
 // chi_squared_cdf(deviation, covariance), stats/chi_squared.hpp:74-81: the quadratic form through the device LL^T
@@ -1657,6 +1623,17 @@ constexpr int predict_type_of() {
 }
 }  // namespace detail
 
+template <typename ModelType, typename StrategyType> class Ransac;  // models/ransac.hpp:427-505, below
+struct RansacConfig;
+
+// what agp_ransac_score_trials returns for a batch of trials (include/albatross_amd.h)
+struct RansacTrialScores {
+  Matrix metric;  // n_groups x n_trials, NaN at a trial's own candidates
+  std::vector<std::int64_t> inlier_groups, inlier_points, candidate_points;
+  Vector candidate_quadratic, candidate_log_det;
+  std::vector<int> status;
+};
+
 template <typename CovFunc, typename MeanFunc = ZeroMean>
 class GaussianProcessRegression {
  public:
@@ -2113,7 +2090,54 @@ class GaussianProcessRegression {
     return -nll;
   }
 
- private:
+  // ModelBase::ransac (ransac.hpp:507-524): a model that performs GP RANSAC each time fit is called (defined below)
+  template <typename StrategyType>
+  Ransac<GaussianProcessRegression, StrategyType> ransac(const StrategyType &strategy, double inlier_threshold,
+                                                         std::size_t random_sample_size, std::size_t min_consensus_size,
+                                                         std::size_t max_iterations, std::size_t max_failed_candidates = 0) const;
+  template <typename StrategyType>
+  Ransac<GaussianProcessRegression, StrategyType> ransac(const StrategyType &strategy, const RansacConfig &config) const;
+
+  // The trials of one RANSAC round scored in lock step (agp_ransac_score_trials): the prior covariance of the
+  // measurements once, then per trial one small factor and the conditional prediction of every other group.  offsets /
+  // indices: the grouping (detail::group_arrays); trials: candidate group positions per trial; inlier_metric:
+  // AGP_RANSAC_NLL_JOINT, AGP_RANSAC_NLL_MARGINAL or AGP_RANSAC_CHI_SQUARED_CDF.
+  template <typename FeatureType>
+  RansacTrialScores ransac_score_trials(const RegressionDataset<FeatureType> &dataset, const std::vector<std::int64_t> &offsets,
+                                        const std::vector<std::int64_t> &indices,
+                                        const std::vector<std::vector<std::size_t>> &trials, int inlier_metric,
+                                        double inlier_threshold) const {
+    auto ctx = detail::default_context();
+    detail::KernelHolder k(covariance_function_.program());
+    detail::Flat f = detail::flatten(covariance_function_, dataset.features);
+    const Vector d = deviation(dataset);
+    const double *yvar = dataset.targets.covariance.empty() ? nullptr : dataset.targets.covariance.data();
+    const std::int64_t n_groups = static_cast<std::int64_t>(offsets.size()) - 1, n_trials = static_cast<std::int64_t>(trials.size());
+    std::vector<std::int64_t> cand_offsets(1, 0), cand_groups;
+    RansacTrialScores out;
+    for (const auto &t : trials) {
+      std::int64_t points = 0;
+      for (const std::size_t g : t) {
+        cand_groups.push_back(static_cast<std::int64_t>(g));
+        if (static_cast<std::int64_t>(g) < n_groups) points += offsets[g + 1] - offsets[g];
+      }
+      cand_offsets.push_back(static_cast<std::int64_t>(cand_groups.size()));
+      out.candidate_points.push_back(points);
+    }
+    out.metric = Matrix(n_groups, n_trials);
+    out.inlier_groups.assign(trials.size(), 0);
+    out.inlier_points.assign(trials.size(), 0);
+    out.candidate_quadratic.assign(trials.size(), 0.);
+    out.candidate_log_det.assign(trials.size(), 0.);
+    out.status.assign(trials.size(), 0);
+    detail::check(agp_ransac_score_trials(ctx->ctx, k.k, &f.view, d.data(), yvar, n_groups, offsets.data(), indices.data(), n_trials,
+                                          cand_offsets.data(), cand_groups.data(), inlier_metric, inlier_threshold, out.metric.data.data(),
+                                          n_groups, AGP_HOST, out.inlier_groups.data(), out.inlier_points.data(),
+                                          out.candidate_quadratic.data(), out.candidate_log_det.data(), out.status.data()),
+                  ctx->ctx, "agp_ransac_score_trials");
+    return out;
+  }
+
   // targets - mu (mean_function_.remove_from)
   template <typename FeatureType>
   Vector deviation(const RegressionDataset<FeatureType> &dataset) const {
@@ -2124,6 +2148,7 @@ class GaussianProcessRegression {
     return y;
   }
 
+ private:
   // every name of get_params() -> NaN: the gradient of a failed problem of a batch
   ParameterStore nan_gradient() const {
     ParameterStore g;
@@ -3041,6 +3066,352 @@ class LeaveOneGroupOutLikelihood {
  private:
   GroupFunction<FeatureType> grouper_;
 };
+
+// ---------------------------------------------------------------------------
+// GP RANSAC: models/ransac.hpp (the loop, the return codes, Ransac<Model, Strategy>), models/ransac_gp.hpp (the strategy
+// parts).  The trials of a round are scored in ONE device call (agp_ransac_score_trials) and the reference's loop walks
+// the scored matrix on the host.  The candidate sets come from agp_ransac_draw_candidates, the project's own seeded draw
+// (it does not reproduce std::default_random_engine: the trials differ from the reference's, the rules do not).
+// Not provided: GenericRansacStrategy / get_generic_ransac_functions, serialisation, RANSAC on the sparse GP.
+// ---------------------------------------------------------------------------
+typedef enum ransac_return_code_e {
+  RANSAC_RETURN_CODE_INVALID = -1,
+  RANSAC_RETURN_CODE_SUCCESS,
+  RANSAC_RETURN_CODE_NO_CONSENSUS,
+  RANSAC_RETURN_CODE_INVALID_ARGUMENTS,
+  RANSAC_RETURN_CODE_EXCEEDED_MAX_FAILED_CANDIDATES,
+  RANSAC_RETURN_CODE_FAILURE
+} ransac_return_code_t;
+
+inline std::string to_string(const ransac_return_code_t &return_code) {
+  switch (return_code) {
+    case RANSAC_RETURN_CODE_INVALID: return "invalid";
+    case RANSAC_RETURN_CODE_SUCCESS: return "success";
+    case RANSAC_RETURN_CODE_NO_CONSENSUS: return "no_consensus";
+    case RANSAC_RETURN_CODE_INVALID_ARGUMENTS: return "invalid_arguments";
+    case RANSAC_RETURN_CODE_EXCEEDED_MAX_FAILED_CANDIDATES: return "exceeded_max_failed_candidates";
+    case RANSAC_RETURN_CODE_FAILURE: return "failure";
+  }
+  return "unknown return code";
+}
+
+inline bool ransac_success(const ransac_return_code_t &rc) { return rc == RANSAC_RETURN_CODE_SUCCESS; }
+
+template <typename GroupKey>
+struct RansacIteration {  // ransac.hpp:92-116
+  std::vector<GroupKey> candidates;
+  std::map<GroupKey, double> inliers;
+  std::map<GroupKey, double> outliers;
+  double consensus_metric_value = std::numeric_limits<double>::quiet_NaN();
+  std::vector<GroupKey> consensus() const {
+    std::vector<GroupKey> output(candidates);
+    for (const auto &pair : inliers) output.emplace_back(pair.first);
+    return output;
+  }
+};
+
+template <typename GroupKey>
+struct RansacOutput {  // ransac.hpp:118-131
+  using key_type = GroupKey;
+  ransac_return_code_t return_code = RANSAC_RETURN_CODE_INVALID;
+  RansacIteration<GroupKey> best;
+  std::vector<RansacIteration<GroupKey>> iterations;
+};
+
+struct RansacConfig {  // ransac.hpp:133-152
+  RansacConfig() = default;
+  RansacConfig(double inlier_threshold_, std::size_t random_sample_size_, std::size_t min_consensus_size_,
+               std::size_t max_iterations_, std::size_t max_failed_candidates_)
+      : inlier_threshold(inlier_threshold_), random_sample_size(random_sample_size_), min_consensus_size(min_consensus_size_),
+        max_iterations(max_iterations_), max_failed_candidates(max_failed_candidates_) {}
+  double inlier_threshold = std::numeric_limits<double>::quiet_NaN();
+  std::size_t random_sample_size = 0, min_consensus_size = 0, max_iterations = 0, max_failed_candidates = 0;
+};
+
+// n_trials candidate sets of sample_size distinct group positions each, ascending (agp_ransac_draw_candidates)
+inline std::vector<std::vector<std::size_t>> ransac_draw_candidates(std::uint64_t seed, std::size_t n_groups, std::size_t sample_size,
+                                                                    std::size_t n_trials) {
+  std::vector<std::int64_t> flat(n_trials * sample_size);
+  detail::check(agp_ransac_draw_candidates(seed, static_cast<std::int64_t>(n_groups), static_cast<std::int64_t>(sample_size),
+                                           static_cast<std::int64_t>(n_trials), flat.data()),
+                nullptr, "agp_ransac_draw_candidates");
+  std::vector<std::vector<std::size_t>> out(n_trials);
+  for (std::size_t t = 0; t < n_trials; ++t) out[t].assign(flat.begin() + t * sample_size, flat.begin() + (t + 1) * sample_size);
+  return out;
+}
+
+// what a scorer returns for the trials of one round: metric(g, t) with NaN at the candidates, valid[t]
+struct RansacRoundScores {
+  Matrix metric;
+  std::vector<bool> valid;
+};
+
+// ransac(ransac_functions, groups, ...), ransac.hpp:172-257, over a scorer with
+//   RansacRoundScores score(const std::vector<std::vector<std::size_t>> &trials)  and
+//   double consensus_metric(const std::vector<std::size_t> &positions).
+// A round draws as many trials as iterations remain; an invalid candidate uses up no iteration, so a further round
+// (seed + round * 0x9E3779B97F4A7C15) is drawn for what the invalid ones left over.
+template <typename Scorer, typename GroupKey>
+RansacOutput<GroupKey> ransac(Scorer &scorer, const std::vector<GroupKey> &groups, const RansacConfig &config, std::uint64_t seed = 0) {
+  RansacOutput<GroupKey> output;
+  output.return_code = RANSAC_RETURN_CODE_FAILURE;
+  if (config.min_consensus_size >= groups.size() || config.min_consensus_size < config.random_sample_size ||
+      config.random_sample_size >= groups.size() || config.random_sample_size <= 0 || config.max_iterations <= 0) {
+    output.return_code = RANSAC_RETURN_CODE_INVALID_ARGUMENTS;
+    return output;
+  }
+  std::size_t i = 0, failed_candidates = 0;
+  std::uint64_t round = 0;
+  while (i < config.max_iterations) {
+    const auto trials = ransac_draw_candidates(seed + round * 0x9E3779B97F4A7C15ull, groups.size(), config.random_sample_size,
+                                               config.max_iterations - i);
+    ++round;
+    const RansacRoundScores scores = scorer.score(trials);
+    for (std::size_t t = 0; t < trials.size(); ++t) {
+      output.iterations.emplace_back(RansacIteration<GroupKey>());
+      RansacIteration<GroupKey> &iteration = output.iterations.back();
+      for (const std::size_t p : trials[t]) iteration.candidates.push_back(groups[p]);
+      if (!scores.valid[t]) {
+        ++failed_candidates;
+        if (failed_candidates >= config.max_failed_candidates) {
+          output.return_code = RANSAC_RETURN_CODE_EXCEEDED_MAX_FAILED_CANDIDATES;
+          return output;
+        }
+        continue;
+      }
+      std::vector<std::size_t> positions(trials[t]);
+      for (std::size_t g = 0; g < groups.size(); ++g) {
+        if (std::find(trials[t].begin(), trials[t].end(), g) != trials[t].end()) continue;
+        const double metric_value = scores.metric(static_cast<std::int64_t>(g), static_cast<std::int64_t>(t));
+        if (metric_value <= config.inlier_threshold) {
+          iteration.inliers.insert({groups[g], metric_value});
+          positions.push_back(g);
+        } else {
+          iteration.outliers.insert({groups[g], metric_value});
+        }
+      }
+      if (positions.size() >= config.min_consensus_size) {
+        iteration.consensus_metric_value = scorer.consensus_metric(positions);
+        if (std::isnan(output.best.consensus_metric_value) || iteration.consensus_metric_value < output.best.consensus_metric_value)
+          output.best = iteration;
+      }
+      ++i;
+    }
+  }
+  output.return_code = output.best.consensus().size() ? RANSAC_RETURN_CODE_SUCCESS : RANSAC_RETURN_CODE_NO_CONSENSUS;
+  return output;
+}
+
+// ---- the strategy parts, ransac_gp.hpp:69-113 and prediction_metrics.hpp:112-145 ----
+template <typename PredictType = JointDistribution>
+struct NegativeLogLikelihood {};
+
+struct FeatureCountConsensusMetric {};         // minus the number of observations in the consensus
+struct ChiSquaredConsensusMetric {};           // chi_squared_cdf(d_S^T (Sigma_SS + R_S)^-1 d_S, |S|)
+struct DifferentialEntropyConsensusMetric {};  // 1/2 k (1 + log 2 pi + log|Sigma_SS|), as differential_entropy.hpp:37-42 writes it
+
+struct AlwaysAcceptCandidateMetric {
+  bool operator()(double, std::size_t) const { return true; }
+};
+
+struct ChiSquaredIsValidCandidateMetric {  // chi_squared_cdf(q_c, s) <= threshold, from the trial's own factor
+  explicit ChiSquaredIsValidCandidateMetric(double chi_squared_threshold_ = 0.999) : chi_squared_threshold(chi_squared_threshold_) {}
+  bool operator()(double quadratic, std::size_t dof) const {
+    return chi_squared_cdf(quadratic, static_cast<double>(dof)) <= chi_squared_threshold;
+  }
+  double chi_squared_threshold;
+};
+
+namespace detail {
+template <typename T> struct ransac_inlier_code;
+template <> struct ransac_inlier_code<NegativeLogLikelihood<JointDistribution>> { static constexpr int value = AGP_RANSAC_NLL_JOINT; };
+template <> struct ransac_inlier_code<NegativeLogLikelihood<MarginalDistribution>> { static constexpr int value = AGP_RANSAC_NLL_MARGINAL; };
+template <> struct ransac_inlier_code<ChiSquaredCdf> { static constexpr int value = AGP_RANSAC_CHI_SQUARED_CDF; };
+}  // namespace detail
+
+template <typename InlierMetric, typename ConsensusMetric, typename IsValidCandidateMetric, typename GrouperFunction>
+struct GaussianProcessRansacStrategy {  // ransac_gp.hpp:147-180
+  GaussianProcessRansacStrategy() = default;
+  GaussianProcessRansacStrategy(const InlierMetric &inlier_metric, const ConsensusMetric &consensus_metric,
+                                const IsValidCandidateMetric &is_valid_candidate, const GrouperFunction &grouper_function)
+      : inlier_metric_(inlier_metric), consensus_metric_(consensus_metric), is_valid_candidate_(is_valid_candidate),
+        grouper_function_(grouper_function) {}
+  template <typename FeatureType>
+  auto get_indexer(const RegressionDataset<FeatureType> &dataset) const {
+    return group_indexer(dataset.features, grouper_function_);
+  }
+  InlierMetric inlier_metric_;
+  ConsensusMetric consensus_metric_;
+  IsValidCandidateMetric is_valid_candidate_;
+  GrouperFunction grouper_function_;
+};
+
+using DefaultGPRansacStrategy = GaussianProcessRansacStrategy<NegativeLogLikelihood<JointDistribution>, FeatureCountConsensusMetric,
+                                                              AlwaysAcceptCandidateMetric, LeaveOneOutGrouper>;
+
+template <typename InlierMetric, typename ConsensusMetric, typename GrouperFunction>
+auto gp_ransac_strategy(const InlierMetric &inlier_metric, const ConsensusMetric &consensus_metric, GrouperFunction grouper_function) {
+  return GaussianProcessRansacStrategy<InlierMetric, ConsensusMetric, AlwaysAcceptCandidateMetric, GrouperFunction>(
+      inlier_metric, consensus_metric, AlwaysAcceptCandidateMetric(), grouper_function);
+}
+
+template <typename InlierMetric, typename ConsensusMetric, typename IsValidCandidateMetric, typename GrouperFunction>
+auto gp_ransac_strategy(const InlierMetric &inlier_metric, const ConsensusMetric &consensus_metric,
+                        const IsValidCandidateMetric &is_valid_candidate, GrouperFunction grouper_function) {
+  return GaussianProcessRansacStrategy<InlierMetric, ConsensusMetric, IsValidCandidateMetric, GrouperFunction>(
+      inlier_metric, consensus_metric, is_valid_candidate, grouper_function);
+}
+
+// The device scorer of a GP strategy.  FeatureCount needs the group sizes only; the ChiSquared and DifferentialEntropy
+// consensus metrics are computed per qualifying trial from the consensus block through the dense factor: not batched.
+template <typename ModelType, typename StrategyType, typename FeatureType>
+class GPRansacScorer {
+ public:
+  GPRansacScorer(const ModelType &model, const StrategyType &strategy, const RegressionDataset<FeatureType> &dataset,
+                 double inlier_threshold)
+      : model_(model), strategy_(strategy), dataset_(dataset), inlier_threshold_(inlier_threshold) {
+    detail::group_arrays(dataset.features, strategy.get_indexer(dataset), &offsets_, &indices_);
+    deviation_ = model.deviation(dataset);
+  }
+
+  RansacRoundScores score(const std::vector<std::vector<std::size_t>> &trials) {
+    using Inlier = decltype(strategy_.inlier_metric_);
+    last_ = model_.ransac_score_trials(dataset_, offsets_, indices_, trials, detail::ransac_inlier_code<Inlier>::value, inlier_threshold_);
+    RansacRoundScores out;
+    out.metric = last_.metric;
+    for (std::size_t t = 0; t < trials.size(); ++t)
+      out.valid.push_back(last_.status[t] == AGP_OK &&
+                          strategy_.is_valid_candidate_(last_.candidate_quadratic[t], static_cast<std::size_t>(last_.candidate_points[t])));
+    return out;
+  }
+
+  double consensus_metric(const std::vector<std::size_t> &positions) const {
+    std::vector<std::size_t> pts;
+    for (const std::size_t g : positions)
+      for (std::int64_t q = offsets_[g]; q < offsets_[g + 1]; ++q) pts.push_back(static_cast<std::size_t>(indices_[static_cast<std::size_t>(q)]));
+    return consensus_metric_impl(strategy_.consensus_metric_, pts);
+  }
+
+  const RansacTrialScores &last_scores() const { return last_; }
+
+ private:
+  double consensus_metric_impl(const FeatureCountConsensusMetric &, const std::vector<std::size_t> &pts) const {
+    return -static_cast<double>(pts.size());
+  }
+  Matrix prior(const std::vector<std::size_t> &pts) const {
+    std::vector<FeatureType> sub;
+    for (const std::size_t i : pts) sub.push_back(dataset_.features[i]);
+    return model_.get_covariance()(as_measurements(sub));
+  }
+  double consensus_metric_impl(const ChiSquaredConsensusMetric &, const std::vector<std::size_t> &pts) const {
+    Matrix K = prior(pts);
+    Vector d(pts.size());
+    for (std::size_t a = 0; a < pts.size(); ++a) {
+      d[a] = deviation_[pts[a]];
+      if (!dataset_.targets.covariance.empty())
+        K(static_cast<std::int64_t>(a), static_cast<std::int64_t>(a)) += dataset_.targets.covariance[pts[a]];
+    }
+    return chi_squared_cdf(d, K);
+  }
+  double consensus_metric_impl(const DifferentialEntropyConsensusMetric &, const std::vector<std::size_t> &pts) const {
+    const double k = static_cast<double>(pts.size());
+    return 0.5 * k * (1. + std::log(2. * M_PI) + SerializableLDLT(prior(pts)).log_determinant());
+  }
+
+  const ModelType &model_;
+  const StrategyType &strategy_;
+  const RegressionDataset<FeatureType> &dataset_;
+  double inlier_threshold_;
+  std::vector<std::int64_t> offsets_, indices_;
+  Vector deviation_;
+  RansacTrialScores last_;
+};
+
+// Fit<RansacFit<...>> (ransac.hpp:383-422): ransac_output and, on success, the sub-model's fit on the consensus set
+template <typename ModelType, typename FeatureType, typename GroupKey>
+struct RansacFit {
+  using FitModelType = decltype(std::declval<const ModelType &>().fit(std::declval<const RegressionDataset<FeatureType> &>()));
+  bool has_fit_model() const { return static_cast<bool>(maybe_empty_fit_model); }
+  const FitModelType &get_fit_model_or_assert() const {
+    if (!maybe_empty_fit_model) throw std::logic_error("RANSAC did not succeed: there is no fit model");
+    return *maybe_empty_fit_model;
+  }
+  std::shared_ptr<FitModelType> maybe_empty_fit_model;
+  RansacOutput<GroupKey> ransac_output;
+};
+
+template <typename RansacModelType, typename FitType>
+class RansacFitModel {
+ public:
+  RansacFitModel(const RansacModelType &model, FitType fit) : model_(model), fit_(std::move(fit)) {}
+  const FitType &get_fit() const { return fit_; }
+  const RansacModelType &get_model() const { return model_; }
+  template <typename PredictFeature>
+  auto predict(const std::vector<PredictFeature> &features) const {
+    return fit_.get_fit_model_or_assert().predict(features);
+  }
+
+ private:
+  RansacModelType model_;
+  FitType fit_;
+};
+
+// Ransac<ModelType, StrategyType> (ransac.hpp:427-505): wraps a model and performs RANSAC each time fit is called
+template <typename ModelType, typename StrategyType>
+class Ransac {
+ public:
+  Ransac() = default;
+  Ransac(const ModelType &sub_model, const StrategyType &strategy, const RansacConfig &config, std::uint64_t seed = 0)
+      : sub_model_(sub_model), strategy_(strategy), config_(config), seed_(seed) {}
+
+  std::string get_name() const { return "ransac[" + sub_model_.get_name() + "]"; }
+  ParameterStore get_params() const { return sub_model_.get_params(); }
+  void set_param(const std::string &name, double value) { sub_model_.set_param(name, value); }
+
+  template <typename FeatureType>
+  auto fit(const RegressionDataset<FeatureType> &dataset) const {
+    const auto indexer = strategy_.get_indexer(dataset);
+    using GroupKey = typename std::decay<decltype(indexer.begin()->first)>::type;
+    std::vector<GroupKey> keys;
+    for (const auto &kv : indexer) keys.push_back(kv.first);
+    GPRansacScorer<ModelType, StrategyType, FeatureType> scorer(sub_model_, strategy_, dataset, config_.inlier_threshold);
+    RansacFit<ModelType, FeatureType, GroupKey> fit;
+    fit.ransac_output = albatross::ransac(scorer, keys, config_, seed_);
+    if (ransac_success(fit.ransac_output.return_code)) {
+      RegressionDataset<FeatureType> consensus_set;
+      for (const auto &key : fit.ransac_output.best.consensus())
+        for (const std::size_t i : indexer.at(key)) {
+          consensus_set.features.push_back(dataset.features[i]);
+          consensus_set.targets.mean.push_back(dataset.targets.mean[i]);
+          if (!dataset.targets.covariance.empty()) consensus_set.targets.covariance.push_back(dataset.targets.covariance[i]);
+        }
+      fit.maybe_empty_fit_model = std::make_shared<typename RansacFit<ModelType, FeatureType, GroupKey>::FitModelType>(
+          sub_model_.fit(consensus_set));
+    }
+    return RansacFitModel<Ransac, RansacFit<ModelType, FeatureType, GroupKey>>(*this, std::move(fit));
+  }
+
+  ModelType sub_model_;
+  StrategyType strategy_;
+  RansacConfig config_;
+  std::uint64_t seed_ = 0;
+};
+
+template <typename CovFunc, typename MeanFunc>
+template <typename StrategyType>
+Ransac<GaussianProcessRegression<CovFunc, MeanFunc>, StrategyType> GaussianProcessRegression<CovFunc, MeanFunc>::ransac(
+    const StrategyType &strategy, double inlier_threshold, std::size_t random_sample_size, std::size_t min_consensus_size,
+    std::size_t max_iterations, std::size_t max_failed_candidates) const {
+  return Ransac<GaussianProcessRegression, StrategyType>(
+      *this, strategy, RansacConfig(inlier_threshold, random_sample_size, min_consensus_size, max_iterations, max_failed_candidates));
+}
+
+template <typename CovFunc, typename MeanFunc>
+template <typename StrategyType>
+Ransac<GaussianProcessRegression<CovFunc, MeanFunc>, StrategyType> GaussianProcessRegression<CovFunc, MeanFunc>::ransac(
+    const StrategyType &strategy, const RansacConfig &config) const {
+  return Ransac<GaussianProcessRegression, StrategyType>(*this, strategy, config);
+}
 
 }  // namespace albatross
 
