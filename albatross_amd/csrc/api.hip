@@ -154,6 +154,10 @@ namespace agp {
 // the Gram launchers have no context: they follow the switches of the context created last
 static bool g_gram_sop = true;
 bool gram_sop_enabled() { return g_gram_sop; }
+// (libalbatross_amd_debug.so holds its own copy of this static, which no agp_context_create of the product library sets: its
+// Gram entry points set it to the switch of the context they are handed for the length of their launch and put it back -
+// debug_api.hip: GramSopScope)
+void gram_sop_set(bool on) { g_gram_sop = on; }
 }  // namespace agp
 
 extern "C" {

@@ -216,6 +216,8 @@ void launch_gtg_lower_batched(hipStream_t s, const double *G, long long ldg, lon
 // optional) is added to the diagonal of the copy first.  Returns the status of the factorisation.  (Declared in the
 // extern "C" block below.)
 namespace agp {
+bool gram_sop_enabled();     // api.hip: the AGP_GRAM_SOP switch the Gram launchers of THIS library image follow
+void gram_sop_set(bool on);  // (debug_api.hip only: GramSopScope)
 void launch_add_diagonal(hipStream_t s, double *A, long long lda, long long n, const double *d);  // scores.hip
 }
 // x = L^-T z for ONE vector (api.hip): z is overwritten with x; ws: backsolve_ws_elems(n) doubles of scratch

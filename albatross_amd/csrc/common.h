@@ -273,6 +273,17 @@ size_t gram_batch_table_bytes(long long count);
 bool launch_gram_batch(hipStream_t s, long long count, const DevProgram *const *host_programs, const FeatView *Xs, double *const *outs,
                        long long ld, const double *const *diag_adds, int *const *nan_flags, void *table_dev, void *host_stage = nullptr);
 void launch_gram_diagonal(hipStream_t s, const DevProgram *P, const FeatView &X, double *out);
+// Which kernel launch_gram / launch_predict_mean runs for a program and two feature views (gram.hip).  The launchers switch
+// on the value these functions return and decide nothing themselves, so the path a caller is told is the path that ran.
+// plan (optional): the parameters of the chosen kernel, for the launcher.
+enum class GramPath : int { FAST_TRI = 0, FAST_RECT = 1, PAIR2 = 2, SOP = 3, INTERP = 4 };
+enum class PredictMeanPath : int { TILED8 = 0, TILED4 = 1, FAST_WAVE = 2, SOP = 3, INTERP = 4 };
+struct GramPlan;
+struct PredictMeanPlan;
+GramPath gram_select_path(const DevProgram *host_program, const FeatView &X, const FeatView &Y, bool lower_only,
+                          GramPlan *plan = nullptr);
+PredictMeanPath predict_mean_select_path(const DevProgram *host_program, const FeatView &X, const FeatView &XS,
+                                         PredictMeanPlan *plan = nullptr);
 // mean_j = sum_i k(x_i, xs_j) alpha_i without materialising the cross Gram
 void launch_predict_mean(hipStream_t s, const DevProgram *P, const FeatView &X, const FeatView &XS,
                          const double *alpha, double *mean, const DevProgram *host_program = nullptr);

@@ -1286,6 +1286,29 @@ struct NullComm : HostReducingComm {
 };
 }  // namespace agp
 
+namespace {
+// a device buffer of the Gram entry points below (agp_debug_gram, ...): freed on every return, the early ones of AGP_HIP_CHECK included
+template <class T>
+struct DevBuf {
+  T *p = nullptr;
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  hipError_t alloc(size_t count) { return hipMalloc(&p, sizeof(T) * count); }
+};
+// This library image has its own copy of the AGP_GRAM_SOP switch the Gram launchers follow (api.hip: g_gram_sop), which a
+// context made by the product library never sets: for the length of one entry point the switch is the one of the context
+// handed in, then what it was.  EVERY debug entry point that launches a covariance kernel holds one of these.
+struct GramSopScope {
+  bool before;
+  explicit GramSopScope(const agp_context *ctx) : before(gram_sop_enabled()) { gram_sop_set(ctx->tune.gram_sop); }
+  GramSopScope(const GramSopScope &) = delete;
+  GramSopScope &operator=(const GramSopScope &) = delete;
+  ~GramSopScope() { gram_sop_set(before); }
+};
+}  // namespace
+
 extern "C" {
 
 // the cycle stamps the factoring workgroup of the LAST potrf / panel launch left (a -DAGP_POTRF_TIMING build; zeros otherwise)
@@ -1319,6 +1342,114 @@ AGP_DEBUG_API int agp_debug_mfma_f64_peak(agp_context *ctx, int iters, double *t
   if (!ctx || !tflops || iters <= 0) return AGP_ERR_INVALID_ARGUMENT;
   AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   return mfma_f64_peak(ctx->stream, iters, tflops);
+}
+
+// ---- the covariance kernels of gram.hip / gram_fast.h one launch at a time (tests/test_gram_paths_gpu.py) ----------------------
+// launch_gram on host data.  out_host: the caller's WHOLE buffer of out_offset_elems + ld * cols doubles (cols = y ? y->n :
+// x->n), padding rows and the elements before the matrix included: uploaded, the launch writes at d_out + out_offset_elems
+// with leading dimension ld, downloaded - what the kernel did not store comes back bit for bit.  (An odd offset leaves the
+// output 8-byte aligned only: the kernels' scalar store pair.)  y = nullptr: Y is the very view of X, as the fits pass it.
+// diag_add (optional): cols values.  nan_flag: the flag the kernel raised; path: the GramPath that gram_select_path chose
+// for exactly these views (the launcher switches on the same call).
+AGP_DEBUG_API int agp_debug_gram(agp_context *ctx, const agp_kernel *k, const agp_features *x, const agp_features *y, int symmetric,
+                                 int lower_only, int64_t ld, int64_t out_offset_elems, const double *diag_add, double *out_host,
+                                 int *nan_flag, int *path) {
+  if (!ctx || !k || !x || !out_host || !nan_flag || !path || out_offset_elems < 0) return AGP_ERR_INVALID_ARGUMENT;
+  int st = validate_features(x);
+  if (st != AGP_OK) return st;
+  if (y && (st = validate_features(y)) != AGP_OK) return st;
+  if (y && (y->dim != x->dim || symmetric)) return AGP_ERR_INVALID_ARGUMENT;
+  const long long rows = x->n, cols = y ? y->n : x->n;
+  if (rows <= 0 || cols <= 0 || ld < rows) return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const DevProgram *dprog = nullptr;
+  if ((st = device_program(ctx, k, &dprog)) != AGP_OK) return st;
+  DeviceFeatures dx, dy;
+  if ((st = to_device(ctx, x, false, &dx)) != AGP_OK) return st;
+  if (y && (st = to_device(ctx, y, false, &dy)) != AGP_OK) return st;
+  const FeatView &vy = y ? dy.v : dx.v;
+  const size_t total = (size_t)out_offset_elems + (size_t)ld * (size_t)cols;
+  DevBuf<double> d_out, d_diag;
+  DevBuf<int> d_flag;
+  AGP_HIP_CHECK(ctx, d_out.alloc(total));
+  AGP_HIP_CHECK(ctx, d_flag.alloc(1));
+  AGP_HIP_CHECK(ctx, hipMemcpy(d_out.p, out_host, sizeof(double) * total, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipMemset(d_flag.p, 0, sizeof(int)));
+  if (diag_add) {
+    AGP_HIP_CHECK(ctx, d_diag.alloc((size_t)cols));
+    AGP_HIP_CHECK(ctx, hipMemcpy(d_diag.p, diag_add, sizeof(double) * (size_t)cols, hipMemcpyHostToDevice));
+  }
+  AGP_HIP_CHECK(ctx, hipDeviceSynchronize());  // (the null-stream copies above do not order with the context's stream)
+  GramSopScope sop_switch(ctx);
+  *path = (int)gram_select_path(&k->prog, dx.v, vy, lower_only != 0);
+  launch_gram(ctx->stream, dprog, dx.v, vy, symmetric != 0, lower_only != 0, d_out.p + out_offset_elems, ld, d_diag.p, d_flag.p,
+              &k->prog);
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipMemcpy(out_host, d_out.p, sizeof(double) * total, hipMemcpyDeviceToHost));
+  AGP_HIP_CHECK(ctx, hipMemcpy(nan_flag, d_flag.p, sizeof(int), hipMemcpyDeviceToHost));
+  return AGP_OK;
+}
+
+// launch_gram_blocks on host data: `count` diagonal blocks of `rows` consecutive features of x each, block g at
+// out + g * stride with leading dimension ld.  out_host: the caller's whole buffer of (count - 1) * stride + ld * rows doubles,
+// uploaded and downloaded as above.  diag_add (optional): rows * count values.  launched: 0 when the tree has none of the
+// fast shapes (nothing ran, the buffer comes back as it went in).
+AGP_DEBUG_API int agp_debug_gram_blocks(agp_context *ctx, const agp_kernel *k, const agp_features *x, int64_t rows, int64_t count,
+                                        int64_t ld, int64_t stride, const double *diag_add, double *out_host, int *launched) {
+  if (!ctx || !k || !x || !out_host || !launched || rows <= 0 || count <= 0 || ld < rows || stride < 0) return AGP_ERR_INVALID_ARGUMENT;
+  int st = validate_features(x);
+  if (st != AGP_OK) return st;
+  if (x->n < rows * count) return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  DeviceFeatures dx;
+  if ((st = to_device(ctx, x, false, &dx)) != AGP_OK) return st;
+  const size_t total = (size_t)(count - 1) * (size_t)stride + (size_t)ld * (size_t)rows;
+  DevBuf<double> d_out, d_diag;
+  AGP_HIP_CHECK(ctx, d_out.alloc(total));
+  AGP_HIP_CHECK(ctx, hipMemcpy(d_out.p, out_host, sizeof(double) * total, hipMemcpyHostToDevice));
+  if (diag_add) {
+    AGP_HIP_CHECK(ctx, d_diag.alloc((size_t)(rows * count)));
+    AGP_HIP_CHECK(ctx, hipMemcpy(d_diag.p, diag_add, sizeof(double) * (size_t)(rows * count), hipMemcpyHostToDevice));
+  }
+  AGP_HIP_CHECK(ctx, hipDeviceSynchronize());
+  GramSopScope sop_switch(ctx);
+  *launched = launch_gram_blocks(ctx->stream, &k->prog, dx.v, rows, count, d_out.p, ld, stride, d_diag.p, nullptr) ? 1 : 0;
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipMemcpy(out_host, d_out.p, sizeof(double) * total, hipMemcpyDeviceToHost));
+  return AGP_OK;
+}
+
+// launch_predict_mean with the caller's alpha (x->n values): no fit and no factorisation between the kernel and the check.
+// mean_host: xs->n + 2 doubles, uploaded first and downloaded whole, so that the two trailing ones show a store past the
+// last test point.  path: the PredictMeanPath that predict_mean_select_path chose for exactly these views.
+AGP_DEBUG_API int agp_debug_predict_mean(agp_context *ctx, const agp_kernel *k, const agp_features *x, const agp_features *xs,
+                                         const double *alpha_host, double *mean_host, int *path) {
+  if (!ctx || !k || !x || !xs || !alpha_host || !mean_host || !path) return AGP_ERR_INVALID_ARGUMENT;
+  int st = validate_features(x);
+  if (st != AGP_OK) return st;
+  if ((st = validate_features(xs)) != AGP_OK) return st;
+  if (x->dim != xs->dim || x->n <= 0 || xs->n <= 0) return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const DevProgram *dprog = nullptr;
+  if ((st = device_program(ctx, k, &dprog)) != AGP_OK) return st;
+  DeviceFeatures dx, dxs;
+  if ((st = to_device(ctx, x, false, &dx)) != AGP_OK) return st;
+  if ((st = to_device(ctx, xs, false, &dxs)) != AGP_OK) return st;
+  const size_t n = (size_t)x->n, m = (size_t)xs->n;
+  DevBuf<double> d;  // alpha (n), then mean (m + 2)
+  AGP_HIP_CHECK(ctx, d.alloc(n + m + 2));
+  AGP_HIP_CHECK(ctx, hipMemcpy(d.p, alpha_host, sizeof(double) * n, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipMemcpy(d.p + n, mean_host, sizeof(double) * (m + 2), hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipDeviceSynchronize());
+  GramSopScope sop_switch(ctx);
+  *path = (int)predict_mean_select_path(&k->prog, dx.v, dxs.v);
+  launch_predict_mean(ctx->stream, dprog, dx.v, dxs.v, d.p, d.p + n, &k->prog);
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipMemcpy(mean_host, d.p + n, sizeof(double) * (m + 2), hipMemcpyDeviceToHost));
+  return AGP_OK;
 }
 
 AGP_DEBUG_API int agp_debug_comm_create_null(int nranks, int rank, agp_comm **out) {

@@ -210,47 +210,41 @@ static bool match_fast(const DevProgram &H, FastParams *fp, int *op) {
   return false;
 }
 
+// the four radial operators of the fast shapes.  (match_fast rejects the ops above AGP_OP_MATERN52 only and the enum
+// starts at 1: a node with op 0 goes to the generic paths, as it did through the `default` of the former launch switch.)
+static bool fast_op(int op) { return op >= AGP_OP_SQUARED_EXPONENTIAL && op <= AGP_OP_MATERN52; }
+
+#define AGP_FAST_OP_SWITCH(LAUNCH)                                           \
+  switch (op) {                                                              \
+  case AGP_OP_SQUARED_EXPONENTIAL: LAUNCH(AGP_OP_SQUARED_EXPONENTIAL); break; \
+  case AGP_OP_EXPONENTIAL: LAUNCH(AGP_OP_EXPONENTIAL); break;                \
+  case AGP_OP_MATERN32: LAUNCH(AGP_OP_MATERN32); break;                      \
+  case AGP_OP_MATERN52: LAUNCH(AGP_OP_MATERN52); break;                      \
+  default: break;                                                            \
+  }
+
+// the lower triangle of one symmetric Gram matrix: workgroups for the tiles on or below the diagonal only
 template <int DIMP>
-static bool launch_gram_fast_t(hipStream_t s, const FastParams &fp, int op, const FeatView &X, const FeatView &Y,
-                               bool lower_only, double *out, long long ld, const double *diag_add, int *nan_flag,
-                               long long blk_rows = 0, long long blk_stride = 0, long long blk_count = 1) {
+static void launch_gram_fast_tri_t(hipStream_t s, const FastParams &fp, int op, const FeatView &X, double *out, long long ld,
+                                   const double *diag_add, int *nan_flag) {
+  const long long rt = (X.n + TM - 1) / TM;
+  dim3 tri((unsigned)(rt * (rt + 1) / 2 * (TM / TN))), block(GRAM_THREADS);
+#define AGP_TRI(O) hipLaunchKernelGGL((gram_fast_tri_kernel<DIMP, O>), tri, block, 0, s, fp, X, out, ld, diag_add, nan_flag)
+  AGP_FAST_OP_SWITCH(AGP_TRI)
+#undef AGP_TRI
+}
+
+template <int DIMP>
+static void launch_gram_fast_rect_t(hipStream_t s, const FastParams &fp, int op, const FeatView &X, const FeatView &Y,
+                                    bool lower_only, double *out, long long ld, const double *diag_add, int *nan_flag,
+                                    long long blk_rows = 0, long long blk_stride = 0, long long blk_count = 1) {
   const long long xn = blk_rows > 0 ? blk_rows : X.n, yn = blk_rows > 0 ? blk_rows : Y.n;
   dim3 grid((unsigned)((xn + TM - 1) / TM), (unsigned)((yn + TN - 1) / TN), (unsigned)blk_count), block(GRAM_THREADS);
   const int lo = lower_only ? 1 : 0;
-  if (lower_only && blk_rows == 0 && blk_count == 1 && X.coords == Y.coords && X.ids == Y.ids && X.n == Y.n && X.meas == Y.meas) {
-    const long long rt = (X.n + TM - 1) / TM;
-    dim3 tri((unsigned)(rt * (rt + 1) / 2 * (TM / TN)));
-    switch (op) {
-    case AGP_OP_SQUARED_EXPONENTIAL:
-      hipLaunchKernelGGL((gram_fast_tri_kernel<DIMP, AGP_OP_SQUARED_EXPONENTIAL>), tri, block, 0, s, fp, X, out, ld, diag_add, nan_flag);
-      return true;
-    case AGP_OP_EXPONENTIAL:
-      hipLaunchKernelGGL((gram_fast_tri_kernel<DIMP, AGP_OP_EXPONENTIAL>), tri, block, 0, s, fp, X, out, ld, diag_add, nan_flag);
-      return true;
-    case AGP_OP_MATERN32:
-      hipLaunchKernelGGL((gram_fast_tri_kernel<DIMP, AGP_OP_MATERN32>), tri, block, 0, s, fp, X, out, ld, diag_add, nan_flag);
-      return true;
-    case AGP_OP_MATERN52:
-      hipLaunchKernelGGL((gram_fast_tri_kernel<DIMP, AGP_OP_MATERN52>), tri, block, 0, s, fp, X, out, ld, diag_add, nan_flag);
-      return true;
-    default: return false;
-    }
-  }
-  switch (op) {
-  case AGP_OP_SQUARED_EXPONENTIAL:
-    hipLaunchKernelGGL((gram_fast_kernel<DIMP, AGP_OP_SQUARED_EXPONENTIAL>), grid, block, 0, s, fp, X, Y, lo, out, ld, diag_add, nan_flag, blk_rows, blk_stride);
-    return true;
-  case AGP_OP_EXPONENTIAL:
-    hipLaunchKernelGGL((gram_fast_kernel<DIMP, AGP_OP_EXPONENTIAL>), grid, block, 0, s, fp, X, Y, lo, out, ld, diag_add, nan_flag, blk_rows, blk_stride);
-    return true;
-  case AGP_OP_MATERN32:
-    hipLaunchKernelGGL((gram_fast_kernel<DIMP, AGP_OP_MATERN32>), grid, block, 0, s, fp, X, Y, lo, out, ld, diag_add, nan_flag, blk_rows, blk_stride);
-    return true;
-  case AGP_OP_MATERN52:
-    hipLaunchKernelGGL((gram_fast_kernel<DIMP, AGP_OP_MATERN52>), grid, block, 0, s, fp, X, Y, lo, out, ld, diag_add, nan_flag, blk_rows, blk_stride);
-    return true;
-  default: return false;
-  }
+#define AGP_RECT(O) \
+  hipLaunchKernelGGL((gram_fast_kernel<DIMP, O>), grid, block, 0, s, fp, X, Y, lo, out, ld, diag_add, nan_flag, blk_rows, blk_stride)
+  AGP_FAST_OP_SWITCH(AGP_RECT)
+#undef AGP_RECT
 }
 
 // Postfix program -> sum-of-products form, when the tree is one (cov_eval.h).  A host-side symbolic evaluation of the
@@ -545,19 +539,15 @@ static bool match_pair2(const SopProgram &S, Pair2Params *pp) {
 }
 
 template <int DIMP>
-static void launch_gram_t(hipStream_t s, const DevProgram *P, const FeatView &X, const FeatView &Y,
-                          bool symmetric, bool lower_only, double *out, long long ld,
-                          const double *diag_add, int *nan_flag, const DevProgram *host_program) {
+static void launch_gram_t(hipStream_t s, const DevProgram *P, const SopProgram &sop, bool use_sop, const FeatView &X, const FeatView &Y,
+                          bool symmetric, bool lower_only, double *out, long long ld, const double *diag_add, int *nan_flag) {
   dim3 grid((unsigned)((X.n + TM - 1) / TM), (unsigned)((Y.n + TN - 1) / TN));
-  SopProgram sop;
-  if (host_program && sop_enabled() && build_sop(*host_program, &sop)) {
+  if (use_sop)
     hipLaunchKernelGGL((gram_kernel<DIMP, true>), grid, dim3(GRAM_THREADS), 0, s, P, sop, X, Y, symmetric ? 1 : 0,
                        lower_only ? 1 : 0, out, ld, diag_add, nan_flag);
-    return;
-  }
-  std::memset(&sop, 0, sizeof(sop));
-  hipLaunchKernelGGL((gram_kernel<DIMP, false>), grid, dim3(GRAM_THREADS), 0, s, P, sop, X, Y, symmetric ? 1 : 0,
-                     lower_only ? 1 : 0, out, ld, diag_add, nan_flag);
+  else
+    hipLaunchKernelGGL((gram_kernel<DIMP, false>), grid, dim3(GRAM_THREADS), 0, s, P, sop, X, Y, symmetric ? 1 : 0,
+                       lower_only ? 1 : 0, out, ld, diag_add, nan_flag);
 }
 
 // `count` diagonal blocks of `rows` consecutive features each - block g = the symmetric Gram matrix of features
@@ -569,10 +559,11 @@ bool launch_gram_blocks(hipStream_t s, const DevProgram *host_program, const Fea
   if (!host_program || X.dim > 3 || rows <= 0 || count <= 0 || count > 65535 || !sop_enabled()) return false;
   FastParams fp;
   int op = 0;
-  if (!match_fast(*host_program, &fp, &op)) return false;
-  if (X.dim == 1) return launch_gram_fast_t<1>(s, fp, op, X, X, true, out, ld, diag_add, nan_flag, rows, stride, count);
-  if (X.dim == 2) return launch_gram_fast_t<2>(s, fp, op, X, X, true, out, ld, diag_add, nan_flag, rows, stride, count);
-  return launch_gram_fast_t<3>(s, fp, op, X, X, true, out, ld, diag_add, nan_flag, rows, stride, count);
+  if (!match_fast(*host_program, &fp, &op) || !fast_op(op)) return false;
+  if (X.dim == 1) launch_gram_fast_rect_t<1>(s, fp, op, X, X, true, out, ld, diag_add, nan_flag, rows, stride, count);
+  else if (X.dim == 2) launch_gram_fast_rect_t<2>(s, fp, op, X, X, true, out, ld, diag_add, nan_flag, rows, stride, count);
+  else launch_gram_fast_rect_t<3>(s, fp, op, X, X, true, out, ld, diag_add, nan_flag, rows, stride, count);
+  return true;
 }
 
 size_t gram_batch_table_bytes(long long count) { return sizeof(GramBatchItem) * (size_t)(count > 0 ? count : 0); }
@@ -628,32 +619,62 @@ bool launch_gram_batch(hipStream_t s, long long count, const DevProgram *const *
   return true;
 }
 
+// What gram_select_path decided, with the parameters the chosen kernel takes (common.h declares the type).
+struct GramPlan {
+  GramPath path;
+  FastParams fp;   // FAST_TRI, FAST_RECT
+  int op;
+  Pair2Params pp;  // PAIR2
+  SopProgram sop;  // SOP (zeros for INTERP: the kernel takes the argument and ignores it)
+};
+
+// THE choice of the Gram kernel (launch_gram switches on it and decides nothing itself):
+//   FAST_TRI   radial<Euclidean> [+ noise], dim <= 3, lower_only of ONE feature vector against itself
+//   FAST_RECT  the same trees otherwise
+//   PAIR2      the sums of at most three fixed terms (match_pair2), dim <= 3
+//   SOP        any tree that expands to a sum of products
+//   INTERP     the postfix interpreter: everything else, no host program, or AGP_GRAM_SOP=0
+GramPath gram_select_path(const DevProgram *host_program, const FeatView &X, const FeatView &Y, bool lower_only, GramPlan *plan) {
+  static thread_local GramPlan scratch;  // (a caller that only asks for the path)
+  if (!plan) plan = &scratch;
+  const bool sop_on = host_program && sop_enabled();
+  plan->op = 0;
+  // (the fast shapes are bitwise symmetric in their arguments, so `symmetric` needs no special handling; every term
+  // of the pair-2 shapes is too)
+  if (sop_on && X.dim <= 3 && match_fast(*host_program, &plan->fp, &plan->op) && fast_op(plan->op)) {
+    const bool one_vector = X.coords == Y.coords && X.ids == Y.ids && X.n == Y.n && X.meas == Y.meas;
+    return plan->path = (lower_only && one_vector) ? GramPath::FAST_TRI : GramPath::FAST_RECT;
+  }
+  if (sop_on && build_sop(*host_program, &plan->sop)) {
+    if (X.dim <= 3 && match_pair2(plan->sop, &plan->pp)) return plan->path = GramPath::PAIR2;
+    return plan->path = GramPath::SOP;
+  }
+  std::memset(&plan->sop, 0, sizeof(plan->sop));
+  return plan->path = GramPath::INTERP;
+}
+
 void launch_gram(hipStream_t s, const DevProgram *P, const FeatView &X, const FeatView &Y, bool symmetric,
                  bool lower_only, double *out, long long ld, const double *diag_add, int *nan_flag,
                  const DevProgram *host_program) {
   if (X.n == 0 || Y.n == 0) return;
+  static thread_local GramPlan plan;
   const int dim = X.dim;
-  if (host_program && dim <= 3) {
-    // (the fast shapes are bitwise symmetric in their arguments, so `symmetric`
-    // needs no special handling)
-    FastParams fp;
-    int op = 0;
-    if (sop_enabled() && match_fast(*host_program, &fp, &op)) {
-      bool done = false;
-      if (dim == 1) done = launch_gram_fast_t<1>(s, fp, op, X, Y, lower_only, out, ld, diag_add, nan_flag);
-      else if (dim == 2) done = launch_gram_fast_t<2>(s, fp, op, X, Y, lower_only, out, ld, diag_add, nan_flag);
-      else done = launch_gram_fast_t<3>(s, fp, op, X, Y, lower_only, out, ld, diag_add, nan_flag);
-      if (done) return;
-    }
-  }
-  if (host_program && dim <= 3 && sop_enabled()) {
-    // (every term of these shapes is bitwise symmetric in its arguments too)
-    SopProgram sop;
-    Pair2Params pp;
-    if (build_sop(*host_program, &sop) && match_pair2(sop, &pp)) {
-      dim3 grid((unsigned)((X.n + TM - 1) / TM), (unsigned)((Y.n + TN - 1) / TN)), block(GRAM_THREADS);
-      const int lo = lower_only ? 1 : 0;
-      const bool eu = (pp.metric_mask & (1 << AGP_METRIC_EUCLIDEAN)) != 0, an = (pp.metric_mask & (1 << AGP_METRIC_ANGULAR)) != 0;
+  switch (gram_select_path(host_program, X, Y, lower_only, &plan)) {
+  case GramPath::FAST_TRI:
+    if (dim == 1) launch_gram_fast_tri_t<1>(s, plan.fp, plan.op, X, out, ld, diag_add, nan_flag);
+    else if (dim == 2) launch_gram_fast_tri_t<2>(s, plan.fp, plan.op, X, out, ld, diag_add, nan_flag);
+    else launch_gram_fast_tri_t<3>(s, plan.fp, plan.op, X, out, ld, diag_add, nan_flag);
+    return;
+  case GramPath::FAST_RECT:
+    if (dim == 1) launch_gram_fast_rect_t<1>(s, plan.fp, plan.op, X, Y, lower_only, out, ld, diag_add, nan_flag);
+    else if (dim == 2) launch_gram_fast_rect_t<2>(s, plan.fp, plan.op, X, Y, lower_only, out, ld, diag_add, nan_flag);
+    else launch_gram_fast_rect_t<3>(s, plan.fp, plan.op, X, Y, lower_only, out, ld, diag_add, nan_flag);
+    return;
+  case GramPath::PAIR2: {
+    const Pair2Params &pp = plan.pp;
+    dim3 grid((unsigned)((X.n + TM - 1) / TM), (unsigned)((Y.n + TN - 1) / TN)), block(GRAM_THREADS);
+    const int lo = lower_only ? 1 : 0;
+    const bool eu = (pp.metric_mask & (1 << AGP_METRIC_EUCLIDEAN)) != 0, an = (pp.metric_mask & (1 << AGP_METRIC_ANGULAR)) != 0;
 #define AGP_P2(D, E, A) hipLaunchKernelGGL((gram_pair2_kernel<D, E, A>), grid, block, 0, s, pp, X, Y, lo, out, ld, diag_add, nan_flag)
 #define AGP_P2_DIM(D)                                   \
   do {                                                  \
@@ -662,19 +683,22 @@ void launch_gram(hipStream_t s, const DevProgram *P, const FeatView &X, const Fe
     else if (an) AGP_P2(D, false, true);                \
     else AGP_P2(D, false, false);                       \
   } while (0)
-      if (dim == 1) AGP_P2_DIM(1);
-      else if (dim == 2) AGP_P2_DIM(2);
-      else AGP_P2_DIM(3);
+    if (dim == 1) AGP_P2_DIM(1);
+    else if (dim == 2) AGP_P2_DIM(2);
+    else AGP_P2_DIM(3);
 #undef AGP_P2_DIM
 #undef AGP_P2
-      return;
-    }
+    return;
   }
-  if (dim == 1) launch_gram_t<1>(s, P, X, Y, symmetric, lower_only, out, ld, diag_add, nan_flag, host_program);
-  else if (dim == 2) launch_gram_t<2>(s, P, X, Y, symmetric, lower_only, out, ld, diag_add, nan_flag, host_program);
-  else if (dim == 3) launch_gram_t<3>(s, P, X, Y, symmetric, lower_only, out, ld, diag_add, nan_flag, host_program);
-  else if (dim == 4) launch_gram_t<4>(s, P, X, Y, symmetric, lower_only, out, ld, diag_add, nan_flag, host_program);
-  else launch_gram_t<8>(s, P, X, Y, symmetric, lower_only, out, ld, diag_add, nan_flag, host_program);
+  case GramPath::SOP:
+  case GramPath::INTERP: {
+    const bool use_sop = plan.path == GramPath::SOP;
+    dispatch_dim(dim, [&](auto D) {
+      launch_gram_t<decltype(D)::value>(s, P, plan.sop, use_sop, X, Y, symmetric, lower_only, out, ld, diag_add, nan_flag);
+    });
+    return;
+  }
+  }
 }
 
 // ---- diagonal: prior_variance[i] = cov(f_i, f_i)  (gp.hpp:339-343) -----------
@@ -906,84 +930,87 @@ __global__ __launch_bounds__(256) void predict_mean_tiled_kernel(FastParams fp, 
 }
 
 template <int DIMP, int TJ>
-static bool launch_predict_mean_tiled_t(hipStream_t s, const FastParams &fp, int op, const FeatView &X, const FeatView &XS,
+static void launch_predict_mean_tiled_t(hipStream_t s, const FastParams &fp, int op, const FeatView &X, const FeatView &XS,
                                         const double *alpha, double *mean) {
   dim3 tgrid((unsigned)((XS.n + TJ - 1) / TJ)), tblock(256);
-  switch (op) {
-  case AGP_OP_SQUARED_EXPONENTIAL:
-    hipLaunchKernelGGL((predict_mean_tiled_kernel<DIMP, AGP_OP_SQUARED_EXPONENTIAL, TJ>), tgrid, tblock, 0, s, fp, X, XS, alpha, mean);
-    return true;
-  case AGP_OP_EXPONENTIAL:
-    hipLaunchKernelGGL((predict_mean_tiled_kernel<DIMP, AGP_OP_EXPONENTIAL, TJ>), tgrid, tblock, 0, s, fp, X, XS, alpha, mean);
-    return true;
-  case AGP_OP_MATERN32:
-    hipLaunchKernelGGL((predict_mean_tiled_kernel<DIMP, AGP_OP_MATERN32, TJ>), tgrid, tblock, 0, s, fp, X, XS, alpha, mean);
-    return true;
-  case AGP_OP_MATERN52:
-    hipLaunchKernelGGL((predict_mean_tiled_kernel<DIMP, AGP_OP_MATERN52, TJ>), tgrid, tblock, 0, s, fp, X, XS, alpha, mean);
-    return true;
-  default: return false;
-  }
+#define AGP_PMT(O) hipLaunchKernelGGL((predict_mean_tiled_kernel<DIMP, O, TJ>), tgrid, tblock, 0, s, fp, X, XS, alpha, mean)
+  AGP_FAST_OP_SWITCH(AGP_PMT)
+#undef AGP_PMT
 }
 
 template <int DIMP>
-static bool launch_predict_mean_fast_t(hipStream_t s, const FastParams &fp, int op, const FeatView &X,
-                                       const FeatView &XS, const double *alpha, double *mean) {
-  // (radial.hpp: the covariance is 0 for a non-positive length scale - the tiled kernel has no test for it in its loop)
-  if (XS.n >= 1024 && XS.dim == DIMP && fp.length_scale > 0.) {  // enough test points for 256 workgroups of four (16384: of eight)
-    // (TJ = 2 below 8192 test points - twice the workgroups - measured in round 6: +6 % at M = 2048, 0 at 4096, -4 % at 8192)
-    const bool done = XS.n >= 16384 ? launch_predict_mean_tiled_t<DIMP, 8>(s, fp, op, X, XS, alpha, mean)
-                                    : launch_predict_mean_tiled_t<DIMP, 4>(s, fp, op, X, XS, alpha, mean);
-    if (done) return true;
-  }
+static void launch_predict_mean_wave_t(hipStream_t s, const FastParams &fp, int op, const FeatView &X, const FeatView &XS,
+                                       const double *alpha, double *mean) {
   dim3 grid((unsigned)((XS.n + PM_WAVES - 1) / PM_WAVES)), block(64 * PM_WAVES);
-  switch (op) {
-  case AGP_OP_SQUARED_EXPONENTIAL:
-    hipLaunchKernelGGL((predict_mean_fast_kernel<DIMP, AGP_OP_SQUARED_EXPONENTIAL>), grid, block, 0, s, fp, X, XS, alpha, mean);
-    return true;
-  case AGP_OP_EXPONENTIAL:
-    hipLaunchKernelGGL((predict_mean_fast_kernel<DIMP, AGP_OP_EXPONENTIAL>), grid, block, 0, s, fp, X, XS, alpha, mean);
-    return true;
-  case AGP_OP_MATERN32:
-    hipLaunchKernelGGL((predict_mean_fast_kernel<DIMP, AGP_OP_MATERN32>), grid, block, 0, s, fp, X, XS, alpha, mean);
-    return true;
-  case AGP_OP_MATERN52:
-    hipLaunchKernelGGL((predict_mean_fast_kernel<DIMP, AGP_OP_MATERN52>), grid, block, 0, s, fp, X, XS, alpha, mean);
-    return true;
-  default: return false;
+#define AGP_PMW(O) hipLaunchKernelGGL((predict_mean_fast_kernel<DIMP, O>), grid, block, 0, s, fp, X, XS, alpha, mean)
+  AGP_FAST_OP_SWITCH(AGP_PMW)
+#undef AGP_PMW
+}
+
+struct PredictMeanPlan {
+  PredictMeanPath path;
+  FastParams fp;   // TILED8, TILED4, FAST_WAVE
+  int op;
+  SopProgram sop;  // SOP (zeros for INTERP)
+};
+
+// THE choice of the predictive-mean kernel (launch_predict_mean switches on it and decides nothing itself):
+//   TILED8 / TILED4  radial<Euclidean> [+ noise], dim <= 3, from 16384 / 1024 test points on: enough test points for 256
+//                    workgroups of four (16384: of eight).  (TJ = 2 below 8192 test points - twice the workgroups - measured
+//                    in round 6: +6 % at M = 2048, 0 at 4096, -4 % at 8192.)  Not for a non-positive length scale
+//                    (radial.hpp: the covariance is 0 - the tiled kernel has no test for it in its loop).
+//   FAST_WAVE        the same trees otherwise: one wave per test point
+//   SOP / INTERP     the generic evaluators, as for the Gram matrix
+PredictMeanPath predict_mean_select_path(const DevProgram *host_program, const FeatView &X, const FeatView &XS, PredictMeanPlan *plan) {
+  static thread_local PredictMeanPlan scratch;  // (a caller that only asks for the path)
+  if (!plan) plan = &scratch;
+  const bool sop_on = host_program && sop_enabled();
+  plan->op = 0;
+  if (sop_on && X.dim <= 3 && X.dim == XS.dim && match_fast(*host_program, &plan->fp, &plan->op) && fast_op(plan->op)) {
+    if (XS.n >= 1024 && plan->fp.length_scale > 0.)
+      return plan->path = XS.n >= 16384 ? PredictMeanPath::TILED8 : PredictMeanPath::TILED4;
+    return plan->path = PredictMeanPath::FAST_WAVE;
   }
+  if (sop_on && build_sop(*host_program, &plan->sop)) return plan->path = PredictMeanPath::SOP;
+  std::memset(&plan->sop, 0, sizeof(plan->sop));
+  return plan->path = PredictMeanPath::INTERP;
 }
 
 void launch_predict_mean(hipStream_t s, const DevProgram *P, const FeatView &X, const FeatView &XS,
                          const double *alpha, double *mean, const DevProgram *host_program) {
   if (XS.n == 0) return;
-  if (host_program && X.dim <= 3 && X.dim == XS.dim) {
-    FastParams fp;
-    int op = 0;
-    if (sop_enabled() && match_fast(*host_program, &fp, &op)) {
-      bool done = false;
-      if (X.dim == 1) done = launch_predict_mean_fast_t<1>(s, fp, op, X, XS, alpha, mean);
-      else if (X.dim == 2) done = launch_predict_mean_fast_t<2>(s, fp, op, X, XS, alpha, mean);
-      else done = launch_predict_mean_fast_t<3>(s, fp, op, X, XS, alpha, mean);
-      if (done) return;
-    }
-  }
-  dim3 grid((unsigned)((XS.n + PM_WAVES - 1) / PM_WAVES)), block(64 * PM_WAVES);
+  static thread_local PredictMeanPlan plan;
   const int dim = X.dim;
-  SopProgram sop;
-  const bool use_sop = host_program && sop_enabled() && build_sop(*host_program, &sop);
-  if (!use_sop) std::memset(&sop, 0, sizeof(sop));
-#define AGP_PM_LAUNCH(D)                                                                                                      \
-  do {                                                                                                                       \
-    if (use_sop) hipLaunchKernelGGL((predict_mean_kernel<D, true>), grid, block, 0, s, P, sop, X, XS, alpha, mean);           \
-    else hipLaunchKernelGGL((predict_mean_kernel<D, false>), grid, block, 0, s, P, sop, X, XS, alpha, mean);                  \
-  } while (0)
-  if (dim == 1) AGP_PM_LAUNCH(1);
-  else if (dim == 2) AGP_PM_LAUNCH(2);
-  else if (dim == 3) AGP_PM_LAUNCH(3);
-  else if (dim == 4) AGP_PM_LAUNCH(4);
-  else AGP_PM_LAUNCH(8);
-#undef AGP_PM_LAUNCH
+  switch (predict_mean_select_path(host_program, X, XS, &plan)) {
+  case PredictMeanPath::TILED8:
+    if (dim == 1) launch_predict_mean_tiled_t<1, 8>(s, plan.fp, plan.op, X, XS, alpha, mean);
+    else if (dim == 2) launch_predict_mean_tiled_t<2, 8>(s, plan.fp, plan.op, X, XS, alpha, mean);
+    else launch_predict_mean_tiled_t<3, 8>(s, plan.fp, plan.op, X, XS, alpha, mean);
+    return;
+  case PredictMeanPath::TILED4:
+    if (dim == 1) launch_predict_mean_tiled_t<1, 4>(s, plan.fp, plan.op, X, XS, alpha, mean);
+    else if (dim == 2) launch_predict_mean_tiled_t<2, 4>(s, plan.fp, plan.op, X, XS, alpha, mean);
+    else launch_predict_mean_tiled_t<3, 4>(s, plan.fp, plan.op, X, XS, alpha, mean);
+    return;
+  case PredictMeanPath::FAST_WAVE:
+    if (dim == 1) launch_predict_mean_wave_t<1>(s, plan.fp, plan.op, X, XS, alpha, mean);
+    else if (dim == 2) launch_predict_mean_wave_t<2>(s, plan.fp, plan.op, X, XS, alpha, mean);
+    else launch_predict_mean_wave_t<3>(s, plan.fp, plan.op, X, XS, alpha, mean);
+    return;
+  case PredictMeanPath::SOP:
+  case PredictMeanPath::INTERP: {
+    dim3 grid((unsigned)((XS.n + PM_WAVES - 1) / PM_WAVES)), block(64 * PM_WAVES);
+    const SopProgram &sop = plan.sop;
+    dispatch_dim(dim, [&](auto D) {
+      constexpr int DP = decltype(D)::value;
+      if (plan.path == PredictMeanPath::SOP)
+        hipLaunchKernelGGL((predict_mean_kernel<DP, true>), grid, block, 0, s, P, sop, X, XS, alpha, mean);
+      else
+        hipLaunchKernelGGL((predict_mean_kernel<DP, false>), grid, block, 0, s, P, sop, X, XS, alpha, mean);
+    });
+    return;
+  }
+  }
 }
 
 }  // namespace agp
