@@ -164,6 +164,7 @@ EXPORTS = [
     ("agp_gram_combined", C.c_int, [_P, _P, C.POINTER(Features), C.c_int64, _P, _P, C.POINTER(Features), C.c_int64, _P, _P, _P,
                            C.c_int64, C.c_int]),
     ("agp_fit_update", C.c_int, [_P, _P, _P, C.POINTER(Features), _P, _P, _PP, _P, _D]),
+    ("agp_fit_update_batch", C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P, _P]),
     ("agp_solver_from_fit", C.c_int, [_P, _P, _PP]),
     ("agp_solver_from_ldlt", C.c_int, [_P, _P, _PP]),
     ("agp_solver_block_symmetric", C.c_int, [_P, _P, _P, C.c_int64, C.c_int, _P, _PP]),

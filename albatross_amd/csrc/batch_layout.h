@@ -130,6 +130,32 @@ inline FitBatchTables carve_fit_batch_tables(WsLayout &ws, const BatchGeometry &
   return {ws.take<char>(copy_table_bytes), ws.take<char>(gram_table_bytes), fused_panels ? ws.take<double>(g.vectors()) : nullptr};
 }
 
+// agp_fit_update_batch, the slab the grown fits share (g: the geometry of the GROWN size; alpha: information; logsum and
+// flags - 4 ints per problem - are one contiguous range, downloaded as one); the grown training features of every
+// problem follow on the same WsLayout
+struct UpdateBatchRegions {
+  double *A, *invd, *alpha, *z, *logsum;
+  int *flags;
+};
+inline UpdateBatchRegions carve_update_batch(WsLayout &ws, const BatchGeometry &g) {
+  return {ws.take<double>(g.slabs()),   ws.take<double>(g.images()),     ws.take<double>(g.vectors()),
+          ws.take<double>(g.vectors()), ws.take<double>((size_t)g.cp2), ws.take<int>(4 * (size_t)g.cp2)};
+}
+
+// agp_fit_update_batch, the scratch that goes with the call: new targets and variances (leading dimension mp2), the
+// staged host features, then the descriptor tables of the grow, cross-covariance and prior launches - the tail of the
+// region, laid out alike in the pinned staging area
+struct UpdateBatchScratch {
+  double *ynew, *yvar, *xstage;
+  void *grow_table, *cross_table, *gram_table;
+};
+inline UpdateBatchScratch carve_update_batch_scratch(WsLayout &ws, const BatchGeometry &g, size_t mp2, bool has_yvar, size_t stage_words,
+                                                     size_t grow_table_bytes, size_t cross_table_bytes, size_t gram_table_bytes) {
+  return {ws.take<double>((size_t)g.count * mp2), has_yvar ? ws.take<double>((size_t)g.count * mp2) : nullptr,
+          ws.take<double>(stage_words),           ws.take<char>(grow_table_bytes),
+          ws.take<char>(cross_table_bytes),       ws.take<char>(gram_table_bytes)};
+}
+
 // the batched gradients, ws_A (z: then alpha, in place; flags: 4 ints per problem)
 struct GradientBatchRegions {
   double *A, *invd, *z, *yvar, *logsum, *quad;

@@ -1626,6 +1626,77 @@ def predict_batch(fit_models, features, what="marginal"):
     return out
 
 
+def update_batch(fit_models, datasets):
+    """`fit_models[b].update(datasets[b])` for several fits of ONE size in lock step (agp_fit_update_batch): the third verb
+    after fit_batch and predict_batch - a caller who keeps many small models and conditions each on every new epoch of
+    observations pays the launch chain of an update once per batch, not once per model.  fit_models: FitModels holding
+    plain fp64 GPFits of one size on one context (of fit, fit_batch, update or update_batch, in any mix); datasets: as
+    many RegressionDatasets, each with the same number of points.  Each model's mean function is removed from its
+    targets.  Returns the FitModels of the grown fits (rows() == old + m, training features concatenated); raises like
+    `update` for the first problem whose covariance has NaN or is not positive definite, after destroying every handle."""
+    fit_models, datasets = list(fit_models), list(datasets)
+    count = len(fit_models)
+    if count == 0:
+        raise ValueError("update_batch: at least one fit model")
+    if len(datasets) != count:
+        raise ValueError("update_batch: as many datasets as fit models")
+    for fm in fit_models:
+        if not isinstance(fm, FitModel) or type(fm._fit) is not GPFit or fm._fit.mixed_precision:
+            raise ValueError("update_batch: every fit must be a plain fp64 GPFit (fit / fit_batch / update)")
+    ctx = fit_models[0]._model._ctx()
+    feats, fsets = [], []
+    for fm, ds in zip(fit_models, datasets):
+        if fm._model._ctx() is not ctx:
+            raise ValueError("update_batch: every fit model must live on one context")
+        f = _values_of(ds.features)
+        if has_linear_combinations(f) or has_linear_combinations(fm._fit.train_features):
+            raise ValueError("update_batch: LinearCombination features are not supported (update one model at a time)")
+        feats.append(f)
+        fsets.append(fm._model.covariance_function_.features(f))
+    m = fsets[0].n
+    if any(fs.n != m for fs in fsets):
+        raise ValueError("update_batch: every dataset must have the same number of points")
+    ys, yvs = [], []
+    for fm, fs, ds in zip(fit_models, fsets, datasets):
+        y, yv = fm._model._targets(fs, ds.targets)  # mean function removed (ModelBase::update -> remove_from)
+        ys.append(y)
+        yvs.append(yv)
+    structs = [fs.as_struct() for fs in fsets]
+    Y = np.asfortranarray(np.stack(ys, axis=1))
+    have_var = any(v is not None for v in yvs)
+    V = np.asfortranarray(np.stack([np.zeros(m) if v is None else v for v in yvs], axis=1)) if have_var else None
+    handles = []
+    out = (C.c_void_p * count)()
+    status = (C.c_int * count)()
+    try:
+        for fm in fit_models:  # private handles: the context's small kernel cache may evict while the batch is assembled
+            handles.append(ctx.private_kernel(fm._model.covariance_function_))
+        kernels = (C.c_void_p * count)(*handles)
+        olds = (C.c_void_p * count)(*[fm._fit._h.value for fm in fit_models])
+        fptrs = (C.c_void_p * count)(*[C.addressof(st) for st in structs])
+        ctx._check(ctx._lib.agp_fit_update_batch(ctx._h, count, kernels, olds, fptrs, _ptr(Y), m, _ptr(V) if have_var else None, m, out,
+                                                 None, 0, None, status), "agp_fit_update_batch")
+    finally:
+        for kh in handles:
+            ctx._lib.agp_kernel_destroy(kh)
+    for b in range(count):
+        if status[b] != capi.AGP_OK:
+            pivot = ctx._lib.agp_fit_failed_pivot(C.c_void_p(out[b]))
+            for h in out:
+                ctx._lib.agp_fit_destroy(C.c_void_p(h))
+            ctx._check(status[b], f"agp_fit_update_batch: problem {b} (pivot {pivot})")
+    grown = []
+    for b, (fm, fs) in enumerate(zip(fit_models, fsets)):
+        old_feats = _values_of(fm._fit.train_features)
+        try:
+            new_feats = np.concatenate([np.asarray(old_feats, dtype=np.float64).reshape(fm._fit.rows(), -1),
+                                        np.asarray(feats[b], dtype=np.float64).reshape(fs.n, -1)])
+        except (TypeError, ValueError):  # feature containers numpy cannot stack: keep them side by side
+            new_feats = (old_feats, feats[b])
+        grown.append(FitModel(fm._model, GPFit(ctx, C.c_void_p(out[b]), fm._fit.rows() + fs.n, new_feats)))
+    return grown
+
+
 class _GradientProblem:
     """the host side of one gradient problem: flattened features, targets (mean removed) and variances, the slot table
     of the covariance function (param_slots), its ctypes form and the tangent columns (n x columns, column-major) of

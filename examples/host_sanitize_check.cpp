@@ -268,6 +268,20 @@ void layouts_under_sanitizers() {
           const agp::FitBatchTables r = agp::carve_fit_batch_tables(w, g, fused, copy_bytes, gram_bytes);
           return std::vector<Region>{{r.copy_table, copy_bytes}, {r.gram_table, gram_bytes}, {r.zpub, D * B * np2}};
         });
+        // agp_fit_update_batch: the slab of the grown fits, then the scratch of the call (mp2 new points per problem)
+        check_layout("carve_update_batch", B * (sA + sI + 2 * np2) + cp2 + 2 * cp2, [&](agp::WsLayout &w) {
+          const agp::UpdateBatchRegions r = agp::carve_update_batch(w, g);
+          return std::vector<Region>{{r.A, D * B * sA}, {r.invd, D * B * sI}, {r.alpha, D * B * np2}, {r.z, D * B * np2}, {r.logsum, D * cp2},
+                                     {r.flags, sizeof(int) * 4 * cp2}};
+        });
+        const size_t mp2 = 2 * (size_t)((n + 3) / 4), stage = fused ? 5 * B * mp2 + 3 : 0;
+        check_layout("carve_update_batch_scratch",
+                     B * mp2 + (has_var ? B * mp2 : 0) + stage + (desc_bytes + up8) / 8 + (copy_bytes + up8) / 8 + (gram_bytes + up8) / 8,
+                     [&](agp::WsLayout &w) {
+                       const agp::UpdateBatchScratch r = agp::carve_update_batch_scratch(w, g, mp2, has_var, stage, desc_bytes, copy_bytes, gram_bytes);
+                       return std::vector<Region>{{r.ynew, D * B * mp2}, {r.yvar, D * B * mp2}, {r.xstage, D * stage}, {r.grow_table, desc_bytes},
+                                                  {r.cross_table, copy_bytes}, {r.gram_table, gram_bytes}};
+                     });
         // the batched gradients: ws_A, ws_aux
         check_layout("carve_gradient_batch", (B * sA + 1) / 2 * 2 + B * sI + B * np2 + (has_var ? B * np2 : 0) + 4 * cp2 + (fused ? B * np2 : 0),
                      [&](agp::WsLayout &w) {

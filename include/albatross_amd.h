@@ -643,6 +643,42 @@ AGP_API int agp_crps_normal(agp_context *ctx, const double *mu, const double *si
 AGP_API int agp_fit_update(agp_context *ctx, const agp_kernel *k, const agp_fit *old, const agp_features *x_new, const double *y_new,
                    const double *y_var_new, agp_fit **out, double *information, double *log_det);
 
+/* agp_fit_update for `count` fits of one size in lock step: problem b computes what
+ * agp_fit_update(ctx, kernels[b], olds[b], x_new[b], ...) computes - the same algebra, the plain-feature semantics of
+ * cross and prior, the phantom rows when the old size is not a multiple of 128, log determinant = old + 2 sum log
+ * diag(L_S) - but every stage is ONE launch or launch chain for the whole batch, the grown fits are slices of ONE device
+ * allocation, and the call synchronises twice at most: once behind the uploads of host-resident inputs and once at its
+ * end, where status words and log sums come down together.  What a caller does who keeps many small models and
+ * conditions each on every new epoch of observations.
+ *   olds[b]          plain fp64 fits of this context with training features and forward-substituted targets, all of one
+ *                    padded size, one number of real rows and the same phantom ranges.  They need NOT lie at one stride
+ *                    or come from one call (their factors, tile images, z and features are gathered through a descriptor
+ *                    table); they stay valid and are not modified
+ *   x_new[b]         the m > 0 further features of problem b: one m and one location for all problems, dim / scale columns
+ *                    / id convention as olds[b] (dim may differ between problems)
+ *   y_new, ldy       their targets with the mean function removed, m x count column-major at that location (ldy = 0: one
+ *                    vector shared by all); y_var_new, ldv likewise, or NULL
+ *   out[b]           an ordinary agp_fit of old + m observations (agp_predict_*, agp_solve, agp_fit_download_*,
+ *                    agp_fit_update, agp_fit_update_batch again).  The grown fits of one call lie at constant strides in one
+ *                    allocation that is released with the last of them, and reference no memory of the old fits; when the
+ *                    old size is a multiple of 128 they have no phantom rows and agp_predict_batch runs them in lock step
+ *   information, ldi (optional, host) the real rows of every good problem, old observations first; log_det[b] (optional, host)
+ *   status[b]        AGP_OK / AGP_ERR_NAN_INPUT / AGP_ERR_NOT_POSITIVE_DEFINITE per problem; a failed problem leaves the
+ *                    others and its own column of `information` untouched.  A problem that is not positive definite reports
+ *                    the pivot through its handle like agp_fit_update (real rows of the old fit + local pivot); a NaN
+ *                    problem gets a handle that only carries its status, as in agp_fit_create_batch
+ * The return value is about the call as a whole: when it is not AGP_OK every out[b] is NULL and nothing is left to
+ * destroy.  A fit without forward-substituted targets: AGP_ERR_UNSUPPORTED.  A mixed-precision or failed fit, a fit of
+ * another context, any mismatch, count outside 1 .. 65535, ldy / ldv / ldi too short: AGP_ERR_INVALID_ARGUMENT.  A
+ * rejected call writes nothing, out and status included.  No float atomics, fixed-order reductions: two identical calls
+ * are bit-identical, and no problem's bits depend on its neighbours (but for the tile shape of the batched MFMA products,
+ * which follows the number of tiles of the whole launch, as agp_predict_batch documents).  With profiling on,
+ * agp_last_stage_ms reports 0 grow, cross covariance and V, 1 Schur complement and its factor, 2 back substitution. */
+AGP_API int agp_fit_update_batch(agp_context *ctx, int count, const agp_kernel *const *kernels, const agp_fit *const *olds,
+                                 const agp_features *const *x_new, const double *y_new, int64_t ldy,
+                                 const double *y_var_new, int64_t ldv, agp_fit **out, double *information, int64_t ldi,
+                                 double *log_det, int *status);
+
 /* ---- leave-one-out fast path (the tuner's LeaveOneOutLikelihood objective; the metric and its gradient: agp_loo_nll_gradient) --- */
 /* diag(K^-1): SerializableLDLT::inverse_diagonal (src/eigen/serializable_ldlt.hpp:
  * 137-199: R = L^-1, then the squared column norms of R).  out: n doubles. */

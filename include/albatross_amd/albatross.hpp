@@ -2527,6 +2527,81 @@ BatchPrediction<ModelType, FeatureType, P> predict_batch(const std::vector<FitMo
   return BatchPrediction<ModelType, FeatureType, P>(&fit_models, &features_per_model);
 }
 
+// `fit_models[b].update(datasets[b])` for SEVERAL fits of one size in lock step (agp_fit_update_batch): the third verb after
+// fit_batch and predict_batch.  Every dataset has the same number of points; the fits may come from fit, fit_batch, update
+// or update_batch in any mix.  Each model's mean function is removed from its targets.  The grown fits are ordinary
+// FitModels that share one device allocation.  Throws like `update` for the first problem whose covariance has NaN or is
+// not positive definite (every handle of the call is released first).
+template <typename ModelType, typename FeatureType>
+std::vector<FitModel<ModelType, FeatureType>> update_batch(const std::vector<FitModel<ModelType, FeatureType>> &fit_models,
+                                                           const std::vector<RegressionDataset<FeatureType>> &datasets) {
+  if (fit_models.empty() || fit_models.size() != datasets.size())
+    throw std::invalid_argument("update_batch: one dataset per fit model, at least one");
+  const std::size_t count = fit_models.size(), m = datasets[0].features.size();
+  auto ctx = fit_models[0].get_fit().context;
+  bool have_var = false;
+  for (const auto &d : datasets) {
+    if (d.features.size() != m || d.targets.size() != m) throw std::invalid_argument("update_batch: every dataset must have the same number of points");
+    if (!d.targets.covariance.empty() && d.targets.covariance.size() != m)
+      throw std::invalid_argument("target covariance must be diagonal (one variance per target)");
+    have_var = have_var || !d.targets.covariance.empty();
+  }
+  std::vector<std::unique_ptr<detail::KernelHolder>> holders;
+  std::vector<detail::Flat> flats;
+  flats.reserve(count);
+  std::vector<const agp_kernel *> kernels(count);
+  std::vector<const agp_fit *> olds(count);
+  std::vector<const agp_features *> views(count);
+  Vector y(m * count), yv(have_var ? m * count : 0, 0.);
+  std::size_t rows = 0;
+  for (std::size_t b = 0; b < count; ++b) {
+    const auto &fm = fit_models[b];
+    const auto &d = datasets[b];
+    holders.emplace_back(new detail::KernelHolder(fm.get_model().get_covariance().program()));
+    flats.push_back(detail::flatten(fm.get_model().get_covariance(), d.features));
+    kernels[b] = holders[b]->k;
+    olds[b] = fm.get_fit().handle.get();
+    Vector zero(m, 0.);
+    fm.get_model().add_mean(d.features, &zero);  // remove_from == subtract what add_to adds (ModelBase::update)
+    for (std::size_t i = 0; i < m; ++i) {
+      y[b * m + i] = d.targets.mean[i] - zero[i];
+      if (!d.targets.covariance.empty()) yv[b * m + i] = d.targets.covariance[i];
+    }
+    rows = std::max(rows, fm.get_fit().train_features.size() + m);
+  }
+  for (std::size_t b = 0; b < count; ++b) views[b] = &flats[b].view;
+  std::vector<agp_fit *> handles(count, nullptr);
+  std::vector<int> status(count, AGP_OK);
+  std::vector<double> info(rows * count), logdet(count);
+  const int st = agp_fit_update_batch(ctx->ctx, (int)count, kernels.data(), olds.data(), views.data(), y.data(), (std::int64_t)m,
+                                      have_var ? yv.data() : nullptr, (std::int64_t)m, handles.data(), info.data(), (std::int64_t)rows,
+                                      logdet.data(), status.data());
+  detail::check(st, ctx->ctx, "agp_fit_update_batch");
+  std::vector<std::shared_ptr<agp_fit>> owned;
+  for (agp_fit *h : handles) owned.emplace_back(h, [ctx](agp_fit *p) { agp_fit_destroy(p); });
+  for (std::size_t b = 0; b < count; ++b)
+    if (status[b] != AGP_OK) {
+      std::string what = "agp_fit_update_batch: problem " + std::to_string(b);
+      if (status[b] == AGP_ERR_NOT_POSITIVE_DEFINITE) what += " (pivot " + std::to_string((long long)agp_fit_failed_pivot(handles[b])) + ")";
+      owned.clear();
+      detail::check(status[b], ctx->ctx, what.c_str());
+    }
+  std::vector<FitModel<ModelType, FeatureType>> out;
+  for (std::size_t b = 0; b < count; ++b) {
+    const GPFit<FeatureType> &old = fit_models[b].get_fit();
+    GPFit<FeatureType> fit;
+    fit.train_features = old.train_features;  // concatenate(...), gp.hpp:387
+    fit.train_features.insert(fit.train_features.end(), datasets[b].features.begin(), datasets[b].features.end());
+    const std::size_t n = fit.train_features.size();
+    fit.information.assign(info.begin() + (std::ptrdiff_t)(b * rows), info.begin() + (std::ptrdiff_t)(b * rows + n));
+    fit.log_determinant = logdet[b];
+    fit.context = ctx;
+    fit.handle = owned[b];
+    out.emplace_back(fit_models[b].get_model(), std::move(fit));
+  }
+  return out;
+}
+
 // factories, gp.hpp:507-537
 template <typename CovFunc>
 GaussianProcessRegression<CovFunc, ZeroMean> gp_from_covariance(const CovFunc &cov,
