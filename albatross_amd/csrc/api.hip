@@ -1537,15 +1537,18 @@ int agp_nll_batch(agp_context *c, int count, const agp_kernel *const *kernels, c
   return AGP_OK;
 }
 
-// problem's training features inside the slab of its batch: coordinates, equality ids, scale columns
-static FeatView carve_features(WsLayout &ws, const agp_features *f) {
+// problem's training features inside the slab of its batch: coordinates, equality ids, scale columns, each of the n rows
+// of the batch (a ragged problem has fewer of its own: the rest are phantom rows)
+static FeatView carve_features(WsLayout &ws, const agp_features *f, long long n) {
   FeatView v;
-  v.n = f->n; v.dim = f->dim; v.nsc = f->n_scale_columns; v.meas = 0;
-  v.coords = ws.take<double>((size_t)f->n * (size_t)f->dim);
-  v.ids = f->eq_id ? ws.take<long long>((size_t)f->n) : nullptr;
-  v.scales = f->n_scale_columns > 0 ? ws.take<double>((size_t)f->n * (size_t)f->n_scale_columns) : nullptr;
+  v.n = n; v.dim = f->dim; v.nsc = f->n_scale_columns; v.meas = 0;
+  v.coords = ws.take<double>((size_t)n * (size_t)f->dim);
+  v.ids = f->eq_id ? ws.take<long long>((size_t)n) : nullptr;
+  v.scales = f->n_scale_columns > 0 ? ws.take<double>((size_t)n * (size_t)f->n_scale_columns) : nullptr;
   return v;
 }
+
+}  // extern "C"
 
 // B independent fits of one shape in lock step: the Fit<GPFit> constructor (models/gp.hpp:61-69) for `count` datasets /
 // parameter vectors at once.  Where the reference's users live - N of a few hundred to a few thousand
@@ -1555,22 +1558,38 @@ static FeatView carve_features(WsLayout &ws, const agp_features *f) {
 // On the shared front end (batch_front.h): one allocation of its own that the fits keep (batch_layout.h:
 // carve_fit_batch, then each problem's training features), the tables of the call from dev_malloc
 // (carve_fit_batch_tables), status words per problem, the look-ahead schedule where the predicate asks for it.
-int agp_fit_create_batch(agp_context *c, int count, const agp_kernel *const *kernels, const agp_features *const *features,
-                         const double *y, int64_t ldy, const double *y_var, int64_t ldv, agp_fit **out, double *information,
-                         int64_t ldi, double *log_det, int *status) {
+//
+// `ragged` (agp_fit_create_batch_ragged) admits problems of unequal sizes n_b.  The padded size n of the call is the
+// largest of them; problem b is the fit of diag(K_b, I) with the trailing phantom rows [n_b, n) (common.h:
+// agp_fit::phantom).  Its Gram launch runs on a view of the n_b real rows - so the NaN flag and the target variances are
+// those of real rows only -, one table-driven pad launch behind it writes the phantom rows of the slab, of z and of the
+// training features (ragged_batch.hip), and from there on the chain below is the one of equal sizes at size n.  With all
+// sizes equal nothing is padded and the two entries run the same launches.  A ragged call checks every argument before
+// it writes anything, out and status included.
+int agp::fit_create_batch(agp_context *c, int count, const agp_kernel *const *kernels, const agp_features *const *features,
+                          const double *y, int64_t ldy, const double *y_var, int64_t ldv, agp_fit **out, double *information,
+                          int64_t ldi, double *log_det, int *status, bool ragged) {
   if (!c || count <= 0 || count > BATCH_MAX_PROBLEMS || !kernels || !features || !y || !out || !status) return AGP_ERR_INVALID_ARGUMENT;
   agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
+  long long n = 0;
+  bool equal = true;
+  int st = AGP_OK;
+  if (ragged) {
+    if ((st = check_batch_problems_ragged(count, kernels, features, ldy, y_var, ldv, &n, &equal)) != AGP_OK) return st;
+    if (information && ldi < n) return AGP_ERR_INVALID_ARGUMENT;
+  }
   AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   for (int b = 0; b < count; ++b) { out[b] = nullptr; status[b] = AGP_ERR_INVALID_ARGUMENT; }
-  long long n = 0;
-  int st = check_batch_problems(count, kernels, features, ldy, y_var, ldv, &n);
-  if (st != AGP_OK) return st;
-  if (information && ldi < n) return AGP_ERR_INVALID_ARGUMENT;
+  if (!ragged) {
+    if ((st = check_batch_problems(count, kernels, features, ldy, y_var, ldv, &n)) != AGP_OK) return st;
+    if (information && ldi < n) return AGP_ERR_INVALID_ARGUMENT;
+  }
+  const bool padded = !equal;  // some problem has phantom rows
   const BatchGeometry g = batch_geometry(n, count);
   hipStream_t s = ctx->stream;
   WsLayout size;
   carve_fit_batch(size, g, y_var != nullptr);
-  for (int b = 0; b < count; ++b) carve_features(size, features[b]);
+  for (int b = 0; b < count; ++b) carve_features(size, features[b], n);
   const size_t bytes = size.bytes();
   double *base = nullptr;
   if (ctx->pool_batch && ctx->pool_batch_bytes == bytes) {
@@ -1601,8 +1620,10 @@ int agp_fit_create_batch(agp_context *c, int count, const agp_kernel *const *ker
   } while (0)
   const int loc = features[0]->location;
   const hipMemcpyKind kind = loc == AGP_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-  if ((st = upload_problem_columns(ctx, y, ldy, n, count, loc, r.z, g.np2)) != AGP_OK) return fail(st);
-  if (y_var && (st = upload_problem_columns(ctx, y_var, ldv, n, count, loc, r.yvar, g.np2)) != AGP_OK) return fail(st);
+  if (!padded) {
+    if ((st = upload_problem_columns(ctx, y, ldy, n, count, loc, r.z, g.np2)) != AGP_OK) return fail(st);
+    if (y_var && (st = upload_problem_columns(ctx, y_var, ldv, n, count, loc, r.yvar, g.np2)) != AGP_OK) return fail(st);
+  }
   // train_features = features (gp.hpp:63): a copy per fit, inside the batch's allocation (no allocation per problem).
   // Device-resident inputs: ONE table-driven copy launch for all problems (pub.h: CopyItem) instead of a copy kernel per array
   std::vector<CopyItem> copies;
@@ -1614,20 +1635,42 @@ int agp_fit_create_batch(agp_context *c, int count, const agp_kernel *const *ker
     if (words > copy_max) copy_max = words;
     return hipSuccess;
   };
+  // (a padded call: the n_b values of column b of the targets and variances go the same way, what follows them in the
+  // column is never read; the scale columns land at the stride n of the padded features)
+  std::vector<RaggedPadItem> pads(padded ? (size_t)count : 0);
   for (int b = 0; b < count; ++b) {
     agp_fit *fit = new (std::nothrow) agp_fit();
     if (!fit) return fail(AGP_ERR_INVALID_ARGUMENT);
     fits[(size_t)b] = fit;
     const agp_features *f = features[b];
-    const FeatView v = carve_features(ws, f);
-    BATCH_CHECK(stage(v.coords, f->coords, n * (long long)f->dim));
-    BATCH_CHECK(stage(v.ids, f->eq_id, n));
-    BATCH_CHECK(stage(v.scales, f->scales, n * (long long)f->n_scale_columns));
+    const long long nb = f->n;
+    const FeatView v = carve_features(ws, f, n);
+    BATCH_CHECK(stage(v.coords, f->coords, nb * (long long)f->dim));
+    BATCH_CHECK(stage(v.ids, f->eq_id, nb));
+    if (nb == n) BATCH_CHECK(stage(v.scales, f->scales, n * (long long)f->n_scale_columns));
+    else
+      for (int k = 0; k < f->n_scale_columns; ++k) BATCH_CHECK(stage(v.scales + (size_t)k * (size_t)n, f->scales + (size_t)k * (size_t)nb, nb));
     fit->train.v = v;  // (not owned: DeviceFeatures::release has nothing to free)
+    if (padded) {
+      BATCH_CHECK(stage(r.z + (size_t)b * (size_t)g.np2, y + (size_t)b * (size_t)ldy, nb));
+      if (y_var) BATCH_CHECK(stage(r.yvar + (size_t)b * (size_t)g.np2, y_var + (size_t)b * (size_t)ldv, nb));
+      RaggedPadItem &pi = pads[(size_t)b];
+      pi.A = r.A + (size_t)b * (size_t)g.stride_A;
+      pi.z = r.z + (size_t)b * (size_t)g.np2;
+      pi.coords = const_cast<double *>(v.coords);
+      pi.ids = const_cast<long long *>(v.ids);
+      pi.scales = const_cast<double *>(v.scales);
+      pi.nb = nb;
+      pi.dim = f->dim;
+      pi.nsc = f->n_scale_columns;
+    }
   }
   // device scratch of the call: the copy table and the Gram table of the batched launches, the z slots of the fused panels
   const bool fused_panels = batched_fused_panels(ctx, g, /*allow_lookahead=*/true);
-  const size_t copy_bytes = sizeof(CopyItem) * copies.size(), gram_bytes = gram_batch_table_bytes(count);
+  // (the pad table of a padded call follows the copy table in the same region)
+  const size_t copy_items_bytes = sizeof(CopyItem) * copies.size(), pad_bytes = sizeof(RaggedPadItem) * pads.size();
+  const size_t pad_off = padded ? (copy_items_bytes + 15) / 16 * 16 : copy_items_bytes;
+  const size_t copy_bytes = pad_off + pad_bytes, gram_bytes = gram_batch_table_bytes(count);
   WsLayout tsize;
   carve_fit_batch_tables(tsize, g, fused_panels, copy_bytes, gram_bytes);
   void *tables = nullptr;
@@ -1640,10 +1683,17 @@ int agp_fit_create_batch(agp_context *c, int count, const agp_kernel *const *ker
   // 256 fits of N = 512)
   const size_t gram_off = (size_t)(static_cast<char *>(t.gram_table) - static_cast<char *>(t.copy_table));
   char *pinned = tables ? static_cast<char *>(host_stage(ctx, gram_off + gram_bytes)) : nullptr;
-  if (!copies.empty()) {
+  if (padded && !tables) {
+    ctx->last_error = "agp_fit_create_batch_ragged: descriptor tables";
+    return fail(AGP_ERR_HIP);
+  }
+  std::vector<char> pageable_tables;
+  if (copy_bytes > 0) {
     if (tables) {
-      const void *src = copies.data();
-      if (pinned) { std::memcpy(pinned, copies.data(), copy_bytes); src = pinned; }
+      char *src = pinned;
+      if (!src) { pageable_tables.resize(copy_bytes); src = pageable_tables.data(); }
+      if (!copies.empty()) std::memcpy(src, copies.data(), copy_items_bytes);
+      if (padded) std::memcpy(src + pad_off, pads.data(), pad_bytes);
       BATCH_CHECK(hipMemcpyAsync(t.copy_table, src, copy_bytes, hipMemcpyHostToDevice, s));
       if (!pinned) BATCH_CHECK(hipStreamSynchronize(s));  // (pageable source)
       launch_copy_table(s, static_cast<const CopyItem *>(t.copy_table), (long long)copies.size(), copy_max);
@@ -1663,9 +1713,15 @@ int agp_fit_create_batch(agp_context *c, int count, const agp_kernel *const *ker
   }
   {
     BatchGramTables gram(g, kernels, r.A, r.yvar, g.np2, r.flags, 4);
-    for (int b = 0; b < count; ++b) gram.set_view(b, fits[(size_t)b]->train.v);
+    for (int b = 0; b < count; ++b) {
+      FeatView v = fits[(size_t)b]->train.v;
+      if (padded) { v.sstride = n; v.n = features[b]->n; }  // the real rows of the padded features
+      gram.set_view(b, v);
+    }
     if ((st = launch_batch_grams(ctx, g, gram, kernels, t.gram_table, pinned ? pinned + gram_off : nullptr)) != AGP_OK) return fail(st);
   }
+  if (padded)
+    launch_ragged_pad(s, reinterpret_cast<const RaggedPadItem *>(static_cast<const char *>(t.copy_table) + pad_off), count, n, g.lda);
   factor_batch(ctx, g, /*allow_lookahead=*/true, r.A, r.invd, r.z, r.flags, 4, r.logsum, t.zpub);
   // information = L^-T (L^-1 y), gp.hpp:68
   if (coop) {
@@ -1690,8 +1746,9 @@ int agp_fit_create_batch(agp_context *c, int count, const agp_kernel *const *ker
   if (information)
     for (int b = 0; b < count; ++b) {
       const int *fl = &h_flags[4 * (size_t)b];
-      if (!fl[0] && !fl[1])
-        BATCH_CHECK(hipMemcpy(information + (size_t)b * (size_t)ldi, r.alpha + (size_t)b * (size_t)g.np2, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+      if (!fl[0] && !fl[1])  // (the real rows: trailing phantom rows follow them)
+        BATCH_CHECK(hipMemcpy(information + (size_t)b * (size_t)ldi, r.alpha + (size_t)b * (size_t)g.np2,
+                              sizeof(double) * (size_t)features[b]->n, hipMemcpyDeviceToHost));
     }
   agp_fit_slab *slab = new (std::nothrow) agp_fit_slab();
   if (!slab) return fail(AGP_ERR_INVALID_ARGUMENT);
@@ -1710,6 +1767,10 @@ int agp_fit_create_batch(agp_context *c, int count, const agp_kernel *const *ker
     fit->invd = r.invd + (size_t)b * (size_t)g.stride_I;
     fit->alpha = r.alpha + (size_t)b * (size_t)g.np2;
     fit->z = r.z + (size_t)b * (size_t)g.np2;
+    if (features[b]->n < n) {  // (a pivot is a real row: the phantom rows come last and never fail)
+      fit->n_real = features[b]->n;
+      fit->phantom.emplace_back((long long)features[b]->n, n);
+    }
     const int *fl = &h_flags[4 * (size_t)b];
     fit->failed_pivot = fl[1] ? (int64_t)fl[1] - 1 : -1;
     fit->log_det = 2. * h_log[(size_t)b];
@@ -1721,6 +1782,22 @@ int agp_fit_create_batch(agp_context *c, int count, const agp_kernel *const *ker
 #undef BATCH_CHECK
   return AGP_OK;
 }
+
+extern "C" {
+
+int agp_fit_create_batch(agp_context *c, int count, const agp_kernel *const *kernels, const agp_features *const *features,
+                         const double *y, int64_t ldy, const double *y_var, int64_t ldv, agp_fit **out, double *information,
+                         int64_t ldi, double *log_det, int *status) {
+  return fit_create_batch(c, count, kernels, features, y, ldy, y_var, ldv, out, information, ldi, log_det, status, false);
+}
+
+int agp_fit_create_batch_ragged(agp_context *c, int count, const agp_kernel *const *kernels, const agp_features *const *features,
+                                const double *y, int64_t ldy, const double *y_var, int64_t ldv, agp_fit **out, double *information,
+                                int64_t ldi, double *log_det, int *status) {
+  return fit_create_batch(c, count, kernels, features, y, ldy, y_var, ldv, out, information, ldi, log_det, status, true);
+}
+
+int64_t agp_fit_padded_size(const agp_fit *fit) { return fit ? fit->n : 0; }
 
 // ---- solve -----------------------------------------------------------------
 int agp_solve(agp_context *ctx, const agp_fit *fit, const double *rhs, int64_t nrhs, double *out, int location) {

@@ -20,6 +20,27 @@ int check_batch_problems(int count, const agp_kernel *const *kernels, const agp_
   return AGP_OK;
 }
 
+int check_batch_problems_ragged(int count, const agp_kernel *const *kernels, const agp_features *const *features, int64_t ldy,
+                                const double *y_var, int64_t ldv, long long *n_out, bool *equal) {
+  if (count <= 0 || count > BATCH_MAX_PROBLEMS || !kernels || !features) return AGP_ERR_INVALID_ARGUMENT;
+  long long n = 0;
+  bool same = true;
+  for (int b = 0; b < count; ++b) {
+    if (!kernels[b] || !features[b] || features[b]->n <= 0 || features[b]->location != features[0]->location)
+      return AGP_ERR_INVALID_ARGUMENT;
+    if (features[b]->n != features[0]->n) same = false;
+    if (features[b]->n > n) n = features[b]->n;
+  }
+  if ((ldy != 0 && ldy < n) || (y_var && ldv != 0 && ldv < n)) return AGP_ERR_INVALID_ARGUMENT;
+  for (int b = 0; b < count; ++b) {
+    const int st = validate_features(features[b]);
+    if (st != AGP_OK) return st;
+  }
+  *n_out = n;
+  *equal = same;
+  return AGP_OK;
+}
+
 int upload_problem_columns(agp_context *ctx, const double *src, int64_t ld, long long n, long long columns, int location,
                            double *dst, long long ld_dst) {
   const hipMemcpyKind kind = location == AGP_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;

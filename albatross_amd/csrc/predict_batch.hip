@@ -14,6 +14,12 @@
 //              cov_b = full symmetric P_b, ld = m   symmetrize_pack_batch_kernel
 //   mean only: mean_b = K*_b^T alpha_b without K*   mean_fast_batch_kernel
 //
+// Fits with phantom rows (agp_fit_create_batch_ragged, agp_fit_update_batch; common.h: agp_fit::phantom) run in lock step
+// like any other: every kernel works on the padded size.  The covariance with a phantom row is zero by definition, but
+// its feature row holds a copy of a real feature, so the phantom rows of K*_b are zeroed by ONE table-driven launch per
+// sub-batch (any number of ranges per problem; ragged_batch.hip) right behind the cross covariance.  The mean-only kernel
+// needs nothing of the kind: alpha_b is exactly zero on phantom rows and the covariance there is finite.
+//
 // The table-driven covariance launches cover the radial<Euclidean> [+ noise] trees (gram_fast.h).  When every problem of
 // a run has such a tree with one operator and one dimension they are one launch; otherwise every problem gets a launch
 // of its own - the SAME kernel on its table entry when its tree has the shape, the generic program launchers of gram.hip
@@ -25,7 +31,7 @@
 #include <limits>
 #include <vector>
 
-#include "api_internal.h"
+#include "batch_front.h"
 #include "gram_fast.h"
 
 namespace agp {
@@ -236,12 +242,12 @@ int agp_predict_batch(agp_context *c, int count, const agp_kernel *const *kernel
   if (out_location != AGP_HOST && out_location != AGP_DEVICE) return AGP_ERR_INVALID_ARGUMENT;
   agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
   if (!kernels[0] || !fits[0] || !xs[0]) return AGP_ERR_INVALID_ARGUMENT;
-  const long long m = xs[0]->n, n_real = fit_real_rows(fits[0]);
+  const long long m = xs[0]->n, n_pad = fits[0]->n;
   const int loc = xs[0]->location;
   for (int b = 0; b < count; ++b) {
     const agp_fit *f = fits[b];
     if (!kernels[b] || !f || !xs[b] || validate_features(xs[b]) != AGP_OK) return AGP_ERR_INVALID_ARGUMENT;
-    if (xs[b]->n != m || xs[b]->location != loc || f->ctx != c || f->mixed || fit_real_rows(f) != n_real) return AGP_ERR_INVALID_ARGUMENT;
+    if (xs[b]->n != m || xs[b]->location != loc || f->ctx != c || f->mixed || f->n != n_pad) return AGP_ERR_INVALID_ARGUMENT;
     // a fit without training features (agp_factor_create), or whose features have another dimension than the test points
     if (f->fail_status == AGP_OK && (!f->A || !f->invd || !f->alpha || !f->train.v.coords)) return AGP_ERR_INVALID_ARGUMENT;
     if (f->train.v.coords && xs[b]->dim != f->train.v.dim) return AGP_ERR_INVALID_ARGUMENT;
@@ -256,7 +262,7 @@ int agp_predict_batch(agp_context *c, int count, const agp_kernel *const *kernel
   // ---- the runs: maximal stretches of good fits whose factors, tile images and information vectors lie at one stride
   auto lockstep_ok = [&](int b) {
     const agp_fit *f = fits[b];
-    return f->fail_status == AGP_OK && f->phantom.empty();
+    return f->fail_status == AGP_OK;
   };
   std::vector<Run> runs;
   for (int b = 0; b < count;) {
@@ -302,19 +308,32 @@ int agp_predict_batch(agp_context *c, int count, const agp_kernel *const *kernel
     }
   }
 
+  // the phantom ranges of the fits in lock-step runs (modes that form V only)
+  RangeTable phantoms;
+  if (any_lockstep && mode != 0) {
+    std::vector<char> in_run((size_t)count, 0);
+    for (const Run &r : runs)
+      for (int i = 0; r.count > 1 && i < r.count; ++i) in_run[(size_t)(r.first + i)] = 1;
+    for (int b = 0; b < count; ++b) {
+      phantoms.begin_problem();
+      if (in_run[(size_t)b])
+        for (const auto &ph : fits[b]->phantom) phantoms.add(ph.first, ph.second);
+    }
+  }
   // ---- descriptor tables of the whole call: device scratch + the context's pinned staging area, entry b = problem b
   const size_t item_bytes = (sizeof(PredictBatchItem) * (size_t)count + 15) / 16 * 16;
   const size_t gram_bytes = mode == 2 ? (gram_batch_table_bytes(count) + 15) / 16 * 16 : 0;
+  const size_t range_off = item_bytes + gram_bytes, range_bytes = phantoms.any() ? phantoms.bytes() : 0;
   void *tables = nullptr;
   char *pinned = nullptr;
   std::vector<PredictBatchItem> pageable;
   if (any_lockstep) {
-    if (dev_malloc(&tables, item_bytes + gram_bytes) != hipSuccess) {
+    if (dev_malloc(&tables, range_off + range_bytes) != hipSuccess) {
       (void)hipGetLastError();
       ctx->last_error = "agp_predict_batch: descriptor tables";
       return AGP_ERR_HIP;
     }
-    pinned = static_cast<char *>(host_stage(ctx, item_bytes + gram_bytes));
+    pinned = static_cast<char *>(host_stage(ctx, range_off + range_bytes));
     if (!pinned) pageable.resize((size_t)count);
   }
   struct FreeTables { void *p; ~FreeTables() { if (p) (void)dev_free(p); } } free_tables{tables};
@@ -327,6 +346,17 @@ int agp_predict_batch(agp_context *c, int count, const agp_kernel *const *kernel
     (void)hipStreamSynchronize(s);
     return code;
   };
+  std::vector<char> pageable_ranges;
+  if (range_bytes > 0) {  // one upload for the whole call
+    char *src = pinned ? pinned + range_off : nullptr;
+    if (!src) { pageable_ranges.resize(range_bytes); src = pageable_ranges.data(); }
+    phantoms.write(src);
+    if (hipMemcpyAsync(static_cast<char *>(tables) + range_off, src, range_bytes, hipMemcpyHostToDevice, s) != hipSuccess) {
+      ctx->last_error = "agp_predict_batch: phantom range table";
+      return finish(AGP_ERR_HIP);
+    }
+    if (!pinned) (void)hipStreamSynchronize(s);  // (pageable source)
+  }
   // Test features of the lock-step runs on the device.  Device-resident arrays are used where they are.  Host arrays go
   // into ONE allocation for the whole call (coordinates | equality ids | scale columns per problem; consecutive problems
   // that share their arrays share the copy) with ONE synchronisation behind the uploads, as agp_fit_create_batch stages
@@ -386,7 +416,7 @@ int agp_predict_batch(agp_context *c, int count, const agp_kernel *const *kernel
     if (loc == AGP_HOST && total > 0) AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));  // (pageable sources: the one wait of the host path)
   }
 
-  const long long ldv = round_up(n_real, 2), ldc = round_up(m, 2);  // (a run has no phantom rows: its n is n_real)
+  const long long ldv = round_up(n_pad, 2), ldc = round_up(m, 2);  // (V has the padded rows of the fits)
   for (const Run &r : runs) {
     if (r.count == 1) {
       const int b = r.first;
@@ -401,7 +431,7 @@ int agp_predict_batch(agp_context *c, int count, const agp_kernel *const *kernel
       continue;
     }
     const agp_fit *f0 = fits[r.first];
-    const long long rn = f0->n;  // (== n: no phantom rows in a run)
+    const long long rn = f0->n;  // (the padded size)
     const long long cap = predict_batch_cap(ctx, rn, m, mode);
     for (int p0 = 0; p0 < r.count; p0 += (int)cap) {
       const int first = r.first + p0;
@@ -467,6 +497,10 @@ int agp_predict_batch(agp_context *c, int count, const agp_kernel *const *kernel
                       launch_gram(s, dprog, it.X, it.Y, false, false, it.V, ldv, nullptr, nullptr, &kernels[b]->prog);
                     });
         if (st != AGP_OK) return finish(st);
+        bool chunk_phantoms = false;
+        for (long long i = 0; i < cnt && !chunk_phantoms; ++i) chunk_phantoms = !fits[first + (int)i]->phantom.empty();
+        if (chunk_phantoms)
+          launch_zero_row_ranges(s, static_cast<const char *>(tables) + range_off, count, first, cnt, V, (long long)v_elems, ldv, m);
         // mean = cross_cov^T information (gp.hpp:82-85), then V = L^-1 K* (gp.hpp:96,111)
         hipLaunchKernelGGL((colvec_batch_kernel<false>), dim3((unsigned)m, (unsigned)cnt), dim3(256), 0, s, tab, ldv, rn);
         forward_solve_mat_batched(s, f0->A + (size_t)p0 * (size_t)r.dA, r.dA, rn, f0->lda, f0->invd + (size_t)p0 * (size_t)r.dI, r.dI, V,

@@ -6,7 +6,7 @@
 //
 //   grow      old factor (lda0 -> lda1), tile images, z, features -> slab b; phantom identity rows     update_grow_kernel
 //   cross     B_b^T = cov(new_b, train_b) into rows n_pad.. of slab b (m x n_pad, ld = lda1)            update_cross_fast_kernel
-//             phantom columns <- 0                                                                      update_zero_columns_kernel
+//             phantom columns <- 0 (per-problem ranges: the old fits may differ in them)                 zero_column_ranges_kernel
 //   V_b^T     = B_b^T L_b^-T                                                                            right_solve_lt_batched
 //   S_b       = cov(new_b, new_b) + diag(y_var_b), lower tiles                                          launch_gram_batch
 //   S_b      -= V_b^T V_b                                                                               launch_gemm_nt_sub_batched
@@ -124,15 +124,6 @@ __global__ __launch_bounds__(GRAM_THREADS) void update_cross_fast_kernel(const U
   gram_fast_body<DIMP, OP>(it.fp, it.Xnew, it.Xold, 0, it.X, ld, nullptr, it.flags, 0, 0, blockIdx.x, blockIdx.y);
 }
 
-// rows 0 .. m of columns [c0, c1) of X_b = X + b * stride <- 0 (the covariance with a phantom row is zero by definition)
-__global__ __launch_bounds__(256) void update_zero_columns_kernel(double *X, long long stride, long long ld, long long m, long long c0,
-                                                                 long long c1) {
-  double *Xb = X + (long long)blockIdx.z * stride;
-  const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (r >= m) return;
-  for (long long c = c0 + blockIdx.y; c < c1; c += gridDim.y) Xb[r + c * ld] = 0.;
-}
-
 // z_b[n_pad + i] = y_b[i] - sum_j X_b[i, j] z_b[j], j < n_pad: blockIdx = (128 rows, problem).  Lane l of every wave owns
 // the rows 2 l, 2 l + 1 (one 16-byte load per column: a wave reads 1 KiB of a column), wave w the columns j = w (mod 4);
 // the four partial sums are added as (0 + 1) + (2 + 3).
@@ -225,13 +216,15 @@ int agp_fit_update_batch(agp_context *c, int count, const agp_kernel *const *ker
     if (!f->z) { no_z = true; continue; }  // (agp_factor_create, replicated fits)
     const FeatView &ov = f->train.v;
     if (!ov.coords || ov.n != f->n) return AGP_ERR_INVALID_ARGUMENT;
-    if (f->n != f0->n || fit_real_rows(f) != fit_real_rows(f0) || f->phantom != f0->phantom) return AGP_ERR_INVALID_ARGUMENT;
+    if (f->n != f0->n) return AGP_ERR_INVALID_ARGUMENT;  // (one padded size; real rows and phantom ranges may differ)
     if (x_new[b]->dim != ov.dim || x_new[b]->n_scale_columns != ov.nsc) return AGP_ERR_INVALID_ARGUMENT;
     if ((ov.ids != nullptr) != (x_new[b]->eq_id != nullptr)) return AGP_ERR_INVALID_ARGUMENT;  // equality by id on one side only
   }
   if (no_z) return AGP_ERR_UNSUPPORTED;
-  const long long n0 = olds[0]->n, n_pad = round_up(n0, NB), n1 = n_pad + m, real0 = fit_real_rows(olds[0]), real1 = real0 + m;
-  if (information && ldi < real1) return AGP_ERR_INVALID_ARGUMENT;
+  const long long n0 = olds[0]->n, n_pad = round_up(n0, NB), n1 = n_pad + m;
+  if (information)
+    for (int b = 0; b < count; ++b)
+      if (ldi < fit_real_rows(olds[b]) + m) return AGP_ERR_INVALID_ARGUMENT;
   AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const BatchGeometry g = batch_geometry(n1, count);
@@ -259,8 +252,17 @@ int agp_fit_update_batch(agp_context *c, int count, const agp_kernel *const *ker
   if (loc == AGP_HOST)
     for (int b = 0; b < count; ++b)
       stage_words += (size_t)m * ((size_t)x_new[b]->dim + (x_new[b]->eq_id ? 1 : 0) + (size_t)x_new[b]->n_scale_columns);
+  // the phantom columns of every problem's cross covariance: those of its old fit and the pad to n_pad (the table follows
+  // the Gram table in its region)
+  RangeTable phantoms;
+  for (int b = 0; b < count; ++b) {
+    phantoms.begin_problem();
+    for (const auto &ph : olds[b]->phantom) phantoms.add(ph.first, ph.second);
+    phantoms.add(n0, n_pad);
+  }
+  const size_t range_off = phantoms.any() ? (gram_batch_table_bytes(count) + 15) / 16 * 16 : gram_batch_table_bytes(count);
   const size_t grow_bytes = sizeof(UpdateGrowItem) * (size_t)count, cross_bytes = sizeof(UpdateCrossItem) * (size_t)count,
-               gram_bytes = gram_batch_table_bytes(count);
+               gram_bytes = range_off + (phantoms.any() ? phantoms.bytes() : 0);
   WsLayout tsize;
   carve_update_batch_scratch(tsize, g, mp2, y_var_new != nullptr, stage_words, grow_bytes, cross_bytes, gram_bytes);
   void *scratch = nullptr;
@@ -378,6 +380,11 @@ int agp_fit_update_batch(agp_context *c, int count, const agp_kernel *const *ker
     return fail(st);
   }
   UPB_CHECK(hipMemcpyAsync(t.grow_table, h_tables, gram_off, hipMemcpyHostToDevice, s));  // grow and cross tables
+  if (phantoms.any()) {
+    phantoms.write(h_tables + gram_off + range_off);
+    UPB_CHECK(hipMemcpyAsync(static_cast<char *>(t.gram_table) + range_off, h_tables + gram_off + range_off, phantoms.bytes(),
+                             hipMemcpyHostToDevice, s));
+  }
   if (loc == AGP_HOST || !pinned) UPB_CHECK(hipStreamSynchronize(s));  // (pageable sources: the one wait for host-resident inputs)
 
   // ---- grow: old factor, tile images, z and features into the slab, phantom rows, zeroed status ----
@@ -395,13 +402,8 @@ int agp_fit_update_batch(agp_context *c, int count, const agp_kernel *const *ker
                   nanf[(size_t)b], &kernels[b]->prog);
     }
   }
-  auto zero_columns = [&](long long c0, long long c1) {
-    const long long cols = c1 - c0;
-    hipLaunchKernelGGL(update_zero_columns_kernel, dim3((unsigned)((m + 255) / 256), (unsigned)(cols < 128 ? cols : 128), (unsigned)count),
-                       dim3(256), 0, s, X, g.stride_A, lda, m, c0, c1);
-  };
-  for (const auto &ph : olds[0]->phantom) zero_columns(ph.first, ph.second);
-  if (n_pad > n0) zero_columns(n0, n_pad);
+  // (the covariance with a phantom row is zero by definition)
+  if (phantoms.any()) launch_zero_column_ranges(s, static_cast<const char *>(t.gram_table) + range_off, count, 0, count, X, g.stride_A, lda, m);
   // ---- X <- X L^-T (the block row V^T of the grown factor; block_symmetric.hpp:51) ----
   right_solve_lt_batched(s, r.A, g.stride_A, n_pad, lda, r.invd, g.stride_I, X, g.stride_A, m, lda, count);
   if (prof) UPB_CHECK(hipEventRecord(ctx->stage_ev[1], s));
@@ -463,7 +465,8 @@ int agp_fit_update_batch(agp_context *c, int count, const agp_kernel *const *ker
     fit->z = r.z + (size_t)b * (size_t)g.np2;
     fit->phantom = old->phantom;
     if (n_pad > n0) fit->phantom.emplace_back(n0, n_pad);
-    fit->n_real = real1;
+    const long long real0 = fit_real_rows(old);
+    fit->n_real = real0 + m;
     const int *fl = h_flags + 4 * (size_t)b;
     fit->failed_pivot = (!fl[0] && fl[1]) ? real0 + (int64_t)fl[1] - 1 : -1;  // real rows of the old fit + local pivot
     fit->log_det = old->log_det + 2. * h_status[(size_t)b];

@@ -8,6 +8,7 @@ Every Gram / factor / solve / predict goes through the C-ABI in
 include/albatross_amd.h (HIP kernels); nothing is computed on the CPU here.
 """
 import ctypes as C
+import itertools
 
 import numpy as np
 
@@ -1511,12 +1512,47 @@ def root_mean_square_error(prediction, truth):
     return float(np.sqrt(np.mean(d * d)))
 
 
+RAGGED_CLASS_ROWS = 128  # the size classes of a ragged batch: ceil(n / 128), the row block of the factorisation
+
+
+def _size_classes(sizes):
+    """The problems of a ragged batch grouped by ceil(n_b / 128): a list of index lists, classes in ascending order, the
+    indices of a class in the caller's order.  One lock-step call runs per class, padded to the class's largest size, so
+    no problem is padded by 128 rows or more; equal sizes are one class without padding."""
+    classes = {}
+    for b, n in enumerate(sizes):
+        classes.setdefault(-(-int(n) // RAGGED_CLASS_ROWS), []).append(b)
+    return [classes[k] for k in sorted(classes)]
+
+
+_BATCH_CALLS = itertools.count()  # serial numbers of the batched calls (GPFit._batch_origin)
+
+
+def _padded_groups(ctx, fit_models):
+    """The positions of fit_models grouped by the padded size of their fits (agp_fit_padded_size), groups in ascending
+    order.  Inside a group the handles of one fit_batch / update_batch call come first, call by call in the order of
+    their slots in the call's allocation (GPFit._batch_origin) - neighbours at one stride, which agp_predict_batch runs in
+    lock step -, then the fits of calls of their own in the caller's order."""
+    groups = {}
+    for b, fm in enumerate(fit_models):
+        groups.setdefault(int(ctx._lib.agp_fit_padded_size(fm._fit._h)), []).append(b)
+
+    def origin(b):
+        tag = getattr(fit_models[b]._fit, "_batch_origin", None)
+        return (1, b, 0) if tag is None else (0,) + tag
+
+    return [sorted(groups[k], key=origin) for k in sorted(groups)]
+
+
 def fit_batch(models, datasets):
-    """`models[b].fit(datasets[b])` for several problems of ONE size in lock step (agp_fit_create_batch): the regime of the
+    """`models[b].fit(datasets[b])` for several problems in lock step (agp_fit_create_batch_ragged): the regime of the
     reference's own workloads (benchmarks/bench_predict.cc: N = 512; one fit per tuner step), where a single fit is bound by the
     latency of its serial pivots - a batch shares it.  models: GaussianProcessRegression objects on one context (one model
-    may appear several times); datasets: as many RegressionDatasets with the same number of points.  Returns the FitModels;
-    raises like `fit` for the first problem whose covariance has NaN or is not positive definite."""
+    may appear several times); datasets: as many RegressionDatasets.  Their sizes may differ: the problems are put into
+    size classes (_size_classes) and one lock-step call runs per class, every problem padded with phantom rows to the
+    largest size of its class; datasets of one size are one class without padding.  Returns the FitModels in the
+    caller's order (rows() and information show the real rows); raises like `fit` for the first problem whose covariance
+    has NaN or is not positive definite."""
     if len(models) != len(datasets) or not models:
         raise ValueError("fit_batch: as many datasets as models, at least one")
     ctx = models[0]._ctx()
@@ -1531,38 +1567,48 @@ def fit_batch(models, datasets):
         structs.append(fs.as_struct())
         ys.append(y)
         yvs.append(yv)
-    n = fsets[0].n
-    if any(fs.n != n for fs in fsets):
-        raise ValueError("fit_batch: every dataset must have the same number of points")
-    Y = np.asfortranarray(np.stack(ys, axis=1))
-    have_var = any(v is not None for v in yvs)
-    V = np.asfortranarray(np.stack([np.zeros(n) if v is None else v for v in yvs], axis=1)) if have_var else None
+    fits, statuses = [None] * count, [capi.AGP_OK] * count
     handles = []
-    out = (C.c_void_p * count)()
-    status = (C.c_int * count)()
     try:
         for m in models:  # private handles: the context's small kernel cache may evict while the batch is assembled
             handles.append(ctx.private_kernel(m.covariance_function_))
-        kernels = (C.c_void_p * count)(*handles)
-        fptrs = (C.c_void_p * count)(*[C.addressof(st) for st in structs])
-        ctx._check(ctx._lib.agp_fit_create_batch(ctx._h, count, kernels, fptrs, _ptr(Y), n, _ptr(V) if have_var else None, n, out, None,
-                                                 0, None, status), "agp_fit_create_batch")
+        for members in _size_classes([fs.n for fs in fsets]):
+            k = len(members)
+            n = max(fsets[b].n for b in members)  # the padded size of the class
+            Y = np.zeros((n, k), order="F")
+            have_var = any(yvs[b] is not None for b in members)
+            V = np.zeros((n, k), order="F") if have_var else None
+            for j, b in enumerate(members):
+                Y[:fsets[b].n, j] = ys[b]
+                if yvs[b] is not None:
+                    V[:fsets[b].n, j] = yvs[b]
+            out = (C.c_void_p * k)()
+            status = (C.c_int * k)()
+            kernels = (C.c_void_p * k)(*[handles[b] for b in members])
+            fptrs = (C.c_void_p * k)(*[C.addressof(structs[b]) for b in members])
+            ctx._check(ctx._lib.agp_fit_create_batch_ragged(ctx._h, k, kernels, fptrs, _ptr(Y), n, _ptr(V) if have_var else None, n,
+                                                            out, None, 0, None, status), "agp_fit_create_batch_ragged")
+            call = next(_BATCH_CALLS)
+            for j, b in enumerate(members):
+                fits[b] = GPFit(ctx, C.c_void_p(out[j]), fsets[b].n, datasets[b].features)
+                fits[b]._batch_origin = (call, j)
+                statuses[b] = status[j]
     finally:
         for kh in handles:
             ctx._lib.agp_kernel_destroy(kh)
-    fits = [GPFit(ctx, C.c_void_p(out[b]), n, datasets[b].features) for b in range(count)]
-    for b in range(count):
-        if status[b] != capi.AGP_OK:
+    for b in range(count):  # the caller's index, whatever class the problem ran in
+        if statuses[b] != capi.AGP_OK:
             pivot = ctx._lib.agp_fit_failed_pivot(fits[b]._h)
-            ctx._check(status[b], f"agp_fit_create_batch: problem {b} (pivot {pivot})")
+            ctx._check(statuses[b], f"agp_fit_create_batch: problem {b} (pivot {pivot})")
     return [FitModel(m, f) for m, f in zip(models, fits)]
 
 
 def predict_batch(fit_models, features, what="marginal"):
-    """`fit_models[b].predict(features[b])` for several fits of ONE size in lock step (agp_predict_batch): what follows
+    """`fit_models[b].predict(features[b])` for several fits in lock step (agp_predict_batch): what follows
     fit_batch - at a few hundred points one prediction is a handful of latency-bound launches, a batch runs each once.
-    fit_models: FitModels holding plain GPFits on one context (the handles of fit_batch, or any mix of fits of one size:
-    neighbours whose factors lie at one stride are predicted together, the others one by one).  features: ONE array
+    fit_models: FitModels holding plain GPFits on one context (the handles of fit_batch or update_batch, or any mix of
+    fits: they are grouped by padded size, one call runs per group, and inside it neighbours whose factors lie at one
+    stride are predicted together, the others one by one).  features: ONE array
     shared by all problems, or a list with one entry per model, every entry with the same number of points;
     Measurement-wrapped features behave as in predict_with_measurement_noise.  what: "mean" | "marginal" | "joint".
     Returns a list of mean arrays, MarginalDistributions or JointDistributions, each with its model's mean function
@@ -1598,22 +1644,36 @@ def predict_batch(fit_models, features, what="marginal"):
     structs = [fs.as_struct() for fs in fsets]
     mean = np.empty((m, count), order="F")
     second = None if mode == 0 else np.empty((m if mode == 1 else m * m, count), order="F")
-    status = (C.c_int * count)()
+    statuses = [capi.AGP_OK] * count
     handles = []
     try:
         for fm in fit_models:  # private handles: the context's small kernel cache may evict while the batch is assembled
             handles.append(ctx.private_kernel(fm._model.covariance_function_))
-        kernels = (C.c_void_p * count)(*handles)
-        fits = (C.c_void_p * count)(*[fm._fit._h.value for fm in fit_models])
-        fptrs = (C.c_void_p * count)(*[C.addressof(st) for st in structs])
-        ctx._check(ctx._lib.agp_predict_batch(ctx._h, count, kernels, fits, fptrs, mode, _ptr(mean), max(m, 1),
-                                              None if second is None else _ptr(second), max(second.shape[0], 1) if second is not None else 0,
-                                              capi.HOST, status), "agp_predict_batch")
+        groups = _padded_groups(ctx, fit_models)
+        for members in groups:
+            k = len(members)
+            whole = k == count and members == list(range(count))  # one group in the caller's order: results land in place
+            g_mean = mean if whole else np.empty((m, k), order="F")
+            g_second = second if whole or second is None else np.empty((second.shape[0], k), order="F")
+            status = (C.c_int * k)()
+            kernels = (C.c_void_p * k)(*[handles[b] for b in members])
+            fits = (C.c_void_p * k)(*[fit_models[b]._fit._h.value for b in members])
+            fptrs = (C.c_void_p * k)(*[C.addressof(structs[b]) for b in members])
+            ctx._check(ctx._lib.agp_predict_batch(ctx._h, k, kernels, fits, fptrs, mode, _ptr(g_mean), max(m, 1),
+                                                  None if g_second is None else _ptr(g_second),
+                                                  max(g_second.shape[0], 1) if g_second is not None else 0, capi.HOST, status),
+                       "agp_predict_batch")
+            for j, b in enumerate(members):
+                statuses[b] = status[j]
+                if not whole:
+                    mean[:, b] = g_mean[:, j]
+                    if second is not None:
+                        second[:, b] = g_second[:, j]
     finally:
         for kh in handles:
             ctx._lib.agp_kernel_destroy(kh)
     for b in range(count):
-        ctx._check(status[b], f"agp_predict_batch: problem {b}")
+        ctx._check(statuses[b], f"agp_predict_batch: problem {b}")
     out = []
     for b, (fm, fs) in enumerate(zip(fit_models, fsets)):
         mu = mean[:, b] + fm._model.mean_function_(fs.coords)  # mean_function_.add_to
@@ -1627,10 +1687,11 @@ def predict_batch(fit_models, features, what="marginal"):
 
 
 def update_batch(fit_models, datasets):
-    """`fit_models[b].update(datasets[b])` for several fits of ONE size in lock step (agp_fit_update_batch): the third verb
+    """`fit_models[b].update(datasets[b])` for several fits in lock step (agp_fit_update_batch): the third verb
     after fit_batch and predict_batch - a caller who keeps many small models and conditions each on every new epoch of
     observations pays the launch chain of an update once per batch, not once per model.  fit_models: FitModels holding
-    plain fp64 GPFits of one size on one context (of fit, fit_batch, update or update_batch, in any mix); datasets: as
+    plain fp64 GPFits on one context (of fit, fit_batch, update or update_batch, in any mix and of any sizes: they are
+    grouped by padded size and one call runs per group); datasets: as
     many RegressionDatasets, each with the same number of points.  Each model's mean function is removed from its
     targets.  Returns the FitModels of the grown fits (rows() == old + m, training features concatenated); raises like
     `update` for the first problem whose covariance has NaN or is not positive definite, after destroying every handle."""
@@ -1662,29 +1723,48 @@ def update_batch(fit_models, datasets):
         ys.append(y)
         yvs.append(yv)
     structs = [fs.as_struct() for fs in fsets]
-    Y = np.asfortranarray(np.stack(ys, axis=1))
-    have_var = any(v is not None for v in yvs)
-    V = np.asfortranarray(np.stack([np.zeros(m) if v is None else v for v in yvs], axis=1)) if have_var else None
     handles = []
-    out = (C.c_void_p * count)()
-    status = (C.c_int * count)()
+    out = [None] * count
+    statuses = [capi.AGP_OK] * count
+    origins = [None] * count
+
+    def destroy_all():
+        for h in out:
+            if h:
+                ctx._lib.agp_fit_destroy(C.c_void_p(h))
+
     try:
         for fm in fit_models:  # private handles: the context's small kernel cache may evict while the batch is assembled
             handles.append(ctx.private_kernel(fm._model.covariance_function_))
-        kernels = (C.c_void_p * count)(*handles)
-        olds = (C.c_void_p * count)(*[fm._fit._h.value for fm in fit_models])
-        fptrs = (C.c_void_p * count)(*[C.addressof(st) for st in structs])
-        ctx._check(ctx._lib.agp_fit_update_batch(ctx._h, count, kernels, olds, fptrs, _ptr(Y), m, _ptr(V) if have_var else None, m, out,
-                                                 None, 0, None, status), "agp_fit_update_batch")
+        for members in _padded_groups(ctx, fit_models):
+            k = len(members)
+            Y = np.asfortranarray(np.stack([ys[b] for b in members], axis=1))
+            have_var = any(yvs[b] is not None for b in members)
+            V = np.asfortranarray(np.stack([np.zeros(m) if yvs[b] is None else yvs[b] for b in members], axis=1)) if have_var else None
+            g_out = (C.c_void_p * k)()
+            status = (C.c_int * k)()
+            kernels = (C.c_void_p * k)(*[handles[b] for b in members])
+            olds = (C.c_void_p * k)(*[fit_models[b]._fit._h.value for b in members])
+            fptrs = (C.c_void_p * k)(*[C.addressof(structs[b]) for b in members])
+            try:
+                ctx._check(ctx._lib.agp_fit_update_batch(ctx._h, k, kernels, olds, fptrs, _ptr(Y), m, _ptr(V) if have_var else None, m,
+                                                         g_out, None, 0, None, status), "agp_fit_update_batch")
+            except Exception:
+                destroy_all()  # (the grown fits of the groups before this one)
+                raise
+            call = next(_BATCH_CALLS)
+            for j, b in enumerate(members):
+                out[b] = g_out[j]
+                statuses[b] = status[j]
+                origins[b] = (call, j)
     finally:
         for kh in handles:
             ctx._lib.agp_kernel_destroy(kh)
     for b in range(count):
-        if status[b] != capi.AGP_OK:
+        if statuses[b] != capi.AGP_OK:
             pivot = ctx._lib.agp_fit_failed_pivot(C.c_void_p(out[b]))
-            for h in out:
-                ctx._lib.agp_fit_destroy(C.c_void_p(h))
-            ctx._check(status[b], f"agp_fit_update_batch: problem {b} (pivot {pivot})")
+            destroy_all()
+            ctx._check(statuses[b], f"agp_fit_update_batch: problem {b} (pivot {pivot})")
     grown = []
     for b, (fm, fs) in enumerate(zip(fit_models, fsets)):
         old_feats = _values_of(fm._fit.train_features)
@@ -1694,6 +1774,7 @@ def update_batch(fit_models, datasets):
         except (TypeError, ValueError):  # feature containers numpy cannot stack: keep them side by side
             new_feats = (old_feats, feats[b])
         grown.append(FitModel(fm._model, GPFit(ctx, C.c_void_p(out[b]), fm._fit.rows() + fs.n, new_feats)))
+        grown[-1]._fit._batch_origin = origins[b]
     return grown
 
 

@@ -554,6 +554,33 @@ AGP_API int agp_fit_create_batch(agp_context *ctx, int count, const agp_kernel *
                                  const double *y, int64_t ldy, const double *y_var, int64_t ldv, agp_fit **out, double *information,
                                  int64_t ldi, double *log_det, int *status);
 
+/* agp_fit_create_batch for problems of UNEQUAL sizes: the same arguments, but features[b]->n = n_b may differ (many small
+ * models, one per station or satellite, never have the same number of observations).  The padded size n of the call is
+ * the largest n_b (not rounded).  Problem b is fitted as diag(K_b, I): its handle is an ordinary fit of n_b observations
+ * that carries the trailing phantom rows [n_b, n) - identity rows of the factor, zero information, decoupled from
+ * everything, the representation agp_fit_update has always used - and every entry shows the n_b real rows only
+ * (agp_fit_size, agp_fit_download_information / _factor, agp_solve, agp_predict_*, agp_fit_update,
+ * agp_fit_inverse_diagonal; the entries that decline phantom fits - cross validation, agp_draw_mvn - decline these too).
+ *   y, ldy            column b holds n_b values; what follows them in the column is never read.  ldy (0: one shared
+ *                     vector of n values), ldv (with y_var) and ldi (with information) are at least n
+ *   information, ldi  column b receives n_b values; the rest of the column is not written
+ *   log_det[b]        that of K_b; status[b] and agp_fit_failed_pivot count real rows
+ * Every size must be positive; otherwise the rules of agp_fit_create_batch hold, per-problem failures included.  A
+ * malformed argument returns AGP_ERR_INVALID_ARGUMENT and writes nothing, out and status included.  With all sizes equal
+ * the call runs the launches of agp_fit_create_batch and returns the same bits.  One device allocation for the batch, one
+ * synchronisation behind host-resident inputs and one at the end; fixed-order reductions, no atomics: two identical calls
+ * give the same bits.  The cost of the padding: every problem is factored at size n.  Callers bound it by batching sizes
+ * of one class ceil(n_b / 128) per call, as the Python and C++ surfaces do.
+ * Not covered: unequal numbers of test points in agp_predict_batch and of new points in agp_fit_update_batch, a ragged
+ * agp_nll_batch and the batched gradients, cross validation of phantom fits, mixed precision, the sharded path. */
+AGP_API int agp_fit_create_batch_ragged(agp_context *ctx, int count, const agp_kernel *const *kernels,
+                                        const agp_features *const *features, const double *y, int64_t ldy, const double *y_var,
+                                        int64_t ldv, agp_fit **out, double *information, int64_t ldi, double *log_det, int *status);
+
+/* The rows the factor of `fit` holds, phantom rows included (agp_fit_size counts the real ones).  agp_predict_batch and
+ * agp_fit_update_batch take fits of one padded size per call. */
+AGP_API int64_t agp_fit_padded_size(const agp_fit *fit);
+
 /* ---- solve (CovarianceRepresentation::solve, gp.hpp:42-45,68,96,111) ----- */
 /* out = K^-1 rhs; rhs/out column-major n x nrhs (ld = n), at `location`. */
 AGP_API int agp_solve(agp_context *ctx, const agp_fit *fit, const double *rhs,
@@ -643,7 +670,7 @@ AGP_API int agp_crps_normal(agp_context *ctx, const double *mu, const double *si
 AGP_API int agp_fit_update(agp_context *ctx, const agp_kernel *k, const agp_fit *old, const agp_features *x_new, const double *y_new,
                    const double *y_var_new, agp_fit **out, double *information, double *log_det);
 
-/* agp_fit_update for `count` fits of one size in lock step: problem b computes what
+/* agp_fit_update for `count` fits of one padded size in lock step: problem b computes what
  * agp_fit_update(ctx, kernels[b], olds[b], x_new[b], ...) computes - the same algebra, the plain-feature semantics of
  * cross and prior, the phantom rows when the old size is not a multiple of 128, log determinant = old + 2 sum log
  * diag(L_S) - but every stage is ONE launch or launch chain for the whole batch, the grown fits are slices of ONE device
@@ -651,7 +678,8 @@ AGP_API int agp_fit_update(agp_context *ctx, const agp_kernel *k, const agp_fit 
  * end, where status words and log sums come down together.  What a caller does who keeps many small models and
  * conditions each on every new epoch of observations.
  *   olds[b]          plain fp64 fits of this context with training features and forward-substituted targets, all of one
- *                    padded size, one number of real rows and the same phantom ranges.  They need NOT lie at one stride
+ *                    padded size (agp_fit_padded_size); their real rows and phantom ranges may differ (the fits of an
+ *                    agp_fit_create_batch_ragged call).  They need NOT lie at one stride
  *                    or come from one call (their factors, tile images, z and features are gathered through a descriptor
  *                    table); they stay valid and are not modified
  *   x_new[b]         the m > 0 further features of problem b: one m and one location for all problems, dim / scale columns
@@ -660,9 +688,11 @@ AGP_API int agp_fit_update(agp_context *ctx, const agp_kernel *k, const agp_fit 
  *                    vector shared by all); y_var_new, ldv likewise, or NULL
  *   out[b]           an ordinary agp_fit of old + m observations (agp_predict_*, agp_solve, agp_fit_download_*,
  *                    agp_fit_update, agp_fit_update_batch again).  The grown fits of one call lie at constant strides in one
- *                    allocation that is released with the last of them, and reference no memory of the old fits; when the
- *                    old size is a multiple of 128 they have no phantom rows and agp_predict_batch runs them in lock step
- *   information, ldi (optional, host) the real rows of every good problem, old observations first; log_det[b] (optional, host)
+ *                    allocation that is released with the last of them, and reference no memory of the old fits;
+ *                    agp_predict_batch runs them in lock step.  Grown fit b carries the phantom ranges of olds[b] plus the
+ *                    pad from the old padded size to the next multiple of 128
+ *   information, ldi (optional, host) the real rows of every good problem, old observations first: column b gets
+ *                    agp_fit_size(olds[b]) + m values, ldi >= the largest of those; log_det[b] (optional, host)
  *   status[b]        AGP_OK / AGP_ERR_NAN_INPUT / AGP_ERR_NOT_POSITIVE_DEFINITE per problem; a failed problem leaves the
  *                    others and its own column of `information` untouched.  A problem that is not positive definite reports
  *                    the pivot through its handle like agp_fit_update (real rows of the old fit + local pivot); a NaN
@@ -923,15 +953,16 @@ AGP_API int agp_predict_joint(agp_context *ctx, const agp_kernel *k, const agp_f
                       const agp_features *xs, double *mean, double *cov,
                       int out_location);
 
-/* agp_predict_mean / _marginal / _joint for `count` fits of one size in lock step: problem b computes exactly what the
+/* agp_predict_mean / _marginal / _joint for `count` fits of one padded size in lock step: problem b computes exactly what the
  * single call computes for kernels[b], fits[b], xs[b] (gp.hpp:305-366, 82-113; each xs[b]'s own is_measurement flag is
  * honoured).  The counterpart of agp_fit_create_batch for what every user does after fitting: at N of a few hundred one
  * prediction is a handful of latency-bound launches, a batch runs each of them once (one grid dimension = problem).
  *   mode                 0 mean, 1 marginal, 2 joint (the numbering of agp_solver_predict)
  *   kernels[b], xs[b]    covariance function and test features of problem b: all xs[b] have one m and one location,
  *                        dim == the training dimension of fits[b]; dim may differ between problems
- *   fits[b]              plain fp64 LL^T fits with training features, of one n, living on ctx (a mixed-precision fit, a
- *                        factor of agp_factor_create: AGP_ERR_INVALID_ARGUMENT)
+ *   fits[b]              plain fp64 LL^T fits with training features, of one padded size (agp_fit_padded_size; the real
+ *                        rows and phantom ranges may differ), living on ctx (a mixed-precision fit, a factor of
+ *                        agp_factor_create: AGP_ERR_INVALID_ARGUMENT)
  *   mean, ldm            m x count, ldm >= m
  *   second, lds          marginal: m x count variances, lds >= m; joint: problem b's full symmetric m x m covariance,
  *                        column-major with ld = m, at second + b * lds, lds >= m * m; ignored for mode 0
@@ -944,8 +975,9 @@ AGP_API int agp_predict_joint(agp_context *ctx, const agp_kernel *k, const agp_f
  * Lock step: fits[] is cut into maximal runs in which the factors, the tile images and the information vectors lie at
  * one constant non-negative stride with one leading dimension - consecutive handles of one agp_fit_create_batch call, or
  * any evenly spaced subset of them; the fits need not come from one call.  A run of two or more goes through the
- * batched launches, a run of one through agp_predict_mean / _marginal / _joint unchanged (so does a fit grown by
- * agp_fit_update).  Inside a run there is no synchronisation but the closing one; the descriptor tables are uploaded
+ * batched launches, a run of one through agp_predict_mean / _marginal / _joint unchanged.  Fits with phantom rows (of
+ * agp_fit_create_batch_ragged, agp_fit_update_batch) join the runs: one table-driven launch zeroes the phantom rows of
+ * their cross covariances before the substitution.  Inside a run there is no synchronisation but the closing one; the descriptor tables are uploaded
  * from the context's pinned staging area.  Host-resident test features of all runs are uploaded into one device
  * allocation before the first launch, with one wait for those uploads (device-resident ones are used in place).  Covariance functions of the radial<Euclidean> [+ noise] shapes with one
  * operator and one dimension in a run are evaluated by ONE launch for the run; other runs by a launch per problem that

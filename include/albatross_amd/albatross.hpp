@@ -22,6 +22,7 @@
 
 #include <algorithm>
 #include <array>
+#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -860,6 +861,9 @@ struct GPFit {
   double log_determinant = 0.;
   std::shared_ptr<detail::ContextHolder> context;
   std::shared_ptr<agp_fit> handle;  // train_covariance (CovarianceRepresentation)
+  // the batched call that made the handle and its slot in that call's allocation (-1: a call of its own): predict_batch
+  // and update_batch keep the handles of one call neighbours in slot order, which agp_predict_batch runs in lock step
+  std::int64_t batch_call = -1, batch_slot = 0;
 
   std::int64_t rows() const { return static_cast<std::int64_t>(train_features.size()); }
 
@@ -1621,6 +1625,48 @@ constexpr int predict_type_of() {
                 "PredictType: JointDistribution or MarginalDistribution");
   return std::is_same<PredictType, MarginalDistribution>::value ? AGP_PREDICT_MARGINAL : AGP_PREDICT_JOINT;
 }
+
+// The problems of a ragged batch grouped by `key`: index lists in ascending key order, the indices of a group in the
+// caller's order.  size_classes: key = ceil(n_b / 128), the classes of fit_batch - one lock-step call runs per class,
+// padded to the largest size of the class, so no problem is padded by 128 rows or more; equal sizes are one class
+// without padding.  padded_groups: key = agp_fit_padded_size, what predict_batch and update_batch take per call.
+inline std::vector<std::vector<std::size_t>> group_by_key(const std::vector<std::int64_t> &keys) {
+  std::map<std::int64_t, std::vector<std::size_t>> groups;
+  for (std::size_t b = 0; b < keys.size(); ++b) groups[keys[b]].push_back(b);
+  std::vector<std::vector<std::size_t>> out;
+  for (auto &g : groups) out.push_back(std::move(g.second));
+  return out;
+}
+inline std::int64_t next_batch_call() {
+  static std::atomic<std::int64_t> serial{0};
+  return serial++;
+}
+inline std::vector<std::vector<std::size_t>> size_classes(const std::vector<std::size_t> &sizes) {
+  std::vector<std::int64_t> keys;
+  for (std::size_t n : sizes) keys.push_back((std::int64_t)((n + 127) / 128));
+  return group_by_key(keys);
+}
+// origin[b] = (batch_call, batch_slot) of fit b: inside a group the handles of one batched call come first, call by call in
+// slot order - neighbours at one stride in their allocation -, then the others in the caller's order
+inline std::vector<std::vector<std::size_t>> padded_groups(const std::vector<const agp_fit *> &fits,
+                                                           const std::vector<std::pair<std::int64_t, std::int64_t>> &origin) {
+  std::vector<std::int64_t> keys;
+  for (const agp_fit *f : fits) keys.push_back(agp_fit_padded_size(f));
+  auto groups = group_by_key(keys);
+  for (auto &g : groups)
+    std::stable_sort(g.begin(), g.end(), [&](std::size_t a, std::size_t b) {
+      const bool ta = origin[a].first >= 0, tb = origin[b].first >= 0;
+      if (ta != tb) return ta;
+      return ta && origin[a] < origin[b];
+    });
+  return groups;
+}
+template <typename FitModels>
+std::vector<std::pair<std::int64_t, std::int64_t>> batch_origins(const FitModels &fit_models) {
+  std::vector<std::pair<std::int64_t, std::int64_t>> origin;
+  for (const auto &fm : fit_models) origin.emplace_back(fm.get_fit().batch_call, fm.get_fit().batch_slot);
+  return origin;
+}
 }  // namespace detail
 
 template <typename ModelType, typename StrategyType> class Ransac;  // models/ransac.hpp:427-505, below
@@ -1735,62 +1781,90 @@ class GaussianProcessRegression {
     return FitModel<GaussianProcessRegression, FeatureType>(*this, std::move(fit));
   }
 
-  // `fit` for SEVERAL datasets of one size in lock step (agp_fit_create_batch): the regime of the reference's own workloads
+  // `fit` for SEVERAL datasets in lock step (agp_fit_create_batch_ragged): the regime of the reference's own workloads
   // (benchmarks/bench_predict.cc:20-40: N = 512; one fit per tuner step), where a single fit is bound by the latency of its
-  // serial pivots - a batch shares it.  Every dataset is fitted with THIS model (its current parameters); throws like `fit`
-  // for the first dataset whose covariance has NaN or is not positive definite.
+  // serial pivots - a batch shares it.  The datasets may differ in size: they are put into size classes
+  // (detail::size_classes) and one lock-step call runs per class, every problem padded with phantom rows to the largest
+  // size of its class; datasets of one size are one class without padding.  Every dataset is fitted with THIS model (its
+  // current parameters); the results come back in the caller's order; throws like `fit` for the first dataset whose
+  // covariance has NaN or is not positive definite.
   template <typename FeatureType>
   std::vector<FitModel<GaussianProcessRegression, FeatureType>> fit_batch(const std::vector<RegressionDataset<FeatureType>> &datasets) const {
     std::vector<FitModel<GaussianProcessRegression, FeatureType>> out;
     if (datasets.empty()) return out;
     if (mixed_precision.enabled) throw std::invalid_argument("fit_batch: fp64 models only");
-    const std::size_t count = datasets.size(), n = datasets[0].features.size();
+    const std::size_t count = datasets.size();
     auto ctx = detail::default_context();
     detail::KernelHolder k(covariance_function_.program());
     std::vector<detail::Flat> flats;
     flats.reserve(count);
-    Vector y(n * count);
-    bool have_var = false;
-    for (const auto &d : datasets) have_var = have_var || !d.targets.covariance.empty();
-    Vector yv(have_var ? n * count : 0, 0.);
+    std::vector<std::size_t> sizes(count);
     for (std::size_t b = 0; b < count; ++b) {
       const auto &d = datasets[b];
-      if (d.features.size() != n || d.targets.size() != n) throw std::invalid_argument("fit_batch: every dataset must have the same number of points");
-      if (!d.targets.covariance.empty() && d.targets.covariance.size() != n)
+      sizes[b] = d.features.size();
+      if (sizes[b] == 0 || d.targets.size() != sizes[b]) throw std::invalid_argument("fit_batch: features and targets differ in size, or are empty");
+      if (!d.targets.covariance.empty() && d.targets.covariance.size() != sizes[b])
         throw std::invalid_argument("target covariance must be diagonal (one variance per target)");
       flats.push_back(detail::flatten(covariance_function_, d.features));
-      for (std::size_t i = 0; i < n; ++i) {
-        double v = d.targets.mean[i];  // mean_function_.remove_from, gp.hpp:291-292
-        if (!std::is_same<MeanFunc, ZeroMean>::value) v -= mean_function_._call_impl(detail::unwrap<FeatureType>::get(d.features[i]));
-        y[b * n + i] = v;
-        if (have_var && !d.targets.covariance.empty()) yv[b * n + i] = d.targets.covariance[i];
+    }
+    std::vector<std::shared_ptr<agp_fit>> owned(count);
+    std::vector<int> statuses(count, AGP_OK);
+    std::vector<Vector> infos(count);
+    std::vector<double> logdets(count, 0.);
+    std::vector<std::pair<std::int64_t, std::int64_t>> origin(count);
+    for (const auto &members : detail::size_classes(sizes)) {
+      const std::size_t kc = members.size();
+      const std::int64_t call = detail::next_batch_call();
+      std::size_t n = 0;  // the padded size of the class
+      bool have_var = false;
+      for (std::size_t b : members) {
+        n = std::max(n, sizes[b]);
+        have_var = have_var || !datasets[b].targets.covariance.empty();
+      }
+      Vector y(n * kc, 0.), yv(have_var ? n * kc : 0, 0.);
+      std::vector<const agp_kernel *> kernels(kc, k.k);
+      std::vector<const agp_features *> views(kc);
+      for (std::size_t j = 0; j < kc; ++j) {
+        const auto &d = datasets[members[j]];
+        views[j] = &flats[members[j]].view;
+        for (std::size_t i = 0; i < sizes[members[j]]; ++i) {
+          double v = d.targets.mean[i];  // mean_function_.remove_from, gp.hpp:291-292
+          if (!std::is_same<MeanFunc, ZeroMean>::value) v -= mean_function_._call_impl(detail::unwrap<FeatureType>::get(d.features[i]));
+          y[j * n + i] = v;
+          if (!d.targets.covariance.empty()) yv[j * n + i] = d.targets.covariance[i];
+        }
+      }
+      std::vector<agp_fit *> handles(kc, nullptr);
+      std::vector<int> status(kc, AGP_OK);
+      std::vector<double> info(n * kc), logdet(kc);
+      const int st = agp_fit_create_batch_ragged(ctx->ctx, (int)kc, kernels.data(), views.data(), y.data(), (std::int64_t)n,
+                                                 have_var ? yv.data() : nullptr, (std::int64_t)n, handles.data(), info.data(),
+                                                 (std::int64_t)n, logdet.data(), status.data());
+      detail::check(st, ctx->ctx, "agp_fit_create_batch_ragged");
+      for (std::size_t j = 0; j < kc; ++j) {
+        const std::size_t b = members[j];
+        owned[b] = std::shared_ptr<agp_fit>(handles[j], [ctx](agp_fit *p) { agp_fit_destroy(p); });
+        statuses[b] = status[j];
+        origin[b] = {call, (std::int64_t)j};
+        logdets[b] = logdet[j];
+        infos[b].assign(info.begin() + (std::ptrdiff_t)(j * n), info.begin() + (std::ptrdiff_t)(j * n + sizes[b]));
       }
     }
-    std::vector<const agp_kernel *> kernels(count, k.k);
-    std::vector<const agp_features *> views(count);
-    for (std::size_t b = 0; b < count; ++b) views[b] = &flats[b].view;
-    std::vector<agp_fit *> handles(count, nullptr);
-    std::vector<int> status(count, AGP_OK);
-    std::vector<double> info(n * count), logdet(count);
-    const int st = agp_fit_create_batch(ctx->ctx, (int)count, kernels.data(), views.data(), y.data(), (std::int64_t)n,
-                                        have_var ? yv.data() : nullptr, (std::int64_t)n, handles.data(), info.data(), (std::int64_t)n,
-                                        logdet.data(), status.data());
-    detail::check(st, ctx->ctx, "agp_fit_create_batch");
-    std::vector<std::shared_ptr<agp_fit>> owned;
-    for (agp_fit *h : handles) owned.emplace_back(h, [ctx](agp_fit *p) { agp_fit_destroy(p); });
-    for (std::size_t b = 0; b < count; ++b)
-      if (status[b] != AGP_OK) {
+    for (std::size_t b = 0; b < count; ++b)  // the caller's index, whatever class the problem ran in
+      if (statuses[b] != AGP_OK) {
         std::string what = "agp_fit_create_batch: problem " + std::to_string(b);
-        if (status[b] == AGP_ERR_NOT_POSITIVE_DEFINITE) what += " (pivot " + std::to_string((long long)agp_fit_failed_pivot(handles[b])) + ")";
-        detail::check(status[b], ctx->ctx, what.c_str());
+        if (statuses[b] == AGP_ERR_NOT_POSITIVE_DEFINITE) what += " (pivot " + std::to_string((long long)agp_fit_failed_pivot(owned[b].get())) + ")";
+        detail::check(statuses[b], ctx->ctx, what.c_str());
       }
     for (std::size_t b = 0; b < count; ++b) {
       GPFit<FeatureType> fit;
       fit.train_features = datasets[b].features;
-      fit.information.assign(info.begin() + (std::ptrdiff_t)(b * n), info.begin() + (std::ptrdiff_t)((b + 1) * n));
-      fit.log_determinant = logdet[b];
+      fit.information = std::move(infos[b]);
+      fit.log_determinant = logdets[b];
       fit.context = ctx;
       fit.handle = owned[b];
+      fit.batch_call = origin[b].first;
+      fit.batch_slot = origin[b].second;
       out.emplace_back(*this, std::move(fit));
     }
     return out;
@@ -2440,9 +2514,10 @@ auto GaussianProcessRegression<CovFunc, MeanFunc>::cross_validate() const {
   return CrossValidation<GaussianProcessRegression<CovFunc, MeanFunc>>(*this);
 }
 
-// `fit_models[b].predict(features[b])` for SEVERAL fits of one size in lock step (agp_predict_batch): what follows fit_batch.
-// Every features[b] has the same number of points (Measurement<> features as in predict_with_measurement_noise); fits whose
-// factors lie at one stride - the FitModels of one fit_batch call - are predicted together, any others one by one.  Each
+// `fit_models[b].predict(features[b])` for SEVERAL fits in lock step (agp_predict_batch): what follows fit_batch.
+// Every features[b] has the same number of points (Measurement<> features as in predict_with_measurement_noise).  The fits
+// are grouped by padded size (detail::padded_groups), one call runs per group, and inside it fits whose factors lie at one
+// stride - the FitModels of one fit_batch or update_batch call - are predicted together, any others one by one.  Each
 // model's mean function is added back (gp.hpp:346,364).  Throws for the first problem whose fit had failed.
 template <typename ModelType, typename FeatureType, typename P>
 class BatchPrediction {
@@ -2504,10 +2579,32 @@ class BatchPrediction {
     const std::size_t per = mode == 1 ? m : m * m;
     if (second) second->assign(mode == 0 ? 0 : per * count, 0.);
     std::vector<int> status(count, AGP_OK);
-    detail::check(agp_predict_batch(ctx->ctx, (int)count, kernels.data(), fits.data(), views.data(), mode, mean.data(),
-                                    (std::int64_t)std::max<std::size_t>(m, 1), mode == 0 ? nullptr : second->data(),
-                                    (std::int64_t)std::max<std::size_t>(per, 1), AGP_HOST, status.data()),
-                  ctx->ctx, "agp_predict_batch");
+    // one call per padded size, results back in the caller's order
+    for (const auto &members : detail::padded_groups(fits, detail::batch_origins(*fms_))) {
+      const std::size_t kc = members.size();
+      std::vector<const agp_kernel *> g_kernels(kc);
+      std::vector<const agp_fit *> g_fits(kc);
+      std::vector<const agp_features *> g_views(kc);
+      for (std::size_t j = 0; j < kc; ++j) {
+        g_kernels[j] = kernels[members[j]];
+        g_fits[j] = fits[members[j]];
+        g_views[j] = views[members[j]];
+      }
+      std::vector<double> g_mean(m * kc), g_second(mode == 0 ? 0 : per * kc);
+      std::vector<int> g_status(kc, AGP_OK);
+      detail::check(agp_predict_batch(ctx->ctx, (int)kc, g_kernels.data(), g_fits.data(), g_views.data(), mode, g_mean.data(),
+                                      (std::int64_t)std::max<std::size_t>(m, 1), mode == 0 ? nullptr : g_second.data(),
+                                      (std::int64_t)std::max<std::size_t>(per, 1), AGP_HOST, g_status.data()),
+                    ctx->ctx, "agp_predict_batch");
+      for (std::size_t j = 0; j < kc; ++j) {
+        const std::size_t b = members[j];
+        status[b] = g_status[j];
+        std::copy(g_mean.begin() + (std::ptrdiff_t)(j * m), g_mean.begin() + (std::ptrdiff_t)((j + 1) * m), mean.begin() + (std::ptrdiff_t)(b * m));
+        if (mode != 0)
+          std::copy(g_second.begin() + (std::ptrdiff_t)(j * per), g_second.begin() + (std::ptrdiff_t)((j + 1) * per),
+                    second->begin() + (std::ptrdiff_t)(b * per));
+      }
+    }
     for (std::size_t b = 0; b < count; ++b)
       if (status[b] != AGP_OK) detail::check(status[b], ctx->ctx, ("agp_predict_batch: problem " + std::to_string(b)).c_str());
     means->clear();
@@ -2527,9 +2624,10 @@ BatchPrediction<ModelType, FeatureType, P> predict_batch(const std::vector<FitMo
   return BatchPrediction<ModelType, FeatureType, P>(&fit_models, &features_per_model);
 }
 
-// `fit_models[b].update(datasets[b])` for SEVERAL fits of one size in lock step (agp_fit_update_batch): the third verb after
+// `fit_models[b].update(datasets[b])` for SEVERAL fits in lock step (agp_fit_update_batch): the third verb after
 // fit_batch and predict_batch.  Every dataset has the same number of points; the fits may come from fit, fit_batch, update
-// or update_batch in any mix.  Each model's mean function is removed from its targets.  The grown fits are ordinary
+// or update_batch in any mix and be of any sizes: they are grouped by padded size (detail::padded_groups) and one call
+// runs per group.  Each model's mean function is removed from its targets.  The grown fits are ordinary
 // FitModels that share one device allocation.  Throws like `update` for the first problem whose covariance has NaN or is
 // not positive definite (every handle of the call is released first).
 template <typename ModelType, typename FeatureType>
@@ -2570,19 +2668,46 @@ std::vector<FitModel<ModelType, FeatureType>> update_batch(const std::vector<Fit
     rows = std::max(rows, fm.get_fit().train_features.size() + m);
   }
   for (std::size_t b = 0; b < count; ++b) views[b] = &flats[b].view;
-  std::vector<agp_fit *> handles(count, nullptr);
   std::vector<int> status(count, AGP_OK);
   std::vector<double> info(rows * count), logdet(count);
-  const int st = agp_fit_update_batch(ctx->ctx, (int)count, kernels.data(), olds.data(), views.data(), y.data(), (std::int64_t)m,
-                                      have_var ? yv.data() : nullptr, (std::int64_t)m, handles.data(), info.data(), (std::int64_t)rows,
-                                      logdet.data(), status.data());
-  detail::check(st, ctx->ctx, "agp_fit_update_batch");
-  std::vector<std::shared_ptr<agp_fit>> owned;
-  for (agp_fit *h : handles) owned.emplace_back(h, [ctx](agp_fit *p) { agp_fit_destroy(p); });
+  std::vector<std::shared_ptr<agp_fit>> owned(count);
+  std::vector<std::pair<std::int64_t, std::int64_t>> origin(count);
+  // one call per padded size, results back in the caller's order
+  for (const auto &members : detail::padded_groups(olds, detail::batch_origins(fit_models))) {
+    const std::size_t kc = members.size();
+    const std::int64_t call = detail::next_batch_call();
+    std::vector<const agp_kernel *> g_kernels(kc);
+    std::vector<const agp_fit *> g_olds(kc);
+    std::vector<const agp_features *> g_views(kc);
+    Vector g_y(m * kc), g_yv(have_var ? m * kc : 0, 0.);
+    for (std::size_t j = 0; j < kc; ++j) {
+      const std::size_t b = members[j];
+      g_kernels[j] = kernels[b];
+      g_olds[j] = olds[b];
+      g_views[j] = views[b];
+      std::copy(y.begin() + (std::ptrdiff_t)(b * m), y.begin() + (std::ptrdiff_t)((b + 1) * m), g_y.begin() + (std::ptrdiff_t)(j * m));
+      if (have_var) std::copy(yv.begin() + (std::ptrdiff_t)(b * m), yv.begin() + (std::ptrdiff_t)((b + 1) * m), g_yv.begin() + (std::ptrdiff_t)(j * m));
+    }
+    std::vector<agp_fit *> handles(kc, nullptr);
+    std::vector<int> g_status(kc, AGP_OK);
+    std::vector<double> g_info(rows * kc), g_logdet(kc);
+    const int st = agp_fit_update_batch(ctx->ctx, (int)kc, g_kernels.data(), g_olds.data(), g_views.data(), g_y.data(), (std::int64_t)m,
+                                        have_var ? g_yv.data() : nullptr, (std::int64_t)m, handles.data(), g_info.data(),
+                                        (std::int64_t)rows, g_logdet.data(), g_status.data());
+    detail::check(st, ctx->ctx, "agp_fit_update_batch");
+    for (std::size_t j = 0; j < kc; ++j) {
+      const std::size_t b = members[j];
+      owned[b] = std::shared_ptr<agp_fit>(handles[j], [ctx](agp_fit *p) { agp_fit_destroy(p); });
+      status[b] = g_status[j];
+      origin[b] = {call, (std::int64_t)j};
+      logdet[b] = g_logdet[j];
+      std::copy(g_info.begin() + (std::ptrdiff_t)(j * rows), g_info.begin() + (std::ptrdiff_t)((j + 1) * rows), info.begin() + (std::ptrdiff_t)(b * rows));
+    }
+  }
   for (std::size_t b = 0; b < count; ++b)
     if (status[b] != AGP_OK) {
       std::string what = "agp_fit_update_batch: problem " + std::to_string(b);
-      if (status[b] == AGP_ERR_NOT_POSITIVE_DEFINITE) what += " (pivot " + std::to_string((long long)agp_fit_failed_pivot(handles[b])) + ")";
+      if (status[b] == AGP_ERR_NOT_POSITIVE_DEFINITE) what += " (pivot " + std::to_string((long long)agp_fit_failed_pivot(owned[b].get())) + ")";
       owned.clear();
       detail::check(status[b], ctx->ctx, what.c_str());
     }
@@ -2597,6 +2722,8 @@ std::vector<FitModel<ModelType, FeatureType>> update_batch(const std::vector<Fit
     fit.log_determinant = logdet[b];
     fit.context = ctx;
     fit.handle = owned[b];
+    fit.batch_call = origin[b].first;
+    fit.batch_slot = origin[b].second;
     out.emplace_back(fit_models[b].get_model(), std::move(fit));
   }
   return out;
