@@ -261,6 +261,11 @@ def load_debug():
                                                             C.POINTER(C.c_int64)]
         _debug_lib.agp_debug_comm_create_null.restype = C.c_int
         _debug_lib.agp_debug_comm_create_null.argtypes = [C.c_int, C.c_int, _PP]
+        # the factorisation's schedule without a device (csrc/factor_plan.h)
+        _debug_lib.agp_debug_factor_plan.restype = C.c_int
+        _debug_lib.agp_debug_factor_plan.argtypes = [_P, C.c_int64, _P, C.c_int64]
+        _debug_lib.agp_debug_step_launch_shape.restype = C.c_int
+        _debug_lib.agp_debug_step_launch_shape.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P]
     return _debug_lib
 
 

@@ -16,12 +16,16 @@
 //                           micro columns are reused directly as MFMA operands
 //       gemm_nt_sub (K=128) update of the rest of the outer block column
 //     gemm_nt_sub (K=512)   trailing update  (the MFMA-bound bulk, gemm.hip)
+// The SCHEDULE - outer block widths, merged / throttled / masked / step / single-stream steps, panel and step-launch
+// shapes, every switch point - is decided in factor_plan.h (plain C++, tested without a device by
+// tests/test_fit_schedule_host.py); factor_lower and panel_phase below carry it out.
 #include <cstdlib>
 #include "common.h"
 #include "mfma_f64.h"
 #include "gemm_tiles.h"
 #include "trsm_kernel.h"
 #include "pub.h"
+#include "factor_plan.h"  // the schedule: switch points, outer steps, panel and step-launch shapes
 
 namespace agp {
 void launch_set_identity_batched(hipStream_t s, double *B, long long ld, long long stride, long long m, long long count);  // reduce.hip
@@ -900,17 +904,11 @@ static void timed_gemm(hipStream_t s, FactorTimers *timers, double *C, long long
   }
 }
 
-// ---- the schedule's switch points (measured on one MI355X; DESIGN.md sections 3 and 8 hold the sweeps) ------------
-// The two switches a caller can set - AGP_PANEL_FUSED=0 (POTRF and TRSM as two launches) and AGP_STEP_BELOW=<rows> (0: no
-// step launches) - are read ONCE, at agp_context_create, into ctx->tune (api.hip); everything else is a constant.
-constexpr long long FUSED_BELOW = 4608;     // remaining rows at or below which POTRF + TRSM are one fused launch (2048 .. 4608 best)
-constexpr long long INNER_LEFT_ABOVE = 6144;  // left-looking inside an outer block while more rows than this remain
-constexpr long long NBO_512_ABOVE = 2048, NBO_256_ABOVE = 1024;  // outer block width 512 / 256 / 128 by remaining rows
-constexpr long long NBO_WIDE_ABOVE = 8192;  // ... and ctx->nbo_wide (mixed precision) above this
-constexpr long long THROTTLE_BELOW = 8192;  // bulk updates handed to their stream by the host once their panel is done
-constexpr long long U1_F32_ABOVE = 4096;    // mixed precision: U1 on the fp32 MFMA path while the block column is this tall
-constexpr long long SINGLE_BELOW = 1536;    // the very end on one stream (when the step launches are off)
-constexpr long long MASK_BELOW = 8704;      // bulk updates on the CU-masked stream from here on
+static_assert(PLAN_NB == NB && STEP_FIXED_CRITICAL == 1 + UPD_BLOCKS && MERGED_STEPS_MAX == agp_context::HEADCNT_WORDS, "factor_plan.h");
+using ScheduleRecord = agp_context::ScheduleRecord;
+static_assert(STEP_BIT_MERGED == ScheduleRecord::MERGED && STEP_BIT_STEP == ScheduleRecord::STEP && STEP_BIT_THROTTLED == ScheduleRecord::THROTTLED &&
+              STEP_BIT_MASKED == ScheduleRecord::MASKED && STEP_BIT_SINGLE == ScheduleRecord::SINGLE && INV_BIT_EARLY == ScheduleRecord::INV_EARLY &&
+              INV_BIT_LAST_STEP == ScheduleRecord::INV_LAST_STEP && INV_BIT_TAIL == ScheduleRecord::INV_TAIL, "factor_plan.h");
 
 // Workgroup slots of panel_fused_kernel<true> on this device: occupancy x CUs, asked of the runtime once per context.
 static long long step_slots(agp_context *ctx) {
@@ -923,15 +921,6 @@ static long long step_slots(agp_context *ctx) {
     ctx->step_slots = (long long)per_cu * ctx->cus;
   }
   return ctx->step_slots;
-}
-
-// May `rows` remaining rows be factored with step launches?  The row workgroups of a step launch wait for trailing
-// workgroups that are dispatched AFTER them: all critical workgroups (10 + one per 64 rows) and at least 64 trailing ones
-// must be resident at once, or the waiters would sit out their 2 s time-out.  Fewer slots than that (a small partition,
-// a CU mask): the two-launch schedule.  Should the hand-over time out all the same (flags[2]), agp_fit_create repeats
-// the fit without step launches (api.hip).
-static bool step_fits(agp_context *ctx, long long rows) {
-  return ctx->tune.step_below > 0 && rows <= ctx->tune.step_below && step_slots(ctx) >= 10 + rows / 64 + 64;
 }
 
 __global__ __launch_bounds__(256) void prep_kernel(PrepArgs a) {
@@ -1024,27 +1013,37 @@ void panel_fused_prepare(agp_context *ctx, hipStream_t s, double *invd, long lon
   if (panel_fused_plan(ctx, invd, k_begin, k_end, want_step, &prep)) launch_prep(s, prep);
 }
 
+// What the schedule reads, from the context (factor_plan.h: FactorSwitches) - once per factorisation, after the fills of
+// panel_fused_plan for the columns [.., upto) and the tile images `invd` have been planned.
+static FactorSwitches factor_switches(agp_context *ctx, const double *invd, long long upto, int variant) {
+  FactorSwitches sw;
+  sw.panel_fused = ctx->tune.panel_fused; sw.step_below = ctx->tune.step_below; sw.merge_above = ctx->tune.merge_above;
+  sw.nbo_override = ctx->nbo_override;
+  sw.nbo_wide = (variant == 4 || variant == 5) ? ctx->nbo_wide : ctx->tune.fp64_nbo;  // (fp64: AGP_FP64_NBO, measurement switch)
+  sw.variant = variant;
+  sw.step_slots = sw.step_below > 0 ? step_slots(ctx) : 0;
+  sw.cus = ctx->cus;
+  sw.have_masked_stream = ctx->stream_masked != nullptr;
+  sw.headcnt_ready = ctx->headcnt_ready;
+  sw.fused_buffers_ready = ctx->d_zpub && ctx->zpub_ready_n >= upto && ctx->img_ready == invd;
+  sw.step_buffers_ready = sw.panel_fused && sw.fused_buffers_ready && ctx->d_dpub && ctx->dpub_cap * NB >= upto && ctx->d_rowcnt;
+  sw.inv_requested = ctx->bs_W && ctx->ev_inv && ctx->stream2;
+  sw.bs_BW = ctx->bs_BW; sw.bs_done = ctx->bs_done;
+  return sw;
+}
+
 // Panel phase of one outer block [K0, kend): for every NB-wide diagonal block
 // POTRF, panel TRSM (with the fused forward substitution on y) and the update
 // of the remaining columns of the outer block.  Everything on stream s.
 static void panel_phase(agp_context *ctx, hipStream_t s, double *A, long long n, long long lda, double *invd,
-                        double *y, long long K0, long long kend, FactorTimers *timers, bool step_mode = false,
-                        long long mark_after = -1, hipEvent_t mark_event = nullptr) {
+                        double *y, long long K0, long long kend, FactorTimers *timers, const FactorSwitches &sw,
+                        bool want_step = false, long long mark_after = -1, hipEvent_t mark_event = nullptr) {
   // step_mode (the chain-bound tail, factor_lower): ONE launch per panel.  The first panel is a plain fused launch;
   // every later one is panel_fused_kernel<true> - the previous panel's update of this panel's 128 columns on the
   // critical workgroups - plus trailing workgroups that apply the previous panel to everything further right while
-  // this panel's POTRF runs.  No update launches, nothing leaves stream s.
-  // Otherwise, while more than INNER_LEFT_ABOVE rows remain: left-looking inside the outer block - panel k is brought
-  // up to date with the panels [K0, k) of this outer block in ONE product of depth k - K0 just before it is factored,
-  // instead of every panel updating all later columns of the outer block with depth 128 (same flop, a third of the C
-  // traffic: 35.2 -> 35.0 ms at N = 16384; where the chain is the critical path the deeper product costs 1-3 %).
-  if (kend != n) step_mode = false;  // (a step launch updates ALL columns right of its panel)
-  const bool inner_left = !step_mode && (n - K0) > INNER_LEFT_ABOVE;
-  // The consumers of the fused kernel hold their slots for the whole POTRF (~30 us): while the bulk update fills the
-  // chip that costs it more than the saved launch (measured: 43.3 -> 41.8 TFLOP/s), so the fused kernel takes over
-  // where the panel chain is the critical path
-  const bool fused = ctx->tune.panel_fused && ctx->d_zpub && ctx->zpub_ready_n >= kend && ctx->img_ready == invd &&
-                     ((n - K0) <= FUSED_BELOW || step_mode);
+  // this panel's POTRF runs.  No update launches, nothing leaves stream s.  (inner_left, fused: factor_plan.h)
+  const PanelPlan pp = plan_panels(n, K0, kend, want_step, sw);
+  const bool step_mode = pp.step_mode, inner_left = pp.inner_left, fused = pp.fused;
   for (long long k = K0; k < kend; k += NB) {
     const int nbk = (int)((n - k < NB) ? n - k : NB);
     if (mark_event && k == mark_after + NB) (void)hipEventRecord(mark_event, s);  // everything up to panel mark_after is enqueued
@@ -1065,46 +1064,12 @@ static void panel_phase(agp_context *ctx, hipStream_t s, double *A, long long n,
         // the panel before this one (columns k - 128 .. k - 1) has not been applied to these columns - nor to anything
         // right of them - yet
         pa.dpub = ctx->d_dpub + (k / NB) * (long long)IMG_DOUBLES;
-        unsigned grid = (unsigned)(1 + UPD_BLOCKS + (pa.below + 63) / 64);
-        if (pa.below > 0) {
-          const long long nt = (pa.below + 63) / 64;  // 64-row blocks below = tile rows of the trailing triangle
-          pa.trail_first = grid;
-          pa.rowcnt = ctx->d_rowcnt + (k + NB) / 64;
-          pa.rowcnt_expect = 2ull * (unsigned long long)((k - K0) / NB);
-          const long long tiles = nt * (nt + 1) / 2 + 2 * nt;
-          // Workgroups go round-robin over the XCDs and, inside one, to its CUs in turn: the first `cus` of a launch get a
-          // CU each, number cus + i lands next to number i (scripts/microbench/hwid_probe.hip).  The critical workgroups -
-          // the factoring one, the nine that update its block, the row workgroups - keep their CUs to themselves:
-          // workgroups cus .. cus + (their number) are PLACEHOLDERS that idle until the image is complete (next to a
-          // trailing workgroup the POTRF takes 40-47 us instead of 27-30 and the diagonal block arrives after 10-13 us
-          // instead of 6).  The trailing workgroups take the tiles worker, worker + workers, ...: as many as fit on the
-          // CUs left, not one per tile (2600 starts and exits per launch at 4000 remaining rows cost ~10 %).  If the
-          // dispatch order ever differs this costs idle slots and nothing else.
-          const long long slots = step_slots(ctx), first_round = ctx->cus, ncrit = grid;
-          long long workers = tiles, nhold = 0;
-          if (ncrit + workers > first_round && ncrit < first_round) {
-            // all critical workgroups while the trailing update is short; from ~2900 remaining rows on it is what the
-            // launch takes and needs the slots: only the factoring workgroup and the nine that feed it
-            nhold = tiles <= 1200 ? ncrit : 1 + UPD_BLOCKS;
-            const long long cap = slots - ncrit - nhold;
-            if (workers > cap) workers = cap;
-            if (ncrit + workers <= first_round) nhold = 0;
-          } else if (workers > slots - ncrit) {
-            workers = slots - ncrit;
-          }
-          // (the row tiles come first in the tile order and every one needs a workgroup of its own up front: the row
-          // workgroups wait for them)
-          if (workers < 2 * nt) workers = 2 * nt < tiles ? 2 * nt : tiles;
-          pa.trail_tiles = tiles;
-          pa.trail_workers = workers;
-          grid += (unsigned)workers;
-          if (nhold > 0) {
-            pa.hold_index = (unsigned)first_round;
-            pa.hold_count = (unsigned)nhold;
-            grid += (unsigned)nhold;
-          }
-        }
-        hipLaunchKernelGGL(panel_fused_kernel<true>, dim3(grid), dim3(256), 0, s, pa);
+        const StepLaunchShape sh = step_launch_shape(pa.below, (k - K0) / NB, sw.step_slots, sw.cus);  // (factor_plan.h: who goes where)
+        pa.trail_first = sh.trail_first; pa.trail_tiles = sh.trail_tiles; pa.trail_workers = sh.trail_workers;
+        pa.hold_index = sh.hold_index; pa.hold_count = sh.hold_count;
+        pa.rowcnt_expect = sh.rowcnt_expect;
+        if (pa.below > 0) pa.rowcnt = ctx->d_rowcnt + (k + NB) / 64;
+        hipLaunchKernelGGL(panel_fused_kernel<true>, dim3(sh.grid), dim3(256), 0, s, pa);
         ++ctx->sched.panels_step;
       } else {
         hipLaunchKernelGGL(panel_fused_kernel<false>, dim3((unsigned)(1 + (pa.below + 63) / 64)), dim3(256), 0, s, pa);
@@ -1169,18 +1134,15 @@ static bool host_wait_event(hipEvent_t ev) {
   }
 }
 
-static bool step_ready(agp_context *ctx, const double *invd, long long kend) {
-  return ctx->tune.panel_fused && ctx->d_dpub && ctx->dpub_cap * NB >= kend && ctx->d_rowcnt && ctx->d_zpub &&
-         ctx->img_ready == invd && ctx->zpub_ready_n >= kend;
-}
-
 void panel_phase_public(agp_context *ctx, hipStream_t s, double *A, long long n, long long lda, double *img,
                         double *y, long long K0, long long kend) {
   // (one block column of a sharded fit, or a probe: the block's own panels as step launches - one launch per panel, no
   // update launches - while the second image and the counters, which are indexed by the GLOBAL block number, stay small)
-  const bool step = kend == n && kend <= 65536 && step_fits(ctx, kend - K0);
+  const long long step_below = ctx->tune.step_below;
+  const bool step = kend == n && kend <= 65536 && step_fits(step_below, step_below > 0 ? step_slots(ctx) : 0, kend - K0);
   panel_fused_prepare(ctx, s, img, K0, kend, step);
-  panel_phase(ctx, s, A, n, lda, img, y, K0, kend, nullptr, step && step_ready(ctx, img, kend));
+  const FactorSwitches sw = factor_switches(ctx, img, kend, ctx->update_variant);
+  panel_phase(ctx, s, A, n, lda, img, y, K0, kend, nullptr, sw, step && sw.step_buffers_ready);
   ctx->img_ready = nullptr;
 }
 
@@ -1213,18 +1175,72 @@ void trsm_rows_wide(hipStream_t s, double *X, long long ld, long long nrows, lon
   }
 }
 
-// Outer block width as a function of the remaining (trailing) size.  Wide blocks (K = 512) keep
-// the bulk update's C traffic off the HBM roofline and its MFMA efficiency up; narrow blocks
-// shorten the serial panel chain per step.  With the current panel kernels the choice barely
-// matters at N = 16384 (scripts/sweep_nbo.sh: every split at or below 4096 within 1 %).
-static long long pick_nbo(long long remaining, long long override_nbo = 0, long long wide = 0) {
-  if (override_nbo > 0) return override_nbo;
-  // (mixed precision, bf16 x 3: at 150 TFLOP/s the fp64 C read-modify-write of a K = 512 update is 2.3 TB/s next to
-  // 2.6 TB/s of operand strips beyond the L2 - a deeper outer block halves the former while many rows remain)
-  if (wide > 512 && remaining > NBO_WIDE_ABOVE) return wide;
-  if (remaining > NBO_512_ABOVE) return 512;
-  if (remaining > NBO_256_ABOVE) return 256;
-  return NB;
+// The wide diagonal blocks [first, first + count) of the factor (width ctx->bs_BW), inverted into ctx->bs_W on the
+// second stream for the back substitution of the fit; records ev_inv (same stream every time, so the latest record
+// covers the earlier inversions too) and reports the blocks in ctx->bs_done.  The caller has ordered the stream behind
+// whatever makes those blocks final.
+static void invert_wide_blocks(agp_context *ctx, double *A, long long lda, double *invd, long long first, long long count) {
+  const long long bw = ctx->bs_BW, img = (bw / NB) * (long long)IMG_DOUBLES;
+  hipStream_t si = ctx->stream2;
+  double *W = ctx->bs_W + first * bw * bw;
+  launch_set_identity_batched(si, W, bw, bw * bw, bw, count);
+  forward_solve_mat_batched(si, A + first * bw * (lda + 1), bw * (lda + 1), bw, lda, invd + first * img, img, W, bw * bw, bw, bw,
+                            /*rhs_lower=*/true, count);
+  (void)hipEventRecord(ctx->ev_inv, si);
+  ctx->bs_done = first + count;
+}
+
+// Mixed precision: ONE low-precision copy of a step's panel for all the tiles of U1 and of the bulk update - fp32
+// (variant 3), three bf16 planes (4, gemm_bf16x3.hip) or two fp16 planes of scaled rows (5, gemm_f16x2.hip).  Two
+// alternating buffers: the bulk update of step j still reads its copy while step j + 1 makes the next one; the copy of
+// step j + 2 is written after U2(j) has been waited for.  Without it every tile rounds the fp64 operands itself while it
+// stages them - twice the operand traffic of the fp32 kernel, which is what it waits for.
+struct StagedPanel {
+  int kind = 0;  // the variant whose copy this is: 3 (P32, ld32), 4 or 5 (P16); 0: none
+  const float *P32 = nullptr;
+  long long ld32 = 0;
+  const unsigned short *P16 = nullptr;
+};
+struct PanelStager {
+  agp_context *ctx;
+  int variant;
+  const double *rs16;  // variant 5: the row scales
+  bool flip = false;   // which of the two buffers is next
+  // P: the panel, rows x K (rows kend.. of the matrix).  Nothing is staged where the copy does not fit its buffer.
+  StagedPanel stage(hipStream_t s, const double *P, long long lda, long long rows, long long K, long long kend) {
+    StagedPanel out;
+    if (!ctx->p32) return out;
+    auto take = [&](auto *base) {  // (half the buffer, counted in elements of the copy's type)
+      auto *dst = base + (size_t)(flip ? 1 : 0) * (ctx->p32_bytes / sizeof(*base) / 2);
+      flip = !flip;
+      return dst;
+    };
+    unsigned short *planes = reinterpret_cast<unsigned short *>(ctx->p32);
+    if (variant == 3) {
+      out.ld32 = (rows + 7) / 8 * 8;
+      if (out.ld32 % 512 == 0) out.ld32 += 8;
+      if (sizeof(float) * (size_t)out.ld32 * (size_t)K * 2 > ctx->p32_bytes) return out;
+      float *dst = take(ctx->p32);
+      launch_convert_panel_f32(s, P, lda, rows, K, dst, out.ld32);
+      out.P32 = dst;
+    } else if (variant == 4 && K % 32 == 0 && 2 * bf16x3_bytes(rows, K) <= ctx->p32_bytes) {
+      unsigned short *dst = take(planes);
+      launch_convert_panel_bf16x3(s, P, lda, rows, K, dst);
+      out.P16 = dst;
+    } else if (variant == 5 && f16x2_depth_ok(K) && 2 * f16x2_bytes(rows, K) <= ctx->p32_bytes) {
+      unsigned short *dst = take(planes);
+      launch_convert_panel_f16x2(s, P, lda, rows, K, rs16 + kend, dst);
+      out.P16 = dst;
+    }
+    if (out.P32 || out.P16) out.kind = variant;
+    return out;
+  }
+};
+
+// The one place the record is filled from the plan: a step factor_lower has carried out, and the inversions that ran.
+static void record_step(ScheduleRecord &rec, const OuterStep &s, unsigned inverted) {
+  rec.add_step(s.next_end, s.bits);
+  rec.inv_bits |= inverted;
 }
 
 // Right-looking LL^T with one outer block of look-ahead on two streams:
@@ -1233,15 +1249,13 @@ static long long pick_nbo(long long remaining, long long override_nbo = 0, long 
 //   stream2: U2(j) = update of everything right of the next block column
 //            (the MFMA-bound bulk), overlapping P(j + 1).
 // Dependencies: U1(j), U2(j) after P(j) and after U2(j - 1).
+// WHICH outer steps there are and what each does is decided by FactorPlanner (factor_plan.h); this function carries the
+// steps out - streams, events, launches - and writes down what it did (ScheduleRecord).
 void factor_lower(agp_context *ctx, double *A, long long n, long long lda, double *invd, double *y,
                   FactorTimers *timers) {
-  hipStream_t sa = ctx->stream, sb = ctx->stream2;
-  hipStream_t sb_prev = sb;
-  bool have_u2 = false, p32_flip = false;
-  agp_context::ScheduleRecord &rec = ctx->sched;
-  rec.reset_factor(n);
-  long long K0 = 0, step_index = 0;
-  const long long nbo_fixed = ctx->nbo_override;
+  hipStream_t sa = ctx->stream, sb = ctx->stream2, sb_prev = sb;
+  bool have_u2 = false;
+  ctx->sched.reset_factor(n);
   int variant = ctx->update_variant;
   // variant 5 (fp16 x 2 products, gemm_f16x2.hip): power-of-two row scales from the diagonal, BEFORE the first panel overwrites it
   const double *rs16 = nullptr, *irs16 = nullptr;
@@ -1254,214 +1268,123 @@ void factor_lower(agp_context *ctx, double *A, long long n, long long lda, doubl
       variant = 4;
     }
   }
-  const long long nbo_wide = (variant == 4 || variant == 5) ? ctx->nbo_wide : ctx->tune.fp64_nbo;  // (fp64: AGP_FP64_NBO, measurement switch)
-  long long kend = K0 + pick_nbo(n, nbo_fixed, nbo_wide);
-  if (kend > n) kend = n;
   // (agp_fit_create has already planned and launched the fills together with its own: prep_external)
   if (!(ctx->prep_external && ctx->img_ready == invd && ctx->zpub_ready_n >= n)) panel_fused_prepare(ctx, sa, invd, 0, n, true);
   ctx->prep_external = false;
-  // the chain-bound tail as one launch per panel on this stream (panel_phase step_mode) once few enough rows are left
-  auto step_ok = [&](long long remaining) { return nbo_fixed == 0 && step_fits(ctx, remaining) && step_ready(ctx, invd, n); };
-  const bool step_all = step_ok(n);  // small matrix: every panel
-  if (step_all) kend = n;
-  // A fit that is ALL step launches (n <= 4608) never reaches the two-stream tail below, where the wide diagonal blocks
-  // of the back substitution get inverted on the idle second stream: here the host marks the panel after which all but
-  // the last wide block are final, and - the stream must not sit at a hipStreamWaitEvent next to the chain (section 8) -
-  // hands the inversion to the second stream itself once that mark has passed; the last four panels run meanwhile.
-  const bool early_inv = step_all && ctx->bs_W && ctx->bs_done == 0 && ctx->ev_inv && ctx->stream2 && ctx->bs_BW > 0 &&
-                         n % ctx->bs_BW == 0 && n / ctx->bs_BW >= 2;
-  rec.add_step(kend, step_all ? rec.STEP : 0u);
-  panel_phase(ctx, sa, A, n, lda, invd, y, K0, kend, timers, step_all, early_inv ? (n / ctx->bs_BW - 1) * ctx->bs_BW - NB : -1,
-              early_inv ? ctx->ev_c : nullptr);
-  if (early_inv) {
-    const long long BW = ctx->bs_BW, done = n / BW - 1;
-    if (host_wait_event(ctx->ev_c)) {  // (otherwise bs_done stays 0: the substitution inverts behind the factorisation)
-      hipStream_t si = ctx->stream2;
-      launch_set_identity_batched(si, ctx->bs_W, BW, BW * BW, BW, done);
-      forward_solve_mat_batched(si, A, BW * (lda + 1), BW, lda, invd, (BW / NB) * (long long)IMG_DOUBLES, ctx->bs_W, BW * BW, BW, BW,
-                                /*rhs_lower=*/true, done);
-      (void)hipEventRecord(ctx->ev_inv, si);
-      ctx->bs_done = done;
-      rec.inv_bits |= rec.INV_EARLY;
-    }
-  }
-  while (kend < n) {
-    long long next_end = kend + pick_nbo(n - kend, nbo_fixed, nbo_wide);
-    if (next_end > n) next_end = n;
-    // The very end runs on ONE stream: the last outer block spans all remaining columns - as step launches (U1 below
-    // becomes the hand-over update of the whole trailing matrix), or, where those are off, with <= SINGLE_BELOW rows left:
-    // there the bulk updates are 10-20 us launches, less than the ~10 us of event record / wait packets that hand each
-    // of them to the second stream and back
-    const long long K = kend - K0;
-    const bool step = step_ok(n - kend);
-    const bool single = !step && nbo_fixed == 0 && n - kend <= SINGLE_BELOW;
-    if (step || single) next_end = n;
-    if (ctx->bs_W && ctx->bs_done == 0 && next_end == n && ctx->ev_inv && ctx->stream2) {
-      // Last step: everything left of kend is final and the second stream has nothing more to do - it inverts the wide
-      // diagonal blocks the backward substitution of the fit will need (all but the last ones), off the chain.
-      const long long BW = ctx->bs_BW, done = kend / BW;
-      if (done > 0) {
-        hipStream_t si = ctx->stream2;
-        (void)hipEventRecord(ctx->ev_c, sa);  // columns < kend final
-        (void)hipStreamWaitEvent(si, ctx->ev_c, 0);
-        if (have_u2) (void)hipStreamWaitEvent(si, ctx->ev_b, 0);
-        launch_set_identity_batched(si, ctx->bs_W, BW, BW * BW, BW, done);
-        forward_solve_mat_batched(si, A, BW * (lda + 1), BW, lda, invd, (BW / NB) * (long long)IMG_DOUBLES, ctx->bs_W, BW * BW, BW, BW,
-                                  /*rhs_lower=*/true, done);
-        (void)hipEventRecord(ctx->ev_inv, si);
-        ctx->bs_done = done;
-        rec.inv_bits |= rec.INV_LAST_STEP;
-      }
-    }
-    const double *P = A + K0 * lda + kend;  // panel rows kend.., columns K0..kend
-    // mixed precision: ONE fp32 copy of the panel for all the tiles of U1 and of the bulk update (two alternating
-    // buffers: the bulk update of step j still reads its copy while step j + 1 makes the next one; the copy of step
-    // j + 2 is written after U2(j) has been waited for below).  Without it every tile rounds the fp64 operands itself
-    // while it stages them - twice the operand traffic of the fp32 kernel, which is what it waits for.
-    const float *P32 = nullptr;
-    long long ld32 = 0;
-    const unsigned short *P16 = nullptr;  // variant 4: the panel as three bf16 planes (gemm_bf16x3.hip), same two alternating buffers
-    if (variant == 3 && ctx->p32 && (n - kend) >= U1_F32_ABOVE) {
-      ld32 = (n - kend + 7) / 8 * 8;
-      if (ld32 % 512 == 0) ld32 += 8;
-      if (sizeof(float) * (size_t)ld32 * (size_t)K * 2 <= ctx->p32_bytes) {
-        float *dst = ctx->p32 + (size_t)(p32_flip ? 1 : 0) * (ctx->p32_bytes / sizeof(float) / 2);
-        p32_flip = !p32_flip;
-        launch_convert_panel_f32(sa, P, lda, n - kend, K, dst, ld32);
-        P32 = dst;
-      }
-    } else if (variant == 4 && ctx->p32 && (n - kend) >= U1_F32_ABOVE && K % 32 == 0 && 2 * bf16x3_bytes(n - kend, K) <= ctx->p32_bytes) {
-      unsigned short *dst = reinterpret_cast<unsigned short *>(ctx->p32) + (size_t)(p32_flip ? 1 : 0) * (ctx->p32_bytes / sizeof(unsigned short) / 2);
-      p32_flip = !p32_flip;
-      launch_convert_panel_bf16x3(sa, P, lda, n - kend, K, dst);
-      P16 = dst;
-    } else if (variant == 5 && ctx->p32 && (n - kend) >= U1_F32_ABOVE && f16x2_depth_ok(K) && 2 * f16x2_bytes(n - kend, K) <= ctx->p32_bytes) {
-      unsigned short *dst = reinterpret_cast<unsigned short *>(ctx->p32) + (size_t)(p32_flip ? 1 : 0) * (ctx->p32_bytes / sizeof(unsigned short) / 2);
-      p32_flip = !p32_flip;
-      launch_convert_panel_f16x2(sa, P, lda, n - kend, K, rs16 + kend, dst);
-      P16 = dst;
-    }
-    (void)hipEventRecord(ctx->ev_a, sa);                       // P(j) done
-    // Bulk-bound phase, fp64: U1(j) and U2(j) are ONE launch on the bulk stream - the whole trailing matrix, the tiles of
-    // the next block column FIRST (at the bulk kernel's efficiency: as a launch of its own on the chain stream U1 ran
-    // 64 x 64 tiles at MfmaUtil 0.38 next to the bulk update, waited for U2(j - 1) through an event, and sat on the
-    // critical path of P(j + 1)) and counted; the chain stream carries a one-wave gate kernel in U1's place, which lets
-    // P(j + 1) start when the count is complete, ~one tile time into the launch.  The chain stream never waits for ev_b here:
-    // the launch is stream-ordered behind U2(j - 1), and its head is what P(j + 1) needs.
-    const bool merged = variant <= 0 && nbo_fixed == 0 && !step && next_end < n && ctx->headcnt_ready && ctx->tune.merge_above > 0 &&
-                        (n - kend) > ctx->tune.merge_above && step_index < agp_context::HEADCNT_WORDS && (next_end - kend) % NB == 0;
-    if (merged) {
-      sb = (ctx->stream_masked && (n - kend) <= MASK_BELOW) ? ctx->stream_masked : ctx->stream2;
-      if (sb != sb_prev && have_u2) (void)hipStreamWaitEvent(sb, ctx->ev_b, 0);
-      sb_prev = sb;
-      (void)hipStreamWaitEvent(sb, ctx->ev_a, 0);
-      BulkTiming bt;
-      const bool timed = timers && timers->ev && timers->used + 2 <= timers->n_ev;
-      if (timed) { bt.e0 = timers->ev[timers->used]; bt.e1 = timers->ev[timers->used + 1]; }
-      long long head_tiles = 0;
-      unsigned long long *cnt = ctx->d_headcnt + step_index;
-      launch_trailing_update_merged(sb, A + kend * lda + kend, lda, P, lda, n - kend, K, (int)((next_end - kend) / NB), cnt, &head_tiles,
-                                    timed ? &bt : nullptr);
-      if (timed && bt.flops > 0.) {
-        timers->flops[timers->used / 2] = bt.flops;
-        timers->used += 2;
-      }
-      (void)hipEventRecord(ctx->ev_b, sb);
-      have_u2 = true;
-      launch_head_gate(sa, cnt, (unsigned long long)head_tiles, ctx->d_flags);
-      rec.add_step(next_end, rec.MERGED | (sb == ctx->stream_masked ? rec.MASKED : 0u));
-      panel_phase(ctx, sa, A, n, lda, invd, y, kend, next_end, timers, false);
-      K0 = kend;
-      kend = next_end;
-      ++step_index;
-      continue;
-    }
-    ++step_index;
-    // U2(j - 1) must be done before anything of step j touches the next block column
-    if (have_u2) (void)hipStreamWaitEvent(sa, ctx->ev_b, 0);
-    // U1: block column [kend, next_end), all rows below its diagonal
-    if (P16 && variant == 5) {
-      // mixed precision, fp16 x 2: U1 and the bulk update from the planes of this step's panel
-      launch_update_f16x2(sa, A + kend * lda + kend, lda, P16, n - kend, 0, 0, irs16 + kend, n - kend, next_end - kend, K);
-    } else if (P16) {
-      // mixed precision, bf16 x 3: U1 and the bulk update from the planes of this step's panel
-      launch_update_bf16x3(sa, A + kend * lda + kend, lda, P16, n - kend, 0, 0, n - kend, next_end - kend, K);
-    } else if ((variant == 3 || variant == 4 || variant == 5) && (n - kend) >= U1_F32_ABOVE) {
-      // mixed precision: U1 on the fp32 MFMA path like the bulk update (products of fp32-rounded panels, fp64
-      // subtraction) while the block column is tall enough for 128 x 128 tiles to fill the chip
-      launch_update_f32(sa, A + kend * lda + kend, lda, P, P, lda, n - kend, next_end - kend, K, P32, P32, ld32);
-    } else if (step && n - kend > 1536) {
-      // hand-over to the step tail: the whole trailing matrix, on the chain stream, alone on the chip - the bulk kernel
-      timed_gemm(sa, timers, A + kend * lda + kend, lda, P, P, n - kend, n - kend, K, true, variant >= 4 ? 3 : variant);
-    } else {
-      timed_gemm(sa, timers, A + kend * lda + kend, lda, P, P, n - kend, next_end - kend, K, false);
-    }
-    // Chain-bound phase (few rows left): a stream that sits at an UNSATISFIED hipStreamWaitEvent slows every dependent
-    // launch of the other streams (measured, scripts/probe_chain.py: the panel chain takes 121 instead of 44 us per 128
-    // columns while another stream waits on an event) - and here the bulk stream would wait for the panel chain all the
-    // time.  So the host enqueues the next panel phase first and hands U2(j) to the bulk stream only once P(j) HAS
-    // finished (hipEventQuery): the bulk stream is idle instead of blocked.  In the bulk-bound phase the host must run
-    // far ahead, and the waits of the bulk stream are satisfied by the time it reaches them.
-    // End phase: the bulk updates move to the CU-masked stream.  A bulk update that fills every CU (the 64 x 64-tile
-    // kernel takes all 160 KB of LDS) keeps the panel kernels - 75-79 KB of LDS per workgroup - out until its grid has
-    // drained: POTRF took 400-500 us instead of 30 (profiles/r02), panel chain and bulk update ran one after the
-    // other.  With a few CUs per XCD left free the two overlap.
-    sb = (ctx->stream_masked && (n - kend) <= MASK_BELOW) ? ctx->stream_masked : ctx->stream2;
+  const FactorSwitches sw = factor_switches(ctx, invd, n, variant);
+  FactorPlanner plan(n, sw);
+  PanelStager stager{ctx, variant, rs16};
+  // The bulk stream of a step - in the end phase the CU-masked one (OuterStep::masked): a bulk update that fills every CU (the
+  // 64 x 64-tile kernel takes all 160 KB of LDS) keeps the panel kernels - 75-79 KB of LDS per workgroup - out until its
+  // grid has drained: POTRF took 400-500 us instead of 30 (profiles/r02), panel chain and bulk update ran one after
+  // the other.  With a few CUs per XCD left free the two overlap.
+  auto pick_bulk_stream = [&](const OuterStep &s) {
+    sb = s.masked ? ctx->stream_masked : ctx->stream2;
     if (sb != sb_prev && have_u2) (void)hipStreamWaitEvent(sb, ctx->ev_b, 0);  // U2(j - 1) ran on the other bulk stream
     sb_prev = sb;
-    const bool throttle = next_end < n && (n - kend) <= THROTTLE_BELOW;
-    rec.add_step(next_end, (step ? rec.STEP : 0u) | (throttle ? rec.THROTTLED : 0u) | (single ? rec.SINGLE : 0u) |
-                               (next_end < n && sb == ctx->stream_masked ? rec.MASKED : 0u));
-    if (throttle) panel_phase(ctx, sa, A, n, lda, invd, y, kend, next_end, timers, step);
-    if (next_end < n) {
-      if (throttle) {
-        if (!host_wait_event(ctx->ev_a)) (void)hipStreamWaitEvent(sb, ctx->ev_a, 0);
-      } else {
+  };
+  OuterStep s;
+  while (plan.next(s)) {
+    const long long kend = s.kend, next_end = s.next_end, K = kend - s.k0, rows = n - kend;
+    const bool throttle = s.bits & STEP_BIT_THROTTLED, last = next_end == n;
+    unsigned inverted = 0;
+    if (s.inv_last_step > 0) {
+      (void)hipEventRecord(ctx->ev_c, sa);  // columns < kend final
+      (void)hipStreamWaitEvent(ctx->stream2, ctx->ev_c, 0);
+      if (have_u2) (void)hipStreamWaitEvent(ctx->stream2, ctx->ev_b, 0);
+      invert_wide_blocks(ctx, A, lda, invd, 0, s.inv_last_step);
+      inverted |= INV_BIT_LAST_STEP;
+    }
+    const double *P = A + s.k0 * lda + kend;  // panel rows kend.., columns K0..kend
+    if (kend > 0) {  // (the first step has no panel to apply)
+      const StagedPanel st = s.mixed_tall ? stager.stage(sa, P, lda, rows, K, kend) : StagedPanel();
+      (void)hipEventRecord(ctx->ev_a, sa);                       // P(j) done
+      if (s.bits & STEP_BIT_MERGED) {
+        // Bulk-bound phase, fp64: U1(j) and U2(j) are ONE launch on the bulk stream - the whole trailing matrix, the tiles of
+        // the next block column FIRST (at the bulk kernel's efficiency: as a launch of its own on the chain stream U1 ran
+        // 64 x 64 tiles at MfmaUtil 0.38 next to the bulk update, waited for U2(j - 1) through an event, and sat on the
+        // critical path of P(j + 1)) and counted; the chain stream carries a one-wave gate kernel in U1's place, which lets
+        // P(j + 1) start when the count is complete, ~one tile time into the launch.  The chain stream never waits for ev_b here:
+        // the launch is stream-ordered behind U2(j - 1), and its head is what P(j + 1) needs.
+        pick_bulk_stream(s);
         (void)hipStreamWaitEvent(sb, ctx->ev_a, 0);
+        BulkTiming bt;
+        const bool timed = timers && timers->ev && timers->used + 2 <= timers->n_ev;
+        if (timed) { bt.e0 = timers->ev[timers->used]; bt.e1 = timers->ev[timers->used + 1]; }
+        long long head_tiles = 0;
+        unsigned long long *cnt = ctx->d_headcnt + s.index;
+        launch_trailing_update_merged(sb, A + kend * lda + kend, lda, P, lda, rows, K, (int)((next_end - kend) / NB), cnt, &head_tiles,
+                                      timed ? &bt : nullptr);
+        if (timed && bt.flops > 0.) {
+          timers->flops[timers->used / 2] = bt.flops;
+          timers->used += 2;
+        }
+        (void)hipEventRecord(ctx->ev_b, sb);
+        have_u2 = true;
+        launch_head_gate(sa, cnt, (unsigned long long)head_tiles, ctx->d_flags);
+      } else {
+        // U2(j - 1) must be done before anything of step j touches the next block column
+        if (have_u2) (void)hipStreamWaitEvent(sa, ctx->ev_b, 0);
+        // U1: block column [kend, next_end), all rows below its diagonal
+        if (st.kind == 5) {
+          // mixed precision, fp16 x 2: U1 and the bulk update from the planes of this step's panel
+          launch_update_f16x2(sa, A + kend * lda + kend, lda, st.P16, rows, 0, 0, irs16 + kend, rows, next_end - kend, K);
+        } else if (st.kind == 4) {
+          // mixed precision, bf16 x 3: U1 and the bulk update from the planes of this step's panel
+          launch_update_bf16x3(sa, A + kend * lda + kend, lda, st.P16, rows, 0, 0, rows, next_end - kend, K);
+        } else if (s.mixed_tall) {
+          // mixed precision: U1 on the fp32 MFMA path like the bulk update (products of fp32-rounded panels, fp64
+          // subtraction) while the block column is tall enough for 128 x 128 tiles to fill the chip
+          launch_update_f32(sa, A + kend * lda + kend, lda, P, P, lda, rows, next_end - kend, K, st.P32, st.P32, st.ld32);
+        } else if (s.handover_whole_trailing) {
+          // hand-over to the step tail: the whole trailing matrix, on the chain stream, alone on the chip - the bulk kernel
+          timed_gemm(sa, timers, A + kend * lda + kend, lda, P, P, rows, rows, K, true, variant >= 4 ? 3 : variant);
+        } else {
+          timed_gemm(sa, timers, A + kend * lda + kend, lda, P, P, rows, next_end - kend, K, false);
+        }
+        // Chain-bound phase (few rows left): a stream that sits at an UNSATISFIED hipStreamWaitEvent slows every dependent
+        // launch of the other streams (measured, scripts/probe_chain.py: the panel chain takes 121 instead of 44 us per 128
+        // columns while another stream waits on an event) - and here the bulk stream would wait for the panel chain all the
+        // time.  So the host enqueues the next panel phase first and hands U2(j) to the bulk stream only once P(j) HAS
+        // finished (hipEventQuery): the bulk stream is idle instead of blocked.  In the bulk-bound phase the host must run
+        // far ahead, and the waits of the bulk stream are satisfied by the time it reaches them.
+        pick_bulk_stream(s);
+        if (throttle) panel_phase(ctx, sa, A, n, lda, invd, y, kend, next_end, timers, sw, s.step_mode);
+        if (!last) {
+          if (!throttle || !host_wait_event(ctx->ev_a)) (void)hipStreamWaitEvent(sb, ctx->ev_a, 0);
+          const double *Q = A + s.k0 * lda + next_end;
+          if (st.P16) {
+            const long long M2 = n - next_end;
+            const int ntr = (int)((M2 + 127) / 128);
+            const long long tiles = (long long)ntr * (ntr + 1) / 2;
+            long long olen = 0;
+            const int *order = tiles >= 1024 ? bulk_tile_order(ntr, tiles, &olen) : nullptr;
+            if (st.kind == 5)
+              launch_update_f16x2(sb, A + next_end * lda + next_end, lda, st.P16, rows, next_end - kend, next_end - kend, irs16 + kend, M2, M2, K,
+                                  order, olen);
+            else
+              launch_update_bf16x3(sb, A + next_end * lda + next_end, lda, st.P16, rows, next_end - kend, next_end - kend, M2, M2, K, order, olen);
+          } else {
+            timed_gemm(sb, timers, A + next_end * lda + next_end, lda, Q, Q, n - next_end, n - next_end, K, true, variant >= 4 ? 3 : variant,
+                       st.P32 ? st.P32 + (next_end - kend) : nullptr, st.ld32);
+          }
+          (void)hipEventRecord(ctx->ev_b, sb);
+        }
+        have_u2 = !last;
       }
-      const double *Q = A + K0 * lda + next_end;
-      if (P16) {
-        const long long M2 = n - next_end;
-        const int ntr = (int)((M2 + 127) / 128);
-        const long long tiles = (long long)ntr * (ntr + 1) / 2;
-        long long olen = 0;
-        const int *order = tiles >= 1024 ? bulk_tile_order(ntr, tiles, &olen) : nullptr;
-        if (variant == 5)
-          launch_update_f16x2(sb, A + next_end * lda + next_end, lda, P16, n - kend, next_end - kend, next_end - kend, irs16 + kend, M2, M2, K,
-                              order, olen);
-        else
-          launch_update_bf16x3(sb, A + next_end * lda + next_end, lda, P16, n - kend, next_end - kend, next_end - kend, M2, M2, K, order, olen);
-      } else
-      timed_gemm(sb, timers, A + next_end * lda + next_end, lda, Q, Q, n - next_end, n - next_end, K, true, variant >= 4 ? 3 : variant,
-                 P32 ? P32 + (next_end - kend) : nullptr, ld32);
-      (void)hipEventRecord(ctx->ev_b, sb);
-      have_u2 = true;
-    } else {
-      have_u2 = false;
     }
-    // The step tail of a large fit, like the all-step fit above: the wide diagonal blocks that become final INSIDE the tail
-    // (all but the last one) are inverted on the idle second stream under the tail's last four panels - the back
-    // substitution of the fit used to invert them behind the factorisation (~0.15 ms of a 29 ms fit at N = 16384).
-    const long long bw = ctx->bs_BW;
-    const bool tail_inv = !throttle && step && next_end == n && ctx->bs_W && bw > 0 && ctx->ev_inv && ctx->stream2 && n % bw == 0 &&
-                          ctx->bs_done > 0 && ctx->bs_done == kend / bw && n / bw - 1 > ctx->bs_done && (n / bw - 1) * bw - NB >= kend;
-    if (!throttle) panel_phase(ctx, sa, A, n, lda, invd, y, kend, next_end, timers, step, tail_inv ? (n / bw - 1) * bw - NB : -1,
-                               tail_inv ? ctx->ev_c : nullptr);
-    if (tail_inv) {
-      const long long first = ctx->bs_done, last = n / bw - 1, cnt = last - first;
-      if (host_wait_event(ctx->ev_c)) {
-        // (ev_inv already carries the first `first` inverses: same stream, so the new record covers both)
-        hipStream_t si = ctx->stream2;
-        launch_set_identity_batched(si, ctx->bs_W + first * bw * bw, bw, bw * bw, bw, cnt);
-        forward_solve_mat_batched(si, A + first * bw * (lda + 1), bw * (lda + 1), bw, lda, invd + first * (bw / NB) * (long long)IMG_DOUBLES,
-                                  (bw / NB) * (long long)IMG_DOUBLES, ctx->bs_W + first * bw * bw, bw * bw, bw, bw, /*rhs_lower=*/true, cnt);
-        (void)hipEventRecord(ctx->ev_inv, si);
-        ctx->bs_done = last;
-        rec.inv_bits |= rec.INV_TAIL;
-      }
+    // P(j + 1).  With an inversion under the panels (factor_plan.h: OuterStep) the host marks the panel after which its
+    // blocks are final and - the second stream must not sit at a hipStreamWaitEvent next to the chain (section 8) - hands
+    // the inversion over itself once that mark has passed; the last four panels run meanwhile.
+    const bool mark = s.inv_count > 0;
+    if (!throttle) panel_phase(ctx, sa, A, n, lda, invd, y, kend, next_end, timers, sw, s.step_mode, s.mark_after, mark ? ctx->ev_c : nullptr);
+    if (mark) {
+      const bool ran = host_wait_event(ctx->ev_c);  // (otherwise bs_done stays: the substitution inverts behind the factorisation)
+      if (ran) invert_wide_blocks(ctx, A, lda, invd, s.inv_first, s.inv_count);
+      if (ran) inverted |= s.inv_bit;
+      plan.inversion_under_panels(s, ran);
     }
-    K0 = kend;
-    kend = next_end;
+    record_step(ctx->sched, s, inverted);
   }
   // the panel stream ran last (its final panel depends on every update)
   ctx->img_ready = nullptr;

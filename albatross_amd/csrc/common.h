@@ -154,8 +154,9 @@ struct agp_context {
   static constexpr long long HEADCNT_WORDS = 256;
   unsigned long long *d_headcnt = nullptr;
   bool headcnt_ready = false;
-  // What the last factorisation / fit of this context ran: host-side only, filled at the branch points of factor_lower,
-  // panel_phase (chol.hip) and fit_create_impl (api.hip), read by the tests through agp_debug_schedule (debug_api.hip,
+  // What the last factorisation / fit of this context ran: host-side only, filled by factor_lower from each planned step
+  // it has carried out (factor_plan.h: OuterStep), at the panel launches of panel_phase (chol.hip) and by fit_create_impl
+  // (api.hip), read by the tests through agp_debug_schedule (debug_api.hip,
   // which documents the layout).  Nothing in the library reads it back.
   struct ScheduleRecord {
     // outer steps: bits of each step

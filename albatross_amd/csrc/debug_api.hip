@@ -11,6 +11,7 @@
 #include "shard_internal.h"
 #include "pub.h"
 #include "trsm_kernel.h"
+#include "factor_plan.h"
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -1228,6 +1229,58 @@ AGP_DEBUG_API int agp_debug_schedule(agp_context *ctx, int64_t *out, int64_t cap
   }
   const int64_t total = SCHED_HEADER + 2 * agp_context::HEADCNT_WORDS;
   for (int64_t i = 0; i < cap && i < total; ++i) out[i] = w[i];
+  return AGP_OK;
+}
+
+// The schedule factor_lower WOULD run for n rows under the given switches (factor_plan.h) - no context, no device.
+// switches (int64, the fields of FactorSwitches in order): panel_fused, step_below, merge_above, nbo_override, nbo_wide,
+// variant, step_slots, cus, have_masked_stream, headcnt_ready, step_buffers_ready, fused_buffers_ready, inv_requested,
+// bs_BW, bs_done.  `out` has the layout of agp_debug_schedule - [0] n, [1] steps, [2] steps beyond the record, [3..5] the
+// panel launches, [7] bs_done and [8] the inversion bits if every host-side wait succeeds, [20 + 2 i] end and bits of
+// step i - followed, from word 20 + 2 * 256 on, by five words per step: the inversion intents of OuterStep
+// (inv_last_step, inv_first, inv_count, mark_after, inv_bit).  At most `cap` words are written.
+constexpr int64_t PLAN_WORDS = SCHED_HEADER + 7 * agp_context::HEADCNT_WORDS;
+AGP_DEBUG_API int agp_debug_factor_plan(const int64_t *switches, int64_t n, int64_t *out, int64_t cap) {
+  if (!switches || !out || n < 1 || cap < 0) return AGP_ERR_INVALID_ARGUMENT;
+  agp::FactorSwitches sw;
+  sw.panel_fused = switches[0] != 0; sw.step_below = switches[1]; sw.merge_above = switches[2];
+  sw.nbo_override = switches[3]; sw.nbo_wide = switches[4]; sw.variant = (int)switches[5];
+  sw.step_slots = switches[6]; sw.cus = switches[7];
+  sw.have_masked_stream = switches[8] != 0; sw.headcnt_ready = switches[9] != 0;
+  sw.step_buffers_ready = switches[10] != 0; sw.fused_buffers_ready = switches[11] != 0;
+  sw.inv_requested = switches[12] != 0; sw.bs_BW = switches[13]; sw.bs_done = switches[14];
+  int64_t w[PLAN_WORDS] = {};
+  int64_t *steps = w + SCHED_HEADER, *intents = steps + 2 * agp_context::HEADCNT_WORDS;
+  agp::FactorPlanner plan(n, sw);
+  agp::OuterStep s;
+  w[0] = n;
+  while (plan.next(s)) {
+    const int64_t blocks = (s.next_end - s.kend + agp::NB - 1) / agp::NB;
+    const agp::PanelPlan pp = agp::plan_panels(n, s.kend, s.next_end, s.step_mode, sw);
+    // (panel_phase: a step block's first panel is a plain fused launch)
+    if (!pp.fused) w[5] += blocks;
+    else if (!pp.step_mode) w[4] += blocks;
+    else { w[4] += 1; w[3] += blocks - 1; }
+    w[8] |= (s.inv_last_step > 0 ? agp::INV_BIT_LAST_STEP : 0u) | (s.inv_count > 0 ? s.inv_bit : 0u);
+    plan.inversion_under_panels(s, s.inv_count > 0);
+    if (w[1] >= agp_context::HEADCNT_WORDS) { ++w[2]; continue; }
+    const int64_t i = w[1]++;
+    steps[2 * i] = s.next_end; steps[2 * i + 1] = s.bits;
+    const int64_t intent[5] = {s.inv_last_step, s.inv_first, s.inv_count, s.mark_after, s.inv_bit};
+    std::copy(intent, intent + 5, intents + 5 * i);
+  }
+  w[7] = plan.bs_done();
+  std::copy(w, w + std::min(cap, PLAN_WORDS), out);
+  return AGP_OK;
+}
+
+// step_launch_shape (factor_plan.h) for `below` rows under the panels_done-th panel of its block: out[0..6] = grid,
+// trail_first, trail_tiles, trail_workers, hold_index, hold_count, rowcnt_expect.
+AGP_DEBUG_API int agp_debug_step_launch_shape(int64_t below, int64_t panels_done, int64_t step_slots, int64_t cus, int64_t *out) {
+  if (!out || below < 0) return AGP_ERR_INVALID_ARGUMENT;
+  const agp::StepLaunchShape sh = agp::step_launch_shape(below, panels_done, step_slots, cus);
+  const int64_t w[7] = {sh.grid, sh.trail_first, sh.trail_tiles, sh.trail_workers, sh.hold_index, sh.hold_count, (int64_t)sh.rowcnt_expect};
+  std::copy(w, w + 7, out);
   return AGP_OK;
 }
 

@@ -1,5 +1,5 @@
 // host_sanitize_check.cpp — the host-side C++ of the project under AddressSanitizer + UndefinedBehaviorSanitizer, on
-// a machine WITHOUT a GPU (examples/Makefile: `make asan`).  Three parts:
+// a machine WITHOUT a GPU (examples/Makefile: `make asan`).  Four parts:
 //
 //  1. the sharded-fit schedule (albatross_amd/csrc/shard_sched.hip is plain C++: compiled INTO this binary with the
 //     sanitizers on) driven through agp_debug_shard_factor_custom (csrc/shard_custom.hip) with naive block operations, one rank and - through
@@ -9,7 +9,9 @@
 //     first device call;
 //  3. the workspace layouts of the batched fits (albatross_amd/csrc/ws_layout.h, batch_layout.h: plain C++) over a
 //     malloc'd base: every region aligned, inside the allocation and disjoint from the others, the sizing pass equal to
-//     the real one, the size within the alignment padding of the plain sums, first and last word of every region written.
+//     the real one, the size within the alignment padding of the plain sums, first and last word of every region written;
+//  4. the schedule of the dense factorisation (albatross_amd/csrc/factor_plan.h: plain C++): every n up to 20480 planned
+//     under two switch sets, every step's panels planned, and a sweep of the step-launch shapes.
 //
 // Prints "host_sanitize_check ok" and exits 0; any sanitizer report aborts with a non-zero status.
 #include <cmath>
@@ -22,6 +24,7 @@
 
 #include "albatross_amd/albatross.hpp"
 #include "batch_layout.h"    // csrc/: WsLayout, BatchGeometry, the carve functions
+#include "factor_plan.h"     // csrc/: FactorPlanner, plan_panels, step_launch_shape
 #include "shard_internal.h"  // agp_shard_ops_callbacks (csrc/, test-only)
 
 extern "C" {
@@ -339,6 +342,40 @@ void layouts_under_sanitizers() {
         }
       }
 }
+
+// ---- part 4: the factorisation's schedule --------------------------------------------------------------------------
+void factor_plan_under_sanitizers() {
+  agp::FactorSwitches on;  // an MI355X with everything set up, a fit's inversion of the wide blocks requested
+  on.step_slots = 512; on.have_masked_stream = on.headcnt_ready = on.step_buffers_ready = on.fused_buffers_ready = true;
+  on.inv_requested = true; on.bs_BW = 512;
+  agp::FactorSwitches off;  // the two-launch schedule of a context that was demoted, nothing requested
+  off.panel_fused = false; off.step_below = off.merge_above = 0;
+  for (const agp::FactorSwitches &sw : {on, off})
+    for (long long n = 1; n <= 20480; ++n) {
+      agp::FactorPlanner plan(n, sw);
+      agp::OuterStep s;
+      long long end = 0, steps = 0, panels = 0;
+      while (plan.next(s)) {
+        require(s.kend == end && s.next_end > end && s.next_end <= n && s.k0 <= s.kend, "outer steps follow each other");
+        const agp::PanelPlan pp = agp::plan_panels(n, s.kend, s.next_end, s.step_mode, sw);
+        require(!(pp.step_mode && pp.inner_left) && (!pp.fused || sw.panel_fused), "panel plan");
+        require(s.inv_count == 0 || (s.mark_after >= s.kend && s.mark_after < n), "mark inside the step");
+        plan.inversion_under_panels(s, s.inv_count > 0);
+        panels += (s.next_end - end + agp::PLAN_NB - 1) / agp::PLAN_NB;
+        end = s.next_end;
+        ++steps;
+      }
+      require(end == n && steps <= 2 + n / agp::PLAN_NB && panels == (n + agp::PLAN_NB - 1) / agp::PLAN_NB, "the steps cover the matrix");
+      require(plan.bs_done() * sw.bs_BW < n || plan.bs_done() == 0, "the last wide block is never inverted early");
+    }
+  for (long long slots : {146ll, 512ll, 1024ll})
+    for (long long below = 0; below <= 4608; ++below) {
+      const agp::StepLaunchShape sh = agp::step_launch_shape(below, 3, slots, 256);
+      const long long critical = agp::STEP_FIXED_CRITICAL + (below + 63) / 64;
+      require(below == 0 ? sh.grid == critical : sh.grid == critical + sh.trail_workers + sh.hold_count, "grid of a step launch");
+      require(sh.trail_workers >= 1 && (below == 0 || sh.trail_workers <= sh.trail_tiles), "trailing workgroups");
+    }
+}
 }  // namespace
 
 int main() {
@@ -346,6 +383,7 @@ int main() {
   schedule_under_sanitizers(true);
   host_layer_under_sanitizers();
   layouts_under_sanitizers();
+  factor_plan_under_sanitizers();
   std::printf("host_sanitize_check ok\n");
   return 0;
 }

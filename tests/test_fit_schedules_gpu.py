@@ -5,8 +5,10 @@ fit_create_impl), checked with componentwise backward-error bounds, and with the
 The factorisation is not one algorithm: the outer block width, the merged / throttled / CU-masked bulk updates, the step
 launches, the fused and the two-launch panels and the single-stream end each switch on the number of REMAINING rows, and
 the back substitution of a fit has four paths of its own.  Every size below is derived from the thresholds so that the
-first outer steps fall on either side of one of them; `expected_schedule` restates the branch conditions of factor_lower
-and each case checks the record against it.
+first outer steps fall on either side of one of them; `expected_schedule` (tests/fit_schedule_cases.py) restates the
+branch conditions independently of the library and each case checks the record against it.  The library decides the
+schedule in csrc/factor_plan.h; tests/test_fit_schedule_host.py compares that plan with the same restatement at every n
+without a device, and this module stays the proof that what a real factorisation RAN is the plan.
 
 Bounds (u = 2^-53, G = |L| |L|^T, c = 4):
   factor       |K - L L^T| <= c n u G elementwise (Higham, Thm 10.3: gamma_{n+1}, plus the check's own product)
@@ -27,19 +29,17 @@ import pytest
 import albatross_amd as ab
 from albatross_amd import _capi as capi
 from conftest import synthetic_3d
+from fit_schedule_cases import (INV_EARLY, INV_LAST_STEP, INV_TAIL, MASKED, MERGED, NB, SCHED_HEADER, SCHED_STEPS, SINGLE, STEP,
+                                THROTTLED, expected_schedule, step_fits)
 
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -53
 CB = 4.0  # c of the bounds above
-NB = 128
 FULL_CHECK_MAX = 4700  # above: whole 128-row block rows only
 
 # ---- the schedule record (csrc/debug_api.hip: agp_debug_schedule, which documents the layout) -----------------------
-SCHED_HEADER, SCHED_STEPS = 20, 256
-MERGED, STEP, THROTTLED, MASKED, SINGLE = 1, 2, 4, 8, 16
 BS_NONE, BS_COOP_DIRECT, BS_COOP_FLAGS, BS_WIDE, BS_CHAIN = 0, 1, 2, 3, 4
-INV_EARLY, INV_LAST_STEP, INV_TAIL = 1, 2, 4
 _HEADER_FIELDS = ("n", "steps", "steps_dropped", "panels_step", "panels_fused", "panels_split", "backsub", "bs_done",
                   "inv", "handover_timeout", "demotions", "step_slots", "cus", "masked_stream", "step_below",
                   "panel_fused", "merge_above", "backsub_coop", "fp64_nbo")
@@ -60,63 +60,6 @@ def schedule(ctx):
 
 def count_steps(rec, bit):
     return sum(1 for _, b in rec["outer"] if b & bit)
-
-
-def step_fits(rec, rows):
-    """chol.hip: step_fits (with step_ready: the step launches need the fused panel kernel's buffers)."""
-    return (rec["panel_fused"] == 1 and rec["step_below"] > 0 and rows <= rec["step_below"]
-            and rec["step_slots"] >= 10 + rows // 64 + 64)
-
-
-def expected_schedule(n, rec):
-    """factor_lower's outer steps and panel launches for an n x n fp64 factorisation under the switches in force (read
-    from the record), restated from chol.hip: (outer [(end, bits)], panel counts {step, fused, split})."""
-    wide = rec["fp64_nbo"]
-
-    def pick_nbo(r):
-        if wide > 512 and r > 8192:
-            return wide
-        return 512 if r > 2048 else 256 if r > 1024 else NB
-
-    fused_on = rec["panel_fused"] == 1
-    headcnt = fused_on and rec["merge_above"] > 0 and n > rec["merge_above"]
-    blocks = []  # (K0, kend, step mode)
-    kend = min(pick_nbo(n), n)
-    step_all = step_fits(rec, n)
-    if step_all:
-        kend = n
-    outer = [(kend, STEP if step_all else 0)]
-    blocks.append((0, kend, step_all))
-    idx = 0
-    while kend < n:
-        r = n - kend
-        ne = min(kend + pick_nbo(r), n)
-        step = step_fits(rec, r)
-        single = not step and r <= 1536
-        if step or single:
-            ne = n
-        masked = rec["masked_stream"] == 1 and r <= 8704
-        merged = (not step and ne < n and headcnt and r > rec["merge_above"] and idx < SCHED_STEPS
-                  and (ne - kend) % NB == 0)
-        idx += 1
-        if merged:
-            outer.append((ne, MERGED | (MASKED if masked else 0)))
-        else:
-            throttle = ne < n and r <= 8192
-            outer.append((ne, (STEP if step else 0) | (THROTTLED if throttle else 0) | (SINGLE if single else 0)
-                          | (MASKED if ne < n and masked else 0)))
-        blocks.append((kend, ne, step))
-        kend = ne
-    panels = {"step": 0, "fused": 0, "split": 0}
-    for k0, k1, step_mode in blocks:
-        count = -(-(k1 - k0) // NB)
-        step_mode = step_mode and k1 == n
-        if fused_on and ((n - k0) <= 4608 or step_mode):
-            panels["fused"] += 1 if step_mode else count
-            panels["step"] += count - 1 if step_mode else 0
-        else:
-            panels["split"] += count
-    return outer, panels
 
 
 def check_schedule(rec, n):
