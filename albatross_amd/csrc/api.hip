@@ -183,7 +183,8 @@ int agp_device_count(void) {
 }
 
 static constexpr long long BACKSUB_COOP_MAX_N = 2047;
-// the switches of include/albatross_amd.h ("switches"): read here, once per context, and nowhere else
+// the switches of include/albatross_amd.h ("switches"): read here, once per context, and nowhere else; they take effect
+// through ctx->tune alone, so a context keeps the settings it was created under (the one exception: AGP_GRAM_SOP, above)
 static agp_context::Tuning read_tuning() {
   agp_context::Tuning t;
   auto flag = [](const char *name, bool dflt) {
@@ -201,14 +202,17 @@ static agp_context::Tuning read_tuning() {
   t.backsub_coop_max = number("AGP_BACKSUB_COOP_MAX", BACKSUB_COOP_MAX_N);
   t.mixed_bf16 = flag("AGP_MIXED_BF16", true);
   t.mixed_f16 = flag("AGP_MIXED_F16", true);
-  set_f16x2_kernel((int)number("AGP_F16X2_LDS_PAD", 8192), (int)number("AGP_F16X2_TERMS", 4), (int)number("AGP_F16X2_CHUNK", 32));
+  t.f16x2.lds_pad = (int)number("AGP_F16X2_LDS_PAD", 8192);
+  t.f16x2.terms = number("AGP_F16X2_TERMS", 4) == 3 ? 3 : 4;
+  t.f16x2.chunk = number("AGP_F16X2_CHUNK", 32) == 64 ? 64 : 32;
   t.mixed_nbo = number("AGP_MIXED_NBO", 512);
   t.fp64_nbo = number("AGP_FP64_NBO", 0);
   // (the rule agp_fit_create_mixed applies to AGP_MIXED_NBO: outer block edges must fall on 128-column panel edges, and
   // only a width above 512 changes anything - the panels of an outer block are NB = 128 wide, and a 700-wide block would
   // end inside its last panel)
   if (t.fp64_nbo <= 512 || t.fp64_nbo % 128 != 0) t.fp64_nbo = 0;
-  set_bf16x3_kernel((int)number("AGP_BF16X3_KERNEL", 2), (int)number("AGP_BF16X3_LDS_PAD", 8192));
+  t.bf16x3.kernel = (int)number("AGP_BF16X3_KERNEL", 2);
+  t.bf16x3.lds_pad = (int)number("AGP_BF16X3_LDS_PAD", 8192);
   t.sparse_pivoted = flag("AGP_SPARSE_PIVOTED", false);
   t.predict_chunk = number("AGP_PREDICT_CHUNK", 0);
   t.shard_block = number("AGP_SHARD_BLOCK", 0);
@@ -589,10 +593,12 @@ static constexpr size_t STATUS_BYTES = 4 * sizeof(int) + 4 * sizeof(double);
 // pre (optional): fills and copies the caller wants made BEFORE the Gram matrix is built, in the same launch as the
 // zeroing of the flags and the sentinel fills of the panel kernels (pub.h: a fit of a few hundred points used to
 // spend ten launches on these)
+// req: what the caller asks of the factorisation (its prep and timers are filled in here); outcome (optional): what
+// factor_lower reported
 static int build_and_factor(agp_context *c, const DevProgram *dprog, const DevProgram *hprog, const FeatView &xm,
                             double *A, long long lda, double *invd, double *y, const double *yvar, bool finish = true,
                             FactorTimers *timers_out = nullptr, PrepArgs *pre = nullptr, bool copy_status = true,
-                            const double *gram_copy = nullptr) {
+                            const double *gram_copy = nullptr, FactorRequest req = {}, FactorOutcome *outcome = nullptr) {
   agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
   const long long n = xm.n;
   hipStream_t s = ctx->stream;
@@ -600,7 +606,7 @@ static int build_and_factor(agp_context *c, const DevProgram *dprog, const DevPr
     PrepArgs local;
     PrepArgs *prep = pre ? pre : &local;
     prep->fill(ctx->d_flags, 0ull, (long long)(STATUS_BYTES / 8));
-    if (prep->n + 5 <= PREP_MAX) ctx->prep_external = panel_fused_plan(ctx, invd, 0, n, true, prep);
+    if (prep->n + 5 <= PREP_MAX) req.prep = panel_fused_plan(ctx, invd, 0, n, true, prep);
     launch_prep(s, *prep);
   }
   const bool prof = ctx->profiling;
@@ -627,8 +633,9 @@ static int build_and_factor(agp_context *c, const DevProgram *dprog, const DevPr
     timers.flops = ctx->gemm_flops.data();
     timers.n_ev = (int)want;
   }
-  factor_lower(ctx, A, n, lda, invd, y, prof ? &timers : nullptr);
-  ctx->prep_external = false;
+  req.timers = prof ? &timers : nullptr;
+  const FactorOutcome done = factor_lower(ctx, A, n, lda, invd, y, req);
+  if (outcome) *outcome = done;
   if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[2], s));
   // (copy_status false: the caller's next launch forwards the status block itself - backsub_coop_kernel)
   if (copy_status || finish) AGP_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_flags, ctx->d_flags, STATUS_BYTES, hipMemcpyDeviceToHost, s));
@@ -1040,6 +1047,10 @@ static int fit_create_impl(agp_context *c, const agp_kernel *k, const agp_featur
   }
   FeatView xm = fit->train.v;
   xm.meas = 1;  // as_measurements(features), gp.hpp:288
+  // what this fit asks of its factorisation: the low-precision bulk update of the mixed fit, the early inversion of the
+  // wide diagonal blocks of the deferred fp64 fit - and what the factorisation reports back
+  FactorRequest req;
+  FactorOutcome factored;
   if (mixed) {
     // the exact fp64 covariance (lower triangle: the refinement multiplies with launch_symv_lower) for the residuals, the targets,
     // and the work vectors r, z, p, q
@@ -1062,8 +1073,8 @@ static int fit_create_impl(agp_context *c, const agp_kernel *k, const agp_featur
     // default (round 6): from two fp16 planes of power-of-two-scaled rows (gemm_f16x2.hip); AGP_MIXED_F16=0: three bf16 planes
     const bool planes16 = ctx->tune.mixed_bf16;
     const bool f16 = planes16 && ctx->tune.mixed_f16;
-    ctx->update_variant = f16 ? 5 : (planes16 ? 4 : 3);
-    ctx->nbo_wide = (planes16 && ctx->tune.mixed_nbo > 512 && ctx->tune.mixed_nbo % 128 == 0) ? ctx->tune.mixed_nbo : 0;
+    req.variant = f16 ? 5 : (planes16 ? 4 : 3);
+    req.nbo_wide = (planes16 && ctx->tune.mixed_nbo > 512 && ctx->tune.mixed_nbo % 128 == 0) ? ctx->tune.mixed_nbo : 0;
     if (f16 && ctx->f16_scales_n < n) {
       if (ctx->f16_scales) (void)hipFree(ctx->f16_scales);
       ctx->f16_scales = nullptr; ctx->f16_scales_n = 0;
@@ -1073,7 +1084,7 @@ static int fit_create_impl(agp_context *c, const agp_kernel *k, const agp_featur
     }
     {  // two panel copies of (n rows + padding) x 512 (chol.hip, factor_lower): fp32, or three bf16 planes (two fp16 planes fit in the
        // same space: the fall-back from fp16 to bf16 planes needs no second allocation); kept in the context
-      const size_t want = planes16 ? 2 * bf16x3_bytes(n, ctx->nbo_wide > 512 ? ctx->nbo_wide : 512)
+      const size_t want = planes16 ? 2 * bf16x3_bytes(n, req.nbo_wide > 512 ? req.nbo_wide : 512)
                                    : sizeof(float) * 2 * ((size_t)n + 16) * 512;
       if (ctx->p32_bytes < want) {
         if (ctx->p32) (void)hipFree(ctx->p32);
@@ -1104,28 +1115,21 @@ static int fit_create_impl(agp_context *c, const agp_kernel *k, const agp_featur
   if (coop && coop_direct) pre.sentinel(fit->alpha, n);
   else if (coop) pre.fill(fit->winv, 0ull, backsub_done_words(n, 1));
   FactorTimers ftimers;
-  long long bs_done = 0;
   if (!coop && deferred && backsolve_width(n)) {
     // the inverses of the wide diagonal blocks for the backward substitution: computed by factor_lower on its idle
-    // second stream while the chain-bound tail of the factorisation runs (common.h: bs_W)
+    // second stream while the chain-bound tail of the factorisation runs (factor_plan.h: FactorRequest)
     if (ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, sizeof(double) * backsolve_ws_elems(n)) == AGP_OK) {
-      ctx->bs_W = ctx->ws_aux + round_up(n, 2);
-      ctx->bs_BW = backsolve_width(n);
-      ctx->bs_done = 0;
+      req.inv_W = ctx->ws_aux + round_up(n, 2);
+      req.inv_BW = backsolve_width(n);
     }
   }
   // (a deferred fit with the one-launch substitution: that launch's last workgroup writes the status block into the
   // pinned mirror - no copy launch behind the factorisation, none behind the substitution)
   const bool status_in_kernel = coop && deferred && ctx->h_status_dev != nullptr;
   st = build_and_factor(ctx, dprog, &k->prog, xm, fit->A, fit->lda, fit->invd, fit->z, yvar_d, !deferred, &ftimers, &pre,
-                        !status_in_kernel, mixed ? Kfull : nullptr);
-  ctx->update_variant = -1;
-  ctx->nbo_override = 0;
-  ctx->nbo_wide = 0;
-  bs_done = ctx->bs_W ? ctx->bs_done : 0;
+                        !status_in_kernel, mixed ? Kfull : nullptr, req, &factored);
+  const long long bs_done = factored.inv_done;
   ctx->sched.bs_done = bs_done;
-  ctx->bs_W = nullptr;
-  ctx->bs_done = 0;
   if (yvar_d) { (void)hipFree(yvar_d); yvar_d = nullptr; }
   if (st != AGP_OK) {
     // (the early inversion may still be writing ws_aux on the second stream: whatever uses it next is ordered behind it)
@@ -1897,7 +1901,7 @@ int factor_dense(agp_context *c, const double *K, long long n, long long ld, int
   AGP_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_scalars, 0, 4 * sizeof(double), s));
   if (diag_add) launch_add_diagonal(s, fit->A, fit->lda, n, diag_add);
   launch_nan_scan_lower(s, fit->A, fit->lda, n, ctx->d_flags);
-  factor_lower(ctx, fit->A, n, fit->lda, fit->invd, y, nullptr);
+  factor_lower(ctx, fit->A, n, fit->lda, fit->invd, y);
   AGP_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
   AGP_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_scalars, ctx->d_scalars, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
   AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));

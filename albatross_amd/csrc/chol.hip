@@ -961,11 +961,11 @@ void launch_prep(hipStream_t s, const PrepArgs &a) {
 // the z slots of those rows are sentinel-filled (and, for step launches, the second image and the row counters).
 // panel_fused_plan makes sure the buffers exist and APPENDS the fills to `prep`, which the caller launches (stream-ordered
 // before the first panel launch) together with whatever else it has to fill or copy; panel_fused_prepare is plan + launch.
-// Not planned (and the two-launch path is used) if the fused kernel is off or a buffer cannot be allocated.
-bool panel_fused_plan(agp_context *ctx, double *invd, long long k_begin, long long k_end, bool want_step, PrepArgs *prep) {
-  ctx->img_ready = nullptr;
-  ctx->headcnt_ready = false;  // (set below, only together with the fill that zeroes the counters)
-  if (!ctx->tune.panel_fused || k_end <= k_begin) return false;
+// Not planned (and the two-launch path is used) if the fused kernel is off or a buffer cannot be allocated.  What was
+// planned is the value returned (factor_plan.h: FusedPrep) - for the one factorisation that runs behind these fills.
+FusedPrep panel_fused_plan(agp_context *ctx, double *invd, long long k_begin, long long k_end, bool want_step, PrepArgs *prep) {
+  FusedPrep planned;  // (headcnt: set below, only together with the fill that zeroes the counters)
+  if (!ctx->tune.panel_fused || k_end <= k_begin) return planned;
   if (ctx->zpub_cap < k_end) {
     // grow; the old buffer may still be read by kernels in flight on this context's streams: drain them first
     (void)hipStreamSynchronize(ctx->stream);
@@ -973,7 +973,7 @@ bool panel_fused_plan(agp_context *ctx, double *invd, long long k_begin, long lo
     ctx->d_zpub = nullptr;
     ctx->zpub_cap = 0;
     const long long cap = (k_end + 4095) / 4096 * 4096;
-    if (hipMalloc(&ctx->d_zpub, sizeof(double) * (size_t)cap) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (hipMalloc(&ctx->d_zpub, sizeof(double) * (size_t)cap) != hipSuccess) { (void)hipGetLastError(); return planned; }
     ctx->zpub_cap = cap;
   }
   const long long b0 = k_begin / NB, b1 = (k_end + NB - 1) / NB;
@@ -1001,34 +1001,34 @@ bool panel_fused_plan(agp_context *ctx, double *invd, long long k_begin, long lo
   // (the counters of the merged bulk updates: factor_lower of a whole matrix large enough to have any)
   if (want_step && k_begin == 0 && ctx->d_headcnt && ctx->tune.merge_above > 0 && k_end > ctx->tune.merge_above && !prep->full()) {
     prep->fill(ctx->d_headcnt, 0ull, agp_context::HEADCNT_WORDS);
-    ctx->headcnt_ready = true;
+    planned.headcnt = true;
   }
-  ctx->zpub_ready_n = k_end;
-  ctx->img_ready = invd;
-  return true;
+  planned.img = invd;
+  planned.upto = k_end;
+  return planned;
 }
 
-void panel_fused_prepare(agp_context *ctx, hipStream_t s, double *invd, long long k_begin, long long k_end, bool want_step) {
+// plan + launch: the token of what has been launched
+FusedPrep panel_fused_prepare(agp_context *ctx, hipStream_t s, double *invd, long long k_begin, long long k_end, bool want_step) {
   PrepArgs prep;
-  if (panel_fused_plan(ctx, invd, k_begin, k_end, want_step, &prep)) launch_prep(s, prep);
+  const FusedPrep planned = panel_fused_plan(ctx, invd, k_begin, k_end, want_step, &prep);
+  if (planned.img) launch_prep(s, prep);
+  return planned;
 }
 
-// What the schedule reads, from the context (factor_plan.h: FactorSwitches) - once per factorisation, after the fills of
-// panel_fused_plan for the columns [.., upto) and the tile images `invd` have been planned.
-static FactorSwitches factor_switches(agp_context *ctx, const double *invd, long long upto, int variant) {
+// What the schedule reads (factor_plan.h: FactorSwitches) - once per factorisation: the tuning and the buffers of the
+// context, and what is particular to this call - the request, the variant it resolved to, and the fills `prep` made for the
+// columns [.., upto) of the tile images `invd`.
+static FactorSwitches factor_switches(agp_context *ctx, const FactorRequest &req, int variant, const FusedPrep &prep,
+                                      const double *invd, long long upto) {
   FactorSwitches sw;
   sw.panel_fused = ctx->tune.panel_fused; sw.step_below = ctx->tune.step_below; sw.merge_above = ctx->tune.merge_above;
-  sw.nbo_override = ctx->nbo_override;
-  sw.nbo_wide = (variant == 4 || variant == 5) ? ctx->nbo_wide : ctx->tune.fp64_nbo;  // (fp64: AGP_FP64_NBO, measurement switch)
-  sw.variant = variant;
   sw.step_slots = sw.step_below > 0 ? step_slots(ctx) : 0;
   sw.cus = ctx->cus;
   sw.have_masked_stream = ctx->stream_masked != nullptr;
-  sw.headcnt_ready = ctx->headcnt_ready;
-  sw.fused_buffers_ready = ctx->d_zpub && ctx->zpub_ready_n >= upto && ctx->img_ready == invd;
+  apply_request(sw, req, variant, prep, invd, upto, ctx->tune.fp64_nbo, ctx->ev_inv && ctx->stream2);
+  sw.fused_buffers_ready = sw.fused_buffers_ready && ctx->d_zpub;
   sw.step_buffers_ready = sw.panel_fused && sw.fused_buffers_ready && ctx->d_dpub && ctx->dpub_cap * NB >= upto && ctx->d_rowcnt;
-  sw.inv_requested = ctx->bs_W && ctx->ev_inv && ctx->stream2;
-  sw.bs_BW = ctx->bs_BW; sw.bs_done = ctx->bs_done;
   return sw;
 }
 
@@ -1140,10 +1140,9 @@ void panel_phase_public(agp_context *ctx, hipStream_t s, double *A, long long n,
   // update launches - while the second image and the counters, which are indexed by the GLOBAL block number, stay small)
   const long long step_below = ctx->tune.step_below;
   const bool step = kend == n && kend <= 65536 && step_fits(step_below, step_below > 0 ? step_slots(ctx) : 0, kend - K0);
-  panel_fused_prepare(ctx, s, img, K0, kend, step);
-  const FactorSwitches sw = factor_switches(ctx, img, kend, ctx->update_variant);
+  const FusedPrep prep = panel_fused_prepare(ctx, s, img, K0, kend, step);
+  const FactorSwitches sw = factor_switches(ctx, FactorRequest(), -1, prep, img, kend);  // (fp64, nothing else asked for)
   panel_phase(ctx, s, A, n, lda, img, y, K0, kend, nullptr, sw, step && sw.step_buffers_ready);
-  ctx->img_ready = nullptr;
 }
 
 // X (nrows x w, ld) <- X L^-T against an ALREADY FACTORED w x w diagonal block (w <= 512) given by its lower
@@ -1175,19 +1174,19 @@ void trsm_rows_wide(hipStream_t s, double *X, long long ld, long long nrows, lon
   }
 }
 
-// The wide diagonal blocks [first, first + count) of the factor (width ctx->bs_BW), inverted into ctx->bs_W on the
-// second stream for the back substitution of the fit; records ev_inv (same stream every time, so the latest record
-// covers the earlier inversions too) and reports the blocks in ctx->bs_done.  The caller has ordered the stream behind
-// whatever makes those blocks final.
-static void invert_wide_blocks(agp_context *ctx, double *A, long long lda, double *invd, long long first, long long count) {
-  const long long bw = ctx->bs_BW, img = (bw / NB) * (long long)IMG_DOUBLES;
+// The wide diagonal blocks [first, first + count) of the factor (width bw), inverted into W_all (FactorRequest::inv_W)
+// on the second stream for the back substitution of the fit; records ev_inv (same stream every time, so the latest
+// record covers the earlier inversions too).  The caller has ordered the stream behind whatever makes those blocks
+// final, and keeps count of the blocks done.
+static void invert_wide_blocks(agp_context *ctx, double *W_all, long long bw, double *A, long long lda, double *invd, long long first,
+                               long long count) {
+  const long long img = (bw / NB) * (long long)IMG_DOUBLES;
   hipStream_t si = ctx->stream2;
-  double *W = ctx->bs_W + first * bw * bw;
+  double *W = W_all + first * bw * bw;
   launch_set_identity_batched(si, W, bw, bw * bw, bw, count);
   forward_solve_mat_batched(si, A + first * bw * (lda + 1), bw * (lda + 1), bw, lda, invd + first * img, img, W, bw * bw, bw, bw,
                             /*rhs_lower=*/true, count);
   (void)hipEventRecord(ctx->ev_inv, si);
-  ctx->bs_done = first + count;
 }
 
 // Mixed precision: ONE low-precision copy of a step's panel for all the tiles of U1 and of the bulk update - fp32
@@ -1227,9 +1226,9 @@ struct PanelStager {
       unsigned short *dst = take(planes);
       launch_convert_panel_bf16x3(s, P, lda, rows, K, dst);
       out.P16 = dst;
-    } else if (variant == 5 && f16x2_depth_ok(K) && 2 * f16x2_bytes(rows, K) <= ctx->p32_bytes) {
+    } else if (variant == 5 && f16x2_depth_ok(ctx->tune.f16x2, K) && 2 * f16x2_bytes(rows, K) <= ctx->p32_bytes) {
       unsigned short *dst = take(planes);
-      launch_convert_panel_f16x2(s, P, lda, rows, K, rs16 + kend, dst);
+      launch_convert_panel_f16x2(s, ctx->tune.f16x2, P, lda, rows, K, rs16 + kend, dst);
       out.P16 = dst;
     }
     if (out.P32 || out.P16) out.kind = variant;
@@ -1250,13 +1249,15 @@ static void record_step(ScheduleRecord &rec, const OuterStep &s, unsigned invert
 //            (the MFMA-bound bulk), overlapping P(j + 1).
 // Dependencies: U1(j), U2(j) after P(j) and after U2(j - 1).
 // WHICH outer steps there are and what each does is decided by FactorPlanner (factor_plan.h); this function carries the
-// steps out - streams, events, launches - and writes down what it did (ScheduleRecord).
-void factor_lower(agp_context *ctx, double *A, long long n, long long lda, double *invd, double *y,
-                  FactorTimers *timers) {
+// steps out - streams, events, launches - and writes down what it did (ScheduleRecord).  What is particular to the call
+// comes in `req` and goes out in the value returned; nothing of it is kept in the context.
+FactorOutcome factor_lower(agp_context *ctx, double *A, long long n, long long lda, double *invd, double *y,
+                           const FactorRequest &req) {
   hipStream_t sa = ctx->stream, sb = ctx->stream2, sb_prev = sb;
   bool have_u2 = false;
+  FactorTimers *timers = req.timers;
   ctx->sched.reset_factor(n);
-  int variant = ctx->update_variant;
+  int variant = req.variant;
   // variant 5 (fp16 x 2 products, gemm_f16x2.hip): power-of-two row scales from the diagonal, BEFORE the first panel overwrites it
   const double *rs16 = nullptr, *irs16 = nullptr;
   if (variant == 5) {
@@ -1268,11 +1269,11 @@ void factor_lower(agp_context *ctx, double *A, long long n, long long lda, doubl
       variant = 4;
     }
   }
-  // (agp_fit_create has already planned and launched the fills together with its own: prep_external)
-  if (!(ctx->prep_external && ctx->img_ready == invd && ctx->zpub_ready_n >= n)) panel_fused_prepare(ctx, sa, invd, 0, n, true);
-  ctx->prep_external = false;
-  const FactorSwitches sw = factor_switches(ctx, invd, n, variant);
-  FactorPlanner plan(n, sw);
+  // (agp_fit_create has already planned and launched the fills together with its own: req.prep.  A caller that planned
+  // and got nothing leaves the planning to this call, which gets the same answer.)
+  const FusedPrep prep = req.prep.covers(invd, n) ? req.prep : panel_fused_prepare(ctx, sa, invd, 0, n, true);
+  const FactorSwitches sw = factor_switches(ctx, req, variant, prep, invd, n);
+  FactorPlanner plan(n, sw);  // (sw.bs_done == 0: no wide block is inverted yet; plan.bs_done() counts them from here)
   PanelStager stager{ctx, variant, rs16};
   // The bulk stream of a step - in the end phase the CU-masked one (OuterStep::masked): a bulk update that fills every CU (the
   // 64 x 64-tile kernel takes all 160 KB of LDS) keeps the panel kernels - 75-79 KB of LDS per workgroup - out until its
@@ -1292,7 +1293,7 @@ void factor_lower(agp_context *ctx, double *A, long long n, long long lda, doubl
       (void)hipEventRecord(ctx->ev_c, sa);  // columns < kend final
       (void)hipStreamWaitEvent(ctx->stream2, ctx->ev_c, 0);
       if (have_u2) (void)hipStreamWaitEvent(ctx->stream2, ctx->ev_b, 0);
-      invert_wide_blocks(ctx, A, lda, invd, 0, s.inv_last_step);
+      invert_wide_blocks(ctx, req.inv_W, req.inv_BW, A, lda, invd, 0, s.inv_last_step);
       inverted |= INV_BIT_LAST_STEP;
     }
     const double *P = A + s.k0 * lda + kend;  // panel rows kend.., columns K0..kend
@@ -1328,10 +1329,10 @@ void factor_lower(agp_context *ctx, double *A, long long n, long long lda, doubl
         // U1: block column [kend, next_end), all rows below its diagonal
         if (st.kind == 5) {
           // mixed precision, fp16 x 2: U1 and the bulk update from the planes of this step's panel
-          launch_update_f16x2(sa, A + kend * lda + kend, lda, st.P16, rows, 0, 0, irs16 + kend, rows, next_end - kend, K);
+          launch_update_f16x2(sa, ctx->tune.f16x2, A + kend * lda + kend, lda, st.P16, rows, 0, 0, irs16 + kend, rows, next_end - kend, K);
         } else if (st.kind == 4) {
           // mixed precision, bf16 x 3: U1 and the bulk update from the planes of this step's panel
-          launch_update_bf16x3(sa, A + kend * lda + kend, lda, st.P16, rows, 0, 0, rows, next_end - kend, K);
+          launch_update_bf16x3(sa, ctx->tune.bf16x3, A + kend * lda + kend, lda, st.P16, rows, 0, 0, rows, next_end - kend, K);
         } else if (s.mixed_tall) {
           // mixed precision: U1 on the fp32 MFMA path like the bulk update (products of fp32-rounded panels, fp64
           // subtraction) while the block column is tall enough for 128 x 128 tiles to fill the chip
@@ -1360,10 +1361,10 @@ void factor_lower(agp_context *ctx, double *A, long long n, long long lda, doubl
             long long olen = 0;
             const int *order = tiles >= 1024 ? bulk_tile_order(ntr, tiles, &olen) : nullptr;
             if (st.kind == 5)
-              launch_update_f16x2(sb, A + next_end * lda + next_end, lda, st.P16, rows, next_end - kend, next_end - kend, irs16 + kend, M2, M2, K,
+              launch_update_f16x2(sb, ctx->tune.f16x2, A + next_end * lda + next_end, lda, st.P16, rows, next_end - kend, next_end - kend, irs16 + kend, M2, M2, K,
                                   order, olen);
             else
-              launch_update_bf16x3(sb, A + next_end * lda + next_end, lda, st.P16, rows, next_end - kend, next_end - kend, M2, M2, K, order, olen);
+              launch_update_bf16x3(sb, ctx->tune.bf16x3, A + next_end * lda + next_end, lda, st.P16, rows, next_end - kend, next_end - kend, M2, M2, K, order, olen);
           } else {
             timed_gemm(sb, timers, A + next_end * lda + next_end, lda, Q, Q, n - next_end, n - next_end, K, true, variant >= 4 ? 3 : variant,
                        st.P32 ? st.P32 + (next_end - kend) : nullptr, st.ld32);
@@ -1380,15 +1381,14 @@ void factor_lower(agp_context *ctx, double *A, long long n, long long lda, doubl
     if (!throttle) panel_phase(ctx, sa, A, n, lda, invd, y, kend, next_end, timers, sw, s.step_mode, s.mark_after, mark ? ctx->ev_c : nullptr);
     if (mark) {
       const bool ran = host_wait_event(ctx->ev_c);  // (otherwise bs_done stays: the substitution inverts behind the factorisation)
-      if (ran) invert_wide_blocks(ctx, A, lda, invd, s.inv_first, s.inv_count);
+      if (ran) invert_wide_blocks(ctx, req.inv_W, req.inv_BW, A, lda, invd, s.inv_first, s.inv_count);
       if (ran) inverted |= s.inv_bit;
       plan.inversion_under_panels(s, ran);
     }
     record_step(ctx->sched, s, inverted);
   }
   // the panel stream ran last (its final panel depends on every update)
-  ctx->img_ready = nullptr;
-  ctx->headcnt_ready = false;
+  return FactorOutcome{plan.bs_done()};
 }
 
 // `count` independent n x n factorisations in lock step (blockIdx.y = problem): the blocks of a sparse GP's A, the

@@ -10,6 +10,7 @@
 
 #include "../../include/albatross_amd.h"
 #include "cov_eval.h"
+#include "factor_plan.h"  // FactorRequest, FactorOutcome, FusedPrep: the arguments of factor_lower
 
 // Wave priority of the panel-chain kernels (s_setprio); the bulk update stays at 0 (the four combinations were measured:
 // DESIGN.md section 8, profiles/r03/sweep_prio.txt)
@@ -36,6 +37,18 @@ inline void dispatch_dim(int dim, F &&f) {
   else if (dim == 4) f(std::integral_constant<int, 4>{});
   else f(std::integral_constant<int, 8>{});
 }
+
+// Which split-plane kernels of the mixed-precision factorisation run and how (gemm_f16x2.hip, gemm_bf16x3.hip): part of a
+// context's tuning, handed to their launchers by value
+struct F16x2Tuning {
+  int lds_pad = 8192;  // AGP_F16X2_LDS_PAD: extra dynamic LDS per workgroup (bytes)
+  int terms = 4;       // AGP_F16X2_TERMS: 3, or 4: with the h2 h2 product
+  int chunk = 32;      // AGP_F16X2_CHUNK: k per LDS stage and per plane chunk, 32 or 64 (fixes the layout of the planes)
+};
+struct Bf16x3Tuning {
+  int kernel = 2;      // AGP_BF16X3_KERNEL: 1: one workgroup per CU (first version), 2: two per CU
+  int lds_pad = 8192;  // AGP_BF16X3_LDS_PAD: extra dynamic LDS per workgroup (bytes)
+};
 
 struct DeviceFeatures {
   FeatView v{};
@@ -97,11 +110,6 @@ struct agp_context {
   // ... and one cached block of a fit's small buffers (agp_fit::aux_base)
   double *pool_aux = nullptr;
   size_t pool_aux_bytes = 0;
-  // bulk-update kernel of the next factorisation: -1 = default (fp64 MFMA), 3 = fp32 products, 4 = bf16 x 3 products (fp32 accuracy on the BF16 pipe), 5 = fp16 x 2 products of scaled rows
-  // (agp_fit_create_mixed sets and resets it around its factor_lower call)
-  int update_variant = -1;
-  long long nbo_override = 0;  // outer block width of the next factorisation (0 = default schedule)
-  long long nbo_wide = 0;      // mixed precision (bf16 x 3): outer block width while many rows remain (0 / 512 = default schedule)
   // scratch of the sharded fit (agp_sharded_fit_destroy parks it here, like pool_A)
   double *pool_shard = nullptr;
   size_t pool_shard_bytes = 0;
@@ -113,10 +121,10 @@ struct agp_context {
   double *pool_batch = nullptr;
   size_t pool_batch_bytes = 0;
   // fused panel kernel (chol.hip: panel_fused_kernel): the slots through which a diagonal block's z_b reaches the
-  // workgroups solving the rows below in the same launch (one per matrix row, sentinel-filled per factorisation), and
-  // which tile-image buffer has been sentinel-filled for the factorisation in progress
+  // workgroups solving the rows below in the same launch (one per matrix row, sentinel-filled per factorisation: what has
+  // been filled for which tile images is the FusedPrep that panel_fused_plan returns, not kept here)
   double *d_zpub = nullptr;
-  long long zpub_cap = 0, zpub_ready_n = 0;
+  long long zpub_cap = 0;
   // ... and the slots through which an UPDATED diagonal block reaches the workgroup that factors it (one tile image
   // per diagonal block, like invd; only allocated when the update-ahead panel kernel is in use)
   double *d_dpub = nullptr;
@@ -142,10 +150,12 @@ struct agp_context {
     bool shard_host_pacing = false;  // AGP_SHARD_HOST_PACING=1: the sharded schedule is paced by the host (round-3 scheme)
     double shard_mask_gflop = 40.;   // AGP_SHARD_MASK_GFLOP: bulk update per step below which a sharded fit is chain-bound
     long long merge_above = 8704;  // AGP_MERGE_ABOVE: trailing rows above which the next-block-column update rides in the bulk launch (0: never)
+    agp::F16x2Tuning f16x2;        // AGP_F16X2_*: the fp16 x 2 kernels of the mixed-precision fit
+    agp::Bf16x3Tuning bf16x3;      // AGP_BF16X3_*: the bf16 x 3 kernels
   } tune;
   unsigned long long *d_rowcnt = nullptr;  // one counter per 64 rows (tail of the d_dpub allocation): hand-over of the step launches' row updates
   // merged bulk updates (chol.hip: factor_lower): one counter per outer step - the tiles of the next block column count
-  // themselves, the chain stream's gate kernel waits for all of them; zeroed by panel_fused_plan (headcnt_ready)
+  // themselves, the chain stream's gate kernel waits for all of them; zeroed by panel_fused_plan (FusedPrep::headcnt)
   // pinned host memory for the small tables a batched entry point uploads (descriptors of its problems): a copy from
   // pinned memory is really asynchronous, so the call needs no synchronisation between building a table and the launch
   // that reads it (api.hip: host_stage; valid until the call's final synchronisation)
@@ -153,7 +163,6 @@ struct agp_context {
   size_t h_stage_bytes = 0;
   static constexpr long long HEADCNT_WORDS = 256;
   unsigned long long *d_headcnt = nullptr;
-  bool headcnt_ready = false;
   // What the last factorisation / fit of this context ran: host-side only, filled by factor_lower from each planned step
   // it has carried out (factor_plan.h: OuterStep), at the panel launches of panel_phase (chol.hip) and by fit_create_impl
   // (api.hip), read by the tests through agp_debug_schedule (debug_api.hip,
@@ -187,15 +196,8 @@ struct agp_context {
       else ++steps_dropped;
     }
   } sched;
-  // Early inversion of the wide diagonal blocks for the backward substitution of a fit (api.hip: backward_solve_vec_any):
-  // set by the caller of factor_lower (bs_W = where the inverses go, bs_BW = their width); factor_lower inverts the
-  // blocks that are final when it enters its single-stream tail on the (then idle) second stream, records ev_inv and
-  // reports how many it did in bs_done.  bs_W == nullptr: not requested.
-  double *bs_W = nullptr;
-  long long bs_BW = 0, bs_done = 0;
+  // recorded behind the early inversion of the wide diagonal blocks a fit asks factor_lower for (FactorRequest::inv_W)
   hipEvent_t ev_inv = nullptr;
-  const double *img_ready = nullptr;
-  bool prep_external = false;  // the caller of factor_lower has made the fills of panel_fused_plan itself (api.hip: fit_create_impl)
   // sharded fit, device-side pacing (shard_hip.hip: HipShardOps): one flag per schedule event + probe flags in device
   // memory, their sequence numbers (monotonic over the life of the context), and the pacing mode (-1: not decided yet)
   hipStream_t stream_comm = nullptr;  // queue of the collectives (created by the first sharded call)
@@ -299,10 +301,12 @@ struct FactorTimers {
   int n_ev = 0;
   int used = 0;
 };
-void factor_lower(agp_context *ctx, double *A, long long n, long long lda, double *invd, double *y,
-                  FactorTimers *timers);
+// req: everything that is particular to this call (factor_plan.h: FactorRequest; the default is the plain fp64 factorisation)
+FactorOutcome factor_lower(agp_context *ctx, double *A, long long n, long long lda, double *invd, double *y,
+                           const FactorRequest &req = {});
 struct PrepArgs;  // pub.h
-bool panel_fused_plan(agp_context *ctx, double *invd, long long k_begin, long long k_end, bool want_step, PrepArgs *prep);
+// the fills planned (FactorRequest::prep for the factor_lower they are meant for); empty: not planned
+FusedPrep panel_fused_plan(agp_context *ctx, double *invd, long long k_begin, long long k_end, bool want_step, PrepArgs *prep);
 
 // Winv[b] = inv(L_bb) for every NB x NB diagonal block (batched, one launch)
 void invert_diag_blocks(hipStream_t s, const double *A, long long n, long long lda, const double *invd,
@@ -411,19 +415,17 @@ void launch_update_f32(hipStream_t s, double *C, long long ldc, const double *P,
 // planes (hi + mid + lo = the value to fp32 accuracy), and C -= P[row_a ..] P[row_b ..]^T from them on the BF16 pipe
 size_t bf16x3_bytes(long long rows, long long K);
 void launch_convert_panel_bf16x3(hipStream_t s, const double *P, long long ldp, long long rows, long long K, unsigned short *planes);
-void set_bf16x3_kernel(int choice, int lds_pad);  // 1: one workgroup per CU (first version), 2: two per CU (AGP_BF16X3_KERNEL)
-void launch_update_bf16x3(hipStream_t s, double *C, long long ldc, const unsigned short *planes, long long panel_rows, long long row_a,
+void launch_update_bf16x3(hipStream_t s, Bf16x3Tuning tune, double *C, long long ldc, const unsigned short *planes, long long panel_rows, long long row_a,
                           long long row_b, long long M, long long N, long long K, const int *order = nullptr, long long order_len = 0);
 // The fp16 x 2 path (gemm_f16x2.hip): power-of-two row scales from the diagonal (rs, irs = 1 / rs: n doubles each), the
 // panel of one outer step as two fp16 planes of the scaled rows, and C -= P[row_a ..] P[row_b ..]^T from them (three
 // v_mfma_f32_16x16x32_f16 per block; irs belongs to the panel's row 0)
 size_t f16x2_bytes(long long rows, long long K);
 void launch_f16x2_row_scales(hipStream_t s, const double *A, long long lda, long long n, double *rs, double *irs);
-void launch_convert_panel_f16x2(hipStream_t s, const double *P, long long ldp, long long rows, long long K, const double *rs,
-                                unsigned short *planes);
-void set_f16x2_kernel(int lds_pad, int terms, int chunk);  // AGP_F16X2_LDS_PAD, AGP_F16X2_TERMS (3, or 4: with h2 h2), AGP_F16X2_CHUNK (32 / 64)
-bool f16x2_depth_ok(long long K);  // K a whole number of the kernel's K chunks
-void launch_update_f16x2(hipStream_t s, double *C, long long ldc, const unsigned short *planes, long long panel_rows, long long row_a,
+void launch_convert_panel_f16x2(hipStream_t s, F16x2Tuning tune, const double *P, long long ldp, long long rows, long long K,
+                                const double *rs, unsigned short *planes);
+bool f16x2_depth_ok(F16x2Tuning tune, long long K);  // K a whole number of the kernel's K chunks
+void launch_update_f16x2(hipStream_t s, F16x2Tuning tune, double *C, long long ldc, const unsigned short *planes, long long panel_rows, long long row_a,
                          long long row_b, const double *irs, long long M, long long N, long long K, const int *order = nullptr,
                          long long order_len = 0);
 // the XCD-aware order of the `tiles` first lower 128 x 128 tiles of a grid with ntr tile rows (gemm.hip; cached): nullptr = none

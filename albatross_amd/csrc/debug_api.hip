@@ -744,7 +744,7 @@ static int make_f16x2_planes(agp_context *ctx, const double *hP, long long ldp, 
   AGP_HIP_CHECK(ctx, hipMalloc(planes_out, f16x2_bytes(M, K)));
   AGP_HIP_CHECK(ctx, hipMemcpy(d_diag, diag.data(), sizeof(double) * (size_t)M, hipMemcpyHostToDevice));
   launch_f16x2_row_scales(ctx->stream, d_diag, 0, M, *scales_out, *scales_out + M);
-  launch_convert_panel_f16x2(ctx->stream, dP, ldp, M, K, *scales_out, *planes_out);
+  launch_convert_panel_f16x2(ctx->stream, ctx->tune.f16x2, dP, ldp, M, K, *scales_out, *planes_out);
   AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   (void)hipFree(d_diag);
   return AGP_OK;
@@ -778,7 +778,7 @@ AGP_DEBUG_API int agp_debug_trailing_update(agp_context *ctx, double *C, int64_t
     const long long tiles = (long long)ntr * (ntr + 1) / 2;
     long long olen = 0;
     const int *order = tiles >= 1024 ? bulk_tile_order(ntr, tiles, &olen) : nullptr;
-    launch_update_bf16x3(ctx->stream, dC, ldc, planes, M, 0, 0, M, M, K, order, olen);
+    launch_update_bf16x3(ctx->stream, ctx->tune.bf16x3, dC, ldc, planes, M, 0, 0, M, M, K, order, olen);
     AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     (void)hipFree(planes);
   } else if (variant == 15) {  // the fp16 x 2 kernel on the two fp16 planes of the row-scaled panel, as the mixed fit runs it (gemm_f16x2.hip)
@@ -790,7 +790,7 @@ AGP_DEBUG_API int agp_debug_trailing_update(agp_context *ctx, double *C, int64_t
     const long long tiles = (long long)ntr * (ntr + 1) / 2;
     long long olen = 0;
     const int *order = tiles >= 1024 ? bulk_tile_order(ntr, tiles, &olen) : nullptr;
-    launch_update_f16x2(ctx->stream, dC, ldc, planes, M, 0, 0, scales + M, M, M, K, order, olen);
+    launch_update_f16x2(ctx->stream, ctx->tune.f16x2, dC, ldc, planes, M, 0, 0, scales + M, M, M, K, order, olen);
     AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     (void)hipFree(planes); (void)hipFree(scales);
   } else if (variant >= 20 && variant < 30) {
@@ -928,8 +928,8 @@ AGP_DEBUG_API int agp_debug_time_trailing_update(agp_context *ctx, int64_t M, in
   for (int r = -2; r < reps && st == AGP_OK; ++r) {
     if (r == 0) AGP_HIP_CHECK(ctx, hipEventRecord(e0, ctx->stream));
     if (variant == 4) launch_trailing_update_as(3, ctx->stream, dC, ld, dP, dP, ld, M, K, nullptr, dP32, dP32, ld32);
-    else if (variant == 5) launch_update_bf16x3(ctx->stream, dC, ld, planes, M, 0, 0, M, M, K, order, olen);
-    else if (variant == 6) launch_update_f16x2(ctx->stream, dC, ld, planes, M, 0, 0, scales + M, M, M, K, order, olen);
+    else if (variant == 5) launch_update_bf16x3(ctx->stream, ctx->tune.bf16x3, dC, ld, planes, M, 0, 0, M, M, K, order, olen);
+    else if (variant == 6) launch_update_f16x2(ctx->stream, ctx->tune.f16x2, dC, ld, planes, M, 0, 0, scales + M, M, M, K, order, olen);
     else launch_trailing_update_as(variant, ctx->stream, dC, ld, dP, dP, ld, M, K);
   }
   AGP_HIP_CHECK(ctx, hipEventRecord(e1, ctx->stream));
@@ -1178,7 +1178,7 @@ AGP_DEBUG_API int agp_debug_factor(agp_context *ctx, double *A, int64_t n, int64
   }
   AGP_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_flags, 0, 4 * sizeof(int), ctx->stream));
   AGP_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_scalars, 0, 4 * sizeof(double), ctx->stream));
-  factor_lower(ctx, dA, n, lda, dI, dy, nullptr);
+  factor_lower(ctx, dA, n, lda, dI, dy);
   AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   AGP_HIP_CHECK(ctx, hipGetLastError());
   AGP_HIP_CHECK(ctx, hipMemcpy(A, dA, ab, hipMemcpyDeviceToHost));

@@ -1,8 +1,9 @@
 // factor_plan.h — the schedule of the dense factorisation as plain C++ (no HIP; g++ -std=c++17 compiles it): which outer
 // steps a factorisation of n rows takes and what each does, how the panels of an outer block are launched, how a step
 // launch is shaped.  Integer arithmetic on n, the remaining rows and FactorSwitches only.  chol.hip fills the switches
-// from the context and carries the plan out (factor_lower, panel_phase); agp_debug_factor_plan (debug_api.hip) shows the
-// same plan to tests/test_fit_schedule_host.py without a device.  Every switch point of the schedule lives HERE.
+// from the context and the call's FactorRequest and carries the plan out (factor_lower, panel_phase);
+// agp_debug_factor_plan (debug_api.hip) shows the same plan to tests/test_fit_schedule_host.py without a device.  Every
+// switch point of the schedule lives HERE.
 #pragma once
 
 namespace agp {
@@ -13,7 +14,7 @@ namespace agp {
 constexpr long long FUSED_BELOW = 4608;     // remaining rows at or below which POTRF + TRSM are one fused launch (2048 .. 4608 best)
 constexpr long long INNER_LEFT_ABOVE = 6144;  // left-looking inside an outer block while more rows than this remain
 constexpr long long NBO_512_ABOVE = 2048, NBO_256_ABOVE = 1024;  // outer block width 512 / 256 / 128 by remaining rows
-constexpr long long NBO_WIDE_ABOVE = 8192;  // ... and ctx->nbo_wide (mixed precision) above this
+constexpr long long NBO_WIDE_ABOVE = 8192;  // ... and FactorRequest::nbo_wide (mixed precision) above this
 constexpr long long THROTTLE_BELOW = 8192;  // bulk updates handed to their stream by the host once their panel is done
 constexpr long long U1_F32_ABOVE = 4096;    // mixed precision: U1 on the fp32 MFMA path while the block column is this tall
 constexpr long long SINGLE_BELOW = 1536;    // the very end on one stream (when the step launches are off)
@@ -24,21 +25,58 @@ constexpr long long PLAN_NB = 128;          // panel width
 constexpr long long STEP_FIXED_CRITICAL = 10;  // step launch: the factoring workgroup and the nine that update its block
 constexpr long long MERGED_STEPS_MAX = 256;    // counters of the merged bulk updates, one per outer step
 
-// Everything the decisions read, as plain values (chol.hip: factor_switches fills it from the context).
+// Everything the decisions read, as plain values (chol.hip: factor_switches fills it from the context's tuning and
+// buffers and from the FactorRequest of the call).
 struct FactorSwitches {
   bool panel_fused = true;                     // ctx->tune
   long long step_below = 4608, merge_above = 8704;
-  long long nbo_override = 0, nbo_wide = 0;    // nbo_wide: ctx->nbo_wide (variants 4, 5) or AGP_FP64_NBO, already resolved
-  int variant = -1;                            // bulk-update kernel (common.h: update_variant)
+  long long nbo_override = 0, nbo_wide = 0;    // nbo_wide: FactorRequest::nbo_wide (variants 4, 5) or AGP_FP64_NBO, already resolved
+  int variant = -1;                            // bulk-update kernel (FactorRequest::variant)
   long long step_slots = 0, cus = 256;         // workgroups of the step kernel the device holds at once / its CUs
   bool have_masked_stream = false;
   bool headcnt_ready = false;                  // the merged updates' counters are zeroed
   bool step_buffers_ready = false;             // second image + row counters + what the fused kernel needs, for all n rows
   bool fused_buffers_ready = false;            // z slots and tile images sentinel-filled for the columns in question
-  // inversion of the wide diagonal blocks for the fit's back substitution under the factorisation (common.h: bs_W)
-  bool inv_requested = false;                  // bs_W, ev_inv and the second stream exist
+  // inversion of the wide diagonal blocks for the fit's back substitution under the factorisation (FactorRequest::inv_W)
+  bool inv_requested = false;                  // asked for, and ev_inv and the second stream exist
   long long bs_BW = 0, bs_done = 0;            // block width / blocks already inverted on entry
 };
+
+// ---- what ONE factorisation is asked to do and what it reports: arguments of factor_lower (chol.hip), never kept --
+// The sentinel fills panel_fused_plan planned for the fused panel kernels: a value, used by the one factorisation it
+// was made for.
+struct FusedPrep {
+  const double *img = nullptr;  // tile images the fills were planned for (nullptr: nothing planned, two-launch path)
+  long long upto = 0;           // columns [.., upto) are covered
+  bool headcnt = false;         // the merged updates' counters are zeroed in the same launch
+  bool covers(const double *images, long long columns) const { return img && img == images && upto >= columns; }
+};
+struct FactorTimers;  // common.h (HIP events)
+struct FactorRequest {
+  int variant = -1;             // bulk-update kernel: -1 fp64 MFMA, 3 fp32 products, 4 bf16 x 3, 5 fp16 x 2 of scaled rows
+  long long nbo_wide = 0;       // mixed precision (4, 5): outer block width while many rows remain (0 / 512: default schedule)
+  // Early inversion of the wide diagonal blocks for the back substitution of a fit: factor_lower inverts the blocks that
+  // are final on its (then idle) second stream while the chain-bound tail runs, and records ev_inv behind them.
+  double *inv_W = nullptr;      // where the inverses go (nullptr: not requested)
+  long long inv_BW = 0;         // ... and their width
+  FusedPrep prep;               // fills the caller has already launched with its own (default: factor_lower prepares)
+  FactorTimers *timers = nullptr;
+};
+struct FactorOutcome { long long inv_done = 0; };  // wide blocks inverted under the factorisation
+
+// The request's part of the switches (the context's part: chol.hip, factor_switches).  variant: req.variant, or what
+// factor_lower fell back to; prep: the fills in force for the tile images `img` up to column `upto`; fp64_nbo:
+// AGP_FP64_NBO (measurement switch); can_invert: the event and the stream of the inversion exist.  Every factorisation
+// enters with no wide block inverted: bs_done stays 0 (only agp_debug_factor_plan sets it, like nbo_override).
+inline void apply_request(FactorSwitches &sw, const FactorRequest &req, int variant, const FusedPrep &prep, const double *img,
+                          long long upto, long long fp64_nbo, bool can_invert) {
+  sw.variant = variant;
+  sw.nbo_wide = (variant == 4 || variant == 5) ? req.nbo_wide : fp64_nbo;
+  sw.fused_buffers_ready = prep.covers(img, upto);
+  sw.headcnt_ready = sw.fused_buffers_ready && prep.headcnt;
+  sw.inv_requested = req.inv_W && can_invert;
+  sw.bs_BW = req.inv_BW;
+}
 
 // bits of an outer step and of the inversions: the values of agp_context::ScheduleRecord (chol.hip asserts it)
 constexpr unsigned STEP_BIT_MERGED = 1, STEP_BIT_STEP = 2, STEP_BIT_THROTTLED = 4, STEP_BIT_MASKED = 8, STEP_BIT_SINGLE = 16;

@@ -433,16 +433,12 @@ __global__ __launch_bounds__(256, 2) void trailing_update_bf16x3_pair_kernel(Bf1
 #undef AGP_BF_STORE
 #undef AGP_BF_STORE_P
 
-// AGP_BF16X3_KERNEL (api.hip): 1 = one workgroup per CU with prefetched C, otherwise two workgroups per CU
-static int bf16x3_kernel_choice = 2;
-// AGP_BF16X3_LDS_PAD: extra dynamic LDS per workgroup (bytes): 0 = three workgroups per CU (3 x 48 KB), >= 6 KB = two.
-// Three are the faster KERNEL (+2 %) and the slower FIT (126.8 against 123.0 ms at N = 32768, same box): the panel
-// kernels of the chain stream need LDS next to the bulk update.
-static int bf16x3_lds_pad = 8192;
-
 // C (M x N, lower tiles, C(0, 0) on the matrix diagonal) -= P[row_a ..] P[row_b ..]^T from the bf16 planes of ONE panel
 // (launch_convert_panel_bf16x3).  order / order_len: the XCD-aware tile order of gemm.hip (nullptr: column-major tiles).
-void launch_update_bf16x3(hipStream_t s, double *C, long long ldc, const unsigned short *planes, long long panel_rows, long long row_a,
+// tune.kernel: 1 = one workgroup per CU with prefetched C, otherwise two workgroups per CU.  tune.lds_pad: 0 = three
+// workgroups per CU (3 x 48 KB), >= 6 KB = two.  Three are the faster KERNEL (+2 %) and the slower FIT (126.8 against
+// 123.0 ms at N = 32768, same box): the panel kernels of the chain stream need LDS next to the bulk update.
+void launch_update_bf16x3(hipStream_t s, Bf16x3Tuning tune, double *C, long long ldc, const unsigned short *planes, long long panel_rows, long long row_a,
                           long long row_b, long long M, long long N, long long K, const int *order, long long order_len) {
   if (M <= 0 || N <= 0 || K <= 0 || K % BK) return;
   Bf16Args g;
@@ -459,10 +455,8 @@ void launch_update_bf16x3(hipStream_t s, double *C, long long ldc, const unsigne
   for (int bj = 0; bj < g.ntc; ++bj) tiles += g.ntr - bj;
   const long long wgs = order ? order_len : tiles;
   if (wgs <= 0) return;
-  if (bf16x3_kernel_choice == 1) hipLaunchKernelGGL(trailing_update_bf16x3_kernel, dim3((unsigned)wgs), dim3(256), 0, s, g);
-  else hipLaunchKernelGGL(trailing_update_bf16x3_pair_kernel, dim3((unsigned)wgs), dim3(256), (size_t)bf16x3_lds_pad, s, g);
+  if (tune.kernel == 1) hipLaunchKernelGGL(trailing_update_bf16x3_kernel, dim3((unsigned)wgs), dim3(256), 0, s, g);
+  else hipLaunchKernelGGL(trailing_update_bf16x3_pair_kernel, dim3((unsigned)wgs), dim3(256), (size_t)tune.lds_pad, s, g);
 }
-
-void set_bf16x3_kernel(int choice, int lds_pad) { bf16x3_kernel_choice = choice; bf16x3_lds_pad = lds_pad; }
 
 }  // namespace agp

@@ -46,7 +46,6 @@ template <int CH>
 __device__ __forceinline__ int sw_piece(int kg, int row) {
   return CH == 32 ? (kg ^ ((4 - ((row >> 2) & 3)) & 3)) : (kg ^ ((row >> 1) & 7));
 }
-int f16x2_chunk = 32;                 // k per LDS stage and per plane chunk (AGP_F16X2_CHUNK: 32 or 64)
 }  // namespace
 
 __global__ __launch_bounds__(256) void f16x2_row_scales_kernel(const double *__restrict__ A, long long lda, long long n, double *__restrict__ rs,
@@ -99,15 +98,16 @@ __global__ __launch_bounds__(256) void convert_panel_f16x2_kernel(const double *
 
 long long f16x2_rows_pad(long long rows) { return (rows + GT - 1) / GT * GT + GT; }  // (+ one tile of zero rows: a tile may start anywhere below `rows`)
 size_t f16x2_bytes(long long rows, long long K) { return sizeof(unsigned short) * 2 * (size_t)f16x2_rows_pad(rows) * (size_t)((K + 63) / 64 * 64); }
-bool f16x2_depth_ok(long long K) { return K > 0 && K % f16x2_chunk == 0; }
+bool f16x2_depth_ok(F16x2Tuning tune, long long K) { return K > 0 && K % tune.chunk == 0; }
 
-// rs: the scales of the panel's rows (rs[0] = the scale of panel row 0)
-void launch_convert_panel_f16x2(hipStream_t s, const double *P, long long ldp, long long rows, long long K, const double *rs,
-                                unsigned short *planes) {
-  if (rows <= 0 || !f16x2_depth_ok(K)) return;
+// rs: the scales of the panel's rows (rs[0] = the scale of panel row 0).  tune.chunk fixes the layout of the planes: the
+// update that reads them gets the same settings (those of the context).
+void launch_convert_panel_f16x2(hipStream_t s, F16x2Tuning tune, const double *P, long long ldp, long long rows, long long K,
+                                const double *rs, unsigned short *planes) {
+  if (rows <= 0 || !f16x2_depth_ok(tune, K)) return;
   const long long rows_pad = f16x2_rows_pad(rows);
-  const dim3 grid((unsigned)((rows_pad + 255) / 256), (unsigned)(K / f16x2_chunk));
-  if (f16x2_chunk == 64) hipLaunchKernelGGL(convert_panel_f16x2_kernel<64>, grid, dim3(256), 0, s, P, ldp, rows, rows_pad, rs, planes, rows_pad * K);
+  const dim3 grid((unsigned)((rows_pad + 255) / 256), (unsigned)(K / tune.chunk));
+  if (tune.chunk == 64) hipLaunchKernelGGL(convert_panel_f16x2_kernel<64>, grid, dim3(256), 0, s, P, ldp, rows, rows_pad, rs, planes, rows_pad * K);
   else hipLaunchKernelGGL(convert_panel_f16x2_kernel<32>, grid, dim3(256), 0, s, P, ldp, rows, rows_pad, rs, planes, rows_pad * K);
 }
 
@@ -296,22 +296,13 @@ __global__ __launch_bounds__(256, 2) void trailing_update_f16x2_kernel(F16Args g
     }
 }
 
-// AGP_F16X2_LDS_PAD: extra dynamic LDS per workgroup (bytes), which sets how many workgroups share a CU next to the panel
-// kernels of the chain stream (32 KB static; registers allow two)
-static int f16x2_lds_pad = 8192;
-static int f16x2_terms = 4;
-void set_f16x2_kernel(int lds_pad, int terms, int chunk) {
-  f16x2_lds_pad = lds_pad;
-  f16x2_terms = terms == 3 ? 3 : 4;
-  f16x2_chunk = chunk == 64 ? 64 : 32;
-}
-
 // C (M x N, lower tiles, C(0, 0) on the matrix diagonal) -= P[row_a ..] P[row_b ..]^T from the fp16 planes of ONE panel
 // (launch_convert_panel_f16x2).  irs: 1 / r of the PANEL's rows (irs[0] belongs to panel row 0).  order / order_len: the
-// XCD-aware tile order of gemm.hip (nullptr: column-major tiles).
-void launch_update_f16x2(hipStream_t s, double *C, long long ldc, const unsigned short *planes, long long panel_rows, long long row_a,
+// XCD-aware tile order of gemm.hip (nullptr: column-major tiles).  tune.lds_pad sets how many workgroups share a CU next to
+// the panel kernels of the chain stream (32 KB static; registers allow two).
+void launch_update_f16x2(hipStream_t s, F16x2Tuning tune, double *C, long long ldc, const unsigned short *planes, long long panel_rows, long long row_a,
                          long long row_b, const double *irs, long long M, long long N, long long K, const int *order, long long order_len) {
-  if (M <= 0 || N <= 0 || !f16x2_depth_ok(K)) return;
+  if (M <= 0 || N <= 0 || !f16x2_depth_ok(tune, K)) return;
   F16Args g;
   g.C = C; g.ldc = ldc; g.planes = planes;
   g.rows_pad = f16x2_rows_pad(panel_rows);
@@ -328,12 +319,12 @@ void launch_update_f16x2(hipStream_t s, double *C, long long ldc, const unsigned
   const long long wgs = order ? order_len : tiles;
   if (wgs <= 0) return;
   const dim3 grid((unsigned)wgs), block(256);
-  const size_t pad = (size_t)f16x2_lds_pad;
-  if (f16x2_chunk == 64) {
-    if (f16x2_terms == 4) hipLaunchKernelGGL((trailing_update_f16x2_kernel<4, 64>), grid, block, pad, s, g);
+  const size_t pad = (size_t)tune.lds_pad;
+  if (tune.chunk == 64) {
+    if (tune.terms == 4) hipLaunchKernelGGL((trailing_update_f16x2_kernel<4, 64>), grid, block, pad, s, g);
     else hipLaunchKernelGGL((trailing_update_f16x2_kernel<3, 64>), grid, block, pad, s, g);
   } else {
-    if (f16x2_terms == 4) hipLaunchKernelGGL((trailing_update_f16x2_kernel<4, 32>), grid, block, pad, s, g);
+    if (tune.terms == 4) hipLaunchKernelGGL((trailing_update_f16x2_kernel<4, 32>), grid, block, pad, s, g);
     else hipLaunchKernelGGL((trailing_update_f16x2_kernel<3, 32>), grid, block, pad, s, g);
   }
 }

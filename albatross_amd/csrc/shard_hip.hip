@@ -918,7 +918,9 @@ int agp_sharded_fit_create(agp_context *c, agp_comm *comm, const agp_kernel *k, 
       timers.flops = ctx->gemm_flops.data();
       timers.n_ev = (int)want;
     }
-    factor_lower(ctx, f->A, n, f->ld, f->buf.img_local, f->y, ctx->profiling ? &timers : nullptr);
+    FactorRequest req;  // (the default request: fp64, nothing else asked for - and the stage timers)
+    req.timers = ctx->profiling ? &timers : nullptr;
+    factor_lower(ctx, f->A, n, f->ld, f->buf.img_local, f->y, req);
     SFIT_CHECK(hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
     SFIT_CHECK(hipMemcpyAsync(ctx->h_scalars, ctx->d_scalars, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
     SFIT_CHECK(hipStreamSynchronize(s));

@@ -231,7 +231,7 @@ int agp_fit_update(agp_context *c, const agp_kernel *k, const agp_fit *old, cons
   if (st != AGP_OK) { (void)hipFree(ynew_d); agp_fit_destroy(fit); return st; }
   launch_matvec(s, X, lda, m, n_pad, fit->z, ctx->ws_aux, -1.0, 1.0, ynew_d, fit->z + n_pad);
   // ---- LL^T of S in place (the sub-matrix is addressed as a matrix of its own: its 128-blocks start at n_pad) ----
-  factor_lower(ctx, S, m, lda, fit->invd + (n_pad / NB) * (long long)(36 * MB * MB), fit->z + n_pad, nullptr);
+  factor_lower(ctx, S, m, lda, fit->invd + (n_pad / NB) * (long long)(36 * MB * MB), fit->z + n_pad);
   UPD_CHECK(hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
   UPD_CHECK(hipMemcpyAsync(ctx->h_scalars, ctx->d_scalars, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
   UPD_CHECK(hipStreamSynchronize(s));

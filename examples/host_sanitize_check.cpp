@@ -11,7 +11,7 @@
 //     malloc'd base: every region aligned, inside the allocation and disjoint from the others, the sizing pass equal to
 //     the real one, the size within the alignment padding of the plain sums, first and last word of every region written;
 //  4. the schedule of the dense factorisation (albatross_amd/csrc/factor_plan.h: plain C++): every n up to 20480 planned
-//     under two switch sets, every step's panels planned, and a sweep of the step-launch shapes.
+//     under four switch sets (two of them resolved from the FactorRequest of a call), every step's panels planned, and a sweep of the step-launch shapes.
 //
 // Prints "host_sanitize_check ok" and exits 0; any sanitizer report aborts with a non-zero status.
 #include <cmath>
@@ -350,7 +350,25 @@ void factor_plan_under_sanitizers() {
   on.inv_requested = true; on.bs_BW = 512;
   agp::FactorSwitches off;  // the two-launch schedule of a context that was demoted, nothing requested
   off.panel_fused = false; off.step_below = off.merge_above = 0;
-  for (const agp::FactorSwitches &sw : {on, off})
+  // the same two through the request of a call (factor_plan.h: apply_request): a deferred fp64 fit that asks for the early
+  // inversion behind fills its caller planned, and a mixed fit (fp16 x 2, wide outer blocks) that found nothing planned
+  double images[1], inverses[1];
+  agp::FactorRequest fp64_fit, mixed_fit;
+  fp64_fit.inv_W = inverses; fp64_fit.inv_BW = 512;
+  fp64_fit.prep.img = images; fp64_fit.prep.upto = 20480; fp64_fit.prep.headcnt = true;
+  mixed_fit.variant = 5; mixed_fit.nbo_wide = 1024;
+  agp::FactorSwitches inv = on, mixed = on;
+  inv.inv_requested = inv.headcnt_ready = inv.fused_buffers_ready = false; inv.bs_BW = 0;
+  agp::apply_request(inv, fp64_fit, fp64_fit.variant, fp64_fit.prep, images, 20480, 0, true);
+  require(inv.inv_requested && inv.bs_BW == 512 && inv.bs_done == 0 && inv.headcnt_ready && inv.fused_buffers_ready && inv.variant == -1 &&
+              inv.nbo_wide == 0, "request of a deferred fp64 fit");
+  require(!fp64_fit.prep.covers(images, 20481) && !fp64_fit.prep.covers(inverses, 512) && !agp::FusedPrep().covers(nullptr, 0),
+          "fills planned for other images or fewer columns do not count");
+  agp::apply_request(mixed, mixed_fit, mixed_fit.variant, mixed_fit.prep, images, 20480, 768, true);
+  require(!mixed.inv_requested && !mixed.headcnt_ready && !mixed.fused_buffers_ready && mixed.variant == 5 && mixed.nbo_wide == 1024,
+          "request of a mixed fit");
+  mixed.fused_buffers_ready = true;  // (as if factor_lower had prepared the fills itself)
+  for (const agp::FactorSwitches &sw : {on, off, inv, mixed})
     for (long long n = 1; n <= 20480; ++n) {
       agp::FactorPlanner plan(n, sw);
       agp::OuterStep s;

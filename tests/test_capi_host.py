@@ -115,7 +115,7 @@ def test_host_cxx_under_address_and_ub_sanitizers():
     """examples/Makefile `asan`: the sharded-fit schedule (albatross_amd/csrc/shard_sched.hip, plain C++, compiled into
     the test binary with -fsanitize=address,undefined) driven with naive block operations on one rank and through the
     forced multi-rank path, plus the header-only host layer, the workspace layouts and the dense factorisation's schedule
-    (csrc/factor_plan.h: every n up to 20480 planned under two switch sets, a sweep of step-launch shapes); no GPU involved."""
+    (csrc/factor_plan.h: every n up to 20480 planned under four switch sets, a sweep of step-launch shapes); no GPU involved."""
     import shutil
     import subprocess
     if shutil.which("g++") is None:

@@ -327,3 +327,51 @@ def test_fit_schedule_edges(make_ctx, monkeypatch, run):
     assert fratio <= 1.0, fratio
     dg = np.log(np.diag(L))
     assert abs(fit.log_determinant - 2 * dg.sum()) <= 4 * n * U * np.abs(dg).sum()
+
+
+# (n of the fp64 fit, n of the mixed fits, back substitution and (bs_done, inversion bits) of the fp64 fit)
+# 2304 is not a multiple of 512: its substitution runs the 128-row chain and no wide block is inverted anywhere.  5120 is
+# the FIT_CASES size whose fit asks for the early inversion AND has a bulk update (the hand-over to its step tail), which a
+# low-precision variant left behind by a mixed fit would run on the fp32 products; 4736 is the smallest mixed fit with a
+# split-plane update on every device (4608: all step launches where the device holds them).
+SEQUENCE_CASES = [(2304, 4608, BS_CHAIN, (0, 0)),
+                  (5120, 4736) + next((c[2], c[3]) for c in FIT_CASES if c[0] == 5120 and not c[1])]
+
+
+@pytest.mark.parametrize("n,n_mixed,backsub,inverted", SEQUENCE_CASES, ids=["2304-4608", "5120-4736"])
+def test_nothing_of_a_factorisation_survives_into_the_next(make_ctx, n, n_mixed, backsub, inverted):
+    """Four fits in sequence on ONE context: (a) an fp64 fit, (b) a mixed fit, (c) a mixed fit that fails with
+    AGP_ERR_NOT_POSITIVE_DEFINITE (the construction of test_mixed_fit_reports_failures), (d) the fit of (a) again.  What a
+    fit asks of its factorisation - the low-precision bulk update, the wide outer blocks, the early inversion of the wide
+    diagonal blocks - is an argument of that call (factor_plan.h: FactorRequest), so (d) returns the factor, information
+    vector and log-determinant of (a) bit for bit and leaves the same schedule record."""
+    ctx = make_ctx()
+    cov = COVS["se"]()
+    x, y = synthetic_3d(n, 300 + n)
+
+    def fp64_fit():
+        fit = ab.gp_from_covariance(cov, context=ctx).fit(ab.RegressionDataset(x, y)).get_fit()
+        rec = schedule(ctx)
+        return np.tril(fit.factor()), np.array(fit.information), fit.log_determinant, rec
+
+    La, aa, lda, rec_a = fp64_fit()
+    require_step_fits(rec_a, min(n, rec_a["step_below"]))
+    check_schedule(rec_a, n)
+    assert rec_a["backsub"] == backsub and (rec_a["bs_done"], rec_a["inv"]) == inverted, rec_a
+
+    xm, ym = synthetic_3d(n_mixed, 300 + n_mixed)
+    mixed = ab.gp_from_covariance(cov, context=ctx)
+    mixed.precision = "mixed"
+    mixed.fit(ab.RegressionDataset(xm, ym))
+    xm[17] = xm[3]  # duplicate point and no noise: singular
+    failing = ab.gp_from_covariance(ab.SquaredExponential(1.0, 1.0), context=ctx)
+    failing.precision = "mixed"
+    failing.pivoted_fallback = False
+    with pytest.raises(ab.NotPositiveDefiniteError):
+        failing.fit(ab.RegressionDataset(xm, ym))
+
+    Ld, ad, ldd, rec_d = fp64_fit()
+    assert np.array_equal(La, Ld)
+    assert np.array_equal(aa, ad)
+    assert lda == ldd
+    assert rec_d == rec_a, (rec_a, rec_d)

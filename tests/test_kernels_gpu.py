@@ -152,6 +152,46 @@ def test_trailing_update_split_planes_badly_scaled_rows(ctx, dbg, variant):
     assert np.array_equal(got[M:], Cm[M:])
 
 
+@pytest.mark.parametrize("variant,M,K,switch,value_a,value_b,b_differs", [
+    (15, 256, 64, "AGP_F16X2_TERMS", "4", "3", True),
+    (15, 130, 64, "AGP_F16X2_CHUNK", "32", "64", False),
+    (14, 256, 64, "AGP_BF16X3_KERNEL", "2", "1", False),
+])
+def test_split_plane_settings_belong_to_the_context(make_ctx, dbg, monkeypatch, variant, M, K, switch, value_a, value_b, b_differs):
+    """The settings of the split-plane kernels (AGP_F16X2_*, AGP_BF16X3_*) are part of the context they were read for:
+    context A keeps its own when context B is created under others afterwards, and the debug entry follows the context
+    it is handed.  A, then B, then A again on the same data: A's two results are equal bit for bit, and both contexts
+    meet the 2e-7 bar of test_trailing_update_large_tiles.  K = 64 is two K chunks of 32 and one of 64; M = 256 one round
+    of whole tiles, M = 130 a ragged one.  Three instead of four products (AGP_F16X2_TERMS=3) drop h2 h2, ~2^-22 of a
+    term and above the fp32 ulp of the accumulated sum: B must differ from A somewhere in the lower triangle, or the
+    switch never reached the kernel and the test would show nothing."""
+    rng = np.random.default_rng(variant + M + K)
+    ldc, ldp = M + 8, M + 10
+    Cm = np.asfortranarray(rng.standard_normal((ldc, M)))
+    P = np.asfortranarray(rng.standard_normal((ldp, K)))
+    want = Cm[:M] - P[:M] @ P[:M].T
+    low = np.tril_indices(M)
+    scale = np.abs(P[:M]).sum(axis=1).max() ** 2
+
+    def update(c):
+        got = Cm.copy(order="F")
+        assert dbg.agp_debug_trailing_update(c._h, _p(got), ldc, _p(P), ldp, M, K, variant) == 0
+        assert np.abs(got[:M][low] - want[low]).max() <= 2e-7 * scale
+        assert np.array_equal(got[M:], Cm[M:])  # padding rows untouched
+        return got[:M][low]
+
+    monkeypatch.setenv(switch, value_a)
+    a = make_ctx()
+    r0 = update(a)
+    monkeypatch.setenv(switch, value_b)
+    b = make_ctx()
+    rb = update(b)
+    r1 = update(a)
+    assert np.array_equal(r1, r0)
+    if b_differs:
+        assert not np.array_equal(rb, r0)
+
+
 @pytest.mark.parametrize("head_cols", [1, 4, 8])
 @pytest.mark.parametrize("M,K", [(9216, 512), (6016, 512), (5900, 128), (1418, 512), (700, 96), (384, 512)])
 def test_trailing_update_merged(ctx, dbg, M, K, head_cols):

@@ -78,6 +78,54 @@ def test_mixed_fit_matches_oracle(ctx, n):
     assert abs(fm.get_fit().log_determinant - ofit.log_determinant) <= 4e-6 * n  # (measured 1.9e-6 n at n = 5300 on the Matern kernel: at the 2e-6 n bar of the fp64 path)
 
 
+@pytest.mark.parametrize("n", [4608, 4736])
+def test_mixed_fit_keeps_the_settings_of_its_context(make_ctx, monkeypatch, n):
+    """The settings of the split-plane kernels travel with the context (agp_context::Tuning): a mixed fit on context A
+    gives the same factor and log-determinant, bit for bit, before and after a context B has been created under
+    AGP_F16X2_TERMS=3.  Both runs meet the bounds of test_mixed_fit_matches_oracle.  n = 4608: 4096 rows remain after
+    512 columns (factor_plan.h: U1_F32_ABOVE) - but where the device holds the step launches of 4608 rows, every panel
+    of that fit is one (AGP_STEP_BELOW) and no split-plane kernel runs; n = 4736 = 4608 + 128 is the smallest size
+    whose first 512 columns are followed by a split-plane update (4224 rows) on every device.  The reference at 4608
+    is the oracle; at 4736 (the oracle takes half a minute per size) the all-fp64 fit of the same context, as in
+    test_mixed_fit_large_property, held to the same bounds."""
+    for name in ("AGP_F16X2_TERMS", "AGP_F16X2_CHUNK", "AGP_F16X2_LDS_PAD"):
+        monkeypatch.delenv(name, raising=False)
+    a = make_ctx()
+    x, y = synthetic_3d(n, 5 + n)
+    xs, _ = synthetic_3d(200, 77)
+    cov = ab.Matern52(2.0, 1.0) + ab.IndependentNoise(0.1)
+    if n == 4608:
+        ofit = orc.OracleFit(cov, ab.FeatureSet(x), y)
+        om, ov = ofit.predict_marginal(ab.FeatureSet(xs))
+        want_information, want_log_determinant = ofit.information, ofit.log_determinant
+    else:
+        f64 = ab.gp_from_covariance(cov, context=a).fit(ab.RegressionDataset(x, y))
+        ref = f64.predict(xs).marginal()
+        om, ov = ref.mean, ref.covariance
+        want_information, want_log_determinant = f64.get_fit().information, f64.get_fit().log_determinant
+
+    def mixed_fit_on_a():
+        model = ab.gp_from_covariance(cov, context=a)
+        model.precision = "mixed"
+        fm = model.fit(ab.RegressionDataset(x, y))
+        its, res = model.refinement_
+        assert res <= 1e-12 and (its >= 1 or n <= 4608), (its, res)
+        assert rel(fm.get_fit().information, want_information) <= 1e-8
+        pred = fm.predict(xs).marginal()
+        assert rel(pred.mean, om) <= 1e-8
+        assert np.abs(pred.covariance - ov).max() <= 1e-4 * np.abs(ov).max()
+        fm.get_fit().accept_mixed_log_determinant = True
+        assert abs(fm.get_fit().log_determinant - want_log_determinant) <= 4e-6 * n
+        return np.tril(fm.get_fit().factor()), fm.get_fit().log_determinant
+
+    L0, ld0 = mixed_fit_on_a()
+    monkeypatch.setenv("AGP_F16X2_TERMS", "3")
+    make_ctx()
+    L1, ld1 = mixed_fit_on_a()
+    assert np.array_equal(L0, L1)
+    assert ld0 == ld1
+
+
 def test_mixed_fit_config4_kernel(ctx):
     """The temperature-example covariance on synthetic stations: mixed vs all-fp64 vs oracle (small N)."""
     n = 1500
