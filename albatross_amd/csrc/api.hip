@@ -25,14 +25,6 @@
 
 namespace agp {
 
-void DeviceFeatures::release() {
-  for (void *&p : owned) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-  }
-  v = FeatView{};
-}
-
 long long round_up(long long x, long long m) { return (x + m - 1) / m * m; }
 
 // leading dimension of the factor: even (16-B aligned columns) and not a
@@ -67,7 +59,9 @@ DevCache &dev_cache() {
 }
 }  // namespace
 
-hipError_t dev_malloc_bytes(void **p, size_t bytes) {
+int dev_malloc_plain_bytes(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+
+int dev_malloc_bytes(void **p, size_t bytes) {
   int dev = 0;
   (void)hipGetDevice(&dev);
   DevCache &c = dev_cache();
@@ -98,7 +92,7 @@ hipError_t dev_malloc_bytes(void **p, size_t bytes) {
   return e;
 }
 
-hipError_t dev_free(void *p) {
+int dev_free(void *p) {
   if (!p) return hipSuccess;
   DevCache &c = dev_cache();
   std::pair<int, size_t> info{-1, 0};
@@ -127,7 +121,7 @@ hipError_t dev_free(void *p) {
 // hipFree of a block that MAY have come from dev_malloc (a factor parked in a context pool, a buffer handed from one
 // owner to another): the `live` entry goes with it - a stale entry would later match an unrelated hipMalloc that
 // happens to return the same address, and dev_free would park that block under the old (larger) size.
-hipError_t dev_release(void *p) {
+int dev_release(void *p) {
   if (!p) return hipSuccess;
   DevCache &c = dev_cache();
   {
@@ -223,17 +217,8 @@ static agp_context::Tuning read_tuning() {
   return t;
 }
 
-int agp_context_create(int device_id, agp_context **out) {
-  if (!out) return AGP_ERR_INVALID_ARGUMENT;
-  *out = nullptr;
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return AGP_ERR_NO_DEVICE;
-  if (device_id < 0 || device_id >= n) return AGP_ERR_INVALID_ARGUMENT;
-  agp_context_impl *ctx = new (std::nothrow) agp_context_impl();
-  if (!ctx) return AGP_ERR_INVALID_ARGUMENT;
-  ctx->device = device_id;
-  ctx->tune = read_tuning();
-  agp::g_gram_sop = ctx->tune.gram_sop;
+// everything of agp_context_create that can fail: the caller destroys the context then
+static int context_init(agp_context_impl *ctx, int device_id) {
   AGP_HIP_CHECK(ctx, hipSetDevice(device_id));
   {
     // main / panel stream at the highest priority: its short kernels must not
@@ -267,14 +252,33 @@ int agp_context_create(int device_id, agp_context **out) {
   AGP_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->ev_a, hipEventDisableTiming));
   AGP_HIP_CHECK(ctx, hipEventCreateWithFlags(&ctx->ev_b, hipEventDisableTiming));
   // flags and scalars of a factorisation: ONE block on either side ([4 ints | 4 doubles]) so that one 48-byte copy brings both back
-  AGP_HIP_CHECK(ctx, hipMalloc(&ctx->d_headcnt, sizeof(unsigned long long) * agp_context::HEADCNT_WORDS));
-  AGP_HIP_CHECK(ctx, hipMalloc(&ctx->d_flags, 4 * sizeof(int) + 4 * sizeof(double)));
+  AGP_HIP_CHECK(ctx, ctx->d_headcnt.alloc_plain(sizeof(unsigned long long) * agp_context::HEADCNT_WORDS));
+  AGP_HIP_CHECK(ctx, ctx->d_flags.alloc_plain(4 * sizeof(int) + 4 * sizeof(double)));
   ctx->d_scalars = reinterpret_cast<double *>(ctx->d_flags + 4);
   AGP_HIP_CHECK(ctx, hipHostMalloc(&ctx->h_flags, 4 * sizeof(int) + 4 * sizeof(double)));
   ctx->h_scalars = reinterpret_cast<double *>(ctx->h_flags + 4);
   if (hipHostGetDevicePointer(&ctx->h_status_dev, ctx->h_flags, 0) != hipSuccess) { (void)hipGetLastError(); ctx->h_status_dev = nullptr; }
   for (auto &e : ctx->stage_ev) AGP_HIP_CHECK(ctx, hipEventCreate(&e));
-  for (auto &sl : ctx->ext.slots) AGP_HIP_CHECK(ctx, hipMalloc(&sl.dev, sizeof(DevProgram)));
+  for (auto &sl : ctx->ext.slots) AGP_HIP_CHECK(ctx, sl.dev.alloc_plain(sizeof(DevProgram)));
+  return AGP_OK;
+}
+
+int agp_context_create(int device_id, agp_context **out) {
+  if (!out) return AGP_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return AGP_ERR_NO_DEVICE;
+  if (device_id < 0 || device_id >= n) return AGP_ERR_INVALID_ARGUMENT;
+  agp_context_impl *ctx = new (std::nothrow) agp_context_impl();
+  if (!ctx) return AGP_ERR_INVALID_ARGUMENT;
+  ctx->device = device_id;
+  ctx->tune = read_tuning();
+  agp::g_gram_sop = ctx->tune.gram_sop;
+  const int st = context_init(ctx, device_id);
+  if (st != AGP_OK) {
+    agp_context_destroy(ctx);
+    return st;
+  }
   *out = ctx;
   return AGP_OK;
 }
@@ -286,30 +290,10 @@ void agp_context_destroy(agp_context *c) {
   (void)hipDeviceSynchronize();
   for (agp_context *h : ctx->helpers) agp_context_destroy(h);
   ctx->helpers.clear();
-  for (auto &sl : ctx->ext.slots)
-    if (sl.dev) (void)hipFree(sl.dev);
   for (auto e : ctx->gemm_events) (void)hipEventDestroy(e);
   for (auto e : ctx->stage_ev)
     if (e) (void)hipEventDestroy(e);
-  if (ctx->partial_ws) (void)hipFree(ctx->partial_ws);
-  if (ctx->ws_A) (void)agp::dev_release(ctx->ws_A);
-  if (ctx->pool_A) (void)agp::dev_release(ctx->pool_A);
-  if (ctx->pool_K) (void)agp::dev_release(ctx->pool_K);
-  if (ctx->ws_refine) (void)hipFree(ctx->ws_refine);
-  if (ctx->p32) (void)hipFree(ctx->p32);
-  if (ctx->f16_scales) (void)hipFree(ctx->f16_scales);
-  if (ctx->pool_L32) (void)hipFree(ctx->pool_L32);
-  if (ctx->pool_aux) (void)agp::dev_release(ctx->pool_aux);
-  if (ctx->pool_shard) (void)agp::dev_release(ctx->pool_shard);
-  if (ctx->pool_sparse) (void)agp::dev_release(ctx->pool_sparse);
-  if (ctx->pool_batch) (void)agp::dev_release(ctx->pool_batch);
-  if (ctx->ws_aux) (void)hipFree(ctx->ws_aux);
-  if (ctx->d_zpub) (void)hipFree(ctx->d_zpub);
-  if (ctx->d_dpub) (void)hipFree(ctx->d_dpub);
-  if (ctx->shard_flags) (void)hipFree(ctx->shard_flags);
-  if (ctx->d_headcnt) (void)hipFree(ctx->d_headcnt);
   if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
-  if (ctx->d_flags) (void)hipFree(ctx->d_flags);  // (d_scalars / h_scalars are the tails of these blocks)
   if (ctx->h_flags) (void)hipHostFree(ctx->h_flags);
   if (ctx->ev_a) (void)hipEventDestroy(ctx->ev_a);
   if (ctx->ev_b) (void)hipEventDestroy(ctx->ev_b);
@@ -320,7 +304,7 @@ void agp_context_destroy(agp_context *c) {
   if (ctx->stream_masked) (void)hipStreamDestroy(ctx->stream_masked);
   if (ctx->stream_comm) (void)hipStreamDestroy(ctx->stream_comm);
   if (ctx->ev_c) (void)hipEventDestroy(ctx->ev_c);
-  delete ctx;
+  delete ctx;  // (its device memory goes with its members: dev_mem.h)
   agp::dev_cache_trim();  // (the parked blocks of dev_free: a process that closes its contexts gives its device memory back)
 }
 
@@ -478,20 +462,20 @@ int to_device(agp_context *ctx, const agp_features *f, bool copy, DeviceFeatures
   if (f->n > 0) {
     if (on_host || copy) {
       const size_t cb = sizeof(double) * (size_t)f->n * (size_t)f->dim;
-      AGP_HIP_CHECK(ctx, hipMalloc(&out->owned[0], cb));
+      AGP_HIP_CHECK(ctx, out->owned[0].alloc_plain(cb));
       AGP_HIP_CHECK(ctx, hipMemcpyAsync(out->owned[0], f->coords, cb, kind, ctx->stream));
-      v.coords = static_cast<const double *>(out->owned[0]);
+      v.coords = static_cast<const double *>(out->owned[0].get());
       if (f->eq_id) {
         const size_t ib = sizeof(long long) * (size_t)f->n;
-        AGP_HIP_CHECK(ctx, hipMalloc(&out->owned[1], ib));
+        AGP_HIP_CHECK(ctx, out->owned[1].alloc_plain(ib));
         AGP_HIP_CHECK(ctx, hipMemcpyAsync(out->owned[1], f->eq_id, ib, kind, ctx->stream));
-        v.ids = static_cast<const long long *>(out->owned[1]);
+        v.ids = static_cast<const long long *>(out->owned[1].get());
       }
       if (f->n_scale_columns > 0) {
         const size_t sb = sizeof(double) * (size_t)f->n * (size_t)f->n_scale_columns;
-        AGP_HIP_CHECK(ctx, hipMalloc(&out->owned[2], sb));
+        AGP_HIP_CHECK(ctx, out->owned[2].alloc_plain(sb));
         AGP_HIP_CHECK(ctx, hipMemcpyAsync(out->owned[2], f->scales, sb, kind, ctx->stream));
-        v.scales = static_cast<const double *>(out->owned[2]);
+        v.scales = static_cast<const double *>(out->owned[2].get());
       }
       if (on_host) AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // pageable source
     } else {
@@ -510,16 +494,10 @@ int features_to_device(agp_context *ctx, const agp_features *f, bool copy, Devic
 }
 }  // namespace agp
 
-int ensure_ws(agp_context *ctx, double **ws, size_t *have, size_t need) {
-  if (*have >= need) return AGP_OK;
-  if (*ws) {
-    AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    AGP_HIP_CHECK(ctx, hipFree(*ws));
-    *ws = nullptr;
-    *have = 0;
-  }
-  AGP_HIP_CHECK(ctx, hipMalloc(ws, need));
-  *have = need;
+int reserve_ws(agp_context *ctx, GrowBuf<double> &ws, size_t need) {
+  if (ws.bytes() >= need) return AGP_OK;
+  if (ws) AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  AGP_HIP_CHECK(ctx, ws.reserve(need));
   return AGP_OK;
 }
 
@@ -548,14 +526,14 @@ int copy_out_2d(agp_context *ctx, const double *dev, long long ld_dev, long long
   }
   if (location == AGP_HOST && (size_t)rows * (size_t)cols >= (1u << 16)) {
     // re-pitch on the device, then one contiguous transfer
-    double *tmp = nullptr;
+    DevMem<double> tmp;
     const size_t elems = (size_t)ld_dst * (size_t)(cols - 1) + (size_t)rows;
-    AGP_HIP_CHECK(ctx, hipMalloc(&tmp, sizeof(double) * elems));
+    AGP_HIP_CHECK(ctx, tmp.alloc_plain(sizeof(double) * elems));
     hipError_t e = hipMemcpy2DAsync(tmp, sizeof(double) * (size_t)ld_dst, dev, sizeof(double) * (size_t)ld_dev,
                                     sizeof(double) * (size_t)rows, (size_t)cols, hipMemcpyDeviceToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dst, tmp, sizeof(double) * elems, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(tmp);
+    tmp.reset();
     if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); return AGP_ERR_HIP; }
     return AGP_OK;
   }
@@ -692,7 +670,7 @@ int agp_gram(agp_context *ctx, const agp_kernel *k, const agp_features *x, const
     if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); st = AGP_ERR_HIP; }
   } else {
     const long long ldd = round_up(rows, 2);
-    st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, sizeof(double) * (size_t)ldd * (size_t)cols);
+    st = reserve_ws(ctx, ctx->ws_aux, sizeof(double) * (size_t)ldd * (size_t)cols);
     if (st == AGP_OK) {
       launch_gram(ctx->stream, dprog, dx.v, vy, y == nullptr, false, ctx->ws_aux, ldd, nullptr, nullptr, &k->prog);
       st = copy_out_2d(ctx, ctx->ws_aux, ldd, rows, cols, out, ld, AGP_HOST);
@@ -732,7 +710,7 @@ int agp_gram_combined(agp_context *ctx, const agp_kernel *k, const agp_features 
   const long long ldk = round_up(ex, 2), ldo = round_up(na, 2);
   const size_t k_elems = (size_t)ldk * (size_t)ey, o_elems = (size_t)ldo * (size_t)nb;
   const size_t meta = (size_t)(x_offsets ? 2 * (nx + 1) + ex : 0) + (size_t)((!symmetric && y_offsets) ? 2 * (ny + 1) + ey : 0) + 8;
-  if ((st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, sizeof(double) * (k_elems + o_elems + meta))) != AGP_OK) return st;
+  if ((st = reserve_ws(ctx, ctx->ws_aux, sizeof(double) * (k_elems + o_elems + meta))) != AGP_OK) return st;
   double *Kd = ctx->ws_aux, *Od = Kd + k_elems, *m = Od + o_elems;
   hipStream_t s = ctx->stream;
   const long long *xoff_d = nullptr, *yoff_d = nullptr;
@@ -763,61 +741,18 @@ int agp_gram_combined(agp_context *ctx, const agp_kernel *k, const agp_features 
 void agp_fit_destroy(agp_fit *fit) {
   if (!fit) return;
   (void)hipSetDevice(fit->device);
-  if (fit->slab) {
-    if (--fit->slab->refs == 0) {
-      agp_context *ctx = fit->ctx;
-      if (ctx && ctx->pool_batch && ctx->pool_batch_bytes != fit->slab->bytes) {  // (the most recent size wins the slot, as pool_A)
-        (void)dev_release(ctx->pool_batch);
-        ctx->pool_batch = nullptr;
-        ctx->pool_batch_bytes = 0;
-      }
-      if (ctx && !ctx->pool_batch) { ctx->pool_batch = fit->slab->base; ctx->pool_batch_bytes = fit->slab->bytes; }  // (like pool_A)
-      else (void)dev_release(fit->slab->base);
-      delete fit->slab;
-    }
-    fit->train.release();
-    delete fit;
-    return;
+  agp_context *ctx = fit->ctx;
+  // What the fit owns is offered to the context's slots, where the next fit of the same size finds it (kernels reading
+  // the blocks were enqueued on the context's streams; their next user is enqueued on the same streams, after them).  The
+  // most recent size wins a slot: a buffer of another size parked there - the headline's 2 GiB factor, say, in a process
+  // that goes on to fit 512 points - would cost every later fit a hipMalloc and a hipFree: +0.2 ms per N = 512 fit, the
+  // "0.21 vs 0.41 ms" of the round-4 review.  What a slot refuses goes with its owner.
+  if (fit->slab && --fit->slab->refs == 0) {
+    if (ctx && ctx->pool_batch.park(fit->slab->base, fit->slab->bytes)) (void)fit->slab->base.release();
+    delete fit->slab;
   }
-  if (fit->A) {
-    agp_context *ctx = fit->ctx;
-    // (the most recent size wins the slot: a buffer of another size parked there - the headline's 2 GiB factor, say, in a
-    // process that goes on to fit 512 points - would cost every later fit a hipMalloc and a hipFree: +0.2 ms per N = 512
-    // fit, the "0.21 vs 0.41 ms" of the round-4 review)
-    if (ctx && ctx->pool_A && ctx->pool_A_bytes != fit->A_bytes) {
-      (void)dev_release(ctx->pool_A);
-      ctx->pool_A = nullptr;
-      ctx->pool_A_bytes = 0;
-    }
-    if (ctx && !ctx->pool_A) {
-      // kernels reading the factor were enqueued on the context's streams; the
-      // next user of the buffer is enqueued on the same streams, after them
-      ctx->pool_A = fit->A;
-      ctx->pool_A_bytes = fit->A_bytes;
-    } else {
-      (void)dev_free(fit->A);
-    }
-  }
-  if (fit->aux_base) {
-    agp_context *ctx = fit->ctx;
-    if (ctx && ctx->pool_aux && ctx->pool_aux_bytes != fit->aux_bytes) {
-      (void)dev_release(ctx->pool_aux);
-      ctx->pool_aux = nullptr;
-      ctx->pool_aux_bytes = 0;
-    }
-    if (ctx && !ctx->pool_aux) {
-      ctx->pool_aux = fit->aux_base;
-      ctx->pool_aux_bytes = fit->aux_bytes;
-    } else {
-      (void)dev_release(fit->aux_base);
-    }
-  } else {
-    if (fit->invd) (void)dev_free(fit->invd);
-    if (fit->winv) (void)dev_free(fit->winv);
-    if (fit->alpha) (void)dev_free(fit->alpha);
-    if (fit->z) (void)dev_free(fit->z);
-  }
-  fit->train.release();
+  if (ctx && fit->own_A && ctx->pool_A.park(fit->own_A, fit->A_bytes)) (void)fit->own_A.release();
+  if (ctx && fit->aux_base && ctx->pool_aux.park(fit->aux_base, fit->aux_bytes)) (void)fit->aux_base.release();
   delete fit;
 }
 
@@ -958,51 +893,34 @@ static int fit_create_impl(agp_context *c, const agp_kernel *k, const agp_featur
   fit->lda = factor_ld(n);
   const long long nblk = (n + NB - 1) / NB;
   hipStream_t s = ctx->stream;
-  double *yvar_d = nullptr;
-  double *Kfull = nullptr, *Wfwd = nullptr, *vec = nullptr;  // mixed precision only
-  size_t Kfull_bytes = 0;
-  auto drop_mixed = [&]() {
-    if (Kfull) {  // parked for the next mixed fit of the same size, like the factor's own buffer (pool_A)
-      if (!ctx->pool_K) { ctx->pool_K = Kfull; ctx->pool_K_bytes = Kfull_bytes; }
-      else (void)hipFree(Kfull);
-    }
-    if (Wfwd) (void)hipFree(Wfwd);
-    if (vec) (void)hipFree(vec);
-    Kfull = Wfwd = vec = nullptr;
-  };
-#define FIT_CHECK(expr)                                                                  \
-  do {                                                                                   \
-    hipError_t _e = (expr);                                                              \
-    if (_e != hipSuccess) {                                                              \
-      ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(_e);               \
-      if (yvar_d) (void)hipFree(yvar_d);                                                 \
-      drop_mixed();                                                                      \
-      agp_fit_destroy(fit);                                                              \
-      return AGP_ERR_HIP;                                                                \
-    }                                                                                    \
-  } while (0)
   fit->ctx = ctx;
+  // an early return destroys the fit (its blocks go to the context's slots), the exact covariance of a mixed fit goes back
+  // to its slot (parked for the next mixed fit of the same size, like the factor's own buffer), the rest is freed
+  FitGuard guard(fit);
+  struct ParkK {
+    ParkSlot &slot;
+    DevMem<double> mem;
+    size_t bytes = 0;
+    void drop() {
+      if (mem && slot.park(mem, bytes)) (void)mem.release();
+      mem.reset();
+    }
+    ~ParkK() { drop(); }
+  } Kfull{ctx->pool_K};
+  DevMem<double> yvar_d;
+  DevMem<double> Wfwd, vec;  // mixed precision only
   fit->A_bytes = sizeof(double) * (size_t)fit->lda * (size_t)n;
-  if (ctx->pool_A && ctx->pool_A_bytes == fit->A_bytes) {
-    fit->A = ctx->pool_A;
-    ctx->pool_A = nullptr;
-    ctx->pool_A_bytes = 0;
-  } else {
-    FIT_CHECK(hipMalloc(&fit->A, fit->A_bytes));
-  }
+  fit->own_A.adopt(static_cast<double *>(ctx->pool_A.take(fit->A_bytes)));
+  if (!fit->own_A) AGP_HIP_CHECK(ctx, fit->own_A.alloc_plain(fit->A_bytes));
+  fit->A = fit->own_A;
   {
     const size_t n_invd = (size_t)nblk * (36 * MB * MB), n_winv = (size_t)nblk * NB * NB, n_vec = (size_t)round_up(n, 2);
     // (+ train_features = features, un-wrapped; gp.hpp:63,293: always a copy, inside this pooled block - a hipMalloc and a
     // hipFree per fit are ~0.1 ms of a 2 ms fit)
     const size_t n_feat = (size_t)n * ((size_t)x->dim + (x->eq_id ? 1 : 0) + (size_t)x->n_scale_columns);
     fit->aux_bytes = sizeof(double) * (n_invd + n_winv + 2 * n_vec + n_feat);
-    if (ctx->pool_aux && ctx->pool_aux_bytes == fit->aux_bytes) {
-      fit->aux_base = ctx->pool_aux;
-      ctx->pool_aux = nullptr;
-      ctx->pool_aux_bytes = 0;
-    } else {
-      FIT_CHECK(hipMalloc(&fit->aux_base, fit->aux_bytes));
-    }
+    fit->aux_base.adopt(static_cast<double *>(ctx->pool_aux.take(fit->aux_bytes)));
+    if (!fit->aux_base) AGP_HIP_CHECK(ctx, fit->aux_base.alloc_plain(fit->aux_bytes));
     fit->invd = fit->aux_base;
     fit->winv = fit->invd + n_invd;
     fit->alpha = fit->winv + n_winv;
@@ -1022,25 +940,25 @@ static int fit_create_impl(agp_context *c, const agp_kernel *k, const agp_featur
     FeatView v;
     v.n = n; v.dim = x->dim; v.nsc = x->n_scale_columns; v.meas = 0;
     v.coords = fcur; v.ids = nullptr; v.scales = nullptr;
-    FIT_CHECK(stage(fcur, x->coords, n * (long long)x->dim));
+    AGP_HIP_CHECK(ctx, stage(fcur, x->coords, n * (long long)x->dim));
     fcur += (size_t)n * (size_t)x->dim;
     if (x->eq_id) {
       v.ids = reinterpret_cast<const long long *>(fcur);
-      FIT_CHECK(stage(fcur, x->eq_id, n));
+      AGP_HIP_CHECK(ctx, stage(fcur, x->eq_id, n));
       fcur += n;
     }
     if (x->n_scale_columns > 0) {
       v.scales = fcur;
-      FIT_CHECK(stage(fcur, x->scales, n * (long long)x->n_scale_columns));
+      AGP_HIP_CHECK(ctx, stage(fcur, x->scales, n * (long long)x->n_scale_columns));
     }
     fit->train.v = v;  // (a view into aux_base: DeviceFeatures::release has nothing to free)
   }
-  FIT_CHECK(stage(fit->z, y, n));
+  AGP_HIP_CHECK(ctx, stage(fit->z, y, n));
   if (y_var) {
-    FIT_CHECK(hipMalloc(&yvar_d, sizeof(double) * (size_t)n));
-    FIT_CHECK(stage(yvar_d, y_var, n));
+    AGP_HIP_CHECK(ctx, yvar_d.alloc_plain(sizeof(double) * (size_t)n));
+    AGP_HIP_CHECK(ctx, stage(yvar_d, y_var, n));
   }
-  if (x->location == AGP_HOST) FIT_CHECK(hipStreamSynchronize(s));
+  if (x->location == AGP_HOST) AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
   if (mixed && pre.n > 0) {  // (the mixed fit reads the staged inputs before build_and_factor: its exact covariance, the copy of y)
     launch_prep(s, pre);
     pre = PrepArgs();
@@ -1054,19 +972,16 @@ static int fit_create_impl(agp_context *c, const agp_kernel *k, const agp_featur
   if (mixed) {
     // the exact fp64 covariance (lower triangle: the refinement multiplies with launch_symv_lower) for the residuals, the targets,
     // and the work vectors r, z, p, q
-    Kfull_bytes = fit->A_bytes;
-    if (ctx->pool_K && ctx->pool_K_bytes == Kfull_bytes) {
-      Kfull = ctx->pool_K;
-      ctx->pool_K = nullptr;
-      ctx->pool_K_bytes = 0;
-    } else {
-      if (ctx->pool_K) { (void)dev_release(ctx->pool_K); ctx->pool_K = nullptr; ctx->pool_K_bytes = 0; }
-      FIT_CHECK(hipMalloc(&Kfull, Kfull_bytes));
+    Kfull.bytes = fit->A_bytes;
+    Kfull.mem.adopt(static_cast<double *>(ctx->pool_K.take(Kfull.bytes)));
+    if (!Kfull.mem) {
+      ctx->pool_K.clear();  // (a block of another size goes BEFORE this one is allocated: both are of the factor's size)
+      AGP_HIP_CHECK(ctx, Kfull.mem.alloc_plain(Kfull.bytes));
     }
-    FIT_CHECK(hipMalloc(&Wfwd, sizeof(double) * (size_t)nblk * NB * NB));
-    FIT_CHECK(hipMalloc(&vec, sizeof(double) * (size_t)n * 5));
-    FIT_CHECK(hipMemcpyAsync(vec, fit->z, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
-    launch_gram(s, dprog, xm, xm, /*symmetric=*/true, /*lower_only=*/true, Kfull, fit->lda, yvar_d, ctx->d_flags,
+    AGP_HIP_CHECK(ctx, Wfwd.alloc_plain(sizeof(double) * (size_t)nblk * NB * NB));
+    AGP_HIP_CHECK(ctx, vec.alloc_plain(sizeof(double) * (size_t)n * 5));
+    AGP_HIP_CHECK(ctx, hipMemcpyAsync(vec, fit->z, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
+    launch_gram(s, dprog, xm, xm, /*symmetric=*/true, /*lower_only=*/true, Kfull.mem, fit->lda, yvar_d, ctx->d_flags,
                 &k->prog);
     // fp32-accurate products of the bulk updates: on the 16-bit matrix pipe from split planes of the panel, or
     // - AGP_MIXED_BF16=0 - on the fp32 MFMA as in rounds 1-4
@@ -1076,22 +991,15 @@ static int fit_create_impl(agp_context *c, const agp_kernel *k, const agp_featur
     req.variant = f16 ? 5 : (planes16 ? 4 : 3);
     req.nbo_wide = (planes16 && ctx->tune.mixed_nbo > 512 && ctx->tune.mixed_nbo % 128 == 0) ? ctx->tune.mixed_nbo : 0;
     if (f16 && ctx->f16_scales_n < n) {
-      if (ctx->f16_scales) (void)hipFree(ctx->f16_scales);
-      ctx->f16_scales = nullptr; ctx->f16_scales_n = 0;
       const long long cap = round_up(n, 2);
-      if (hipMalloc(&ctx->f16_scales, sizeof(double) * 2 * (size_t)cap) == hipSuccess) ctx->f16_scales_n = cap;
-      else (void)hipGetLastError();  // (factor_lower falls back to the bf16 planes)
+      ctx->f16_scales_n = ctx->f16_scales.reserve(sizeof(double) * 2 * (size_t)cap) == 0 ? cap : 0;
+      if (!ctx->f16_scales_n) (void)hipGetLastError();  // (factor_lower falls back to the bf16 planes)
     }
     {  // two panel copies of (n rows + padding) x 512 (chol.hip, factor_lower): fp32, or three bf16 planes (two fp16 planes fit in the
        // same space: the fall-back from fp16 to bf16 planes needs no second allocation); kept in the context
       const size_t want = planes16 ? 2 * bf16x3_bytes(n, req.nbo_wide > 512 ? req.nbo_wide : 512)
                                    : sizeof(float) * 2 * ((size_t)n + 16) * 512;
-      if (ctx->p32_bytes < want) {
-        if (ctx->p32) (void)hipFree(ctx->p32);
-        ctx->p32 = nullptr; ctx->p32_bytes = 0;
-        if (hipMalloc(&ctx->p32, want) == hipSuccess) ctx->p32_bytes = want;
-        else (void)hipGetLastError();  // (the kernels round the operands themselves then)
-      }
+      if (ctx->p32.reserve(want) != 0) (void)hipGetLastError();  // (the kernels round the operands themselves then)
     }
   }
   // The fp64 fit does not wait for the factorisation before it enqueues the backward substitution: one host round trip
@@ -1118,7 +1026,7 @@ static int fit_create_impl(agp_context *c, const agp_kernel *k, const agp_featur
   if (!coop && deferred && backsolve_width(n)) {
     // the inverses of the wide diagonal blocks for the backward substitution: computed by factor_lower on its idle
     // second stream while the chain-bound tail of the factorisation runs (factor_plan.h: FactorRequest)
-    if (ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, sizeof(double) * backsolve_ws_elems(n)) == AGP_OK) {
+    if (reserve_ws(ctx, ctx->ws_aux, sizeof(double) * backsolve_ws_elems(n)) == AGP_OK) {
       req.inv_W = ctx->ws_aux + round_up(n, 2);
       req.inv_BW = backsolve_width(n);
     }
@@ -1127,15 +1035,13 @@ static int fit_create_impl(agp_context *c, const agp_kernel *k, const agp_featur
   // pinned mirror - no copy launch behind the factorisation, none behind the substitution)
   const bool status_in_kernel = coop && deferred && ctx->h_status_dev != nullptr;
   st = build_and_factor(ctx, dprog, &k->prog, xm, fit->A, fit->lda, fit->invd, fit->z, yvar_d, !deferred, &ftimers, &pre,
-                        !status_in_kernel, mixed ? Kfull : nullptr, req, &factored);
+                        !status_in_kernel, mixed ? Kfull.mem.get() : nullptr, req, &factored);
   const long long bs_done = factored.inv_done;
   ctx->sched.bs_done = bs_done;
-  if (yvar_d) { (void)hipFree(yvar_d); yvar_d = nullptr; }
+  yvar_d.reset();  // (here, not at scope exit: the free synchronises the device)
   if (st != AGP_OK) {
     // (the early inversion may still be writing ws_aux on the second stream: whatever uses it next is ordered behind it)
     if (bs_done > 0) (void)hipStreamWaitEvent(s, ctx->ev_inv, 0);
-    drop_mixed();
-    agp_fit_destroy(fit);
     return st;
   }
   if (!deferred) {
@@ -1144,31 +1050,30 @@ static int fit_create_impl(agp_context *c, const agp_kernel *k, const agp_featur
     fit->log_det = 2. * ctx->h_scalars[0];
     if (st != AGP_OK) {
       // keep a handle so the caller can query the failed pivot, but no factor
-      drop_mixed();
       fit->fail_status = st;
-      *out = fit;
+      *out = guard.release();
       return st;
     }
   }
   // information = L^-T (L^-1 y)
-  if (ctx->profiling) FIT_CHECK(hipEventRecord(ctx->stage_ev[3], s));
+  if (ctx->profiling) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[3], s));
   if (coop) {
     TraceRange tr("agp: backward substitution (information = ldlt.solve(y), gp.hpp:68)");
     backward_solve_coop(s, fit->A, n, fit->lda, fit->invd, fit->z, fit->alpha, ctx->d_flags,
                         coop_direct ? nullptr : reinterpret_cast<unsigned long long *>(fit->winv), 1, 0, 0, 0, 0, 0,
                         status_in_kernel ? ctx->d_flags : nullptr, ctx->h_status_dev, (int)(STATUS_BYTES / 8));
     // (the hand-over flag of the substitution: the 48-byte status copy left before it ran)
-    if (!status_in_kernel) FIT_CHECK(hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (!status_in_kernel) AGP_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
   } else {
-    const int st2 = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, sizeof(double) * backsolve_ws_elems(n));
-    if (st2 != AGP_OK) { drop_mixed(); agp_fit_destroy(fit); return st2; }
+    const int st2 = reserve_ws(ctx, ctx->ws_aux, sizeof(double) * backsolve_ws_elems(n));
+    if (st2 != AGP_OK) return st2;
     {
       TraceRange tr("agp: backward substitution (information = ldlt.solve(y), gp.hpp:68)");
       backward_solve_vec_from(s, fit->A, n, fit->lda, fit->invd, fit->z, fit->alpha, ctx->ws_aux, bs_done, ctx->ev_inv,
                               ctx->tune.backsub_coop ? ctx->d_flags : nullptr);
       // (its last wide block goes through the one-launch substitution, which records a timed-out hand-over in flags[2]: the
       // status block left for the host BEFORE the substitution ran - the flags once more behind it)
-      if (deferred) FIT_CHECK(hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+      if (deferred) AGP_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
     }
     // the refinement steps of the mixed-precision fit use the 128-row chain on fit->winv
     if (mixed) invert_diag_blocks(s, fit->A, n, fit->lda, fit->invd, fit->winv);
@@ -1176,16 +1081,18 @@ static int fit_create_impl(agp_context *c, const agp_kernel *k, const agp_featur
   if (mixed) {
     fit->mixed = true;
     invert_diag_blocks_forward(s, n, fit->invd, Wfwd);
-    const int st3 = refine_information(ctx, fit, Kfull, Wfwd, vec, mixed);
-    drop_mixed();
-    if (st3 != AGP_OK) { agp_fit_destroy(fit); return st3; }
+    const int st3 = refine_information(ctx, fit, Kfull.mem, Wfwd, vec, mixed);
+    Kfull.drop();  // (these three here, not at scope exit: a free synchronises the device)
+    Wfwd.reset();
+    vec.reset();
+    if (st3 != AGP_OK) return st3;
   }
-  if (ctx->profiling) FIT_CHECK(hipEventRecord(ctx->stage_ev[4], s));
+  if (ctx->profiling) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[4], s));
   // (deferred status: the caller's buffer is written only once the factor is known to be good - a NaN, a non-positive
   // pivot or a timed-out hand-over leaves it untouched)
-  if (information && !deferred) FIT_CHECK(hipMemcpyAsync(information, fit->alpha, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
-  FIT_CHECK(hipStreamSynchronize(s));
-  FIT_CHECK(hipGetLastError());
+  if (information && !deferred) AGP_HIP_CHECK(ctx, hipMemcpyAsync(information, fit->alpha, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
   if (deferred) {
     finish_factor(ctx, ftimers);
     st = status_from_flags(ctx);
@@ -1193,13 +1100,12 @@ static int fit_create_impl(agp_context *c, const agp_kernel *k, const agp_featur
     fit->log_det = 2. * ctx->h_scalars[0];
     if (st != AGP_OK) {  // keep a handle so the caller can query the failed pivot, but no factor
       fit->fail_status = st;
-      *out = fit;
+      *out = guard.release();
       return st;
     }
-    if (information) FIT_CHECK(hipMemcpy(information, fit->alpha, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    if (information) AGP_HIP_CHECK(ctx, hipMemcpy(information, fit->alpha, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
   } else if (coop && ctx->h_flags[2]) {  // the one-launch substitution gave up on a hand-over (its producer died)
     ctx->last_error = "back substitution: hand-over timed out";
-    agp_fit_destroy(fit);
     return AGP_ERR_HIP;
   }
   if (ctx->profiling) {
@@ -1208,8 +1114,7 @@ static int fit_create_impl(agp_context *c, const agp_kernel *k, const agp_featur
     ctx->stage_ms[2] = ms;
   }
   if (log_det) *log_det = fit->log_det;
-  *out = fit;
-#undef FIT_CHECK
+  *out = guard.release();
   return AGP_OK;
 }
 
@@ -1279,7 +1184,7 @@ static int refine_information(agp_context_impl *ctx, agp_fit *fit, const double 
   const size_t wide_elems = BW ? (size_t)(n / BW) * (size_t)BW * (size_t)BW : 0;
   const size_t np2 = (size_t)round_up(n, 2);
   {
-    const int st_ws = ensure_ws(ctx, &ctx->ws_refine, &ctx->ws_refine_bytes, sizeof(double) * (symv_elems + 2 * wide_elems + 2 * np2));
+    const int st_ws = reserve_ws(ctx, ctx->ws_refine, sizeof(double) * (symv_elems + 2 * wide_elems + 2 * np2));
     if (st_ws != AGP_OK) return st_ws;
   }
   double *symv_ws = ctx->ws_refine;
@@ -1298,12 +1203,13 @@ static int refine_information(agp_context_impl *ctx, agp_fit *fit, const double 
   float *L32 = nullptr;
   if (BW) {
     const size_t want = sizeof(float) * (size_t)lda * (size_t)n;
-    if (ctx->pool_L32 && ctx->pool_L32_bytes != want) { (void)hipFree(ctx->pool_L32); ctx->pool_L32 = nullptr; ctx->pool_L32_bytes = 0; }
-    if (!ctx->pool_L32) {
-      if (hipMalloc(&ctx->pool_L32, want) == hipSuccess) ctx->pool_L32_bytes = want;
-      else { (void)hipGetLastError(); ctx->pool_L32 = nullptr; }
+    // (the slot's occupant when it has this size, else a new block in its place; it stays in the slot while it is used)
+    L32 = static_cast<float *>(ctx->pool_L32.take(want));
+    if (!L32) {
+      ctx->pool_L32.clear();
+      if (dev_malloc_plain_bytes(reinterpret_cast<void **>(&L32), want) != 0) { (void)hipGetLastError(); L32 = nullptr; }
     }
-    L32 = ctx->pool_L32;
+    if (L32) (void)ctx->pool_L32.park(L32, want);
     if (L32) launch_convert_lower_f32(s, fit->A, lda, n, L32);
   }
   auto precondition = [&](const double *in, double *outv) {
@@ -1406,7 +1312,7 @@ int agp_fit_download_factor(agp_context *ctx, const agp_fit *fit, double *L, int
   if (!fit->phantom.empty()) {
     // drop the phantom rows AND columns: they are decoupled (identity rows), what remains is the factor of the real matrix
     const long long nr = fit_real_rows(fit), ldt = round_up(nr, 2);
-    int st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, sizeof(double) * ((size_t)fit->lda * (size_t)n + (size_t)ldt * (size_t)n));
+    int st = reserve_ws(ctx, ctx->ws_aux, sizeof(double) * ((size_t)fit->lda * (size_t)n + (size_t)ldt * (size_t)n));
     if (st != AGP_OK) return st;
     double *full = ctx->ws_aux, *rows = full + (size_t)fit->lda * (size_t)n;
     AGP_HIP_CHECK(ctx, hipMemcpyAsync(full, fit->A, sizeof(double) * (size_t)fit->lda * (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
@@ -1424,7 +1330,7 @@ int agp_fit_download_factor(agp_context *ctx, const agp_fit *fit, double *L, int
     if (n > pad && (st = copy_cols(pad, real, n - pad)) != AGP_OK) return st;
     return AGP_OK;
   }
-  int st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, sizeof(double) * (size_t)fit->lda * (size_t)n);
+  int st = reserve_ws(ctx, ctx->ws_aux, sizeof(double) * (size_t)fit->lda * (size_t)n);
   if (st != AGP_OK) return st;
   AGP_HIP_CHECK(ctx, hipMemcpyAsync(ctx->ws_aux, fit->A, sizeof(double) * (size_t)fit->lda * (size_t)n,
                                     hipMemcpyDeviceToDevice, ctx->stream));
@@ -1448,7 +1354,7 @@ int agp_nll(agp_context *c, const agp_kernel *k, const agp_features *x, const do
   const long long lda = g.lda;
   WsLayout size;
   carve_fit(size, g);
-  if ((st = ensure_ws(ctx, &ctx->ws_A, &ctx->ws_A_bytes, size.bytes())) != AGP_OK) return st;
+  if ((st = reserve_ws(ctx, ctx->ws_A, size.bytes())) != AGP_OK) return st;
   WsLayout ws(ctx->ws_A);
   const FitRegions r = carve_fit(ws, g);
   double *A = r.A, *invd = r.invd, *z = r.z, *yvar_d = y_var ? r.yvar : nullptr;
@@ -1513,7 +1419,7 @@ int agp_nll_batch(agp_context *c, int count, const agp_kernel *const *kernels, c
   const size_t table_bytes = gram_batch_table_bytes(count);
   WsLayout size;
   carve_nll_batch(size, g, fused_panels, table_bytes);
-  if ((st = ensure_ws(ctx, &ctx->ws_A, &ctx->ws_A_bytes, size.bytes())) != AGP_OK) return st;
+  if ((st = reserve_ws(ctx, ctx->ws_A, size.bytes())) != AGP_OK) return st;
   WsLayout ws(ctx->ws_A);
   const NllBatchRegions r = carve_nll_batch(ws, g, fused_panels, table_bytes);
   const int loc = features[0]->location;
@@ -1595,23 +1501,20 @@ int agp::fit_create_batch(agp_context *c, int count, const agp_kernel *const *ke
   carve_fit_batch(size, g, y_var != nullptr);
   for (int b = 0; b < count; ++b) carve_features(size, features[b], n);
   const size_t bytes = size.bytes();
-  double *base = nullptr;
-  if (ctx->pool_batch && ctx->pool_batch_bytes == bytes) {
-    base = ctx->pool_batch;
-    ctx->pool_batch = nullptr;
-    ctx->pool_batch_bytes = 0;
-  } else {
-    if (ctx->pool_batch) { (void)dev_release(ctx->pool_batch); ctx->pool_batch = nullptr; ctx->pool_batch_bytes = 0; }
-    AGP_HIP_CHECK(ctx, hipMalloc(&base, bytes));
+  DevMem<double> base;
+  base.adopt(static_cast<double *>(ctx->pool_batch.take(bytes)));
+  if (!base) {
+    ctx->pool_batch.clear();  // (a slab of another size goes BEFORE this one is allocated)
+    AGP_HIP_CHECK(ctx, base.alloc_plain(bytes));
   }
-  WsLayout ws(base);
+  WsLayout ws(base.get());
   const FitBatchRegions r = carve_fit_batch(ws, g, y_var != nullptr);
   std::vector<agp_fit *> fits((size_t)count, nullptr);
   auto fail = [&](int code) {
     (void)hipStreamSynchronize(s);
     for (auto *f : fits)
-      if (f) { f->train.release(); delete f; }
-    (void)hipFree(base);
+      if (f) delete f;
+    base.reset();
     return code;
   };
 #define BATCH_CHECK(expr)                                                     \
@@ -1677,10 +1580,9 @@ int agp::fit_create_batch(agp_context *c, int count, const agp_kernel *const *ke
   const size_t copy_bytes = pad_off + pad_bytes, gram_bytes = gram_batch_table_bytes(count);
   WsLayout tsize;
   carve_fit_batch_tables(tsize, g, fused_panels, copy_bytes, gram_bytes);
-  void *tables = nullptr;
-  if (dev_malloc(&tables, tsize.bytes()) != hipSuccess) { (void)hipGetLastError(); tables = nullptr; }
-  struct FreeTables { void *p; ~FreeTables() { if (p) (void)dev_free(p); } } free_tables{tables};
-  WsLayout tws(tables);
+  DevMem<void> tables;
+  if (tables.alloc_cached(tsize.bytes()) != 0) (void)hipGetLastError();
+  WsLayout tws(tables.get());
   const FitBatchTables t = carve_fit_batch_tables(tws, g, fused_panels, copy_bytes, gram_bytes);  // (all null without `tables`)
   // (both tables are built in the context's pinned staging area, laid out like the device's: no synchronisation between
   // the uploads and the launches that read them - the two mid-call synchronisations of round 5 were ~4 % of a batch of
@@ -1756,7 +1658,7 @@ int agp::fit_create_batch(agp_context *c, int count, const agp_kernel *const *ke
     }
   agp_fit_slab *slab = new (std::nothrow) agp_fit_slab();
   if (!slab) return fail(AGP_ERR_INVALID_ARGUMENT);
-  slab->base = base;
+  slab->base = std::move(base);
   slab->bytes = bytes;
   slab->refs = count;
   for (int b = 0; b < count; ++b) {
@@ -1813,8 +1715,8 @@ int agp_solve(agp_context *ctx, const agp_fit *fit, const double *rhs, int64_t n
   if (!fit->phantom.empty()) {
     // rhs / out hold the REAL rows: spread them over the padded rows (phantom rows zero), solve, gather
     const long long nr = fit_real_rows(fit);
-    double *B = nullptr;
-    AGP_HIP_CHECK(ctx, hipMalloc(&B, sizeof(double) * (size_t)ldb * (size_t)nrhs));
+    DevMem<double> B;
+    AGP_HIP_CHECK(ctx, B.alloc_plain(sizeof(double) * (size_t)ldb * (size_t)nrhs));
     int st = fit_expand_matrix(ctx, fit, rhs, nr, nrhs, B, ldb, location);
     if (st == AGP_OK) {
       forward_solve_mat_lookahead(ctx, fit->A, n, fit->lda, fit->invd, B, nrhs, ldb);
@@ -1822,7 +1724,6 @@ int agp_solve(agp_context *ctx, const agp_fit *fit, const double *rhs, int64_t n
       st = fit_compact_matrix(ctx, fit, B, ldb, nrhs, out, nr, location);
     }
     (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(B);
     return st;
   }
   if (nrhs == 1 && n >= 1024) {
@@ -1830,7 +1731,7 @@ int agp_solve(agp_context *ctx, const agp_fit *fit, const double *rhs, int64_t n
     // (fused 128-row forward steps, blocked backward substitution) are 4x shorter (N = 16384: 11.3 -> 2.7 ms)
     const long long nblk = (n + NB - 1) / NB;
     const size_t wf = (size_t)nblk * NB * NB;
-    int st1 = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, sizeof(double) * ((size_t)ldb + wf + backsolve_ws_elems(n)));
+    int st1 = reserve_ws(ctx, ctx->ws_aux, sizeof(double) * ((size_t)ldb + wf + backsolve_ws_elems(n)));
     if (st1 != AGP_OK) return st1;
     double *z = ctx->ws_aux, *Wfwd = z + ldb, *ws = Wfwd + wf;
     hipStream_t s = ctx->stream;
@@ -1850,7 +1751,7 @@ int agp_solve(agp_context *ctx, const agp_fit *fit, const double *rhs, int64_t n
     backward_solve_vec_any(s, fit->A, n, fit->lda, fit->invd, z, ws);
     return copy_out(ctx, z, n, out, location);
   }
-  int st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, sizeof(double) * (size_t)ldb * (size_t)nrhs);
+  int st = reserve_ws(ctx, ctx->ws_aux, sizeof(double) * (size_t)ldb * (size_t)nrhs);
   if (st != AGP_OK) return st;
   AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(ctx->ws_aux, sizeof(double) * (size_t)ldb, rhs, sizeof(double) * (size_t)n,
                                       sizeof(double) * (size_t)n, (size_t)nrhs, kind, ctx->stream));
@@ -1874,20 +1775,17 @@ int factor_dense(agp_context *c, const double *K, long long n, long long ld, int
   fit->n = n;
   fit->lda = factor_ld(n);
   fit->A_bytes = sizeof(double) * (size_t)fit->lda * (size_t)n;
-  if (ctx->pool_A && ctx->pool_A_bytes == fit->A_bytes) {
-    fit->A = ctx->pool_A;
-    ctx->pool_A = nullptr;
-    ctx->pool_A_bytes = 0;
-  } else {
-    AGP_HIP_CHECK(ctx, dev_malloc(&fit->A, fit->A_bytes));
-  }
-  AGP_HIP_CHECK(ctx, dev_malloc(&fit->invd, sizeof(double) * (size_t)nblk * (36 * MB * MB)));
+  fit->own_A.adopt(static_cast<double *>(ctx->pool_A.take(fit->A_bytes)));
+  if (!fit->own_A) AGP_HIP_CHECK(ctx, fit->own_A.alloc_cached(fit->A_bytes));
+  fit->A = fit->own_A;
+  AGP_HIP_CHECK(ctx, fit->own_part[0].alloc_cached(sizeof(double) * (size_t)nblk * (36 * MB * MB)));
+  fit->invd = fit->own_part[0];
   const double *src = K;  // device-resident source of the triangle
   if (location == AGP_HOST) {
     // a pitched copy from pageable host memory degenerates into one small copy per
     // column; upload the matrix in one piece and re-pitch it on the device
     const size_t bytes = sizeof(double) * (size_t)ld * (size_t)n;
-    int st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, bytes);
+    int st = reserve_ws(ctx, ctx->ws_aux, bytes);
     if (st != AGP_OK) return st;
     AGP_HIP_CHECK(ctx, hipMemcpyAsync(ctx->ws_aux, K, bytes - sizeof(double) * (size_t)(ld - n), hipMemcpyHostToDevice, s));
     src = ctx->ws_aux;
@@ -1938,8 +1836,8 @@ int agp_nll_dense(agp_context *ctx, const double *deviation, const double *K, in
   }
   agp_fit *fit = new (std::nothrow) agp_fit();
   if (!fit) return AGP_ERR_INVALID_ARGUMENT;
-  double *z = nullptr;
-  hipError_t e = hipMalloc(&z, sizeof(double) * (size_t)n);
+  DevMem<double> z;
+  hipError_t e = static_cast<hipError_t>(z.alloc_plain(sizeof(double) * (size_t)n));
   if (e != hipSuccess) { delete fit; ctx->last_error = hipGetErrorString(e); return AGP_ERR_HIP; }
   int st = vector_to_device(ctx, deviation, n, location, z);
   if (st == AGP_OK) st = factor_dense(ctx, K, n, ld, uplo, location, fit, z);
@@ -1950,7 +1848,7 @@ int agp_nll_dense(agp_context *ctx, const double *deviation, const double *K, in
     if (e != hipSuccess) { ctx->last_error = hipGetErrorString(e); st = AGP_ERR_HIP; }
     else *out = 0.5 * (fit->log_det + ctx->h_scalars[1] + (double)n * std::log(2 * M_PI));
   }
-  (void)hipFree(z);
+  z.reset();  // (before the factor, as ever)
   agp_fit_destroy(fit);
   return st;
 }
@@ -1960,7 +1858,7 @@ int agp_nll_dense(agp_context *ctx, const double *deviation, const double *K, in
 static int inverse_diagonal_device(agp_context *ctx, const agp_fit *fit, double **diag_out) {
   const long long n = fit->n, ldr = factor_ld(n);
   const size_t r_elems = (size_t)ldr * (size_t)n;
-  int st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, sizeof(double) * (r_elems + 3 * (size_t)round_up(n, 2)));
+  int st = reserve_ws(ctx, ctx->ws_aux, sizeof(double) * (r_elems + 3 * (size_t)round_up(n, 2)));
   if (st != AGP_OK) return st;
   double *R = ctx->ws_aux, *diag = R + r_elems;
   hipStream_t s = ctx->stream;
@@ -2020,7 +1918,7 @@ int agp_predict_mean(agp_context *ctx, const agp_kernel *k, const agp_fit *fit, 
     launch_predict_mean(ctx->stream, dprog, fit->train.v, dxs.v, fit->alpha, mean, &k->prog);
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->last_error = "agp_predict_mean: stream"; st = AGP_ERR_HIP; }
   } else {
-    st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, sizeof(double) * (size_t)m);
+    st = reserve_ws(ctx, ctx->ws_aux, sizeof(double) * (size_t)m);
     if (st == AGP_OK) {
       launch_predict_mean(ctx->stream, dprog, fit->train.v, dxs.v, fit->alpha, ctx->ws_aux, &k->prog);
       st = copy_out(ctx, ctx->ws_aux, m, mean, out_location);
@@ -2070,7 +1968,7 @@ static int predict_common(agp_context *ctx, const agp_kernel *k, const agp_fit *
   const long long ldc = round_up(chunk, 2);
   const size_t v_elems = (size_t)ldv * (size_t)chunk;
   const size_t p_elems = joint ? (size_t)ldc * (size_t)chunk : (size_t)ldc;
-  st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, sizeof(double) * (v_elems + (size_t)ldc + p_elems));
+  st = reserve_ws(ctx, ctx->ws_aux, sizeof(double) * (v_elems + (size_t)ldc + p_elems));
   if (st != AGP_OK) { dxs.release(); return st; }
   double *V = ctx->ws_aux, *mean_d = V + v_elems, *prior = mean_d + ldc;
   hipStream_t s = ctx->stream;
@@ -2086,15 +1984,15 @@ static int predict_common(agp_context *ctx, const agp_kernel *k, const agp_fit *
     if (m == 1 && n >= 1024) {
       // a single test point: the vector chain (one fused launch per 128 rows) instead of the matrix kernels
       const long long nblk = (n + NB - 1) / NB;
-      double *Wfwd = nullptr, *stage = nullptr;
+      DevMem<double> Wfwd;
       const long long BWp = backsolve_width(n);
       const size_t w_elems = BWp ? (size_t)(n / BWp) * (size_t)BWp * (size_t)BWp : (size_t)nblk * NB * NB;
-      if (hipMalloc(&Wfwd, sizeof(double) * (w_elems + (size_t)round_up(n, 2))) != hipSuccess) {
+      if (Wfwd.alloc_plain(sizeof(double) * (w_elems + (size_t)round_up(n, 2))) != 0) {
         dxs.release();
         ctx->last_error = "hipMalloc (single-point prediction workspace)";
         return AGP_ERR_HIP;
       }
-      stage = Wfwd + w_elems;
+      double *stage = Wfwd + w_elems;
       if (BWp) {  // through 512-wide inverted diagonal blocks (see agp_solve)
         invert_wide_blocks(s, fit->A, n, fit->lda, fit->invd, BWp, Wfwd);
         forward_solve_vec_wide(s, fit->A, n, fit->lda, Wfwd, BWp, V, stage);
@@ -2103,7 +2001,6 @@ static int predict_common(agp_context *ctx, const agp_kernel *k, const agp_fit *
         forward_solve_vec(s, fit->A, n, fit->lda, Wfwd, V, stage);
       }
       (void)hipStreamSynchronize(s);
-      (void)hipFree(Wfwd);
     } else {
       forward_solve_mat_lookahead(ctx, fit->A, n, fit->lda, fit->invd, V, m, ldv);
     }

@@ -4,6 +4,7 @@
 // argument checks, uploads, Gram tables, factor schedule - is batch_front.h, which builds on this header.
 #pragma once
 #include <atomic>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -11,20 +12,11 @@
 #include "contract.h"
 
 namespace agp {
-// Device allocations of the entry points that build several medium-sized objects per call (sparse GP fits, dense factors,
-// cross validation): a hipMalloc / hipFree of tens of MB is 1-6 ms on this runtime, a sparse fit did ~40 of them (20 ms in
-// its first stage alone).  dev_free parks the block (after the device-wide synchronisation hipFree implies) and
-// dev_malloc hands out a parked block of exactly the requested size; at most DEV_CACHE_BYTES are kept, the oldest
-// blocks go first; agp_context_destroy empties the cache.  Pointers that did not come from dev_malloc are hipFree'd.
-// A block that leaves through any other door (a context pool that is closed, a hand-over between owners) goes through
-// dev_release, so that the table of live blocks never holds an address the runtime may hand out again.
-hipError_t dev_malloc_bytes(void **p, size_t bytes);
-template <class T>
-inline hipError_t dev_malloc(T **p, size_t bytes) { return dev_malloc_bytes(reinterpret_cast<void **>(p), bytes); }
-hipError_t dev_free(void *p);
-// plain hipFree of a block that may have come from dev_malloc (forgets it first; never parks)
-hipError_t dev_release(void *p);
 void dev_cache_trim();
+// `elems` doubles (at least one) of a call's scratch from the cached allocator
+inline hipError_t alloc_doubles(DevMem<double> &m, size_t elems) {
+  return static_cast<hipError_t>(m.alloc_cached(sizeof(double) * (elems ? elems : 1)));
+}
 void launch_symmetrize(hipStream_t s, double *A, long long ld, long long n);
 void launch_transpose_blocks(hipStream_t s, const double *src, double *dst, long long m, long long count);  // reduce.hip
 void launch_copy_lower(hipStream_t s, const double *src, long long ld, long long n, double *dst, int *nan_flag);  // reduce.hip
@@ -105,11 +97,17 @@ void qr_back_solve(hipStream_t s, const double *R, long long ldr, const long lon
                    double *out);
 }  // namespace agp
 
+// holds a fit while its maker builds it: an early return destroys it (its blocks go to the context's slots)
+struct FitDestroy {
+  void operator()(agp_fit *f) const { agp_fit_destroy(f); }
+};
+using FitGuard = std::unique_ptr<agp_fit, FitDestroy>;
+
 struct agp_ldlt {
   agp_context *ctx = nullptr;
   long long n = 0, lda = 0;
-  double *A = nullptr;          // matrixLDLT: L strictly below the diagonal (unit diagonal implied), D on it
-  long long *q_dev = nullptr;   // the permutation the transpositions compose to: (P b)[i] = b[q[i]]
+  agp::DevMem<double> A;        // matrixLDLT: L strictly below the diagonal (unit diagonal implied), D on it
+  agp::DevMem<long long> q_dev; // the permutation the transpositions compose to: (P b)[i] = b[q[i]]
   std::vector<long long> tr;
   std::vector<double> d;        // vectorD (host copy)
   int success = 1;              // Eigen's info() == Success
@@ -117,7 +115,7 @@ struct agp_ldlt {
 
 struct ProgSlot {
   unsigned long long uid = 0;
-  agp::DevProgram *dev = nullptr;
+  agp::DevMem<agp::DevProgram> dev;
 };
 
 struct agp_context_ext {
@@ -137,8 +135,6 @@ struct agp_context_impl : agp_context {
   std::vector<hipEvent_t> gemm_events;
   std::vector<double> gemm_flops;
   hipEvent_t stage_ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  double *partial_ws = nullptr;
-  size_t partial_bytes = 0;
   double gemm_ms_sum = 0., gemm_flop_sum = 0.;
   int gemm_launches = 0;
   // helper contexts (own streams / workspaces) for host threads that work through independent
@@ -151,7 +147,9 @@ int device_program(agp_context *ctx, const agp_kernel *k, const agp::DevProgram 
 int validate_features(const agp_features *f);
 // device view of a feature vector (uploads host data; `copy` forces an owned device copy)
 int to_device(agp_context *ctx, const agp_features *f, bool copy, agp::DeviceFeatures *out);
-int ensure_ws(agp_context *ctx, double **ws, size_t *have, size_t need);
+// grow a scratch buffer of the context that launches on ctx->stream may still read: waits for the stream before the old
+// block goes, and reports a failure in last_error
+int reserve_ws(agp_context *ctx, agp::GrowBuf<double> &ws, size_t need);
 int vector_to_device(agp_context *ctx, const double *src, long long n, int location, double *dst);
 int copy_out(agp_context *ctx, const double *dev, long long count, double *dst, int location);
 int copy_out_2d(agp_context *ctx, const double *dev, long long ld_dev, long long rows, long long cols, double *dst,

@@ -969,27 +969,18 @@ FusedPrep panel_fused_plan(agp_context *ctx, double *invd, long long k_begin, lo
   if (ctx->zpub_cap < k_end) {
     // grow; the old buffer may still be read by kernels in flight on this context's streams: drain them first
     (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->d_zpub) (void)hipFree(ctx->d_zpub);
-    ctx->d_zpub = nullptr;
-    ctx->zpub_cap = 0;
     const long long cap = (k_end + 4095) / 4096 * 4096;
-    if (hipMalloc(&ctx->d_zpub, sizeof(double) * (size_t)cap) != hipSuccess) { (void)hipGetLastError(); return planned; }
-    ctx->zpub_cap = cap;
+    ctx->zpub_cap = ctx->d_zpub.reserve(sizeof(double) * (size_t)cap) == 0 ? cap : 0;
+    if (!ctx->zpub_cap) { (void)hipGetLastError(); return planned; }
   }
   const long long b0 = k_begin / NB, b1 = (k_end + NB - 1) / NB;
   if (want_step && ctx->tune.step_below > 0 && ctx->dpub_cap < b1) {
     (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->d_dpub) (void)hipFree(ctx->d_dpub);
-    ctx->d_dpub = nullptr;
-    ctx->d_rowcnt = nullptr;
-    ctx->dpub_cap = 0;
     const long long cap = (b1 + 31) / 32 * 32;
     // (+ two 64-row counters per diagonal block behind the images: the hand-over of the step launches' row updates)
-    if (hipMalloc(&ctx->d_dpub, sizeof(double) * (size_t)cap * (IMG_DOUBLES + 2)) == hipSuccess) {
-      ctx->dpub_cap = cap;
-      ctx->d_rowcnt = reinterpret_cast<unsigned long long *>(ctx->d_dpub + cap * (long long)IMG_DOUBLES);
-    }
-    else (void)hipGetLastError();
+    ctx->dpub_cap = ctx->d_dpub.reserve(sizeof(double) * (size_t)cap * (IMG_DOUBLES + 2)) == 0 ? cap : 0;
+    ctx->d_rowcnt = ctx->dpub_cap ? reinterpret_cast<unsigned long long *>(ctx->d_dpub + cap * (long long)IMG_DOUBLES) : nullptr;
+    if (!ctx->dpub_cap) (void)hipGetLastError();
   }
   const long long cnt_img = (b1 - b0) * (long long)IMG_DOUBLES, cnt_z = k_end - k_begin;
   if (ctx->d_dpub && ctx->dpub_cap >= b1) {
@@ -1210,23 +1201,23 @@ struct PanelStager {
     StagedPanel out;
     if (!ctx->p32) return out;
     auto take = [&](auto *base) {  // (half the buffer, counted in elements of the copy's type)
-      auto *dst = base + (size_t)(flip ? 1 : 0) * (ctx->p32_bytes / sizeof(*base) / 2);
+      auto *dst = base + (size_t)(flip ? 1 : 0) * (ctx->p32.bytes() / sizeof(*base) / 2);
       flip = !flip;
       return dst;
     };
-    unsigned short *planes = reinterpret_cast<unsigned short *>(ctx->p32);
+    unsigned short *planes = reinterpret_cast<unsigned short *>(ctx->p32.get());
     if (variant == 3) {
       out.ld32 = (rows + 7) / 8 * 8;
       if (out.ld32 % 512 == 0) out.ld32 += 8;
-      if (sizeof(float) * (size_t)out.ld32 * (size_t)K * 2 > ctx->p32_bytes) return out;
-      float *dst = take(ctx->p32);
+      if (sizeof(float) * (size_t)out.ld32 * (size_t)K * 2 > ctx->p32.bytes()) return out;
+      float *dst = take(ctx->p32.get());
       launch_convert_panel_f32(s, P, lda, rows, K, dst, out.ld32);
       out.P32 = dst;
-    } else if (variant == 4 && K % 32 == 0 && 2 * bf16x3_bytes(rows, K) <= ctx->p32_bytes) {
+    } else if (variant == 4 && K % 32 == 0 && 2 * bf16x3_bytes(rows, K) <= ctx->p32.bytes()) {
       unsigned short *dst = take(planes);
       launch_convert_panel_bf16x3(s, P, lda, rows, K, dst);
       out.P16 = dst;
-    } else if (variant == 5 && f16x2_depth_ok(ctx->tune.f16x2, K) && 2 * f16x2_bytes(rows, K) <= ctx->p32_bytes) {
+    } else if (variant == 5 && f16x2_depth_ok(ctx->tune.f16x2, K) && 2 * f16x2_bytes(rows, K) <= ctx->p32.bytes()) {
       unsigned short *dst = take(planes);
       launch_convert_panel_f16x2(s, ctx->tune.f16x2, P, lda, rows, K, rs16 + kend, dst);
       out.P16 = dst;

@@ -10,6 +10,7 @@
 
 #include "../../include/albatross_amd.h"
 #include "cov_eval.h"
+#include "dev_mem.h"      // DevMem, ParkSlot, GrowBuf: the owners of device memory
 #include "factor_plan.h"  // FactorRequest, FactorOutcome, FusedPrep: the arguments of factor_lower
 
 // Wave priority of the panel-chain kernels (s_setprio); the bulk update stays at 0 (the four combinations were measured:
@@ -52,12 +53,11 @@ struct Bf16x3Tuning {
 
 struct DeviceFeatures {
   FeatView v{};
-  void *owned[3] = {nullptr, nullptr, nullptr};
-  DeviceFeatures() = default;
-  DeviceFeatures(const DeviceFeatures &) = delete;
-  DeviceFeatures &operator=(const DeviceFeatures &) = delete;
-  ~DeviceFeatures() { release(); }  // error paths return early: the owned device copies go with the object
-  void release();
+  DevMem<void> owned[3];  // error paths return early: the owned device copies go with the object
+  void release() {
+    for (auto &p : owned) p.reset();
+    v = FeatView{};
+  }
 };
 
 }  // namespace agp
@@ -78,7 +78,7 @@ struct agp_context {
   hipEvent_t ev_a = nullptr, ev_b = nullptr;
   std::vector<hipEvent_t> ev_pool;
   std::string last_error;
-  int *d_flags = nullptr;  // [0] nan flag, [1] first bad pivot + 1
+  agp::DevMem<int> d_flags;  // [0] nan flag, [1] first bad pivot + 1
   int *h_flags = nullptr;  // pinned mirror
   double *d_scalars = nullptr;  // [0] sum log L_ii, [1] z^T z
   double *h_scalars = nullptr;  // pinned mirror
@@ -86,48 +86,37 @@ struct agp_context {
   bool profiling = false;
   double stage_ms[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   // reusable factor workspace (agp_nll re-uses it between tuner steps)
-  double *ws_A = nullptr;
-  size_t ws_A_bytes = 0;
-  double *ws_aux = nullptr;
-  size_t ws_aux_bytes = 0;
-  double *ws_refine = nullptr;  // scratch of the mixed fit's refinement (api.hip: refine_information), kept between fits
-  size_t ws_refine_bytes = 0;
+  agp::GrowBuf<double> ws_A;
+  agp::GrowBuf<double> ws_aux;
+  agp::GrowBuf<double> ws_refine;  // scratch of the mixed fit's refinement (api.hip: refine_information), kept between fits
   // one cached factor allocation (agp_fit_destroy parks its N x N buffer here;
   // the next agp_fit_create of the same size takes it instead of hipMalloc)
-  double *pool_A = nullptr;
-  size_t pool_A_bytes = 0;
+  agp::ParkSlot pool_A;
   // ... and one cached exact-covariance buffer of the mixed-precision fit (its CG refinement multiplies with K itself)
-  double *pool_K = nullptr;
-  size_t pool_K_bytes = 0;
+  agp::ParkSlot pool_K;
   // mixed-precision fits: two alternating fp32 copies of the current panel (rows x 512 each)
-  float *p32 = nullptr;
-  size_t p32_bytes = 0;
-  double *f16_scales = nullptr;  // fp16 x 2 products (gemm_f16x2.hip): row scales r and 1 / r, f16_scales_n doubles each
+  agp::GrowBuf<float> p32;
+  agp::GrowBuf<double> f16_scales;  // fp16 x 2 products (gemm_f16x2.hip): row scales r and 1 / r, f16_scales_n doubles each
   long long f16_scales_n = 0;
   // ... and the fp32 copy of the factor that preconditions their refinement
-  float *pool_L32 = nullptr;
-  size_t pool_L32_bytes = 0;
+  agp::ParkSlot pool_L32;
   // ... and one cached block of a fit's small buffers (agp_fit::aux_base)
-  double *pool_aux = nullptr;
-  size_t pool_aux_bytes = 0;
+  agp::ParkSlot pool_aux;
   // scratch of the sharded fit (agp_sharded_fit_destroy parks it here, like pool_A)
-  double *pool_shard = nullptr;
-  size_t pool_shard_bytes = 0;
+  agp::ParkSlot pool_shard;
   // the n-sized buffers of a sparse GP fit (K_uf / W, P / Q1^T, split-K slabs): grow-only, kept between fits - a tuner
   // re-fits the same shapes, and hipMalloc / hipFree of several GB per call costs more than some of the stages
-  double *pool_sparse = nullptr;
-  size_t pool_sparse_bytes = 0;
+  agp::GrowBuf<double> pool_sparse;
   // ... and one cached slab of agp_fit_create_batch (released by the last fit of a batch)
-  double *pool_batch = nullptr;
-  size_t pool_batch_bytes = 0;
+  agp::ParkSlot pool_batch;
   // fused panel kernel (chol.hip: panel_fused_kernel): the slots through which a diagonal block's z_b reaches the
   // workgroups solving the rows below in the same launch (one per matrix row, sentinel-filled per factorisation: what has
   // been filled for which tile images is the FusedPrep that panel_fused_plan returns, not kept here)
-  double *d_zpub = nullptr;
+  agp::GrowBuf<double> d_zpub;
   long long zpub_cap = 0;
   // ... and the slots through which an UPDATED diagonal block reaches the workgroup that factors it (one tile image
   // per diagonal block, like invd; only allocated when the update-ahead panel kernel is in use)
-  double *d_dpub = nullptr;
+  agp::GrowBuf<double> d_dpub;
   long long dpub_cap = 0;  // diagonal blocks
   int cus = 256;  // CUs of the device (hipDeviceAttributeMultiprocessorCount)
   long long step_slots = 0;  // workgroups of the panel step kernel the device holds at once (chol.hip: step_slots)
@@ -162,7 +151,7 @@ struct agp_context {
   void *h_stage = nullptr;
   size_t h_stage_bytes = 0;
   static constexpr long long HEADCNT_WORDS = 256;
-  unsigned long long *d_headcnt = nullptr;
+  agp::DevMem<unsigned long long> d_headcnt;
   // What the last factorisation / fit of this context ran: host-side only, filled by factor_lower from each planned step
   // it has carried out (factor_plan.h: OuterStep), at the panel launches of panel_phase (chol.hip) and by fit_create_impl
   // (api.hip), read by the tests through agp_debug_schedule (debug_api.hip,
@@ -201,7 +190,7 @@ struct agp_context {
   // sharded fit, device-side pacing (shard_hip.hip: HipShardOps): one flag per schedule event + probe flags in device
   // memory, their sequence numbers (monotonic over the life of the context), and the pacing mode (-1: not decided yet)
   hipStream_t stream_comm = nullptr;  // queue of the collectives (created by the first sharded call)
-  unsigned long long *shard_flags = nullptr;
+  agp::DevMem<unsigned long long> shard_flags;
   unsigned long long shard_seq[16] = {};
   unsigned long long shard_probe_seq = 0;
   int shard_host_pacing = -1;
@@ -211,7 +200,7 @@ struct agp_context {
 // agp_fit_create_batch: the fits of one batch are slices of ONE device allocation (the batched kernels need constant
 // strides between the problems); it goes when the last of them is destroyed
 struct agp_fit_slab {
-  double *base = nullptr;
+  agp::DevMem<double> base;
   size_t bytes = 0;
   int refs = 0;
 };
@@ -229,11 +218,16 @@ struct agp_fit {
   double *winv = nullptr;   // (n/NB) inverted NB x NB diagonal blocks
   double *alpha = nullptr;  // information vector K^-1 y
   double *z = nullptr;      // L^-1 y
-  // agp_fit_create makes invd / winv / alpha / z slices of ONE allocation (aux_base, aux_bytes), which agp_fit_destroy
-  // parks in the context like the factor's buffer: four hipMalloc + four hipFree per fit less.  nullptr: the four are
-  // allocations of their own (every other maker of an agp_fit).
-  double *aux_base = nullptr;
+  // A, invd, winv, alpha and z above are what the kernels read.  What the fit OWNS of them, every maker says here, and
+  // agp_fit_destroy never asks which regime it is in: it offers own_A and aux_base to the context's slots and deletes.
+  //   own_A: the factor's block (empty for a fit of a batch, whose blocks are slices of slab->base)
+  //   aux_base: agp_fit_create makes invd / winv / alpha / z (and the training features) slices of ONE allocation, which
+  //             parks in the context like the factor's buffer: four hipMalloc + four hipFree per fit less
+  //   own_part: invd / winv / alpha / z where they are allocations of their own (every other maker of a single fit)
+  agp::DevMem<double> own_A;
+  agp::DevMem<double> aux_base;
   size_t aux_bytes = 0;
+  agp::DevMem<double> own_part[4];
   agp::DeviceFeatures train;
   double log_det = 0.;
   int64_t failed_pivot = -1;
@@ -251,7 +245,7 @@ struct agp_fit {
 
 #define AGP_HIP_CHECK(ctx, expr)                                              \
   do {                                                                        \
-    hipError_t _e = (expr);                                                   \
+    const hipError_t _e = static_cast<hipError_t>(expr);                      \
     if (_e != hipSuccess) {                                                   \
       if (ctx) {                                                              \
         (ctx)->last_error = std::string(#expr) + ": " + hipGetErrorString(_e); \

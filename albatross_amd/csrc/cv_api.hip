@@ -23,12 +23,9 @@ namespace {
 
 struct GroupWork {
   agp_context *ctx = nullptr;
-  double *R = nullptr, *G = nullptr, *B = nullptr, *tmp = nullptr;
-  long long *idx = nullptr;
+  DevMem<double> R, G, B, tmp;
+  DevMem<long long> idx;
   long long n = 0, ldr = 0, ldg = 0, ldb = 0, mmax = 0;
-  ~GroupWork() {
-    (void)hipFree(R); (void)hipFree(G); (void)hipFree(B); (void)hipFree(tmp); (void)hipFree(idx);
-  }
 };
 
 int group_work_init(agp_context *ctx, const agp_fit *fit, int64_t n_groups, const int64_t *offsets,
@@ -49,11 +46,11 @@ int group_work_init(agp_context *ctx, const agp_fit *fit, int64_t n_groups, cons
   w->ctx = ctx; w->n = n; w->mmax = mmax;
   if (total == 0) return AGP_OK;
   w->ldr = factor_ld(n); w->ldg = round_up(n, 2); w->ldb = factor_ld(mmax);
-  AGP_HIP_CHECK(ctx, hipMalloc(&w->R, sizeof(double) * (size_t)w->ldr * (size_t)n));
-  AGP_HIP_CHECK(ctx, hipMalloc(&w->G, sizeof(double) * (size_t)w->ldg * (size_t)mmax));
-  AGP_HIP_CHECK(ctx, hipMalloc(&w->B, sizeof(double) * (size_t)w->ldb * (size_t)mmax));
-  AGP_HIP_CHECK(ctx, hipMalloc(&w->tmp, sizeof(double) * (size_t)(4 * round_up(mmax, 2) + 2 * round_up(n, 2))));
-  AGP_HIP_CHECK(ctx, hipMalloc(&w->idx, sizeof(long long) * (size_t)total));
+  AGP_HIP_CHECK(ctx, w->R.alloc_plain(sizeof(double) * (size_t)w->ldr * (size_t)n));
+  AGP_HIP_CHECK(ctx, w->G.alloc_plain(sizeof(double) * (size_t)w->ldg * (size_t)mmax));
+  AGP_HIP_CHECK(ctx, w->B.alloc_plain(sizeof(double) * (size_t)w->ldb * (size_t)mmax));
+  AGP_HIP_CHECK(ctx, w->tmp.alloc_plain(sizeof(double) * (size_t)(4 * round_up(mmax, 2) + 2 * round_up(n, 2))));
+  AGP_HIP_CHECK(ctx, w->idx.alloc_plain(sizeof(long long) * (size_t)total));
   static_assert(sizeof(long long) == sizeof(int64_t), "index width");
   AGP_HIP_CHECK(ctx, hipMemcpyAsync(w->idx, indices, sizeof(long long) * (size_t)total, hipMemcpyHostToDevice, ctx->stream));
   hipStream_t s = ctx->stream;
@@ -84,14 +81,10 @@ int group_inverse_block(GroupWork *w, const int64_t *indices, long long off, lon
 // Groups of one size use slabs of that size; ragged groups of comparable size are padded to the largest
 // one (padding columns of G are zero, the padded diagonal of B_g is set to one: B_pad = [B 0; 0 I]).
 struct LockStep {
-  double *Gall = nullptr, *Ball = nullptr, *img = nullptr, *Q = nullptr, *vecs = nullptr, *packed = nullptr;
-  long long *meta = nullptr;  // idx_pad (count * smax) | off (count + 1) | boff (count + 1)
+  DevMem<double> Gall, Ball, img, Q, vecs, packed;
+  DevMem<long long> meta;  // idx_pad (count * smax) | off (count + 1) | boff (count + 1)
   long long smax = 0, count = 0, total = 0, padded = 0, elems = 0;
   const long long *idx_pad = nullptr, *off_d = nullptr, *boff_d = nullptr;
-  ~LockStep() {
-    (void)hipFree(Gall); (void)hipFree(Ball); (void)hipFree(img); (void)hipFree(Q); (void)hipFree(vecs); (void)hipFree(packed);
-    (void)hipFree(meta);
-  }
 };
 
 // true when the lock-step path applies: >= 2 non-empty groups whose padded size stays within 3x
@@ -119,7 +112,7 @@ bool lock_step_plan(GroupWork *w, int64_t n_groups, const int64_t *offsets, cons
   boff[n_groups] = e;
   u->elems = e;
   agp_context *ctx = w->ctx;
-  if (hipMalloc(&u->meta, sizeof(long long) * meta.size()) != hipSuccess) return false;
+  if (u->meta.alloc_plain(sizeof(long long) * meta.size()) != 0) return false;
   if (hipMemcpy(u->meta, meta.data(), sizeof(long long) * meta.size(), hipMemcpyHostToDevice) != hipSuccess) return false;
   (void)ctx;
   u->idx_pad = u->meta;
@@ -133,15 +126,15 @@ int lock_step_inverse_blocks(GroupWork *w, LockStep *u) {
   agp_context *ctx = w->ctx;
   hipStream_t s = ctx->stream;
   const long long m = u->smax, ldb = factor_ld(m);
-  AGP_HIP_CHECK(ctx, hipMalloc(&u->Gall, sizeof(double) * (size_t)w->ldg * (size_t)u->padded));
-  AGP_HIP_CHECK(ctx, hipMalloc(&u->Ball, sizeof(double) * (size_t)ldb * (size_t)u->padded));
+  AGP_HIP_CHECK(ctx, u->Gall.alloc_plain(sizeof(double) * (size_t)w->ldg * (size_t)u->padded));
+  AGP_HIP_CHECK(ctx, u->Ball.alloc_plain(sizeof(double) * (size_t)ldb * (size_t)u->padded));
   launch_gather_cols(s, w->R, w->ldr, u->idx_pad, u->padded, 0, w->n, u->Gall, w->ldg);
   AGP_HIP_CHECK(ctx, hipMemsetAsync(u->Ball, 0, sizeof(double) * (size_t)ldb * (size_t)u->padded, s));
   launch_gemm_nt_sub_batched(s, u->Ball, ldb, ldb * m, u->Gall, w->ldg, true, m * w->ldg, u->Gall, w->ldg, true, m * w->ldg, m,
                              m, w->n, false, u->count);
   launch_axpby(s, ldb * u->padded, -1.0, u->Ball, 0.0, nullptr, u->Ball);
   if (u->padded != u->total) launch_pad_identity(s, u->Ball, ldb, ldb * m, u->off_d, m, u->count);
-  (void)hipFree(u->Gall); u->Gall = nullptr;
+  u->Gall.reset();  // (here: the largest block of the path, dead from now on)
   AGP_HIP_CHECK(ctx, hipGetLastError());
   return AGP_OK;
 }
@@ -151,7 +144,7 @@ int copy_out_blocks(agp_context *ctx, LockStep *u, const double *slabs, long lon
   const long long m = u->smax;
   if (u->padded == u->total)  // one size: all columns of all slabs are ld apart, ONE pitched copy
     return copy_out_2d(ctx, slabs, ld, m, m * u->count, dst, m, location);
-  if (!u->packed) AGP_HIP_CHECK(ctx, hipMalloc(&u->packed, sizeof(double) * (size_t)u->elems));
+  if (!u->packed) AGP_HIP_CHECK(ctx, u->packed.alloc_plain(sizeof(double) * (size_t)u->elems));
   launch_compact_blocks(ctx->stream, slabs, ld, ld * m, u->off_d, u->boff_d, m, u->count, u->packed);
   return copy_out(ctx, u->packed, u->elems, dst, location);
 }
@@ -208,9 +201,9 @@ int agp_held_out_predictions(agp_context *ctx, const agp_fit *fit, const double 
     const long long m = u.smax, count = u.count, padded = u.padded;
     const long long ldb = factor_ld(m), nblk_b = (m + NB - 1) / NB, stride_B = ldb * m, stride_I = nblk_b * (36 * MB * MB);
     if ((st = lock_step_inverse_blocks(&w, &u)) != AGP_OK) return st;
-    AGP_HIP_CHECK(ctx, hipMalloc(&u.img, sizeof(double) * ((size_t)stride_I * (size_t)count + (size_t)round_up(count, 2))));
-    AGP_HIP_CHECK(ctx, hipMalloc(&u.Q, sizeof(double) * (size_t)stride_B * (size_t)count));
-    AGP_HIP_CHECK(ctx, hipMalloc(&u.vecs, sizeof(double) * 4 * (size_t)round_up(padded, 2)));
+    AGP_HIP_CHECK(ctx, u.img.alloc_plain(sizeof(double) * ((size_t)stride_I * (size_t)count + (size_t)round_up(count, 2))));
+    AGP_HIP_CHECK(ctx, u.Q.alloc_plain(sizeof(double) * (size_t)stride_B * (size_t)count));
+    AGP_HIP_CHECK(ctx, u.vecs.alloc_plain(sizeof(double) * 4 * (size_t)round_up(padded, 2)));
     double *logsum = u.img + (size_t)stride_I * (size_t)count;
     double *vz = u.vecs, *xs = vz + round_up(padded, 2), *outv = xs + round_up(padded, 2), *compact = outv + round_up(padded, 2);
     AGP_HIP_CHECK(ctx, hipMemsetAsync(logsum, 0, sizeof(double) * (size_t)round_up(count, 2), s));
@@ -258,7 +251,7 @@ int agp_held_out_predictions(agp_context *ctx, const agp_fit *fit, const double 
     if (st == AGP_OK && (variance || joint)) {
       // R_B = L_B^-1 ; inverse = R_B^T R_B  (inverse_diagonal :183 / inverse :192)
       const long long ldq = factor_ld(m);
-      st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, sizeof(double) * 2 * (size_t)ldq * (size_t)m);
+      st = reserve_ws(ctx, ctx->ws_aux, sizeof(double) * 2 * (size_t)ldq * (size_t)m);
       if (st == AGP_OK) {
         double *Q = ctx->ws_aux, *J = Q + (size_t)ldq * (size_t)m;
         launch_set_identity(s, Q, ldq, m);

@@ -655,7 +655,8 @@ static XcdOrder xcd_order(int ntr, long long full) {
     for (size_t q = 0; q < per[x].size(); ++q) table[q * XCDS + x] = per[x][q];
   XcdOrder o;
   o.len = (long long)table.size();
-  if (hipMalloc(&o.dev, sizeof(int) * table.size()) != hipSuccess ||
+  // (kept for the life of the process: the cache above is its owner and is never emptied)
+  if (dev_malloc_plain_bytes(reinterpret_cast<void **>(&o.dev), sizeof(int) * table.size()) != 0 ||
       hipMemcpy(o.dev, table.data(), sizeof(int) * table.size(), hipMemcpyHostToDevice) != hipSuccess) {
     (void)hipGetLastError();
     o.dev = nullptr; o.len = 0;

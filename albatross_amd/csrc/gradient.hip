@@ -654,8 +654,8 @@ static int gradient_setup(agp_context_impl *ctx, const agp_kernel *k, const agp_
   WsLayout size_A, size_aux;
   carve_fit(size_A, geo);
   carve_aux(size_aux);
-  if ((st = ensure_ws(ctx, &ctx->ws_A, &ctx->ws_A_bytes, size_A.bytes())) != AGP_OK) return st;
-  if ((st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, size_aux.bytes())) != AGP_OK) return st;
+  if ((st = reserve_ws(ctx, ctx->ws_A, size_A.bytes())) != AGP_OK) return st;
+  if ((st = reserve_ws(ctx, ctx->ws_aux, size_aux.bytes())) != AGP_OK) return st;
   WsLayout ws_A(ctx->ws_A), ws_aux(ctx->ws_aux);
   const FitRegions r = carve_fit(ws_A, geo);
   const GradientAuxRegions a = carve_aux(ws_aux);
@@ -1124,8 +1124,8 @@ static int gradient_batch_begin(agp_context_impl *ctx, int count, const agp_kern
   WsLayout size_A, size_aux;
   carve_gradient_batch(size_A, geo, y_var != nullptr, fused_panels);
   carve_aux(size_aux);
-  if ((st = ensure_ws(ctx, &ctx->ws_A, &ctx->ws_A_bytes, size_A.bytes())) != AGP_OK) return st;
-  if ((st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, size_aux.bytes())) != AGP_OK) return st;
+  if ((st = reserve_ws(ctx, ctx->ws_A, size_A.bytes())) != AGP_OK) return st;
+  if ((st = reserve_ws(ctx, ctx->ws_aux, size_aux.bytes())) != AGP_OK) return st;
   WsLayout ws_A(ctx->ws_A), ws_aux(ctx->ws_aux);
   const GradientBatchRegions r = carve_gradient_batch(ws_A, geo, y_var != nullptr, fused_panels);
   const GradientBatchAuxRegions a = carve_aux(ws_aux);

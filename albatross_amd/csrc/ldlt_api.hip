@@ -15,8 +15,6 @@ extern "C" {
 void agp_ldlt_destroy(agp_ldlt *f) {
   if (!f) return;
   if (f->ctx) (void)hipSetDevice(f->ctx->device);
-  if (f->A) (void)hipFree(f->A);
-  if (f->q_dev) (void)hipFree(f->q_dev);
   delete f;
 }
 
@@ -31,36 +29,28 @@ int agp_ldlt_create(agp_context *ctx, const double *K, int64_t n, int64_t ld, in
   agp_ldlt *f = new (std::nothrow) agp_ldlt();
   if (!f) return AGP_ERR_INVALID_ARGUMENT;
   f->ctx = ctx; f->n = n; f->lda = round_up(n, 2);
-#define LD_HIP(expr)                                                                     \
-  do {                                                                                   \
-    hipError_t _e = (expr);                                                              \
-    if (_e != hipSuccess) {                                                              \
-      ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(_e);               \
-      agp_ldlt_destroy(f);                                                               \
-      return AGP_ERR_HIP;                                                                \
-    }                                                                                    \
-  } while (0)
-  LD_HIP(hipMalloc(&f->A, sizeof(double) * (size_t)f->lda * (size_t)n));
-  LD_HIP(hipMalloc(&f->q_dev, sizeof(long long) * (size_t)n));
+  std::unique_ptr<agp_ldlt, void (*)(agp_ldlt *)> guard(f, agp_ldlt_destroy);  // an early return destroys it
+  AGP_HIP_CHECK(ctx, f->A.alloc_plain(sizeof(double) * (size_t)f->lda * (size_t)n));
+  AGP_HIP_CHECK(ctx, f->q_dev.alloc_plain(sizeof(long long) * (size_t)n));
   // bring the triangle in (lower as given, or the transpose of the upper one)
   const double *src = K;
   if (location == AGP_HOST) {
     const size_t bytes = sizeof(double) * ((size_t)ld * (size_t)(n - 1) + (size_t)n);
-    int st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, sizeof(double) * (size_t)ld * (size_t)n);
-    if (st != AGP_OK) { agp_ldlt_destroy(f); return st; }
-    LD_HIP(hipMemcpyAsync(ctx->ws_aux, K, bytes, hipMemcpyHostToDevice, s));
+    int st = reserve_ws(ctx, ctx->ws_aux, sizeof(double) * (size_t)ld * (size_t)n);
+    if (st != AGP_OK) return st;
+    AGP_HIP_CHECK(ctx, hipMemcpyAsync(ctx->ws_aux, K, bytes, hipMemcpyHostToDevice, s));
     src = ctx->ws_aux;
   }
   if (uplo == 0)
-    LD_HIP(hipMemcpy2DAsync(f->A, sizeof(double) * (size_t)f->lda, src, sizeof(double) * (size_t)ld, sizeof(double) * (size_t)n,
+    AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(f->A, sizeof(double) * (size_t)f->lda, src, sizeof(double) * (size_t)ld, sizeof(double) * (size_t)n,
                             (size_t)n, hipMemcpyDeviceToDevice, s));
   else
     launch_upper_to_lower(s, src, ld, f->A, f->lda, n);
   // the transposition sequence follows from the initial diagonal alone (see ldlt.hip)
   f->d.resize((size_t)n);
-  LD_HIP(hipMemcpy2DAsync(f->d.data(), sizeof(double), f->A, sizeof(double) * (size_t)(f->lda + 1), sizeof(double), (size_t)n,
+  AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(f->d.data(), sizeof(double), f->A, sizeof(double) * (size_t)(f->lda + 1), sizeof(double), (size_t)n,
                           hipMemcpyDeviceToHost, s));
-  LD_HIP(hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
   f->tr.resize((size_t)n);
   {
     std::vector<double> d = f->d;
@@ -78,31 +68,27 @@ int agp_ldlt_create(agp_context *ctx, const double *K, int64_t n, int64_t ld, in
   std::vector<long long> q((size_t)n);
   for (long long i = 0; i < n; ++i) q[(size_t)i] = i;
   for (long long k = 0; k < n; ++k) std::swap(q[(size_t)k], q[(size_t)f->tr[(size_t)k]]);
-  LD_HIP(hipMemcpyAsync(f->q_dev, q.data(), sizeof(long long) * (size_t)n, hipMemcpyHostToDevice, s));
-  LD_HIP(hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(f->q_dev, q.data(), sizeof(long long) * (size_t)n, hipMemcpyHostToDevice, s));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
   // scratch: temp (n) | scal (2) | info (2 ints) | dotacc (n) | T panel (n x 32)
-  double *scratch = nullptr;
-  LD_HIP(hipMalloc(&scratch, sizeof(double) * (size_t)(n + 4 + n + 32 * n)));
+  DevMem<double> scratch;
+  AGP_HIP_CHECK(ctx, scratch.alloc_plain(sizeof(double) * (size_t)(n + 4 + n + 32 * n)));
   double *scal = scratch + n;
   int *info = reinterpret_cast<int *>(scal + 2);
   double *dotacc = scratch + n + 4, *Tpanel = dotacc + n;
   const int init_info[2] = {0, 1};
   hipError_t e = hipMemcpyAsync(info, init_info, sizeof(init_info), hipMemcpyHostToDevice, s);
-  double *Ap = nullptr;
+  DevMem<double> Ap;
   if (e == hipSuccess && n >= 64) {
     // permute once (Ap = P A P^T), then the blocked factorisation: same arithmetic, ~n / 32 * 3 launches
-    e = hipMalloc(&Ap, sizeof(double) * (size_t)f->lda * (size_t)n);
+    e = static_cast<hipError_t>(Ap.alloc_plain(sizeof(double) * (size_t)f->lda * (size_t)n));
     if (e == hipSuccess) {
       launch_symmetrize(s, f->A, f->lda, n);
       ldlt_permute_sym(s, f->A, f->lda, f->q_dev, n, Ap, f->lda);
       ldlt_factor_blocked(s, Ap, f->lda, n, Tpanel, dotacc, info);
       e = hipStreamSynchronize(s);
     }
-    if (e == hipSuccess) {
-      (void)hipFree(f->A);
-      f->A = Ap;
-      Ap = nullptr;
-    }
+    if (e == hipSuccess) f->A = std::move(Ap);  // (the unpermuted copy is freed here)
   } else if (e == hipSuccess) {
     ldlt_factor(s, f->A, f->lda, n, f->tr.data(), scratch, info, scal);
   }
@@ -116,16 +102,12 @@ int agp_ldlt_create(agp_context *ctx, const double *K, int64_t n, int64_t ld, in
     if (e == hipSuccess) e = hipGetLastError();
     f->success = h_info[1];
   }
-  if (Ap) (void)hipFree(Ap);
-  (void)hipFree(scratch);
   if (e != hipSuccess) {
     ctx->last_error = hipGetErrorString(e);
-    agp_ldlt_destroy(f);
     return AGP_ERR_HIP;
   }
-#undef LD_HIP
   if (success) *success = f->success;
-  *out = f;
+  *out = guard.release();
   return AGP_OK;
 }
 
@@ -134,7 +116,7 @@ int agp_ldlt_solve(agp_context *ctx, const agp_ldlt *f, const double *rhs, int64
   if (nrhs == 0) return AGP_OK;
   AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const long long n = f->n, ldw = round_up(n, 2);
-  int st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, sizeof(double) * 2 * (size_t)ldw * (size_t)nrhs);
+  int st = reserve_ws(ctx, ctx->ws_aux, sizeof(double) * 2 * (size_t)ldw * (size_t)nrhs);
   if (st != AGP_OK) return st;
   double *W = ctx->ws_aux, *R = W + (size_t)ldw * (size_t)nrhs;
   const hipMemcpyKind kind = location == AGP_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
@@ -150,7 +132,7 @@ int agp_ldlt_sqrt_solve(agp_context *ctx, const agp_ldlt *f, const double *rhs, 
   if (nrhs == 0) return AGP_OK;
   AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const long long n = f->n, ldw = round_up(n, 2);
-  int st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, sizeof(double) * 2 * (size_t)ldw * (size_t)nrhs);
+  int st = reserve_ws(ctx, ctx->ws_aux, sizeof(double) * 2 * (size_t)ldw * (size_t)nrhs);
   if (st != AGP_OK) return st;
   double *W = ctx->ws_aux, *R = W + (size_t)ldw * (size_t)nrhs;
   const hipMemcpyKind kind = location == AGP_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;

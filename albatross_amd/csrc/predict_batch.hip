@@ -324,11 +324,11 @@ int agp_predict_batch(agp_context *c, int count, const agp_kernel *const *kernel
   const size_t item_bytes = (sizeof(PredictBatchItem) * (size_t)count + 15) / 16 * 16;
   const size_t gram_bytes = mode == 2 ? (gram_batch_table_bytes(count) + 15) / 16 * 16 : 0;
   const size_t range_off = item_bytes + gram_bytes, range_bytes = phantoms.any() ? phantoms.bytes() : 0;
-  void *tables = nullptr;
+  DevMem<void> tables;
   char *pinned = nullptr;
   std::vector<PredictBatchItem> pageable;
   if (any_lockstep) {
-    if (dev_malloc(&tables, range_off + range_bytes) != hipSuccess) {
+    if (tables.alloc_cached(range_off + range_bytes) != 0) {
       (void)hipGetLastError();
       ctx->last_error = "agp_predict_batch: descriptor tables";
       return AGP_ERR_HIP;
@@ -336,9 +336,8 @@ int agp_predict_batch(agp_context *c, int count, const agp_kernel *const *kernel
     pinned = static_cast<char *>(host_stage(ctx, range_off + range_bytes));
     if (!pinned) pageable.resize((size_t)count);
   }
-  struct FreeTables { void *p; ~FreeTables() { if (p) (void)dev_free(p); } } free_tables{tables};
   PredictBatchItem *h_items = pinned ? reinterpret_cast<PredictBatchItem *>(pinned) : pageable.data();
-  PredictBatchItem *d_items = static_cast<PredictBatchItem *>(tables);
+  PredictBatchItem *d_items = static_cast<PredictBatchItem *>(tables.get());
   const size_t gram_item = mode == 2 ? gram_batch_table_bytes(1) : 0;
 
   int st = AGP_OK;
@@ -351,7 +350,7 @@ int agp_predict_batch(agp_context *c, int count, const agp_kernel *const *kernel
     char *src = pinned ? pinned + range_off : nullptr;
     if (!src) { pageable_ranges.resize(range_bytes); src = pageable_ranges.data(); }
     phantoms.write(src);
-    if (hipMemcpyAsync(static_cast<char *>(tables) + range_off, src, range_bytes, hipMemcpyHostToDevice, s) != hipSuccess) {
+    if (hipMemcpyAsync(static_cast<char *>(tables.get()) + range_off, src, range_bytes, hipMemcpyHostToDevice, s) != hipSuccess) {
       ctx->last_error = "agp_predict_batch: phantom range table";
       return finish(AGP_ERR_HIP);
     }
@@ -362,8 +361,7 @@ int agp_predict_batch(agp_context *c, int count, const agp_kernel *const *kernel
   // that share their arrays share the copy) with ONE synchronisation behind the uploads, as agp_fit_create_batch stages
   // its training features: no allocation and no synchronisation per problem.
   std::vector<FeatView> yv((size_t)count);
-  void *xbuf = nullptr;
-  struct FreeStage { void **p; ~FreeStage() { if (*p) (void)dev_free(*p); } } free_stage{&xbuf};
+  DevMem<double> xbuf;
   if (any_lockstep) {
     auto same_arrays = [&](int a, int b) {
       return xs[a]->coords == xs[b]->coords && xs[a]->scales == xs[b]->scales && xs[a]->eq_id == xs[b]->eq_id && xs[a]->dim == xs[b]->dim &&
@@ -375,13 +373,12 @@ int agp_predict_batch(agp_context *c, int count, const agp_kernel *const *kernel
       for (const Run &r : runs)
         for (int i = 0; r.count > 1 && i < r.count; ++i)
           if (i == 0 || !same_arrays(r.first + i, r.first + i - 1)) total += words(xs[r.first + i]);
-    if (total > 0 && dev_malloc(&xbuf, sizeof(double) * total) != hipSuccess) {
+    if (total > 0 && xbuf.alloc_cached(sizeof(double) * total) != 0) {
       (void)hipGetLastError();
-      xbuf = nullptr;
       ctx->last_error = "agp_predict_batch: test feature staging";
       return AGP_ERR_HIP;
     }
-    double *cur = static_cast<double *>(xbuf);
+    double *cur = xbuf;
     for (const Run &r : runs)
       for (int i = 0; r.count > 1 && i < r.count; ++i) {
         const int b = r.first + i;
@@ -440,7 +437,7 @@ int agp_predict_batch(agp_context *c, int count, const agp_kernel *const *kernel
       const size_t v_elems = mode == 0 ? 0 : (size_t)ldv * (size_t)m, p_elems = mode == 0 ? 0 : (mode == 1 ? (size_t)ldc : (size_t)ldc * (size_t)m);
       const bool stage_out = out_location == AGP_HOST;
       const size_t so_elems = stage_out ? (size_t)ldc + (mode == 0 ? 0 : (size_t)round_up(second_elems, 2)) : 0;
-      if ((st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, sizeof(double) * (size_t)cnt * (v_elems + p_elems + so_elems))) != AGP_OK)
+      if ((st = reserve_ws(ctx, ctx->ws_aux, sizeof(double) * (size_t)cnt * (v_elems + p_elems + so_elems))) != AGP_OK)
         return finish(st);
       double *V = ctx->ws_aux, *prior = V + (size_t)cnt * v_elems, *mean_s = prior + (size_t)cnt * p_elems;
       double *second_s = mean_s + (size_t)cnt * (size_t)ldc;
@@ -500,7 +497,7 @@ int agp_predict_batch(agp_context *c, int count, const agp_kernel *const *kernel
         bool chunk_phantoms = false;
         for (long long i = 0; i < cnt && !chunk_phantoms; ++i) chunk_phantoms = !fits[first + (int)i]->phantom.empty();
         if (chunk_phantoms)
-          launch_zero_row_ranges(s, static_cast<const char *>(tables) + range_off, count, first, cnt, V, (long long)v_elems, ldv, m);
+          launch_zero_row_ranges(s, static_cast<const char *>(tables.get()) + range_off, count, first, cnt, V, (long long)v_elems, ldv, m);
         // mean = cross_cov^T information (gp.hpp:82-85), then V = L^-1 K* (gp.hpp:96,111)
         hipLaunchKernelGGL((colvec_batch_kernel<false>), dim3((unsigned)m, (unsigned)cnt), dim3(256), 0, s, tab, ldv, rn);
         forward_solve_mat_batched(s, f0->A + (size_t)p0 * (size_t)r.dA, r.dA, rn, f0->lda, f0->invd + (size_t)p0 * (size_t)r.dI, r.dI, V,
@@ -524,7 +521,7 @@ int agp_predict_batch(agp_context *c, int count, const agp_kernel *const *kernel
               outs[(size_t)i] = h_items[(size_t)(first + i)].prior;
             }
             gram_done = launch_gram_batch(s, cnt, hprogs.data(), &yv[(size_t)first], outs.data(), ldc, nullptr, nullptr,
-                                          static_cast<char *>(tables) + item_bytes + gram_item * (size_t)first,
+                                          static_cast<char *>(tables.get()) + item_bytes + gram_item * (size_t)first,
                                           pinned ? pinned + item_bytes + gram_item * (size_t)first : nullptr);
           }
           for (long long i = 0; i < cnt && !gram_done; ++i) {

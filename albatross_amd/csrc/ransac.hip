@@ -485,8 +485,8 @@ int agp_ransac_score_trials(agp_context *c, const agp_kernel *k, const agp_featu
     carve_chunk(w, batch_geometry(class_size[ci], cnt));
     chunk_bytes = std::max(chunk_bytes, w.bytes());
   }
-  if ((st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, size_fixed.bytes())) != AGP_OK) return st;
-  if ((st = ensure_ws(ctx, &ctx->ws_A, &ctx->ws_A_bytes, chunk_bytes)) != AGP_OK) return st;
+  if ((st = reserve_ws(ctx, ctx->ws_aux, size_fixed.bytes())) != AGP_OK) return st;
+  if ((st = reserve_ws(ctx, ctx->ws_A, chunk_bytes)) != AGP_OK) return st;
   WsLayout ws_fixed(ctx->ws_aux);
   const FixedRegions f = fixed(ws_fixed);
   hipStream_t s = ctx->stream;

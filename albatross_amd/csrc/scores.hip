@@ -280,33 +280,24 @@ __global__ void add_diagonal_kernel(double *__restrict__ A, long long lda, long 
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-struct DevBuf {  // device scratch of one call (parked in the allocation cache when it goes)
-  double *p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf &) = delete;
-  DevBuf &operator=(const DevBuf &) = delete;
-  ~DevBuf() { if (p) (void)dev_free(p); }
-  hipError_t alloc(size_t elems) { return dev_malloc(&p, sizeof(double) * (elems ? elems : 1)); }
-};
-
 // `src` (n doubles at `location`, may be nullptr) as a device pointer: itself, or a copy in `buf`
-int device_vector(agp_context *ctx, const double *src, long long n, int location, DevBuf *buf, const double **out) {
+int device_vector(agp_context *ctx, const double *src, long long n, int location, DevMem<double> *buf, const double **out) {
   *out = src;
   if (!src || location == AGP_DEVICE) return AGP_OK;
-  AGP_HIP_CHECK(ctx, buf->alloc((size_t)n));
-  *out = buf->p;
-  return vector_to_device(ctx, src, n, AGP_HOST, buf->p);
+  AGP_HIP_CHECK(ctx, alloc_doubles(*buf, (size_t)n));
+  *out = buf->get();
+  return vector_to_device(ctx, src, n, AGP_HOST, buf->get());
 }
 
 // the same for a rows x cols matrix with leading dimension ld; the copy keeps ld
-int device_matrix(agp_context *ctx, const double *src, long long rows, long long cols, long long ld, int location, DevBuf *buf,
+int device_matrix(agp_context *ctx, const double *src, long long rows, long long cols, long long ld, int location, DevMem<double> *buf,
                   const double **out) {
   *out = src;
   if (!src || location == AGP_DEVICE) return AGP_OK;
   const size_t elems = (size_t)ld * (size_t)(cols - 1) + (size_t)rows;
-  AGP_HIP_CHECK(ctx, buf->alloc(elems));
-  *out = buf->p;
-  AGP_HIP_CHECK(ctx, hipMemcpyAsync(buf->p, src, sizeof(double) * elems, hipMemcpyHostToDevice, ctx->stream));
+  AGP_HIP_CHECK(ctx, alloc_doubles(*buf, elems));
+  *out = buf->get();
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(buf->get(), src, sizeof(double) * elems, hipMemcpyHostToDevice, ctx->stream));
   AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   return AGP_OK;
 }
@@ -360,11 +351,11 @@ int agp_standard_normal(agp_context *ctx, uint64_t seed, int64_t m, int64_t firs
     return AGP_OK;
   }
   const long long ld = round_up(m, 2);
-  DevBuf buf;
-  AGP_HIP_CHECK(ctx, buf.alloc((size_t)ld * (size_t)n_columns));
-  launch_standard_normal(ctx->stream, seed, m, first_column, n_columns, buf.p, ld);
+  DevMem<double> buf;
+  AGP_HIP_CHECK(ctx, alloc_doubles(buf, (size_t)ld * (size_t)n_columns));
+  launch_standard_normal(ctx->stream, seed, m, first_column, n_columns, buf.get(), ld);
   AGP_HIP_CHECK(ctx, hipGetLastError());
-  return copy_out_block(ctx, buf.p, ld, m, n_columns, out, ldo);
+  return copy_out_block(ctx, buf.get(), ld, m, n_columns, out, ldo);
 }
 
 int agp_draw_mvn(agp_context *ctx, const agp_fit *fit, const double *mean, int64_t n_draws, uint64_t seed, const double *z,
@@ -376,7 +367,7 @@ int agp_draw_mvn(agp_context *ctx, const agp_fit *fit, const double *mean, int64
   AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const long long ld = round_up(m, 2);
-  DevBuf mean_b, z_b, out_b;
+  DevMem<double> mean_b, z_b, out_b;
   const double *mean_d = nullptr, *z_d = nullptr;
   int st = device_vector(ctx, mean, m, location, &mean_b, &mean_d);
   if (st != AGP_OK) return st;
@@ -384,9 +375,9 @@ int agp_draw_mvn(agp_context *ctx, const agp_fit *fit, const double *mean, int64
   if (z) {
     if ((st = device_matrix(ctx, z, m, n_draws, ldz, location, &z_b, &z_d)) != AGP_OK) return st;
   } else {
-    AGP_HIP_CHECK(ctx, z_b.alloc((size_t)ld * (size_t)n_draws));
-    launch_standard_normal(s, seed, m, 0, n_draws, z_b.p, ld);
-    z_d = z_b.p;
+    AGP_HIP_CHECK(ctx, alloc_doubles(z_b, (size_t)ld * (size_t)n_draws));
+    launch_standard_normal(s, seed, m, 0, n_draws, z_b.get(), ld);
+    z_d = z_b.get();
     ldz_d = ld;
   }
   if (location == AGP_DEVICE) {
@@ -395,10 +386,10 @@ int agp_draw_mvn(agp_context *ctx, const agp_fit *fit, const double *mean, int64
     AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
     return AGP_OK;
   }
-  AGP_HIP_CHECK(ctx, out_b.alloc((size_t)ld * (size_t)n_draws));
-  launch_draw(s, fit->A, fit->lda, m, z_d, ldz_d, n_draws, mean_d, out_b.p, ld);
+  AGP_HIP_CHECK(ctx, alloc_doubles(out_b, (size_t)ld * (size_t)n_draws));
+  launch_draw(s, fit->A, fit->lda, m, z_d, ldz_d, n_draws, mean_d, out_b.get(), ld);
   AGP_HIP_CHECK(ctx, hipGetLastError());
-  return copy_out_block(ctx, out_b.p, ld, m, n_draws, out, ldo);
+  return copy_out_block(ctx, out_b.get(), ld, m, n_draws, out, ldo);
 }
 
 int agp_energy_score(agp_context *ctx, const double *mean, const double *cov, int64_t ldc, int64_t m, const double *truth,
@@ -410,7 +401,7 @@ int agp_energy_score(agp_context *ctx, const double *mean, const double *cov, in
   AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const long long k = num_samples / 2 + 1, ncols = 2 * k, ld = round_up(m, 2);  // antithetic_sample, :265
-  DevBuf mean_b, truth_b, var_b, w_b, z_b, v_b, cols_b;
+  DevMem<double> mean_b, truth_b, var_b, w_b, z_b, v_b, cols_b;
   const double *mean_d = nullptr, *truth_d = nullptr, *var_d = nullptr, *w_d = nullptr, *z_d = nullptr;
   int st;
   if ((st = device_vector(ctx, mean, m, location, &mean_b, &mean_d)) != AGP_OK) return st;
@@ -426,21 +417,21 @@ int agp_energy_score(agp_context *ctx, const double *mean, const double *cov, in
   hipError_t e = hipSuccess;
   if (z) {
     st = device_matrix(ctx, z, m, ncols, ldz, location, &z_b, &z_d);
-  } else if ((e = z_b.alloc((size_t)ld * (size_t)ncols)) == hipSuccess) {
-    launch_standard_normal(s, seed, m, 0, ncols, z_b.p, ld);  // set A: columns 0 .. k - 1, set B: k .. 2 k - 1
-    z_d = z_b.p;
+  } else if ((e = alloc_doubles(z_b, (size_t)ld * (size_t)ncols)) == hipSuccess) {
+    launch_standard_normal(s, seed, m, 0, ncols, z_b.get(), ld);  // set A: columns 0 .. k - 1, set B: k .. 2 k - 1
+    z_d = z_b.get();
     ldz_d = ld;
   }
-  if (st == AGP_OK && e == hipSuccess) e = v_b.alloc((size_t)ld * (size_t)ncols);
-  if (st == AGP_OK && e == hipSuccess) e = cols_b.alloc((size_t)(5 * k + 4));
+  if (st == AGP_OK && e == hipSuccess) e = alloc_doubles(v_b, (size_t)ld * (size_t)ncols);
+  if (st == AGP_OK && e == hipSuccess) e = alloc_doubles(cols_b, (size_t)(5 * k + 4));
   if (st == AGP_OK && e == hipSuccess) {
-    launch_draw(s, fit->A, fit->lda, m, z_d, ldz_d, ncols, nullptr, v_b.p, ld);
-    energy_columns_kernel<<<(unsigned)k, RED_THREADS, 0, s>>>(v_b.p, ld, m, k, mean_d, truth_d, w_d, cols_b.p);
-    energy_finish_kernel<<<1, RED_THREADS, 0, s>>>(cols_b.p, k, cols_b.p + 5 * k);
+    launch_draw(s, fit->A, fit->lda, m, z_d, ldz_d, ncols, nullptr, v_b.get(), ld);
+    energy_columns_kernel<<<(unsigned)k, RED_THREADS, 0, s>>>(v_b.get(), ld, m, k, mean_d, truth_d, w_d, cols_b.get());
+    energy_finish_kernel<<<1, RED_THREADS, 0, s>>>(cols_b.get(), k, cols_b.get() + 5 * k);
     e = hipGetLastError();
   }
   double sums[3] = {0., 0., 0.};
-  if (st == AGP_OK && e == hipSuccess) e = hipMemcpyAsync(sums, cols_b.p + 5 * k, sizeof(sums), hipMemcpyDeviceToHost, s);
+  if (st == AGP_OK && e == hipSuccess) e = hipMemcpyAsync(sums, cols_b.get() + 5 * k, sizeof(sums), hipMemcpyDeviceToHost, s);
   if (st == AGP_OK && e == hipSuccess) e = hipStreamSynchronize(s);
   agp_fit_destroy(fit);
   if (st != AGP_OK) return st;
@@ -458,7 +449,7 @@ int agp_variogram_score(agp_context *ctx, const double *mean, const double *cov,
   if (m == 1) { *out = 0.; return AGP_OK; }  // no pair
   AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  DevBuf mean_b, truth_b, var_b, c_b, w_b, part_b;
+  DevMem<double> mean_b, truth_b, var_b, c_b, w_b, part_b;
   const double *mean_d = nullptr, *truth_d = nullptr, *var_d = nullptr, *c_d = nullptr, *w_d = nullptr;
   int st;
   if ((st = device_vector(ctx, mean, m, location, &mean_b, &mean_d)) != AGP_OK) return st;
@@ -467,15 +458,15 @@ int agp_variogram_score(agp_context *ctx, const double *mean, const double *cov,
   if ((st = device_matrix(ctx, cov, m, m, ldc, location, &c_b, &c_d)) != AGP_OK) return st;
   if ((st = device_matrix(ctx, weights, m, m, ldw, location, &w_b, &w_d)) != AGP_OK) return st;
   const long long nt = (m + 63) / 64, tiles = nt * (nt + 1) / 2;
-  AGP_HIP_CHECK(ctx, part_b.alloc((size_t)tiles + 1));
+  AGP_HIP_CHECK(ctx, alloc_doubles(part_b, (size_t)tiles + 1));
   if (order == 2)
-    variogram_kernel<true><<<(unsigned)tiles, RED_THREADS, 0, s>>>(mean_d, c_d, ldc, m, truth_d, var_d, w_d, ldw, part_b.p);
+    variogram_kernel<true><<<(unsigned)tiles, RED_THREADS, 0, s>>>(mean_d, c_d, ldc, m, truth_d, var_d, w_d, ldw, part_b.get());
   else
-    variogram_kernel<false><<<(unsigned)tiles, RED_THREADS, 0, s>>>(mean_d, c_d, ldc, m, truth_d, var_d, w_d, ldw, part_b.p);
-  sum_partials_kernel<<<1, RED_THREADS, 0, s>>>(part_b.p, tiles, part_b.p + tiles);
+    variogram_kernel<false><<<(unsigned)tiles, RED_THREADS, 0, s>>>(mean_d, c_d, ldc, m, truth_d, var_d, w_d, ldw, part_b.get());
+  sum_partials_kernel<<<1, RED_THREADS, 0, s>>>(part_b.get(), tiles, part_b.get() + tiles);
   AGP_HIP_CHECK(ctx, hipGetLastError());
   double total = 0.;
-  AGP_HIP_CHECK(ctx, hipMemcpyAsync(&total, part_b.p + tiles, sizeof(double), hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(&total, part_b.get() + tiles, sizeof(double), hipMemcpyDeviceToHost, s));
   AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
   *out = total;
   return AGP_OK;
@@ -486,7 +477,7 @@ int agp_crps_normal(agp_context *ctx, const double *mu, const double *sigma, con
   if (!ctx || !mu || !sigma || !y || !out || n < 0) return AGP_ERR_INVALID_ARGUMENT;
   if (n == 0) return AGP_OK;
   AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-  DevBuf mu_b, sigma_b, y_b, out_b;
+  DevMem<double> mu_b, sigma_b, y_b, out_b;
   const double *mu_d = nullptr, *sigma_d = nullptr, *y_d = nullptr;
   int st;
   if ((st = device_vector(ctx, mu, n, location, &mu_b, &mu_d)) != AGP_OK) return st;
@@ -494,8 +485,8 @@ int agp_crps_normal(agp_context *ctx, const double *mu, const double *sigma, con
   if ((st = device_vector(ctx, y, n, location, &y_b, &y_d)) != AGP_OK) return st;
   double *out_d = out;
   if (location == AGP_HOST) {
-    AGP_HIP_CHECK(ctx, out_b.alloc((size_t)n));
-    out_d = out_b.p;
+    AGP_HIP_CHECK(ctx, alloc_doubles(out_b, (size_t)n));
+    out_d = out_b.get();
   }
   crps_normal_kernel<<<(unsigned)((n + 255) / 256), 256, 0, ctx->stream>>>(mu_d, sigma_d, y_d, n, out_d);
   AGP_HIP_CHECK(ctx, hipGetLastError());

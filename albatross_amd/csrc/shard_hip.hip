@@ -292,11 +292,10 @@ struct HipShardOps : ShardOps {
     device_pacing = ok && ctx->shard_host_pacing == 0;
     if (device_pacing) {
       if (!ctx->shard_flags) {
-        if (hipMalloc(&ctx->shard_flags, sizeof(unsigned long long) * 2 * EV_COUNT) != hipSuccess ||
+        if (ctx->shard_flags.alloc_plain(sizeof(unsigned long long) * 2 * EV_COUNT) != 0 ||
             hipMemset(ctx->shard_flags, 0, sizeof(unsigned long long) * 2 * EV_COUNT) != hipSuccess) {
           (void)hipGetLastError();
-          if (ctx->shard_flags) (void)hipFree(ctx->shard_flags);
-          ctx->shard_flags = nullptr;
+          ctx->shard_flags.reset();
         }
       }
       flags = ctx->shard_flags;
@@ -768,12 +767,11 @@ void agp_sharded_fit_destroy(agp_sharded_fit *f) {
   // park the two large buffers in the context for the next fit of the same size (kernels that used them were enqueued
   // on the context's streams, and so is whatever uses them next)
   if (f->A) {
-    if (f->ctx && !f->ctx->pool_A) { f->ctx->pool_A = f->A; f->ctx->pool_A_bytes = f->A_bytes; }
-    else (void)dev_release(f->A);  // (may have come from a dense factor's dev_malloc through pool_A)
+    // (evict = false: a sharded fit leaves a slot that holds another size alone)
+    if (!f->ctx || !f->ctx->pool_A.park(f->A, f->A_bytes, false)) (void)dev_release(f->A);  // (may have come from a dense factor's dev_malloc through pool_A)
   }
   if (f->work) {
-    if (f->ctx && !f->ctx->pool_shard) { f->ctx->pool_shard = f->work; f->ctx->pool_shard_bytes = f->work_bytes; }
-    else (void)dev_release(f->work);
+    if (!f->ctx || !f->ctx->pool_shard.park(f->work, f->work_bytes, false)) (void)dev_release(f->work);
   }
   f->train.release();
   delete f;
@@ -831,22 +829,12 @@ int agp_sharded_fit_create(agp_context *c, agp_comm *comm, const agp_kernel *k, 
   if ((st = to_device(ctx, x, true, &f->train)) != AGP_OK) { agp_sharded_fit_destroy(f); return st; }
   f->train.v.meas = 0;
   f->A_bytes = sizeof(double) * (size_t)f->ld * (size_t)n;
-  if (ctx->pool_A && ctx->pool_A_bytes == f->A_bytes) {
-    f->A = ctx->pool_A;
-    ctx->pool_A = nullptr;
-    ctx->pool_A_bytes = 0;
-  } else {
-    SFIT_CHECK(hipMalloc(&f->A, f->A_bytes));
-  }
+  f->A = static_cast<double *>(ctx->pool_A.take(f->A_bytes));
+  if (!f->A) SFIT_CHECK(hipMalloc(&f->A, f->A_bytes));
   const long long work_doubles = shard_work_doubles(plan);
   f->work_bytes = sizeof(double) * (size_t)(work_doubles + plan.max_local_blocks() * B + 8);
-  if (ctx->pool_shard && ctx->pool_shard_bytes == f->work_bytes) {
-    f->work = ctx->pool_shard;
-    ctx->pool_shard = nullptr;
-    ctx->pool_shard_bytes = 0;
-  } else {
-    SFIT_CHECK(hipMalloc(&f->work, f->work_bytes));
-  }
+  f->work = static_cast<double *>(ctx->pool_shard.take(f->work_bytes));
+  if (!f->work) SFIT_CHECK(hipMalloc(&f->work, f->work_bytes));
   f->y = f->work + work_doubles;
   shard_carve(plan, f->work, &f->buf);
   const hipMemcpyKind kind = x->location == AGP_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
@@ -930,7 +918,7 @@ int agp_sharded_fit_create(agp_context *c, agp_comm *comm, const agp_kernel *k, 
     if (ctx->h_flags[2]) { agp_sharded_fit_destroy(f); return status_from_flags(ctx); }
     if (st == AGP_OK) {
       SFIT_CHECK(hipMemcpyAsync(f->buf.xfull, f->y, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
-      const int st2 = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes, sizeof(double) * backsolve_ws_elems(n));
+      const int st2 = reserve_ws(ctx, ctx->ws_aux, sizeof(double) * backsolve_ws_elems(n));
       if (st2 != AGP_OK) { agp_sharded_fit_destroy(f); return st2; }
       backward_solve_vec_any(s, f->A, n, f->ld, f->buf.img_local, f->buf.xfull, ctx->ws_aux);
       SFIT_CHECK(hipStreamSynchronize(s));
@@ -1161,9 +1149,12 @@ int agp_sharded_fit_replicate(agp_context *c, agp_sharded_fit *f, agp_fit **out)
       return AGP_ERR_HIP;                                                    \
     }                                                                        \
   } while (0)
-  REP_CHECK(hipMalloc(&fit->A, fit->A_bytes));
-  REP_CHECK(hipMalloc(&fit->invd, sizeof(double) * (size_t)nblk * SHARD_IMG));
-  REP_CHECK(hipMalloc(&fit->alpha, sizeof(double) * (size_t)n));
+  REP_CHECK(static_cast<hipError_t>(fit->own_A.alloc_plain(fit->A_bytes)));
+  REP_CHECK(static_cast<hipError_t>(fit->own_part[0].alloc_plain(sizeof(double) * (size_t)nblk * SHARD_IMG)));
+  REP_CHECK(static_cast<hipError_t>(fit->own_part[2].alloc_plain(sizeof(double) * (size_t)n)));
+  fit->A = fit->own_A;
+  fit->invd = fit->own_part[0];
+  fit->alpha = fit->own_part[2];
   int st = AGP_OK;
   {
     HipShardOps ops(ctx);

@@ -25,10 +25,10 @@ struct agp_solver {
   // BlockSymmetric: solver of [[A, B], [B^T, C]] from a solver of A, Ai_B = A^-1 B (na x nb, ld = na, owned) and the solver
   // of the Schur complement S = C - B^T A^-1 B (both sub-solvers borrowed: they must outlive this object)
   const agp_solver *A = nullptr, *S = nullptr;
-  double *AiB = nullptr;
+  DevMem<double> AiB;
   // ExplainedCovariance: S^-1 = outer^-1 inner outer^-1 (outer borrowed; inner n x n, ld = n, owned)
   const agp_solver *outer = nullptr;
-  double *inner = nullptr;
+  DevMem<double> inner;
   long long n = 0, na = 0, nb = 0;
 };
 
@@ -43,12 +43,6 @@ namespace {
     }                                                                        \
   } while (0)
 
-struct DevBuf {  // scratch that goes with the scope (through the caching allocator of api.hip)
-  double *p = nullptr;
-  ~DevBuf() { if (p) (void)dev_free(p); }
-  hipError_t get(size_t elems) { return dev_malloc(&p, sizeof(double) * std::max<size_t>(elems, 1)); }
-};
-
 // out (n x r, ld = n) = solver^-1 rhs (n x r, ld = n), both on the device
 int solve_dev(agp_context *ctx, const agp_solver *sv, const double *rhs, long long r, double *out) {
   if (r <= 0) return AGP_OK;
@@ -58,46 +52,46 @@ int solve_dev(agp_context *ctx, const agp_solver *sv, const double *rhs, long lo
   case 1: return agp_ldlt_solve(ctx, sv->ldlt, rhs, r, out, AGP_DEVICE);
   case 2: {  // block_symmetric.hpp:75-98
     const long long na = sv->na, nb = sv->nb, n = sv->n;
-    DevBuf ra, rb, t1, si1, sib, xa;
-    SOL_HIP(ra.get((size_t)na * r));
-    SOL_HIP(rb.get((size_t)nb * r));
-    SOL_HIP(t1.get((size_t)nb * r));
-    SOL_HIP(si1.get((size_t)nb * r));
-    SOL_HIP(sib.get((size_t)nb * r));
-    SOL_HIP(xa.get((size_t)na * r));
-    SOL_HIP(hipMemcpy2DAsync(ra.p, sizeof(double) * (size_t)na, rhs, sizeof(double) * (size_t)n, sizeof(double) * (size_t)na, (size_t)r,
+    DevMem<double> ra, rb, t1, si1, sib, xa;
+    SOL_HIP(alloc_doubles(ra, (size_t)na * r));
+    SOL_HIP(alloc_doubles(rb, (size_t)nb * r));
+    SOL_HIP(alloc_doubles(t1, (size_t)nb * r));
+    SOL_HIP(alloc_doubles(si1, (size_t)nb * r));
+    SOL_HIP(alloc_doubles(sib, (size_t)nb * r));
+    SOL_HIP(alloc_doubles(xa, (size_t)na * r));
+    SOL_HIP(hipMemcpy2DAsync(ra.get(), sizeof(double) * (size_t)na, rhs, sizeof(double) * (size_t)n, sizeof(double) * (size_t)na, (size_t)r,
                              hipMemcpyDeviceToDevice, s));
-    SOL_HIP(hipMemcpy2DAsync(rb.p, sizeof(double) * (size_t)nb, rhs + na, sizeof(double) * (size_t)n, sizeof(double) * (size_t)nb,
+    SOL_HIP(hipMemcpy2DAsync(rb.get(), sizeof(double) * (size_t)nb, rhs + na, sizeof(double) * (size_t)n, sizeof(double) * (size_t)nb,
                              (size_t)r, hipMemcpyDeviceToDevice, s));
     // Bt_Ai_rhs = Ai_B^T rhs_a   (nb x r):  t1 = 0 - Ai_B^T rhs_a, then negated
-    SOL_HIP(hipMemsetAsync(t1.p, 0, sizeof(double) * (size_t)nb * (size_t)r, s));
-    launch_gemm_nt_sub(s, t1.p, nb, sv->AiB, na, true, ra.p, na, true, nb, r, na, false);
-    launch_axpby(s, nb * r, -1.0, t1.p, 0.0, t1.p, t1.p);
-    int st = solve_dev(ctx, sv->S, t1.p, r, si1.p);              // Si_Bt_Ai_rhs
-    if (st == AGP_OK) st = solve_dev(ctx, sv->S, rb.p, r, sib.p);  // Si_rhs_b
-    if (st == AGP_OK) st = solve_dev(ctx, sv->A, ra.p, r, xa.p);   // Ai_rhs_a
+    SOL_HIP(hipMemsetAsync(t1.get(), 0, sizeof(double) * (size_t)nb * (size_t)r, s));
+    launch_gemm_nt_sub(s, t1.get(), nb, sv->AiB, na, true, ra.get(), na, true, nb, r, na, false);
+    launch_axpby(s, nb * r, -1.0, t1.get(), 0.0, t1.get(), t1.get());
+    int st = solve_dev(ctx, sv->S, t1.get(), r, si1.get());              // Si_Bt_Ai_rhs
+    if (st == AGP_OK) st = solve_dev(ctx, sv->S, rb.get(), r, sib.get());  // Si_rhs_b
+    if (st == AGP_OK) st = solve_dev(ctx, sv->A, ra.get(), r, xa.get());   // Ai_rhs_a
     if (st != AGP_OK) return st;
     // d = Si_rhs_b - Si_Bt_Ai_rhs  = the b part of the answer;  a part = Ai_rhs_a - Ai_B d
-    launch_axpby(s, nb * r, 1.0, sib.p, -1.0, si1.p, t1.p);
-    launch_gemm_nt_sub(s, xa.p, na, sv->AiB, na, false, t1.p, nb, true, na, r, nb, false);
-    SOL_HIP(hipMemcpy2DAsync(out, sizeof(double) * (size_t)n, xa.p, sizeof(double) * (size_t)na, sizeof(double) * (size_t)na, (size_t)r,
+    launch_axpby(s, nb * r, 1.0, sib.get(), -1.0, si1.get(), t1.get());
+    launch_gemm_nt_sub(s, xa.get(), na, sv->AiB, na, false, t1.get(), nb, true, na, r, nb, false);
+    SOL_HIP(hipMemcpy2DAsync(out, sizeof(double) * (size_t)n, xa.get(), sizeof(double) * (size_t)na, sizeof(double) * (size_t)na, (size_t)r,
                              hipMemcpyDeviceToDevice, s));
-    SOL_HIP(hipMemcpy2DAsync(out + na, sizeof(double) * (size_t)n, t1.p, sizeof(double) * (size_t)nb, sizeof(double) * (size_t)nb,
+    SOL_HIP(hipMemcpy2DAsync(out + na, sizeof(double) * (size_t)n, t1.get(), sizeof(double) * (size_t)nb, sizeof(double) * (size_t)nb,
                              (size_t)r, hipMemcpyDeviceToDevice, s));
     SOL_HIP(hipStreamSynchronize(s));
     return AGP_OK;
   }
   case 3: {  // representations.hpp:80-82: outer^-1 (inner (outer^-1 rhs))
     const long long n = sv->n;
-    DevBuf t, u;
-    SOL_HIP(t.get((size_t)n * r));
-    SOL_HIP(u.get((size_t)n * r));
-    int st = solve_dev(ctx, sv->outer, rhs, r, t.p);
+    DevMem<double> t, u;
+    SOL_HIP(alloc_doubles(t, (size_t)n * r));
+    SOL_HIP(alloc_doubles(u, (size_t)n * r));
+    int st = solve_dev(ctx, sv->outer, rhs, r, t.get());
     if (st != AGP_OK) return st;
-    SOL_HIP(hipMemsetAsync(u.p, 0, sizeof(double) * (size_t)n * (size_t)r, s));
-    launch_gemm_nt_sub(s, u.p, n, sv->inner, n, false, t.p, n, true, n, r, n, false);  // u = -inner t
-    launch_axpby(s, n * r, -1.0, u.p, 0.0, u.p, u.p);
-    st = solve_dev(ctx, sv->outer, u.p, r, out);
+    SOL_HIP(hipMemsetAsync(u.get(), 0, sizeof(double) * (size_t)n * (size_t)r, s));
+    launch_gemm_nt_sub(s, u.get(), n, sv->inner, n, false, t.get(), n, true, n, r, n, false);  // u = -inner t
+    launch_axpby(s, n * r, -1.0, u.get(), 0.0, u.get(), u.get());
+    st = solve_dev(ctx, sv->outer, u.get(), r, out);
     SOL_HIP(hipStreamSynchronize(s));
     return st;
   }
@@ -140,8 +134,6 @@ int64_t agp_solver_rows(const agp_solver *s) { return s ? s->n : 0; }
 void agp_solver_destroy(agp_solver *s) {
   if (!s) return;
   if (s->ctx) (void)hipSetDevice(s->ctx->device);
-  if (s->AiB) (void)dev_free(s->AiB);
-  if (s->inner) (void)dev_free(s->inner);
   delete s;
 }
 
@@ -153,14 +145,14 @@ int agp_solver_block_symmetric(agp_context *ctx, const agp_solver *A, const doub
   agp_solver *s = new (std::nothrow) agp_solver();
   if (!s) return AGP_ERR_INVALID_ARGUMENT;
   s->kind = 2; s->ctx = ctx; s->A = A; s->S = S; s->na = na; s->nb = nb; s->n = na + nb;
-  DevBuf Bd;
-  if (Bd.get((size_t)na * nb) != hipSuccess || dev_malloc(&s->AiB, sizeof(double) * (size_t)std::max<long long>(na * nb, 1)) != hipSuccess) {
+  DevMem<double> Bd;
+  if (alloc_doubles(Bd, (size_t)na * nb) != hipSuccess || alloc_doubles(s->AiB, (size_t)(na * nb)) != hipSuccess) {
     agp_solver_destroy(s);
     ctx->last_error = "agp_solver_block_symmetric: allocation";
     return AGP_ERR_HIP;
   }
-  int st = to_dev_matrix(ctx, B, na, nb, ldb, location, Bd.p);
-  if (st == AGP_OK) st = solve_dev(ctx, A, Bd.p, nb, s->AiB);  // Ai_B = A.solve(B), block_symmetric.hpp:51
+  int st = to_dev_matrix(ctx, B, na, nb, ldb, location, Bd.get());
+  if (st == AGP_OK) st = solve_dev(ctx, A, Bd.get(), nb, s->AiB);  // Ai_B = A.solve(B), block_symmetric.hpp:51
   if (st != AGP_OK) { agp_solver_destroy(s); return st; }
   *out = s;
   return AGP_OK;
@@ -173,7 +165,7 @@ int agp_solver_explained(agp_context *ctx, const agp_solver *outer, const double
   agp_solver *s = new (std::nothrow) agp_solver();
   if (!s) return AGP_ERR_INVALID_ARGUMENT;
   s->kind = 3; s->ctx = ctx; s->outer = outer; s->n = n;
-  if (dev_malloc(&s->inner, sizeof(double) * (size_t)std::max<long long>(n * n, 1)) != hipSuccess) {
+  if (alloc_doubles(s->inner, (size_t)(n * n)) != hipSuccess) {
     agp_solver_destroy(s);
     ctx->last_error = "agp_solver_explained: allocation";
     return AGP_ERR_HIP;
@@ -189,11 +181,11 @@ int agp_solver_solve(agp_context *ctx, const agp_solver *sv, const double *rhs, 
   if (nrhs == 0 || sv->n == 0) return AGP_OK;
   AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (location == AGP_DEVICE) return solve_dev(ctx, sv, rhs, nrhs, out);
-  DevBuf r, o;
-  if (r.get((size_t)sv->n * nrhs) != hipSuccess || o.get((size_t)sv->n * nrhs) != hipSuccess) { ctx->last_error = "agp_solver_solve: allocation"; return AGP_ERR_HIP; }
-  int st = to_dev_matrix(ctx, rhs, sv->n, nrhs, sv->n, AGP_HOST, r.p);
-  if (st == AGP_OK) st = solve_dev(ctx, sv, r.p, nrhs, o.p);
-  if (st == AGP_OK) st = copy_out(ctx, o.p, sv->n * nrhs, out, AGP_HOST);
+  DevMem<double> r, o;
+  if (alloc_doubles(r, (size_t)sv->n * nrhs) != hipSuccess || alloc_doubles(o, (size_t)sv->n * nrhs) != hipSuccess) { ctx->last_error = "agp_solver_solve: allocation"; return AGP_ERR_HIP; }
+  int st = to_dev_matrix(ctx, rhs, sv->n, nrhs, sv->n, AGP_HOST, r.get());
+  if (st == AGP_OK) st = solve_dev(ctx, sv, r.get(), nrhs, o.get());
+  if (st == AGP_OK) st = copy_out(ctx, o.get(), sv->n * nrhs, out, AGP_HOST);
   return st;
 }
 
@@ -220,27 +212,27 @@ int agp_solver_predict(agp_context *ctx, const agp_kernel *k, const agp_solver *
   if ((st = to_device(ctx, train, false, &dtr)) != AGP_OK) return st;
   if ((st = to_device(ctx, xs, false, &dxs)) != AGP_OK) return st;
   hipStream_t s = ctx->stream;
-  DevBuf cross, expl, info, mean_d, prior;
-  if (cross.get((size_t)n * m) != hipSuccess || info.get((size_t)n) != hipSuccess || mean_d.get((size_t)m) != hipSuccess ||
-      (mode > 0 && expl.get((size_t)n * m) != hipSuccess) || (mode > 0 && prior.get(mode == 2 ? (size_t)m * m : (size_t)m) != hipSuccess)) {
+  DevMem<double> cross, expl, info, mean_d, prior;
+  if (alloc_doubles(cross, (size_t)n * m) != hipSuccess || alloc_doubles(info, (size_t)n) != hipSuccess || alloc_doubles(mean_d, (size_t)m) != hipSuccess ||
+      (mode > 0 && alloc_doubles(expl, (size_t)n * m) != hipSuccess) || (mode > 0 && alloc_doubles(prior, mode == 2 ? (size_t)m * m : (size_t)m) != hipSuccess)) {
     ctx->last_error = "agp_solver_predict: allocation";
     return AGP_ERR_HIP;
   }
-  if ((st = vector_to_device(ctx, information, n, location, info.p)) != AGP_OK) return st;
+  if ((st = vector_to_device(ctx, information, n, location, info.get())) != AGP_OK) return st;
   // cross_cov = cov(train_features, features); mean = cross_cov^T information   (gp.hpp:316,337,361-363)
-  launch_gram(s, dprog, dtr.v, dxs.v, false, false, cross.p, n, nullptr, nullptr, &k->prog);
-  launch_colvec_dot(s, cross.p, n, n, m, info.p, 1.0, 0.0, nullptr, mean_d.p);
-  if ((st = copy_out(ctx, mean_d.p, m, mean, location)) != AGP_OK) return st;
+  launch_gram(s, dprog, dtr.v, dxs.v, false, false, cross.get(), n, nullptr, nullptr, &k->prog);
+  launch_colvec_dot(s, cross.get(), n, n, m, info.get(), 1.0, 0.0, nullptr, mean_d.get());
+  if ((st = copy_out(ctx, mean_d.get(), m, mean, location)) != AGP_OK) return st;
   if (mode == 0) return AGP_OK;
-  if ((st = solve_dev(ctx, sv, cross.p, m, expl.p)) != AGP_OK) return st;  // train_covariance.solve(cross_cov), gp.hpp:96,111
+  if ((st = solve_dev(ctx, sv, cross.get(), m, expl.get())) != AGP_OK) return st;  // train_covariance.solve(cross_cov), gp.hpp:96,111
   if (mode == 1) {
-    launch_gram_diagonal(s, dprog, dxs.v, prior.p);                          // gp.hpp:339-343
-    launch_coldot(s, expl.p, n, cross.p, n, n, m, prior.p, 1.0, prior.p);    // prior - colsum(explained o cross), gp.hpp:97-99
-    return copy_out(ctx, prior.p, m, var_or_cov, location);
+    launch_gram_diagonal(s, dprog, dxs.v, prior.get());                          // gp.hpp:339-343
+    launch_coldot(s, expl.get(), n, cross.get(), n, n, m, prior.get(), 1.0, prior.get());    // prior - colsum(explained o cross), gp.hpp:97-99
+    return copy_out(ctx, prior.get(), m, var_or_cov, location);
   }
-  launch_gram(s, dprog, dxs.v, dxs.v, true, false, prior.p, m, nullptr, nullptr, &k->prog);    // prior_cov, gp.hpp:317
-  launch_gemm_nt_sub(s, prior.p, m, cross.p, n, true, expl.p, n, true, m, m, n, false);       // - cross^T explained, gp.hpp:111
-  return copy_out(ctx, prior.p, m * m, var_or_cov, location);
+  launch_gram(s, dprog, dxs.v, dxs.v, true, false, prior.get(), m, nullptr, nullptr, &k->prog);    // prior_cov, gp.hpp:317
+  launch_gemm_nt_sub(s, prior.get(), m, cross.get(), n, true, expl.get(), n, true, m, m, n, false);       // - cross^T explained, gp.hpp:111
+  return copy_out(ctx, prior.get(), m * m, var_or_cov, location);
 }
 
 // FitModel::update on a generic representation (gp.hpp:403-407): the information vector of the conditioned fit,
@@ -253,9 +245,9 @@ int agp_solver_update_information(agp_context *ctx, const agp_solver *bs, const 
   if (bs->ctx != ctx) return AGP_ERR_INVALID_ARGUMENT;
   AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const long long na = bs->na, nb = bs->nb;
-  DevBuf v;
-  if (v.get((size_t)(2 * na + nb)) != hipSuccess) { ctx->last_error = "agp_solver_update_information: allocation"; return AGP_ERR_HIP; }
-  double *info = v.p, *res = v.p + na;  // res: na + nb
+  DevMem<double> v;
+  if (alloc_doubles(v, (size_t)(2 * na + nb)) != hipSuccess) { ctx->last_error = "agp_solver_update_information: allocation"; return AGP_ERR_HIP; }
+  double *info = v.get(), *res = v.get() + na;  // res: na + nb
   int st = vector_to_device(ctx, information, na, location, info);
   if (st == AGP_OK) st = vector_to_device(ctx, si_delta, nb, location, res + na);
   if (st != AGP_OK) return st;
@@ -283,31 +275,31 @@ int agp_solver_predict_combined(agp_context *ctx, const agp_kernel *k, const agp
   AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   if (m == 0) return AGP_OK;
   hipStream_t s = ctx->stream;
-  DevBuf cross, expl, info, mean_d, prior, pdiag;
-  if (cross.get((size_t)n * m) != hipSuccess || info.get((size_t)n) != hipSuccess || mean_d.get((size_t)m) != hipSuccess ||
-      (mode > 0 && expl.get((size_t)n * m) != hipSuccess) || (mode > 0 && prior.get((size_t)m * m) != hipSuccess) ||
-      (mode == 1 && pdiag.get((size_t)m) != hipSuccess)) {
+  DevMem<double> cross, expl, info, mean_d, prior, pdiag;
+  if (alloc_doubles(cross, (size_t)n * m) != hipSuccess || alloc_doubles(info, (size_t)n) != hipSuccess || alloc_doubles(mean_d, (size_t)m) != hipSuccess ||
+      (mode > 0 && alloc_doubles(expl, (size_t)n * m) != hipSuccess) || (mode > 0 && alloc_doubles(prior, (size_t)m * m) != hipSuccess) ||
+      (mode == 1 && alloc_doubles(pdiag, (size_t)m) != hipSuccess)) {
     ctx->last_error = "agp_solver_predict_combined: allocation";
     return AGP_ERR_HIP;
   }
-  if ((st = vector_to_device(ctx, information, n, location, info.p)) != AGP_OK) return st;
+  if ((st = vector_to_device(ctx, information, n, location, info.get())) != AGP_OK) return st;
   // cross_cov = cov(train_features, features) through LinearCombinationCaller; mean = cross_cov^T information
-  if ((st = agp_gram_combined(ctx, k, train, n_train, train_offsets, train_coefficients, xs, n_xs, xs_offsets, xs_coefficients, cross.p, n,
+  if ((st = agp_gram_combined(ctx, k, train, n_train, train_offsets, train_coefficients, xs, n_xs, xs_offsets, xs_coefficients, cross.get(), n,
                               AGP_DEVICE)) != AGP_OK) return st;
-  launch_colvec_dot(s, cross.p, n, n, m, info.p, 1.0, 0.0, nullptr, mean_d.p);
-  if ((st = copy_out(ctx, mean_d.p, m, mean, location)) != AGP_OK) return st;
+  launch_colvec_dot(s, cross.get(), n, n, m, info.get(), 1.0, 0.0, nullptr, mean_d.get());
+  if ((st = copy_out(ctx, mean_d.get(), m, mean, location)) != AGP_OK) return st;
   if (mode == 0) return AGP_OK;
-  if ((st = solve_dev(ctx, sv, cross.p, m, expl.p)) != AGP_OK) return st;  // train_covariance.solve(cross_cov), gp.hpp:96,111
-  if ((st = agp_gram_combined(ctx, k, xs, n_xs, xs_offsets, xs_coefficients, nullptr, 0, nullptr, nullptr, prior.p, m, AGP_DEVICE)) != AGP_OK)
+  if ((st = solve_dev(ctx, sv, cross.get(), m, expl.get())) != AGP_OK) return st;  // train_covariance.solve(cross_cov), gp.hpp:96,111
+  if ((st = agp_gram_combined(ctx, k, xs, n_xs, xs_offsets, xs_coefficients, nullptr, 0, nullptr, nullptr, prior.get(), m, AGP_DEVICE)) != AGP_OK)
     return st;                                                              // prior_cov, gp.hpp:317,339-343
   if (mode == 1) {
-    SOL_HIP(hipMemcpy2DAsync(pdiag.p, sizeof(double), prior.p, sizeof(double) * (size_t)(m + 1), sizeof(double), (size_t)m,
+    SOL_HIP(hipMemcpy2DAsync(pdiag.get(), sizeof(double), prior.get(), sizeof(double) * (size_t)(m + 1), sizeof(double), (size_t)m,
                              hipMemcpyDeviceToDevice, s));                  // its diagonal
-    launch_coldot(s, expl.p, n, cross.p, n, n, m, pdiag.p, 1.0, pdiag.p);   // prior - colsum(explained o cross), gp.hpp:97-99
-    return copy_out(ctx, pdiag.p, m, var_or_cov, location);
+    launch_coldot(s, expl.get(), n, cross.get(), n, n, m, pdiag.get(), 1.0, pdiag.get());   // prior - colsum(explained o cross), gp.hpp:97-99
+    return copy_out(ctx, pdiag.get(), m, var_or_cov, location);
   }
-  launch_gemm_nt_sub(s, prior.p, m, cross.p, n, true, expl.p, n, true, m, m, n, false);  // - cross^T explained, gp.hpp:111
-  return copy_out(ctx, prior.p, m * m, var_or_cov, location);
+  launch_gemm_nt_sub(s, prior.get(), m, cross.get(), n, true, expl.get(), n, true, m, m, n, false);  // - cross^T explained, gp.hpp:111
+  return copy_out(ctx, prior.get(), m * m, var_or_cov, location);
 }
 
 }  // extern "C"

@@ -43,14 +43,6 @@ FeatView feature_rows(const FeatView &v, long long o, long long cnt) {
   return r;
 }
 
-#define SPX_HIP(expr)                                                                    \
-  do {                                                                                   \
-    hipError_t _e = (expr);                                                              \
-    if (_e != hipSuccess) {                                                              \
-      ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(_e);               \
-      return AGP_ERR_HIP;                                                                \
-    }                                                                                    \
-  } while (0)
 
 // C (m x m, lower tiles) -= W W^T for W m x n with n >> m: 136 tiles of 128 x 128 at m = 2048 would leave most of the
 // chip idle behind one very long K loop, so the columns are cut into `slab_count` equal slices that run as one batched
@@ -124,16 +116,16 @@ int sparse_observations(agp_context *ctx, const agp_kernel *k, const DevProgram 
   xm.meas = 1;  // as_measurements(out_of_order_features), sparse_gp.hpp:649-650
   const long long ldk = round_up(m, 2), np2 = round_up(n, 2);
   // vectors: dvar (n) | yw (n) | t (n)
-  SPX_HIP(dev_malloc(&w.vecs, sizeof(double) * (size_t)(3 * np2)));
+  AGP_HIP_CHECK(ctx, w.vecs.alloc_cached(sizeof(double) * (size_t)(3 * np2)));
   double *dvar = w.vecs, *yw = dvar + np2, *tvec = yw + np2;
   const hipMemcpyKind kind = x->location == AGP_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-  SPX_HIP(hipMemcpyAsync(yw, y, sizeof(double) * (size_t)n, kind, s));
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(yw, y, sizeof(double) * (size_t)n, kind, s));
   if (y_var) {
-    SPX_HIP(hipMemcpyAsync(tvec, y_var, sizeof(double) * (size_t)n, kind, s));
-    if (x->location == AGP_HOST) SPX_HIP(hipStreamSynchronize(s));
+    AGP_HIP_CHECK(ctx, hipMemcpyAsync(tvec, y_var, sizeof(double) * (size_t)n, kind, s));
+    if (x->location == AGP_HOST) AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
     launch_axpby(s, n, 1.0, tvec, measurement_nugget, nullptr, dvar);  // target variance + measurement nugget, :692-696
   } else {
-    if (x->location == AGP_HOST) SPX_HIP(hipStreamSynchronize(s));
+    if (x->location == AGP_HOST) AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
     launch_axpby(s, n, 0.0, nullptr, measurement_nugget, nullptr, dvar);
   }
   stage("upload");
@@ -149,8 +141,7 @@ int sparse_observations(agp_context *ctx, const agp_kernel *k, const DevProgram 
     const size_t kuf_e = (size_t)ldk * (size_t)n, pq_e = (size_t)ldk * (size_t)(n + m),
                  slab_e = (size_t)w.slab_count * (size_t)ldm_p * (size_t)m,
                  pad_e = padded_path ? (size_t)ldk * (size_t)(smax * n_groups) : 0, q_e = w.keep_P ? pq_e : 0;
-    if ((st = ensure_ws(ctx, &ctx->pool_sparse, &ctx->pool_sparse_bytes,
-                        sizeof(double) * (kuf_e + pq_e + slab_e + 2 * pad_e + q_e))) != AGP_OK)
+    if ((st = reserve_ws(ctx, ctx->pool_sparse, sizeof(double) * (kuf_e + pq_e + slab_e + 2 * pad_e + q_e))) != AGP_OK)
       return st;
     w.Kuf = ctx->pool_sparse;
     w.Pbuf = w.Kuf + kuf_e;
@@ -163,14 +154,14 @@ int sparse_observations(agp_context *ctx, const agp_kernel *k, const DevProgram 
     ldlt_sqrt_solve(s, kp->A, kp->lda, m, kp->q_dev, w.Pbuf, w.Kuf, ldk, n);
   } else if (forward_solve_wide_ok(m, n)) {
     // many more observations than inducing points: out of place through the inverted 512 x 512 diagonal blocks
-    if (!w.Winv) SPX_HIP(dev_malloc(&w.Winv, sizeof(double) * (size_t)m * (size_t)WIDE_BW));
+    if (!w.Winv) AGP_HIP_CHECK(ctx, w.Winv.alloc_cached(sizeof(double) * (size_t)m * (size_t)WIDE_BW));
     invert_wide_blocks(s, kuu->A, m, kuu->lda, kuu->invd, WIDE_BW, w.Winv);
     forward_solve_wide(s, kuu->A, m, kuu->lda, w.Winv, w.Kuf, ldk, w.Pbuf, ldk, n);
   } else {
-    SPX_HIP(hipMemcpyAsync(w.Pbuf, w.Kuf, sizeof(double) * (size_t)ldk * (size_t)n, hipMemcpyDeviceToDevice, s));
+    AGP_HIP_CHECK(ctx, hipMemcpyAsync(w.Pbuf, w.Kuf, sizeof(double) * (size_t)ldk * (size_t)n, hipMemcpyDeviceToDevice, s));
     forward_solve_mat(s, kuu->A, m, kuu->lda, kuu->invd, w.Pbuf, n, ldk);
   }
-  SPX_HIP(hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
   stage("K_uf, P = L_u^-1 K_uf");
   // A block by block, then W = K_uf A^-T/2 (in place in K_uf) and y_w = A^-1/2 y  (:652-704; B's top block
   // transposed, :347-349; :372)
@@ -184,11 +175,11 @@ int sparse_observations(agp_context *ctx, const agp_kernel *k, const DevProgram 
     // is what the per-block path below is bound by (the HIP launch path is serial per process).
     const long long sb = smax, lda_b = factor_ld(sb), nblk_b = (sb + NB - 1) / NB;
     const long long stride_A = lda_b * sb, stride_I = nblk_b * (36 * MB * MB);
-    SPX_HIP(dev_malloc(&w.Ag, sizeof(double) * (size_t)stride_A * (size_t)n_groups));
-    SPX_HIP(dev_malloc(&w.Pimg, sizeof(double) * ((size_t)stride_I + 1) * (size_t)n_groups));
+    AGP_HIP_CHECK(ctx, w.Ag.alloc_cached(sizeof(double) * (size_t)stride_A * (size_t)n_groups));
+    AGP_HIP_CHECK(ctx, w.Pimg.alloc_cached(sizeof(double) * ((size_t)stride_I + 1) * (size_t)n_groups));
     double *logsum = w.Pimg + (size_t)stride_I * (size_t)n_groups;
-    SPX_HIP(hipMemsetAsync(logsum, 0, sizeof(double) * (size_t)n_groups, s));
-    SPX_HIP(hipMemsetAsync(ctx->d_flags, 0, 4 * sizeof(int), s));
+    AGP_HIP_CHECK(ctx, hipMemsetAsync(logsum, 0, sizeof(double) * (size_t)n_groups, s));
+    AGP_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_flags, 0, 4 * sizeof(int), s));
     // K_gg + target variance, all groups: one launch for the radial fast-path kernels, else one per group
     if (!launch_gram_blocks(s, &k->prog, xm, sb, n_groups, w.Ag, lda_b, stride_A, dvar, ctx->d_flags))
       for (int64_t g = 0; g < n_groups; ++g) {
@@ -202,10 +193,10 @@ int sparse_observations(agp_context *ctx, const agp_kernel *k, const DevProgram 
     factor_lower_batched(s, w.Ag, stride_A, sb, lda_b, w.Pimg, stride_I, yw, sb, n_groups, ctx->d_flags, logsum);
     right_solve_lt_batched(s, w.Ag, stride_A, sb, lda_b, w.Pimg, stride_I, w.Kuf, sb * ldk, m, ldk, n_groups);
     std::vector<double> hl((size_t)n_groups);
-    SPX_HIP(hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-    SPX_HIP(hipMemcpyAsync(hl.data(), logsum, sizeof(double) * (size_t)n_groups, hipMemcpyDeviceToHost, s));
-    SPX_HIP(hipStreamSynchronize(s));
-    SPX_HIP(hipGetLastError());
+    AGP_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+    AGP_HIP_CHECK(ctx, hipMemcpyAsync(hl.data(), logsum, sizeof(double) * (size_t)n_groups, hipMemcpyDeviceToHost, s));
+    AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+    AGP_HIP_CHECK(ctx, hipGetLastError());
     if ((st = status_from_flags(ctx)) != AGP_OK) return st;
     for (int64_t g = 0; g < n_groups; ++g) log_det_a += 2. * hl[(size_t)g];  // fixed order
   } else if (n_groups >= 4 && smax * n_groups <= 3 * n) {
@@ -214,28 +205,19 @@ int sparse_observations(agp_context *ctx, const agp_kernel *k, const DevProgram 
     // zero-padded slabs and W / y_w copied back.  At most 3x the compact memory.
     const long long sb = smax, lda_b = factor_ld(sb), nblk_b = (sb + NB - 1) / NB, G = n_groups;
     const long long stride_A = lda_b * sb, stride_I = nblk_b * (36 * MB * MB), padded = sb * G;
-    double *Ppad = nullptr, *Kpad = nullptr, *ypad = nullptr;
-    long long *off_d = nullptr;
-    auto free_pads = [&]() { (void)dev_free(ypad); (void)dev_free(off_d); };
-#define SPX_HIP2(expr)                                                                   \
-  do {                                                                                   \
-    hipError_t _e = (expr);                                                              \
-    if (_e != hipSuccess) {                                                              \
-      ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(_e);               \
-      free_pads();                                                                       \
-      return AGP_ERR_HIP;                                                                \
-    }                                                                                    \
-  } while (0)
-    SPX_HIP2(dev_malloc(&off_d, sizeof(long long) * (size_t)(G + 1)));
-    SPX_HIP2(hipMemcpyAsync(off_d, offsets, sizeof(long long) * (size_t)(G + 1), hipMemcpyHostToDevice, s));
+    double *Ppad = nullptr, *Kpad = nullptr;
+    DevMem<double> ypad;
+    DevMem<long long> off_d;
+    AGP_HIP_CHECK(ctx, off_d.alloc_cached(sizeof(long long) * (size_t)(G + 1)));
+    AGP_HIP_CHECK(ctx, hipMemcpyAsync(off_d, offsets, sizeof(long long) * (size_t)(G + 1), hipMemcpyHostToDevice, s));
     Ppad = w.pads;  // in the pool (sized above)
     Kpad = Ppad + (size_t)ldk * (size_t)padded;
-    SPX_HIP2(dev_malloc(&ypad, sizeof(double) * (size_t)round_up(padded, 2)));
-    SPX_HIP2(dev_malloc(&w.Ag, sizeof(double) * (size_t)stride_A * (size_t)G));
-    SPX_HIP2(dev_malloc(&w.Pimg, sizeof(double) * ((size_t)stride_I + 1) * (size_t)G));
+    AGP_HIP_CHECK(ctx, ypad.alloc_cached(sizeof(double) * (size_t)round_up(padded, 2)));
+    AGP_HIP_CHECK(ctx, w.Ag.alloc_cached(sizeof(double) * (size_t)stride_A * (size_t)G));
+    AGP_HIP_CHECK(ctx, w.Pimg.alloc_cached(sizeof(double) * ((size_t)stride_I + 1) * (size_t)G));
     double *logsum = w.Pimg + (size_t)stride_I * (size_t)G;
-    SPX_HIP2(hipMemsetAsync(logsum, 0, sizeof(double) * (size_t)G, s));
-    SPX_HIP2(hipMemsetAsync(ctx->d_flags, 0, 4 * sizeof(int), s));
+    AGP_HIP_CHECK(ctx, hipMemsetAsync(logsum, 0, sizeof(double) * (size_t)G, s));
+    AGP_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_flags, 0, 4 * sizeof(int), s));
     launch_pad_columns(s, w.Pbuf, ldk, off_d, sb, G, m, Ppad, ldk, 0);
     launch_pad_columns(s, w.Kuf, ldk, off_d, sb, G, m, Kpad, ldk, 0);
     launch_pad_columns(s, yw, 1, off_d, sb, G, 1, ypad, 1, 0);
@@ -251,12 +233,12 @@ int sparse_observations(agp_context *ctx, const agp_kernel *k, const DevProgram 
     launch_pad_columns(s, Kpad, ldk, off_d, sb, G, m, w.Kuf, ldk, 1);
     launch_pad_columns(s, ypad, 1, off_d, sb, G, 1, yw, 1, 1);
     std::vector<double> hl((size_t)G);
-    SPX_HIP2(hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-    SPX_HIP2(hipMemcpyAsync(hl.data(), logsum, sizeof(double) * (size_t)G, hipMemcpyDeviceToHost, s));
-    SPX_HIP2(hipStreamSynchronize(s));
-    SPX_HIP2(hipGetLastError());
-#undef SPX_HIP2
-    free_pads();
+    AGP_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+    AGP_HIP_CHECK(ctx, hipMemcpyAsync(hl.data(), logsum, sizeof(double) * (size_t)G, hipMemcpyDeviceToHost, s));
+    AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+    AGP_HIP_CHECK(ctx, hipGetLastError());
+    ypad.reset();  // (here, not at scope exit: a free synchronises the device)
+    off_d.reset();
     if ((st = status_from_flags(ctx)) != AGP_OK) return st;
     for (int64_t g = 0; g < G; ++g) log_det_a += 2. * hl[(size_t)g];  // fixed order
   } else {
@@ -280,8 +262,8 @@ int sparse_observations(agp_context *ctx, const agp_kernel *k, const DevProgram 
       if (hipSetDevice(ctx->device) != hipSuccess) { stt = AGP_ERR_HIP; return; }
       const DevProgram *hprog = nullptr;
       if ((stt = device_program(h, k, &hprog)) != AGP_OK) return;
-      double *Ag = nullptr;
-      if (dev_malloc(&Ag, sizeof(double) * (size_t)lda_g * (size_t)smax) != hipSuccess) { stt = AGP_ERR_HIP; return; }
+      DevMem<double> Ag;
+      if (Ag.alloc_cached(sizeof(double) * (size_t)lda_g * (size_t)smax) != 0) { stt = AGP_ERR_HIP; return; }
       hipStream_t hs = h->stream;
       for (int64_t g = t; g < n_groups && stt == AGP_OK; g += T) {
         const long long o = offsets[g], sg = offsets[g + 1] - o;
@@ -297,7 +279,6 @@ int sparse_observations(agp_context *ctx, const agp_kernel *k, const DevProgram 
       }
       if (hipStreamSynchronize(hs) != hipSuccess && stt == AGP_OK) stt = AGP_ERR_HIP;
       if (stt != AGP_OK) errors[(size_t)t] = h->last_error;
-      (void)dev_free(Ag);
     };
     std::vector<std::thread> pool;
     for (int t = 1; t < T; ++t) pool.emplace_back(worker, t);
@@ -333,8 +314,8 @@ int sparse_sigma(agp_context *ctx, agp_sparse_fit *f, const double *T, long long
   hipStream_t s = ctx->stream;
   int st = AGP_OK;
   // M = T T^T + W W^T   (the W part summed over the ranks)
-  SPX_HIP(dev_malloc(&w.M0, sizeof(double) * (size_t)ldm * (size_t)m));
-  SPX_HIP(hipMemsetAsync(w.M0, 0, sizeof(double) * (size_t)ldm * (size_t)m, s));
+  AGP_HIP_CHECK(ctx, w.M0.alloc_cached(sizeof(double) * (size_t)ldm * (size_t)m));
+  AGP_HIP_CHECK(ctx, hipMemsetAsync(w.M0, 0, sizeof(double) * (size_t)ldm * (size_t)m, s));
   if (n > 0) syrk_over_observations(s, w, w.M0, ldm, W, ldk, m, n);
   if ((st = comm_all_reduce_device(ctx, comm, w.M0, ldm * m, 0)) != AGP_OK) return st;
   launch_gemm_nt_sub(s, w.M0, ldm, T, ldt, false, T, ldt, false, m, m, m, true);
@@ -343,20 +324,20 @@ int sparse_sigma(agp_context *ctx, agp_sparse_fit *f, const double *T, long long
   if ((st = agp_factor_create(ctx, w.M0, m, ldm, 0, AGP_DEVICE, &f->sigma)) != AGP_OK) return st;
   stage("factor M");
   // CholeskyQR2: Q1^T = L1^-1 [T | W]  (m x (m + n)), G = Q1^T Q1 = L2 L2^T
-  SPX_HIP(hipMemcpy2DAsync(w.Q1T, sizeof(double) * (size_t)ldk, T, sizeof(double) * (size_t)ldt, sizeof(double) * (size_t)m,
+  AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(w.Q1T, sizeof(double) * (size_t)ldk, T, sizeof(double) * (size_t)ldt, sizeof(double) * (size_t)m,
                            (size_t)m, hipMemcpyDeviceToDevice, s));
   if (n > 0 && forward_solve_wide_ok(m, n)) {  // the W columns out of place (no copy), the T columns in place
-    if (!w.Winv) SPX_HIP(dev_malloc(&w.Winv, sizeof(double) * (size_t)m * (size_t)WIDE_BW));
+    if (!w.Winv) AGP_HIP_CHECK(ctx, w.Winv.alloc_cached(sizeof(double) * (size_t)m * (size_t)WIDE_BW));
     invert_wide_blocks(s, f->sigma->A, m, f->sigma->lda, f->sigma->invd, WIDE_BW, w.Winv);
     forward_solve_wide(s, f->sigma->A, m, f->sigma->lda, w.Winv, W, ldk, w.Q1T + (size_t)ldk * (size_t)m, ldk, n);
     forward_solve_mat(s, f->sigma->A, m, f->sigma->lda, f->sigma->invd, w.Q1T, m, ldk, /*rhs_lower=*/true);
   } else {
     if (n > 0)
-      SPX_HIP(hipMemcpyAsync(w.Q1T + (size_t)ldk * (size_t)m, W, sizeof(double) * (size_t)ldk * (size_t)n,
+      AGP_HIP_CHECK(ctx, hipMemcpyAsync(w.Q1T + (size_t)ldk * (size_t)m, W, sizeof(double) * (size_t)ldk * (size_t)n,
                              hipMemcpyDeviceToDevice, s));
     forward_solve_mat(s, f->sigma->A, m, f->sigma->lda, f->sigma->invd, w.Q1T, n + m, ldk);
   }
-  SPX_HIP(hipMemsetAsync(w.M0, 0, sizeof(double) * (size_t)ldm * (size_t)m, s));
+  AGP_HIP_CHECK(ctx, hipMemsetAsync(w.M0, 0, sizeof(double) * (size_t)ldm * (size_t)m, s));
   if (n > 0)  // the W columns of Q1 (summed over the ranks), then the T columns
     syrk_over_observations(s, w, w.M0, ldm, w.Q1T + (size_t)ldk * (size_t)m, ldk, m, n);
   if ((st = comm_all_reduce_device(ctx, comm, w.M0, ldm * m, 0)) != AGP_OK) return st;
@@ -375,18 +356,17 @@ int sparse_sigma(agp_context *ctx, agp_sparse_fit *f, const double *T, long long
     return AGP_OK;
   };
   // vectors: b | v | r | dv | tt (m each) | t (n) ; partial sums of the mat-vecs
-  double *mv = nullptr;
-  SPX_HIP(dev_malloc(&mv, sizeof(double) * (size_t)(5 * mp2 + np2 + 2)));
-  std::unique_ptr<double, void (*)(double *)> mv_guard(mv, [](double *p) { (void)dev_free(p); });
+  DevMem<double> mv;
+  AGP_HIP_CHECK(ctx, mv.alloc_cached(sizeof(double) * (size_t)(5 * mp2 + np2 + 2)));
   double *bvec = mv, *vvec = bvec + mp2, *rvec = vvec + mp2, *dv = rvec + mp2, *tt = dv + mp2, *tvec = tt + mp2;
   const long long cols = std::max(n, m), chunks = (cols + 1023) / 1024;
-  SPX_HIP(dev_malloc(&w.partial, sizeof(double) * (size_t)chunks * (size_t)m));
+  AGP_HIP_CHECK(ctx, w.partial.alloc_cached(sizeof(double) * (size_t)chunks * (size_t)m));
   // b = T y_t + W y_w   (B^T y_aug: :370-372 for a fit, :344-350 for an update)
   if (n > 0) launch_matvec(s, W, ldk, m, n, yw, w.partial, 1.0, 0.0, nullptr, bvec);
   else launch_axpby(s, m, 0.0, nullptr, 0.0, nullptr, bvec);
   if ((st = comm_all_reduce_device(ctx, comm, bvec, m, 0)) != AGP_OK) return st;
   if (yt) launch_matvec(s, T, ldt, m, m, yt, w.partial, 1.0, 1.0, bvec, bvec);
-  SPX_HIP(hipMemcpyAsync(vvec, bvec, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, s));
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(vvec, bvec, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, s));
   if ((st = sigma_solve(vvec)) != AGP_OK) return st;
   // two refinement steps against B itself: r = W (y_w - W^T v) + T (y_t - T^T v), v += (B^T B)^-1 r
   for (int it = 0; it < 2; ++it) {
@@ -400,7 +380,7 @@ int sparse_sigma(agp_context *ctx, agp_sparse_fit *f, const double *T, long long
     if ((st = comm_all_reduce_device(ctx, comm, rvec, m, 0)) != AGP_OK) return st;
     launch_colvec_dot(s, T, ldt, m, m, vvec, -1.0, 1.0, yt, tt);
     launch_matvec(s, T, ldt, m, m, tt, w.partial, 1.0, 1.0, rvec, rvec);
-    SPX_HIP(hipMemcpyAsync(dv, rvec, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, s));
+    AGP_HIP_CHECK(ctx, hipMemcpyAsync(dv, rvec, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, s));
     if ((st = sigma_solve(dv)) != AGP_OK) return st;
     launch_axpby(s, m, 1.0, vvec, 1.0, dv, vvec);
     if (it == 0) {
@@ -409,13 +389,13 @@ int sparse_sigma(agp_context *ctx, agp_sparse_fit *f, const double *T, long long
       double *nrm = tvec + np2, h[2] = {1., 0.};
       launch_dot(s, dv, dv, m, nrm);
       launch_dot(s, vvec, vvec, m, nrm + 1);
-      SPX_HIP(hipMemcpyAsync(h, nrm, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-      SPX_HIP(hipStreamSynchronize(s));
+      AGP_HIP_CHECK(ctx, hipMemcpyAsync(h, nrm, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+      AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
       if (h[0] <= 1e-20 * h[1]) break;
     }
   }
-  SPX_HIP(dev_malloc(&f->v, sizeof(double) * (size_t)m));
-  SPX_HIP(hipMemcpyAsync(f->v, vvec, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, s));
+  AGP_HIP_CHECK(ctx, f->v.alloc_cached(sizeof(double) * (size_t)m));
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(f->v, vvec, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, s));
   if (bq) {  // y_b = R^-T P^T B^T y_aug = L2^-1 L1^-1 b  (:590)
     forward_solve_mat(s, f->sigma->A, m, f->sigma->lda, f->sigma->invd, bvec, 1, m);
     forward_solve_mat(s, f->sigma2->A, m, f->sigma2->lda, f->sigma2->invd, bvec, 1, m);
@@ -423,24 +403,23 @@ int sparse_sigma(agp_context *ctx, agp_sparse_fit *f, const double *T, long long
   }
   stage("information + refinement");
   // L_acc = L1 L2 (for update): C = 0 - L1z (L2z^T)^T, negated
-  SPX_HIP(dev_malloc(&f->Lacc, sizeof(double) * (size_t)ldm * (size_t)m));
+  AGP_HIP_CHECK(ctx, f->Lacc.alloc_cached(sizeof(double) * (size_t)ldm * (size_t)m));
   {
     double *L1z = w.M0;  // m x ldm scratch, no longer needed
-    double *L2z = nullptr;
-    SPX_HIP(dev_malloc(&L2z, sizeof(double) * (size_t)ldm * (size_t)m));
-    std::unique_ptr<double, void (*)(double *)> g2(L2z, [](double *p) { (void)dev_free(p); });
-    SPX_HIP(hipMemcpy2DAsync(L1z, sizeof(double) * (size_t)ldm, f->sigma->A, sizeof(double) * (size_t)f->sigma->lda,
+    DevMem<double> L2z;
+    AGP_HIP_CHECK(ctx, L2z.alloc_cached(sizeof(double) * (size_t)ldm * (size_t)m));
+    AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(L1z, sizeof(double) * (size_t)ldm, f->sigma->A, sizeof(double) * (size_t)f->sigma->lda,
                              sizeof(double) * (size_t)m, (size_t)m, hipMemcpyDeviceToDevice, s));
-    SPX_HIP(hipMemcpy2DAsync(L2z, sizeof(double) * (size_t)ldm, f->sigma2->A, sizeof(double) * (size_t)f->sigma2->lda,
+    AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(L2z, sizeof(double) * (size_t)ldm, f->sigma2->A, sizeof(double) * (size_t)f->sigma2->lda,
                              sizeof(double) * (size_t)m, (size_t)m, hipMemcpyDeviceToDevice, s));
     launch_zero_upper(s, L1z, ldm, m);
     launch_zero_upper(s, L2z, ldm, m);
-    SPX_HIP(hipMemsetAsync(f->Lacc, 0, sizeof(double) * (size_t)ldm * (size_t)m, s));
+    AGP_HIP_CHECK(ctx, hipMemsetAsync(f->Lacc, 0, sizeof(double) * (size_t)ldm * (size_t)m, s));
     launch_gemm_nt_sub(s, f->Lacc, ldm, L1z, ldm, false, L2z, ldm, true, m, m, m, false);
     launch_negate(s, f->Lacc, ldm, m, nullptr);
-    SPX_HIP(hipStreamSynchronize(s));
+    AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
   }
-  SPX_HIP(hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipGetLastError());
   return AGP_OK;
 }
 
@@ -455,12 +434,8 @@ void agp_sparse_fit_destroy(agp_sparse_fit *f) {
   f->kuu.reset();
   if (f->sigma) agp_fit_destroy(f->sigma);
   if (f->sigma2) agp_fit_destroy(f->sigma2);
-  if (f->Lacc) (void)dev_free(f->Lacc);
-  if (f->v) (void)dev_free(f->v);
   f->kz.reset();
   f->kp.reset();
-  if (f->R) (void)dev_free(f->R);
-  if (f->perm) (void)dev_free(f->perm);
   delete f;
 }
 
@@ -490,21 +465,19 @@ __global__ __launch_bounds__(256) void add_to_diagonal_kernel(double *A, long lo
 
 // LL^T of K_uu + nugget I  (compute_internal_components, sparse_gp.hpp:674-679)
 static int factor_kuu(agp_context *ctx, const agp_kernel *k, const DevProgram *dprog, const FeatView &uv, double nugget,
-                      std::shared_ptr<agp_fit> *out, double **T_out) {
+                      std::shared_ptr<agp_fit> *out, DevMem<double> *T_out) {
   const long long m = uv.n, ldm = factor_ld(m);
   hipStream_t s = ctx->stream;
-  double *nug = nullptr, *T = nullptr;
-  SPX_HIP(dev_malloc(&nug, sizeof(double) * (size_t)round_up(m, 2)));
-  std::unique_ptr<double, void (*)(double *)> nug_guard(nug, [](double *p) { (void)dev_free(p); });
+  DevMem<double> nug, T;
+  AGP_HIP_CHECK(ctx, nug.alloc_cached(sizeof(double) * (size_t)round_up(m, 2)));
   launch_axpby(s, m, 0.0, nullptr, nugget, nullptr, nug);
-  SPX_HIP(dev_malloc(&T, sizeof(double) * (size_t)ldm * (size_t)m));
-  std::unique_ptr<double, void (*)(double *)> t_guard(T, [](double *p) { (void)dev_free(p); });
+  AGP_HIP_CHECK(ctx, T.alloc_cached(sizeof(double) * (size_t)ldm * (size_t)m));
   launch_gram(s, dprog, uv, uv, true, true, T, ldm, nug, nullptr, &k->prog);
   agp_fit *kuu = nullptr;
   const int st = agp_factor_create(ctx, T, m, ldm, 0, AGP_DEVICE, &kuu);
   *out = std::shared_ptr<agp_fit>(kuu, [](agp_fit *p) { agp_fit_destroy(p); });
   if (st != AGP_OK) return st;
-  if (T_out) *T_out = t_guard.release();
+  if (T_out) *T_out = std::move(T);
   return AGP_OK;
 }
 
@@ -525,9 +498,8 @@ static int factor_kuu_pivoted(agp_context *ctx, const agp_kernel *k, const DevPr
                               std::shared_ptr<agp_ldlt> *out) {
   const long long m = uv.n, ldq = round_up(m, 2);
   hipStream_t s = ctx->stream;
-  double *K = nullptr;
-  SPX_HIP(dev_malloc(&K, sizeof(double) * (size_t)ldq * (size_t)m));
-  std::unique_ptr<double, void (*)(double *)> guard(K, [](double *p) { (void)dev_free(p); });
+  DevMem<double> K;
+  AGP_HIP_CHECK(ctx, K.alloc_cached(sizeof(double) * (size_t)ldq * (size_t)m));
   launch_gram(s, dprog, uv, uv, true, false, K, ldq, nullptr, nullptr, &k->prog);
   hipLaunchKernelGGL(add_to_diagonal_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, K, ldq, m, nugget);
   agp_ldlt *kz = nullptr;
@@ -566,8 +538,8 @@ static int sparse_fit_create_pivoted(agp_context *ctx, const agp_kernel *k, cons
   if ((st = to_device(ctx, u, true, f->u.get())) != AGP_OK) return st;
   if ((st = factor_kuu_pivoted(ctx, k, dprog, f->u->v, inducing_nugget, &f->kz)) != AGP_OK) return st;
   f->kp = f->kz;
-  SPX_HIP(dev_malloc(&w.T, sizeof(double) * (size_t)ldm * (size_t)m));
-  SPX_HIP(hipMemsetAsync(w.T, 0, sizeof(double) * (size_t)ldm * (size_t)m, s));
+  AGP_HIP_CHECK(ctx, w.T.alloc_cached(sizeof(double) * (size_t)ldm * (size_t)m));
+  AGP_HIP_CHECK(ctx, hipMemsetAsync(w.T, 0, sizeof(double) * (size_t)ldm * (size_t)m, s));
   hipLaunchKernelGGL(ldlt_root_kernel, dim3((unsigned)((m + 255) / 256), (unsigned)m), dim3(256), 0, s, f->kz->A, f->kz->lda,
                      f->kz->q_dev, m, w.T, ldm);
   stage("K_uu + pivoted factor");
@@ -579,22 +551,21 @@ static int sparse_fit_create_pivoted(agp_context *ctx, const agp_kernel *k, cons
   stage("pivoted QR of B");
   // negative log likelihood (:524-596): log|K| = log|A| + 2 log|R| - log|K_uu|; q = y^T A^-1 y - y_b^T y_b, y_b = R^-T P^T K_uf A^-1 y
   const long long chunks = (std::max(n, m) + 1023) / 1024;
-  double *vb = nullptr;
-  SPX_HIP(dev_malloc(&vb, sizeof(double) * ((size_t)chunks * (size_t)m + (size_t)3 * (size_t)ldk)));
-  std::unique_ptr<double, void (*)(double *)> vb_guard(vb, [](double *p) { (void)dev_free(p); });
+  DevMem<double> vb;
+  AGP_HIP_CHECK(ctx, vb.alloc_cached(sizeof(double) * ((size_t)chunks * (size_t)m + (size_t)3 * (size_t)ldk)));
   double *partial = vb, *bvec = vb + (size_t)chunks * (size_t)m, *yb = bvec + ldk, *rdiag = yb + ldk;
   launch_matvec(s, w.Kuf, ldk, m, n, yw, partial, 1.0, 0.0, nullptr, bvec);
   qr_sqrt_solve(s, f->R, ldk, f->perm, m, bvec, ldk, yb, ldk, 1);
   launch_dot(s, yw, yw, n, ctx->d_scalars + 1);
   launch_dot(s, yb, yb, m, ctx->d_scalars + 2);
-  SPX_HIP(hipMemcpy2DAsync(rdiag, sizeof(double), f->R, sizeof(double) * (size_t)(ldk + 1), sizeof(double), (size_t)m,
+  AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(rdiag, sizeof(double), f->R, sizeof(double) * (size_t)(ldk + 1), sizeof(double), (size_t)m,
                            hipMemcpyDeviceToDevice, s));
   std::vector<double> hr((size_t)m);
-  SPX_HIP(hipMemcpyAsync(hr.data(), rdiag, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, s));
-  SPX_HIP(hipMemcpyAsync(ctx->h_scalars, ctx->d_scalars, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (information) SPX_HIP(hipMemcpyAsync(information, f->v, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, s));
-  SPX_HIP(hipStreamSynchronize(s));
-  SPX_HIP(hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(hr.data(), rdiag, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_scalars, ctx->d_scalars, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (information) AGP_HIP_CHECK(ctx, hipMemcpyAsync(information, f->v, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
   double log_det_r = 0., log_det_kuu = 0.;
   for (long long i = 0; i < m; ++i) {
     log_det_r += std::log(std::fabs(hr[(size_t)i]));     // matrixR().diagonal().array().cwiseAbs().log().sum() (:549-550)
@@ -625,7 +596,7 @@ static int features_checksum(agp_context *ctx, const agp_features *u, double *ou
   const double *p = u->coords;
   if (u->location != AGP_HOST) {
     host.resize(cnt);
-    SPX_HIP(hipMemcpy(host.data(), u->coords, sizeof(double) * cnt, hipMemcpyDeviceToHost));
+    AGP_HIP_CHECK(ctx, hipMemcpy(host.data(), u->coords, sizeof(double) * cnt, hipMemcpyDeviceToHost));
     p = host.data();
   }
   unsigned long long h = 1469598103934665603ull;
@@ -688,7 +659,7 @@ static int sparse_fit_create_fast(agp_context *ctx, agp_comm *comm, const agp_ke
 
     // K_uu + inducing_nugget I  (:674-679) -> LL^T ; T = L_u with explicit zeros above the diagonal
     if ((e = factor_kuu(ctx, k, dprog, f->u->v, inducing_nugget, &f->kuu, &w.T)) != AGP_OK) return e;
-    SPX_HIP(hipMemcpy2DAsync(w.T, sizeof(double) * (size_t)ldm, f->kuu->A, sizeof(double) * (size_t)f->kuu->lda,
+    AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(w.T, sizeof(double) * (size_t)ldm, f->kuu->A, sizeof(double) * (size_t)f->kuu->lda,
                              sizeof(double) * (size_t)m, (size_t)m, hipMemcpyDeviceToDevice, s));
     launch_zero_upper(s, w.T, ldm, m);  // K_uu^T/2 = L_u^T (sqrt_transpose, :349): its transpose L_u
     stage("K_uu + factor");
@@ -704,14 +675,14 @@ static int sparse_fit_create_fast(agp_context *ctx, agp_comm *comm, const agp_ke
     return st;
   launch_dot(s, yw, yw, n, ctx->d_scalars + 1);  // y^T A^-1 y = y_w^T y_w  (:583-592); after the factor calls, which reset the scalars
   // negative log likelihood (:524-596): log|K| = log|A| + log|B^T B| - log|K_uu'|
-  SPX_HIP(hipMemcpyAsync(ctx->h_scalars, ctx->d_scalars, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (information) SPX_HIP(hipMemcpyAsync(information, f->v, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_scalars, ctx->d_scalars, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (information) AGP_HIP_CHECK(ctx, hipMemcpyAsync(information, f->v, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, s));
   if (comm) {
     if ((st = comm_wait_stream(ctx, s)) != AGP_OK) return st;  // bounded: a dead peer is AGP_ERR_COMM, not a hang
   } else {
-    SPX_HIP(hipStreamSynchronize(s));
+    AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
   }
-  SPX_HIP(hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipGetLastError());
   // sums over the observations of all ranks: log|A|, y^T A^-1 y, n
   double sums[3] = {log_det_a, ctx->h_scalars[1], (double)n};
   if (comm && (st = agp_comm_all_reduce_host(comm, sums, 3, 0)) != AGP_OK) return st;
@@ -780,45 +751,43 @@ static int sparse_pivoted_from_rows(agp_context *ctx, agp_sparse_fit *f, const d
   const long long m = f->m, rows = (T ? m : 0) + n, ldb = round_up(rows, 2), ldr = round_up(m, 2), ldm = factor_ld(m);
   const long long extra = (yt || yw) ? 1 : 0;
   hipStream_t s = ctx->stream;
-  double *B = nullptr, *aux = nullptr;
-  SPX_HIP(dev_malloc(&B, sizeof(double) * (size_t)ldb * (size_t)(m + extra)));
-  std::unique_ptr<double, void (*)(double *)> b_guard(B, [](double *p) { (void)dev_free(p); });
-  SPX_HIP(dev_malloc(&aux, sizeof(double) * (size_t)(2 * ldr + 8)));  // tau | norms | state
-  std::unique_ptr<double, void (*)(double *)> a_guard(aux, [](double *p) { (void)dev_free(p); });
+  DevMem<double> B, aux;
+  AGP_HIP_CHECK(ctx, B.alloc_cached(sizeof(double) * (size_t)ldb * (size_t)(m + extra)));
+  AGP_HIP_CHECK(ctx, aux.alloc_cached(sizeof(double) * (size_t)(2 * ldr + 8)));  // tau | norms | state
   double *tau = aux, *norms = aux + ldr, *state = norms + ldr;
-  SPX_HIP(hipMemsetAsync(B, 0, sizeof(double) * (size_t)ldb * (size_t)(m + extra), s));
+  AGP_HIP_CHECK(ctx, hipMemsetAsync(B, 0, sizeof(double) * (size_t)ldb * (size_t)(m + extra), s));
   long long r0 = 0;
   const dim3 tb(256);
   if (T) {
     hipLaunchKernelGGL(transpose_into_kernel, dim3((unsigned)((m + 31) / 32), (unsigned)((m + 31) / 32)), tb, 0, s, T, ldt, m, m, B,
                        ldb, 0ll);
-    if (yt) SPX_HIP(hipMemcpyAsync(B + (size_t)ldb * (size_t)m, yt, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, s));
+    if (yt) AGP_HIP_CHECK(ctx, hipMemcpyAsync(B + (size_t)ldb * (size_t)m, yt, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, s));
     r0 = m;
   }
   if (n > 0) {
     hipLaunchKernelGGL(transpose_into_kernel, dim3((unsigned)((m + 31) / 32), (unsigned)((n + 31) / 32)), tb, 0, s, W, ldw, m, n, B,
                        ldb, r0);
-    if (yw) SPX_HIP(hipMemcpyAsync(B + (size_t)ldb * (size_t)m + r0, yw, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
+    if (yw) AGP_HIP_CHECK(ctx, hipMemcpyAsync(B + (size_t)ldb * (size_t)m + r0, yw, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
   }
-  if (!f->perm) SPX_HIP(dev_malloc(&f->perm, sizeof(long long) * (size_t)m));
+  if (!f->perm) AGP_HIP_CHECK(ctx, f->perm.alloc_cached(sizeof(long long) * (size_t)m));
   colpiv_qr(s, B, ldb, rows, m, extra, tau, f->perm, norms, state);
   double hstate[4] = {0., 0., 0., 0.};
-  SPX_HIP(hipMemcpyAsync(hstate, state, sizeof(hstate), hipMemcpyDeviceToHost, s));
-  SPX_HIP(hipStreamSynchronize(s));
-  SPX_HIP(hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(hstate, state, sizeof(hstate), hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
   f->rank = (long long)hstate[3];
   const long long nonzero_pivots = (long long)hstate[2];
-  if (!f->R) SPX_HIP(dev_malloc(&f->R, sizeof(double) * (size_t)ldr * (size_t)m));
+  if (!f->R) AGP_HIP_CHECK(ctx, f->R.alloc_cached(sizeof(double) * (size_t)ldr * (size_t)m));
   qr_extract_r(s, B, ldb, m, f->R, ldr, 0.0);
   if (extra) {
-    if (!f->v) SPX_HIP(dev_malloc(&f->v, sizeof(double) * (size_t)m));
+    if (!f->v) AGP_HIP_CHECK(ctx, f->v.alloc_cached(sizeof(double) * (size_t)m));
     qr_back_solve(s, f->R, ldr, f->perm, m, nonzero_pivots, B + (size_t)ldb * (size_t)m, f->v);  // the last column is Q^T y_aug
   }
   if (inflate && f->rank < m) qr_extract_r(s, B, ldb, m, f->R, ldr, 1e-10);
-  if (!f->Lacc) SPX_HIP(dev_malloc(&f->Lacc, sizeof(double) * (size_t)ldm * (size_t)m));
+  if (!f->Lacc) AGP_HIP_CHECK(ctx, f->Lacc.alloc_cached(sizeof(double) * (size_t)ldm * (size_t)m));
   qr_root(s, f->R, ldr, f->perm, m, f->Lacc, ldm);
-  SPX_HIP(hipStreamSynchronize(s));
-  SPX_HIP(hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
   return AGP_OK;
 }
 
@@ -861,16 +830,15 @@ int agp_sparse_fit_update(agp_context *ctx, const agp_kernel *k, const agp_spars
                                 &yw, &log_det_a, stage, f->kuu ? nullptr : f->kp.get())) != AGP_OK)
     return st;
   const long long ldm = factor_ld(m);
-  double *yt = nullptr;
-  SPX_HIP(dev_malloc(&yt, sizeof(double) * (size_t)round_up(m, 2)));
-  std::unique_ptr<double, void (*)(double *)> yt_guard(yt, [](double *p) { (void)dev_free(p); });
+  DevMem<double> yt;
+  AGP_HIP_CHECK(ctx, yt.alloc_cached(sizeof(double) * (size_t)round_up(m, 2)));
   launch_colvec_dot(s, old->Lacc, ldm, m, m, old->v, 1.0, 0.0, nullptr, yt);  // y_t = L_acc^T v_old  (:344-347)
   if (old->R) {
     // pivoted form: the reference's own algorithm (:336-371) - column-pivoted QR of B = [R_old P_old^T; A^-1/2 K_fu]
     // with y_aug = [R_old P_old^T v_old; A^-1/2 y] carried as one more column, v = B_qr.solve(y_aug)
     if ((st = sparse_pivoted_from_rows(ctx, f.get(), old->Lacc, ldm, w.Kuf, round_up(m, 2), n, yt, yw, true)) != AGP_OK) return st;
-    if (information) SPX_HIP(hipMemcpyAsync(information, f->v, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, s));
-    SPX_HIP(hipStreamSynchronize(s));
+    if (information) AGP_HIP_CHECK(ctx, hipMemcpyAsync(information, f->v, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, s));
+    AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
     f->nll = std::nan("");
     *out = f.release();
     return AGP_OK;
@@ -882,8 +850,8 @@ int agp_sparse_fit_update(agp_context *ctx, const agp_kernel *k, const agp_spars
     st = sparse_pivoted_from_rows(ctx, f.get(), old->Lacc, ldm, w.Kuf, round_up(m, 2), n, yt, yw, true);
   }
   if (st != AGP_OK) return st;
-  if (information) SPX_HIP(hipMemcpyAsync(information, f->v, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, s));
-  SPX_HIP(hipStreamSynchronize(s));
+  if (information) AGP_HIP_CHECK(ctx, hipMemcpyAsync(information, f->v, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
   f->nll = std::nan("");  // the likelihood of an updated fit is not defined by the reference
   *out = f.release();
   return AGP_OK;
@@ -914,9 +882,8 @@ int agp_sparse_fit_from_prediction(agp_context *ctx, const agp_kernel *k, const 
   f->u = std::shared_ptr<DeviceFeatures>(new DeviceFeatures(), [](DeviceFeatures *d) { d->release(); delete d; });
   if ((st = to_device(ctx, z, true, f->u.get())) != AGP_OK) return st;
   // buffers: K_zz | C (later B_z) | W (m x m each, ld ldq) | mean, scratch (2 ldq)
-  double *buf = nullptr;
-  SPX_HIP(dev_malloc(&buf, sizeof(double) * ((size_t)3 * (size_t)ldq * (size_t)m + (size_t)2 * (size_t)ldq)));
-  std::unique_ptr<double, void (*)(double *)> guard(buf, [](double *p) { (void)dev_free(p); });
+  DevMem<double> buf;
+  AGP_HIP_CHECK(ctx, buf.alloc_cached(sizeof(double) * ((size_t)3 * (size_t)ldq * (size_t)m + (size_t)2 * (size_t)ldq)));
   double *Kzz = buf, *C = Kzz + (size_t)ldq * (size_t)m, *Bz = C + (size_t)ldq * (size_t)m, *mv = Bz + (size_t)ldq * (size_t)m,
          *mw = mv + ldq;
   launch_gram(s, dprog, f->u->v, f->u->v, true, false, Kzz, ldq, nullptr, nullptr, &k->prog);  // K_zz, both triangles (:416-417)
@@ -927,13 +894,13 @@ int agp_sparse_fit_from_prediction(agp_context *ctx, const agp_kernel *k, const 
     if (st != AGP_OK) return st;
   }
   const hipMemcpyKind kind = location == AGP_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-  SPX_HIP(hipMemcpyAsync(mv, mean, sizeof(double) * (size_t)m, kind, s));
-  SPX_HIP(hipMemcpy2DAsync(C, sizeof(double) * (size_t)ldq, covariance, sizeof(double) * (size_t)ldc, sizeof(double) * (size_t)m,
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(mv, mean, sizeof(double) * (size_t)m, kind, s));
+  AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(C, sizeof(double) * (size_t)ldq, covariance, sizeof(double) * (size_t)ldc, sizeof(double) * (size_t)m,
                            (size_t)m, kind, s));
-  if (location == AGP_HOST) SPX_HIP(hipStreamSynchronize(s));
+  if (location == AGP_HOST) AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
   ldlt_solve(s, f->kz->A, f->kz->lda, m, f->kz->q_dev, mw, mv, ldq, 1);                        // information (:426)
-  SPX_HIP(dev_malloc(&f->v, sizeof(double) * (size_t)m));
-  SPX_HIP(hipMemcpyAsync(f->v, mv, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, s));
+  AGP_HIP_CHECK(ctx, f->v.alloc_cached(sizeof(double) * (size_t)m));
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(f->v, mv, sizeof(double) * (size_t)m, hipMemcpyDeviceToDevice, s));
   {
     // DEFAULT_NUGGET on the diagonal of the predictive covariance (:20, 423-425)
     hipLaunchKernelGGL(add_to_diagonal_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, C, ldq, m, 1e-8);
@@ -942,7 +909,7 @@ int agp_sparse_fit_from_prediction(agp_context *ctx, const agp_kernel *k, const 
     std::unique_ptr<agp_ldlt, void (*)(agp_ldlt *)> cl_guard(cl, agp_ldlt_destroy);
     if (st != AGP_OK) return st;
     ldlt_sqrt_solve(s, cl->A, cl->lda, m, cl->q_dev, Bz, Kzz, ldq, m);                        // sigma_inv_sqrt (:453)
-    SPX_HIP(hipStreamSynchronize(s));
+    AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
   }
   // (R, P) = QR(B_z) (:454-458): B_z is handed over as W^T, i.e. W = B_z^T ... the helper transposes, so pass B_z^T's
   // transpose: rows of B are the rows of B_z
@@ -952,9 +919,9 @@ int agp_sparse_fit_from_prediction(agp_context *ctx, const agp_kernel *k, const 
                        m, Wt, ldq, 0ll);
     if ((st = sparse_pivoted_from_rows(ctx, f.get(), nullptr, 0, Wt, ldq, m, nullptr, nullptr, false)) != AGP_OK) return st;
   }
-  if (information) SPX_HIP(hipMemcpyAsync(information, f->v, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, s));
-  SPX_HIP(hipStreamSynchronize(s));
-  SPX_HIP(hipGetLastError());
+  if (information) AGP_HIP_CHECK(ctx, hipMemcpyAsync(information, f->v, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
   if (numerical_rank) *numerical_rank = f->rank;
   f->nll = std::nan("");
   *out = f.release();
@@ -1005,8 +972,7 @@ static int sparse_predict_common(agp_context *ctx, const agp_kernel *k, const ag
   const size_t q_elems = (size_t)ldq * (size_t)chunk;
   const size_t p_elems = mode == 2 ? (size_t)ldc * (size_t)chunk : (size_t)ldc;
   const bool pivoted = f->kz || f->R;  // a third m x M buffer: the pivoted substitutions are out of place
-  st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes,
-                 sizeof(double) * ((pivoted ? 3 : 2) * q_elems + (size_t)ldc + p_elems));
+  st = reserve_ws(ctx, ctx->ws_aux, sizeof(double) * ((pivoted ? 3 : 2) * q_elems + (size_t)ldc + p_elems));
   if (st != AGP_OK) { dxs.release(); return st; }
   double *Q = ctx->ws_aux, *S = Q + q_elems, *mean_d = S + q_elems, *prior = mean_d + ldc, *X = prior + p_elems;
   hipStream_t s = ctx->stream;

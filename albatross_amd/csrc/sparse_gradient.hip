@@ -43,21 +43,6 @@ using namespace agp;
 
 namespace {
 
-struct DevFree {
-  void operator()(void *p) const { (void)dev_free(p); }
-};
-template <class T>
-using dev_ptr = std::unique_ptr<T, DevFree>;
-
-#define SG_HIP(expr)                                                                     \
-  do {                                                                                   \
-    hipError_t _e = (expr);                                                              \
-    if (_e != hipSuccess) {                                                              \
-      ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(_e);               \
-      return AGP_ERR_HIP;                                                                \
-    }                                                                                    \
-  } while (0)
-
 // group of global point i: off[g] <= i < off[g + 1]  (off has G + 1 entries)
 __device__ __forceinline__ long long find_group(const long long *__restrict__ off, long long G, long long i) {
   long long lo = 0, hi = G;
@@ -205,9 +190,9 @@ __global__ __launch_bounds__(256) void sparse_grad_reduce_kernel(const double *_
 struct InverseBlocks {
   std::vector<long long> tab;  // off | roff | rld | tstart, G + 1 entries each
   long long *h_off = nullptr, *h_roff = nullptr, *h_rld = nullptr, *h_tstart = nullptr;
-  dev_ptr<long long> d_tab;
+  DevMem<long long> d_tab;
   const long long *d_off = nullptr, *d_roff = nullptr, *d_rld = nullptr, *d_tstart = nullptr;
-  dev_ptr<double> Rg, Bg;
+  DevMem<double> Rg, Bg;
   long long smax = 0, lda_b = 0, stride_A = 0, stride_I = 0, r_elems = 0, tiles_blocks = 0;
   bool uniform = false, slabbed = false;
   double *Nm = nullptr;  // N (m x n, ld round_up(m, 2)): in the fit's pool
@@ -237,16 +222,11 @@ int inverse_blocks_begin(agp_context_impl *ctx, const SparseScratch &w, long lon
     b.tiles_blocks += lower_tiles(sg);
   }
   b.h_off[G] = n; b.h_roff[G] = b.r_elems; b.h_rld[G] = 0; b.h_tstart[G] = b.tiles_blocks;
-  long long *tab_raw = nullptr;
-  SG_HIP(dev_malloc(&tab_raw, sizeof(long long) * b.tab.size()));
-  b.d_tab.reset(tab_raw);
-  b.d_off = tab_raw; b.d_roff = b.d_off + (G + 1); b.d_rld = b.d_roff + (G + 1); b.d_tstart = b.d_rld + (G + 1);
-  SG_HIP(hipMemcpyAsync(tab_raw, b.tab.data(), sizeof(long long) * b.tab.size(), hipMemcpyHostToDevice, s));
-  double *Rg = nullptr, *Bg = nullptr;
-  SG_HIP(dev_malloc(&Rg, sizeof(double) * (size_t)round_up(b.r_elems, 2)));
-  b.Rg.reset(Rg);
-  SG_HIP(dev_malloc(&Bg, sizeof(double) * (size_t)round_up(b.r_elems, 2)));
-  b.Bg.reset(Bg);
+  AGP_HIP_CHECK(ctx, b.d_tab.alloc_cached(sizeof(long long) * b.tab.size()));
+  b.d_off = b.d_tab; b.d_roff = b.d_off + (G + 1); b.d_rld = b.d_roff + (G + 1); b.d_tstart = b.d_rld + (G + 1);
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(b.d_tab, b.tab.data(), sizeof(long long) * b.tab.size(), hipMemcpyHostToDevice, s));
+  AGP_HIP_CHECK(ctx, b.Rg.alloc_cached(sizeof(double) * (size_t)round_up(b.r_elems, 2)));
+  AGP_HIP_CHECK(ctx, b.Bg.alloc_cached(sizeof(double) * (size_t)round_up(b.r_elems, 2)));
   return AGP_OK;
 }
 
@@ -285,7 +265,7 @@ int inverse_blocks_run(agp_context_impl *ctx, SparseScratch &w, const agp_sparse
   const agp_fit *L2 = fit->sigma2;
   double *Q1W = w.Q1T + (size_t)ldk * (size_t)m, *Z = nullptr, *Nm = nullptr;
   if (forward_solve_wide_ok(m, n)) {  // out of place into W's buffer (W is dead: aw has been formed)
-    if (!w.Winv) SG_HIP(dev_malloc(&w.Winv, sizeof(double) * (size_t)m * (size_t)WIDE_BW));
+    if (!w.Winv) AGP_HIP_CHECK(ctx, w.Winv.alloc_cached(sizeof(double) * (size_t)m * (size_t)WIDE_BW));
     invert_wide_blocks(s, L2->A, m, L2->lda, L2->invd, WIDE_BW, w.Winv);
     forward_solve_wide(s, L2->A, m, L2->lda, w.Winv, Q1W, ldk, w.Kuf, ldk, n);
     Z = w.Kuf; Nm = w.Q1T;
@@ -293,7 +273,7 @@ int inverse_blocks_run(agp_context_impl *ctx, SparseScratch &w, const agp_sparse
     forward_solve_mat(s, L2->A, m, L2->lda, L2->invd, Q1W, n, ldk);
     Z = Q1W; Nm = w.Kuf;
   }
-  SG_HIP(hipMemsetAsync(Nm, 0, sizeof(double) * (size_t)ldk * (size_t)n, s));
+  AGP_HIP_CHECK(ctx, hipMemsetAsync(Nm, 0, sizeof(double) * (size_t)ldk * (size_t)n, s));
   per_group([&](long long g, long long sg, long long cnt) {
     const size_t o = (size_t)offsets[g] * (size_t)ldk;
     launch_gemm_nt_sub_batched(s, Nm + o, ldk, sg * ldk, Z + o, ldk, false, sg * ldk, Rg + h_roff[g], h_rld[g], true, stride_A, m, sg, sg,
@@ -466,15 +446,13 @@ int agp_sparse_nll_gradient(agp_context *c, const agp_kernel *k, const agp_featu
   if (tiles_blocks > 0x7fffffffLL || tiles_fu > 0x7fffffffLL) return fail(AGP_ERR_INVALID_ARGUMENT);
 
   // ---- device buffers beyond the pool ----
-  double *Wn = nullptr, *vec = nullptr;
-  SG_HIP(dev_malloc(&Wn, sizeof(double) * (size_t)ldm * (size_t)m));
-  dev_ptr<double> wn_guard(Wn);
+  DevMem<double> Wn, vec;
+  AGP_HIP_CHECK(ctx, Wn.alloc_cached(sizeof(double) * (size_t)ldm * (size_t)m));
   const bool tx_copy = ntc > 0 && x->location == AGP_HOST, tu_copy = ntc > 0 && u->location == AGP_HOST;
   const size_t part_elems = (size_t)(tiles_blocks + tiles_fu + tiles_uu) * GRAD_GROUP;
   const size_t vec_elems = 3 * (size_t)np2 + (size_t)mp2 + 8 + (size_t)round_up(AGP_MAX_GRADIENT_SLOTS, 2) + part_elems +
                            (tx_copy ? (size_t)np2 * (size_t)ntc : 0) + (tu_copy ? (size_t)mp2 * (size_t)ntc : 0);
-  SG_HIP(dev_malloc(&vec, sizeof(double) * vec_elems));
-  dev_ptr<double> vec_guard(vec);
+  AGP_HIP_CHECK(ctx, vec.alloc_cached(sizeof(double) * vec_elems));
   double *aw = vec, *alpha = aw + np2, *diag = alpha + np2, *q = diag + np2, *scal = q + mp2, *grad_d = scal + 8;
   double *part_blocks = grad_d + round_up(AGP_MAX_GRADIENT_SLOTS, 2), *part_fu = part_blocks + (size_t)tiles_blocks * GRAD_GROUP,
          *part_uu = part_fu + (size_t)tiles_fu * GRAD_GROUP, *tcopy = part_uu + (size_t)tiles_uu * GRAD_GROUP;
@@ -482,7 +460,7 @@ int agp_sparse_nll_gradient(agp_context *c, const agp_kernel *k, const agp_featu
   long long ld_tx = 0, ld_tu = 0;
   if ((st = stage_tangents(ctx, s, tangents_x, ldtx, x->location, n, ntc, &tcopy, &tang_x, &ld_tx)) != AGP_OK) return st;
   if ((st = stage_tangents(ctx, s, tangents_u, ldtu, u->location, m, ntc, &tcopy, &tang_u, &ld_tu)) != AGP_OK) return st;
-  SG_HIP(hipStreamSynchronize(s));  // (pageable sources)
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));  // (pageable sources)
 
   // ---- R_g, alpha, Z, N_g and the lower triangles of bd(Kt^-1)_g ----
   if ((st = inverse_blocks_run(ctx, w, fit.get(), offsets, G, n, m, yw, aw, alpha, ib, stage)) != AGP_OK) return st;
@@ -519,7 +497,7 @@ int agp_sparse_nll_gradient(agp_context *c, const agp_kernel *k, const agp_featu
   stage("gradient: (H E)^T");
 
   // ---- -W_uu = E^T (H E): lower tiles, summed over the observations through the fit's split-K slabs ----
-  SG_HIP(hipMemsetAsync(Wn, 0, sizeof(double) * (size_t)ldm * (size_t)m, s));
+  AGP_HIP_CHECK(ctx, hipMemsetAsync(Wn, 0, sizeof(double) * (size_t)ldm * (size_t)m, s));
   gemm_over_observations(s, w, Wn, ldm, Et, Nm, ldk, m, n);
   hipLaunchKernelGGL(strided_sum_kernel, dim3(1), dim3(1024), 0, s, diag, n, 1LL, 0.5, scal);           // 1/2 trace(bd(G))
   hipLaunchKernelGGL(strided_sum_kernel, dim3(1), dim3(1024), 0, s, Wn, m, ldm + 1, -0.5, scal + 1);    // 1/2 trace(W_uu)
@@ -554,13 +532,13 @@ int agp_sparse_nll_gradient(agp_context *c, const agp_kernel *k, const agp_featu
   }
   stage("gradient: contractions");
 
-  SG_HIP(hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipGetLastError());
   double h_scal[2] = {nan, nan};
-  SG_HIP(hipMemcpyAsync(h_scal, scal, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (n_slots > 0) SG_HIP(hipMemcpyAsync(grad_nll, grad_d, sizeof(double) * (size_t)n_slots, hipMemcpyDeviceToHost, s));
-  if (alpha_out) SG_HIP(hipMemcpyAsync(alpha_out, alpha, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
-  SG_HIP(hipStreamSynchronize(s));
-  SG_HIP(hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(h_scal, scal, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (n_slots > 0) AGP_HIP_CHECK(ctx, hipMemcpyAsync(grad_nll, grad_d, sizeof(double) * (size_t)n_slots, hipMemcpyDeviceToHost, s));
+  if (alpha_out) AGP_HIP_CHECK(ctx, hipMemcpyAsync(alpha_out, alpha, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
   if (grad_nuggets) { grad_nuggets[0] = h_scal[0]; grad_nuggets[1] = h_scal[1]; }
   *nll = nll_v;
   return AGP_OK;
@@ -640,26 +618,25 @@ int agp_sparse_held_out(agp_context *c, const agp_kernel *k, const agp_features 
   };
   WsLayout size_own;
   carve(size_own);
-  char *own_raw = nullptr;
-  SG_HIP(dev_malloc(&own_raw, size_own.bytes()));
-  dev_ptr<char> own_guard(own_raw);
-  WsLayout own(own_raw);
+  DevMem<void> own_mem;
+  AGP_HIP_CHECK(ctx, own_mem.alloc_cached(size_own.bytes()));
+  WsLayout own(own_mem.get());
   const SparseHeldOutRegions r = carve(own);
   InverseBlocks ib;
   if ((st = inverse_blocks_begin(ctx, w, G, offsets, n, ib)) != AGP_OK) return st;
   const hipMemcpyKind in_kind = on_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-  SG_HIP(hipMemcpyAsync(r.chain.meta, plan.meta.data(), sizeof(long long) * plan.meta.size(), hipMemcpyHostToDevice, s));
-  if (r.joff) SG_HIP(hipMemcpyAsync(r.joff, joff.data(), sizeof(long long) * joff.size(), hipMemcpyHostToDevice, s));
-  if (r.y) SG_HIP(hipMemcpyAsync(r.y, y, sizeof(double) * (size_t)n, in_kind, s));
-  if (r.yvar) SG_HIP(hipMemcpyAsync(r.yvar, y_var, sizeof(double) * (size_t)n, in_kind, s));
-  SG_HIP(hipStreamSynchronize(s));  // (pageable sources)
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(r.chain.meta, plan.meta.data(), sizeof(long long) * plan.meta.size(), hipMemcpyHostToDevice, s));
+  if (r.joff) AGP_HIP_CHECK(ctx, hipMemcpyAsync(r.joff, joff.data(), sizeof(long long) * joff.size(), hipMemcpyHostToDevice, s));
+  if (r.y) AGP_HIP_CHECK(ctx, hipMemcpyAsync(r.y, y, sizeof(double) * (size_t)n, in_kind, s));
+  if (r.yvar) AGP_HIP_CHECK(ctx, hipMemcpyAsync(r.yvar, y_var, sizeof(double) * (size_t)n, in_kind, s));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));  // (pageable sources)
 
   // ---- R_g, alpha, Z, N_g and B_g = bd(Kt^-1)_g ----
   if ((st = inverse_blocks_run(ctx, w, fit.get(), offsets, G, n, m, yw, r.aw, r.alpha, ib, stage)) != AGP_OK) return st;
   stage("held out: bd(Kt^-1) slabs");
 
   // ---- per chunk: B_g -> Sigma_g = B_g^-1 -> V_g = Sigma_g - nugget I - M_g -> the NLL terms and the predictions ----
-  SG_HIP(hipMemsetAsync(ctx->d_flags, 0, 4 * sizeof(int), s));
+  AGP_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_flags, 0, 4 * sizeof(int), s));
   for (const LogoChunk &ch : plan.chunks) {
     const long long cm = ch.m, ldb = factor_ld(cm), stride_B = ldb * cm;
     const long long *idx = r.chain.meta + ch.idx_off, *sizes = r.chain.meta + ch.size_off;
@@ -683,17 +660,17 @@ int agp_sparse_held_out(agp_context *c, const agp_kernel *k, const agp_features 
   launch_logo_sum(s, r.chain.term, plan.terms, ctx->d_scalars + 2);
   stage("held out: group chains");
 
-  SG_HIP(hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipGetLastError());
   const hipMemcpyKind out_kind = on_host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
   std::vector<double> h_term(group_nll ? (size_t)plan.terms : 0);
-  SG_HIP(hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-  SG_HIP(hipMemcpyAsync(ctx->h_scalars, ctx->d_scalars, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (!h_term.empty()) SG_HIP(hipMemcpyAsync(h_term.data(), r.chain.term, sizeof(double) * h_term.size(), hipMemcpyDeviceToHost, s));
-  if (mean) SG_HIP(hipMemcpyAsync(mean, r.mean, sizeof(double) * (size_t)n, out_kind, s));
-  if (variance) SG_HIP(hipMemcpyAsync(variance, r.variance, sizeof(double) * (size_t)n, out_kind, s));
-  if (joint) SG_HIP(hipMemcpyAsync(joint, r.joint, sizeof(double) * joint_total, out_kind, s));
-  SG_HIP(hipStreamSynchronize(s));
-  SG_HIP(hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_scalars, ctx->d_scalars, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (!h_term.empty()) AGP_HIP_CHECK(ctx, hipMemcpyAsync(h_term.data(), r.chain.term, sizeof(double) * h_term.size(), hipMemcpyDeviceToHost, s));
+  if (mean) AGP_HIP_CHECK(ctx, hipMemcpyAsync(mean, r.mean, sizeof(double) * (size_t)n, out_kind, s));
+  if (variance) AGP_HIP_CHECK(ctx, hipMemcpyAsync(variance, r.variance, sizeof(double) * (size_t)n, out_kind, s));
+  if (joint) AGP_HIP_CHECK(ctx, hipMemcpyAsync(joint, r.joint, sizeof(double) * joint_total, out_kind, s));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
   if ((st = status_from_flags(ctx)) != AGP_OK) return fail(st);  // a B_g or (Joint) a V_g that is not positive definite
   if (logo_nll) *logo_nll = ctx->h_scalars[2];
   if (group_nll)  // the terms are in the plan's order (by size) and hold 2 NLL_g

@@ -15,8 +15,8 @@ struct agp_sparse_fit {
   std::shared_ptr<agp_fit> kuu;        // train_covariance = factor of K_uu + inducing_nugget I
   agp_fit *sigma = nullptr;            // L1
   agp_fit *sigma2 = nullptr;           // L2
-  double *Lacc = nullptr;              // L1 L2, m x ldm, zero above the diagonal
-  double *v = nullptr;                 // information (m)
+  agp::DevMem<double> Lacc;            // L1 L2, m x ldm, zero above the diagonal
+  agp::DevMem<double> v;               // information (m)
   double nll = 0.;
   // "pivoted form" of a fit made by agp_sparse_fit_from_prediction (rebase_inducing_points) or by an update of one:
   // the reference's own representation, for covariances that are singular to working precision.
@@ -24,8 +24,8 @@ struct agp_sparse_fit {
                                        // (:416-418), K_uu + inducing nugget after a pivoted fit (:676-679); else kuu
   std::shared_ptr<agp_ldlt> kp;        // pivoted L D L^T of K_uu + inducing nugget for P = K_uu^-1/2 K_uf of an update, when
                                        // the LL^T of that matrix (kuu) does not exist
-  double *R = nullptr;                 // m x round_up(m, 2), upper triangular: Sigma^-1 = P R^T R P^T; else sigma/sigma2
-  long long *perm = nullptr;           // P: perm[i] = original index of the column at position i
+  agp::DevMem<double> R;               // m x round_up(m, 2), upper triangular: Sigma^-1 = P R^T R P^T; else sigma/sigma2
+  agp::DevMem<long long> perm;         // P: perm[i] = original index of the column at position i
   long long rank = -1;                 // numerical_rank of the QR (-1: not a pivoted fit)
   double inducing_nugget = 0.;         // the nugget an update adds to K_uu for P = K_uu^-1/2 K_uf (:674-685)
 };
@@ -33,8 +33,8 @@ struct agp_sparse_fit {
 namespace agp {
 
 struct SparseScratch {
-  double *Kuf = nullptr, *Pbuf = nullptr, *M0 = nullptr, *T = nullptr, *vecs = nullptr, *partial = nullptr,
-         *Ag = nullptr, *Pimg = nullptr, *Q1T = nullptr, *Winv = nullptr;
+  double *Kuf = nullptr, *Pbuf = nullptr, *Q1T = nullptr;  // (regions of ctx->pool_sparse, below)
+  DevMem<double> M0, T, vecs, partial, Ag, Pimg, Winv;
   std::vector<agp_fit *> blocks;
   DeviceFeatures dx;
   // Kuf, Pbuf / Q1T (one region: P is dead before Q1^T is formed) and the split-K slabs live in ctx->pool_sparse
@@ -44,10 +44,7 @@ struct SparseScratch {
   bool keep_P = false;
   int layout = 0;  // which path built the blocks of A: 0 lock step (Ag, Pimg), 1 the same on padded slabs, 2 one agp_fit per block
   ~SparseScratch() {
-    (void)dev_free(M0); (void)dev_free(T); (void)dev_free(vecs);
-    (void)dev_free(partial); (void)dev_free(Ag); (void)dev_free(Pimg); (void)dev_free(Winv);
     for (agp_fit *b : blocks) agp_fit_destroy(b);
-    dx.release();
   }
 };
 

@@ -144,56 +144,49 @@ int agp_fit_update(agp_context *c, const agp_kernel *k, const agp_fit *old, cons
   if (n_pad > n0) fit->phantom.emplace_back(n0, n_pad);
   fit->n_real = fit_real_rows(old) + m;
   const long long lda = fit->lda;
-  double *ynew_d = nullptr, *yvar_d = nullptr;
-#define UPD_CHECK(expr)                                                      \
-  do {                                                                       \
-    hipError_t _e = (expr);                                                  \
-    if (_e != hipSuccess) {                                                  \
-      ctx->last_error = std::string(#expr) + ": " + hipGetErrorString(_e);   \
-      if (ynew_d) (void)hipFree(ynew_d);                                     \
-      agp_fit_destroy(fit);                                                  \
-      return AGP_ERR_HIP;                                                    \
-    }                                                                        \
-  } while (0)
-  if (ctx->pool_A && ctx->pool_A_bytes == fit->A_bytes) {
-    fit->A = ctx->pool_A; ctx->pool_A = nullptr; ctx->pool_A_bytes = 0;
-  } else {
-    UPD_CHECK(hipMalloc(&fit->A, fit->A_bytes));
-  }
-  UPD_CHECK(hipMalloc(&fit->invd, sizeof(double) * (size_t)nblk1 * (36 * MB * MB)));
-  UPD_CHECK(hipMalloc(&fit->winv, sizeof(double) * (size_t)nblk1 * NB * NB));
-  UPD_CHECK(hipMalloc(&fit->alpha, sizeof(double) * (size_t)n1));
-  UPD_CHECK(hipMalloc(&fit->z, sizeof(double) * (size_t)n1));
-  UPD_CHECK(hipMalloc(&ynew_d, sizeof(double) * 2 * (size_t)round_up(m, 2)));
-  yvar_d = y_var_new ? ynew_d + round_up(m, 2) : nullptr;
+  FitGuard guard(fit);  // an early return destroys the fit
+  DevMem<double> ynew_d;
+  fit->own_A.adopt(static_cast<double *>(ctx->pool_A.take(fit->A_bytes)));
+  if (!fit->own_A) AGP_HIP_CHECK(ctx, fit->own_A.alloc_plain(fit->A_bytes));
+  fit->A = fit->own_A;
+  AGP_HIP_CHECK(ctx, fit->own_part[0].alloc_plain(sizeof(double) * (size_t)nblk1 * (36 * MB * MB)));
+  AGP_HIP_CHECK(ctx, fit->own_part[1].alloc_plain(sizeof(double) * (size_t)nblk1 * NB * NB));
+  AGP_HIP_CHECK(ctx, fit->own_part[2].alloc_plain(sizeof(double) * (size_t)n1));
+  AGP_HIP_CHECK(ctx, fit->own_part[3].alloc_plain(sizeof(double) * (size_t)n1));
+  fit->invd = fit->own_part[0];
+  fit->winv = fit->own_part[1];
+  fit->alpha = fit->own_part[2];
+  fit->z = fit->own_part[3];
+  AGP_HIP_CHECK(ctx, ynew_d.alloc_plain(sizeof(double) * 2 * (size_t)round_up(m, 2)));
+  double *yvar_d = y_var_new ? ynew_d + round_up(m, 2) : nullptr;
 
   // ---- train_features = concatenate(fit.train_features, features)   gp.hpp:387 ----
   const hipMemcpyKind kind = x_new->location == AGP_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
   DeviceFeatures &tr = fit->train;
-  UPD_CHECK(hipMalloc(&tr.owned[0], sizeof(double) * (size_t)n1 * (size_t)dim));
-  double *coords = static_cast<double *>(tr.owned[0]);
-  UPD_CHECK(hipMemcpyAsync(coords, ov.coords, sizeof(double) * (size_t)n0 * (size_t)dim, hipMemcpyDeviceToDevice, s));
-  UPD_CHECK(hipMemcpyAsync(coords + n_pad * dim, x_new->coords, sizeof(double) * (size_t)m * (size_t)dim, kind, s));
+  AGP_HIP_CHECK(ctx, tr.owned[0].alloc_plain(sizeof(double) * (size_t)n1 * (size_t)dim));
+  double *coords = static_cast<double *>(tr.owned[0].get());
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(coords, ov.coords, sizeof(double) * (size_t)n0 * (size_t)dim, hipMemcpyDeviceToDevice, s));
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(coords + n_pad * dim, x_new->coords, sizeof(double) * (size_t)m * (size_t)dim, kind, s));
   long long *ids = nullptr;
   if (ov.ids) {
-    UPD_CHECK(hipMalloc(&tr.owned[1], sizeof(long long) * (size_t)n1));
-    ids = static_cast<long long *>(tr.owned[1]);
-    UPD_CHECK(hipMemcpyAsync(ids, ov.ids, sizeof(long long) * (size_t)n0, hipMemcpyDeviceToDevice, s));
-    UPD_CHECK(hipMemcpyAsync(ids + n_pad, x_new->eq_id, sizeof(long long) * (size_t)m, kind, s));
+    AGP_HIP_CHECK(ctx, tr.owned[1].alloc_plain(sizeof(long long) * (size_t)n1));
+    ids = static_cast<long long *>(tr.owned[1].get());
+    AGP_HIP_CHECK(ctx, hipMemcpyAsync(ids, ov.ids, sizeof(long long) * (size_t)n0, hipMemcpyDeviceToDevice, s));
+    AGP_HIP_CHECK(ctx, hipMemcpyAsync(ids + n_pad, x_new->eq_id, sizeof(long long) * (size_t)m, kind, s));
   }
   double *scales = nullptr;
   if (nsc > 0) {
-    UPD_CHECK(hipMalloc(&tr.owned[2], sizeof(double) * (size_t)n1 * (size_t)nsc));
-    scales = static_cast<double *>(tr.owned[2]);
+    AGP_HIP_CHECK(ctx, tr.owned[2].alloc_plain(sizeof(double) * (size_t)n1 * (size_t)nsc));
+    scales = static_cast<double *>(tr.owned[2].get());
     for (int kc = 0; kc < nsc; ++kc) {
-      UPD_CHECK(hipMemcpyAsync(scales + (long long)kc * n1, ov.scales + (long long)kc * scale_stride(ov), sizeof(double) * (size_t)n0,
+      AGP_HIP_CHECK(ctx, hipMemcpyAsync(scales + (long long)kc * n1, ov.scales + (long long)kc * scale_stride(ov), sizeof(double) * (size_t)n0,
                                hipMemcpyDeviceToDevice, s));
-      UPD_CHECK(hipMemcpyAsync(scales + (long long)kc * n1 + n_pad, x_new->scales + (long long)kc * m, sizeof(double) * (size_t)m, kind, s));
+      AGP_HIP_CHECK(ctx, hipMemcpyAsync(scales + (long long)kc * n1 + n_pad, x_new->scales + (long long)kc * m, sizeof(double) * (size_t)m, kind, s));
     }
   }
-  UPD_CHECK(hipMemcpyAsync(ynew_d, y_new, sizeof(double) * (size_t)m, kind, s));
-  if (yvar_d) UPD_CHECK(hipMemcpyAsync(yvar_d, y_var_new, sizeof(double) * (size_t)m, kind, s));
-  if (x_new->location == AGP_HOST) UPD_CHECK(hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(ynew_d, y_new, sizeof(double) * (size_t)m, kind, s));
+  if (yvar_d) AGP_HIP_CHECK(ctx, hipMemcpyAsync(yvar_d, y_var_new, sizeof(double) * (size_t)m, kind, s));
+  if (x_new->location == AGP_HOST) AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
   if (n_pad > n0)
     hipLaunchKernelGGL(replicate_feature_kernel, dim3((unsigned)((n_pad - n0 + 255) / 256)), dim3(256), 0, s, coords, dim, ids, scales,
                        (long long)n1, nsc, n0, n_pad - n0, n_pad);
@@ -201,14 +194,14 @@ int agp_fit_update(agp_context *c, const agp_kernel *k, const agp_fit *old, cons
   tr.v.n = n1; tr.v.dim = dim; tr.v.nsc = nsc; tr.v.meas = 0; tr.v.sstride = 0;
 
   // ---- the old factor, its tile images and forward-substituted targets; phantom rows = identity ----
-  UPD_CHECK(hipMemcpy2DAsync(fit->A, sizeof(double) * (size_t)lda, old->A, sizeof(double) * (size_t)old->lda, sizeof(double) * (size_t)n0,
+  AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(fit->A, sizeof(double) * (size_t)lda, old->A, sizeof(double) * (size_t)old->lda, sizeof(double) * (size_t)n0,
                              (size_t)n0, hipMemcpyDeviceToDevice, s));
-  UPD_CHECK(hipMemcpyAsync(fit->invd, old->invd, sizeof(double) * (size_t)nblk0 * (36 * MB * MB), hipMemcpyDeviceToDevice, s));
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(fit->invd, old->invd, sizeof(double) * (size_t)nblk0 * (36 * MB * MB), hipMemcpyDeviceToDevice, s));
   launch_fill_block(s, fit->A, lda, n0, n_pad, 0, n_pad, true);   // phantom rows: e_i^T
-  UPD_CHECK(hipMemsetAsync(fit->z, 0, sizeof(double) * (size_t)n1, s));
-  UPD_CHECK(hipMemcpyAsync(fit->z, old->z, sizeof(double) * (size_t)n0, hipMemcpyDeviceToDevice, s));
-  UPD_CHECK(hipMemsetAsync(ctx->d_flags, 0, 4 * sizeof(int), s));
-  UPD_CHECK(hipMemsetAsync(ctx->d_scalars, 0, 4 * sizeof(double), s));
+  AGP_HIP_CHECK(ctx, hipMemsetAsync(fit->z, 0, sizeof(double) * (size_t)n1, s));
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(fit->z, old->z, sizeof(double) * (size_t)n0, hipMemcpyDeviceToDevice, s));
+  AGP_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_flags, 0, 4 * sizeof(int), s));
+  AGP_HIP_CHECK(ctx, hipMemsetAsync(ctx->d_scalars, 0, 4 * sizeof(double), s));
 
   // ---- cross = covariance_function_(fit_.train_features, features)  (gp.hpp:395-396; plain features on both sides),
   //      written transposed where V^T belongs: rows n_pad.., columns 0..n_pad ----
@@ -226,34 +219,31 @@ int agp_fit_update(agp_context *c, const agp_kernel *k, const agp_fit *old, cons
   launch_gram(s, dprog, vnew, vnew, true, true, S, lda, yvar_d, ctx->d_flags, &k->prog);
   launch_gemm_nt_sub(s, S, lda, X, lda, false, X, lda, false, m, m, n_pad, true);
   // ---- forward substitution of the new targets: y_new - V^T z_old, then through L_S (fused into its factorisation) ----
-  st = ensure_ws(ctx, &ctx->ws_aux, &ctx->ws_aux_bytes,
-                 sizeof(double) * (((size_t)(n_pad + 1023) / 1024) * (size_t)m + backsolve_ws_elems(n1) + 16));
-  if (st != AGP_OK) { (void)hipFree(ynew_d); agp_fit_destroy(fit); return st; }
+  st = reserve_ws(ctx, ctx->ws_aux, sizeof(double) * (((size_t)(n_pad + 1023) / 1024) * (size_t)m + backsolve_ws_elems(n1) + 16));
+  if (st != AGP_OK) return st;
   launch_matvec(s, X, lda, m, n_pad, fit->z, ctx->ws_aux, -1.0, 1.0, ynew_d, fit->z + n_pad);
   // ---- LL^T of S in place (the sub-matrix is addressed as a matrix of its own: its 128-blocks start at n_pad) ----
   factor_lower(ctx, S, m, lda, fit->invd + (n_pad / NB) * (long long)(36 * MB * MB), fit->z + n_pad);
-  UPD_CHECK(hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
-  UPD_CHECK(hipMemcpyAsync(ctx->h_scalars, ctx->d_scalars, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
-  UPD_CHECK(hipStreamSynchronize(s));
-  UPD_CHECK(hipGetLastError());
-  (void)hipFree(ynew_d);
-  ynew_d = nullptr;
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_flags, ctx->d_flags, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(ctx->h_scalars, ctx->d_scalars, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  ynew_d.reset();  // (here, not at scope exit: the free synchronises the device)
   fit->log_det = old->log_det + 2. * ctx->h_scalars[0];
-  if (ctx->h_flags[0]) { agp_fit_destroy(fit); return AGP_ERR_NAN_INPUT; }
+  if (ctx->h_flags[0]) return AGP_ERR_NAN_INPUT;
   if (ctx->h_flags[1]) {
     fit->failed_pivot = fit_real_rows(old) + (int64_t)ctx->h_flags[1] - 1;
-    *out = fit;  // the handle only reports the pivot
+    *out = guard.release();  // the handle only reports the pivot
     return AGP_ERR_NOT_POSITIVE_DEFINITE;
   }
   // ---- information = L^-T z over the whole grown factor ----
-  UPD_CHECK(hipMemcpyAsync(fit->alpha, fit->z, sizeof(double) * (size_t)n1, hipMemcpyDeviceToDevice, s));
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(fit->alpha, fit->z, sizeof(double) * (size_t)n1, hipMemcpyDeviceToDevice, s));
   backward_solve_vec_any(s, fit->A, n1, lda, fit->invd, fit->alpha, ctx->ws_aux);
-  UPD_CHECK(hipStreamSynchronize(s));
-  UPD_CHECK(hipGetLastError());
-#undef UPD_CHECK
-  if (information && (st = fit_compact_vector(ctx, fit, fit->alpha, information, AGP_HOST)) != AGP_OK) { agp_fit_destroy(fit); return st; }
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  if (information && (st = fit_compact_vector(ctx, fit, fit->alpha, information, AGP_HOST)) != AGP_OK) return st;
   if (log_det) *log_det = fit->log_det;
-  *out = fit;
+  *out = guard.release();
   return AGP_OK;
 }
 

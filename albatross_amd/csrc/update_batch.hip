@@ -237,15 +237,10 @@ int agp_fit_update_batch(agp_context *c, int count, const agp_kernel *const *ker
   carve_update_batch(size, g);
   for (int b = 0; b < count; ++b) carve_grown_features(size, n1, x_new[b]->dim, x_new[b]->eq_id != nullptr, x_new[b]->n_scale_columns);
   const size_t bytes = size.bytes();
-  double *base = nullptr;
-  if (ctx->pool_batch && ctx->pool_batch_bytes == bytes) {
-    base = ctx->pool_batch;
-    ctx->pool_batch = nullptr;
-    ctx->pool_batch_bytes = 0;
-  } else {
-    AGP_HIP_CHECK(ctx, hipMalloc(&base, bytes));
-  }
-  WsLayout ws(base);
+  DevMem<double> base;
+  base.adopt(static_cast<double *>(ctx->pool_batch.take(bytes)));
+  if (!base) AGP_HIP_CHECK(ctx, base.alloc_plain(bytes));
+  WsLayout ws(base.get());
   const UpdateBatchRegions r = carve_update_batch(ws, g);
   // ---- the scratch of the call: targets, variances, staged host features, the three descriptor tables ----
   size_t stage_words = 0;  // host-resident new features go through one staging region
@@ -265,18 +260,16 @@ int agp_fit_update_batch(agp_context *c, int count, const agp_kernel *const *ker
                gram_bytes = range_off + (phantoms.any() ? phantoms.bytes() : 0);
   WsLayout tsize;
   carve_update_batch_scratch(tsize, g, mp2, y_var_new != nullptr, stage_words, grow_bytes, cross_bytes, gram_bytes);
-  void *scratch = nullptr;
-  if (dev_malloc(&scratch, tsize.bytes()) != hipSuccess) {
+  DevMem<void> scratch;
+  if (scratch.alloc_cached(tsize.bytes()) != 0) {
     (void)hipGetLastError();
-    (void)hipFree(base);
     ctx->last_error = "agp_fit_update_batch: scratch";
     return AGP_ERR_HIP;
   }
-  struct FreeScratch { void *p; ~FreeScratch() { (void)dev_free(p); } } free_scratch{scratch};
-  WsLayout tws(scratch);
+  WsLayout tws(scratch.get());
   const UpdateBatchScratch t =
       carve_update_batch_scratch(tws, g, mp2, y_var_new != nullptr, stage_words, grow_bytes, cross_bytes, gram_bytes);
-  const size_t table_off = (size_t)(static_cast<char *>(t.grow_table) - static_cast<char *>(scratch));
+  const size_t table_off = (size_t)(static_cast<char *>(t.grow_table) - static_cast<char *>(scratch.get()));
   const size_t cross_off = (size_t)(static_cast<char *>(t.cross_table) - static_cast<char *>(t.grow_table));
   const size_t gram_off = (size_t)(static_cast<char *>(t.gram_table) - static_cast<char *>(t.grow_table));
   const size_t tables_bytes = tsize.bytes() - table_off;  // (the tables are the tail of the scratch, laid out alike in the pinned stage)
@@ -289,8 +282,8 @@ int agp_fit_update_batch(agp_context *c, int count, const agp_kernel *const *ker
   auto fail = [&](int code) {
     (void)hipStreamSynchronize(s);
     for (auto *f : fits)
-      if (f) { f->train.release(); delete f; }
-    (void)hipFree(base);
+      if (f) delete f;
+    base.reset();
     return code;
   };
 #define UPB_CHECK(expr)                                                      \
@@ -447,7 +440,7 @@ int agp_fit_update_batch(agp_context *c, int count, const agp_kernel *const *ker
   const int *h_flags = reinterpret_cast<const int *>(h_status.data() + g.cp2);
   agp_fit_slab *slab = new (std::nothrow) agp_fit_slab();
   if (!slab) return fail(AGP_ERR_INVALID_ARGUMENT);
-  slab->base = base;
+  slab->base = std::move(base);
   slab->bytes = bytes;
   slab->refs = count;
   for (int b = 0; b < count; ++b) {

@@ -1,5 +1,5 @@
 // host_sanitize_check.cpp — the host-side C++ of the project under AddressSanitizer + UndefinedBehaviorSanitizer, on
-// a machine WITHOUT a GPU (examples/Makefile: `make asan`).  Four parts:
+// a machine WITHOUT a GPU (examples/Makefile: `make asan`).  Five parts:
 //
 //  1. the sharded-fit schedule (albatross_amd/csrc/shard_sched.hip is plain C++: compiled INTO this binary with the
 //     sanitizers on) driven through agp_debug_shard_factor_custom (csrc/shard_custom.hip) with naive block operations, one rank and - through
@@ -12,6 +12,9 @@
 //     the real one, the size within the alignment padding of the plain sums, first and last word of every region written;
 //  4. the schedule of the dense factorisation (albatross_amd/csrc/factor_plan.h: plain C++): every n up to 20480 planned
 //     under four switch sets (two of them resolved from the FactorRequest of a call), every step's panels planned, and a sweep of the step-launch shapes.
+//  5. the owners of device memory (albatross_amd/csrc/dev_mem.h: plain C++) over malloc / free: the four allocator
+//     functions are defined HERE with a table of live blocks, a log of the calls and a switch that fails the k-th
+//     allocation; every move, hand-over, refusal and failure of DevMem, ParkSlot and GrowBuf, no block left at the end.
 //
 // Prints "host_sanitize_check ok" and exits 0; any sanitizer report aborts with a non-zero status.
 #include <cmath>
@@ -19,10 +22,13 @@
 #include <cstdint>
 #include <cstdlib>
 #include <functional>
+#include <set>
+#include <string>
 #include <utility>
 #include <vector>
 
 #include "albatross_amd/albatross.hpp"
+#include "dev_mem.h"         // csrc/: DevMem, ParkSlot, GrowBuf
 #include "batch_layout.h"    // csrc/: WsLayout, BatchGeometry, the carve functions
 #include "factor_plan.h"     // csrc/: FactorPlanner, plan_panels, step_launch_shape
 #include "shard_internal.h"  // agp_shard_ops_callbacks (csrc/, test-only)
@@ -394,6 +400,94 @@ void factor_plan_under_sanitizers() {
       require(sh.trail_workers >= 1 && (below == 0 || sh.trail_workers <= sh.trail_tiles), "trailing workgroups");
     }
 }
+
+// ---- part 5: the owners of device memory -----------------------------------------------------------------------------
+struct FakeDevice {
+  std::set<void *> live;
+  std::string log;       // one letter per call: c cached allocation, p plain allocation, f dev_free, r dev_release
+  int fail_at = 0;       // the allocation that fails, counted from the next one (0: none)
+  int alloc(void **p, std::size_t bytes, char tag) {
+    log += tag;
+    if (fail_at > 0 && --fail_at == 0) return 2;  // (hipErrorOutOfMemory)
+    *p = std::malloc(bytes ? bytes : 1);
+    live.insert(*p);
+    return 0;
+  }
+  int free(void *p, char tag) {
+    log += tag;
+    require(live.erase(p) == 1, "a block is freed once, and only a live one");
+    std::free(p);
+    return 0;
+  }
+  std::string take_log() { std::string l; l.swap(log); return l; }
+} fake;
+}  // namespace
+
+namespace agp {  // the four functions dev_mem.h declares (the library's are in csrc/api.hip)
+int dev_malloc_bytes(void **p, std::size_t bytes) { return fake.alloc(p, bytes, 'c'); }
+int dev_malloc_plain_bytes(void **p, std::size_t bytes) { return fake.alloc(p, bytes, 'p'); }
+int dev_free(void *p) { return p ? fake.free(p, 'f') : 0; }
+int dev_release(void *p) { return p ? fake.free(p, 'r') : 0; }
+}  // namespace agp
+
+namespace {
+void dev_mem_under_sanitizers() {
+  using agp::DevMem; using agp::GrowBuf; using agp::ParkSlot;
+  {  // DevMem
+    DevMem<double> empty;  // (destroyed empty at the end of the block: no call)
+    DevMem<double> a, b;
+    require(a.alloc_cached(64) == 0 && b.alloc_plain(32) == 0 && a && b && fake.take_log() == "cp", "both allocators");
+    double *pa = a, *pb = b;
+    DevMem<double> c(std::move(a));
+    require(!a && c.get() == pa && fake.take_log().empty(), "move construction hands the block over");
+    c = std::move(b);  // onto an occupied owner: its block goes first
+    require(!b && c.get() == pb && fake.take_log() == "f" && !fake.live.count(pa), "move assignment frees the occupant");
+    double *raw = c.release();
+    require(!c && raw == pb && fake.take_log().empty(), "release gives the block up without a call");
+    c.adopt(raw);
+    require(c.get() == pb, "adopt");
+    c.reset();
+    c.reset();
+    require(!c && fake.take_log() == "f", "reset twice frees once");
+    fake.fail_at = 1;
+    require(c.alloc_plain(16) != 0 && !c && fake.take_log() == "p", "a failed allocation leaves the owner empty");
+    DevMem<void> v;
+    require(v.alloc_cached(8) == 0 && v.get() != nullptr && fake.take_log() == "c", "an untyped block");
+  }
+  require(fake.take_log() == "f" && fake.live.empty(), "scope exit frees what is still owned");
+  {  // ParkSlot
+    ParkSlot slot;
+    require(slot.take(100) == nullptr && !slot, "take from an empty slot");
+    void *p100 = nullptr, *q100 = nullptr, *p200 = nullptr, *p300 = nullptr;
+    agp::dev_malloc_plain_bytes(&p100, 100); agp::dev_malloc_plain_bytes(&q100, 100);
+    agp::dev_malloc_plain_bytes(&p200, 200); agp::dev_malloc_plain_bytes(&p300, 300);
+    (void)fake.take_log();
+    require(slot.park(p100, 100) && slot.bytes() == 100, "an empty slot keeps the block");
+    require(slot.take(100) == p100 && !slot && fake.take_log().empty(), "the same size comes back, without a call");
+    require(slot.park(p100, 100) && slot.take(200) == nullptr && slot.bytes() == 100, "another size: null, the occupant stays");
+    require(!slot.park(q100, 100) && fake.live.count(q100) && fake.take_log().empty(), "the same size onto an occupied slot is refused");
+    require(slot.park(p200, 200) && fake.take_log() == "r" && !fake.live.count(p100) && slot.bytes() == 200,
+            "another size over an occupant: the occupant is released, once");
+    require(!slot.park(p300, 300, /*evict=*/false) && slot.bytes() == 200 && fake.take_log().empty(),
+            "without eviction an occupant of another size stays and the block is refused");
+    require(slot.take(200) == p200 && slot.park(p300, 300, false) && fake.take_log().empty(), "without eviction an empty slot keeps the block");
+    agp::dev_free(q100); agp::dev_free(p200);
+    (void)fake.take_log();
+  }  // (the slot goes with p300 in it)
+  require(fake.take_log() == "r" && fake.live.empty(), "a slot releases its occupant when it goes");
+  {  // GrowBuf
+    GrowBuf<float> buf;
+    require(buf.reserve(0) == 0 && !buf && fake.take_log().empty(), "nothing asked, nothing done");
+    require(buf.reserve(64) == 0 && buf && buf.bytes() == 64 && fake.take_log() == "p", "first growth: one allocation");
+    float *p = buf;
+    require(buf.reserve(64) == 0 && buf.reserve(8) == 0 && buf.get() == p && fake.take_log().empty(), "smaller or equal: no call");
+    require(buf.reserve(128) == 0 && buf.bytes() == 128 && fake.take_log() == "fp", "growth: one free, then one allocation");
+    fake.fail_at = 1;
+    require(buf.reserve(256) != 0 && !buf && buf.bytes() == 0 && fake.take_log() == "fp", "a failing allocation: empty, size 0");
+    require(buf.reserve(256) == 0 && buf.bytes() == 256 && fake.take_log() == "p", "a later reserve succeeds");
+  }
+  require(fake.take_log() == "f" && fake.live.empty(), "no block is left");
+}
 }  // namespace
 
 int main() {
@@ -402,6 +496,7 @@ int main() {
   host_layer_under_sanitizers();
   layouts_under_sanitizers();
   factor_plan_under_sanitizers();
+  dev_mem_under_sanitizers();
   std::printf("host_sanitize_check ok\n");
   return 0;
 }
