@@ -119,6 +119,10 @@ EXPORTS = [
                                          C.c_int64, _P, C.c_int64, _P]),
     ("agp_loo_nll_gradient_batch", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P,
                                              C.c_int64, _P, C.c_int64, _P]),
+    ("agp_nll_gradient_batch_ragged", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P,
+                                                C.c_int64, _P, C.c_int64, _P]),
+    ("agp_loo_nll_gradient_batch_ragged", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64, _P,
+                                                    _P, C.c_int64, _P, C.c_int64, _P]),
     ("agp_nll_batch", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, _P, _P]),
     ("agp_fit_create_batch", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P, _P]),
     ("agp_fit_create_batch_ragged", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P, _P]),

@@ -66,7 +66,8 @@ void factor_batch(agp_context *ctx, const BatchGeometry &g, bool allow_lookahead
 // A fit of n_b points in a batch of padded size n carries the trailing phantom rows [n_b, n) (common.h: agp_fit::phantom).
 // One problem of the pad launch that runs behind the Gram launches, which work on views of n_b rows: the phantom rows of
 // the lower triangle of slab b become e_i^T, z_b is zeroed there, and the phantom rows of the training features become
-// copies of the problem's first feature (ids: -2 - k, which no caller's id equals).
+// copies of the problem's first feature (ids: -2 - k, which no caller's id equals).  An item with dim = 0, nsc = 0 and
+// ids = nullptr (the batched gradients, which keep no features) has the slab and z written and nothing else touched.
 struct RaggedPadItem {
   double *A, *z;       // slab b (ld = lda) and its targets
   double *coords;      // n rows

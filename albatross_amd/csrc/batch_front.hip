@@ -73,7 +73,7 @@ int BatchGramTables::upload_features(agp_context *ctx, const agp_features *const
   for (int b = 0; b < count; ++b) {
     const agp_features *f = features[b];
     const bool same = last && f->coords == last->coords && f->scales == last->scales && f->eq_id == last->eq_id &&
-                      f->dim == last->dim && f->n_scale_columns == last->n_scale_columns;
+                      f->dim == last->dim && f->n_scale_columns == last->n_scale_columns && f->n == last->n;
     if (!same) {
       const int st = to_device(ctx, f, false, &uploads[(size_t)b]);
       if (st != AGP_OK) return st;

@@ -44,6 +44,8 @@
 // every kernel below takes the problem from blockIdx.y (blockIdx.z where y is a tile index) and per-problem strides, and
 // the single-problem calls are its count = 1 case.  Their checks, uploads, Gram and factor are the front end the batched
 // fits share (batch_front.h); every workspace here is carved by a layout of batch_layout.h.
+// agp_nll_gradient_batch_ragged and agp_loo_nll_gradient_batch_ragged are the same two bodies for problems of UNEQUAL sizes:
+// problem b is diag(K_b, I) at the padded size of the call (ragged_batch.hip; gradient_batch_begin says what changes).
 #include <algorithm>
 #include <climits>
 #include <cstring>
@@ -112,10 +114,18 @@ struct ContractArgs {
 
 // The body of both the single-problem kernel and the batched one.  LOO: the weight of agp_loo_nll_gradient in place of
 // K^-1_ij - alpha_i alpha_j.
+// The pairs are those of X.n points, whatever the grid was sized for: a problem of n_b rows in a batch of padded size n
+// (ragged_batch.hip) hands in its view of n_b rows and so contracts no phantom pair - a phantom diagonal pair would carry
+// the weight 1/2 against dK_ii / dtheta of whatever feature the row is read as.  A tile wholly behind X.n (bi CT >= X.n;
+// bj <= bi) writes its zero partial, which the reduction sums with the rest, and leaves before it loads a point.
 template <int DIMP, bool LOO>
 __device__ __forceinline__ void contract_lower(const DevProgram *__restrict__ P, const FeatView &X, const ContractArgs &a) {
   ContractTile t;
   lower_tile(blockIdx.x, t.bi, t.bj);
+  if ((long long)t.bi * CT >= X.n) {  // (the whole workgroup)
+    if (threadIdx.x < GRAD_GROUP) a.partial[(long long)blockIdx.x * GRAD_GROUP + threadIdx.x] = 0.;
+    return;
+  }
   t.rbase = t.cbase = 0;
   t.nrl = t.ncl = X.n;
   t.lower = true;
@@ -205,10 +215,18 @@ static void launch_contract_batched(hipStream_t s, int dim_max, const ContractDe
 // alpha_i: term[i] = log v_i + d_i^2 / v_i (the NLL term without 1/2 and log 2 pi), a[i] = d_i / (v_i c_i) and
 // sqrt_b[i] = sqrt(b_i); b_i > 0 always (c_i v_i >= 1).  a and sqrt_b may be nullptr (value only).  blockIdx.y = problem:
 // its c starts at cdiag + b * cbatch, its vectors at b * vbatch (one problem: a grid of height 1).
+// rows: the descriptors of a batch of unequal sizes, whose problem b has rows[b].X.n real rows of the n (nullptr: n for
+// everybody).  A phantom row gets term = a = sqrt_b = 0 - the sum, the product C a and G read all n rows - and neither its
+// c (1, from diag(C_b, I)) nor its target variance (never written) is looked at.
+__device__ __forceinline__ long long real_rows(const ContractDesc *__restrict__ rows, long long n) {
+  return rows ? rows[blockIdx.y].X.n : n;
+}
+
 __global__ __launch_bounds__(256) void loo_terms_kernel(const double *__restrict__ cdiag, long long cstride, long long cbatch,
                                                         const double *__restrict__ alpha, const double *__restrict__ yvar,
                                                         long long n, long long vbatch, double *__restrict__ term,
-                                                        double *__restrict__ a, double *__restrict__ sqrt_b) {
+                                                        double *__restrict__ a, double *__restrict__ sqrt_b,
+                                                        const ContractDesc *__restrict__ rows) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const long long vb = (long long)blockIdx.y * vbatch;
@@ -217,6 +235,12 @@ __global__ __launch_bounds__(256) void loo_terms_kernel(const double *__restrict
   if (yvar) yvar += vb;
   if (a) a += vb;
   if (sqrt_b) sqrt_b += vb;
+  if (i >= real_rows(rows, n)) {
+    term[i] = 0.;
+    if (a) a[i] = 0.;
+    if (sqrt_b) sqrt_b[i] = 0.;
+    return;
+  }
   const double c = cdiag[i * cstride], al = alpha[i];
   const double v = 1. / c + (yvar ? yvar[i] : 0.);  // the LOO variance plus the truth's (prediction_metrics.hpp:113-119)
   const double d = al / c;                           // cross_validation_utils.hpp:146-163
@@ -227,10 +251,11 @@ __global__ __launch_bounds__(256) void loo_terms_kernel(const double *__restrict
 }
 
 // out[b] = 1/2 (sum_i term_b[i] + n log 2 pi), term_b = term + b * tbatch, b = blockIdx.y   (one workgroup per problem,
-// fixed order)
+// fixed order).  rows as in loo_terms_kernel: problem b sums its rows[b].X.n real terms and its n is that number.
 __global__ __launch_bounds__(1024) void loo_sum_kernel(const double *__restrict__ term, long long n, long long tbatch,
-                                                       double *__restrict__ out) {
+                                                       double *__restrict__ out, const ContractDesc *__restrict__ rows) {
   __shared__ double red[16];
+  n = real_rows(rows, n);
   term += (long long)blockIdx.y * tbatch;
   double acc = 0.;
   for (long long i = threadIdx.x; i < n; i += 1024) acc += term[i];
@@ -911,14 +936,14 @@ int agp_loo_nll_gradient(agp_context *c, const agp_kernel *k, const agp_features
   if (!need_c) {
     // c_i = ||R[:, i]||^2, as agp_fit_inverse_diagonal
     launch_coldot(s, g.R, g.lda, g.R, g.lda, n, n, cdiag, -1.0, nullptr);
-    hipLaunchKernelGGL(loo_terms_kernel, dim3(eblocks), dim3(256), 0, s, cdiag, 1LL, 0LL, alpha, g.yvar_d, n, 0LL, term, nullptr, nullptr);
-    hipLaunchKernelGGL(loo_sum_kernel, dim3(1), dim3(1024), 0, s, term, n, 0LL, ctx->d_scalars + 2);
+    hipLaunchKernelGGL(loo_terms_kernel, dim3(eblocks), dim3(256), 0, s, cdiag, 1LL, 0LL, alpha, g.yvar_d, n, 0LL, term, nullptr, nullptr, nullptr);
+    hipLaunchKernelGGL(loo_sum_kernel, dim3(1), dim3(1024), 0, s, term, n, 0LL, ctx->d_scalars + 2, nullptr);
     if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[5], s));
   } else {
     launch_rtr_lower(s, g.R, g.lda, n, g.A, g.lda);  // C = K^-1 over L
     if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[4], s));
-    hipLaunchKernelGGL(loo_terms_kernel, dim3(eblocks), dim3(256), 0, s, g.A, g.lda + 1, 0LL, alpha, g.yvar_d, n, 0LL, term, a, sqrt_b);
-    hipLaunchKernelGGL(loo_sum_kernel, dim3(1), dim3(1024), 0, s, term, n, 0LL, ctx->d_scalars + 2);
+    hipLaunchKernelGGL(loo_terms_kernel, dim3(eblocks), dim3(256), 0, s, g.A, g.lda + 1, 0LL, alpha, g.yvar_d, n, 0LL, term, a, sqrt_b, nullptr);
+    hipLaunchKernelGGL(loo_sum_kernel, dim3(1), dim3(1024), 0, s, term, n, 0LL, ctx->d_scalars + 2, nullptr);
     launch_symv_lower(s, g.A, g.lda, n, a, 1., 0., nullptr, u, symv_ws);  // u = C a
     if (n_slots > 0) {
       const unsigned gt = (unsigned)((n + GF_T - 1) / GF_T);
@@ -1070,6 +1095,8 @@ struct GradientBatch {
   double *quad = nullptr;    // one scalar per problem: z_b^T z_b (NLL) or the leave-one-out sum
   double *R = nullptr, *grad_d = nullptr, *extra = nullptr;
   ContractDesc *desc_d = nullptr;
+  const ContractDesc *rows_d = nullptr;  // desc_d when some problem has phantom rows (loo_terms_kernel: rows), else null
+  std::vector<long long> nb;             // the real rows of every problem
   long long count = 0;
   double *vector(int k) const { return extra + (size_t)k * (size_t)count * (size_t)np2; }  // extra array k (np2 x count)
 };
@@ -1081,14 +1108,28 @@ struct GradientBatch {
 // vec / ldvec: the entry's n x count host output, checked only.  quad: z_b^T z_b before alpha overwrites z.
 // extra_vectors: further np2 x count arrays behind the descriptors, laid out like z (GradientBatch::vector(k): array k,
 // problem b's vector at + b * np2); u_vector >= 0: the array that holds every problem's u, for the descriptors.
+//
+// `ragged` (the _ragged entries) admits problems of unequal sizes n_b, as fit_create_batch does (api.hip).  The padded size
+// n of the call is the largest of them and problem b is diag(K_b, I): column b of the targets, the variances and the
+// tangents holds n_b values that go up in copies of their own (device inputs: one table-driven copy launch), the Gram
+// launches run on the views of n_b rows, and ONE pad launch behind them writes the phantom rows of slab b as identity rows
+// and z_b[n_b .. n) = 0.  No covariance is ever evaluated on a phantom row, so the pad items carry no features.  The
+// factor, alpha, R and R^T R then run at size n on diag(L_b, I), diag(R_b, I) and diag(C_b, I).  The descriptors hold the
+// views of n_b rows, which is what masks the phantom pairs of the contraction (contract_lower) and tells the leave-one-out
+// kernels the real rows (GradientBatch::rows_d).  With all sizes equal nothing of this runs: the launches and the bits
+// are those of the equal-size call.
 static int gradient_batch_begin(agp_context_impl *ctx, int count, const agp_kernel *const *kernels,
                                 const agp_features *const *features, const double *y, int64_t ldy, const double *y_var,
                                 int64_t ldv, const int *n_slots, const agp_gradient_slot *const *slots,
                                 const double *const *tangents, int64_t ldt, const double *grad, int64_t ldg, const double *vec,
-                                int64_t ldvec, bool quad, bool rtr, int extra_vectors, int u_vector, GradientBatch &g) {
+                                int64_t ldvec, bool quad, bool rtr, int extra_vectors, int u_vector, bool ragged,
+                                GradientBatch &g) {
   long long n = 0;
-  int st = check_batch_problems(count, kernels, features, ldy, y_var, ldv, &n);
+  bool equal = true;
+  int st = ragged ? check_batch_problems_ragged(count, kernels, features, ldy, y_var, ldv, &n, &equal)
+                  : check_batch_problems(count, kernels, features, ldy, y_var, ldv, &n);
   if (st != AGP_OK) return st;
+  const bool padded = !equal;  // some problem has phantom rows
   if (vec && ldvec < n) return AGP_ERR_INVALID_ARGUMENT;
   int max_slots = 0, dim_max = 1;
   std::vector<int> ntc((size_t)count, 0);
@@ -1118,8 +1159,14 @@ static int gradient_batch_begin(agp_context_impl *ctx, int count, const agp_kern
   if (loc == AGP_HOST)
     for (int b = 0; b < count; ++b) tang_elems += (long long)ntc[(size_t)b] * np2;
   const size_t gram_bytes = gram_batch_table_bytes(count), desc_bytes = sizeof(ContractDesc) * (size_t)count;
+  // a padded call: behind the descriptors, in the same region and the same upload, the pad table and (device inputs) the
+  // copy table of the targets and variances
+  const size_t pad_off = (desc_bytes + 15) / 16 * 16, pad_bytes = padded ? sizeof(RaggedPadItem) * (size_t)count : 0;
+  const size_t copy_off = pad_off + pad_bytes;
+  const size_t copy_cap = padded && loc != AGP_HOST ? sizeof(CopyItem) * (size_t)count * (y_var ? 2 : 1) : 0;
+  const size_t tables_bytes = padded ? copy_off + copy_cap : desc_bytes;
   auto carve_aux = [&](WsLayout &w) {
-    return carve_gradient_batch_aux(w, geo, (size_t)tang_elems, (size_t)part_per, (size_t)ldgd, gram_bytes, desc_bytes, (size_t)extra_vectors);
+    return carve_gradient_batch_aux(w, geo, (size_t)tang_elems, (size_t)part_per, (size_t)ldgd, gram_bytes, tables_bytes, (size_t)extra_vectors);
   };
   WsLayout size_A, size_aux;
   carve_gradient_batch(size_A, geo, y_var != nullptr, fused_panels);
@@ -1135,11 +1182,34 @@ static int gradient_batch_begin(agp_context_impl *ctx, int count, const agp_kern
   g.groups = groups; g.max_slots = max_slots; g.dim_max = dim_max;
   g.A = A; g.z = z; g.yvar_d = r.yvar; g.logsum = r.logsum; g.quad = r.quad; g.R = R; g.grad_d = a.grad; g.desc_d = desc_d;
   g.extra = a.extra;
+  g.rows_d = padded ? desc_d : nullptr;
+  g.nb.resize((size_t)count);
+  for (int b = 0; b < count; ++b) g.nb[(size_t)b] = features[b]->n;
   hipStream_t s = ctx->stream;
   const bool prof = ctx->profiling;
 
-  if ((st = upload_problem_columns(ctx, y, ldy, n, count, loc, z, np2)) != AGP_OK) return st;
-  if (y_var && (st = upload_problem_columns(ctx, y_var, ldv, n, count, loc, r.yvar, np2)) != AGP_OK) return st;
+  std::vector<CopyItem> copies;  // (a padded call with device inputs)
+  long long copy_max = 0;
+  if (!padded) {
+    if ((st = upload_problem_columns(ctx, y, ldy, n, count, loc, z, np2)) != AGP_OK) return st;
+    if (y_var && (st = upload_problem_columns(ctx, y_var, ldv, n, count, loc, r.yvar, np2)) != AGP_OK) return st;
+  } else {
+    // the n_b values of column b; what follows them in the column is never read
+    for (int b = 0; b < count; ++b) {
+      const long long nb = g.nb[(size_t)b];
+      const double *src[2] = {y + (size_t)b * (size_t)ldy, y_var ? y_var + (size_t)b * (size_t)ldv : nullptr};
+      double *dst[2] = {z + (size_t)b * (size_t)np2, y_var ? r.yvar + (size_t)b * (size_t)np2 : nullptr};
+      for (int k = 0; k < 2; ++k) {
+        if (!src[k]) continue;
+        if (loc == AGP_HOST) {
+          AGP_HIP_CHECK(ctx, hipMemcpyAsync(dst[k], src[k], sizeof(double) * (size_t)nb, hipMemcpyHostToDevice, s));
+        } else {
+          copies.push_back(CopyItem{reinterpret_cast<unsigned long long *>(dst[k]), reinterpret_cast<const unsigned long long *>(src[k]), nb});
+          if (nb > copy_max) copy_max = nb;
+        }
+      }
+    }
+  }
   // tangent columns: host columns are copied into the workspace (leading dimension np2), device ones are read in place
   std::vector<const double *> tcol((size_t)count, nullptr);
   std::vector<long long> tld((size_t)count, 0);
@@ -1147,7 +1217,8 @@ static int gradient_batch_begin(agp_context_impl *ctx, int count, const agp_kern
     double *tcur = a.tang;
     for (int b = 0; b < count; ++b) {
       if (ntc[(size_t)b] == 0) continue;
-      if ((st = stage_tangents(ctx, s, tangents[b], ldt, loc, n, ntc[(size_t)b], &tcur, &tcol[(size_t)b], &tld[(size_t)b])) != AGP_OK) return st;
+      if ((st = stage_tangents(ctx, s, tangents[b], ldt, loc, g.nb[(size_t)b], ntc[(size_t)b], &tcur, &tcol[(size_t)b], &tld[(size_t)b])) != AGP_OK)
+        return st;
     }
   }
   BatchGramTables gram(geo, kernels, A, r.yvar, np2, r.flags, 4);
@@ -1160,11 +1231,12 @@ static int gradient_batch_begin(agp_context_impl *ctx, int count, const agp_kern
   }
   // the contraction's descriptors, built in the pinned staging area behind the Gram table's, as they lie on the device
   const size_t desc_off = (size_t)(static_cast<char *>(a.desc) - static_cast<char *>(a.gram_table));
-  char *pinned = static_cast<char *>(host_stage(ctx, desc_off + desc_bytes));
-  std::vector<ContractDesc> desc_pageable;
-  ContractDesc *desc_h = nullptr;
-  if (pinned) desc_h = reinterpret_cast<ContractDesc *>(pinned + desc_off);
-  else { desc_pageable.resize((size_t)count); desc_h = desc_pageable.data(); }
+  char *pinned = static_cast<char *>(host_stage(ctx, desc_off + tables_bytes));
+  std::vector<double> desc_pageable;  // (doubles: aligned as the tables need it)
+  char *tables_h = nullptr;
+  if (pinned) tables_h = pinned + desc_off;
+  else { desc_pageable.resize((tables_bytes + sizeof(double) - 1) / sizeof(double)); tables_h = reinterpret_cast<char *>(desc_pageable.data()); }
+  ContractDesc *desc_h = reinterpret_cast<ContractDesc *>(tables_h);
   for (int b = 0; b < count; ++b) {
     ContractDesc &d = desc_h[b];
     std::memset(static_cast<void *>(&d), 0, sizeof(ContractDesc));
@@ -1183,11 +1255,26 @@ static int gradient_batch_begin(agp_context_impl *ctx, int count, const agp_kern
         d.tang[grp * GRAD_GROUP + j] = scaling[j] ? tcol[(size_t)b] + (size_t)d.slots[grp].param[j] * (size_t)tld[(size_t)b] : nullptr;
     }
   }
-  AGP_HIP_CHECK(ctx, hipMemcpyAsync(desc_d, desc_h, sizeof(ContractDesc) * (size_t)count, hipMemcpyHostToDevice, s));
+  const size_t copy_bytes = sizeof(CopyItem) * copies.size();
+  if (padded) {
+    RaggedPadItem *pads = reinterpret_cast<RaggedPadItem *>(tables_h + pad_off);
+    for (int b = 0; b < count; ++b) {  // the slab and z only: no phantom feature rows (dim = nsc = 0, no ids)
+      RaggedPadItem &pi = pads[b];
+      std::memset(static_cast<void *>(&pi), 0, sizeof(RaggedPadItem));
+      pi.A = A + (size_t)b * (size_t)stride_A;
+      pi.z = z + (size_t)b * (size_t)np2;
+      pi.nb = g.nb[(size_t)b];
+    }
+    if (copy_bytes > 0) std::memcpy(tables_h + copy_off, copies.data(), copy_bytes);
+  }
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(desc_d, tables_h, padded ? copy_off + copy_bytes : desc_bytes, hipMemcpyHostToDevice, s));
   if (!pinned) AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));  // (pageable source)
+  const char *tables_d = reinterpret_cast<const char *>(desc_d);
+  if (!copies.empty()) launch_copy_table(s, reinterpret_cast<const CopyItem *>(tables_d + copy_off), (long long)copies.size(), copy_max);
 
   if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[0], s));
   if ((st = launch_batch_grams(ctx, geo, gram, kernels, a.gram_table, pinned)) != AGP_OK) return st;
+  if (padded) launch_ragged_pad(s, reinterpret_cast<const RaggedPadItem *>(tables_d + pad_off), count, n, lda);
   if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[1], s));
   factor_batch(ctx, geo, /*allow_lookahead=*/true, A, invd, z, r.flags, 4, r.logsum, r.zpub);
   if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[2], s));
@@ -1207,8 +1294,8 @@ static int gradient_batch_begin(agp_context_impl *ctx, int count, const agp_kern
 }
 
 // [logsum | quad | flags], the gradients and (when asked for) every vec_d column: three transfers, one synchronisation;
-// then the host outputs.  value(b, logsum_b, quad_b): problem b's objective.  A failed problem gets NaN for its value and
-// its gradient column and keeps its column of vec.
+// then the host outputs.  value(n_b, logsum_b, quad_b): the objective of a problem of n_b (real) rows.  A failed problem gets
+// NaN for its value and its gradient column and keeps its column of vec; a good one receives the n_b values of its column.
 template <class Value>
 static int gradient_batch_finish(agp_context_impl *ctx, const GradientBatch &g, int count, const int *n_slots, Value value,
                                  double *values, double *grad, int64_t ldg, const double *vec_d, double *vec, int64_t ldvec,
@@ -1237,28 +1324,27 @@ static int gradient_batch_finish(agp_context_impl *ctx, const GradientBatch &g, 
     const int *fl = h_flags + 4 * b;
     status[b] = fl[0] ? AGP_ERR_NAN_INPUT : (fl[1] ? AGP_ERR_NOT_POSITIVE_DEFINITE : AGP_OK);
     const bool ok = status[b] == AGP_OK;
-    values[b] = ok ? value(h_head[(size_t)b], h_head[(size_t)cp2 + (size_t)b]) : nan;
+    values[b] = ok ? value(g.nb[(size_t)b], h_head[(size_t)b], h_head[(size_t)cp2 + (size_t)b]) : nan;
     for (int j = 0; j < n_slots[b]; ++j) grad[(size_t)b * (size_t)ldg + (size_t)j] = ok ? h_grad[(size_t)b * (size_t)g.ldgd + (size_t)j] : nan;
-    if (vec && ok) std::memcpy(vec + (size_t)b * (size_t)ldvec, h_vec.data() + (size_t)b * (size_t)n, sizeof(double) * (size_t)n);
+    if (vec && ok) std::memcpy(vec + (size_t)b * (size_t)ldvec, h_vec.data() + (size_t)b * (size_t)n, sizeof(double) * (size_t)g.nb[(size_t)b]);
   }
   return AGP_OK;
 }
 
-extern "C" {
-
-// ---- agp_nll_gradient for `count` problems of one size in lock step ---------------------------------------------
+// ---- agp_nll_gradient for `count` problems in lock step ----------------------------------------------------------
 // The steps of agp_nll_gradient with blockIdx.y = problem: gradient_batch_begin (z_b^T z_b, alpha_b, R_b, K_b^-1 =
 // R_b^T R_b over L_b), the contraction (grid x = tile, y = problem, z = slot group) and the reduction.  Workspace: the A
 // and R slabs (2 lda n doubles per problem) plus the tile images (stride_I) and O(n) vectors per problem.
-int agp_nll_gradient_batch(agp_context *c, int count, const agp_kernel *const *kernels, const agp_features *const *features,
-                           const double *y, int64_t ldy, const double *y_var, int64_t ldv, const int *n_slots,
-                           const agp_gradient_slot *const *slots, const double *const *tangents, int64_t ldt, double *nll,
-                           double *grad_nll, int64_t ldg, double *information, int64_t ldi, int *status) {
+// `ragged`: agp_nll_gradient_batch_ragged (gradient_batch_begin); the grids keep the padded size.
+static int nll_gradient_batch(agp_context *c, int count, const agp_kernel *const *kernels, const agp_features *const *features,
+                              const double *y, int64_t ldy, const double *y_var, int64_t ldv, const int *n_slots,
+                              const agp_gradient_slot *const *slots, const double *const *tangents, int64_t ldt, double *nll,
+                              double *grad_nll, int64_t ldg, double *information, int64_t ldi, int *status, bool ragged) {
   if (!c || count <= 0 || !kernels || !features || !y || !n_slots || !nll || !status) return AGP_ERR_INVALID_ARGUMENT;
   agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
   GradientBatch g;
   int st = gradient_batch_begin(ctx, count, kernels, features, y, ldy, y_var, ldv, n_slots, slots, tangents, ldt, grad_nll, ldg,
-                                information, ldi, /*quad=*/true, /*rtr=*/true, 0, -1, g);
+                                information, ldi, /*quad=*/true, /*rtr=*/true, 0, -1, ragged, g);
   if (st != AGP_OK) return st;
   hipStream_t s = ctx->stream;
   const bool prof = ctx->profiling;
@@ -1268,9 +1354,11 @@ int agp_nll_gradient_batch(agp_context *c, int count, const agp_kernel *const *k
                        g.tiles, 0.5, g.grad_d, g.ldgd);
   }
   if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[5], s));
-  const double n_log_2pi = (double)g.n * std::log(2 * M_PI);
   st = gradient_batch_finish(ctx, g, count, n_slots,
-                             [&](double logsum, double quad) { return 0.5 * (2. * logsum + quad + n_log_2pi); },  // likelihood.hpp:46
+                             [&](long long nb, double logsum, double quad) {  // likelihood.hpp:46
+                               const double n_log_2pi = (double)nb * std::log(2 * M_PI);
+                               return 0.5 * (2. * logsum + quad + n_log_2pi);
+                             },
                              nll, grad_nll, ldg, g.z, information, ldi, status);
   if (st != AGP_OK) return st;
   if (prof) {
@@ -1284,7 +1372,7 @@ int agp_nll_gradient_batch(agp_context *c, int count, const agp_kernel *const *k
   return AGP_OK;
 }
 
-// ---- agp_loo_nll_gradient for `count` problems of one size in lock step -------------------------------------------
+// ---- agp_loo_nll_gradient for `count` problems in lock step --------------------------------------------------------
 // The steps of agp_loo_nll_gradient with blockIdx.y (z for the G tiles) = problem, each ONE launch for the batch:
 // gradient_batch_begin (alpha_b, R_b, C_b = R_b^T R_b over L_b), the per-point terms from C_b's diagonal and their sum,
 // u_b = C_b a_b (launch_symv_lower_batched), G_b over R_b, S_b = G_b^T G_b over C_b, the contraction of
@@ -1292,11 +1380,14 @@ int agp_nll_gradient_batch(agp_context *c, int count, const agp_kernel *const *k
 // column norms of the R slabs, which lie back to back and are one lda x (count n) matrix; no C, G or G^T G.
 // Workspace: that of agp_nll_gradient_batch plus five vectors per problem, [term | a | sqrt_b | u | c], each an
 // np2 x count array like z.
-int agp_loo_nll_gradient_batch(agp_context *c, int count, const agp_kernel *const *kernels, const agp_features *const *features,
-                               const double *y, int64_t ldy, const double *y_var, int64_t ldv, const int *n_slots,
-                               const agp_gradient_slot *const *slots, const double *const *tangents, int64_t ldt,
-                               double *loo_nll, double *grad_loo_nll, int64_t ldg, double *mean_weights, int64_t ldw,
-                               int *status) {
+// `ragged`: agp_loo_nll_gradient_batch_ragged.  The terms kernel and the sum know every problem's real rows (g.rows_d): a
+// phantom row has term = a = sqrt_b = 0, so u_b = diag(C_b, I) (a_b, 0) and G_b = diag(sqrt_b) diag(C_b, I) are zero there
+// and S_b = G_b^T G_b is diag(S_b, 0); the value-only path sees c = 1 on a phantom row and never reads it.
+static int loo_nll_gradient_batch(agp_context *c, int count, const agp_kernel *const *kernels, const agp_features *const *features,
+                                  const double *y, int64_t ldy, const double *y_var, int64_t ldv, const int *n_slots,
+                                  const agp_gradient_slot *const *slots, const double *const *tangents, int64_t ldt,
+                                  double *loo_nll, double *grad_loo_nll, int64_t ldg, double *mean_weights, int64_t ldw,
+                                  int *status, bool ragged) {
   if (!c || count <= 0 || count > BATCH_MAX_PROBLEMS || !kernels || !features || !y || !n_slots || !loo_nll || !status)
     return AGP_ERR_INVALID_ARGUMENT;
   agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
@@ -1305,7 +1396,7 @@ int agp_loo_nll_gradient_batch(agp_context *c, int count, const agp_kernel *cons
   enum { TERM, A_VEC, SQRT_B, U_VEC, C_DIAG, N_VECTORS };  // the extra np2 x count arrays
   GradientBatch g;
   int st = gradient_batch_begin(ctx, count, kernels, features, y, ldy, y_var, ldv, n_slots, slots, tangents, ldt, grad_loo_nll, ldg,
-                                mean_weights, ldw, /*quad=*/false, /*rtr=*/need_c, N_VECTORS, U_VEC, g);
+                                mean_weights, ldw, /*quad=*/false, /*rtr=*/need_c, N_VECTORS, U_VEC, ragged, g);
   if (st != AGP_OK) return st;
   hipStream_t s = ctx->stream;
   const bool prof = ctx->profiling;
@@ -1315,11 +1406,13 @@ int agp_loo_nll_gradient_batch(agp_context *c, int count, const agp_kernel *cons
   if (!need_c) {
     // c_b[i] = ||R_b[:, i]||^2: count n values, contiguous (the terms kernel's cbatch = n)
     launch_coldot(s, g.R, g.lda, g.R, g.lda, n, (long long)count * n, cdiag, -1.0, nullptr);
-    hipLaunchKernelGGL(loo_terms_kernel, egrid, dim3(256), 0, s, cdiag, 1LL, n, g.z, g.yvar_d, n, g.np2, term, nullptr, nullptr);
+    hipLaunchKernelGGL(loo_terms_kernel, egrid, dim3(256), 0, s, cdiag, 1LL, n, g.z, g.yvar_d, n, g.np2, term, nullptr, nullptr,
+                       g.rows_d);
   } else {
-    hipLaunchKernelGGL(loo_terms_kernel, egrid, dim3(256), 0, s, g.A, g.lda + 1, g.stride_A, g.z, g.yvar_d, n, g.np2, term, a, sqrt_b);
+    hipLaunchKernelGGL(loo_terms_kernel, egrid, dim3(256), 0, s, g.A, g.lda + 1, g.stride_A, g.z, g.yvar_d, n, g.np2, term, a, sqrt_b,
+                       g.rows_d);
   }
-  hipLaunchKernelGGL(loo_sum_kernel, dim3(1, (unsigned)count), dim3(1024), 0, s, term, n, np2, g.quad);
+  hipLaunchKernelGGL(loo_sum_kernel, dim3(1, (unsigned)count), dim3(1024), 0, s, term, n, np2, g.quad, g.rows_d);
   if (need_c) {
     launch_symv_lower_batched(s, g.A, g.lda, g.stride_A, n, a, np2, u, count);  // u_b = C_b a_b
     if (g.groups > 0) {
@@ -1337,7 +1430,7 @@ int agp_loo_nll_gradient_batch(agp_context *c, int count, const agp_kernel *cons
                        g.tiles, 1.0, g.grad_d, g.ldgd);
     if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[7], s));
   }
-  st = gradient_batch_finish(ctx, g, count, n_slots, [](double, double loo) { return loo; }, loo_nll, grad_loo_nll, ldg, u,
+  st = gradient_batch_finish(ctx, g, count, n_slots, [](long long, double, double loo) { return loo; }, loo_nll, grad_loo_nll, ldg, u,
                              mean_weights, ldw, status);
   if (st != AGP_OK) return st;
   if (prof) {
@@ -1358,6 +1451,42 @@ int agp_loo_nll_gradient_batch(agp_context *c, int count, const agp_kernel *cons
     }
   }
   return AGP_OK;
+}
+
+extern "C" {
+
+int agp_nll_gradient_batch(agp_context *c, int count, const agp_kernel *const *kernels, const agp_features *const *features,
+                           const double *y, int64_t ldy, const double *y_var, int64_t ldv, const int *n_slots,
+                           const agp_gradient_slot *const *slots, const double *const *tangents, int64_t ldt, double *nll,
+                           double *grad_nll, int64_t ldg, double *information, int64_t ldi, int *status) {
+  return nll_gradient_batch(c, count, kernels, features, y, ldy, y_var, ldv, n_slots, slots, tangents, ldt, nll, grad_nll, ldg,
+                            information, ldi, status, false);
+}
+
+int agp_nll_gradient_batch_ragged(agp_context *c, int count, const agp_kernel *const *kernels, const agp_features *const *features,
+                                  const double *y, int64_t ldy, const double *y_var, int64_t ldv, const int *n_slots,
+                                  const agp_gradient_slot *const *slots, const double *const *tangents, int64_t ldt, double *nll,
+                                  double *grad_nll, int64_t ldg, double *information, int64_t ldi, int *status) {
+  return nll_gradient_batch(c, count, kernels, features, y, ldy, y_var, ldv, n_slots, slots, tangents, ldt, nll, grad_nll, ldg,
+                            information, ldi, status, true);
+}
+
+int agp_loo_nll_gradient_batch(agp_context *c, int count, const agp_kernel *const *kernels, const agp_features *const *features,
+                               const double *y, int64_t ldy, const double *y_var, int64_t ldv, const int *n_slots,
+                               const agp_gradient_slot *const *slots, const double *const *tangents, int64_t ldt,
+                               double *loo_nll, double *grad_loo_nll, int64_t ldg, double *mean_weights, int64_t ldw,
+                               int *status) {
+  return loo_nll_gradient_batch(c, count, kernels, features, y, ldy, y_var, ldv, n_slots, slots, tangents, ldt, loo_nll,
+                                grad_loo_nll, ldg, mean_weights, ldw, status, false);
+}
+
+int agp_loo_nll_gradient_batch_ragged(agp_context *c, int count, const agp_kernel *const *kernels,
+                                      const agp_features *const *features, const double *y, int64_t ldy, const double *y_var,
+                                      int64_t ldv, const int *n_slots, const agp_gradient_slot *const *slots,
+                                      const double *const *tangents, int64_t ldt, double *loo_nll, double *grad_loo_nll,
+                                      int64_t ldg, double *mean_weights, int64_t ldw, int *status) {
+  return loo_nll_gradient_batch(c, count, kernels, features, y, ldy, y_var, ldv, n_slots, slots, tangents, ldt, loo_nll,
+                                grad_loo_nll, ldg, mean_weights, ldw, status, true);
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
-// ragged_batch.hip — the device side of batches of small fits of UNEQUAL sizes (agp_fit_create_batch_ragged, and the
-// phantom fits that agp_predict_batch and agp_fit_update_batch take in lock step).
+// ragged_batch.hip — the device side of batches of small fits of UNEQUAL sizes (agp_fit_create_batch_ragged, the phantom
+// fits that agp_predict_batch and agp_fit_update_batch take in lock step, and the batched gradients
+// agp_nll_gradient_batch_ragged / agp_loo_nll_gradient_batch_ragged, whose pad items carry the slab and z only).
 //
 // A fit of n_b points in a batch of padded size n is the ordinary fit of diag(K_b, I): its factor is diag(L_b, I), z and
 // the information vector are zero on the trailing phantom rows [n_b, n), the log determinant is that of K_b.  The

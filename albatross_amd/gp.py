@@ -1807,58 +1807,91 @@ def _gradient_problem(model, dataset, entry="agp_nll_gradient"):
     return _GradientProblem(fs, y, yv, slots, table, tangents)
 
 
+def _ragged_columns(problems, members, n, column):
+    """the n x len(members) column-major array whose column j holds column(problems[members[j]]) - n_b values, zeros
+    behind them - or None when no member has that vector (a member without one keeps its zeros)"""
+    vectors = [column(problems[b]) for b in members]
+    if all(v is None for v in vectors):
+        return None
+    out = np.zeros((n, len(members)), order="F")
+    for j, v in enumerate(vectors):
+        if v is not None:
+            out[:len(v), j] = v
+    return out
+
+
+def _ragged_tangents(problems, members, n):
+    """the tangent columns of the members at the leading dimension n of their call (the padded size): the problem's own
+    array where it has n rows already, else a copy with zeros behind the n_b values.  Returns (pointer array, the arrays
+    to keep alive)."""
+    keep = []
+    for b in members:
+        t = problems[b].tangents
+        if t is not None and t.shape[0] != n:
+            wide = np.zeros((n, t.shape[1]), order="F")
+            wide[:t.shape[0]] = t
+            t = wide
+        keep.append(t)
+    return (C.c_void_p * len(members))(*[None if t is None else t.ctypes.data for t in keep]), keep
+
+
 def _log_likelihood_gradients(ctx, models, datasets):
-    """one agp_nll_gradient_batch call over models[b] on datasets[b]: ([log p_b], [{name: d log p_b / d name}]), NaN
-    throughout for a problem whose covariance has NaN or is not positive definite"""
+    """models[b] on datasets[b], of any mix of sizes: one agp_nll_gradient_batch_ragged call per size class
+    (_size_classes; datasets of one size are one class and run the launches of agp_nll_gradient_batch).  Returns
+    ([log p_b], [{name: d log p_b / d name}]) in the caller's order, NaN throughout for a problem whose covariance has NaN
+    or is not positive definite"""
     count = len(models)
     for m, ds in zip(models, datasets):
         if m.precision != "fp64" or m._ctx() is not ctx:
             raise ValueError("log_likelihood_gradient_batch: fp64 models on one context")
     problems = [_gradient_problem(m, ds, "agp_nll_gradient_batch") for m, ds in zip(models, datasets)]
-    n = problems[0].fs.n
-    if any(p.fs.n != n for p in problems):
-        raise ValueError("log_likelihood_gradient_batch: every dataset must have the same number of points")
     structs = [p.fs.as_struct() for p in problems]
-    Y = np.asfortranarray(np.stack([p.y for p in problems], axis=1))
-    ldg = max(1, max(len(p.slots) for p in problems))
-    nll = np.empty(count)
-    grad = np.zeros((count, ldg))   # column b of the ldg x count array: row b here
-    alpha = np.empty((count, n))    # likewise, ldi = n
-    status = (C.c_int * count)()
-    n_slots = (C.c_int * count)(*[len(p.slots) for p in problems])
-    tables = (C.c_void_p * count)(*[C.addressof(p.table) for p in problems])
-    tangents = (C.c_void_p * count)(*[None if p.tangents is None else p.tangents.ctypes.data for p in problems])
+    lls, grads = [None] * count, [None] * count
     handles = []
     try:
         for m in models:  # private handles: the context's small kernel cache may evict while the batch is assembled
             handles.append(ctx.private_kernel(m.covariance_function_))
-        kernels = (C.c_void_p * count)(*handles)
-        fptrs = (C.c_void_p * count)(*[C.addressof(st) for st in structs])
-        # log_likelihood ignores the target variance (gp.hpp:442-451): y_var = NULL
-        ctx._check(ctx._lib.agp_nll_gradient_batch(ctx._h, count, kernels, fptrs, _ptr(Y), n, None, 0, n_slots, tables, tangents,
-                                                   n, _ptr(nll), _ptr(grad), ldg, _ptr(alpha), n, status),
-                   "agp_nll_gradient_batch")
+        for members in _size_classes([p.fs.n for p in problems]):
+            k = len(members)
+            n = max(problems[b].fs.n for b in members)  # the padded size of the class
+            Y = _ragged_columns(problems, members, n, lambda p: p.y)
+            ldg = max(1, max(len(problems[b].slots) for b in members))
+            nll = np.empty(k)
+            grad = np.zeros((k, ldg))   # column j of the ldg x k array: row j here
+            alpha = np.zeros((k, n))    # likewise, ldi = n; problem b's n_b values lead its row
+            status = (C.c_int * k)()
+            n_slots = (C.c_int * k)(*[len(problems[b].slots) for b in members])
+            tables = (C.c_void_p * k)(*[C.addressof(problems[b].table) for b in members])
+            tangents, _keep = _ragged_tangents(problems, members, n)
+            kernels = (C.c_void_p * k)(*[handles[b] for b in members])
+            fptrs = (C.c_void_p * k)(*[C.addressof(structs[b]) for b in members])
+            # log_likelihood ignores the target variance (gp.hpp:442-451): y_var = NULL
+            ctx._check(ctx._lib.agp_nll_gradient_batch_ragged(ctx._h, k, kernels, fptrs, _ptr(Y), n, None, 0, n_slots, tables,
+                                                              tangents, n, _ptr(nll), _ptr(grad), ldg, _ptr(alpha), n, status),
+                       f"agp_nll_gradient_batch_ragged: problems {members}")
+            for j, b in enumerate(members):
+                m, p = models[b], problems[b]
+                if status[j] != capi.AGP_OK:
+                    lls[b] = float("nan")
+                    grads[b] = {name: float("nan") for name in m.get_params()}
+                    continue
+                lls[b] = -nll[j]
+                grads[b] = m._log_likelihood_gradient_dict(p.slots, grad[j, :len(p.slots)], alpha[j, :p.fs.n], p.fs)
     finally:
         for kh in handles:
             ctx._lib.agp_kernel_destroy(kh)
-    lls, grads = [], []
-    for b, (m, p) in enumerate(zip(models, problems)):
-        if status[b] != capi.AGP_OK:
-            lls.append(float("nan"))
-            grads.append({name: float("nan") for name in m.get_params()})
-            continue
-        lls.append(-nll[b])
-        grads.append(m._log_likelihood_gradient_dict(p.slots, grad[b, :len(p.slots)], alpha[b], p.fs))
     return lls, grads
 
 
 def log_likelihood_gradient_batch(models, datasets):
-    """`models[b].log_likelihood_gradient(datasets[b])` for several INDEPENDENT problems of one size in one call
-    (agp_nll_gradient_batch): the gradient counterpart of fit_batch, for multi-start tuning and one model per
+    """`models[b].log_likelihood_gradient(datasets[b])` for several INDEPENDENT problems in lock step
+    (agp_nll_gradient_batch_ragged): the gradient counterpart of fit_batch, for multi-start tuning and one model per
     station / group.  models: fp64 GaussianProcessRegression objects on one context (their covariance trees and feature
-    dimensions may differ); datasets: as many RegressionDatasets with the same number of points.  Returns a list of
-    (log_likelihood, {name: gradient}); a problem whose covariance has NaN or is not positive definite gives NaN
-    throughout instead of raising."""
+    dimensions may differ; one model may appear several times); datasets: as many RegressionDatasets.  Their sizes may
+    differ: the problems are put into size classes (_size_classes) and one lock-step call runs per class, every problem
+    padded with phantom rows to the largest size of its class; equal sizes are one class without padding.
+    Returns a list of (log_likelihood, {name: gradient}) in the caller's order; a problem whose covariance has NaN or is
+    not positive definite gives NaN throughout instead of raising."""
     if len(models) != len(datasets) or not models:
         raise ValueError("log_likelihood_gradient_batch: as many datasets as models, at least one")
     lls, grads = _log_likelihood_gradients(models[0]._ctx(), list(models), list(datasets))
@@ -1866,9 +1899,10 @@ def log_likelihood_gradient_batch(models, datasets):
 
 
 def _leave_one_out_likelihood_gradients(models, datasets, caller, value_only=False):
-    """one agp_loo_nll_gradient_batch call over models[b] on datasets[b]: ([LOO_b], [{name: d LOO_b / d name}]), NaN
-    throughout for a problem whose covariance has NaN or is not positive definite.  caller: the public name, for the
-    error texts.  value_only: no slots and no mean weights (the entry's value-only path); the gradients are None."""
+    """models[b] on datasets[b], of any mix of sizes: one agp_loo_nll_gradient_batch_ragged call per size class.  Returns
+    ([LOO_b], [{name: d LOO_b / d name}]) in the caller's order, NaN throughout for a problem whose covariance has NaN or
+    is not positive definite.  caller: the public name, for the error texts.  value_only: no slots and no mean weights
+    (the entry's value-only path); the gradients are None."""
     count = len(models)
     # plain checks first, none of which needs a device: LinearCombination features, precision, then one context
     for ds in datasets:
@@ -1880,60 +1914,92 @@ def _leave_one_out_likelihood_gradients(models, datasets, caller, value_only=Fal
     if any(m._ctx() is not ctx for m in models):
         raise ValueError(f"{caller}: every model must live on one context")
     problems = [_gradient_problem(m, ds, "agp_loo_nll_gradient_batch") for m, ds in zip(models, datasets)]
-    n = problems[0].fs.n
-    if any(p.fs.n != n for p in problems):
-        raise ValueError(f"{caller}: every dataset must have the same number of points")
     structs = [p.fs.as_struct() for p in problems]
-    Y = np.asfortranarray(np.stack([p.y for p in problems], axis=1))
-    # the target variance, in the fit and as the truth's variance; problems without one get zeros beside those with one
-    have_var = any(p.yv is not None for p in problems)
-    V = np.asfortranarray(np.stack([np.zeros(n) if p.yv is None else p.yv for p in problems], axis=1)) if have_var else None
-    n_used = [0 if value_only else len(p.slots) for p in problems]
-    ldg = max(1, max(n_used))
-    loo = np.empty(count)
-    grad = np.zeros((count, ldg))                   # column b of the ldg x count array: row b here
-    u = None if value_only else np.empty((count, n))  # likewise, ldw = n
-    status = (C.c_int * count)()
-    n_slots = (C.c_int * count)(*n_used)
-    tables = (C.c_void_p * count)(*[C.addressof(p.table) for p in problems])
-    tangents = (C.c_void_p * count)(*[None if p.tangents is None else p.tangents.ctypes.data for p in problems])
+    values, grads = [None] * count, [None] * count
     handles = []
     try:
         for m in models:  # private handles: the context's small kernel cache may evict while the batch is assembled
             handles.append(ctx.private_kernel(m.covariance_function_))
-        kernels = (C.c_void_p * count)(*handles)
-        fptrs = (C.c_void_p * count)(*[C.addressof(st) for st in structs])
-        ctx._check(ctx._lib.agp_loo_nll_gradient_batch(ctx._h, count, kernels, fptrs, _ptr(Y), n, _ptr(V) if have_var else None, n,
-                                                       n_slots, tables, tangents, n, _ptr(loo), _ptr(grad), ldg,
-                                                       None if value_only else _ptr(u), n, status),
-                   "agp_loo_nll_gradient_batch")
+        for members in _size_classes([p.fs.n for p in problems]):
+            k = len(members)
+            n = max(problems[b].fs.n for b in members)  # the padded size of the class
+            Y = _ragged_columns(problems, members, n, lambda p: p.y)
+            # the target variance, in the fit and as the truth's variance; problems without one get zeros beside those with one
+            V = _ragged_columns(problems, members, n, lambda p: p.yv)
+            n_used = [0 if value_only else len(problems[b].slots) for b in members]
+            ldg = max(1, max(n_used))
+            loo = np.empty(k)
+            grad = np.zeros((k, ldg))                      # column j of the ldg x k array: row j here
+            u = None if value_only else np.zeros((k, n))  # likewise, ldw = n
+            status = (C.c_int * k)()
+            n_slots = (C.c_int * k)(*n_used)
+            tables = (C.c_void_p * k)(*[C.addressof(problems[b].table) for b in members])
+            tangents, _keep = _ragged_tangents(problems, members, n)
+            kernels = (C.c_void_p * k)(*[handles[b] for b in members])
+            fptrs = (C.c_void_p * k)(*[C.addressof(structs[b]) for b in members])
+            ctx._check(ctx._lib.agp_loo_nll_gradient_batch_ragged(ctx._h, k, kernels, fptrs, _ptr(Y), n,
+                                                                  None if V is None else _ptr(V), n, n_slots, tables, tangents, n,
+                                                                  _ptr(loo), _ptr(grad), ldg, None if value_only else _ptr(u), n,
+                                                                  status),
+                       f"agp_loo_nll_gradient_batch_ragged: problems {members}")
+            for j, b in enumerate(members):
+                m, p = models[b], problems[b]
+                ok = status[j] == capi.AGP_OK
+                values[b] = float(loo[j]) if ok else float("nan")
+                if value_only:
+                    grads[b] = None
+                elif ok:
+                    grads[b] = m._leave_one_out_gradient_dict(p.slots, grad[j, :len(p.slots)], u[j, :p.fs.n], p.fs)
+                else:
+                    grads[b] = {name: float("nan") for name in m.get_params()}
     finally:
         for kh in handles:
             ctx._lib.agp_kernel_destroy(kh)
-    values, grads = [], []
-    for b, (m, p) in enumerate(zip(models, problems)):
-        ok = status[b] == capi.AGP_OK
-        values.append(float(loo[b]) if ok else float("nan"))
-        if value_only:
-            grads.append(None)
-        elif ok:
-            grads.append(m._leave_one_out_gradient_dict(p.slots, grad[b, :len(p.slots)], u[b], p.fs))
-        else:
-            grads.append({name: float("nan") for name in m.get_params()})
     return values, grads
 
 
 def leave_one_out_likelihood_gradient_batch(models, datasets):
-    """`models[b].leave_one_out_likelihood_gradient(datasets[b])` for several INDEPENDENT problems of one size in one
-    call (agp_loo_nll_gradient_batch): the counterpart of log_likelihood_gradient_batch for the leave-one-out metric.
+    """`models[b].leave_one_out_likelihood_gradient(datasets[b])` for several INDEPENDENT problems in lock step
+    (agp_loo_nll_gradient_batch_ragged): the counterpart of log_likelihood_gradient_batch for the leave-one-out metric.
     models: fp64 GaussianProcessRegression objects on one context (their covariance trees and feature dimensions may
-    differ); datasets: as many RegressionDatasets with the same number of points, each with or without a target
-    variance.  Returns a list of (value, {name: gradient}); a problem whose covariance has NaN or is not positive
-    definite gives NaN throughout instead of raising."""
+    differ); datasets: as many RegressionDatasets of any mix of sizes (one call per size class, as
+    log_likelihood_gradient_batch), each with or without a target variance.  Returns a list of (value, {name: gradient})
+    in the caller's order; a problem whose covariance has NaN or is not positive definite gives NaN throughout instead of
+    raising."""
     if len(models) != len(datasets) or not models:
         raise ValueError("leave_one_out_likelihood_gradient_batch: as many datasets as models, at least one")
     values, grads = _leave_one_out_likelihood_gradients(list(models), list(datasets), "leave_one_out_likelihood_gradient_batch")
     return list(zip(values, grads))
+
+
+def _pooled(model, results):
+    """(sum of the values, {name: sum of the gradients}) of the per-dataset results of one model, summed in the caller's
+    order; NaN throughout if any problem failed"""
+    names = list(model.get_params())
+    if any(np.isnan(v) for v, _ in results):
+        return float("nan"), {name: float("nan") for name in names}
+    total = 0.
+    grad = {name: 0. for name in names}
+    for v, g in results:
+        total += v
+        for name in names:
+            grad[name] += g[name]
+    return total, grad
+
+
+def pooled_log_likelihood_gradient(model, datasets):
+    """One model shared by many datasets of any sizes (one parameter vector tuned on every station's data):
+    (sum_b log p_b, {name: sum_b d log p_b / d name}) over log_likelihood_gradient_batch([model] * B, datasets).  NaN
+    throughout if any problem fails."""
+    datasets = list(datasets)
+    return _pooled(model, log_likelihood_gradient_batch([model] * len(datasets), datasets))
+
+
+def pooled_leave_one_out_likelihood_gradient(model, datasets):
+    """pooled_log_likelihood_gradient for the leave-one-out metric: (sum_b LOO_b, {name: sum_b d LOO_b / d name}) over
+    leave_one_out_likelihood_gradient_batch([model] * B, datasets).  NaN throughout if any problem fails."""
+    datasets = list(datasets)
+    return _pooled(model, leave_one_out_likelihood_gradient_batch([model] * len(datasets), datasets))
 
 
 def gp_from_covariance(covariance_function, model_name="gaussian_process_regression", context=None):

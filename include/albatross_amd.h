@@ -572,7 +572,8 @@ AGP_API int agp_fit_create_batch(agp_context *ctx, int count, const agp_kernel *
  * give the same bits.  The cost of the padding: every problem is factored at size n.  Callers bound it by batching sizes
  * of one class ceil(n_b / 128) per call, as the Python and C++ surfaces do.
  * Not covered: unequal numbers of test points in agp_predict_batch and of new points in agp_fit_update_batch, a ragged
- * agp_nll_batch and the batched gradients, cross validation of phantom fits, mixed precision, the sharded path. */
+ * agp_nll_batch, cross validation of phantom fits, mixed precision, the sharded path.  (The batched gradients of unequal
+ * sizes: agp_nll_gradient_batch_ragged and agp_loo_nll_gradient_batch_ragged below.) */
 AGP_API int agp_fit_create_batch_ragged(agp_context *ctx, int count, const agp_kernel *const *kernels,
                                         const agp_features *const *features, const double *y, int64_t ldy, const double *y_var,
                                         int64_t ldv, agp_fit **out, double *information, int64_t ldi, double *log_det, int *status);
@@ -580,6 +581,56 @@ AGP_API int agp_fit_create_batch_ragged(agp_context *ctx, int count, const agp_k
 /* The rows the factor of `fit` holds, phantom rows included (agp_fit_size counts the real ones).  agp_predict_batch and
  * agp_fit_update_batch take fits of one padded size per call. */
 AGP_API int64_t agp_fit_padded_size(const agp_fit *fit);
+
+/* agp_nll_gradient_batch for problems of UNEQUAL sizes: the same arguments, but features[b]->n = n_b > 0 may differ (the
+ * models that agp_fit_create_batch_ragged fits are tuned with this).  The padded size n of the call is the largest n_b
+ * (not rounded).  Problem b computes what agp_nll_gradient computes for its n_b points - the value with n_b log 2 pi, the
+ * gradient, alpha_b - as the problem diag(K_b, I): its Gram launch runs on the n_b real rows (so the target variance goes
+ * onto real diagonals and the NaN flag comes from real rows only), one pad launch writes the phantom rows [n_b, n) of
+ * its slab as identity rows, the factor, alpha, R = L^-1 and R^T R run at size n, and the contraction takes the pairs of
+ * the n_b real points only.
+ *   y, ldy            column b holds n_b values; what follows them in the column is never read.  ldy and (with y_var) ldv
+ *                     are 0 (one shared vector of n values, of which problem b uses the first n_b) or at least n
+ *   tangents[b], ldt  every tangent column holds n_b values; ldt >= n whenever some problem has a tangent column
+ *   information, ldi  column b receives n_b values; the rest of the column is not written; ldi >= n
+ *   status[b]         per problem, about real rows only
+ * A failed problem gets nll[b] = NaN and a NaN gradient column and leaves its column of information untouched; its
+ * neighbours are unaffected.  A malformed argument anywhere (the list of agp_nll_gradient_batch without the n mismatch, a
+ * size <= 0, a leading dimension below n, mixed locations, count > 65535) returns AGP_ERR_INVALID_ARGUMENT and writes
+ * nothing, status included.  With all sizes equal the call runs the launches of agp_nll_gradient_batch and returns the
+ * same bits.  No float atomics, fixed-order reductions: two identical calls are bit-identical.  The cost of the padding:
+ * every problem is factored at size n; callers bound it by batching sizes of one class ceil(n_b / 128) per call, as the
+ * Python and C++ surfaces do.  Stage indices of agp_last_stage_ms as agp_nll_gradient_batch (the pad launch counts to
+ * stage 0). */
+AGP_API int agp_nll_gradient_batch_ragged(agp_context *ctx, int count,
+                                          const agp_kernel *const *kernels, const agp_features *const *features,
+                                          const double *y, int64_t ldy,
+                                          const double *y_var, int64_t ldv,
+                                          const int *n_slots,
+                                          const agp_gradient_slot *const *slots,
+                                          const double *const *tangents, int64_t ldt,
+                                          double *nll,
+                                          double *grad_nll, int64_t ldg,
+                                          double *information, int64_t ldi,
+                                          int *status);
+
+/* agp_loo_nll_gradient_batch for problems of UNEQUAL sizes, with the rules of agp_nll_gradient_batch_ragged: problem b
+ * computes what agp_loo_nll_gradient computes for its n_b points (the sum of n_b terms with n_b log 2 pi, the gradient,
+ * u_b).  The per-point terms of a phantom row are written as zero and its target variance is never read.
+ *   mean_weights, ldw  column b receives the n_b values of u_b; the rest of the column is not written; ldw >= n
+ * The value-only path (every n_slots[b] == 0, mean_weights NULL) is that of agp_loo_nll_gradient_batch.  With all sizes
+ * equal the call runs the launches of agp_loo_nll_gradient_batch and returns the same bits; stage indices likewise. */
+AGP_API int agp_loo_nll_gradient_batch_ragged(agp_context *ctx, int count,
+                                              const agp_kernel *const *kernels, const agp_features *const *features,
+                                              const double *y, int64_t ldy,
+                                              const double *y_var, int64_t ldv,
+                                              const int *n_slots,
+                                              const agp_gradient_slot *const *slots,
+                                              const double *const *tangents, int64_t ldt,
+                                              double *loo_nll,
+                                              double *grad_loo_nll, int64_t ldg,
+                                              double *mean_weights, int64_t ldw,
+                                              int *status);
 
 /* ---- solve (CovarianceRepresentation::solve, gp.hpp:42-45,68,96,111) ----- */
 /* out = K^-1 rhs; rhs/out column-major n x nrhs (ld = n), at `location`. */

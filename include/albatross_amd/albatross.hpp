@@ -2003,15 +2003,24 @@ class GaussianProcessRegression {
     std::vector<LogLikelihoodGradient> out;
     // like log_likelihood: the target variance is NOT part of the covariance (gp.hpp:442-451)
     const BatchedSlotGradients r = slot_gradients_batch(agp_nll_gradient_batch, "agp_nll_gradient_batch", dataset, parameter_sets, false);
-    const std::size_t n = dataset.features.size();
-    for (std::size_t b = 0; b < parameter_sets.size(); ++b) {
-      if (r.status[b] != AGP_OK) {
-        out.push_back(LogLikelihoodGradient{std::numeric_limits<double>::quiet_NaN(), r.models[b].nan_gradient()});
-        continue;
-      }
-      const std::vector<double> a(r.vec.begin() + static_cast<std::ptrdiff_t>(b * n), r.vec.begin() + static_cast<std::ptrdiff_t>((b + 1) * n));
-      out.push_back(r.models[b].gradient_of_log_likelihood(dataset, r.value[b], r.names[b], r.grad.data() + b * r.ldg, a));
-    }
+    for (std::size_t b = 0; b < parameter_sets.size(); ++b) out.push_back(log_likelihood_result(r, b, dataset));
+    return out;
+  }
+
+  // log_likelihood_gradient(datasets[b]) of THIS model for several datasets of any sizes (one model per station): the
+  // datasets are put into size classes (detail::size_classes) and one lock-step call runs per class
+  // (agp_nll_gradient_batch_ragged), every problem padded with phantom rows to the largest size of its class; datasets of
+  // one size are one class without padding.  Results in the caller's order; NaN throughout for a dataset whose covariance
+  // is not positive definite (or has NaN).
+  template <typename FeatureType>
+  std::vector<LogLikelihoodGradient> log_likelihood_gradient_batch(const std::vector<RegressionDataset<FeatureType>> &datasets) const {
+    std::vector<LogLikelihoodGradient> out(datasets.size());
+    for_each_size_class(datasets, [&](const std::vector<std::size_t> &members,
+                                      const std::vector<const RegressionDataset<FeatureType> *> &ptrs) {
+      const BatchedSlotGradients r = slot_gradients_batch(agp_nll_gradient_batch_ragged, "agp_nll_gradient_batch_ragged", ptrs,
+                                                          std::vector<ParameterStore>(members.size()), false);
+      for (std::size_t j = 0; j < members.size(); ++j) out[members[j]] = log_likelihood_result(r, j, *ptrs[j]);
+    });
     return out;
   }
 
@@ -2117,21 +2126,22 @@ class GaussianProcessRegression {
     std::vector<LeaveOneOutLikelihoodGradient> out;
     const BatchedSlotGradients r =
         slot_gradients_batch(agp_loo_nll_gradient_batch, "agp_loo_nll_gradient_batch", dataset, parameter_sets, true);
-    const std::size_t n = dataset.features.size();
-    for (std::size_t b = 0; b < parameter_sets.size(); ++b) {
-      if (r.status[b] != AGP_OK) {
-        out.push_back(LeaveOneOutLikelihoodGradient{std::numeric_limits<double>::quiet_NaN(), r.models[b].nan_gradient()});
-        continue;
-      }
-      const GaussianProcessRegression &m = r.models[b];
-      LeaveOneOutLikelihoodGradient g{r.value[b], {}};
-      for (const auto &kv : m.get_params()) g.gradient[kv.first] = 0.;
-      for (std::size_t s = 0; s < r.names[b].size(); ++s) g.gradient[r.names[b][s]] += r.grad[b * r.ldg + s];
-      const std::vector<double> u(r.vec.begin() + static_cast<std::ptrdiff_t>(b * n), r.vec.begin() + static_cast<std::ptrdiff_t>((b + 1) * n));
-      for (const auto &kv : m.mean_function_.get_params())  // y = targets - mu: d LOO / d theta = -u^T (d mu / d theta)
-        g.gradient[kv.first] -= m.mean_tangent_dot(dataset, kv.first, kv.second, u);
-      out.push_back(g);
-    }
+    for (std::size_t b = 0; b < parameter_sets.size(); ++b) out.push_back(leave_one_out_result(r, b, dataset));
+    return out;
+  }
+
+  // leave_one_out_likelihood_gradient(datasets[b]) of THIS model for several datasets of any sizes, each with or without
+  // a target variance: one agp_loo_nll_gradient_batch_ragged call per size class, as log_likelihood_gradient_batch.
+  template <typename FeatureType>
+  std::vector<LeaveOneOutLikelihoodGradient> leave_one_out_likelihood_gradient_batch(
+      const std::vector<RegressionDataset<FeatureType>> &datasets) const {
+    std::vector<LeaveOneOutLikelihoodGradient> out(datasets.size());
+    for_each_size_class(datasets, [&](const std::vector<std::size_t> &members,
+                                      const std::vector<const RegressionDataset<FeatureType> *> &ptrs) {
+      const BatchedSlotGradients r = slot_gradients_batch(agp_loo_nll_gradient_batch_ragged, "agp_loo_nll_gradient_batch_ragged", ptrs,
+                                                          std::vector<ParameterStore>(members.size()), true);
+      for (std::size_t j = 0; j < members.size(); ++j) out[members[j]] = leave_one_out_result(r, j, *ptrs[j]);
+    });
     return out;
   }
 
@@ -2230,16 +2240,19 @@ class GaussianProcessRegression {
     return g;
   }
 
-  // One call of a batched gradient entry (agp_nll_gradient_batch / agp_loo_nll_gradient_batch) over one model copy per
-  // parameter set: the copies, their slot names, and per problem the value, the ldg slot gradients, the n values the
-  // entry returns (alpha / mean weights) and the status.  with_variance: dataset.targets.covariance is passed on, one
-  // vector shared by every problem.  value_only: no slots and no n-vector are asked for (names, grad and vec stay empty).
+  // One call of a batched gradient entry (agp_nll_gradient_batch / agp_loo_nll_gradient_batch or their _ragged twins) over
+  // one model copy per problem, each with its parameter set and its dataset: the copies, their slot names, and per
+  // problem the value, the ldg slot gradients, the values the entry returns (alpha / mean weights: problem b's n_b values
+  // at vec[b * n], n the padded size of the call - the largest dataset) and the status.  Targets, variances and tangent
+  // columns are laid out at the stride n; the equal-size entries take datasets of one size only.  with_variance: the
+  // datasets' targets.covariance is passed on (zeros for a dataset without one beside datasets that have one).
+  // value_only: no slots and no n-vector are asked for (names, grad and vec stay empty).
   struct BatchedSlotGradients {
     std::vector<GaussianProcessRegression> models;
     std::vector<std::vector<std::string>> names;
     std::vector<double> value, grad, vec;
     std::vector<int> status;
-    std::size_t ldg = 1;
+    std::size_t ldg = 1, n = 0;
   };
   using BatchedGradientEntry = int (*)(agp_context *, int, const agp_kernel *const *, const agp_features *const *, const double *,
                                        std::int64_t, const double *, std::int64_t, const int *, const agp_gradient_slot *const *,
@@ -2247,12 +2260,20 @@ class GaussianProcessRegression {
                                        int *);
 
   template <typename FeatureType>
-  BatchedSlotGradients slot_gradients_batch(BatchedGradientEntry entry, const char *what, const RegressionDataset<FeatureType> &dataset,
+  BatchedSlotGradients slot_gradients_batch(BatchedGradientEntry entry, const char *what,
+                                            const std::vector<const RegressionDataset<FeatureType> *> &datasets,
                                             const std::vector<ParameterStore> &parameter_sets, bool with_variance,
                                             bool value_only = false) const {
-    const std::size_t count = parameter_sets.size(), n = dataset.features.size();
+    const std::size_t count = parameter_sets.size();
     BatchedSlotGradients r;
     if (count == 0) return r;
+    std::size_t n = 0;
+    bool have_variance = false;
+    for (const auto *ds : datasets) {
+      n = std::max(n, static_cast<std::size_t>(ds->features.size()));
+      have_variance = have_variance || (with_variance && !ds->targets.covariance.empty());
+    }
+    r.n = n;
     auto ctx = detail::default_context();
     r.models.assign(count, *this);
     r.names.resize(count);
@@ -2260,18 +2281,28 @@ class GaussianProcessRegression {
     std::vector<detail::Flat> flats(count);
     std::vector<const agp_kernel *> kptr(count);
     std::vector<const agp_features *> fptr(count);
-    std::vector<double> Y(n * count);
+    std::vector<double> Y(n * count), V(have_variance ? n * count : 0);
     std::vector<std::vector<agp_gradient_slot>> slots(count);
     std::vector<std::vector<double>> tangents(count);
     std::vector<int> n_slots(count);
     for (std::size_t b = 0; b < count; ++b) {
+      const RegressionDataset<FeatureType> &dataset = *datasets[b];
+      const std::size_t nb = dataset.features.size();
       r.models[b].set_param_values(parameter_sets[b]);
       kernels.emplace_back(new detail::KernelHolder(r.models[b].covariance_function_.program()));
       flats[b] = detail::flatten(r.models[b].covariance_function_, dataset.features);
       kptr[b] = kernels.back()->k;
       const Vector y = r.models[b].deviation(dataset);
-      for (std::size_t i = 0; i < n; ++i) Y[b * n + i] = y[i];
+      for (std::size_t i = 0; i < nb; ++i) Y[b * n + i] = y[i];
+      if (have_variance && !dataset.targets.covariance.empty())
+        for (std::size_t i = 0; i < nb; ++i) V[b * n + i] = dataset.targets.covariance[i];
       if (!value_only) r.models[b].slot_table(dataset, &r.names[b], &slots[b], &tangents[b]);
+      if (nb != n && !tangents[b].empty()) {  // the columns of n_b values at the stride of the padded size
+        const std::size_t columns = tangents[b].size() / nb;
+        std::vector<double> wide(n * columns, 0.);
+        for (std::size_t c = 0; c < columns; ++c) std::copy_n(tangents[b].begin() + static_cast<std::ptrdiff_t>(c * nb), nb, wide.begin() + static_cast<std::ptrdiff_t>(c * n));
+        tangents[b].swap(wide);
+      }
       n_slots[b] = static_cast<int>(slots[b].size());
       r.ldg = std::max(r.ldg, slots[b].size());
     }
@@ -2286,13 +2317,59 @@ class GaussianProcessRegression {
     r.grad.resize(r.ldg * count);
     if (!value_only) r.vec.resize(n * count);
     r.status.resize(count);
-    const double *yvar = with_variance && !dataset.targets.covariance.empty() ? dataset.targets.covariance.data() : nullptr;
-    detail::check(entry(ctx->ctx, static_cast<int>(count), kptr.data(), fptr.data(), Y.data(), static_cast<std::int64_t>(n), yvar, 0,
-                        n_slots.data(), sptr.data(), tptr.data(), static_cast<std::int64_t>(n), r.value.data(), r.grad.data(),
-                        static_cast<std::int64_t>(r.ldg), value_only ? nullptr : r.vec.data(), static_cast<std::int64_t>(n),
-                        r.status.data()),
+    detail::check(entry(ctx->ctx, static_cast<int>(count), kptr.data(), fptr.data(), Y.data(), static_cast<std::int64_t>(n),
+                        have_variance ? V.data() : nullptr, static_cast<std::int64_t>(n), n_slots.data(), sptr.data(), tptr.data(),
+                        static_cast<std::int64_t>(n), r.value.data(), r.grad.data(), static_cast<std::int64_t>(r.ldg),
+                        value_only ? nullptr : r.vec.data(), static_cast<std::int64_t>(n), r.status.data()),
                   ctx->ctx, what);
     return r;
+  }
+
+  // ... over the parameter sets of one dataset
+  template <typename FeatureType>
+  BatchedSlotGradients slot_gradients_batch(BatchedGradientEntry entry, const char *what, const RegressionDataset<FeatureType> &dataset,
+                                            const std::vector<ParameterStore> &parameter_sets, bool with_variance,
+                                            bool value_only = false) const {
+    const std::vector<const RegressionDataset<FeatureType> *> datasets(parameter_sets.size(), &dataset);
+    return slot_gradients_batch(entry, what, datasets, parameter_sets, with_variance, value_only);
+  }
+
+  // problem b of a batched leave-one-out call as the public surface reports it
+  template <typename FeatureType>
+  static LeaveOneOutLikelihoodGradient leave_one_out_result(const BatchedSlotGradients &r, std::size_t b,
+                                                            const RegressionDataset<FeatureType> &dataset) {
+    if (r.status[b] != AGP_OK) return LeaveOneOutLikelihoodGradient{std::numeric_limits<double>::quiet_NaN(), r.models[b].nan_gradient()};
+    const GaussianProcessRegression &m = r.models[b];
+    LeaveOneOutLikelihoodGradient g{r.value[b], {}};
+    for (const auto &kv : m.get_params()) g.gradient[kv.first] = 0.;
+    for (std::size_t s = 0; s < r.names[b].size(); ++s) g.gradient[r.names[b][s]] += r.grad[b * r.ldg + s];
+    const auto first = r.vec.begin() + static_cast<std::ptrdiff_t>(b * r.n);
+    const std::vector<double> u(first, first + static_cast<std::ptrdiff_t>(dataset.features.size()));
+    for (const auto &kv : m.mean_function_.get_params())  // y = targets - mu: d LOO / d theta = -u^T (d mu / d theta)
+      g.gradient[kv.first] -= m.mean_tangent_dot(dataset, kv.first, kv.second, u);
+    return g;
+  }
+
+  // ... and of a batched log-likelihood call
+  template <typename FeatureType>
+  static LogLikelihoodGradient log_likelihood_result(const BatchedSlotGradients &r, std::size_t b,
+                                                     const RegressionDataset<FeatureType> &dataset) {
+    if (r.status[b] != AGP_OK) return LogLikelihoodGradient{std::numeric_limits<double>::quiet_NaN(), r.models[b].nan_gradient()};
+    const auto first = r.vec.begin() + static_cast<std::ptrdiff_t>(b * r.n);
+    const std::vector<double> a(first, first + static_cast<std::ptrdiff_t>(dataset.features.size()));
+    return r.models[b].gradient_of_log_likelihood(dataset, r.value[b], r.names[b], r.grad.data() + b * r.ldg, a);
+  }
+
+  // the datasets of one size class each (detail::size_classes), as pointers, with the caller's indices
+  template <typename FeatureType, typename PerClass>
+  static void for_each_size_class(const std::vector<RegressionDataset<FeatureType>> &datasets, PerClass per_class) {
+    std::vector<std::size_t> sizes;
+    for (const auto &ds : datasets) sizes.push_back(static_cast<std::size_t>(ds.features.size()));
+    for (const auto &members : detail::size_classes(sizes)) {
+      std::vector<const RegressionDataset<FeatureType> *> ptrs;
+      for (std::size_t b : members) ptrs.push_back(&datasets[b]);
+      per_class(members, ptrs);
+    }
   }
 
   // The slot table of the covariance function at the dataset's features: names[s] / slots[s] per slot, and the tangent
