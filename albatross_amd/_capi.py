@@ -270,6 +270,17 @@ def load_debug():
         _debug_lib.agp_debug_factor_plan.argtypes = [_P, C.c_int64, _P, C.c_int64]
         _debug_lib.agp_debug_step_launch_shape.restype = C.c_int
         _debug_lib.agp_debug_step_launch_shape.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P]
+        # the column-pivoted QR and the substitutions against its R on host arrays (csrc/qr.hip)
+        i64 = C.c_int64
+        for name, argtypes in (
+                ("agp_debug_colpiv_qr", [_P, _P, i64, i64, i64, i64, i64, _P, _P, _P]),
+                ("agp_debug_qr_extract_r", [_P, _P, i64, i64, _P, i64, C.c_double]),
+                ("agp_debug_qr_root", [_P, _P, i64, _P, i64, _P, i64]),
+                ("agp_debug_qr_sqrt_solve", [_P, _P, i64, _P, i64, _P, i64, _P, i64, i64, i64]),
+                ("agp_debug_qr_back_solve", [_P, _P, i64, _P, i64, i64, _P, _P])):
+            fn = getattr(_debug_lib, name)
+            fn.restype = C.c_int
+            fn.argtypes = argtypes
     return _debug_lib
 
 

@@ -1505,6 +1505,144 @@ AGP_DEBUG_API int agp_debug_predict_mean(agp_context *ctx, const agp_kernel *k, 
   return AGP_OK;
 }
 
+// ---- the column-pivoted QR of qr.hip and the substitutions against its R, one building block at a time (tests/test_qr_gpu.py) ----
+// Every entry point takes the caller's WHOLE padded host buffers, uploads them, runs on ctx->stream and downloads them whole:
+// what the kernels did not store comes back bit for bit.  A permutation that is not one of 0 .. m - 1 is refused before
+// anything is launched (the kernels index with it).
+static bool qr_perm_valid(const int64_t *perm, int64_t m) {
+  std::vector<char> seen((size_t)m, 0);
+  for (int64_t i = 0; i < m; ++i) {
+    if (perm[i] < 0 || perm[i] >= m || seen[(size_t)perm[i]]) return false;
+    seen[(size_t)perm[i]] = 1;
+  }
+  return true;
+}
+
+// colpiv_qr: A (lda x alloc_cols; the rows x (cols + extra) part is factored in place), tau (cols), perm (cols), state (4:
+// threshold helper, max |pivot|, nonzero_pivots, rank).  rows < cols is refused: the product never factors a wide matrix
+// (sparse_api.hip: sparse_pivoted_from_rows has rows >= m) and qr_extract_r reads m rows of it.
+AGP_DEBUG_API int agp_debug_colpiv_qr(agp_context *ctx, double *A, int64_t lda, int64_t rows, int64_t cols, int64_t extra,
+                                      int64_t alloc_cols, double *tau, int64_t *perm, double *state) {
+  if (!ctx || !A || !tau || !perm || !state || rows <= 0 || cols <= 0 || extra < 0 || rows < cols || lda < rows ||
+      alloc_cols < cols + extra)
+    return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const size_t na = (size_t)lda * (size_t)alloc_cols, nc = (size_t)cols;
+  DevBuf<double> dA, aux;  // aux: tau | norms | state
+  DevBuf<long long> dperm;
+  AGP_HIP_CHECK(ctx, dA.alloc(na));
+  AGP_HIP_CHECK(ctx, aux.alloc(2 * nc + 4));
+  AGP_HIP_CHECK(ctx, dperm.alloc(nc));
+  AGP_HIP_CHECK(ctx, hipMemcpy(dA.p, A, sizeof(double) * na, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipMemset(aux.p, 0xFF, sizeof(double) * (2 * nc + 4)));  // (all ones: a NaN)
+  AGP_HIP_CHECK(ctx, hipMemset(dperm.p, 0xFF, sizeof(long long) * nc));
+  AGP_HIP_CHECK(ctx, hipDeviceSynchronize());  // (the null-stream copies above do not order with the context's stream)
+  colpiv_qr(ctx->stream, dA.p, lda, rows, cols, extra, aux.p, dperm.p, aux.p + nc, aux.p + 2 * nc);
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  static_assert(sizeof(long long) == sizeof(int64_t), "perm is copied as it is");
+  AGP_HIP_CHECK(ctx, hipMemcpy(A, dA.p, sizeof(double) * na, hipMemcpyDeviceToHost));
+  AGP_HIP_CHECK(ctx, hipMemcpy(tau, aux.p, sizeof(double) * nc, hipMemcpyDeviceToHost));
+  AGP_HIP_CHECK(ctx, hipMemcpy(state, aux.p + 2 * nc, sizeof(double) * 4, hipMemcpyDeviceToHost));
+  AGP_HIP_CHECK(ctx, hipMemcpy(perm, dperm.p, sizeof(int64_t) * nc, hipMemcpyDeviceToHost));
+  return AGP_OK;
+}
+
+// qr_extract_r: A (lda x m, read), R (ldr x m, the caller's filling; its first m rows are written)
+AGP_DEBUG_API int agp_debug_qr_extract_r(agp_context *ctx, const double *A, int64_t lda, int64_t m, double *R, int64_t ldr,
+                                         double inflate) {
+  if (!ctx || !A || !R || m <= 0 || lda < m || ldr < m) return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const size_t na = (size_t)lda * (size_t)m, nr = (size_t)ldr * (size_t)m;
+  DevBuf<double> dA, dR;
+  AGP_HIP_CHECK(ctx, dA.alloc(na));
+  AGP_HIP_CHECK(ctx, dR.alloc(nr));
+  AGP_HIP_CHECK(ctx, hipMemcpy(dA.p, A, sizeof(double) * na, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipMemcpy(dR.p, R, sizeof(double) * nr, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipDeviceSynchronize());
+  qr_extract_r(ctx->stream, dA.p, lda, m, dR.p, ldr, inflate);
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipMemcpy(R, dR.p, sizeof(double) * nr, hipMemcpyDeviceToHost));
+  return AGP_OK;
+}
+
+// qr_root: R (ldr x m, read), T (ldt x m, the caller's filling; qr_root clears all of it and writes P R^T)
+AGP_DEBUG_API int agp_debug_qr_root(agp_context *ctx, const double *R, int64_t ldr, const int64_t *perm, int64_t m, double *T,
+                                    int64_t ldt) {
+  if (!ctx || !R || !perm || !T || m <= 0 || ldr < m || ldt < m || !qr_perm_valid(perm, m)) return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const size_t nr = (size_t)ldr * (size_t)m, nt = (size_t)ldt * (size_t)m;
+  DevBuf<double> dR, dT;
+  DevBuf<long long> dperm;
+  AGP_HIP_CHECK(ctx, dR.alloc(nr));
+  AGP_HIP_CHECK(ctx, dT.alloc(nt));
+  AGP_HIP_CHECK(ctx, dperm.alloc((size_t)m));
+  AGP_HIP_CHECK(ctx, hipMemcpy(dR.p, R, sizeof(double) * nr, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipMemcpy(dT.p, T, sizeof(double) * nt, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipMemcpy(dperm.p, perm, sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipDeviceSynchronize());
+  qr_root(ctx->stream, dR.p, ldr, dperm.p, m, dT.p, ldt);
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipMemcpy(T, dT.p, sizeof(double) * nt, hipMemcpyDeviceToHost));
+  return AGP_OK;
+}
+
+// qr_sqrt_solve: W = R^-T P^T X.  X (ldx x alloc_cols, read) and W (ldw x alloc_cols) are the caller's whole buffers; both
+// come back, so that the test sees X unchanged and W written in its m x nrhs part only.
+AGP_DEBUG_API int agp_debug_qr_sqrt_solve(agp_context *ctx, const double *R, int64_t ldr, const int64_t *perm, int64_t m, double *X,
+                                          int64_t ldx, double *W, int64_t ldw, int64_t nrhs, int64_t alloc_cols) {
+  if (!ctx || !R || !perm || !X || !W || m <= 0 || nrhs <= 0 || ldr < m || ldx < m || ldw < m || alloc_cols < nrhs ||
+      !qr_perm_valid(perm, m))
+    return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const size_t nr = (size_t)ldr * (size_t)m, nx = (size_t)ldx * (size_t)alloc_cols, nw = (size_t)ldw * (size_t)alloc_cols;
+  DevBuf<double> dR, dX, dW;
+  DevBuf<long long> dperm;
+  AGP_HIP_CHECK(ctx, dR.alloc(nr));
+  AGP_HIP_CHECK(ctx, dX.alloc(nx));
+  AGP_HIP_CHECK(ctx, dW.alloc(nw));
+  AGP_HIP_CHECK(ctx, dperm.alloc((size_t)m));
+  AGP_HIP_CHECK(ctx, hipMemcpy(dR.p, R, sizeof(double) * nr, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipMemcpy(dX.p, X, sizeof(double) * nx, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipMemcpy(dW.p, W, sizeof(double) * nw, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipMemcpy(dperm.p, perm, sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipDeviceSynchronize());
+  qr_sqrt_solve(ctx->stream, dR.p, ldr, dperm.p, m, dX.p, ldx, dW.p, ldw, nrhs);
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipMemcpy(X, dX.p, sizeof(double) * nx, hipMemcpyDeviceToHost));
+  AGP_HIP_CHECK(ctx, hipMemcpy(W, dW.p, sizeof(double) * nw, hipMemcpyDeviceToHost));
+  return AGP_OK;
+}
+
+// qr_back_solve: out = P [R11^-1 c[0 : np]; 0].  c and out are m + 2 doubles each, uploaded and downloaded whole: c comes
+// back with its first np entries solved in place, and the two trailing doubles of either show a store past the end.
+AGP_DEBUG_API int agp_debug_qr_back_solve(agp_context *ctx, const double *R, int64_t ldr, const int64_t *perm, int64_t m, int64_t np,
+                                          double *c, double *out) {
+  if (!ctx || !R || !perm || !c || !out || m <= 0 || np < 0 || np > m || ldr < m || !qr_perm_valid(perm, m))
+    return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const size_t nr = (size_t)ldr * (size_t)m, nv = (size_t)m + 2;
+  DevBuf<double> dR, dv;  // dv: c (m + 2), then out (m + 2)
+  DevBuf<long long> dperm;
+  AGP_HIP_CHECK(ctx, dR.alloc(nr));
+  AGP_HIP_CHECK(ctx, dv.alloc(2 * nv));
+  AGP_HIP_CHECK(ctx, dperm.alloc((size_t)m));
+  AGP_HIP_CHECK(ctx, hipMemcpy(dR.p, R, sizeof(double) * nr, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipMemcpy(dv.p, c, sizeof(double) * nv, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipMemcpy(dv.p + nv, out, sizeof(double) * nv, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipMemcpy(dperm.p, perm, sizeof(int64_t) * (size_t)m, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipDeviceSynchronize());
+  qr_back_solve(ctx->stream, dR.p, ldr, dperm.p, m, np, dv.p, dv.p + nv);
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipMemcpy(c, dv.p, sizeof(double) * nv, hipMemcpyDeviceToHost));
+  AGP_HIP_CHECK(ctx, hipMemcpy(out, dv.p + nv, sizeof(double) * nv, hipMemcpyDeviceToHost));
+  return AGP_OK;
+}
+
 AGP_DEBUG_API int agp_debug_comm_create_null(int nranks, int rank, agp_comm **out) {
   if (!out || nranks < 1 || rank < 0 || rank >= nranks) return AGP_ERR_INVALID_ARGUMENT;
   NullComm *c = new (std::nothrow) NullComm();
