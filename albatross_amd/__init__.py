@@ -15,7 +15,8 @@ from .gp import (AlbatrossAmdError, DeviceJointDistribution, BlockSymmetric, Exp
                  LinearMean, MeanFunction, SumOfMeanFunctions, ProductOfMeanFunctions, MarginalDistribution, NanInputError, NotPositiveDefiniteError, Prediction,
                  RegressionDataset, ZeroMean, default_context, fit_batch, predict_batch, update_batch, log_likelihood_gradient_batch,
                  leave_one_out_likelihood_gradient_batch, pooled_log_likelihood_gradient,
-                 pooled_leave_one_out_likelihood_gradient, gp_from_covariance, gp_from_covariance_and_mean)
+                 pooled_leave_one_out_likelihood_gradient, leave_one_group_out_likelihood_gradient_batch,
+                 pooled_leave_one_group_out_likelihood_gradient, gp_from_covariance, gp_from_covariance_and_mean)
 
 from .sparse_gp import (FixedInducingPoints, SparseCrossValidation, SparseCrossValidationPrediction, SparseFitModel, SparseGaussianProcessRegression, SparseGPFit,
                         UniformlySpacedInducingPoints, rebase_inducing_points, sparse_gp_from_covariance,

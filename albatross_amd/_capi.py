@@ -123,6 +123,8 @@ EXPORTS = [
                                                 C.c_int64, _P, C.c_int64, _P]),
     ("agp_loo_nll_gradient_batch_ragged", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int64, _P,
                                                     _P, C.c_int64, _P, C.c_int64, _P]),
+    ("agp_logo_nll_gradient_batch", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.c_int, _P, _P, _P,
+                                              C.c_int64, _P, _P, C.c_int64, _P, C.c_int64, _P, _P]),
     ("agp_nll_batch", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, _P, _P]),
     ("agp_fit_create_batch", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P, _P]),
     ("agp_fit_create_batch_ragged", C.c_int, [_P, C.c_int, _P, _P, _P, C.c_int64, _P, C.c_int64, _P, _P, C.c_int64, _P, _P]),
@@ -268,6 +270,9 @@ def load_debug():
         # the factorisation's schedule without a device (csrc/factor_plan.h)
         _debug_lib.agp_debug_factor_plan.restype = C.c_int
         _debug_lib.agp_debug_factor_plan.argtypes = [_P, C.c_int64, _P, C.c_int64]
+        # the pooled plan of agp_logo_nll_gradient_batch without a device (csrc/logo_batch_plan.h)
+        _debug_lib.agp_debug_logo_batch_plan.restype = C.c_int
+        _debug_lib.agp_debug_logo_batch_plan.argtypes = [C.c_int64, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, _P]
         _debug_lib.agp_debug_step_launch_shape.restype = C.c_int
         _debug_lib.agp_debug_step_launch_shape.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P]
         # the column-pivoted QR and the substitutions against its R on host arrays (csrc/qr.hip)

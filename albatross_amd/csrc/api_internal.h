@@ -189,9 +189,14 @@ long long logo_img_stride(long long m);
 // AGP_ERR_INVALID_ARGUMENT for malformed offsets, an index out of range, or an index that occurs twice (in one group or
 // in two); empty groups are dropped, points in no group are allowed
 int logo_plan(long long n, int64_t n_groups, const int64_t *offsets, const int64_t *indices, LogoPlan &p);
-// the halves of a chunk's value chain on either side of the sigma kernel, and the fixed-order sum of the terms
-void logo_chunk_sigma(agp_context_impl *ctx, const agp::LogoRegions &r, const LogoChunk &ch);
-void logo_chunk_terms(agp_context_impl *ctx, const agp::LogoRegions &r, const LogoChunk &ch, bool marginal);
+// the halves of a chunk's value chain on either side of the sigma kernel, and the fixed-order sum of the terms.
+// group_flags: 4 status words per group of the chunk (agp_logo_nll_gradient_batch, whose groups belong to different
+// problems); nullptr: the context's one status for all of them
+void logo_chunk_sigma(agp_context_impl *ctx, const agp::LogoRegions &r, const LogoChunk &ch, int *group_flags = nullptr);
+void logo_chunk_terms(agp_context_impl *ctx, const agp::LogoRegions &r, const LogoChunk &ch, bool marginal, int *group_flags = nullptr);
+// the limits of one chunk, shared with the pooled plan of agp_logo_nll_gradient_batch (logo_batch_plan.h)
+long long logo_chunk_groups_max();
+long long logo_chunk_img_elems_max();
 void launch_logo_sum(hipStream_t s, const double *term, long long count, double *out);
 namespace agp {
 // Gram + LL^T + forward substitution of y exactly as agp_nll makes them (api.hip: build_and_factor); on return the stream

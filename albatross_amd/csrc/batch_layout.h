@@ -59,6 +59,37 @@ inline LogoRegions carve_logo(WsLayout &ws, const BatchGeometry &g, bool gradien
           ws.take<double>(symv_elems),  ws.take<long long>(meta_elems)};
 }
 
+// agp_logo_nll_gradient_batch, the entry's own region behind its a and u arrays in the extra arrays of
+// carve_gradient_batch_aux.  chain.S: the third slab of EVERY problem (count lda x n slabs, C_b B_b C_b; gradient calls only;
+// first, so that the descriptors find it at a fixed place); chain.X0 .. term as carve_logo, for the chunk of the POOLED plan
+// in flight; chain.a, u, symv: not carved (a and u are np2 x count arrays of the caller, the batched symv needs no scratch);
+// chain.meta: the chunk tables and the per-problem term lists (logo_batch_plan.h); gflags: 4 status words per term, which
+// the block factorisations write and the per-problem sum folds into the problem's own.
+struct LogoBatchRegions {
+  LogoRegions chain;
+  int *gflags;
+};
+inline LogoBatchRegions carve_logo_batch(WsLayout &ws, const BatchGeometry &g, bool gradient, size_t block_elems, size_t img_elems,
+                                         size_t vec_elems, size_t count_elems, size_t term_elems, size_t meta_elems) {
+  LogoBatchRegions r;
+  LogoRegions &c = r.chain;
+  c.a = c.u = c.symv = nullptr;
+  c.S = gradient ? ws.take<double>(g.slabs()) : nullptr;
+  c.X0 = ws.take<double>(block_elems);
+  c.X1 = ws.take<double>(block_elems);
+  c.X2 = ws.take<double>(block_elems);
+  c.img = ws.take<double>(img_elems);
+  c.d = ws.take<double>(vec_elems);
+  c.z = ws.take<double>(vec_elems);
+  c.a_pad = ws.take<double>(vec_elems);
+  c.logs_A = ws.take<double>(count_elems);
+  c.logs_V = ws.take<double>(count_elems);
+  c.term = ws.take<double>(term_elems);
+  c.meta = ws.take<long long>(meta_elems);
+  r.gflags = ws.take<int>(4 * term_elems);
+  return r;
+}
+
 // agp_sparse_held_out, the entry's one allocation beyond what the fit and the inverse blocks hold.  chain: the regions
 // the value chain of a chunk works in (S, a, u, symv: not used, nullptr); M: the chunk's slabs of M_g + nugget I; aw,
 // alpha: n-vectors in the grouped order; y, yvar, mean, variance: the same, each only where an output needs it; joint:

@@ -12,6 +12,8 @@
 #include "pub.h"
 #include "trsm_kernel.h"
 #include "factor_plan.h"
+#include "logo_batch_plan.h"
+#include <vector>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -1271,6 +1273,36 @@ AGP_DEBUG_API int agp_debug_factor_plan(const int64_t *switches, int64_t n, int6
   }
   w[7] = plan.bs_done();
   std::copy(w, w + std::min(cap, PLAN_WORDS), out);
+  return AGP_OK;
+}
+
+// The pooled plan agp_logo_nll_gradient_batch WOULD run for `count` problems of n[b] rows with the given groups
+// (logo_batch_plan.h) - no context, no device.  cols_max <= 0: the entry's own bound, count * max n.  Returns
+// AGP_ERR_INVALID_ARGUMENT where the entry would.  *words receives the length of the record, of which at most `cap` words
+// are written to `out`:
+//   [0] terms T, [1] chunks K, [2] cols_max in force, [3] the group limit, [4] the image limit (doubles), [5] reserved
+//   K x 4: m, count, term_off, image doubles of one group       T x 3: problem, group (the caller's number), size
+//   per chunk count * m padded indices (-1 = padding)            count + 1 words csr_off, T words csr_terms
+AGP_DEBUG_API int agp_debug_logo_batch_plan(int64_t count, const int64_t *n, const int64_t *n_groups, const int64_t *const *offsets,
+                                            const int64_t *const *indices, int64_t cols_max, int64_t *out, int64_t cap, int64_t *words) {
+  if (count <= 0 || !n || !n_groups || !words || cap < 0 || (cap > 0 && !out)) return AGP_ERR_INVALID_ARGUMENT;
+  std::vector<long long> nb((size_t)count);
+  long long n_max = 0;
+  for (int64_t b = 0; b < count; ++b) {
+    nb[(size_t)b] = n[b];
+    n_max = std::max(n_max, nb[(size_t)b]);
+  }
+  if (cols_max <= 0) cols_max = count * n_max;
+  const agp::LogoBatchLimits lim{logo_chunk_groups_max(), logo_chunk_img_elems_max(), cols_max, factor_ld, logo_img_stride};
+  agp::LogoBatchPlan p;
+  if (!agp::logo_batch_plan(count, nb.data(), n_groups, offsets, indices, lim, p)) return AGP_ERR_INVALID_ARGUMENT;
+  std::vector<int64_t> w{p.terms, (int64_t)p.chunks.size(), cols_max, lim.groups_max, lim.img_elems_max, 0};
+  for (const agp::LogoBatchChunk &ch : p.chunks) w.insert(w.end(), {ch.m, ch.count, ch.term_off, logo_img_stride(ch.m)});
+  for (long long q = 0; q < p.terms; ++q) w.insert(w.end(), {p.problem[(size_t)q], p.group[(size_t)q], p.size[(size_t)q]});
+  for (const agp::LogoBatchChunk &ch : p.chunks) w.insert(w.end(), p.meta.begin() + ch.idx_off, p.meta.begin() + ch.idx_off + ch.count * ch.m);
+  w.insert(w.end(), p.meta.begin() + p.csr_at, p.meta.end());
+  *words = (int64_t)w.size();
+  std::copy(w.begin(), w.begin() + std::min<int64_t>(cap, (int64_t)w.size()), out);
   return AGP_OK;
 }
 

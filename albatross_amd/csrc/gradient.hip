@@ -46,6 +46,9 @@
 // fits share (batch_front.h); every workspace here is carved by a layout of batch_layout.h.
 // agp_nll_gradient_batch_ragged and agp_loo_nll_gradient_batch_ragged are the same two bodies for problems of UNEQUAL sizes:
 // problem b is diag(K_b, I) at the padded size of the call (ragged_batch.hip; gradient_batch_begin says what changes).
+// agp_logo_nll_gradient_batch is agp_logo_nll_gradient_typed for problems of any mix of sizes on that front end: the group
+// blocks of ALL problems go through ONE chain per size class of groups (the pooled plan of logo_batch_plan.h; the kernels
+// around the chain take every group's problem from a table, LogoProblems).
 #include <algorithm>
 #include <climits>
 #include <cstring>
@@ -58,6 +61,7 @@
 #include "contract.h"
 #include "cov_eval.h"
 #include "gemm_tiles.h"
+#include "logo_batch_plan.h"
 #include "pub.h"
 
 namespace agp {
@@ -363,13 +367,34 @@ __global__ __launch_bounds__(256) void mirror_lower_kernel(double *__restrict__ 
   }
 }
 
+// The problems of a POOLED chunk (agp_logo_nll_gradient_batch: the groups of all problems of a batch in one chain).  Group g
+// of the chunk belongs to problem prob[g]: its indices are row numbers of that problem, whose slabs (C, H) start stride_M
+// and whose vectors (alpha, y_var, a) stride_v doubles behind those of problem 0.  flags: the problems' status words (4
+// each: NaN input, failed pivot, ...) as the front end left them.  The plan is built before any status is known, so the
+// groups of a FAILED problem run with the rest: the gather hands the chain an identity block in place of whatever the
+// failed factor left in C_b and the sigma kernels take zeros for its alpha and variances, so nothing NaN enters the block
+// chain and every launch keeps its trip counts; the problem's results are discarded at the end.
+// prob == nullptr: one problem (the single-problem entries), nothing is offset and no status is read.
+struct LogoProblems {
+  const long long *prob = nullptr;
+  long long stride_M = 0, stride_v = 0;
+  const int *flags = nullptr;
+};
+__device__ __forceinline__ long long logo_problem(const LogoProblems &P, long long g) { return P.prob ? P.prob[g] : 0; }
+__device__ __forceinline__ bool logo_problem_failed(const LogoProblems &P, long long b) {
+  return P.prob && P.flags && (P.flags[4 * b] != 0 || P.flags[4 * b + 1] != 0);
+}
+
 // X0_g = [C[I_g, I_g] 0; 0 I] from the full symmetric C: column blockIdx.x of group blockIdx.y
 __global__ __launch_bounds__(256) void logo_gather_blocks_kernel(const double *__restrict__ C, long long ldc,
                                                                  const long long *__restrict__ idx, long long m,
-                                                                 double *__restrict__ X0, long long ldb, long long stride) {
+                                                                 double *__restrict__ X0, long long ldb, long long stride,
+                                                                 LogoProblems P) {
   const long long c = blockIdx.x, g = blockIdx.y;
+  const long long b = logo_problem(P, g);
+  C += b * P.stride_M;
   const long long *ig = idx + g * m;
-  const long long ic = ig[c];
+  const long long ic = logo_problem_failed(P, b) ? -1 : ig[c];
   double *out = X0 + g * stride + c * ldb;
   for (long long r = threadIdx.x; r < m; r += 256) {
     const long long ir = ig[r];
@@ -404,9 +429,12 @@ __global__ __launch_bounds__(256) void logo_sigma_kernel(const double *__restric
                                                          long long m, long long ldb, long long stride,
                                                          const double *__restrict__ alpha, const double *__restrict__ yvar,
                                                          double *__restrict__ X0, double *__restrict__ X1,
-                                                         double *__restrict__ d, double *__restrict__ z) {
+                                                         double *__restrict__ d, double *__restrict__ z, LogoProblems P) {
   __shared__ double red[4];
   const long long c = blockIdx.x, g = blockIdx.y;
+  const long long b = logo_problem(P, g);
+  if (logo_problem_failed(P, b)) { alpha = nullptr; yvar = nullptr; }
+  else { alpha += b * P.stride_v; if (yvar) yvar += b * P.stride_v; }
   const long long *ig = idx + g * m;
   const long long off = g * stride + c * ldb, ic = ig[c];
   const double sc = (yvar && ic >= 0) ? yvar[ic] : 0.;
@@ -414,7 +442,7 @@ __global__ __launch_bounds__(256) void logo_sigma_kernel(const double *__restric
   for (long long r = threadIdx.x; r < m; r += 256) {
     const double sg = -X2[off + r];
     const long long ir = ig[r];
-    acc += sg * (ir >= 0 ? alpha[ir] : 0.);
+    acc += sg * ((ir >= 0 && alpha) ? alpha[ir] : 0.);
     X0[off + r] = r == c ? sg + sc : sg;
     if (X1) X1[off + r] = sg;
   }
@@ -440,8 +468,9 @@ __global__ __launch_bounds__(256) void logo_term_kernel(const double *__restrict
 __global__ __launch_bounds__(256) void logo_assemble_kernel(const long long *__restrict__ idx, long long m, long long ldb,
                                                             long long stride, const double *__restrict__ a_pad,
                                                             const double *__restrict__ d, double *__restrict__ X2,
-                                                            double *__restrict__ a) {
+                                                            double *__restrict__ a, LogoProblems P) {
   const long long c = blockIdx.x, g = blockIdx.y;
+  a += logo_problem(P, g) * P.stride_v;
   const long long *ig = idx + g * m;
   const long long ic = ig[c];
   const double ac = a_pad[g * m + c], dc = d[g * m + c];
@@ -462,15 +491,18 @@ __global__ __launch_bounds__(256) void logo_marginal_sigma_kernel(const double *
                                                                   const double *__restrict__ alpha, const double *__restrict__ yvar,
                                                                   double *__restrict__ X0, double *__restrict__ X1,
                                                                   double *__restrict__ d, double *__restrict__ q,
-                                                                  double *__restrict__ t) {
+                                                                  double *__restrict__ t, LogoProblems P) {
   __shared__ double red[4];
   const long long c = blockIdx.x, g = blockIdx.y;
+  const long long b = logo_problem(P, g);
+  if (logo_problem_failed(P, b)) { alpha = nullptr; yvar = nullptr; }
+  else { alpha += b * P.stride_v; if (yvar) yvar += b * P.stride_v; }
   const long long *ig = idx + g * m;
   const long long off = g * stride + c * ldb, ic = ig[c];
   double acc = 0.;
   for (long long r = threadIdx.x; r < m; r += 256) {
     const long long ir = ig[r];
-    acc += -X2[off + r] * (ir >= 0 ? alpha[ir] : 0.);
+    acc += -X2[off + r] * ((ir >= 0 && alpha) ? alpha[ir] : 0.);
   }
   const double dc = logo_block_sum(acc, red);
   const double vc = -X2[off + c] + ((yvar && ic >= 0) ? yvar[ic] : 0.);
@@ -506,8 +538,9 @@ __global__ __launch_bounds__(256) void logo_marginal_term_kernel(const double *_
 __global__ __launch_bounds__(256) void logo_marginal_assemble_kernel(const long long *__restrict__ idx, long long m, long long ldb,
                                                                      long long stride, const double *__restrict__ a_pad,
                                                                      const double *__restrict__ d, double *__restrict__ X2,
-                                                                     double *__restrict__ a) {
+                                                                     double *__restrict__ a, LogoProblems P) {
   const long long c = blockIdx.x, g = blockIdx.y;
+  a += logo_problem(P, g) * P.stride_v;
   const long long *ig = idx + g * m;
   const long long ic = ig[c];
   const double ac = a_pad[g * m + c], dc = d[g * m + c];
@@ -526,9 +559,12 @@ constexpr int LOGO_HR = 8;
 __global__ __launch_bounds__(256) void logo_h_kernel(const double *__restrict__ C, long long ldc, long long n,
                                                      const long long *__restrict__ idx, const long long *__restrict__ sizes,
                                                      long long m, const double *__restrict__ X2, long long ldb, long long stride,
-                                                     double *__restrict__ H, long long ldh) {
+                                                     double *__restrict__ H, long long ldh, LogoProblems P) {
   const long long g = blockIdx.z, r0 = (long long)blockIdx.y * LOGO_HR, sz = sizes[g];
   if (r0 >= sz) return;  // (the whole workgroup)
+  const long long pb = logo_problem(P, g);
+  C += pb * P.stride_M;
+  H += pb * P.stride_M;
   const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
   const long long *ig = idx + g * m;
   const double *B = X2 + g * stride;
@@ -559,6 +595,39 @@ __global__ __launch_bounds__(1024) void logo_sum_kernel(const double *__restrict
     double s = 0.;
     for (int w = 0; w < 16; ++w) s += red[w];
     *out = 0.5 * s;
+  }
+}
+
+// agp_logo_nll_gradient_batch: the terms lie in the pooled order of the plan (by size, across problems).  Workgroup b walks
+// problem b's own terms - list[off[b] .. off[b + 1]), ascending term indices, built on the host - in a fixed order:
+// out[b] = 1/2 sum of them (0 for a problem without a non-empty group), and a group block that did not factor
+// (gflags[4 q + 1], written by the block factorisations) becomes the problem's failed pivot in flags[4 b + 1].
+// The front end reports NaN in the features and variances only (the Gram sees them); a NaN TARGET reaches alpha_b and from
+// there this problem's own terms and columns, nobody else's: the n_b real values of alpha_b (D[b].X.n of them, at
+// alpha + b * stride_v) are looked through here, and a NaN among them of a problem that did factor becomes flags[4 b].
+__global__ __launch_bounds__(256) void logo_problem_sum_kernel(const double *__restrict__ term, const int *__restrict__ gflags,
+                                                               const long long *__restrict__ off, const long long *__restrict__ list,
+                                                               const double *__restrict__ alpha, long long stride_v,
+                                                               const ContractDesc *__restrict__ D, double *__restrict__ out,
+                                                               int *__restrict__ flags) {
+  __shared__ double red[4];
+  const long long b = blockIdx.x;
+  int nan_alpha = 0;
+  for (long long i = threadIdx.x; i < D[b].X.n; i += 256) nan_alpha |= isnan(alpha[b * stride_v + i]);
+  nan_alpha = __syncthreads_or(nan_alpha);
+  double acc = 0.;
+  int bad = 0;
+  for (long long i = off[b] + threadIdx.x; i < off[b + 1]; i += 256) {
+    const long long q = list[i];
+    acc += term[q];
+    bad |= gflags[4 * q + 1] != 0 || gflags[4 * q] != 0;
+  }
+  const double sum = logo_block_sum(acc, red);
+  const int any_bad = __syncthreads_or(bad);
+  if (threadIdx.x == 0) {
+    out[b] = 0.5 * sum;
+    if (nan_alpha && flags[4 * b] == 0 && flags[4 * b + 1] == 0) flags[4 * b] = 1;
+    if (any_bad && flags[4 * b + 1] == 0) flags[4 * b + 1] = 1;
   }
 }
 
@@ -730,6 +799,8 @@ static void contract_slots(hipStream_t s, const agp_kernel *k, int n_slots, cons
 constexpr long long LOGO_CHUNK_GROUPS_MAX = 16384;
 constexpr long long LOGO_CHUNK_IMG_ELEMS_MAX = 32ll << 20;  // 256 MiB of tile images per chunk
 long long logo_img_stride(long long m) { return (m + NB - 1) / NB * (36ll * MB * MB); }
+long long logo_chunk_groups_max() { return LOGO_CHUNK_GROUPS_MAX; }
+long long logo_chunk_img_elems_max() { return LOGO_CHUNK_IMG_ELEMS_MAX; }
 
 int logo_plan(long long n, int64_t n_groups, const int64_t *offsets, const int64_t *indices, LogoPlan &p) {
   if (n_groups < 0 || (n_groups > 0 && (!offsets || offsets[0] != 0))) return AGP_ERR_INVALID_ARGUMENT;
@@ -788,21 +859,22 @@ int logo_plan(long long n, int64_t n_groups, const int64_t *offsets, const int64
 // X2 = -Sigma_g = -X1^T X1.  The caller's sigma kernel then puts V_g into X0 and d into d / z (Joint), or the columns'
 // shares of 2 NLL_g into a_pad (Marginal).  logo_chunk_terms: Joint V_g = L_V L_V^T with z = L_V^-1 d riding along, then
 // term[g] = 2 NLL_g; Marginal: the sum of the shares.
-void logo_chunk_sigma(agp_context_impl *ctx, const LogoRegions &r, const LogoChunk &ch) {
+void logo_chunk_sigma(agp_context_impl *ctx, const LogoRegions &r, const LogoChunk &ch, int *group_flags) {
   hipStream_t s = ctx->stream;
   const long long m = ch.m, count = ch.count;
   const long long ldb = factor_ld(m), stride_B = ldb * m, stride_I = logo_img_stride(m);
   const size_t slab_bytes = sizeof(double) * (size_t)stride_B * (size_t)count;
   (void)hipMemsetAsync(r.logs_A, 0, sizeof(double) * (size_t)round_up(count, 2), s);
   (void)hipMemsetAsync(r.logs_V, 0, sizeof(double) * (size_t)round_up(count, 2), s);
-  factor_lower_batched(s, r.X0, stride_B, m, ldb, r.img, stride_I, nullptr, 0, count, ctx->d_flags, r.logs_A);
+  factor_lower_batched(s, r.X0, stride_B, m, ldb, r.img, stride_I, nullptr, 0, count, group_flags ? group_flags : ctx->d_flags, r.logs_A,
+                       group_flags ? 4 : 0);
   launch_set_identity_batched(s, r.X1, ldb, stride_B, m, count);
   forward_solve_mat_batched(s, r.X0, stride_B, m, ldb, r.img, stride_I, r.X1, stride_B, m, ldb, /*rhs_lower=*/true, count);
   (void)hipMemsetAsync(r.X2, 0, slab_bytes, s);
   launch_gemm_nt_sub_batched(s, r.X2, ldb, stride_B, r.X1, ldb, true, stride_B, r.X1, ldb, true, stride_B, m, m, m, false, count);  // -Sigma
 }
 
-void logo_chunk_terms(agp_context_impl *ctx, const LogoRegions &r, const LogoChunk &ch, bool marginal) {
+void logo_chunk_terms(agp_context_impl *ctx, const LogoRegions &r, const LogoChunk &ch, bool marginal, int *group_flags) {
   hipStream_t s = ctx->stream;
   const long long m = ch.m, count = ch.count;
   const long long ldb = factor_ld(m), stride_B = ldb * m, stride_I = logo_img_stride(m);
@@ -810,7 +882,8 @@ void logo_chunk_terms(agp_context_impl *ctx, const LogoRegions &r, const LogoChu
   if (marginal) {
     hipLaunchKernelGGL(logo_marginal_term_kernel, dim3((unsigned)count), dim3(256), 0, s, r.a_pad, m, sizes, r.term + ch.term_off);
   } else {
-    factor_lower_batched(s, r.X0, stride_B, m, ldb, r.img, stride_I, r.z, m, count, ctx->d_flags, r.logs_V);
+    factor_lower_batched(s, r.X0, stride_B, m, ldb, r.img, stride_I, r.z, m, count, group_flags ? group_flags : ctx->d_flags, r.logs_V,
+                         group_flags ? 4 : 0);
     hipLaunchKernelGGL(logo_term_kernel, dim3((unsigned)count), dim3(256), 0, s, r.z, m, r.logs_V, sizes, r.term + ch.term_off);
   }
 }
@@ -827,47 +900,64 @@ void launch_logo_sum(hipStream_t s, const double *term, long long count, double 
 // marginal (AGP_PREDICT_MARGINAL): the same up to -Sigma_g in X2; then d, q = d / v and the terms per column (the shares of
 // 2 NLL_g wait in a_pad until the term kernel has summed them), and for the gradient Sigma into X0, Sigma diag(w) into X1,
 // a_I = Sigma q, -(Sigma diag(w)) Sigma^T as a product of two different operands, B_g, H.  No second LL^T, no T.
+// The pooled chunks of agp_logo_nll_gradient_batch run the same chain through logo_chunk_run with P naming every group's
+// problem: the blocks always come from C_b there (from_c), need_c means "the gradient's half of the chain", group_flags are
+// its per-group status words.
+struct LogoChainArgs {
+  long long n, lda;
+  double *C, *H, *a;
+  const double *R, *alpha, *yvar;
+};
+static void logo_chunk_run(agp_context_impl *ctx, const LogoChainArgs &g, const LogoRegions &r, const LogoChunk &ch, bool from_c,
+                           bool need_c, bool need_h, bool marginal, const LogoProblems &P, int *group_flags);
+
 static void logo_chunk(agp_context_impl *ctx, const GradientCall &g, const LogoRegions &r, const LogoChunk &ch, bool need_c,
                        bool need_h, bool marginal) {
+  const LogoChainArgs a{g.n, g.lda, g.A, g.R, r.a, g.R, g.z, g.yvar_d};
+  logo_chunk_run(ctx, a, r, ch, need_c, need_c, need_h, marginal, LogoProblems{}, nullptr);
+}
+
+static void logo_chunk_run(agp_context_impl *ctx, const LogoChainArgs &g, const LogoRegions &r, const LogoChunk &ch, bool from_c,
+                           bool need_c, bool need_h, bool marginal, const LogoProblems &P, int *group_flags) {
   hipStream_t s = ctx->stream;
   const long long m = ch.m, count = ch.count, n = g.n;
   const long long ldb = factor_ld(m), stride_B = ldb * m, stride_I = logo_img_stride(m);
   const long long *idx = r.meta + ch.idx_off, *sizes = r.meta + ch.size_off;
   const size_t slab_bytes = sizeof(double) * (size_t)stride_B * (size_t)count;
   const dim3 cols((unsigned)m, (unsigned)count);
-  if (need_c) {
-    hipLaunchKernelGGL(logo_gather_blocks_kernel, cols, dim3(256), 0, s, g.A, g.lda, idx, m, r.X0, ldb, stride_B);
+  if (from_c) {
+    hipLaunchKernelGGL(logo_gather_blocks_kernel, cols, dim3(256), 0, s, g.C, g.lda, idx, m, r.X0, ldb, stride_B, P);
   } else {
     for (long long c0 = 0; c0 < count * m; c0 += 32768)  // (grid limit of the gather: 65535 columns per launch)
-      launch_gather_cols(s, g.R, g.lda, idx + c0, count * m - c0 < 32768 ? count * m - c0 : 32768, 0, n, g.A + c0 * g.lda, g.lda);
+      launch_gather_cols(s, g.R, g.lda, idx + c0, count * m - c0 < 32768 ? count * m - c0 : 32768, 0, n, g.C + c0 * g.lda, g.lda);
     (void)hipMemsetAsync(r.X0, 0, slab_bytes, s);
-    launch_gemm_nt_sub_batched(s, r.X0, ldb, stride_B, g.A, g.lda, true, m * g.lda, g.A, g.lda, true, m * g.lda, m, m, n, false, count);
+    launch_gemm_nt_sub_batched(s, r.X0, ldb, stride_B, g.C, g.lda, true, m * g.lda, g.C, g.lda, true, m * g.lda, m, m, n, false, count);
     hipLaunchKernelGGL(logo_fix_blocks_kernel, cols, dim3(256), 0, s, idx, m, r.X0, ldb, stride_B);
   }
-  logo_chunk_sigma(ctx, r, ch);
+  logo_chunk_sigma(ctx, r, ch, group_flags);
   if (marginal) {
-    hipLaunchKernelGGL(logo_marginal_sigma_kernel, cols, dim3(256), 0, s, r.X2, idx, m, ldb, stride_B, g.z, g.yvar_d,
-                       need_c ? r.X0 : nullptr, need_c ? r.X1 : nullptr, r.d, r.z, r.a_pad);
-    logo_chunk_terms(ctx, r, ch, true);
+    hipLaunchKernelGGL(logo_marginal_sigma_kernel, cols, dim3(256), 0, s, r.X2, idx, m, ldb, stride_B, g.alpha, g.yvar,
+                       need_c ? r.X0 : nullptr, need_c ? r.X1 : nullptr, r.d, r.z, r.a_pad, P);
+    logo_chunk_terms(ctx, r, ch, true, group_flags);
     if (!need_c) return;
     launch_colvec_dot_batched(s, r.X0, ldb, stride_B, m, r.z, m, count, r.a_pad);  // a_I = Sigma q (Sigma symmetric)
     (void)hipMemsetAsync(r.X2, 0, slab_bytes, s);
     launch_gemm_nt_sub_batched(s, r.X2, ldb, stride_B, r.X1, ldb, false, stride_B, r.X0, ldb, false, stride_B, m, m, m, false, count);
-    hipLaunchKernelGGL(logo_marginal_assemble_kernel, cols, dim3(256), 0, s, idx, m, ldb, stride_B, r.a_pad, r.d, r.X2, r.a);
+    hipLaunchKernelGGL(logo_marginal_assemble_kernel, cols, dim3(256), 0, s, idx, m, ldb, stride_B, r.a_pad, r.d, r.X2, g.a, P);
   } else {
-    hipLaunchKernelGGL(logo_sigma_kernel, cols, dim3(256), 0, s, r.X2, idx, m, ldb, stride_B, g.z, g.yvar_d, r.X0, need_c ? r.X1 : nullptr,
-                       r.d, r.z);
-    logo_chunk_terms(ctx, r, ch, false);
+    hipLaunchKernelGGL(logo_sigma_kernel, cols, dim3(256), 0, s, r.X2, idx, m, ldb, stride_B, g.alpha, g.yvar, r.X0, need_c ? r.X1 : nullptr,
+                       r.d, r.z, P);
+    logo_chunk_terms(ctx, r, ch, false, group_flags);
     if (!need_c) return;
     forward_solve_mat_batched(s, r.X0, stride_B, m, ldb, r.img, stride_I, r.X1, stride_B, m, ldb, /*rhs_lower=*/false, count);  // T
     launch_colvec_dot_batched(s, r.X1, ldb, stride_B, m, r.z, m, count, r.a_pad);
     (void)hipMemsetAsync(r.X2, 0, slab_bytes, s);
     launch_gemm_nt_sub_batched(s, r.X2, ldb, stride_B, r.X1, ldb, true, stride_B, r.X1, ldb, true, stride_B, m, m, m, false, count);  // -T^T T
-    hipLaunchKernelGGL(logo_assemble_kernel, cols, dim3(256), 0, s, idx, m, ldb, stride_B, r.a_pad, r.d, r.X2, r.a);
+    hipLaunchKernelGGL(logo_assemble_kernel, cols, dim3(256), 0, s, idx, m, ldb, stride_B, r.a_pad, r.d, r.X2, g.a, P);
   }
   if (need_h)
     hipLaunchKernelGGL(logo_h_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)((m + LOGO_HR - 1) / LOGO_HR), (unsigned)count), dim3(256),
-                       0, s, g.A, g.lda, n, idx, sizes, m, r.X2, ldb, stride_B, g.R, g.lda);
+                       0, s, g.C, g.lda, n, idx, sizes, m, r.X2, ldb, stride_B, g.H, g.lda, P);
 }
 
 static float elapsed(hipEvent_t a, hipEvent_t b) {
@@ -1093,6 +1183,7 @@ struct GradientBatch {
   double *A = nullptr, *z = nullptr, *yvar_d = nullptr;
   double *logsum = nullptr;  // [logsum | quad | flags]: what gradient_batch_finish downloads
   double *quad = nullptr;    // one scalar per problem: z_b^T z_b (NLL) or the leave-one-out sum
+  int *flags = nullptr;      // 4 status words per problem
   double *R = nullptr, *grad_d = nullptr, *extra = nullptr;
   ContractDesc *desc_d = nullptr;
   const ContractDesc *rows_d = nullptr;  // desc_d when some problem has phantom rows (loo_terms_kernel: rows), else null
@@ -1107,7 +1198,8 @@ struct GradientBatch {
 // 3), then with `rtr` K_b^-1 = R_b^T R_b over L_b (stage event 4).
 // vec / ldvec: the entry's n x count host output, checked only.  quad: z_b^T z_b before alpha overwrites z.
 // extra_vectors: further np2 x count arrays behind the descriptors, laid out like z (GradientBatch::vector(k): array k,
-// problem b's vector at + b * np2); u_vector >= 0: the array that holds every problem's u, for the descriptors.
+// problem b's vector at + b * np2); u_vector >= 0: the array that holds every problem's u, for the descriptors;
+// weight_vector >= 0: the contraction's weight slabs (ld lda, stride_A apart) start at that array instead of at A.
 //
 // `ragged` (the _ragged entries) admits problems of unequal sizes n_b, as fit_create_batch does (api.hip).  The padded size
 // n of the call is the largest of them and problem b is diag(K_b, I): column b of the targets, the variances and the
@@ -1123,7 +1215,7 @@ static int gradient_batch_begin(agp_context_impl *ctx, int count, const agp_kern
                                 int64_t ldv, const int *n_slots, const agp_gradient_slot *const *slots,
                                 const double *const *tangents, int64_t ldt, const double *grad, int64_t ldg, const double *vec,
                                 int64_t ldvec, bool quad, bool rtr, int extra_vectors, int u_vector, bool ragged,
-                                GradientBatch &g) {
+                                int weight_vector, GradientBatch &g) {
   long long n = 0;
   bool equal = true;
   int st = ragged ? check_batch_problems_ragged(count, kernels, features, ldy, y_var, ldv, &n, &equal)
@@ -1180,7 +1272,7 @@ static int gradient_batch_begin(agp_context_impl *ctx, int count, const agp_kern
   ContractDesc *desc_d = static_cast<ContractDesc *>(a.desc);
   g.count = count; g.n = n; g.lda = lda; g.np2 = np2; g.cp2 = cp2; g.stride_A = stride_A; g.tiles = tiles; g.ldgd = ldgd;
   g.groups = groups; g.max_slots = max_slots; g.dim_max = dim_max;
-  g.A = A; g.z = z; g.yvar_d = r.yvar; g.logsum = r.logsum; g.quad = r.quad; g.R = R; g.grad_d = a.grad; g.desc_d = desc_d;
+  g.A = A; g.z = z; g.yvar_d = r.yvar; g.logsum = r.logsum; g.quad = r.quad; g.flags = r.flags; g.R = R; g.grad_d = a.grad; g.desc_d = desc_d;
   g.extra = a.extra;
   g.rows_d = padded ? desc_d : nullptr;
   g.nb.resize((size_t)count);
@@ -1242,7 +1334,7 @@ static int gradient_batch_begin(agp_context_impl *ctx, int count, const agp_kern
     std::memset(static_cast<void *>(&d), 0, sizeof(ContractDesc));
     d.prog = kernels[b]->prog;
     d.X = gram.views[(size_t)b];
-    d.C = A + (size_t)b * (size_t)stride_A;
+    d.C = (weight_vector >= 0 ? g.vector(weight_vector) : A) + (size_t)b * (size_t)stride_A;
     d.ldc = lda;
     d.alpha = z + (size_t)b * (size_t)np2;
     d.u = u_vector >= 0 ? g.vector(u_vector) + (size_t)b * (size_t)np2 : nullptr;
@@ -1344,7 +1436,7 @@ static int nll_gradient_batch(agp_context *c, int count, const agp_kernel *const
   agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
   GradientBatch g;
   int st = gradient_batch_begin(ctx, count, kernels, features, y, ldy, y_var, ldv, n_slots, slots, tangents, ldt, grad_nll, ldg,
-                                information, ldi, /*quad=*/true, /*rtr=*/true, 0, -1, ragged, g);
+                                information, ldi, /*quad=*/true, /*rtr=*/true, 0, -1, ragged, -1, g);
   if (st != AGP_OK) return st;
   hipStream_t s = ctx->stream;
   const bool prof = ctx->profiling;
@@ -1396,7 +1488,7 @@ static int loo_nll_gradient_batch(agp_context *c, int count, const agp_kernel *c
   enum { TERM, A_VEC, SQRT_B, U_VEC, C_DIAG, N_VECTORS };  // the extra np2 x count arrays
   GradientBatch g;
   int st = gradient_batch_begin(ctx, count, kernels, features, y, ldy, y_var, ldv, n_slots, slots, tangents, ldt, grad_loo_nll, ldg,
-                                mean_weights, ldw, /*quad=*/false, /*rtr=*/need_c, N_VECTORS, U_VEC, ragged, g);
+                                mean_weights, ldw, /*quad=*/false, /*rtr=*/need_c, N_VECTORS, U_VEC, ragged, -1, g);
   if (st != AGP_OK) return st;
   hipStream_t s = ctx->stream;
   const bool prof = ctx->profiling;
@@ -1448,6 +1540,135 @@ static int loo_nll_gradient_batch(agp_context *c, int count, const agp_kernel *c
         ctx->stage_ms[9] = elapsed(ctx->stage_ev[5], ctx->stage_ev[6]);
         ctx->stage_ms[7] = elapsed(ctx->stage_ev[6], ctx->stage_ev[7]);
       }
+    }
+  }
+  return AGP_OK;
+}
+
+// ---- agp_logo_nll_gradient for `count` problems in lock step ---------------------------------------------------------
+// gradient_batch_begin as for the leave-one-out batch (alpha_b, R_b, C_b = R_b^T R_b over L_b; `ragged`, so problem b is
+// diag(K_b, I) at the padded size), C_b mirrored (ONE launch, blockIdx.z = problem), then the group-block chain ONCE for the
+// groups of ALL problems: the pooled plan (logo_batch_plan.h) sorts them by (size, problem, group) and cuts them into
+// chunks, each chunk is the chain of logo_chunk_run with every group's problem in its table (LogoProblems), so the number
+// of chains follows the size classes of the batch.  The blocks ALWAYS come from C_b, value-only calls included (no
+// gathered columns of R: at these sizes R^T R is a small share and one route is one chain to get right); a value-only
+// call forms no a, H or S.  Phantom rows belong to no group (the plan refuses an index >= n_b), so they appear in no block,
+// a_b and the columns of H_b are zero there, and the descriptors mask the phantom pairs of the contraction.
+// Then ONE launch sums every problem's terms in a fixed order and folds its groups' status words into its own
+// (logo_problem_sum_kernel), u_b = C_b a_b (launch_symv_lower_batched), S_b = H_b C_b^T into a third slab per problem
+// (launch_hct_lower_batched), and the contraction of S_b - sym(u_b alpha_b^T) with the descriptors pointing at S_b.
+// Every stage is a plain launch on the context's stream; nothing waits on the host between the uploads and the download.
+// Workspace (carve_logo_batch, behind the arrays a and u): the third slab per problem (gradient calls), three block slabs
+// and the tile images of the chunk in flight (at most count * n padded columns), O(terms) vectors and the tables.
+extern "C" int agp_logo_nll_gradient_batch(agp_context *c, int count, const agp_kernel *const *kernels,
+                                           const agp_features *const *features, const double *y, int64_t ldy, const double *y_var,
+                                           int64_t ldv, const int64_t *n_groups, const int64_t *const *offsets,
+                                           const int64_t *const *indices, int predict_type, const int *n_slots,
+                                           const agp_gradient_slot *const *slots, const double *const *tangents, int64_t ldt,
+                                           double *logo_nll, double *grad_logo_nll, int64_t ldg, double *mean_weights, int64_t ldw,
+                                           double *const *group_nll, int *status) {
+  if (!c || count <= 0 || count > BATCH_MAX_PROBLEMS || !kernels || !features || !y || !n_groups || !n_slots || !logo_nll || !status)
+    return AGP_ERR_INVALID_ARGUMENT;
+  if (predict_type != AGP_PREDICT_JOINT && predict_type != AGP_PREDICT_MARGINAL) return AGP_ERR_INVALID_ARGUMENT;
+  const bool marginal = predict_type == AGP_PREDICT_MARGINAL;
+  agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
+  bool need_h = false;  // some problem has a slot: H and S
+  std::vector<long long> nb((size_t)count);
+  long long n_max = 0;
+  for (int b = 0; b < count; ++b) {
+    if (!features[b] || features[b]->n <= 0) return AGP_ERR_INVALID_ARGUMENT;
+    nb[(size_t)b] = features[b]->n;
+    n_max = std::max(n_max, nb[(size_t)b]);
+    need_h = need_h || n_slots[b] > 0;
+  }
+  const bool need_grad = need_h || mean_weights;  // the gradient's half of the chain: a, u (and B_g)
+  LogoBatchPlan plan;
+  const LogoBatchLimits lim{logo_chunk_groups_max(), logo_chunk_img_elems_max(), (long long)count * n_max, factor_ld, logo_img_stride};
+  if (!logo_batch_plan(count, nb.data(), n_groups, offsets, indices, lim, plan)) return AGP_ERR_INVALID_ARGUMENT;
+
+  const BatchGeometry geo = batch_geometry(n_max, count);
+  const size_t term_elems = (size_t)round_up(plan.terms > 0 ? plan.terms : 1, 2);
+  auto carve = [&](WsLayout &w) {
+    return carve_logo_batch(w, geo, need_h, plan.block_elems, plan.img_elems, plan.vec_elems, plan.count_elems, term_elems, plan.meta.size());
+  };
+  WsLayout size_own;
+  carve(size_own);
+  enum { A_VEC, U_VEC, OWN };  // the extra np2 x count arrays: a, u, then the entry's own region (S first)
+  const size_t per_vector = sizeof(double) * geo.vectors();
+  const int extra_vectors = OWN + (int)((size_own.bytes() + per_vector - 1) / per_vector);
+  GradientBatch g;
+  int st = gradient_batch_begin(ctx, count, kernels, features, y, ldy, y_var, ldv, n_slots, slots, tangents, ldt, grad_logo_nll, ldg,
+                                mean_weights, ldw, /*quad=*/false, /*rtr=*/true, extra_vectors, U_VEC, /*ragged=*/true,
+                                need_h ? OWN : -1, g);
+  if (st != AGP_OK) return st;
+  hipStream_t s = ctx->stream;
+  // The plan's tables go up and the terms come down without a synchronisation of their own: both host vectors outlive the
+  // call's one synchronisation (gradient_batch_finish), and on an early return this drains the stream before they go.
+  std::vector<double> h_term;
+  struct Drain {
+    hipStream_t s;
+    ~Drain() { (void)hipStreamSynchronize(s); }
+  } drain{s};
+  const bool prof = ctx->profiling;
+  const long long n = g.n, np2 = g.np2;
+  WsLayout own(g.vector(OWN));
+  const LogoBatchRegions rb = carve(own);
+  const LogoRegions &r = rb.chain;
+  double *a = g.vector(A_VEC), *u = g.vector(U_VEC);
+  int *flags = g.flags;
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(r.meta, plan.meta.data(), sizeof(long long) * plan.meta.size(), hipMemcpyHostToDevice, s));
+  AGP_HIP_CHECK(ctx, hipMemsetAsync(rb.gflags, 0, sizeof(int) * 4 * term_elems, s));
+  const unsigned mt = (unsigned)((n + GF_T - 1) / GF_T);
+  hipLaunchKernelGGL(mirror_lower_kernel, dim3(mt, mt, (unsigned)count), dim3(256), 0, s, g.A, g.lda, n, g.stride_A);
+  if (need_grad) AGP_HIP_CHECK(ctx, hipMemsetAsync(a, 0, sizeof(double) * geo.vectors(), s));
+  if (need_h) AGP_HIP_CHECK(ctx, hipMemsetAsync(g.R, 0, sizeof(double) * geo.slabs(), s));  // H_b over R_b
+  const LogoChainArgs chain{n, g.lda, g.A, g.R, a, g.R, g.z, g.yvar_d};
+  for (const LogoBatchChunk &bc : plan.chunks) {
+    const LogoChunk ch{bc.m, bc.count, bc.idx_off, bc.size_off, bc.term_off};
+    const LogoProblems P{r.meta + bc.prob_off, g.stride_A, np2, flags};
+    logo_chunk_run(ctx, chain, r, ch, /*from_c=*/true, need_grad, need_h, marginal, P, rb.gflags + 4 * bc.term_off);
+  }
+  hipLaunchKernelGGL(logo_problem_sum_kernel, dim3((unsigned)count), dim3(256), 0, s, r.term, rb.gflags, r.meta + plan.csr_at,
+                     r.meta + plan.csr_terms_at, g.z, np2, g.desc_d, g.quad, flags);
+  if (need_grad) launch_symv_lower_batched(s, g.A, g.lda, g.stride_A, n, a, np2, u, count);  // u_b = C_b a_b
+  if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[5], s));
+  if (need_h) {
+    launch_hct_lower_batched(s, g.R, g.lda, g.stride_A, g.A, g.lda, g.stride_A, n, r.S, g.lda, g.stride_A, count);  // S_b = C_b B_b C_b
+    if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[6], s));
+    launch_contract_batched<true>(s, g.dim_max, g.desc_d, g.tiles, count, g.groups);
+    hipLaunchKernelGGL(nll_grad_reduce_batched_kernel, dim3((unsigned)(g.groups * GRAD_GROUP), (unsigned)count), dim3(256), 0, s, g.desc_d,
+                       g.tiles, 1.0, g.grad_d, g.ldgd);
+    if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[7], s));
+  }
+  bool want_terms = false;
+  if (group_nll)
+    for (int b = 0; b < count; ++b) want_terms = want_terms || (group_nll[b] && n_groups[b] > 0);
+  if (want_terms) h_term.resize((size_t)plan.terms);
+  if (!h_term.empty()) AGP_HIP_CHECK(ctx, hipMemcpyAsync(h_term.data(), r.term, sizeof(double) * h_term.size(), hipMemcpyDeviceToHost, s));
+  st = gradient_batch_finish(ctx, g, count, n_slots, [](long long, double, double logo) { return logo; }, logo_nll, grad_logo_nll, ldg,
+                             u, mean_weights, ldw, status);
+  if (st != AGP_OK) return st;
+  if (want_terms) {  // the terms hold 2 NLL_g in the plan's order; an empty group has none; a failed problem's are NaN
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int b = 0; b < count; ++b)
+      if (group_nll[b]) std::fill(group_nll[b], group_nll[b] + n_groups[b], status[b] == AGP_OK ? 0. : nan);
+    for (size_t q = 0; q < h_term.size(); ++q) {
+      const long long b = plan.problem[q];
+      if (group_nll[b] && status[b] == AGP_OK) group_nll[b][plan.group[q]] = 0.5 * h_term[q];
+    }
+  }
+  if (prof) {
+    // whole-batch times, the indices of agp_logo_nll_gradient: 6 R^T R, 8 the mirror, the group blocks, the sums, u and H,
+    // 9 the products H C^T, 7 the contraction
+    for (int k : {3, 4, 5, 6, 7, 8, 9}) ctx->stage_ms[k] = 0.;
+    ctx->stage_ms[0] = elapsed(ctx->stage_ev[0], ctx->stage_ev[1]);
+    ctx->stage_ms[1] = elapsed(ctx->stage_ev[1], ctx->stage_ev[2]);
+    ctx->stage_ms[2] = elapsed(ctx->stage_ev[2], ctx->stage_ev[3]);
+    ctx->stage_ms[6] = elapsed(ctx->stage_ev[3], ctx->stage_ev[4]);
+    ctx->stage_ms[8] = elapsed(ctx->stage_ev[4], ctx->stage_ev[5]);
+    if (need_h) {
+      ctx->stage_ms[9] = elapsed(ctx->stage_ev[5], ctx->stage_ev[6]);
+      ctx->stage_ms[7] = elapsed(ctx->stage_ev[6], ctx->stage_ev[7]);
     }
   }
   return AGP_OK;

@@ -1308,6 +1308,31 @@ class GaussianProcessRegression:
                    "agp_logo_nll_gradient_typed")
         return value.value, self._leave_one_out_gradient_dict(p.slots, grad, u, p.fs)
 
+    def leave_one_group_out_likelihoods(self, dataset, grouper, parameter_sets, predict_type="joint"):
+        """LeaveOneGroupOutLikelihood(grouper, predict_type)(dataset, self) for several parameter vectors at once
+        (agp_logo_nll_gradient_batch without slots: the value alone, no H and no C B C).  parameter_sets: iterable of
+        {name: value} overrides of the current parameters; grouper, predict_type and the target variance as in
+        leave_one_group_out_likelihood_gradient.  Returns an array of metric values, NaN for a parameter vector whose
+        covariance or one of whose group blocks is not positive definite (or has NaN).  fp64 models only."""
+        models = self._override_copies(parameter_sets)
+        if not models:
+            return np.zeros(0)
+        values, _, _ = _leave_one_group_out_likelihood_gradients(models, [dataset] * len(models), grouper, predict_type,
+                                                                 "leave_one_group_out_likelihoods", value_only=True)
+        return np.asarray(values)
+
+    def leave_one_group_out_likelihood_gradients(self, dataset, grouper, parameter_sets, predict_type="joint"):
+        """leave_one_group_out_likelihood_gradient(dataset, grouper, predict_type) for several parameter vectors at once
+        (agp_logo_nll_gradient_batch): the counterpart of leave_one_out_likelihood_gradients for the grouped metric.
+        Returns (values: array[count], gradients: [{name: value}] with every name of get_params()); NaN throughout for a
+        parameter vector that fails.  fp64 models only."""
+        models = self._override_copies(parameter_sets)
+        if not models:
+            return np.zeros(0), []
+        values, grads, _ = _leave_one_group_out_likelihood_gradients(models, [dataset] * len(models), grouper, predict_type,
+                                                                     "leave_one_group_out_likelihood_gradients")
+        return np.asarray(values), grads
+
     def _leave_one_out_gradient_dict(self, slots, grad_loo, u, fs):
         """{name: d LOO / d name} from agp_loo_nll_gradient's per-slot values and mean weights u (slots sharing a name
         summed)"""
@@ -1972,10 +1997,94 @@ def leave_one_out_likelihood_gradient_batch(models, datasets):
     return list(zip(values, grads))
 
 
+def _leave_one_group_out_likelihood_gradients(models, datasets, grouper, predict_type, caller, value_only=False):
+    """models[b] on datasets[b], of any mix of sizes, each with its own groups: one agp_logo_nll_gradient_batch call per
+    size class.  grouper: one for every dataset, or a list / tuple with one per dataset.  Returns ([LOGO_b],
+    [{name: d LOGO_b / d name}], [status_b]) in the caller's order, NaN throughout for a problem that failed (its covariance
+    or a group block not positive definite, NaN input).  value_only: no slots and no mean weights; the gradients are None."""
+    count = len(models)
+    ptype = _predict_type(predict_type)
+    for ds in datasets:
+        if has_linear_combinations(ds.features):
+            raise NotImplementedError(f"{caller} (agp_logo_nll_gradient_batch): LinearCombination features go through the dense path")
+    if any(m.precision != "fp64" for m in models):
+        raise ValueError(f"{caller}: fp64 models only")
+    ctx = models[0]._ctx()
+    if any(m._ctx() is not ctx for m in models):
+        raise ValueError(f"{caller}: every model must live on one context")
+    groupers = list(grouper) if isinstance(grouper, (list, tuple)) else [grouper] * count
+    if len(groupers) != count:
+        raise ValueError(f"{caller}: one grouper, or one per dataset")
+    problems = [_gradient_problem(m, ds, "agp_logo_nll_gradient_batch") for m, ds in zip(models, datasets)]
+    groups = [_group_arrays(ds, gr, p.fs.n) for ds, gr, p in zip(datasets, groupers, problems)]  # (offsets, indices)
+    structs = [p.fs.as_struct() for p in problems]
+    values, grads, statuses = [None] * count, [None] * count, [None] * count
+    handles = []
+    try:
+        for m in models:  # private handles: the context's small kernel cache may evict while the batch is assembled
+            handles.append(ctx.private_kernel(m.covariance_function_))
+        for members in _size_classes([p.fs.n for p in problems]):
+            k = len(members)
+            n = max(problems[b].fs.n for b in members)  # the padded size of the class
+            Y = _ragged_columns(problems, members, n, lambda p: p.y)
+            V = _ragged_columns(problems, members, n, lambda p: p.yv)
+            n_used = [0 if value_only else len(problems[b].slots) for b in members]
+            ldg = max(1, max(n_used))
+            logo = np.empty(k)
+            grad = np.zeros((k, ldg))                      # column j of the ldg x k array: row j here
+            u = None if value_only else np.zeros((k, n))  # likewise, ldw = n
+            status = (C.c_int * k)()
+            n_slots = (C.c_int * k)(*n_used)
+            n_groups = (C.c_int64 * k)(*[len(groups[b][0]) - 1 for b in members])
+            offsets = (C.c_void_p * k)(*[groups[b][0].ctypes.data for b in members])
+            indices = (C.c_void_p * k)(*[groups[b][1].ctypes.data for b in members])
+            tables = (C.c_void_p * k)(*[C.addressof(problems[b].table) for b in members])
+            tangents, _keep = _ragged_tangents(problems, members, n)
+            kernels = (C.c_void_p * k)(*[handles[b] for b in members])
+            fptrs = (C.c_void_p * k)(*[C.addressof(structs[b]) for b in members])
+            ctx._check(ctx._lib.agp_logo_nll_gradient_batch(ctx._h, k, kernels, fptrs, _ptr(Y), n, None if V is None else _ptr(V), n,
+                                                            n_groups, offsets, indices, ptype, n_slots, tables, tangents, n,
+                                                            _ptr(logo), _ptr(grad), ldg, None if value_only else _ptr(u), n, None,
+                                                            status),
+                       f"agp_logo_nll_gradient_batch: problems {members}")
+            for j, b in enumerate(members):
+                m, p = models[b], problems[b]
+                statuses[b] = int(status[j])
+                ok = status[j] == capi.AGP_OK
+                values[b] = float(logo[j]) if ok else float("nan")
+                if value_only:
+                    grads[b] = None
+                elif ok:
+                    grads[b] = m._leave_one_out_gradient_dict(p.slots, grad[j, :len(p.slots)], u[j, :p.fs.n], p.fs)
+                else:
+                    grads[b] = {name: float("nan") for name in m.get_params()}
+    finally:
+        for kh in handles:
+            ctx._lib.agp_kernel_destroy(kh)
+    return values, grads, statuses
+
+
+def leave_one_group_out_likelihood_gradient_batch(models, datasets, grouper, predict_type="joint"):
+    """`models[b].leave_one_group_out_likelihood_gradient(datasets[b], grouper_b, predict_type)` for several INDEPENDENT
+    problems in lock step (agp_logo_nll_gradient_batch): the counterpart of leave_one_out_likelihood_gradient_batch for the
+    metric to tune with when observations come in correlated bunches.  models: fp64 GaussianProcessRegression objects on one
+    context; datasets: as many RegressionDatasets of any mix of sizes (one call per size class); grouper: one for all, or a
+    list / tuple with one per dataset (what leave_one_group_out_likelihood_gradient accepts).  The group blocks of all
+    problems of a call run as one chain per size class of groups.  Returns a list of (value, {name: gradient}, status) in
+    the caller's order; a problem that fails (status != 0: its covariance or one of its group blocks is not positive
+    definite, or its input has NaN) gives NaN throughout instead of raising."""
+    if len(models) != len(datasets) or not models:
+        raise ValueError("leave_one_group_out_likelihood_gradient_batch: as many datasets as models, at least one")
+    values, grads, statuses = _leave_one_group_out_likelihood_gradients(list(models), list(datasets), grouper, predict_type,
+                                                                        "leave_one_group_out_likelihood_gradient_batch")
+    return list(zip(values, grads, statuses))
+
+
 def _pooled(model, results):
     """(sum of the values, {name: sum of the gradients}) of the per-dataset results of one model, summed in the caller's
     order; NaN throughout if any problem failed"""
     names = list(model.get_params())
+    results = [r[:2] for r in results]
     if any(np.isnan(v) for v, _ in results):
         return float("nan"), {name: float("nan") for name in names}
     total = 0.
@@ -2000,6 +2109,14 @@ def pooled_leave_one_out_likelihood_gradient(model, datasets):
     leave_one_out_likelihood_gradient_batch([model] * B, datasets).  NaN throughout if any problem fails."""
     datasets = list(datasets)
     return _pooled(model, leave_one_out_likelihood_gradient_batch([model] * len(datasets), datasets))
+
+
+def pooled_leave_one_group_out_likelihood_gradient(model, datasets, grouper, predict_type="joint"):
+    """pooled_log_likelihood_gradient for the leave-one-group-out metric: (sum_b LOGO_b, {name: sum_b d LOGO_b / d name})
+    over leave_one_group_out_likelihood_gradient_batch([model] * B, datasets, grouper, predict_type).  NaN throughout if
+    any problem fails."""
+    datasets = list(datasets)
+    return _pooled(model, leave_one_group_out_likelihood_gradient_batch([model] * len(datasets), datasets, grouper, predict_type))
 
 
 def gp_from_covariance(covariance_function, model_name="gaussian_process_regression", context=None):

@@ -1,5 +1,5 @@
 // host_sanitize_check.cpp — the host-side C++ of the project under AddressSanitizer + UndefinedBehaviorSanitizer, on
-// a machine WITHOUT a GPU (examples/Makefile: `make asan`).  Five parts:
+// a machine WITHOUT a GPU (examples/Makefile: `make asan`).  Six parts:
 //
 //  1. the sharded-fit schedule (albatross_amd/csrc/shard_sched.hip is plain C++: compiled INTO this binary with the
 //     sanitizers on) driven through agp_debug_shard_factor_custom (csrc/shard_custom.hip) with naive block operations, one rank and - through
@@ -16,6 +16,9 @@
 //     functions are defined HERE with a table of live blocks, a log of the calls and a switch that fails the k-th
 //     allocation; every move, hand-over, refusal and failure of DevMem, ParkSlot and GrowBuf, no block left at the end.
 //
+//  6. the pooled plan of the batched leave-one-group-out gradient (albatross_amd/csrc/logo_batch_plan.h: plain C++) on
+//     ragged groupings over 1-12 problems, every table walked, with the carve of its workspace (carve_logo_batch, part 3).
+//
 // Prints "host_sanitize_check ok" and exits 0; any sanitizer report aborts with a non-zero status.
 #include <cmath>
 #include <cstdio>
@@ -31,6 +34,7 @@
 #include "dev_mem.h"         // csrc/: DevMem, ParkSlot, GrowBuf
 #include "batch_layout.h"    // csrc/: WsLayout, BatchGeometry, the carve functions
 #include "factor_plan.h"     // csrc/: FactorPlanner, plan_panels, step_launch_shape
+#include "logo_batch_plan.h" // csrc/: the pooled plan of agp_logo_nll_gradient_batch
 #include "shard_internal.h"  // agp_shard_ops_callbacks (csrc/, test-only)
 
 extern "C" {
@@ -306,6 +310,19 @@ void layouts_under_sanitizers() {
                        return std::vector<Region>{{r.R, D * B * sA}, {r.tang, D * tang}, {r.partial, D * B * part_per}, {r.grad, D * B * ldgd},
                                                   {r.gram_table, gram_bytes}, {r.desc, desc_bytes}, {r.extra, D * extra * B * np2}};
                      });
+        {  // agp_logo_nll_gradient_batch's own region behind its a and u arrays (odd element counts; with and without S)
+          const size_t blk = 3 * (size_t)lda + 5, img = 2 * (size_t)IMG, vec = 2 * np2, cnt = 6, terms = 2 * B + 4, meta = 5 * np2 + B + 8;
+          const bool slab = fused != 0;
+          check_layout("carve_logo_batch", (slab ? (B * sA + 1) / 2 * 2 : 0) + 3 * blk + img + 3 * vec + 2 * cnt + terms + meta + 2 * terms,
+                       [&](agp::WsLayout &w) {
+                         const agp::LogoBatchRegions r = agp::carve_logo_batch(w, g, slab, blk, img, vec, cnt, terms, meta);
+                         const agp::LogoRegions &c = r.chain;
+                         require(!c.a && !c.u && !c.symv, "carve_logo_batch: regions of the single entry");
+                         return std::vector<Region>{{c.S, D * B * sA}, {c.X0, D * blk}, {c.X1, D * blk}, {c.X2, D * blk}, {c.img, D * img},
+                                                    {c.d, D * vec}, {c.z, D * vec}, {c.a_pad, D * vec}, {c.logs_A, D * cnt}, {c.logs_V, D * cnt},
+                                                    {c.term, D * terms}, {c.meta, sizeof(long long) * meta}, {r.gflags, sizeof(int) * 4 * terms}};
+                       });
+        }
         if (count == 1) {  // the single-problem entries: agp_nll's ws_A, the gradients' ws_aux
           check_layout("carve_fit", sA + sI + 2 * np2, [&](agp::WsLayout &w) {
             const agp::FitRegions r = agp::carve_fit(w, g);
@@ -347,6 +364,112 @@ void layouts_under_sanitizers() {
                        });
         }
       }
+}
+
+// ---- part 6: the pooled plan of agp_logo_nll_gradient_batch (csrc/logo_batch_plan.h) ------------------------------------------
+// Ragged groupings over 1-12 problems from a fixed linear congruential stream, under the entry's limits and under small
+// ones that split every size class: every table of the plan is walked (each read inside meta), every non-empty group is
+// found once with its problem and its indices, the per-problem lists partition the terms, and the carve sized from the
+// plan holds every chunk's slabs, vectors and tables.  Malformed groupings are refused.
+long long ld_of(long long n) {  // csrc/api.hip: factor_ld
+  long long ld = (n + 7) / 8 * 8;
+  return ld % 256 == 0 ? ld + 8 : ld;
+}
+long long img_stride_of(long long m) { return (m + 127) / 128 * (36ll * 16 * 16); }  // gradient.hip: logo_img_stride
+
+void logo_batch_plan_under_sanitizers() {
+  std::uint64_t state = 12345;
+  auto next = [&](std::uint64_t mod) {
+    state = state * 6364136223846793005ull + 1442695040888963407ull;
+    return (state >> 33) % mod;
+  };
+  for (long long count = 1; count <= 12; ++count)
+    for (int small = 0; small < 2; ++small) {
+      std::vector<long long> n((size_t)count);
+      std::vector<std::int64_t> n_groups((size_t)count);
+      std::vector<std::vector<std::int64_t>> offsets((size_t)count), indices((size_t)count);
+      long long n_max = 0, want_terms = 0;
+      for (long long b = 0; b < count; ++b) {
+        n[(size_t)b] = 1 + (long long)next(300);
+        n_max = std::max(n_max, n[(size_t)b]);
+        std::vector<std::int64_t> perm((size_t)n[(size_t)b]);
+        for (size_t i = 0; i < perm.size(); ++i) perm[i] = (std::int64_t)i;
+        for (size_t i = perm.size(); i > 1; --i) std::swap(perm[i - 1], perm[(size_t)next(i)]);
+        offsets[(size_t)b].push_back(0);
+        long long at = 0;
+        if (next(6) != 0)  // (else: a problem without groups)
+          while (at < n[(size_t)b] && next(20) != 0) {
+            const long long sizes[] = {0, 1, 1, 2, 3, 4, 7, 16, 33, 64, 130};
+            const long long m = std::min(n[(size_t)b] - at, sizes[next(11)]);
+            for (long long i = 0; i < m; ++i) indices[(size_t)b].push_back(perm[(size_t)(at + i)]);
+            at += m;
+            offsets[(size_t)b].push_back(at);
+            want_terms += m > 0;
+          }
+        n_groups[(size_t)b] = (std::int64_t)offsets[(size_t)b].size() - 1;
+      }
+      std::vector<const std::int64_t *> optr, iptr;
+      for (long long b = 0; b < count; ++b) {
+        optr.push_back(offsets[(size_t)b].data());
+        iptr.push_back(indices[(size_t)b].empty() ? nullptr : indices[(size_t)b].data());
+      }
+      const agp::LogoBatchLimits lim{small ? 5 : 16384, small ? 3 * img_stride_of(1) : (32ll << 20), small ? 40 : count * n_max, ld_of,
+                                     img_stride_of};
+      agp::LogoBatchPlan p;
+      require(agp::logo_batch_plan(count, n.data(), n_groups.data(), optr.data(), iptr.data(), lim, p), "logo_batch_plan");
+      require(p.terms == want_terms && p.problems == count, "logo_batch_plan: terms");
+      std::vector<int> seen((size_t)p.terms, 0);
+      long long at = 0;
+      for (const agp::LogoBatchChunk &ch : p.chunks) {
+        require(ch.term_off == at && ch.count >= 1, "logo_batch_plan: chunk order");
+        require(ch.count <= lim.groups_max && ch.count * img_stride_of(ch.m) <= lim.img_elems_max, "logo_batch_plan: limits");
+        require(ch.count == 1 || ch.count * ch.m <= lim.cols_max, "logo_batch_plan: columns");
+        require((size_t)ch.count * (size_t)(ld_of(ch.m) * ch.m) <= p.block_elems && (size_t)(ch.count * ch.m) <= p.vec_elems &&
+                    (size_t)ch.count <= p.count_elems && (size_t)(ch.count * img_stride_of(ch.m)) <= p.img_elems,
+                "logo_batch_plan: carve sizes");
+        long long smallest = ch.m;
+        for (long long q = 0; q < ch.count; ++q) {
+          const long long sz = p.meta.at((size_t)(ch.size_off + q)), b = p.meta.at((size_t)(ch.prob_off + q));
+          const long long term = ch.term_off + q;
+          require(sz >= 1 && sz <= ch.m && b == p.problem.at((size_t)term) && sz == p.size.at((size_t)term), "logo_batch_plan: tables");
+          smallest = std::min(smallest, sz);
+          const std::int64_t *src = indices[(size_t)b].data() + offsets[(size_t)b][(size_t)p.group.at((size_t)term)];
+          require(offsets[(size_t)b][(size_t)p.group[(size_t)term] + 1] - offsets[(size_t)b][(size_t)p.group[(size_t)term]] == sz, "logo_batch_plan: group");
+          for (long long a = 0; a < ch.m; ++a) {
+            const long long v = p.meta.at((size_t)(ch.idx_off + q * ch.m + a));
+            require(a < sz ? (v == src[a] && v < n[(size_t)b]) : v == -1, "logo_batch_plan: indices");
+          }
+        }
+        require(ch.m <= 2 * smallest, "logo_batch_plan: padding");
+        at += ch.count;
+      }
+      require(at == p.terms, "logo_batch_plan: every term in a chunk");
+      for (long long b = 0; b < count; ++b) {
+        long long last = -1;
+        for (long long i = p.meta.at((size_t)(p.csr_at + b)); i < p.meta.at((size_t)(p.csr_at + b + 1)); ++i) {
+          const long long q = p.meta.at((size_t)(p.csr_terms_at + i));
+          require(q > last && p.problem.at((size_t)q) == b && !seen.at((size_t)q)++, "logo_batch_plan: term lists");
+          last = q;
+        }
+      }
+      for (int v : seen) require(v == 1, "logo_batch_plan: the lists partition the terms");
+      require((size_t)(p.csr_terms_at + p.terms) == p.meta.size(), "logo_batch_plan: meta");
+      // refused: an index of a problem at or past its own size, and one that occurs twice
+      for (long long b = 0; b < count; ++b)
+        if (!indices[(size_t)b].empty()) {
+          const std::int64_t keep = indices[(size_t)b][0];
+          agp::LogoBatchPlan q;
+          indices[(size_t)b][0] = n[(size_t)b];
+          require(!agp::logo_batch_plan(count, n.data(), n_groups.data(), optr.data(), iptr.data(), lim, q), "logo_batch_plan: index >= n_b");
+          if (indices[(size_t)b].size() > 1) {
+            agp::LogoBatchPlan t;
+            indices[(size_t)b][0] = indices[(size_t)b][1];
+            require(!agp::logo_batch_plan(count, n.data(), n_groups.data(), optr.data(), iptr.data(), lim, t), "logo_batch_plan: index twice");
+          }
+          indices[(size_t)b][0] = keep;
+          break;
+        }
+    }
 }
 
 // ---- part 4: the factorisation's schedule --------------------------------------------------------------------------
@@ -497,6 +620,7 @@ int main() {
   layouts_under_sanitizers();
   factor_plan_under_sanitizers();
   dev_mem_under_sanitizers();
+  logo_batch_plan_under_sanitizers();
   std::printf("host_sanitize_check ok\n");
   return 0;
 }

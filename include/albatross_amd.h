@@ -632,6 +632,63 @@ AGP_API int agp_loo_nll_gradient_batch_ragged(agp_context *ctx, int count,
                                               double *mean_weights, int64_t ldw,
                                               int *status);
 
+/* agp_logo_nll_gradient_typed for `count` problems of any mix of sizes in lock step, with the rules of
+ * agp_loo_nll_gradient_batch_ragged for everything but the groups: problem b computes what agp_logo_nll_gradient_typed
+ * computes on its own n_b = features[b]->n points (formulas there), as the problem diag(K_b, I) at the padded size n of the
+ * call (the largest n_b).  Phantom rows belong to no group and to no pair of the contraction.
+ *   n_groups[b], offsets[b], indices[b]   the groups of problem b, host arrays with the rules of agp_logo_nll_gradient and
+ *                     indices < n_b: empty groups and points in no group are allowed; offsets[b] and indices[b] may be NULL
+ *                     where n_groups[b] == 0 (the tables themselves may then be NULL).  A problem with no non-empty group
+ *                     gets the value 0 and a zero gradient
+ *   predict_type      AGP_PREDICT_JOINT or AGP_PREDICT_MARGINAL, one for the call
+ *   logo_nll[b]       the value per problem (host)
+ *   grad_logo_nll, ldg   column b holds the n_slots[b] derivatives of problem b (host); ldg >= the largest n_slots[b]
+ *   mean_weights, ldw    column b receives the n_b values of u_b (host), or NULL; ldw >= n
+ *   group_nll         NULL, or a host table of `count` pointers; group_nll[b] is NULL or receives n_groups[b] values in the
+ *                     caller's order, 0 for an empty group, their sum logo_nll[b] up to rounding (NaN for a failed problem)
+ *   status[b]         AGP_OK / AGP_ERR_NAN_INPUT / AGP_ERR_NOT_POSITIVE_DEFINITE per problem (host)
+ * A problem FAILS when its covariance or one of its group blocks (A_g, Joint: or V_g) does not factor, or when its input has
+ * NaN: it gets its status, logo_nll[b] = NaN, a NaN gradient column and an untouched column of mean_weights, and the rest of
+ * the batch is unaffected.  A malformed argument in ANY problem - the lists of agp_logo_nll_gradient and of
+ * agp_loo_nll_gradient_batch_ragged, an index >= n_b even where it is below n, an unknown predict_type, count <= 0 or
+ * > 65535 - returns AGP_ERR_INVALID_ARGUMENT and writes nothing, status included: every problem is checked before anything is
+ * launched.
+ * Steps: the front end of agp_loo_nll_gradient_batch_ragged up to C_b = R_b^T R_b (with all sizes equal: its equal-size
+ * launches), C_b mirrored; then the group-block chain of agp_logo_nll_gradient_typed ONCE for the groups of all problems:
+ * the non-empty groups of the whole batch are sorted by (size, problem, group) and cut into chunks under the limits of the
+ * single call (largest group at most 2x the smallest, 16384 groups, 256 MiB of tile images, count * n padded columns), each
+ * chunk ONE chain of batched launches whose kernels take every group's problem from a table, so the number of chains
+ * follows the size classes of the batch, not the number of problems or groups.  The plan is made before any status is
+ * known: the groups of a failed problem run as identity blocks with zero alpha, so nothing NaN enters the chain and
+ * nothing waits on the host.  Then one launch sums every problem's terms in a fixed order and folds the status of its
+ * blocks into its own, u_b = C_b a_b, H_b, S_b = H_b C_b^T and the contraction, each one launch for the batch.  The value
+ * alone (every n_slots[b] == 0, mean_weights NULL) takes its blocks from C_b too - the route over gathered columns of R of
+ * the single call is not used - and forms no a, H or S.
+ * A group shares its chunk's padded size with groups of OTHER problems, so a problem's bits may depend on the composition
+ * of the batch: agreement with agp_logo_nll_gradient_typed called alone is to rounding (1e-10 relative on the value in the
+ * tests), not to bits.  No float atomics, fixed-order reductions: two identical calls are bit-identical.
+ * Workspace per problem: that of agp_loo_nll_gradient_batch_ragged (the C and R slabs, 2 lda n doubles, images and O(n)
+ * vectors) plus, for gradient calls, ONE more lda x n slab (S_b; H_b lies over R_b); per call three padded block slabs and
+ * the tile images of the chunk in flight, and O(total groups) words of terms, status and tables.
+ * With profiling on, agp_last_stage_ms reports whole-batch times under the indices of agp_logo_nll_gradient: 0 gram (and
+ * the pad launch), 1 factor, 2 alpha and R, 6 R^T R, 8 the mirror, the group blocks, the sums, u and H, 9 the products
+ * H C^T, 7 the contraction; stages a call does not run report 0. */
+AGP_API int agp_logo_nll_gradient_batch(agp_context *ctx, int count,
+                                        const agp_kernel *const *kernels, const agp_features *const *features,
+                                        const double *y, int64_t ldy,
+                                        const double *y_var, int64_t ldv,
+                                        const int64_t *n_groups,
+                                        const int64_t *const *offsets, const int64_t *const *indices,
+                                        int predict_type,
+                                        const int *n_slots,
+                                        const agp_gradient_slot *const *slots,
+                                        const double *const *tangents, int64_t ldt,
+                                        double *logo_nll,
+                                        double *grad_logo_nll, int64_t ldg,
+                                        double *mean_weights, int64_t ldw,
+                                        double *const *group_nll,
+                                        int *status);
+
 /* ---- solve (CovarianceRepresentation::solve, gp.hpp:42-45,68,96,111) ----- */
 /* out = K^-1 rhs; rhs/out column-major n x nrhs (ld = n), at `location`. */
 AGP_API int agp_solve(agp_context *ctx, const agp_fit *fit, const double *rhs,

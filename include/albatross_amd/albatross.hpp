@@ -2145,6 +2145,41 @@ class GaussianProcessRegression {
     return out;
   }
 
+  // leave_one_group_out_likelihood_gradient<PredictType>(datasets[b], grouper) of THIS model for several datasets of any
+  // sizes, each with the groups `grouper` gives its features: one agp_logo_nll_gradient_batch call per size class, in which
+  // the group blocks of all its datasets run as one chain per size class of groups.  Results in the caller's order; NaN
+  // throughout for a dataset whose covariance or one of whose group blocks is not positive definite (or has NaN).
+  template <typename PredictType = JointDistribution, typename FeatureType, typename Grouper>
+  std::vector<LeaveOneOutLikelihoodGradient> leave_one_group_out_likelihood_gradient_batch(
+      const std::vector<RegressionDataset<FeatureType>> &datasets, const Grouper &grouper) const {
+    std::vector<LeaveOneOutLikelihoodGradient> out(datasets.size());
+    for_each_size_class(datasets, [&](const std::vector<std::size_t> &members,
+                                      const std::vector<const RegressionDataset<FeatureType> *> &ptrs) {
+      const std::size_t count = members.size();
+      std::vector<std::vector<std::int64_t>> offsets(count), indices(count);
+      std::vector<std::int64_t> n_groups(count);
+      std::vector<const std::int64_t *> optr(count), iptr(count);
+      for (std::size_t j = 0; j < count; ++j) {
+        detail::group_arrays(ptrs[j]->features, grouper, &offsets[j], &indices[j]);
+        n_groups[j] = static_cast<std::int64_t>(offsets[j].size()) - 1;
+        optr[j] = offsets[j].data();
+        iptr[j] = indices[j].data();
+      }
+      const auto entry = [&](agp_context *c, int k, const agp_kernel *const *kernels, const agp_features *const *features,
+                             const double *y, std::int64_t ldy, const double *y_var, std::int64_t ldv, const int *n_slots,
+                             const agp_gradient_slot *const *slots, const double *const *tangents, std::int64_t ldt, double *value,
+                             double *grad, std::int64_t ldg, double *weights, std::int64_t ldw, int *status) {
+        return agp_logo_nll_gradient_batch(c, k, kernels, features, y, ldy, y_var, ldv, n_groups.data(), optr.data(), iptr.data(),
+                                           detail::predict_type_of<PredictType>(), n_slots, slots, tangents, ldt, value, grad, ldg,
+                                           weights, ldw, nullptr, status);
+      };
+      const BatchedSlotGradients r =
+          slot_gradients_batch(entry, "agp_logo_nll_gradient_batch", ptrs, std::vector<ParameterStore>(count), true);
+      for (std::size_t j = 0; j < count; ++j) out[members[j]] = leave_one_out_result(r, j, *ptrs[j]);
+    });
+    return out;
+  }
+
   // leave_one_out_likelihood(dataset) for several parameter vectors in ONE batched device pass: the value-only path of
   // agp_loo_nll_gradient_batch (no slots, no mean weights: c_i from the column norms of R, no K^-1).  NaN where the
   // covariance is not positive definite.
@@ -2259,8 +2294,9 @@ class GaussianProcessRegression {
                                        const double *const *, std::int64_t, double *, double *, std::int64_t, double *, std::int64_t,
                                        int *);
 
-  template <typename FeatureType>
-  BatchedSlotGradients slot_gradients_batch(BatchedGradientEntry entry, const char *what,
+  // Entry: a BatchedGradientEntry, or a callable with its arguments (the leave-one-group-out batch binds its groups)
+  template <typename FeatureType, typename Entry>
+  BatchedSlotGradients slot_gradients_batch(Entry entry, const char *what,
                                             const std::vector<const RegressionDataset<FeatureType> *> &datasets,
                                             const std::vector<ParameterStore> &parameter_sets, bool with_variance,
                                             bool value_only = false) const {
@@ -2326,8 +2362,8 @@ class GaussianProcessRegression {
   }
 
   // ... over the parameter sets of one dataset
-  template <typename FeatureType>
-  BatchedSlotGradients slot_gradients_batch(BatchedGradientEntry entry, const char *what, const RegressionDataset<FeatureType> &dataset,
+  template <typename FeatureType, typename Entry>
+  BatchedSlotGradients slot_gradients_batch(Entry entry, const char *what, const RegressionDataset<FeatureType> &dataset,
                                             const std::vector<ParameterStore> &parameter_sets, bool with_variance,
                                             bool value_only = false) const {
     const std::vector<const RegressionDataset<FeatureType> *> datasets(parameter_sets.size(), &dataset);
