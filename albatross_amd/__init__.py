@@ -22,6 +22,8 @@ from .sparse_gp import (FixedInducingPoints, SparseCrossValidation, SparseCrossV
                         UniformlySpacedInducingPoints, rebase_inducing_points, sparse_gp_from_covariance,
                         sparse_gp_from_covariance_and_mean)
 
+from .pivoted import GreedyVarianceInducingPoints, PivotedCholesky, pivoted_cholesky
+
 from .scores import chi_squared_cdf, crps_normal, draw_mvn, energy_score, variogram_score
 
 from .ransac import (RANSAC_RETURN_CODE_EXCEEDED_MAX_FAILED_CANDIDATES, RANSAC_RETURN_CODE_FAILURE, RANSAC_RETURN_CODE_INVALID,

@@ -147,6 +147,7 @@ EXPORTS = [
     ("agp_ldlt_vector_d", C.c_int, [_P, _P]),
     ("agp_ldlt_transpositions", C.c_int, [_P, _P]),
     ("agp_ldlt_download", C.c_int, [_P, _P, _P, C.c_int64]),
+    ("agp_pivoted_cholesky", C.c_int, [_P, _P, C.POINTER(Features), C.c_int64, C.c_double, _P, _P, _P, C.c_int64, _P, C.c_int, _P]),
     ("agp_sparse_fit_create", C.c_int, [_P, _P, C.POINTER(Features), C.c_int64, _P, _P, _P, C.POINTER(Features), C.c_double, C.c_double, _PP, _P, _D]),
     ("agp_sparse_fit_create_sharded", C.c_int, [_P, _P, _P, C.POINTER(Features), C.c_int64, _P, _P, _P, C.POINTER(Features), C.c_double, C.c_double, _PP, _P, _D]),
     ("agp_sparse_fit_update", C.c_int, [_P, _P, _P, C.POINTER(Features), C.c_int64, _P, _P, _P, C.c_double, _PP, _P]),

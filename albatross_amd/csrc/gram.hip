@@ -314,6 +314,8 @@ static bool build_sop(const DevProgram &H, SopProgram *out) {
 bool gram_sop_enabled();  // api.hip: AGP_GRAM_SOP of the context created last (0: always the postfix interpreter)
 static bool sop_enabled() { return gram_sop_enabled(); }
 bool gram_match_fast(const DevProgram &H, FastParams *fp, int *op) { return sop_enabled() && match_fast(H, fp, op); }  // gram_fast.h
+// the sum-of-products form launch_gram would evaluate (pivoted_chol.hip builds its columns with the same evaluator)
+bool gram_build_sop(const DevProgram &H, SopProgram *out) { return sop_enabled() && build_sop(H, out); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Second fast path: sums of AT MOST three terms of fixed kinds,

@@ -881,6 +881,39 @@ AGP_API int agp_ldlt_vector_d(const agp_ldlt *ldlt, double *d);
 AGP_API int agp_ldlt_transpositions(const agp_ldlt *ldlt, int64_t *tr);
 AGP_API int agp_ldlt_download(agp_context *ctx, const agp_ldlt *ldlt, double *packed, int64_t ld);
 
+/* ---- greedy pivoted Cholesky of a covariance ------------------------------------------------
+ * The partial Cholesky factorisation of K = k(x, x) with diagonal pivoting, K evaluated column by column and never
+ * stored: greedy conditional-variance selection (every step picks the point whose prior variance is least explained
+ * by the points chosen so far), the Nystrom factor K ~ L L^T and its residual trace tr(K - L L^T).  K is the matrix
+ * agp_gram gives for x (is_measurement, equality ids, scale columns and metrics included), entry by entry the same bits.
+ *   d_i = K_ii;  d0 = max_i d_i;  step j = 0 .. max_rank - 1:
+ *     p_j = the unselected index with the largest d (the lowest index on equal values);
+ *     stop with rank = j if d_{p_j} <= rel_tol d0 or d_{p_j} <= 0;
+ *     L_ij = (k(x_i, x_{p_j}) - sum_{t<j} L_it L_{p_j t}) / sqrt(d_{p_j}), the sum in the order t = 0, 1, ...;
+ *     d_i = max(d_i - L_ij^2, 0);  exactly: L_{p_j j} = sqrt(d_{p_j}), d_{p_j} = 0, L_ij = 0 for rows selected before.
+ *   The rows of L in pivot order form a lower trapezoid with a positive diagonal.
+ *   pivots         (host) max_rank entries; p_0 .. p_{rank-1} are written, the entries from rank on are not touched
+ *   rank           (host) the steps carried out
+ *   L, ldl         n x max_rank column-major at `location` (ldl >= n), or NULL: columns 0 .. rank - 1 are written, the
+ *                  columns from rank on and the rows >= n of a padded ldl are not touched
+ *   residual_diag  n values at `location`, or NULL: d after the last step
+ *   trace_residual (host) or NULL: sum_i d_i, reduced in a fixed order
+ * x may be host or device memory (x->location); `location` is that of L and residual_diag.
+ * Status: max_rank < 1, max_rank > n, rel_tol < 0 or NaN, ldl < n with an L, a location that is neither AGP_HOST nor
+ * AGP_DEVICE, a NULL pivots or rank: AGP_ERR_INVALID_ARGUMENT, nothing written.  A NaN on the diagonal or in a computed
+ * column (a NaN coordinate): AGP_ERR_NAN_INPUT, pivots and rank not written (an L on the device may hold the columns
+ * computed up to there).
+ * One launch per step: a thread per two rows reads L coalesced (the kernel is bound by the n j doubles of L that step
+ * j reads: n max_rank^2 / 2 doubles in all); the argmax of a step is left as one partial per workgroup and reduced by
+ * every workgroup of the next launch; the stop decision is taken on the device and the host looks at it once per 64
+ * steps with the next 64 queued, otherwise the call waits once, at its end.  No float atomics and a fixed order of
+ * every sum: two identical calls return identical bits.  Scratch beyond the caller's L: about 1.2 n + max_rank doubles, plus an
+ * n x max_rank slab on the device when L is NULL or on the host.  With profiling on, agp_last_stage_ms reports the
+ * chain of step launches under stage 10. */
+AGP_API int agp_pivoted_cholesky(agp_context *ctx, const agp_kernel *k, const agp_features *x, int64_t max_rank, double rel_tol,
+                                 int64_t *pivots, int64_t *rank, double *L, int64_t ldl, double *residual_diag, int location,
+                                 double *trace_residual);
+
 /* ---- sparse Gaussian process (FITC / PITC) --------------------------------------------------
  * SparseGaussianProcessRegression, include/albatross/src/models/sparse_gp.hpp.
  *
@@ -1244,7 +1277,7 @@ AGP_API int agp_sharded_fit_stage(const agp_sharded_fit *fit, int stage, double 
  * HIP events on the stream the kernels were launched on.  Stages:
  * 0 gram, 1 factor (total), 2 solve, 3 trailing-update kernels only (sum),
  * 4 number of trailing-update launches.  Returns ms (or a count for 4).  Stages 6-9:
- * the gradient entries (agp_nll_gradient, agp_loo_nll_gradient). */
+ * the gradient entries (agp_nll_gradient, agp_loo_nll_gradient).  Stage 10: the step chain of agp_pivoted_cholesky. */
 AGP_API int agp_last_stage_ms(const agp_context *ctx, int stage, double *ms);
 /* enable (1) / disable (0) per-stage event timing (default off: events add
  * host overhead to the launch chain). */

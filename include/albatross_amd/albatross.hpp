@@ -2881,6 +2881,66 @@ struct UniformlySpacedInducingPoints {  // :36-49
   std::size_t num_points;
 };
 
+// The greedy pivoted (partial) Cholesky factorisation of cov(features) on the device (agp_pivoted_cholesky): step j
+// picks the unselected point with the largest residual variance (the lowest index on equal values) and stops when
+// that is <= tolerance * max_i K_ii or <= 0.  K ~ factor factor^T, residual_diagonal = diag(K - factor factor^T).
+struct PivotedCholesky {
+  std::vector<std::int64_t> pivots;  // rank indices in the order they were chosen
+  std::int64_t rank = 0;
+  Matrix factor;                     // n x rank
+  Vector residual_diagonal;          // n values, exactly 0 at the pivots
+  double trace_residual = 0.;
+};
+
+// max_rank is clipped to the number of features; want_factor = false leaves `factor` empty
+template <typename CovFunc, typename FeatureType>
+PivotedCholesky pivoted_cholesky(const CovFunc &cov, const std::vector<FeatureType> &features, std::size_t max_rank,
+                                 double tolerance = 0., bool want_factor = true) {
+  static_assert(!detail::expansion<FeatureType>::expands, "pivoted_cholesky: LinearCombination features are not supported");
+  if (features.empty()) throw std::invalid_argument("pivoted_cholesky: no features");
+  auto ctx = detail::default_context();
+  detail::KernelHolder k(cov.program());
+  detail::Flat f = detail::flatten(cov, features);
+  const std::int64_t n = static_cast<std::int64_t>(features.size());
+  const std::int64_t m = static_cast<std::int64_t>(max_rank) < n ? static_cast<std::int64_t>(max_rank) : n;
+  PivotedCholesky out;
+  out.pivots.assign(static_cast<std::size_t>(m > 0 ? m : 1), 0);
+  out.residual_diagonal.assign(static_cast<std::size_t>(n), 0.);
+  Matrix full;
+  if (want_factor) full = Matrix(n, m > 0 ? m : 1);
+  detail::check(agp_pivoted_cholesky(ctx->ctx, k.k, &f.view, m, tolerance, out.pivots.data(), &out.rank,
+                                     want_factor ? full.data.data() : nullptr, n, out.residual_diagonal.data(), AGP_HOST,
+                                     &out.trace_residual),
+                ctx->ctx, "agp_pivoted_cholesky");
+  out.pivots.resize(static_cast<std::size_t>(out.rank));
+  if (want_factor) {
+    out.factor = Matrix(n, out.rank);
+    std::copy(full.data.begin(), full.data.begin() + static_cast<std::ptrdiff_t>(n * out.rank), out.factor.data.begin());
+  }
+  return out;
+}
+
+// An InducingPointStrategy: the num_points features that the greedy pivoted Cholesky factorisation of cov(features)
+// selects, in the order it selects them.  Fewer are returned when the largest residual variance falls to `tolerance`
+// times the largest prior variance first (copies of a chosen point are never chosen; a tolerance of 0 would go on to
+// select their rounding dust); num_points is clipped to the number of features.  The selection sees the covariance of the
+// plain features: measurement_only terms are zero for it, as they are in K_uu; an unwrapped IndependentNoise term
+// raises every diagonal entry, so the selection sees it and the residual never falls below it.
+struct GreedyVarianceInducingPoints {
+  explicit GreedyVarianceInducingPoints(std::size_t num_points_ = 10, double tolerance_ = 1e-12)
+      : num_points(num_points_), tolerance(tolerance_) {}
+  template <typename CovarianceFunction, typename FeatureType>
+  std::vector<FeatureType> operator()(const CovarianceFunction &cov, const std::vector<FeatureType> &features) const {
+    const PivotedCholesky f = pivoted_cholesky(cov, features, num_points, tolerance, false);
+    std::vector<FeatureType> out;
+    out.reserve(f.pivots.size());
+    for (std::int64_t p : f.pivots) out.push_back(features[static_cast<std::size_t>(p)]);
+    return out;
+  }
+  std::size_t num_points;
+  double tolerance;
+};
+
 // Fit<SparseGPFit<InducingFeature>> (:92-124)
 template <typename InducingFeature>
 struct SparseGPFit {
