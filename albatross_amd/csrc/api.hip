@@ -759,10 +759,11 @@ void agp_fit_destroy(agp_fit *fit) {
 // ---- x = L^-T z for ONE vector ------------------------------------------------------------------------------
 // Wide path (n a multiple of 512, n >= 2048): the 512 x 512 diagonal blocks are inverted explicitly (one batched
 // triangular solve against the identity), after which a step is two column-dot launches per 512 rows instead of
-// four fused launches per 128 rows: the chain is launch-latency-bound (AGP_WIDE_BACKSOLVE=0: off, =<width>: other
-// block width).  Otherwise the 128-row chain on 128 x 128 inverses.  ws: backsolve_ws_elems(n) doubles of scratch.
+// four fused launches per 128 rows: the chain is launch-latency-bound.  The width is fixed; no environment switch
+// changes it.  Otherwise the 128-row chain on 128 x 128 inverses.  ws: backsolve_ws_elems(n) doubles of scratch.
 long long backsolve_width(long long n) {
   constexpr long long BW = 512;
+  static_assert(BW <= TALL_MATVEC_MAX_COLS, "forward_solve_vec_wide's launch_tall_matvec takes BW columns");
   return (n >= 4 * BW && n % BW == 0) ? BW : 0;
 }
 
@@ -808,9 +809,11 @@ void backward_solve_vec_any(hipStream_t s, const double *A, long long n, long lo
 // instead of one fused launch per 128 (the chain is launch-latency-bound).  partial: n doubles of scratch.
 // A32 (optional): an fp32 copy of the factor's lower triangle (same leading dimension) for the products with the rows
 // below / the columns left of a diagonal block - half the bytes of sweeps that are bound by them; for a PRECONDITIONER
-static void forward_solve_vec_wide(hipStream_t s, const double *A, long long n, long long lda, const double *W, long long BW,
-                                   double *z, double *partial, const float *A32 = nullptr) {
+void forward_solve_vec_wide(hipStream_t s, const double *A, long long n, long long lda, const double *W, long long BW,
+                            double *z, double *partial, const float *A32) {
   const long long nb = n / BW;
+  // (BW <= TALL_MATVEC_MAX_COLS, or the launches below do nothing: backsolve_width's static_assert and
+  // mixed_precondition_setup check it where the width is chosen)
   for (long long b = 0; b < nb; ++b) {
     const long long k0 = b * BW, below = n - k0 - BW;
     // (x_B goes through `partial` first: the kernel may not overwrite z_B while other workgroups still read it)
@@ -848,8 +851,8 @@ void backward_solve_vec_from(hipStream_t s, const double *A, long long n, long l
 }
 
 // z <- L^-T z with the same inverses (the loop of backward_solve_vec_any); xs: n doubles of scratch
-static void backward_solve_vec_wide(hipStream_t s, const double *A, long long n, long long lda, const double *W, long long BW,
-                                    double *z, double *xs, const float *A32 = nullptr) {
+void backward_solve_vec_wide(hipStream_t s, const double *A, long long n, long long lda, const double *W, long long BW,
+                             double *z, double *xs, const float *A32) {
   const long long nb = n / BW;
   for (long long b = nb - 1; b >= 0; --b) {
     const long long k0 = b * BW;
@@ -858,6 +861,56 @@ static void backward_solve_vec_wide(hipStream_t s, const double *A, long long n,
     else if (k0 > 0) launch_colvec_dot(s, A + k0, lda, BW, k0, xs + k0, -1.0, 1.0, z, z);
   }
   (void)hipMemcpyAsync(z, xs, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s);
+}
+
+// ---- the preconditioner of the mixed fit's refinement (api_internal.h: MixedPreconditioner) ---------------------------
+int mixed_precondition_setup(hipStream_t s, const MixedPreconditioner &pc, const double *invd) {
+  // (the widths the sweeps' kernels are written for; launch_tall_matvec* would do NOTHING beyond TALL_MATVEC_MAX_COLS and
+  // leave the vector of the step before in place)
+  if ((pc.BW != 512 && pc.BW != 1024) || pc.BW > TALL_MATVEC_MAX_COLS || pc.n <= 0 || pc.n % pc.BW != 0) return AGP_ERR_INVALID_ARGUMENT;
+  invert_wide_blocks(s, pc.A, pc.n, pc.lda, invd, pc.BW, pc.W);
+  // ... and their transposes: the forward sweep applies inv(L_BB) as a column-wise product with the transposed copy
+  // (one workgroup per output, like the backward sweep) instead of a row-wise one on BW / 64 workgroups
+  launch_transpose_blocks(s, pc.W, pc.WT, pc.BW, pc.n / pc.BW);
+  if (pc.L32) launch_convert_lower_f32(s, pc.A, pc.lda, pc.n, pc.L32);
+  return AGP_OK;
+}
+
+// both sweeps out of place - no staging copy per block, none at the end: t1 = in is consumed by the forward sweep
+// (x_B into t2, the rows below updated in t1), t2 by the backward sweep (x_B into outv, the rows above updated in t2)
+void mixed_precondition_forward(hipStream_t s, const MixedPreconditioner &pc, const double *in) {
+  const long long n = pc.n, lda = pc.lda, BW = pc.BW, nbw = n / BW;
+  double *t1 = pc.t1, *t2 = pc.t2;
+  (void)hipMemcpyAsync(t1, in, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s);
+  for (long long b = 0; b < nbw; ++b) {
+    const long long k0 = b * BW, below = n - k0 - BW;
+    launch_colvec_dot(s, pc.WT + b * BW * BW, BW, BW, BW, t1 + k0, 1.0, 0.0, nullptr, t2 + k0);  // x_B = inv(L_BB) z_B
+    // (BW <= TALL_MATVEC_MAX_COLS: mixed_precondition_setup)
+    if (below > 0) launch_tall_matvec_f32(s, pc.L32 + k0 * lda + k0 + BW, lda, below, BW, t2 + k0, -1.0, 1.0, t1 + k0 + BW, t1 + k0 + BW);
+  }
+}
+
+void mixed_precondition_backward(hipStream_t s, const MixedPreconditioner &pc, double *outv) {
+  const long long n = pc.n, lda = pc.lda, BW = pc.BW, nbw = n / BW;
+  double *t2 = pc.t2;
+  for (long long b = nbw - 1; b >= 0; --b) {
+    const long long k0 = b * BW;
+    launch_colvec_dot(s, pc.W + b * BW * BW, BW, BW, BW, t2 + k0, 1.0, 0.0, nullptr, outv + k0);  // x_B = inv(L_BB)^T z_B
+    if (k0 > 0) launch_colvec_dot_f32(s, pc.L32 + k0, lda, BW, k0, outv + k0, -1.0, 1.0, t2, t2);
+  }
+}
+
+void mixed_precondition_apply(hipStream_t s, const MixedPreconditioner &pc, const double *in, double *outv) {
+  const long long n = pc.n, lda = pc.lda, BW = pc.BW;
+  if (pc.L32) {
+    mixed_precondition_forward(s, pc, in);
+    mixed_precondition_backward(s, pc, outv);
+    return;
+  }
+  // (no fp32 copy - its allocation failed: the fp64 factor, in place)
+  (void)hipMemcpyAsync(outv, in, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s);
+  forward_solve_vec_wide(s, pc.A, n, lda, pc.W, BW, outv, pc.scratch, nullptr);
+  backward_solve_vec_wide(s, pc.A, n, lda, pc.W, BW, outv, pc.scratch, nullptr);
 }
 
 namespace {
@@ -1189,14 +1242,8 @@ static int refine_information(agp_context_impl *ctx, agp_fit *fit, const double 
   }
   double *symv_ws = ctx->ws_refine;
   double *Wwide = BW ? ctx->ws_refine + symv_elems : nullptr;
-  // ... and their transposes: the forward sweep applies inv(L_BB) as a column-wise product with the transposed copy
-  // (one workgroup per output, like the backward sweep) instead of a row-wise one on BW / 64 workgroups
   double *WwideT = BW ? Wwide + wide_elems : nullptr;
   double *t1 = ctx->ws_refine + symv_elems + 2 * wide_elems, *t2 = t1 + np2;  // the sweeps' work vectors
-  if (BW) {
-    invert_wide_blocks(s, fit->A, n, lda, fit->invd, BW, Wwide);
-    launch_transpose_blocks(s, Wwide, WwideT, BW, n / BW);
-  }
   // The preconditioner M = L L^T is applied eight-odd times and each application streams L twice; it does not have to
   // be exact - L itself comes from fp32-rounded products -, so the sweeps read an fp32 COPY of L's off-diagonal blocks
   // (the inverted diagonal blocks stay fp64): half the bytes, kept in the context between fits.
@@ -1210,31 +1257,20 @@ static int refine_information(agp_context_impl *ctx, agp_fit *fit, const double 
       if (dev_malloc_plain_bytes(reinterpret_cast<void **>(&L32), want) != 0) { (void)hipGetLastError(); L32 = nullptr; }
     }
     if (L32) (void)ctx->pool_L32.park(L32, want);
-    if (L32) launch_convert_lower_f32(s, fit->A, lda, n, L32);
+  }
+  MixedPreconditioner pc;
+  pc.A = fit->A; pc.n = n; pc.lda = lda; pc.BW = BW;
+  pc.W = Wwide; pc.WT = WwideT; pc.L32 = L32;
+  pc.t1 = t1; pc.t2 = t2; pc.scratch = ctx->ws_aux;
+  if (BW) {
+    const int st_pc = mixed_precondition_setup(s, pc, fit->invd);
+    if (st_pc != AGP_OK) return st_pc;
   }
   auto precondition = [&](const double *in, double *outv) {
-    if (BW && L32) {
-      // both sweeps out of place - no staging copy per block, none at the end: t1 = in is consumed by the forward sweep
-      // (x_B into t2, the rows below updated in t1), t2 by the backward sweep (x_B into outv, the rows above updated in t2)
-      const long long nbw = n / BW;
-      (void)hipMemcpyAsync(t1, in, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s);
-      for (long long b = 0; b < nbw; ++b) {
-        const long long k0 = b * BW, below = n - k0 - BW;
-        launch_colvec_dot(s, WwideT + b * BW * BW, BW, BW, BW, t1 + k0, 1.0, 0.0, nullptr, t2 + k0);  // x_B = inv(L_BB) z_B
-        if (below > 0) launch_tall_matvec_f32(s, L32 + k0 * lda + k0 + BW, lda, below, BW, t2 + k0, -1.0, 1.0, t1 + k0 + BW, t1 + k0 + BW);
-      }
-      for (long long b = nbw - 1; b >= 0; --b) {
-        const long long k0 = b * BW;
-        launch_colvec_dot(s, Wwide + b * BW * BW, BW, BW, BW, t2 + k0, 1.0, 0.0, nullptr, outv + k0);  // x_B = inv(L_BB)^T z_B
-        if (k0 > 0) launch_colvec_dot_f32(s, L32 + k0, lda, BW, k0, outv + k0, -1.0, 1.0, t2, t2);
-      }
-      return;
-    }
-    (void)hipMemcpyAsync(outv, in, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s);
     if (BW) {
-      forward_solve_vec_wide(s, fit->A, n, lda, Wwide, BW, outv, ctx->ws_aux, L32);
-      backward_solve_vec_wide(s, fit->A, n, lda, Wwide, BW, outv, ctx->ws_aux, L32);
+      mixed_precondition_apply(s, pc, in, outv);
     } else {
+      (void)hipMemcpyAsync(outv, in, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s);
       forward_solve_vec(s, fit->A, n, lda, Wfwd, outv, ctx->ws_aux);
       backward_solve_vec(s, fit->A, n, lda, fit->winv, outv, ctx->ws_aux);
     }

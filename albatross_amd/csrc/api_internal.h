@@ -34,6 +34,7 @@ void launch_matvec(hipStream_t s, const double *W, long long ld, long long m, lo
                    double *partial, double alpha, double beta, const double *base, double *out);
 void launch_contract_combinations(hipStream_t s, const double *K, long long ldk, const long long *xoff, const double *xc, long long na,
                                   const long long *yoff, const double *yc, long long nb, bool symmetric, double *out, long long ldo);
+// (no launch for more than TALL_MATVEC_MAX_COLS columns: common.h)
 void launch_tall_matvec(hipStream_t s, const double *W, long long ld, long long rows, long long ncols, const double *x, double alpha,
                         double beta, const double *base, double *out);
 void launch_tall_matvec_f32(hipStream_t s, const float *W, long long ld, long long rows, long long ncols, const double *x, double alpha,
@@ -229,7 +230,37 @@ int factor_dense(agp_context *ctx, const double *K, long long n, long long ld, i
                  const double *diag_add = nullptr);
 // `bytes` of the context's pinned staging area, or nullptr; valid until the call's final synchronisation
 void *host_stage(agp_context *ctx, size_t bytes);
+long long backsolve_width(long long n);  // the wide path's block width (512), or 0: the 128-row chain
 size_t backsolve_ws_elems(long long n);
 void backward_solve_vec_any(hipStream_t s, const double *A, long long n, long long lda, const double *invd, double *z,
                             double *ws, long long first_done = 0, hipEvent_t ev_done = nullptr);
+// One right-hand side through explicitly inverted BW x BW diagonal blocks W (invert_wide_blocks; n a multiple of BW,
+// BW <= TALL_MATVEC_MAX_COLS): z <- L^-1 z and z <- L^-T z in place; partial / xs: n doubles of scratch; A32 (optional):
+// the fp32 copy of the factor (launch_convert_lower_f32) for the products with the blocks off the diagonal.
+void forward_solve_vec_wide(hipStream_t s, const double *A, long long n, long long lda, const double *W, long long BW,
+                            double *z, double *partial, const float *A32 = nullptr);
+void backward_solve_vec_wide(hipStream_t s, const double *A, long long n, long long lda, const double *W, long long BW,
+                             double *z, double *xs, const float *A32 = nullptr);
+// The preconditioner of the mixed fit's refinement (api.hip: refine_information): out = Lt^-T Lt^-1 in, where Lt has the
+// factor's BW-wide diagonal blocks in fp64 - applied through their explicit inverses W and the transposed copies WT -
+// and the fp32 copy L32 of everything below them.  The caller owns every buffer: W, WT n / BW blocks of BW x BW; L32
+// lda x n floats, or nullptr (then the sweeps read the fp64 factor, through forward / backward_solve_vec_wide and
+// `scratch`); t1, t2, scratch n doubles each.
+struct MixedPreconditioner {
+  const double *A = nullptr;
+  long long n = 0, lda = 0, BW = 0;
+  double *W = nullptr, *WT = nullptr;
+  float *L32 = nullptr;
+  double *t1 = nullptr, *t2 = nullptr, *scratch = nullptr;
+};
+// inverts the diagonal blocks into W, transposes them into WT and converts the factor into L32 (when there is one);
+// AGP_ERR_INVALID_ARGUMENT, with nothing launched, for a BW the sweeps' kernels do not take
+int mixed_precondition_setup(hipStream_t s, const MixedPreconditioner &pc, const double *invd);
+// out = M^-1 in; `in` is left as it is
+void mixed_precondition_apply(hipStream_t s, const MixedPreconditioner &pc, const double *in, double *out);
+// its two sweeps with an L32 (apply is one after the other): t2 = Lt^-1 in, consuming t1; out = Lt^-T t2, consuming t2.
+// Declared here ONLY for agp_debug_wide_sweep (debug_api.hip), which copies t2 between them to check each sweep on its
+// own: product code calls mixed_precondition_apply - backward alone reads whatever the last forward sweep left in t2.
+void mixed_precondition_forward(hipStream_t s, const MixedPreconditioner &pc, const double *in);
+void mixed_precondition_backward(hipStream_t s, const MixedPreconditioner &pc, double *out);
 }

@@ -368,6 +368,10 @@ void launch_gemm_tn_sub(hipStream_t s, const double *V, long long ldv, const dou
 void launch_gemv_t(hipStream_t s, const double *A, long long lda, long long n, long long m,
                    const double *x, double *y);
 void launch_dot(hipStream_t s, const double *a, const double *b, long long n, double *out);
+// launch_tall_matvec / launch_tall_matvec_f32 (reduce.hip; declared in api_internal.h) stage x in LDS and launch NOTHING for more columns than this: every
+// caller checks its width against it where the width is chosen - api.hip: backsolve_width (static_assert) and
+// mixed_precondition_setup; solver_api.hip: agp_solver_update_information (launch_matvec beyond it)
+constexpr long long TALL_MATVEC_MAX_COLS = 2048;
 
 }  // namespace agp
 

@@ -1675,6 +1675,324 @@ AGP_DEBUG_API int agp_debug_qr_back_solve(agp_context *ctx, const double *R, int
   return AGP_OK;
 }
 
+// ONE wide vector sweep of api.hip on host data (tests/test_reduce_kernels_gpu.py): the single-right-hand-side substitutions
+// through explicitly inverted BW x BW diagonal blocks, and one application of the mixed fit's preconditioner.
+//   kind   WS_FWD_VEC_WIDE / WS_BWD_VEC_WIDE: forward_solve_vec_wide / backward_solve_vec_wide, with the fp32 copy of the
+//          factor for the blocks off the diagonal when use_a32;  WS_BWD_VEC_ANY_WIDE: backward_solve_vec_any's wide branch
+//          (first_done = 0, no event; BW must be backsolve_width(n));  WS_MIXED_PRECONDITION: mixed_precondition_setup
+//          and ONE application, sweep by sweep (always with the fp32 copy)
+//   K      the SPD matrix (n x n, ld n), factored by agp_factor_create; n a multiple of BW, BW 512 or 1024
+//   z      the caller's whole vector buffer, z_doubles >= n long, padding included: copied in, solved in place (the
+//          preconditioner: read from a copy, its output written over the buffer's first n words), copied back
+//   t2_out (WS_MIXED_PRECONDITION, z_doubles long) the forward sweep's result (t2 before the backward sweep consumes it),
+//          the words behind it all-ones NaN
+//   L_out  (optional, n x n, ld n) the factor;  L32_out (optional, n x n FLOATS, ld n) the top n rows of the fp32 copy,
+//          all-ones NaN before the conversion.  Only z and t2 come back with their padding: the padding rows of the factor
+//          and of its fp32 copy (lda > n) are not returned - RED_CONVERT_LOWER_F32 below checks the whole buffer of the copy
+enum { WS_FWD_VEC_WIDE = 0, WS_BWD_VEC_WIDE, WS_BWD_VEC_ANY_WIDE, WS_MIXED_PRECONDITION, WS_KINDS };
+AGP_DEBUG_API int agp_debug_wide_sweep(agp_context *ctx, int kind, const double *K, int64_t n, int64_t BW, int use_a32, double *z,
+                                       int64_t z_doubles, double *t2_out, double *L_out, float *L32_out) {
+  if (!ctx || !K || !z || kind < 0 || kind >= WS_KINDS || (BW != 512 && BW != 1024) || n <= 0 || n > 16384 || n % BW != 0 ||
+      z_doubles < n || z_doubles > n + 4096)
+    return AGP_ERR_INVALID_ARGUMENT;
+  if (kind == WS_BWD_VEC_ANY_WIDE && (use_a32 || BW != backsolve_width(n))) return AGP_ERR_INVALID_ARGUMENT;
+  if (kind == WS_MIXED_PRECONDITION && !t2_out) return AGP_ERR_INVALID_ARGUMENT;
+  const bool a32 = use_a32 || kind == WS_MIXED_PRECONDITION;
+  if (L32_out && !a32) return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  struct FitHolder {
+    agp_fit *f = nullptr;
+    ~FitHolder() { if (f) agp_fit_destroy(f); }
+  } fh;
+  const int st = agp_factor_create(ctx, K, n, n, 0, AGP_HOST, &fh.f);
+  if (st != AGP_OK) return st;
+  const agp_fit *f = fh.f;
+  const long long lda = f->lda;
+  const size_t zbytes = sizeof(double) * (size_t)z_doubles, wide = (size_t)n * (size_t)BW;
+  DevBuf<double> dz, din, dt1, dt2, dW, dWT, dws;
+  DevBuf<float> dL32;
+  AGP_HIP_CHECK(ctx, dz.alloc((size_t)z_doubles));
+  AGP_HIP_CHECK(ctx, hipMemcpy(dz.p, z, zbytes, hipMemcpyHostToDevice));
+  if (a32) {
+    AGP_HIP_CHECK(ctx, dL32.alloc((size_t)lda * (size_t)n));
+    AGP_HIP_CHECK(ctx, hipMemsetAsync(dL32.p, 0xFF, sizeof(float) * (size_t)lda * (size_t)n, s));  // (all ones: a NaN)
+  }
+  if (kind == WS_BWD_VEC_ANY_WIDE) {
+    AGP_HIP_CHECK(ctx, dws.alloc(backsolve_ws_elems(n)));
+    backward_solve_vec_any(s, f->A, n, lda, f->invd, dz.p, dws.p, 0, nullptr);
+  } else if (kind == WS_MIXED_PRECONDITION) {
+    AGP_HIP_CHECK(ctx, din.alloc((size_t)n));
+    AGP_HIP_CHECK(ctx, dt1.alloc((size_t)z_doubles));
+    AGP_HIP_CHECK(ctx, dt2.alloc((size_t)z_doubles));
+    AGP_HIP_CHECK(ctx, dW.alloc(wide));
+    AGP_HIP_CHECK(ctx, dWT.alloc(wide));
+    AGP_HIP_CHECK(ctx, dws.alloc((size_t)n));
+    AGP_HIP_CHECK(ctx, hipMemcpy(din.p, z, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+    AGP_HIP_CHECK(ctx, hipMemsetAsync(dt1.p, 0xFF, zbytes, s));
+    AGP_HIP_CHECK(ctx, hipMemsetAsync(dt2.p, 0xFF, zbytes, s));
+    MixedPreconditioner pc;
+    pc.A = f->A; pc.n = n; pc.lda = lda; pc.BW = BW;
+    pc.W = dW.p; pc.WT = dWT.p; pc.L32 = dL32.p;
+    pc.t1 = dt1.p; pc.t2 = dt2.p; pc.scratch = dws.p;
+    const int stp = mixed_precondition_setup(s, pc, f->invd);
+    if (stp != AGP_OK) return stp;
+    // (mixed_precondition_apply, with the forward sweep's result kept before the backward sweep consumes it)
+    mixed_precondition_forward(s, pc, din.p);
+    AGP_HIP_CHECK(ctx, hipMemcpyAsync(dt1.p, dt2.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
+    mixed_precondition_backward(s, pc, dz.p);
+  } else {
+    AGP_HIP_CHECK(ctx, dW.alloc(wide));
+    AGP_HIP_CHECK(ctx, dws.alloc((size_t)n));
+    invert_wide_blocks(s, f->A, n, lda, f->invd, BW, dW.p);
+    if (a32) launch_convert_lower_f32(s, f->A, lda, n, dL32.p);
+    if (kind == WS_FWD_VEC_WIDE) forward_solve_vec_wide(s, f->A, n, lda, dW.p, BW, dz.p, dws.p, dL32.p);
+    else backward_solve_vec_wide(s, f->A, n, lda, dW.p, BW, dz.p, dws.p, dL32.p);
+  }
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipMemcpy(z, dz.p, zbytes, hipMemcpyDeviceToHost));
+  if (kind == WS_MIXED_PRECONDITION) AGP_HIP_CHECK(ctx, hipMemcpy(t2_out, dt1.p, zbytes, hipMemcpyDeviceToHost));
+  if (L_out)
+    AGP_HIP_CHECK(ctx, hipMemcpy2D(L_out, sizeof(double) * (size_t)n, f->A, sizeof(double) * (size_t)lda, sizeof(double) * (size_t)n,
+                                   (size_t)n, hipMemcpyDeviceToHost));
+  if (L32_out)
+    AGP_HIP_CHECK(ctx, hipMemcpy2D(L32_out, sizeof(float) * (size_t)n, dL32.p, sizeof(float) * (size_t)lda, sizeof(float) * (size_t)n,
+                                   (size_t)n, hipMemcpyDeviceToHost));
+  return AGP_OK;
+}
+
+// ONE launch_* of reduce.hip on host data (tests/test_reduce_kernels_gpu.py).  bufs[k] (bytes[k] long, or null for an optional
+// pointer) are copied to the device whole, the launcher runs once on the context's stream, and every buffer is copied back
+// whole - padding, gaps and sentinels included.  Two entries with the SAME host pointer share one device buffer (base
+// aliasing out, the variance of loo aliasing diag(K^-1)).  ip / dp: the integer and floating-point arguments, per op in the
+// order of the table below; buffers in the order given there.  Every extent the kernels address - the index lists' contents
+// included - is checked against bytes[] on the host first: AGP_ERR_INVALID_ARGUMENT, with nothing launched.  So is a
+// tall_matvec of more than TALL_MATVEC_MAX_COLS columns, for which the launcher would silently do nothing.
+//   RED_COLDOT               ip lda ldb n m;  dp scale;  A B out [base]
+//   RED_DOT                  ip n;  a b out
+//   RED_MATVEC               ip ld m n;  dp alpha beta;  W x partial [base] out        (n = 0: W and x may be null)
+//   RED_TALL_MATVEC(_F32)    ip ld rows ncols;  dp alpha beta;  W x [base] out
+//   RED_COLVEC_DOT(_F32)     ip ld m n;  dp alpha beta;  W v [base] out
+//   RED_COLVEC_DOT_STRIDED   ip ld stride_W m n stride_v count;  dp alpha beta;  W v [base] out
+//   RED_COLVEC_DOT_BATCHED   ip ld stride_Q m stride_z count;  Q z out
+//   RED_SYMV_LOWER_BATCHED   ip ld stride_K n stride_v count;  K p out
+//   RED_CONTRACT             ip ldk na nb symmetric ldo;  K [xoff] [xc] [yoff] [yc] out
+//   RED_SYMMETRIZE, RED_ZERO_UPPER, RED_SET_IDENTITY   ip ld n;  A
+//   RED_UPPER_TO_LOWER       ip ld_src ld_dst n;  src dst
+//   RED_TRANSPOSE_BLOCKS     ip m count;  src dst
+//   RED_SET_IDENTITY_BATCHED ip ld stride m count;  B
+//   RED_NEGATE               ip ld m;  A [diag_out]
+//   RED_NAN_SCAN_LOWER       ip ld n;  A flag(int)
+//   RED_COPY_LOWER           ip ld n;  src dst [flag(int)]          (ld even)
+//   RED_CONVERT_LOWER_F32    ip ld n;  L L32(float)                 (ld even)
+//   RED_LOO                  ip n;  kinv_diag y information mean variance
+//   RED_GATHER_COLS          ip ldr m row0 n ldg cols_of_R;  R idx(int64) G
+//   RED_GATHER_VEC           ip m len_of_src;  src idx(int64) [sub] out
+//   RED_PAD_COLUMNS          ip ld_src smax n_groups rows ld_dst dir;  src off(int64) dst
+//   RED_PAD_IDENTITY         ip ld stride smax n_groups;  A off(int64)
+//   RED_COMPACT_BLOCKS       ip ld stride smax n_groups;  slabs off(int64) boff(int64) out
+//   RED_AXPBY                ip n;  dp a b;  [x] [y] out
+enum {
+  RED_COLDOT = 0, RED_DOT, RED_MATVEC, RED_TALL_MATVEC, RED_TALL_MATVEC_F32, RED_COLVEC_DOT, RED_COLVEC_DOT_STRIDED,
+  RED_COLVEC_DOT_BATCHED, RED_COLVEC_DOT_F32, RED_SYMV_LOWER_BATCHED, RED_CONTRACT, RED_SYMMETRIZE, RED_UPPER_TO_LOWER,
+  RED_TRANSPOSE_BLOCKS, RED_ZERO_UPPER, RED_SET_IDENTITY, RED_SET_IDENTITY_BATCHED, RED_NEGATE, RED_NAN_SCAN_LOWER,
+  RED_COPY_LOWER, RED_CONVERT_LOWER_F32, RED_LOO, RED_GATHER_COLS, RED_GATHER_VEC, RED_PAD_COLUMNS, RED_PAD_IDENTITY,
+  RED_COMPACT_BLOCKS, RED_AXPBY, RED_OPS
+};
+AGP_DEBUG_API int agp_debug_reduce(agp_context *ctx, int op, const int64_t *ip, int n_ip, const double *dp, int n_dp, void *const *bufs,
+                                   const int64_t *bytes, int n_bufs) {
+  constexpr int MAXB = 6;
+  constexpr long long LIM = 1ll << 26;  // no dimension, stride or count of a test comes near it: the products below cannot overflow
+  if (!ctx || op < 0 || op >= RED_OPS || !ip || !bufs || !bytes || n_ip < 1 || n_ip > 8 || n_dp < 0 || n_dp > 2 || (n_dp && !dp) ||
+      n_bufs < 1 || n_bufs > MAXB)
+    return AGP_ERR_INVALID_ARGUMENT;
+  long long I[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int k = 0; k < n_ip; ++k) {
+    if (ip[k] < 0 || ip[k] > LIM) return AGP_ERR_INVALID_ARGUMENT;
+    I[k] = ip[k];
+  }
+  const double d0 = n_dp > 0 ? dp[0] : 0., d1 = n_dp > 1 ? dp[1] : 0.;
+  for (int k = 0; k < n_bufs; ++k)
+    if (bytes[k] < 0 || (bufs[k] && bytes[k] == 0)) return AGP_ERR_INVALID_ARGUMENT;
+  auto has = [&](int k) { return k < n_bufs && bufs[k] != nullptr; };
+  // buffer k is there and holds `elems` elements of `esize` bytes
+  auto fits = [&](int k, long long elems, long long esize = 8) { return has(k) && elems >= 0 && elems <= LIM * 64 && bytes[k] >= elems * esize; };
+  auto opt_fits = [&](int k, long long elems) { return !has(k) || fits(k, elems); };
+  // elements a column-major rows x cols matrix of leading dimension ld spans; -1 (fits nothing) for ld < rows
+  auto mat = [](long long ld, long long rows, long long cols) -> long long {
+    if (ld < rows || rows < 1 || cols < 1) return -1;
+    return ld * (cols - 1) + rows;
+  };
+  auto slabs = [&](long long count, long long stride, long long one) -> long long {
+    return (count < 1 || one < 0) ? -1 : (count - 1) * stride + one;
+  };
+  // a list of `entries` int64 in buffer k
+  auto list = [&](int k, long long entries) -> const long long * {
+    return fits(k, entries) ? static_cast<const long long *>(bufs[k]) : nullptr;
+  };
+  // group offsets off[0 .. groups]: ascending from >= 0, no group larger than smax; the total, or -1
+  auto groups_total = [&](const long long *off, long long groups, long long smax) -> long long {
+    if (!off || off[0] < 0) return -1;
+    for (long long g = 0; g < groups; ++g)
+      if (off[g + 1] < off[g] || off[g + 1] - off[g] > smax || off[g + 1] > LIM) return -1;
+    return off[groups];
+  };
+  bool ok = false;
+  switch (op) {
+  case RED_COLDOT:
+    ok = n_ip == 4 && fits(0, mat(I[0], I[2], I[3])) && fits(1, mat(I[1], I[2], I[3])) && fits(2, I[3]) && I[3] >= 1 && opt_fits(3, I[3]);
+    break;
+  case RED_DOT: ok = n_ip == 1 && I[0] >= 1 && fits(0, I[0]) && fits(1, I[0]) && fits(2, 1); break;
+  case RED_MATVEC:
+    ok = n_ip == 3 && I[1] >= 1 && I[0] >= I[1] && (I[2] == 0 || (fits(0, mat(I[0], I[1], I[2])) && fits(1, I[2]))) &&
+         fits(2, (I[2] + 1023) / 1024 * I[1]) && opt_fits(3, I[1]) && fits(4, I[1]);
+    break;
+  case RED_TALL_MATVEC:
+  case RED_TALL_MATVEC_F32:
+    ok = n_ip == 3 && I[2] <= TALL_MATVEC_MAX_COLS && fits(0, mat(I[0], I[1], I[2]), op == RED_TALL_MATVEC ? 8 : 4) && fits(1, I[2]) &&
+         opt_fits(2, I[1]) && fits(3, I[1]);
+    break;
+  case RED_COLVEC_DOT:
+  case RED_COLVEC_DOT_F32:
+    ok = n_ip == 3 && fits(0, mat(I[0], I[1], I[2]), op == RED_COLVEC_DOT ? 8 : 4) && fits(1, I[1]) && opt_fits(2, I[2]) && fits(3, I[2]);
+    break;
+  case RED_COLVEC_DOT_STRIDED:
+    ok = n_ip == 6 && fits(0, slabs(I[5], I[1], mat(I[0], I[2], I[3]))) && fits(1, slabs(I[5], I[4], I[2])) &&
+         opt_fits(2, slabs(I[5], I[4], I[3])) && fits(3, slabs(I[5], I[4], I[3]));
+    break;
+  case RED_COLVEC_DOT_BATCHED:
+    ok = n_ip == 5 && fits(0, slabs(I[4], I[1], mat(I[0], I[2], I[2]))) && fits(1, slabs(I[4], I[3], I[2])) && I[4] >= 1 &&
+         fits(2, I[4] * I[2]);
+    break;
+  case RED_SYMV_LOWER_BATCHED:
+    ok = n_ip == 5 && fits(0, slabs(I[4], I[1], mat(I[0], I[2], I[2]))) && fits(1, slabs(I[4], I[3], I[2])) &&
+         fits(2, slabs(I[4], I[3], I[2]));
+    break;
+  case RED_CONTRACT: {
+    const long long na = I[1], nb = I[2];
+    if (n_ip != 5 || na < 1 || nb < 1 || (I[3] && na != nb)) break;
+    const long long nx = has(1) ? groups_total(list(1, na + 1), na, LIM) : na, ny = has(3) ? groups_total(list(3, nb + 1), nb, LIM) : nb;
+    // (an empty K - every member list empty - is never addressed)
+    ok = nx >= 0 && ny >= 0 && (nx == 0 || ny == 0 || fits(0, mat(I[0], nx, ny))) && has(0) && opt_fits(2, nx) && opt_fits(4, ny) &&
+         fits(5, mat(I[4], na, nb));
+    break;
+  }
+  case RED_SYMMETRIZE:
+  case RED_ZERO_UPPER:
+  case RED_SET_IDENTITY: ok = n_ip == 2 && fits(0, mat(I[0], I[1], I[1])); break;
+  case RED_UPPER_TO_LOWER: ok = n_ip == 3 && fits(0, mat(I[0], I[2], I[2])) && fits(1, mat(I[1], I[2], I[2])) && bufs[0] != bufs[1]; break;
+  case RED_TRANSPOSE_BLOCKS:
+    ok = n_ip == 2 && I[0] >= 1 && I[1] >= 1 && fits(0, I[1] * I[0] * I[0]) && fits(1, I[1] * I[0] * I[0]) && bufs[0] != bufs[1];
+    break;
+  case RED_SET_IDENTITY_BATCHED: ok = n_ip == 4 && fits(0, slabs(I[3], I[1], mat(I[0], I[2], I[2]))); break;
+  case RED_NEGATE: ok = n_ip == 2 && fits(0, mat(I[0], I[1], I[1])) && opt_fits(1, I[1]); break;
+  case RED_NAN_SCAN_LOWER: ok = n_ip == 2 && fits(0, mat(I[0], I[1], I[1])) && fits(1, 1, 4); break;
+  case RED_COPY_LOWER:
+    ok = n_ip == 2 && I[0] % 2 == 0 && fits(0, mat(I[0], I[1], I[1])) && fits(1, mat(I[0], I[1], I[1])) && bufs[0] != bufs[1] &&
+         (!has(2) || fits(2, 1, 4));
+    break;
+  case RED_CONVERT_LOWER_F32: ok = n_ip == 2 && I[0] % 2 == 0 && fits(0, mat(I[0], I[1], I[1])) && fits(1, mat(I[0], I[1], I[1]), 4); break;
+  case RED_LOO: ok = n_ip == 1 && I[0] >= 1 && fits(0, I[0]) && fits(1, I[0]) && fits(2, I[0]) && fits(3, I[0]) && fits(4, I[0]); break;
+  case RED_GATHER_COLS: {
+    const long long *idx = n_ip == 6 ? list(1, I[1]) : nullptr;
+    ok = idx && I[1] >= 1 && I[2] < I[3] && fits(0, mat(I[0], I[3], I[5])) && fits(2, mat(I[4], I[3], I[1]));
+    for (long long a = 0; ok && a < I[1]; ++a) ok = idx[a] < I[5];
+    break;
+  }
+  case RED_GATHER_VEC: {
+    const long long *idx = n_ip == 2 ? list(1, I[0]) : nullptr;
+    ok = idx && I[0] >= 1 && I[1] >= 1 && fits(0, I[1]) && opt_fits(2, I[0]) && fits(3, I[0]);
+    for (long long a = 0; ok && a < I[0]; ++a) ok = idx[a] < I[1];
+    break;
+  }
+  case RED_PAD_COLUMNS: {
+    if (n_ip != 6 || I[1] < 1 || I[2] < 1 || I[5] > 1) break;
+    const long long total = groups_total(list(1, I[2] + 1), I[2], I[1]);
+    const long long compact = total > 0 ? mat(I[5] == 0 ? I[0] : I[4], I[3], total) : 0;
+    const long long padded = mat(I[5] == 0 ? I[4] : I[0], I[3], I[1] * I[2]);
+    ok = total >= 0 && compact >= 0 && has(I[5] == 0 ? 0 : 2) && fits(I[5] == 0 ? 0 : 2, compact) && fits(I[5] == 0 ? 2 : 0, padded);
+    break;
+  }
+  case RED_PAD_IDENTITY:
+    ok = n_ip == 4 && I[2] >= 1 && I[3] >= 1 && groups_total(list(1, I[3] + 1), I[3], I[2]) >= 0 &&
+         fits(0, slabs(I[3], I[1], mat(I[0], I[2], I[2])));
+    break;
+  case RED_COMPACT_BLOCKS: {
+    if (n_ip != 4 || I[2] < 1 || I[3] < 1) break;
+    const long long *off = list(1, I[3] + 1), *boff = list(2, I[3]);
+    ok = boff && groups_total(off, I[3], I[2]) >= 0 && fits(0, slabs(I[3], I[1], mat(I[0], I[2], I[2]))) && has(3);
+    for (long long g = 0; ok && g < I[3]; ++g) {
+      const long long sg = off[g + 1] - off[g];
+      ok = boff[g] >= 0 && boff[g] <= LIM && fits(3, boff[g] + sg * sg);
+    }
+    break;
+  }
+  default:  // RED_AXPBY
+    ok = n_ip == 1 && I[0] >= 1 && opt_fits(0, I[0]) && opt_fits(1, I[0]) && fits(2, I[0]);
+    break;
+  }
+  if (!ok) return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  DevBuf<char> dev[MAXB];
+  void *d[MAXB] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  int owner[MAXB];
+  for (int k = 0; k < n_bufs; ++k) {
+    owner[k] = k;
+    if (!bufs[k]) continue;
+    for (int j = 0; j < k; ++j)
+      if (bufs[j] == bufs[k]) { owner[k] = j; break; }
+    if (owner[k] != k) {
+      if (bytes[k] > bytes[owner[k]]) return AGP_ERR_INVALID_ARGUMENT;
+      d[k] = d[owner[k]];
+      continue;
+    }
+    AGP_HIP_CHECK(ctx, dev[k].alloc((size_t)bytes[k]));
+    AGP_HIP_CHECK(ctx, hipMemcpy(dev[k].p, bufs[k], (size_t)bytes[k], hipMemcpyHostToDevice));
+    d[k] = dev[k].p;
+  }
+  auto D = [&](int k) { return static_cast<double *>(d[k]); };
+  auto F = [&](int k) { return static_cast<float *>(d[k]); };
+  auto L = [&](int k) { return static_cast<long long *>(d[k]); };
+  auto N = [&](int k) { return static_cast<int *>(d[k]); };
+  switch (op) {
+  case RED_COLDOT: launch_coldot(s, D(0), I[0], D(1), I[1], I[2], I[3], D(2), d0, D(3)); break;
+  case RED_DOT: launch_dot(s, D(0), D(1), I[0], D(2)); break;
+  case RED_MATVEC: launch_matvec(s, D(0), I[0], I[1], I[2], D(1), D(2), d0, d1, D(3), D(4)); break;
+  case RED_TALL_MATVEC: launch_tall_matvec(s, D(0), I[0], I[1], I[2], D(1), d0, d1, D(2), D(3)); break;
+  case RED_TALL_MATVEC_F32: launch_tall_matvec_f32(s, F(0), I[0], I[1], I[2], D(1), d0, d1, D(2), D(3)); break;
+  case RED_COLVEC_DOT: launch_colvec_dot(s, D(0), I[0], I[1], I[2], D(1), d0, d1, D(2), D(3)); break;
+  case RED_COLVEC_DOT_F32: launch_colvec_dot_f32(s, F(0), I[0], I[1], I[2], D(1), d0, d1, D(2), D(3)); break;
+  case RED_COLVEC_DOT_STRIDED: launch_colvec_dot_strided(s, D(0), I[0], I[1], I[2], I[3], D(1), I[4], d0, d1, D(2), D(3), I[5]); break;
+  case RED_COLVEC_DOT_BATCHED: launch_colvec_dot_batched(s, D(0), I[0], I[1], I[2], D(1), I[3], I[4], D(2)); break;
+  case RED_SYMV_LOWER_BATCHED: launch_symv_lower_batched(s, D(0), I[0], I[1], I[2], D(1), I[3], D(2), I[4]); break;
+  case RED_CONTRACT: launch_contract_combinations(s, D(0), I[0], L(1), D(2), I[1], L(3), D(4), I[2], I[3] != 0, D(5), I[4]); break;
+  case RED_SYMMETRIZE: launch_symmetrize(s, D(0), I[0], I[1]); break;
+  case RED_ZERO_UPPER: launch_zero_upper(s, D(0), I[0], I[1]); break;
+  case RED_SET_IDENTITY: launch_set_identity(s, D(0), I[0], I[1]); break;
+  case RED_UPPER_TO_LOWER: launch_upper_to_lower(s, D(0), I[0], D(1), I[1], I[2]); break;
+  case RED_TRANSPOSE_BLOCKS: launch_transpose_blocks(s, D(0), D(1), I[0], I[1]); break;
+  case RED_SET_IDENTITY_BATCHED: launch_set_identity_batched(s, D(0), I[0], I[1], I[2], I[3]); break;
+  case RED_NEGATE: launch_negate(s, D(0), I[0], I[1], D(1)); break;
+  case RED_NAN_SCAN_LOWER: launch_nan_scan_lower(s, D(0), I[0], I[1], N(1)); break;
+  case RED_COPY_LOWER: launch_copy_lower(s, D(0), I[0], I[1], D(1), N(2)); break;
+  case RED_CONVERT_LOWER_F32: launch_convert_lower_f32(s, D(0), I[0], I[1], F(1)); break;
+  case RED_LOO: launch_loo(s, D(0), D(1), D(2), I[0], D(3), D(4)); break;
+  case RED_GATHER_COLS: launch_gather_cols(s, D(0), I[0], L(1), I[1], I[2], I[3], D(2), I[4]); break;
+  case RED_GATHER_VEC: launch_gather_vec(s, D(0), L(1), I[0], D(2), D(3)); break;
+  case RED_PAD_COLUMNS: launch_pad_columns(s, D(0), I[0], L(1), I[1], I[2], I[3], D(2), I[4], (int)I[5]); break;
+  case RED_PAD_IDENTITY: launch_pad_identity(s, D(0), I[0], I[1], L(1), I[2], I[3]); break;
+  case RED_COMPACT_BLOCKS: launch_compact_blocks(s, D(0), I[0], I[1], L(1), L(2), I[2], I[3], D(3)); break;
+  default: launch_axpby(s, I[0], d0, D(0), d1, D(1), D(2)); break;
+  }
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  for (int k = 0; k < n_bufs; ++k)
+    if (bufs[k] && owner[k] == k) AGP_HIP_CHECK(ctx, hipMemcpy(bufs[k], dev[k].p, (size_t)bytes[k], hipMemcpyDeviceToHost));
+  return AGP_OK;
+}
+
 AGP_DEBUG_API int agp_debug_comm_create_null(int nranks, int rank, agp_comm **out) {
   if (!out || nranks < 1 || rank < 0 || rank >= nranks) return AGP_ERR_INVALID_ARGUMENT;
   NullComm *c = new (std::nothrow) NullComm();

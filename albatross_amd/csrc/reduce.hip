@@ -293,7 +293,7 @@ template <typename T>  // T: the matrix's element type (double; float: the fp32 
 __global__ __launch_bounds__(256) void tall_matvec_kernel(const T *__restrict__ W, long long ld, long long rows, int ncols,
                                                           const double *__restrict__ x, double alpha, double beta,
                                                           const double *base, double *out) {
-  __shared__ double xs[2048], red[4][64];
+  __shared__ double xs[TALL_MATVEC_MAX_COLS], red[4][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int c = threadIdx.x; c < ncols; c += 256) xs[c] = x[c];
   __syncthreads();
@@ -334,13 +334,13 @@ __global__ __launch_bounds__(256) void tall_matvec_kernel(const T *__restrict__ 
 
 void launch_tall_matvec(hipStream_t s, const double *W, long long ld, long long rows, long long ncols, const double *x, double alpha,
                         double beta, const double *base, double *out) {
-  if (rows <= 0 || ncols <= 0 || ncols > 2048) return;
+  if (rows <= 0 || ncols <= 0 || ncols > TALL_MATVEC_MAX_COLS) return;  // (every caller checks its width: common.h)
   hipLaunchKernelGGL(tall_matvec_kernel<double>, dim3((unsigned)((rows + 63) / 64)), dim3(256), 0, s, W, ld, rows, (int)ncols, x, alpha, beta,
                      base, out);
 }
 void launch_tall_matvec_f32(hipStream_t s, const float *W, long long ld, long long rows, long long ncols, const double *x, double alpha,
                             double beta, const double *base, double *out) {
-  if (rows <= 0 || ncols <= 0 || ncols > 2048) return;
+  if (rows <= 0 || ncols <= 0 || ncols > TALL_MATVEC_MAX_COLS) return;  // (every caller checks its width: common.h)
   hipLaunchKernelGGL(tall_matvec_kernel<float>, dim3((unsigned)((rows + 63) / 64)), dim3(256), 0, s, W, ld, rows, (int)ncols, x, alpha, beta,
                      base, out);
 }
@@ -421,7 +421,10 @@ void launch_colvec_dot_f32(hipStream_t s, const float *W, long long ld, long lon
 }
 
 // L32 (lower triangle incl. diagonal, ld) = (float) L: the fp32 copy of a factor that preconditions the refinement of a
-// mixed-precision fit (api.hip: refine_information)
+// mixed-precision fit (api.hip: refine_information).  This kernel and copy_lower_kernel move ALIGNED PAIRS of rows
+// (2 i, 2 i + 1) from the even row at or above the diagonal: they rely on an EVEN leading dimension and 16-byte-aligned
+// matrices (factor_ld gives a multiple of 8), write the entry (j - 1, j) above the diagonal of every odd column j besides
+// the lower triangle, and nothing else.
 __global__ __launch_bounds__(256) void convert_lower_f32_kernel(const double *__restrict__ L, long long ld, long long n, float *__restrict__ L32) {
   const long long j = blockIdx.y;
   const long long i = j / 2 * 2 + ((long long)blockIdx.x * 256 + threadIdx.x) * 2;  // pairs from the even row at or above the diagonal

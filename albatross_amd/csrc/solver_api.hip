@@ -245,14 +245,20 @@ int agp_solver_update_information(agp_context *ctx, const agp_solver *bs, const 
   if (bs->ctx != ctx) return AGP_ERR_INVALID_ARGUMENT;
   AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const long long na = bs->na, nb = bs->nb;
+  // (launch_tall_matvec stages the vector in LDS and launches nothing beyond TALL_MATVEC_MAX_COLS columns; nb is the
+  // caller's block size, so a wider block goes through launch_matvec, which has no limit and needs its partial sums)
+  const bool tall = nb <= TALL_MATVEC_MAX_COLS;
+  const long long partial_elems = tall ? 0 : (nb + 1023) / 1024 * na;
   DevMem<double> v;
-  if (alloc_doubles(v, (size_t)(2 * na + nb)) != hipSuccess) { ctx->last_error = "agp_solver_update_information: allocation"; return AGP_ERR_HIP; }
+  if (alloc_doubles(v, (size_t)(2 * na + nb + partial_elems)) != hipSuccess) { ctx->last_error = "agp_solver_update_information: allocation"; return AGP_ERR_HIP; }
   double *info = v.get(), *res = v.get() + na;  // res: na + nb
+  double *partial = res + na + nb;
   int st = vector_to_device(ctx, information, na, location, info);
   if (st == AGP_OK) st = vector_to_device(ctx, si_delta, nb, location, res + na);
   if (st != AGP_OK) return st;
   // res[0 : na] = information - Ai_B (na x nb, ld = na) Si_delta
-  launch_tall_matvec(ctx->stream, bs->AiB, na, na, nb, res + na, -1.0, 1.0, info, res);
+  if (tall) launch_tall_matvec(ctx->stream, bs->AiB, na, na, nb, res + na, -1.0, 1.0, info, res);
+  else launch_matvec(ctx->stream, bs->AiB, na, na, nb, res + na, partial, -1.0, 1.0, info, res);
   return copy_out(ctx, res, na + nb, out, location);
 }
 

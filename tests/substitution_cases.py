@@ -297,6 +297,34 @@ def case_rhs(case, p=0):
     return rhs_matrix(case["n"], case["cols"], 17 + 31 * p + case["n"] + case["cols"], case["lower"])
 
 
+# ---- the wide vector sweeps and the mixed fit's preconditioner (csrc/api.hip; tests/test_reduce_kernels_gpu.py) ------
+# forward_solve_vec_wide, backward_solve_vec_wide, the wide branch of backward_solve_vec_any and mixed_precondition_apply:
+# one right-hand side through explicitly inverted BW x BW diagonal blocks, b = BW in the bound (512, and 1024 as the mixed
+# fit takes it from n = 8192 - here at n = 2048).  The variants that read the fp32 copy of the factor solve EXACTLY the
+# system of Lt = fp32_off_diagonal(L): the fp32 entries are widened and multiplied in fp64, so the bound holds against Lt
+# with nothing added, and no fp32 tolerance appears.
+WIDE_SWEEP_SHAPES = [(2048, 512), (2560, 512), (2048, 1024)]
+
+
+def fp32_off_diagonal(L, bw):
+    """L with everything below its bw-wide diagonal blocks replaced by its fp32 rounding (the matrix the sweeps with the
+    fp32 copy of a factor solve against)."""
+    n = L.shape[0]
+    T = np.tril(L).astype(np.float32).astype(np.float64)
+    for i in range(0, n, bw):
+        T[i:i + bw, i:i + bw] = np.tril(L[i:i + bw, i:i + bw])
+    return T
+
+
+def wide_sweep_cases():
+    """(n, BW, family) of the sweeps: every shape on both matrix families."""
+    return [dict(n=n, bw=bw, family=fam, id=f"{n}-bw{bw}-{fam}") for n, bw in WIDE_SWEEP_SHAPES for fam in ("rand", "gram")]
+
+
+def wide_sweep_rhs(case):
+    return rhs_matrix(case["n"], 1, 91 + case["n"] + case["bw"])
+
+
 def wide_problem(n, ncols):
     """The matrix and right-hand side of test_forward_solve_wide (tests/test_kernels_gpu.py)."""
     rng = np.random.default_rng(n + ncols)

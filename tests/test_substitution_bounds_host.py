@@ -38,6 +38,26 @@ def test_restated_wide_solve_meets_bound(n, ncols):
     assert ratio <= 1.0, ratio
 
 
+WIDE_SWEEPS = sc.wide_sweep_cases()
+
+
+@pytest.mark.parametrize("case", WIDE_SWEEPS, ids=[c["id"] for c in WIDE_SWEEPS])
+def test_restated_wide_sweep_meets_bound(case):
+    """The wide vector sweeps and the two sweeps of the mixed fit's preconditioner (tests/test_reduce_kernels_gpu.py):
+    b = 512 and 1024, against the fp64 factor and against the factor whose off-diagonal blocks are rounded to fp32; the
+    backward sweep of the preconditioner starts from the forward sweep's result."""
+    n, bw = case["n"], case["bw"]
+    L = np.linalg.cholesky(sc.spd_matrix(case["family"], n))
+    B = sc.wide_sweep_rhs(case)
+    for T in (L, sc.fp32_off_diagonal(L, bw)):
+        t2 = sc.blocked_substitution(T, B, bw, False)
+        fwd = sc.residual_ratio(T, t2, B, bw, False)
+        bwd = sc.residual_ratio(T, sc.blocked_substitution(T, B, bw, True), B, bw, True)
+        pre = sc.residual_ratio(T, sc.blocked_substitution(T, t2, bw, True), t2, bw, True)
+        print(f"wide sweeps {case['id']}: residual / bound forward {fwd:.3g}, backward {bwd:.3g}, preconditioner's backward {pre:.3g}")
+        assert max(fwd, bwd, pre) <= 1.0, (fwd, bwd, pre)
+
+
 @pytest.mark.parametrize("n,k0", sc.BACK_UPDATE_SHAPES)
 def test_restated_back_update_meets_bound(n, k0):
     """back_update_kernel is a product, z -= L[k0 : k0 + nbk, : k0]^T x: its bound is that of a dot product of length

@@ -77,6 +77,28 @@ def test_block_symmetric_matches_dense(ctx):
     assert np.abs(bs.solve(rhs) - want).max() <= 1e-10 * np.abs(want).max()
 
 
+@pytest.mark.parametrize("nb", [3, 2048, 2049, 2100])
+def test_update_information_beyond_the_tall_matvec_limit(ctx, nb):
+    """agp_solver_update_information: [information - Ai_B Si_delta ; Si_delta] with a block of nb new observations on both
+    sides of the 2048 columns launch_tall_matvec takes (csrc/common.h: TALL_MATVEC_MAX_COLS) - beyond it that launcher
+    launches nothing and the head of the result would be whatever the scratch held; the product goes through launch_matvec
+    there (2049: a last chunk of one column; 2100: three chunks).  The bar is test_block_symmetric_matches_dense's 1e-10,
+    relative to |information| + |Ai_B| |Si_delta| row by row: a dropped column misses it by eight orders of magnitude."""
+    na = 70
+    M = spd(na + nb, 11 + nb)
+    A, Bm, Cm = M[:na, :na], M[:na, na:], M[na:, na:]
+    AiB = np.linalg.solve(A, Bm)
+    bs = ab.BlockSymmetric(ab.DenseFactor(A, ctx), Bm, ab.DenseFactor(Cm - Bm.T @ AiB, ctx))
+    rng = np.random.default_rng(nb)
+    info, sd = rng.standard_normal(na), rng.standard_normal(nb)
+    got = bs.update_information(info, sd)
+    assert got.shape == (na + nb,) and np.array_equal(got[na:], sd)
+    scale = np.abs(info) + np.abs(AiB) @ np.abs(sd)
+    err = (np.abs(got[:na] - (info - AiB @ sd)) / scale).max()
+    print(f"update_information na={na} nb={nb}: error / scale {err:.3g}")
+    assert err <= 1e-10, err
+
+
 def test_device_compositions_nest_and_predict(ctx):
     """agp_solver_* (include/albatross_amd.h): BlockSymmetric over a BlockSymmetric over a pivoted L D L^T, ExplainedCovariance
     over a pivoted factor - solves against numpy - and the generic _predict_impl (agp_solver_predict, gp.hpp:305-366) of a fit
