@@ -24,6 +24,9 @@ from .sparse_gp import (FixedInducingPoints, SparseCrossValidation, SparseCrossV
 
 from .pivoted import GreedyVarianceInducingPoints, PivotedCholesky, pivoted_cholesky
 
+from .iterative import (MATVEC_MAX_RHS, IterativeFitModel, IterativeGPFit, IterativePrediction, NotConvergedError,
+                        gram_matvec)
+
 from .scores import chi_squared_cdf, crps_normal, draw_mvn, energy_score, variogram_score
 
 from .ransac import (RANSAC_RETURN_CODE_EXCEEDED_MAX_FAILED_CANDIDATES, RANSAC_RETURN_CODE_FAILURE, RANSAC_RETURN_CODE_INVALID,

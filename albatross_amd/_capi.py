@@ -15,6 +15,7 @@ AGP_ERR_HIP = 4
 AGP_ERR_COMM = 5
 AGP_ERR_UNSUPPORTED = 6
 AGP_ERR_NO_DEVICE = 7
+AGP_ERR_NOT_CONVERGED = 8
 
 OP_SQUARED_EXPONENTIAL = 1
 OP_EXPONENTIAL = 2
@@ -65,6 +66,11 @@ class KernelNode(C.Structure):
 
 class GradientSlot(C.Structure):
     _fields_ = [("node", C.c_int32), ("param", C.c_int32)]
+
+
+class IterativeOptions(C.Structure):
+    _fields_ = [("precond_rank", C.c_int64), ("precond_rel_tol", C.c_double), ("tolerance", C.c_double),
+                ("max_iterations", C.c_int)]
 
 
 class Features(C.Structure):
@@ -148,6 +154,15 @@ EXPORTS = [
     ("agp_ldlt_transpositions", C.c_int, [_P, _P]),
     ("agp_ldlt_download", C.c_int, [_P, _P, _P, C.c_int64]),
     ("agp_pivoted_cholesky", C.c_int, [_P, _P, C.POINTER(Features), C.c_int64, C.c_double, _P, _P, _P, C.c_int64, _P, C.c_int, _P]),
+    ("agp_gram_matvec", C.c_int, [_P, _P, C.POINTER(Features), _P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int]),
+    ("agp_iterative_fit_create", C.c_int, [_P, _P, C.POINTER(Features), _P, _P, _P, _PP, _P, _P, _P]),
+    ("agp_iterative_fit_destroy", None, [_P]),
+    ("agp_iterative_fit_size", C.c_int64, [_P]),
+    ("agp_iterative_fit_preconditioner_rank", C.c_int64, [_P]),
+    ("agp_iterative_fit_download_information", C.c_int, [_P, _P, _P]),
+    ("agp_iterative_solve", C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int, _P, _P]),
+    ("agp_iterative_predict_mean", C.c_int, [_P, _P, _P, C.POINTER(Features), _P, C.c_int]),
+    ("agp_iterative_predict_marginal", C.c_int, [_P, _P, _P, C.POINTER(Features), _P, _P, C.c_int]),
     ("agp_sparse_fit_create", C.c_int, [_P, _P, C.POINTER(Features), C.c_int64, _P, _P, _P, C.POINTER(Features), C.c_double, C.c_double, _PP, _P, _D]),
     ("agp_sparse_fit_create_sharded", C.c_int, [_P, _P, _P, C.POINTER(Features), C.c_int64, _P, _P, _P, C.POINTER(Features), C.c_double, C.c_double, _PP, _P, _D]),
     ("agp_sparse_fit_update", C.c_int, [_P, _P, _P, C.POINTER(Features), C.c_int64, _P, _P, _P, C.c_double, _PP, _P]),

@@ -166,6 +166,7 @@ const char *agp_status_string(int status) {
   case AGP_ERR_COMM: return "communication error";
   case AGP_ERR_UNSUPPORTED: return "unsupported";
   case AGP_ERR_NO_DEVICE: return "no HIP device";
+  case AGP_ERR_NOT_CONVERGED: return "iterative solve did not converge";
   default: return "unknown status";
   }
 }
@@ -351,7 +352,7 @@ int agp_set_profiling(agp_context *ctx, int enabled) {
 }
 
 int agp_last_stage_ms(const agp_context *c, int stage, double *ms) {
-  if (!c || !ms || stage < 0 || stage > 10) return AGP_ERR_INVALID_ARGUMENT;
+  if (!c || !ms || stage < 0 || stage > 12) return AGP_ERR_INVALID_ARGUMENT;
   *ms = c->stage_ms[stage];
   return AGP_OK;
 }

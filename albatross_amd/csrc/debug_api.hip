@@ -8,6 +8,7 @@
 #include "common.h"
 #include "api_internal.h"
 #include "mfma_f64.h"
+#include "gram_matvec.h"
 #include "shard_internal.h"
 #include "pub.h"
 #include "trsm_kernel.h"
@@ -1534,6 +1535,23 @@ AGP_DEBUG_API int agp_debug_predict_mean(agp_context *ctx, const agp_kernel *k, 
   AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   AGP_HIP_CHECK(ctx, hipGetLastError());
   AGP_HIP_CHECK(ctx, hipMemcpy(mean_host, d.p + n, sizeof(double) * (m + 2), hipMemcpyDeviceToHost));
+  return AGP_OK;
+}
+
+// What agp_gram_matvec runs for these features (gram_matvec.hip: the launcher switches on the same gram_matvec_plan call):
+// plan[0] the evaluator (0 radial fast path, 1 sum of products, 2 interpreter), plan[1] the column slices S, plan[2] the
+// columns of a slice, plan[3] the rows of a workgroup, plan[4] the columns of an LDS tile, plan[5] the right-hand sides of
+// the first chunk's kernel for `nrhs` of them (1, 4 or 16).  Launches nothing (tests/test_gram_matvec_gpu.py).
+AGP_DEBUG_API int agp_debug_gram_matvec_plan(agp_context *ctx, const agp_kernel *k, const agp_features *x, int64_t nrhs, int64_t *plan) {
+  if (!ctx || !k || !x || !plan || nrhs < 1) return AGP_ERR_INVALID_ARGUMENT;
+  const int st = validate_features(x);
+  if (st != AGP_OK) return st;
+  GramSopScope sop_switch(ctx);
+  FeatView v{};
+  v.n = x->n; v.dim = x->dim; v.nsc = x->n_scale_columns; v.meas = x->is_measurement;
+  const MvPlan p = gram_matvec_plan(&k->prog, v);
+  plan[0] = p.path; plan[1] = p.slices; plan[2] = p.cols_per_slice;
+  plan[3] = MV_ROWS; plan[4] = MV_COLS; plan[5] = gram_matvec_chunk_width(nrhs);
   return AGP_OK;
 }
 

@@ -1,0 +1,538 @@
+// iterative.hip — the exact Gaussian-process fit that never forms K: preconditioned conjugate gradients around the fused
+// product of gram_matvec.hip, preconditioned by the greedy pivoted Cholesky factor of pivoted_chol.hip
+// (agp_iterative_fit_create, agp_iterative_solve, agp_iterative_predict_*; include/albatross_amd.h).
+//
+//   A = k(x, x) + diag(y_var);  A ~ L L^T + (A - L L^T), L = n x m from the pivoted Cholesky of A (m <= precond_rank);
+//   P = L L^T + delta I,  delta = max(tr(A - L L^T) / (n - m), 1e-8 max_i A_ii)  (m = n: the floor alone);
+//   P^-1 r = (r - L (delta I + L^T L)^-1 L^T r) / delta  (Woodbury): L^T L once on the fp64 GEMM, its m x m matrix factored
+//   by the dense LL^T; per iteration two skinny products (pcg_lt_r_kernel, pcg_precond_kernel) and the two substitutions.
+//
+// The right-hand sides of a chunk (<= 16) run INDEPENDENT recurrences that share each launch - this is not block CG.  All
+// per-column scalars (alpha, beta, r^T z, p^T A p, the norms, the stop marks) live in one control block on the device;
+// every reduction is one workgroup per column with a fixed order (no float atomics), and its last thread derives the
+// scalars.  A column stops when ||r|| <= tolerance ||b||; from then on every kernel skips it, so its vectors keep their
+// bits whatever is queued behind.  The host looks at the control block once per PCG_LOOK iterations with the next
+// PCG_LOOK queued behind (the pattern of agp_pivoted_cholesky); once no column is active, or an error is marked, every
+// queued kernel returns at its first instruction.
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <vector>
+#include "api_internal.h"
+#include "gram_matvec.h"
+#include "trace.h"
+
+int pivoted_cholesky_impl(agp_context *c, const agp_kernel *k, const agp_features *x, const double *diag_dev, int64_t max_rank,
+                          double rel_tol, int64_t *pivots, int64_t *rank, double *L, int64_t ldl, double *residual_diag, int location,
+                          double *trace_residual, double *d0_out);  // pivoted_chol.hip
+
+namespace agp {
+
+constexpr int PCG_LOOK = 8;             // iterations between two looks of the host
+constexpr int PCG_COLS = MV_MAX_RHS;    // right-hand sides of a chunk
+constexpr int PCG_DOT_THREADS = 1024;
+constexpr int PCG_ERROR = 1 << 20;      // subtracted from `active` by the kernel that marks an error: nothing runs after
+
+struct PcgCtrl {
+  int active;              // columns still iterating; <= 0: every kernel returns at once (also gram_matvec's `go` word)
+  int npd;                 // p^T A p <= 0 in an active column
+  int nan;                 // a NaN in a reduction or in an entry of A
+  int pad;
+  int stopped[PCG_COLS];
+  int iters[PCG_COLS];     // iterations carried out by the column
+  double bb[PCG_COLS], rz[2][PCG_COLS], alpha[PCG_COLS], beta[PCG_COLS], resid[PCG_COLS];
+};
+
+enum { DOT_BB = 0, DOT_RZ = 1, DOT_PQ = 2, DOT_RR = 3 };
+
+// one workgroup per column c: s = sum_i A[i, c] B[i, c] in a fixed order, then the scalars that follow from it
+template <int MODE>
+__global__ __launch_bounds__(PCG_DOT_THREADS) void pcg_dot_kernel(PcgCtrl *ctrl, const double *A, const double *B, long long ld,
+                                                                  long long n, int k, double tol) {
+  if (MODE != DOT_BB && ctrl->active <= 0) return;
+  const int c = blockIdx.x;
+  if (MODE != DOT_BB && ctrl->stopped[c]) return;
+  __shared__ double red[PCG_DOT_THREADS / 64];
+  const double *a = A + (long long)c * ld, *b = B + (long long)c * ld;
+  double acc = 0.;
+  for (long long i = threadIdx.x; i < n; i += PCG_DOT_THREADS) acc += a[i] * b[i];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  double s = 0.;
+  for (int w = 0; w < PCG_DOT_THREADS / 64; ++w) s += red[w];
+  if (s != s) {
+    ctrl->nan = 1;
+    atomicSub(&ctrl->active, PCG_ERROR);
+    return;
+  }
+  if (MODE == DOT_BB) {
+    ctrl->bb[c] = s;
+    ctrl->resid[c] = s > 0. ? 1. : 0.;
+    if (s > 0.) atomicAdd(&ctrl->active, 1);
+    else ctrl->stopped[c] = 1;  // a zero right-hand side: the solution is zero, no iteration
+  } else if (MODE == DOT_RZ) {
+    ctrl->rz[k & 1][c] = s;
+    ctrl->beta[c] = k == 0 ? 0. : s / ctrl->rz[(k - 1) & 1][c];
+  } else if (MODE == DOT_PQ) {
+    if (s <= 0.) {
+      ctrl->npd = 1;
+      atomicSub(&ctrl->active, PCG_ERROR);
+      return;
+    }
+    ctrl->alpha[c] = ctrl->rz[k & 1][c] / s;
+  } else {
+    const double bb = ctrl->bb[c];
+    ctrl->iters[c] = k + 1;
+    ctrl->resid[c] = sqrt(s) / sqrt(bb);
+    if (sqrt(s) <= tol * sqrt(bb)) {
+      ctrl->stopped[c] = 1;
+      atomicSub(&ctrl->active, 1);
+    }
+  }
+}
+
+// T1[j, c] = sum_i L[i, j] R[i, c]: workgroup j reads column j of L once for the t right-hand sides
+__global__ __launch_bounds__(256) void pcg_lt_r_kernel(const PcgCtrl *ctrl, const double *L, long long ldl, long long n, const double *R,
+                                                       long long ldr, int t, double *T1, long long ldt) {
+  if (ctrl->active <= 0) return;
+  __shared__ double red[4][PCG_COLS];
+  const long long j = blockIdx.x;
+  const double *col = L + j * ldl;
+  double acc[PCG_COLS];
+#pragma unroll
+  for (int c = 0; c < PCG_COLS; ++c) acc[c] = 0.;
+  for (long long i = threadIdx.x; i < n; i += 256) {
+    const double l = col[i];
+#pragma unroll
+    for (int c = 0; c < PCG_COLS; ++c)
+      if (c < t) acc[c] += l * R[(long long)c * ldr + i];
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int c = 0; c < PCG_COLS; ++c) {
+    double r = acc[c];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) r += __shfl_down(r, off, 64);
+    if (lane == 0) red[wave][c] = r;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < t) T1[(long long)threadIdx.x * ldt + j] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
+// Z = (R - L U) / delta, a thread per row, the sum over j = 0, 1, ... (m = 0: Z = R / delta)
+__global__ __launch_bounds__(256) void pcg_precond_kernel(const PcgCtrl *ctrl, const double *L, long long ldl, long long n, long long m,
+                                                          const double *U, long long ldu, const double *R, double *Z, long long ld, int t,
+                                                          double delta) {
+  if (ctrl->active <= 0) return;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double acc[PCG_COLS];
+#pragma unroll
+  for (int c = 0; c < PCG_COLS; ++c) acc[c] = 0.;
+  for (long long j = 0; j < m; ++j) {
+    const double l = L[j * ldl + i];
+#pragma unroll
+    for (int c = 0; c < PCG_COLS; ++c)
+      if (c < t) acc[c] += l * U[(long long)c * ldu + j];
+  }
+#pragma unroll
+  for (int c = 0; c < PCG_COLS; ++c)
+    if (c < t && !ctrl->stopped[c]) Z[(long long)c * ld + i] = (R[(long long)c * ld + i] - acc[c]) / delta;
+}
+
+// P = Z + beta P (the first iteration: P = Z); blockIdx.y = column
+__global__ __launch_bounds__(256) void pcg_p_kernel(const PcgCtrl *ctrl, const double *Z, double *P, long long ld, long long n, int first) {
+  if (ctrl->active <= 0) return;
+  const int c = blockIdx.y;
+  if (ctrl->stopped[c]) return;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const long long e = (long long)c * ld + i;
+  P[e] = first ? Z[e] : Z[e] + ctrl->beta[c] * P[e];
+}
+
+// X += alpha P, R -= alpha Q; blockIdx.y = column
+__global__ __launch_bounds__(256) void pcg_xr_kernel(const PcgCtrl *ctrl, double *X, long long ldx, double *R, const double *P, const double *Q,
+                                                     long long ld, long long n) {
+  if (ctrl->active <= 0) return;
+  const int c = blockIdx.y;
+  if (ctrl->stopped[c]) return;
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const double alpha = ctrl->alpha[c];
+  const long long e = (long long)c * ld + i;
+  X[(long long)c * ldx + i] += alpha * P[e];
+  R[e] -= alpha * Q[e];
+}
+
+// stats[0] = max, [1] = min, [2] = sum (fixed order), [3] = 1 on a NaN, of d_i + yvar_i
+__global__ __launch_bounds__(1024) void pcg_diag_stats_kernel(const double *d, const double *yvar, long long n, double *stats) {
+  __shared__ double smax[1024], smin[1024], ssum[1024];
+  __shared__ int snan;
+  if (threadIdx.x == 0) snan = 0;
+  __syncthreads();
+  double mx = -INFINITY, mn = INFINITY, sm = 0.;
+  bool bad = false;
+  for (long long i = threadIdx.x; i < n; i += 1024) {
+    const double v = d[i] + (yvar ? yvar[i] : 0.);
+    bad = bad || v != v;
+    mx = fmax(mx, v);
+    mn = fmin(mn, v);
+    sm += v;
+  }
+  if (bad) atomicOr(&snan, 1);
+  smax[threadIdx.x] = mx; smin[threadIdx.x] = mn; ssum[threadIdx.x] = sm;
+  __syncthreads();
+  for (int w = 512; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) {
+      smax[threadIdx.x] = fmax(smax[threadIdx.x], smax[threadIdx.x + w]);
+      smin[threadIdx.x] = fmin(smin[threadIdx.x], smin[threadIdx.x + w]);
+      ssum[threadIdx.x] += ssum[threadIdx.x + w];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { stats[0] = smax[0]; stats[1] = smin[0]; stats[2] = ssum[0]; stats[3] = snan ? 1. : 0.; }
+}
+
+// M = delta I - C (C = -L^T L from the GEMM), m x m
+__global__ __launch_bounds__(256) void pcg_shift_kernel(double *C, long long ldc, long long m, double delta) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x, j = blockIdx.y;
+  if (i >= m) return;
+  C[j * ldc + i] = (i == j ? delta : 0.) - C[j * ldc + i];
+}
+
+// var_j = prior_j - sum_i Kc[i, j] S[i, j]; one workgroup per test point of the slice
+__global__ __launch_bounds__(256) void pcg_variance_kernel(const double *Kc, const double *S, long long ld, long long n, const double *prior,
+                                                           double *var) {
+  __shared__ double red[4];
+  const long long j = blockIdx.x;
+  double acc = 0.;
+  for (long long i = threadIdx.x; i < n; i += 256) acc += Kc[j * ld + i] * S[j * ld + i];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) var[j] = prior[j] - ((red[0] + red[1]) + (red[2] + red[3]));
+}
+
+}  // namespace agp
+
+using namespace agp;
+
+struct agp_iterative_fit {
+  agp_context *ctx = nullptr;
+  int64_t n = 0, rank = 0;
+  agp_kernel_full kernel;              // the covariance function of the fit (host copy)
+  DevMem<DevProgram> dprog;            // ... and its device copy
+  DeviceFeatures train;                // owned copy of the features, as the predictions see them (not measurements)
+  // ... and as the fit sees them: as_measurements(features), gp.hpp:288 - what agp_fit_create builds its covariance of
+  FeatView fit_view() const {
+    FeatView v = train.v;
+    v.meas = 1;
+    return v;
+  }
+  DevMem<double> yvar, alpha, L;       // y_var (or empty), K^-1 y, the n x rank Nystrom factor (ldl)
+  long long ldl = 0;
+  agp_fit *mfac = nullptr;             // LL^T of delta I + L^T L (rank x rank), or nullptr for rank 0
+  double delta = 0.;
+  double tolerance = 0.;
+  int max_iterations = 0;
+  ~agp_iterative_fit() {
+    if (mfac) agp_fit_destroy(mfac);
+  }
+};
+
+namespace {
+
+struct IterDestroy {
+  void operator()(agp_iterative_fit *f) const { delete f; }
+};
+
+// X (n x nrhs, ldx, device) = A^-1 B (n x nrhs, ldb, device) by PCG, chunk by chunk; iterations / residual: nrhs host values
+int pcg_solve(agp_context_impl *ctx, const agp_iterative_fit *f, const double *B, long long ldb, long long nrhs, double *X, long long ldx,
+              int *iterations, double *residual) {
+  hipStream_t s = ctx->stream;
+  const long long n = f->n, m = f->rank, ld = round_up(n, 2), ldt = round_up(m > 0 ? m : 1, 2);
+  const int tmax = (int)(nrhs < PCG_COLS ? nrhs : PCG_COLS);
+  // scratch: control block | r z p q (n x t each) | t1 (m x t) | the matvec's partial sums
+  const size_t ctrl_elems = (sizeof(PcgCtrl) + sizeof(double) - 1) / sizeof(double);
+  const size_t vec = (size_t)ld * (size_t)tmax;
+  DevMem<double> ws;
+  AGP_HIP_CHECK(ctx, alloc_doubles(ws, ctrl_elems + 4 * vec + (size_t)ldt * (size_t)tmax + gram_matvec_ws_elems(n)));
+  PcgCtrl *ctrl = reinterpret_cast<PcgCtrl *>(ws.get());
+  double *R = ws.get() + ctrl_elems, *Z = R + vec, *P = Z + vec, *Q = P + vec, *T1 = Q + vec, *mvws = T1 + (size_t)ldt * (size_t)tmax;
+  PcgCtrl *h_look = static_cast<PcgCtrl *>(host_stage(ctx, 3 * sizeof(PcgCtrl)));
+  if (!h_look) { ctx->last_error = "agp_iterative: no pinned staging memory"; return AGP_ERR_HIP; }
+  PcgCtrl *h_final = h_look + 2;
+  hipEvent_t ev[2] = {ctx->ev_a, ctx->ev_b};
+  const unsigned rows = (unsigned)((n + 255) / 256);
+  const FeatView xm = f->fit_view();
+  int status = AGP_OK;
+  for (long long c0 = 0; c0 < nrhs && status == AGP_OK; c0 += PCG_COLS) {
+    const int t = (int)(nrhs - c0 < PCG_COLS ? nrhs - c0 : PCG_COLS);
+    double *Xc = X + c0 * ldx;
+    AGP_HIP_CHECK(ctx, hipMemsetAsync(ctrl, 0, sizeof(PcgCtrl), s));
+    AGP_HIP_CHECK(ctx, hipMemsetAsync(Z, 0, sizeof(double) * 3 * vec, s));  // (a zero right-hand side never writes its z, p, q)
+    AGP_HIP_CHECK(ctx, hipMemset2DAsync(Xc, sizeof(double) * (size_t)ldx, 0, sizeof(double) * (size_t)n, (size_t)t, s));
+    AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(R, sizeof(double) * (size_t)ld, B + c0 * ldb, sizeof(double) * (size_t)ldb, sizeof(double) * (size_t)n,
+                                        (size_t)t, hipMemcpyDeviceToDevice, s));
+    hipLaunchKernelGGL(pcg_dot_kernel<DOT_BB>, dim3(t), dim3(PCG_DOT_THREADS), 0, s, ctrl, R, R, ld, n, 0, f->tolerance);
+    long long blocks = 0;
+    bool done = false;
+    for (int k0 = 0; k0 < f->max_iterations && !done; k0 += PCG_LOOK, ++blocks) {
+      const int k1 = k0 + PCG_LOOK < f->max_iterations ? k0 + PCG_LOOK : f->max_iterations;
+      for (int k = k0; k < k1; ++k) {
+        if (m > 0) {
+          hipLaunchKernelGGL(pcg_lt_r_kernel, dim3((unsigned)m), dim3(256), 0, s, ctrl, f->L.get(), f->ldl, n, R, ld, t, T1, ldt);
+          forward_solve_mat(s, f->mfac->A, m, f->mfac->lda, f->mfac->invd, T1, t, ldt);
+          backward_solve_mat(s, f->mfac->A, m, f->mfac->lda, f->mfac->invd, T1, t, ldt);
+        }
+        hipLaunchKernelGGL(pcg_precond_kernel, dim3(rows), dim3(256), 0, s, ctrl, f->L.get(), f->ldl, n, m, T1, ldt, R, Z, ld, t, f->delta);
+        hipLaunchKernelGGL(pcg_dot_kernel<DOT_RZ>, dim3(t), dim3(PCG_DOT_THREADS), 0, s, ctrl, R, Z, ld, n, k, f->tolerance);
+        hipLaunchKernelGGL(pcg_p_kernel, dim3(rows, t), dim3(256), 0, s, ctrl, Z, P, ld, n, k == 0 ? 1 : 0);
+        launch_gram_matvec(s, f->dprog.get(), &f->kernel.prog, xm, f->yvar.get(), P, ld, t, Q, ld, mvws, &ctrl->nan, &ctrl->active);
+        hipLaunchKernelGGL(pcg_dot_kernel<DOT_PQ>, dim3(t), dim3(PCG_DOT_THREADS), 0, s, ctrl, P, Q, ld, n, k, f->tolerance);
+        hipLaunchKernelGGL(pcg_xr_kernel, dim3(rows, t), dim3(256), 0, s, ctrl, Xc, ldx, R, P, Q, ld, n);
+        hipLaunchKernelGGL(pcg_dot_kernel<DOT_RR>, dim3(t), dim3(PCG_DOT_THREADS), 0, s, ctrl, R, R, ld, n, k, f->tolerance);
+      }
+      if (k1 == f->max_iterations) break;
+      AGP_HIP_CHECK(ctx, hipMemcpyAsync(&h_look[blocks & 1], ctrl, sizeof(PcgCtrl), hipMemcpyDeviceToHost, s));
+      AGP_HIP_CHECK(ctx, hipEventRecord(ev[blocks & 1], s));
+      if (blocks >= 1) {
+        AGP_HIP_CHECK(ctx, hipEventSynchronize(ev[(blocks - 1) & 1]));
+        done = h_look[(blocks - 1) & 1].active <= 0;
+      }
+    }
+    AGP_HIP_CHECK(ctx, hipMemcpyAsync(h_final, ctrl, sizeof(PcgCtrl), hipMemcpyDeviceToHost, s));
+    AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+    AGP_HIP_CHECK(ctx, hipGetLastError());
+    for (int c = 0; c < t; ++c) {
+      if (iterations) iterations[c0 + c] = h_final->iters[c];
+      if (residual) residual[c0 + c] = h_final->resid[c];
+    }
+    if (h_final->nan) status = AGP_ERR_NAN_INPUT;
+    else if (h_final->npd) status = AGP_ERR_NOT_POSITIVE_DEFINITE;
+    else if (h_final->active > 0) status = AGP_ERR_NOT_CONVERGED;
+  }
+  return status;
+}
+
+// diag(A) statistics, the pivoted Cholesky factor, delta and the factor of delta I + L^T L
+int build_preconditioner(agp_context_impl *ctx, agp_iterative_fit *f, const agp_kernel *k, long long want_rank, double rel_tol) {
+  hipStream_t s = ctx->stream;
+  const long long n = f->n;
+  DevMem<double> ws;
+  AGP_HIP_CHECK(ctx, alloc_doubles(ws, (size_t)n + 4));
+  double *stats_dev = ws.get() + n;
+  launch_gram_diagonal(s, f->dprog.get(), f->fit_view(), ws.get());
+  hipLaunchKernelGGL(pcg_diag_stats_kernel, dim3(1), dim3(1024), 0, s, ws.get(), f->yvar.get(), n, stats_dev);
+  double stats[4];
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(stats, stats_dev, sizeof(stats), hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  if (stats[3] != 0.) return AGP_ERR_NAN_INPUT;
+  if (!(stats[1] > 0.)) return AGP_ERR_NOT_POSITIVE_DEFINITE;
+  const double d0 = stats[0];
+  double trace = stats[2];
+  long long rank = 0;
+  if (want_rank > 0) {
+    f->ldl = round_up(n, 2);
+    AGP_HIP_CHECK(ctx, f->L.alloc_cached(sizeof(double) * (size_t)f->ldl * (size_t)want_rank));
+    agp_features xs{};
+    xs.n = n; xs.dim = f->train.v.dim; xs.n_scale_columns = f->train.v.nsc; xs.coords = f->train.v.coords;
+    xs.eq_id = reinterpret_cast<const int64_t *>(f->train.v.ids); xs.scales = f->train.v.scales;
+    xs.is_measurement = 1; xs.location = AGP_DEVICE;
+    std::vector<int64_t> pivots((size_t)want_rank);
+    int64_t r = 0;
+    const int st = pivoted_cholesky_impl(ctx, k, &xs, f->yvar.get(), want_rank, rel_tol, pivots.data(), &r, f->L.get(), f->ldl, nullptr,
+                                         AGP_DEVICE, &trace, nullptr);
+    if (st != AGP_OK) return st;
+    rank = r;
+  }
+  f->rank = rank;
+  const double floor_delta = 1e-8 * d0;
+  f->delta = rank < n ? std::fmax(trace / (double)(n - rank), floor_delta) : floor_delta;
+  if (rank == 0) { f->L.reset(); return AGP_OK; }
+  // M = delta I + L^T L: C = 0 - L^T L on the fp64 GEMM (both operands read transposed), then the shift
+  const long long ldm = round_up(rank, 2);
+  DevMem<double> M;
+  AGP_HIP_CHECK(ctx, M.alloc_cached(sizeof(double) * (size_t)ldm * (size_t)rank));
+  AGP_HIP_CHECK(ctx, hipMemsetAsync(M.get(), 0, sizeof(double) * (size_t)ldm * (size_t)rank, s));
+  launch_gemm_nt_sub(s, M.get(), ldm, f->L.get(), f->ldl, true, f->L.get(), f->ldl, true, rank, rank, n, false);
+  hipLaunchKernelGGL(pcg_shift_kernel, dim3((unsigned)((rank + 255) / 256), (unsigned)rank), dim3(256), 0, s, M.get(), ldm, rank, f->delta);
+  return agp_factor_create(ctx, M.get(), rank, ldm, 0, AGP_DEVICE, &f->mfac);
+}
+
+int check_fit(const agp_context *ctx, const agp_iterative_fit *fit) {
+  return (ctx && fit && fit->ctx == ctx) ? AGP_OK : AGP_ERR_INVALID_ARGUMENT;
+}
+
+}  // namespace
+
+extern "C" {
+
+int agp_iterative_fit_create(agp_context *c, const agp_kernel *k, const agp_features *x, const double *y, const double *y_var,
+                             const agp_iterative_options *opt, agp_iterative_fit **out, double *information, int *iterations,
+                             double *residual) {
+  if (!c || !k || !x || !y || !opt || !out) return AGP_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+  agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
+  int st = validate_features(x);
+  if (st != AGP_OK) return st;
+  const long long n = x->n;
+  if (n < 1 || opt->precond_rank < 0 || !(opt->precond_rel_tol >= 0.) || !(opt->tolerance > 0.) || opt->max_iterations < 1)
+    return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  if (iterations) *iterations = 0;
+  if (residual) *residual = 0.;
+  std::unique_ptr<agp_iterative_fit, IterDestroy> f(new (std::nothrow) agp_iterative_fit());
+  if (!f) return AGP_ERR_INVALID_ARGUMENT;
+  f->ctx = ctx;
+  f->n = n;
+  f->tolerance = opt->tolerance;
+  f->max_iterations = opt->max_iterations;
+  f->kernel.prog = k->prog;
+  f->kernel.uid = 0;
+  AGP_HIP_CHECK(ctx, f->dprog.alloc_plain(sizeof(DevProgram)));
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(f->dprog.get(), &k->prog, sizeof(DevProgram), hipMemcpyHostToDevice, s));
+  if ((st = to_device(ctx, x, true, &f->train)) != AGP_OK) return st;
+  f->train.v.meas = 0;
+  const long long ld = round_up(n, 2);
+  if (y_var) {
+    AGP_HIP_CHECK(ctx, f->yvar.alloc_cached(sizeof(double) * (size_t)ld));
+    if ((st = vector_to_device(ctx, y_var, n, x->location, f->yvar.get())) != AGP_OK) return st;
+  }
+  AGP_HIP_CHECK(ctx, f->alpha.alloc_cached(sizeof(double) * (size_t)ld));
+  DevMem<double> yd;
+  AGP_HIP_CHECK(ctx, alloc_doubles(yd, (size_t)ld));
+  if ((st = vector_to_device(ctx, y, n, x->location, yd.get())) != AGP_OK) return st;
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));  // (the program's pageable source)
+  const bool prof = ctx->profiling;
+  if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[0], s));
+  {
+    TraceRange tr("agp: iterative fit, preconditioner (pivoted Cholesky, L^T L, its factor)");
+    const long long want = opt->precond_rank < n ? opt->precond_rank : n;
+    if ((st = build_preconditioner(ctx, f.get(), k, want, opt->precond_rel_tol)) != AGP_OK) return st;
+  }
+  if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[1], s));
+  int its = 0;
+  double res = 0.;
+  {
+    TraceRange tr("agp: iterative fit, preconditioned conjugate gradients");
+    st = pcg_solve(ctx, f.get(), yd.get(), ld, 1, f->alpha.get(), ld, &its, &res);
+  }
+  if (prof) {
+    AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[2], s));
+    AGP_HIP_CHECK(ctx, hipEventSynchronize(ctx->stage_ev[2]));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ctx->stage_ev[0], ctx->stage_ev[1]) == hipSuccess) ctx->stage_ms[11] = ms;
+    if (hipEventElapsedTime(&ms, ctx->stage_ev[1], ctx->stage_ev[2]) == hipSuccess) ctx->stage_ms[12] = ms;
+  }
+  if (iterations) *iterations = its;
+  if (residual) *residual = res;
+  if (st != AGP_OK) return st;
+  if (information && (st = copy_out(ctx, f->alpha.get(), n, information, AGP_HOST)) != AGP_OK) return st;
+  *out = f.release();
+  return AGP_OK;
+}
+
+void agp_iterative_fit_destroy(agp_iterative_fit *fit) { delete fit; }
+
+int64_t agp_iterative_fit_size(const agp_iterative_fit *fit) { return fit ? fit->n : 0; }
+
+int64_t agp_iterative_fit_preconditioner_rank(const agp_iterative_fit *fit) { return fit ? fit->rank : 0; }
+
+int agp_iterative_fit_download_information(agp_context *ctx, const agp_iterative_fit *fit, double *information) {
+  if (check_fit(ctx, fit) != AGP_OK || !information) return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  return copy_out(ctx, fit->alpha.get(), fit->n, information, AGP_HOST);
+}
+
+int agp_iterative_solve(agp_context *c, const agp_iterative_fit *fit, const double *rhs, int64_t ldr, int64_t nrhs, double *out,
+                        int64_t ldo, int location, int *iterations, double *residual) {
+  if (check_fit(c, fit) != AGP_OK || !rhs || !out || nrhs < 1 || ldr < fit->n || ldo < fit->n ||
+      (location != AGP_HOST && location != AGP_DEVICE))
+    return AGP_ERR_INVALID_ARGUMENT;
+  agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const long long n = fit->n, ld = round_up(n, 2);
+  if (location == AGP_DEVICE) return pcg_solve(ctx, fit, rhs, ldr, nrhs, out, ldo, iterations, residual);
+  DevMem<double> stage;
+  AGP_HIP_CHECK(ctx, alloc_doubles(stage, 2 * (size_t)ld * (size_t)nrhs));
+  double *Bd = stage.get(), *Xd = Bd + (size_t)ld * (size_t)nrhs;
+  AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(Bd, sizeof(double) * (size_t)ld, rhs, sizeof(double) * (size_t)ldr, sizeof(double) * (size_t)n,
+                                      (size_t)nrhs, hipMemcpyHostToDevice, s));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  const int st = pcg_solve(ctx, fit, Bd, ld, nrhs, Xd, ld, iterations, residual);
+  if (st != AGP_OK) return st;
+  AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(out, sizeof(double) * (size_t)ldo, Xd, sizeof(double) * (size_t)ld, sizeof(double) * (size_t)n,
+                                      (size_t)nrhs, hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  return AGP_OK;
+}
+
+int agp_iterative_predict_mean(agp_context *c, const agp_kernel *k, const agp_iterative_fit *fit, const agp_features *xs, double *mean,
+                               int location) {
+  if (check_fit(c, fit) != AGP_OK || !k || !xs || !mean || (location != AGP_HOST && location != AGP_DEVICE))
+    return AGP_ERR_INVALID_ARGUMENT;
+  agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
+  int st = validate_features(xs);
+  if (st != AGP_OK) return st;
+  if (xs->dim != fit->train.v.dim) return AGP_ERR_INVALID_ARGUMENT;
+  const long long M = xs->n;
+  if (M == 0) return AGP_OK;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const DevProgram *dprog = nullptr;
+  if ((st = device_program(ctx, k, &dprog)) != AGP_OK) return st;
+  DeviceFeatures dxs;
+  if ((st = to_device(ctx, xs, false, &dxs)) != AGP_OK) return st;
+  DevMem<double> md;
+  double *dst = mean;
+  if (location == AGP_HOST) {
+    AGP_HIP_CHECK(ctx, alloc_doubles(md, (size_t)M));
+    dst = md.get();
+  }
+  launch_predict_mean(ctx->stream, dprog, fit->train.v, dxs.v, fit->alpha.get(), dst, &k->prog);
+  if (location == AGP_HOST) return copy_out(ctx, dst, M, mean, AGP_HOST);
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  return AGP_OK;
+}
+
+int agp_iterative_predict_marginal(agp_context *c, const agp_kernel *k, const agp_iterative_fit *fit, const agp_features *xs,
+                                   double *mean, double *variance, int location) {
+  if (!variance) return AGP_ERR_INVALID_ARGUMENT;
+  int st = agp_iterative_predict_mean(c, k, fit, xs, mean, location);
+  if (st != AGP_OK) return st;
+  agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
+  const long long M = xs->n, n = fit->n, ld = round_up(n, 2);
+  if (M == 0) return AGP_OK;
+  hipStream_t s = ctx->stream;
+  const DevProgram *dprog = nullptr;
+  if ((st = device_program(ctx, k, &dprog)) != AGP_OK) return st;
+  DeviceFeatures dxs;
+  if ((st = to_device(ctx, xs, false, &dxs)) != AGP_OK) return st;
+  // prior variances | variances | the cross covariances of a slice | their solutions
+  DevMem<double> ws;
+  AGP_HIP_CHECK(ctx, alloc_doubles(ws, 2 * (size_t)M + 2 * (size_t)ld * PCG_COLS));
+  double *prior = ws.get(), *var = prior + M, *Kc = var + M, *S = Kc + (size_t)ld * PCG_COLS;
+  launch_gram_diagonal(s, dprog, dxs.v, prior);
+  for (long long j0 = 0; j0 < M; j0 += PCG_COLS) {
+    const long long t = M - j0 < PCG_COLS ? M - j0 : PCG_COLS;
+    FeatView slice = dxs.v;
+    slice.coords += j0 * slice.dim;
+    if (slice.ids) slice.ids += j0;
+    if (slice.scales) { slice.sstride = scale_stride(dxs.v); slice.scales += j0; }
+    slice.n = t;
+    launch_gram(s, dprog, fit->train.v, slice, false, false, Kc, ld, nullptr, nullptr, &k->prog);
+    if ((st = pcg_solve(ctx, fit, Kc, ld, t, S, ld, nullptr, nullptr)) != AGP_OK) return st;
+    hipLaunchKernelGGL(pcg_variance_kernel, dim3((unsigned)t), dim3(256), 0, s, Kc, S, ld, n, prior + j0, var + j0);
+  }
+  return copy_out(ctx, var, M, variance, location);
+}
+
+}  // extern "C"

@@ -67,6 +67,7 @@ struct PcArgs {
   long long *pivots;
   double rel_tol;
   long long max_rank;
+  const double *diag;  // n values added to the diagonal of K (the matrix-free fit's y_var), or nullptr
 };
 
 // "larger value, then lower index": a total order, NaN never wins
@@ -130,7 +131,8 @@ __global__ __launch_bounds__(PC_THREADS) void pc_init_kernel(PcArgs a, SopProgra
     if (r < n) {
       Point<DIMP> x;
       load_point<DIMP>(a.X, r, a.need_norm != 0, x);
-      const double v = pc_eval<DIMP, EVAL>(a, sop, x, x, false, have_ids, meas);
+      double v = pc_eval<DIMP, EVAL>(a, sop, x, x, false, have_ids, meas);
+      if (a.diag) v += a.diag[r];  // (off the diagonal the columns are those of K: a step never reads entry (p, p) of its column)
       saw_nan = saw_nan || v != v;
       a.d[r] = v;
       a.sel[r] = 0;
@@ -344,11 +346,11 @@ static PcLaunch pc_select(const DevProgram &host_program, int dim, PcArgs *a, So
 
 using namespace agp;
 
-extern "C" {
-
-int agp_pivoted_cholesky(agp_context *c, const agp_kernel *k, const agp_features *x, int64_t max_rank, double rel_tol,
-                         int64_t *pivots, int64_t *rank, double *L, int64_t ldl, double *residual_diag, int location,
-                         double *trace_residual) {
+// agp_pivoted_cholesky of K + diag(diag_dev) (n device values, or nullptr: K itself - the public entry, whose bits this
+// leaves as they were); d0 (optional): the largest diagonal entry.  iterative.hip builds its preconditioner with it.
+int pivoted_cholesky_impl(agp_context *c, const agp_kernel *k, const agp_features *x, const double *diag_dev, int64_t max_rank,
+                          double rel_tol, int64_t *pivots, int64_t *rank, double *L, int64_t ldl, double *residual_diag, int location,
+                          double *trace_residual, double *d0_out) {
   if (!c || !k || !x || !pivots || !rank) return AGP_ERR_INVALID_ARGUMENT;
   agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
   int st = validate_features(x);
@@ -408,6 +410,7 @@ int agp_pivoted_cholesky(agp_context *c, const agp_kernel *k, const agp_features
   a.pivots = piv_dev;
   a.rel_tol = rel_tol;
   a.max_rank = max_rank;
+  a.diag = diag_dev;
   static thread_local SopProgram sop;
   const PcLaunch launch = pc_select(k->prog, x->dim, &a, &sop);
 
@@ -456,7 +459,17 @@ int agp_pivoted_cholesky(agp_context *c, const agp_kernel *k, const agp_features
   for (long long j = 0; j < r; ++j) pivots[j] = h_piv[j];
   *rank = r;
   if (trace_residual) *trace_residual = *h_trace;
+  if (d0_out) *d0_out = h_ctrl->d0;
   return AGP_OK;
+}
+
+extern "C" {
+
+int agp_pivoted_cholesky(agp_context *c, const agp_kernel *k, const agp_features *x, int64_t max_rank, double rel_tol,
+                         int64_t *pivots, int64_t *rank, double *L, int64_t ldl, double *residual_diag, int location,
+                         double *trace_residual) {
+  return pivoted_cholesky_impl(c, k, x, nullptr, max_rank, rel_tol, pivots, rank, L, ldl, residual_diag, location, trace_residual,
+                               nullptr);
 }
 
 }  // extern "C"

@@ -1037,6 +1037,13 @@ class GaussianProcessRegression:
         fit.mixed_precision = self.precision == "mixed"
         return FitModel(self, fit)
 
+    def fit_iterative(self, dataset, preconditioner_rank=256, preconditioner_tolerance=1e-12, tolerance=1e-10,
+                      max_iterations=1000):
+        """The exact fit that never forms the n x n covariance (albatross_amd/iterative.py: fit_iterative): an
+        IterativeFitModel with .predict(features).mean() / .marginal()."""
+        from .iterative import fit_iterative
+        return fit_iterative(self, dataset, preconditioner_rank, preconditioner_tolerance, tolerance, max_iterations)
+
     pivoted_fallback = True
     # 'fp64' (the reference's arithmetic) or 'mixed' (fp32 MFMA products in the bulk updates of the factorisation,
     # information vector refined to fp64; see agp_fit_create_mixed in include/albatross_amd.h)

@@ -43,7 +43,10 @@ typedef enum {
   AGP_ERR_HIP = 4,
   AGP_ERR_COMM = 5,
   AGP_ERR_UNSUPPORTED = 6,
-  AGP_ERR_NO_DEVICE = 7
+  AGP_ERR_NO_DEVICE = 7,
+  /* agp_iterative_fit_create / agp_iterative_solve: max_iterations reached with a right-hand side still above the
+   * tolerance */
+  AGP_ERR_NOT_CONVERGED = 8
 } agp_status;
 
 /* ---- covariance-function descriptor ------------------------------------- */
@@ -914,6 +917,87 @@ AGP_API int agp_pivoted_cholesky(agp_context *ctx, const agp_kernel *k, const ag
                                  int64_t *pivots, int64_t *rank, double *L, int64_t ldl, double *residual_diag, int location,
                                  double *trace_residual);
 
+/* ---- the covariance times a block of vectors, without the matrix ---------------------------
+ *   out[:, c] = (k(x, x) + diag(y_var)) V[:, c],   c = 0 .. nrhs - 1
+ * with K evaluated pair by pair inside the product and never stored (memory O(n nrhs) instead of O(n^2)): the building
+ * block of a matrix-free solve.  K is the matrix agp_gram(ctx, k, x, NULL, ...) gives (is_measurement, equality ids, scale
+ * columns and all metrics included), entry by entry the same bits; y_var is added to the diagonal entry before the
+ * product.  Every covariance tree is served: the radial fast path (dim <= 3), the sum-of-products evaluator, the postfix
+ * interpreter, chosen as agp_gram chooses.
+ *   y_var     n values at x->location, or NULL (zeros)
+ *   V, ldv    n x nrhs column-major at `location`, ldv >= n
+ *   out, ldo  n x nrhs column-major at `location`, ldo >= n, not overlapping V: rows >= n of a padded ldo and everything
+ *             beyond nrhs columns are not touched
+ * x may be host or device memory (x->location).  Any nrhs >= 1: the right-hand sides are served in chunks of at most
+ * AGP_MATVEC_MAX_RHS inside the call (16, then 4 or 1 for the rest), each entry K_ij evaluated once per chunk.
+ * Status: nrhs < 1, ldv < n, ldo < n, a location that is neither AGP_HOST nor AGP_DEVICE, a NULL V or out:
+ * AGP_ERR_INVALID_ARGUMENT, nothing written.  A NaN entry of K (a NaN coordinate): AGP_ERR_NAN_INPUT; a host `out` is not
+ * written, a device `out` holds the NaNs.  n == 0: AGP_OK.
+ * A thread owns one row and the accumulators of a chunk; the column points and their rows of V pass through LDS in tiles
+ * of 64, read as broadcasts.  For n below 262144 the column range is split into S slices over a second grid dimension
+ * (S depends on n alone) and a second launch adds the S partial sums of an entry in slice order.  No float atomics and a
+ * fixed order of every sum: two identical calls return identical bits.  Scratch: S * 16 * n doubles when S > 1, plus
+ * copies of V and out (2 n nrhs doubles) for host arrays. */
+#define AGP_MATVEC_MAX_RHS 16
+AGP_API int agp_gram_matvec(agp_context *ctx, const agp_kernel *k, const agp_features *x, const double *y_var, const double *V,
+                            int64_t ldv, int64_t nrhs, double *out, int64_t ldo, int location);
+
+/* ---- matrix-free fit: preconditioned conjugate gradients around agp_gram_matvec --------------
+ * The exact fit that never forms A = k(x, x) + diag(y_var) (x as measurements, exactly the matrix agp_fit_create
+ * factors; the predictions see the training features as agp_predict_* do): information = A^-1 y by conjugate gradients whose products
+ * are agp_gram_matvec launches, preconditioned by the greedy pivoted Cholesky factor of A.  Memory is O(n (m + t)) for a
+ * preconditioner of rank m and t right-hand sides in flight, instead of O(n^2).
+ *   (L, m, trace) = agp_pivoted_cholesky of A with max_rank = min(precond_rank, n), rel_tol = precond_rel_tol (m may come
+ *   out below precond_rank: duplicated points);  P = L L^T + delta I,  delta = max(trace / (n - m), 1e-8 max_i A_ii), the
+ *   floor alone when m = n;  P^-1 r = (r - L (delta I + L^T L)^-1 L^T r) / delta, with L^T L formed once on the fp64 GEMM
+ *   and its m x m matrix factored by the dense LL^T.  precond_rank = 0: P = delta I with delta the mean of diag(A), plain CG.
+ * The right-hand sides of a call run INDEPENDENT recurrences in chunks of at most AGP_MATVEC_MAX_RHS that share each
+ * product launch (not block CG).  A right-hand side stops at the first iteration with ||r||_2 <= tolerance ||b||_2 (r the
+ * recurrence's residual) and is frozen from then on; a zero right-hand side returns zeros after 0 iterations.  The scalars
+ * of the recurrences live on the device; the host looks at the stop marks once per 8 iterations with the next 8 queued.
+ *   options       precond_rank >= 0, precond_rel_tol >= 0, tolerance > 0, max_iterations >= 1
+ *   y, y_var      n values at x->location; y_var may be NULL (zeros)
+ *   information   n doubles (host), may be NULL;  iterations / residual (host, may be NULL): the iterations carried out and
+ *                 the final ||r|| / ||y|| of the recurrence - written whenever the iteration ran, also on
+ *                 AGP_ERR_NOT_CONVERGED
+ * The handle owns a copy of the features, y_var, the information vector, L, the factor of delta I + L^T L and delta; it
+ * belongs to its context and must be destroyed before it.
+ * Status: a malformed argument AGP_ERR_INVALID_ARGUMENT, nothing written.  A_ii <= 0 for some i (before any iteration) or
+ * p^T A p <= 0 in an active recurrence: AGP_ERR_NOT_POSITIVE_DEFINITE.  A NaN coordinate, target or variance:
+ * AGP_ERR_NAN_INPUT.  max_iterations reached with a right-hand side still active: AGP_ERR_NOT_CONVERGED (no handle, no
+ * solution).  No float atomics, a fixed order of every sum: two identical calls return identical bits, iteration counts
+ * included.  Scratch of a solve: 4 n t doubles for the recurrences, m t for the preconditioner, plus that of
+ * agp_gram_matvec.  With profiling on, agp_last_stage_ms reports the preconditioner build under stage 11 and the
+ * conjugate-gradient chain under stage 12.
+ * agp_iterative_solve: out = A^-1 rhs for nrhs >= 1 right-hand sides (n x nrhs column-major at `location`, ldr, ldo >= n)
+ *   at the fit's tolerance and max_iterations; iterations / residual: nrhs host values each, may be NULL.
+ * agp_iterative_predict_mean: mean_j = sum_i k(x_i, xs_j) information_i, the launches of agp_predict_mean.
+ * agp_iterative_predict_marginal: also variance_j = k(xs_j, xs_j) - k_j^T A^-1 k_j; the cross covariances come from the
+ *   Gram kernels in slices of 16 test points, each slice solved by the same conjugate gradients (its status is returned).
+ * Out of scope, by design: joint predictions, the log-determinant and the log-likelihood (they need stochastic Lanczos
+ * quadrature), gradients, LinearCombination features, the sharded and the mixed-precision path - the dense entry points
+ * serve them up to the n their memory allows. */
+typedef struct {
+  int64_t precond_rank;
+  double precond_rel_tol;
+  double tolerance;
+  int max_iterations;
+} agp_iterative_options;
+typedef struct agp_iterative_fit agp_iterative_fit;
+AGP_API int agp_iterative_fit_create(agp_context *ctx, const agp_kernel *k, const agp_features *x, const double *y, const double *y_var,
+                                     const agp_iterative_options *options, agp_iterative_fit **out, double *information,
+                                     int *iterations, double *residual);
+AGP_API void agp_iterative_fit_destroy(agp_iterative_fit *fit);
+AGP_API int64_t agp_iterative_fit_size(const agp_iterative_fit *fit);
+AGP_API int64_t agp_iterative_fit_preconditioner_rank(const agp_iterative_fit *fit);
+AGP_API int agp_iterative_fit_download_information(agp_context *ctx, const agp_iterative_fit *fit, double *information);
+AGP_API int agp_iterative_solve(agp_context *ctx, const agp_iterative_fit *fit, const double *rhs, int64_t ldr, int64_t nrhs, double *out,
+                                int64_t ldo, int location, int *iterations, double *residual);
+AGP_API int agp_iterative_predict_mean(agp_context *ctx, const agp_kernel *k, const agp_iterative_fit *fit, const agp_features *xs,
+                                       double *mean, int location);
+AGP_API int agp_iterative_predict_marginal(agp_context *ctx, const agp_kernel *k, const agp_iterative_fit *fit, const agp_features *xs,
+                                           double *mean, double *variance, int location);
+
 /* ---- sparse Gaussian process (FITC / PITC) --------------------------------------------------
  * SparseGaussianProcessRegression, include/albatross/src/models/sparse_gp.hpp.
  *
@@ -1277,7 +1361,8 @@ AGP_API int agp_sharded_fit_stage(const agp_sharded_fit *fit, int stage, double 
  * HIP events on the stream the kernels were launched on.  Stages:
  * 0 gram, 1 factor (total), 2 solve, 3 trailing-update kernels only (sum),
  * 4 number of trailing-update launches.  Returns ms (or a count for 4).  Stages 6-9:
- * the gradient entries (agp_nll_gradient, agp_loo_nll_gradient).  Stage 10: the step chain of agp_pivoted_cholesky. */
+ * the gradient entries (agp_nll_gradient, agp_loo_nll_gradient).  Stage 10: the step chain of agp_pivoted_cholesky.
+ * Stages 11, 12: the preconditioner build and the conjugate-gradient chain of agp_iterative_fit_create. */
 AGP_API int agp_last_stage_ms(const agp_context *ctx, int stage, double *ms);
 /* enable (1) / disable (0) per-stage event timing (default off: events add
  * host overhead to the launch chain). */

@@ -1680,9 +1680,158 @@ struct RansacTrialScores {
   std::vector<int> status;
 };
 
+// ---- the matrix-free fit (include/albatross_amd.h: agp_gram_matvec, agp_iterative_*) ----------------------------------
+// out = (cov(features) + diag(targets_variance)) V without the n x n matrix: every entry is evaluated inside the product,
+// with the bits cov(features) has.  V is n x columns; targets_variance is empty or has n values.
+template <typename CovFunc, typename FeatureType>
+Matrix gram_matvec(const CovFunc &cov, const std::vector<FeatureType> &features, const Matrix &V, const Vector &targets_variance = {}) {
+  static_assert(!detail::expansion<FeatureType>::expands, "gram_matvec: LinearCombination features are not supported");
+  const std::int64_t n = static_cast<std::int64_t>(features.size());
+  if (n == 0 || V.rows() != n || V.cols() < 1) throw std::invalid_argument("gram_matvec: V must have one row per feature and a column");
+  if (!targets_variance.empty() && targets_variance.size() != features.size())
+    throw std::invalid_argument("gram_matvec: one variance per feature");
+  auto ctx = detail::default_context();
+  detail::KernelHolder k(cov.program());
+  detail::Flat f = detail::flatten(cov, features);
+  Matrix out(n, V.cols());
+  detail::check(agp_gram_matvec(ctx->ctx, k.k, &f.view, targets_variance.empty() ? nullptr : targets_variance.data(), V.data.data(), n,
+                                V.cols(), out.data.data(), n, AGP_HOST),
+                ctx->ctx, "agp_gram_matvec");
+  return out;
+}
+
+// the options of GaussianProcessRegression::fit_iterative (agp_iterative_options)
+struct IterativeOptions {
+  std::int64_t preconditioner_rank = 256;  // rank of the pivoted Cholesky preconditioner (0: plain conjugate gradients)
+  double preconditioner_tolerance = 1e-12;
+  double tolerance = 1e-10;                // ||r|| <= tolerance ||b||
+  int max_iterations = 1000;
+};
+
+// AGP_ERR_NOT_CONVERGED: max_iterations reached above the tolerance
+struct NotConvergedError : std::runtime_error {
+  NotConvergedError(const std::string &what, int iterations_, double residual_)
+      : std::runtime_error(what), iterations(iterations_), residual(residual_) {}
+  int iterations;
+  double residual;
+};
+
+template <typename FeatureType>
+struct IterativeGPFit {
+  std::vector<FeatureType> train_features;
+  Vector information;
+  int iterations = 0;
+  double residual = 0.;
+  std::int64_t preconditioner_rank = 0;
+  std::shared_ptr<agp_iterative_fit> handle;
+  std::shared_ptr<detail::ContextHolder> context;
+  // (K + diag(variance))^-1 rhs at the fit's tolerance, rhs n x columns
+  Matrix solve(const Matrix &rhs) const {
+    const std::int64_t n = static_cast<std::int64_t>(train_features.size());
+    if (rhs.rows() != n || rhs.cols() < 1) throw std::invalid_argument("IterativeGPFit::solve: one row per training feature");
+    Matrix out(n, rhs.cols());
+    std::vector<int> its(static_cast<std::size_t>(rhs.cols()));
+    Vector res(static_cast<std::size_t>(rhs.cols()));
+    const int st = agp_iterative_solve(context->ctx, handle.get(), rhs.data.data(), n, rhs.cols(), out.data.data(), n, AGP_HOST,
+                                       its.data(), res.data());
+    if (st == AGP_ERR_NOT_CONVERGED) throw NotConvergedError("albatross_amd: agp_iterative_solve: not converged", its[0], res[0]);
+    detail::check(st, context->ctx, "agp_iterative_solve");
+    return out;
+  }
+};
+
+template <typename ModelType, typename FeatureType>
+class IterativeFitModel;
+
+// .mean() and .marginal(); .joint() is out of scope for a fit that never forms the covariance
+template <typename ModelType, typename FeatureType, typename PredictFeature>
+class IterativePrediction {
+ public:
+  IterativePrediction(const IterativeFitModel<ModelType, FeatureType> &fm, std::vector<PredictFeature> xs) : fm_(fm), xs_(std::move(xs)) {}
+  Vector mean() const { return fm_.predict_(xs_, false).mean; }
+  MarginalDistribution marginal() const { return fm_.predict_(xs_, true); }
+  JointDistribution joint() const {
+    throw std::logic_error("fit_iterative: joint predictions are not supported by the matrix-free fit; use marginal(), or fit()");
+  }
+
+ private:
+  const IterativeFitModel<ModelType, FeatureType> &fm_;
+  std::vector<PredictFeature> xs_;
+};
+
+template <typename ModelType, typename FeatureType>
+class IterativeFitModel {
+ public:
+  IterativeFitModel(const ModelType &model, IterativeGPFit<FeatureType> fit) : model_(model), fit_(std::move(fit)) {}
+  const IterativeGPFit<FeatureType> &get_fit() const { return fit_; }
+  const ModelType &get_model() const { return model_; }
+  template <typename PredictFeature>
+  IterativePrediction<ModelType, FeatureType, PredictFeature> predict(const std::vector<PredictFeature> &xs) const {
+    return IterativePrediction<ModelType, FeatureType, PredictFeature>(*this, xs);
+  }
+  template <typename PredictFeature>
+  MarginalDistribution predict_(const std::vector<PredictFeature> &xs, bool marginal) const {
+    static_assert(!detail::expansion<PredictFeature>::expands, "fit_iterative: LinearCombination features are not supported");
+    detail::KernelHolder k(model_.get_covariance().program());
+    detail::Flat f = detail::flatten(model_.get_covariance(), xs);
+    MarginalDistribution out;
+    out.mean.assign(xs.size(), 0.);
+    agp_context *c = fit_.context->ctx;
+    if (marginal) {
+      out.covariance.assign(xs.size(), 0.);
+      const int st = agp_iterative_predict_marginal(c, k.k, fit_.handle.get(), &f.view, out.mean.data(), out.covariance.data(), AGP_HOST);
+      if (st == AGP_ERR_NOT_CONVERGED) throw NotConvergedError("albatross_amd: agp_iterative_predict_marginal: not converged", 0, 0.);
+      detail::check(st, c, "agp_iterative_predict_marginal");
+    } else {
+      detail::check(agp_iterative_predict_mean(c, k.k, fit_.handle.get(), &f.view, out.mean.data(), AGP_HOST), c,
+                    "agp_iterative_predict_mean");
+    }
+    model_.add_mean(xs, &out.mean);
+    return out;
+  }
+
+ private:
+  ModelType model_;
+  IterativeGPFit<FeatureType> fit_;
+};
+
 template <typename CovFunc, typename MeanFunc = ZeroMean>
 class GaussianProcessRegression {
  public:
+  // The exact fit that never forms the n x n covariance: preconditioned conjugate gradients around gram_matvec
+  // (agp_iterative_fit_create).  The mean function is removed from the targets exactly as `fit` does.  Throws
+  // NotConvergedError when options.max_iterations do not reach options.tolerance.
+  template <typename FeatureType>
+  IterativeFitModel<GaussianProcessRegression, FeatureType> fit_iterative(const RegressionDataset<FeatureType> &dataset,
+                                                                          const IterativeOptions &options = {}) const {
+    static_assert(!detail::expansion<FeatureType>::expands, "fit_iterative: LinearCombination features are not supported");
+    const auto &features = dataset.features;
+    const MarginalDistribution &targets = dataset.targets;
+    if (features.size() != targets.size()) throw std::invalid_argument("features and targets differ in size");
+    if (!targets.covariance.empty() && targets.covariance.size() != targets.size())
+      throw std::invalid_argument("target covariance must be diagonal (one variance per target)");
+    auto ctx = detail::default_context();
+    detail::KernelHolder k(covariance_function_.program());
+    detail::Flat f = detail::flatten(covariance_function_, features);
+    Vector y = targets.mean;  // mean_function_.remove_from, gp.hpp:291-292
+    if (!std::is_same<MeanFunc, ZeroMean>::value)
+      for (std::size_t i = 0; i < y.size(); ++i) y[i] -= mean_function_._call_impl(detail::unwrap<FeatureType>::get(features[i]));
+    IterativeGPFit<FeatureType> fit;
+    fit.train_features = features;
+    fit.information.resize(features.size());
+    fit.context = ctx;
+    agp_iterative_options opt{options.preconditioner_rank, options.preconditioner_tolerance, options.tolerance, options.max_iterations};
+    agp_iterative_fit *h = nullptr;
+    const int st = agp_iterative_fit_create(ctx->ctx, k.k, &f.view, y.data(), targets.covariance.empty() ? nullptr : targets.covariance.data(),
+                                            &opt, &h, fit.information.data(), &fit.iterations, &fit.residual);
+    if (st == AGP_ERR_NOT_CONVERGED)
+      throw NotConvergedError("albatross_amd: agp_iterative_fit_create: not converged", fit.iterations, fit.residual);
+    detail::check(st, ctx->ctx, "agp_iterative_fit_create");
+    fit.preconditioner_rank = agp_iterative_fit_preconditioner_rank(h);
+    fit.handle = std::shared_ptr<agp_iterative_fit>(h, [ctx](agp_iterative_fit *p) { agp_iterative_fit_destroy(p); });
+    return IterativeFitModel<GaussianProcessRegression, FeatureType>(*this, std::move(fit));
+  }
+
   GaussianProcessRegression() = default;
   explicit GaussianProcessRegression(const CovFunc &cov, const std::string &name = "gaussian_process_regression")
       : covariance_function_(cov), model_name_(name) {}
