@@ -9,6 +9,7 @@
 #include "api_internal.h"
 #include "mfma_f64.h"
 #include "gram_matvec.h"
+#include "iterative_internal.h"
 #include "shard_internal.h"
 #include "pub.h"
 #include "trsm_kernel.h"
@@ -2008,6 +2009,207 @@ AGP_DEBUG_API int agp_debug_reduce(agp_context *ctx, int op, const int64_t *ip, 
   AGP_HIP_CHECK(ctx, hipGetLastError());
   for (int k = 0; k < n_bufs; ++k)
     if (bufs[k] && owner[k] == k) AGP_HIP_CHECK(ctx, hipMemcpy(bufs[k], dev[k].p, (size_t)bytes[k], hipMemcpyDeviceToHost));
+  return AGP_OK;
+}
+
+// sizeof(PcgCtrl) and the byte offset of every field (iterative_internal.h), then PCG_COLS, PCG_LOOK, PCG_DOT_THREADS and
+// PCG_ERROR: out[0 .. 15].  tests/test_pcg_kernels_gpu.py asserts its mirror of the struct against this.
+AGP_DEBUG_API int agp_debug_pcg_ctrl_layout(int64_t *out, int cap) {
+  if (!out || cap < 16) return AGP_ERR_INVALID_ARGUMENT;
+  const int64_t v[16] = {(int64_t)sizeof(PcgCtrl), (int64_t)offsetof(PcgCtrl, active), (int64_t)offsetof(PcgCtrl, npd),
+                         (int64_t)offsetof(PcgCtrl, nan), (int64_t)offsetof(PcgCtrl, pad), (int64_t)offsetof(PcgCtrl, stopped),
+                         (int64_t)offsetof(PcgCtrl, iters), (int64_t)offsetof(PcgCtrl, bb), (int64_t)offsetof(PcgCtrl, rz),
+                         (int64_t)offsetof(PcgCtrl, alpha), (int64_t)offsetof(PcgCtrl, beta), (int64_t)offsetof(PcgCtrl, resid),
+                         PCG_COLS, PCG_LOOK, PCG_DOT_THREADS, PCG_ERROR};
+  for (int k = 0; k < 16; ++k) out[k] = v[k];
+  return AGP_OK;
+}
+
+// ONE kernel of iterative.hip on host data, through its launcher of iterative_internal.h - the grid and block arithmetic
+// the product runs (tests/test_pcg_kernels_gpu.py).  The calling convention of agp_debug_reduce: bufs[k] (bytes[k] long, or
+// null for an optional pointer) are copied to the device whole, the launcher runs once on the context's stream, and every
+// buffer is copied back whole - padding and sentinels included.  Two entries with the SAME host pointer share one device
+// buffer (the r . r of DOT_BB and DOT_RR).  The control block is a buffer like the others: the test sets active, stopped[]
+// and rz[][] before the launch and reads every field after it.  Every extent a kernel addresses is checked against bytes[]
+// on the host first: AGP_ERR_INVALID_ARGUMENT, with nothing launched.
+//   PCG_OP_DOT_BB / _RZ / _PQ / _RR   ip ld n t k;  dp tol;  ctrl A B
+//   PCG_OP_LT_R                       ip ldl n m ldr t ldt;  ctrl L R T1                     (m >= 1)
+//   PCG_OP_PRECOND                    ip ldl n m ldu ld t;  dp delta;  ctrl [L] [U] R Z      (m = 0: L and U may be null)
+//   PCG_OP_P                          ip ld n t first;  ctrl Z P
+//   PCG_OP_XR                         ip ldx ld n t;  ctrl X R P Q
+//   PCG_OP_DIAG_STATS                 ip n;  d [yvar] stats(4)
+//   PCG_OP_SHIFT                      ip ldc m;  dp delta;  C
+//   PCG_OP_VARIANCE                   ip ld n t;  Kc S prior var
+enum {
+  PCG_OP_DOT_BB = 0, PCG_OP_DOT_RZ, PCG_OP_DOT_PQ, PCG_OP_DOT_RR, PCG_OP_LT_R, PCG_OP_PRECOND, PCG_OP_P, PCG_OP_XR,
+  PCG_OP_DIAG_STATS, PCG_OP_SHIFT, PCG_OP_VARIANCE, PCG_OPS
+};
+AGP_DEBUG_API int agp_debug_pcg(agp_context *ctx, int op, const int64_t *ip, int n_ip, const double *dp, int n_dp, void *const *bufs,
+                                const int64_t *bytes, int n_bufs) {
+  constexpr int MAXB = 5;
+  constexpr long long LIM = 1ll << 26;  // no dimension of a test comes near it: the products below cannot overflow
+  if (!ctx || op < 0 || op >= PCG_OPS || !ip || !bufs || !bytes || n_ip < 1 || n_ip > 6 || n_dp < 0 || n_dp > 1 || (n_dp && !dp) ||
+      n_bufs < 1 || n_bufs > MAXB)
+    return AGP_ERR_INVALID_ARGUMENT;
+  long long I[6] = {0, 0, 0, 0, 0, 0};
+  for (int k = 0; k < n_ip; ++k) {
+    if (ip[k] < 0 || ip[k] > LIM) return AGP_ERR_INVALID_ARGUMENT;
+    I[k] = ip[k];
+  }
+  const double d0 = n_dp > 0 ? dp[0] : 0.;
+  for (int k = 0; k < n_bufs; ++k)
+    if (bytes[k] < 0 || (bufs[k] && bytes[k] == 0)) return AGP_ERR_INVALID_ARGUMENT;
+  auto has = [&](int k) { return k < n_bufs && bufs[k] != nullptr; };
+  auto fits = [&](int k, long long elems) { return has(k) && elems >= 0 && elems <= LIM * 64 && bytes[k] >= elems * 8; };
+  auto opt_fits = [&](int k, long long elems) { return !has(k) || fits(k, elems); };
+  auto ctrl_fits = [&](int k) { return has(k) && bytes[k] >= (long long)sizeof(PcgCtrl); };
+  // elements a column-major rows x cols matrix of leading dimension ld spans; -1 (fits nothing) for ld < rows
+  auto mat = [](long long ld, long long rows, long long cols) -> long long {
+    if (ld < rows || rows < 1 || cols < 1) return -1;
+    return ld * (cols - 1) + rows;
+  };
+  auto cols_ok = [](long long t) { return t >= 1 && t <= PCG_COLS; };
+  // an output that is also read by the launch under another name would race
+  auto distinct = [&](int a, int b) { return !has(a) || !has(b) || bufs[a] != bufs[b]; };
+  bool ok = false;
+  switch (op) {
+  case PCG_OP_DOT_BB:
+  case PCG_OP_DOT_RZ:
+  case PCG_OP_DOT_PQ:
+  case PCG_OP_DOT_RR:
+    ok = n_ip == 4 && cols_ok(I[2]) && ctrl_fits(0) && fits(1, mat(I[0], I[1], I[2])) && fits(2, mat(I[0], I[1], I[2])) && distinct(0, 1) &&
+         distinct(0, 2);
+    break;
+  case PCG_OP_LT_R:
+    ok = n_ip == 6 && cols_ok(I[4]) && ctrl_fits(0) && fits(1, mat(I[0], I[1], I[2])) && fits(2, mat(I[3], I[1], I[4])) &&
+         fits(3, mat(I[5], I[2], I[4])) && distinct(3, 0) && distinct(3, 1) && distinct(3, 2);
+    break;
+  case PCG_OP_PRECOND:
+    ok = n_ip == 6 && cols_ok(I[5]) && ctrl_fits(0) && (I[2] == 0 || (fits(1, mat(I[0], I[1], I[2])) && fits(2, mat(I[3], I[2], I[5])))) &&
+         fits(3, mat(I[4], I[1], I[5])) && fits(4, mat(I[4], I[1], I[5])) && distinct(4, 0) && distinct(4, 1) && distinct(4, 2) &&
+         distinct(4, 3);
+    break;
+  case PCG_OP_P:
+    ok = n_ip == 4 && cols_ok(I[2]) && ctrl_fits(0) && fits(1, mat(I[0], I[1], I[2])) && fits(2, mat(I[0], I[1], I[2])) && distinct(2, 0) &&
+         distinct(2, 1);
+    break;
+  case PCG_OP_XR:
+    ok = n_ip == 4 && cols_ok(I[3]) && ctrl_fits(0) && fits(1, mat(I[0], I[2], I[3])) && fits(2, mat(I[1], I[2], I[3])) &&
+         fits(3, mat(I[1], I[2], I[3])) && fits(4, mat(I[1], I[2], I[3])) && distinct(1, 0) && distinct(2, 0) && distinct(1, 2) &&
+         distinct(1, 3) && distinct(1, 4) && distinct(2, 3) && distinct(2, 4);
+    break;
+  case PCG_OP_DIAG_STATS: ok = n_ip == 1 && I[0] >= 1 && fits(0, I[0]) && opt_fits(1, I[0]) && fits(2, 4) && distinct(2, 0) && distinct(2, 1); break;
+  case PCG_OP_SHIFT: ok = n_ip == 2 && fits(0, mat(I[0], I[1], I[1])); break;
+  default:  // PCG_OP_VARIANCE
+    ok = n_ip == 3 && I[2] >= 1 && fits(0, mat(I[0], I[1], I[2])) && fits(1, mat(I[0], I[1], I[2])) && fits(2, I[2]) && fits(3, I[2]) &&
+         distinct(3, 0) && distinct(3, 1) && distinct(3, 2);
+    break;
+  }
+  if (!ok) return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  DevBuf<char> dev[MAXB];
+  void *d[MAXB] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  int owner[MAXB];
+  for (int k = 0; k < n_bufs; ++k) {
+    owner[k] = k;
+    if (!bufs[k]) continue;
+    for (int j = 0; j < k; ++j)
+      if (bufs[j] == bufs[k]) { owner[k] = j; break; }
+    if (owner[k] != k) {
+      if (bytes[k] > bytes[owner[k]]) return AGP_ERR_INVALID_ARGUMENT;
+      d[k] = d[owner[k]];
+      continue;
+    }
+    AGP_HIP_CHECK(ctx, dev[k].alloc((size_t)bytes[k]));
+    AGP_HIP_CHECK(ctx, hipMemcpy(dev[k].p, bufs[k], (size_t)bytes[k], hipMemcpyHostToDevice));
+    d[k] = dev[k].p;
+  }
+  auto D = [&](int k) { return static_cast<double *>(d[k]); };
+  PcgCtrl *ctrl = static_cast<PcgCtrl *>(d[0]);  // (of the ops that have one)
+  switch (op) {
+  case PCG_OP_DOT_BB: launch_pcg_dot(s, DOT_BB, ctrl, D(1), D(2), I[0], I[1], (int)I[2], (int)I[3], d0); break;
+  case PCG_OP_DOT_RZ: launch_pcg_dot(s, DOT_RZ, ctrl, D(1), D(2), I[0], I[1], (int)I[2], (int)I[3], d0); break;
+  case PCG_OP_DOT_PQ: launch_pcg_dot(s, DOT_PQ, ctrl, D(1), D(2), I[0], I[1], (int)I[2], (int)I[3], d0); break;
+  case PCG_OP_DOT_RR: launch_pcg_dot(s, DOT_RR, ctrl, D(1), D(2), I[0], I[1], (int)I[2], (int)I[3], d0); break;
+  case PCG_OP_LT_R: launch_pcg_lt_r(s, ctrl, D(1), I[0], I[1], I[2], D(2), I[3], (int)I[4], D(3), I[5]); break;
+  case PCG_OP_PRECOND: launch_pcg_precond(s, ctrl, D(1), I[0], I[1], I[2], D(2), I[3], D(3), D(4), I[4], (int)I[5], d0); break;
+  case PCG_OP_P: launch_pcg_p(s, ctrl, D(1), D(2), I[0], I[1], (int)I[2], (int)I[3]); break;
+  case PCG_OP_XR: launch_pcg_xr(s, ctrl, D(1), I[0], D(2), D(3), D(4), I[1], I[2], (int)I[3]); break;
+  case PCG_OP_DIAG_STATS: launch_pcg_diag_stats(s, D(0), D(1), I[0], D(2)); break;
+  case PCG_OP_SHIFT: launch_pcg_shift(s, D(0), I[0], I[1], d0); break;
+  default: launch_pcg_variance(s, D(0), D(1), I[0], I[1], I[2], D(2), D(3)); break;
+  }
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  for (int k = 0; k < n_bufs; ++k)
+    if (bufs[k] && owner[k] == k) AGP_HIP_CHECK(ctx, hipMemcpy(bufs[k], dev[k].p, (size_t)bytes[k], hipMemcpyDeviceToHost));
+  return AGP_OK;
+}
+
+// The preconditioner a live matrix-free fit holds: dims[0 .. 2] = n, rank, ldl of the device; *delta; and, where the
+// pointers are given, L (n x rank at ldl_out) and the factor of delta I + L^T L (rank x rank at ldc_out: the lower
+// triangle as the device holds it, zeros above).  A first call with both null asks for the sizes.
+AGP_DEBUG_API int agp_debug_iterative_state(agp_context *ctx, const agp_iterative_fit *fit, int64_t *dims, double *delta, double *L,
+                                            int64_t ldl_out, double *C, int64_t ldc_out) {
+  if (!ctx || !fit || !dims || !delta) return AGP_ERR_INVALID_ARGUMENT;
+  const PcgPrecondState st = iterative_precond_state(fit);
+  if (st.ctx != ctx) return AGP_ERR_INVALID_ARGUMENT;
+  dims[0] = st.n; dims[1] = st.rank; dims[2] = st.ldl;
+  *delta = st.delta;
+  if (st.rank == 0 || (!L && !C)) return AGP_OK;
+  if ((L && ldl_out < st.n) || (C && ldc_out < st.rank) || !st.L || !st.mfac) return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  if (L)
+    AGP_HIP_CHECK(ctx, hipMemcpy2D(L, sizeof(double) * (size_t)ldl_out, st.L, sizeof(double) * (size_t)st.ldl, sizeof(double) * (size_t)st.n,
+                                   (size_t)st.rank, hipMemcpyDeviceToHost));
+  if (C) {
+    AGP_HIP_CHECK(ctx, hipMemcpy2D(C, sizeof(double) * (size_t)ldc_out, st.mfac->A, sizeof(double) * (size_t)st.mfac->lda,
+                                   sizeof(double) * (size_t)st.rank, (size_t)st.rank, hipMemcpyDeviceToHost));
+    for (long long j = 1; j < st.rank; ++j)
+      for (long long i = 0; i < j; ++i) C[j * ldc_out + i] = 0.;
+  }
+  return AGP_OK;
+}
+
+// ONE application Z = P^-1 R of a live fit's preconditioner through pcg_apply_preconditioner - the function every
+// iteration of pcg_solve calls - at the leading dimension and with the scratch pcg_solve gives it; the control block has
+// active = 1 and stopped[] as given (t ints).  R: n x t at ldr, read; Z: n x t at ldz, uploaded first, so that the column of
+// a stopped right-hand side comes back with the bits it had.  The device's padding row (odd n) is NaN on the way in.
+AGP_DEBUG_API int agp_debug_iterative_precondition(agp_context *ctx, const agp_iterative_fit *fit, const double *R, int64_t ldr, int t,
+                                                   const int *stopped, double *Z, int64_t ldz) {
+  if (!ctx || !fit || !R || !Z || !stopped || t < 1 || t > PCG_COLS) return AGP_ERR_INVALID_ARGUMENT;
+  const PcgPrecondState st = iterative_precond_state(fit);
+  if (st.ctx != ctx || ldr < st.n || ldz < st.n) return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const long long n = st.n, m = st.rank, ld = round_up(n, 2), ldt = round_up(m > 0 ? m : 1, 2);
+  const size_t vec = (size_t)ld * (size_t)t, t1 = (size_t)ldt * (size_t)t;
+  DevBuf<double> Rd, Zd, T1;
+  DevBuf<PcgCtrl> cd;
+  AGP_HIP_CHECK(ctx, Rd.alloc(vec));
+  AGP_HIP_CHECK(ctx, Zd.alloc(vec));
+  AGP_HIP_CHECK(ctx, T1.alloc(t1));
+  AGP_HIP_CHECK(ctx, cd.alloc(1));
+  PcgCtrl h;
+  std::memset(&h, 0, sizeof(h));
+  h.active = 1;
+  for (int c = 0; c < t; ++c) h.stopped[c] = stopped[c];
+  AGP_HIP_CHECK(ctx, hipMemset(Rd.p, 0xff, sizeof(double) * vec));  // (all bits set: a NaN)
+  AGP_HIP_CHECK(ctx, hipMemset(Zd.p, 0xff, sizeof(double) * vec));
+  AGP_HIP_CHECK(ctx, hipMemset(T1.p, 0xff, sizeof(double) * t1));
+  AGP_HIP_CHECK(ctx, hipMemcpy(cd.p, &h, sizeof(h), hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipMemcpy2D(Rd.p, sizeof(double) * (size_t)ld, R, sizeof(double) * (size_t)ldr, sizeof(double) * (size_t)n, (size_t)t,
+                                 hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipMemcpy2D(Zd.p, sizeof(double) * (size_t)ld, Z, sizeof(double) * (size_t)ldz, sizeof(double) * (size_t)n, (size_t)t,
+                                 hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  pcg_apply_preconditioner(s, fit, cd.p, Rd.p, Zd.p, ld, t, T1.p, ldt);
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipMemcpy2D(Z, sizeof(double) * (size_t)ldz, Zd.p, sizeof(double) * (size_t)ld, sizeof(double) * (size_t)n, (size_t)t,
+                                 hipMemcpyDeviceToHost));
   return AGP_OK;
 }
 

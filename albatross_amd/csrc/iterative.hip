@@ -20,6 +20,7 @@
 #include <vector>
 #include "api_internal.h"
 #include "gram_matvec.h"
+#include "iterative_internal.h"
 #include "trace.h"
 
 int pivoted_cholesky_impl(agp_context *c, const agp_kernel *k, const agp_features *x, const double *diag_dev, int64_t max_rank,
@@ -27,23 +28,6 @@ int pivoted_cholesky_impl(agp_context *c, const agp_kernel *k, const agp_feature
                           double *trace_residual, double *d0_out);  // pivoted_chol.hip
 
 namespace agp {
-
-constexpr int PCG_LOOK = 8;             // iterations between two looks of the host
-constexpr int PCG_COLS = MV_MAX_RHS;    // right-hand sides of a chunk
-constexpr int PCG_DOT_THREADS = 1024;
-constexpr int PCG_ERROR = 1 << 20;      // subtracted from `active` by the kernel that marks an error: nothing runs after
-
-struct PcgCtrl {
-  int active;              // columns still iterating; <= 0: every kernel returns at once (also gram_matvec's `go` word)
-  int npd;                 // p^T A p <= 0 in an active column
-  int nan;                 // a NaN in a reduction or in an entry of A
-  int pad;
-  int stopped[PCG_COLS];
-  int iters[PCG_COLS];     // iterations carried out by the column
-  double bb[PCG_COLS], rz[2][PCG_COLS], alpha[PCG_COLS], beta[PCG_COLS], resid[PCG_COLS];
-};
-
-enum { DOT_BB = 0, DOT_RZ = 1, DOT_PQ = 2, DOT_RR = 3 };
 
 // one workgroup per column c: s = sum_i A[i, c] B[i, c] in a fixed order, then the scalars that follow from it
 template <int MODE>
@@ -218,6 +202,50 @@ __global__ __launch_bounds__(256) void pcg_variance_kernel(const double *Kc, con
   if (threadIdx.x == 0) var[j] = prior[j] - ((red[0] + red[1]) + (red[2] + red[3]));
 }
 
+// ---- the launchers (iterative_internal.h): the product below and the probes of debug_api.hip launch through these ----
+void launch_pcg_dot(hipStream_t s, int mode, PcgCtrl *ctrl, const double *A, const double *B, long long ld, long long n, int t, int k,
+                    double tol) {
+  const dim3 grid(t), block(PCG_DOT_THREADS);
+  switch (mode) {
+  case DOT_BB: hipLaunchKernelGGL(pcg_dot_kernel<DOT_BB>, grid, block, 0, s, ctrl, A, B, ld, n, k, tol); break;
+  case DOT_RZ: hipLaunchKernelGGL(pcg_dot_kernel<DOT_RZ>, grid, block, 0, s, ctrl, A, B, ld, n, k, tol); break;
+  case DOT_PQ: hipLaunchKernelGGL(pcg_dot_kernel<DOT_PQ>, grid, block, 0, s, ctrl, A, B, ld, n, k, tol); break;
+  default: hipLaunchKernelGGL(pcg_dot_kernel<DOT_RR>, grid, block, 0, s, ctrl, A, B, ld, n, k, tol); break;
+  }
+}
+
+void launch_pcg_lt_r(hipStream_t s, const PcgCtrl *ctrl, const double *L, long long ldl, long long n, long long m, const double *R,
+                     long long ldr, int t, double *T1, long long ldt) {
+  hipLaunchKernelGGL(pcg_lt_r_kernel, dim3((unsigned)m), dim3(256), 0, s, ctrl, L, ldl, n, R, ldr, t, T1, ldt);
+}
+
+void launch_pcg_precond(hipStream_t s, const PcgCtrl *ctrl, const double *L, long long ldl, long long n, long long m, const double *U,
+                        long long ldu, const double *R, double *Z, long long ld, int t, double delta) {
+  hipLaunchKernelGGL(pcg_precond_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ctrl, L, ldl, n, m, U, ldu, R, Z, ld, t, delta);
+}
+
+void launch_pcg_p(hipStream_t s, const PcgCtrl *ctrl, const double *Z, double *P, long long ld, long long n, int t, int first) {
+  hipLaunchKernelGGL(pcg_p_kernel, dim3((unsigned)((n + 255) / 256), t), dim3(256), 0, s, ctrl, Z, P, ld, n, first);
+}
+
+void launch_pcg_xr(hipStream_t s, const PcgCtrl *ctrl, double *X, long long ldx, double *R, const double *P, const double *Q, long long ld,
+                   long long n, int t) {
+  hipLaunchKernelGGL(pcg_xr_kernel, dim3((unsigned)((n + 255) / 256), t), dim3(256), 0, s, ctrl, X, ldx, R, P, Q, ld, n);
+}
+
+void launch_pcg_diag_stats(hipStream_t s, const double *d, const double *yvar, long long n, double *stats) {
+  hipLaunchKernelGGL(pcg_diag_stats_kernel, dim3(1), dim3(1024), 0, s, d, yvar, n, stats);
+}
+
+void launch_pcg_shift(hipStream_t s, double *C, long long ldc, long long m, double delta) {
+  hipLaunchKernelGGL(pcg_shift_kernel, dim3((unsigned)((m + 255) / 256), (unsigned)m), dim3(256), 0, s, C, ldc, m, delta);
+}
+
+void launch_pcg_variance(hipStream_t s, const double *Kc, const double *S, long long ld, long long n, long long t, const double *prior,
+                         double *var) {
+  hipLaunchKernelGGL(pcg_variance_kernel, dim3((unsigned)t), dim3(256), 0, s, Kc, S, ld, n, prior, var);
+}
+
 }  // namespace agp
 
 using namespace agp;
@@ -245,6 +273,33 @@ struct agp_iterative_fit {
   }
 };
 
+namespace agp {
+
+void pcg_apply_preconditioner(hipStream_t s, const agp_iterative_fit *f, const PcgCtrl *ctrl, const double *R, double *Z, long long ld,
+                              int t, double *T1, long long ldt) {
+  const long long n = f->n, m = f->rank;
+  if (m > 0) {
+    launch_pcg_lt_r(s, ctrl, f->L.get(), f->ldl, n, m, R, ld, t, T1, ldt);
+    forward_solve_mat(s, f->mfac->A, m, f->mfac->lda, f->mfac->invd, T1, t, ldt);
+    backward_solve_mat(s, f->mfac->A, m, f->mfac->lda, f->mfac->invd, T1, t, ldt);
+  }
+  launch_pcg_precond(s, ctrl, f->L.get(), f->ldl, n, m, T1, ldt, R, Z, ld, t, f->delta);
+}
+
+PcgPrecondState iterative_precond_state(const agp_iterative_fit *f) {
+  PcgPrecondState st;
+  st.ctx = f->ctx;
+  st.n = f->n;
+  st.rank = f->rank;
+  st.ldl = f->ldl;
+  st.delta = f->delta;
+  st.L = f->L.get();
+  st.mfac = f->mfac;
+  return st;
+}
+
+}  // namespace agp
+
 namespace {
 
 struct IterDestroy {
@@ -268,7 +323,6 @@ int pcg_solve(agp_context_impl *ctx, const agp_iterative_fit *f, const double *B
   if (!h_look) { ctx->last_error = "agp_iterative: no pinned staging memory"; return AGP_ERR_HIP; }
   PcgCtrl *h_final = h_look + 2;
   hipEvent_t ev[2] = {ctx->ev_a, ctx->ev_b};
-  const unsigned rows = (unsigned)((n + 255) / 256);
   const FeatView xm = f->fit_view();
   int status = AGP_OK;
   for (long long c0 = 0; c0 < nrhs && status == AGP_OK; c0 += PCG_COLS) {
@@ -279,24 +333,19 @@ int pcg_solve(agp_context_impl *ctx, const agp_iterative_fit *f, const double *B
     AGP_HIP_CHECK(ctx, hipMemset2DAsync(Xc, sizeof(double) * (size_t)ldx, 0, sizeof(double) * (size_t)n, (size_t)t, s));
     AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(R, sizeof(double) * (size_t)ld, B + c0 * ldb, sizeof(double) * (size_t)ldb, sizeof(double) * (size_t)n,
                                         (size_t)t, hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(pcg_dot_kernel<DOT_BB>, dim3(t), dim3(PCG_DOT_THREADS), 0, s, ctrl, R, R, ld, n, 0, f->tolerance);
+    launch_pcg_dot(s, DOT_BB, ctrl, R, R, ld, n, t, 0, f->tolerance);
     long long blocks = 0;
     bool done = false;
     for (int k0 = 0; k0 < f->max_iterations && !done; k0 += PCG_LOOK, ++blocks) {
       const int k1 = k0 + PCG_LOOK < f->max_iterations ? k0 + PCG_LOOK : f->max_iterations;
       for (int k = k0; k < k1; ++k) {
-        if (m > 0) {
-          hipLaunchKernelGGL(pcg_lt_r_kernel, dim3((unsigned)m), dim3(256), 0, s, ctrl, f->L.get(), f->ldl, n, R, ld, t, T1, ldt);
-          forward_solve_mat(s, f->mfac->A, m, f->mfac->lda, f->mfac->invd, T1, t, ldt);
-          backward_solve_mat(s, f->mfac->A, m, f->mfac->lda, f->mfac->invd, T1, t, ldt);
-        }
-        hipLaunchKernelGGL(pcg_precond_kernel, dim3(rows), dim3(256), 0, s, ctrl, f->L.get(), f->ldl, n, m, T1, ldt, R, Z, ld, t, f->delta);
-        hipLaunchKernelGGL(pcg_dot_kernel<DOT_RZ>, dim3(t), dim3(PCG_DOT_THREADS), 0, s, ctrl, R, Z, ld, n, k, f->tolerance);
-        hipLaunchKernelGGL(pcg_p_kernel, dim3(rows, t), dim3(256), 0, s, ctrl, Z, P, ld, n, k == 0 ? 1 : 0);
+        pcg_apply_preconditioner(s, f, ctrl, R, Z, ld, t, T1, ldt);
+        launch_pcg_dot(s, DOT_RZ, ctrl, R, Z, ld, n, t, k, f->tolerance);
+        launch_pcg_p(s, ctrl, Z, P, ld, n, t, k == 0 ? 1 : 0);
         launch_gram_matvec(s, f->dprog.get(), &f->kernel.prog, xm, f->yvar.get(), P, ld, t, Q, ld, mvws, &ctrl->nan, &ctrl->active);
-        hipLaunchKernelGGL(pcg_dot_kernel<DOT_PQ>, dim3(t), dim3(PCG_DOT_THREADS), 0, s, ctrl, P, Q, ld, n, k, f->tolerance);
-        hipLaunchKernelGGL(pcg_xr_kernel, dim3(rows, t), dim3(256), 0, s, ctrl, Xc, ldx, R, P, Q, ld, n);
-        hipLaunchKernelGGL(pcg_dot_kernel<DOT_RR>, dim3(t), dim3(PCG_DOT_THREADS), 0, s, ctrl, R, R, ld, n, k, f->tolerance);
+        launch_pcg_dot(s, DOT_PQ, ctrl, P, Q, ld, n, t, k, f->tolerance);
+        launch_pcg_xr(s, ctrl, Xc, ldx, R, P, Q, ld, n, t);
+        launch_pcg_dot(s, DOT_RR, ctrl, R, R, ld, n, t, k, f->tolerance);
       }
       if (k1 == f->max_iterations) break;
       AGP_HIP_CHECK(ctx, hipMemcpyAsync(&h_look[blocks & 1], ctrl, sizeof(PcgCtrl), hipMemcpyDeviceToHost, s));
@@ -328,7 +377,7 @@ int build_preconditioner(agp_context_impl *ctx, agp_iterative_fit *f, const agp_
   AGP_HIP_CHECK(ctx, alloc_doubles(ws, (size_t)n + 4));
   double *stats_dev = ws.get() + n;
   launch_gram_diagonal(s, f->dprog.get(), f->fit_view(), ws.get());
-  hipLaunchKernelGGL(pcg_diag_stats_kernel, dim3(1), dim3(1024), 0, s, ws.get(), f->yvar.get(), n, stats_dev);
+  launch_pcg_diag_stats(s, ws.get(), f->yvar.get(), n, stats_dev);
   double stats[4];
   AGP_HIP_CHECK(ctx, hipMemcpyAsync(stats, stats_dev, sizeof(stats), hipMemcpyDeviceToHost, s));
   AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
@@ -362,7 +411,7 @@ int build_preconditioner(agp_context_impl *ctx, agp_iterative_fit *f, const agp_
   AGP_HIP_CHECK(ctx, M.alloc_cached(sizeof(double) * (size_t)ldm * (size_t)rank));
   AGP_HIP_CHECK(ctx, hipMemsetAsync(M.get(), 0, sizeof(double) * (size_t)ldm * (size_t)rank, s));
   launch_gemm_nt_sub(s, M.get(), ldm, f->L.get(), f->ldl, true, f->L.get(), f->ldl, true, rank, rank, n, false);
-  hipLaunchKernelGGL(pcg_shift_kernel, dim3((unsigned)((rank + 255) / 256), (unsigned)rank), dim3(256), 0, s, M.get(), ldm, rank, f->delta);
+  launch_pcg_shift(s, M.get(), ldm, rank, f->delta);
   return agp_factor_create(ctx, M.get(), rank, ldm, 0, AGP_DEVICE, &f->mfac);
 }
 
@@ -530,7 +579,7 @@ int agp_iterative_predict_marginal(agp_context *c, const agp_kernel *k, const ag
     slice.n = t;
     launch_gram(s, dprog, fit->train.v, slice, false, false, Kc, ld, nullptr, nullptr, &k->prog);
     if ((st = pcg_solve(ctx, fit, Kc, ld, t, S, ld, nullptr, nullptr)) != AGP_OK) return st;
-    hipLaunchKernelGGL(pcg_variance_kernel, dim3((unsigned)t), dim3(256), 0, s, Kc, S, ld, n, prior + j0, var + j0);
+    launch_pcg_variance(s, Kc, S, ld, n, t, prior + j0, var + j0);
   }
   return copy_out(ctx, var, M, variance, location);
 }
