@@ -206,7 +206,6 @@ static agp_context::Tuning read_tuning() {
   // only a width above 512 changes anything - the panels of an outer block are NB = 128 wide, and a 700-wide block would
   // end inside its last panel)
   if (t.fp64_nbo <= 512 || t.fp64_nbo % 128 != 0) t.fp64_nbo = 0;
-  t.bf16x3.kernel = (int)number("AGP_BF16X3_KERNEL", 2);
   t.bf16x3.lds_pad = (int)number("AGP_BF16X3_LDS_PAD", 8192);
   t.sparse_pivoted = flag("AGP_SPARSE_PIVOTED", false);
   t.predict_chunk = number("AGP_PREDICT_CHUNK", 0);
@@ -1037,24 +1036,12 @@ static int fit_create_impl(agp_context *c, const agp_kernel *k, const agp_featur
     AGP_HIP_CHECK(ctx, hipMemcpyAsync(vec, fit->z, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
     launch_gram(s, dprog, xm, xm, /*symmetric=*/true, /*lower_only=*/true, Kfull.mem, fit->lda, yvar_d, ctx->d_flags,
                 &k->prog);
-    // fp32-accurate products of the bulk updates: on the 16-bit matrix pipe from split planes of the panel, or
-    // - AGP_MIXED_BF16=0 - on the fp32 MFMA as in rounds 1-4
-    // default (round 6): from two fp16 planes of power-of-two-scaled rows (gemm_f16x2.hip); AGP_MIXED_F16=0: three bf16 planes
-    const bool planes16 = ctx->tune.mixed_bf16;
-    const bool f16 = planes16 && ctx->tune.mixed_f16;
-    req.variant = f16 ? 5 : (planes16 ? 4 : 3);
-    req.nbo_wide = (planes16 && ctx->tune.mixed_nbo > 512 && ctx->tune.mixed_nbo % 128 == 0) ? ctx->tune.mixed_nbo : 0;
-    if (f16 && ctx->f16_scales_n < n) {
-      const long long cap = round_up(n, 2);
-      ctx->f16_scales_n = ctx->f16_scales.reserve(sizeof(double) * 2 * (size_t)cap) == 0 ? cap : 0;
-      if (!ctx->f16_scales_n) (void)hipGetLastError();  // (factor_lower falls back to the bf16 planes)
-    }
-    {  // two panel copies of (n rows + padding) x 512 (chol.hip, factor_lower): fp32, or three bf16 planes (two fp16 planes fit in the
-       // same space: the fall-back from fp16 to bf16 planes needs no second allocation); kept in the context
-      const size_t want = planes16 ? 2 * bf16x3_bytes(n, req.nbo_wide > 512 ? req.nbo_wide : 512)
-                                   : sizeof(float) * 2 * ((size_t)n + 16) * 512;
-      if (ctx->p32.reserve(want) != 0) (void)hipGetLastError();  // (the kernels round the operands themselves then)
-    }
+    // fp32-accurate products of the bulk updates: on the 16-bit matrix pipe from split planes of the panel - default
+    // (round 6): two fp16 planes of power-of-two-scaled rows; AGP_MIXED_F16=0: three bf16 planes - or - AGP_MIXED_BF16=0 -
+    // on the fp32 MFMA as in rounds 1-4
+    req.products = !ctx->tune.mixed_bf16 ? BulkProducts::Fp32 : (ctx->tune.mixed_f16 ? BulkProducts::F16x2 : BulkProducts::Bf16x3);
+    req.nbo_wide = (uses_planes(req.products) && ctx->tune.mixed_nbo > 512 && ctx->tune.mixed_nbo % 128 == 0) ? ctx->tune.mixed_nbo : 0;
+    PanelStager::reserve(ctx, req.products, n, req.nbo_wide);
   }
   // The fp64 fit does not wait for the factorisation before it enqueues the backward substitution: one host round trip
   // (~0.1 ms) less; the status is read after the single synchronisation at the end, and a substitution through a factor

@@ -884,20 +884,22 @@ static void launch_potrf(hipStream_t s, double *A, long long lda, long long k0, 
 
 // trailing update C -= P P^T (lower tiles) bracketed by a HIP-event pair when
 // the caller collects per-launch timings (bench.py's roofline block)
+// (kernel: the selector of launch_trailing_update_as, -1: the fp64 default; ldp: of P and Q, 0: lda)
 static void timed_gemm(hipStream_t s, FactorTimers *timers, double *C, long long lda, const double *P,
-                       const double *Q, long long M, long long N, long long K, bool bulk, int variant = -1,
-                       const float *P32 = nullptr, long long ld32 = 0) {
+                       const double *Q, long long M, long long N, long long K, bool bulk, int kernel = -1,
+                       const float *P32 = nullptr, long long ld32 = 0, long long ldp = 0) {
+  if (ldp == 0) ldp = lda;
   // only the bulk trailing updates' trailing_update_kernel launches (their own kernel symbol) are
   // event-timed: they run on the second stream, where an event gap is off the critical path
   if (!bulk) {
-    launch_gemm_nt_sub(s, C, lda, P, lda, false, Q, lda, false, M, N, K, true);
+    launch_gemm_nt_sub(s, C, lda, P, ldp, false, Q, ldp, false, M, N, K, true);
     return;
   }
   BulkTiming bt;
   const bool timed = timers && timers->ev && timers->used + 2 <= timers->n_ev;
   if (timed) { bt.e0 = timers->ev[timers->used]; bt.e1 = timers->ev[timers->used + 1]; }
-  if (variant >= 0) launch_trailing_update_as(variant, s, C, lda, P, Q, lda, M, K, timed ? &bt : nullptr, P32, P32, ld32);
-  else launch_trailing_update(s, C, lda, P, Q, lda, M, K, timed ? &bt : nullptr);
+  if (kernel >= 0) launch_trailing_update_as(kernel, s, C, lda, P, Q, ldp, M, K, timed ? &bt : nullptr, P32, P32, ld32);
+  else launch_trailing_update(s, C, lda, P, Q, ldp, M, K, timed ? &bt : nullptr);
   if (timed && bt.flops > 0.) {
     timers->flops[timers->used / 2] = bt.flops;  // algorithmic flop: 2 K per covered C entry on or below the diagonal
     timers->used += 2;
@@ -1008,16 +1010,16 @@ FusedPrep panel_fused_prepare(agp_context *ctx, hipStream_t s, double *invd, lon
 }
 
 // What the schedule reads (factor_plan.h: FactorSwitches) - once per factorisation: the tuning and the buffers of the
-// context, and what is particular to this call - the request, the variant it resolved to, and the fills `prep` made for the
+// context, and what is particular to this call - the request, the products it resolved to, and the fills `prep` made for the
 // columns [.., upto) of the tile images `invd`.
-static FactorSwitches factor_switches(agp_context *ctx, const FactorRequest &req, int variant, const FusedPrep &prep,
+static FactorSwitches factor_switches(agp_context *ctx, const FactorRequest &req, BulkProducts products, const FusedPrep &prep,
                                       const double *invd, long long upto) {
   FactorSwitches sw;
   sw.panel_fused = ctx->tune.panel_fused; sw.step_below = ctx->tune.step_below; sw.merge_above = ctx->tune.merge_above;
   sw.step_slots = sw.step_below > 0 ? step_slots(ctx) : 0;
   sw.cus = ctx->cus;
   sw.have_masked_stream = ctx->stream_masked != nullptr;
-  apply_request(sw, req, variant, prep, invd, upto, ctx->tune.fp64_nbo, ctx->ev_inv && ctx->stream2);
+  apply_request(sw, req, products, prep, invd, upto, ctx->tune.fp64_nbo, ctx->ev_inv && ctx->stream2);
   sw.fused_buffers_ready = sw.fused_buffers_ready && ctx->d_zpub;
   sw.step_buffers_ready = sw.panel_fused && sw.fused_buffers_ready && ctx->d_dpub && ctx->dpub_cap * NB >= upto && ctx->d_rowcnt;
   return sw;
@@ -1132,7 +1134,7 @@ void panel_phase_public(agp_context *ctx, hipStream_t s, double *A, long long n,
   const long long step_below = ctx->tune.step_below;
   const bool step = kend == n && kend <= 65536 && step_fits(step_below, step_below > 0 ? step_slots(ctx) : 0, kend - K0);
   const FusedPrep prep = panel_fused_prepare(ctx, s, img, K0, kend, step);
-  const FactorSwitches sw = factor_switches(ctx, FactorRequest(), -1, prep, img, kend);  // (fp64, nothing else asked for)
+  const FactorSwitches sw = factor_switches(ctx, FactorRequest(), BulkProducts::Fp64, prep, img, kend);  // (fp64, nothing else asked for)
   panel_phase(ctx, s, A, n, lda, img, y, K0, kend, nullptr, sw, step && sw.step_buffers_ready);
 }
 
@@ -1180,52 +1182,104 @@ static void invert_wide_blocks(agp_context *ctx, double *W_all, long long bw, do
   (void)hipEventRecord(ctx->ev_inv, si);
 }
 
-// Mixed precision: ONE low-precision copy of a step's panel for all the tiles of U1 and of the bulk update - fp32
-// (variant 3), three bf16 planes (4, gemm_bf16x3.hip) or two fp16 planes of scaled rows (5, gemm_f16x2.hip).  Two
-// alternating buffers: the bulk update of step j still reads its copy while step j + 1 makes the next one; the copy of
-// step j + 2 is written after U2(j) has been waited for.  Without it every tile rounds the fp64 operands itself while it
-// stages them - twice the operand traffic of the fp32 kernel, which is what it waits for.
-struct StagedPanel {
-  int kind = 0;  // the variant whose copy this is: 3 (P32, ld32), 4 or 5 (P16); 0: none
-  const float *P32 = nullptr;
-  long long ld32 = 0;
-  const unsigned short *P16 = nullptr;
-};
-struct PanelStager {
-  agp_context *ctx;
-  int variant;
-  const double *rs16;  // variant 5: the row scales
-  bool flip = false;   // which of the two buffers is next
-  // P: the panel, rows x K (rows kend.. of the matrix).  Nothing is staged where the copy does not fit its buffer.
-  StagedPanel stage(hipStream_t s, const double *P, long long lda, long long rows, long long K, long long kend) {
-    StagedPanel out;
-    if (!ctx->p32) return out;
-    auto take = [&](auto *base) {  // (half the buffer, counted in elements of the copy's type)
-      auto *dst = base + (size_t)(flip ? 1 : 0) * (ctx->p32.bytes() / sizeof(*base) / 2);
-      flip = !flip;
-      return dst;
-    };
-    unsigned short *planes = reinterpret_cast<unsigned short *>(ctx->p32.get());
-    if (variant == 3) {
-      out.ld32 = (rows + 7) / 8 * 8;
-      if (out.ld32 % 512 == 0) out.ld32 += 8;
-      if (sizeof(float) * (size_t)out.ld32 * (size_t)K * 2 > ctx->p32.bytes()) return out;
-      float *dst = take(ctx->p32.get());
-      launch_convert_panel_f32(s, P, lda, rows, K, dst, out.ld32);
-      out.P32 = dst;
-    } else if (variant == 4 && K % 32 == 0 && 2 * bf16x3_bytes(rows, K) <= ctx->p32.bytes()) {
-      unsigned short *dst = take(planes);
-      launch_convert_panel_bf16x3(s, P, lda, rows, K, dst);
-      out.P16 = dst;
-    } else if (variant == 5 && f16x2_depth_ok(ctx->tune.f16x2, K) && 2 * f16x2_bytes(rows, K) <= ctx->p32.bytes()) {
-      unsigned short *dst = take(planes);
-      launch_convert_panel_f16x2(s, ctx->tune.f16x2, P, lda, rows, K, rs16 + kend, dst);
-      out.P16 = dst;
-    }
-    if (out.P32 || out.P16) out.kind = variant;
-    return out;
+// Mixed precision: the low-precision copy of a step's panel, its formats and its kernels (common.h: PanelStager, StagedPanel;
+// the split-plane kernels: gemm_split_planes.hip).  Everything that depends on the format is between here and record_step.
+void PanelStager::reserve(agp_context *ctx, BulkProducts requested, long long n, long long nbo_wide) {
+  if (requested == BulkProducts::F16x2 && ctx->f16_scales_n < n) {
+    const long long cap = (n + 1) / 2 * 2;
+    ctx->f16_scales_n = ctx->f16_scales.reserve(sizeof(double) * 2 * (size_t)cap) == 0 ? cap : 0;
+    if (!ctx->f16_scales_n) (void)hipGetLastError();
   }
-};
+  // two panel copies of (n rows + padding) x width: fp32, or three bf16 planes (two fp16 planes fit in the same space: the
+  // fall-back from fp16 to bf16 planes needs no second allocation); kept in the context
+  const long long width = nbo_wide > 512 ? nbo_wide : 512;
+  const size_t want = uses_planes(requested) ? 2 * split_planes_bytes(3, n, width) : sizeof(float) * 2 * ((size_t)n + 16) * (size_t)width;
+  if (ctx->panel_copies.reserve(want) != 0) (void)hipGetLastError();
+}
+
+BulkProducts PanelStager::begin(agp_context *ctx, hipStream_t s, BulkProducts requested, const double *A, long long lda, long long n) {
+  ctx_ = ctx;
+  products_ = requested;
+  rs_ = irs_ = nullptr;
+  if (requested == BulkProducts::F16x2) {
+    if (ctx->f16_scales && ctx->f16_scales_n >= n) {
+      rs_ = ctx->f16_scales;
+      irs_ = ctx->f16_scales + ctx->f16_scales_n;
+      launch_f16x2_row_scales(s, A, lda, n, ctx->f16_scales, ctx->f16_scales + ctx->f16_scales_n);
+    } else {
+      products_ = BulkProducts::Bf16x3;
+    }
+  }
+  return products_;
+}
+
+StagedPanel PanelStager::unstaged(const double *P, long long ldp) const {
+  StagedPanel out;
+  out.P_ = P; out.ldp_ = ldp;
+  return out;
+}
+
+StagedPanel PanelStager::stage(hipStream_t s, const double *P, long long ldp, long long rows, long long K, long long kend) {
+  StagedPanel out = unstaged(P, ldp);
+  const size_t bytes = ctx_->panel_copies.bytes();
+  if (!ctx_->panel_copies) return out;
+  auto take = [&](auto *base) {  // (half the buffer, counted in elements of the copy's type)
+    auto *dst = base + (size_t)(flip_ ? 1 : 0) * (bytes / sizeof(*base) / 2);
+    flip_ = !flip_;
+    return dst;
+  };
+  float *f32 = reinterpret_cast<float *>(ctx_->panel_copies.get());
+  unsigned short *planes = reinterpret_cast<unsigned short *>(ctx_->panel_copies.get());
+  const F16x2Tuning f16x2 = ctx_->tune.f16x2;
+  if (products_ == BulkProducts::Fp32) {
+    out.ld32_ = (rows + 7) / 8 * 8;
+    if (out.ld32_ % 512 == 0) out.ld32_ += 8;
+    if (sizeof(float) * (size_t)out.ld32_ * (size_t)K * 2 > bytes) return out;
+    float *dst = take(f32);
+    launch_convert_panel_f32(s, P, ldp, rows, K, dst, out.ld32_);
+    out.P32_ = dst;
+  } else if (products_ == BulkProducts::Bf16x3 && K % 32 == 0 && 2 * split_planes_bytes(3, rows, K) <= bytes) {
+    unsigned short *dst = take(planes);
+    launch_convert_panel_bf16x3(s, P, ldp, rows, K, dst);
+    out.P16_ = dst;
+  } else if (products_ == BulkProducts::F16x2 && f16x2_depth_ok(f16x2, K) && 2 * split_planes_bytes(2, rows, K) <= bytes) {
+    unsigned short *dst = take(planes);
+    launch_convert_panel_f16x2(s, f16x2, P, ldp, rows, K, rs_ + kend, dst);
+    out.P16_ = dst;
+    out.irs_ = irs_ + kend;
+  }
+  if (out.P16_) {
+    out.products_ = products_;
+    out.rows_ = rows;
+    out.f16x2_ = f16x2;
+    out.bf16x3_ = ctx_->tune.bf16x3;
+  }
+  return out;
+}
+
+void StagedPanel::apply(hipStream_t s, double *C, long long ldc, long long row_offset, long long M, long long N, long long K,
+                        FactorTimers *timers) const {
+  const bool bulk = M == N;
+  if (P16_) {
+    long long olen = 0;
+    const int *order = nullptr;
+    if (bulk) {
+      const int ntr = (int)((M + 127) / 128);
+      const long long tiles = (long long)ntr * (ntr + 1) / 2;
+      if (tiles >= 1024) order = bulk_tile_order(ntr, tiles, &olen);
+    }
+    if (products_ == BulkProducts::F16x2)
+      launch_update_f16x2(s, f16x2_, C, ldc, P16_, rows_, row_offset, row_offset, irs_, M, N, K, order, olen);
+    else
+      launch_update_bf16x3(s, bf16x3_, C, ldc, P16_, rows_, row_offset, row_offset, M, N, K, order, olen);
+    return;
+  }
+  // products of fp32-rounded panels on the fp32 MFMA path, fp64 subtraction: from the fp32 copy, or rounded by the kernel
+  const double *Q = P_ + row_offset;
+  const float *Q32 = P32_ ? P32_ + row_offset : nullptr;
+  if (bulk) timed_gemm(s, timers, C, ldc, Q, Q, M, N, K, true, /*kernel=*/3, Q32, ld32_, ldp_);
+  else launch_update_f32(s, C, ldc, Q, Q, ldp_, M, N, K, Q32, Q32, ld32_);
+}
 
 // The one place the record is filled from the plan: a step factor_lower has carried out, and the inversions that ran.
 static void record_step(ScheduleRecord &rec, const OuterStep &s, unsigned inverted) {
@@ -1248,24 +1302,16 @@ FactorOutcome factor_lower(agp_context *ctx, double *A, long long n, long long l
   bool have_u2 = false;
   FactorTimers *timers = req.timers;
   ctx->sched.reset_factor(n);
-  int variant = req.variant;
-  // variant 5 (fp16 x 2 products, gemm_f16x2.hip): power-of-two row scales from the diagonal, BEFORE the first panel overwrites it
-  const double *rs16 = nullptr, *irs16 = nullptr;
-  if (variant == 5) {
-    if (ctx->f16_scales && ctx->f16_scales_n >= n) {
-      launch_f16x2_row_scales(sa, A, lda, n, ctx->f16_scales, ctx->f16_scales + ctx->f16_scales_n);
-      rs16 = ctx->f16_scales;
-      irs16 = ctx->f16_scales + ctx->f16_scales_n;
-    } else {
-      variant = 4;
-    }
-  }
+  // mixed precision: what the low-precision copies need of the matrix BEFORE the first panel overwrites it, and the
+  // products in force
+  PanelStager stager;
+  const BulkProducts products = stager.begin(ctx, sa, req.products, A, lda, n);
+  const bool mixed = is_mixed(products);
   // (agp_fit_create has already planned and launched the fills together with its own: req.prep.  A caller that planned
   // and got nothing leaves the planning to this call, which gets the same answer.)
   const FusedPrep prep = req.prep.covers(invd, n) ? req.prep : panel_fused_prepare(ctx, sa, invd, 0, n, true);
-  const FactorSwitches sw = factor_switches(ctx, req, variant, prep, invd, n);
+  const FactorSwitches sw = factor_switches(ctx, req, products, prep, invd, n);
   FactorPlanner plan(n, sw);  // (sw.bs_done == 0: no wide block is inverted yet; plan.bs_done() counts them from here)
-  PanelStager stager{ctx, variant, rs16};
   // The bulk stream of a step - in the end phase the CU-masked one (OuterStep::masked): a bulk update that fills every CU (the
   // 64 x 64-tile kernel takes all 160 KB of LDS) keeps the panel kernels - 75-79 KB of LDS per workgroup - out until its
   // grid has drained: POTRF took 400-500 us instead of 30 (profiles/r02), panel chain and bulk update ran one after
@@ -1289,7 +1335,8 @@ FactorOutcome factor_lower(agp_context *ctx, double *A, long long n, long long l
     }
     const double *P = A + s.k0 * lda + kend;  // panel rows kend.., columns K0..kend
     if (kend > 0) {  // (the first step has no panel to apply)
-      const StagedPanel st = s.mixed_tall ? stager.stage(sa, P, lda, rows, K, kend) : StagedPanel();
+      // (mixed precision: U1 and the bulk update read ONE low-precision copy of this step's panel while it is tall)
+      const StagedPanel st = s.mixed_tall ? stager.stage(sa, P, lda, rows, K, kend) : stager.unstaged(P, lda);
       (void)hipEventRecord(ctx->ev_a, sa);                       // P(j) done
       if (s.bits & STEP_BIT_MERGED) {
         // Bulk-bound phase, fp64: U1(j) and U2(j) are ONE launch on the bulk stream - the whole trailing matrix, the tiles of
@@ -1318,19 +1365,14 @@ FactorOutcome factor_lower(agp_context *ctx, double *A, long long n, long long l
         // U2(j - 1) must be done before anything of step j touches the next block column
         if (have_u2) (void)hipStreamWaitEvent(sa, ctx->ev_b, 0);
         // U1: block column [kend, next_end), all rows below its diagonal
-        if (st.kind == 5) {
-          // mixed precision, fp16 x 2: U1 and the bulk update from the planes of this step's panel
-          launch_update_f16x2(sa, ctx->tune.f16x2, A + kend * lda + kend, lda, st.P16, rows, 0, 0, irs16 + kend, rows, next_end - kend, K);
-        } else if (st.kind == 4) {
-          // mixed precision, bf16 x 3: U1 and the bulk update from the planes of this step's panel
-          launch_update_bf16x3(sa, ctx->tune.bf16x3, A + kend * lda + kend, lda, st.P16, rows, 0, 0, rows, next_end - kend, K);
-        } else if (s.mixed_tall) {
-          // mixed precision: U1 on the fp32 MFMA path like the bulk update (products of fp32-rounded panels, fp64
-          // subtraction) while the block column is tall enough for 128 x 128 tiles to fill the chip
-          launch_update_f32(sa, A + kend * lda + kend, lda, P, P, lda, rows, next_end - kend, K, st.P32, st.P32, st.ld32);
+        if (s.mixed_tall) {
+          // mixed precision: U1 with low-precision products like the bulk update while the block column is tall enough
+          // for 128 x 128 tiles to fill the chip
+          st.apply(sa, A + kend * lda + kend, lda, 0, rows, next_end - kend, K, timers);
         } else if (s.handover_whole_trailing) {
           // hand-over to the step tail: the whole trailing matrix, on the chain stream, alone on the chip - the bulk kernel
-          timed_gemm(sa, timers, A + kend * lda + kend, lda, P, P, rows, rows, K, true, variant >= 4 ? 3 : variant);
+          if (mixed) st.apply(sa, A + kend * lda + kend, lda, 0, rows, rows, K, timers);
+          else timed_gemm(sa, timers, A + kend * lda + kend, lda, P, P, rows, rows, K, true);
         } else {
           timed_gemm(sa, timers, A + kend * lda + kend, lda, P, P, rows, next_end - kend, K, false);
         }
@@ -1345,21 +1387,9 @@ FactorOutcome factor_lower(agp_context *ctx, double *A, long long n, long long l
         if (!last) {
           if (!throttle || !host_wait_event(ctx->ev_a)) (void)hipStreamWaitEvent(sb, ctx->ev_a, 0);
           const double *Q = A + s.k0 * lda + next_end;
-          if (st.P16) {
-            const long long M2 = n - next_end;
-            const int ntr = (int)((M2 + 127) / 128);
-            const long long tiles = (long long)ntr * (ntr + 1) / 2;
-            long long olen = 0;
-            const int *order = tiles >= 1024 ? bulk_tile_order(ntr, tiles, &olen) : nullptr;
-            if (st.kind == 5)
-              launch_update_f16x2(sb, ctx->tune.f16x2, A + next_end * lda + next_end, lda, st.P16, rows, next_end - kend, next_end - kend, irs16 + kend, M2, M2, K,
-                                  order, olen);
-            else
-              launch_update_bf16x3(sb, ctx->tune.bf16x3, A + next_end * lda + next_end, lda, st.P16, rows, next_end - kend, next_end - kend, M2, M2, K, order, olen);
-          } else {
-            timed_gemm(sb, timers, A + next_end * lda + next_end, lda, Q, Q, n - next_end, n - next_end, K, true, variant >= 4 ? 3 : variant,
-                       st.P32 ? st.P32 + (next_end - kend) : nullptr, st.ld32);
-          }
+          const long long M2 = n - next_end;
+          if (mixed) st.apply(sb, A + next_end * lda + next_end, lda, next_end - kend, M2, M2, K, timers);
+          else timed_gemm(sb, timers, A + next_end * lda + next_end, lda, Q, Q, M2, M2, K, true);
           (void)hipEventRecord(ctx->ev_b, sb);
         }
         have_u2 = !last;

@@ -39,7 +39,7 @@ inline void dispatch_dim(int dim, F &&f) {
   else f(std::integral_constant<int, 8>{});
 }
 
-// Which split-plane kernels of the mixed-precision factorisation run and how (gemm_f16x2.hip, gemm_bf16x3.hip): part of a
+// Which split-plane kernels of the mixed-precision factorisation run and how (gemm_split_planes.hip): part of a
 // context's tuning, handed to their launchers by value
 struct F16x2Tuning {
   int lds_pad = 8192;  // AGP_F16X2_LDS_PAD: extra dynamic LDS per workgroup (bytes)
@@ -47,7 +47,6 @@ struct F16x2Tuning {
   int chunk = 32;      // AGP_F16X2_CHUNK: k per LDS stage and per plane chunk, 32 or 64 (fixes the layout of the planes)
 };
 struct Bf16x3Tuning {
-  int kernel = 2;      // AGP_BF16X3_KERNEL: 1: one workgroup per CU (first version), 2: two per CU
   int lds_pad = 8192;  // AGP_BF16X3_LDS_PAD: extra dynamic LDS per workgroup (bytes)
 };
 
@@ -94,9 +93,10 @@ struct agp_context {
   agp::ParkSlot pool_A;
   // ... and one cached exact-covariance buffer of the mixed-precision fit (its CG refinement multiplies with K itself)
   agp::ParkSlot pool_K;
-  // mixed-precision fits: two alternating fp32 copies of the current panel (rows x 512 each)
-  agp::GrowBuf<float> p32;
-  agp::GrowBuf<double> f16_scales;  // fp16 x 2 products (gemm_f16x2.hip): row scales r and 1 / r, f16_scales_n doubles each
+  // mixed-precision fits: two alternating low-precision copies of the current panel, in whichever format the fit's
+  // products take (fp32, or split 16-bit planes); reserved and handed out by PanelStager (chol.hip) alone
+  agp::GrowBuf<unsigned char> panel_copies;
+  agp::GrowBuf<double> f16_scales;  // fp16 x 2 products (gemm_split_planes.hip): row scales r and 1 / r, f16_scales_n doubles each
   long long f16_scales_n = 0;
   // ... and the fp32 copy of the factor that preconditions their refinement
   agp::ParkSlot pool_L32;
@@ -401,7 +401,7 @@ void launch_trailing_update_as(int variant, hipStream_t s, double *C, long long 
 void launch_trailing_update(hipStream_t s, double *C, long long ldc, const double *P, const double *Q,
                             long long ldp, long long M, long long K, BulkTiming *timing = nullptr);
 void read_bulk_probe(unsigned long long *out);   // gemm.hip: cycles and 100 MHz ticks of one tile of a -DAGP_BULK_STAMPS build (zeros otherwise)
-void read_bf16_probe(unsigned long long *out);   // gemm_bf16x3.hip: 8 words of a -DAGP_BF16_STAMPS build (zeros otherwise)
+void read_bf16_probe(unsigned long long *out);   // gemm_split_planes.hip: 8 words of a -DAGP_BF16_STAMPS build (zeros otherwise)
 void read_potrf_probe(unsigned long long *out);  // chol.hip: 4 x 32 cycle stamps of a -DAGP_POTRF_TIMING build (zeros otherwise)
 void launch_head_gate(hipStream_t s, const unsigned long long *done, unsigned long long expect, int *flags);  // chol.hip
 // the whole trailing matrix of an outer step in ONE launch, the next block column's tiles first and counted (gemm.hip)
@@ -409,16 +409,16 @@ void launch_trailing_update_merged(hipStream_t s, double *C, long long ldc, cons
                                    int head_cols, unsigned long long *head_done, long long *head_tiles, BulkTiming *timing = nullptr);
 void launch_update_f32(hipStream_t s, double *C, long long ldc, const double *P, const double *Q, long long ldp, long long M,
                        long long N, long long K, const float *P32 = nullptr, const float *Q32 = nullptr, long long ld32 = 0);
-// The bf16 x 3 path of the mixed-precision factorisation (gemm_bf16x3.hip): the panel of one outer step as three bf16
-// planes (hi + mid + lo = the value to fp32 accuracy), and C -= P[row_a ..] P[row_b ..]^T from them on the BF16 pipe
-size_t bf16x3_bytes(long long rows, long long K);
+// The split-plane paths of the mixed-precision factorisation (gemm_split_planes.hip).  bf16 x 3: the panel of one outer
+// step as three bf16 planes (hi + mid + lo = the value to fp32 accuracy), and C -= P[row_a ..] P[row_b ..]^T from them on
+// the BF16 pipe
+size_t split_planes_bytes(int planes, long long rows, long long K);  // `planes` planes of a rows x K panel, padding included
 void launch_convert_panel_bf16x3(hipStream_t s, const double *P, long long ldp, long long rows, long long K, unsigned short *planes);
 void launch_update_bf16x3(hipStream_t s, Bf16x3Tuning tune, double *C, long long ldc, const unsigned short *planes, long long panel_rows, long long row_a,
                           long long row_b, long long M, long long N, long long K, const int *order = nullptr, long long order_len = 0);
-// The fp16 x 2 path (gemm_f16x2.hip): power-of-two row scales from the diagonal (rs, irs = 1 / rs: n doubles each), the
+// fp16 x 2: power-of-two row scales from the diagonal (rs, irs = 1 / rs: n doubles each), the
 // panel of one outer step as two fp16 planes of the scaled rows, and C -= P[row_a ..] P[row_b ..]^T from them (three
 // v_mfma_f32_16x16x32_f16 per block; irs belongs to the panel's row 0)
-size_t f16x2_bytes(long long rows, long long K);
 void launch_f16x2_row_scales(hipStream_t s, const double *A, long long lda, long long n, double *rs, double *irs);
 void launch_convert_panel_f16x2(hipStream_t s, F16x2Tuning tune, const double *P, long long ldp, long long rows, long long K,
                                 const double *rs, unsigned short *planes);
@@ -430,4 +430,52 @@ void launch_update_f16x2(hipStream_t s, F16x2Tuning tune, double *C, long long l
 const int *bulk_tile_order(int ntr, long long tiles, long long *len);
 // P32 (rows x K, ld32) = (float) P: the fp32 copy of one outer step's panel for the fp32-product kernels
 void launch_convert_panel_f32(hipStream_t s, const double *P, long long ldp, long long rows, long long K, float *P32, long long ld32);
+
+// Mixed precision (chol.hip): ONE low-precision copy of a step's panel for all the tiles of U1 and of the bulk update, in
+// the format of the fit's BulkProducts (factor_plan.h) - fp32, three bf16 planes or two fp16 planes of scaled rows.
+// PanelStager owns the format: the buffers, the fall-backs, the layout; StagedPanel is one step's copy and launches the
+// kernel that reads it.  Without a copy (nothing reserved, or the panel does not fit) the fp32-product kernels round the
+// fp64 operands themselves while they stage them - twice their operand traffic, which is what they wait for.
+class StagedPanel {
+ public:
+  bool staged() const { return P32_ || P16_; }
+  // C (M x N, lower tiles; C(0, 0) at panel row row_offset, on the matrix diagonal) -= P[row_offset ..] P[row_offset ..]^T
+  // with low-precision products.  M == N is the bulk shape: the tiles in the XCD-aware order once there are 1024 of them,
+  // and `timers` as for every bulk launch (chol.hip: timed_gemm); the split-plane kernels are not timed.
+  void apply(hipStream_t s, double *C, long long ldc, long long row_offset, long long M, long long N, long long K,
+             FactorTimers *timers = nullptr) const;
+
+ private:
+  friend class PanelStager;
+  BulkProducts products_ = BulkProducts::Fp32;  // of the copy; without a copy: Fp32, rounded by the kernel itself
+  const double *P_ = nullptr;                   // the fp64 panel
+  long long ldp_ = 0, rows_ = 0;
+  const float *P32_ = nullptr;
+  long long ld32_ = 0;
+  const unsigned short *P16_ = nullptr;
+  const double *irs_ = nullptr;                 // F16x2: 1 / r of the panel's rows
+  F16x2Tuning f16x2_;
+  Bf16x3Tuning bf16x3_;
+};
+class PanelStager {
+ public:
+  // The context's two alternating buffers for fits of n rows and outer blocks up to max(512, nbo_wide) columns, sized for
+  // the largest format `requested` may fall back to, and the row scales of F16x2.  A reservation that fails clears the HIP
+  // error: no scales - begin() resolves to Bf16x3; no buffers - nothing is staged.
+  static void reserve(agp_context *ctx, BulkProducts requested, long long n, long long nbo_wide);
+  // Before the first panel of a factorisation of A (n x n): the fp16 row scales from its diagonal, which the panels
+  // overwrite.  Returns the products in force.
+  BulkProducts begin(agp_context *ctx, hipStream_t s, BulkProducts requested, const double *A, long long lda, long long n);
+  // P: the panel, rows x K (rows kend.. of the matrix).  The two buffers alternate: the bulk update of step j still reads
+  // its copy while step j + 1 makes the next one; the copy of step j + 2 is written after U2(j) has been waited for.
+  // Nothing is staged where the copy does not fit its buffer or K is no whole number of the format's K chunks.
+  StagedPanel stage(hipStream_t s, const double *P, long long ldp, long long rows, long long K, long long kend);
+  StagedPanel unstaged(const double *P, long long ldp) const;  // the panel of a step too short for a copy to pay
+
+ private:
+  agp_context *ctx_ = nullptr;
+  BulkProducts products_ = BulkProducts::Fp64;
+  const double *rs_ = nullptr, *irs_ = nullptr;  // F16x2: the row scales r and 1 / r of the whole matrix
+  bool flip_ = false;                            // which of the two buffers is next
+};
 }  // namespace agp

@@ -735,30 +735,37 @@ AGP_DEBUG_API int agp_debug_mfma_shape(agp_context *ctx, int mode, int nacc, int
   return AGP_OK;
 }
 
-// fp16 x 2 planes of a host panel (gemm_f16x2.hip) with the row scales of a matrix whose diagonal is the squared row norm of
-// the panel - the bound a Cholesky factor's rows obey; *scales_out = [r | 1 / r] (M doubles each), *planes_out the planes
-static int make_f16x2_planes(agp_context *ctx, const double *hP, long long ldp, const double *dP, long long M, long long K,
-                             double **scales_out, unsigned short **planes_out) {
-  std::vector<double> diag((size_t)M, 0.);
+// The panel of a probe (host copy hP, device copy dP: rows x K) staged as the mixed fit stages a step's panel - through the
+// fit's own PanelStager and the context's buffers.  The fp16 row scales come from a diagonal of the panel's squared row
+// norms - the bound a Cholesky factor's rows obey.  A probe runs the products it names: a fall-back is an error.
+static int stage_probe_panel(agp_context *ctx, agp::BulkProducts products, const double *hP, const double *dP, long long ldp,
+                             long long rows, long long K, agp::StagedPanel *out) {
+  std::vector<double> diag((size_t)rows, 0.);
   for (long long k = 0; k < K; ++k)
-    for (long long i = 0; i < M; ++i) diag[(size_t)i] += hP[i + k * ldp] * hP[i + k * ldp];
-  double *d_diag = nullptr;
-  AGP_HIP_CHECK(ctx, hipMalloc(&d_diag, sizeof(double) * (size_t)M));
-  AGP_HIP_CHECK(ctx, hipMalloc(scales_out, sizeof(double) * 2 * (size_t)M));
-  AGP_HIP_CHECK(ctx, hipMalloc(planes_out, f16x2_bytes(M, K)));
-  AGP_HIP_CHECK(ctx, hipMemcpy(d_diag, diag.data(), sizeof(double) * (size_t)M, hipMemcpyHostToDevice));
-  launch_f16x2_row_scales(ctx->stream, d_diag, 0, M, *scales_out, *scales_out + M);
-  launch_convert_panel_f16x2(ctx->stream, ctx->tune.f16x2, dP, ldp, M, K, *scales_out, *planes_out);
+    for (long long i = 0; i < rows; ++i) diag[(size_t)i] += hP[i + k * ldp] * hP[i + k * ldp];
+  agp::DevMem<double> d_diag;
+  AGP_HIP_CHECK(ctx, d_diag.alloc_plain(sizeof(double) * (size_t)rows));
+  AGP_HIP_CHECK(ctx, hipMemcpy(d_diag, diag.data(), sizeof(double) * (size_t)rows, hipMemcpyHostToDevice));
+  agp::PanelStager::reserve(ctx, products, rows, K);
+  agp::PanelStager stager;
+  const bool in_force = stager.begin(ctx, ctx->stream, products, d_diag, 0, rows) == products;
+  if (in_force) *out = stager.stage(ctx->stream, dP, ldp, rows, K, 0);
   AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-  (void)hipFree(d_diag);
+  if (!in_force || !out->staged()) {
+    ctx->last_error = "the panel copy of a probe was not staged";
+    return AGP_ERR_HIP;
+  }
   return AGP_OK;
 }
 
 // Bulk trailing update C (M x M, lower tiles) -= P P^T on host data.  variant 0: MFMA kernel,
-// 2: DPP-broadcast VALU kernel.
+// 2: DPP-broadcast VALU kernel; 13 / 14 / 15: the fp32-product kernel on an fp32 copy of the panel / the bf16 x 3 kernel on
+// its three bf16 planes / the fp16 x 2 kernel on the two fp16 planes of its scaled rows, staged and applied as the mixed fit does.
 AGP_DEBUG_API int agp_debug_trailing_update(agp_context *ctx, double *C, int64_t ldc, const double *P, int64_t ldp, int64_t M,
                               int64_t K, int variant) {
   if (!ctx) return AGP_ERR_INVALID_ARGUMENT;
+  const agp::BulkProducts products = variant == 13 ? agp::BulkProducts::Fp32 : variant == 14 ? agp::BulkProducts::Bf16x3
+                                   : variant == 15 ? agp::BulkProducts::F16x2 : agp::BulkProducts::Fp64;
   AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
   const size_t cb = sizeof(double) * (size_t)ldc * (size_t)M;
   const size_t pb = sizeof(double) * (size_t)ldp * (size_t)K;
@@ -768,35 +775,10 @@ AGP_DEBUG_API int agp_debug_trailing_update(agp_context *ctx, double *C, int64_t
   AGP_HIP_CHECK(ctx, hipMemcpy(dC, C, cb, hipMemcpyHostToDevice));
   AGP_HIP_CHECK(ctx, hipMemcpy(dP, P, pb, hipMemcpyHostToDevice));
   int st = AGP_OK;
-  float *dP32 = nullptr;
-  if (variant == 13) {  // the fp32-product kernel (3) reading an fp32 copy of the panel, as the mixed fit runs it
-    const long long ld32 = (M + 7) / 8 * 8 + 8;
-    AGP_HIP_CHECK(ctx, hipMalloc(&dP32, sizeof(float) * (size_t)ld32 * (size_t)K));
-    launch_convert_panel_f32(ctx->stream, dP, ldp, M, K, dP32, ld32);
-    launch_trailing_update_as(3, ctx->stream, dC, ldc, dP, dP, ldp, M, K, nullptr, dP32, dP32, ld32);
-  } else if (variant == 14) {  // the bf16 x 3 kernel on the three bf16 planes of the panel, as the mixed fit runs it (gemm_bf16x3.hip)
-    unsigned short *planes = nullptr;
-    AGP_HIP_CHECK(ctx, hipMalloc(&planes, bf16x3_bytes(M, K)));
-    launch_convert_panel_bf16x3(ctx->stream, dP, ldp, M, K, planes);
-    const int ntr = (int)((M + 127) / 128);
-    const long long tiles = (long long)ntr * (ntr + 1) / 2;
-    long long olen = 0;
-    const int *order = tiles >= 1024 ? bulk_tile_order(ntr, tiles, &olen) : nullptr;
-    launch_update_bf16x3(ctx->stream, ctx->tune.bf16x3, dC, ldc, planes, M, 0, 0, M, M, K, order, olen);
-    AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(planes);
-  } else if (variant == 15) {  // the fp16 x 2 kernel on the two fp16 planes of the row-scaled panel, as the mixed fit runs it (gemm_f16x2.hip)
-    unsigned short *planes = nullptr;
-    double *scales = nullptr;
-    const int stp = make_f16x2_planes(ctx, P, ldp, dP, M, K, &scales, &planes);
-    if (stp != AGP_OK) return stp;
-    const int ntr = (int)((M + 127) / 128);
-    const long long tiles = (long long)ntr * (ntr + 1) / 2;
-    long long olen = 0;
-    const int *order = tiles >= 1024 ? bulk_tile_order(ntr, tiles, &olen) : nullptr;
-    launch_update_f16x2(ctx->stream, ctx->tune.f16x2, dC, ldc, planes, M, 0, 0, scales + M, M, M, K, order, olen);
-    AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(planes); (void)hipFree(scales);
+  if (agp::is_mixed(products)) {
+    agp::StagedPanel staged;
+    st = stage_probe_panel(ctx, products, P, dP, ldp, M, K, &staged);
+    if (st == AGP_OK) staged.apply(ctx->stream, dC, ldc, 0, M, M, K);
   } else if (variant >= 20 && variant < 30) {
     // the MERGED update of factor_lower with head_cols = variant - 20: the launch on the bulk stream, the gate kernel on
     // the chain stream (it must end - the head counted itself completely - although the launch it waits for is on another
@@ -820,11 +802,38 @@ AGP_DEBUG_API int agp_debug_trailing_update(agp_context *ctx, double *C, int64_t
   AGP_HIP_CHECK(ctx, hipGetLastError());
   AGP_HIP_CHECK(ctx, hipMemcpy(C, dC, cb, hipMemcpyDeviceToHost));
   (void)hipFree(dC); (void)hipFree(dP);
-  if (dP32) (void)hipFree(dP32);
   return st;
 }
 
-// The same on a stream restricted to a CU mask (hipExtStreamCreateWithCUMask): mask_words 32-bit words, bit i = CU i.
+// C (M x N lower tiles; C(0, 0) at row row_offset of the panel) -= P[row_offset ..] P[row_offset ..]^T with the products
+// named (3 / 4 / 5: factor_plan.h, BulkProducts) from a copy of the WHOLE panel P (rows x K) - staged and applied as
+// factor_lower does for the next block column (N < M, offset 0) and for the bulk update (M == N at an offset).  The host
+// C has ldc rows and N + 128 columns: the 128 guard columns behind the updated ones travel to the device and back, so that
+// the caller sees a kernel that writes beyond column N.
+AGP_DEBUG_API int agp_debug_staged_update(agp_context *ctx, double *C, int64_t ldc, const double *P, int64_t ldp, int64_t rows, int64_t K,
+                                          int products, int64_t row_offset, int64_t M, int64_t N) {
+  const agp::BulkProducts bp = (agp::BulkProducts)products;
+  if (!ctx || !C || !P || !agp::is_mixed(bp) || K <= 0 || N <= 0 || N > M || row_offset < 0 || row_offset + M > rows || ldc < M || ldp < rows)
+    return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const size_t cb = sizeof(double) * (size_t)ldc * (size_t)(N + 128);
+  const size_t pb = sizeof(double) * (size_t)ldp * (size_t)K;
+  agp::DevMem<double> dC, dP;
+  AGP_HIP_CHECK(ctx, dC.alloc_plain(cb));
+  AGP_HIP_CHECK(ctx, dP.alloc_plain(pb));
+  AGP_HIP_CHECK(ctx, hipMemcpy(dC, C, cb, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipMemcpy(dP, P, pb, hipMemcpyHostToDevice));
+  agp::StagedPanel staged;
+  const int st = stage_probe_panel(ctx, bp, P, dP, ldp, rows, K, &staged);
+  if (st != AGP_OK) return st;
+  staged.apply(ctx->stream, dC, ldc, row_offset, M, N, K);
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipMemcpy(C, dC, cb, hipMemcpyDeviceToHost));
+  return AGP_OK;
+}
+
+// The bulk trailing update on a stream restricted to a CU mask (hipExtStreamCreateWithCUMask): mask_words 32-bit words, bit i = CU i.
 // At the same time (optional, chain_reps > 0) the panel chain of an n = M block runs on the context's main stream:
 // *chain_us = its time per 512-wide panel phase while the masked bulk updates are in flight.
 AGP_DEBUG_API int agp_debug_time_masked_update(agp_context *ctx, int64_t M, int64_t K, int variant, int reps, const uint32_t *mask,
@@ -906,46 +915,27 @@ AGP_DEBUG_API int agp_debug_time_trailing_update(agp_context *ctx, int64_t M, in
   AGP_HIP_CHECK(ctx, hipEventCreate(&e0));
   AGP_HIP_CHECK(ctx, hipEventCreate(&e1));
   int st = AGP_OK;
-  float *dP32 = nullptr;  // variant 4: the fp32-product kernel on an fp32 copy of the panel
-  const long long ld32 = (M + 7) / 8 * 8 + 8;
-  if (variant == 4) {
-    AGP_HIP_CHECK(ctx, hipMalloc(&dP32, sizeof(float) * (size_t)ld32 * (size_t)K));
-    launch_convert_panel_f32(ctx->stream, dP, ld, M, K, dP32, ld32);
-  }
-  unsigned short *planes = nullptr;  // variant 5: the bf16 x 3 kernel on the panel's planes
-  const int ntr5 = (int)((M + 127) / 128);
-  long long olen = 0;
-  const int *order = nullptr;
-  if (variant == 5) {
-    AGP_HIP_CHECK(ctx, hipMalloc(&planes, bf16x3_bytes(M, K)));
-    launch_convert_panel_bf16x3(ctx->stream, dP, ld, M, K, planes);
-    const long long tiles = (long long)ntr5 * (ntr5 + 1) / 2;
-    if (tiles >= 1024) order = bulk_tile_order(ntr5, tiles, &olen);
-  }
-  double *scales = nullptr;  // variant 6: the fp16 x 2 kernel on the row-scaled panel's planes
-  if (variant == 6) {
-    const int stp = make_f16x2_planes(ctx, (zero_mode == 1 || zero_mode == 2) ? hz.data() : h.data(), ld, dP, M, K, &scales, &planes);
-    if (stp != AGP_OK) return stp;
-    const long long tiles = (long long)ntr5 * (ntr5 + 1) / 2;
-    if (tiles >= 1024) order = bulk_tile_order(ntr5, tiles, &olen);
-  }
+  // variants 4 / 5 / 6: the low-precision products of the mixed fit - fp32 panel copy / bf16 x 3 / fp16 x 2 of scaled rows -
+  // on a copy of the panel staged once
+  const agp::BulkProducts products = variant == 4 ? agp::BulkProducts::Fp32 : variant == 5 ? agp::BulkProducts::Bf16x3
+                                   : variant == 6 ? agp::BulkProducts::F16x2 : agp::BulkProducts::Fp64;
+  agp::StagedPanel staged;
+  if (agp::is_mixed(products))
+    st = stage_probe_panel(ctx, products, (zero_mode == 1 || zero_mode == 2) ? hz.data() : h.data(), dP, ld, M, K, &staged);
   for (int r = -2; r < reps && st == AGP_OK; ++r) {
     if (r == 0) AGP_HIP_CHECK(ctx, hipEventRecord(e0, ctx->stream));
-    if (variant == 4) launch_trailing_update_as(3, ctx->stream, dC, ld, dP, dP, ld, M, K, nullptr, dP32, dP32, ld32);
-    else if (variant == 5) launch_update_bf16x3(ctx->stream, ctx->tune.bf16x3, dC, ld, planes, M, 0, 0, M, M, K, order, olen);
-    else if (variant == 6) launch_update_f16x2(ctx->stream, ctx->tune.f16x2, dC, ld, planes, M, 0, 0, scales + M, M, M, K, order, olen);
+    if (agp::is_mixed(products)) staged.apply(ctx->stream, dC, ld, 0, M, M, K);
     else launch_trailing_update_as(variant, ctx->stream, dC, ld, dP, dP, ld, M, K);
   }
-  AGP_HIP_CHECK(ctx, hipEventRecord(e1, ctx->stream));
-  AGP_HIP_CHECK(ctx, hipEventSynchronize(e1));
-  float ms = 0.f;
-  AGP_HIP_CHECK(ctx, hipEventElapsedTime(&ms, e0, e1));
-  *ms_out = (double)ms / reps;
+  if (st == AGP_OK) {
+    AGP_HIP_CHECK(ctx, hipEventRecord(e1, ctx->stream));
+    AGP_HIP_CHECK(ctx, hipEventSynchronize(e1));
+    float ms = 0.f;
+    AGP_HIP_CHECK(ctx, hipEventElapsedTime(&ms, e0, e1));
+    *ms_out = (double)ms / reps;
+  }
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
   (void)hipFree(dC); (void)hipFree(dP);
-  if (dP32) (void)hipFree(dP32);
-  if (planes) (void)hipFree(planes);
-  if (scales) (void)hipFree(scales);
   return st;
 }
 
@@ -1238,7 +1228,7 @@ AGP_DEBUG_API int agp_debug_schedule(agp_context *ctx, int64_t *out, int64_t cap
 
 // The schedule factor_lower WOULD run for n rows under the given switches (factor_plan.h) - no context, no device.
 // switches (int64, the fields of FactorSwitches in order): panel_fused, step_below, merge_above, nbo_override, nbo_wide,
-// variant, step_slots, cus, have_masked_stream, headcnt_ready, step_buffers_ready, fused_buffers_ready, inv_requested,
+// products, step_slots, cus, have_masked_stream, headcnt_ready, step_buffers_ready, fused_buffers_ready, inv_requested,
 // bs_BW, bs_done.  `out` has the layout of agp_debug_schedule - [0] n, [1] steps, [2] steps beyond the record, [3..5] the
 // panel launches, [7] bs_done and [8] the inversion bits if every host-side wait succeeds, [20 + 2 i] end and bits of
 // step i - followed, from word 20 + 2 * 256 on, by five words per step: the inversion intents of OuterStep
@@ -1248,7 +1238,7 @@ AGP_DEBUG_API int agp_debug_factor_plan(const int64_t *switches, int64_t n, int6
   if (!switches || !out || n < 1 || cap < 0) return AGP_ERR_INVALID_ARGUMENT;
   agp::FactorSwitches sw;
   sw.panel_fused = switches[0] != 0; sw.step_below = switches[1]; sw.merge_above = switches[2];
-  sw.nbo_override = switches[3]; sw.nbo_wide = switches[4]; sw.variant = (int)switches[5];
+  sw.nbo_override = switches[3]; sw.nbo_wide = switches[4]; sw.products = (agp::BulkProducts)switches[5];
   sw.step_slots = switches[6]; sw.cus = switches[7];
   sw.have_masked_stream = switches[8] != 0; sw.headcnt_ready = switches[9] != 0;
   sw.step_buffers_ready = switches[10] != 0; sw.fused_buffers_ready = switches[11] != 0;

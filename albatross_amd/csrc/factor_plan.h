@@ -25,13 +25,20 @@ constexpr long long PLAN_NB = 128;          // panel width
 constexpr long long STEP_FIXED_CRITICAL = 10;  // step launch: the factoring workgroup and the nine that update its block
 constexpr long long MERGED_STEPS_MAX = 256;    // counters of the merged bulk updates, one per outer step
 
+// What the bulk updates of a factorisation multiply: the fp64 panels themselves, or - the mixed-precision fit - a
+// low-precision copy of each step's panel in one of three formats.  The values are what agp_debug_factor_plan receives
+// in switches[5]; they are NOT the kernel selector of launch_trailing_update_as (gemm.hip), which is a different thing.
+enum class BulkProducts : int { Fp64 = -1, Fp32 = 3, Bf16x3 = 4, F16x2 = 5 };
+inline bool uses_planes(BulkProducts p) { return p == BulkProducts::Bf16x3 || p == BulkProducts::F16x2; }  // split 16-bit planes
+inline bool is_mixed(BulkProducts p) { return p == BulkProducts::Fp32 || uses_planes(p); }
+
 // Everything the decisions read, as plain values (chol.hip: factor_switches fills it from the context's tuning and
 // buffers and from the FactorRequest of the call).
 struct FactorSwitches {
   bool panel_fused = true;                     // ctx->tune
   long long step_below = 4608, merge_above = 8704;
-  long long nbo_override = 0, nbo_wide = 0;    // nbo_wide: FactorRequest::nbo_wide (variants 4, 5) or AGP_FP64_NBO, already resolved
-  int variant = -1;                            // bulk-update kernel (FactorRequest::variant)
+  long long nbo_override = 0, nbo_wide = 0;    // nbo_wide: FactorRequest::nbo_wide (split planes) or AGP_FP64_NBO, already resolved
+  BulkProducts products = BulkProducts::Fp64;  // of the bulk updates (FactorRequest::products, or what it fell back to)
   long long step_slots = 0, cus = 256;         // workgroups of the step kernel the device holds at once / its CUs
   bool have_masked_stream = false;
   bool headcnt_ready = false;                  // the merged updates' counters are zeroed
@@ -53,8 +60,8 @@ struct FusedPrep {
 };
 struct FactorTimers;  // common.h (HIP events)
 struct FactorRequest {
-  int variant = -1;             // bulk-update kernel: -1 fp64 MFMA, 3 fp32 products, 4 bf16 x 3, 5 fp16 x 2 of scaled rows
-  long long nbo_wide = 0;       // mixed precision (4, 5): outer block width while many rows remain (0 / 512: default schedule)
+  BulkProducts products = BulkProducts::Fp64;  // of the bulk updates
+  long long nbo_wide = 0;       // mixed precision, split planes: outer block width while many rows remain (0 / 512: default schedule)
   // Early inversion of the wide diagonal blocks for the back substitution of a fit: factor_lower inverts the blocks that
   // are final on its (then idle) second stream while the chain-bound tail runs, and records ev_inv behind them.
   double *inv_W = nullptr;      // where the inverses go (nullptr: not requested)
@@ -64,14 +71,14 @@ struct FactorRequest {
 };
 struct FactorOutcome { long long inv_done = 0; };  // wide blocks inverted under the factorisation
 
-// The request's part of the switches (the context's part: chol.hip, factor_switches).  variant: req.variant, or what
+// The request's part of the switches (the context's part: chol.hip, factor_switches).  products: req.products, or what
 // factor_lower fell back to; prep: the fills in force for the tile images `img` up to column `upto`; fp64_nbo:
 // AGP_FP64_NBO (measurement switch); can_invert: the event and the stream of the inversion exist.  Every factorisation
 // enters with no wide block inverted: bs_done stays 0 (only agp_debug_factor_plan sets it, like nbo_override).
-inline void apply_request(FactorSwitches &sw, const FactorRequest &req, int variant, const FusedPrep &prep, const double *img,
+inline void apply_request(FactorSwitches &sw, const FactorRequest &req, BulkProducts products, const FusedPrep &prep, const double *img,
                           long long upto, long long fp64_nbo, bool can_invert) {
-  sw.variant = variant;
-  sw.nbo_wide = (variant == 4 || variant == 5) ? req.nbo_wide : fp64_nbo;
+  sw.products = products;
+  sw.nbo_wide = uses_planes(products) ? req.nbo_wide : fp64_nbo;
   sw.fused_buffers_ready = prep.covers(img, upto);
   sw.headcnt_ready = sw.fused_buffers_ready && prep.headcnt;
   sw.inv_requested = req.inv_W && can_invert;
@@ -161,9 +168,9 @@ class FactorPlanner {
     if (invertible() && bs_done_ == 0 && last && kend_ / bw > 0) bs_done_ = s.inv_last_step = kend_ / bw;
     // End phase: the bulk updates move to the CU-masked stream (chol.hip: factor_lower says why)
     s.masked = sw_.have_masked_stream && rows <= MASK_BELOW;
-    s.mixed_tall = (sw_.variant == 3 || sw_.variant == 4 || sw_.variant == 5) && rows >= U1_F32_ABOVE;
+    s.mixed_tall = is_mixed(sw_.products) && rows >= U1_F32_ABOVE;
     // Bulk-bound phase, fp64: U1(j) and U2(j) as ONE launch on the bulk stream, gated by a counter (factor_lower)
-    const bool merged = sw_.variant <= 0 && sw_.nbo_override == 0 && !step && !last && sw_.headcnt_ready && sw_.merge_above > 0 &&
+    const bool merged = !is_mixed(sw_.products) && sw_.nbo_override == 0 && !step && !last && sw_.headcnt_ready && sw_.merge_above > 0 &&
                         rows > sw_.merge_above && s.index < MERGED_STEPS_MAX && (s.next_end - kend_) % PLAN_NB == 0;
     if (merged) {
       s.bits = STEP_BIT_MERGED | (s.masked ? STEP_BIT_MASKED : 0u);

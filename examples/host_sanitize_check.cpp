@@ -485,16 +485,16 @@ void factor_plan_under_sanitizers() {
   agp::FactorRequest fp64_fit, mixed_fit;
   fp64_fit.inv_W = inverses; fp64_fit.inv_BW = 512;
   fp64_fit.prep.img = images; fp64_fit.prep.upto = 20480; fp64_fit.prep.headcnt = true;
-  mixed_fit.variant = 5; mixed_fit.nbo_wide = 1024;
+  mixed_fit.products = agp::BulkProducts::F16x2; mixed_fit.nbo_wide = 1024;
   agp::FactorSwitches inv = on, mixed = on;
   inv.inv_requested = inv.headcnt_ready = inv.fused_buffers_ready = false; inv.bs_BW = 0;
-  agp::apply_request(inv, fp64_fit, fp64_fit.variant, fp64_fit.prep, images, 20480, 0, true);
-  require(inv.inv_requested && inv.bs_BW == 512 && inv.bs_done == 0 && inv.headcnt_ready && inv.fused_buffers_ready && inv.variant == -1 &&
+  agp::apply_request(inv, fp64_fit, fp64_fit.products, fp64_fit.prep, images, 20480, 0, true);
+  require(inv.inv_requested && inv.bs_BW == 512 && inv.bs_done == 0 && inv.headcnt_ready && inv.fused_buffers_ready && inv.products == agp::BulkProducts::Fp64 &&
               inv.nbo_wide == 0, "request of a deferred fp64 fit");
   require(!fp64_fit.prep.covers(images, 20481) && !fp64_fit.prep.covers(inverses, 512) && !agp::FusedPrep().covers(nullptr, 0),
           "fills planned for other images or fewer columns do not count");
-  agp::apply_request(mixed, mixed_fit, mixed_fit.variant, mixed_fit.prep, images, 20480, 768, true);
-  require(!mixed.inv_requested && !mixed.headcnt_ready && !mixed.fused_buffers_ready && mixed.variant == 5 && mixed.nbo_wide == 1024,
+  agp::apply_request(mixed, mixed_fit, mixed_fit.products, mixed_fit.prep, images, 20480, 768, true);
+  require(!mixed.inv_requested && !mixed.headcnt_ready && !mixed.fused_buffers_ready && mixed.products == agp::BulkProducts::F16x2 && mixed.nbo_wide == 1024,
           "request of a mixed fit");
   mixed.fused_buffers_ready = true;  // (as if factor_lower had prepared the fills itself)
   for (const agp::FactorSwitches &sw : {on, off, inv, mixed})

@@ -208,11 +208,11 @@ AGP_API int agp_fit_create(agp_context *ctx, const agp_kernel *k, const agp_feat
  * of two taken from the diagonal (|L[i, k]| <= sqrt(A[i, i])), every panel is split
  * ONCE into two fp16 planes (h1 + h2 = the scaled value to 22 bits), a product is
  * the four partial products (four v_mfma_f32_16x16x32_f16 per 16 x 16 x 32 block,
- * each exact in fp32; csrc/gemm_f16x2.hip), accumulated in fp32 inside one launch,
+ * each exact in fp32; csrc/gemm_split_planes.hip), accumulated in fp32 inside one launch,
  * un-scaled exactly and subtracted from the fp64 matrix; the panel chain, the matrix
  * and every accumulation between outer steps stay fp64.  (AGP_MIXED_F16=0 selects
  * round 5's path, three bf16 planes and six products per block,
- * csrc/gemm_bf16x3.hip; AGP_MIXED_BF16=0 the oldest fallback: fp32-rounded panels on
+ * csrc/gemm_split_planes.hip; AGP_MIXED_BF16=0 the oldest fallback: fp32-rounded panels on
  * v_mfma_f32_16x16x4_f32.)  The information
  * vector is then refined in fp64: conjugate gradients on the exact fp64 covariance,
  * preconditioned with that factor, until ||y - K a||_2 <= tolerance * ||y||_2,
@@ -1379,11 +1379,10 @@ AGP_API int agp_set_profiling(agp_context *ctx, int enabled);
  *                            of its own behind an event (default 8704; 0: the round-5 schedule)
  *   AGP_GRAM_SOP=0           covariance trees through the stack interpreter only (parity tests run both evaluators)
  *   AGP_MIXED_F16=0          agp_fit_create_mixed forms its products from three bf16 planes (round 5) instead of two fp16 planes
- *   AGP_F16X2_TERMS=3        ... from two fp16 planes WITHOUT the h2 h2 product (3 % faster, log_det outside the bar: gemm_f16x2.hip)
+ *   AGP_F16X2_TERMS=3        ... from two fp16 planes WITHOUT the h2 h2 product (3 % faster, log_det outside the bar: gemm_split_planes.hip)
  *   AGP_F16X2_LDS_PAD=<b>    extra LDS bytes per workgroup of the fp16 x 2 kernel (default 8192: two per CU; 0: three)
  *   AGP_MIXED_BF16=0         agp_fit_create_mixed forms its fp32-accurate products on the fp32 MFMA instead of the 16-bit planes
- *   AGP_BF16X3_KERNEL=1      ... with the first bf16 x 3 tile kernel (one workgroup per CU) instead of the pair kernel
- *   AGP_BF16X3_LDS_PAD=<b>   extra LDS bytes per workgroup of the pair kernel (default 8192: two per CU; 0: three)
+ *   AGP_BF16X3_LDS_PAD=<b>   extra LDS bytes per workgroup of the bf16 x 3 kernel (default 8192: two per CU; 0: three)
  *   AGP_MIXED_NBO=<w>        outer block width of the mixed factorisation while > 8192 rows remain (default 512)
  *   AGP_SOLVE_NBO=<w>        outer block width of the forward substitution with many right-hand sides (predictions; default 512;
  *                            measured flat from 256 to 1024: profiles/r06/time_predict_marginal_nbo.txt)

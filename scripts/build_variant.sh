@@ -8,7 +8,7 @@ NAME=${1:?usage: build_variant.sh <name> [flags...]}
 shift
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 B=/tmp/agp_variant_build_$NAME
-rm -rf "$B" && mkdir -p "$B/albatross_amd" "$B/include" && cp -r "$ROOT/albatross_amd/csrc" "$B/albatross_amd/" && cp "$ROOT/include/albatross_amd.h" "$B/include/"
+rm -rf "$B" && mkdir -p "$B/albatross_amd" && cp -r "$ROOT/albatross_amd/csrc" "$B/albatross_amd/" && cp -r "$ROOT/include" "$B/"
 rm -rf "$B/albatross_amd/csrc/build"
 # (EXTRA, not HIPFLAGS: a HIPFLAGS given on the command line would switch off the per-file -ffp-contract=off of gram.o / ldlt.o)
 make -s -j8 -C "$B/albatross_amd/csrc" EXTRA="$*"

@@ -62,7 +62,7 @@ def test_config4_n32768_mixed(ctx):
     # this system (cond ~ 2e6, n = 32768): a few 1e-13 above
     assert res <= 2e-12 and 1 <= its <= 50, (its, res)
     assert rel(amx, a64) <= 1e-8                                   # the stated bar for the information vector
-    # log|K| of the mixed factor: the bulk products come from two fp16 planes of power-of-two-scaled rows (csrc/gemm_f16x2.hip:
+    # log|K| of the mixed factor: the bulk products come from two fp16 planes of power-of-two-scaled rows (csrc/gemm_split_planes.hip:
     # four exact partial products, fp32 accumulation inside a launch, fp64 between launches) - MEASURED 0.017 absolute = 3.7e-7
     # relative on this kernel at this size (profiles/r06/time_mixed.txt; round 5's bf16 x 3 products: 0.027), inside the
     # log-likelihood bar of BASELINE.md (|nll error| <= 1e-6 N, i.e. |log_det error| <= 2e-6 N = 0.066).  The bf16 x 3 path

@@ -1,6 +1,7 @@
 """GPU tests of the building blocks, through the debug entry points of the
 C-ABI library: MFMA lane map, the fp64 MFMA update kernel, the blocked LL^T."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -107,9 +108,9 @@ def test_trailing_update_large_tiles(ctx, dbg, M, K, variant):
     round as 64 x 64 quadrants at the head of the same launch, ragged edge tiles (M = 5900) on the old path.  Variant 0:
     fp64 MFMA; 3: fp32 products of operands rounded while staged; 13: fp32 products of an fp32 copy of the panel
     (launch_convert_panel_f32) - the two must agree bit for bit; 14 (round 5): fp32-accurate products on the BF16 pipe from
-    three bf16 planes of the panel (gemm_bf16x3.hip: hi + mid + lo, six partial products) - the same 2e-7 bar as the fp32
+    three bf16 planes of the panel (gemm_split_planes.hip: hi + mid + lo, six partial products) - the same 2e-7 bar as the fp32
     kernel (measured: both ~3e-8 of the scale), interior tiles with C prefetched and ragged / shallow ones without; 15
-    (round 6): products from two fp16 planes of power-of-two-scaled rows (gemm_f16x2.hip: h1 + h2, three partial products,
+    (round 6): products from two fp16 planes of power-of-two-scaled rows (gemm_split_planes.hip: h1 + h2, three partial products,
     scales from the rows' squared norms - the bound a Cholesky factor's rows obey), same bar."""
     rng = np.random.default_rng(M + K)
     ldc, ldp = M + 8, M + 10
@@ -155,7 +156,7 @@ def test_trailing_update_split_planes_badly_scaled_rows(ctx, dbg, variant):
 @pytest.mark.parametrize("variant,M,K,switch,value_a,value_b,b_differs", [
     (15, 256, 64, "AGP_F16X2_TERMS", "4", "3", True),
     (15, 130, 64, "AGP_F16X2_CHUNK", "32", "64", False),
-    (14, 256, 64, "AGP_BF16X3_KERNEL", "2", "1", False),
+    (14, 256, 64, "AGP_BF16X3_LDS_PAD", "8192", "0", False),
 ])
 def test_split_plane_settings_belong_to_the_context(make_ctx, dbg, monkeypatch, variant, M, K, switch, value_a, value_b, b_differs):
     """The settings of the split-plane kernels (AGP_F16X2_*, AGP_BF16X3_*) are part of the context they were read for:
@@ -190,6 +191,55 @@ def test_split_plane_settings_belong_to_the_context(make_ctx, dbg, monkeypatch, 
     assert np.array_equal(r1, r0)
     if b_differs:
         assert not np.array_equal(rb, r0)
+
+
+STAGED_GUARD_COLS = 128  # agp_debug_staged_update: columns of C behind the N updated ones that travel to the device and back
+
+
+@functools.lru_cache(maxsize=None)
+def staged_update_case(rows, row_offset, M, N, K):
+    """Input and fp64 reference of one agp_debug_staged_update call, made once per shape and read-only: C0 (ldc x
+    (N + guard columns), ldc = M + 8), the panel P (ldp x K, ldp = rows + 10), want = C - P[o:o+M] @ P[o:o+N].T (M x N),
+    the mask of the entries on or below the diagonal of C, and the scale of the error bar."""
+    rng = np.random.default_rng(rows + 3 * row_offset + 5 * M + 7 * N)
+    ldc, ldp = M + 8, rows + 10
+    C0 = np.asfortranarray(rng.standard_normal((ldc, N + STAGED_GUARD_COLS)))
+    P = np.asfortranarray(rng.standard_normal((ldp, K)))
+    A = P[row_offset:row_offset + M]
+    want = C0[:M, :N] - A @ A[:N].T
+    low = np.tril(np.ones((M, N), dtype=bool))
+    scale = np.abs(A).sum(axis=1).max() ** 2
+    for a in (C0, P, want, low):
+        a.setflags(write=False)
+    return C0, P, want, low, scale
+
+
+def check_staged_update(got, rows, row_offset, M, N, K):
+    """The assertions of test_staged_update_offsets_and_heads on the buffer `got` that came back."""
+    C0, _, want, low, scale = staged_update_case(rows, row_offset, M, N, K)
+    err = np.abs(got[:M, :N] - want)[low].max()
+    print(f"rows={rows} offset={row_offset} M={M} N={N}: max error {err / scale:.2e} of the scale")
+    assert err <= 2e-7 * scale
+    assert np.array_equal(got[M:], C0[M:])            # padding rows M .. ldc untouched
+    assert np.array_equal(got[:, N:], C0[:, N:])      # columns beyond N untouched
+
+
+@pytest.mark.parametrize("products", [3, 4, 5])
+@pytest.mark.parametrize("rows,row_offset,M,N", [(700, 0, 700, 128), (700, 128, 572, 572), (384, 256, 128, 128)])
+def test_staged_update_offsets_and_heads(ctx, dbg, rows, row_offset, M, N, products):
+    """The low-precision copy of a panel as the mixed fit stages and applies it (csrc/chol.hip: PanelStager, StagedPanel),
+    in the two shapes the other kernel tests leave out: the next block column (N < M: one tile column with a ragged last
+    tile row) and the bulk update at a non-zero row offset into the panel (ragged, and the last whole tile of the panel).
+    products 3 / 4 / 5: fp32 copy, three bf16 planes, two fp16 planes of scaled rows; K = 64 is two K chunks of 32.  The
+    bar and the scale are those of test_trailing_update_large_tiles."""
+    K = 64
+    C0, P, _, _, _ = staged_update_case(rows, row_offset, M, N, K)
+    got = C0.copy(order="F")
+    dbg.agp_debug_staged_update.restype = C.c_int
+    dbg.agp_debug_staged_update.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int,
+                                            C.c_int64, C.c_int64, C.c_int64]
+    assert dbg.agp_debug_staged_update(ctx._h, _p(got), got.shape[0], _p(P), P.shape[0], rows, K, products, row_offset, M, N) == 0
+    check_staged_update(got, rows, row_offset, M, N, K)
 
 
 @pytest.mark.parametrize("head_cols", [1, 4, 8])

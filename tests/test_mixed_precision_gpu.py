@@ -5,7 +5,7 @@ against the oracle and against the all-fp64 fit.
 
 Stated tolerances: information vector and predicted means 1e-8 relative (the same as the fp64 path: the refinement
 runs to a 1e-12 relative residual); predictive variances 1e-4 relative; log-determinant on the default path (fp16 x 2
-planes of scaled rows, four products: csrc/gemm_f16x2.hip): 4e-6 N absolute here (measured, profiles/r06/
+planes of scaled rows, four products: csrc/gemm_split_planes.hip): 4e-6 N absolute here (measured, profiles/r06/
 mixed_log_determinant_by_path.txt: 1.9e-6 N on Matern-5/2 + noise at N = 5300, 1.4e-6 N on config 3's SE(1,1) + noise(0.1) at
 N = 8192 - inside the 2e-6 N log-likelihood bar of the fp64 path, but close to it; BASELINE config 4's covariance at its own
 size: 0.5e-6 N, and tests/test_full_size_configs_gpu.py holds it and the other paths: include/albatross_amd.h, agp_fit_create_mixed)."""
@@ -189,7 +189,7 @@ def test_mixed_fit_wide_sweeps_property(ctx, n):
 def test_mixed_fit_badly_scaled_diagonal(ctx):
     """K = D (SE + 0.01 I) D with D spanning 1e-4 ... 1e+4 (a ScalingTerm factor, scaling_function.hpp:58-112, and the noise as
     per-target variances (0.1 d)^2, gp.hpp:64): the diagonal of the covariance spans 16 orders of magnitude.  The fp16 x 2
-    products of the mixed factorisation (csrc/gemm_f16x2.hip) scale every row by a power of two taken from the diagonal
+    products of the mixed factorisation (csrc/gemm_split_planes.hip) scale every row by a power of two taken from the diagonal
     first - without that the large rows overflow fp16 and the small ones vanish, and a scale taken from the wrong row
     would wreck the factor; with it the factor is as good a preconditioner as on the unscaled problem: same 1e-8
     agreement of the information vector with the all-fp64 fit (entry by entry in the unscaled problem's units), a handful
