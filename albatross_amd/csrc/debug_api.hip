@@ -4,12 +4,14 @@
 // libalbatross_amd_debug.so (the product objects + this file; csrc/Makefile), loaded by
 // albatross_amd._capi.load_debug().
 #include <algorithm>
+#include <climits>
 #include <cstdio>
 #include "common.h"
 #include "api_internal.h"
 #include "mfma_f64.h"
 #include "gram_matvec.h"
 #include "iterative_internal.h"
+#include "contract_internal.h"
 #include "shard_internal.h"
 #include "pub.h"
 #include "trsm_kernel.h"
@@ -2200,6 +2202,273 @@ AGP_DEBUG_API int agp_debug_iterative_precondition(agp_context *ctx, const agp_i
   AGP_HIP_CHECK(ctx, hipGetLastError());
   AGP_HIP_CHECK(ctx, hipMemcpy2D(Z, sizeof(double) * (size_t)ldz, Zd.p, sizeof(double) * (size_t)ld, sizeof(double) * (size_t)n, (size_t)t,
                                  hipMemcpyDeviceToHost));
+  return AGP_OK;
+}
+
+// ---- the gradient contraction kernels (contract.h: contract_tile) on the caller's weights ---------------------------------
+// The launchers of contract_internal.h, which the gradient entries call too: no fit, Gram or factorisation between the input
+// and the kernel.  Every host array comes with its length in doubles and is uploaded whole, padding and canaries included;
+// `out`, `partial` (and `combo`) are uploaded from the caller and downloaded whole, so what no kernel wrote comes back bit for
+// bit.  The features keep the is_measurement flag the caller set.
+}  // extern "C"
+
+namespace {
+int upload_doubles(agp_context *ctx, DevBuf<double> &d, const double *src, int64_t elems) {
+  AGP_HIP_CHECK(ctx, d.alloc((size_t)(elems > 0 ? elems : 1)));
+  if (elems > 0) AGP_HIP_CHECK(ctx, hipMemcpy(d.p, src, sizeof(double) * (size_t)elems, hipMemcpyHostToDevice));
+  return AGP_OK;
+}
+// a column-major rows x cols matrix at leading dimension ld fits `elems` doubles
+bool matrix_fits(int64_t rows, int64_t cols, int64_t ld, int64_t elems) {
+  return rows > 0 && cols > 0 && ld >= rows && elems >= ld * (cols - 1) + rows;
+}
+// the slot table of a probe, and the tangent columns its AGP_OP_SCALING slots read: n values per column at ldt
+int check_probe_slots(const agp_kernel *k, int n_slots, const agp_gradient_slot *slots, int64_t n, const double *tangents, int64_t ldt,
+                      int64_t tang_elems, int *ntc) {
+  if (n_slots < 0 || n_slots > AGP_MAX_GRADIENT_SLOTS || (n_slots > 0 && !slots)) return AGP_ERR_INVALID_ARGUMENT;
+  const int st = check_slots(k, n_slots, slots, ntc);
+  if (st != AGP_OK) return st;
+  if (*ntc > 0 && (!tangents || !matrix_fits(n, *ntc, ldt, tang_elems))) return AGP_ERR_INVALID_ARGUMENT;
+  return AGP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// nll_grad_contract_kernel<DIMP, LOO> + nll_grad_reduce_kernel, GRAD_GROUP slots per pass as contract_slots runs them:
+// out[slot] = scale * sum over the lower triangle of (C_ij - alpha_i alpha_j) dk_ij / dslot (off-diagonal pairs twice), or with
+// loo of (C_ij - (u_i alpha_j + alpha_i u_j) / 2) ...  C: n x n at ldc (only its lower triangle may be read), alpha and u: n
+// values (u is uploaded and handed to the kernel whatever loo says).  partial: at least lower_tiles(n) * GRAD_GROUP doubles,
+// comes back holding the partial[tile][GRAD_GROUP] of the LAST slot group.
+AGP_DEBUG_API int agp_debug_contract_dense(agp_context *ctx, const agp_kernel *k, const agp_features *x, int n_slots,
+                                           const agp_gradient_slot *slots, const double *tangents, int64_t ldt, int64_t tang_elems,
+                                           int loo, const double *C, int64_t ldc, int64_t c_elems, const double *alpha, const double *u,
+                                           double scale, double *out, int64_t out_elems, double *partial, int64_t partial_elems) {
+  if (!ctx || !k || !x || !C || !alpha || !u || !out || !partial) return AGP_ERR_INVALID_ARGUMENT;
+  int st = validate_features(x);
+  if (st != AGP_OK) return st;
+  const long long n = x->n;
+  if (n <= 0 || !matrix_fits(n, n, ldc, c_elems)) return AGP_ERR_INVALID_ARGUMENT;
+  int ntc = 0;
+  if ((st = check_probe_slots(k, n_slots, slots, n, tangents, ldt, tang_elems, &ntc)) != AGP_OK) return st;
+  const long long tiles = lower_tiles(n);
+  if (tiles * CT_THREADS > (long long)UINT_MAX || out_elems < n_slots || out_elems < 1 || partial_elems < tiles * GRAD_GROUP)
+    return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const DevProgram *dprog = nullptr;
+  if ((st = device_program(ctx, k, &dprog)) != AGP_OK) return st;
+  DeviceFeatures dx;
+  if ((st = to_device(ctx, x, false, &dx)) != AGP_OK) return st;
+  FeatView X = dx.v;
+  X.meas = x->is_measurement;
+  DevBuf<double> d_C, d_alpha, d_u, d_tang, d_out, d_partial;
+  if ((st = upload_doubles(ctx, d_C, C, c_elems)) != AGP_OK) return st;
+  if ((st = upload_doubles(ctx, d_alpha, alpha, n)) != AGP_OK) return st;
+  if ((st = upload_doubles(ctx, d_u, u, n)) != AGP_OK) return st;
+  if ((st = upload_doubles(ctx, d_tang, tangents, ntc > 0 ? tang_elems : 0)) != AGP_OK) return st;
+  if ((st = upload_doubles(ctx, d_out, out, out_elems)) != AGP_OK) return st;
+  if ((st = upload_doubles(ctx, d_partial, partial, partial_elems)) != AGP_OK) return st;
+  AGP_HIP_CHECK(ctx, hipDeviceSynchronize());  // (the null-stream copies above do not order with the context's stream)
+  hipStream_t s = ctx->stream;
+  for (int g0 = 0; g0 < n_slots; g0 += GRAD_GROUP) {
+    ContractArgs ca;
+    ca.C = d_C.p; ca.ldc = ldc; ca.alpha = d_alpha.p; ca.u = d_u.p; ca.partial = d_partial.p;
+    bool scaling[GRAD_GROUP];
+    const int cnt = fill_slot_group(k, n_slots, slots, g0, ca.slots, scaling);
+    for (int j = 0; j < GRAD_GROUP; ++j) ca.tang[j] = scaling[j] ? d_tang.p + (size_t)ca.slots.param[j] * (size_t)ldt : nullptr;
+    if (loo) launch_contract<true>(s, dprog, X, ca, tiles);
+    else launch_contract<false>(s, dprog, X, ca, tiles);
+    launch_grad_reduce(s, d_partial.p, tiles, cnt, scale, d_out.p + g0);
+  }
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipMemcpy(out, d_out.p, sizeof(double) * (size_t)out_elems, hipMemcpyDeviceToHost));
+  AGP_HIP_CHECK(ctx, hipMemcpy(partial, d_partial.p, sizeof(double) * (size_t)partial_elems, hipMemcpyDeviceToHost));
+  return AGP_OK;
+}
+
+// nll_grad_contract_batched_kernel<DIMP, LOO> + nll_grad_reduce_batched_kernel on descriptors that fill_contract_desc
+// builds: `count` problems, each with its own program, features (of any n_b <= n_pad and any dimension), slot table, tangent
+// columns and weight operands (arrays of `count` pointers and lengths as in agp_debug_contract_dense); the grid is that of a
+// batch padded to n_pad rows.  out[b * ldo + slot]; partial: [problem][slot group][tile][GRAD_GROUP] with
+// ceil(max n_slots / GRAD_GROUP) slot groups and lower_tiles(n_pad) tiles.
+AGP_DEBUG_API int agp_debug_contract_batched(agp_context *ctx, int count, const agp_kernel *const *kernels,
+                                             const agp_features *const *features, const int *n_slots,
+                                             const agp_gradient_slot *const *slots, const double *const *tangents, const int64_t *ldt,
+                                             const int64_t *tang_elems, int loo, const double *const *C, const int64_t *ldc,
+                                             const int64_t *c_elems, const double *const *alpha, const double *const *u, int64_t n_pad,
+                                             double scale, double *out, int64_t ldo, int64_t out_elems, double *partial,
+                                             int64_t partial_elems) {
+  if (!ctx || count <= 0 || count > 65535 || !kernels || !features || !n_slots || !slots || !tangents || !ldt || !tang_elems || !C ||
+      !ldc || !c_elems || !alpha || !u || !out || !partial || n_pad <= 0)
+    return AGP_ERR_INVALID_ARGUMENT;
+  int st, max_slots = 0, dim_max = 1;
+  std::vector<int> ntc((size_t)count, 0);
+  for (int b = 0; b < count; ++b) {
+    if (!kernels[b] || !features[b] || !C[b] || !alpha[b] || !u[b]) return AGP_ERR_INVALID_ARGUMENT;
+    if ((st = validate_features(features[b])) != AGP_OK) return st;
+    const long long nb = features[b]->n;
+    if (nb <= 0 || nb > n_pad || !matrix_fits(nb, nb, ldc[b], c_elems[b])) return AGP_ERR_INVALID_ARGUMENT;
+    if ((st = check_probe_slots(kernels[b], n_slots[b], slots[b], nb, tangents[b], ldt[b], tang_elems[b], &ntc[(size_t)b])) != AGP_OK)
+      return st;
+    if (n_slots[b] > max_slots) max_slots = n_slots[b];
+    if (features[b]->dim > dim_max) dim_max = features[b]->dim;
+  }
+  const long long tiles = lower_tiles(n_pad);
+  const int groups = (max_slots + GRAD_GROUP - 1) / GRAD_GROUP;
+  const long long part_per = (long long)groups * tiles * GRAD_GROUP;
+  if (tiles * CT_THREADS > (long long)UINT_MAX || tiles * count > (long long)UINT_MAX || ldo < max_slots || ldo < 1 ||
+      out_elems < ldo * (count - 1) + (max_slots > 0 ? max_slots : 1) || partial_elems < part_per * count || partial_elems < 1)
+    return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  std::vector<DeviceFeatures> dx((size_t)count);
+  std::vector<DevBuf<double>> d_C((size_t)count), d_alpha((size_t)count), d_u((size_t)count), d_tang((size_t)count);
+  DevBuf<double> d_out, d_partial;
+  DevBuf<ContractDesc> d_desc;
+  if ((st = upload_doubles(ctx, d_out, out, out_elems)) != AGP_OK) return st;
+  if ((st = upload_doubles(ctx, d_partial, partial, partial_elems)) != AGP_OK) return st;
+  std::vector<ContractDesc> desc((size_t)count);
+  for (int b = 0; b < count; ++b) {
+    const size_t i = (size_t)b;
+    const long long nb = features[b]->n;
+    if ((st = to_device(ctx, features[b], false, &dx[i])) != AGP_OK) return st;
+    if ((st = upload_doubles(ctx, d_C[i], C[b], c_elems[b])) != AGP_OK) return st;
+    if ((st = upload_doubles(ctx, d_alpha[i], alpha[b], nb)) != AGP_OK) return st;
+    if ((st = upload_doubles(ctx, d_u[i], u[b], nb)) != AGP_OK) return st;
+    if ((st = upload_doubles(ctx, d_tang[i], tangents[b], ntc[i] > 0 ? tang_elems[b] : 0)) != AGP_OK) return st;
+    FeatView X = dx[i].v;
+    X.meas = features[b]->is_measurement;
+    fill_contract_desc(desc[i], kernels[b], X, d_C[i].p, ldc[b], d_alpha[i].p, d_u[i].p, d_partial.p + (size_t)b * (size_t)part_per,
+                       n_slots[b], n_slots[b] > 0 ? slots[b] : nullptr, d_tang[i].p, ldt[b]);
+  }
+  AGP_HIP_CHECK(ctx, d_desc.alloc((size_t)count));
+  AGP_HIP_CHECK(ctx, hipMemcpy(d_desc.p, desc.data(), sizeof(ContractDesc) * (size_t)count, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipDeviceSynchronize());
+  hipStream_t s = ctx->stream;
+  if (groups > 0) {
+    if (loo) launch_contract_batched<true>(s, dim_max, d_desc.p, tiles, count, groups);
+    else launch_contract_batched<false>(s, dim_max, d_desc.p, tiles, count, groups);
+    launch_grad_reduce_batched(s, d_desc.p, tiles, count, groups, scale, d_out.p, ldo);
+  }
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipMemcpy(out, d_out.p, sizeof(double) * (size_t)out_elems, hipMemcpyDeviceToHost));
+  AGP_HIP_CHECK(ctx, hipMemcpy(partial, d_partial.p, sizeof(double) * (size_t)partial_elems, hipMemcpyDeviceToHost));
+  return AGP_OK;
+}
+
+// sparse_contract_kernel<DIMP> in one of its three modes, GRAD_GROUP slots per pass as agp_sparse_nll_gradient runs them.
+//   mode 0: rows = r, columns = c (same dimension), W: r->n x c->n at ldw, tang_r / tang_c the tangent columns at either set
+//   mode 1: c = nullptr (the columns are the very view of the rows), W: n x n at ldw, lower triangle
+//   mode 2: c = nullptr, G groups of the points off[g] .. off[g + 1] (off[0] >= 0, off[G] <= n, no empty group), slab g at
+//           W + woff[g] with leading dimension wld[g] >= its size, inside the w_elems doubles of W; ldw is not read
+// In modes 1 and 2 tang_c = nullptr hands the kernel tang_r for both sides.
+// out[slot]: the sum of that contraction's partials (nll_grad_reduce_kernel at scale 1).  combo[slot]: what
+// sparse_grad_reduce_kernel forms from three partial sets, this contraction's at position `which` (0, 1, 2) and the caller's
+// other_a (tiles_a x GRAD_GROUP) and other_b (tiles_b x GRAD_GROUP) at the two remaining positions in that order; they are
+// the same for every slot group.  partial: at least tiles * GRAD_GROUP doubles, comes back holding the last slot group's.
+AGP_DEBUG_API int agp_debug_contract_sparse(agp_context *ctx, const agp_kernel *k, const agp_features *r, const agp_features *c, int mode,
+                                            int n_slots, const agp_gradient_slot *slots, const double *tang_r, int64_t ldtr,
+                                            int64_t tr_elems, const double *tang_c, int64_t ldtc, int64_t tc_elems, const double *W,
+                                            int64_t ldw, int64_t w_elems, int64_t G, const int64_t *off, const int64_t *woff,
+                                            const int64_t *wld, int which, const double *other_a, int64_t tiles_a, const double *other_b,
+                                            int64_t tiles_b, double *out, int64_t out_elems, double *combo, int64_t combo_elems,
+                                            double *partial, int64_t partial_elems) {
+  if (!ctx || !k || !r || !W || !out || !combo || !partial || mode < 0 || mode > 2 || which < 0 || which > 2 || tiles_a < 0 ||
+      tiles_b < 0 || (tiles_a > 0 && !other_a) || (tiles_b > 0 && !other_b) || w_elems <= 0)
+    return AGP_ERR_INVALID_ARGUMENT;
+  if ((mode == 0) != (c != nullptr)) return AGP_ERR_INVALID_ARGUMENT;
+  int st = validate_features(r);
+  if (st != AGP_OK) return st;
+  if (c && (st = validate_features(c)) != AGP_OK) return st;
+  if (c && c->dim != r->dim) return AGP_ERR_INVALID_ARGUMENT;
+  const long long rows = r->n, cols = c ? c->n : r->n;
+  if (rows <= 0 || cols <= 0) return AGP_ERR_INVALID_ARGUMENT;
+  int ntc = 0, ntc_c = 0;
+  if ((st = check_probe_slots(k, n_slots, slots, rows, tang_r, ldtr, tr_elems, &ntc)) != AGP_OK) return st;
+  const bool own_tc = c != nullptr || tang_c != nullptr;
+  if (own_tc && (st = check_probe_slots(k, n_slots, slots, cols, tang_c, ldtc, tc_elems, &ntc_c)) != AGP_OK) return st;
+  long long tiles = 0, tiles_r = 0;
+  std::vector<long long> tab;  // off | woff | wld | tstart, G + 1 entries each
+  if (mode == 0) {
+    if (!matrix_fits(rows, cols, ldw, w_elems)) return AGP_ERR_INVALID_ARGUMENT;
+    tiles_r = (rows + CT - 1) / CT;
+    tiles = tiles_r * ((cols + CT - 1) / CT);
+  } else if (mode == 1) {
+    if (!matrix_fits(rows, rows, ldw, w_elems)) return AGP_ERR_INVALID_ARGUMENT;
+    tiles = lower_tiles(rows);
+  } else {
+    if (G <= 0 || !off || !woff || !wld || off[0] < 0 || off[G] > rows) return AGP_ERR_INVALID_ARGUMENT;
+    tab.assign(4 * (size_t)(G + 1), 0);
+    for (long long g = 0; g <= G; ++g) tab[(size_t)g] = off[g];
+    for (long long g = 0; g < G; ++g) {
+      const long long sg = off[g + 1] - off[g];
+      if (sg <= 0 || woff[g] < 0 || !matrix_fits(sg, sg, wld[g], w_elems - woff[g])) return AGP_ERR_INVALID_ARGUMENT;
+      tab[(size_t)(G + 1 + g)] = woff[g];
+      tab[(size_t)(2 * (G + 1) + g)] = wld[g];
+      tab[(size_t)(3 * (G + 1) + g)] = tiles;
+      tiles += lower_tiles(sg);
+    }
+    tab[(size_t)(3 * (G + 1) + G)] = tiles;
+  }
+  if (tiles * CT_THREADS > (long long)UINT_MAX || out_elems < n_slots || out_elems < 1 || combo_elems < n_slots || combo_elems < 1 ||
+      partial_elems < tiles * GRAD_GROUP)
+    return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const DevProgram *dprog = nullptr;
+  if ((st = device_program(ctx, k, &dprog)) != AGP_OK) return st;
+  DeviceFeatures dr, dc;
+  if ((st = to_device(ctx, r, false, &dr)) != AGP_OK) return st;
+  if (c && (st = to_device(ctx, c, false, &dc)) != AGP_OK) return st;
+  FeatView R = dr.v;
+  R.meas = r->is_measurement;
+  FeatView Cv = c ? dc.v : R;
+  if (c) Cv.meas = c->is_measurement;
+  DevBuf<double> d_W, d_tr, d_tc, d_a, d_b, d_out, d_combo, d_partial;
+  DevBuf<long long> d_tab;
+  if ((st = upload_doubles(ctx, d_W, W, w_elems)) != AGP_OK) return st;
+  if ((st = upload_doubles(ctx, d_tr, tang_r, ntc > 0 ? tr_elems : 0)) != AGP_OK) return st;
+  if ((st = upload_doubles(ctx, d_tc, tang_c, own_tc && ntc_c > 0 ? tc_elems : 0)) != AGP_OK) return st;
+  if ((st = upload_doubles(ctx, d_a, other_a, tiles_a * GRAD_GROUP)) != AGP_OK) return st;
+  if ((st = upload_doubles(ctx, d_b, other_b, tiles_b * GRAD_GROUP)) != AGP_OK) return st;
+  if ((st = upload_doubles(ctx, d_out, out, out_elems)) != AGP_OK) return st;
+  if ((st = upload_doubles(ctx, d_combo, combo, combo_elems)) != AGP_OK) return st;
+  if ((st = upload_doubles(ctx, d_partial, partial, partial_elems)) != AGP_OK) return st;
+  if (mode == 2) {
+    AGP_HIP_CHECK(ctx, d_tab.alloc(tab.size()));
+    AGP_HIP_CHECK(ctx, hipMemcpy(d_tab.p, tab.data(), sizeof(long long) * tab.size(), hipMemcpyHostToDevice));
+  }
+  AGP_HIP_CHECK(ctx, hipDeviceSynchronize());
+  hipStream_t s = ctx->stream;
+  const double *sets[3];
+  long long set_tiles[3];
+  for (int q = 0, o = 0; q < 3; ++q) {
+    if (q == which) { sets[q] = d_partial.p; set_tiles[q] = tiles; }
+    else { sets[q] = o == 0 ? d_a.p : d_b.p; set_tiles[q] = o == 0 ? tiles_a : tiles_b; ++o; }
+  }
+  for (int g0 = 0; g0 < n_slots; g0 += GRAD_GROUP) {
+    SparseContractArgs ca;
+    std::memset(static_cast<void *>(&ca), 0, sizeof(ca));
+    bool scaling[GRAD_GROUP];
+    const int cnt = fill_slot_group(k, n_slots, slots, g0, ca.slots, scaling);
+    for (int j = 0; j < GRAD_GROUP; ++j) {
+      ca.tr[j] = scaling[j] ? d_tr.p + (size_t)ca.slots.param[j] * (size_t)ldtr : nullptr;
+      ca.tc[j] = !own_tc ? ca.tr[j] : (scaling[j] ? d_tc.p + (size_t)ca.slots.param[j] * (size_t)ldtc : nullptr);
+    }
+    ca.W = d_W.p; ca.ldw = mode == 2 ? 0 : ldw; ca.tiles_r = tiles_r; ca.partial = d_partial.p; ca.mode = mode;
+    if (mode == 2) {
+      ca.off = d_tab.p; ca.woff = d_tab.p + (G + 1); ca.wld = d_tab.p + 2 * (G + 1); ca.tstart = d_tab.p + 3 * (G + 1);
+      ca.G = G;
+    }
+    launch_sparse_contract(s, dprog, R, Cv, ca, tiles);
+    launch_grad_reduce(s, d_partial.p, tiles, cnt, 1.0, d_out.p + g0);
+    launch_sparse_grad_reduce(s, sets[0], set_tiles[0], sets[1], set_tiles[1], sets[2], set_tiles[2], cnt, d_combo.p + g0);
+  }
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipMemcpy(out, d_out.p, sizeof(double) * (size_t)out_elems, hipMemcpyDeviceToHost));
+  AGP_HIP_CHECK(ctx, hipMemcpy(combo, d_combo.p, sizeof(double) * (size_t)combo_elems, hipMemcpyDeviceToHost));
+  AGP_HIP_CHECK(ctx, hipMemcpy(partial, d_partial.p, sizeof(double) * (size_t)partial_elems, hipMemcpyDeviceToHost));
   return AGP_OK;
 }
 

@@ -59,6 +59,7 @@
 #include "api_internal.h"
 #include "batch_front.h"
 #include "contract.h"
+#include "contract_internal.h"
 #include "cov_eval.h"
 #include "gemm_tiles.h"
 #include "logo_batch_plan.h"
@@ -106,15 +107,7 @@ void launch_rtr_lower(hipStream_t s, const double *R, long long ldr, long long n
 }
 
 // ---- contraction of a weight's lower triangle (contract.h): tile blockIdx.x of the row-major lower enumeration ----
-struct ContractArgs {
-  TangentSlots<GRAD_GROUP> slots;
-  const double *tang[GRAD_GROUP];  // AGP_OP_SCALING slot g: its tangent column (n values), else nullptr
-  const double *C;                 // K^-1 (LOO: S = C diag(b) C), lower triangle
-  long long ldc;
-  const double *alpha;
-  const double *u;                 // LOO only: u = C a
-  double *partial;                 // [tile][GRAD_GROUP]
-};
+// (ContractArgs: contract_internal.h)
 
 // The body of both the single-problem kernel and the batched one.  LOO: the weight of agp_loo_nll_gradient in place of
 // K^-1_ij - alpha_i alpha_j.
@@ -153,23 +146,7 @@ __global__ __launch_bounds__(256) void nll_grad_reduce_kernel(const double *__re
 }
 
 // ---- the batched contraction (agp_nll_gradient_batch, agp_loo_nll_gradient_batch) -----------------------------------
-// One descriptor per problem, built on the host for the call and uploaded with it: the program by value (not the
-// context's device program cache, whose slots later problems would overwrite), the features, K^-1 and alpha of the
-// problem's slabs, its slot table in groups of GRAD_GROUP and the tangent column of every AGP_OP_SCALING slot.
-constexpr int GRAD_GROUPS_MAX = (AGP_MAX_GRADIENT_SLOTS + GRAD_GROUP - 1) / GRAD_GROUP;
-struct ContractDesc {
-  DevProgram prog;
-  FeatView X;
-  const double *C;         // K_b^-1 (LOO: S_b = C_b diag(b) C_b), lower triangle
-  long long ldc;
-  const double *alpha;
-  const double *u;         // LOO only: u_b = C_b a_b
-  double *partial;         // [group][tile][GRAD_GROUP]
-  int n_slots;
-  int pad;
-  TangentSlots<GRAD_GROUP> slots[GRAD_GROUPS_MAX];
-  const double *tang[GRAD_GROUPS_MAX * GRAD_GROUP];
-};
+// One descriptor per problem, ContractDesc (contract_internal.h), built on the host for the call and uploaded with it.
 
 // grid: x = tile, y = problem, z = slot group.  DIMP covers the batch's largest dimension (load_point zero-pads);
 // problems with fewer slot groups leave their unused z-slices at once.  LOO: the weight of agp_loo_nll_gradient.
@@ -200,18 +177,32 @@ __global__ __launch_bounds__(256) void nll_grad_reduce_batched_kernel(const Cont
 }
 
 template <bool LOO>
-static void launch_contract(hipStream_t s, const DevProgram *P, const FeatView &X, const ContractArgs &a, long long tiles) {
+void launch_contract(hipStream_t s, const DevProgram *P, const FeatView &X, const ContractArgs &a, long long tiles) {
   dispatch_dim(X.dim, [&](auto D) {
     hipLaunchKernelGGL((nll_grad_contract_kernel<decltype(D)::value, LOO>), dim3((unsigned)tiles), dim3(CT_THREADS), 0, s, P, X, a);
   });
 }
+template void launch_contract<false>(hipStream_t, const DevProgram *, const FeatView &, const ContractArgs &, long long);
+template void launch_contract<true>(hipStream_t, const DevProgram *, const FeatView &, const ContractArgs &, long long);
+
+void launch_grad_reduce(hipStream_t s, const double *partial, long long tiles, int count, double scale, double *out) {
+  hipLaunchKernelGGL(nll_grad_reduce_kernel, dim3(GRAD_GROUP), dim3(256), 0, s, partial, tiles, count, scale, out);
+}
 
 template <bool LOO>
-static void launch_contract_batched(hipStream_t s, int dim_max, const ContractDesc *D, long long tiles, long long count, int groups) {
+void launch_contract_batched(hipStream_t s, int dim_max, const ContractDesc *D, long long tiles, long long count, int groups) {
   dispatch_dim(dim_max, [&](auto DIMP) {
     hipLaunchKernelGGL((nll_grad_contract_batched_kernel<decltype(DIMP)::value, LOO>), dim3((unsigned)tiles, (unsigned)count, (unsigned)groups),
                        dim3(CT_THREADS), 0, s, D, tiles);
   });
+}
+template void launch_contract_batched<false>(hipStream_t, int, const ContractDesc *, long long, long long, int);
+template void launch_contract_batched<true>(hipStream_t, int, const ContractDesc *, long long, long long, int);
+
+void launch_grad_reduce_batched(hipStream_t s, const ContractDesc *D, long long tiles, long long count, int groups, double scale,
+                                double *out, long long ldo) {
+  hipLaunchKernelGGL(nll_grad_reduce_batched_kernel, dim3((unsigned)(groups * GRAD_GROUP), (unsigned)count), dim3(256), 0, s, D, tiles, scale,
+                     out, ldo);
 }
 
 // ---- leave-one-out terms -----------------------------------------------------------------------------------------
@@ -695,6 +686,25 @@ int fill_slot_group(const agp_kernel *k, int n_slots, const agp_gradient_slot *s
   return cnt > 0 ? cnt : 0;
 }
 
+void fill_contract_desc(ContractDesc &d, const agp_kernel *k, const FeatView &X, const double *C, long long ldc, const double *alpha,
+                        const double *u, double *partial, int n_slots, const agp_gradient_slot *slots, const double *tcol, long long tld) {
+  std::memset(static_cast<void *>(&d), 0, sizeof(ContractDesc));
+  d.prog = k->prog;
+  d.X = X;
+  d.C = C;
+  d.ldc = ldc;
+  d.alpha = alpha;
+  d.u = u;
+  d.partial = partial;
+  d.n_slots = n_slots;
+  for (int grp = 0; grp < GRAD_GROUPS_MAX; ++grp) {
+    bool scaling[GRAD_GROUP];
+    fill_slot_group(k, n_slots, slots, grp * GRAD_GROUP, d.slots[grp], scaling);
+    for (int j = 0; j < GRAD_GROUP; ++j)
+      d.tang[grp * GRAD_GROUP + j] = scaling[j] ? tcol + (size_t)d.slots[grp].param[j] * (size_t)tld : nullptr;
+  }
+}
+
 int stage_tangents(agp_context *ctx, hipStream_t s, const double *tangents, long long ld, int location, long long n, int ntc,
                    double **cursor, const double **dev, long long *ld_dev) {
   *dev = tangents;
@@ -791,7 +801,7 @@ static void contract_slots(hipStream_t s, const agp_kernel *k, int n_slots, cons
     const int cnt = fill_slot_group(k, n_slots, slots, g0, ca.slots, scaling);
     for (int j = 0; j < GRAD_GROUP; ++j) ca.tang[j] = scaling[j] ? g.tang_d + (size_t)ca.slots.param[j] * (size_t)g.ldt_d : nullptr;
     launch_contract<LOO>(s, g.dprog, g.xm, ca, g.tiles);
-    hipLaunchKernelGGL(nll_grad_reduce_kernel, dim3(GRAD_GROUP), dim3(256), 0, s, g.partial, g.tiles, cnt, scale, g.grad_d + g0);
+    launch_grad_reduce(s, g.partial, g.tiles, cnt, scale, g.grad_d + g0);
   }
 }
 
@@ -1330,22 +1340,10 @@ static int gradient_batch_begin(agp_context_impl *ctx, int count, const agp_kern
   else { desc_pageable.resize((tables_bytes + sizeof(double) - 1) / sizeof(double)); tables_h = reinterpret_cast<char *>(desc_pageable.data()); }
   ContractDesc *desc_h = reinterpret_cast<ContractDesc *>(tables_h);
   for (int b = 0; b < count; ++b) {
-    ContractDesc &d = desc_h[b];
-    std::memset(static_cast<void *>(&d), 0, sizeof(ContractDesc));
-    d.prog = kernels[b]->prog;
-    d.X = gram.views[(size_t)b];
-    d.C = (weight_vector >= 0 ? g.vector(weight_vector) : A) + (size_t)b * (size_t)stride_A;
-    d.ldc = lda;
-    d.alpha = z + (size_t)b * (size_t)np2;
-    d.u = u_vector >= 0 ? g.vector(u_vector) + (size_t)b * (size_t)np2 : nullptr;
-    d.partial = a.partial + (size_t)b * (size_t)part_per;
-    d.n_slots = n_slots[b];
-    for (int grp = 0; grp < GRAD_GROUPS_MAX; ++grp) {
-      bool scaling[GRAD_GROUP];
-      fill_slot_group(kernels[b], n_slots[b], n_slots[b] > 0 ? slots[b] : nullptr, grp * GRAD_GROUP, d.slots[grp], scaling);
-      for (int j = 0; j < GRAD_GROUP; ++j)
-        d.tang[grp * GRAD_GROUP + j] = scaling[j] ? tcol[(size_t)b] + (size_t)d.slots[grp].param[j] * (size_t)tld[(size_t)b] : nullptr;
-    }
+    fill_contract_desc(desc_h[b], kernels[b], gram.views[(size_t)b],
+                       (weight_vector >= 0 ? g.vector(weight_vector) : A) + (size_t)b * (size_t)stride_A, lda, z + (size_t)b * (size_t)np2,
+                       u_vector >= 0 ? g.vector(u_vector) + (size_t)b * (size_t)np2 : nullptr, a.partial + (size_t)b * (size_t)part_per,
+                       n_slots[b], n_slots[b] > 0 ? slots[b] : nullptr, tcol[(size_t)b], tld[(size_t)b]);
   }
   const size_t copy_bytes = sizeof(CopyItem) * copies.size();
   if (padded) {
@@ -1442,8 +1440,7 @@ static int nll_gradient_batch(agp_context *c, int count, const agp_kernel *const
   const bool prof = ctx->profiling;
   if (g.groups > 0) {
     launch_contract_batched<false>(s, g.dim_max, g.desc_d, g.tiles, count, g.groups);
-    hipLaunchKernelGGL(nll_grad_reduce_batched_kernel, dim3((unsigned)(g.groups * GRAD_GROUP), (unsigned)count), dim3(256), 0, s, g.desc_d,
-                       g.tiles, 0.5, g.grad_d, g.ldgd);
+    launch_grad_reduce_batched(s, g.desc_d, g.tiles, count, g.groups, 0.5, g.grad_d, g.ldgd);
   }
   if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[5], s));
   st = gradient_batch_finish(ctx, g, count, n_slots,
@@ -1518,8 +1515,7 @@ static int loo_nll_gradient_batch(agp_context *c, int count, const agp_kernel *c
     launch_gtg_lower_batched(s, g.R, g.lda, g.stride_A, n, g.A, g.lda, g.stride_A, count);  // S_b = C_b diag(b) C_b over C_b
     if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[6], s));
     launch_contract_batched<true>(s, g.dim_max, g.desc_d, g.tiles, count, g.groups);
-    hipLaunchKernelGGL(nll_grad_reduce_batched_kernel, dim3((unsigned)(g.groups * GRAD_GROUP), (unsigned)count), dim3(256), 0, s, g.desc_d,
-                       g.tiles, 1.0, g.grad_d, g.ldgd);
+    launch_grad_reduce_batched(s, g.desc_d, g.tiles, count, g.groups, 1.0, g.grad_d, g.ldgd);
     if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[7], s));
   }
   st = gradient_batch_finish(ctx, g, count, n_slots, [](long long, double, double loo) { return loo; }, loo_nll, grad_loo_nll, ldg, u,
@@ -1636,8 +1632,7 @@ extern "C" int agp_logo_nll_gradient_batch(agp_context *c, int count, const agp_
     launch_hct_lower_batched(s, g.R, g.lda, g.stride_A, g.A, g.lda, g.stride_A, n, r.S, g.lda, g.stride_A, count);  // S_b = C_b B_b C_b
     if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[6], s));
     launch_contract_batched<true>(s, g.dim_max, g.desc_d, g.tiles, count, g.groups);
-    hipLaunchKernelGGL(nll_grad_reduce_batched_kernel, dim3((unsigned)(g.groups * GRAD_GROUP), (unsigned)count), dim3(256), 0, s, g.desc_d,
-                       g.tiles, 1.0, g.grad_d, g.ldgd);
+    launch_grad_reduce_batched(s, g.desc_d, g.tiles, count, g.groups, 1.0, g.grad_d, g.ldgd);
     if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[7], s));
   }
   bool want_terms = false;

@@ -37,6 +37,7 @@
 #include "batch_layout.h"
 #include "sparse_internal.h"
 #include "contract.h"
+#include "contract_internal.h"
 #include "cov_eval.h"
 
 using namespace agp;
@@ -111,25 +112,7 @@ __global__ __launch_bounds__(1024) void strided_sum_kernel(const double *__restr
 }
 
 // ---- the contractions: partial[tile][g] = sum over the tile's pairs of mult * w(row, col) dk(row, col) / dslot_g -----
-// One kernel, three shapes (mode):
-//   0  rectangular: rows = feature set R (the inducing points), columns = feature set C (the observations), weight W
-//      (rows x cols, ldw), every pair once.  Tiles column-block-major: id = bc * tiles_r + br.
-//   1  symmetric over one feature set (R == C): lower tiles only, pairs row >= col, off-diagonal pairs twice
-//   2  group blocks: tile ids run over the lower tiles of every group's s_g x s_g slab (tstart[g] = first tile of group
-//      g); rows and columns are the points off[g] .. off[g + 1] of ONE feature set, the weight slab of group g is
-//      W + woff[g] with leading dimension wld[g]
-struct SparseContractArgs {
-  TangentSlots<GRAD_GROUP> slots;
-  const double *tr[GRAD_GROUP];  // AGP_OP_SCALING slot g: its tangent column at the row features, else nullptr
-  const double *tc[GRAD_GROUP];  // ... at the column features
-  const double *W;
-  long long ldw;
-  long long tiles_r;           // mode 0: row tiles
-  const long long *off, *woff, *wld, *tstart;  // mode 2
-  long long G;
-  double *partial;             // [tile][GRAD_GROUP]
-  int mode;
-};
+// One kernel, three shapes (SparseContractArgs::mode, contract_internal.h).
 
 template <int DIMP>
 __global__ __launch_bounds__(CT_THREADS) void sparse_contract_kernel(const DevProgram *__restrict__ P, FeatView R, FeatView C,
@@ -156,13 +139,17 @@ __global__ __launch_bounds__(CT_THREADS) void sparse_contract_kernel(const DevPr
   contract_tile<DIMP>(P, a.slots, R, C, t, a.tr, a.tc, w, id, a.partial);
 }
 
-void launch_sparse_contract(hipStream_t s, const DevProgram *P, const FeatView &R, const FeatView &C, const SparseContractArgs &a,
+}  // namespace
+
+void agp::launch_sparse_contract(hipStream_t s, const DevProgram *P, const FeatView &R, const FeatView &C, const SparseContractArgs &a,
                             long long tiles) {
   if (tiles <= 0) return;
   dispatch_dim(R.dim, [&](auto D) {
     hipLaunchKernelGGL(sparse_contract_kernel<decltype(D)::value>, dim3((unsigned)tiles), dim3(CT_THREADS), 0, s, P, R, C, a);
   });
 }
+
+namespace {
 
 // out[g] = -1/2 S_blocks[g] - S_fu[g] - 1/2 S_uu[g], every S the sum of its tiles' partials in a fixed order
 // (reduce_partials); one workgroup per slot of the group.  The signs: the weights held are -bd(G), -(H E)^T, -W_uu.
@@ -183,6 +170,14 @@ __global__ __launch_bounds__(256) void sparse_grad_reduce_kernel(const double *_
   if (threadIdx.x == 0) out[g] = total;
 }
 
+}  // namespace
+
+void agp::launch_sparse_grad_reduce(hipStream_t s, const double *p0, long long t0, const double *p1, long long t1, const double *p2,
+                               long long t2, int count, double *out) {
+  hipLaunchKernelGGL(sparse_grad_reduce_kernel, dim3(GRAD_GROUP), dim3(256), 0, s, p0, t0, p1, t1, p2, t2, count, out);
+}
+
+namespace {
 
 // ---- what agp_sparse_nll_gradient and agp_sparse_held_out share: the group tables and, per group, R_g = L_g^-1 and the
 // lower triangle of bd(Kt^-1)_g = R_g^T R_g - N_g^T N_g in s_g x s_g slabs (h_roff / h_rld), for all three layouts of the
@@ -527,8 +522,7 @@ int agp_sparse_nll_gradient(agp_context *c, const agp_kernel *k, const agp_featu
     for (int j = 0; j < GRAD_GROUP; ++j) ca.tr[j] = ca.tc[j] = col_u[j];
     ca.W = Wn; ca.ldw = ldm; ca.partial = part_uu; ca.mode = 1;
     launch_sparse_contract(s, dprog, uv, uv, ca, tiles_uu);
-    hipLaunchKernelGGL(sparse_grad_reduce_kernel, dim3(GRAD_GROUP), dim3(256), 0, s, part_blocks, tiles_blocks, part_fu, tiles_fu, part_uu,
-                       tiles_uu, cnt, grad_d + g0);
+    launch_sparse_grad_reduce(s, part_blocks, tiles_blocks, part_fu, tiles_fu, part_uu, tiles_uu, cnt, grad_d + g0);
   }
   stage("gradient: contractions");
 
