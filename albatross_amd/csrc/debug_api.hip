@@ -835,6 +835,73 @@ AGP_DEBUG_API int agp_debug_staged_update(agp_context *ctx, double *C, int64_t l
   return AGP_OK;
 }
 
+// One outer step's panel of the mixed fit, staged and applied exactly as factor_lower does - PanelStager::begin on the
+// caller's diagonal, PanelStager::stage at kend = first_row, StagedPanel::apply - with everything the step leaves behind
+// handed back (tests/test_split_plane_kernels_gpu.py).
+//   products   3 / 4 / 5 (factor_plan.h, BulkProducts); P: the panel, rows x K (ldp)
+//   diag       first_row + rows diagonal entries of the matrix the panel belongs to: panel row 0 is matrix row first_row,
+//              so its fp16 scales are those of diag[first_row]
+//   C, ldc, row_offset, M, N   as agp_debug_staged_update, the 128 guard columns included; C == NULL: the copy is made and
+//              nothing is applied
+//   copy_out   (optional, copy_bytes long) the staged copy as it lies in the context's buffer: the planes, padding
+//              included (split_planes_bytes), or the fp32 copy (*ld32_out floats per column).  The buffer is filled with
+//              0xff bytes before the panel is staged, so whatever the conversion did not write comes back as 0xff.
+//   rs_out, irs_out   (optional, first_row + rows each) the row scales r and 1 / r (products 5 only)
+// Returns AGP_OK when the copy was staged in the format asked for, AGP_DEBUG_NOT_STAGED when PanelStager declined to make a
+// copy (K no whole number of chunks, no buffer) and AGP_DEBUG_OTHER_PRODUCTS when begin() resolved to another format; in
+// both of these nothing is applied and C comes back unchanged.
+enum { AGP_DEBUG_NOT_STAGED = 100, AGP_DEBUG_OTHER_PRODUCTS = 101 };
+AGP_DEBUG_API int agp_debug_split_plane_step(agp_context *ctx, int products, const double *P, int64_t ldp, int64_t rows, int64_t K,
+                                             const double *diag, int64_t first_row, double *C, int64_t ldc, int64_t row_offset,
+                                             int64_t M, int64_t N, void *copy_out, int64_t copy_bytes, int64_t *ld32_out,
+                                             double *rs_out, double *irs_out) {
+  const agp::BulkProducts bp = (agp::BulkProducts)products;
+  if (!ctx || !P || !diag || !agp::is_mixed(bp) || rows <= 0 || K <= 0 || ldp < rows || first_row < 0 || copy_bytes < 0) return AGP_ERR_INVALID_ARGUMENT;
+  if (C && (N <= 0 || N > M || row_offset < 0 || row_offset + M > rows || ldc < M)) return AGP_ERR_INVALID_ARGUMENT;
+  if ((rs_out || irs_out) && bp != agp::BulkProducts::F16x2) return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  const long long n = first_row + rows;
+  const size_t cb = C ? sizeof(double) * (size_t)ldc * (size_t)(N + 128) : 0;
+  const size_t pb = sizeof(double) * (size_t)ldp * (size_t)K;
+  agp::DevMem<double> dC, dP, d_diag;
+  if (C) {
+    AGP_HIP_CHECK(ctx, dC.alloc_plain(cb));
+    AGP_HIP_CHECK(ctx, hipMemcpy(dC, C, cb, hipMemcpyHostToDevice));
+  }
+  AGP_HIP_CHECK(ctx, dP.alloc_plain(pb));
+  AGP_HIP_CHECK(ctx, hipMemcpy(dP, P, pb, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, d_diag.alloc_plain(sizeof(double) * (size_t)n));
+  AGP_HIP_CHECK(ctx, hipMemcpy(d_diag, diag, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+  agp::PanelStager::reserve(ctx, bp, n, K);
+  // a new PanelStager hands out the first of the context's two buffers first
+  const size_t half = ctx->panel_copies.bytes() / 2;
+  if ((size_t)copy_bytes > half) return AGP_ERR_INVALID_ARGUMENT;
+  if (ctx->panel_copies && copy_bytes > 0) AGP_HIP_CHECK(ctx, hipMemsetAsync(ctx->panel_copies.get(), 0xFF, (size_t)copy_bytes, ctx->stream));
+  agp::PanelStager stager;
+  if (stager.begin(ctx, ctx->stream, bp, d_diag, 0, n) != bp) {
+    AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return AGP_DEBUG_OTHER_PRODUCTS;
+  }
+  const agp::StagedPanel staged = stager.stage(ctx->stream, dP, ldp, rows, K, first_row);
+  if (!staged.staged()) {
+    AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return AGP_DEBUG_NOT_STAGED;
+  }
+  if (C) staged.apply(ctx->stream, dC, ldc, row_offset, M, N, K);
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  if (C) AGP_HIP_CHECK(ctx, hipMemcpy(C, dC, cb, hipMemcpyDeviceToHost));
+  if (copy_out && copy_bytes > 0) AGP_HIP_CHECK(ctx, hipMemcpy(copy_out, ctx->panel_copies.get(), (size_t)copy_bytes, hipMemcpyDeviceToHost));
+  if (ld32_out) {  // (PanelStager::stage: whole groups of 8 rows, and no multiple of 512)
+    *ld32_out = (rows + 7) / 8 * 8;
+    if (*ld32_out % 512 == 0) *ld32_out += 8;
+  }
+  if (rs_out) AGP_HIP_CHECK(ctx, hipMemcpy(rs_out, ctx->f16_scales.get(), sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+  if (irs_out)
+    AGP_HIP_CHECK(ctx, hipMemcpy(irs_out, ctx->f16_scales.get() + ctx->f16_scales_n, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+  return AGP_OK;
+}
+
 // The bulk trailing update on a stream restricted to a CU mask (hipExtStreamCreateWithCUMask): mask_words 32-bit words, bit i = CU i.
 // At the same time (optional, chain_reps > 0) the panel chain of an n = M block runs on the context's main stream:
 // *chain_us = its time per 512-wide panel phase while the masked bulk updates are in flight.
