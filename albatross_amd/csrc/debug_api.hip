@@ -762,7 +762,9 @@ static int stage_probe_panel(agp_context *ctx, agp::BulkProducts products, const
 
 // Bulk trailing update C (M x M, lower tiles) -= P P^T on host data.  variant 0: MFMA kernel,
 // 2: DPP-broadcast VALU kernel; 13 / 14 / 15: the fp32-product kernel on an fp32 copy of the panel / the bf16 x 3 kernel on
-// its three bf16 planes / the fp16 x 2 kernel on the two fp16 planes of its scaled rows, staged and applied as the mixed fit does.
+// its three bf16 planes / the fp16 x 2 kernel on the two fp16 planes of its scaled rows, staged and applied as the mixed fit does;
+// 20 + h: the merged update with a head of h tile columns; 30 / 31: every tile a whole 128 x 128 workgroup, on the ring loop /
+// on the register-staged loop (launch_trailing_update_as) - shapes of a few tile rows reach the large tile bodies this way.
 AGP_DEBUG_API int agp_debug_trailing_update(agp_context *ctx, double *C, int64_t ldc, const double *P, int64_t ldp, int64_t M,
                               int64_t K, int variant) {
   if (!ctx) return AGP_ERR_INVALID_ARGUMENT;
@@ -955,6 +957,7 @@ AGP_DEBUG_API int agp_debug_time_masked_update(agp_context *ctx, int64_t M, int6
 }
 
 // Average milliseconds of `reps` bulk trailing updates of an M x M matrix (device-side random-ish data).
+// (variants 30 / 31 in alternation: the ring loop against the register-staged loop in one build, scripts/time_update_k.py)
 AGP_DEBUG_API int agp_debug_time_trailing_update(agp_context *ctx, int64_t M, int64_t K, int variant, int reps, double *ms_out) {
   if (!ctx || M <= 0 || K <= 0 || reps <= 0) return AGP_ERR_INVALID_ARGUMENT;
   AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));

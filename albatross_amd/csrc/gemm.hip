@@ -10,6 +10,8 @@
 // -> LDS (double buffered, one barrier per chunk); fragments are one
 // ds_read_b64 per lane from a [k][row] image padded to 144 doubles per k so
 // the two 16-lane halves of a 32-lane LDS group fall on disjoint banks.
+// (The whole interior tiles of the bulk update - trailing_update_kernel - load the same image global -> LDS directly
+// into a ring of four 8-deep stages instead: gemm_tiles.h, gemm_nt_sub_tile_ring.)
 // The MFMA "A" operand carries the C-column panel (pre-negated while staging)
 // and the MFMA "B" operand the C-row panel, so that a C/D register holds 16
 // CONSECUTIVE ROWS of one C column: epilogue accesses are 128-B segments of
@@ -93,6 +95,17 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_nt_ext_kernel(GemmArgs g
 // -DAGP_BULK_STAMPS (scripts/build_variant.sh bulk_stamps -DAGP_BULK_STAMPS; scripts/probe_bulk_clock.py): the workgroup in the
 // middle of the grid leaves the shader cycles (s_memtime) and the 100 MHz ticks (s_memrealtime) of its whole tile: the clock
 // the chip holds under the fp64 bulk update = 100 MHz x cycles / ticks.
+// -DAGP_BULK_RING=0 / -DAGP_RING_STAGES=S -DAGP_RING_CHUNK=CK (scripts/build_variant.sh): the product kernel on the
+// register-staged loop / another shape of the ring (S x CK <= 32: 4 x 8, 3 x 8, 2 x 16), for measurements.
+#ifndef AGP_BULK_RING
+#define AGP_BULK_RING 1
+#endif
+#ifndef AGP_RING_STAGES
+#define AGP_RING_STAGES 4
+#endif
+#ifndef AGP_RING_CHUNK
+#define AGP_RING_CHUNK 8
+#endif
 #ifdef AGP_BULK_STAMPS
 __device__ unsigned long long g_bulk_probe[4];
 void read_bulk_probe(unsigned long long *out) { (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_bulk_probe), sizeof(unsigned long long) * 4); }
@@ -100,8 +113,8 @@ void read_bulk_probe(unsigned long long *out) { (void)hipMemcpyFromSymbol(out, H
 void read_bulk_probe(unsigned long long *out) { for (int i = 0; i < 4; ++i) out[i] = 0; }
 #endif
 
-__global__ __launch_bounds__(GEMM_THREADS, 2) void trailing_update_kernel(GemmArgs g) {
-  __shared__ double lds[2 * 2 * GK * GLD];
+template <bool RING>
+__device__ __forceinline__ void trailing_update_body(const GemmArgs &g, double *lds) {
 #ifdef AGP_BULK_STAMPS
   const unsigned long long stamp_c0 = __builtin_amdgcn_s_memtime(), stamp_r0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -144,8 +157,12 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void trailing_update_kernel(GemmAr
       return;
     }
   }
-  if (tile_takes_cpf(g, bi, bj)) gemm_nt_sub_tile_cpf<false, false>(g, bi, bj, lds);
-  else gemm_nt_sub_tile<false, false>(g, bi, bj, lds);
+  if (tile_takes_cpf(g, bi, bj)) {
+    if (RING) gemm_nt_sub_tile_ring<AGP_RING_STAGES, AGP_RING_CHUNK>(g, bi, bj, lds);
+    else gemm_nt_sub_tile_cpf<false, false>(g, bi, bj, lds);
+  } else {
+    gemm_nt_sub_tile<false, false>(g, bi, bj, lds);
+  }
 #ifdef AGP_BULK_STAMPS
   if (blockIdx.x == gridDim.x / 2 && threadIdx.x == 0) {
     __builtin_amdgcn_s_waitcnt(0);
@@ -160,6 +177,21 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void trailing_update_kernel(GemmAr
     __syncthreads();
     if (threadIdx.x == 0) __hip_atomic_fetch_add(g.head_done, 1ull, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
   }
+}
+
+// The product kernel carries ONE of the two loops of the whole interior tiles - AGP_BULK_RING: the ring of directly loaded
+// LDS stages (gemm_nt_sub_tile_ring), otherwise the register-staged double buffer (gemm_nt_sub_tile_cpf) -, and the other
+// loop lives under a kernel symbol of its own for the same-build comparison of the two (launch_trailing_update_as,
+// variants 30 / 31).  All LDS of either kernel is this one array: a second __shared__ object beside directly loaded
+// stages makes the compiler wait for every load in flight in front of each fragment read.
+__global__ __launch_bounds__(GEMM_THREADS, 2) void trailing_update_kernel(GemmArgs g) {
+  __shared__ __attribute__((aligned(16))) double lds[2 * 2 * GK * GLD];
+  trailing_update_body<AGP_BULK_RING != 0>(g, lds);
+}
+
+__global__ __launch_bounds__(GEMM_THREADS, 2) void trailing_update_other_loop_kernel(GemmArgs g) {
+  __shared__ __attribute__((aligned(16))) double lds[2 * 2 * GK * GLD];
+  trailing_update_body<AGP_BULK_RING == 0>(g, lds);
 }
 
 // ---------------------------------------------------------------------------
@@ -671,7 +703,8 @@ const int *bulk_tile_order(int ntr, long long tiles, long long *len) {
   return o.dev;
 }
 
-// variant 0: fp64 MFMA kernel, 3: fp32-product MFMA kernel (mixed precision)
+// variant 0: fp64 MFMA kernel, 3: fp32-product MFMA kernel (mixed precision); 30 / 31: the fp64 kernel with whole tiles only,
+// on the ring loop / on the register-staged loop (launch_trailing_update_planned)
 void launch_trailing_update_as(int variant, hipStream_t s, double *C, long long ldc, const double *P,
                                const double *Q, long long ldp, long long M, long long K, BulkTiming *timing, const float *P32,
                                const float *Q32, long long ld32) {
@@ -718,6 +751,16 @@ static void launch_trailing_update_planned(int variant, hipStream_t s, GemmArgs 
     }
     if (g.A32) hipLaunchKernelGGL(trailing_update_f32_kernel<true>, dim3((unsigned)wgs), dim3(GEMM_THREADS), 0, s, g);
     else hipLaunchKernelGGL(trailing_update_f32_kernel<false>, dim3((unsigned)wgs), dim3(GEMM_THREADS), 0, s, g);
+    return;
+  }
+  if (variant == 30 || variant == 31) {
+    // every tile a whole 128 x 128 workgroup in column-major tile order, however few there are (no quadrants, no XCD
+    // table): 30 with the ring loop where a tile is eligible, 31 with the register-staged loop
+    g.small_first = tiles;
+    g.small_count = 0;
+    const bool product = (variant == 30) == (AGP_BULK_RING != 0);
+    if (product) hipLaunchKernelGGL(trailing_update_kernel, dim3((unsigned)tiles), dim3(GEMM_THREADS), 0, s, g);
+    else hipLaunchKernelGGL(trailing_update_other_loop_kernel, dim3((unsigned)tiles), dim3(GEMM_THREADS), 0, s, g);
     return;
   }
   // Tail split: a launch of T tiles runs floor(T / slots) full rounds of 128 x 128 workgroups (slots = 2 per

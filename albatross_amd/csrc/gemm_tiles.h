@@ -326,6 +326,149 @@ __device__ __forceinline__ bool tile_takes_cpf(const GemmArgs &g, const int bi, 
   return aligned && g.K >= 8 * GK && g.K % GK == 0 && (long long)(bi + 1) * GT <= g.M && (long long)(bj + 1) * GT <= g.N;
 }
 
+// The tile of gemm_nt_sub_tile_cpf for two row-major panels (the bulk update), its operands staged global -> LDS directly
+// (global_load_lds_dwordx4: no staging registers, no ds_write, no negation pass) into a RING of S stages of CK k-rows in
+// the same LDS array and the same [k][row] image: one wave-instruction moves one k-row of 128 doubles (64 lanes x 16 B,
+// contiguous at both ends; every k-row has its own LDS base, so the 16 doubles of padding behind it stay), each wave a
+// quarter of the k-rows of a chunk.  Chunk c lives in stage c mod S:
+//   - at the top of chunk c the loads of chunk c + S - 1 go into the stage that chunk c - 1 was read from (every wave
+//     has consumed its fragments of chunk c - 1 before it arrives at the barrier that ends it);
+//   - at the end of chunk c every wave waits - COUNTED, s_waitcnt vmcnt(n), the loads of the chunks behind stay in
+//     flight - until its own loads of chunk c + W have landed, then a raw s_barrier (a __syncthreads() here waits
+//     vmcnt(0) and drains the ring): the chunks up to c + W are visible to the whole workgroup from there on;
+//   - S >= 4: W = 2, so the stage of chunk c + 1 was published one barrier EARLIER and the fragments of its first
+//     k-step are read in front of the last MFMAs of chunk c - no restart of the fragment reads behind the barrier.
+//     S <= 3: W = 1 (there is no stage to spare), the first fragments are read behind the barrier.
+// Nothing is negated in the loop: the accumulators hold A B^T - C, the NEGATIVE of gemm_nt_sub_tile_cpf's (part p of C is
+// SUBTRACTED where that body adds it, the epilogue stores -acc).  The MFMAs run in the same order over k and the parts
+// enter at the same k, and rounding to nearest is symmetric in the sign, so every intermediate is exactly the negative
+// of that body's and the tile is bit-identical to it - up to the sign of an entry that comes out exactly zero.
+// (Negating the C-column fragments after their read - four v_xor per k-step - was tried first: the compiler puts the
+// flips and their lgkmcnt(0) right behind the reads, in front of the k-step's MFMAs.)
+// (S, CK) = (4, 8), (3, 8), (2, 16) fill the 73,728 B of the double buffer or less.
+__device__ __forceinline__ void ring_load_row(const double *lane_src, double *wave_dst) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)lane_src, (__attribute__((address_space(3))) void *)wave_dst, 16,
+                                   0, 0);
+}
+template <int N>
+__device__ __forceinline__ void ring_wait_loads() {  // at most N of this wave's loads still in flight
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+template <int S, int CK>
+__device__ __forceinline__ void gemm_nt_sub_tile_ring(const GemmArgs &g, const int bi, const int bj, double *lds) {
+  constexpr int KS = CK / 4;            // k-steps (MFMA depth 4) per chunk
+  constexpr int STAGE = 2 * CK * GLD;   // doubles per stage: [operand][k][row]
+  constexpr int RPW = CK / 4;           // k-rows per wave, operand and chunk
+  constexpr int LPW = 2 * RPW;          // loads per wave and chunk
+  constexpr int W = S >= 4 ? 2 : 1;     // chunks published ahead of the one being multiplied
+  constexpr int FLY = S - 1 - W;        // chunks whose loads stay in flight across a barrier
+  constexpr bool EARLY = W == 2;
+  static_assert(S >= 2 && CK % 4 == 0 && GK % CK == 0 && S * STAGE <= 2 * 2 * GK * GLD && FLY >= 0 && FLY <= 1, "ring shape");
+
+  const long long i0 = (long long)bi * GT, j0 = (long long)bj * GT;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wr = wave >> 1, wc = wave & 1;
+  const int ln = lane & 15, lg = lane >> 4;
+
+  v4d acc[4][4];  // [tj][ti]
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) acc[a][b] = v4zero();
+
+  const long long nc = g.K / CK, nq = (g.K / GK) / 8 * (GK / CK);  // chunks; chunks per C part (the last takes the rest)
+  // this wave's k-rows RPW wave .. of a chunk: lane l moves the row pair 2 l
+  const double *const pa = g.A + i0 + 2 * lane + (long long)(wave * RPW) * g.lda;
+  const double *const pb = g.B + j0 + 2 * lane + (long long)(wave * RPW) * g.ldb;
+  double *const lw = lds + wave * RPW * GLD;
+  auto issue = [&](const long long c, const int stage) {
+    double *d = lw + stage * STAGE;
+    const double *sa = pa + c * CK * g.lda, *sb = pb + c * CK * g.ldb;
+#pragma unroll
+    for (int r = 0; r < RPW; ++r) {
+      ring_load_row(sa + r * g.lda, d + r * GLD);
+      ring_load_row(sb + r * g.ldb, d + CK * GLD + r * GLD);
+    }
+  };
+  const int fa_off = 64 * wc + ln + lg * GLD, fb_off = 64 * wr + ln + lg * GLD;
+  auto fragments = [&](double (&a)[4], double (&b)[4], const double *stage, const int s) {
+    const double *As = stage + 4 * s * GLD, *Bs = As + CK * GLD;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      a[t] = Bs[fa_off + 16 * t];  // MFMA A operand: C-column panel
+      b[t] = As[fb_off + 16 * t];  // MFMA B operand: C-row panel
+    }
+  };
+
+#pragma unroll
+  for (int c = 0; c < S - 1; ++c) issue(c, c);  // (nc >= 8 > S - 1)
+  ring_wait_loads<FLY * LPW>();  // chunks 0 .. W - 1
+  __builtin_amdgcn_s_barrier();
+
+  const long long coff = (i0 + 64 * wr + ln) + (j0 + 64 * wc + lg) * g.ldc;
+  double *const cbase = g.C + coff;
+  // two fragment sets, k-step s of a chunk in set s & 1 (KS is even: every chunk starts in set 0, nothing is copied)
+  static_assert(KS % 2 == 0, "fragment sets alternate");
+  double fa[2][4], fb[2][4];
+  if (EARLY) fragments(fa[0], fb[0], lds, 0);
+  long long c = 0;
+  int st = 0;  // stage of chunk c
+#pragma unroll
+  for (int p = 0; p < 8; ++p) {
+    v4d ct[2];
+    const long long c_end = (p == 7) ? nc : (p + 1) * nq;
+    bool first = true;
+    for (; c < c_end; ++c) {
+      const int st_prev = st == 0 ? S - 1 : st - 1, st_next = st + 1 == S ? 0 : st + 1;
+      const bool more = c + S - 1 < nc;
+      if (more) issue(c + S - 1, st_prev);
+      if (first) {  // part p of C: see gemm_nt_sub_tile_cpf
+        first = false;
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) ct[t][r] = __builtin_nontemporal_load(&cbase[16 * (2 * (p & 1) + t) + (long long)(16 * (p >> 1) + 4 * r) * g.ldc]);
+      }
+      const double *stage = lds + st * STAGE;
+      if (!EARLY) fragments(fa[0], fb[0], stage, 0);
+#pragma unroll
+      for (int s = 0; s < KS; ++s) {
+        const int cur = s & 1, nxt = cur ^ 1;
+#pragma unroll
+        for (int ti = 0; ti < 4; ++ti) acc[0][ti] = mfma16(fa[cur][0], fb[cur][ti], acc[0][ti]);
+        // The next k-step's fragments are read behind the first four MFMAs of this one and in front of its other twelve,
+        // and stay there (sched_barrier): the wait in front of the first MFMA then covers this k-step's fragments alone
+        // (in front of the reads it came out as lgkmcnt(0) for both sets), and left to itself the scheduler sinks the
+        // reads of the next chunk behind the last MFMAs, so that every chunk starts on a wait.
+        // (EARLY: the first k-step of chunk c + 1, published one barrier ago; behind the last chunk the stage holds an
+        // older chunk and the fragments are not used)
+        __builtin_amdgcn_sched_barrier(0);
+        if (s + 1 < KS) fragments(fa[nxt], fb[nxt], stage, s + 1);
+        else if (EARLY) fragments(fa[nxt], fb[nxt], lds + st_next * STAGE, 0);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int tj = 1; tj < 4; ++tj)
+#pragma unroll
+          for (int ti = 0; ti < 4; ++ti) acc[tj][ti] = mfma16(fa[cur][tj], fb[cur][ti], acc[tj][ti]);
+      }
+      // loads issued so far: the chunks up to min(c + S - 1, nc - 1); wanted: up to c + W (behind the last chunk: nothing)
+      if (FLY > 0 && more) ring_wait_loads<FLY * LPW>();
+      else ring_wait_loads<0>();
+      __builtin_amdgcn_s_barrier();
+      st = st_next;
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) acc[p >> 1][2 * (p & 1) + t] -= ct[t];  // (acc = A B^T - C)
+  }
+#pragma unroll
+  for (int tj = 0; tj < 4; ++tj)
+#pragma unroll
+    for (int ti = 0; ti < 4; ++ti)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) __builtin_nontemporal_store(-acc[tj][ti][r], &cbase[16 * ti + (long long)(16 * tj + 4 * r) * g.ldc]);
+}
+
 // ---------------------------------------------------------------------------
 // 64 x 64-tile variant for launches too small to fill the chip with 128 x 128
 // tiles (the next-panel and inner updates of the serial panel chain): four
