@@ -291,6 +291,9 @@ def load_debug():
         _debug_lib.agp_debug_logo_batch_plan.argtypes = [C.c_int64, _P, _P, _P, _P, C.c_int64, _P, C.c_int64, _P]
         _debug_lib.agp_debug_step_launch_shape.restype = C.c_int
         _debug_lib.agp_debug_step_launch_shape.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P]
+        # the tiling of the update launches without a device (csrc/update_plan.h)
+        _debug_lib.agp_debug_update_plan.restype = C.c_int
+        _debug_lib.agp_debug_update_plan.argtypes = [_P, C.c_int64, _P, C.c_int64, _P]
         # the column-pivoted QR and the substitutions against its R on host arrays (csrc/qr.hip)
         i64 = C.c_int64
         for name, argtypes in (

@@ -811,6 +811,8 @@ __device__ __forceinline__ void trail_one_tile(const PotrfArgs &p, long long id,
   double *Cc = p.A + t0 * p.lda + t0;
   const double *P = p.A + (p.k0 - NB) * p.lda + t0;
   const int ntr = (int)((p.below + ST - 1) / ST);
+  // (update_plan.h: lower_tile_at is this walk; calling it here renumbers the registers of the whole step kernel, so
+  // the chain's kernel keeps its own copy)
   int bj = 0;
   while (id >= ntr - bj) {
     id -= ntr - bj;
@@ -884,9 +886,9 @@ static void launch_potrf(hipStream_t s, double *A, long long lda, long long k0, 
 
 // trailing update C -= P P^T (lower tiles) bracketed by a HIP-event pair when
 // the caller collects per-launch timings (bench.py's roofline block)
-// (kernel: the selector of launch_trailing_update_as, -1: the fp64 default; ldp: of P and Q, 0: lda)
+// (kernel: of the bulk update; ldp: of P and Q, 0: lda)
 static void timed_gemm(hipStream_t s, FactorTimers *timers, double *C, long long lda, const double *P,
-                       const double *Q, long long M, long long N, long long K, bool bulk, int kernel = -1,
+                       const double *Q, long long M, long long N, long long K, bool bulk, BulkKernel kernel = BulkKernel::Fp64,
                        const float *P32 = nullptr, long long ld32 = 0, long long ldp = 0) {
   if (ldp == 0) ldp = lda;
   // only the bulk trailing updates' trailing_update_kernel launches (their own kernel symbol) are
@@ -898,8 +900,7 @@ static void timed_gemm(hipStream_t s, FactorTimers *timers, double *C, long long
   BulkTiming bt;
   const bool timed = timers && timers->ev && timers->used + 2 <= timers->n_ev;
   if (timed) { bt.e0 = timers->ev[timers->used]; bt.e1 = timers->ev[timers->used + 1]; }
-  if (kernel >= 0) launch_trailing_update_as(kernel, s, C, lda, P, Q, ldp, M, K, timed ? &bt : nullptr, P32, P32, ld32);
-  else launch_trailing_update(s, C, lda, P, Q, ldp, M, K, timed ? &bt : nullptr);
+  launch_trailing_update_as(kernel, s, C, lda, P, Q, ldp, M, K, timed ? &bt : nullptr, P32, P32, ld32);
   if (timed && bt.flops > 0.) {
     timers->flops[timers->used / 2] = bt.flops;  // algorithmic flop: 2 K per covered C entry on or below the diagonal
     timers->used += 2;
@@ -1264,9 +1265,9 @@ void StagedPanel::apply(hipStream_t s, double *C, long long ldc, long long row_o
     long long olen = 0;
     const int *order = nullptr;
     if (bulk) {
-      const int ntr = (int)((M + 127) / 128);
-      const long long tiles = (long long)ntr * (ntr + 1) / 2;
-      if (tiles >= 1024) order = bulk_tile_order(ntr, tiles, &olen);
+      const int ntr = tile_rows(M);
+      const long long tiles = lower_tile_count(ntr, ntr, 1);
+      if (mixed_bulk_ordered(tiles)) order = bulk_tile_order(ntr, tiles, &olen);
     }
     if (products_ == BulkProducts::F16x2)
       launch_update_f16x2(s, f16x2_, C, ldc, P16_, rows_, row_offset, row_offset, irs_, M, N, K, order, olen);
@@ -1277,7 +1278,7 @@ void StagedPanel::apply(hipStream_t s, double *C, long long ldc, long long row_o
   // products of fp32-rounded panels on the fp32 MFMA path, fp64 subtraction: from the fp32 copy, or rounded by the kernel
   const double *Q = P_ + row_offset;
   const float *Q32 = P32_ ? P32_ + row_offset : nullptr;
-  if (bulk) timed_gemm(s, timers, C, ldc, Q, Q, M, N, K, true, /*kernel=*/3, Q32, ld32_, ldp_);
+  if (bulk) timed_gemm(s, timers, C, ldc, Q, Q, M, N, K, true, BulkKernel::Fp32Products, Q32, ld32_, ldp_);
   else launch_update_f32(s, C, ldc, Q, Q, ldp_, M, N, K, Q32, Q32, ld32_);
 }
 

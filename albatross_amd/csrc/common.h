@@ -12,6 +12,7 @@
 #include "cov_eval.h"
 #include "dev_mem.h"      // DevMem, ParkSlot, GrowBuf: the owners of device memory
 #include "factor_plan.h"  // FactorRequest, FactorOutcome, FusedPrep: the arguments of factor_lower
+#include "update_plan.h"  // BulkKernel and the tile decode of the update launches
 
 // Wave priority of the panel-chain kernels (s_setprio); the bulk update stays at 0 (the four combinations were measured:
 // DESIGN.md section 8, profiles/r03/sweep_prio.txt)
@@ -394,7 +395,7 @@ struct BulkTiming {
   hipEvent_t e0 = nullptr, e1 = nullptr;
   double flops = 0.;
 };
-void launch_trailing_update_as(int variant, hipStream_t s, double *C, long long ldc, const double *P,
+void launch_trailing_update_as(BulkKernel kernel, hipStream_t s, double *C, long long ldc, const double *P,
                                const double *Q, long long ldp, long long M, long long K,
                                BulkTiming *timing = nullptr, const float *P32 = nullptr, const float *Q32 = nullptr,
                                long long ld32 = 0);

@@ -16,6 +16,7 @@
 #include "pub.h"
 #include "trsm_kernel.h"
 #include "factor_plan.h"
+#include "update_plan.h"
 #include "logo_batch_plan.h"
 #include <vector>
 #include <cstdlib>
@@ -760,11 +761,19 @@ static int stage_probe_panel(agp_context *ctx, agp::BulkProducts products, const
   return AGP_OK;
 }
 
-// Bulk trailing update C (M x M, lower tiles) -= P P^T on host data.  variant 0: MFMA kernel,
-// 2: DPP-broadcast VALU kernel; 13 / 14 / 15: the fp32-product kernel on an fp32 copy of the panel / the bf16 x 3 kernel on
-// its three bf16 planes / the fp16 x 2 kernel on the two fp16 planes of its scaled rows, staged and applied as the mixed fit does;
-// 20 + h: the merged update with a head of h tile columns; 30 / 31: every tile a whole 128 x 128 workgroup, on the ring loop /
-// on the register-staged loop (launch_trailing_update_as) - shapes of a few tile rows reach the large tile bodies this way.
+// The kernel selector of the bulk-update probes below: the ONE place their integers become a BulkKernel (update_plan.h).
+// 0: the fp64 product launch, 3: the fp32-product kernel, 30 / 31: every tile a whole 128 x 128 workgroup on the ring loop /
+// on the register-staged loop.  Every other integer runs the fp64 product launch too: 2, 4 and 5 once named kernels that
+// are gone (a VALU kernel, all-quadrants, a tile tail), and tests and scripts still pass them.
+static agp::BulkKernel bulk_kernel_of(int variant) {
+  return variant == 3 ? agp::BulkKernel::Fp32Products : variant == 30 ? agp::BulkKernel::Fp64WholeRing
+       : variant == 31 ? agp::BulkKernel::Fp64WholeRegisterStaged : agp::BulkKernel::Fp64;
+}
+
+// Bulk trailing update C (M x M, lower tiles) -= P P^T on host data.  variant: bulk_kernel_of (with 30 / 31 shapes of a few
+// tile rows reach the large tile bodies), and 13 / 14 / 15: the fp32-product kernel on an fp32 copy of the panel / the
+// bf16 x 3 kernel on its three bf16 planes / the fp16 x 2 kernel on the two fp16 planes of its scaled rows, staged and applied
+// as the mixed fit does; 20 + h: the merged update with a head of h tile columns.
 AGP_DEBUG_API int agp_debug_trailing_update(agp_context *ctx, double *C, int64_t ldc, const double *P, int64_t ldp, int64_t M,
                               int64_t K, int variant) {
   if (!ctx) return AGP_ERR_INVALID_ARGUMENT;
@@ -800,7 +809,7 @@ AGP_DEBUG_API int agp_debug_trailing_update(agp_context *ctx, double *C, int64_t
     AGP_HIP_CHECK(ctx, hipMemcpy(flags, ctx->d_flags, sizeof(flags), hipMemcpyDeviceToHost));
     if (seen != (unsigned long long)head_tiles || flags[2] != 0 || head_tiles <= 0) st = AGP_ERR_HIP;
   } else {
-    launch_trailing_update_as(variant, ctx->stream, dC, ldc, dP, dP, ldp, M, K);
+    launch_trailing_update_as(bulk_kernel_of(variant), ctx->stream, dC, ldc, dP, dP, ldp, M, K);
   }
   AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   AGP_HIP_CHECK(ctx, hipGetLastError());
@@ -931,7 +940,7 @@ AGP_DEBUG_API int agp_debug_time_masked_update(agp_context *ctx, int64_t M, int6
   AGP_HIP_CHECK(ctx, hipEventCreate(&c1));
   for (int r = -2; r < reps; ++r) {
     if (r == 0) AGP_HIP_CHECK(ctx, hipEventRecord(e0, sm));
-    launch_trailing_update_as(variant, sm, dC, ld, dP, dP, ld, M, K);
+    launch_trailing_update_as(bulk_kernel_of(variant), sm, dC, ld, dP, dP, ld, M, K);
     if (r == 0 && chain_reps > 0) {
       AGP_HIP_CHECK(ctx, hipEventRecord(c0, ctx->stream));
       for (int c = 0; c < chain_reps; ++c) agp::panel_phase_public(ctx, ctx->stream, pA, M, plda, pimg, nullptr, 0, pw);
@@ -997,7 +1006,7 @@ AGP_DEBUG_API int agp_debug_time_trailing_update(agp_context *ctx, int64_t M, in
   for (int r = -2; r < reps && st == AGP_OK; ++r) {
     if (r == 0) AGP_HIP_CHECK(ctx, hipEventRecord(e0, ctx->stream));
     if (agp::is_mixed(products)) staged.apply(ctx->stream, dC, ld, 0, M, M, K);
-    else launch_trailing_update_as(variant, ctx->stream, dC, ld, dP, dP, ld, M, K);
+    else launch_trailing_update_as(bulk_kernel_of(variant), ctx->stream, dC, ld, dP, dP, ld, M, K);
   }
   if (st == AGP_OK) {
     AGP_HIP_CHECK(ctx, hipEventRecord(e1, ctx->stream));
@@ -1377,6 +1386,53 @@ AGP_DEBUG_API int agp_debug_step_launch_shape(int64_t below, int64_t panels_done
   const agp::StepLaunchShape sh = agp::step_launch_shape(below, panels_done, step_slots, cus);
   const int64_t w[7] = {sh.grid, sh.trail_first, sh.trail_tiles, sh.trail_workers, sh.hold_index, sh.hold_count, (int64_t)sh.rowcnt_expect};
   std::copy(w, w + 7, out);
+  return AGP_OK;
+}
+
+// The tiling an update launch WOULD get (update_plan.h) - no context, no device.  in[0] says what is asked:
+//   0  bulk update: in = {0, nth, head_cols, slots} (nth: tile rows of the whole trailing matrix) ->
+//      {ntr, tiles, full, rem, kernel (0 trailing_update_kernel, 1 trailing_update_tail_kernel), head_count, order_len, grid}
+//      as launch_trailing_update_merged (head_cols > 0) / launch_trailing_update_as (Fp64) fill them; order_len: length of
+//      the order table of the whole tiles, 0 without one
+//   1  plan_nt_sub: in = {1, M, N, K, tri, a_kmajor, b_kmajor, count, small_limit} -> {edge, transposed, ntr, ntc, grid}
+//   2  plan_stair: in = {2, M, N, block, c0, slots} -> {edge, ntr, ntc, st_tpb, st_c0t}
+//   3  lower_tile_of: in = {3, first id, ids, ntr, ntc, tri} -> per id {found, bi, bj}
+//   4  xcd_tile_order: in = {4, ntr, full} -> the table
+// *words receives the length of the answer, of which at most `cap` words are written to `out`.
+AGP_DEBUG_API int agp_debug_update_plan(const int64_t *in, int64_t n_in, int64_t *out, int64_t cap, int64_t *words) {
+  static const int64_t need[5] = {4, 9, 6, 6, 3};
+  if (!in || !words || n_in < 1 || cap < 0 || (cap > 0 && !out) || in[0] < 0 || in[0] > 4 || n_in < need[in[0]]) return AGP_ERR_INVALID_ARGUMENT;
+  std::vector<int64_t> w;
+  if (in[0] == 0) {
+    const int nth = (int)in[1], head_cols = (int)std::min(in[2], in[1]), ntr = nth - head_cols;
+    if (nth < 1 || head_cols < 0 || in[3] < 1) return AGP_ERR_INVALID_ARGUMENT;
+    const long long tiles = agp::lower_tile_count(ntr, ntr, 1), head_count = agp::lower_tile_count(nth, head_cols, 1);
+    const agp::BulkSplit sp = agp::plan_bulk_update(tiles, in[3], head_cols > 0);
+    const bool tail = sp.kernel == agp::SplitKernel::QuadrantsOnly;
+    const long long order_len = !tail && sp.full > 0 ? (long long)agp::xcd_tile_order(ntr, sp.full).size() : 0;
+    w = {ntr, tiles, sp.full, sp.rem, tail ? 1 : 0, head_count, order_len, agp::bulk_grid(sp, head_count, order_len)};
+  } else if (in[0] == 1) {
+    if (in[1] < 1 || in[2] < 1 || in[3] < 1 || in[7] < 1) return AGP_ERR_INVALID_ARGUMENT;
+    const agp::NtSubPlan p = agp::plan_nt_sub(in[1], in[2], in[3], in[4] != 0, in[5] != 0, in[6] != 0, in[7], in[8]);
+    w = {p.edge, p.transposed ? 1 : 0, p.ntr, p.ntc, p.grid};
+  } else if (in[0] == 2) {
+    if (in[1] < 1 || in[2] < 1 || in[3] < 1 || in[4] < 0 || in[5] < 1) return AGP_ERR_INVALID_ARGUMENT;
+    const agp::StairPlan p = agp::plan_stair(in[1], in[2], in[3], in[4], in[5]);
+    w = {p.edge, p.ntr, p.ntc, p.st_tpb, p.st_c0t};
+  } else if (in[0] == 3) {
+    if (in[1] < 0 || in[2] < 0 || in[3] < 1 || in[4] < 1) return AGP_ERR_INVALID_ARGUMENT;
+    for (int64_t id = in[1]; id < in[1] + in[2]; ++id) {
+      int bi = -1, bj = -1;
+      const bool found = agp::lower_tile_of(id, (int)in[3], (int)in[4], in[5] != 0, bi, bj);
+      w.insert(w.end(), {found ? 1 : 0, found ? bi : -1, found ? bj : -1});
+    }
+  } else {
+    if (in[1] < 1 || in[2] < 0) return AGP_ERR_INVALID_ARGUMENT;
+    const std::vector<int> table = agp::xcd_tile_order((int)in[1], in[2]);
+    w.assign(table.begin(), table.end());
+  }
+  *words = (int64_t)w.size();
+  std::copy(w.begin(), w.begin() + std::min<int64_t>(cap, (int64_t)w.size()), out);
   return AGP_OK;
 }
 

@@ -27,7 +27,7 @@ constexpr long long MERGED_STEPS_MAX = 256;    // counters of the merged bulk up
 
 // What the bulk updates of a factorisation multiply: the fp64 panels themselves, or - the mixed-precision fit - a
 // low-precision copy of each step's panel in one of three formats.  The values are what agp_debug_factor_plan receives
-// in switches[5]; they are NOT the kernel selector of launch_trailing_update_as (gemm.hip), which is a different thing.
+// in switches[5].
 enum class BulkProducts : int { Fp64 = -1, Fp32 = 3, Bf16x3 = 4, F16x2 = 5 };
 inline bool uses_planes(BulkProducts p) { return p == BulkProducts::Bf16x3 || p == BulkProducts::F16x2; }  // split 16-bit planes
 inline bool is_mixed(BulkProducts p) { return p == BulkProducts::Fp32 || uses_planes(p); }

@@ -6,12 +6,16 @@
 //
 // One workgroup = 4 waves = one 128 x 128 tile of C; each wave owns a 64 x 64
 // quadrant = 4 x 4 tiles of v_mfma_f64_16x16x4_f64 (128 accumulator VGPRs).
-// The K loop streams 16-deep chunks of both operand panels global -> registers
-// -> LDS (double buffered, one barrier per chunk); fragments are one
-// ds_read_b64 per lane from a [k][row] image padded to 144 doubles per k so
-// the two 16-lane halves of a 32-lane LDS group fall on disjoint banks.
-// (The whole interior tiles of the bulk update - trailing_update_kernel - load the same image global -> LDS directly
-// into a ring of four 8-deep stages instead: gemm_tiles.h, gemm_nt_sub_tile_ring.)
+// Fragments are one ds_read_b64 per lane from a [k][row] LDS image padded to 144
+// doubles per k so the two 16-lane halves of a 32-lane LDS group fall on disjoint
+// banks.  Two K loops fill that image (gemm_tiles.h): the whole interior tiles of
+// the bulk update (trailing_update_kernel) load it global -> LDS directly into a
+// ring of four 8-deep stages (gemm_nt_sub_tile_ring); every other tile streams
+// 16-deep chunks of both operand panels global -> registers -> LDS (double
+// buffered, one barrier per chunk).
+// Which tile edge a launch gets, how a bulk update is cut and ordered and which
+// tile a workgroup computes is decided in update_plan.h; the launchers below
+// carry those plans out.
 // The MFMA "A" operand carries the C-column panel (pre-negated while staging)
 // and the MFMA "B" operand the C-row panel, so that a C/D register holds 16
 // CONSECUTIVE ROWS of one C column: epilogue accesses are 128-B segments of
@@ -32,8 +36,7 @@
 
 namespace agp {
 
-
-
+static_assert(PLAN_GT == GT && PLAN_ST == ST && PLAN_TT == TT, "update_plan.h");
 
 // Which C tile a workgroup computes.  Returns false for padding workgroups.
 __device__ __forceinline__ bool tile_of_block(const GemmArgs &g, int &bi, int &bj) {
@@ -41,19 +44,9 @@ __device__ __forceinline__ bool tile_of_block(const GemmArgs &g, int &bi, int &b
     const long long id = blockIdx.x;
     bi = (int)(id % g.ntr);
     bj = (int)(id / g.ntr);
-    const long long lb = g.st_lb0 + bi / g.st_tpb;
-    const long long gi = lb * g.st_world + ((lb & 1) ? g.st_world - 1 - g.st_rank : g.st_rank);
-    return bj <= gi * g.st_tpb - g.st_c0t + (bi % g.st_tpb);
+    return stair_tile_owned(bi, bj, g.st_lb0, g.st_tpb, g.st_world, g.st_rank, g.st_c0t);
   }
-  bj = 0;
-  long long id = blockIdx.x + g.tile_first;
-  while (true) {
-    const int cnt = g.tri ? (g.ntr - bj) : g.ntr;
-    if (id < cnt) break;
-    id -= cnt;
-    ++bj;
-  }
-  bi = (g.tri ? bj : 0) + (int)id;
+  lower_tile_at(blockIdx.x + g.tile_first, g.ntr, g.tri, bi, bj);
   return true;
 }
 
@@ -120,39 +113,24 @@ __device__ __forceinline__ void trailing_update_body(const GemmArgs &g, double *
 #endif
   long long wg = blockIdx.x;
   const bool head = wg < g.head_count;
-  int bi, bj = 0;
+  int bi, bj;
   if (head) {
-    const int nth = g.ntr + g.head_cols;  // tile rows of the whole trailing matrix
-    long long id = wg;
-    while (id >= nth - bj) {
-      id -= nth - bj;
-      ++bj;
-    }
-    bi = bj + (int)id;
+    lower_tile_at(wg, g.ntr + g.head_cols, 1, bi, bj);  // (tile rows of the whole trailing matrix: ntr + head_cols)
   } else {
     wg -= g.head_count;
     const bool small = wg < 4LL * g.small_count;
-    long long id = small ? (wg >> 2) + g.small_first : wg - 4LL * g.small_count + g.tile_first;
+    const long long id = small ? (wg >> 2) + g.small_first : wg - 4LL * g.small_count + g.tile_first;
     if (!small && g.order) {
-      const int packed = g.order[id];
-      if (packed < 0) return;
-      bi = packed >> 16;
-      bj = packed & 0xffff;
+      if (!order_entry(g.order, id, bi, bj)) return;
     } else {
-      while (true) {
-        const int cnt = g.ntr - bj;
-        if (id < cnt) break;
-        id -= cnt;
-        ++bj;
-      }
-      bi = bj + (int)id;
+      lower_tile_at(id, g.ntr, 1, bi, bj);
     }
     // (the sub-triangle right of the head, in the frame of the whole trailing matrix)
     bi += g.head_cols;
     bj += g.head_cols;
     if (small) {
       const int q = (int)(wg & 3), qi = q & 1, qj = q >> 1;
-      if (bi == bj && qj > qi) return;  // upper quadrant of a diagonal tile
+      if (quadrant_skipped(bi, bj, qi, qj)) return;
       gemm64_body(g, (long long)bi * GT + qi * ST, (long long)bj * GT + qj * ST, lds);
       return;
     }
@@ -181,8 +159,8 @@ __device__ __forceinline__ void trailing_update_body(const GemmArgs &g, double *
 
 // The product kernel carries ONE of the two loops of the whole interior tiles - AGP_BULK_RING: the ring of directly loaded
 // LDS stages (gemm_nt_sub_tile_ring), otherwise the register-staged double buffer (gemm_nt_sub_tile_cpf) -, and the other
-// loop lives under a kernel symbol of its own for the same-build comparison of the two (launch_trailing_update_as,
-// variants 30 / 31).  All LDS of either kernel is this one array: a second __shared__ object beside directly loaded
+// loop lives under a kernel symbol of its own for the same-build comparison of the two (BulkKernel::Fp64WholeRing /
+// Fp64WholeRegisterStaged).  All LDS of either kernel is this one array: a second __shared__ object beside directly loaded
 // stages makes the compiler wait for every load in flight in front of each fragment read.
 __global__ __launch_bounds__(GEMM_THREADS, 2) void trailing_update_kernel(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) double lds[2 * 2 * GK * GLD];
@@ -260,12 +238,7 @@ template <bool P32>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void trailing_update_f32_kernel(GemmArgs g) {
   __shared__ float lds[2 * 2 * GK * GLD];
   int bi, bj;
-  if (g.order) {  // XCD-aware order (launch_trailing_update_as)
-    const int packed = g.order[blockIdx.x];
-    if (packed < 0) return;
-    bi = packed >> 16;
-    bj = packed & 0xffff;
-  } else if (!tile_of_block(g, bi, bj)) return;
+  if (!ordered_tile_of(g.order, blockIdx.x, g.ntr, g.ntc, bi, bj)) return;  // (always lower tiles: launch_trailing_update_as, launch_update_f32)
   const long long i0 = (long long)bi * GT, j0 = (long long)bj * GT;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wr = wave >> 1, wc = wave & 1;
@@ -435,22 +408,12 @@ __global__ __launch_bounds__(GEMM_THREADS, 4) void gemm64_nt_sub_kernel(GemmArgs
   if (g.stair) {  // (see GemmArgs::stair; st_tpb and st_c0t are in 64-tile units here)
     const long long sid = blockIdx.x;
     const int sbi = (int)(sid % g.ntr), sbj = (int)(sid / g.ntr);
-    const long long lb = g.st_lb0 + sbi / g.st_tpb;
-    const long long gi = lb * g.st_world + ((lb & 1) ? g.st_world - 1 - g.st_rank : g.st_rank);
-    if (sbj > gi * g.st_tpb - g.st_c0t + (sbi % g.st_tpb)) return;
+    if (!stair_tile_owned(sbi, sbj, g.st_lb0, g.st_tpb, g.st_world, g.st_rank, g.st_c0t)) return;
     gemm64_body(g, (long long)sbi * ST, (long long)sbj * ST, lds);
     return;
   }
-  int bj = 0;
-  long long id = blockIdx.x;
-  while (true) {
-    // tri: column bj of 64-tiles holds the row tiles bi >= bj
-    const int cnt = g.tri ? (g.ntr - bj) : g.ntr;
-    if (id < cnt) break;
-    id -= cnt;
-    ++bj;
-  }
-  const int bi = (g.tri ? bj : 0) + (int)id;
+  int bi, bj;
+  lower_tile_at(blockIdx.x, g.ntr, g.tri, bi, bj);
   gemm64_body(g, (long long)bi * ST, (long long)bj * ST, lds);
 }
 
@@ -460,15 +423,8 @@ __global__ __launch_bounds__(GEMM_THREADS, 6) void gemm32_nt_sub_kernel(GemmArgs
   g.A += (long long)blockIdx.y * g.batch_A;
   g.B += (long long)blockIdx.y * g.batch_B;
   __shared__ double lds[2 * 2 * GK * TLD];
-  int bj = 0;
-  long long id = blockIdx.x;
-  while (true) {
-    const int cnt = g.tri ? (g.ntr - bj) : g.ntr;
-    if (id < cnt) break;
-    id -= cnt;
-    ++bj;
-  }
-  const int bi = (g.tri ? bj : 0) + (int)id;
+  int bi, bj;
+  lower_tile_at(blockIdx.x, g.ntr, g.tri, bi, bj);
   gemm32_body(g, (long long)bi * TT, (long long)bj * TT, lds);
 }
 
@@ -491,25 +447,25 @@ __global__ __launch_bounds__(GEMM_THREADS, 4) void gemm64_nt_sub_bk_kernel(GemmA
 // are in 128-tile units like trailing_update_kernel's.
 __global__ __launch_bounds__(GEMM_THREADS, 4) void trailing_update_tail_kernel(GemmArgs g) {
   __shared__ double lds[2 * 2 * GK * SLD];
-  int bj = 0;
-  long long id = (long long)(blockIdx.x >> 2) + g.tile_first;
-  while (true) {
-    const int cnt = g.ntr - bj;
-    if (id < cnt) break;
-    id -= cnt;
-    ++bj;
-  }
-  const int bi = bj + (int)id;
+  int bi, bj;
+  lower_tile_at((long long)(blockIdx.x >> 2) + g.tile_first, g.ntr, 1, bi, bj);
   const int q = blockIdx.x & 3, qi = q & 1, qj = q >> 1;
-  if (bi == bj && qj > qi) return;  // upper quadrant of a diagonal tile
+  if (quadrant_skipped(bi, bj, qi, qj)) return;
   gemm64_body(g, (long long)bi * GT + qi * ST, (long long)bj * GT + qj * ST, lds);
 }
 
-static void launch_trailing_update_planned(int variant, hipStream_t s, GemmArgs &g, BulkTiming *timing);
-static long long count_tiles(int ntr, int ntc, int tri) {
-  long long total = 0;
-  for (int bj = 0; bj < ntc; ++bj) total += tri ? (ntr - bj > 0 ? ntr - bj : 0) : ntr;
-  return total;
+static void launch_trailing_update_planned(BulkKernel kernel, hipStream_t s, GemmArgs &g, BulkTiming *timing);
+
+// Workgroup slots of the large-tile kernels (2 per CU) on the current device: asked once per process, 256 CUs if the
+// query fails.
+static int bulk_slots() {
+  static const int slots = [] {
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+      cus = 256;
+    return 2 * cus;
+  }();
+  return slots;
 }
 
 // C(M x N) -= A(M x K) * B(N x K)^T ; tri != 0 keeps only tiles on/below the diagonal.
@@ -523,46 +479,19 @@ void launch_gemm_nt_sub_batched(hipStream_t s, double *C, long long ldc, long lo
   g.C = C; g.ldc = ldc; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb;
   g.M = M; g.N = N; g.K = K; g.tri = tri ? 1 : 0;
   g.batch_C = batch_C; g.batch_A = batch_A; g.batch_B = batch_B;
-  g.ntr = (int)((M + GT - 1) / GT);
-  g.ntc = (int)((N + GT - 1) / GT);
-  if (tri && g.ntc > g.ntr) g.ntc = g.ntr;
-  const long long tiles = count_tiles(g.ntr, g.ntc, g.tri);
-  if (tiles <= 0) return;
-  // fewer 128-tiles than workgroup slots (2 per CU): use 64 x 64 tiles instead (128 ... 512: flat, profiles/r03)
+  // (plan_nt_sub: tiles smaller than 128 x 128 while tiles * count < small_limit)
   static const int small_limit = [] { const char *e = getenv("AGP_GEMM_SMALL_LIMIT"); return e && e[0] ? atoi(e) : 512; }();
-  if (b_kmajor && !tri && tiles * count < small_limit) {
-    // launches that cannot fill the chip with 128 x 128 tiles (few right-hand sides, or the inner updates of a
-    // substitution with few rows): 64 x 64 tiles with the transposed-operand loader(s).  N = 16384, predict
-    // marginal: M = 64: 10.5 -> 5.0 ms, M = 1024: 12.3 -> 8.9 ms, M = 4096: 25.8 -> 24.8 ms.
-    GemmArgs h = g;
-    h.a_kmajor = a_kmajor ? 1 : 0;
-    h.ntr = (int)((M + ST - 1) / ST);
-    h.ntc = (int)((N + ST - 1) / ST);
-    hipLaunchKernelGGL(gemm64_nt_sub_bk_kernel, dim3((unsigned)((long long)h.ntr * h.ntc), (unsigned)count), dim3(GEMM_THREADS), 0, s,
-                       h);
-    return;
-  }
-  if (!a_kmajor && !b_kmajor && tiles * count < small_limit) {
-    GemmArgs h = g;
-    h.ntr = (int)((M + ST - 1) / ST);
-    h.ntc = (int)((N + ST - 1) / ST);
-    if (tri && h.ntc > h.ntr) h.ntc = h.ntr;
-    const long long t64 = count_tiles(h.ntr, h.ntc, h.tri);
-    if (t64 * count < 256 && K >= 256) {
-      // fewer 64-tiles than CUs and a deep product: every wave would carry K / 4 x 4 MFMAs one behind the other on a
-      // mostly idle chip - 32 x 32 tiles (1536 x 512 x 512: 58 -> 2x us next to a bulk update)
-      h.ntr = (int)((M + TT - 1) / TT);
-      h.ntc = (int)((N + TT - 1) / TT);
-      if (tri && h.ntc > h.ntr) h.ntc = h.ntr;
-      const long long t32 = count_tiles(h.ntr, h.ntc, h.tri);
-      hipLaunchKernelGGL(gemm32_nt_sub_kernel, dim3((unsigned)t32, (unsigned)count), dim3(GEMM_THREADS), 0, s, h);
-      return;
-    }
-    hipLaunchKernelGGL(gemm64_nt_sub_kernel, dim3((unsigned)t64, (unsigned)count), dim3(GEMM_THREADS), 0, s, h);
-    return;
-  }
-  dim3 grid((unsigned)tiles, (unsigned)count), block(GEMM_THREADS);
-  if (!a_kmajor && !b_kmajor) hipLaunchKernelGGL((gemm_nt_sub_kernel<false, false>), grid, block, 0, s, g);
+  const NtSubPlan plan = plan_nt_sub(M, N, K, tri, a_kmajor, b_kmajor, count, small_limit);
+  if (plan.grid <= 0) return;
+  g.ntr = plan.ntr;
+  g.ntc = plan.ntc;
+  const dim3 grid((unsigned)plan.grid, (unsigned)count), block(GEMM_THREADS);
+  if (plan.transposed) {
+    g.a_kmajor = a_kmajor ? 1 : 0;
+    hipLaunchKernelGGL(gemm64_nt_sub_bk_kernel, grid, block, 0, s, g);
+  } else if (plan.edge == TT) hipLaunchKernelGGL(gemm32_nt_sub_kernel, grid, block, 0, s, g);
+  else if (plan.edge == ST) hipLaunchKernelGGL(gemm64_nt_sub_kernel, grid, block, 0, s, g);
+  else if (!a_kmajor && !b_kmajor) hipLaunchKernelGGL((gemm_nt_sub_kernel<false, false>), grid, block, 0, s, g);
   else if (!a_kmajor && b_kmajor) hipLaunchKernelGGL((gemm_nt_sub_kernel<false, true>), grid, block, 0, s, g);
   else if (a_kmajor && !b_kmajor) hipLaunchKernelGGL((gemm_nt_sub_kernel<true, false>), grid, block, 0, s, g);
   else hipLaunchKernelGGL((gemm_nt_sub_kernel<true, true>), grid, block, 0, s, g);
@@ -577,28 +506,14 @@ void launch_gemm_nt_sub_stair(hipStream_t s, double *C, long long ldc, const dou
   GemmArgs g;
   g.C = C; g.ldc = ldc; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb;
   g.M = M; g.N = N; g.K = K; g.tri = 0;
-  g.ntr = (int)((M + GT - 1) / GT);
-  g.ntc = (int)((N + GT - 1) / GT);
-  g.stair = 1; g.st_world = world; g.st_rank = rank; g.st_tpb = (int)(block / GT);
-  g.st_lb0 = lb0; g.st_c0t = c0 / GT;
-  // Few rounds of 128 x 128 tiles (a rank's share of a sharded fit: 12 tile rows): the last round is mostly idle slots -
-  // 64 x 64 tiles balance the CUs better (the single-GPU bulk update makes the same switch below four rounds)
-  static int slots = 0;
-  if (slots == 0) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    slots = 2 * cus;
-  }
-  if ((long long)g.ntr * g.ntc / 2 < 4LL * slots) {
-    g.ntr = (int)((M + ST - 1) / ST);
-    g.ntc = (int)((N + ST - 1) / ST);
-    g.st_tpb = (int)(block / ST);
-    g.st_c0t = c0 / ST;
-    hipLaunchKernelGGL(gemm64_nt_sub_kernel, dim3((unsigned)((long long)g.ntr * g.ntc)), dim3(GEMM_THREADS), 0, s, g);
-    return;
-  }
-  hipLaunchKernelGGL((gemm_nt_sub_kernel<false, false>), dim3((unsigned)((long long)g.ntr * g.ntc)), dim3(GEMM_THREADS), 0, s, g);
+  const StairPlan plan = plan_stair(M, N, block, c0, bulk_slots());
+  g.ntr = plan.ntr;
+  g.ntc = plan.ntc;
+  g.stair = 1; g.st_world = world; g.st_rank = rank; g.st_tpb = plan.st_tpb;
+  g.st_lb0 = lb0; g.st_c0t = plan.st_c0t;
+  const dim3 grid((unsigned)((long long)g.ntr * g.ntc)), block_dim(GEMM_THREADS);
+  if (plan.edge == ST) hipLaunchKernelGGL(gemm64_nt_sub_kernel, grid, block_dim, 0, s, g);
+  else hipLaunchKernelGGL((gemm_nt_sub_kernel<false, false>), grid, block_dim, 0, s, g);
 }
 
 // C (M x N, ldc) = Cin (ldcin) - A B^T, or C = A B^T if Cin == nullptr;  A (M x K): element (i, k) at A[i + k lda],
@@ -621,26 +536,8 @@ void launch_gemm_nt_sub(hipStream_t s, double *C, long long ldc, const double *A
   launch_gemm_nt_sub_batched(s, C, ldc, 0, A, lda, a_kmajor, 0, B, ldb, b_kmajor, 0, M, N, K, tri, 1);
 }
 
-// entries on or below the diagonal of C covered by the first `count` lower tiles (column-major tile order)
-static double lower_entries(long long M, int ntr, long long count) {
-  double e = 0.;
-  for (int bj = 0; bj < ntr && count > 0; ++bj) {
-    const long long w = (M - (long long)bj * GT < GT) ? M - (long long)bj * GT : GT;  // tile column width
-    for (int bi = bj; bi < ntr && count > 0; ++bi, --count) {
-      const long long h = (M - (long long)bi * GT < GT) ? M - (long long)bi * GT : GT;
-      e += (bi == bj) ? 0.5 * (double)w * (double)(w + 1) : (double)h * (double)w;
-    }
-  }
-  return e;
-}
-
-// The order in which the whole tiles of a bulk update are handed out, for a part whose workgroup i runs on XCD i % 8:
-// the lower-triangular tile grid is cut into 8 x 8 blocks of tiles; every XCD gets whole blocks (longest first to the
-// least loaded XCD, then single tiles moved until the XCDs differ by at most one tile), so that the 64 workgroups resident
-// on an XCD at a time read 16 panel strips between them instead of 65 - the strips are what the update fetches from the
-// Infinity Cache / HBM (measured: FETCH_SIZE 5.8 -> 2.95 GB per launch at M = 15872, the launch 2 % faster;
-// profiles/r04/bulk_update_vs_k.txt).
-// Tables are cached per (tile rows, tile count) and device; they are a few KB each.
+// The device copy of xcd_tile_order(ntr, full) (update_plan.h): the order in which the whole tiles of a bulk update are
+// handed out.  Tables are cached per (tile rows, tile count) and device; they are a few KB each.
 struct XcdOrder { int *dev = nullptr; long long len = 0; };
 static XcdOrder xcd_order(int ntr, long long full) {
   static std::mutex mu;
@@ -651,40 +548,7 @@ static XcdOrder xcd_order(int ntr, long long full) {
   auto key = std::make_tuple(device, ntr, full);
   auto it = cache.find(key);
   if (it != cache.end()) return it->second;
-  constexpr int SB = 8, XCDS = 8;  // (blocks of 4 ... 16 tiles a side measure the same)
-  // column-major index of tile (bi, bj) in the lower-triangular order: tiles before column bj + (bi - bj)
-  auto index_of = [&](int bi, int bj) { return (long long)bj * ntr - (long long)bj * (bj - 1) / 2 + (bi - bj); };
-  const int nsb = (ntr + SB - 1) / SB;
-  std::vector<std::vector<int>> blocks;
-  for (int SJ = 0; SJ < nsb; ++SJ)
-    for (int SI = SJ; SI < nsb; ++SI) {
-      std::vector<int> t;
-      for (int tj = 0; tj < SB; ++tj)
-        for (int ti = 0; ti < SB; ++ti) {
-          const int bi = SI * SB + ti, bj = SJ * SB + tj;
-          if (bi < ntr && bj <= bi && index_of(bi, bj) < full) t.push_back((bi << 16) | bj);
-        }
-      if (!t.empty()) blocks.push_back(std::move(t));
-    }
-  std::stable_sort(blocks.begin(), blocks.end(), [](const std::vector<int> &a, const std::vector<int> &b) { return a.size() > b.size(); });
-  std::vector<std::vector<int>> per(XCDS);
-  for (auto &b : blocks) {
-    int best = 0;
-    for (int x = 1; x < XCDS; ++x) if (per[x].size() < per[best].size()) best = x;
-    per[best].insert(per[best].end(), b.begin(), b.end());
-  }
-  while (true) {  // single tiles from the longest list to the shortest
-    int lo = 0, hi = 0;
-    for (int x = 1; x < XCDS; ++x) { if (per[x].size() < per[lo].size()) lo = x; if (per[x].size() > per[hi].size()) hi = x; }
-    if (per[hi].size() <= per[lo].size() + 1) break;
-    per[lo].push_back(per[hi].back());
-    per[hi].pop_back();
-  }
-  size_t L = 0;
-  for (auto &v : per) L = std::max(L, v.size());
-  std::vector<int> table(L * XCDS, -1);
-  for (int x = 0; x < XCDS; ++x)
-    for (size_t q = 0; q < per[x].size(); ++q) table[q * XCDS + x] = per[x][q];
+  const std::vector<int> table = xcd_tile_order(ntr, full);
   XcdOrder o;
   o.len = (long long)table.size();
   // (kept for the life of the process: the cache above is its owner and is never emptied)
@@ -703,9 +567,8 @@ const int *bulk_tile_order(int ntr, long long tiles, long long *len) {
   return o.dev;
 }
 
-// variant 0: fp64 MFMA kernel, 3: fp32-product MFMA kernel (mixed precision); 30 / 31: the fp64 kernel with whole tiles only,
-// on the ring loop / on the register-staged loop (launch_trailing_update_planned)
-void launch_trailing_update_as(int variant, hipStream_t s, double *C, long long ldc, const double *P,
+// The bulk update C (M x M, lower tiles) -= P Q^T on the kernel named (update_plan.h: BulkKernel)
+void launch_trailing_update_as(BulkKernel kernel, hipStream_t s, double *C, long long ldc, const double *P,
                                const double *Q, long long ldp, long long M, long long K, BulkTiming *timing, const float *P32,
                                const float *Q32, long long ld32) {
   if (timing) timing->flops = 0.;
@@ -716,7 +579,7 @@ void launch_trailing_update_as(int variant, hipStream_t s, double *C, long long 
   g.M = M; g.N = M; g.K = K; g.tri = 1;
   g.ntr = (int)((M + GT - 1) / GT);
   g.ntc = g.ntr;
-  launch_trailing_update_planned(variant, s, g, timing);
+  launch_trailing_update_planned(kernel, s, g, timing);
 }
 
 // fp64 only: C (M x M lower, the WHOLE trailing matrix of an outer step) -= P P^T in one launch whose first workgroups are
@@ -733,101 +596,51 @@ void launch_trailing_update_merged(hipStream_t s, double *C, long long ldc, cons
   if (head_cols > nth) head_cols = nth;
   g.head_cols = head_cols;
   g.head_done = head_done;
-  for (int c = 0; c < head_cols; ++c) g.head_count += nth - c;
+  g.head_count = lower_tile_count(nth, head_cols, 1);
   g.ntr = nth - head_cols;  // the sub-triangle right of the head
   g.ntc = g.ntr;
   *head_tiles = g.head_count;
-  launch_trailing_update_planned(0, s, g, timing);
+  launch_trailing_update_planned(BulkKernel::Fp64, s, g, timing);
 }
 
-static void launch_trailing_update_planned(int variant, hipStream_t s, GemmArgs &g, BulkTiming *timing) {
-  const long long M = g.M, K = g.K;
-  const long long tiles = count_tiles(g.ntr, g.ntc, 1);
-  if (variant == 3) {
+static void launch_trailing_update_planned(BulkKernel kernel, hipStream_t s, GemmArgs &g, BulkTiming *timing) {
+  const long long tiles = lower_tile_count(g.ntr, g.ntc, 1);
+  const dim3 block(GEMM_THREADS);
+  if (kernel == BulkKernel::Fp32Products) {
     long long wgs = tiles;
-    if (tiles >= 1024) {  // (the same XCD-aware order as the fp64 kernel's whole tiles; all tiles are whole here)
+    if (mixed_bulk_ordered(tiles)) {  // (the same XCD-aware order as the fp64 kernel's whole tiles; all tiles are whole here)
       const XcdOrder o = xcd_order(g.ntr, tiles);
       if (o.dev) { g.order = o.dev; wgs = o.len; }
     }
-    if (g.A32) hipLaunchKernelGGL(trailing_update_f32_kernel<true>, dim3((unsigned)wgs), dim3(GEMM_THREADS), 0, s, g);
-    else hipLaunchKernelGGL(trailing_update_f32_kernel<false>, dim3((unsigned)wgs), dim3(GEMM_THREADS), 0, s, g);
+    if (g.A32) hipLaunchKernelGGL(trailing_update_f32_kernel<true>, dim3((unsigned)wgs), block, 0, s, g);
+    else hipLaunchKernelGGL(trailing_update_f32_kernel<false>, dim3((unsigned)wgs), block, 0, s, g);
     return;
   }
-  if (variant == 30 || variant == 31) {
-    // every tile a whole 128 x 128 workgroup in column-major tile order, however few there are (no quadrants, no XCD
-    // table): 30 with the ring loop where a tile is eligible, 31 with the register-staged loop
-    g.small_first = tiles;
-    g.small_count = 0;
-    const bool product = (variant == 30) == (AGP_BULK_RING != 0);
-    if (product) hipLaunchKernelGGL(trailing_update_kernel, dim3((unsigned)tiles), dim3(GEMM_THREADS), 0, s, g);
-    else hipLaunchKernelGGL(trailing_update_other_loop_kernel, dim3((unsigned)tiles), dim3(GEMM_THREADS), 0, s, g);
+  // Fp64WholeRing / Fp64WholeRegisterStaged: every tile a whole 128 x 128 workgroup in column-major tile order, however
+  // few there are (no quadrants, no XCD table), with the ring loop where a tile is eligible / the register-staged loop
+  const bool whole_only = kernel != BulkKernel::Fp64;
+  BulkSplit split;
+  if (whole_only) { split.full = tiles; timing = nullptr; }  // (a measurement variant: never timed)
+  else split = plan_bulk_update(tiles, bulk_slots(), g.head_cols > 0);
+  if (split.kernel == SplitKernel::QuadrantsOnly) {  // (not timed: BulkTiming)
+    hipLaunchKernelGGL(trailing_update_tail_kernel, dim3((unsigned)bulk_grid(split, 0, 0)), block, 0, s, g);
     return;
   }
-  // Tail split: a launch of T tiles runs floor(T / slots) full rounds of 128 x 128 workgroups (slots = 2 per
-  // CU); the T mod slots tiles left over would occupy a fraction of the chip for a whole further round.
-  // They go to trailing_update_tail_kernel as four 64 x 64 workgroups each.
-  static int slots = 0;
-  if (slots == 0) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    slots = 2 * cus;
+  if (timing && timing->e0) (void)hipEventRecord(timing->e0, s);
+  g.small_first = split.full;
+  g.small_count = (int)split.rem;
+  long long order_len = 0;
+  if (split.full > 0 && !whole_only) {
+    const XcdOrder o = xcd_order(g.ntr, split.full);
+    if (o.dev) { g.order = o.dev; order_len = o.len; }
   }
-  long long full, rem;
-  if (g.head_cols > 0) {
-    // merged update: the head's tiles are the first round(s); behind them whole rounds of large tiles, the remainder as
-    // 64 x 64 quadrants right after the head (the launch still ends with full rounds)
-    if (tiles < 2LL * slots) { full = 0; rem = tiles; }
-    else {
-      full = (tiles / slots) * slots;
-      rem = tiles - full;
-      if (rem * 4 >= 3LL * slots) { full = tiles; rem = 0; }
-    }
-    if (timing && timing->e0) (void)hipEventRecord(timing->e0, s);
-    g.small_first = full;
-    g.small_count = (int)rem;
-    long long big = full;
-    if (full > 0) {
-      const XcdOrder o = xcd_order(g.ntr, full);
-      if (o.dev) { g.order = o.dev; big = o.len; }
-    }
-    hipLaunchKernelGGL(trailing_update_kernel, dim3((unsigned)(g.head_count + big + 4 * rem)), dim3(GEMM_THREADS), 0, s, g);
-    if (timing && timing->e1) {
-      (void)hipEventRecord(timing->e1, s);
-      timing->flops = 2. * (double)K * lower_entries(M, g.ntr + g.head_cols, (long long)(g.ntr + g.head_cols) * (g.ntr + g.head_cols + 1) / 2);
-    }
-    return;
-  }
-  if (tiles < 2LL * slots) {
-    // fewer than two rounds of large tiles: 64 x 64 workgroups throughout balance the CUs better (M = 4096, K = 512:
-    // 0.196 ms instead of 0.272; with the store-only epilogue of the large tiles two rounds are enough: M = 6144 448 -> 424 us,
-    // M = 7680 707 -> 670 us)
-    full = 0; rem = tiles;
-  } else {
-    full = (tiles / slots) * slots;
-    rem = tiles - full;
-    if (rem * 4 >= 3LL * slots) { full = tiles; rem = 0; }  // an almost full round: leave it to the large tiles
-  }
-  if (full > 0) {
-    if (timing && timing->e0) (void)hipEventRecord(timing->e0, s);
-    g.small_first = full;
-    g.small_count = (int)rem;
-    long long big = full;
-    {  // XCD-aware order of the whole tiles (halves the launch's fetch traffic: 5.8 -> 2.95 GB at M = 15872; fit 30.4 -> 30.05 ms)
-      const XcdOrder o = xcd_order(g.ntr, full);
-      if (o.dev) { g.order = o.dev; big = o.len; }
-    }
-    hipLaunchKernelGGL(trailing_update_kernel, dim3((unsigned)(big + 4 * rem)), dim3(GEMM_THREADS), 0, s, g);
-    if (timing && timing->e1) {
-      (void)hipEventRecord(timing->e1, s);
-      timing->flops = 2. * (double)K * lower_entries(M, g.ntr, tiles);
-    }
-    return;
-  }
-  if (rem > 0) {
-    GemmArgs h = g;
-    h.tile_first = full;
-    hipLaunchKernelGGL(trailing_update_tail_kernel, dim3((unsigned)(4 * rem)), dim3(GEMM_THREADS), 0, s, h);
+  const bool other_loop = whole_only && (kernel == BulkKernel::Fp64WholeRing) != (AGP_BULK_RING != 0);
+  hipLaunchKernelGGL(other_loop ? trailing_update_other_loop_kernel : trailing_update_kernel,
+                     dim3((unsigned)bulk_grid(split, g.head_count, order_len)), block, 0, s, g);
+  if (timing && timing->e1) {
+    (void)hipEventRecord(timing->e1, s);
+    const int nth = g.ntr + g.head_cols;  // the launch covers the whole lower triangle, head included
+    timing->flops = 2. * (double)g.K * lower_entries(g.M, nth, lower_tile_count(nth, nth, 1));
   }
 }
 
@@ -844,7 +657,7 @@ void launch_update_f32(hipStream_t s, double *C, long long ldc, const double *P,
   g.ntr = (int)((M + GT - 1) / GT);
   g.ntc = (int)((N + GT - 1) / GT);
   if (g.ntc > g.ntr) g.ntc = g.ntr;
-  const long long tiles = count_tiles(g.ntr, g.ntc, 1);
+  const long long tiles = lower_tile_count(g.ntr, g.ntc, 1);
   if (tiles <= 0) return;
   if (g.A32) hipLaunchKernelGGL(trailing_update_f32_kernel<true>, dim3((unsigned)tiles), dim3(GEMM_THREADS), 0, s, g);
   else hipLaunchKernelGGL(trailing_update_f32_kernel<false>, dim3((unsigned)tiles), dim3(GEMM_THREADS), 0, s, g);
@@ -852,7 +665,7 @@ void launch_update_f32(hipStream_t s, double *C, long long ldc, const double *P,
 
 void launch_trailing_update(hipStream_t s, double *C, long long ldc, const double *P, const double *Q,
                             long long ldp, long long M, long long K, BulkTiming *timing) {
-  launch_trailing_update_as(0, s, C, ldc, P, Q, ldp, M, K, timing);
+  launch_trailing_update_as(BulkKernel::Fp64, s, C, ldc, P, Q, ldp, M, K, timing);
 }
 
 }  // namespace agp

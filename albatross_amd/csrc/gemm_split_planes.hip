@@ -210,8 +210,10 @@ struct PlaneArgs {
   const int *order;              // XCD-aware tile order (gemm.hip: xcd_order) or nullptr
 };
 
-// the tile (bi, bj) of this workgroup: from the order table, or of the lower-triangular grid in column-major order (as
-// gemm.hip's tile_of_block with tri = 1); false: none
+// the tile (bi, bj) of this workgroup: from the order table, or of the lower-triangular grid in column-major order; false:
+// none.  The walk is update_plan.h's lower_tile_of, kept in its own words here: through the shared helper the compiler
+// lays the blocks of these kernels out differently and reorders the loads, LDS reads and MFMAs of their K loops
+// (profiles/r08/update_plan_resources.txt).
 __device__ __forceinline__ bool plane_tile_of_block(const PlaneArgs &g, int &bi, int &bj) {
   if (g.order) {
     const int packed = g.order[blockIdx.x];
@@ -582,9 +584,7 @@ static long long plane_args(PlaneArgs &g, double *C, long long ldc, const unsign
   g.ntc = (int)((N + GT - 1) / GT);
   if (g.ntc > g.ntr) g.ntc = g.ntr;
   g.order = order;
-  long long tiles = 0;
-  for (int bj = 0; bj < g.ntc; ++bj) tiles += g.ntr - bj;
-  return order ? order_len : tiles;
+  return order ? order_len : lower_tile_count(g.ntr, g.ntc, 1);
 }
 
 // tune.lds_pad (extra dynamic LDS) sets how many workgroups share a CU next to the panel kernels of the chain stream.

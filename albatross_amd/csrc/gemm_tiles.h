@@ -58,6 +58,19 @@ struct GemmArgs {
   unsigned long long *head_done = nullptr;
 };
 
+// Entry `wg` of an XCD-aware order table (update_plan.h: xcd_tile_order): the tile (bi, bj); false: no tile.
+__device__ __forceinline__ bool order_entry(const int *order, long long wg, int &bi, int &bj) {
+  const int packed = order[wg];
+  if (packed < 0) return false;
+  bi = packed >> 16;
+  bj = packed & 0xffff;
+  return true;
+}
+// The tile of workgroup `wg` of a launch over lower tiles: from the order table where there is one, otherwise tile `wg`
+// of the column-major order; false: none.
+__device__ __forceinline__ bool ordered_tile_of(const int *order, long long wg, int ntr, int ntc, int &bi, int &bj) {
+  return order ? order_entry(order, wg, bi, bj) : lower_tile_of(wg, ntr, ntc, 1, bi, bj);
+}
 
 // Load this thread's 8 doubles of a 128 x 16 operand chunk.
 //   !KMAJOR: element (row, k) at P[row + k * ld]   (panel stored like the matrix)

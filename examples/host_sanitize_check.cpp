@@ -1,5 +1,5 @@
 // host_sanitize_check.cpp — the host-side C++ of the project under AddressSanitizer + UndefinedBehaviorSanitizer, on
-// a machine WITHOUT a GPU (examples/Makefile: `make asan`).  Six parts:
+// a machine WITHOUT a GPU (examples/Makefile: `make asan`).  Seven parts:
 //
 //  1. the sharded-fit schedule (albatross_amd/csrc/shard_sched.hip is plain C++: compiled INTO this binary with the
 //     sanitizers on) driven through agp_debug_shard_factor_custom (csrc/shard_custom.hip) with naive block operations, one rank and - through
@@ -19,6 +19,10 @@
 //  6. the pooled plan of the batched leave-one-group-out gradient (albatross_amd/csrc/logo_batch_plan.h: plain C++) on
 //     ragged groupings over 1-12 problems, every table walked, with the carve of its workspace (carve_logo_batch, part 3).
 //
+//  7. the tiling of the MFMA update launches (albatross_amd/csrc/update_plan.h: plain C++): every bulk update up to 160
+//     tile rows planned under three slot counts and five heads, the tile decode walked there and back, every order table
+//     built and read entry by entry, and sweeps of the product and staircase plans.
+//
 // Prints "host_sanitize_check ok" and exits 0; any sanitizer report aborts with a non-zero status.
 #include <cmath>
 #include <cstdio>
@@ -35,6 +39,7 @@
 #include "batch_layout.h"    // csrc/: WsLayout, BatchGeometry, the carve functions
 #include "factor_plan.h"     // csrc/: FactorPlanner, plan_panels, step_launch_shape
 #include "logo_batch_plan.h" // csrc/: the pooled plan of agp_logo_nll_gradient_batch
+#include "update_plan.h"     // csrc/: plan_bulk_update, plan_nt_sub, plan_stair, lower_tile_of, xcd_tile_order
 #include "shard_internal.h"  // agp_shard_ops_callbacks (csrc/, test-only)
 
 extern "C" {
@@ -524,6 +529,82 @@ void factor_plan_under_sanitizers() {
     }
 }
 
+// ---- part 7: the tiling of the update launches -----------------------------------------------------------------------
+void update_plan_under_sanitizers() {
+  for (int ntr = 1; ntr <= 160; ++ntr) {
+    // the decode there and back: every tile of the lower and of the full grid, and nothing behind the last one
+    for (int tri = 0; tri <= 1; ++tri)
+      for (int ntc : {1, (ntr + 1) / 2, ntr}) {
+        const long long count = agp::lower_tile_count(ntr, ntc, tri);
+        long long id = 0;
+        for (int bj = 0; bj < ntc; ++bj)
+          for (int bi = tri ? bj : 0; bi < ntr; ++bi, ++id) {
+            int gi = -1, gj = -1;
+            require(agp::lower_tile_of(id, ntr, ntc, tri, gi, gj) && gi == bi && gj == bj, "decode of a tile number");
+            require(!tri || agp::lower_tile_index(bi, bj, ntr) == id, "tile number of a tile");
+          }
+        int gi, gj;
+        require(id == count && !agp::lower_tile_of(count, ntr, ntc, tri, gi, gj) && !agp::lower_tile_of(count + 7, ntr, ntc, tri, gi, gj),
+                "no tile from the count on");
+      }
+    for (long long slots : {512ll, 208ll, 64ll})
+      for (int head_cols : {0, 1, 2, 4, 8}) {
+        const int h = head_cols < ntr ? head_cols : ntr, sub = ntr - h;
+        const long long tiles = agp::lower_tile_count(sub, sub, 1), head_count = agp::lower_tile_count(ntr, h, 1);
+        const agp::BulkSplit sp = agp::plan_bulk_update(tiles, slots, h > 0);
+        require(sp.full >= 0 && sp.rem >= 0 && sp.full + sp.rem == tiles && (sp.full % slots == 0 || sp.full == tiles), "split of a bulk update");
+        require((sp.kernel == agp::SplitKernel::QuadrantsOnly) == (sp.full == 0 && h == 0), "kernel of a bulk update");
+        if (sp.full == 0) {
+          require(agp::bulk_grid(sp, head_count, 0) == head_count + 4 * tiles, "grid without whole tiles");
+          continue;
+        }
+        // the order table of the whole tiles: every entry read, every tile [0, full) exactly once
+        const std::vector<int> table = agp::xcd_tile_order(sub, sp.full);
+        std::vector<char> seen((std::size_t)sp.full, 0);
+        require(table.size() == (std::size_t)((sp.full + agp::XCDS - 1) / agp::XCDS * agp::XCDS), "length of an order table");
+        for (std::size_t i = 0; i < table.size(); ++i) {
+          if (table[i] < 0) {
+            require(i + agp::XCDS >= table.size(), "fillers only in the last row");
+            continue;
+          }
+          const int bi = table[i] >> 16, bj = table[i] & 0xffff;
+          const long long id = agp::lower_tile_index(bi, bj, sub);
+          require(bj <= bi && bi < sub && id < sp.full && !seen[(std::size_t)id], "an order table names every whole tile once");
+          seen[(std::size_t)id] = 1;
+        }
+        require(agp::bulk_grid(sp, head_count, (long long)table.size()) == head_count + (long long)table.size() + 4 * sp.rem, "grid with a table");
+        require(agp::lower_entries(128ll * sub - 5, sub, tiles) == 0.5 * (double)(128ll * sub - 5) * (double)(128ll * sub - 4), "entries of all tiles");
+      }
+  }
+  // products and staircases: ragged sizes on both sides of every rule, every layout
+  for (long long M : {1ll, 64ll, 65ll, 960ll, 1024ll, 1408ll, 2900ll, 8192ll})
+    for (long long N : {1ll, 63ll, 128ll, 1088ll, 2944ll, 9344ll})
+      for (long long K : {1ll, 255ll, 256ll})
+        for (int layout = 0; layout < 8; ++layout)
+          for (long long count : {1ll, 7ll}) {
+            const bool tri = layout & 4;
+            const agp::NtSubPlan p = agp::plan_nt_sub(M, N, K, tri, layout & 1, layout & 2, count, 512);
+            require((p.edge == 128 || p.edge == 64 || p.edge == 32) && (!p.transposed || (p.edge == 64 && !tri)), "tile edge of a product");
+            require(p.ntr == (M + p.edge - 1) / p.edge && p.ntc <= (N + p.edge - 1) / p.edge && p.grid == agp::lower_tile_count(p.ntr, p.ntc, tri && !p.transposed),
+                    "grid of a product");
+            int bi, bj;
+            require(p.grid > 0 && agp::lower_tile_of(p.grid - 1, p.ntr, p.ntc, tri && !p.transposed, bi, bj) && bi < p.ntr && bj < p.ntc, "last tile of a product");
+          }
+  for (long long slots : {512ll, 208ll, 64ll})
+    for (long long blocks = 1; blocks <= 24; ++blocks)
+      for (long long cols : {1ll, 16ll, 80ll, 240ll}) {
+        const agp::StairPlan p = agp::plan_stair(blocks * 1536, cols * 128, 1536, 384, slots);
+        require((p.edge == 128 || p.edge == 64) && p.st_tpb * p.edge == 1536 && p.st_c0t * p.edge == 384 && p.ntr == blocks * p.st_tpb, "staircase plan");
+        // the last row tile of the last block owns its own diagonal tile and nothing right of it (rank 0 of 1, first block 0)
+        const long long diag = (blocks - 1) * p.st_tpb - p.st_c0t + (p.st_tpb - 1);
+        require(agp::stair_tile_owned(p.ntr - 1, (int)diag, 0, p.st_tpb, 1, 0, p.st_c0t) &&
+                    !agp::stair_tile_owned(p.ntr - 1, (int)diag + 1, 0, p.st_tpb, 1, 0, p.st_c0t), "staircase edge");
+      }
+  require(agp::quadrant_skipped(3, 3, 0, 1) && !agp::quadrant_skipped(3, 3, 1, 0) && !agp::quadrant_skipped(4, 3, 0, 1) && !agp::quadrant_skipped(3, 3, 1, 1),
+          "only the upper quadrant of a diagonal tile is skipped");
+  require(!agp::mixed_bulk_ordered(agp::ORDERED_FROM_TILES - 1) && agp::mixed_bulk_ordered(agp::ORDERED_FROM_TILES), "order rule of the mixed fit");
+}
+
 // ---- part 5: the owners of device memory -----------------------------------------------------------------------------
 struct FakeDevice {
   std::set<void *> live;
@@ -621,6 +702,7 @@ int main() {
   factor_plan_under_sanitizers();
   dev_mem_under_sanitizers();
   logo_batch_plan_under_sanitizers();
+  update_plan_under_sanitizers();
   std::printf("host_sanitize_check ok\n");
   return 0;
 }

@@ -101,11 +101,14 @@ def test_gemm_nt_sub_prefetching_tiles(ctx, dbg, M, N, K, tri, akm, bkm):
     test_gemm_nt_sub(ctx, dbg, M, N, K, tri, akm, bkm)
 
 
-@pytest.mark.parametrize("variant", [0, 3, 13, 14, 15])
-@pytest.mark.parametrize("M,K", [(5900, 128), (6016, 512), (700, 512), (1418, 96)])
+@pytest.mark.parametrize("M,K,variant", [(M, K, v) for v in (0, 3, 13, 14, 15) for M, K in ((5900, 128), (6016, 512), (700, 512), (1418, 96))]
+                         + [(6700, 16, 0), (6700, 16, 3)])
 def test_trailing_update_large_tiles(ctx, dbg, M, K, variant):
     """Bulk updates of more than two rounds of 128 x 128 tiles: full rounds of prefetching tiles, the tiles of the partial
-    round as 64 x 64 quadrants at the head of the same launch, ragged edge tiles (M = 5900) on the old path.  Variant 0:
+    round as 64 x 64 quadrants at the head of the same launch, ragged edge tiles (M = 5900) on the old path.  M = 6700
+    (53 tile rows, 1431 tiles, the last row ragged): the 407 tiles behind two rounds of 512 are an almost full round and
+    stay whole (csrc/update_plan.h: plan_bulk_update; tests/test_update_plan_host.py has the rule at other slot counts);
+    K = 16 keeps the case to the transfer of its matrix.  Variant 0:
     fp64 MFMA; 3: fp32 products of operands rounded while staged; 13: fp32 products of an fp32 copy of the panel
     (launch_convert_panel_f32) - the two must agree bit for bit; 14 (round 5): fp32-accurate products on the BF16 pipe from
     three bf16 planes of the panel (gemm_split_planes.hip: hi + mid + lo, six partial products) - the same 2e-7 bar as the fp32
@@ -267,8 +270,9 @@ def test_trailing_update_merged(ctx, dbg, M, K, head_cols):
 @pytest.mark.parametrize("variant", [0, 2, 4, 5])
 @pytest.mark.parametrize("M,K", [(256, 16), (640, 128), (1000, 256), (1418, 512), (130, 32), (4300, 64)])
 def test_trailing_update_variants(ctx, dbg, M, K, variant):
-    """Bulk update C -= P P^T on the lower tiles: MFMA kernel (0), the DPP-broadcast VALU kernel (2), every tile as
-    four 64 x 64 workgroups (4), full rounds of 128-tiles + a 64-tile tail (5)."""
+    """Bulk update C -= P P^T on the lower tiles through the fp64 product launch (variant 0).  Variants 2, 4 and 5 once
+    named kernels that are gone - a DPP-broadcast VALU kernel, every tile as four 64 x 64 workgroups, a 64-tile tail - and
+    run the same product launch today (csrc/debug_api.hip: bulk_kernel_of); they stay in the list as they were."""
     rng = np.random.default_rng(M + K)
     ldc, ldp = M + 8 - (M % 2), M + 10 - (M % 2)
     Cm = np.asfortranarray(rng.standard_normal((ldc, M)))

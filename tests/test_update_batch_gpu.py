@@ -44,13 +44,20 @@ def _single_predict(fm, xs):
 
 
 def _gemm_small_limit():
-    """the number of 128 x 128 tiles below which launch_gemm_nt_sub_batched switches to smaller tiles, read from its code"""
+    """the number of 128 x 128 tiles below which launch_gemm_nt_sub_batched switches to smaller tiles, read from its code;
+    the rule itself (csrc/update_plan.h: plan_nt_sub) is asked of the library: a triangular product of 3 large tiles per
+    problem gets them from tiles * count >= limit on and smaller ones below"""
     import os
     import re
+    import update_plan_cases as uc
     text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "albatross_amd", "csrc", "gemm.hip")).read()
     m = re.search(r"AGP_GEMM_SMALL_LIMIT.*?atoi\(e\)\s*:\s*(\d+)", text)
     assert m and "tiles * count < small_limit" in text
-    return int(m.group(1))
+    limit = int(m.group(1))
+    below = (limit - 1) // 3
+    assert uc.planned_nt_sub(256, 256, 128, True, False, False, below, limit)["edge"] < 128
+    assert uc.planned_nt_sub(256, 256, 128, True, False, False, below + 1, limit)["edge"] == 128
+    return limit
 
 
 def _threshold_counts():
