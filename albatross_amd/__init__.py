@@ -24,8 +24,8 @@ from .sparse_gp import (FixedInducingPoints, SparseCrossValidation, SparseCrossV
 
 from .pivoted import GreedyVarianceInducingPoints, PivotedCholesky, pivoted_cholesky
 
-from .iterative import (MATVEC_MAX_RHS, IterativeFitModel, IterativeGPFit, IterativePrediction, NotConvergedError,
-                        gram_matvec)
+from .iterative import (MATVEC_MAX_RHS, TANGENT_FORMS_MAX_PAIRS, IterativeFitModel, IterativeGPFit, IterativePrediction,
+                        NotConvergedError, gram_matvec, gram_tangent_forms)
 
 from .scores import chi_squared_cdf, crps_normal, draw_mvn, energy_score, variogram_score
 

@@ -155,6 +155,8 @@ EXPORTS = [
     ("agp_ldlt_download", C.c_int, [_P, _P, _P, C.c_int64]),
     ("agp_pivoted_cholesky", C.c_int, [_P, _P, C.POINTER(Features), C.c_int64, C.c_double, _P, _P, _P, C.c_int64, _P, C.c_int, _P]),
     ("agp_gram_matvec", C.c_int, [_P, _P, C.POINTER(Features), _P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int]),
+    ("agp_gram_tangent_forms", C.c_int, [_P, _P, C.POINTER(Features), C.c_int, _P, _P, C.c_int64, _P, C.c_int64, _P, C.c_int64,
+                                         C.c_int64, _P, C.c_int64, C.c_int]),
     ("agp_iterative_fit_create", C.c_int, [_P, _P, C.POINTER(Features), _P, _P, _P, _PP, _P, _P, _P]),
     ("agp_iterative_fit_destroy", None, [_P]),
     ("agp_iterative_fit_size", C.c_int64, [_P]),
@@ -163,6 +165,8 @@ EXPORTS = [
     ("agp_iterative_solve", C.c_int, [_P, _P, _P, C.c_int64, C.c_int64, _P, C.c_int64, C.c_int, _P, _P]),
     ("agp_iterative_predict_mean", C.c_int, [_P, _P, _P, C.POINTER(Features), _P, C.c_int]),
     ("agp_iterative_predict_marginal", C.c_int, [_P, _P, _P, C.POINTER(Features), _P, _P, C.c_int]),
+    ("agp_iterative_nll_gradient", C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int64, C.c_int64, C.c_uint64, _P, C.c_int64, C.c_int, _P, _P,
+                                             _P, C.c_int64, _P, _P]),
     ("agp_sparse_fit_create", C.c_int, [_P, _P, C.POINTER(Features), C.c_int64, _P, _P, _P, C.POINTER(Features), C.c_double, C.c_double, _PP, _P, _D]),
     ("agp_sparse_fit_create_sharded", C.c_int, [_P, _P, _P, C.POINTER(Features), C.c_int64, _P, _P, _P, C.POINTER(Features), C.c_double, C.c_double, _PP, _P, _D]),
     ("agp_sparse_fit_update", C.c_int, [_P, _P, _P, C.POINTER(Features), C.c_int64, _P, _P, _P, C.c_double, _PP, _P]),

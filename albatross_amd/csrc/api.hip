@@ -351,7 +351,7 @@ int agp_set_profiling(agp_context *ctx, int enabled) {
 }
 
 int agp_last_stage_ms(const agp_context *c, int stage, double *ms) {
-  if (!c || !ms || stage < 0 || stage > 12) return AGP_ERR_INVALID_ARGUMENT;
+  if (!c || !ms || stage < 0 || stage > 13) return AGP_ERR_INVALID_ARGUMENT;
   *ms = c->stage_ms[stage];
   return AGP_OK;
 }

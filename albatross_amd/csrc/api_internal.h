@@ -223,6 +223,9 @@ namespace agp {
 bool gram_sop_enabled();     // api.hip: the AGP_GRAM_SOP switch the Gram launchers of THIS library image follow
 void gram_sop_set(bool on);  // (debug_api.hip only: GramSopScope)
 void launch_add_diagonal(hipStream_t s, double *A, long long lda, long long n, const double *d);  // scores.hip
+// out[i + j * ldo] = +1 where entry (i, first_column + j) of agp_standard_normal(seed) is >= 0, else -1 (scores.hip)
+void launch_rademacher(hipStream_t s, unsigned long long seed, long long m, long long first_column, long long n_columns, double *out,
+                       long long ldo);
 }
 // x = L^-T z for ONE vector (api.hip): z is overwritten with x; ws: backsolve_ws_elems(n) doubles of scratch
 extern "C" {  // (defined inside api.hip's extern "C" block)

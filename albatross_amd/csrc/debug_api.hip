@@ -10,6 +10,7 @@
 #include "api_internal.h"
 #include "mfma_f64.h"
 #include "gram_matvec.h"
+#include "gram_tangent.h"
 #include "iterative_internal.h"
 #include "contract_internal.h"
 #include "shard_internal.h"
@@ -1671,6 +1672,17 @@ AGP_DEBUG_API int agp_debug_gram_matvec_plan(agp_context *ctx, const agp_kernel 
   const MvPlan p = gram_matvec_plan(&k->prog, v);
   plan[0] = p.path; plan[1] = p.slices; plan[2] = p.cols_per_slice;
   plan[3] = MV_ROWS; plan[4] = MV_COLS; plan[5] = gram_matvec_chunk_width(nrhs);
+  return AGP_OK;
+}
+
+// the tiling launch_gram_tangent_forms runs for n rows (gram_tangent.h; no device): plan = [row blocks, units (pairs of row
+// blocks), slices, tiles per slice, the longest tile list of a unit, TF_ROWS, TF_COLS, TF_MAX_PAIRS, GRAD_GROUP, the width
+// of the first chunk of ncols column pairs]
+AGP_DEBUG_API int agp_debug_gram_tangent_plan(int64_t n, int64_t ncols, int64_t *plan) {
+  if (!plan || n < 1 || ncols < 1) return AGP_ERR_INVALID_ARGUMENT;
+  const TfPlan p = gram_tangent_plan(n);
+  plan[0] = p.row_blocks; plan[1] = p.units; plan[2] = p.slices; plan[3] = p.tiles_per_slice; plan[4] = p.max_tiles;
+  plan[5] = TF_ROWS; plan[6] = TF_COLS; plan[7] = TF_MAX_PAIRS; plan[8] = GRAD_GROUP; plan[9] = gram_tangent_chunk_width(ncols);
   return AGP_OK;
 }
 

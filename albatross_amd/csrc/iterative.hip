@@ -1,6 +1,7 @@
 // iterative.hip — the exact Gaussian-process fit that never forms K: preconditioned conjugate gradients around the fused
 // product of gram_matvec.hip, preconditioned by the greedy pivoted Cholesky factor of pivoted_chol.hip
-// (agp_iterative_fit_create, agp_iterative_solve, agp_iterative_predict_*; include/albatross_amd.h).
+// (agp_iterative_fit_create, agp_iterative_solve, agp_iterative_predict_*; include/albatross_amd.h), and the probe estimate
+// of its log-likelihood gradient (agp_iterative_nll_gradient) around the tangent forms of gram_tangent.hip.
 //
 //   A = k(x, x) + diag(y_var);  A ~ L L^T + (A - L L^T), L = n x m from the pivoted Cholesky of A (m <= precond_rank);
 //   P = L L^T + delta I,  delta = max(tr(A - L L^T) / (n - m), 1e-8 max_i A_ii)  (m = n: the floor alone);
@@ -20,6 +21,7 @@
 #include <vector>
 #include "api_internal.h"
 #include "gram_matvec.h"
+#include "gram_tangent.h"
 #include "iterative_internal.h"
 #include "trace.h"
 
@@ -582,6 +584,117 @@ int agp_iterative_predict_marginal(agp_context *c, const agp_kernel *k, const ag
     launch_pcg_variance(s, Kc, S, ld, n, t, prior + j0, var + j0);
   }
   return copy_out(ctx, var, M, variance, location);
+}
+
+
+// dNLL / dslot_p = 1/2 tr(A^-1 dA_p) - 1/2 alpha^T dA_p alpha with the trace estimated from probes: s_cp = w_c^T dA_p z_c,
+// w_c = A^-1 z_c by the fit's own conjugate gradients, chunk by chunk (n x 16 of probes and of solutions at a time).  The
+// handle is read, never written.
+int agp_iterative_nll_gradient(agp_context *c, const agp_iterative_fit *fit, int n_slots, const agp_gradient_slot *slots,
+                               const double *tangents, int64_t ldt, int64_t n_probes, uint64_t seed, const double *probes, int64_t ldp,
+                               int location, double *grad_nll, double *grad_stderr, double *samples, int64_t lds, int *iterations,
+                               double *residual) {
+  if (check_fit(c, fit) != AGP_OK) return AGP_ERR_INVALID_ARGUMENT;
+  if (n_slots < 0 || n_slots > AGP_MAX_GRADIENT_SLOTS || (n_slots > 0 && (!slots || !grad_nll || !grad_stderr)) || n_probes <= 0 ||
+      (location != AGP_HOST && location != AGP_DEVICE))
+    return AGP_ERR_INVALID_ARGUMENT;
+  const long long n = fit->n, t = n_probes;
+  if ((probes && ldp < n) || (samples && lds < t) || t > 0x7fffffffll) return AGP_ERR_INVALID_ARGUMENT;
+  int ntc = 0, st = check_slots(&fit->kernel, n_slots, slots, &ntc);
+  if (st != AGP_OK) return st;
+  if (ntc > 0 && (!tangents || ldt < n)) return AGP_ERR_INVALID_ARGUMENT;
+  if (n_slots == 0) return AGP_OK;
+  agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const bool prof = ctx->profiling, host = location == AGP_HOST;
+  const long long ld = round_up(n, 2), ldf = round_up(t + 1, 2);  // column t of the forms: the alpha term
+  // scratch: the NaN flag | the forms | the tangent columns of a host caller | the probes and the solutions of a chunk | the
+  // workgroups' blocks of the forms kernel
+  const size_t forms_elems = (size_t)ldf * (size_t)n_slots, tang_elems = host ? (size_t)ld * (size_t)ntc : 0;
+  const size_t vec = (size_t)ld * PCG_COLS;
+  DevMem<double> ws;
+  AGP_HIP_CHECK(ctx, alloc_doubles(ws, 2 + forms_elems + tang_elems + 2 * vec + gram_tangent_ws_elems(n)));
+  int *flag = reinterpret_cast<int *>(ws.get());
+  double *forms_d = ws.get() + 2, *tang_stage = forms_d + forms_elems, *Z = tang_stage + tang_elems, *W = Z + vec, *tfws = W + vec;
+  const double *Td = tangents;
+  long long ldtd = ldt;
+  if (host && ntc > 0) {
+    AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(tang_stage, sizeof(double) * (size_t)ld, tangents, sizeof(double) * (size_t)ldt,
+                                        sizeof(double) * (size_t)n, (size_t)ntc, hipMemcpyHostToDevice, s));
+    AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));  // pageable source
+    Td = tang_stage;
+    ldtd = ld;
+  }
+  AGP_HIP_CHECK(ctx, hipMemsetAsync(flag, 0, sizeof(int), s));
+  const FeatView xm = fit->fit_view();
+  double solve_ms = 0., forms_ms = 0.;
+  auto lap = [&](int a, int b, double &into) -> hipError_t {  // (profiling only: waits for event b)
+    hipError_t e = hipEventSynchronize(ctx->stage_ev[b]);
+    float ms = 0.f;
+    if (e == hipSuccess && (e = hipEventElapsedTime(&ms, ctx->stage_ev[a], ctx->stage_ev[b])) == hipSuccess) into += ms;
+    return e;
+  };
+  for (long long c0 = 0; c0 < t; c0 += PCG_COLS) {
+    const long long tc = t - c0 < PCG_COLS ? t - c0 : PCG_COLS;
+    const double *Zc = Z;
+    if (!probes) {
+      launch_rademacher(s, seed, n, c0, tc, Z, ld);
+    } else if (host) {
+      AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(Z, sizeof(double) * (size_t)ld, probes + c0 * ldp, sizeof(double) * (size_t)ldp,
+                                          sizeof(double) * (size_t)n, (size_t)tc, hipMemcpyHostToDevice, s));
+      AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));  // pageable source
+    } else {
+      Zc = probes + c0 * ldp;
+    }
+    const long long ldz = Zc == Z ? ld : ldp;
+    if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[0], s));
+    {
+      TraceRange tr("agp: iterative gradient, probe solves");
+      st = pcg_solve(ctx, fit, Zc, ldz, tc, W, ld, iterations ? iterations + c0 : nullptr, residual ? residual + c0 : nullptr);
+    }
+    if (st != AGP_OK) return st;
+    if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[1], s));
+    {
+      TraceRange tr("agp: iterative gradient, tangent forms");
+      launch_gram_tangent_forms(s, fit->dprog.get(), &fit->kernel, xm, n_slots, slots, Td, ldtd, W, ld, Zc, ldz, tc, forms_d + c0, ldf, tfws,
+                                flag);
+    }
+    if (prof) {
+      AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[2], s));
+      AGP_HIP_CHECK(ctx, lap(0, 1, solve_ms));
+      AGP_HIP_CHECK(ctx, lap(1, 2, forms_ms));
+    }
+  }
+  if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[1], s));
+  launch_gram_tangent_forms(s, fit->dprog.get(), &fit->kernel, xm, n_slots, slots, Td, ldtd, fit->alpha.get(), ld, fit->alpha.get(), ld, 1,
+                            forms_d + t, ldf, tfws, flag);
+  if (prof) {
+    AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[2], s));
+    AGP_HIP_CHECK(ctx, lap(1, 2, forms_ms));
+    ctx->stage_ms[12] = solve_ms;
+    ctx->stage_ms[13] = forms_ms;
+  }
+  std::vector<double> h_forms(forms_elems);
+  int h_flag = 0;
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(h_forms.data(), forms_d, sizeof(double) * forms_elems, hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(&h_flag, flag, sizeof(int), hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  if (h_flag) return AGP_ERR_NAN_INPUT;
+  for (int p = 0; p < n_slots; ++p) {
+    const double *sp = h_forms.data() + (size_t)p * (size_t)ldf;
+    double sum = 0.;
+    for (long long cc = 0; cc < t; ++cc) sum += sp[cc];
+    const double tau = sum / (double)t;
+    double dev2 = 0.;
+    for (long long cc = 0; cc < t; ++cc) dev2 += (sp[cc] - tau) * (sp[cc] - tau);
+    grad_nll[p] = 0.5 * tau - 0.5 * sp[t];
+    grad_stderr[p] = t > 1 ? 0.5 * std::sqrt(dev2 / ((double)t * (double)(t - 1))) : NAN;
+    if (samples)
+      for (long long cc = 0; cc < t; ++cc) samples[cc + (long long)p * lds] = sp[cc];
+  }
+  return AGP_OK;
 }
 
 }  // extern "C"

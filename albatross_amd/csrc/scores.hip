@@ -43,6 +43,15 @@ __global__ void standard_normal_kernel(unsigned k0, unsigned k1, long long m, lo
     out[i + j * ldo] = standard_normal(k0, k1, (unsigned)i, (unsigned)(first_column + j));
 }
 
+// the Rademacher probes of agp_iterative_nll_gradient: +1 where the normal of the same (seed, row, column) is >= 0, else -1
+__global__ void rademacher_kernel(unsigned k0, unsigned k1, long long m, long long first_column, long long n_columns,
+                                  double *__restrict__ out, long long ldo) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  for (long long j = blockIdx.y; j < n_columns; j += gridDim.y)
+    out[i + j * ldo] = standard_normal(k0, k1, (unsigned)i, (unsigned)(first_column + j)) >= 0. ? 1. : -1.;
+}
+
 // ---- S = mean 1^T + L Z -------------------------------------------------------------------------------------------------
 // One 64 x 64 tile of S per workgroup of 256 threads (four waves, 32 x 32 each: the operand layout, the LDS pitch and the
 // lane maps of gemm64_body, gemm_tiles.h).  L is lower triangular: the K loop of row tile bi ends at that tile's diagonal
@@ -328,6 +337,13 @@ void launch_draw(hipStream_t s, const double *L, long long ldl, long long m, con
 bool usable_factor(const agp_fit *fit) { return fit && fit->A && fit->failed_pivot < 0; }
 
 }  // namespace
+
+void launch_rademacher(hipStream_t s, unsigned long long seed, long long m, long long first_column, long long n_columns, double *out,
+                       long long ldo) {
+  const long long gy = n_columns < 1024 ? n_columns : 1024;
+  rademacher_kernel<<<dim3((unsigned)((m + 255) / 256), (unsigned)gy), 256, 0, s>>>((unsigned)seed, (unsigned)(seed >> 32), m, first_column,
+                                                                                    n_columns, out, ldo);
+}
 
 void launch_add_diagonal(hipStream_t s, double *A, long long lda, long long n, const double *d) {
   add_diagonal_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(A, lda, n, d);

@@ -3,6 +3,8 @@
     out = ab.gram_matvec(cov, x, V, targets_variance=None)        # (cov(x, x) + diag(targets_variance)) @ V
     fm = model.fit_iterative(dataset, preconditioner_rank=256, tolerance=1e-10)
     fm.predict(xs).mean(); fm.predict(xs).marginal(); fm.get_fit().information / .iterations / .residual / .solve(rhs)
+    forms = ab.gram_tangent_forms(cov, x, U, V)                   # {name: U[:, c] @ d cov(x, x) / d name @ V[:, c]}
+    grad, stderr = fm.log_likelihood_gradient(num_probes=16, seed=0)   # probe estimate, no log-determinant
 
 K = cov(x, x) is evaluated pair by pair inside the product on the device and never stored: memory is O(n * columns)
 instead of O(n^2).  Every entry has the bits `Context.gram(cov, x)` gives it.
@@ -16,6 +18,71 @@ from .covariance import Measurement, has_linear_combinations
 from .gp import AlbatrossAmdError, DeviceArray, MarginalDistribution, _ptr, _values_of, default_context
 
 MATVEC_MAX_RHS = 16  # AGP_MATVEC_MAX_RHS: right-hand sides that share one evaluation of an entry
+TANGENT_FORMS_MAX_PAIRS = 8  # AGP_TANGENT_FORMS_MAX_PAIRS: column pairs that share one evaluation of a pair's tangents
+
+
+def _slot_tables(cov, fs):
+    """(slots, ctypes table, tangent columns or None) of `cov` at the features, as gp._gradient_problem builds them"""
+    slots, columns = cov.param_slots()
+    if len(slots) > capi.MAX_GRADIENT_SLOTS:
+        raise ValueError(f"more than {capi.MAX_GRADIENT_SLOTS} covariance parameter slots")
+    tangents = None
+    if columns:
+        tangents = np.empty((fs.n, len(columns)), order="F")
+        for c, (fn, name) in enumerate(columns):
+            tangents[:, c] = fn.derivative(fs.coords, name)
+    table = (capi.GradientSlot * max(1, len(slots)))(*[capi.GradientSlot(node, p) for node, p, _ in slots])
+    return slots, table, tangents
+
+
+def gram_tangent_forms(cov, features, U, V, names=None, on_device=False, context=None):
+    """{name: array[ncols]} with entry c = U[:, c] @ (d cov(features, features) / d name) @ V[:, c] for every parameter
+    name of `cov` (or those in `names`), the derivative matrix evaluated pair by pair on the device and never stored
+    (agp_gram_tangent_forms).  Slots that share a name are summed.  U, V: shape (n,) or (n, ncols); `on_device=True`
+    takes both as DeviceArrays of shape (n, ncols).  The features are taken as given: wrap them in Measurement for the
+    matrix a fit factors."""
+    ctx = context or default_context()
+    if has_linear_combinations(features):
+        raise ValueError("gram_tangent_forms: LinearCombination features are not supported")
+    fs = cov.features(features)
+    n = fs.n
+    if n == 0:
+        raise ValueError("gram_tangent_forms: no features")
+    slots, table, tangents = _slot_tables(cov, fs)
+    if names is not None:
+        unknown = set(names) - {name for _, _, name in slots}
+        if unknown:
+            raise KeyError(f"gram_tangent_forms: no covariance parameter named {sorted(unknown)}")
+    s = fs.as_struct()
+    keep = []
+    if on_device:
+        for M in (U, V):
+            if not isinstance(M, DeviceArray) or len(M.shape) != 2 or M.shape[0] != n:
+                raise ValueError("gram_tangent_forms: on_device=True takes DeviceArrays of shape (n, columns)")
+        if U.shape != V.shape:
+            raise ValueError("gram_tangent_forms: U and V must have the same shape")
+        ncols = int(U.shape[1])
+        up, vp, loc = C.c_void_p(U.ptr), C.c_void_p(V.ptr), capi.DEVICE
+        tp = None
+        if tangents is not None:
+            td = ctx.to_device(np.ascontiguousarray(tangents.T))  # (the bytes of the column-major n x columns matrix)
+            keep.append(td)
+            tp = C.c_void_p(td.ptr)
+    else:
+        Uh, Vh = (np.asfortranarray(np.asarray(M, dtype=np.float64).reshape(n, -1)) for M in (U, V))
+        if Uh.shape != Vh.shape:
+            raise ValueError("gram_tangent_forms: U and V must have the same shape")
+        ncols = Uh.shape[1]
+        up, vp, loc, tp = _ptr(Uh), _ptr(Vh), capi.HOST, _ptr(tangents)
+    forms = np.zeros((max(1, ncols), max(1, len(slots))), order="F")
+    st = ctx._lib.agp_gram_tangent_forms(ctx._h, ctx.kernel(cov), C.byref(s), len(slots), table, tp, n, up, n, vp, n, ncols,
+                                         _ptr(forms), forms.shape[0], loc)
+    ctx._check(st, "agp_gram_tangent_forms")
+    out = {}
+    for p, (_, _, name) in enumerate(slots):
+        if names is None or name in names:
+            out[name] = out.get(name, 0.) + forms[:ncols, p]
+    return out
 
 
 def gram_matvec(cov, features, V, targets_variance=None, on_device=False, context=None):
@@ -88,9 +155,10 @@ class IterativeGPFit:
     `residual` of the conjugate-gradient solve that produced it, `preconditioner_rank` of the pivoted Cholesky factor
     that preconditions it (below the requested rank when the points ran out: duplicates), `solve(rhs)`."""
 
-    def __init__(self, ctx, handle, n, train_features, information, iterations, residual):
+    def __init__(self, ctx, handle, n, train_features, information, iterations, residual, feature_set=None):
         self._ctx, self._h, self.n = ctx, handle, n
         self.train_features = train_features
+        self.feature_set = feature_set  # the flattened features of the fit (the gradient's tangents are taken there)
         self.information = information
         self.iterations = iterations
         self.residual = residual
@@ -143,7 +211,11 @@ class IterativePrediction:
 
 
 class IterativeFitModel:
-    """What `GaussianProcessRegression.fit_iterative` returns."""
+    """What `GaussianProcessRegression.fit_iterative` returns.  `gradient_iterations` / `gradient_residual`: per probe, the
+    iterations and final relative residuals of the solves of the last `log_likelihood_gradient` call (None before one)."""
+
+    gradient_iterations = None
+    gradient_residual = None
 
     def __init__(self, model, fit):
         self._model, self._fit = model, fit
@@ -159,6 +231,56 @@ class IterativeFitModel:
 
     def predict_with_measurement_noise(self, features):
         return IterativePrediction(self, features if isinstance(features, Measurement) else Measurement(features))
+
+    def log_likelihood_gradient(self, num_probes=16, seed=0, probes=None, return_samples=False):
+        """(grad, stderr): {name: d log p / d name} over every name of get_params() - the sign of
+        `GaussianProcessRegression.log_likelihood_gradient` - and the standard error of each, WITHOUT the log-likelihood
+        itself (agp_iterative_nll_gradient).  The trace term is estimated from `num_probes` Rademacher probes, a documented
+        function of `seed`, or from the columns of `probes` (n x t, used as is; sqrt(n) * identity gives the exact
+        gradient, stderr then measures nothing).  Slots that share a name have their samples summed before the standard
+        error is taken.  Mean-function parameters are exact, (d mu / d name)^T alpha, with stderr 0.
+        return_samples=True: also {name: array[t]} of the per-probe trace samples.  Raises NotConvergedError (with
+        `iterations` and `residual` per probe) when a probe solve runs out of iterations.  After a call that returned,
+        `gradient_iterations` and `gradient_residual` of this object hold the t probe solves' iteration counts and final
+        relative residuals."""
+        m, fit = self._model, self._fit
+        ctx, fs, n = fit._ctx, fit.feature_set, fit.n
+        cov = m.covariance_function_
+        slots, table, tangents = _slot_tables(cov, fs)
+        if probes is None:
+            t, pp, ldp = int(num_probes), None, 0
+        else:
+            Z = np.asfortranarray(np.asarray(probes, dtype=np.float64).reshape(n, -1))
+            t, pp, ldp = Z.shape[1], _ptr(Z), n
+        if t < 1:
+            raise ValueError("log_likelihood_gradient: at least one probe")
+        P = len(slots)
+        g, se = np.zeros(max(1, P)), np.zeros(max(1, P))
+        samples = np.zeros((t, max(1, P)), order="F")
+        its, res = np.zeros(t, dtype=np.int32), np.zeros(t)
+        st = ctx._lib.agp_iterative_nll_gradient(ctx._h, fit._h, P, table, _ptr(tangents), n, t, int(seed), pp, ldp, capi.HOST,
+                                                 _ptr(g), _ptr(se), _ptr(samples), t, _ptr(its), _ptr(res))
+        _raise(ctx, st, "agp_iterative_nll_gradient", its, res)
+        self.gradient_iterations, self.gradient_residual = its, res
+        # per name: the gradients of its slots add; a name with one slot keeps the entry's standard error, a shared name
+        # takes it from the summed samples of its slots
+        grad = {name: 0. for name in m.get_params()}
+        stderr = {name: 0. for name in m.get_params()}
+        by_name, count = {}, {}
+        for p, (_, _, name) in enumerate(slots):
+            grad[name] -= g[p]
+            by_name[name] = by_name.get(name, 0.) + samples[:, p]
+            count[name] = count.get(name, 0) + 1
+            stderr[name] = se[p]
+        for name, sm in by_name.items():
+            if count[name] > 1:
+                tau = sm.sum() / t
+                stderr[name] = 0.5 * np.sqrt(((sm - tau) ** 2).sum() / (t * (t - 1))) if t > 1 else float("nan")
+        for name in m.mean_function_.get_params():
+            grad[name] += float(m._mean_tangent(fs, name) @ fit.information)
+        if return_samples:
+            return grad, stderr, by_name
+        return grad, stderr
 
     def _predict(self, features, marginal):
         m, ctx = self._model, self._fit._ctx
@@ -196,4 +318,4 @@ def fit_iterative(model, dataset, preconditioner_rank=256, preconditioner_tolera
     st = ctx._lib.agp_iterative_fit_create(ctx._h, ctx.kernel(model.covariance_function_), C.byref(s), _ptr(y), _ptr(yv),
                                            C.byref(opt), C.byref(h), _ptr(info), C.byref(it), C.byref(res))
     _raise(ctx, st, "agp_iterative_fit_create", it.value, res.value)
-    return IterativeFitModel(model, IterativeGPFit(ctx, h, fs.n, dataset.features, info, it.value, res.value))
+    return IterativeFitModel(model, IterativeGPFit(ctx, h, fs.n, dataset.features, info, it.value, res.value, fs))

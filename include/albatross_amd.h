@@ -942,6 +942,30 @@ AGP_API int agp_pivoted_cholesky(agp_context *ctx, const agp_kernel *k, const ag
 AGP_API int agp_gram_matvec(agp_context *ctx, const agp_kernel *k, const agp_features *x, const double *y_var, const double *V,
                             int64_t ldv, int64_t nrhs, double *out, int64_t ldo, int location);
 
+/* ---- tangent bilinear forms without the matrix ----------------------------------------------
+ *   forms[c + p * ldf] = sum_i sum_j U[i, c] (dk(x_i, x_j) / dslot_p) V[j, c]      c < ncols, p < n_slots
+ * with the tangent matrix dk(x, x) / dslot_p evaluated pair by pair inside the product, never stored, and no n x n weight
+ * either: the contraction of agp_nll_gradient against VECTORS.  x is taken as given (is_measurement decides what a
+ * measurement_only term contributes, exactly as for agp_gram_matvec); y_var carries no parameter and is not an argument.
+ *   slots, tangents, ldt   as for agp_nll_gradient: n_slots <= AGP_MAX_GRADIENT_SLOTS (node, param) pairs, and for the
+ *                          AGP_OP_SCALING slots the n x (columns) tangent matrix at `location`, ldt >= n
+ *   U, ldu, V, ldv         n x ncols column-major at `location`, ldu, ldv >= n
+ *   forms, ldf             HOST memory, ldf >= ncols; nothing beyond ncols x n_slots is touched
+ * ncols == 0 or n_slots == 0: AGP_OK, nothing written.  A malformed argument or slot table: AGP_ERR_INVALID_ARGUMENT,
+ * nothing written.  A NaN tangent (a NaN coordinate): AGP_ERR_NAN_INPUT, nothing written.
+ * The tangent matrix is symmetric: a pair i > j is evaluated once, as agp_nll_gradient evaluates it, and applied with the
+ * weight U_ic V_jc + V_ic U_jc, the diagonal once.  A lane owns a row and the accumulators of a chunk of at most
+ * AGP_TANGENT_FORMS_MAX_PAIRS column pairs (8, then 4 or 1 for the rest) times 4 slots; one evaluation of a pair's
+ * tangents serves the whole chunk.  A workgroup walks the column tiles of row blocks b and (blocks - 1 - b) - together the
+ * same length for every b - or a fixed slice of them, keeps its sums in registers and writes one block of them; a second
+ * launch adds the blocks in a fixed order.  No float atomics: two identical calls return identical bits.  Scratch: 32
+ * doubles per workgroup (about a thousand workgroups), plus copies of U, V and the tangent columns for host arrays -
+ * never a table per tile of the matrix. */
+#define AGP_TANGENT_FORMS_MAX_PAIRS 8
+AGP_API int agp_gram_tangent_forms(agp_context *ctx, const agp_kernel *k, const agp_features *x, int n_slots,
+                                   const agp_gradient_slot *slots, const double *tangents, int64_t ldt, const double *U, int64_t ldu,
+                                   const double *V, int64_t ldv, int64_t ncols, double *forms, int64_t ldf, int location);
+
 /* ---- matrix-free fit: preconditioned conjugate gradients around agp_gram_matvec --------------
  * The exact fit that never forms A = k(x, x) + diag(y_var) (x as measurements, exactly the matrix agp_fit_create
  * factors; the predictions see the training features as agp_predict_* do): information = A^-1 y by conjugate gradients whose products
@@ -974,8 +998,29 @@ AGP_API int agp_gram_matvec(agp_context *ctx, const agp_kernel *k, const agp_fea
  * agp_iterative_predict_mean: mean_j = sum_i k(x_i, xs_j) information_i, the launches of agp_predict_mean.
  * agp_iterative_predict_marginal: also variance_j = k(xs_j, xs_j) - k_j^T A^-1 k_j; the cross covariances come from the
  *   Gram kernels in slices of 16 test points, each slice solved by the same conjugate gradients (its status is returned).
- * Out of scope, by design: joint predictions, the log-determinant and the log-likelihood (they need stochastic Lanczos
- * quadrature), gradients, LinearCombination features, the sharded and the mixed-precision path - the dense entry points
+ * agp_iterative_nll_gradient: the gradient of the negative log-likelihood with respect to parameter slots, WITHOUT its
+ *   value.  With A, alpha = information, the preconditioner, tolerance and max_iterations those of `fit`, dA_p = dA / dslot_p:
+ *     dNLL / dslot_p = 1/2 tr(A^-1 dA_p) - 1/2 alpha^T dA_p alpha
+ *   The second term is exact (one agp_gram_tangent_forms column pair U = V = alpha).  The trace is estimated from t =
+ *   n_probes probe vectors z_c:  w_c = A^-1 z_c by the fit's conjugate gradients in chunks of AGP_MATVEC_MAX_RHS,
+ *     s_cp = w_c^T dA_p z_c (agp_gram_tangent_forms on the features as measurements),  tau_p = mean_c s_cp,
+ *     grad_nll[p] = 1/2 tau_p - 1/2 alpha^T dA_p alpha,
+ *     grad_stderr[p] = 1/2 sqrt(sum_c (s_cp - tau_p)^2 / (t (t - 1)))   (NaN when t = 1).
+ *   probes == NULL: Rademacher probes, z_ic = +1 if entry (i, c) of agp_standard_normal(seed) is >= 0, else -1; column c
+ *     depends on (seed, c) alone, and the probes are generated chunk by chunk (never n x t).
+ *   probes != NULL: the caller's n x t matrix at `location` (ldp >= n), used as is.  The estimator is unbiased when
+ *     E z z^T = I, and EXACT for Z = sqrt(n) I with t = n.
+ *   slots, tangents, ldt   as for agp_nll_gradient (the covariance function is the fit's); tangents at `location`
+ *   grad_nll, grad_stderr  n_slots host values each;  samples (host, t x n_slots column-major at lds >= t, may be NULL): s_cp
+ *   iterations, residual   t host values each, may be NULL
+ *   Status: invalid slots, n_probes <= 0, ldp < n, lds < n_probes: AGP_ERR_INVALID_ARGUMENT.  A probe solve that runs out of
+ *   iterations: AGP_ERR_NOT_CONVERGED with iterations / residual filled as far as the solves went and the gradient outputs
+ *   untouched.  NaN and not-positive-definite as agp_iterative_solve reports them.  The handle is not modified.  Two
+ *   identical calls return identical bits.  Scratch: 2 n 16 doubles of probes and solutions plus that of a solve.  With
+ *   profiling on, the probe solves report under stage 12 and the forms (the alpha term included) under stage 13.
+ * Out of scope, by design: joint predictions, the log-determinant and the log-likelihood VALUE (they need stochastic
+ * Lanczos quadrature - the gradient above needs neither), variance-reduced trace estimators, gradients of the
+ * leave-one-out metrics, LinearCombination features, the sharded and the mixed-precision path - the dense entry points
  * serve them up to the n their memory allows. */
 typedef struct {
   int64_t precond_rank;
@@ -997,6 +1042,10 @@ AGP_API int agp_iterative_predict_mean(agp_context *ctx, const agp_kernel *k, co
                                        double *mean, int location);
 AGP_API int agp_iterative_predict_marginal(agp_context *ctx, const agp_kernel *k, const agp_iterative_fit *fit, const agp_features *xs,
                                            double *mean, double *variance, int location);
+AGP_API int agp_iterative_nll_gradient(agp_context *ctx, const agp_iterative_fit *fit, int n_slots, const agp_gradient_slot *slots,
+                                       const double *tangents, int64_t ldt, int64_t n_probes, uint64_t seed, const double *probes,
+                                       int64_t ldp, int location, double *grad_nll, double *grad_stderr, double *samples, int64_t lds,
+                                       int *iterations, double *residual);
 
 /* ---- sparse Gaussian process (FITC / PITC) --------------------------------------------------
  * SparseGaussianProcessRegression, include/albatross/src/models/sparse_gp.hpp.
@@ -1362,7 +1411,8 @@ AGP_API int agp_sharded_fit_stage(const agp_sharded_fit *fit, int stage, double 
  * 0 gram, 1 factor (total), 2 solve, 3 trailing-update kernels only (sum),
  * 4 number of trailing-update launches.  Returns ms (or a count for 4).  Stages 6-9:
  * the gradient entries (agp_nll_gradient, agp_loo_nll_gradient).  Stage 10: the step chain of agp_pivoted_cholesky.
- * Stages 11, 12: the preconditioner build and the conjugate-gradient chain of agp_iterative_fit_create. */
+ * Stages 11, 12: the preconditioner build and the conjugate-gradient chain of agp_iterative_fit_create.
+ * Stages 12, 13: the probe solves and the tangent forms of agp_iterative_nll_gradient. */
 AGP_API int agp_last_stage_ms(const agp_context *ctx, int stage, double *ms);
 /* enable (1) / disable (0) per-stage event timing (default off: events add
  * host overhead to the launch chain). */

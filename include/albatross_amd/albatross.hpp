@@ -1700,6 +1700,69 @@ Matrix gram_matvec(const CovFunc &cov, const std::vector<FeatureType> &features,
   return out;
 }
 
+// {name: forms} with forms[c] = U[:, c]^T (d cov(features, features) / d name) V[:, c] for every parameter name of `cov`: the
+// derivative matrix is evaluated pair by pair on the device and never stored (agp_gram_tangent_forms).  Slots that share a
+// name are summed.  U and V are n x columns.  The features are taken as given (wrap them as measurements for the matrix
+// a fit factors).
+template <typename CovFunc, typename FeatureType>
+std::map<std::string, Vector> gram_tangent_forms(const CovFunc &cov, const std::vector<FeatureType> &features, const Matrix &U,
+                                                 const Matrix &V) {
+  static_assert(!detail::expansion<FeatureType>::expands, "gram_tangent_forms: LinearCombination features are not supported");
+  using X = typename detail::unwrap<FeatureType>::type;
+  const std::int64_t n = static_cast<std::int64_t>(features.size());
+  if (n == 0 || U.rows() != n || V.rows() != n || U.cols() != V.cols())
+    throw std::invalid_argument("gram_tangent_forms: U and V must have one row per feature and the same columns");
+  std::vector<detail::GradSlot<X>> rows;
+  int node = 0;
+  cov.template emit_slots<X>(rows, node);
+  std::vector<agp_gradient_slot> slots;
+  std::vector<double> tangents;
+  int columns = 0;
+  for (auto &r : rows) {
+    if (r.tangent) {
+      r.slot.param = columns++;
+      tangents.resize(static_cast<std::size_t>(n) * static_cast<std::size_t>(columns));
+      for (std::int64_t i = 0; i < n; ++i)
+        tangents[static_cast<std::size_t>(r.slot.param) * static_cast<std::size_t>(n) + static_cast<std::size_t>(i)] =
+            r.tangent(detail::unwrap<FeatureType>::get(features[static_cast<std::size_t>(i)]));
+    }
+    slots.push_back(r.slot);
+  }
+  auto ctx = detail::default_context();
+  detail::KernelHolder k(cov.program());
+  detail::Flat f = detail::flatten(cov, features);
+  const std::int64_t ncols = U.cols();
+  std::vector<double> forms(static_cast<std::size_t>(std::max<std::int64_t>(ncols, 1)) * std::max<std::size_t>(slots.size(), 1), 0.);
+  detail::check(agp_gram_tangent_forms(ctx->ctx, k.k, &f.view, static_cast<int>(slots.size()), slots.data(),
+                                       tangents.empty() ? nullptr : tangents.data(), n, U.data.data(), n, V.data.data(), n, ncols,
+                                       forms.data(), std::max<std::int64_t>(ncols, 1), AGP_HOST),
+                ctx->ctx, "agp_gram_tangent_forms");
+  std::map<std::string, Vector> out;
+  for (std::size_t s = 0; s < rows.size(); ++s) {
+    Vector &dst = out[rows[s].name];
+    dst.resize(static_cast<std::size_t>(ncols), 0.);
+    for (std::int64_t c = 0; c < ncols; ++c)
+      dst[static_cast<std::size_t>(c)] += forms[static_cast<std::size_t>(c) + s * static_cast<std::size_t>(std::max<std::int64_t>(ncols, 1))];
+  }
+  return out;
+}
+
+// the options of IterativeFitModel::log_likelihood_gradient (agp_iterative_nll_gradient)
+struct IterativeGradientOptions {
+  std::int64_t num_probes = 16;  // Rademacher probes, a function of (seed, column) alone ...
+  std::uint64_t seed = 0;
+  Matrix probes;                 // ... or, when it has columns, the caller's n x t probes used as they are (sqrt(n) I: exact)
+};
+
+// {name: d log p / d name}, its standard error (0 for mean-function parameters, NaN with one probe) and the per-probe trace
+// samples per name (slots sharing a name summed); iterations / residual of the probe solves
+struct IterativeGradient {
+  ParameterStore gradient, standard_error;
+  std::map<std::string, Vector> samples;
+  std::vector<int> iterations;
+  Vector residual;
+};
+
 // the options of GaussianProcessRegression::fit_iterative (agp_iterative_options)
 struct IterativeOptions {
   std::int64_t preconditioner_rank = 256;  // rank of the pivoted Cholesky preconditioner (0: plain conjugate gradients)
@@ -1769,6 +1832,12 @@ class IterativeFitModel {
   IterativePrediction<ModelType, FeatureType, PredictFeature> predict(const std::vector<PredictFeature> &xs) const {
     return IterativePrediction<ModelType, FeatureType, PredictFeature>(*this, xs);
   }
+  // The gradient of the log-likelihood WITHOUT its value: the trace term from probes, the alpha term exactly
+  // (agp_iterative_nll_gradient; the sign of GaussianProcessRegression::log_likelihood_gradient).  Throws NotConvergedError
+  // (iterations and residual of the worst probe) when a probe solve runs out of iterations.
+  IterativeGradient log_likelihood_gradient(const IterativeGradientOptions &options = {}) const {
+    return model_.iterative_log_likelihood_gradient(fit_, options);
+  }
   template <typename PredictFeature>
   MarginalDistribution predict_(const std::vector<PredictFeature> &xs, bool marginal) const {
     static_assert(!detail::expansion<PredictFeature>::expands, "fit_iterative: LinearCombination features are not supported");
@@ -1830,6 +1899,61 @@ class GaussianProcessRegression {
     fit.preconditioner_rank = agp_iterative_fit_preconditioner_rank(h);
     fit.handle = std::shared_ptr<agp_iterative_fit>(h, [ctx](agp_iterative_fit *p) { agp_iterative_fit_destroy(p); });
     return IterativeFitModel<GaussianProcessRegression, FeatureType>(*this, std::move(fit));
+  }
+
+  // IterativeFitModel::log_likelihood_gradient: the slot table and the tangent columns at the fit's features, one call of
+  // agp_iterative_nll_gradient, then per name - the samples of its slots summed before the standard error is taken - and
+  // the mean-function parameters exactly through (d mu / d name)^T alpha, standard error 0
+  template <typename FeatureType>
+  IterativeGradient iterative_log_likelihood_gradient(const IterativeGPFit<FeatureType> &fit, const IterativeGradientOptions &options) const {
+    RegressionDataset<FeatureType> dataset;
+    dataset.features = fit.train_features;
+    const std::int64_t n = static_cast<std::int64_t>(fit.train_features.size());
+    std::vector<std::string> names;
+    std::vector<agp_gradient_slot> slots;
+    std::vector<double> tangents;
+    slot_table(dataset, &names, &slots, &tangents);
+    const bool own = options.probes.cols() > 0;
+    if (own && options.probes.rows() != n) throw std::invalid_argument("log_likelihood_gradient: one probe row per training feature");
+    const std::int64_t t = own ? options.probes.cols() : options.num_probes;
+    if (t < 1) throw std::invalid_argument("log_likelihood_gradient: at least one probe");
+    const std::size_t P = slots.size(), T = static_cast<std::size_t>(t);
+    std::vector<double> g(std::max<std::size_t>(P, 1), 0.), se(std::max<std::size_t>(P, 1), 0.), smp(T * std::max<std::size_t>(P, 1), 0.);
+    IterativeGradient out;
+    out.iterations.assign(T, 0);
+    out.residual.assign(T, 0.);
+    const int st = agp_iterative_nll_gradient(fit.context->ctx, fit.handle.get(), static_cast<int>(P), slots.data(),
+                                              tangents.empty() ? nullptr : tangents.data(), n, t, options.seed,
+                                              own ? options.probes.data.data() : nullptr, n, AGP_HOST, g.data(), se.data(), smp.data(), t,
+                                              out.iterations.data(), out.residual.data());
+    if (st == AGP_ERR_NOT_CONVERGED) {
+      std::size_t worst = 0;
+      for (std::size_t c = 1; c < T; ++c)
+        if (out.residual[c] > out.residual[worst]) worst = c;
+      throw NotConvergedError("albatross_amd: agp_iterative_nll_gradient: not converged", out.iterations[worst], out.residual[worst]);
+    }
+    detail::check(st, fit.context->ctx, "agp_iterative_nll_gradient");
+    for (const auto &kv : get_params()) out.gradient[kv.first] = out.standard_error[kv.first] = 0.;
+    std::map<std::string, int> count;
+    for (std::size_t s = 0; s < P; ++s) {  // the gradients of a name's slots add; so do their samples
+      Vector &dst = out.samples[names[s]];
+      dst.resize(T, 0.);
+      for (std::size_t c = 0; c < T; ++c) dst[c] += smp[c + s * T];
+      out.gradient[names[s]] -= g[s];
+      out.standard_error[names[s]] = se[s];
+      ++count[names[s]];
+    }
+    for (const auto &kv : out.samples) {  // a shared name: the standard error of the summed samples
+      if (count[kv.first] < 2) continue;
+      double sum = 0., dev2 = 0.;
+      for (double v : kv.second) sum += v;
+      const double tau = sum / static_cast<double>(t);
+      for (double v : kv.second) dev2 += (v - tau) * (v - tau);
+      out.standard_error[kv.first] =
+          t > 1 ? 0.5 * std::sqrt(dev2 / (static_cast<double>(t) * static_cast<double>(t - 1))) : std::numeric_limits<double>::quiet_NaN();
+    }
+    for (const auto &kv : mean_function_.get_params()) out.gradient[kv.first] += mean_tangent_dot(dataset, kv.first, kv.second, fit.information);
+    return out;
   }
 
   GaussianProcessRegression() = default;
