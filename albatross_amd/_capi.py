@@ -167,6 +167,8 @@ EXPORTS = [
     ("agp_iterative_predict_marginal", C.c_int, [_P, _P, _P, C.POINTER(Features), _P, _P, C.c_int]),
     ("agp_iterative_nll_gradient", C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int64, C.c_int64, C.c_uint64, _P, C.c_int64, C.c_int, _P, _P,
                                              _P, C.c_int64, _P, _P]),
+    ("agp_iterative_nll", C.c_int, [_P, _P, C.c_int64, C.c_uint64, _P, C.c_int64, C.c_int, C.c_double, C.c_int, _P, _P, C.c_int64, _D, _D, _D,
+                                    _P, _P, _P, _P, C.c_int64, _P, _P]),
     ("agp_sparse_fit_create", C.c_int, [_P, _P, C.POINTER(Features), C.c_int64, _P, _P, _P, C.POINTER(Features), C.c_double, C.c_double, _PP, _P, _D]),
     ("agp_sparse_fit_create_sharded", C.c_int, [_P, _P, _P, C.POINTER(Features), C.c_int64, _P, _P, _P, C.POINTER(Features), C.c_double, C.c_double, _PP, _P, _D]),
     ("agp_sparse_fit_update", C.c_int, [_P, _P, _P, C.POINTER(Features), C.c_int64, _P, _P, _P, C.c_double, _PP, _P]),

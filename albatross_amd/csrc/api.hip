@@ -131,6 +131,17 @@ int dev_release(void *p) {
   return hipFree(p);
 }
 
+// A block of dev_malloc that moves into a context slot (ParkSlot) stops being this table's: the slot frees through
+// dev_release or hands the block to whoever takes it next, and that may be the OTHER image of the library in a process that
+// loads both (the tests: libalbatross_amd.so and libalbatross_amd_debug.so each have a table, the context and its slots
+// are one).  An entry left behind would outlive a hipFree made by that image and match the next block at the address.
+void dev_forget(void *p) {
+  if (!p) return;
+  DevCache &c = dev_cache();
+  std::lock_guard<std::mutex> lock(c.mu);
+  c.live.erase(p);
+}
+
 void dev_cache_trim() {
   DevCache &c = dev_cache();
   std::vector<void *> all;
@@ -351,7 +362,7 @@ int agp_set_profiling(agp_context *ctx, int enabled) {
 }
 
 int agp_last_stage_ms(const agp_context *c, int stage, double *ms) {
-  if (!c || !ms || stage < 0 || stage > 13) return AGP_ERR_INVALID_ARGUMENT;
+  if (!c || !ms || stage < 0 || stage > 14) return AGP_ERR_INVALID_ARGUMENT;
   *ms = c->stage_ms[stage];
   return AGP_OK;
 }
@@ -751,7 +762,8 @@ void agp_fit_destroy(agp_fit *fit) {
     if (ctx && ctx->pool_batch.park(fit->slab->base, fit->slab->bytes)) (void)fit->slab->base.release();
     delete fit->slab;
   }
-  if (ctx && fit->own_A && ctx->pool_A.park(fit->own_A, fit->A_bytes)) (void)fit->own_A.release();
+  // (agp_factor_create takes its factor from dev_malloc: what the slot keeps is forgotten by the table of live blocks)
+  if (ctx && fit->own_A && ctx->pool_A.park(fit->own_A, fit->A_bytes)) dev_forget(fit->own_A.release());
   if (ctx && fit->aux_base && ctx->pool_aux.park(fit->aux_base, fit->aux_bytes)) (void)fit->aux_base.release();
   delete fit;
 }

@@ -13,6 +13,7 @@
 
 namespace agp {
 void dev_cache_trim();
+void dev_forget(void *p);  // the table of dev_malloc's live blocks drops p: it moved into a context slot (api.hip)
 // `elems` doubles (at least one) of a call's scratch from the cached allocator
 inline hipError_t alloc_doubles(DevMem<double> &m, size_t elems) {
   return static_cast<hipError_t>(m.alloc_cached(sizeof(double) * (elems ? elems : 1)));
@@ -223,6 +224,9 @@ namespace agp {
 bool gram_sop_enabled();     // api.hip: the AGP_GRAM_SOP switch the Gram launchers of THIS library image follow
 void gram_sop_set(bool on);  // (debug_api.hip only: GramSopScope)
 void launch_add_diagonal(hipStream_t s, double *A, long long lda, long long n, const double *d);  // scores.hip
+// out[i + j * ldo] = entry (i, first_column + j) of agp_standard_normal(seed) (scores.hip)
+void launch_standard_normal(hipStream_t s, unsigned long long seed, long long m, long long first_column, long long n_columns,
+                            double *out, long long ldo);
 // out[i + j * ldo] = +1 where entry (i, first_column + j) of agp_standard_normal(seed) is >= 0, else -1 (scores.hip)
 void launch_rademacher(hipStream_t s, unsigned long long seed, long long m, long long first_column, long long n_columns, double *out,
                        long long ldo);

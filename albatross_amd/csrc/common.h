@@ -84,7 +84,7 @@ struct agp_context {
   double *h_scalars = nullptr;  // pinned mirror
   void *h_status_dev = nullptr;  // h_flags (the whole status block) as the device addresses it, or nullptr
   bool profiling = false;
-  double stage_ms[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // [10]: the step chain of agp_pivoted_cholesky; [11], [12]: agp_iterative_fit_create; [12], [13]: agp_iterative_nll_gradient
+  double stage_ms[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // [10]: the step chain of agp_pivoted_cholesky; [11], [12]: agp_iterative_fit_create; [12], [13]: agp_iterative_nll_gradient; [12] .. [14]: agp_iterative_nll
   // reusable factor workspace (agp_nll re-uses it between tuner steps)
   agp::GrowBuf<double> ws_A;
   agp::GrowBuf<double> ws_aux;

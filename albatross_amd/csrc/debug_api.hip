@@ -12,6 +12,7 @@
 #include "gram_matvec.h"
 #include "gram_tangent.h"
 #include "iterative_internal.h"
+#include "lanczos_quadrature.h"
 #include "contract_internal.h"
 #include "shard_internal.h"
 #include "pub.h"
@@ -2339,6 +2340,110 @@ AGP_DEBUG_API int agp_debug_iterative_precondition(agp_context *ctx, const agp_i
   AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
   AGP_HIP_CHECK(ctx, hipGetLastError());
   AGP_HIP_CHECK(ctx, hipMemcpy2D(Z, sizeof(double) * (size_t)ldz, Zd.p, sizeof(double) * (size_t)ld, sizeof(double) * (size_t)n, (size_t)t,
+                                 hipMemcpyDeviceToHost));
+  return AGP_OK;
+}
+
+// ---- the log-likelihood value of the matrix-free fit (agp_iterative_nll) -----------------------------------------------------
+// lanczos_quadrature.h on host arrays: *out = rz0 e_1^T log(T) e_1 for the tridiagonal of the k coefficient pairs.  Host
+// only: no context, no device.
+AGP_DEBUG_API int agp_debug_lanczos_quadrature(double rz0, const double *a, const double *b, int k, double *out) {
+  return lanczos_quadrature(rz0, a, b, 1, k, out);
+}
+
+// ONE launch of pcg_record_kernel through launch_pcg_record.  ctrl: a host PcgCtrl; buf: log_len doubles, uploaded and
+// downloaded whole, the log (pcg_log_elems(max_iterations) doubles) starting at buf[offset] - what lies around it are the
+// caller's canaries.  Extents are checked first: AGP_ERR_INVALID_ARGUMENT, nothing launched.
+AGP_DEBUG_API int agp_debug_pcg_record(agp_context *ctx, const void *ctrl, double *buf, int64_t log_len, int64_t offset, int max_iterations,
+                                       int k, int t) {
+  if (!ctx || !ctrl || !buf || max_iterations < 1 || max_iterations > (1 << 20) || k < 0 || k >= max_iterations || t < 1 || t > PCG_COLS ||
+      offset < 0 || log_len < 1 || offset > log_len || (int64_t)pcg_log_elems(max_iterations) > log_len - offset)
+    return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  DevBuf<double> d;
+  DevBuf<PcgCtrl> cd;
+  AGP_HIP_CHECK(ctx, d.alloc((size_t)log_len));
+  AGP_HIP_CHECK(ctx, cd.alloc(1));
+  AGP_HIP_CHECK(ctx, hipMemcpy(d.p, buf, sizeof(double) * (size_t)log_len, hipMemcpyHostToDevice));
+  AGP_HIP_CHECK(ctx, hipMemcpy(cd.p, ctrl, sizeof(PcgCtrl), hipMemcpyHostToDevice));
+  launch_pcg_record(ctx->stream, cd.p, d.p + offset, max_iterations, k, t);
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  AGP_HIP_CHECK(ctx, hipMemcpy(buf, d.p, sizeof(double) * (size_t)log_len, hipMemcpyDeviceToHost));
+  return AGP_OK;
+}
+
+// The probes agp_iterative_nll draws for `seed` on a live fit, columns 0 .. t - 1 chunk by chunk through
+// iterative_queue_probes, at the leading dimensions the entry uses.  Z: host, n x t at ldz.
+AGP_DEBUG_API int agp_debug_iterative_probes(agp_context *ctx, const agp_iterative_fit *fit, uint64_t seed, int64_t t, double *Z, int64_t ldz) {
+  if (!ctx || !fit || !Z || t < 1 || t > (1 << 20)) return AGP_ERR_INVALID_ARGUMENT;
+  const PcgPrecondState st = iterative_precond_state(fit);
+  if (st.ctx != ctx || ldz < st.n) return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const long long n = st.n, m = st.rank, ld = round_up(n, 2), ldg = round_up(m > 0 ? m : 1, 2);
+  DevBuf<double> Zd, G1;
+  AGP_HIP_CHECK(ctx, Zd.alloc((size_t)ld * PCG_COLS));
+  AGP_HIP_CHECK(ctx, G1.alloc((size_t)ldg * PCG_COLS));
+  for (long long c0 = 0; c0 < t; c0 += PCG_COLS) {
+    const int tc = (int)(t - c0 < PCG_COLS ? t - c0 : PCG_COLS);
+    iterative_queue_probes(s, fit, seed, c0, tc, Zd.p, ld, G1.p, ldg);
+    AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+    AGP_HIP_CHECK(ctx, hipGetLastError());
+    AGP_HIP_CHECK(ctx, hipMemcpy2D(Z + c0 * ldz, sizeof(double) * (size_t)ldz, Zd.p, sizeof(double) * (size_t)ld, sizeof(double) * (size_t)n,
+                                   (size_t)tc, hipMemcpyDeviceToHost));
+  }
+  return AGP_OK;
+}
+
+// agp_iterative_solve on host right-hand sides with the coefficient log kept (iterative_solve_logged: pcg_solve itself).
+// log: ceil(nrhs / PCG_COLS) * pcg_log_elems(max_iterations) host doubles, one log per chunk; only rows 0 .. (the chunk's
+// longest recurrence) - 1 are written, the rest keeps the caller's bits.  *max_iterations: the fit's.  A first call with B
+// null asks for that alone.
+AGP_DEBUG_API int agp_debug_iterative_solve_logged(agp_context *ctx, const agp_iterative_fit *fit, const double *B, int64_t ldb, int64_t nrhs,
+                                                   double *X, int64_t ldx, int *iterations, double *residual, double *log, int64_t log_len,
+                                                   double tolerance, int *max_iterations) {
+  if (!ctx || !fit || !max_iterations) return AGP_ERR_INVALID_ARGUMENT;
+  const PcgPrecondState st = iterative_precond_state(fit);
+  if (st.ctx != ctx) return AGP_ERR_INVALID_ARGUMENT;
+  *max_iterations = iterative_max_iterations(fit);
+  if (!B) return AGP_OK;
+  const long long n = st.n, ld = round_up(n, 2), chunks = (nrhs + PCG_COLS - 1) / PCG_COLS;
+  if (!X || !log || nrhs < 1 || nrhs > 4096 || ldb < n || ldx < n || log_len < chunks * (int64_t)pcg_log_elems(*max_iterations))
+    return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  DevBuf<double> Bd, Xd;
+  AGP_HIP_CHECK(ctx, Bd.alloc((size_t)ld * (size_t)nrhs));
+  AGP_HIP_CHECK(ctx, Xd.alloc((size_t)ld * (size_t)nrhs));
+  AGP_HIP_CHECK(ctx, hipMemcpy2D(Bd.p, sizeof(double) * (size_t)ld, B, sizeof(double) * (size_t)ldb, sizeof(double) * (size_t)n, (size_t)nrhs,
+                                 hipMemcpyHostToDevice));
+  const int status = iterative_solve_logged(ctx, fit, Bd.p, ld, nrhs, Xd.p, ld, iterations, residual, log, tolerance);
+  if (status != AGP_OK) return status;
+  AGP_HIP_CHECK(ctx, hipMemcpy2D(X, sizeof(double) * (size_t)ldx, Xd.p, sizeof(double) * (size_t)ld, sizeof(double) * (size_t)n, (size_t)nrhs,
+                                 hipMemcpyDeviceToHost));
+  return AGP_OK;
+}
+
+// ONE chunk of a live solve iteration by iteration (iterative_solve_stepped): trace receives the control block after every
+// iteration (trace_len >= max_iterations * sizeof(PcgCtrl) bytes), *steps the iterations queued, log the chunk's
+// coefficient log (pcg_log_elems(max_iterations) doubles, rows 0 .. *steps - 1 written).
+AGP_DEBUG_API int agp_debug_iterative_solve_stepped(agp_context *ctx, const agp_iterative_fit *fit, const double *B, int64_t ldb, int t, double *X,
+                                                    int64_t ldx, void *trace, int64_t trace_len, int *steps, double *log, int64_t log_len) {
+  if (!ctx || !fit || !B || !X || !trace || !steps || !log || t < 1 || t > PCG_COLS) return AGP_ERR_INVALID_ARGUMENT;
+  const PcgPrecondState st = iterative_precond_state(fit);
+  const int max_it = iterative_max_iterations(fit);
+  const long long n = st.n, ld = round_up(n, 2);
+  if (st.ctx != ctx || ldb < n || ldx < n || trace_len < (int64_t)max_it * (int64_t)sizeof(PcgCtrl) || log_len < (int64_t)pcg_log_elems(max_it))
+    return AGP_ERR_INVALID_ARGUMENT;
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  DevBuf<double> Bd, Xd;
+  AGP_HIP_CHECK(ctx, Bd.alloc((size_t)ld * (size_t)t));
+  AGP_HIP_CHECK(ctx, Xd.alloc((size_t)ld * (size_t)t));
+  AGP_HIP_CHECK(ctx, hipMemcpy2D(Bd.p, sizeof(double) * (size_t)ld, B, sizeof(double) * (size_t)ldb, sizeof(double) * (size_t)n, (size_t)t,
+                                 hipMemcpyHostToDevice));
+  const int status = iterative_solve_stepped(ctx, fit, Bd.p, ld, t, Xd.p, ld, static_cast<PcgCtrl *>(trace), steps, log);
+  if (status != AGP_OK) return status;
+  AGP_HIP_CHECK(ctx, hipMemcpy2D(X, sizeof(double) * (size_t)ldx, Xd.p, sizeof(double) * (size_t)ld, sizeof(double) * (size_t)n, (size_t)t,
                                  hipMemcpyDeviceToHost));
   return AGP_OK;
 }

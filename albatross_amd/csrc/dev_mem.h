@@ -12,7 +12,8 @@ namespace agp {
 // blocks go first; agp_context_destroy empties the cache.  Pointers that did not come from dev_malloc are hipFree'd: so
 // dev_free is a correct way to free ANY device block, and the one door of the owners below.
 // A block that leaves through any other door (a context slot that is closed or takes another size) goes through
-// dev_release, so that the table of live blocks never holds an address the runtime may hand out again.
+// dev_release, and a block of dev_malloc that moves INTO a context slot is dropped from the table there (api.hip:
+// dev_forget), so that the table of live blocks never holds an address the runtime may hand out again.
 int dev_malloc_bytes(void **p, size_t bytes);        // the cached allocator
 int dev_malloc_plain_bytes(void **p, size_t bytes);  // hipMalloc
 template <class T>

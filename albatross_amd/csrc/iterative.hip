@@ -1,7 +1,10 @@
 // iterative.hip — the exact Gaussian-process fit that never forms K: preconditioned conjugate gradients around the fused
 // product of gram_matvec.hip, preconditioned by the greedy pivoted Cholesky factor of pivoted_chol.hip
-// (agp_iterative_fit_create, agp_iterative_solve, agp_iterative_predict_*; include/albatross_amd.h), and the probe estimate
-// of its log-likelihood gradient (agp_iterative_nll_gradient) around the tangent forms of gram_tangent.hip.
+// (agp_iterative_fit_create, agp_iterative_solve, agp_iterative_predict_*; include/albatross_amd.h), the probe estimate
+// of its log-likelihood gradient (agp_iterative_nll_gradient) around the tangent forms of gram_tangent.hip, and the
+// log-likelihood VALUE by stochastic Lanczos quadrature (agp_iterative_nll): the alpha and beta of every iteration, which
+// the recurrences derive on the device anyway, are the Lanczos tridiagonal of the preconditioned matrix; pcg_record_kernel
+// keeps them, lanczos_quadrature.h takes the Gauss quadrature of log on the host, and log det P is known in closed form.
 //
 //   A = k(x, x) + diag(y_var);  A ~ L L^T + (A - L L^T), L = n x m from the pivoted Cholesky of A (m <= precond_rank);
 //   P = L L^T + delta I,  delta = max(tr(A - L L^T) / (n - m), 1e-8 max_i A_ii)  (m = n: the floor alone);
@@ -15,14 +18,17 @@
 // bits whatever is queued behind.  The host looks at the control block once per PCG_LOOK iterations with the next
 // PCG_LOOK queued behind (the pattern of agp_pivoted_cholesky); once no column is active, or an error is marked, every
 // queued kernel returns at its first instruction.
+#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <new>
+#include <thread>
 #include <vector>
 #include "api_internal.h"
 #include "gram_matvec.h"
 #include "gram_tangent.h"
 #include "iterative_internal.h"
+#include "lanczos_quadrature.h"
 #include "trace.h"
 
 int pivoted_cholesky_impl(agp_context *c, const agp_kernel *k, const agp_features *x, const double *diag_dev, int64_t max_rank,
@@ -127,6 +133,37 @@ __global__ __launch_bounds__(256) void pcg_precond_kernel(const PcgCtrl *ctrl, c
 #pragma unroll
   for (int c = 0; c < PCG_COLS; ++c)
     if (c < t && !ctrl->stopped[c]) Z[(long long)c * ld + i] = (R[(long long)c * ld + i] - acc[c]) / delta;
+}
+
+// row k of the coefficient log (iterative_internal.h) = alpha, beta of the columns that iterate; one wave, lane = column
+__global__ __launch_bounds__(64) void pcg_record_kernel(const PcgCtrl *ctrl, double *log, int max_iterations, int k, int t) {
+  if (ctrl->active <= 0) return;
+  const int c = threadIdx.x;
+  if (c >= t || c >= PCG_COLS || ctrl->stopped[c]) return;
+  if (k == 0) log[c] = ctrl->rz[0][c];
+  double *alpha = log + PCG_COLS, *beta = alpha + (size_t)max_iterations * PCG_COLS;
+  alpha[(size_t)k * PCG_COLS + c] = ctrl->alpha[c];
+  beta[(size_t)k * PCG_COLS + c] = ctrl->beta[c];
+}
+
+// Z = L G1 + sqrt_delta G2, a thread per row, the sum over j = 0, 1, ... (m = 0: Z = sqrt_delta G2); Z may be G2
+__global__ __launch_bounds__(256) void pcg_probe_kernel(const double *L, long long ldl, long long n, long long m, const double *G1,
+                                                        long long ldg1, const double *G2, long long ldg2, double *Z, long long ldz, int t,
+                                                        double sqrt_delta) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  double acc[PCG_COLS];
+#pragma unroll
+  for (int c = 0; c < PCG_COLS; ++c) acc[c] = 0.;
+  for (long long j = 0; j < m; ++j) {
+    const double l = L[j * ldl + i];
+#pragma unroll
+    for (int c = 0; c < PCG_COLS; ++c)
+      if (c < t) acc[c] += l * G1[(long long)c * ldg1 + j];
+  }
+#pragma unroll
+  for (int c = 0; c < PCG_COLS; ++c)
+    if (c < t) Z[(long long)c * ldz + i] = acc[c] + sqrt_delta * G2[(long long)c * ldg2 + i];
 }
 
 // P = Z + beta P (the first iteration: P = Z); blockIdx.y = column
@@ -248,6 +285,16 @@ void launch_pcg_variance(hipStream_t s, const double *Kc, const double *S, long 
   hipLaunchKernelGGL(pcg_variance_kernel, dim3((unsigned)t), dim3(256), 0, s, Kc, S, ld, n, prior, var);
 }
 
+void launch_pcg_record(hipStream_t s, const PcgCtrl *ctrl, double *log, int max_iterations, int k, int t) {
+  hipLaunchKernelGGL(pcg_record_kernel, dim3(1), dim3(64), 0, s, ctrl, log, max_iterations, k, t);
+}
+
+void launch_pcg_probe(hipStream_t s, const double *L, long long ldl, long long n, long long m, const double *G1, long long ldg1,
+                      const double *G2, long long ldg2, double *Z, long long ldz, int t, double sqrt_delta) {
+  hipLaunchKernelGGL(pcg_probe_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, L, ldl, n, m, G1, ldg1, G2, ldg2, Z, ldz, t,
+                     sqrt_delta);
+}
+
 }  // namespace agp
 
 using namespace agp;
@@ -308,19 +355,80 @@ struct IterDestroy {
   void operator()(agp_iterative_fit *f) const { delete f; }
 };
 
-// X (n x nrhs, ldx, device) = A^-1 B (n x nrhs, ldb, device) by PCG, chunk by chunk; iterations / residual: nrhs host values
-int pcg_solve(agp_context_impl *ctx, const agp_iterative_fit *f, const double *B, long long ldb, long long nrhs, double *X, long long ldx,
-              int *iterations, double *residual) {
-  hipStream_t s = ctx->stream;
-  const long long n = f->n, m = f->rank, ld = round_up(n, 2), ldt = round_up(m > 0 ? m : 1, 2);
-  const int tmax = (int)(nrhs < PCG_COLS ? nrhs : PCG_COLS);
-  // scratch: control block | r z p q (n x t each) | t1 (m x t) | the matvec's partial sums
-  const size_t ctrl_elems = (sizeof(PcgCtrl) + sizeof(double) - 1) / sizeof(double);
-  const size_t vec = (size_t)ld * (size_t)tmax;
+// the scratch of one chunk of recurrences: control block | r z p q (n x t each) | t1 (m x t) | the matvec's partial sums | the
+// coefficient log, where one is kept
+struct PcgWork {
   DevMem<double> ws;
-  AGP_HIP_CHECK(ctx, alloc_doubles(ws, ctrl_elems + 4 * vec + (size_t)ldt * (size_t)tmax + gram_matvec_ws_elems(n)));
-  PcgCtrl *ctrl = reinterpret_cast<PcgCtrl *>(ws.get());
-  double *R = ws.get() + ctrl_elems, *Z = R + vec, *P = Z + vec, *Q = P + vec, *T1 = Q + vec, *mvws = T1 + (size_t)ldt * (size_t)tmax;
+  PcgCtrl *ctrl = nullptr;
+  double *R = nullptr, *Z = nullptr, *P = nullptr, *Q = nullptr, *T1 = nullptr, *mvws = nullptr, *log = nullptr;
+  long long ld = 0, ldt = 0;
+  size_t vec = 0;
+  hipError_t alloc(const agp_iterative_fit *f, int tmax, bool with_log) {
+    const long long n = f->n, m = f->rank;
+    ld = round_up(n, 2);
+    ldt = round_up(m > 0 ? m : 1, 2);
+    vec = (size_t)ld * (size_t)tmax;
+    const size_t ctrl_elems = (sizeof(PcgCtrl) + sizeof(double) - 1) / sizeof(double), t1 = (size_t)ldt * (size_t)tmax;
+    const size_t mv = gram_matvec_ws_elems(n);
+    const hipError_t e = alloc_doubles(ws, ctrl_elems + 4 * vec + t1 + mv + (with_log ? pcg_log_elems(f->max_iterations) : 0));
+    if (e != hipSuccess) return e;
+    ctrl = reinterpret_cast<PcgCtrl *>(ws.get());
+    R = ws.get() + ctrl_elems; Z = R + vec; P = Z + vec; Q = P + vec; T1 = Q + vec; mvws = T1 + t1;
+    log = with_log ? mvws + mv : nullptr;
+    return hipSuccess;
+  }
+};
+
+// the start of a chunk: x = 0, r = b, the norms of b and the columns that iterate at all
+hipError_t pcg_queue_start(hipStream_t s, const agp_iterative_fit *f, const PcgWork &w, const double *B, long long ldb, double *Xc,
+                           long long ldx, int t, double tol) {
+  const long long n = f->n;
+  hipError_t e = hipMemsetAsync(w.ctrl, 0, sizeof(PcgCtrl), s);
+  if (e == hipSuccess) e = hipMemsetAsync(w.Z, 0, sizeof(double) * 3 * w.vec, s);  // (a zero right-hand side never writes its z, p, q)
+  if (e == hipSuccess) e = hipMemset2DAsync(Xc, sizeof(double) * (size_t)ldx, 0, sizeof(double) * (size_t)n, (size_t)t, s);
+  if (e == hipSuccess)
+    e = hipMemcpy2DAsync(w.R, sizeof(double) * (size_t)w.ld, B, sizeof(double) * (size_t)ldb, sizeof(double) * (size_t)n, (size_t)t,
+                         hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess && w.log) e = hipMemsetAsync(w.log, 0xff, sizeof(double) * pcg_log_elems(f->max_iterations), s);  // (NaNs)
+  if (e != hipSuccess) return e;
+  launch_pcg_dot(s, DOT_BB, w.ctrl, w.R, w.R, w.ld, n, t, 0, tol);
+  return hipSuccess;
+}
+
+// the launches of iteration k of a chunk; with a coefficient log, one more after p^T A p: its row k
+void pcg_queue_iteration(hipStream_t s, const agp_iterative_fit *f, const PcgWork &w, const FeatView &xm, double *Xc, long long ldx, int t,
+                         int k, double tol) {
+  const long long n = f->n, ld = w.ld;
+  pcg_apply_preconditioner(s, f, w.ctrl, w.R, w.Z, ld, t, w.T1, w.ldt);
+  launch_pcg_dot(s, DOT_RZ, w.ctrl, w.R, w.Z, ld, n, t, k, tol);
+  launch_pcg_p(s, w.ctrl, w.Z, w.P, ld, n, t, k == 0 ? 1 : 0);
+  launch_gram_matvec(s, f->dprog.get(), &f->kernel.prog, xm, f->yvar.get(), w.P, ld, t, w.Q, ld, w.mvws, &w.ctrl->nan, &w.ctrl->active);
+  launch_pcg_dot(s, DOT_PQ, w.ctrl, w.P, w.Q, ld, n, t, k, tol);
+  if (w.log) launch_pcg_record(s, w.ctrl, w.log, f->max_iterations, k, t);
+  launch_pcg_xr(s, w.ctrl, Xc, ldx, w.R, w.P, w.Q, ld, n, t);
+  launch_pcg_dot(s, DOT_RR, w.ctrl, w.R, w.R, ld, n, t, k, tol);
+}
+
+// rows 0 .. rows - 1 of a chunk's device log to the host copy of the same layout (after the chunk's synchronisation)
+hipError_t pcg_download_log(hipStream_t s, const double *log, int max_iterations, int rows, double *host) {
+  const size_t mi = (size_t)max_iterations * PCG_COLS, nr = (size_t)rows * PCG_COLS;
+  hipError_t e = hipMemcpyAsync(host, log, sizeof(double) * (PCG_COLS + nr), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && rows > 0)
+    e = hipMemcpyAsync(host + PCG_COLS + mi, log + PCG_COLS + mi, sizeof(double) * nr, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  return e;
+}
+
+// X (n x nrhs, ldx, device) = A^-1 B (n x nrhs, ldb, device) by PCG, chunk by chunk; iterations / residual: nrhs host values.
+// host_log (optional): pcg_log_elems(max_iterations) doubles per chunk, the coefficient logs; tolerance <= 0: the fit's
+int pcg_solve(agp_context_impl *ctx, const agp_iterative_fit *f, const double *B, long long ldb, long long nrhs, double *X, long long ldx,
+              int *iterations, double *residual, double *host_log = nullptr, double tolerance = 0.) {
+  hipStream_t s = ctx->stream;
+  const double tol = tolerance > 0. ? tolerance : f->tolerance;
+  const int tmax = (int)(nrhs < PCG_COLS ? nrhs : PCG_COLS);
+  PcgWork w;
+  AGP_HIP_CHECK(ctx, w.alloc(f, tmax, host_log != nullptr));
+  PcgCtrl *ctrl = w.ctrl;
   PcgCtrl *h_look = static_cast<PcgCtrl *>(host_stage(ctx, 3 * sizeof(PcgCtrl)));
   if (!h_look) { ctx->last_error = "agp_iterative: no pinned staging memory"; return AGP_ERR_HIP; }
   PcgCtrl *h_final = h_look + 2;
@@ -330,25 +438,12 @@ int pcg_solve(agp_context_impl *ctx, const agp_iterative_fit *f, const double *B
   for (long long c0 = 0; c0 < nrhs && status == AGP_OK; c0 += PCG_COLS) {
     const int t = (int)(nrhs - c0 < PCG_COLS ? nrhs - c0 : PCG_COLS);
     double *Xc = X + c0 * ldx;
-    AGP_HIP_CHECK(ctx, hipMemsetAsync(ctrl, 0, sizeof(PcgCtrl), s));
-    AGP_HIP_CHECK(ctx, hipMemsetAsync(Z, 0, sizeof(double) * 3 * vec, s));  // (a zero right-hand side never writes its z, p, q)
-    AGP_HIP_CHECK(ctx, hipMemset2DAsync(Xc, sizeof(double) * (size_t)ldx, 0, sizeof(double) * (size_t)n, (size_t)t, s));
-    AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(R, sizeof(double) * (size_t)ld, B + c0 * ldb, sizeof(double) * (size_t)ldb, sizeof(double) * (size_t)n,
-                                        (size_t)t, hipMemcpyDeviceToDevice, s));
-    launch_pcg_dot(s, DOT_BB, ctrl, R, R, ld, n, t, 0, f->tolerance);
+    AGP_HIP_CHECK(ctx, pcg_queue_start(s, f, w, B + c0 * ldb, ldb, Xc, ldx, t, tol));
     long long blocks = 0;
     bool done = false;
     for (int k0 = 0; k0 < f->max_iterations && !done; k0 += PCG_LOOK, ++blocks) {
       const int k1 = k0 + PCG_LOOK < f->max_iterations ? k0 + PCG_LOOK : f->max_iterations;
-      for (int k = k0; k < k1; ++k) {
-        pcg_apply_preconditioner(s, f, ctrl, R, Z, ld, t, T1, ldt);
-        launch_pcg_dot(s, DOT_RZ, ctrl, R, Z, ld, n, t, k, f->tolerance);
-        launch_pcg_p(s, ctrl, Z, P, ld, n, t, k == 0 ? 1 : 0);
-        launch_gram_matvec(s, f->dprog.get(), &f->kernel.prog, xm, f->yvar.get(), P, ld, t, Q, ld, mvws, &ctrl->nan, &ctrl->active);
-        launch_pcg_dot(s, DOT_PQ, ctrl, P, Q, ld, n, t, k, f->tolerance);
-        launch_pcg_xr(s, ctrl, Xc, ldx, R, P, Q, ld, n, t);
-        launch_pcg_dot(s, DOT_RR, ctrl, R, R, ld, n, t, k, f->tolerance);
-      }
+      for (int k = k0; k < k1; ++k) pcg_queue_iteration(s, f, w, xm, Xc, ldx, t, k, tol);
       if (k1 == f->max_iterations) break;
       AGP_HIP_CHECK(ctx, hipMemcpyAsync(&h_look[blocks & 1], ctrl, sizeof(PcgCtrl), hipMemcpyDeviceToHost, s));
       AGP_HIP_CHECK(ctx, hipEventRecord(ev[blocks & 1], s));
@@ -360,10 +455,14 @@ int pcg_solve(agp_context_impl *ctx, const agp_iterative_fit *f, const double *B
     AGP_HIP_CHECK(ctx, hipMemcpyAsync(h_final, ctrl, sizeof(PcgCtrl), hipMemcpyDeviceToHost, s));
     AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
     AGP_HIP_CHECK(ctx, hipGetLastError());
+    int rows = 0;
     for (int c = 0; c < t; ++c) {
       if (iterations) iterations[c0 + c] = h_final->iters[c];
       if (residual) residual[c0 + c] = h_final->resid[c];
+      if (h_final->iters[c] > rows) rows = h_final->iters[c];
     }
+    if (host_log)
+      AGP_HIP_CHECK(ctx, pcg_download_log(s, w.log, f->max_iterations, rows, host_log + (size_t)(c0 / PCG_COLS) * pcg_log_elems(f->max_iterations)));
     if (h_final->nan) status = AGP_ERR_NAN_INPUT;
     else if (h_final->npd) status = AGP_ERR_NOT_POSITIVE_DEFINITE;
     else if (h_final->active > 0) status = AGP_ERR_NOT_CONVERGED;
@@ -422,6 +521,46 @@ int check_fit(const agp_context *ctx, const agp_iterative_fit *fit) {
 }
 
 }  // namespace
+
+namespace agp {
+
+int iterative_max_iterations(const agp_iterative_fit *f) { return f->max_iterations; }
+
+void iterative_queue_probes(hipStream_t s, const agp_iterative_fit *f, unsigned long long seed, long long c0, int tc, double *Z,
+                            long long ldz, double *G1, long long ldg) {
+  launch_standard_normal(s, seed, f->n, c0, tc, Z, ldz);
+  if (f->rank > 0) launch_standard_normal(s, pcg_probe_factor_seed(seed), f->rank, c0, tc, G1, ldg);
+  launch_pcg_probe(s, f->L.get(), f->ldl, f->n, f->rank, G1, ldg, Z, ldz, Z, ldz, tc, std::sqrt(f->delta));
+}
+
+int iterative_solve_logged(agp_context *c, const agp_iterative_fit *f, const double *B, long long ldb, long long nrhs, double *X,
+                           long long ldx, int *iterations, double *residual, double *host_log, double tolerance) {
+  return pcg_solve(static_cast<agp_context_impl *>(c), f, B, ldb, nrhs, X, ldx, iterations, residual, host_log, tolerance);
+}
+
+int iterative_solve_stepped(agp_context *c, const agp_iterative_fit *f, const double *B, long long ldb, int t, double *X, long long ldx,
+                            PcgCtrl *trace, int *steps, double *host_log) {
+  agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
+  hipStream_t s = ctx->stream;
+  PcgWork w;
+  AGP_HIP_CHECK(ctx, w.alloc(f, t, true));
+  const FeatView xm = f->fit_view();
+  AGP_HIP_CHECK(ctx, pcg_queue_start(s, f, w, B, ldb, X, ldx, t, f->tolerance));
+  int k = 0;
+  while (k < f->max_iterations) {
+    pcg_queue_iteration(s, f, w, xm, X, ldx, t, k, f->tolerance);
+    AGP_HIP_CHECK(ctx, hipMemcpyAsync(&trace[k], w.ctrl, sizeof(PcgCtrl), hipMemcpyDeviceToHost, s));
+    AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+    if (trace[k++].active <= 0) break;
+  }
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  *steps = k;
+  AGP_HIP_CHECK(ctx, pcg_download_log(s, w.log, f->max_iterations, k, host_log));
+  const PcgCtrl &last = trace[k - 1];
+  return last.nan ? AGP_ERR_NAN_INPUT : last.npd ? AGP_ERR_NOT_POSITIVE_DEFINITE : last.active > 0 ? AGP_ERR_NOT_CONVERGED : AGP_OK;
+}
+
+}  // namespace agp
 
 extern "C" {
 
@@ -589,7 +728,8 @@ int agp_iterative_predict_marginal(agp_context *c, const agp_kernel *k, const ag
 
 // dNLL / dslot_p = 1/2 tr(A^-1 dA_p) - 1/2 alpha^T dA_p alpha with the trace estimated from probes: s_cp = w_c^T dA_p z_c,
 // w_c = A^-1 z_c by the fit's own conjugate gradients, chunk by chunk (n x 16 of probes and of solutions at a time).  The
-// handle is read, never written.
+// handle is read, never written.  No value: agp_iterative_nll below returns value and gradient from one chain of solves
+// (probes of covariance P there; this entry keeps its Rademacher probes and its bits).
 int agp_iterative_nll_gradient(agp_context *c, const agp_iterative_fit *fit, int n_slots, const agp_gradient_slot *slots,
                                const double *tangents, int64_t ldt, int64_t n_probes, uint64_t seed, const double *probes, int64_t ldp,
                                int location, double *grad_nll, double *grad_stderr, double *samples, int64_t lds, int *iterations,
@@ -693,6 +833,189 @@ int agp_iterative_nll_gradient(agp_context *c, const agp_iterative_fit *fit, int
     grad_stderr[p] = t > 1 ? 0.5 * std::sqrt(dev2 / ((double)t * (double)(t - 1))) : NAN;
     if (samples)
       for (long long cc = 0; cc < t; ++cc) samples[cc + (long long)p * lds] = sp[cc];
+  }
+  return AGP_OK;
+}
+
+// NLL = 1/2 alpha^T A alpha + 1/2 log det A + n/2 log 2 pi with log det A = log det P + tr log(P^-1/2 A P^-1/2), the trace by
+// stochastic Lanczos quadrature: the probes z_c ~ N(0, P) go through the fit's conjugate gradients with the coefficient log
+// kept, and each column's alpha_k, beta_k are the Lanczos tridiagonal of the preconditioned matrix (lanczos_quadrature.h).
+// The same solves serve the gradient: w_c = A^-1 z_c, v_c = P^-1 z_c, E[w^T dA_p v] = tr(A^-1 dA_p).  The handle is read,
+// never written.  The host takes the quadrature of a chunk while the device works on that chunk's forms.
+int agp_iterative_nll(agp_context *c, const agp_iterative_fit *fit, int64_t n_probes, uint64_t seed, const double *probes, int64_t ldp,
+                      int location, double quadrature_tolerance, int n_slots, const agp_gradient_slot *slots, const double *tangents,
+                      int64_t ldt, double *nll, double *nll_stderr, double *log_det, double *log_det_samples, double *grad_nll,
+                      double *grad_stderr, double *grad_samples, int64_t lds, int *iterations, double *residual) {
+  if (check_fit(c, fit) != AGP_OK) return AGP_ERR_INVALID_ARGUMENT;
+  if (n_slots < 0 || n_slots > AGP_MAX_GRADIENT_SLOTS || (n_slots > 0 && (!slots || !grad_nll || !grad_stderr)) || n_probes <= 0 ||
+      (location != AGP_HOST && location != AGP_DEVICE) || quadrature_tolerance != quadrature_tolerance)
+    return AGP_ERR_INVALID_ARGUMENT;
+  const long long n = fit->n, m = fit->rank, t = n_probes;
+  if ((probes && ldp < n) || (grad_samples && lds < t) || t > 0x7fffffffll) return AGP_ERR_INVALID_ARGUMENT;
+  int ntc = 0, st = check_slots(&fit->kernel, n_slots, slots, &ntc);
+  if (st != AGP_OK) return st;
+  if (ntc > 0 && (!tangents || ldt < n)) return AGP_ERR_INVALID_ARGUMENT;
+  agp_context_impl *ctx = static_cast<agp_context_impl *>(c);
+  AGP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const bool prof = ctx->profiling, host = location == AGP_HOST, grad = n_slots > 0, draw = probes == nullptr;
+  const double tol = grad || !(quadrature_tolerance > 0.) ? fit->tolerance : quadrature_tolerance;
+  const long long ld = round_up(n, 2), ldf = round_up(t + 1, 2), ldg = round_up(m > 0 ? m : 1, 2);  // column t of the forms: the alpha term
+  // scratch: the NaN flag | alpha^T A alpha | the forms | the tangent columns of a host caller | the probes, the solutions and
+  // the preconditioned probes of a chunk | A alpha | the m x 16 normals of a chunk | the preconditioner's m x 16 | its control
+  // block | the workgroups' sums of the product and of the forms
+  const size_t forms_elems = grad ? (size_t)ldf * (size_t)n_slots : 0, tang_elems = host ? (size_t)ld * (size_t)ntc : 0;
+  const size_t vec = (size_t)ld * PCG_COLS, small = (size_t)ldg * PCG_COLS;
+  const size_t ctrl_elems = (sizeof(PcgCtrl) + sizeof(double) - 1) / sizeof(double), mv_elems = gram_matvec_ws_elems(n);
+  DevMem<double> ws;
+  AGP_HIP_CHECK(ctx, alloc_doubles(ws, 4 + forms_elems + tang_elems + (grad ? 3 : 2) * vec + (size_t)ld + 2 * small + ctrl_elems + mv_elems +
+                                           (grad ? gram_tangent_ws_elems(n) : 0)));
+  int *flag = reinterpret_cast<int *>(ws.get());
+  double *quad_d = ws.get() + 2, *forms_d = ws.get() + 4, *tang_stage = forms_d + forms_elems, *Z = tang_stage + tang_elems, *W = Z + vec;
+  double *V = W + vec, *Aa = V + (grad ? vec : 0), *G1 = Aa + ld, *T1 = G1 + small;
+  PcgCtrl *pctrl = reinterpret_cast<PcgCtrl *>(T1 + small);
+  double *mvws = T1 + small + ctrl_elems, *tfws = mvws + mv_elems;
+  const double *Td = tangents;
+  long long ldtd = ldt;
+  if (host && ntc > 0 && grad) {
+    AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(tang_stage, sizeof(double) * (size_t)ld, tangents, sizeof(double) * (size_t)ldt,
+                                        sizeof(double) * (size_t)n, (size_t)ntc, hipMemcpyHostToDevice, s));
+    AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));  // pageable source
+    Td = tang_stage;
+    ldtd = ld;
+  }
+  AGP_HIP_CHECK(ctx, hipMemsetAsync(flag, 0, sizeof(int), s));
+  if (grad) {  // the preconditioner's kernels read a control block: one column set that is all active
+    PcgCtrl hc;
+    std::memset(&hc, 0, sizeof(hc));
+    hc.active = 1;
+    AGP_HIP_CHECK(ctx, hipMemcpyAsync(pctrl, &hc, sizeof(hc), hipMemcpyHostToDevice, s));
+    AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));  // pageable source
+  }
+  const FeatView xm = fit->fit_view();
+  // the data term: one product with alpha and one dot, both in a fixed order
+  launch_gram_matvec(s, fit->dprog.get(), &fit->kernel.prog, xm, fit->yvar.get(), fit->alpha.get(), ld, 1, Aa, ld, mvws, flag);
+  launch_dot(s, fit->alpha.get(), Aa, n, quad_d);
+  double solve_ms = 0., forms_ms = 0., value_ms = 0.;
+  auto lap = [&](int a, int b, double &into) -> hipError_t {  // (profiling only: waits for event b)
+    hipError_t e = hipEventSynchronize(ctx->stage_ev[b]);
+    float ms = 0.f;
+    if (e == hipSuccess && (e = hipEventElapsedTime(&ms, ctx->stage_ev[a], ctx->stage_ev[b])) == hipSuccess) into += ms;
+    return e;
+  };
+  std::vector<double> hlog(pcg_log_elems(fit->max_iterations)), sample((size_t)t);
+  std::vector<int> its((size_t)PCG_COLS);
+  for (long long c0 = 0; c0 < t; c0 += PCG_COLS) {
+    const int tc = (int)(t - c0 < PCG_COLS ? t - c0 : PCG_COLS);
+    if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[3], s));
+    if (draw) {
+      TraceRange tr("agp: iterative value, probes");
+      iterative_queue_probes(s, fit, seed, c0, tc, Z, ld, G1, ldg);
+    } else {
+      AGP_HIP_CHECK(ctx, hipMemcpy2DAsync(Z, sizeof(double) * (size_t)ld, probes + c0 * ldp, sizeof(double) * (size_t)ldp,
+                                          sizeof(double) * (size_t)n, (size_t)tc, host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+      if (host) AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));  // pageable source
+    }
+    if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[0], s));
+    {
+      TraceRange tr("agp: iterative value, probe solves");
+      st = pcg_solve(ctx, fit, Z, ld, tc, W, ld, its.data(), residual ? residual + c0 : nullptr, hlog.data(), tol);
+    }
+    if (iterations)
+      for (int cc = 0; cc < tc; ++cc) iterations[c0 + cc] = its[cc];
+    if (st != AGP_OK) return st;
+    if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[1], s));
+    if (grad) {
+      TraceRange tr("agp: iterative value, tangent forms");
+      pcg_apply_preconditioner(s, fit, pctrl, Z, V, ld, tc, T1, ldg);
+      launch_gram_tangent_forms(s, fit->dprog.get(), &fit->kernel, xm, n_slots, slots, Td, ldtd, W, ld, V, ld, tc, forms_d + c0, ldf, tfws, flag);
+    }
+    if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[2], s));
+    {
+      TraceRange tr("agp: iterative value, Lanczos quadrature");
+      const auto t0 = std::chrono::steady_clock::now();
+      const double *la = hlog.data() + PCG_COLS, *lb = la + (size_t)fit->max_iterations * PCG_COLS;
+      int quad[PCG_COLS], longest = 0;
+      auto column = [&](int cc) { quad[cc] = lanczos_quadrature(hlog[cc], la + cc, lb + cc, PCG_COLS, its[cc], &sample[c0 + cc]); };
+      for (int cc = 0; cc < tc; ++cc) longest = its[cc] > longest ? its[cc] : longest;
+      // O(k^2) per column and one dependent chain of rotations: the columns of a chunk go to a host thread each once they
+      // are long enough to repay it (each writes its own sample: the bits do not depend on the threads)
+      // (a thread that cannot be started - std::system_error, bad_alloc - leaves its column and the later ones to this one:
+      // no exception leaves the entry)
+      std::vector<std::thread> pool;
+      int threaded = 0;
+      try {
+        if (longest >= 128) {
+          pool.reserve((size_t)tc);
+          for (int cc = 1; cc < tc; ++cc) { pool.emplace_back(column, cc); threaded = cc; }
+        }
+      } catch (...) {
+      }
+      column(0);
+      for (int cc = threaded + 1; cc < tc; ++cc) column(cc);
+      for (auto &th : pool) th.join();
+      for (int cc = 0; cc < tc; ++cc)
+        if (quad[cc] != AGP_OK) return quad[cc];
+      if (prof) value_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    if (prof) {
+      AGP_HIP_CHECK(ctx, lap(3, 0, value_ms));
+      AGP_HIP_CHECK(ctx, lap(0, 1, solve_ms));
+      AGP_HIP_CHECK(ctx, lap(1, 2, forms_ms));
+    }
+  }
+  if (grad) {
+    if (prof) AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[1], s));
+    launch_gram_tangent_forms(s, fit->dprog.get(), &fit->kernel, xm, n_slots, slots, Td, ldtd, fit->alpha.get(), ld, fit->alpha.get(), ld, 1,
+                              forms_d + t, ldf, tfws, flag);
+    if (prof) {
+      AGP_HIP_CHECK(ctx, hipEventRecord(ctx->stage_ev[2], s));
+      AGP_HIP_CHECK(ctx, lap(1, 2, forms_ms));
+    }
+  }
+  std::vector<double> h_forms(forms_elems);
+  int h_flag = 0;
+  double quad = 0.;
+  if (grad) AGP_HIP_CHECK(ctx, hipMemcpyAsync(h_forms.data(), forms_d, sizeof(double) * forms_elems, hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(&quad, quad_d, sizeof(double), hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipMemcpyAsync(&h_flag, flag, sizeof(int), hipMemcpyDeviceToHost, s));
+  AGP_HIP_CHECK(ctx, hipStreamSynchronize(s));
+  AGP_HIP_CHECK(ctx, hipGetLastError());
+  if (h_flag || quad != quad) return AGP_ERR_NAN_INPUT;
+  // log det P = (n - m) log delta + log det(delta I + L^T L)
+  double ld_p = (double)(n - m) * std::log(fit->delta);
+  if (m > 0) {
+    double ld_m = 0.;
+    if ((st = agp_fit_log_determinant(fit->mfac, &ld_m)) != AGP_OK) return st;
+    ld_p += ld_m;
+  }
+  double sum = 0.;
+  for (long long cc = 0; cc < t; ++cc) sum += sample[cc];
+  const double mean = sum / (double)t;
+  double dev2 = 0.;
+  for (long long cc = 0; cc < t; ++cc) dev2 += (sample[cc] - mean) * (sample[cc] - mean);
+  const double ld_a = ld_p + mean, ld_se = t > 1 ? std::sqrt(dev2 / ((double)t * (double)(t - 1))) : NAN;
+  if (prof) {
+    ctx->stage_ms[12] = solve_ms;
+    ctx->stage_ms[13] = forms_ms;
+    ctx->stage_ms[14] = value_ms;
+  }
+  if (log_det) *log_det = ld_a;
+  if (nll) *nll = 0.5 * quad + 0.5 * ld_a + 0.5 * (double)n * std::log(2. * M_PI);
+  if (nll_stderr) *nll_stderr = 0.5 * ld_se;
+  if (log_det_samples)
+    for (long long cc = 0; cc < t; ++cc) log_det_samples[cc] = sample[cc];
+  for (int p = 0; p < n_slots; ++p) {
+    const double *sp = h_forms.data() + (size_t)p * (size_t)ldf;
+    double fsum = 0.;
+    for (long long cc = 0; cc < t; ++cc) fsum += sp[cc];
+    const double tau = fsum / (double)t;
+    double fdev2 = 0.;
+    for (long long cc = 0; cc < t; ++cc) fdev2 += (sp[cc] - tau) * (sp[cc] - tau);
+    grad_nll[p] = 0.5 * tau - 0.5 * sp[t];
+    grad_stderr[p] = t > 1 ? 0.5 * std::sqrt(fdev2 / ((double)t * (double)(t - 1))) : NAN;
+    if (grad_samples)
+      for (long long cc = 0; cc < t; ++cc) grad_samples[cc + (long long)p * lds] = sp[cc];
   }
   return AGP_OK;
 }

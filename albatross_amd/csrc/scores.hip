@@ -321,13 +321,6 @@ int copy_out_block(agp_context *ctx, const double *dev, long long ld_dev, long l
   return AGP_OK;
 }
 
-void launch_standard_normal(hipStream_t s, unsigned long long seed, long long m, long long first_column, long long n_columns,
-                            double *out, long long ldo) {
-  const long long gy = n_columns < 1024 ? n_columns : 1024;
-  standard_normal_kernel<<<dim3((unsigned)((m + 255) / 256), (unsigned)gy), 256, 0, s>>>(
-      (unsigned)seed, (unsigned)(seed >> 32), m, first_column, n_columns, out, ldo);
-}
-
 void launch_draw(hipStream_t s, const double *L, long long ldl, long long m, const double *Z, long long ldz, long long n,
                  const double *mean, double *S, long long lds_) {
   DrawArgs g{L, ldl, m, Z, ldz, n, mean, S, lds_};
@@ -337,6 +330,13 @@ void launch_draw(hipStream_t s, const double *L, long long ldl, long long m, con
 bool usable_factor(const agp_fit *fit) { return fit && fit->A && fit->failed_pivot < 0; }
 
 }  // namespace
+
+void launch_standard_normal(hipStream_t s, unsigned long long seed, long long m, long long first_column, long long n_columns,
+                            double *out, long long ldo) {
+  const long long gy = n_columns < 1024 ? n_columns : 1024;
+  standard_normal_kernel<<<dim3((unsigned)((m + 255) / 256), (unsigned)gy), 256, 0, s>>>(
+      (unsigned)seed, (unsigned)(seed >> 32), m, first_column, n_columns, out, ldo);
+}
 
 void launch_rademacher(hipStream_t s, unsigned long long seed, long long m, long long first_column, long long n_columns, double *out,
                        long long ldo) {

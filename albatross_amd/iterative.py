@@ -5,6 +5,8 @@
     fm.predict(xs).mean(); fm.predict(xs).marginal(); fm.get_fit().information / .iterations / .residual / .solve(rhs)
     forms = ab.gram_tangent_forms(cov, x, U, V)                   # {name: U[:, c] @ d cov(x, x) / d name @ V[:, c]}
     grad, stderr = fm.log_likelihood_gradient(num_probes=16, seed=0)   # probe estimate, no log-determinant
+    value, stderr = fm.log_likelihood(num_probes=16, seed=0)           # stochastic Lanczos quadrature
+    value, stderr, grad, grad_stderr = fm.log_likelihood_and_gradient(num_probes=16, seed=0)   # one chain of solves
 
 K = cov(x, x) is evaluated pair by pair inside the product on the device and never stored: memory is O(n * columns)
 instead of O(n^2).  Every entry has the bits `Context.gram(cov, x)` gives it.
@@ -180,6 +182,39 @@ class IterativeGPFit:
         x = out[:, 0].copy() if one else out
         return (x, its, res) if return_info else x
 
+    def _nll(self, num_probes, seed, probes, quadrature_tolerance, slots=(), table=None, tangents=None):
+        """one agp_iterative_nll call: dict(nll, nll_stderr, log_det, samples (t), grad, grad_stderr (P each), grad_samples
+        (t x P), iterations, residual)"""
+        ctx, n = self._ctx, self.n
+        if probes is None:
+            t, pp, ldp = int(num_probes), None, 0
+        else:
+            Z = np.asfortranarray(np.asarray(probes, dtype=np.float64).reshape(n, -1))
+            t, pp, ldp = Z.shape[1], _ptr(Z), n
+        if t < 1:
+            raise ValueError("log_likelihood: at least one probe")
+        P = len(slots)
+        nll, se, ld = C.c_double(), C.c_double(), C.c_double()
+        samples = np.zeros(t)
+        g, gse = np.zeros(max(1, P)), np.zeros(max(1, P))
+        gs = np.zeros((t, max(1, P)), order="F")
+        its, res = np.zeros(t, dtype=np.int32), np.zeros(t)
+        qt = 0. if quadrature_tolerance is None else float(quadrature_tolerance)
+        st = ctx._lib.agp_iterative_nll(ctx._h, self._h, t, int(seed), pp, ldp, capi.HOST, qt, P, table, _ptr(tangents), n,
+                                        C.byref(nll), C.byref(se), C.byref(ld), _ptr(samples), _ptr(g), _ptr(gse), _ptr(gs), t,
+                                        _ptr(its), _ptr(res))
+        _raise(ctx, st, "agp_iterative_nll", its, res)
+        return dict(nll=nll.value, nll_stderr=se.value, log_det=ld.value, samples=samples, grad=g[:P], grad_stderr=gse[:P],
+                    grad_samples=gs[:, :P], iterations=its, residual=res)
+
+    def log_determinant(self, num_probes=16, seed=0, probes=None, quadrature_tolerance=None, return_samples=False):
+        """(log det(K + diag(var)), its standard error) by stochastic Lanczos quadrature (agp_iterative_nll): the closed-form
+        log-determinant of the preconditioner plus the probe estimate of tr log of the preconditioned matrix - see
+        `IterativeFitModel.log_likelihood` for the arguments.  return_samples=True: also the t per-probe samples."""
+        r = self._nll(num_probes, seed, probes, quadrature_tolerance)
+        out = (r["log_det"], 2. * r["nll_stderr"])
+        return out + (r["samples"],) if return_samples else out
+
     def close(self):
         if getattr(self, "_h", None) and getattr(self._ctx, "_h", None):
             self._ctx._lib.agp_iterative_fit_destroy(self._h)
@@ -212,10 +247,13 @@ class IterativePrediction:
 
 class IterativeFitModel:
     """What `GaussianProcessRegression.fit_iterative` returns.  `gradient_iterations` / `gradient_residual`: per probe, the
-    iterations and final relative residuals of the solves of the last `log_likelihood_gradient` call (None before one)."""
+    iterations and final relative residuals of the solves of the last `log_likelihood_gradient` call (None before one);
+    `value_iterations` / `value_residual`: the same of the last `log_likelihood` / `log_likelihood_and_gradient` call."""
 
     gradient_iterations = None
     gradient_residual = None
+    value_iterations = None
+    value_residual = None
 
     def __init__(self, model, fit):
         self._model, self._fit = model, fit
@@ -262,8 +300,47 @@ class IterativeFitModel:
                                                  _ptr(g), _ptr(se), _ptr(samples), t, _ptr(its), _ptr(res))
         _raise(ctx, st, "agp_iterative_nll_gradient", its, res)
         self.gradient_iterations, self.gradient_residual = its, res
-        # per name: the gradients of its slots add; a name with one slot keeps the entry's standard error, a shared name
-        # takes it from the summed samples of its slots
+        grad, stderr, by_name = self._gradient_by_name(slots, g, se, samples)
+        if return_samples:
+            return grad, stderr, by_name
+        return grad, stderr
+
+    def log_likelihood(self, num_probes=16, seed=0, probes=None, quadrature_tolerance=None, return_samples=False):
+        """(value, stderr): the log-likelihood of the fitted dataset - the sign and the constant of
+        `GaussianProcessRegression.log_likelihood` - and its standard error, by stochastic Lanczos quadrature
+        (agp_iterative_nll).  log det A = log det P + tr log(P^-1/2 A P^-1/2): the first term in closed form from the
+        preconditioner the fit holds, the trace estimated from `num_probes` probes z ~ N(0, P), a documented function of
+        `seed`, whose conjugate-gradient coefficients are the Lanczos tridiagonal of the preconditioned matrix.  The data
+        term is exact to the fit's tolerance.  The better the preconditioner, the smaller the standard error.
+        probes: an n x t matrix used as z as is (sqrt(t) [L | sqrt(delta) I] with t = n + rank is exact).
+        quadrature_tolerance: the relative residual at which a probe's recurrence stops; None: the fit's tolerance.
+        return_samples=True: also the t per-probe samples of tr log.  Raises NotConvergedError like
+        `log_likelihood_gradient`; `value_iterations` / `value_residual` hold the probe solves' counts after a call."""
+        r = self._fit._nll(num_probes, seed, probes, quadrature_tolerance)
+        self.value_iterations, self.value_residual = r["iterations"], r["residual"]
+        out = (-r["nll"], r["nll_stderr"])
+        return out + (r["samples"],) if return_samples else out
+
+    def log_likelihood_and_gradient(self, num_probes=16, seed=0, probes=None, return_samples=False):
+        """(value, stderr, grad, grad_stderr): `log_likelihood` and {name: d log p / d name} with its standard errors from
+        ONE chain of probe solves (agp_iterative_nll): with w = A^-1 z and v = P^-1 z, E[w^T dA v] = tr(A^-1 dA) for
+        z ~ N(0, P).  The solves run at the fit's tolerance.  Names, signs, shared names and mean-function parameters
+        as in `log_likelihood_gradient` (whose Rademacher probes give other samples of the same trace).
+        return_samples=True: also (the t samples of tr log, {name: array[t]} of the trace samples)."""
+        m, fit = self._model, self._fit
+        fs = fit.feature_set
+        slots, table, tangents = _slot_tables(m.covariance_function_, fs)
+        r = fit._nll(num_probes, seed, probes, None, slots, table, tangents)
+        self.value_iterations, self.value_residual = r["iterations"], r["residual"]
+        grad, stderr, by_name = self._gradient_by_name(slots, r["grad"], r["grad_stderr"], r["grad_samples"])
+        out = (-r["nll"], r["nll_stderr"], grad, stderr)
+        return out + (r["samples"], by_name) if return_samples else out
+
+    def _gradient_by_name(self, slots, g, se, samples):
+        """per name: the gradients of its slots add; a name with one slot keeps the entry's standard error, a shared name
+        takes it from the summed samples of its slots; mean-function parameters are exact"""
+        m, fit = self._model, self._fit
+        t = samples.shape[0]
         grad = {name: 0. for name in m.get_params()}
         stderr = {name: 0. for name in m.get_params()}
         by_name, count = {}, {}
@@ -277,10 +354,8 @@ class IterativeFitModel:
                 tau = sm.sum() / t
                 stderr[name] = 0.5 * np.sqrt(((sm - tau) ** 2).sum() / (t * (t - 1))) if t > 1 else float("nan")
         for name in m.mean_function_.get_params():
-            grad[name] += float(m._mean_tangent(fs, name) @ fit.information)
-        if return_samples:
-            return grad, stderr, by_name
-        return grad, stderr
+            grad[name] += float(m._mean_tangent(fit.feature_set, name) @ fit.information)
+        return grad, stderr, by_name
 
     def _predict(self, features, marginal):
         m, ctx = self._model, self._fit._ctx

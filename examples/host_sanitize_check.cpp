@@ -23,8 +23,13 @@
 //     tile rows planned under three slot counts and five heads, the tile decode walked there and back, every order table
 //     built and read entry by entry, and sweeps of the product and staircase plans.
 //
+//  8. the host quadrature of the matrix-free fit's log-likelihood value (albatross_amd/csrc/lanczos_quadrature.h: plain
+//     C++): coefficient sets of 1 to 600 rows, strided as the coefficient log strides them, against the closed forms at one
+//     and two rows and against the double instantiation, and every refused input.
+//
 // Prints "host_sanitize_check ok" and exits 0; any sanitizer report aborts with a non-zero status.
 #include <cmath>
+#include <random>
 #include <cstdio>
 #include <cstdint>
 #include <cstdlib>
@@ -40,6 +45,7 @@
 #include "factor_plan.h"     // csrc/: FactorPlanner, plan_panels, step_launch_shape
 #include "logo_batch_plan.h" // csrc/: the pooled plan of agp_logo_nll_gradient_batch
 #include "update_plan.h"     // csrc/: plan_bulk_update, plan_nt_sub, plan_stair, lower_tile_of, xcd_tile_order
+#include "lanczos_quadrature.h"  // csrc/: the Gauss quadrature of log from conjugate-gradient coefficients
 #include "shard_internal.h"  // agp_shard_ops_callbacks (csrc/, test-only)
 
 extern "C" {
@@ -694,6 +700,37 @@ void dev_mem_under_sanitizers() {
 }
 }  // namespace
 
+// ---- part 8: the Gauss quadrature of agp_iterative_nll (csrc/lanczos_quadrature.h) ----------------------------------------------
+void lanczos_quadrature_under_sanitizers() {
+  std::mt19937 gen(8);
+  std::uniform_real_distribution<double> ua(0.02, 2.), ub(0.05, 0.95);
+  const long long stride = 16;  // PCG_COLS: the log's rows
+  for (int k : {0, 1, 2, 3, 17, 128, 343, 600}) {
+    std::vector<double> a((size_t)std::max(k, 1) * stride, NAN), b((size_t)std::max(k, 1) * stride, NAN);
+    for (int i = 0; i < k; ++i) { a[(size_t)(i * stride + 5)] = ua(gen); b[(size_t)(i * stride + 5)] = ub(gen); }
+    double wide = NAN, plain = NAN;
+    require(agp::lanczos_quadrature(3.5, a.data() + 5, b.data() + 5, stride, k, &wide) == AGP_OK, "lanczos_quadrature: status");
+    require(agp::lanczos_quadrature_as<double>(3.5, a.data() + 5, b.data() + 5, stride, k, &plain) == AGP_OK, "lanczos_quadrature: double");
+    require(std::fabs(wide - plain) <= 1e-11 * (1. + std::fabs(wide)), "lanczos_quadrature: the two precisions agree");
+    if (k == 0) require(wide == 0., "lanczos_quadrature: no row");
+    if (k == 1) require(std::fabs(wide - 3.5 * std::log(1. / a[5])) <= 1e-14 * (1. + std::fabs(wide)), "lanczos_quadrature: one row");
+    if (k == 2) {  // e_1^T log(T) e_1 of a 2 x 2 matrix from its eigenvalues and the first components of its eigenvectors
+      const double t00 = 1. / a[5], t11 = 1. / a[stride + 5] + b[stride + 5] / a[5], t01 = std::sqrt(b[stride + 5]) / a[5];
+      const double mid = 0.5 * (t00 + t11), rad = std::sqrt(0.25 * (t00 - t11) * (t00 - t11) + t01 * t01);
+      const double l0 = mid - rad, l1 = mid + rad, w1 = (t00 - l0) / (l1 - l0);
+      require(std::fabs(wide - 3.5 * ((1. - w1) * std::log(l0) + w1 * std::log(l1))) <= 1e-12 * (1. + std::fabs(wide)), "lanczos_quadrature: two rows");
+    }
+  }
+  double out = -7.;
+  const double a_neg[2] = {1., -1. / 3.}, b_neg[2] = {0., 4.}, a_nan[2] = {1., NAN}, b_bad[2] = {0., -1.}, a_one[2] = {1., 1.};
+  require(agp::lanczos_quadrature(1., a_neg, b_neg, 1, 2, &out) == AGP_ERR_NOT_POSITIVE_DEFINITE, "lanczos_quadrature: a < 0");
+  require(agp::lanczos_quadrature(1., a_nan, b_neg, 1, 2, &out) == AGP_ERR_NOT_POSITIVE_DEFINITE, "lanczos_quadrature: NaN");
+  require(agp::lanczos_quadrature(1., a_one, b_bad, 1, 2, &out) == AGP_ERR_NOT_POSITIVE_DEFINITE, "lanczos_quadrature: b < 0");
+  require(agp::lanczos_quadrature(0., a_one, b_neg, 1, 2, &out) == AGP_ERR_NOT_POSITIVE_DEFINITE, "lanczos_quadrature: rz0");
+  require(agp::lanczos_quadrature(1., nullptr, nullptr, 1, 2, &out) == AGP_ERR_INVALID_ARGUMENT, "lanczos_quadrature: null");
+  require(out == -7., "lanczos_quadrature: a refusal writes nothing");
+}
+
 int main() {
   schedule_under_sanitizers(false);
   schedule_under_sanitizers(true);
@@ -703,6 +740,7 @@ int main() {
   dev_mem_under_sanitizers();
   logo_batch_plan_under_sanitizers();
   update_plan_under_sanitizers();
+  lanczos_quadrature_under_sanitizers();
   std::printf("host_sanitize_check ok\n");
   return 0;
 }

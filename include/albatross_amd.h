@@ -999,7 +999,7 @@ AGP_API int agp_gram_tangent_forms(agp_context *ctx, const agp_kernel *k, const 
  * agp_iterative_predict_marginal: also variance_j = k(xs_j, xs_j) - k_j^T A^-1 k_j; the cross covariances come from the
  *   Gram kernels in slices of 16 test points, each slice solved by the same conjugate gradients (its status is returned).
  * agp_iterative_nll_gradient: the gradient of the negative log-likelihood with respect to parameter slots, WITHOUT its
- *   value.  With A, alpha = information, the preconditioner, tolerance and max_iterations those of `fit`, dA_p = dA / dslot_p:
+ *   value (agp_iterative_nll below returns both from one chain of solves; this entry keeps its Rademacher probes).  With A, alpha = information, the preconditioner, tolerance and max_iterations those of `fit`, dA_p = dA / dslot_p:
  *     dNLL / dslot_p = 1/2 tr(A^-1 dA_p) - 1/2 alpha^T dA_p alpha
  *   The second term is exact (one agp_gram_tangent_forms column pair U = V = alpha).  The trace is estimated from t =
  *   n_probes probe vectors z_c:  w_c = A^-1 z_c by the fit's conjugate gradients in chunks of AGP_MATVEC_MAX_RHS,
@@ -1018,10 +1018,45 @@ AGP_API int agp_gram_tangent_forms(agp_context *ctx, const agp_kernel *k, const 
  *   untouched.  NaN and not-positive-definite as agp_iterative_solve reports them.  The handle is not modified.  Two
  *   identical calls return identical bits.  Scratch: 2 n 16 doubles of probes and solutions plus that of a solve.  With
  *   profiling on, the probe solves report under stage 12 and the forms (the alpha term included) under stage 13.
- * Out of scope, by design: joint predictions, the log-determinant and the log-likelihood VALUE (they need stochastic
- * Lanczos quadrature - the gradient above needs neither), variance-reduced trace estimators, gradients of the
- * leave-one-out metrics, LinearCombination features, the sharded and the mixed-precision path - the dense entry points
- * serve them up to the n their memory allows. */
+ * agp_iterative_nll: the VALUE of the negative log-likelihood by stochastic Lanczos quadrature, and - from the same
+ *   solves - its gradient.  With P = L L^T + delta I the fit's preconditioner (rank m) and M = P^-1/2 A P^-1/2:
+ *     log det A = log det P + tr log M,   log det P = (n - m) log delta + log det(delta I + L^T L)   (m = 0: n log delta)
+ *   the second term of log det P from the factor the fit holds.  For z ~ N(0, P), u = P^-1/2 z is standard normal and
+ *   E[u^T log(M) u] = tr log M.  The fit's conjugate gradients on A w = z are Lanczos on M started at u: with a_k, b_k the
+ *   alpha and beta of iteration k (b_0 = 0), which the solve keeps per column instead of overwriting them,
+ *     T[k, k] = 1 / a_k + b_k / a_{k-1},   T[k-1, k] = T[k, k-1] = sqrt(b_k) / a_{k-1}     (k < the column's iterations)
+ *     s_c = (z_c^T P^-1 z_c) sum_i V[0, i]^2 log lambda_i,   (lambda, V) the eigendecomposition of T   (Gauss quadrature)
+ *   taken on the host by the implicit QL iteration carrying the first row of V alone, O(k^2) per column, without
+ *   reorthogonalisation.  Then
+ *     log_det = log det P + mean_c s_c,   its standard error e = sqrt(sum_c (s_c - mean)^2 / (t (t - 1)))  (NaN when t = 1),
+ *     nll = 1/2 alpha^T A alpha + 1/2 log_det + n/2 log 2 pi,   nll_stderr = e / 2,
+ *   the data term from one agp_gram_matvec of alpha and one dot in a fixed order (the handle does not keep y).
+ *   probes == NULL: z_c = L g1_c + sqrt(delta) g2_c with g2_c column c of agp_standard_normal(seed) on n rows and g1_c
+ *     column c of agp_standard_normal(seed ^ 0x9E3779B97F4A7C15) on m rows; column c depends on (seed, c) alone and the
+ *     probes are generated chunk by chunk (never n x t).  The better the preconditioner, the nearer M is to I and the
+ *     smaller the variance: at rank 0 the estimator is the plain one on A / delta.
+ *   probes != NULL: the caller's n x t matrix at `location` (ldp >= n), used as z as is.  The estimate is unbiased when
+ *     E z z^T = P, and EXACT for Z = sqrt(t) [L | sqrt(delta) I] with t = n + m.
+ *   quadrature_tolerance: the relative residual at which a probe's recurrence stops when n_slots == 0; <= 0: the fit's.  A
+ *     looser one shortens T; the quadrature converges about twice as fast as the solve, and what it costs is the
+ *     caller's to judge.  With n_slots > 0 the solves run at the fit's tolerance whatever it says.
+ *   n_slots > 0: also the gradient.  With w_c = A^-1 z_c (the solve) and v_c = P^-1 z_c (one preconditioner application),
+ *     E[w^T dA_p v] = tr(A^-1 dA_p):  g_cp = w_c^T dA_p v_c (agp_gram_tangent_forms),
+ *     grad_nll[p] = 1/2 mean_c g_cp - 1/2 alpha^T dA_p alpha,   grad_stderr[p] = 1/2 sqrt(sum_c (g_cp - mean)^2 / (t (t - 1))).
+ *     slots, tangents, ldt as for agp_iterative_nll_gradient; n_slots == 0: the value alone, the four are not read.
+ *   nll, nll_stderr, log_det   one host double each, any may be NULL;  log_det_samples (host, t values, may be NULL): s_c
+ *   grad_nll, grad_stderr      n_slots host values each;  grad_samples (host, t x n_slots at lds >= t, may be NULL): g_cp
+ *   iterations, residual       t host values each, may be NULL
+ *   Status: as agp_iterative_nll_gradient; a probe solve that runs out of iterations: AGP_ERR_NOT_CONVERGED with
+ *   iterations / residual filled as far as the solves went and every other output untouched.  A T with an eigenvalue <= 0:
+ *   AGP_ERR_NOT_POSITIVE_DEFINITE.  The handle is not modified; agp_iterative_solve and agp_iterative_nll_gradient return
+ *   the bits they returned before.  No float atomics, a fixed order of every sum: two identical calls return identical
+ *   bits.  Scratch: 3 n 16 doubles (2 n 16 for the value alone) plus that of a solve, and 16 (1 + 2 max_iterations) doubles
+ *   of coefficients.  With profiling on: the probe solves under stage 12, the forms under 13, and the probes' generation, the
+ *   quadrature (host time) and log det P under 14.
+ * Out of scope, by design: joint predictions, variance-reduced trace estimators, gradients of the leave-one-out metrics,
+ * LinearCombination features, the sharded and the mixed-precision path - the dense entry points serve them up to the n
+ * their memory allows. */
 typedef struct {
   int64_t precond_rank;
   double precond_rel_tol;
@@ -1046,6 +1081,11 @@ AGP_API int agp_iterative_nll_gradient(agp_context *ctx, const agp_iterative_fit
                                        const double *tangents, int64_t ldt, int64_t n_probes, uint64_t seed, const double *probes,
                                        int64_t ldp, int location, double *grad_nll, double *grad_stderr, double *samples, int64_t lds,
                                        int *iterations, double *residual);
+AGP_API int agp_iterative_nll(agp_context *ctx, const agp_iterative_fit *fit, int64_t n_probes, uint64_t seed, const double *probes,
+                              int64_t ldp, int location, double quadrature_tolerance, int n_slots, const agp_gradient_slot *slots,
+                              const double *tangents, int64_t ldt, double *nll, double *nll_stderr, double *log_det,
+                              double *log_det_samples, double *grad_nll, double *grad_stderr, double *grad_samples, int64_t lds,
+                              int *iterations, double *residual);
 
 /* ---- sparse Gaussian process (FITC / PITC) --------------------------------------------------
  * SparseGaussianProcessRegression, include/albatross/src/models/sparse_gp.hpp.
@@ -1412,7 +1452,8 @@ AGP_API int agp_sharded_fit_stage(const agp_sharded_fit *fit, int stage, double 
  * 4 number of trailing-update launches.  Returns ms (or a count for 4).  Stages 6-9:
  * the gradient entries (agp_nll_gradient, agp_loo_nll_gradient).  Stage 10: the step chain of agp_pivoted_cholesky.
  * Stages 11, 12: the preconditioner build and the conjugate-gradient chain of agp_iterative_fit_create.
- * Stages 12, 13: the probe solves and the tangent forms of agp_iterative_nll_gradient. */
+ * Stages 12, 13: the probe solves and the tangent forms of agp_iterative_nll_gradient and agp_iterative_nll.
+ * Stage 14: the probes' generation, the host quadrature and log det P of agp_iterative_nll. */
 AGP_API int agp_last_stage_ms(const agp_context *ctx, int stage, double *ms);
 /* enable (1) / disable (0) per-stage event timing (default off: events add
  * host overhead to the launch chain). */

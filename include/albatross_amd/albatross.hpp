@@ -1763,6 +1763,26 @@ struct IterativeGradient {
   Vector residual;
 };
 
+// the options of IterativeFitModel::log_likelihood and ::log_likelihood_and_gradient (agp_iterative_nll)
+struct IterativeLikelihoodOptions {
+  std::int64_t num_probes = 16;      // probes z ~ N(0, P), P the fit's preconditioner: a function of (seed, column) alone ...
+  std::uint64_t seed = 0;
+  Matrix probes;                     // ... or, when it has columns, the caller's n x t probes used as they are
+  double quadrature_tolerance = 0.;  // where a probe's recurrence stops (value alone); <= 0: the fit's tolerance
+};
+
+// The log-likelihood by stochastic Lanczos quadrature: value (the sign of GaussianProcessRegression::log_likelihood) and its
+// standard error (NaN with one probe), the log-determinant it contains with its standard error and the per-probe samples of
+// tr log(P^-1/2 A P^-1/2), iterations / residual of the probe solves; `gradient` is filled by log_likelihood_and_gradient
+// from the same solves (its iterations / residual are these).
+struct IterativeLikelihood {
+  double value = 0., standard_error = 0., log_determinant = 0., log_determinant_standard_error = 0.;
+  Vector samples;
+  std::vector<int> iterations;
+  Vector residual;
+  IterativeGradient gradient;
+};
+
 // the options of GaussianProcessRegression::fit_iterative (agp_iterative_options)
 struct IterativeOptions {
   std::int64_t preconditioner_rank = 256;  // rank of the pivoted Cholesky preconditioner (0: plain conjugate gradients)
@@ -1837,6 +1857,15 @@ class IterativeFitModel {
   // (iterations and residual of the worst probe) when a probe solve runs out of iterations.
   IterativeGradient log_likelihood_gradient(const IterativeGradientOptions &options = {}) const {
     return model_.iterative_log_likelihood_gradient(fit_, options);
+  }
+  // The log-likelihood VALUE by stochastic Lanczos quadrature (agp_iterative_nll): log det P in closed form from the
+  // preconditioner, tr log of the preconditioned matrix from the conjugate-gradient coefficients of the probe solves.
+  IterativeLikelihood log_likelihood(const IterativeLikelihoodOptions &options = {}) const {
+    return model_.iterative_log_likelihood(fit_, options, false);
+  }
+  // ... and the gradient from the same chain of solves, which run at the fit's tolerance
+  IterativeLikelihood log_likelihood_and_gradient(const IterativeLikelihoodOptions &options = {}) const {
+    return model_.iterative_log_likelihood(fit_, options, true);
   }
   template <typename PredictFeature>
   MarginalDistribution predict_(const std::vector<PredictFeature> &xs, bool marginal) const {
@@ -1933,6 +1962,18 @@ class GaussianProcessRegression {
       throw NotConvergedError("albatross_amd: agp_iterative_nll_gradient: not converged", out.iterations[worst], out.residual[worst]);
     }
     detail::check(st, fit.context->ctx, "agp_iterative_nll_gradient");
+    iterative_gradient_by_name(dataset, fit, names, g, se, smp, t, &out);
+    return out;
+  }
+
+  // per name from per slot: the gradients of a name's slots add, and so do their samples before the standard error is taken;
+  // the mean-function parameters exactly
+  template <typename FeatureType>
+  void iterative_gradient_by_name(const RegressionDataset<FeatureType> &dataset, const IterativeGPFit<FeatureType> &fit,
+                                  const std::vector<std::string> &names, const std::vector<double> &g, const std::vector<double> &se,
+                                  const std::vector<double> &smp, std::int64_t t, IterativeGradient *result) const {
+    IterativeGradient &out = *result;
+    const std::size_t P = names.size(), T = static_cast<std::size_t>(t);
     for (const auto &kv : get_params()) out.gradient[kv.first] = out.standard_error[kv.first] = 0.;
     std::map<std::string, int> count;
     for (std::size_t s = 0; s < P; ++s) {  // the gradients of a name's slots add; so do their samples
@@ -1953,6 +1994,50 @@ class GaussianProcessRegression {
           t > 1 ? 0.5 * std::sqrt(dev2 / (static_cast<double>(t) * static_cast<double>(t - 1))) : std::numeric_limits<double>::quiet_NaN();
     }
     for (const auto &kv : mean_function_.get_params()) out.gradient[kv.first] += mean_tangent_dot(dataset, kv.first, kv.second, fit.information);
+  }
+
+  // IterativeFitModel::log_likelihood / ::log_likelihood_and_gradient: one call of agp_iterative_nll
+  template <typename FeatureType>
+  IterativeLikelihood iterative_log_likelihood(const IterativeGPFit<FeatureType> &fit, const IterativeLikelihoodOptions &options,
+                                               bool with_gradient) const {
+    RegressionDataset<FeatureType> dataset;
+    dataset.features = fit.train_features;
+    const std::int64_t n = static_cast<std::int64_t>(fit.train_features.size());
+    std::vector<std::string> names;
+    std::vector<agp_gradient_slot> slots;
+    std::vector<double> tangents;
+    if (with_gradient) slot_table(dataset, &names, &slots, &tangents);
+    const bool own = options.probes.cols() > 0;
+    if (own && options.probes.rows() != n) throw std::invalid_argument("log_likelihood: one probe row per training feature");
+    const std::int64_t t = own ? options.probes.cols() : options.num_probes;
+    if (t < 1) throw std::invalid_argument("log_likelihood: at least one probe");
+    const std::size_t P = slots.size(), T = static_cast<std::size_t>(t);
+    std::vector<double> g(std::max<std::size_t>(P, 1), 0.), se(std::max<std::size_t>(P, 1), 0.), smp(T * std::max<std::size_t>(P, 1), 0.);
+    IterativeLikelihood out;
+    out.samples.assign(T, 0.);
+    out.iterations.assign(T, 0);
+    out.residual.assign(T, 0.);
+    double nll = 0., nll_se = 0.;
+    const int st = agp_iterative_nll(fit.context->ctx, fit.handle.get(), t, options.seed, own ? options.probes.data.data() : nullptr, n,
+                                     AGP_HOST, options.quadrature_tolerance, static_cast<int>(P), P ? slots.data() : nullptr,
+                                     tangents.empty() ? nullptr : tangents.data(), n, &nll, &nll_se, &out.log_determinant,
+                                     out.samples.data(), P ? g.data() : nullptr, P ? se.data() : nullptr, P ? smp.data() : nullptr, t,
+                                     out.iterations.data(), out.residual.data());
+    if (st == AGP_ERR_NOT_CONVERGED) {
+      std::size_t worst = 0;
+      for (std::size_t c = 1; c < T; ++c)
+        if (out.residual[c] > out.residual[worst]) worst = c;
+      throw NotConvergedError("albatross_amd: agp_iterative_nll: not converged", out.iterations[worst], out.residual[worst]);
+    }
+    detail::check(st, fit.context->ctx, "agp_iterative_nll");
+    out.value = -nll;
+    out.standard_error = nll_se;
+    out.log_determinant_standard_error = 2. * nll_se;
+    if (with_gradient) {
+      out.gradient.iterations = out.iterations;
+      out.gradient.residual = out.residual;
+      iterative_gradient_by_name(dataset, fit, names, g, se, smp, t, &out.gradient);
+    }
     return out;
   }
 
